@@ -13,12 +13,19 @@ peer-copy or RCCL gather inside the C++ library).
 A "step" is one pass of the hot path (keyframe build + 7 Gauss-Newton iterations, 75 x 24 voxels) over
 one batch of synthetic 64-channel scan pairs per GPU: BASELINE.json configs[2] (256 independent pairs,
 throughput mode) at N=1, and its sharded form configs[3] (256 pairs per GPU, pair k -> rank k mod N,
-one RCCL all-gather of 48 floats per pair) at N>1 -- weak scaling.  configs[1] (ONE pair, latency) is
-measured in the same run and reported under "latency"; configs[0] is the CPU-only plumbing case and
-configs[4] the high-resolution sweep: parity-test cases; configs[4] is also timed in the same run ("highres").
+one RCCL all-gather of 48 floats per pair) at N>1 -- weak scaling.  Exactly K steps are timed (after W
+untimed ones); `ms_per_step` is one of them.  With `--full`, configs[1] (ONE pair, latency) is also
+measured and reported under "latency"; configs[0] is the CPU-only plumbing case and configs[4] the
+high-resolution sweep: parity-test cases; configs[4] is also timed under `--full` ("highres").
 
-Inputs are generated on the device (icet_amd.lidar_sim) and are resident in HBM before the timed
-region.  rank 0 prints ONE JSON line with the driver's contract fields plus
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs DIR` (X.npy, pred_stds.npy,
+cov.npy of every pair of the last timed step; the node workloads: the last frame's result) and prints
+its line.  Everything else -- the sub-records below, the gather alone, the other storage order, the
+real-data batch, the PCIe-inclusive and constructor paths, the nodes' phase timing and burst -- runs
+only with `--full`; without it those fields are null.
+
+Inputs are generated on the device (icet_amd.lidar_sim, seeded per pair) and are resident in HBM before
+the timed region.  rank 0 prints ONE JSON line with the driver's contract fields plus, with `--full`,
   "roofline":     k_gn_accumulate (the dominant kernel): algorithmic bytes per launch = 12 B x scan-2
                   points of the batch (x|y|z read once, transform fused, nothing N-sized written),
                   divided by the launch duration measured with HIP events on the solve stream.
@@ -59,7 +66,10 @@ def parse(argv=None):
     ap.add_argument("--distinct", type=int, default=0, help="generate only this many distinct pairs and cycle them (0 = all distinct)")
     ap.add_argument("--multi", action="store_true", help="one process, N GPUs through the native icet_multi_* entry (no torch.distributed)")
     ap.add_argument("--multi-gather", choices=["peer", "rccl"], default="peer", help="--multi: peer copies (default) or the library's RCCL all-gather")
-    ap.add_argument("--min-timed-s", type=float, default=0.5, help="the K timed steps are repeated until the timed region is at least this long")
+    ap.add_argument("--min-timed-s", type=float, default=0.0, help="repeat the K timed steps until the timed region is at least this long (default 0: exactly K timed steps)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: per-kernel timing and roofline, HBM traffic, CPU baseline, latency, "
+                                                        "highres, the other storage order, real-data batch, PCIe-inclusive and constructor paths, the nodes' phase timing and burst")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--no-h2d", action="store_true", help="skip the PCIe-inclusive sub-record")
     ap.add_argument("--traffic", choices=["live", "file", "none"], default="live",
                     help="roofline.traffic: measured by two child runs under rocprofv3 --pmc (each capped at 60 s; falls back to the file), read from profiles/traffic_latest.json, or left null")
@@ -97,6 +107,12 @@ def plan_launch(args, env):
     return "run", "rank of a %s-rank launch" % world
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (the outputs of the last timed step, as a caller of that path receives them)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
+
 
 def _is_elf(path):
     try:
@@ -125,7 +141,7 @@ def measure_traffic_live(timeout_s=60):
         d = tempfile.mkdtemp(prefix="icet_pmc_", dir="/tmp")
         # counters for k_gn_accumulate only: with every dispatch of the pair generator profiled a pass took 70 s (round 5: 142 s of the default run's 155 s)
         cmd = [exe, "--kernel-trace", "--pmc", counter, "--kernel-include-regex", "k_gn_accumulate", "--output-format", "csv", "-d", d, "--", py, os.path.abspath(__file__),
-               "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--no-h2d", "--min-timed-s", "0"]
+               "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-latency", "--no-h2d", "--min-timed-s", "0"]
         try:
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout_s)
         except Exception as e:
@@ -187,8 +203,10 @@ def run_nodes(args):
     dt = time.perf_counter() - t0
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=(dev if dist.get_backend() == "nccl" else "cpu")); dist.all_reduce(tt, op=dist.ReduceOp.MAX); dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k2: r[k2] for k2 in ("X", "pred_stds", "pose", "quat", "solved", "diverged", "n_kept", "map_rows")})
     for key in tim: tim[key] /= max(args.steps, 1)
-    if world == 1:
+    if world == 1 and args.full:
         # a pipelined frame is one graph launch (filter + loop together, no timing events): the phases are timed on a second node that keeps them apart (ICET_NODE_TIME_PHASES)
         node_t = api.Node(ctx, **dict(kw, flags=kw.get("flags", 0) | api.NODE_TIME_PHASES))
         for k in range(args.warmup + 1):
@@ -203,7 +221,7 @@ def run_nodes(args):
     # ---- the same frames through ONE call (icet_node_push_many_device): the library pushes them one after the other -- what is left out is this script's per-frame
     # Python / ctypes work (round 6: the device-chained burst of rounds 4-5 was slower than one-launch frames and was removed) ----
     burst = None
-    if args.workload == "odometry" and world == 1:
+    if args.workload == "odometry" and world == 1 and args.full:
         node_b = api.Node(ctx, **kw)
         for k in range(args.warmup + 1):
             node_b.push_device(bufs[k].data_ptr(), frames[k].shape[1], bufs[k].shape[1])
@@ -226,7 +244,7 @@ def run_nodes(args):
         note = "x|y|z read by the count and the scatter pass + kept rows written (~36 B/row); filter_ms / solve_ms from a second node with ICET_NODE_TIME_PHASES (the timed frames run filter + loop as one graph launch)"
     achieved = bytes_per_launch / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import pyoracle as po
         o = po.Node(**kw)
         host = [f.T.cpu().numpy() for f in frames]
@@ -248,7 +266,7 @@ def run_nodes(args):
                                    % (args.workload, n_mean // 1000), "points_per_frame_mean": n_mean, **{k2: v for k2, v in kw.items()}},
             "roofline": {"kernel": kern, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": None, "algorithmic_bytes_per_launch": bytes_per_launch, "avg_launch_ms": round(ms, 5), "note": note,
-                         "filter_ms": round(tim["filter_ms"], 4), "solve_ms": round(tim["solve_ms"], 4), "map_ms": round(tim["map_ms"], 4)},
+                         "filter_ms": round(tim["filter_ms"], 4), "solve_ms": round(tim["solve_ms"], 4), "map_ms": round(tim["map_ms"], 4)} if args.full else None,
             "burst": burst,
             "cpu_baseline": cpu, "last_X": [round(float(v), 5) for v in r["X"]]}), flush=True)
     node.close(); ctx.close()
@@ -455,9 +473,9 @@ def main(argv=None):
     for _ in range(args.warmup):
         step(p_plain)
     fence()
-    # The K timed steps, bracketed by barrier + synchronize.  One pass of K steps over 256 pairs is only ~50 ms, so the bracket is
-    # REPEATED (each repetition: exactly K steps between two fences) until the timed region is at least --min-timed-s; `steps`
-    # stays K, `ms_per_step` is the mean over every timed step, `value` the pairs of all of them / the total time.
+    # The K timed steps, bracketed by barrier + synchronize.  With --min-timed-s > 0 the bracket is REPEATED (each repetition:
+    # exactly K steps between two fences) until the timed region is at least that long; `ms_per_step` is the mean over every
+    # timed step, `value` the pairs of all of them / the total time.  By default exactly K steps are timed.
     reps_t, dt, rep_ms = 0, 0.0, []
     while True:
         fence()
@@ -476,10 +494,17 @@ def main(argv=None):
     steps_total = args.steps * reps_t
     ms_per_step = dt / max(steps_total, 1) * 1e3
     pairs_per_s = n_global * steps_total / dt
+    if args.dump_outputs and rank == 0:
+        r_host = res.float().cpu().numpy()                         # n_global x 48 in global pair order: X | pred_stds | cov
+        pick = {}
+        if r_host.nbytes > 60 * 2**20:                             # beyond ~320 k pairs: a fixed, seeded sample of pairs (their ids in pair_index.npy)
+            idx = np.sort(np.random.RandomState(0).choice(len(r_host), (60 * 2**20) // (48 * 4), replace=False))
+            r_host, pick = r_host[idx], {"pair_index": idx}
+        dump_outputs(args.dump_outputs, {"X": r_host[:, :6], "pred_stds": r_host[:, 6:12], "cov": r_host[:, 12:48].reshape(-1, 6, 6), **pick})
 
     # ---- the gather alone (N > 1): what the collective costs on top of the solve ----
     gather_ms = None
-    if world > 1 and backend == "nccl":
+    if world > 1 and backend == "nccl" and args.full:
         fence()
         tg = time.perf_counter()
         with torch.cuda.stream(stream):
@@ -492,7 +517,7 @@ def main(argv=None):
     # ---- per-kernel timing with HIP events on the solve stream (extra steps, not part of `value`) ----
     acc_ms, kf_ms, gn_ms, launches = 0.0, 0.0, 0.0, 0
     reps = max(3, min(args.steps, 10))
-    for _ in range(reps):
+    for _ in range(reps if args.full else 0):
         step(p_timed)
         t = ctx.last_timing()
         acc_ms += t["accumulate_ms"]; kf_ms += t["keyframe_ms"]; gn_ms += t["gn_loop_ms"]; launches += t["accumulate_launches"]
@@ -507,12 +532,12 @@ def main(argv=None):
     tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
     default_workload = args.workload == "batch" and n_local == 256 and args.distinct == 0 and not args.set and not args.flags and args.order == "ring"
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ)      # no profiler inside a profiled run
-    if args.traffic == "live" and default_workload and rank == 0 and n_gpus == 1 and not args.no_latency and not os.environ.get("ICET_BENCH_CHILD") and not under_profiler:
+    if args.full and args.traffic == "live" and default_workload and rank == 0 and n_gpus == 1 and not args.no_latency and not os.environ.get("ICET_BENCH_CHILD") and not under_profiler:
         # measured live (review r4, weak 9: the number used to come from a file a builder-side profile run had left behind)
         mark("traffic_live")
         traffic, traffic_note = measure_traffic_live()
         mark("roofline_events")
-    if traffic is None and args.traffic != "none" and os.path.exists(tpath) and args.workload == "batch" and n_local == 256 and args.distinct == 0:
+    if args.full and traffic is None and args.traffic != "none" and os.path.exists(tpath) and args.workload == "batch" and n_local == 256 and args.distinct == 0:
         # fallback: the PMC numbers profiles/collect.sh collected on exactly this workload (256 distinct pairs per GPU)
         try:
             traffic = json.load(open(tpath)).get("k_gn_accumulate_bytes_per_launch")
@@ -526,7 +551,7 @@ def main(argv=None):
     # hold points of DIFFERENT voxels (rings 7.5 degrees of polar angle apart), i.e. shorter runs per lane and more LDS adds.  The reference's result
     # depends on the storage order (its swap loop is a function of the row indices), so this is another input, not another route to the same bits.
     az_major = None
-    if args.workload == "batch" and not args.no_latency and world == 1 and not multi and args.distinct == 0:
+    if args.full and args.workload == "batch" and not args.no_latency and world == 1 and not multi and args.distinct == 0:
         def reorder(sc):
             az = torch.atan2(sc[1], sc[0]); az = torch.where(az < 0, az + 2 * math.pi, az)
             step_id = torch.floor(az.double() * (steps_az / (2 * math.pi))).long()
@@ -566,7 +591,7 @@ def main(argv=None):
     # icet_solve_batch_device call per step.  Real scans differ from the synthetic ones where it hurts: thousands of exact-zero rows that share one key and
     # one voxel, a near field that puts tens of thousands of rows into a few bins, half the rows in a third of the voxels.
     sample_batch = None
-    if args.workload == "batch" and not args.no_latency and world == 1 and not multi and args.distinct == 0:
+    if args.full and args.workload == "batch" and not args.no_latency and world == 1 and not multi and args.distinct == 0:
         rp = [real_pair(k, dev) for k in range(len(ids))]
         r1 = [padded(a) for a, _ in rp]; r2 = [padded(b) for _, b in rp]
         m1 = [int(a.shape[1]) for a, _ in rp]; m2 = [int(b.shape[1]) for _, b in rp]
@@ -619,11 +644,11 @@ def main(argv=None):
         real_X = real_res[:4, :6].copy()
         del r1, r2, rp
 
-    one_ctx = ctx if not multi else icet_amd.Context(dev_ids[0], stream=stream.cuda_stream)
+    one_ctx = ctx if not (multi and args.full) else icet_amd.Context(dev_ids[0], stream=stream.cuda_stream)
     mark("latency")
     # ---- single-pair latency (configs[1]) on rank 0's first pair -----------------------------------
     lat = None
-    if args.workload == "batch" and not args.no_latency:
+    if args.full and args.workload == "batch" and not args.no_latency:
         one1, one2 = d1[:1], d2[:1]
         o1 = torch.zeros((1, 48), dtype=torch.float32, device=dev)
         with torch.cuda.stream(stream):
@@ -649,7 +674,7 @@ def main(argv=None):
     mark("highres")
     # ---- configs[4] (high-resolution sweep) as a sub-record of the default line: one 128-channel pair, 150 x 48 voxels, 10 iterations ----
     hires = None
-    if args.workload == "batch" and not args.no_latency and rank == 0:
+    if args.full and args.workload == "batch" and not args.no_latency and rank == 0:
         h1, h2, _ = lidar_sim.make_pair(9000, 9001, lidar_sim.DEFAULT_MOTION, 128, 4096, device=dev, order=args.order)
         hb1, hb2 = padded(h1), padded(h2)
         hd1 = [(hb1.data_ptr(), int(h1.shape[1]), hb1.shape[1])]; hd2 = [(hb2.data_ptr(), int(h2.shape[1]), hb2.shape[1])]
@@ -682,7 +707,7 @@ def main(argv=None):
     # ---- PCIe-inclusive ("reported both with and without H2D"): 64 pairs through icet_solve_batch, host pointers in,
     # host results out -- from pageable numpy arrays and from pinned torch tensors.  Never `value`. ----
     h2d = None
-    if args.workload == "batch" and not args.no_h2d and rank == 0 and not args.no_latency:
+    if args.full and args.workload == "batch" and not args.no_h2d and rank == 0 and not args.no_latency:
         m = min(64, len(ids))
         # pageable host arrays in the layout the reference's callers hold (Eigen::MatrixXf: column-major N x 3), so nothing is transposed on the way in
         hs1 = [scans1[j].cpu().contiguous() for j in range(m)]; hs2 = [scans2[j].cpu().contiguous() for j in range(m)]          # (3, N) C-order == column-major N x 3
@@ -721,7 +746,7 @@ def main(argv=None):
     # ---- the constructor path (what src/odometry.cpp:73-79 pays per frame): ONE 64-ch pair from PAGEABLE host memory through icet_solve with the
     # side tables include/icet.h asks for, and the same through the compiled adapter (tests/cpp/adapter_demo.cpp against the Eigen-API mock) ----
     ctor = None
-    if args.workload == "batch" and not args.no_h2d and rank == 0 and not args.no_latency:
+    if args.full and args.workload == "batch" and not args.no_h2d and rank == 0 and not args.no_latency:
         import ctypes as C
         L = api.load_library()
         cctx = icet_amd.Context(dev_ids[0])
@@ -786,7 +811,7 @@ def main(argv=None):
     mark("cpu_baseline")
     # ---- CPU baseline: the oracle ("port") on this box's host cores, bounded sample, rank 0 at N=1 -----
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle as po
         cores = min(os.cpu_count() or 1, 16)
         m = min(len(ids), args.cpu_sample_pairs if args.workload == "batch" else 1)
@@ -847,7 +872,7 @@ def main(argv=None):
     # python/point_clouds/sample_pc_1/2.npy, committed as float32 fixtures) through the GPU path and through the oracle on the host (literal mode:
     # serial loop = the live path of src/icet.cpp:391-404, and the 4-worker ThreadPool structure of :346-370), as src/icet_cpp_demo.cpp:25-45 runs them ----
     sample = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and args.workload == "batch":
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and args.workload == "batch":
         from oracle import pyoracle as po
         sample = {"workload": "configs[0]: the reference's sample scan pairs (real lidar data), 75x24 voxels, 7 iters, X0 = 0; GPU: icet_solve from pageable host memory "
                               "(PCIe-inclusive) and device-resident; CPU: oracle in its literal mode, serial and ThreadPool-4", "data": "real", "pairs": {}}
@@ -911,7 +936,7 @@ def main(argv=None):
                          "algorithmic_bytes_per_launch": bytes_per_launch, "avg_launch_ms": round(acc_launch_ms, 5), "launches_timed": launches,
                          "whole_path_GBs": round(bytes_path / (ms_per_step * 1e-3) / 1e9, 1),
                          "whole_path_frac": round(bytes_path / (ms_per_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * n_gpus), 4),      # B_pair x pairs / t / peak (frac above is the dominant kernel alone)
-                         "keyframe_ms_per_step": round(kf_ms / reps, 4), "gn_loop_ms_per_step": round(gn_ms / reps, 4)},
+                         "keyframe_ms_per_step": round(kf_ms / reps, 4), "gn_loop_ms_per_step": round(gn_ms / reps, 4)} if args.full else None,
             "cpu_baseline": cpu,
             "latency": lat,
             "highres": hires,

@@ -2,7 +2,7 @@
 # Device timeline of the LAST frames of `bench.py --workload odometry` (the burst): per launch start offset, duration, stream.  Run through gpurun.
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-rm -rf /tmp/p_bt; rocprofv3 --kernel-trace --output-format csv -d /tmp/p_bt -- python3 $R/bench.py --workload odometry --steps 40 --warmup 3 --no-cpu-baseline > /tmp/bt.log 2>&1
+rm -rf /tmp/p_bt; rocprofv3 --kernel-trace --output-format csv -d /tmp/p_bt -- python3 $R/bench.py --full --workload odometry --steps 40 --warmup 3 --no-cpu-baseline > /tmp/bt.log 2>&1
 python3 - <<'PY'
 import csv, glob, re
 f = glob.glob("/tmp/p_bt/*/*kernel_trace.csv")[0]

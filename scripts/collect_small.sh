@@ -8,11 +8,11 @@ OUT=$R/gpurun_out/profiles_small
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/p_one /tmp/p_hi
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_one -- python3 $R/bench.py --pairs-per-gpu 1 --steps 50 --warmup 5 --no-cpu-baseline --no-latency --no-h2d --min-timed-s 0 > $OUT/one.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_one -- python3 $R/bench.py --full --pairs-per-gpu 1 --steps 50 --warmup 5 --no-cpu-baseline --no-latency --no-h2d --min-timed-s 0 > $OUT/one.log 2>&1
 grep -E "^\"Name\"|icet::" /tmp/p_one/*/*kernel_stats.csv > $OUT/one_stats.csv
 python3 $R/profiles/summarize.py $OUT/one_stats.csv 53 > $OUT/${TAG}_single_pair_kernels.txt
 grep "^{\"metric\"" $OUT/one.log | tail -1 >> $OUT/${TAG}_single_pair_kernels.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_hi -- python3 $R/bench.py --workload highres --steps 50 --warmup 5 --no-cpu-baseline --no-latency --no-h2d --min-timed-s 0 > $OUT/hi.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_hi -- python3 $R/bench.py --full --workload highres --steps 50 --warmup 5 --no-cpu-baseline --no-latency --no-h2d --min-timed-s 0 > $OUT/hi.log 2>&1
 grep -E "^\"Name\"|icet::" /tmp/p_hi/*/*kernel_stats.csv > $OUT/hi_stats.csv
 python3 $R/profiles/summarize.py $OUT/hi_stats.csv 53 > $OUT/${TAG}_highres_kernels.txt
 grep "^{\"metric\"" $OUT/hi.log | tail -1 >> $OUT/${TAG}_highres_kernels.txt

@@ -2,7 +2,7 @@
 # Durations of the LAST step's launches in launch order (which iteration is the slow one?), for the bench arguments given.  Run through gpurun.
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-rm -rf /tmp/p_kq; rocprofv3 --kernel-trace --output-format csv -d /tmp/p_kq -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-latency "$@" > /tmp/kq.log 2>&1
+rm -rf /tmp/p_kq; rocprofv3 --kernel-trace --output-format csv -d /tmp/p_kq -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-latency "$@" > /tmp/kq.log 2>&1
 python3 - <<'PY'
 import csv, glob, re
 f = glob.glob("/tmp/p_kq/*/*kernel_trace.csv")[0]

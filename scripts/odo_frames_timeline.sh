@@ -1,7 +1,7 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
-rm -rf /tmp/p_ot; rocprofv3 --kernel-trace --output-format csv -d /tmp/p_ot -- python3 $R/bench.py --workload odometry --steps 60 --warmup 3 --no-cpu-baseline > /tmp/ot.log 2>&1
+rm -rf /tmp/p_ot; rocprofv3 --kernel-trace --output-format csv -d /tmp/p_ot -- python3 $R/bench.py --full --workload odometry --steps 60 --warmup 3 --no-cpu-baseline > /tmp/ot.log 2>&1
 # (the node with ICET_NODE_TIME_PHASES and the push_many pass come after the timed frames: take frames from the first part of the trace)
 python3 - <<'PY'
 import csv, glob, re

@@ -11,6 +11,7 @@ Fixtures are DATA, not code:
                             per-iteration per-voxel counts.  The reference ships no golden vectors
                             (SURVEY.md section 4), so these pin the oracle against ITSELF across
                             platforms/compilers and pin the GPU path against the oracle.
+  ref_formats.npz           the reference's own file formats as tests/test_io.py needs them (see ref_formats())
 """
 import os
 import sys
@@ -67,9 +68,43 @@ def degenerate():
     np.savez_compressed(os.path.join(HERE, "golden_degenerate.npz"), **out)
 
 
+def ref_formats():
+    """ref_formats.npz: what tests/test_io.py compares with, so that it needs no reference tree.  The .npy header bytes and SHA-256 of the
+    reference's src/sample_data/frame_804.npy / frame_805.npy (header + the committed scans as float64 rebuild each file byte for byte), and the
+    rows the reference's own csv.hpp (oracle/_ref/csv_ref) yields for every CSV / xyz file test_io.py writes."""
+    import hashlib
+    import shutil
+    import tempfile
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import test_io
+    from oracle import scan_io
+    out = {}
+    d = np.load(os.path.join(HERE, "scans_frame_804_805.npz"))
+    for name, key in (("frame_804", "scan1"), ("frame_805", "scan2")):
+        raw = open(os.path.join(REF, "src", "sample_data", name + ".npy"), "rb").read()
+        body = d[key].astype("<f8").tobytes()
+        assert raw.endswith(body)
+        out["npy_header_" + name] = np.frombuffer(raw[:len(raw) - len(body)], np.uint8)
+        out["npy_sha256_" + name] = np.array(hashlib.sha256(raw).hexdigest())
+    td = tempfile.mkdtemp()
+    for crlf, blank, trail in test_io.OUSTER_CASES:
+        p = os.path.join(td, "pcap_out_000261.csv")
+        test_io._ouster_file(p, crlf=crlf, blank_lines=blank, trailing_newline=trail)
+        out[test_io.ouster_rows_key(crlf, blank, trail)] = scan_io.reference_parser_rows(p, "ouster")
+    p = os.path.join(td, "desk_test_20.txt")
+    test_io._tsv_file(p)
+    out["csv_rows_xyz"] = scan_io.reference_parser_rows(p, "xyz")
+    assert all(v is not None for v in out.values()), "oracle/_ref/csv_ref is not built (make -C oracle ref)"
+    shutil.rmtree(td)
+    np.savez_compressed(os.path.join(HERE, "ref_formats.npz"), **out)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "degenerate":
         degenerate()
+    elif len(sys.argv) > 1 and sys.argv[1] == "ref_formats":
+        ref_formats()
     else:
         main()
         degenerate()
+        ref_formats()

@@ -122,6 +122,20 @@ def test_bench_plans_its_processes_before_touching_the_gpu():
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_plain_run_times_exactly_k_steps_and_dumps_float32(tmp_path):
+    """A plain run times exactly --steps steps and nothing beside the headline (the rest is behind --full); --dump-outputs writes float32 .npy."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.min_timed_s == 0 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", str(tmp_path / "d")])
+    assert a.full and a.dump_outputs == str(tmp_path / "d")
+    bench.dump_outputs(a.dump_outputs, {"X": np.arange(12, dtype=np.float64).reshape(2, 6), "solved": True})
+    X, solved = np.load(str(tmp_path / "d" / "X.npy")), np.load(str(tmp_path / "d" / "solved.npy"))
+    assert X.dtype == np.float32 and X.shape == (2, 6) and np.array_equal(X, np.arange(12).reshape(2, 6)) and solved.dtype == np.float32 and solved == 1
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode of the self-launched ranks")
 def test_bench_self_launch_fails_loudly_without_gpus():
     """`python bench.py --gpus 2` really starts two ranks through torch.distributed.run; on this box they find no GPU, and the parent

@@ -1,11 +1,32 @@
 """Scan file formats: include/icet_io.h against oracle/scan_io.py, and both against the
-reference's own third-party CSV parser (oracle/_ref/csv_ref, built from /root/reference/include/csv.hpp when that tree is
-present).  Bit-exact: the loaders only parse and convert."""
+reference's own third-party CSV parser: the rows it yields for every file written here are stored in tests/golden/ref_formats.npz
+(and compared live as well where oracle/_ref/csv_ref was built from the reference's include/csv.hpp).  Bit-exact: the loaders
+only parse and convert."""
 import os
 import numpy as np
 import pytest
 
 from conftest import GOLDEN
+
+OUSTER_CASES = [(False, False, True), (True, False, True), (False, True, False)]
+
+
+def ouster_rows_key(crlf, blank, trail):
+    return "csv_rows_ouster_%d%d%d" % (crlf, blank, trail)
+
+
+def _ref_formats():
+    return np.load(os.path.join(GOLDEN, "ref_formats.npz"))
+
+
+def _reference_rows(path, mode, key):
+    """The reference parser's rows for `path`: the stored ones, checked against a live run of oracle/_ref/csv_ref where it is built."""
+    from oracle import scan_io
+    rows = _ref_formats()[key]
+    live = scan_io.reference_parser_rows(path, mode)
+    if live is not None:
+        assert np.array_equal(live, rows)
+    return rows
 
 
 def _ouster_file(path, n=300, seed=3, crlf=False, blank_lines=False, trailing_newline=True):
@@ -31,7 +52,7 @@ def _tsv_file(path, n=200, seed=4):
     return pts
 
 
-@pytest.mark.parametrize("crlf,blank,trail", [(False, False, True), (True, False, True), (False, True, False)])
+@pytest.mark.parametrize("crlf,blank,trail", OUSTER_CASES)
 def test_ouster_csv_matches_oracle_and_reference_parser(tmp_path, crlf, blank, trail):
     from icet_amd import api
     from oracle import scan_io
@@ -42,9 +63,8 @@ def test_ouster_csv_matches_oracle_and_reference_parser(tmp_path, crlf, blank, t
     assert got.dtype == np.float32 and np.array_equal(got, ref)
     # the quirk: two header lines AND the first two data rows are gone (utils.cpp:21-29)
     assert len(got) == len(vals) - 2 and np.array_equal(got[0], vals[2, 8:11].astype(np.float32) / np.float32(1000))
-    rows = scan_io.reference_parser_rows(p, "ouster")
-    if rows is not None:                                     # the reference's own csv.hpp
-        assert np.array_equal(rows.astype(np.int64).astype(np.float32) / np.float32(1000), got)
+    rows = _reference_rows(p, "ouster", ouster_rows_key(crlf, blank, trail))      # the reference's own csv.hpp
+    assert np.array_equal(rows.astype(np.int64).astype(np.float32) / np.float32(1000), got)
 
 
 def test_xyz_tsv_matches_oracle_and_reference_parser(tmp_path):
@@ -55,9 +75,8 @@ def test_xyz_tsv_matches_oracle_and_reference_parser(tmp_path):
     got = api.load_scan(p)
     assert np.array_equal(got, scan_io.load_xyz_tsv(p))
     assert len(got) == len(pts) - 1                          # the quirk: the first point is taken for a header (utils.cpp:65)
-    rows = scan_io.reference_parser_rows(p, "xyz")
-    if rows is not None:
-        assert np.array_equal(rows.astype(np.float32), got)
+    rows = _reference_rows(p, "xyz", "csv_rows_xyz")
+    assert np.array_equal(rows.astype(np.float32), got)
 
 
 @pytest.mark.parametrize("dtype,order", [("<f8", "C"), ("<f8", "F"), ("<f4", "C"), ("<f4", "F")])
@@ -113,13 +132,19 @@ def test_loader_errors(tmp_path):
     assert api.load_scan(str(tmp_path / "nothing.bin") if (tmp_path / "nothing.bin").write_bytes(b"") == 0 else "").shape == (0, 3)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/sample_data/frame_804.npy"), reason="reference tree not present (GPU box)")
-def test_reference_sample_data_loads_to_the_committed_fixture():
-    """The reference's own sample files (float64, C order) through the C loader == the float32 scans the golden fixtures hold."""
+def test_reference_sample_data_loads_to_the_committed_fixture(tmp_path):
+    """The reference's own sample files (src/sample_data/frame_804.npy / frame_805.npy: float64, C order) through the C loader == the float32
+    scans the golden fixtures hold.  Each file is rebuilt byte for byte from its stored .npy header and the fixture's values in float64; its
+    SHA-256 is the original file's."""
+    import hashlib
     from icet_amd import api
     d = np.load(os.path.join(GOLDEN, "scans_frame_804_805.npz"))
-    for name, key in (("frame_804.npy", "scan1"), ("frame_805.npy", "scan2")):
-        got = api.load_scan("/root/reference/src/sample_data/" + name)
+    ref = _ref_formats()
+    for name, key in (("frame_804", "scan1"), ("frame_805", "scan2")):
+        raw = ref["npy_header_" + name].tobytes() + d[key].astype("<f8").tobytes()
+        assert hashlib.sha256(raw).hexdigest() == str(ref["npy_sha256_" + name])
+        p = tmp_path / (name + ".npy"); p.write_bytes(raw)
+        got = api.load_scan(str(p))
         assert np.array_equal(got.view(np.uint32), d[key].view(np.uint32))
 
 
