@@ -26,7 +26,7 @@ FLAG_HALF_GAP_BOUNDS = 8  # non-parity extension (half-gap cluster buffers of th
 
 # every symbol include/icet_hip.h, include/icet_nodes.h and include/icet_io.h declare
 EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_version", "icet_solve", "icet_solve_begin", "icet_solve_keyframe_tables", "icet_solve_end", "icet_solve_batch",
-                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
+                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
                     "icet_node_prev_scan", "icet_node_aligned", "icet_node_snail_trail", "icet_node_last_timing", "icet_stream", "icet_device",
@@ -108,6 +108,9 @@ def load_library():
     L.icet_register_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
     L.icet_keyframe_device_n.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p]
     L.icet_register_device_n.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_register_indexed_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
+    L.icet_solve_indexed.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
     L.icet_multi_destroy.argtypes = [C.c_void_p]
     L.icet_multi_last_error.argtypes = [C.c_void_p]; L.icet_multi_last_error.restype = C.c_char_p
@@ -222,6 +225,17 @@ class Context:
         self._check(load_library().icet_register_device_n(self._h, C.byref(params), len(scan2_descs), B, C.c_void_p(d_rows_ptr) if d_rows_ptr else None,
                                                           C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr)))
 
+    def register_indexed_device(self, kf_index, scan2_descs, params, d_out_ptr, d_x0_ptr=None):
+        """Gauss-Newton loop of every scan 2 (device_ptr, n, ld) against the parked keyframe kf_index[r] (icet_register_indexed_device): repeats and
+        any order allowed; d_out_ptr: device pointer to len(scan2_descs) x 48 floats.  The keyframe stays parked."""
+        k = len(scan2_descs)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
+        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        self._check(load_library().icet_register_indexed_device(self._h, C.byref(params), k, idx.ctypes.data, B,
+                                                                C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr)))
+
     def set_option(self, name, value):
         """Launch-shape / diagnostic knob of this context (icet_set_option, include/icet_hip.h).  Launch-shape knobs leave the result
         bits alone; force_exact / guard_scale / lut_polar_quantile keep every decision but regroup float partial sums."""
@@ -308,6 +322,25 @@ class Context:
         X = np.zeros((k, 6), np.float32); ps = np.zeros((k, 6), np.float32); cov = np.zeros((k, 36), np.float32)
         st = load_library().icet_solve_batch(self._h, C.byref(p), k, a1, n1.ctypes.data, a2, n2.ctypes.data,
                                              x0.ctypes.data if x0 is not None else None, X.ctypes.data, ps.ctypes.data, cov.ctypes.data)
+        self._check(st)
+        return dict(X=X, pred_stds=ps, cov=cov.reshape(k, 6, 6))
+
+    # -- many scans against shared keyframes, host arrays ------------------------------------------------
+    def solve_indexed(self, scans1, scans2, kf_index, runlen, X0=None, num_bins_phi=24, num_bins_theta=75, n=25, thresh=0.1, buff=0.1, flags=0):
+        """icet_solve_indexed: registration r solves (scans1[kf_index[r]], scans2[r]) from X0[r], each keyframe built once.  The keyframes stay
+        parked in this context.  Returns X, pred_stds and cov per registration, like solve_batch."""
+        k = len(scans2)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scans2 differ in length")
+        p = Params(int(runlen), int(num_bins_phi), int(num_bins_theta), int(n), float(thresh), float(buff), int(flags))
+        s1 = [_colmajor(s) for s in scans1]; s2 = [_colmajor(s) for s in scans2]
+        a1 = (C.c_void_p * max(len(s1), 1))(*[s.ctypes.data for s in s1]); a2 = (C.c_void_p * max(k, 1))(*[s.ctypes.data for s in s2])
+        n1 = np.array([s.shape[1] for s in s1], np.int64); n2 = np.array([s.shape[1] for s in s2], np.int64)
+        x0 = None if X0 is None else np.ascontiguousarray(np.asarray(X0, np.float32).reshape(k, 6))
+        X = np.zeros((k, 6), np.float32); ps = np.zeros((k, 6), np.float32); cov = np.zeros((k, 36), np.float32)
+        st = load_library().icet_solve_indexed(self._h, C.byref(p), len(s1), a1, n1.ctypes.data, k, idx.ctypes.data, a2, n2.ctypes.data,
+                                               x0.ctypes.data if x0 is not None else None, X.ctypes.data, ps.ctypes.data, cov.ctypes.data)
         self._check(st)
         return dict(X=X, pred_stds=ps, cov=cov.reshape(k, 6, 6))
 

@@ -129,14 +129,17 @@ __device__ __forceinline__ int keep_pair_of_slot(const int32_t* __restrict__ mod
 }
 constexpr int kKeepOwn = 63;            // list pass: entries a wave-trip owns (lanes 1..63); lane 0 repeats the last entry of the previous trip (the "ghost")
 
-template <bool kVec4, bool kRT2, bool kSmall, bool kKeep>
+// kIdx (icet_register_indexed_device): the block's registration `pair` reads the keyframe tables (n_slots, hotS, slot_of_voxel) of keyframe kf_of[pair]; its
+// descriptor, transform, sums and overflow list stay its own.
+template <bool kVec4, bool kRT2, bool kSmall, bool kKeep, bool kIdx = false>
 __device__ __forceinline__ void gn_accumulate_body(const PairDesc* __restrict__ desc, const float* __restrict__ xf_all,
                                                           const int16_t* __restrict__ slot_of_voxel, const int32_t* __restrict__ n_slots,
                                                           const SlotHot* __restrict__ hotS, uint32_t* __restrict__ acc,
                                                           const float* __restrict__ thr, const LutCell* __restrict__ lut,
                                                           int T, int P, int Mt, int Mp, float guard_t, float guard_p,
                                                           int lds_slots, int chunks, int n_pairs, int force_exact,
-                                                          uint32_t* __restrict__ near_over, uint32_t* __restrict__ near_over_count, const KeepDev& kd) {
+                                                          uint32_t* __restrict__ near_over, uint32_t* __restrict__ near_over_count, const KeepDev& kd,
+                                                          const int32_t* __restrict__ kf_of = nullptr) {
     constexpr uint32_t near_cap = kSmall ? kNearCapSmall : kNearCap;
     constexpr int kW = kAccBlock / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -186,14 +189,16 @@ __device__ __forceinline__ void gn_accumulate_body(const PairDesc* __restrict__ 
     [[maybe_unused]] float* k_edge_t = reinterpret_cast<float*>(nearq + near_cap + 5);
     [[maybe_unused]] float* k_edge_p = k_edge_t + (T + 2);
     [[maybe_unused]] uint8_t* k_nb = reinterpret_cast<uint8_t*>(k_edge_p + (P + 2)) + T;
-    const int ns = n_slots[pair];
+    int kf = pair;                                                        // the row of the keyframe tables
+    if constexpr (kIdx) kf = __builtin_amdgcn_readfirstlane(kf_of[pair]);  // (one scalar load per block)
+    const int ns = n_slots[kf];
     const int nl = min(ns, lds_slots);
-    const SlotHot* hs = hotS + (size_t)pair * V;
+    const SlotHot* hs = hotS + (size_t)kf * V;
     {
         // The block's tables come from L2 through registers with every read of a thread in flight at once: the first two trips of the
         // voxel map, the first three of the LUTs and the first hot record are requested before anything is stored (written as plain
         // copy loops they compile to load - wait - store per trip: six dependent round trips in front of the block's first point).
-        const uint32_t* gm = reinterpret_cast<const uint32_t*>(slot_of_voxel + (size_t)pair * ((V + 1) & ~1));   // rows padded to even length
+        const uint32_t* gm = reinterpret_cast<const uint32_t*>(slot_of_voxel + (size_t)kf * ((V + 1) & ~1));   // rows padded to even length
         uint32_t* lm = reinterpret_cast<uint32_t*>(map);
         const uint2* gl = reinterpret_cast<const uint2*>(lut);
         uint2* ll = reinterpret_cast<uint2*>(lut_t);
@@ -620,6 +625,18 @@ __global__ __launch_bounds__(kAccBlock, kRT2 ? 1 : (kSmall ? 2 : kAccWavesPerSim
     gn_accumulate_body<kVec4, kRT2, kSmall, false>(desc, xf_all, slot_of_voxel, n_slots, hotS, acc, thr, lut, T, P, Mt, Mp, guard_t, guard_p, lds_slots, chunks, n_pairs, force_exact, near_over, near_over_count, KeepDev{});
 }
 
+// The point pass of indexed registrations (icet_register_indexed_device): block `pair` against the parked keyframe kf_of[pair].
+template <bool kVec4, bool kRT2, bool kSmall>
+__global__ __launch_bounds__(kAccBlock, kRT2 ? 1 : (kSmall ? 2 : kAccWavesPerSimd)) void k_gn_accumulate_indexed(const PairDesc* __restrict__ desc, const float* __restrict__ xf_all,
+                                                          const int16_t* __restrict__ slot_of_voxel, const int32_t* __restrict__ n_slots,
+                                                          const SlotHot* __restrict__ hotS, uint32_t* __restrict__ acc,
+                                                          const float* __restrict__ thr, const LutCell* __restrict__ lut,
+                                                          int T, int P, int Mt, int Mp, float guard_t, float guard_p,
+                                                          int lds_slots, int chunks, int n_pairs, int force_exact,
+                                                          uint32_t* __restrict__ near_over, uint32_t* __restrict__ near_over_count, const int32_t* __restrict__ kf_of) {
+    gn_accumulate_body<kVec4, kRT2, kSmall, false, true>(desc, xf_all, slot_of_voxel, n_slots, hotS, acc, thr, lut, T, P, Mt, Mp, guard_t, guard_p, lds_slots, chunks, n_pairs, force_exact, near_over, near_over_count, KeepDev{}, kf_of);
+}
+
 // The point pass with the keep list (throughput batches; KeepState in icet_internal.h): every block reads its pair's mode -- the list, or the whole scan plus
 // the keep masks of its points.  Same sums, same bits as k_gn_accumulate.
 template <bool kVec4>
@@ -685,6 +702,10 @@ hipError_t init_accumulate_kernels() {
     ICET_ACC_ATTR(true, false, false); ICET_ACC_ATTR(false, false, false); ICET_ACC_ATTR(true, true, false); ICET_ACC_ATTR(false, true, false);
     ICET_ACC_ATTR(true, false, true); ICET_ACC_ATTR(false, false, true); ICET_ACC_ATTR(true, true, true); ICET_ACC_ATTR(false, true, true);
 #undef ICET_ACC_ATTR
+#define ICET_ACC_ATTR(V4, RT, SM) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gn_accumulate_indexed<V4, RT, SM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+    ICET_ACC_ATTR(true, false, false); ICET_ACC_ATTR(false, false, false); ICET_ACC_ATTR(true, true, false); ICET_ACC_ATTR(false, true, false);
+    ICET_ACC_ATTR(true, false, true); ICET_ACC_ATTR(false, false, true); ICET_ACC_ATTR(true, true, true); ICET_ACC_ATTR(false, true, true);
+#undef ICET_ACC_ATTR
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gn_accumulate_keep<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gn_accumulate_keep<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gn_accumulate_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
@@ -727,6 +748,7 @@ size_t acc_row_lds_bytes() { return (kHotWords + kAccLds) * 4; }
 
 hipError_t launch_gn_accumulate(const Workspace& w, const LaunchCfg& c, hipStream_t st, const FuseArgs* fuse, bool* fused, int keep_pass) {
     if (fused) *fused = false;
+    if ((keep_pass || fuse) && c.kf_of) return hipErrorInvalidValue;        // (indexed registrations: the plain point pass only)
     if (keep_pass && (c.n_pairs < 32 || c.rt2 || !w.keep_state || !w.keep_mask || !w.keep_list || !w.edges || !w.keep_modes)) return hipErrorInvalidValue;      // (enqueue_loop asks for it on throughput batches only)
     // LDS rows for active voxels: a throughput batch keeps 320 rows (measured optimum on 64-channel scans: fewer rows
     // spill busy voxels to HBM atomics, more rows cost occupancy); a small batch has
@@ -749,8 +771,10 @@ hipError_t launch_gn_accumulate(const Workspace& w, const LaunchCfg& c, hipStrea
     const size_t lds = fixed + (size_t)lds_slots * row;
     dim3 grid(grid_groups(c.n_pairs) * chunks), blk(kAccBlock);
     const LutCell* lut = reinterpret_cast<const LutCell*>(w.lut);
-#define ICET_ACC_LAUNCH(V4, RT, SM) k_gn_accumulate<V4, RT, SM><<<grid, blk, lds, st>>>(w.desc, w.xf, w.slot_of_voxel, w.n_slots, w.hotS, w.acc, w.thr, lut, c.T, c.P, w.lut_Mt, w.lut_Mp, \
-                                                     w.guard_t, w.guard_p, lds_slots, chunks, c.n_pairs, c.force_exact, w.near_over, w.near_over_count)
+#define ICET_ACC_LAUNCH(V4, RT, SM) do { if (c.kf_of) k_gn_accumulate_indexed<V4, RT, SM><<<grid, blk, lds, st>>>(w.desc, w.xf, w.slot_of_voxel, w.n_slots, w.hotS, w.acc, w.thr, lut, c.T, c.P, w.lut_Mt, w.lut_Mp, \
+                                                     w.guard_t, w.guard_p, lds_slots, chunks, c.n_pairs, c.force_exact, w.near_over, w.near_over_count, c.kf_of); \
+                                      else k_gn_accumulate<V4, RT, SM><<<grid, blk, lds, st>>>(w.desc, w.xf, w.slot_of_voxel, w.n_slots, w.hotS, w.acc, w.thr, lut, c.T, c.P, w.lut_Mt, w.lut_Mp, \
+                                                     w.guard_t, w.guard_p, lds_slots, chunks, c.n_pairs, c.force_exact, w.near_over, w.near_over_count); } while (0)
     if (fuse_it) {
         AuxDev aux{}; if (fuse->aux) aux = *fuse->aux;
         aux.pair_user = c.pair_user; aux.done_flag = (fuse->iter == c.runlen - 1) ? c.done_flag : nullptr;      // (as launch_gn_solve sets them)

@@ -36,6 +36,8 @@ struct icet_ctx {
     PairDesc* h_desc = nullptr; int32_t* h_seg = nullptr; int32_t h_cap_pairs = 0;
     bool desc_kf_valid = false, desc_reg_valid = false;   // the pinned descriptors hold what the last icet_keyframe_device_n / icet_register_device_n call wrote (any other writer, and a re-allocation, clears both)
     PairDesc* h_desc_rt = nullptr; int32_t h_cap_rt = 0;       // ICET_FLAG_ROUNDTRIP_SCAN2: descriptors of the round-tripped copy of scan 2
+    PairDesc* h_desc_reg = nullptr; int32_t* h_kf_of = nullptr;  // staging of an indexed call (icet_register_indexed_device), w.cap_regs (+ 1): apart from h_desc, whose scan-1 halves the same_desc shortcut keeps
+    int64_t ws_gen = 0;                                          // counts re-allocations of workspace buffers (part of the indexed call's graph key)
     // device staging for host-pointer entry points
     float* d_stage1 = nullptr; float* d_stage2 = nullptr; int64_t cap_stage1 = 0, cap_stage2 = 0;
     float* d_out = nullptr; float* d_x0 = nullptr; int32_t cap_out_pairs = 0;
@@ -72,7 +74,7 @@ struct icet_ctx {
     struct GraphKey { int64_t v[45]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key (graph_key_of)
     struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false; };
     bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
-    GraphSlot g_solve, g_keyframe, g_loop;                     // the whole solve (icet_solve_batch_device) and its two halves (icet_keyframe_device_n / icet_register_device_n)
+    GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
     hipEvent_t ev_graph = nullptr; bool graph_in_flight = false;
     // A caller inside this library (the sequential nodes, icet_nodes.hip) can put work of its own at the head of the NEXT icet_register_device_n call's launch
     // sequence -- enqueued on the context's stream right before the loop's first kernel, captured into the same graph: the range filter and the loop of a frame
@@ -109,6 +111,44 @@ bool params_ok(const icet_params* p) {
     return true;
 }
 
+// The REGISTRATION side of the workspace (Workspace, icet_internal.h): n_regs registrations on a grid of V voxels.  Leaves the keyframe side alone.
+icet_status ensure_regs(icet_ctx* c, int32_t n_regs, int V) {
+    Workspace& w = c->w;
+    if (n_regs <= w.cap_regs && V <= w.cap_reg_V) return ICET_OK;
+    const int np = n_regs > w.cap_regs ? n_regs : w.cap_regs;
+    const int VV = V > w.cap_reg_V ? V : w.cap_reg_V;
+    const size_t pv = (size_t)np * VV;
+    HIPCHK(c, hipStreamSynchronize(c->stream));                            // (also: no replay or copy still reads the registration staging)
+    HIPCHK(c, dev_realloc(w.acc, pv * kAccWords));
+    HIPCHK(c, hipMemset(w.acc, 0, pv * kAccWords * sizeof(uint32_t)));
+    HIPCHK(c, dev_realloc(w.near_over_count, 2 * (size_t)np));
+    HIPCHK(c, hipMemset(w.near_over_count, 0, 2 * (size_t)np * sizeof(uint32_t)));
+    HIPCHK(c, dev_realloc(w.xf, (size_t)np * 48));
+    HIPCHK(c, dev_realloc(w.X, (size_t)np * 6));
+    HIPCHK(c, dev_realloc(w.desc_reg, np));
+    HIPCHK(c, dev_realloc(w.kf_of, (size_t)np + 1));
+    if (c->h_desc_reg) { HIPCHK(c, hipHostFree(c->h_desc_reg)); c->h_desc_reg = nullptr; }
+    if (c->h_kf_of) { HIPCHK(c, hipHostFree(c->h_kf_of)); c->h_kf_of = nullptr; }
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_desc_reg), sizeof(PairDesc) * np));
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_kf_of), sizeof(int32_t) * ((size_t)np + 1)));
+    w.cap_regs = np; w.cap_reg_V = VV;
+    c->ws_gen++;
+    return ICET_OK;
+}
+
+// The scan-2 overflow list (registration side, sized by the scan-2 points of a call).
+icet_status ensure_scan2(icet_ctx* c, int64_t total_n2) {
+    Workspace& w = c->w;
+    if (total_n2 >= (int64_t)1 << 31) { c->err = "total scan-2 points per call must be < 2^31"; return ICET_ERR_UNSUPPORTED; }
+    if (total_n2 > w.cap_n2) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, dev_realloc(w.near_over, (size_t)total_n2));
+        w.cap_n2 = total_n2;
+        c->ws_gen++;
+    }
+    return ICET_OK;
+}
+
 icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2) {
     Workspace& w = c->w;
     const int V = p->bins_phi * p->bins_theta;
@@ -117,7 +157,7 @@ icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs,
     if (total_n1 >= (int64_t)1 << 31) { c->err = "total scan-1 points per call must be < 2^31"; return ICET_ERR_UNSUPPORTED; }
     const bool grow_pairs = n_pairs > w.cap_pairs || V > w.cap_V;
     if (grow_pairs) {
-        c->kf_pairs = 0;                       // the parked keyframe's tables (hotS / fitS / slot_of_voxel / n_slots / acc) are about to be re-allocated
+        c->kf_pairs = 0;                       // the parked keyframe's tables (hotS / fitS / slot_of_voxel / n_slots) are about to be re-allocated
         const int np = n_pairs > w.cap_pairs ? n_pairs : w.cap_pairs;
         const int VV = V > w.cap_V ? V : w.cap_V;
         const size_t pv = (size_t)np * VV;
@@ -130,11 +170,7 @@ icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs,
         HIPCHK(c, dev_realloc(w.hotD, pv)); HIPCHK(c, dev_realloc(w.fitD, pv)); HIPCHK(c, dev_realloc(w.activeD, pv)); HIPCHK(c, dev_realloc(w.midD, pv));
         HIPCHK(c, dev_realloc(w.hotS, pv)); HIPCHK(c, dev_realloc(w.fitS, pv));
         HIPCHK(c, dev_realloc(w.slot_of_voxel, (size_t)np * ((VV + 1) & ~1)));
-        HIPCHK(c, dev_realloc(w.n_slots, np)); HIPCHK(c, dev_realloc(w.near_over_count, 2 * (size_t)np));
-        HIPCHK(c, dev_realloc(w.acc, pv * kAccWords));
-        HIPCHK(c, hipMemset(w.acc, 0, pv * kAccWords * sizeof(uint32_t)));
-        HIPCHK(c, dev_realloc(w.xf, (size_t)np * 48));
-        HIPCHK(c, dev_realloc(w.X, (size_t)np * 6));
+        HIPCHK(c, dev_realloc(w.n_slots, np));
         HIPCHK(c, dev_realloc(w.gn_part, (size_t)kGnPartWords));
         HIPCHK(c, dev_realloc(w.flags, np));
         HIPCHK(c, dev_realloc(w.zero_rows, (size_t)np * 4));
@@ -147,14 +183,12 @@ icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs,
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_seg), sizeof(int32_t) * (2 * (size_t)np + 1)));
         c->h_cap_pairs = np;
         w.cap_pairs = np; w.cap_V = VV;
+        c->ws_gen++;
     }
-    if (total_n2 >= (int64_t)1 << 31) { c->err = "total scan-2 points per call must be < 2^31"; return ICET_ERR_UNSUPPORTED; }
-    if (total_n2 > w.cap_n2) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_realloc(w.near_over, (size_t)total_n2));
-        w.cap_n2 = total_n2;
-    }
+    { const icet_status rs = ensure_regs(c, n_pairs, V); if (rs != ICET_OK) return rs; }      // (the keyframe build clears the sums and overflow counts of its pairs)
+    { const icet_status ss = ensure_scan2(c, total_n2); if (ss != ICET_OK) return ss; }
     if (total_n1 > w.cap_n1 || grow_pairs) {
+        c->ws_gen++;
         const int64_t n = total_n1 > w.cap_n1 ? total_n1 : w.cap_n1;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (n > w.cap_n1) {
@@ -396,7 +430,9 @@ icet_status ensure_pack(icet_ctx* c, int V, int runlen) {
 // (icet_keyframe_device / icet_register_device): enqueue_keyframe = ICET::fitScan1 (src/icet.cpp:68-107) for the scan-1 halves of the
 // descriptors in c->h_desc[0..n_pairs), enqueue_loop = prepScan2 + runlen x fitScan2 (:254-277, :372-436) for their scan-2 halves
 // against the tables the keyframe left in the workspace.
-LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs) {
+// hd / hs: the staging the call's descriptors sit in (default: h_desc / h_seg; an indexed call passes its own staging and no segment table).
+LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs, PairDesc* hd = nullptr, int32_t* hs = nullptr) {
+    if (!hd) { hd = c->h_desc; hs = c->h_seg; }
     LaunchCfg cfg{};
     cfg.T = p->bins_theta; cfg.P = p->bins_phi; cfg.V = cfg.T * cfg.P; cfg.n = p->n; cfg.runlen = p->runlen;
     cfg.thresh = p->thresh; cfg.buff = p->buff; cfg.n_pairs = n_pairs;
@@ -421,13 +457,14 @@ LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs) {
     cfg.vec4_ok = 1;
     int64_t tot = 0, tot2 = 0; int mx1 = 0, mx2 = 0;
     for (int k = 0; k < n_pairs; k++) {
-        if ((reinterpret_cast<uintptr_t>(c->h_desc[k].s2) & 15u) || (c->h_desc[k].ld2 & 3)) cfg.vec4_ok = 0;
-        c->h_seg[k] = (int32_t)tot; c->h_desc[k].off1 = (int32_t)tot; tot += c->h_desc[k].n1;
-        c->h_desc[k].off2 = (int32_t)tot2; tot2 += c->h_desc[k].n2;
-        if (c->h_desc[k].n1 > mx1) mx1 = c->h_desc[k].n1;
-        if (c->h_desc[k].n2 > mx2) mx2 = c->h_desc[k].n2;
+        if ((reinterpret_cast<uintptr_t>(hd[k].s2) & 15u) || (hd[k].ld2 & 3)) cfg.vec4_ok = 0;
+        if (hs) hs[k] = (int32_t)tot;
+        hd[k].off1 = (int32_t)tot; tot += hd[k].n1;
+        hd[k].off2 = (int32_t)tot2; tot2 += hd[k].n2;
+        if (hd[k].n1 > mx1) mx1 = hd[k].n1;
+        if (hd[k].n2 > mx2) mx2 = hd[k].n2;
     }
-    c->h_seg[n_pairs] = (int32_t)tot;
+    if (hs) hs[n_pairs] = (int32_t)tot;
     cfg.total_n1 = tot; cfg.max_n1 = mx1; cfg.max_n2 = mx2;
     // A small batch of ordinary scans leaves most CUs without a keyframe tile at the full tile size (one 120 k-row scan: 59 tiles on 256 CUs): half-size tiles
     // then (measured, single pair: keyframe 0.170 -> 0.160 ms; a 485 k-row scan keeps the full size: 0.29 vs 0.31).  Same bits either way.
@@ -481,6 +518,39 @@ icet_status enqueue_keyframe(icet_ctx* c, const icet_params* p, int32_t n_pairs,
     return ICET_OK;
 }
 
+// ICET_FLAG_ROUNDTRIP_SCAN2: the round-tripped copy of the scan 2s that the host descriptors `hd` name -- and `wl.desc` on the device, which the
+// pre-pass reads --; on return wl's descriptors are the copy's (wl.desc = w.desc_rt).
+icet_status enqueue_rt2(icet_ctx* c, const LaunchCfg& cfg, int32_t n_pairs, const PairDesc* hd, Workspace& wl, hipEvent_t scan2_ready) {
+    Workspace& w = c->w;
+    int64_t tot = 0;
+    for (int k = 0; k < n_pairs; k++) tot += (hd[k].n2 + 63) / 64 * 64;
+    if (tot > w.cap_rt2 || !w.desc_rt || n_pairs > c->h_cap_rt) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (tot > w.cap_rt2) { HIPCHK(c, dev_realloc(w.rt2, (size_t)3 * tot)); w.cap_rt2 = tot; }
+        if (n_pairs > c->h_cap_rt || !w.desc_rt) {
+            const int np = n_pairs > w.cap_pairs ? n_pairs : w.cap_pairs;
+            HIPCHK(c, dev_realloc(w.desc_rt, np));
+            if (c->h_desc_rt) { HIPCHK(c, hipHostFree(c->h_desc_rt)); c->h_desc_rt = nullptr; }
+            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_desc_rt), sizeof(PairDesc) * np));
+            c->h_cap_rt = np;
+        }
+    } else if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
+    int64_t o = 0;
+    for (int k = 0; k < n_pairs; k++) {
+        const int64_t l = (hd[k].n2 + 63) / 64 * 64;
+        PairDesc dr = hd[k];
+        dr.s2 = w.rt2 + 3 * o; dr.ld2 = (int32_t)l;
+        c->h_desc_rt[k] = dr; o += l;
+    }
+    HIPCHK(c, hipMemcpyAsync(w.desc_rt, c->h_desc_rt, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
+    if (scan2_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, scan2_ready, 0));
+    wl.desc_rt = w.desc_rt; wl.rt2 = w.rt2; wl.cap_rt2 = w.cap_rt2;
+    HIPCHK(c, launch_rt2_prepare(wl, cfg, c->stream));
+    wl.desc = w.desc_rt;
+    return ICET_OK;
+}
+
 icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, const float* d_x0, float* d_out, const AuxDev* aux, bool reupload, float* pts2_out = nullptr, hipEvent_t scan2_ready = nullptr, const int32_t* d_counts2 = nullptr) {
     const bool want_pts2 = aux && aux->xf_last && p->runlen > 0;      // pts2_out: the device computes `points2` (else only the transform snapshot + its event: the host does)
     Workspace& w = c->w;
@@ -492,33 +562,7 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
     while ((int)c->ev_acc.size() < 2 * p->runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }
     Workspace wl = w;                                    // what the loop kernels see: with ICET_FLAG_ROUNDTRIP_SCAN2 their scan 2 is the round-tripped copy
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_b, c->stream));      // keyframe_ms ends here: the scan-2 pre-pass of ICET_FLAG_ROUNDTRIP_SCAN2 belongs to the loop
-    if (cfg.rt2) {
-        int64_t tot = 0;
-        for (int k = 0; k < n_pairs; k++) tot += (c->h_desc[k].n2 + 63) / 64 * 64;
-        if (tot > w.cap_rt2 || !w.desc_rt || n_pairs > c->h_cap_rt) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (tot > w.cap_rt2) { HIPCHK(c, dev_realloc(w.rt2, (size_t)3 * tot)); w.cap_rt2 = tot; }
-            if (n_pairs > c->h_cap_rt || !w.desc_rt) {
-                const int np = n_pairs > w.cap_pairs ? n_pairs : w.cap_pairs;
-                HIPCHK(c, dev_realloc(w.desc_rt, np));
-                if (c->h_desc_rt) { HIPCHK(c, hipHostFree(c->h_desc_rt)); c->h_desc_rt = nullptr; }
-                HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_desc_rt), sizeof(PairDesc) * np));
-                c->h_cap_rt = np;
-            }
-        } else if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
-        int64_t o = 0;
-        for (int k = 0; k < n_pairs; k++) {
-            const int64_t l = (c->h_desc[k].n2 + 63) / 64 * 64;
-            PairDesc dr = c->h_desc[k];
-            dr.s2 = w.rt2 + 3 * o; dr.ld2 = (int32_t)l;
-            c->h_desc_rt[k] = dr; o += l;
-        }
-        HIPCHK(c, hipMemcpyAsync(w.desc_rt, c->h_desc_rt, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
-        if (scan2_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, scan2_ready, 0));
-        HIPCHK(c, launch_rt2_prepare(w, cfg, c->stream));
-        wl = w; wl.desc = w.desc_rt;
-    }
+    if (cfg.rt2) { const icet_status rs = enqueue_rt2(c, cfg, n_pairs, c->h_desc, wl, scan2_ready); if (rs != ICET_OK) return rs; }
     LaunchCfg lcfg = cfg; if (cfg.rt2) lcfg.vec4_ok = 1;     // the copy is 64-float aligned whatever the caller's layout was
     if (cfg.keep) {                                          // masks, list and per-pair state of the keep list (grown here: only throughput batches use them)
         int64_t tot2 = 0; for (int k = 0; k < n_pairs; k++) tot2 += c->h_desc[k].n2;
@@ -574,6 +618,46 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
     icet_status s = enqueue_keyframe(c, p, n_pairs, aux);
     if (s != ICET_OK) return s;
     return enqueue_loop(c, p, n_pairs, d_x0, d_out, aux, false);
+}
+
+// The Gauss-Newton loop of n_regs INDEXED registrations (icet_register_indexed_device) against the parked keyframe: descriptors in c->h_desc_reg, keyframe of
+// registration r in c->h_kf_of[r].  The registration-side tables (acc, xf, X, overflow counts, tickets) are indexed by r, the keyframe tables by h_kf_of[r]
+// (LaunchCfg::kf_of).  The plain point pass and solve: no fused launch, no keep list.
+icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out) {
+    Workspace& w = c->w;
+    LaunchCfg cfg = make_cfg(c, p, n_regs, c->h_desc_reg, nullptr);
+    cfg.pair_user = nullptr; cfg.done_flag = nullptr; cfg.keep = 0; cfg.fuse_solve = 0; cfg.kf_of = w.kf_of;
+    Workspace wl = w; wl.desc = w.desc_reg; wl.seg_off = w.kf_of;           // (k_init_state / k_upload_desc copy the keyframe index as their "segment" table: n_regs + 1 words)
+    // a small batch without the scan-2 round trip: k_init_state, the loop's first kernel, copies the staging itself (a replayed graph re-reads it then)
+    const bool init_uploads = n_regs <= kUploadDescMaxPairs && !cfg.rt2;
+    if (!init_uploads) {
+        if (n_regs <= kUploadDescMaxPairs) HIPCHK(c, launch_upload_desc(wl, c->h_desc_reg, c->h_kf_of, n_regs, c->stream));
+        else {
+            HIPCHK(c, hipMemcpyAsync(w.desc_reg, c->h_desc_reg, sizeof(PairDesc) * n_regs, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(w.kf_of, c->h_kf_of, sizeof(int32_t) * (n_regs + 1), hipMemcpyHostToDevice, c->stream));
+        }
+        if (!c->ev_desc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;      // (never captured: a graph replays small batches without the round trip only)
+    }
+    while ((int)c->ev_acc.size() < 2 * p->runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }
+    if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
+    if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_b, c->stream));        // (no keyframe build in this call: keyframe_ms = 0)
+    if (cfg.rt2) { const icet_status rs = enqueue_rt2(c, cfg, n_regs, c->h_desc_reg, wl, nullptr); if (rs != ICET_OK) return rs; }
+    LaunchCfg lcfg = cfg; if (cfg.rt2) lcfg.vec4_ok = 1;                     // the copy is 64-float aligned whatever the caller's layout was
+    HIPCHK(c, launch_init_state(wl, lcfg, d_x0, c->stream, nullptr, nullptr, init_uploads ? c->h_desc_reg : nullptr, init_uploads ? c->h_kf_of : nullptr));
+    if (init_uploads && !c->capturing) {
+        if (!c->ev_desc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
+    }
+    const bool per_iter = (p->flags & ICET_FLAG_TIMING) != 0;
+    for (int it = 0; it < p->runlen; it++) {
+        if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it], c->stream));
+        HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
+        if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it + 1], c->stream));
+        HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, nullptr, c->stream));
+    }
+    if (!c->capturing) { HIPCHK(c, hipEventRecord(c->ev_c, c->stream)); c->timing_valid = true; c->last_iters = per_iter ? p->runlen : 0; }
+    return ICET_OK;
 }
 
 // Staging buffers of the host-pointer entry points (3 x l floats per scan, leading dimension l = n rounded up to 64).
@@ -644,7 +728,7 @@ icet_status icet_destroy(icet_ctx* c) {
     Workspace& w = c->w;
     void* ps[] = {w.key64A, w.key64B, w.bin16, w.execbits, w.binpos, w.bkt, w.splitters, w.n_buckets, w.bucket_start, w.counts, w.tile_base, w.desc, w.seg_off, w.r1, w.cart1, w.keyA, w.keyB, w.valA, w.valB, w.pred, w.src,
                   w.desc_rt, w.rt2, w.gn_part, w.bin_count, w.bin_start, w.hotD, w.fitD, w.activeD, w.midD, w.hotS, w.fitS, w.slot_of_voxel, w.n_slots, w.near_over, w.near_over_count, w.acc, w.xf, w.X, w.flags, w.zero_rows, w.vrange, w.tile_vr,
-                  w.sort_tmp, w.fit_items, w.fit_n_items, w.live_bins, w.n_live, w.thr, w.lut, w.keep_mask, w.keep_list, w.keep_state, w.keep_modes, w.edges, c->d_stage1, c->d_stage2, c->d_out, c->d_x0};
+                  w.sort_tmp, w.fit_items, w.fit_n_items, w.live_bins, w.n_live, w.thr, w.lut, w.keep_mask, w.keep_list, w.keep_state, w.keep_modes, w.edges, w.desc_reg, w.kf_of, c->d_stage1, c->d_stage2, c->d_out, c->d_x0};
     for (void* p : ps) if (p) (void)hipFree(p);
     free_aux(c);
     if (c->st_copy) (void)hipStreamSynchronize(c->st_copy);
@@ -658,6 +742,8 @@ icet_status icet_destroy(icet_ctx* c) {
     if (c->h_desc) (void)hipHostFree(c->h_desc);
     if (c->h_seg) (void)hipHostFree(c->h_seg);
     if (c->h_desc_rt) (void)hipHostFree(c->h_desc_rt);
+    if (c->h_desc_reg) (void)hipHostFree(c->h_desc_reg);
+    if (c->h_kf_of) (void)hipHostFree(c->h_kf_of);
     if (c->h_out) (void)hipHostFree(c->h_out);
     for (hipEvent_t e : c->ev_acc) (void)hipEventDestroy(e);
     if (c->ev_a) (void)hipEventDestroy(c->ev_a);
@@ -666,7 +752,7 @@ icet_status icet_destroy(icet_ctx* c) {
     for (icet_ctx* h : c->helpers) (void)icet_destroy(h);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_desc) (void)hipEventDestroy(c->ev_desc);
-    for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop}) if (g->have_graph) { (void)hipGraphExecDestroy(g->exec); (void)hipGraphDestroy(g->graph); }
+    for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop, &c->g_indexed}) if (g->have_graph) { (void)hipGraphExecDestroy(g->exec); (void)hipGraphDestroy(g->graph); }
     if (c->ev_graph) (void)hipEventDestroy(c->ev_graph);
     if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
@@ -802,9 +888,9 @@ extern "C++" {
 // every replay, and patched with device-side row counts where the caller has them); what the launches themselves depend on is the LaunchCfg
 // (grids, LDS sizes, point counts passed by value) and the workspace pointers.  A call whose key equals the previous call's is captured;
 // later calls with that key replay: one hipGraphLaunch instead of 15 - 35 launches on the host.
-static icet_ctx::GraphKey graph_key_of(icet_ctx* c, const icet_params* p, int32_t n_pairs, const void* a0, const void* a1, const void* a2, const void* a3) {
+static icet_ctx::GraphKey graph_key_of(icet_ctx* c, const icet_params* p, int32_t n_pairs, const void* a0, const void* a1, const void* a2, const void* a3, PairDesc* hd = nullptr) {
     icet_ctx::GraphKey key{};
-    const LaunchCfg k = make_cfg(c, p, n_pairs);
+    const LaunchCfg k = make_cfg(c, p, n_pairs, hd, hd ? nullptr : c->h_seg);
     auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return (int64_t)i; };
     const int64_t vals[] = {k.T, k.P, k.V, k.n, k.runlen, bits(k.thresh), bits(k.buff), k.n_pairs, k.max_n1, k.max_n2, k.total_n1, k.lds_slots, k.acc_min_pts_per_thread,
                             k.acc_target_blocks, k.kf_chunks, k.kf_pts_per_thread, k.use_library_sort, k.vec4_ok, k.true_sort, k.force_exact, k.rs_cap, k.rs_max_cell,
@@ -992,6 +1078,98 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     };
     if (graph_eligible(c, p, n_pairs)) return run_or_replay(c, c->g_loop, graph_key_of(c, p, n_pairs, d_x0, d_out, d_rows, (const void*)2), enq);
     return enq();
+}
+
+icet_status icet_register_indexed_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || !d_out))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (n_regs == 0) return ICET_OK;
+    // everything is checked before anything is touched: a refused call leaves the parked keyframe as it was
+    const icet_params& q = c->kf_params;
+    if (c->kf_pairs < 1 || q.bins_phi != p->bins_phi || q.bins_theta != p->bins_theta || q.n != p->n || q.thresh != p->thresh || q.buff != p->buff ||
+        ((q.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) { c->err = "no keyframe with these parameters is parked in this context (icet_keyframe_device)"; return ICET_ERR_BAD_ARG; }
+    int64_t tot2 = 0;
+    for (int r = 0; r < n_regs; r++) {
+        if (kf_index[r] < 0 || kf_index[r] >= c->kf_pairs) { c->err = "kf_index[" + std::to_string(r) + "] = " + std::to_string(kf_index[r]) + " is not a parked keyframe (0 .. " + std::to_string(c->kf_pairs - 1) + ")"; return ICET_ERR_BAD_ARG; }
+        const icet_dev_scan& b = scan2[r];
+        if (b.n < 0 || b.ld < b.n || (b.n > 0 && !b.ptr) || b.ld >= ((int64_t)1 << 30)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+        tot2 += b.n;
+    }
+    if (c->tune.keep != 0) { c->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->armed_calls = 2;
+    if (p->runlen == 0) return write_runlen0(c, n_regs, d_x0, d_out);
+    icet_status s = ensure_regs(c, n_regs, p->bins_phi * p->bins_theta);   // the registration side only: the keyframe tables stay where they are
+    if (s == ICET_OK) s = ensure_scan2(c, tot2);
+    if (s == ICET_OK) s = ensure_thresholds(c, p->bins_theta, p->bins_phi);
+    if (s != ICET_OK) return s;
+    // the previous call may still read the registration staging (an upload, or a replay, which re-reads it when it runs)
+    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
+    if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }
+    for (int r = 0; r < n_regs; r++) {
+        PairDesc& d = c->h_desc_reg[r];
+        d.s1 = nullptr; d.n1 = 0; d.ld1 = 0; d.off1 = 0; d.off2 = 0;      // (the loop reads no scan-1 field)
+        d.s2 = scan2[r].ptr; d.n2 = (int32_t)scan2[r].n; d.ld2 = (int32_t)scan2[r].ld;
+        c->h_kf_of[r] = kf_index[r];
+    }
+    c->h_kf_of[n_regs] = 0;
+    auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out); };
+    // a replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved)
+    if (graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg), enq);
+    return enq();
+}
+
+icet_status icet_solve_indexed(icet_ctx* c, const icet_params* p, int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                               int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                               const float* x0, float* x_out, float* pred_stds_out, float* cov_out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!params_ok(p) || n_kf < 1 || n_regs < 0 || !scan1 || !n1 || (n_regs > 0 && (!kf_index || !scan2 || !n2 || !x_out || !pred_stds_out))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (c->pend.active) { c->err = "icet_solve_begin without icet_solve_end on this context"; return ICET_ERR_BAD_ARG; }
+    int64_t tot1 = 0, tot2 = 0;
+    for (int k = 0; k < n_kf; k++) {
+        if (n1[k] < 0 || (n1[k] > 0 && !scan1[k])) { c->err = "bad scan"; return ICET_ERR_BAD_ARG; }
+        tot1 += (n1[k] + 63) / 64 * 64;
+    }
+    for (int r = 0; r < n_regs; r++) {
+        if (n2[r] < 0 || (n2[r] > 0 && !scan2[r])) { c->err = "bad scan"; return ICET_ERR_BAD_ARG; }
+        if (kf_index[r] < 0 || kf_index[r] >= n_kf) { c->err = "kf_index[" + std::to_string(r) + "] out of range"; return ICET_ERR_BAD_ARG; }
+        tot2 += (n2[r] + 63) / 64 * 64;
+    }
+    if (n_regs == 0) return ICET_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    icet_status s = ensure_out(c, n_regs);
+    if (s == ICET_OK) s = ensure_stage(c, tot1, tot2);
+    if (s != ICET_OK) return s;
+    // scans into the staging buffers (dense column-major), then the two device halves
+    std::vector<icet_dev_scan> d1((size_t)n_kf), d2((size_t)n_regs);
+    int64_t o = 0;
+    for (int k = 0; k < n_kf; k++) {
+        const int64_t l = (n1[k] + 63) / 64 * 64;
+        d1[(size_t)k] = icet_dev_scan{c->d_stage1 + 3 * o, n1[k], l};
+        HIPCHK(c, upload_scan(c->d_stage1 + 3 * o, l, scan1[k], n1[k], n1[k], c->stream));
+        o += l;
+    }
+    o = 0;
+    for (int r = 0; r < n_regs; r++) {
+        const int64_t l = (n2[r] + 63) / 64 * 64;
+        d2[(size_t)r] = icet_dev_scan{c->d_stage2 + 3 * o, n2[r], l};
+        HIPCHK(c, upload_scan(c->d_stage2 + 3 * o, l, scan2[r], n2[r], n2[r], c->stream));
+        o += l;
+    }
+    const float* dx0 = nullptr;
+    if (x0) { std::memcpy(c->h_x0, x0, sizeof(float) * 6 * n_regs); HIPCHK(c, hipMemcpyAsync(c->d_x0, c->h_x0, sizeof(float) * 6 * n_regs, hipMemcpyHostToDevice, c->stream)); dx0 = c->d_x0; }
+    s = icet_keyframe_device(c, p, n_kf, d1.data());
+    if (s == ICET_OK) s = icet_register_indexed_device(c, p, n_regs, kf_index, d2.data(), dx0, c->d_out);
+    if (s != ICET_OK) { (void)hipStreamSynchronize(c->stream); return s; }
+    HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(float) * 48 * n_regs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->armed_calls = 0; c->desc_in_flight = false; c->graph_in_flight = false;
+    for (int r = 0; r < n_regs; r++) {
+        std::memcpy(x_out + 6 * r, c->h_out + 48 * r, 6 * sizeof(float));
+        std::memcpy(pred_stds_out + 6 * r, c->h_out + 48 * r + 6, 6 * sizeof(float));
+        if (cov_out) std::memcpy(cov_out + 36 * r, c->h_out + 48 * r + 12, 36 * sizeof(float));
+    }
+    return ICET_OK;
 }
 
 icet_status icet_solve_batch(icet_ctx* c, const icet_params* p, int32_t n_pairs,

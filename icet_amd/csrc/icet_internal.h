@@ -110,9 +110,17 @@ struct AuxDev {
     float* xf_last;      // 48 floats: the transform record the LAST iteration's point pass uses (written by k_init_state / the solve of iteration runlen - 2), for `points2`
 };
 
+// Two sides, sized apart ("the workspace split").  KEYFRAME side: what fitScan1 writes -- hotS / fitS / slot_of_voxel / n_slots and the
+// build's temporaries --, cap_pairs x cap_V; growing it moves the tables and un-parks a parked keyframe.  REGISTRATION side: what the Gauss-Newton loop
+// keeps per registration -- acc, xf, X, the overflow list and its counts + block tickets, the indexed call's descriptors and keyframe index --,
+// cap_regs x cap_reg_V; growing it leaves the keyframe side (and a parked keyframe) alone.  cap_regs >= cap_pairs: the keyframe build clears the
+// accumulators and overflow counts of its pairs.
 struct Workspace {
     // capacities
     int32_t cap_pairs = 0; int64_t cap_n1 = 0; int32_t cap_V = 0;
+    int32_t cap_regs = 0; int32_t cap_reg_V = 0;
+    PairDesc* desc_reg = nullptr;             // registration side: scan-2 descriptors of an indexed call (icet_register_indexed_device), cap_regs
+    int32_t* kf_of = nullptr;                 // registration side: the keyframe of every registration of an indexed call, cap_regs + 1
     PairDesc* desc = nullptr;
     PairDesc* desc_rt = nullptr; float* rt2 = nullptr; int64_t cap_rt2 = 0;   // ICET_FLAG_ROUNDTRIP_SCAN2: descriptors whose scan 2 is the round-tripped copy, and that copy (3 x cap_rt2 floats)
     int32_t* seg_off = nullptr;               // pairs+1, scan-1 segment offsets
@@ -134,12 +142,12 @@ struct Workspace {
     void* fit_items = nullptr; size_t cap_fit_items = 0; uint32_t* fit_n_items = nullptr;   // work items of k_fit_roundtrip (16 B each) and their count
     SlotHot* hotS = nullptr; SlotFit* fitS = nullptr;                               // compact, pairs x V
     int16_t* slot_of_voxel = nullptr; int32_t* n_slots = nullptr;
-    uint32_t* acc = nullptr;                  // pairs x V x kAccWords
+    uint32_t* acc = nullptr;                  // regs x V x kAccWords (all zero between solves: the solve clears what the point pass adds)
     // Scan-2 points that the fast classification cannot decide and that did not fit the block's LDS queue (k_gn_accumulate):
     // point indices, one segment of n2 entries per pair, and the fill count per pair.  Drained -- and the count reset -- by
     // k_gn_solve.  Empty on ordinary data (~0.02 % of the points are undecided and a block's queue holds 512 of them).
-    uint32_t* near_over = nullptr; int64_t cap_n2 = 0; uint32_t* near_over_count = nullptr;   // (2 x cap_pairs words: the second half are the point pass' per-pair block tickets, gn_done())
-    uint32_t* gn_done() const { return near_over_count ? near_over_count + cap_pairs : nullptr; }
+    uint32_t* near_over = nullptr; int64_t cap_n2 = 0; uint32_t* near_over_count = nullptr;   // (2 x cap_regs words: the second half are the point pass' per-pair block tickets, gn_done())
+    uint32_t* gn_done() const { return near_over_count ? near_over_count + cap_regs : nullptr; }
     float* xf = nullptr;                      // pairs x 48: t[3], R[9] row-major, angles[3], pad, J[27] (see write_xf)
     float* gn_part = nullptr;                 // two-stage solve of fine grids: kGnPartWords floats of partial sums (icet_solve.hip)
     float* X = nullptr;                       // pairs x 6
@@ -220,6 +228,7 @@ struct LaunchCfg {
     float gn_cond_bound2 = 6.25e10f;     // Tuning::gn_cond_bound squared: k_gn_solve's Cholesky route needs |A|_F |A^-1|_F <= the bound (icet_solve.hip gn_tail)
     int32_t* done_flag = nullptr;          // set: the solve of the last iteration stores 1 there (pinned host memory) behind its results (icet_ctx_set_done_flag)
     const int32_t* pair_user = nullptr;    // set (ragged throughput batches, icet_capi.hip solve_device_part): slot s of the tables holds the caller's pair pair_user[s] -- X0 is read and the results are written there
+    const int32_t* kf_of = nullptr;        // set (indexed registrations, icet_register_indexed_device): the loop's block of registration r reads the keyframe tables of kf_of[r]
     const PairDesc* h_desc_up = nullptr; const int32_t* h_seg_up = nullptr;      // set: the keyframe's first kernel (k_rs_splitters) copies the descriptors / segment offsets from this pinned staging itself (small batches: launch_upload_desc's job)
 };
 constexpr float kRejectMovingThresh = 0.3f;        // python/ICET_spherical.py:38  RM_thresh

@@ -43,6 +43,14 @@ __global__ __launch_bounds__(kT) void k_gn_solve(const int32_t* __restrict__ n_s
                                                      int V, int n, int iter, int runlen, NearOverflow over, int reject_moving, float* __restrict__ part, int nblk, float cond_bound2, KeepArgs keep) {
     gn_solve_body<kT, kStage, kT, kRefW>(n_slots, fitS, acc, X_all, xf_all, out, aux, V, n, iter, runlen, over, reject_moving, part, nblk, cond_bound2, keep);
 }
+// The same for indexed registrations (icet_register_indexed_device): registration `pair` against the parked keyframe kf_of[pair].
+template <int kT, int kStage, bool kRefW = false>
+__global__ __launch_bounds__(kT) void k_gn_solve_indexed(const int32_t* __restrict__ n_slots, const SlotFit* __restrict__ fitS, uint32_t* __restrict__ acc,
+                                                             float* __restrict__ X_all, float* __restrict__ xf_all, float* __restrict__ out, AuxDev aux,
+                                                             int V, int n, int iter, int runlen, NearOverflow over, int reject_moving, float* __restrict__ part, int nblk, float cond_bound2, KeepArgs keep,
+                                                             const int32_t* __restrict__ kf_of) {
+    gn_solve_body<kT, kStage, kT, kRefW, true>(n_slots, fitS, acc, X_all, xf_all, out, aux, V, n, iter, runlen, over, reject_moving, part, nblk, cond_bound2, keep, -1, kf_of);
+}
 
 
 // Test hook (icet_debug_gn_tail): n independent (HTWH, HTWdz), one WAVE each, through the SAME gn_tail k_gn_solve runs.
@@ -156,18 +164,19 @@ hipError_t launch_gn_solve(const Workspace& w, const LaunchCfg& c, int iter, flo
     const KeepArgs keep{w.desc, w.keep_mask, w.keep_list, w.keep_state, c.keep_bt * c.keep_bt * c.keep_check_scale * c.keep_check_scale, c.keep_br * c.keep_br * c.keep_check_scale * c.keep_check_scale, w.keep_state ? keep_pass : 0,      // 1: build / check; 2: behind the last pass (statistics only)
                         w.keep_modes ? w.keep_modes + (size_t)((iter + 1) & 1) * c.n_pairs : nullptr, c.n_pairs};
     NearOverflow over{w.desc, w.slot_of_voxel, w.hotS, w.thr, w.near_over, w.near_over_count, c.T, c.P, c.rt2};
-#define ICET_SOLVE_LAUNCHES(RW) do {                                                                                                                                   \
+#define ICET_SOLVE_LAUNCHES(K, RW, ...) do {                                                                                                                            \
     if (c.V > 4096 && c.n_pairs <= kTwoStageMaxPairs && w.gn_part) {                                                                                                      \
         /* two stages: several blocks per pair reduce their share of the slots to 27 partial sums each, one block per pair adds them and solves */                        \
         const int nblk = kTwoStageBlocks;                                                                                                                                 \
-        k_gn_solve<512, 1, RW><<<c.n_pairs * nblk, 512, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, w.gn_part, nblk, c.gn_cond_bound2, keep); \
+        K<512, 1, RW><<<c.n_pairs * nblk, 512, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, w.gn_part, nblk, c.gn_cond_bound2, keep, ##__VA_ARGS__); \
         ICET_LAUNCH_CHECK();                                                                                                                                              \
-        k_gn_solve<512, 2, RW><<<c.n_pairs, 512, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, w.gn_part, nblk, c.gn_cond_bound2, keep); \
+        K<512, 2, RW><<<c.n_pairs, 512, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, w.gn_part, nblk, c.gn_cond_bound2, keep, ##__VA_ARGS__); \
     }                                                                                                                                                                     \
-    else if (c.V > 4096) k_gn_solve<512, 0, RW><<<c.n_pairs, 512, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, nullptr, 1, c.gn_cond_bound2, keep); \
-    else k_gn_solve<kBlock, 0, RW><<<c.n_pairs, kBlock, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, nullptr, 1, c.gn_cond_bound2, keep); \
+    else if (c.V > 4096) K<512, 0, RW><<<c.n_pairs, 512, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, nullptr, 1, c.gn_cond_bound2, keep, ##__VA_ARGS__); \
+    else K<kBlock, 0, RW><<<c.n_pairs, kBlock, 0, st>>>(w.n_slots, w.fitS, w.acc, w.X, w.xf, d_out, aux, c.V, c.n, iter, c.runlen, over, c.reject_moving, nullptr, 1, c.gn_cond_bound2, keep, ##__VA_ARGS__); \
 } while (0)
-    if (c.ref_w) ICET_SOLVE_LAUNCHES(true); else ICET_SOLVE_LAUNCHES(false);
+    if (c.kf_of) { if (c.ref_w) ICET_SOLVE_LAUNCHES(k_gn_solve_indexed, true, c.kf_of); else ICET_SOLVE_LAUNCHES(k_gn_solve_indexed, false, c.kf_of); }      // (indexed registrations: the keyframe row of every block)
+    else if (c.ref_w) ICET_SOLVE_LAUNCHES(k_gn_solve, true); else ICET_SOLVE_LAUNCHES(k_gn_solve, false);
 #undef ICET_SOLVE_LAUNCHES
     ICET_LAUNCH_CHECK();
     return hipSuccess;

@@ -237,11 +237,13 @@ __device__ __forceinline__ void keep_budget_check(const KeepArgs& k, int pair, c
 // reach every barrier).  The pointers carry no __restrict__: in the fused kernel acc / the overflow list were written through other names a few lines earlier.
 // kRefW (ICET_FLAG_REFERENCE_W): the per-voxel weight W as the reference computes it -- the float CompleteOrthogonalDecomposition of the full (not
 // symmetrised) 3 x 3 L U^T R_noise U L^T -- instead of the double-precision pseudo-inverse of the default path.
-template <int kT, int kStage, int kBlockT = kT, bool kRefW = false>
+// kIdx (icet_register_indexed_device): registration `pair` reads the keyframe tables (n_slots, fitS, the overflow drain's slot_of_voxel / hotS) of keyframe
+// kf_of[pair]; everything else -- acc, X, xf, out, the overflow list -- stays the registration's own.
+template <int kT, int kStage, int kBlockT = kT, bool kRefW = false, bool kIdx = false>
 __device__ __forceinline__ void gn_solve_body(const int32_t* n_slots, const SlotFit* fitS, uint32_t* acc,
                                               float* X_all, float* xf_all, float* out, const AuxDev& aux,
                                               int V, int n, int iter, int runlen, const NearOverflow& over, int reject_moving, float* part, int nblk, float cond_bound2,
-                                              const KeepArgs& keep = KeepArgs{}, int pair_of_block = -1) {
+                                              const KeepArgs& keep = KeepArgs{}, int pair_of_block = -1, const int32_t* kf_of = nullptr) {
     // No contraction of a * b + c in this function: the bits of the per-voxel algebra must not depend on which instantiation the compiler is looking at (its choice of
     // what to fuse follows the surrounding code: after this body moved into a header the two-stage and the one-block form of one pair disagreed in last bits), and the
     // CPU restatement evaluates these expressions unfused as well.
@@ -256,6 +258,8 @@ __device__ __forceinline__ void gn_solve_body(const int32_t* n_slots, const Slot
     const bool own = kBlockT == kT || (int)threadIdx.x < kT;        // (a thread beyond kT: no slot, no row of the reduction table)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s_first = blk * kT + (int)threadIdx.x, vb_stride = kStage == 1 ? nblk : 1;
+    int kf = pair;                                                      // the row of the keyframe tables
+    if constexpr (kIdx) kf = __builtin_amdgcn_readfirstlane(kf_of[pair]);   // (one scalar load per block)
     float* X = X_all + pair * 6;
     // The block is a chain of dependent latencies, so everything it will need is requested up front: the two counts, the Jacobian
     // table and -- speculatively, for slot threadIdx.x, before the number of slots is known (any slot < V is valid memory) -- the
@@ -263,7 +267,7 @@ __device__ __forceinline__ void gn_solve_body(const int32_t* n_slots, const Slot
     struct Rec { uint4 q[5]; };
     static_assert(sizeof(Rec) == kAccWords * 4 && sizeof(Rec) == sizeof(SlotFit), "80-byte records");
     const uint32_t nov = over.count[pair];                              // block-uniform
-    const int ns = n_slots[pair];
+    const int ns = n_slots[kf];
     const float jmine = (threadIdx.x < 27) ? xf_all[pair * kXf + 16 + threadIdx.x] : 0.f;      // written by the previous update (write_xf)
     auto load_rec = [](const void* p) { Rec r; const uint4* q = reinterpret_cast<const uint4*>(p);
 #pragma unroll
@@ -272,9 +276,14 @@ __device__ __forceinline__ void gn_solve_body(const int32_t* n_slots, const Slot
     if (kStage == 1 && nov) return;                                     // block-uniform (and the same in every block of the pair): stage 2 does the whole solve
     const bool from_partials = kStage == 2 && nov == 0u;                // stage 1 has reduced the slots already
     Rec accR{}, fitR{};
-    if (!from_partials && own && s_first < V) { accR = load_rec(acc + ((size_t)pair * V + s_first) * kAccWords); fitR = load_rec(fitS + (size_t)pair * V + s_first); }
+    if (!from_partials && own && s_first < V) { accR = load_rec(acc + ((size_t)pair * V + s_first) * kAccWords); fitR = load_rec(fitS + (size_t)kf * V + s_first); }
     if (nov) {
-        drain_near_overflow(over, pair, V, xf_all + pair * kXf, acc + (size_t)pair * V * kAccWords, nov);
+        if constexpr (kIdx) {
+            // the drain indexes the keyframe tables by the registration's own row: hand it views rebased so that row `pair` of them is row `kf` of the tables
+            NearOverflow o = over;
+            o.slot_of_voxel += ((ptrdiff_t)kf - pair) * ((V + 1) & ~1); o.hotS += ((ptrdiff_t)kf - pair) * V;
+            drain_near_overflow(o, pair, V, xf_all + pair * kXf, acc + (size_t)pair * V * kAccWords, nov);
+        } else drain_near_overflow(over, pair, V, xf_all + pair * kXf, acc + (size_t)pair * V * kAccWords, nov);
         __threadfence();                                                // this block reads the sums it has just added to
         __syncthreads();
         if (threadIdx.x == 0) over.count[pair] = 0u;
@@ -295,7 +304,7 @@ __device__ __forceinline__ void gn_solve_body(const int32_t* n_slots, const Slot
       const int s = vb * kT + (int)threadIdx.x;
       if (own && s < ns) do {
         uint32_t* A = acc + ((size_t)pair * V + s) * kAccWords;
-        if (s != s_first) { accR = load_rec(A); fitR = load_rec(fitS + (size_t)pair * V + s); }       // later rounds
+        if (s != s_first) { accR = load_rec(A); fitR = load_rec(fitS + (size_t)kf * V + s); }       // later rounds
         uint32_t aw[kAccWords];
         __builtin_memcpy(aw, &accR, sizeof(Rec));
         const uint32_t n2 = aw[0], m = aw[1];

@@ -194,6 +194,31 @@ icet_status icet_keyframe_device_n(icet_ctx* ctx, const icet_params* p, int32_t 
 icet_status icet_register_device_n(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, const icet_dev_scan* scan2, const int32_t* d_rows,
                                    const float* d_x0, float* d_out);
 
+/* --- many scans against shared parked keyframes: each keyframe is built once, however often it is registered against ---------------
+ * Multi-start (one pair from several X0), loop-closure / relocalisation candidates (one scan against K stored keyframes, or K scans against
+ * one map keyframe), several sensors against one reference.  Registration r runs prepScan2 + runlen x fitScan2 of scan2[r], from d_x0[r]
+ * (NULL = zeros), against parked keyframe kf_index[r] (HOST array, 0 <= kf_index[r] < the parked count; repeats and any order allowed).
+ * d_out: n_regs x 48 floats in the layout of icet_solve_batch_device.  Bit for bit the result icet_solve_batch_device gives for the pair
+ * (scan1[kf_index[r]], scan2[r], x0[r]).  Asynchronous on the context's stream (icet_sync); kf_index is read before the call returns.
+ * The parked keyframe stays parked: it can be registered against again, by this call or icet_register_device.  What un-parks it: a whole
+ * solve on the context (icet_solve, icet_solve_begin, icet_solve_batch[_device], icet_solve_indexed), another icet_keyframe_device[_n], and
+ * an icet_reserve that has to grow the keyframe side of the workspace (more keyframes, a finer grid or more scan-1 points than any call so far).
+ * Growing the registration side -- more registrations or scan-2 points than before -- leaves the keyframe alone.
+ * Same argument rules as icet_register_device_n: ICET_ERR_BAD_ARG when no keyframe is parked, when the grid, n, thresh, buff or the
+ * keyframe-shaping flags (ICET_FLAG_TRUE_SORT, ICET_FLAG_HALF_GAP_BOUNDS) differ from the parked keyframe's, or when an index is out of range;
+ * ICET_ERR_UNSUPPORTED while option "keep" is on (the indexed loop runs the plain point pass).  A refused call leaves the parked keyframe valid.
+ * runlen == 0 writes X = X0, pred_stds = cov = 0; n_regs == 0 returns ICET_OK and does nothing.  n_regs may be larger or smaller than the
+ * parked count; the limits are those of a batch of n_regs pairs.  ICET_FLAG_ROUNDTRIP_SCAN2, REJECT_MOVING and DOUBLE_W apply per call. */
+icet_status icet_register_indexed_device(icet_ctx* ctx, const icet_params* p, int32_t n_regs, const int32_t* kf_index,
+                                         const icet_dev_scan* scan2, const float* d_x0, float* d_out);
+
+/* Host-pointer form, shaped like icet_solve_batch: parks the keyframes of the n_kf scan 1s (they stay parked after the call), runs the
+ * n_regs registrations and copies the results out (x0: n_regs x 6 or NULL; x_out, pred_stds_out: n_regs x 6; cov_out: n_regs x 36 or NULL). */
+icet_status icet_solve_indexed(icet_ctx* ctx, const icet_params* p,
+                               int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                               int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                               const float* x0, float* x_out, float* pred_stds_out, float* cov_out);
+
 /* Pre-size the workspace (so the first timed call does not allocate). */
 icet_status icet_reserve(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2);
 
