@@ -30,8 +30,10 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
                     "icet_node_prev_scan", "icet_node_aligned", "icet_node_snail_trail", "icet_node_last_timing", "icet_stream", "icet_device",
+                    "icet_node_group_create", "icet_node_group_destroy", "icet_node_group_last_error", "icet_node_group_push_device", "icet_node_group_map",
+                    "icet_node_group_prev_scan", "icet_node_group_aligned", "icet_node_group_snail_trail",
                     "icet_load_scan", "icet_free_scan", "icet_save_scan_npy")
-_NON_STATUS = ("icet_version", "icet_last_error", "icet_node_last_error", "icet_stream", "icet_device", "icet_free_scan", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context")
+_NON_STATUS = ("icet_version", "icet_last_error", "icet_node_last_error", "icet_node_group_last_error", "icet_stream", "icet_device", "icet_free_scan", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context")
 
 
 class IcetError(RuntimeError):
@@ -134,6 +136,12 @@ def load_library():
     L.icet_node_prev_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.icet_node_aligned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.icet_node_snail_trail.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.icet_node_group_create.argtypes = [C.c_void_p, C.POINTER(NodeParams), C.c_int32, C.POINTER(C.c_void_p)]
+    L.icet_node_group_destroy.argtypes = [C.c_void_p]
+    L.icet_node_group_last_error.argtypes = [C.c_void_p]; L.icet_node_group_last_error.restype = C.c_char_p
+    L.icet_node_group_push_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(DevScan), C.POINTER(NodeResult)]
+    for name in ("icet_node_group_map", "icet_node_group_prev_scan", "icet_node_group_aligned", "icet_node_group_snail_trail"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.icet_load_scan.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]
     L.icet_free_scan.argtypes = [C.POINTER(C.c_float)]; L.icet_free_scan.restype = None
     L.icet_save_scan_npy.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_int64]
@@ -629,6 +637,79 @@ class Node:
         if st != ICET_OK:
             raise IcetError(st, "icet_node_last_timing: " + (load_library().icet_node_last_error(self._h) or b"").decode())
         return dict(filter_ms=t[0], solve_ms=t[1], map_ms=t[2])
+
+
+class NodeGroup:
+    """``icet_node_group``: ``n_streams`` independent nodes with one set of parameters (the presets above), advanced together.  Every call carries one frame for
+    each of any subset of the streams and pays the frame's launch chain once; every stream gets the bits of its own :class:`Node` fed the same frames."""
+
+    def __init__(self, ctx=None, n_streams=1, device=0, **kw):
+        self._ctx = ctx if ctx is not None else Context(device)
+        self._p = node_params(**kw)
+        self.n_streams = int(n_streams)
+        h = C.c_void_p()
+        st = load_library().icet_node_group_create(self._ctx._h if self._ctx is not None else None, C.byref(self._p), self.n_streams, C.byref(h))
+        if st != ICET_OK:
+            raise IcetError(st, "icet_node_group_create")
+        self._h = h
+        import weakref
+        if not hasattr(self._ctx, "_nodes"):
+            self._ctx._nodes = []
+        self._ctx._nodes.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().icet_node_group_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, st, what):
+        return IcetError(st, what + ": " + (load_library().icet_node_group_last_error(self._h) or b"").decode())
+
+    def push_device(self, frames):
+        """One frame for each of several streams, scans already in HBM on the context's device (and complete): [(stream, device_ptr, n, ld), ...] ->
+        one result dict per frame, in the order given."""
+        k = len(frames)
+        ids = (C.c_int32 * max(k, 1))(*[int(f[0]) for f in frames])
+        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (_, p, n, ld) in frames])
+        R = (NodeResult * max(k, 1))()
+        st = load_library().icet_node_group_push_device(self._h, k, ids, A, R)
+        if st != ICET_OK:
+            raise self._err(st, "icet_node_group_push_device")
+        return [_result_dict(R[i]) for i in range(k)]
+
+    def _rows(self, fn, s, what):
+        rows = C.c_int64()
+        st = fn(self._h, int(s), None, 0, C.byref(rows))
+        if st != ICET_OK:
+            raise self._err(st, what)
+        out = np.zeros((3, max(rows.value, 1)), np.float32)
+        if rows.value:
+            st = fn(self._h, int(s), out.ctypes.data_as(C.c_void_p), rows.value, C.byref(rows))
+            if st != ICET_OK:
+                raise self._err(st, what)
+        return np.ascontiguousarray(out[:, :rows.value].T)
+
+    def map(self, s):
+        """Stream s's ``EigenQueue::getQueue()``: rows x 3, oldest first."""
+        return self._rows(load_library().icet_node_group_map, s, "icet_node_group_map")
+
+    def prev_scan(self, s):
+        """Stream s's ``prev_pcl_matrix``: rows x 3."""
+        return self._rows(load_library().icet_node_group_prev_scan, s, "icet_node_group_prev_scan")
+
+    def aligned(self, s):
+        """Stream s's ``scan2_in_scan1_frame`` of its last frame: rows x 3."""
+        return self._rows(load_library().icet_node_group_aligned, s, "icet_node_group_aligned")
+
+    def snail_trail(self, s):
+        """Stream s's ``snailTrail``: rows x 3."""
+        return self._rows(load_library().icet_node_group_snail_trail, s, "icet_node_group_snail_trail")
 
 
 # ---------------------------------------------------------------------------------------------------------------------

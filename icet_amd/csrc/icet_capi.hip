@@ -121,8 +121,8 @@ icet_status ensure_regs(icet_ctx* c, int32_t n_regs, int V) {
     HIPCHK(c, hipStreamSynchronize(c->stream));                            // (also: no replay or copy still reads the registration staging)
     HIPCHK(c, dev_realloc(w.acc, pv * kAccWords));
     HIPCHK(c, hipMemset(w.acc, 0, pv * kAccWords * sizeof(uint32_t)));
-    HIPCHK(c, dev_realloc(w.near_over_count, 2 * (size_t)np));
-    HIPCHK(c, hipMemset(w.near_over_count, 0, 2 * (size_t)np * sizeof(uint32_t)));
+    HIPCHK(c, dev_realloc(w.near_over_count, 2 * (size_t)np + 1));
+    HIPCHK(c, hipMemset(w.near_over_count, 0, (2 * (size_t)np + 1) * sizeof(uint32_t)));
     HIPCHK(c, dev_realloc(w.xf, (size_t)np * 48));
     HIPCHK(c, dev_realloc(w.X, (size_t)np * 6));
     HIPCHK(c, dev_realloc(w.desc_reg, np));

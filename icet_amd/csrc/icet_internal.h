@@ -107,6 +107,8 @@ struct AuxDev {
     float* x_hist; float* htwh; float* htwdz; float* cond; int32_t* n2_raw; int32_t* n2_in; float* test_points;
     const int32_t* pair_user;   // LaunchCfg::pair_user (set by launch_gn_solve, not by callers)
     int32_t* done_flag;         // LaunchCfg::done_flag, in the last iteration's launch only (set by launch_gn_solve)
+    uint32_t* done_count;       // with done_flag: the launch's arrival counter (Workspace::done_count) -- only the block of the LAST pair to finish raises the flag
+    int32_t done_pairs;         //   pairs of the launch
     float* xf_last;      // 48 floats: the transform record the LAST iteration's point pass uses (written by k_init_state / the solve of iteration runlen - 2), for `points2`
 };
 
@@ -146,8 +148,9 @@ struct Workspace {
     // Scan-2 points that the fast classification cannot decide and that did not fit the block's LDS queue (k_gn_accumulate):
     // point indices, one segment of n2 entries per pair, and the fill count per pair.  Drained -- and the count reset -- by
     // k_gn_solve.  Empty on ordinary data (~0.02 % of the points are undecided and a block's queue holds 512 of them).
-    uint32_t* near_over = nullptr; int64_t cap_n2 = 0; uint32_t* near_over_count = nullptr;   // (2 x cap_regs words: the second half are the point pass' per-pair block tickets, gn_done())
+    uint32_t* near_over = nullptr; int64_t cap_n2 = 0; uint32_t* near_over_count = nullptr;   // (2 x cap_regs + 1 words: the second half are the point pass' per-pair block tickets, gn_done(); the last the done word's arrival counter, done_count())
     uint32_t* gn_done() const { return near_over_count ? near_over_count + cap_regs : nullptr; }
+    uint32_t* done_count() const { return near_over_count ? near_over_count + 2 * (size_t)cap_regs : nullptr; }
     float* xf = nullptr;                      // pairs x 48: t[3], R[9] row-major, angles[3], pad, J[27] (see write_xf)
     float* gn_part = nullptr;                 // two-stage solve of fine grids: kGnPartWords floats of partial sums (icet_solve.hip)
     float* X = nullptr;                       // pairs x 6

@@ -31,6 +31,7 @@
 #include <mutex>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -359,12 +360,70 @@ icet_status ensure_scan(icet_node* nd, int which, int64_t n) {
 
 // The frame's down-sample indices into pinned h_idx (simpleMapMaker.cpp:147-158: iota, std::shuffle with the node's generator, the first map_downsample entries): returns
 // how many.  Only the first entries of the shuffled vector are ever used, so only they are tracked while the generator makes its n - 1 draws (icet_shuffle.h).
-int draw_downsample(icet_node* nd, int64_t nk) {
-    if (nd->fast_shuffle) icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)nd->p.map_downsample, nd->fgen, nd->indices);
-    else icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)nd->p.map_downsample, nd->gen, nd->indices);
-    const int m = (int)nd->indices.size();
-    for (int i = 0; i < m; i++) nd->h_idx[i] = (int32_t)nd->indices[i];
+// (a node group's streams draw the same way, each from its own generator)
+int draw_downsample_into(bool fast, icet_shuffle::FastMt& fgen, std::mt19937& gen, std::vector<std::size_t>& indices, int32_t map_downsample, int64_t nk, int32_t* h_idx) {
+    if (fast) icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)map_downsample, fgen, indices);
+    else icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)map_downsample, gen, indices);
+    const int m = (int)indices.size();
+    for (int i = 0; i < m; i++) h_idx[i] = (int32_t)indices[i];
     return m;
+}
+int draw_downsample(icet_node* nd, int64_t nk) { return draw_downsample_into(nd->fast_shuffle, nd->fgen, nd->gen, nd->indices, nd->p.map_downsample, nk, nd->h_idx); }
+
+// The host tail of a solved frame, shared by icet_node and icet_node_group so that the two cannot drift apart: X and pred_stds from the solve's 48 result floats,
+// X0 seeded for the next frame (odometry.cpp:82 / simpleMapMaker.cpp:124), the divergence guard (simpleMapMaker.cpp:129-137), the map ring's bookkeeping
+// (simpleMapMaker.cpp:147-158, 34-41), the snail trail (scanMatcher.cpp:79-84), the pose chain X_homo = X_homo * X_homo_i (odometry.cpp:91-98) and the result.
+// The device work in between is the caller's: map_dev(X, R^-1, ring position, rows) in front of the ring's bookkeeping, align_dev(X, R^-1) behind it; a failure
+// either returns ends the tail there (nothing behind it has changed).  One compiled body (noinline): the same bits whoever calls it.
+struct NodeTail { float* X0; float* pose; int64_t* map_pos; bool* map_filled; std::vector<float>* snail; };
+using TailMapDev = std::function<icet_status(const float* X, const float* Ri, int64_t pos, int m)>;
+using TailAlignDev = std::function<icet_status(const float* X, const float* Ri)>;
+__attribute__((noinline)) icet_status frame_tail(const icet_node_params& p, const NodeTail& st, const float* out48, int64_t nk, int m_map, icet_node_result* res,
+                                                 const TailMapDev& map_dev, const TailAlignDev& align_dev) {
+    float X[6];
+    std::memcpy(X, out48, sizeof(X)); std::memcpy(res->pred_stds, out48 + 6, sizeof(float) * 6);
+    // seed for the next frame (odometry.cpp:82 / simpleMapMaker.cpp:124), then the guard (simpleMapMaker.cpp:129-137)
+    for (int k = 0; k < 6; k++) st.X0[k] = p.seed_x0 ? X[k] : 0.f;
+    {
+        // each group is guarded only when ITS threshold is set (0 = off, include/icet_nodes.h): a caller who sets one of the two
+        // must not have the other group compared against 0
+        const float tt = p.trans_thresh, rt = p.rot_thresh;
+        if ((tt > 0.f && (std::fabs(X[0]) > tt || std::fabs(X[1]) > tt || std::fabs(X[2]) > tt)) ||
+            (rt > 0.f && (std::fabs(X[3]) > rt || std::fabs(X[4]) > rt || std::fabs(X[5]) > rt))) {
+            for (int k = 0; k < 6; k++) X[k] = 0.f;
+            res->diverged = 1;
+        }
+    }
+    float R[9]; euler_R_host(X[3], X[4], X[5], R);
+    float Ri[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (p.map_capacity > 0 || (p.flags & (ICET_NODE_ALIGNED_CLOUD | ICET_NODE_SNAIL_TRAIL))) inverse3_lu(R, Ri);
+    // ---- map queue (simpleMapMaker.cpp:147-158, 34-41) ----
+    if (p.map_capacity > 0) {
+        const int cap = p.map_capacity;
+        const icet_status ds = map_dev(X, Ri, *st.map_pos, m_map); if (ds != ICET_OK) return ds;
+        if (*st.map_pos + m_map >= cap) *st.map_filled = true;
+        *st.map_pos = (*st.map_pos + m_map) % cap;
+    }
+    if (p.flags & ICET_NODE_ALIGNED_CLOUD) { const icet_status ds = align_dev(X, Ri); if (ds != ICET_OK) return ds; }
+    if (p.flags & ICET_NODE_SNAIL_TRAIL) {                        // snailTrail = (snailTrail * rot_mat.inverse()).rowwise() - trans; append the origin
+        std::vector<float>& sn = *st.snail;
+        for (size_t i = 0; i + 2 < sn.size(); i += 3) {
+            const float a = sn[i], b = sn[i + 1], c = sn[i + 2];
+            sn[i] = ((a * Ri[0] + b * Ri[3]) + c * Ri[6]) - X[0];
+            sn[i + 1] = ((a * Ri[1] + b * Ri[4]) + c * Ri[7]) - X[1];
+            sn[i + 2] = ((a * Ri[2] + b * Ri[5]) + c * Ri[8]) - X[2];
+        }
+        sn.insert(sn.end(), {0.f, 0.f, 0.f});
+    }
+    // X_homo = X_homo * X_homo_i (odometry.cpp:91-98)
+    const float Hi[16] = {R[0], R[1], R[2], X[0], R[3], R[4], R[5], X[1], R[6], R[7], R[8], X[2], 0, 0, 0, 1};
+    float P[16];
+    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { float acc = 0.f; for (int k = 0; k < 4; k++) acc += st.pose[r * 4 + k] * Hi[k * 4 + c]; P[r * 4 + c] = acc; }
+    std::memcpy(st.pose, P, sizeof(P));
+    res->solved = 1; res->n_kept = nk;
+    std::memcpy(res->X, X, sizeof(X)); std::memcpy(res->pose, P, sizeof(P)); quat_of(P, res->quat);
+    res->map_rows = *st.map_filled ? p.map_capacity : *st.map_pos;
+    return ICET_OK;
 }
 
 // ---- the one-launch frame (round 6) ----
@@ -624,73 +683,39 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
         NCHK(nd, hipEventSynchronize(nd->ev_f2));
     }
     if (dev_count) { nk = *nd->h_nkept; nd->n_scan[cur] = nk; }   // the filter's count has arrived with everything else
-    float X[6];
-    std::memcpy(X, nd->h_out, sizeof(X)); std::memcpy(res->pred_stds, nd->h_out + 6, sizeof(float) * 6);
-    // seed for the next frame (odometry.cpp:82 / simpleMapMaker.cpp:124), then the guard (simpleMapMaker.cpp:129-137)
-    for (int k = 0; k < 6; k++) nd->X0[k] = nd->p.seed_x0 ? X[k] : 0.f;
-    {
-        // each group is guarded only when ITS threshold is set (0 = off, include/icet_nodes.h): a caller who sets one of the two
-        // must not have the other group compared against 0
-        const float tt = nd->p.trans_thresh, rt = nd->p.rot_thresh;
-        if ((tt > 0.f && (std::fabs(X[0]) > tt || std::fabs(X[1]) > tt || std::fabs(X[2]) > tt)) ||
-            (rt > 0.f && (std::fabs(X[3]) > rt || std::fabs(X[4]) > rt || std::fabs(X[5]) > rt))) {
-            for (int k = 0; k < 6; k++) X[k] = 0.f;
-            res->diverged = 1;
-        }
-    }
-    float R[9]; euler_R_host(X[3], X[4], X[5], R);
-    // ---- map queue (simpleMapMaker.cpp:147-158, 34-41) ----
+    // ---- the tail (frame_tail): guard, map queue, aligned cloud, snail trail, pose ----
     nd->timed_map = false;
-    if (nd->p.map_capacity > 0) {
-        const int m = m_map;
-        float Ri[9]; inverse3_lu(R, Ri);
+    const NodeTail tail{nd->X0, nd->pose, &nd->map_pos, &nd->map_filled, &nd->snail};
+    auto map_dev = [&](const float* X, const float* Ri, int64_t pos, int m) -> icet_status {
         const int cap = nd->p.map_capacity;
         float* q = nd->d_map; const float* sc = nd->d_scan[cur];
         const int blocks = std::min((cap + 255) / 256, 256 * 8);
         if (!fused) NCHK(nd, hipEventRecord(nd->ev[4], st));
-        k_map_add_scan<<<blocks, 256, 0, st>>>(q, q + cap, q + 2 * (size_t)cap, cap, (int)nd->map_pos, m, sc, sc + lcur, sc + 2 * lcur, fused ? nd->h_idx : nd->d_idx,
+        k_map_add_scan<<<blocks, 256, 0, st>>>(q, q + cap, q + 2 * (size_t)cap, cap, (int)pos, m, sc, sc + lcur, sc + 2 * lcur, fused ? nd->h_idx : nd->d_idx,
                                                X[0], X[1], X[2], Ri[0], Ri[1], Ri[2], Ri[3], Ri[4], Ri[5], Ri[6], Ri[7], Ri[8]);
         NCHK(nd, hipGetLastError());
         if (!fused) NCHK(nd, hipEventRecord(nd->ev[3], st));      // not waited for: the next push (or icet_node_map) synchronises the stream
-        if (nd->map_pos + m >= cap) nd->map_filled = true;
-        nd->map_pos = (nd->map_pos + m) % cap;
         nd->timed_map = !fused;
-    }
-    if (nd->p.flags & (ICET_NODE_ALIGNED_CLOUD | ICET_NODE_SNAIL_TRAIL)) {
-        float Ri[9]; inverse3_lu(R, Ri);
-        if (nd->p.flags & ICET_NODE_ALIGNED_CLOUD) {
-            if (lcur > nd->cap_aligned) {
-                NCHK(nd, hipStreamSynchronize(st));
-                if (nd->d_aligned) { NCHK(nd, hipFree(nd->d_aligned)); nd->d_aligned = nullptr; }
-                NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_aligned), sizeof(float) * 3 * (size_t)lcur));
-                nd->cap_aligned = lcur;
-            }
-            const float* sc = nd->d_scan[cur]; float* o = nd->d_aligned; const int64_t la = nd->cap_aligned;
-            if (nk) k_align_cloud<<<(int)std::min<int64_t>((nk + 255) / 256, 2048), 256, 0, st>>>(sc, sc + lcur, sc + 2 * lcur, (int)nk, o, o + la, o + 2 * la, X[0], X[1], X[2],
-                                                                                               Ri[0], Ri[1], Ri[2], Ri[3], Ri[4], Ri[5], Ri[6], Ri[7], Ri[8]);
-            NCHK(nd, hipGetLastError());
-            nd->n_aligned = nk; nd->ld_aligned = la;
+        return ICET_OK;
+    };
+    auto align_dev = [&](const float* X, const float* Ri) -> icet_status {
+        if (lcur > nd->cap_aligned) {
+            NCHK(nd, hipStreamSynchronize(st));
+            if (nd->d_aligned) { NCHK(nd, hipFree(nd->d_aligned)); nd->d_aligned = nullptr; }
+            NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_aligned), sizeof(float) * 3 * (size_t)lcur));
+            nd->cap_aligned = lcur;
         }
-        if (nd->p.flags & ICET_NODE_SNAIL_TRAIL) {               // snailTrail = (snailTrail * rot_mat.inverse()).rowwise() - trans; append the origin
-            for (size_t i = 0; i + 2 < nd->snail.size(); i += 3) {
-                const float a = nd->snail[i], b = nd->snail[i + 1], c = nd->snail[i + 2];
-                nd->snail[i] = ((a * Ri[0] + b * Ri[3]) + c * Ri[6]) - X[0];
-                nd->snail[i + 1] = ((a * Ri[1] + b * Ri[4]) + c * Ri[7]) - X[1];
-                nd->snail[i + 2] = ((a * Ri[2] + b * Ri[5]) + c * Ri[8]) - X[2];
-            }
-            nd->snail.insert(nd->snail.end(), {0.f, 0.f, 0.f});
-        }
-    }
+        const float* sc = nd->d_scan[cur]; float* o = nd->d_aligned; const int64_t la = nd->cap_aligned;
+        if (nk) k_align_cloud<<<(int)std::min<int64_t>((nk + 255) / 256, 2048), 256, 0, st>>>(sc, sc + lcur, sc + 2 * lcur, (int)nk, o, o + la, o + 2 * la, X[0], X[1], X[2],
+                                                                                           Ri[0], Ri[1], Ri[2], Ri[3], Ri[4], Ri[5], Ri[6], Ri[7], Ri[8]);
+        NCHK(nd, hipGetLastError());
+        nd->n_aligned = nk; nd->ld_aligned = la;
+        return ICET_OK;
+    };
+    s = frame_tail(nd->p, tail, nd->h_out, nk, m_map, res, map_dev, align_dev);
+    if (s != ICET_OK) return s;
     nd->prev = cur;                                               // prev_pcl_matrix = pcl_matrix (odometry.cpp:88)
     if (flip_owner) nd->owner ^= 1;                               // ... and the keyframe parked for it becomes the one the next frame registers against
-    // X_homo = X_homo * X_homo_i (odometry.cpp:91-98)
-    const float Hi[16] = {R[0], R[1], R[2], X[0], R[3], R[4], R[5], X[1], R[6], R[7], R[8], X[2], 0, 0, 0, 1};
-    float P[16];
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { float acc = 0.f; for (int k = 0; k < 4; k++) acc += nd->pose[r * 4 + k] * Hi[k * 4 + c]; P[r * 4 + c] = acc; }
-    std::memcpy(nd->pose, P, sizeof(P));
-    res->solved = 1; res->n_kept = nk;
-    std::memcpy(res->X, X, sizeof(X)); std::memcpy(res->pose, P, sizeof(P)); quat_of(P, res->quat);
-    res->map_rows = nd->map_filled ? nd->p.map_capacity : nd->map_pos;
     nd->timing_valid = !fused;
 #ifdef ICET_DIAG_ENV
     if (trace_on && tq[1] > 0) { tq[5] = now_us(); if (++nd->tr_seen > 6) { for (int k = 0; k < 5; k++) nd->tr[k] += tq[k + 1] - tq[k]; nd->tr_n++; } }      // (steady state: the first frames capture their graphs)
@@ -883,6 +908,531 @@ icet_status icet_node_last_timing(icet_node* nd, float out_ms[3]) {
     NCHK(nd, hipEventElapsedTime(&b, nd->pipelined ? nd->ev[5] : nd->ev[1], nd->ev[2]));
     if (nd->timed_map) { NCHK(nd, hipEventSynchronize(nd->ev[3])); NCHK(nd, hipEventElapsedTime(&c, nd->ev[4], nd->ev[3])); }
     out_ms[0] = a; out_ms[1] = b; out_ms[2] = c;
+    return ICET_OK;
+}
+
+}  // extern "C"
+
+// ==================================================================================================================================================================
+// Node groups (include/icet_nodes.h, icet_node_group_*): S independent streams that share one icet_node_params, advanced together.  A frame of one stream needs the
+// previous frame's X, so one stream is bound by the launch chain of its frame (DESIGN.md sections 10-11); a call of the group carries one frame for each of any
+// subset of its streams and pays that chain once:
+//   k_group_count / k_group_scan / k_group_scatter   the range filter of every frame of the call -- ragged: a per-call table (the kernels' argument, no copy
+//                                                    command) gives each frame its source, rows, destination and first block; first frames and
+//                                                    ICET_NODE_NO_RANGE_FILTER streams keep every row (a copy through the same kernels)
+//   icet_keyframe_device_n + icet_register_device_n   ONE keyframe build over the named streams' stored previous scans and ONE Gauss-Newton loop over their
+//                                                    filtered frames (the raw row counts are the launch bounds, the filter's device-side counts the rows)
+//   k_group_map_add_scan                             EigenQueue::add_new_scan of every map-maker stream of the call, one launch (k_map_add_scan's arithmetic)
+//   k_group_align_cloud                              scan2_in_scan1_frame of every stream of the call (k_align_cloud's arithmetic)
+// A pair's result does not depend on the batch it is solved in, so every stream gets the bits of its own icet_node.
+// ==================================================================================================================================================================
+namespace {
+
+constexpr int kGroupMaxFrames = 64;          // frames per filter launch: the table is the kernels' argument (kernarg), ~2.3 KB
+constexpr int kGroupMaxRings = 32;           // rings / clouds per map or aligned-cloud launch, ~2.8 KB of kernarg
+constexpr int kGroupMaxThreads = 16;         // the down-sample draws: this thread and at most 15 helpers, whatever the host's core count
+
+struct GFrame { const float* x; float* o; int32_t n, ld, ldo, keep_all; };      // keep_all: a copy (first frame, ICET_NODE_NO_RANGE_FILTER)
+struct GFilterArgs { int32_t n_frames; float min_range; int32_t blk_off[kGroupMaxFrames + 1]; GFrame f[kGroupMaxFrames]; };
+struct GRing { float* q; const float* s; const int32_t* idx; int32_t pos, m, lds; float t[3]; float ri[9]; };
+struct GMapArgs { int32_t n_rings, cap; GRing r[kGroupMaxRings]; };
+struct GAlign { const float* s; float* o; int32_t n, lds, ldo; float t[3]; float ri[9]; };
+struct GAlignArgs { int32_t n; GAlign a[kGroupMaxRings]; };
+
+// the frame that owns block b: the last k with blk_off[k] <= b (a frame without rows owns no block)
+__device__ __forceinline__ int group_frame_of(const GFilterArgs& a, int b) {
+    int lo = 0, hi = a.n_frames - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.blk_off[mid] <= b) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// pass 1: kept rows per block, blocks of all frames in one grid (the block layout of k_range_count inside each frame)
+__global__ __launch_bounds__(kFB) void k_group_count(const GFilterArgs a, int32_t* __restrict__ counts) {
+    __shared__ int wsum[kFB / 64];
+    const int k = group_frame_of(a, blockIdx.x);
+    const GFrame f = a.f[k];
+    const float* x = f.x; const float* y = f.x + f.ld; const float* z = f.x + 2 * (size_t)f.ld;
+    const int base = (blockIdx.x - a.blk_off[k]) * kFB * kFRows;
+    int c = 0;
+#pragma unroll
+    for (int r = 0; r < kFRows; r++) {
+        const int i = base + r * kFB + threadIdx.x;
+        if (i < f.n) c += (f.keep_all || keep_row(x[i], y[i], z[i], a.min_range)) ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < kFB / 64; w++) t += wsum[w]; counts[blockIdx.x] = t; }
+}
+
+// pass 2: one block per frame: exclusive scan of the frame's block counts; the total is the frame's row count, to the device (the solve's d_rows) and to pinned
+// host memory (a host thread may be watching it: the map maker's down-sample draw)
+__global__ __launch_bounds__(kFB) void k_group_scan(const GFilterArgs a, const int32_t* __restrict__ counts, int32_t* __restrict__ bases, int32_t* __restrict__ rows, int32_t* __restrict__ h_rows) {
+    __shared__ int part[kFB];
+    const int k = blockIdx.x;
+    const int b0 = a.blk_off[k], n_blocks = a.blk_off[k + 1] - b0;
+    const int per = (n_blocks + kFB - 1) / kFB;
+    const int lo = threadIdx.x * per, hi = min(n_blocks, lo + per);
+    int s = 0;
+    for (int i = lo; i < hi; i++) s += counts[b0 + i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < kFB; t++) { const int v = part[t]; part[t] = run; run += v; } rows[k] = run; h_rows[k] = run; __threadfence_system(); }
+    __syncthreads();
+    int run = part[threadIdx.x];
+    for (int i = lo; i < hi; i++) { bases[b0 + i] = run; run += counts[b0 + i]; }
+}
+
+// pass 3: stable scatter (k_range_scatter's row order: k-major inside a block, kept rows in earlier slices, then lower threads of the same slice)
+__global__ __launch_bounds__(kFB) void k_group_scatter(const GFilterArgs a, const int32_t* __restrict__ bases) {
+    __shared__ int wcnt[kFRows][kFB / 64];
+    const int k = group_frame_of(a, blockIdx.x);
+    const GFrame f = a.f[k];
+    const float* x = f.x; const float* y = f.x + f.ld; const float* z = f.x + 2 * (size_t)f.ld;
+    float* ox = f.o; float* oy = f.o + f.ldo; float* oz = f.o + 2 * (size_t)f.ldo;
+    const int base = (blockIdx.x - a.blk_off[k]) * kFB * kFRows;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float vx[kFRows], vy[kFRows], vz[kFRows];
+    bool keep[kFRows];
+    int below[kFRows];
+#pragma unroll
+    for (int r = 0; r < kFRows; r++) {
+        const int i = base + r * kFB + threadIdx.x;
+        keep[r] = false; vx[r] = vy[r] = vz[r] = 0.f;
+        if (i < f.n) { vx[r] = x[i]; vy[r] = y[i]; vz[r] = z[i]; keep[r] = f.keep_all || keep_row(vx[r], vy[r], vz[r], a.min_range); }
+        const unsigned long long m = __ballot(keep[r]);
+        below[r] = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wcnt[r][wave] = __popcll(m);
+    }
+    __syncthreads();
+    int run = bases[blockIdx.x];
+#pragma unroll
+    for (int r = 0; r < kFRows; r++) {
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kFB / 64; w++) { const int cw = wcnt[r][w]; before += (w < wave) ? cw : 0; total += cw; }
+        if (keep[r]) { const int o = run + before + below[r]; ox[o] = vx[r]; oy[o] = vy[r]; oz[o] = vz[r]; }
+        run += total;
+    }
+}
+
+// EigenQueue::add_new_scan of every ring of the call: blockIdx.y picks the ring; per row exactly k_map_add_scan
+__global__ __launch_bounds__(256) void k_group_map_add_scan(const GMapArgs a) {
+    const GRing& g = a.r[blockIdx.y];
+    const int cap = a.cap, pos = g.pos, m = g.m;
+    float* qx = g.q; float* qy = g.q + cap; float* qz = g.q + 2 * (size_t)cap;
+    const float* sx = g.s; const float* sy = g.s + g.lds; const float* sz = g.s + 2 * (size_t)g.lds;
+    const float tx = g.t[0], ty = g.t[1], tz = g.t[2];
+    const float i00 = g.ri[0], i01 = g.ri[1], i02 = g.ri[2], i10 = g.ri[3], i11 = g.ri[4], i12 = g.ri[5], i20 = g.ri[6], i21 = g.ri[7], i22 = g.ri[8];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += gridDim.x * blockDim.x) {
+        int j = i - pos; if (j < 0) j += cap;
+        float a0, b0, c0;
+        if (j < m) { const int r = g.idx[j]; a0 = sx[r]; b0 = sy[r]; c0 = sz[r]; }
+        else { a0 = qx[i]; b0 = qy[i]; c0 = qz[i]; }
+        a0 -= tx; b0 -= ty; c0 -= tz;
+        {
+#pragma clang fp contract(off)
+            qx[i] = (a0 * i00 + b0 * i10) + c0 * i20;
+            qy[i] = (a0 * i01 + b0 * i11) + c0 * i21;
+            qz[i] = (a0 * i02 + b0 * i12) + c0 * i22;
+        }
+    }
+}
+
+// scan2_in_scan1_frame of every cloud of the call: blockIdx.y picks the cloud; per row exactly k_align_cloud
+__global__ __launch_bounds__(256) void k_group_align_cloud(const GAlignArgs a) {
+    const GAlign& g = a.a[blockIdx.y];
+    const float* sx = g.s; const float* sy = g.s + g.lds; const float* sz = g.s + 2 * (size_t)g.lds;
+    float* ox = g.o; float* oy = g.o + g.ldo; float* oz = g.o + 2 * (size_t)g.ldo;
+    const float tx = g.t[0], ty = g.t[1], tz = g.t[2];
+    const float i00 = g.ri[0], i01 = g.ri[1], i02 = g.ri[2], i10 = g.ri[3], i11 = g.ri[4], i12 = g.ri[5], i20 = g.ri[6], i21 = g.ri[7], i22 = g.ri[8];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < g.n; i += gridDim.x * blockDim.x) {
+        const float a0 = sx[i], b0 = sy[i], c0 = sz[i];
+        {
+#pragma clang fp contract(off)
+            ox[i] = ((a0 * i00 + b0 * i10) + c0 * i20) - tx;
+            oy[i] = ((a0 * i01 + b0 * i11) + c0 * i21) - ty;
+            oz[i] = ((a0 * i02 + b0 * i12) + c0 * i22) - tz;
+        }
+    }
+}
+
+// f(0) .. f(n - 1) on the calling thread and up to kGroupMaxThreads - 1 persistent helpers; returns when all have run (the first exception is rethrown here)
+class DrawPool {
+public:
+    ~DrawPool() {
+        { std::lock_guard<std::mutex> lk(m_); stop_ = true; }
+        cv_.notify_all();
+        for (std::thread& t : th_) if (t.joinable()) t.join();
+    }
+    void run(int n, const std::function<void(int)>& f) {
+        if (n <= 0) return;
+        const int want = std::min(n, kGroupMaxThreads) - 1;
+        while ((int)th_.size() < want) th_.emplace_back([this] { loop(); });
+        { std::lock_guard<std::mutex> lk(m_); f_ = &f; n_ = n; next_ = 0; done_ = 0; err_ = nullptr; gen_++; }
+        cv_.notify_all();
+        work();
+        std::exception_ptr e;
+        { std::unique_lock<std::mutex> lk(m_); cv_done_.wait(lk, [&] { return done_ == n_; }); f_ = nullptr; e = err_; err_ = nullptr; }
+        if (e) std::rethrow_exception(e);
+    }
+private:
+    void work() {
+        for (;;) {
+            int i; const std::function<void(int)>* f;
+            { std::lock_guard<std::mutex> lk(m_); if (!f_ || next_ >= n_) return; i = next_++; f = f_; }
+            try { (*f)(i); } catch (...) { std::lock_guard<std::mutex> lk(m_); if (!err_) err_ = std::current_exception(); }
+            bool last; { std::lock_guard<std::mutex> lk(m_); last = ++done_ == n_; }
+            if (last) cv_done_.notify_all();
+        }
+    }
+    void loop() {
+        long seen = 0;
+        for (;;) {
+            { std::unique_lock<std::mutex> lk(m_); cv_.wait(lk, [&] { return stop_ || gen_ != seen; }); if (stop_) return; seen = gen_; }
+            work();
+        }
+    }
+    std::vector<std::thread> th_; std::mutex m_; std::condition_variable cv_, cv_done_;
+    const std::function<void(int)>* f_ = nullptr; int n_ = 0, next_ = 0, done_ = 0; long gen_ = 0; bool stop_ = false; std::exception_ptr err_;
+};
+
+// What an icet_node keeps between frames, per stream of a group (the pipelining state and the timing events stay with the node: the group has none)
+struct GroupStream {
+    bool initialized = false;
+    float* d_scan[2] = {nullptr, nullptr}; int64_t cap_scan[2] = {0, 0}; int64_t n_scan[2] = {0, 0}; int64_t ld_scan[2] = {0, 0};
+    int prev = 0;
+    float X0[6] = {0, 0, 0, 0, 0, 0};
+    float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::mt19937 gen; icet_shuffle::FastMt fgen;                  // default-seeded, one per stream (simpleMapMaker.cpp:258)
+    std::vector<std::size_t> indices;
+    float* d_map = nullptr; int64_t map_pos = 0; bool map_filled = false;
+    int32_t* h_idx = nullptr;                                     // pinned: the map kernel reads the down-sample indices in place
+    float* d_aligned = nullptr; int64_t cap_aligned = 0, n_aligned = 0, ld_aligned = 0;
+    std::vector<float> snail;
+};
+
+}  // namespace
+
+struct icet_node_group {
+    icet_ctx* ctx = nullptr; hipStream_t stream = nullptr; int device = 0;
+    icet_node_params p{};
+    std::string err;
+    int32_t n_streams = 0;
+    bool fast_shuffle = false;
+    std::vector<GroupStream> s;
+    // per-call tables, by position in the call (the solved frames first): row counts on the device and pinned, X0 and results pinned, results on the device (runlen 0)
+    int32_t* d_rows = nullptr; int32_t* h_rows = nullptr; float* h_x0 = nullptr; float* h_out = nullptr; float* d_out = nullptr;
+    int32_t* d_counts = nullptr; int32_t* d_bases = nullptr; int64_t cap_blocks = 0;     // the ragged filter's block counts / bases
+    DrawPool* pool = nullptr;
+};
+
+namespace {
+
+#define GCHK(g, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    (g)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
+
+icet_status group_grow(icet_node_group* g, float*& buf, int64_t& cap, int64_t n) {   // a stream's scan-sized buffer: (n + n / 8) rows rounded to 64, as icet_node
+    if (n <= cap) return ICET_OK;
+    GCHK(g, hipStreamSynchronize(g->stream));                     // everything of this group runs on one stream
+    if (buf) { GCHK(g, hipFree(buf)); buf = nullptr; cap = 0; }
+    const int64_t c = (n + n / 8 + 63) / 64 * 64;
+    GCHK(g, hipMalloc(reinterpret_cast<void**>(&buf), sizeof(float) * 3 * (size_t)c));
+    cap = c;
+    return ICET_OK;
+}
+
+// The first frames of a call are stored and not solved (odometry.cpp:46-52): the result of icet_node's first push
+void group_first_result(const icet_node_group* g, const GroupStream& st, int64_t n, icet_node_result* res) {
+    res->solved = 0; res->n_kept = n;
+    std::memcpy(res->pose, st.pose, sizeof(st.pose)); quat_of(st.pose, res->quat);
+    res->map_rows = st.map_filled ? g->p.map_capacity : st.map_pos;
+}
+
+icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids, const icet_dev_scan* frames, icet_node_result* results) {
+    for (int i = 0; i < n; i++) std::memset(&results[i], 0, sizeof(icet_node_result));
+    hipStream_t hs = g->stream;
+    const icet_node_params& p = g->p;
+    // the call's order: the frames that are solved (their stream has a previous scan) first -- positions 0 .. K-1 of the row counts are the loop's d_rows --, then first frames
+    std::vector<int> order; order.reserve((size_t)n);
+    for (int i = 0; i < n; i++) if (g->s[(size_t)ids[i]].initialized) order.push_back(i);
+    const int K = (int)order.size();
+    for (int i = 0; i < n; i++) if (!g->s[(size_t)ids[i]].initialized) order.push_back(i);
+    // ---- buffers: a solved frame goes to its stream's other buffer, a first frame to the "previous" one ----
+    int64_t total_blocks = 0;
+    for (int j = 0; j < n; j++) {
+        const int i = order[(size_t)j]; GroupStream& st = g->s[(size_t)ids[i]];
+        const int to = j < K ? (st.prev ^ 1) : st.prev;
+        icet_status s = group_grow(g, st.d_scan[to], st.cap_scan[to], frames[i].n); if (s != ICET_OK) return s;
+        if (j < K && (p.flags & ICET_NODE_ALIGNED_CLOUD)) { s = group_grow(g, st.d_aligned, st.cap_aligned, st.cap_scan[to]); if (s != ICET_OK) return s; }
+        total_blocks += (frames[i].n + kFB * kFRows - 1) / (kFB * kFRows);
+    }
+    if (total_blocks > g->cap_blocks) {
+        GCHK(g, hipStreamSynchronize(hs));
+        if (g->d_counts) { GCHK(g, hipFree(g->d_counts)); g->d_counts = nullptr; }
+        if (g->d_bases) { GCHK(g, hipFree(g->d_bases)); g->d_bases = nullptr; }
+        g->cap_blocks = 0;
+        GCHK(g, hipMalloc(reinterpret_cast<void**>(&g->d_counts), sizeof(int32_t) * (size_t)total_blocks));
+        GCHK(g, hipMalloc(reinterpret_cast<void**>(&g->d_bases), sizeof(int32_t) * (size_t)total_blocks));
+        g->cap_blocks = total_blocks;
+    }
+    // ---- the range filter of every frame (odometry.cpp:57-70), kGroupMaxFrames frames per launch triple ----
+    for (int j = 0; j < n; j++) static_cast<volatile int32_t*>(g->h_rows)[j] = -1;                // ("not yet": watched below)
+    int64_t blk0 = 0;
+    for (int j0 = 0; j0 < n; j0 += kGroupMaxFrames) {
+        GFilterArgs a{};
+        a.n_frames = std::min(kGroupMaxFrames, n - j0); a.min_range = p.min_range;
+        int32_t nb = 0;
+        for (int f = 0; f < a.n_frames; f++) {
+            const int j = j0 + f, i = order[(size_t)j]; const GroupStream& st = g->s[(size_t)ids[i]];
+            const int to = j < K ? (st.prev ^ 1) : st.prev;
+            a.blk_off[f] = nb;
+            a.f[f] = GFrame{frames[i].ptr, st.d_scan[to], (int32_t)frames[i].n, (int32_t)frames[i].ld, (int32_t)st.cap_scan[to],
+                            (j >= K || (p.flags & ICET_NODE_NO_RANGE_FILTER)) ? 1 : 0};
+            nb += (int32_t)((frames[i].n + kFB * kFRows - 1) / (kFB * kFRows));
+        }
+        a.blk_off[a.n_frames] = nb;
+        int32_t* counts = g->d_counts + blk0; int32_t* bases = g->d_bases + blk0;
+        if (nb) k_group_count<<<nb, kFB, 0, hs>>>(a, counts);
+        k_group_scan<<<a.n_frames, kFB, 0, hs>>>(a, counts, bases, g->d_rows + j0, g->h_rows + j0);
+        if (nb) k_group_scatter<<<nb, kFB, 0, hs>>>(a, bases);
+        GCHK(g, hipGetLastError());
+        blk0 += nb;
+    }
+    // ---- ONE keyframe build over the stored previous scans, ONE loop over the filtered frames ----
+    icet_params sp = p.solve; sp.flags = (p.flags & ICET_NODE_DOUBLE_W) ? ICET_FLAG_DOUBLE_W : ICET_FLAG_NONE;
+    float* out_dev = sp.runlen > 0 ? g->h_out : g->d_out;        // (the loop stores its results straight into pinned memory; runlen 0 is a copy on the device)
+    if (K > 0) {
+        std::vector<icet_dev_scan> a((size_t)K), b((size_t)K);
+        for (int j = 0; j < K; j++) {
+            const int i = order[(size_t)j]; const GroupStream& st = g->s[(size_t)ids[i]];
+            const int cur = st.prev ^ 1;
+            a[(size_t)j] = icet_dev_scan{st.d_scan[st.prev], st.n_scan[st.prev], st.ld_scan[st.prev]};
+            b[(size_t)j] = icet_dev_scan{st.d_scan[cur], frames[i].n, st.cap_scan[cur]};           // the raw rows: an upper bound; the filter's count is d_rows[j]
+            std::memcpy(g->h_x0 + 6 * (size_t)j, st.X0, sizeof(st.X0));
+        }
+        icet_status s = icet_keyframe_device_n(g->ctx, &sp, K, a.data(), nullptr);
+        if (s == ICET_OK) s = icet_register_device_n(g->ctx, &sp, K, b.data(), g->d_rows, g->h_x0, out_dev);
+        if (s != ICET_OK) { g->err = icet_last_error(g->ctx); return s; }
+        if (out_dev != g->h_out) GCHK(g, hipMemcpyAsync(g->h_out, g->d_out, sizeof(float) * 48 * (size_t)K, hipMemcpyDeviceToHost, hs));
+    }
+    // ---- the map maker's down-sample draws (simpleMapMaker.cpp:147-158), each over exactly its frame's kept rows: the counts land in pinned memory early in the
+    // call, the draws run on the pool while the loop iterates ----
+    std::vector<int> m_map((size_t)K, 0);
+    if (p.map_capacity > 0 && K > 0) {
+        volatile int32_t* hr = g->h_rows;
+        auto arrived = [&]() { for (int j = 0; j < K; j++) if (hr[j] < 0) return false; return true; };
+        for (long spins = 1; !arrived(); spins++)
+            if ((spins & 4095) == 0 && hipStreamQuery(hs) != hipErrorNotReady) break;      // (finished or failed without a count: decided below)
+        (void)hipGetLastError();
+        if (!arrived()) GCHK(g, hipStreamSynchronize(hs));
+        if (!arrived()) { g->err = "the range filter's row counts did not arrive"; return ICET_ERR_HIP; }
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        const bool fast = g->fast_shuffle;
+        g->pool->run(K, [&](int j) {
+            GroupStream& st = g->s[(size_t)ids[order[(size_t)j]]];
+            m_map[(size_t)j] = draw_downsample_into(fast, st.fgen, st.gen, st.indices, p.map_downsample, (int64_t)hr[j], st.h_idx);
+        });
+    }
+    GCHK(g, hipStreamSynchronize(hs));
+    // ---- the tails, stream by stream (frame_tail: the node's own), then the batched map and aligned-cloud launches ----
+    std::vector<GRing> rings; std::vector<GAlign> clouds;
+    for (int j = 0; j < K; j++) {
+        const int i = order[(size_t)j]; GroupStream& st = g->s[(size_t)ids[i]];
+        const int cur = st.prev ^ 1;
+        const int64_t nk = g->h_rows[j];
+        st.n_scan[cur] = nk; st.ld_scan[cur] = st.cap_scan[cur];
+        const NodeTail tail{st.X0, st.pose, &st.map_pos, &st.map_filled, &st.snail};
+        auto map_dev = [&](const float* X, const float* Ri, int64_t pos, int m) -> icet_status {
+            GRing r{st.d_map, st.d_scan[cur], st.h_idx, (int32_t)pos, m, (int32_t)st.cap_scan[cur], {X[0], X[1], X[2]}, {}};
+            std::memcpy(r.ri, Ri, sizeof(r.ri));
+            rings.push_back(r);
+            return ICET_OK;
+        };
+        auto align_dev = [&](const float* X, const float* Ri) -> icet_status {
+            GAlign c{st.d_scan[cur], st.d_aligned, (int32_t)nk, (int32_t)st.cap_scan[cur], (int32_t)st.cap_aligned, {X[0], X[1], X[2]}, {}};
+            std::memcpy(c.ri, Ri, sizeof(c.ri));
+            if (nk) clouds.push_back(c);
+            st.n_aligned = nk; st.ld_aligned = st.cap_aligned;
+            return ICET_OK;
+        };
+        const icet_status s = frame_tail(p, tail, g->h_out + 48 * (size_t)j, nk, m_map[(size_t)j], &results[i], map_dev, align_dev);
+        if (s != ICET_OK) return s;
+        st.prev = cur;                                            // prev_pcl_matrix = pcl_matrix (odometry.cpp:88)
+    }
+    for (int j = K; j < n; j++) {
+        const int i = order[(size_t)j]; GroupStream& st = g->s[(size_t)ids[i]];
+        st.n_scan[st.prev] = frames[i].n; st.ld_scan[st.prev] = st.cap_scan[st.prev];
+        st.initialized = true;
+        group_first_result(g, st, frames[i].n, &results[i]);
+    }
+    for (size_t r0 = 0; r0 < rings.size(); r0 += kGroupMaxRings) {
+        GMapArgs a{}; a.n_rings = (int32_t)std::min<size_t>(kGroupMaxRings, rings.size() - r0); a.cap = p.map_capacity;
+        for (int r = 0; r < a.n_rings; r++) a.r[r] = rings[r0 + (size_t)r];
+        k_group_map_add_scan<<<dim3(std::min((p.map_capacity + 255) / 256, 2048), a.n_rings), 256, 0, hs>>>(a);
+        GCHK(g, hipGetLastError());                               // not waited for: the next call (or an accessor) runs behind it on the same stream
+    }
+    for (size_t c0 = 0; c0 < clouds.size(); c0 += kGroupMaxRings) {
+        GAlignArgs a{}; a.n = (int32_t)std::min<size_t>(kGroupMaxRings, clouds.size() - c0);
+        int64_t most = 0;
+        for (int c = 0; c < a.n; c++) { a.a[c] = clouds[c0 + (size_t)c]; most = std::max<int64_t>(most, a.a[c].n); }
+        k_group_align_cloud<<<dim3((unsigned)std::min<int64_t>((most + 255) / 256, 2048), a.n), 256, 0, hs>>>(a);
+        GCHK(g, hipGetLastError());
+    }
+    return ICET_OK;
+}
+
+// As push_device for one node: no exception crosses the C ABI, and a call that fails after it has started drains the stream and drops every stream it named back to
+// "no previous scan" (their next frame is stored like a first one; the pose chain continues)
+icet_status group_push(icet_node_group* g, int32_t n, const int32_t* ids, const icet_dev_scan* frames, icet_node_result* results) {
+    icet_status s;
+    try {
+        s = group_push_frames(g, n, ids, frames, results);
+    } catch (const std::bad_alloc&) { g->err = "out of host memory"; s = ICET_ERR_NOMEM;
+    } catch (const std::exception& e) { g->err = std::string("host error: ") + e.what(); s = ICET_ERR_NOMEM;
+    } catch (...) { g->err = "host error"; s = ICET_ERR_NOMEM; }
+    if (s != ICET_OK) {
+        (void)hipStreamSynchronize(g->stream);
+        (void)hipGetLastError();
+        for (int i = 0; i < n; i++) g->s[(size_t)ids[i]].initialized = false;
+    }
+    return s;
+}
+
+icet_status group_copy_out(icet_node_group* g, const float* src, int64_t lds, int64_t rows, float* out, int64_t ld) {
+    GCHK(g, hipMemcpy2DAsync(out, ld * sizeof(float), src, lds * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, g->stream));
+    GCHK(g, hipStreamSynchronize(g->stream));
+    return ICET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+icet_status icet_node_group_create(icet_ctx* ctx, const icet_node_params* p, int32_t n_streams, icet_node_group** out) {
+    if (!out) return ICET_ERR_BAD_ARG;
+    *out = nullptr;
+    if (!ctx || !p || n_streams <= 0 || p->map_capacity < 0 || p->map_downsample < 0 || (p->map_capacity > 0 && p->map_downsample > p->map_capacity) ||
+        p->solve.bins_phi <= 0 || p->solve.bins_theta <= 0 || p->solve.n < 1 || p->solve.runlen < 0) return ICET_ERR_BAD_ARG;
+    icet_node_group* g = new (std::nothrow) icet_node_group();
+    if (!g) return ICET_ERR_NOMEM;
+    auto fail = [&](icet_status s) { icet_node_group_destroy(g); return s; };
+    try {
+        g->ctx = ctx; g->p = *p; g->n_streams = n_streams; g->stream = reinterpret_cast<hipStream_t>(icet_stream(ctx)); g->device = icet_device(ctx);
+        g->s.resize((size_t)n_streams);
+        g->pool = new DrawPool();
+    } catch (...) { return fail(ICET_ERR_NOMEM); }
+    if (hipSetDevice(g->device) != hipSuccess) return fail(ICET_ERR_NO_DEVICE);
+    const size_t S = (size_t)n_streams;
+    if (hipMalloc(reinterpret_cast<void**>(&g->d_rows), sizeof(int32_t) * S) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&g->h_rows), sizeof(int32_t) * S, hipHostMallocCoherent) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&g->h_x0), sizeof(float) * 6 * S) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&g->h_out), sizeof(float) * 48 * S, hipHostMallocCoherent) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&g->d_out), sizeof(float) * 48 * S) != hipSuccess)
+        return fail(ICET_ERR_NOMEM);
+    if (p->map_capacity > 0) {
+        static const bool fast_ok = icet_shuffle::matches_std_shuffle() && icet_shuffle::fast_matches_std_shuffle();
+        g->fast_shuffle = fast_ok;
+        const size_t m = p->map_downsample > 0 ? p->map_downsample : 1;
+        for (GroupStream& st : g->s) {
+            if (hipMalloc(reinterpret_cast<void**>(&st.d_map), sizeof(float) * 3 * (size_t)p->map_capacity) != hipSuccess) return fail(ICET_ERR_NOMEM);
+            if (hipMemset(st.d_map, 0, sizeof(float) * 3 * (size_t)p->map_capacity) != hipSuccess) return fail(ICET_ERR_HIP);
+            if (hipHostMalloc(reinterpret_cast<void**>(&st.h_idx), sizeof(int32_t) * m) != hipSuccess) return fail(ICET_ERR_NOMEM);
+        }
+    }
+    if (p->flags & ICET_NODE_SNAIL_TRAIL) for (GroupStream& st : g->s) st.snail.assign(3, 0.f);      // scanMatcher.cpp:27-28: one row at the origin
+    *out = g;
+    return ICET_OK;
+}
+
+icet_status icet_node_group_destroy(icet_node_group* g) {
+    if (!g) return ICET_ERR_BAD_ARG;
+    delete g->pool; g->pool = nullptr;                            // (joins the helpers: none is drawing between calls)
+    (void)hipSetDevice(g->device);
+    (void)hipDeviceSynchronize();                                 // not the borrowed stream: the context may already be gone
+    for (GroupStream& st : g->s) {
+        void* dp[] = {st.d_scan[0], st.d_scan[1], st.d_map, st.d_aligned};
+        for (void* q : dp) if (q) (void)hipFree(q);
+        if (st.h_idx) (void)hipHostFree(st.h_idx);
+    }
+    void* dp[] = {g->d_rows, g->d_out, g->d_counts, g->d_bases};
+    for (void* q : dp) if (q) (void)hipFree(q);
+    void* hp[] = {g->h_rows, g->h_x0, g->h_out};
+    for (void* q : hp) if (q) (void)hipHostFree(q);
+    delete g;
+    return ICET_OK;
+}
+
+const char* icet_node_group_last_error(const icet_node_group* g) { return g ? g->err.c_str() : ""; }
+
+icet_status icet_node_group_push_device(icet_node_group* g, int32_t n, const int32_t* stream_ids, const icet_dev_scan* frames, icet_node_result* results) {
+    // every argument is checked before anything is touched: a refused call leaves every stream as it was
+    if (!g || n < 0 || (n > 0 && (!stream_ids || !frames || !results))) return ICET_ERR_BAD_ARG;
+    if (n == 0) return ICET_OK;
+    if (n > g->n_streams) return ICET_ERR_BAD_ARG;                // (n distinct ids cannot fit otherwise)
+    std::vector<char> seen;
+    try { seen.assign((size_t)g->n_streams, 0); } catch (...) { return ICET_ERR_NOMEM; }
+    for (int i = 0; i < n; i++) {
+        const int32_t id = stream_ids[i];
+        if (id < 0 || id >= g->n_streams || seen[(size_t)id]) return ICET_ERR_BAD_ARG;
+        seen[(size_t)id] = 1;
+        const icet_dev_scan& f = frames[i];
+        if (f.n < 0 || f.ld < f.n || (f.n > 0 && !f.ptr) || f.n >= ((int64_t)1 << 30) || f.ld >= ((int64_t)1 << 30)) return ICET_ERR_BAD_ARG;
+    }
+    if (hipSetDevice(g->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
+    return group_push(g, n, stream_ids, frames, results);
+}
+
+icet_status icet_node_group_map(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
+    if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
+    const GroupStream& st = g->s[(size_t)stream];
+    const int64_t rows = st.map_filled ? g->p.map_capacity : st.map_pos;
+    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
+    *rows_out = rows;
+    if (!out || rows == 0) return ICET_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
+    float* tmp = nullptr;
+    GCHK(g, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(float) * 3 * (size_t)rows));
+    const int cap = g->p.map_capacity;
+    k_map_unroll<<<std::min((int)((rows + 255) / 256), 2048), 256, 0, g->stream>>>(st.d_map, st.d_map + cap, st.d_map + 2 * (size_t)cap, cap, (int)st.map_pos,
+                                                                                    st.map_filled ? 1 : 0, (int)rows, tmp, (int)rows);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy2DAsync(out, ld * sizeof(float), tmp, rows * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    (void)hipFree(tmp);
+    if (e != hipSuccess) { g->err = hipGetErrorString(e); return ICET_ERR_HIP; }
+    return ICET_OK;
+}
+
+icet_status icet_node_group_prev_scan(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
+    if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
+    const GroupStream& st = g->s[(size_t)stream];
+    const int64_t rows = st.initialized ? st.n_scan[st.prev] : 0;
+    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
+    *rows_out = rows;
+    if (!out || rows == 0) return ICET_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
+    return group_copy_out(g, st.d_scan[st.prev], st.ld_scan[st.prev], rows, out, ld);
+}
+
+icet_status icet_node_group_aligned(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
+    if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
+    const GroupStream& st = g->s[(size_t)stream];
+    const int64_t rows = st.n_aligned;
+    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
+    *rows_out = rows;
+    if (!out || rows == 0) return ICET_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
+    return group_copy_out(g, st.d_aligned, st.ld_aligned, rows, out, ld);
+}
+
+icet_status icet_node_group_snail_trail(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
+    if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
+    const std::vector<float>& sn = g->s[(size_t)stream].snail;
+    const int64_t rows = (int64_t)(sn.size() / 3);
+    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
+    *rows_out = rows;
+    if (!out || rows == 0) return ICET_OK;
+    for (int64_t i = 0; i < rows; i++) { out[i] = sn[3 * i]; out[ld + i] = sn[3 * i + 1]; out[2 * ld + i] = sn[3 * i + 2]; }
     return ICET_OK;
 }
 

@@ -505,7 +505,16 @@ __device__ __forceinline__ void gn_solve_body(const int32_t* n_slots, const Slot
     if (lane < 6) X[lane] = stage[kXf + lane];
     if (aux.done_flag) {                                          // a sequential caller watches this word of pinned host memory instead of synchronising the stream: results first, then the word
         __threadfence_system();
-        if (lane == 0) *reinterpret_cast<volatile int32_t*>(aux.done_flag) = 1;
+        // every pair's block gets here once per launch: only the one that arrives LAST raises the word (the others' results are out behind their own system-scope
+        // fences, in front of their arrival), and it resets the counter for the next launch
+        if (lane == 0) {
+            const bool last = !aux.done_count || atomicAdd(aux.done_count, 1u) == (uint32_t)aux.done_pairs - 1u;
+            if (last) {
+                if (aux.done_count) *reinterpret_cast<volatile uint32_t*>(aux.done_count) = 0u;
+                __threadfence_system();
+                *reinterpret_cast<volatile int32_t*>(aux.done_flag) = 1;
+            }
+        }
     }
     if (lane == 0) {
         if (aux.x_hist) for (int k = 0; k < 6; k++) aux.x_hist[((size_t)pair * runlen + iter) * 6 + k] = Xn[k];

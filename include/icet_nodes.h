@@ -105,6 +105,35 @@ icet_status icet_node_snail_trail(icet_node* node, float* out, int64_t ld, int64
  * one-launch odometry frame (range filter on, no map, no aligned cloud / snail trail, pipelined) unless the node has ICET_NODE_TIME_PHASES. */
 icet_status icet_node_last_timing(icet_node* node, float out_ms[3]);
 
+/* --- node groups: many lidar streams advanced in one call -------------------------------------------------------------------------------------------------
+ * A frame of one stream needs the previous frame's X, so one stream cannot go faster than the launch chain of its frame; a vehicle with several lidars, a server
+ * with several vehicles or an offline run over many drives has many streams.  A group holds n_streams independent nodes that share one icet_node_params, and one
+ * call advances any subset of them: one range filter launch over all frames of the call, ONE keyframe build and ONE Gauss-Newton loop over their pairs, one map
+ * launch over their rings.  Every stream behaves exactly like its own icet_node created with the same parameters and fed the same frames in the same order -- the
+ * same bits in every field of icet_node_result and in the map, previous scan, aligned cloud and snail trail (first frame stored unfiltered, X0 seeding, guard,
+ * pose chain, its own default-seeded mt19937, map ring wrap-around, empty frames).  The scheduling flags ICET_NODE_NO_PIPELINE, _SERIAL_ENQUEUE and _TIME_PHASES
+ * never change bits; the group accepts and ignores them.  Streams with different parameters need groups of their own. */
+typedef struct icet_node_group icet_node_group;   /* opaque: n_streams nodes' state, the per-call tables */
+
+/* n_streams >= 1 streams, each in the state of a freshly created icet_node.  Borrows `ctx` like icet_node_create (its device, stream and workspace: a keyframe
+ * parked there is overwritten by the group's next call); destroy the group before the context. */
+icet_status icet_node_group_create(icet_ctx* ctx, const icet_node_params* p, int32_t n_streams, icet_node_group** out);
+icet_status icet_node_group_destroy(icet_node_group* g);
+const char* icet_node_group_last_error(const icet_node_group* g);
+
+/* One frame for each of n streams: stream_ids[i] (HOST array; distinct, any order, 0 <= id < n_streams) receives frames[i] (DEVICE pointers, layout of
+ * icet_dev_scan; each buffer may be reused once the call returns); results[i] belongs to frames[i].  Returns when every result is on the host.  Streams the call
+ * does not name are left untouched, so sensors that are not synchronised work.  ICET_ERR_BAD_ARG -- checked before anything is touched, so that a refused call
+ * leaves every stream as it was -- for a duplicate or out-of-range id, n < 0, frames[i].n < 0 or ld < n (or either >= 2^30), a NULL pointer with n > 0.  A call that fails after
+ * it has started drops every stream it named back to "no previous scan" (as icet_node_push_device does for one node); the pose chains continue. */
+icet_status icet_node_group_push_device(icet_node_group* g, int32_t n, const int32_t* stream_ids, const icet_dev_scan* frames, icet_node_result* results);
+
+/* The per-stream forms of icet_node_map / _prev_scan / _aligned / _snail_trail (ICET_ERR_BAD_ARG for a stream out of range). */
+icet_status icet_node_group_map(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows);
+icet_status icet_node_group_prev_scan(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows);
+icet_status icet_node_group_aligned(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows);
+icet_status icet_node_group_snail_trail(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,50 @@ private:
     icet_node* node_ = nullptr;
 };
 
+// Many lidar streams with one set of settings (icet_node_group_*): a vehicle with several lidars, a server with several vehicles.  One call advances any subset
+// of the streams; stream k behaves exactly like its own LidarNode fed the same frames.
+class NodeGroup {
+public:
+    NodeGroup(const icet_node_params& p, int32_t n_streams, int device = 0) {
+        icet_ctx* ctx = thread_context(device, &status);
+        if (!ctx) { error = "icet_create failed (no usable HIP device; this path has no CPU fallback)"; return; }
+        status = icet_node_group_create(ctx, &p, n_streams, &group_);
+        if (status != ICET_OK) error = "icet_node_group_create failed";
+        else n_streams_ = n_streams;
+    }
+    ~NodeGroup() { if (group_) icet_node_group_destroy(group_); }
+    NodeGroup(const NodeGroup&) = delete;
+    NodeGroup& operator=(const NodeGroup&) = delete;
+
+    int32_t streams() const { return n_streams_; }
+    // frames[i] (device pointers) goes to stream stream_ids[i] (distinct); results[i] belongs to frames[i].  Returns false on failure (status, error).
+    bool pushDevice(const std::vector<int32_t>& stream_ids, const std::vector<icet_dev_scan>& frames, std::vector<icet_node_result>& results) {
+        results.assign(frames.size(), icet_node_result{});
+        if (!group_ || stream_ids.size() != frames.size()) { status = ICET_ERR_BAD_ARG; return false; }
+        status = icet_node_group_push_device(group_, (int32_t)frames.size(), stream_ids.data(), frames.data(), results.data());
+        if (status != ICET_OK) { error = std::string("icet_node_group_push_device failed: ") + icet_node_group_last_error(group_); return false; }
+        return true;
+    }
+    // stream's EigenQueue::getQueue() / prev_pcl_matrix: rows x 3 column-major
+    std::vector<float> mapPC(int32_t stream, int64_t* rows) { return copy(icet_node_group_map, stream, rows); }
+    std::vector<float> prevScan(int32_t stream, int64_t* rows) { return copy(icet_node_group_prev_scan, stream, rows); }
+    icet_status status = ICET_OK;
+    std::string error;
+
+private:
+    std::vector<float> copy(icet_status (*fn)(icet_node_group*, int32_t, float*, int64_t, int64_t*), int32_t stream, int64_t* rows) {
+        int64_t r = 0; std::vector<float> out;
+        if (!group_ || fn(group_, stream, nullptr, 0, &r) != ICET_OK) { if (rows) *rows = 0; return out; }
+        out.assign((size_t)3 * (r > 0 ? r : 1), 0.f);
+        if (r) status = fn(group_, stream, out.data(), r, &r);
+        out.resize((size_t)3 * r);
+        if (rows) *rows = r;
+        return out;
+    }
+    icet_node_group* group_ = nullptr;
+    int32_t n_streams_ = 0;
+};
+
 // odometry_node's settings: src/odometry.cpp:58 (minD = 2), :73-76 (7, 24, 75), :82 (X0 <- X)
 struct OdometryNode : LidarNode {
     explicit OdometryNode(int device = 0) : LidarNode(icet_node_params{{7, 24, 75, 25, 0.1f, 0.1f, ICET_FLAG_NONE}, 2.0f, 1, 0.f, 0.f, 0, 0, 0}, device) {}
