@@ -26,7 +26,7 @@ FLAG_HALF_GAP_BOUNDS = 8  # non-parity extension (half-gap cluster buffers of th
 
 # every symbol include/icet_hip.h, include/icet_nodes.h and include/icet_io.h declare
 EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_version", "icet_solve", "icet_solve_begin", "icet_solve_keyframe_tables", "icet_solve_end", "icet_solve_batch",
-                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
+                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device", "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
                     "icet_node_prev_scan", "icet_node_aligned", "icet_node_snail_trail", "icet_node_last_timing", "icet_stream", "icet_device",
@@ -45,6 +45,17 @@ class IcetError(RuntimeError):
 class Params(C.Structure):
     _fields_ = [("runlen", C.c_int32), ("bins_phi", C.c_int32), ("bins_theta", C.c_int32), ("n", C.c_int32),
                 ("thresh", C.c_float), ("buff", C.c_float), ("flags", C.c_int32)]
+
+
+# icet_score (include/icet_hip.h): the registration score, 32 bytes
+SCORE_DTYPE = np.dtype([("chi2", "<f4"), ("chi2_per_voxel", "<f4"), ("voxels", "<i4"), ("points_in", "<i4"), ("points", "<i4"), ("overlap", "<f4"),
+                        ("reserved", "<i4", (2,))])
+assert SCORE_DTYPE.itemsize == 32
+
+
+def scores_as_dict(rec):
+    """An icet_score array (SCORE_DTYPE) as named arrays: chi2, chi2_per_voxel, voxels, points_in, points, overlap."""
+    return {k: np.array(rec[k]) for k in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")}
 
 
 class NodeParams(C.Structure):
@@ -113,6 +124,11 @@ def load_library():
     L.icet_register_indexed_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
     L.icet_solve_indexed.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_score_indexed_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
+    L.icet_register_indexed_scored_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_solve_indexed_scored.argtypes = L.icet_solve_indexed.argtypes + [C.c_void_p]
+    L.icet_score_indexed.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_select_best_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
     L.icet_multi_destroy.argtypes = [C.c_void_p]
     L.icet_multi_last_error.argtypes = [C.c_void_p]; L.icet_multi_last_error.restype = C.c_char_p
@@ -161,6 +177,25 @@ def _colmajor(scan):
     if a.ndim != 2 or a.shape[1] != 3:
         raise IcetError(ICET_ERR_BAD_ARG, "scan must be N x 3")
     return np.ascontiguousarray(a.T)
+
+
+def select_best(score, group, n_groups):
+    """The rule of icet_select_best_device on the host (include/icet_hip.h): per group, among the registrations whose voxels reach
+    max(1, ceil(0.5 x the group's largest)), the lowest chi2_per_voxel (NaN last), ties to the lowest index; -1 when none is eligible.
+    ``score``: a dict of arrays or a SCORE_DTYPE array."""
+    vox = np.asarray(score["voxels"]).astype(np.int64); cpv = np.asarray(score["chi2_per_voxel"], np.float32)
+    group = np.asarray(group).reshape(-1)
+    best = np.full(int(n_groups), -1, np.int32)
+    for g in range(int(n_groups)):
+        mem = np.nonzero(group == g)[0]
+        if mem.size == 0:
+            continue
+        need = max(1, (int(vox[mem].max()) + 1) // 2)
+        el = [r for r in mem if vox[r] >= need]
+        if el:
+            key = [(np.inf if np.isnan(cpv[r]) else float(cpv[r]), int(r)) for r in el]
+            best[g] = min(key)[1]
+    return best
 
 
 class Context:
@@ -243,6 +278,36 @@ class Context:
         B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
         self._check(load_library().icet_register_indexed_device(self._h, C.byref(params), k, idx.ctypes.data, B,
                                                                 C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr)))
+
+    def register_indexed_scored_device(self, kf_index, scan2_descs, params, d_out_ptr, d_score_ptr, d_x0_ptr=None):
+        """register_indexed_device followed by the score at every final X (icet_register_indexed_scored_device): d_out carries the bits of the unscored
+        call; d_score_ptr: device pointer to len(scan2_descs) icet_score records (32 bytes each, SCORE_DTYPE)."""
+        k = len(scan2_descs)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
+        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        self._check(load_library().icet_register_indexed_scored_device(self._h, C.byref(params), k, idx.ctypes.data, B,
+                                                                       C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr), C.c_void_p(d_score_ptr)))
+
+    def score_indexed_device(self, kf_index, scan2_descs, params, d_X_ptr, d_score_ptr):
+        """The score of scan 2 r at pose d_X[r] (device, len x 6 float32) against parked keyframe kf_index[r] (icet_score_indexed_device): no
+        iteration; d_score_ptr: device pointer to len(scan2_descs) icet_score records."""
+        k = len(scan2_descs)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
+        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        self._check(load_library().icet_score_indexed_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_score_ptr)))
+
+    def select_best_device(self, group, n_groups, d_score_ptr, d_best_ptr, d_out_ptr=None, d_best_out_ptr=None):
+        """The best registration of every group on the device (icet_select_best_device; the rule is in include/icet_hip.h): group[r] = the group of
+        registration r (host, any order); d_best_ptr: device int32 x n_groups (-1: no eligible registration); d_best_out_ptr (optional): device
+        n_groups x 48 floats, the winner's row of d_out_ptr."""
+        g = np.ascontiguousarray(np.asarray(group, np.int32).reshape(-1))
+        self._check(load_library().icet_select_best_device(self._h, g.shape[0], g.ctypes.data, int(n_groups), C.c_void_p(d_score_ptr),
+                                                           C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(d_best_ptr),
+                                                           C.c_void_p(d_best_out_ptr) if d_best_out_ptr else None))
 
     def set_option(self, name, value):
         """Launch-shape / diagnostic knob of this context (icet_set_option, include/icet_hip.h).  Launch-shape knobs leave the result
@@ -351,6 +416,61 @@ class Context:
                                                x0.ctypes.data if x0 is not None else None, X.ctypes.data, ps.ctypes.data, cov.ctypes.data)
         self._check(st)
         return dict(X=X, pred_stds=ps, cov=cov.reshape(k, 6, 6))
+
+    def solve_indexed_scored(self, scans1, scans2, kf_index, runlen, X0=None, num_bins_phi=24, num_bins_theta=75, n=25, thresh=0.1, buff=0.1, flags=0):
+        """icet_solve_indexed_scored: what solve_indexed returns plus ``score``, a dict of arrays (chi2, chi2_per_voxel, voxels, points_in, points,
+        overlap) with the score of every registration at its final X."""
+        k = len(scans2)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scans2 differ in length")
+        p = Params(int(runlen), int(num_bins_phi), int(num_bins_theta), int(n), float(thresh), float(buff), int(flags))
+        s1 = [_colmajor(s) for s in scans1]; s2 = [_colmajor(s) for s in scans2]
+        a1 = (C.c_void_p * max(len(s1), 1))(*[s.ctypes.data for s in s1]); a2 = (C.c_void_p * max(k, 1))(*[s.ctypes.data for s in s2])
+        n1 = np.array([s.shape[1] for s in s1], np.int64); n2 = np.array([s.shape[1] for s in s2], np.int64)
+        x0 = None if X0 is None else np.ascontiguousarray(np.asarray(X0, np.float32).reshape(k, 6))
+        X = np.zeros((k, 6), np.float32); ps = np.zeros((k, 6), np.float32); cov = np.zeros((k, 36), np.float32)
+        sc = np.zeros(k, SCORE_DTYPE)
+        st = load_library().icet_solve_indexed_scored(self._h, C.byref(p), len(s1), a1, n1.ctypes.data, k, idx.ctypes.data, a2, n2.ctypes.data,
+                                                      x0.ctypes.data if x0 is not None else None, X.ctypes.data, ps.ctypes.data, cov.ctypes.data, sc.ctypes.data)
+        self._check(st)
+        return dict(X=X, pred_stds=ps, cov=cov.reshape(k, 6, 6), score=scores_as_dict(sc))
+
+    def score_indexed(self, scans1, scans2, kf_index, X, num_bins_phi=24, num_bins_theta=75, n=25, thresh=0.1, buff=0.1, flags=0, runlen=0):
+        """icet_score_indexed: the score of scans2[r] at pose X[r] against scans1[kf_index[r]] (no iteration; ``runlen`` only places the moving-voxel
+        gate of FLAG_REJECT_MOVING).  The keyframes stay parked.  Returns a dict of arrays like solve_indexed_scored's ``score``."""
+        k = len(scans2)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scans2 differ in length")
+        x = np.ascontiguousarray(np.asarray(X, np.float32))
+        if x.size != 6 * k:
+            raise IcetError(ICET_ERR_BAD_ARG, "X must hold 6 floats per registration")
+        p = Params(int(runlen), int(num_bins_phi), int(num_bins_theta), int(n), float(thresh), float(buff), int(flags))
+        s1 = [_colmajor(s) for s in scans1]; s2 = [_colmajor(s) for s in scans2]
+        a1 = (C.c_void_p * max(len(s1), 1))(*[s.ctypes.data for s in s1]); a2 = (C.c_void_p * max(k, 1))(*[s.ctypes.data for s in s2])
+        n1 = np.array([s.shape[1] for s in s1], np.int64); n2 = np.array([s.shape[1] for s in s2], np.int64)
+        sc = np.zeros(k, SCORE_DTYPE)
+        st = load_library().icet_score_indexed(self._h, C.byref(p), len(s1), a1, n1.ctypes.data, k, idx.ctypes.data, a2, n2.ctypes.data,
+                                               x.ctypes.data, sc.ctypes.data)
+        self._check(st)
+        return scores_as_dict(sc)
+
+    def solve_multistart(self, scan1, scan2, starts, runlen, num_bins_phi=24, num_bins_theta=75, n=25, thresh=0.1, buff=0.1, flags=0):
+        """One pair from several starts (``starts``: k x 6 X0), each solved and scored against the one keyframe of scan1; the start chosen by the rule of
+        icet_select_best_device (include/icet_hip.h).  Returns dict(best, X, pred_stds, cov, score, X_all): ``best`` is the chosen start's index
+        (-1 when no start has a contributing voxel: X, pred_stds and cov are then None), ``score`` every start's score (named arrays), X_all every final X."""
+        x0 = np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
+        k = x0.shape[0]
+        res = self.solve_indexed_scored([scan1], [scan2] * k, [0] * k, runlen, X0=x0, num_bins_phi=num_bins_phi, num_bins_theta=num_bins_theta,
+                                        n=n, thresh=thresh, buff=buff, flags=flags)
+        best = select_best(res["score"], np.zeros(k, np.int32), 1)[0]
+        out = dict(best=int(best), score=res["score"], X_all=res["X"])
+        if best < 0:
+            out.update(X=None, pred_stds=None, cov=None)
+        else:
+            out.update(X=res["X"][best].copy(), pred_stds=res["pred_stds"][best].copy(), cov=res["cov"][best].copy())
+        return out
 
     # -- batch, device-resident (raw device pointers; torch is only the allocator in callers) ---------
     def solve_batch_device(self, scan1_descs, scan2_descs, params, d_out_ptr, d_x0_ptr=None):

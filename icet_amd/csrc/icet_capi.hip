@@ -48,6 +48,9 @@ struct icet_ctx {
     uint32_t* d_pack = nullptr; uint32_t* h_pack = nullptr; size_t cap_pack = 0;
     float* h_pts2 = nullptr; float* d_pts2 = nullptr; size_t cap_pts2 = 0;   // `points2` (scan 2 under the last iteration's transform): device buffer + pinned host copy
     float* h_x0 = nullptr;                                       // pinned, 6 x cap_out_pairs
+    icet_score* d_score = nullptr; icet_score* h_score = nullptr; int32_t cap_score = 0;     // scores of the host-pointer entry points (device + pinned)
+    int32_t* d_sel = nullptr; int32_t* h_sel = nullptr; int64_t cap_sel = 0;                // icet_select_best_device: the groups' members | offsets (device + pinned staging)
+    hipEvent_t ev_sel = nullptr; bool sel_in_flight = false;                                 // the copy out of h_sel
     float* d_sph1 = nullptr; int32_t* d_idx1 = nullptr; size_t cap_side1 = 0;      // points1Spherical / pointIndices1 on request (icet_sidetables.hip)
     float* d_sph2 = nullptr; int32_t* d_vox2 = nullptr; size_t cap_side2 = 0;      // points2Spherical / the rows' voxels on request
     // host-pointer entry points: scan 2 is uploaded on a stream of its own, beside the keyframe build of scan 1
@@ -75,6 +78,7 @@ struct icet_ctx {
     struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false; };
     bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
     GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
+    GraphSlot g_scored, g_score;                               // indexed registrations + score (icet_register_indexed_scored_device), the score of given poses (icet_score_indexed_device)
     hipEvent_t ev_graph = nullptr; bool graph_in_flight = false;
     // A caller inside this library (the sequential nodes, icet_nodes.hip) can put work of its own at the head of the NEXT icet_register_device_n call's launch
     // sequence -- enqueued on the context's stream right before the loop's first kernel, captured into the same graph: the range filter and the loop of a frame
@@ -623,7 +627,10 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
 // The Gauss-Newton loop of n_regs INDEXED registrations (icet_register_indexed_device) against the parked keyframe: descriptors in c->h_desc_reg, keyframe of
 // registration r in c->h_kf_of[r].  The registration-side tables (acc, xf, X, overflow counts, tickets) are indexed by r, the keyframe tables by h_kf_of[r]
 // (LaunchCfg::kf_of).  The plain point pass and solve: no fused launch, no keep list.
-icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out) {
+// d_score != nullptr: one more point pass at the final transform records and the score (icet_score.hip) behind the loop; `iters` (default runlen): 0 scores the
+// poses d_x0 without iterating.
+icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1) {
+    if (iters < 0) iters = p->runlen;
     Workspace& w = c->w;
     LaunchCfg cfg = make_cfg(c, p, n_regs, c->h_desc_reg, nullptr);
     cfg.pair_user = nullptr; cfg.done_flag = nullptr; cfg.keep = 0; cfg.fuse_solve = 0; cfg.kf_of = w.kf_of;
@@ -650,11 +657,15 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
         HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
     }
     const bool per_iter = (p->flags & ICET_FLAG_TIMING) != 0;
-    for (int it = 0; it < p->runlen; it++) {
+    for (int it = 0; it < iters; it++) {
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it], c->stream));
         HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it + 1], c->stream));
         HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, nullptr, c->stream));
+    }
+    if (d_score) {                                                          // the last solve (or k_init_state) left the transform record of the pose to score in w.xf
+        HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
+        HIPCHK(c, launch_gn_score(wl, lcfg, p->runlen, d_score, c->stream));
     }
     if (!c->capturing) { HIPCHK(c, hipEventRecord(c->ev_c, c->stream)); c->timing_valid = true; c->last_iters = per_iter ? p->runlen : 0; }
     return ICET_OK;
@@ -736,6 +747,11 @@ icet_status icet_destroy(icet_ctx* c) {
     if (c->d_pts2) (void)hipFree(c->d_pts2);
     for (void* q : {(void*)c->d_sph1, (void*)c->d_idx1, (void*)c->d_sph2, (void*)c->d_vox2}) if (q) (void)hipFree(q);
     if (c->h_x0) (void)hipHostFree(c->h_x0);
+    if (c->d_score) (void)hipFree(c->d_score);
+    if (c->h_score) (void)hipHostFree(c->h_score);
+    if (c->d_sel) (void)hipFree(c->d_sel);
+    if (c->h_sel) (void)hipHostFree(c->h_sel);
+    if (c->ev_sel) (void)hipEventDestroy(c->ev_sel);
     if (c->h_sync_word) (void)hipHostFree(c->h_sync_word);
     for (hipEvent_t e : {c->ev_s2, c->ev_kf, c->ev_kfd, c->ev_prev, c->ev_pts2}) if (e) (void)hipEventDestroy(e);
     if (c->st_copy) (void)hipStreamDestroy(c->st_copy);
@@ -752,7 +768,7 @@ icet_status icet_destroy(icet_ctx* c) {
     for (icet_ctx* h : c->helpers) (void)icet_destroy(h);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_desc) (void)hipEventDestroy(c->ev_desc);
-    for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop, &c->g_indexed}) if (g->have_graph) { (void)hipGraphExecDestroy(g->exec); (void)hipGraphDestroy(g->graph); }
+    for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop, &c->g_indexed, &c->g_scored, &c->g_score}) if (g->have_graph) { (void)hipGraphExecDestroy(g->exec); (void)hipGraphDestroy(g->graph); }
     if (c->ev_graph) (void)hipEventDestroy(c->ev_graph);
     if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
@@ -1080,9 +1096,14 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     return enq();
 }
 
-icet_status icet_register_indexed_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out) {
+// The indexed registrations of icet_register_indexed_device (mode kIdxRegister), the same followed by the score (kIdxScored: d_score), or the score of the poses
+// d_x0 alone (kIdxScoreOnly: no iteration, d_out unused).
+enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2 };
+static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
+                                    icet_score* d_score, IndexedMode mode) {
     if (!c) return ICET_ERR_BAD_ARG;
-    if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || !d_out))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    const bool need_out = mode != kIdxScoreOnly, need_score = mode != kIdxRegister;
+    if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (mode == kIdxScoreOnly && !d_x0)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n_regs == 0) return ICET_OK;
     // everything is checked before anything is touched: a refused call leaves the parked keyframe as it was
     const icet_params& q = c->kf_params;
@@ -1098,7 +1119,7 @@ icet_status icet_register_indexed_device(icet_ctx* c, const icet_params* p, int3
     if (c->tune.keep != 0) { c->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
     HIPCHK(c, hipSetDevice(c->device));
     c->armed_calls = 2;
-    if (p->runlen == 0) return write_runlen0(c, n_regs, d_x0, d_out);
+    if (mode == kIdxRegister && p->runlen == 0) return write_runlen0(c, n_regs, d_x0, d_out);
     icet_status s = ensure_regs(c, n_regs, p->bins_phi * p->bins_theta);   // the registration side only: the keyframe tables stay where they are
     if (s == ICET_OK) s = ensure_scan2(c, tot2);
     if (s == ICET_OK) s = ensure_thresholds(c, p->bins_theta, p->bins_phi);
@@ -1113,17 +1134,60 @@ icet_status icet_register_indexed_device(icet_ctx* c, const icet_params* p, int3
         c->h_kf_of[r] = kf_index[r];
     }
     c->h_kf_of[n_regs] = 0;
-    auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out); };
-    // a replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved)
-    if (graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg), enq);
+    if (mode == kIdxRegister) {
+        auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out); };
+        // a replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved)
+        if (graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg), enq);
+        return enq();
+    }
+    // scored calls: runlen == 0 scores X0 (results as the unscored call writes them); score-only calls score d_x0 without iterating
+    const bool no_iters = mode == kIdxScoreOnly || p->runlen == 0;
+    auto enq = [&]() -> icet_status {
+        if (mode == kIdxScored && p->runlen == 0) { const icet_status ws = write_runlen0(c, n_regs, d_x0, d_out); if (ws != ICET_OK) return ws; }
+        return enqueue_indexed(c, p, n_regs, d_x0, d_out, d_score, no_iters ? 0 : p->runlen);
+    };
+    if (graph_eligible(c, p, n_regs)) {
+        // slots and keys of their own: a scored call never replays an unscored call's graph, nor the reverse (the mode is a bit of the key as well)
+        const intptr_t tag = (intptr_t)c->ws_gen | ((intptr_t)mode << 56);
+        return run_or_replay(c, mode == kIdxScored ? c->g_scored : c->g_score,
+                             graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>(tag), d_score, c->h_desc_reg), enq);
+    }
     return enq();
 }
 
-icet_status icet_solve_indexed(icet_ctx* c, const icet_params* p, int32_t n_kf, const float* const* scan1, const int64_t* n1,
-                               int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
-                               const float* x0, float* x_out, float* pred_stds_out, float* cov_out) {
+icet_status icet_register_indexed_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out) {
+    return register_indexed(c, p, n_regs, kf_index, scan2, d_x0, d_out, nullptr, kIdxRegister);
+}
+
+icet_status icet_register_indexed_scored_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
+                                                const float* d_x0, float* d_out, icet_score* d_score) {
+    return register_indexed(c, p, n_regs, kf_index, scan2, d_x0, d_out, d_score, kIdxScored);
+}
+
+icet_status icet_score_indexed_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
+                                      const float* d_X, icet_score* d_score) {
+    return register_indexed(c, p, n_regs, kf_index, scan2, d_X, nullptr, d_score, kIdxScoreOnly);
+}
+
+// Scores of the host-pointer entry points: device + pinned, n entries.
+static icet_status ensure_score(icet_ctx* c, int32_t n) {
+    if (n <= c->cap_score) return ICET_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, dev_realloc(c->d_score, (size_t)n));
+    if (c->h_score) { HIPCHK(c, hipHostFree(c->h_score)); c->h_score = nullptr; }
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_score), sizeof(icet_score) * (size_t)n));
+    c->cap_score = n;
+    return ICET_OK;
+}
+
+// icet_solve_indexed (score_out == nullptr), icet_solve_indexed_scored (mode kIdxScored) and icet_score_indexed (kIdxScoreOnly: x0 = the poses, no results but the scores).
+static icet_status solve_indexed_host(icet_ctx* c, const icet_params* p, int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                                      int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                                      const float* x0, float* x_out, float* pred_stds_out, float* cov_out, icet_score* score_out, IndexedMode mode) {
     if (!c) return ICET_ERR_BAD_ARG;
-    if (!params_ok(p) || n_kf < 1 || n_regs < 0 || !scan1 || !n1 || (n_regs > 0 && (!kf_index || !scan2 || !n2 || !x_out || !pred_stds_out))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    const bool need_out = mode != kIdxScoreOnly;
+    if (!params_ok(p) || n_kf < 1 || n_regs < 0 || !scan1 || !n1 || (n_regs > 0 && (!kf_index || !scan2 || !n2 || (need_out && (!x_out || !pred_stds_out)) ||
+                                                                                     (mode != kIdxRegister && !score_out) || (mode == kIdxScoreOnly && !x0)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (c->pend.active) { c->err = "icet_solve_begin without icet_solve_end on this context"; return ICET_ERR_BAD_ARG; }
     int64_t tot1 = 0, tot2 = 0;
     for (int k = 0; k < n_kf; k++) {
@@ -1139,6 +1203,7 @@ icet_status icet_solve_indexed(icet_ctx* c, const icet_params* p, int32_t n_kf, 
     HIPCHK(c, hipSetDevice(c->device));
     icet_status s = ensure_out(c, n_regs);
     if (s == ICET_OK) s = ensure_stage(c, tot1, tot2);
+    if (s == ICET_OK && mode != kIdxRegister) s = ensure_score(c, n_regs);
     if (s != ICET_OK) return s;
     // scans into the staging buffers (dense column-major), then the two device halves
     std::vector<icet_dev_scan> d1((size_t)n_kf), d2((size_t)n_regs);
@@ -1159,16 +1224,68 @@ icet_status icet_solve_indexed(icet_ctx* c, const icet_params* p, int32_t n_kf, 
     const float* dx0 = nullptr;
     if (x0) { std::memcpy(c->h_x0, x0, sizeof(float) * 6 * n_regs); HIPCHK(c, hipMemcpyAsync(c->d_x0, c->h_x0, sizeof(float) * 6 * n_regs, hipMemcpyHostToDevice, c->stream)); dx0 = c->d_x0; }
     s = icet_keyframe_device(c, p, n_kf, d1.data());
-    if (s == ICET_OK) s = icet_register_indexed_device(c, p, n_regs, kf_index, d2.data(), dx0, c->d_out);
+    if (s == ICET_OK) s = register_indexed(c, p, n_regs, kf_index, d2.data(), dx0, need_out ? c->d_out : nullptr, mode != kIdxRegister ? c->d_score : nullptr, mode);
     if (s != ICET_OK) { (void)hipStreamSynchronize(c->stream); return s; }
-    HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(float) * 48 * n_regs, hipMemcpyDeviceToHost, c->stream));
+    if (need_out) HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(float) * 48 * n_regs, hipMemcpyDeviceToHost, c->stream));
+    if (mode != kIdxRegister) HIPCHK(c, hipMemcpyAsync(c->h_score, c->d_score, sizeof(icet_score) * n_regs, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->armed_calls = 0; c->desc_in_flight = false; c->graph_in_flight = false;
-    for (int r = 0; r < n_regs; r++) {
+    for (int r = 0; r < n_regs && need_out; r++) {
         std::memcpy(x_out + 6 * r, c->h_out + 48 * r, 6 * sizeof(float));
         std::memcpy(pred_stds_out + 6 * r, c->h_out + 48 * r + 6, 6 * sizeof(float));
         if (cov_out) std::memcpy(cov_out + 36 * r, c->h_out + 48 * r + 12, 36 * sizeof(float));
     }
+    if (mode != kIdxRegister) std::memcpy(score_out, c->h_score, sizeof(icet_score) * n_regs);
+    return ICET_OK;
+}
+
+icet_status icet_solve_indexed(icet_ctx* c, const icet_params* p, int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                               int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                               const float* x0, float* x_out, float* pred_stds_out, float* cov_out) {
+    return solve_indexed_host(c, p, n_kf, scan1, n1, n_regs, kf_index, scan2, n2, x0, x_out, pred_stds_out, cov_out, nullptr, kIdxRegister);
+}
+
+icet_status icet_solve_indexed_scored(icet_ctx* c, const icet_params* p, int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                                      int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                                      const float* x0, float* x_out, float* pred_stds_out, float* cov_out, icet_score* score_out) {
+    return solve_indexed_host(c, p, n_kf, scan1, n1, n_regs, kf_index, scan2, n2, x0, x_out, pred_stds_out, cov_out, score_out, kIdxScored);
+}
+
+icet_status icet_score_indexed(icet_ctx* c, const icet_params* p, int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                               int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                               const float* X, icet_score* score_out) {
+    return solve_indexed_host(c, p, n_kf, scan1, n1, n_regs, kf_index, scan2, n2, X, nullptr, nullptr, nullptr, score_out, kIdxScoreOnly);
+}
+
+icet_status icet_select_best_device(icet_ctx* c, int32_t n_regs, const int32_t* group, int32_t n_groups,
+                                    const icet_score* d_score, const float* d_out, int32_t* d_best, float* d_best_out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (n_regs < 0 || n_groups < 0 || (n_regs > 0 && (!group || !d_score || (d_best_out && !d_out))) || (n_groups > 0 && !d_best)) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    for (int r = 0; r < n_regs; r++)
+        if (group[r] < 0 || group[r] >= n_groups) { c->err = "group[" + std::to_string(r) + "] = " + std::to_string(group[r]) + " is not a group (0 .. " + std::to_string(n_groups - 1) + ")"; return ICET_ERR_BAD_ARG; }
+    if (n_groups == 0) return ICET_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // members of every group in ascending order, then the offsets: one upload from pinned staging
+    const int64_t need = (int64_t)n_regs + n_groups + 1;
+    if (c->sel_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_sel)); c->sel_in_flight = false; }
+    if (need > c->cap_sel) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, dev_realloc(c->d_sel, (size_t)need));
+        if (c->h_sel) { HIPCHK(c, hipHostFree(c->h_sel)); c->h_sel = nullptr; }
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_sel), sizeof(int32_t) * (size_t)need));
+        c->cap_sel = need;
+    }
+    int32_t* members = c->h_sel; int32_t* offs = c->h_sel + n_regs;
+    for (int g = 0; g <= n_groups; g++) offs[g] = 0;
+    for (int r = 0; r < n_regs; r++) offs[group[r] + 1] += 1;
+    for (int g = 0; g < n_groups; g++) offs[g + 1] += offs[g];
+    std::vector<int32_t> fill(offs, offs + n_groups);
+    for (int r = 0; r < n_regs; r++) members[fill[(size_t)group[r]]++] = r;
+    HIPCHK(c, hipMemcpyAsync(c->d_sel, c->h_sel, sizeof(int32_t) * (size_t)need, hipMemcpyHostToDevice, c->stream));
+    if (!c->ev_sel) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sel, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_sel, c->stream)); c->sel_in_flight = true;
+    c->armed_calls = 2;
+    HIPCHK(c, launch_select_best(c->d_sel, c->d_sel + n_regs, n_groups, d_score, d_out, d_best, d_best_out, c->stream));
     return ICET_OK;
 }
 

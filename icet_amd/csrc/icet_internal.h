@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct icet_score;                         // include/icet_hip.h
+
 namespace icet {
 
 // Per-slot accumulator: raw count (u32), in-bounds count (u32), then 9 sums Sd[3], Sdd[6] as 64-bit FIXED POINT
@@ -243,6 +245,11 @@ hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev*
 hipError_t launch_init_state(const Workspace& w, const LaunchCfg& c, const float* d_x0, hipStream_t st, float* xf_last = nullptr, const int32_t* d_n2 = nullptr, const PairDesc* h_desc = nullptr, const int32_t* h_seg = nullptr);   // (also clears the block tickets and the keep-list state)
 // keep_pass: the point pass in front of this solve was launched with keep_pass (below): build the list of every pair that walked its whole scan, check every pair's budgets
 hipError_t launch_gn_solve(const Workspace& w, const LaunchCfg& c, int iter, float* d_out, const AuxDev* aux, hipStream_t st, int keep_pass = 0);
+// The registration score (icet_score.hip): behind a point pass at the transform records in w.xf, one block per registration of an indexed call;
+// `iter` is the iteration index of the moving-voxel gate.  Then the best of each group (one wave per group).
+hipError_t launch_gn_score(const Workspace& w, const LaunchCfg& c, int iter, ::icet_score* d_score, hipStream_t st);
+hipError_t launch_select_best(const int32_t* d_members, const int32_t* d_offs, int n_groups, const ::icet_score* d_score, const float* d_out,
+                              int32_t* d_best, float* d_best_out, hipStream_t st);
 hipError_t launch_gn_tail_debug(const float* d_H, const float* d_g, float* d_out, int n, float bound2, hipStream_t st);     // test hook: the 6x6 tail on its own
 hipError_t launch_pinv3_debug(const float* d_A, float* d_out, int n, hipStream_t st);                                        // test hook: the 3x3 float COD pseudo-inverse of ICET_FLAG_REFERENCE_W
 // `points2` of pair 0 (include/icet.h:80): scan 2 under the transform record `xf` (AuxDev::xf_last); out = n2 x 3 column-major, ld n2 (may be pinned host memory)

@@ -219,6 +219,48 @@ icet_status icet_solve_indexed(icet_ctx* ctx, const icet_params* p,
                                int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
                                const float* x0, float* x_out, float* pred_stds_out, float* cov_out);
 
+/* --- how well scan 2 sits on its keyframe at a pose: the registration score ------------------------------------------------------------
+ * The quantity the Gauss-Newton step minimises, evaluated at pose X over the voxels and gates of the iteration the loop would run next at X:
+ * a slot of the keyframe with a fitted Gaussian whose angular bin holds n2 > n scan-2 points, m > n of them inside the cluster bounds, and --
+ * with ICET_FLAG_REJECT_MOVING -- the moving-voxel gate at iteration index p->runlen.  With the loop's own dz = L U^T (mu2 - mu1) and
+ * W = pinv(L U^T R_noise U L^T) (float COD, or the double path under ICET_FLAG_DOUBLE_W):
+ *     chi2 = sum_v dz^T W dz        voxels = contributing voxels        points_in = sum_v m        points = scan-2 rows
+ *     chi2_per_voxel = chi2 / voxels (+inf when voxels == 0)            overlap = points_in / points (0 when points == 0)
+ * chi2 is summed in double in a fixed order and rounded once: a registration's score bits do not depend on the other registrations of the call.
+ * Lower chi2_per_voxel = better fit; overlap hardly moves between a stuck and a converged solve, so it is no criterion on its own. */
+typedef struct icet_score {
+    float   chi2, chi2_per_voxel;
+    int32_t voxels, points_in, points;
+    float   overlap;
+    int32_t reserved[2];          /* zero */
+} icet_score;                     /* 32 bytes */
+
+/* The score of given poses: registration r = scan2[r] at pose d_X[r] (device, n_regs x 6) against parked keyframe kf_index[r].  Runs no
+ * iteration (p->runlen only places the moving-voxel gate); d_score: device, n_regs.  Argument rules, keyframe survival and asynchrony are those
+ * of icet_register_indexed_device.  The pose-hypothesis and candidate-verification primitive. */
+icet_status icet_score_indexed_device(icet_ctx* ctx, const icet_params* p, int32_t n_regs, const int32_t* kf_index,
+                                      const icet_dev_scan* scan2, const float* d_X, icet_score* d_score);
+/* icet_register_indexed_device followed by the score at every final X, in one enqueue.  d_out carries exactly the bits of the unscored
+ * call; d_score[r] equals icet_score_indexed_device at X = d_out[r][0..6).  runlen == 0 scores X0. */
+icet_status icet_register_indexed_scored_device(icet_ctx* ctx, const icet_params* p, int32_t n_regs, const int32_t* kf_index,
+                                                const icet_dev_scan* scan2, const float* d_x0, float* d_out, icet_score* d_score);
+/* Host-pointer forms, shaped like icet_solve_indexed (the keyframes stay parked).  score_out: n_regs; X: n_regs x 6. */
+icet_status icet_solve_indexed_scored(icet_ctx* ctx, const icet_params* p,
+                                      int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                                      int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                                      const float* x0, float* x_out, float* pred_stds_out, float* cov_out, icet_score* score_out);
+icet_status icet_score_indexed(icet_ctx* ctx, const icet_params* p,
+                               int32_t n_kf, const float* const* scan1, const int64_t* n1,
+                               int32_t n_regs, const int32_t* kf_index, const float* const* scan2, const int64_t* n2,
+                               const float* X, icet_score* score_out);
+/* The best registration of every group, on the device.  group (HOST, n_regs): the group of registration r, 0 <= group[r] < n_groups, in any
+ * order.  RULE: registration r is eligible when d_score[r].voxels >= max(1, ceil(0.5 x the largest voxels in its group)); among the eligible
+ * the lowest chi2_per_voxel wins (NaN ranks last), ties go to the lowest r.  d_best (device, n_groups): the winner, or -1 for a group without
+ * an eligible registration (an empty group included).  d_best_out (device, n_groups x 48, may be NULL): the winner's row of d_out (n_regs x 48,
+ * may be NULL when d_best_out is), a zero row for -1.  Asynchronous on the context's stream; group is read before the call returns. */
+icet_status icet_select_best_device(icet_ctx* ctx, int32_t n_regs, const int32_t* group, int32_t n_groups,
+                                    const icet_score* d_score, const float* d_out, int32_t* d_best, float* d_best_out);
+
 /* Pre-size the workspace (so the first timed call does not allocate). */
 icet_status icet_reserve(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2);
 
