@@ -26,7 +26,7 @@ FLAG_HALF_GAP_BOUNDS = 8  # non-parity extension (half-gap cluster buffers of th
 
 # every symbol include/icet_hip.h, include/icet_nodes.h and include/icet_io.h declare
 EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_version", "icet_solve", "icet_solve_begin", "icet_solve_keyframe_tables", "icet_solve_end", "icet_solve_batch",
-                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device", "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
+                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device", "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
                     "icet_node_prev_scan", "icet_node_aligned", "icet_node_snail_trail", "icet_node_last_timing", "icet_stream", "icet_device",
@@ -117,6 +117,7 @@ def load_library():
     L.icet_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
     L.icet_debug_gn_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_debug_pinv3.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.icet_debug_pinv3_double.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_keyframe_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan)]
     L.icet_register_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
     L.icet_keyframe_device_n.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p]
@@ -338,6 +339,14 @@ class Context:
         self._check(load_library().icet_debug_pinv3(self._h, A.ctypes.data, A.shape[0], out.ctypes.data))
         return out.reshape(-1, 3, 3)
 
+    def debug_pinv3_double(self, packed):
+        """icet_debug_pinv3_double (test hook): the 3 x 3 double pseudo-inverse of ICET_FLAG_DOUBLE_W on the device for n packed symmetric matrices
+        (n, 6) = xx, xy, xz, yy, yz, zz -> (n, 6) in the same packing."""
+        A = np.ascontiguousarray(packed, np.float32).reshape(-1, 6)
+        out = np.zeros_like(A)
+        self._check(load_library().icet_debug_pinv3_double(self._h, A.ctypes.data, A.shape[0], out.ctypes.data))
+        return out
+
     def debug_gn_tail(self, htwh, htwdz):
         """icet_debug_gn_tail (test hook): the 6x6 tail of an iteration on the device for n (HTWH, HTWdz).  Returns dict of arrays with leading dimension n:
         cov (6, 6), pred_stds, dx, eigvals (NaN on the Cholesky route), pruned, route."""
@@ -346,6 +355,7 @@ class Context:
         out = np.zeros((n, 56), np.float32)
         self._check(load_library().icet_debug_gn_tail(self._h, H.ctypes.data, g.ctypes.data, n, out.ctypes.data))
         return dict(cov=out[:, :36].reshape(n, 6, 6), pred_stds=out[:, 36:42], dx=out[:, 42:48], eigvals=out[:, 48:54], pruned=out[:, 54].astype(np.int32), route=out[:, 55].astype(np.int32))
+
 
     # -- single pair, host arrays ---------------------------------------------------------------
     def solve(self, scan1, scan2, runlen, X0, num_bins_phi, num_bins_theta, n=25, thresh=0.1, buff=0.1, aux=False, flags=0):

@@ -1596,6 +1596,22 @@ icet_status icet_debug_pinv3(icet_ctx* c, const float* a, int32_t n, float* out)
     return ICET_OK;
 }
 
+// Test hook: the per-voxel weight's pseudo-inverse under ICET_FLAG_DOUBLE_W on n host-side packed symmetric 3 x 3 matrices, through the device function the solve runs.
+icet_status icet_debug_pinv3_double(icet_ctx* c, const float* a, int32_t n, float* out) {
+    if (!c || !a || !out || n < 0) return ICET_ERR_BAD_ARG;
+    if (n == 0) return ICET_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(float) * (size_t)n * 12));
+    hipError_t e = hipMemcpyAsync(d, a, sizeof(float) * (size_t)n * 6, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_pinv3_double_debug(d, d + (size_t)n * 6, n, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + (size_t)n * 6, sizeof(float) * (size_t)n * 6, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { c->err = std::string("icet_debug_pinv3_double: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
+    return ICET_OK;
+}
+
 icet_status icet_set_option(icet_ctx* c, const char* name, double value) {
     if (!c || !name) return ICET_ERR_BAD_ARG;
     Tuning& t = c->tune;

@@ -252,6 +252,7 @@ hipError_t launch_select_best(const int32_t* d_members, const int32_t* d_offs, i
                               int32_t* d_best, float* d_best_out, hipStream_t st);
 hipError_t launch_gn_tail_debug(const float* d_H, const float* d_g, float* d_out, int n, float bound2, hipStream_t st);     // test hook: the 6x6 tail on its own
 hipError_t launch_pinv3_debug(const float* d_A, float* d_out, int n, hipStream_t st);                                        // test hook: the 3x3 float COD pseudo-inverse of ICET_FLAG_REFERENCE_W
+hipError_t launch_pinv3_double_debug(const float* d_A, float* d_out, int n, hipStream_t st);                                 // test hook: the 3x3 double pseudo-inverse of ICET_FLAG_DOUBLE_W
 // `points2` of pair 0 (include/icet.h:80): scan 2 under the transform record `xf` (AuxDev::xf_last); out = n2 x 3 column-major, ld n2 (may be pinned host memory)
 hipError_t launch_points2(const Workspace& w, const LaunchCfg& c, const float* xf, float* out, hipStream_t st);
 // icet_accumulate.hip

@@ -85,11 +85,27 @@ __global__ __launch_bounds__(64) void k_pinv3_debug(const float* __restrict__ A,
     icetdev::cod_pinv3_lane(a, w);
     for (int k = 0; k < 9; k++) out[(size_t)i * 9 + k] = w[k];
 }
+// Test hook (icet_debug_pinv3_double): n packed symmetric 3 x 3 matrices (xx, xy, xz, yy, yz, zz) through the per-voxel pseudo-inverse of the
+// solve under ICET_FLAG_DOUBLE_W (and of k_gn_score<false>), one lane each, called as gn_solve_body calls it.
+__global__ __launch_bounds__(64) void k_pinv3_double_debug(const float* __restrict__ A, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    float a[6], w[6];
+    for (int k = 0; k < 6; k++) a[k] = A[(size_t)i * 6 + k];
+    icetdev::pinv3_sym_fast(a, 3.0f * FLT_EPSILON, w);
+    for (int k = 0; k < 6; k++) out[(size_t)i * 6 + k] = w[k];
+}
 }  // namespace
 
 hipError_t launch_pinv3_debug(const float* d_A, float* d_out, int n, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     k_pinv3_debug<<<(n + 63) / 64, 64, 0, st>>>(d_A, d_out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_pinv3_double_debug(const float* d_A, float* d_out, int n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    k_pinv3_double_debug<<<(n + 63) / 64, 64, 0, st>>>(d_A, d_out, n);
     return hipGetLastError();
 }
 

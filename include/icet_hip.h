@@ -295,6 +295,9 @@ icet_status icet_debug_gn_tail(icet_ctx* ctx, const float* htwh, const float* ht
 /* Diagnostic hook for the parity tests: the per-voxel weight W = pinv(.) of ICET_FLAG_REFERENCE_W (Eigen's float CompleteOrthogonalDecomposition, src/icet.cpp:320-321) for n
  * host-side 3 x 3 matrices (row-major, n x 9 in, n x 9 out), through the device function the solve kernel runs. */
 icet_status icet_debug_pinv3(icet_ctx* ctx, const float* a, int32_t n, float* out);
+/* Diagnostic hook for the parity tests: the per-voxel weight W = pinv(.) of ICET_FLAG_DOUBLE_W (the double-precision pseudo-inverse with the 3 eps rank rule) for n
+ * host-side symmetric 3 x 3 matrices, packed (xx, xy, xz, yy, yz, zz): n x 6 in, n x 6 out, through the device function the solve kernel runs. */
+icet_status icet_debug_pinv3_double(icet_ctx* ctx, const float* a, int32_t n, float* out);
 
 /* Launch-shape and diagnostic knobs of ONE context (the library never reads the environment).  Defaults are the measured
  * optima.  Launch-shape knobs yield the same result bits; "force_exact", "guard_scale" and "lut_polar_quantile" preserve every

@@ -1507,6 +1507,299 @@ def test_gn_tail_literal_bits(gpu_ctx):
     ctx.close()
 
 
+# ---- the 6x6 tail (icet_debug_gn_tail): the route boundary, the Cholesky route against a 50-digit inverse, exact scale equivariance ---------------------
+
+_U24 = 2.0 ** -24
+_TAIL_KEYS = ("cov", "pred_stds", "dx", "eigvals")
+# Route-0 bound constant: the Cholesky factorisation, the triangular inverse and the product L^-T L^-1 each add at most gamma_6 ~ 6 u of relative backward
+# error per entry, and the step from a norm-wise forward bound (cond x backward error) to entries measured against sqrt(diag) outer products costs up to
+# another factor n = 6: c = 3 x 6 x 6 = 108.
+_C_CHOL = 108.0
+
+
+def _sym_upper(H):
+    """HTWH as the solve kernel holds it: the upper triangle mirrored (the 27 sums).  The golden HTWH of _cond_sweep_matrices come from the reference's
+    full-matrix product and are not all exactly symmetric."""
+    H = np.asarray(H, np.float32)
+    U = np.triu(H)
+    return (U + np.swapaxes(np.triu(H, 1), -1, -2)).astype(np.float32)
+
+
+def _tail_both(ctx, H, g):
+    return (ctx.debug_gn_tail(H, g),)
+
+
+def _route0_errors(H, g, out, i):
+    """The Cholesky route's outputs of matrix i against the 50-digit inverse: the largest error of cov, dx, pred_stds as a fraction of its bound
+    c cond 2^-24 (sqrt(diag) outer products for cov; the same propagated through g for dx, plus the matvec's own rounding)."""
+    from oracle import mpref
+    inv, cond = mpref.inverse6(H[i])
+    d = np.sqrt(np.abs(np.diag(inv)))
+    gi = g[i].astype(np.float64)
+    e = _C_CHOL * cond * _U24
+    b_cov = e * np.outer(d, d)
+    dx_ref = inv @ gi
+    b_dx = e * d * (d @ np.abs(gi)) + 8 * _U24 * (np.abs(inv) @ np.abs(gi))
+    b_ps = e * d + _U24 * d
+    r_cov = np.max(np.abs(out["cov"][i].astype(np.float64) - inv) / b_cov)
+    r_dx = np.max(np.abs(out["dx"][i].astype(np.float64) - dx_ref) / np.maximum(b_dx, 1e-300))
+    r_ps = np.max(np.abs(out["pred_stds"][i].astype(np.float64) - d) / np.maximum(b_ps, 1e-300))
+    return cond, r_cov, r_dx, r_ps
+
+
+def _spd(rng, lam):
+    Q, _ = np.linalg.qr(rng.standard_normal((6, 6)))
+    A = (Q * np.asarray(lam, np.float64)) @ Q.T
+    return ((A + A.T) / 2).astype(np.float32)
+
+
+def _boundary_sweep(bound, rng, n_base=3, n_c=96):
+    """Matrices whose |H|_F^2 |H^-1|_F^2 runs through bound^2 in 0.05 % steps: lambda = (1, .., 1, 1/c), |H|_F^2 |H^-1|_F^2 = (5 + c^-2)(5 + c^2)."""
+    Hs = []
+    c0 = np.sqrt((bound * bound - 26.0) / 5.0) if bound > 6 else 1.0
+    for _ in range(n_base):
+        Q, _ = np.linalg.qr(rng.standard_normal((6, 6)))
+        for c in c0 * (1.0 + np.linspace(-0.024, 0.024, n_c)):
+            A = (Q * np.array([1, 1, 1, 1, 1, 1.0 / c])) @ Q.T
+            Hs.append(((A + A.T) / 2).astype(np.float32))
+    return np.stack(Hs)
+
+
+def _ulp_walks(H, route):
+    """Where the device's route flips between neighbours of a sweep: the matrices between them, then H[5,5] walked 12 ulps either side."""
+    out = []
+    for i in np.nonzero(route[:-1] != route[1:])[0]:
+        a, b = H[i].astype(np.float64), H[i + 1].astype(np.float64)
+        for t in np.linspace(0, 1, 9)[1:-1]:
+            out.append((a + t * (b - a)).astype(np.float32))
+        for k in range(-12, 13):
+            M = H[i].copy()
+            M[5, 5] = np.float32(M[5, 5]) + np.float32(k) * np.spacing(M[5, 5])
+            out.append(M)
+    return np.stack(out) if out else np.zeros((0, 6, 6), np.float32)
+
+
+def _edge_matrices(rng):
+    Hs = []
+    base = _spd(rng, [4, 3, 2, 1.5, 1, 0.5])
+    for k in range(0, 9):                                                 # the last Cholesky pivot a few ulps above (and at) zero
+        B = rng.standard_normal((6, 5)).astype(np.float64)
+        A = (B @ B.T).astype(np.float32)
+        A[5, 5] += np.float32(k) * np.spacing(A[5, 5])
+        Hs.append(A)
+    for s in range(8):                                                    # rank 5 formed in float: indefinite or not by one rounding
+        B = np.random.default_rng(100 + s).standard_normal((6, 5)).astype(np.float32)
+        Hs.append((B @ B.T).astype(np.float32))
+    for pos in ((0, 0), (2, 2), (1, 4)):                                  # inf entries
+        A = base.copy(); A[pos] = np.inf; A[pos[::-1]] = np.inf; Hs.append(A)
+    A = base.copy(); A[3, 3] = -np.inf; Hs.append(A)
+    for scale in (1e-20, 1e18, 4e18):                                     # |H|_F^2 or |H^-1|_F^2 under- or overflows float
+        for cond in (1.0, 1e3, 1e5, 1e7):
+            Hs.append((_spd(rng, np.geomspace(1.0, 1.0 / cond, 6)).astype(np.float64) * scale).astype(np.float32))
+    return _sym_upper(np.stack(Hs))
+
+
+def test_gn_tail_route_boundary(gpu_ctx):
+    """Matrices at the Cholesky route's bound -- |H|_F^2 |H^-1|_F^2 a few ulps either side of bound^2, at the default bound and two others -- and at its
+    other edges: a pivot a few ulps above zero, indefinite by one rounding, inf entries, scales where |H|_F or |H^-1|_F under- or overflows float.  Every
+    matrix gets route 0 or 2 and the outputs of that route: the oracle's bits on route 2, the 50-digit inverse within c cond 2^-24 on route 0, and route 0
+    only where the condition number is within the bound."""
+    import icet_amd
+    from oracle import pyoracle as po
+    rng = np.random.default_rng(77)
+    ctx = icet_amd.Context(0)
+    counts = {}
+    worst = np.zeros(3)
+    for bound in (2.5e5, 1e3, 7e5):
+        ctx.set_option("gn_cond_bound", bound)
+        H = _boundary_sweep(bound, rng)
+        (blk,) = _tail_both(ctx, H, np.ones((H.shape[0], 6), np.float32))
+        walks = _ulp_walks(H, blk["route"]); n_walk = walks.shape[0]
+        H = np.concatenate([H, walks] + ([_edge_matrices(rng)] if bound == 2.5e5 else []))
+        g = rng.standard_normal((H.shape[0], 6)).astype(np.float32)
+        (blk,) = _tail_both(ctx, H, g)
+        for name, out in (("one-wave", blk),):
+            assert set(np.unique(out["route"]).tolist()) <= {0, 2}
+            for i in range(H.shape[0]):
+                if out["route"][i] == 2:
+                    ref = po.gn_tail(H[i], g[i])
+                    assert out["pruned"][i] == ref["pruned"], (bound, name, i)
+                    for k in _TAIL_KEYS:
+                        assert _same_bits(out[k][i], ref[k]), (bound, name, i, k)
+                else:
+                    assert out["pruned"][i] == 0 and np.isnan(out["eigvals"][i]).all()
+                    cond, r_cov, r_dx, r_ps = _route0_errors(H, g, out, i)
+                    assert cond <= 1.25 * bound, (bound, name, i, cond)       # the Frobenius bound proves cond_2 <= |H|_F |H^-1|_F (less the float fi's own error)
+                    assert r_cov <= 1 and r_dx <= 1 and r_ps <= 1, (bound, name, i, cond, r_cov, r_dx, r_ps)
+                    worst = np.maximum(worst, [r_cov, r_dx, r_ps])
+        n0 = int((blk["route"] == 0).sum())
+        counts[bound] = (H.shape[0], n0, H.shape[0] - n0, n_walk)
+        assert n0 > 0 and H.shape[0] - n0 > 0, (bound, counts[bound])             # the set does straddle the bound
+        assert n_walk > 0, bound                                                   # ulp-level neighbours of the device's flip are in the set
+    print("route boundary: (matrices, route 0, route 2, of them ulp-walk) per bound %s; worst route-0 error / bound: cov %.3f dx %.3f pred_stds %.3f" % (counts, *worst))
+    ctx.close()
+
+
+def test_gn_tail_cholesky_route_against_a_50_digit_inverse(gpu_ctx):
+    """On every matrix of the condition sweep (and 200 more, cond 1 .. 2e5) that the default bound sends down route 0 -- the route of every ordinary pair
+    in every iteration -- cov, dx = cov g and pred_stds = sqrt|diag cov| against mpmath's inverse of the exact float32 input, within c cond 2^-24
+    (c = 108, _C_CHOL)."""
+    import icet_amd
+    H, g = _cond_sweep_matrices()
+    rng = np.random.default_rng(11)
+    extra = [_spd(rng, np.geomspace(1.0, 1.0 / c, 6) * rng.uniform(1e-3, 1e6)) for c in np.geomspace(1.0, 2e5, 200)]
+    H = _sym_upper(np.concatenate([H, np.stack(extra)])); g = np.concatenate([g, rng.standard_normal((200, 6)).astype(np.float32)])
+    ctx = icet_amd.Context(0)
+    (blk,) = _tail_both(ctx, H, g)
+    worst = np.zeros(3); n = 0
+    for out in (blk,):
+        for i in np.nonzero(out["route"] == 0)[0]:
+            cond, r_cov, r_dx, r_ps = _route0_errors(H, g, out, i)
+            assert r_cov <= 1 and r_dx <= 1 and r_ps <= 1, (i, cond, r_cov, r_dx, r_ps)
+            worst = np.maximum(worst, [r_cov, r_dx, r_ps]); n += 1
+    assert (blk["route"] == 0).sum() >= 200
+    print("route 0 vs 50 digits: %d evaluations; worst error / bound: cov %.3f dx %.3f pred_stds %.3f" % (n, *worst))
+    ctx.close()
+
+
+def test_gn_tail_is_exactly_scale_equivariant(gpu_ctx):
+    """(4^j H, 4^j g) for j in [-8, 8]: both routes are built from products, quotients, sums and square roots with relative thresholds only, so
+    cov scales by exactly 4^-j, dx is identical, pred_stds scales by exactly 2^-j where nothing is pruned, and route and pruned count do not move."""
+    import icet_amd
+    H, g = _cond_sweep_matrices()
+    ok = np.isfinite(H).all(axis=(1, 2))
+    H, g = _sym_upper(H[ok]), g[ok]
+    ctx = icet_amd.Context(0)
+    base = _tail_both(ctx, H, g)
+    # The limit: sums of squares of H's entries (|H|_F, the QR's column norms) and of the inverse's (|H^-1|_F) must neither overflow nor lose
+    # bits to underflow, nor may the QR's rank threshold (eps |col|)^2: exact while the largest |H| and |cov| stay in [2^-30, 2^61].  The sweep's
+    # golden matrices reach |H| = 3.7e14, so 4^8 of them is beyond it (|H|^2 overflows float: cov -> 0).
+    mh = np.abs(H).max(axis=(1, 2)).astype(np.float64); mc = np.abs(base[0]["cov"]).max(axis=(1, 2)).astype(np.float64)
+    n_checked = 0
+    for j in range(-8, 9):
+        s = np.float32(4.0 ** j)
+        got = _tail_both(ctx, H * s, g * s)
+        inside = (mh * 4.0 ** j <= 2.0 ** 61) & (mh * 4.0 ** j >= 2.0 ** -30) & (mc * 4.0 ** -j <= 2.0 ** 61) & (mc * 4.0 ** -j >= 2.0 ** -30)
+        n_checked += int(inside.sum())
+        for b, o in zip(base, got):
+            assert np.array_equal(o["route"][inside], b["route"][inside]) and np.array_equal(o["pruned"][inside], b["pruned"][inside]), j
+            assert _same_bits(np.ldexp(o["cov"][inside], 2 * j), b["cov"][inside]), j
+            assert _same_bits(o["dx"][inside], b["dx"][inside]), j
+            un = inside & (b["pruned"] == 0)
+            assert _same_bits(np.ldexp(o["pred_stds"][un], j), b["pred_stds"][un]), j
+    assert n_checked >= 8 * H.shape[0]
+    print("scale equivariance: %d (matrix, scale) pairs of %d matrices x 17 scales; routes %s" % (n_checked, H.shape[0], np.bincount(base[0]["route"]).tolist()))
+    ctx.close()
+
+
+# ---- the per-voxel weight of ICET_FLAG_DOUBLE_W (pinv3_sym_fast) against a 50-digit pseudo-inverse ----------------------------------------------------------
+
+_C_JACOBI = 64.0      # double Jacobi: ~10 rotations of O(1) eps each, and a convergence test at 1e-17 of the diagonal
+
+
+def _pack(A):
+    A = np.asarray(A, np.float64)
+    return np.array([A[0, 0], A[0, 1], A[0, 2], A[1, 1], A[1, 2], A[2, 2]])
+
+
+def _rot3(rng):
+    Q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+    return Q
+
+
+def _pinv3_double_cases():
+    """(packed float32 matrices, family name per matrix)."""
+    eps = float(np.finfo(np.float32).eps)
+    rng = np.random.default_rng(31)
+    P, fam = [], []
+    def add(A, f):
+        P.append(_pack(A).astype(np.float32)); fam.append(f)
+    for c in np.geomspace(1.0, 1e10, 41):                                  # PSD, cond 1 .. 1e10 (the fast route's proof bound 1e12 on |A|_F^2 |A^-1|_F^2)
+        for _ in range(6):
+            Q = _rot3(rng); add((Q * np.array([1.0, c ** -0.5, 1.0 / c]) * rng.uniform(0.1, 10)) @ Q.T, "psd")
+    for sgn in (-1, 1):                                                    # lambda_min / lambda_max at the rank threshold 3 eps (1 +- 1e-3), exact in float
+        for d in (1e-3, 1e-4):
+            for perm in ((0, 1, 2), (2, 0, 1), (1, 2, 0)):
+                lam = np.array([1.0, 0.5, 3 * eps * (1 + sgn * d)])[list(perm)]
+                add(np.diag(lam), "threshold")
+    n_thr = 0
+    while n_thr < 60:                                                      # the same, rotated: keep the float matrices whose exact ratio lands within 1e-2 of it
+        Q = _rot3(rng)
+        A = ((Q * np.array([1.0, 0.5, 3 * eps * (1 + rng.uniform(-0.5, 0.5))])) @ Q.T).astype(np.float32)
+        ev = np.linalg.eigvalsh(A.astype(np.float64))
+        if abs(abs(ev[0]) / ev[2] / (3 * eps) - 1) < 1e-2:
+            add(A, "threshold"); n_thr += 1
+    for ax in range(3):                                                    # one or two axes masked by exact zeros
+        for c in (1.0, 1e3, 1e8):
+            B = np.zeros((3, 3)); k = [i for i in range(3) if i != ax]
+            Q2 = _rot3(rng)[:2, :2]; Q2, _ = np.linalg.qr(Q2)
+            B[np.ix_(k, k)] = (Q2 * np.array([1.0, 1.0 / c])) @ Q2.T
+            add(B, "masked")
+            D = B.astype(np.float32); D[ax, k[0]] = D[k[0], ax] = np.float32(1e-40)      # the same with a denormal off-diagonal: not clean
+            add(D, "masked_denormal")
+            E = np.zeros((3, 3)); E[k[0], k[0]] = 2.5 * c; add(E, "masked")
+    for _ in range(12):
+        Q = _rot3(rng); add((Q * np.array([1.0, 0.3, -1e-9])) @ Q.T, "indefinite_rounding")
+        Q = _rot3(rng); add((Q * np.array([1.0, -0.5, -0.2])) @ Q.T, "indefinite")
+    add(np.zeros((3, 3)), "zero")
+    for s in (1e-40, 1e-30, 1e30):
+        for c in (1.0, 10.0, 1e4):
+            Q = _rot3(rng); add((Q * np.array([1.0, 0.7, 1.0 / c]) * s) @ Q.T if s != 1e-40 else np.diag([1.0, 0.7, 1.0 / c]) * s, "scale")
+    return np.stack(P), fam
+
+
+def test_pinv3_double_against_a_50_digit_pseudo_inverse(gpu_ctx):
+    """pinv3_sym_fast (the per-voxel weight under ICET_FLAG_DOUBLE_W, of k_gn_score<false> and of node groups with double_w) against mpmath's
+    pseudo-inverse under the same rule (|lambda| <= 3 eps_f max|lambda| dropped).  Fast route (clean, cond <= 1e6): within 2^-24 |W| + 1e-9 max|W|;
+    Jacobi route: within c cond 2^-53 max|W| + 2^-24 |W| (c = 64).  The rank at the threshold is the reference's (a wrong rank misses by 1 / lambda_min).
+    Axes masked by exact zeros come out exactly 0; a float overflow of 1 / lambda is inf as in the reference's rounding."""
+    from oracle import mpref
+    P, fam = _pinv3_double_cases()
+    W = gpu_ctx.debug_pinv3_double(P).astype(np.float64)
+    fmax = float(np.finfo(np.float32).max)
+    worst = {}
+    for i in range(P.shape[0]):
+        ref, rank, cond = mpref.pinv3_sym(P[i])
+        A = mpref.unpack3(P[i])
+        clean_psd = fam[i] == "psd" and cond <= 3.3e5                   # 9 cond^2 >= |A|_F^2 |A^-1|_F^2: the fast route's 1e12 holds for sure
+        over = np.abs(ref) > fmax
+        assert np.array_equal(W[i][over], np.sign(ref[over]) * np.inf), (i, fam[i], W[i], ref)
+        r = ref[~over]; w = W[i][~over]
+        m = np.abs(r).max() if r.size else 0.0
+        if clean_psd:
+            b = _U24 * np.abs(r) + 1e-9 * m
+        else:
+            b = _C_JACOBI * cond * 2.0 ** -53 * m + _U24 * np.abs(r)
+        err = np.abs(w - r)
+        assert (err <= b).all(), (i, fam[i], cond, rank, P[i], W[i], ref)
+        q = float(np.max(np.where(b > 0, err / np.where(b > 0, b, 1), 0.0))) if r.size else 0.0
+        worst[fam[i]] = max(worst.get(fam[i], 0.0), q)
+        if fam[i] == "masked":                                            # exactly zero on the masked axes
+            z = np.nonzero(np.diag(A) == 0)[0]
+            Wm = mpref.unpack3(W[i])
+            assert (Wm[z, :] == 0).all() and (Wm[:, z] == 0).all(), (i, W[i])
+    print("pinv3_sym_fast vs 50 digits: %d matrices; worst error / bound per family %s" % (P.shape[0], {k: round(v, 3) for k, v in worst.items()}))
+
+
+def test_pinv3_double_nan_and_scale_equivariance(gpu_ctx):
+    """NaN: on the diagonal of an otherwise decoupled axis the axis is DROPPED (the Jacobi route's fmax-based lambda_max ignores it and |NaN| > thr is
+    false: W is the pseudo-inverse of the rest); NaN off the diagonal poisons every entry (the rotation it enters is NaN).  And A -> 4^j A for j in [-8, 8]
+    scales W by exactly 4^-j on both routes (relative thresholds only)."""
+    from oracle import mpref
+    Pn = np.array([[np.nan, 0, 0, 2, 0, 4], [1, np.nan, 0, 1, 0, 1], [2, 0.5, 0.1, 1, 0.2, np.nan]], np.float32)
+    Wn = gpu_ctx.debug_pinv3_double(Pn)
+    assert np.array_equal(Wn[0], np.array([0, 0, 0, 0.5, 0, 0.25], np.float32)), Wn[0]
+    assert np.isnan(Wn[1]).all() and np.isnan(Wn[2]).all(), Wn
+    P, fam = _pinv3_double_cases()
+    keep = np.array([f not in ("scale", "masked_denormal") for f in fam])
+    P = P[keep]
+    base = gpu_ctx.debug_pinv3_double(P)
+    for j in range(-8, 9):
+        got = gpu_ctx.debug_pinv3_double(P * np.float32(4.0 ** j))
+        assert _same_bits(np.ldexp(got, 2 * j), base), j
+    print("pinv3_sym_fast scale equivariance: %d matrices x 17 scales" % P.shape[0])
+
+
 def _degenerate_golden():
     g = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_degenerate.npz")))
     return {nm: {k.split("/")[1]: v for k, v in g.items() if k.startswith(nm + "/")} for nm in sorted({k.split("/")[0] for k in g})}

@@ -99,10 +99,11 @@ def _score_rows(t):
     return np.frombuffer(t.detach().cpu().numpy().tobytes(), dtype=api.SCORE_DTYPE)
 
 
-def _oracle_score(a, b, X):
+def _oracle_score(a, b, X, double_w=False):
     """The score at X from the CPU restatement's per-voxel trace of iteration 0 (runlen 1 from x0 = X, the device's arithmetic), with W = the restated
-    float COD of the float matrix M R_noise M^T."""
+    float COD of the float matrix M R_noise M^T; double_w: W = the 50-digit pseudo-inverse of its upper triangle under the 3 eps rank rule (ICET_FLAG_DOUBLE_W)."""
     from oracle import pyoracle as po
+    from oracle import mpref
     ref = po.solve(a, b, x0=np.asarray(X, np.float32), runlen=1, trace=True, mode=po.DEVICE_ARITH)
     tr = ref["trace"]
     used = np.nonzero(tr["used"][0])[0]
@@ -112,7 +113,10 @@ def _oracle_score(a, b, X):
         d1 = np.float32(tr["n1_raw"][v] - 1); d2 = np.float32(tr["n2_raw"][0][v] - 1)
         Rn = (tr["sigma1"][v] / d1 + tr["sigma2"][0][v] / d2).astype(np.float32)
         Rp = (M @ Rn @ M.T).astype(np.float32)
-        W, _ = po.pinv(Rp)
+        if double_w:
+            W = mpref.unpack3(mpref.pinv3_sym(mpref.pack_upper(Rp))[0])
+        else:
+            W, _ = po.pinv(Rp)
         dz = M.astype(np.float64) @ (tr["mu2"][0][v].astype(np.float64) - tr["mu1"][v].astype(np.float64))
         chi2 += float(dz @ W.astype(np.float64) @ dz)
     return dict(chi2=chi2, voxels=int(used.size), points_in=int(tr["n2_in"][0][used].sum()), points=int(b.shape[0]))
@@ -146,6 +150,25 @@ def test_score_matches_the_cpu_restatement(gpu_ctx, frames, sample_pc):
             assert abs(float(got["chi2"][k]) - ref["chi2"]) <= rtol * abs(ref["chi2"]), (name, k, float(got["chi2"][k]), ref["chi2"])
             assert np.isclose(got["chi2_per_voxel"][k], got["chi2"][k] / got["voxels"][k], rtol=1e-6)
             assert np.isclose(got["overlap"][k], got["points_in"][k] / got["points"][k], rtol=1e-6)
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_double_w_score_matches_a_50_digit_restatement(gpu_ctx, frames, sample_pc):
+    """Under ICET_FLAG_DOUBLE_W (k_gn_score<false>): chi2, voxels and points_in against the trace with W = the 50-digit pseudo-inverse (3 eps rank rule)."""
+    import icet_amd
+    from icet_amd import api
+    ctx = icet_amd.Context(0)
+    for name, a, b, poses in _cases(frames, sample_pc):
+        X = np.asarray(poses, np.float32)
+        got = ctx.score_indexed([a], [b] * 3, [0, 0, 0], X, flags=api.FLAG_DOUBLE_W)
+        for k in range(3):
+            ref = _oracle_score(a, b, X[k], double_w=True)
+            assert got["voxels"][k] == ref["voxels"], (name, k, got["voxels"][k], ref["voxels"])
+            assert got["points_in"][k] == ref["points_in"], (name, k, got["points_in"][k], ref["points_in"])
+            assert got["points"][k] == ref["points"]
+            rtol = 1e-4
+            assert abs(float(got["chi2"][k]) - ref["chi2"]) <= rtol * abs(ref["chi2"]), (name, k, float(got["chi2"][k]), ref["chi2"])
     ctx.close()
 
 
