@@ -26,14 +26,18 @@ FLAG_HALF_GAP_BOUNDS = 8  # non-parity extension (half-gap cluster buffers of th
 
 # every symbol include/icet_hip.h, include/icet_nodes.h and include/icet_io.h declare
 EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_version", "icet_solve", "icet_solve_begin", "icet_solve_keyframe_tables", "icet_solve_end", "icet_solve_batch",
-                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device", "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
+                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
+                    "icet_keyframe_store_create", "icet_keyframe_store_destroy", "icet_keyframe_store_last_error", "icet_keyframe_store_reserve", "icet_keyframe_store_put_device",
+                    "icet_keyframe_store_register_device", "icet_keyframe_store_register_scored_device", "icet_keyframe_store_score_device", "icet_keyframe_store_debug_fetch",
+                    "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
                     "icet_node_prev_scan", "icet_node_aligned", "icet_node_snail_trail", "icet_node_last_timing", "icet_stream", "icet_device",
                     "icet_node_group_create", "icet_node_group_destroy", "icet_node_group_last_error", "icet_node_group_push_device", "icet_node_group_map",
                     "icet_node_group_prev_scan", "icet_node_group_aligned", "icet_node_group_snail_trail",
                     "icet_load_scan", "icet_free_scan", "icet_save_scan_npy")
-_NON_STATUS = ("icet_version", "icet_last_error", "icet_node_last_error", "icet_node_group_last_error", "icet_stream", "icet_device", "icet_free_scan", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context")
+_NON_STATUS = ("icet_version", "icet_last_error", "icet_node_last_error", "icet_node_group_last_error", "icet_stream", "icet_device", "icet_free_scan", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
+               "icet_keyframe_store_last_error")
 
 
 class IcetError(RuntimeError):
@@ -130,6 +134,15 @@ def load_library():
     L.icet_solve_indexed_scored.argtypes = L.icet_solve_indexed.argtypes + [C.c_void_p]
     L.icet_score_indexed.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_select_best_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(C.c_void_p)]
+    L.icet_keyframe_store_destroy.argtypes = [C.c_void_p]
+    L.icet_keyframe_store_last_error.argtypes = [C.c_void_p]; L.icet_keyframe_store_last_error.restype = C.c_char_p
+    L.icet_keyframe_store_reserve.argtypes = [C.c_void_p, C.c_int32]
+    L.icet_keyframe_store_put_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p]
+    L.icet_keyframe_store_register_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_register_scored_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_score_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_debug_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
     L.icet_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
     L.icet_multi_destroy.argtypes = [C.c_void_p]
     L.icet_multi_last_error.argtypes = [C.c_void_p]; L.icet_multi_last_error.restype = C.c_char_p
@@ -491,6 +504,143 @@ class Context:
         st = load_library().icet_solve_batch_device(self._h, C.byref(params), k, A, B,
                                                     C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr))
         self._check(st)
+
+
+class KeyframeStore:
+    """``icet_keyframe_store`` (include/icet_hip.h): slots of keyframes built once and kept on ``ctx``'s device, whatever else runs on the context;
+    scans register and are scored against any set of slots.  The store borrows ``ctx`` (closed before it)."""
+
+    def __init__(self, ctx, capacity, num_bins_phi=24, num_bins_theta=75, n=25, thresh=0.1, buff=0.1, flags=0):
+        self._ctx = ctx
+        self.params = Params(0, int(num_bins_phi), int(num_bins_theta), int(n), float(thresh), float(buff), int(flags))
+        h = C.c_void_p()
+        st = load_library().icet_keyframe_store_create(ctx._h, C.byref(self.params), int(capacity), C.byref(h))
+        if st != ICET_OK:
+            raise IcetError(st, "icet_keyframe_store_create: " + load_library().icet_last_error(ctx._h).decode())
+        self._h = h
+        self.V = int(num_bins_phi) * int(num_bins_theta)
+        import weakref
+        if not hasattr(ctx, "_nodes"):
+            ctx._nodes = []
+        ctx._nodes.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            # (a context finalised first -- both in one garbage cycle, whose weak references are cleared before any finaliser runs -- took the
+            # device with it: the store's memory goes with the process then; destroying it would touch the freed context)
+            if getattr(self._ctx, "_h", None):
+                load_library().icet_keyframe_store_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        if st != ICET_OK:
+            raise IcetError(st, load_library().icet_keyframe_store_last_error(self._h).decode())
+
+    def _params(self, runlen, flags):
+        q = self.params
+        return Params(int(runlen), q.bins_phi, q.bins_theta, q.n, q.thresh, q.buff, (q.flags & (FLAG_TRUE_SORT | FLAG_HALF_GAP_BOUNDS)) | int(flags))
+
+    @staticmethod
+    def _index(slot_index, k):
+        idx = np.ascontiguousarray(np.asarray(slot_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "slot_index and scan2_descs differ in length")
+        return idx
+
+    def reserve(self, capacity):
+        self._check(load_library().icet_keyframe_store_reserve(self._h, int(capacity)))
+
+    def put_device(self, slots, scan1_descs, d_rows_ptr=None):
+        """Build the keyframes of the scans (device_ptr, n, ld) and park keyframe k in slot slots[k] (icet_keyframe_store_put_device; with d_rows_ptr
+        -- a device int32 array -- n is an upper bound and the actual row counts are read on the device).  Asynchronous on the context's stream."""
+        k = len(scan1_descs)
+        sl = self._index(slots, k)
+        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan1_descs])
+        self._check(load_library().icet_keyframe_store_put_device(self._h, k, sl.ctypes.data, A, C.c_void_p(d_rows_ptr) if d_rows_ptr else None))
+
+    def put(self, slots, scans):
+        """put_device for host N x 3 arrays: staged on the device; returns once the put has run."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        torch.cuda.synchronize(dev)
+        self.put_device(slots, [(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs])
+        self._ctx.sync()
+
+    def register_device(self, slot_index, scan2_descs, params, d_out_ptr, d_x0_ptr=None):
+        """Context.register_indexed_device against the store's slots (icet_keyframe_store_register_device)."""
+        k = len(scan2_descs)
+        idx = self._index(slot_index, k)
+        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        self._check(load_library().icet_keyframe_store_register_device(self._h, C.byref(params), k, idx.ctypes.data, B,
+                                                                       C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr)))
+
+    def register_scored_device(self, slot_index, scan2_descs, params, d_out_ptr, d_score_ptr, d_x0_ptr=None):
+        """Context.register_indexed_scored_device against the store's slots (icet_keyframe_store_register_scored_device)."""
+        k = len(scan2_descs)
+        idx = self._index(slot_index, k)
+        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        self._check(load_library().icet_keyframe_store_register_scored_device(self._h, C.byref(params), k, idx.ctypes.data, B,
+                                                                              C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr), C.c_void_p(d_score_ptr)))
+
+    def score_device(self, slot_index, scan2_descs, params, d_X_ptr, d_score_ptr):
+        """Context.score_indexed_device against the store's slots (icet_keyframe_store_score_device)."""
+        k = len(scan2_descs)
+        idx = self._index(slot_index, k)
+        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        self._check(load_library().icet_keyframe_store_score_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_score_ptr)))
+
+    def debug_fetch(self, slot, what, count=None):
+        """Diagnostic: one occupied slot's tables -- 'n_slots' (int), 'hot' ((n_slots, 12) words of SlotHot), 'fit' ((n_slots, 20) words of SlotFit),
+        'slot_of_voxel' (int16, V).  Words are returned as uint32 (view them as float32 / int32)."""
+        L = load_library()
+        ns = np.zeros(1, np.int32)
+        self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 0, ns.ctypes.data, 1))
+        ns = int(ns[0])
+        if what == "n_slots":
+            return ns
+        if what == "slot_of_voxel":
+            out = np.zeros(self.V if count is None else int(count), np.int16)
+            self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 3, out.ctypes.data, out.size))
+            return out
+        code, words = {"hot": (1, 12), "fit": (2, 20)}[what]
+        out = np.zeros(ns * words if count is None else int(count), np.uint32)
+        self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), code, out.ctypes.data, out.size))
+        return out.reshape(-1, words) if count is None else out
+
+    def best_match(self, scan2, slot_index, x0, runlen, flags=0):
+        """The loop-closure check: registration r = host scan2 (N x 3) against slot slot_index[r] from x0[r]; all of them one group, scored and
+        reduced on the device (icet_select_best_device).  Returns dict(best, slot, X, pred_stds, cov, score, X_all) like Context.solve_multistart:
+        ``best`` the winning registration (-1: none has a contributing voxel; slot, X, pred_stds, cov are then None), ``slot`` its slot."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        idx = np.ascontiguousarray(np.asarray(slot_index, np.int32).reshape(-1))
+        k = idx.shape[0]
+        x = np.ascontiguousarray(np.asarray(x0, np.float32).reshape(k, 6))
+        s2 = torch.from_numpy(_colmajor(scan2)).to(dev)
+        xd = torch.from_numpy(x).to(dev)
+        out = torch.zeros((k, 48), dtype=torch.float32, device=dev)
+        sc = torch.zeros((k, 8), dtype=torch.int32, device=dev)
+        best = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.register_scored_device(idx, [(s2.data_ptr(), s2.shape[1], s2.shape[1])] * k, self._params(runlen, flags), out.data_ptr(), sc.data_ptr(), xd.data_ptr())
+        self._ctx.select_best_device(np.zeros(k, np.int32), 1, sc.data_ptr(), best.data_ptr())
+        self._ctx.sync()
+        score = scores_as_dict(np.frombuffer(sc.cpu().numpy().tobytes(), SCORE_DTYPE))
+        o = out.cpu().numpy()
+        b = int(best.cpu().numpy()[0])
+        res = dict(best=b, score=score, X_all=o[:, :6].copy())
+        if b < 0:
+            res.update(slot=None, X=None, pred_stds=None, cov=None)
+        else:
+            res.update(slot=int(idx[b]), X=o[b, :6].copy(), pred_stds=o[b, 6:12].copy(), cov=o[b, 12:48].reshape(6, 6).copy())
+        return res
 
 
 class MultiContext:

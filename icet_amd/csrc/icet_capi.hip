@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <new>
+#include <atomic>
 
 using namespace icet;
 
@@ -74,7 +75,7 @@ struct icet_ctx {
     hipEvent_t ev_desc = nullptr; bool desc_in_flight = false;   // completion of the last copy out of the pinned descriptor staging
     // Small device batches whose launch geometry repeats call after call are replayed from a captured hipGraph (option "graph"): the ~33
     // launches of a single-pair solve then cost one hipGraphLaunch on the host, and the command processor runs them back to back.
-    struct GraphKey { int64_t v[45]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key (graph_key_of)
+    struct GraphKey { int64_t v[47]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key + the keyframe source (graph_key_of)
     struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false; };
     bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
     GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
@@ -94,6 +95,20 @@ struct icet_ctx {
     // last kernel.  armed_calls counts such solves since the last icet_sync; anything else enqueued on the context (or a second solve, whose reset of the word races with the
     // first one's store) makes it 2 or more and icet_sync synchronises the stream as before.
     int32_t* h_sync_word = nullptr; int armed_calls = 2;
+};
+
+// A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
+// keyframe side (row stride V; (V + 1) & ~1 for slot_of_voxel), on the borrowed context's device.  A put builds on the context and parks into rows of its own
+// (k_keyframe_store_park); the indexed calls read a row the way they read a parked keyframe.  id (never reused) and gen (bumped when the tables move) name
+// the tables in the graph key of an indexed call.
+struct icet_keyframe_store {
+    icet_ctx* ctx = nullptr;
+    icet_params shape{};                       // bins_phi, bins_theta, n, thresh, buff, flags & (TRUE_SORT | HALF_GAP_BOUNDS); runlen 0
+    int V = 0; int32_t capacity = 0;
+    SlotHot* hotS = nullptr; SlotFit* fitS = nullptr; int16_t* slot_of_voxel = nullptr; int32_t* n_slots = nullptr;
+    std::vector<uint8_t> occupied;             // capacity: the rows a put has filled
+    int64_t id = 0, gen = 0;
+    std::string err;
 };
 
 namespace {
@@ -629,12 +644,15 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
 // (LaunchCfg::kf_of).  The plain point pass and solve: no fused launch, no keep list.
 // d_score != nullptr: one more point pass at the final transform records and the score (icet_score.hip) behind the loop; `iters` (default runlen): 0 scores the
 // poses d_x0 without iterating.
-icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1) {
+// src: the keyframe tables the registrations read -- nullptr: the context's parked keyframe; a store: its rows (h_kf_of then holds slot indices).
+icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1,
+                            const icet_keyframe_store* src = nullptr) {
     if (iters < 0) iters = p->runlen;
     Workspace& w = c->w;
     LaunchCfg cfg = make_cfg(c, p, n_regs, c->h_desc_reg, nullptr);
     cfg.pair_user = nullptr; cfg.done_flag = nullptr; cfg.keep = 0; cfg.fuse_solve = 0; cfg.kf_of = w.kf_of;
     Workspace wl = w; wl.desc = w.desc_reg; wl.seg_off = w.kf_of;           // (k_init_state / k_upload_desc copy the keyframe index as their "segment" table: n_regs + 1 words)
+    if (src) { wl.hotS = src->hotS; wl.fitS = src->fitS; wl.slot_of_voxel = src->slot_of_voxel; wl.n_slots = src->n_slots; }
     // a small batch without the scan-2 round trip: k_init_state, the loop's first kernel, copies the staging itself (a replayed graph re-reads it then)
     const bool init_uploads = n_regs <= kUploadDescMaxPairs && !cfg.rt2;
     if (!init_uploads) {
@@ -904,7 +922,9 @@ extern "C++" {
 // every replay, and patched with device-side row counts where the caller has them); what the launches themselves depend on is the LaunchCfg
 // (grids, LDS sizes, point counts passed by value) and the workspace pointers.  A call whose key equals the previous call's is captured;
 // later calls with that key replay: one hipGraphLaunch instead of 15 - 35 launches on the host.
-static icet_ctx::GraphKey graph_key_of(icet_ctx* c, const icet_params* p, int32_t n_pairs, const void* a0, const void* a1, const void* a2, const void* a3, PairDesc* hd = nullptr) {
+// src_id / src_gen: the keyframe tables of an indexed call -- 0 / 0 the context's own, else a store's identity and generation (icet_keyframe_store)
+static icet_ctx::GraphKey graph_key_of(icet_ctx* c, const icet_params* p, int32_t n_pairs, const void* a0, const void* a1, const void* a2, const void* a3, PairDesc* hd = nullptr,
+                                       int64_t src_id = 0, int64_t src_gen = 0) {
     icet_ctx::GraphKey key{};
     const LaunchCfg k = make_cfg(c, p, n_pairs, hd, hd ? nullptr : c->h_seg);
     auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return (int64_t)i; };
@@ -913,7 +933,7 @@ static icet_ctx::GraphKey graph_key_of(icet_ctx* c, const icet_params* p, int32_
                             k.exec_bits_lds, k.exec_pairwise, k.lds_rank, k.reject_moving, k.half_gap, k.rt2 + 2 * k.ref_w, p->flags, (int64_t)(intptr_t)a0, (int64_t)(intptr_t)a1, (int64_t)(intptr_t)a2, (int64_t)(intptr_t)a3,
                             (int64_t)(intptr_t)c->w.desc, (int64_t)(intptr_t)c->w.thr, (int64_t)(intptr_t)c->w.lut, (int64_t)(intptr_t)c->w.r1, (int64_t)(intptr_t)c->w.counts,
                             (int64_t)(intptr_t)c->w.near_over, (int64_t)(intptr_t)c->w.acc, (int64_t)(intptr_t)c->w.fit_items, (int64_t)(intptr_t)c->w.sort_tmp, (int64_t)(intptr_t)c->w.tile_vr,
-                            c->prologue ? c->prologue_key : 0, (int64_t)(intptr_t)c->done_flag};
+                            c->prologue ? c->prologue_key : 0, (int64_t)(intptr_t)c->done_flag, src_id, src_gen};
     static_assert(sizeof(vals) == sizeof(key.v), "GraphKey size");
     std::memcpy(key.v, vals, sizeof(vals));
     return key;
@@ -1088,6 +1108,8 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
         for (int k = 0; k < n_pairs; k++) { PairDesc& d = c->h_desc[k]; d.s2 = scan2[k].ptr; d.n2 = (int32_t)scan2[k].n; d.ld2 = (int32_t)scan2[k].ld; }
         c->desc_reg_valid = true;
     }
+    s = ensure_thresholds(c, p->bins_theta, p->bins_phi);                 // (a keyframe store's call on another grid may have rebuilt them since the keyframe was parked)
+    if (s != ICET_OK) return s;
     auto enq = [&]() -> icet_status {
         if (c->prologue) HIPCHK(c, c->prologue(c->prologue_user, c->stream));
         return enqueue_loop(c, p, n_pairs, d_x0, d_out, nullptr, true, nullptr, nullptr, d_rows);
@@ -1097,21 +1119,29 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
 }
 
 // The indexed registrations of icet_register_indexed_device (mode kIdxRegister), the same followed by the score (kIdxScored: d_score), or the score of the poses
-// d_x0 alone (kIdxScoreOnly: no iteration, d_out unused).
+// d_x0 alone (kIdxScoreOnly: no iteration, d_out unused).  src: the keyframe tables -- nullptr the context's parked keyframe (kf_index: parked keyframes), or a
+// keyframe store (kf_index: its occupied slots; icet_keyframe_store_register_device and its kin).
 enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2 };
 static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
-                                    icet_score* d_score, IndexedMode mode) {
+                                    icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr) {
     if (!c) return ICET_ERR_BAD_ARG;
     const bool need_out = mode != kIdxScoreOnly, need_score = mode != kIdxRegister;
     if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (mode == kIdxScoreOnly && !d_x0)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n_regs == 0) return ICET_OK;
-    // everything is checked before anything is touched: a refused call leaves the parked keyframe as it was
-    const icet_params& q = c->kf_params;
-    if (c->kf_pairs < 1 || q.bins_phi != p->bins_phi || q.bins_theta != p->bins_theta || q.n != p->n || q.thresh != p->thresh || q.buff != p->buff ||
-        ((q.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) { c->err = "no keyframe with these parameters is parked in this context (icet_keyframe_device)"; return ICET_ERR_BAD_ARG; }
+    // everything is checked before anything is touched: a refused call leaves the parked keyframe (and every slot of a store) as it was
+    const icet_params& q = src ? src->shape : c->kf_params;
+    const int32_t n_kf = src ? src->capacity : c->kf_pairs;
+    if (n_kf < 1 || q.bins_phi != p->bins_phi || q.bins_theta != p->bins_theta || q.n != p->n || q.thresh != p->thresh || q.buff != p->buff ||
+        ((q.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
+        c->err = src ? "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape" : "no keyframe with these parameters is parked in this context (icet_keyframe_device)";
+        return ICET_ERR_BAD_ARG;
+    }
     int64_t tot2 = 0;
     for (int r = 0; r < n_regs; r++) {
-        if (kf_index[r] < 0 || kf_index[r] >= c->kf_pairs) { c->err = "kf_index[" + std::to_string(r) + "] = " + std::to_string(kf_index[r]) + " is not a parked keyframe (0 .. " + std::to_string(c->kf_pairs - 1) + ")"; return ICET_ERR_BAD_ARG; }
+        if (src && (kf_index[r] < 0 || kf_index[r] >= n_kf || !src->occupied[(size_t)kf_index[r]])) {
+            c->err = "slot_index[" + std::to_string(r) + "] = " + std::to_string(kf_index[r]) + " is not an occupied slot of the store (capacity " + std::to_string(n_kf) + ")"; return ICET_ERR_BAD_ARG;
+        }
+        if (kf_index[r] < 0 || kf_index[r] >= n_kf) { c->err = "kf_index[" + std::to_string(r) + "] = " + std::to_string(kf_index[r]) + " is not a parked keyframe (0 .. " + std::to_string(c->kf_pairs - 1) + ")"; return ICET_ERR_BAD_ARG; }
         const icet_dev_scan& b = scan2[r];
         if (b.n < 0 || b.ld < b.n || (b.n > 0 && !b.ptr) || b.ld >= ((int64_t)1 << 30)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
         tot2 += b.n;
@@ -1135,22 +1165,24 @@ static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n
     }
     c->h_kf_of[n_regs] = 0;
     if (mode == kIdxRegister) {
-        auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out); };
-        // a replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved)
-        if (graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg), enq);
+        auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out, nullptr, -1, src); };
+        // a replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved;
+        // the keyframe source: the context's tables, or a store's identity and generation)
+        if (graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg,
+                                                                  src ? src->id : 0, src ? src->gen : 0), enq);
         return enq();
     }
     // scored calls: runlen == 0 scores X0 (results as the unscored call writes them); score-only calls score d_x0 without iterating
     const bool no_iters = mode == kIdxScoreOnly || p->runlen == 0;
     auto enq = [&]() -> icet_status {
         if (mode == kIdxScored && p->runlen == 0) { const icet_status ws = write_runlen0(c, n_regs, d_x0, d_out); if (ws != ICET_OK) return ws; }
-        return enqueue_indexed(c, p, n_regs, d_x0, d_out, d_score, no_iters ? 0 : p->runlen);
+        return enqueue_indexed(c, p, n_regs, d_x0, d_out, d_score, no_iters ? 0 : p->runlen, src);
     };
     if (graph_eligible(c, p, n_regs)) {
         // slots and keys of their own: a scored call never replays an unscored call's graph, nor the reverse (the mode is a bit of the key as well)
         const intptr_t tag = (intptr_t)c->ws_gen | ((intptr_t)mode << 56);
         return run_or_replay(c, mode == kIdxScored ? c->g_scored : c->g_score,
-                             graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>(tag), d_score, c->h_desc_reg), enq);
+                             graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>(tag), d_score, c->h_desc_reg, src ? src->id : 0, src ? src->gen : 0), enq);
     }
     return enq();
 }
@@ -1167,6 +1199,167 @@ icet_status icet_register_indexed_scored_device(icet_ctx* c, const icet_params* 
 icet_status icet_score_indexed_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
                                       const float* d_X, icet_score* d_score) {
     return register_indexed(c, p, n_regs, kf_index, scan2, d_X, nullptr, d_score, kIdxScoreOnly);
+}
+
+// ---- the keyframe store ----------------------------------------------------------------------------------------
+#define STORECHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    (s)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
+
+// The four tables of `cap` rows of V voxels; all or nothing.
+static hipError_t store_alloc(int V, int32_t cap, SlotHot*& hot, SlotFit*& fit, int16_t*& sov, int32_t*& ns) {
+    hot = nullptr; fit = nullptr; sov = nullptr; ns = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&hot), sizeof(SlotHot) * (size_t)cap * V);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fit), sizeof(SlotFit) * (size_t)cap * V);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sov), sizeof(int16_t) * (size_t)cap * ((V + 1) & ~1));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ns), sizeof(int32_t) * (size_t)cap);
+    if (e != hipSuccess) {
+        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) if (q) (void)hipFree(q);
+        hot = nullptr; fit = nullptr; sov = nullptr; ns = nullptr;
+        (void)hipGetLastError();
+    }
+    return e;
+}
+
+const char* icet_keyframe_store_last_error(const icet_keyframe_store* s) { return s ? s->err.c_str() : "null store"; }
+
+icet_status icet_keyframe_store_create(icet_ctx* c, const icet_params* p, int32_t capacity, icet_keyframe_store** out) {
+    if (out) *out = nullptr;
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!out || !p || p->bins_phi <= 0 || p->bins_theta <= 0 || p->n < 1 || capacity < 1) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if ((int64_t)p->bins_phi * p->bins_theta > kMaxVoxels) { c->err = "bins_phi*bins_theta exceeds the voxel limit (10000)"; return ICET_ERR_UNSUPPORTED; }
+    const int V = p->bins_phi * p->bins_theta;
+    if ((size_t)V * 12 + 8 + 4096 > (size_t)c->max_lds) { c->err = "grid too fine for this device's LDS (k_bin_scatter keeps 12 B per voxel in one block)"; return ICET_ERR_UNSUPPORTED; }
+    HIPCHK(c, hipSetDevice(c->device));
+    icet_keyframe_store* s = new (std::nothrow) icet_keyframe_store();
+    if (!s) { c->err = "host allocation failed"; return ICET_ERR_NOMEM; }
+    static std::atomic<int64_t> next_id{1};
+    s->ctx = c; s->V = V; s->capacity = capacity; s->id = next_id++;
+    s->shape = *p; s->shape.runlen = 0; s->shape.flags = p->flags & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS);
+    const hipError_t e = store_alloc(V, capacity, s->hotS, s->fitS, s->slot_of_voxel, s->n_slots);
+    if (e != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(e); delete s; return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    s->occupied.assign((size_t)capacity, 0);
+    const hipError_t z = hipMemsetAsync(s->n_slots, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
+    if (z != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(z); (void)icet_keyframe_store_destroy(s); return ICET_ERR_HIP; }
+    *out = s;
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_destroy(icet_keyframe_store* s) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);              // (a put or a registration may still read or write the tables)
+    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots}) if (q) (void)hipFree(q);
+    delete s;
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    if (capacity <= s->capacity) return ICET_OK;
+    icet_ctx* c = s->ctx;
+    STORECHK(s, hipSetDevice(c->device));
+    STORECHK(s, hipStreamSynchronize(c->stream));            // nothing on the stream reads the old tables any more
+    SlotHot* hot; SlotFit* fit; int16_t* sov; int32_t* ns;
+    STORECHK(s, store_alloc(s->V, capacity, hot, fit, sov, ns));
+    const size_t old = (size_t)s->capacity, V = (size_t)s->V;
+    hipError_t e = hipMemcpyAsync(hot, s->hotS, sizeof(SlotHot) * old * V, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fit, s->fitS, sizeof(SlotFit) * old * V, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sov, s->slot_of_voxel, sizeof(int16_t) * old * ((V + 1) & ~(size_t)1), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ns, s->n_slots, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ns + old, 0, sizeof(int32_t) * ((size_t)capacity - old), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) (void)hipFree(q);
+        s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+    }
+    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots}) (void)hipFree(q);
+    s->hotS = hot; s->fitS = fit; s->slot_of_voxel = sov; s->n_slots = ns;
+    s->capacity = capacity; s->occupied.resize((size_t)capacity, 0);
+    s->gen++;                                                // the tables moved: no graph captured against the old ones is replayed
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, const int32_t* slots, const icet_dev_scan* scan1, const int32_t* d_rows) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (n < 0 || (n > 0 && (!slots || !scan1))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (n == 0) return ICET_OK;
+    // everything is checked before anything is touched: a refused put leaves every slot and the context's parked keyframe as they were
+    std::vector<uint8_t> named((size_t)s->capacity, 0);
+    for (int k = 0; k < n; k++) {
+        const int32_t sl = slots[k];
+        if (sl < 0 || sl >= s->capacity) { s->err = "slots[" + std::to_string(k) + "] = " + std::to_string(sl) + " is not a slot (0 .. " + std::to_string(s->capacity - 1) + ")"; return ICET_ERR_BAD_ARG; }
+        if (named[(size_t)sl]) { s->err = "slot " + std::to_string(sl) + " is named twice in one put"; return ICET_ERR_BAD_ARG; }
+        named[(size_t)sl] = 1;
+        const icet_dev_scan& a = scan1[k];
+        if (a.n < 0 || a.ld < a.n || (a.n > 0 && !a.ptr) || a.ld >= ((int64_t)1 << 30)) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    }
+    // the build: icet_keyframe_device_n in the store's shape (a replayed graph for <= 8 scans included), then the copy into the slots, never captured
+    icet_status st = icet_keyframe_device_n(c, &s->shape, n, scan1, d_rows);
+    c->kf_pairs = 0;                                         // a put is a keyframe build on the context: its own parked keyframe is gone
+    if (st != ICET_OK) { s->err = c->err; return st; }
+    for (int first = 0; first < n; first += kStoreParkMax) {
+        const int cnt = std::min(kStoreParkMax, n - first);
+        StoreParkSlots dst{};
+        for (int k = 0; k < cnt; k++) dst.slot[k] = slots[first + k];
+        const hipError_t e = launch_keyframe_store_park(c->w, s->V, first, cnt, dst, s->hotS, s->fitS, s->slot_of_voxel, s->n_slots, c->stream);
+        if (e != hipSuccess) {
+            for (int k = first; k < n; k++) s->occupied[(size_t)slots[k]] = 0;    // (what these rows hold is unknown)
+            s->err = std::string("k_keyframe_store_park: ") + hipGetErrorString(e);
+            return ICET_ERR_HIP;
+        }
+        for (int k = 0; k < cnt; k++) s->occupied[(size_t)dst.slot[k]] = 1;
+    }
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_register_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
+                                                const icet_dev_scan* scan2, const float* d_x0, float* d_out) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    const icet_status st = register_indexed(s->ctx, p, n_regs, slot_index, scan2, d_x0, d_out, nullptr, kIdxRegister, s);
+    if (st != ICET_OK) s->err = s->ctx->err;
+    return st;
+}
+
+icet_status icet_keyframe_store_register_scored_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
+                                                       const icet_dev_scan* scan2, const float* d_x0, float* d_out, icet_score* d_score) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    const icet_status st = register_indexed(s->ctx, p, n_regs, slot_index, scan2, d_x0, d_out, d_score, kIdxScored, s);
+    if (st != ICET_OK) s->err = s->ctx->err;
+    return st;
+}
+
+icet_status icet_keyframe_store_score_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
+                                             const icet_dev_scan* scan2, const float* d_X, icet_score* d_score) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    const icet_status st = register_indexed(s->ctx, p, n_regs, slot_index, scan2, d_X, nullptr, d_score, kIdxScoreOnly, s);
+    if (st != ICET_OK) s->err = s->ctx->err;
+    return st;
+}
+
+// Test hook: one occupied slot's tables on the host (what: 0 n_slots, 1 SlotHot words, 2 SlotFit words, 3 slot_of_voxel int16).  Synchronises the context's stream.
+icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot, int32_t what, void* out, int64_t count) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    if (!out || count < 0 || slot < 0 || slot >= s->capacity || !s->occupied[(size_t)slot]) { s->err = "bad argument or empty slot"; return ICET_ERR_BAD_ARG; }
+    icet_ctx* c = s->ctx;
+    STORECHK(s, hipSetDevice(c->device));
+    STORECHK(s, hipStreamSynchronize(c->stream));
+    int32_t ns = 0;
+    STORECHK(s, hipMemcpy(&ns, s->n_slots + slot, sizeof(int32_t), hipMemcpyDeviceToHost));
+    const void* src = nullptr; int64_t cap = 0; size_t elem = 4;
+    switch (what) {
+        case 0: src = s->n_slots + slot; cap = 1; break;
+        case 1: src = s->hotS + (size_t)slot * s->V; cap = (int64_t)ns * (int64_t)(sizeof(SlotHot) / 4); break;
+        case 2: src = s->fitS + (size_t)slot * s->V; cap = (int64_t)ns * (int64_t)(sizeof(SlotFit) / 4); break;
+        case 3: src = s->slot_of_voxel + (size_t)slot * ((s->V + 1) & ~1); cap = s->V; elem = 2; break;
+        default: s->err = "unknown table id"; return ICET_ERR_BAD_ARG;
+    }
+    if (count > cap) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
+    if (count > 0) STORECHK(s, hipMemcpy(out, src, (size_t)count * elem, hipMemcpyDeviceToHost));
+    return ICET_OK;
 }
 
 // Scores of the host-pointer entry points: device + pinned, n entries.

@@ -270,6 +270,12 @@ hipError_t launch_patch_counts(const Workspace& w, const LaunchCfg& c, const int
 // -- and a replayed graph, as a memcpy node -- 10 to 60 us on this part before the next kernel starts; a kernel that reads the pinned words itself costs a launch.
 constexpr int kUploadDescMaxPairs = 64;
 hipError_t launch_upload_desc(const Workspace& w, const PairDesc* h_desc, const int32_t* h_seg, int n_pairs, hipStream_t st);   // icet_solve.hip
+// icet_kfstore.hip: the keyframe store (icet_keyframe_store_put_device) -- workspace keyframe rows first .. first + count - 1 into store rows dst.slot[0 .. count),
+// row stride V (slot_of_voxel: (V + 1) & ~1).  At most kStoreParkMax rows per launch; the destination rows are the launch's argument.
+constexpr int kStoreParkMax = 64;
+struct StoreParkSlots { int32_t slot[kStoreParkMax]; };
+hipError_t launch_keyframe_store_park(const Workspace& w, int V, int first, int count, const StoreParkSlots& dst,
+                                      SlotHot* hot_dst, SlotFit* fit_dst, int16_t* sov_dst, int32_t* n_slots_dst, hipStream_t st);
 // icet_sidetables.hip: the per-point members of the reference object, on request (pair 0 of a single-pair solve)
 hipError_t launch_side_scan1(const Workspace& w, const LaunchCfg& c, float* sph, int32_t* index, hipStream_t st);
 hipError_t launch_side_scan2(const Workspace& w, const LaunchCfg& c, const float* xf, float* pts, float* sph, int32_t* voxel, hipStream_t st);

@@ -261,6 +261,49 @@ icet_status icet_score_indexed(icet_ctx* ctx, const icet_params* p,
 icet_status icet_select_best_device(icet_ctx* ctx, int32_t n_regs, const int32_t* group, int32_t n_groups,
                                     const icet_score* d_score, const float* d_out, int32_t* d_best, float* d_best_out);
 
+/* --- the keyframe store: keyframes built once and kept, whatever else runs on the context --------------------------------------------------
+ * Loop-closure / relocalisation candidates: every k-th odometry frame's keyframe is put into a slot the caller chooses; a query registers and
+ * scores a scan against any set of slots through the indexed kernels above, without rebuilding (or keeping the raw scans of) the candidates.
+ * SHAPE.  create fixes the store's keyframe shape: bins_phi, bins_theta, n, thresh, buff and the keyframe-shaping flags ICET_FLAG_TRUE_SORT and
+ *   ICET_FLAG_HALF_GAP_BOUNDS (runlen and the other flags are ignored).  capacity >= 1.  The store BORROWS ctx (device, stream, workspace), like a
+ *   node: destroy the store before the context.  All slots start empty.  A grid above the 10 000-voxel limit: ICET_ERR_UNSUPPORTED; a failed
+ *   allocation: ICET_ERR_NOMEM (*out is left NULL).  Device memory per slot: V x (48 + 80) + 2 x ((V + 1) & ~1) + 4 bytes (234 KB at 75 x 24,
+ *   936 KB at 150 x 48).
+ * PUT.  put_device builds the keyframes of n scans and parks keyframe k in slot slots[k] (HOST array of distinct entries, 0 <= slot < capacity).
+ *   scan1 and d_rows (may be NULL) follow the rules of icet_keyframe_device_n.  A slot's tables are exactly what icet_keyframe_device_n builds for
+ *   that scan in the store's shape, whatever batch the scan was put in.  A put replaces whatever the slot held; every other slot keeps its bytes.
+ *   The store keeps no reference to the scan: its buffer may be reused once the put has run on the context's stream.  A put is a keyframe build on
+ *   the context, so it un-parks the context's own keyframe (as icet_keyframe_device does); it never touches another store.  n == 0: ICET_OK,
+ *   nothing.  Asynchronous on the context's stream; the host arrays are read before the call returns.
+ * REGISTER / SCORE.  The three calls are icet_register_indexed_device, icet_register_indexed_scored_device and icet_score_indexed_device with
+ *   kf_index replaced by slot_index (HOST array; every index must name an occupied slot; repeats and any order allowed).  p must match the store's
+ *   shape (else ICET_ERR_BAD_ARG); ICET_FLAG_ROUNDTRIP_SCAN2, REJECT_MOVING, DOUBLE_W and TIMING apply per call; option "keep" on:
+ *   ICET_ERR_UNSUPPORTED.  d_out / d_score carry exactly the bits icet_solve_batch_device / the indexed calls give for the expanded pair: the scan
+ *   put into the slot (with its d_rows count), scan2[r] and x0[r].  These calls leave every slot and the context's parked keyframe as they were.
+ * RESERVE.  reserve grows the store; every occupied slot keeps its bytes.  A smaller value: ICET_OK, nothing.  Synchronises the context's stream.
+ * REFUSALS.  Every argument is checked before anything is touched; a refused call leaves every slot and the context's parked keyframe as they
+ *   were.  ICET_ERR_BAD_ARG for a NULL store, n < 0, a slot out of range or empty, a slot named twice in one put, a bad scan descriptor, a shape
+ *   mismatch. */
+typedef struct icet_keyframe_store icet_keyframe_store;   /* opaque: slots of parked keyframe tables on one context's device */
+
+icet_status icet_keyframe_store_create(icet_ctx* ctx, const icet_params* p, int32_t capacity, icet_keyframe_store** out);
+icet_status icet_keyframe_store_destroy(icet_keyframe_store* s);
+const char* icet_keyframe_store_last_error(const icet_keyframe_store* s);   /* never NULL; "null store" for NULL */
+icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity);
+icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, const int32_t* slots,
+                                           const icet_dev_scan* scan1, const int32_t* d_rows);
+icet_status icet_keyframe_store_register_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
+                                                const icet_dev_scan* scan2, const float* d_x0, float* d_out);
+icet_status icet_keyframe_store_register_scored_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
+                                                       const icet_dev_scan* scan2, const float* d_x0, float* d_out, icet_score* d_score);
+icet_status icet_keyframe_store_score_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
+                                             const icet_dev_scan* scan2, const float* d_X, icet_score* d_score);
+/* Test hook, like icet_debug_fetch: one OCCUPIED slot's tables on the host; synchronises the context's stream.  what = 0: n_slots (1 int32);
+ * 1: the SlotHot records (12 words each: cluster_bounds row, mu1, voxel, 2 pad), count <= n_slots x 12; 2: the SlotFit records (20 words each:
+ * mu1, sigma1 upper triangle / (n1_raw - 1), M = diag(l_diag) x evecs1 row-major, n1, voxel), count <= n_slots x 20; 3: slot_of_voxel (int16,
+ * -1 = no slot), count <= V. */
+icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot, int32_t what, void* out, int64_t count);
+
 /* Pre-size the workspace (so the first timed call does not allocate). */
 icet_status icet_reserve(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2);
 
