@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
                     "icet_keyframe_store_create", "icet_keyframe_store_destroy", "icet_keyframe_store_last_error", "icet_keyframe_store_reserve", "icet_keyframe_store_put_device",
                     "icet_keyframe_store_register_device", "icet_keyframe_store_register_scored_device", "icet_keyframe_store_score_device", "icet_keyframe_store_debug_fetch",
+                    "icet_keyframe_store_set_pose", "icet_keyframe_store_candidates_device", "icet_keyframe_store_close_device", "icet_pose_step_from_x",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
@@ -37,7 +38,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_node_group_prev_scan", "icet_node_group_aligned", "icet_node_group_snail_trail",
                     "icet_load_scan", "icet_free_scan", "icet_save_scan_npy")
 _NON_STATUS = ("icet_version", "icet_last_error", "icet_node_last_error", "icet_node_group_last_error", "icet_stream", "icet_device", "icet_free_scan", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
-               "icet_keyframe_store_last_error")
+               "icet_keyframe_store_last_error", "icet_pose_step_from_x")
 
 
 class IcetError(RuntimeError):
@@ -55,6 +56,39 @@ class Params(C.Structure):
 SCORE_DTYPE = np.dtype([("chi2", "<f4"), ("chi2_per_voxel", "<f4"), ("voxels", "<i4"), ("points_in", "<i4"), ("points", "<i4"), ("overlap", "<f4"),
                         ("reserved", "<i4", (2,))])
 assert SCORE_DTYPE.itemsize == 32
+
+
+class ClosureQuery(C.Structure):
+    """icet_closure_query (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("radius", C.c_float), ("max_candidates", C.c_int32), ("min_stamp_gap", C.c_int64), ("n_starts", C.c_int32),
+                ("max_chi2_per_voxel", C.c_float), ("min_voxels", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Score(C.Structure):
+    """icet_score (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("chi2", C.c_float), ("chi2_per_voxel", C.c_float), ("voxels", C.c_int32), ("points_in", C.c_int32), ("points", C.c_int32),
+                ("overlap", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class Closure(C.Structure):
+    """icet_closure (include/icet_hip.h), 288 bytes: one record per query of icet_keyframe_store_close_device."""
+    _fields_ = [("slot", C.c_int32), ("reg", C.c_int32), ("accepted", C.c_int32), ("n_candidates", C.c_int32), ("stamp", C.c_int64), ("d2", C.c_float),
+                ("reserved0", C.c_int32), ("x0", C.c_float * 6), ("reserved1", C.c_int32 * 2), ("out", C.c_float * 48), ("score", Score)]
+
+
+# the same record as a NumPy dtype (a device buffer of records comes back as bytes)
+CLOSURE_DTYPE = np.dtype([("slot", "<i4"), ("reg", "<i4"), ("accepted", "<i4"), ("n_candidates", "<i4"), ("stamp", "<i8"), ("d2", "<f4"), ("reserved0", "<i4"),
+                          ("x0", "<f4", (6,)), ("reserved1", "<i4", (2,)), ("out", "<f4", (48,)), ("score", SCORE_DTYPE)])
+assert CLOSURE_DTYPE.itemsize == 288 == C.sizeof(Closure) and C.sizeof(ClosureQuery) == 32 and C.sizeof(Score) == 32
+
+
+def pose_step_from_X(X):
+    """One step of a pose chain from a registration result X (icet_pose_step_from_x): the 4 x 4 float32 T = [R(X)^T | R(X)^T X_t]; a caller chains
+    T_world,k = T_world,k-1 @ T.  This is the PHYSICAL sensor motion, not the chain icet_node_result.pose keeps (include/icet_hip.h, POSE)."""
+    x = np.ascontiguousarray(np.asarray(X, np.float32).reshape(6))
+    T = np.zeros(16, np.float32)
+    load_library().icet_pose_step_from_x(x.ctypes.data, T.ctypes.data)
+    return T.reshape(4, 4)
 
 
 def scores_as_dict(rec):
@@ -143,6 +177,11 @@ def load_library():
     L.icet_keyframe_store_register_scored_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_score_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_debug_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+    L.icet_keyframe_store_set_pose.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_candidates_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(ClosureQuery), C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_close_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.POINTER(ClosureQuery), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_pose_step_from_x.argtypes = [C.c_void_p, C.c_void_p]; L.icet_pose_step_from_x.restype = None
     L.icet_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
     L.icet_multi_destroy.argtypes = [C.c_void_p]
     L.icet_multi_last_error.argtypes = [C.c_void_p]; L.icet_multi_last_error.restype = C.c_char_p
@@ -598,8 +637,17 @@ class KeyframeStore:
 
     def debug_fetch(self, slot, what, count=None):
         """Diagnostic: one occupied slot's tables -- 'n_slots' (int), 'hot' ((n_slots, 12) words of SlotHot), 'fit' ((n_slots, 20) words of SlotFit),
-        'slot_of_voxel' (int16, V).  Words are returned as uint32 (view them as float32 / int32)."""
+        'slot_of_voxel' (int16, V), 'pose' (4 x 4 float32, NaN entries without a pose), 'stamp' (int; -1 without a pose).  Words are returned as uint32
+        (view them as float32 / int32)."""
         L = load_library()
+        if what == "pose":
+            out = np.zeros(16, np.float32)
+            self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 4, out.ctypes.data, 16))
+            return out.reshape(4, 4)
+        if what == "stamp":
+            out = np.zeros(1, np.int64)
+            self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 5, out.ctypes.data, 1))
+            return int(out[0])
         ns = np.zeros(1, np.int32)
         self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 0, ns.ctypes.data, 1))
         ns = int(ns[0])
@@ -613,6 +661,84 @@ class KeyframeStore:
         out = np.zeros(ns * words if count is None else int(count), np.uint32)
         self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), code, out.ctypes.data, out.size))
         return out.reshape(-1, words) if count is None else out
+
+    @staticmethod
+    def _poses(poses, stamps):
+        T = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
+        st = np.ascontiguousarray(np.asarray(stamps, np.int64).reshape(-1))
+        if T.shape[0] != st.shape[0]:
+            raise IcetError(ICET_ERR_BAD_ARG, "poses and stamps differ in length")
+        return T, st
+
+    def set_pose(self, slots, poses, stamps):
+        """Give occupied slots a pose (4 x 4 float32 each: the physical sensor pose, p_world = R p + t) and an int64 stamp
+        (icet_keyframe_store_set_pose).  In stream order with puts and queries; a later put into a slot clears its pose."""
+        T, st = self._poses(poses, stamps)
+        sl = self._index(slots, T.shape[0])
+        self._check(load_library().icet_keyframe_store_set_pose(self._h, T.shape[0], sl.ctypes.data, T.ctypes.data, st.ctypes.data))
+
+    def candidates_device(self, poses, stamps, query, d_cand_ptr, d_x0_base_ptr=None):
+        """icet_keyframe_store_candidates_device: the search alone, into device buffers (Q x K int32; Q x K x 6 float32 or None).  Asynchronous."""
+        T, st = self._poses(poses, stamps)
+        self._check(load_library().icet_keyframe_store_candidates_device(self._h, T.shape[0], T.ctypes.data, st.ctypes.data, C.byref(query), C.c_void_p(d_cand_ptr),
+                                                                          C.c_void_p(d_x0_base_ptr) if d_x0_base_ptr else None))
+
+    def candidates(self, poses, stamps, radius, k, min_stamp_gap=0):
+        """Place recognition by pose: for every query pose the first ``k`` eligible slots in ascending (d2, slot) order (include/icet_hip.h, CANDIDATES).
+        Returns (cand, x0_base): (Q, k) int32 with -1 behind the last, and (Q, k, 6) float32 start poses (zeros for -1)."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        T, st = self._poses(poses, stamps)
+        q = T.shape[0]
+        cand = torch.full((q, int(k)), -2, dtype=torch.int32, device=dev)
+        x0 = torch.zeros((q, int(k), 6), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.candidates_device(T, st, ClosureQuery(float(radius), int(k), int(min_stamp_gap), 1, float("inf"), 0, 0), cand.data_ptr(), x0.data_ptr())
+        self._ctx.sync()
+        return cand.cpu().numpy(), x0.cpu().numpy()
+
+    def close_device(self, scan2_descs, poses, stamps, params, query, d_closure_ptr, start_offsets=None, d_cand_ptr=None, d_x0_ptr=None, d_out_ptr=None, d_score_ptr=None):
+        """icet_keyframe_store_close_device: find, register, score, pick and gate, one record (CLOSURE_DTYPE) per scan.  Asynchronous on the context's stream."""
+        T, st = self._poses(poses, stamps)
+        q = len(scan2_descs)
+        if T.shape[0] != q:
+            raise IcetError(ICET_ERR_BAD_ARG, "scans and poses differ in length")
+        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        off = None
+        if start_offsets is not None:
+            off = np.ascontiguousarray(np.asarray(start_offsets, np.float32).reshape(-1, 6))
+            if off.shape[0] != query.n_starts:
+                raise IcetError(ICET_ERR_BAD_ARG, "start_offsets must hold n_starts rows of 6")
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._check(load_library().icet_keyframe_store_close_device(self._h, C.byref(params), q, B, T.ctypes.data, st.ctypes.data, C.byref(query),
+                                                                     off.ctypes.data if off is not None else None, C.c_void_p(d_closure_ptr),
+                                                                     vp(d_cand_ptr), vp(d_x0_ptr), vp(d_out_ptr), vp(d_score_ptr)))
+
+    def find_closures(self, scans, poses, stamps, runlen, radius, k, starts=None, min_stamp_gap=0, max_chi2_per_voxel=float("inf"), min_voxels=0, flags=0):
+        """The loop-closure query for host scans (N x 3 each) with their poses and stamps: one dict per scan -- slot (None: no winner), accepted, reg,
+        n_candidates, stamp, d2, x0, X, pred_stds, cov, score -- from one icet_keyframe_store_close_device call.  ``starts``: S x 6 offsets added to each
+        candidate's start pose (default: one start, no offset)."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        off = np.zeros((1, 6), np.float32) if starts is None else np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        rec = torch.zeros((len(bufs), CLOSURE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        query = ClosureQuery(float(radius), int(k), int(min_stamp_gap), off.shape[0], float(max_chi2_per_voxel), int(min_voxels), 0)
+        self.close_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], poses, stamps, self._params(runlen, flags), query, rec.data_ptr(), off)
+        self._ctx.sync()
+        recs = np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE)
+        res = []
+        for r in recs:
+            d = dict(slot=None if r["slot"] < 0 else int(r["slot"]), reg=int(r["reg"]), accepted=bool(r["accepted"]), n_candidates=int(r["n_candidates"]))
+            if d["slot"] is None:
+                d.update(stamp=None, d2=None, x0=None, X=None, pred_stds=None, cov=None, score=None)
+            else:
+                o = np.array(r["out"])
+                d.update(stamp=int(r["stamp"]), d2=float(r["d2"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(), cov=o[12:48].reshape(6, 6).copy(),
+                         score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")})
+            res.append(d)
+        return res
 
     def best_match(self, scan2, slot_index, x0, runlen, flags=0):
         """The loop-closure check: registration r = host scan2 (N x 3) against slot slot_index[r] from x0[r]; all of them one group, scored and

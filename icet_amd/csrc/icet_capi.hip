@@ -8,6 +8,7 @@
 #include "../../include/icet_nodes.h"
 #include "icet_internal.h"
 #include "icet_layout.h"
+#include "icet_closure.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -109,6 +110,16 @@ struct icet_keyframe_store {
     std::vector<uint8_t> occupied;             // capacity: the rows a put has filled
     int64_t id = 0, gen = 0;
     std::string err;
+    // the pose table: ONE allocation of capacity x 56 bytes at pose_stamp -- stamp[capacity] | tx | ty | tz | r0 .. r8 --, 0xFF bytes
+    // (NaN, stamp -1) where a slot has no pose; set_pose stages through h_pose (pinned), which its kernel reads when it runs (ev_pose: it has)
+    int64_t* pose_stamp = nullptr;
+    PoseTable pose_table() const { return PoseTable{pose_stamp, reinterpret_cast<float*>(pose_stamp + capacity), capacity}; }
+    PoseUpload* h_pose = nullptr; int32_t cap_h_pose = 0; hipEvent_t ev_pose = nullptr; bool pose_in_flight = false;
+    // buffers of a query (icet_keyframe_store_close_device), grown on demand: the search's per-tile lists; per (query, candidate); per registration; per query
+    unsigned long long* q_part = nullptr; size_t cap_part = 0;
+    unsigned long long* q_keys = nullptr; int32_t* q_cand = nullptr; int32_t cap_qk = 0;
+    float* q_x0 = nullptr; float* q_out = nullptr; icet_score* q_score = nullptr; int32_t* q_kf_of = nullptr; int32_t* q_rows = nullptr; int32_t* q_members = nullptr; int32_t cap_qr = 0;
+    int32_t* q_offs = nullptr; int32_t* q_best = nullptr;       // kClosureMaxQueries + 1, kClosureMaxQueries
 };
 
 namespace {
@@ -645,8 +656,13 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
 // d_score != nullptr: one more point pass at the final transform records and the score (icet_score.hip) behind the loop; `iters` (default runlen): 0 scores the
 // poses d_x0 without iterating.
 // src: the keyframe tables the registrations read -- nullptr: the context's parked keyframe; a store: its rows (h_kf_of then holds slot indices).
+// dev: the keyframe index and the scan-2 row counts of the registrations are known to the DEVICE only (a loop-closure query, whose candidates a kernel found a
+// moment ago on the same stream): the staging holds an occupied slot and the scans' full row counts -- the launch geometry is sized from those, as in
+// icet_register_device_n --, and behind the descriptor upload rows[r] replaces the count (k_init_state, or k_patch_counts in front of the scan-2 round trip) and
+// kf_of[r] the index.
+struct IndexedDev { const int32_t* kf_of; const int32_t* rows; };
 icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1,
-                            const icet_keyframe_store* src = nullptr) {
+                            const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr) {
     if (iters < 0) iters = p->runlen;
     Workspace& w = c->w;
     LaunchCfg cfg = make_cfg(c, p, n_regs, c->h_desc_reg, nullptr);
@@ -667,9 +683,11 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
     while ((int)c->ev_acc.size() < 2 * p->runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_b, c->stream));        // (no keyframe build in this call: keyframe_ms = 0)
+    if (cfg.rt2 && dev) HIPCHK(c, launch_patch_counts(wl, cfg, nullptr, dev->rows, c->stream));      // (the pre-pass reads the counts of the caller's descriptors)
     if (cfg.rt2) { const icet_status rs = enqueue_rt2(c, cfg, n_regs, c->h_desc_reg, wl, nullptr); if (rs != ICET_OK) return rs; }
     LaunchCfg lcfg = cfg; if (cfg.rt2) lcfg.vec4_ok = 1;                     // the copy is 64-float aligned whatever the caller's layout was
-    HIPCHK(c, launch_init_state(wl, lcfg, d_x0, c->stream, nullptr, nullptr, init_uploads ? c->h_desc_reg : nullptr, init_uploads ? c->h_kf_of : nullptr));
+    HIPCHK(c, launch_init_state(wl, lcfg, d_x0, c->stream, nullptr, dev ? dev->rows : nullptr, init_uploads ? c->h_desc_reg : nullptr, init_uploads ? c->h_kf_of : nullptr));
+    if (dev) HIPCHK(c, launch_closure_apply(w.kf_of, dev->kf_of, n_regs, c->stream));
     if (init_uploads && !c->capturing) {
         if (!c->ev_desc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
@@ -1123,7 +1141,7 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
 // keyframe store (kf_index: its occupied slots; icet_keyframe_store_register_device and its kin).
 enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2 };
 static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
-                                    icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr) {
+                                    icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr) {
     if (!c) return ICET_ERR_BAD_ARG;
     const bool need_out = mode != kIdxScoreOnly, need_score = mode != kIdxRegister;
     if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (mode == kIdxScoreOnly && !d_x0)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
@@ -1165,10 +1183,10 @@ static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n
     }
     c->h_kf_of[n_regs] = 0;
     if (mode == kIdxRegister) {
-        auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out, nullptr, -1, src); };
+        auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out, nullptr, -1, src, dev); };
         // a replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved;
         // the keyframe source: the context's tables, or a store's identity and generation)
-        if (graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg,
+        if (!dev && graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg,
                                                                   src ? src->id : 0, src ? src->gen : 0), enq);
         return enq();
     }
@@ -1176,9 +1194,9 @@ static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n
     const bool no_iters = mode == kIdxScoreOnly || p->runlen == 0;
     auto enq = [&]() -> icet_status {
         if (mode == kIdxScored && p->runlen == 0) { const icet_status ws = write_runlen0(c, n_regs, d_x0, d_out); if (ws != ICET_OK) return ws; }
-        return enqueue_indexed(c, p, n_regs, d_x0, d_out, d_score, no_iters ? 0 : p->runlen, src);
+        return enqueue_indexed(c, p, n_regs, d_x0, d_out, d_score, no_iters ? 0 : p->runlen, src, dev);
     };
-    if (graph_eligible(c, p, n_regs)) {
+    if (!dev && graph_eligible(c, p, n_regs)) {                           // (a query is never captured: its search kernels take this call's poses as arguments)
         // slots and keys of their own: a scored call never replays an unscored call's graph, nor the reverse (the mode is a bit of the key as well)
         const intptr_t tag = (intptr_t)c->ws_gen | ((intptr_t)mode << 56);
         return run_or_replay(c, mode == kIdxScored ? c->g_scored : c->g_score,
@@ -1205,6 +1223,8 @@ icet_status icet_score_indexed_device(icet_ctx* c, const icet_params* p, int32_t
 #define STORECHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     (s)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
     return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
+
+constexpr size_t kPoseBytes = sizeof(int64_t) + 12 * sizeof(float);      // the pose table, per slot (icet_keyframe_store::pose_table)
 
 // The four tables of `cap` rows of V voxels; all or nothing.
 static hipError_t store_alloc(int V, int32_t cap, SlotHot*& hot, SlotFit*& fit, int16_t*& sov, int32_t*& ns) {
@@ -1239,7 +1259,10 @@ icet_status icet_keyframe_store_create(icet_ctx* c, const icet_params* p, int32_
     const hipError_t e = store_alloc(V, capacity, s->hotS, s->fitS, s->slot_of_voxel, s->n_slots);
     if (e != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(e); delete s; return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
     s->occupied.assign((size_t)capacity, 0);
-    const hipError_t z = hipMemsetAsync(s->n_slots, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
+    hipError_t z = hipMalloc(reinterpret_cast<void**>(&s->pose_stamp), kPoseBytes * (size_t)capacity);
+    if (z != hipSuccess) { (void)hipGetLastError(); c->err = std::string("keyframe store: ") + hipGetErrorString(z); s->pose_stamp = nullptr; (void)icet_keyframe_store_destroy(s); return z == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    z = hipMemsetAsync(s->pose_stamp, 0xFF, kPoseBytes * (size_t)capacity, c->stream);      // no slot has a pose
+    if (z == hipSuccess) z = hipMemsetAsync(s->n_slots, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
     if (z != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(z); (void)icet_keyframe_store_destroy(s); return ICET_ERR_HIP; }
     *out = s;
     return ICET_OK;
@@ -1249,7 +1272,10 @@ icet_status icet_keyframe_store_destroy(icet_keyframe_store* s) {
     if (!s) return ICET_ERR_BAD_ARG;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);              // (a put or a registration may still read or write the tables)
-    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots, (void*)s->pose_stamp, (void*)s->q_part, (void*)s->q_keys, (void*)s->q_cand,
+                    (void*)s->q_x0, (void*)s->q_out, (void*)s->q_score, (void*)s->q_kf_of, (void*)s->q_rows, (void*)s->q_members, (void*)s->q_offs, (void*)s->q_best}) if (q) (void)hipFree(q);
+    if (s->h_pose) (void)hipHostFree(s->h_pose);
+    if (s->ev_pose) (void)hipEventDestroy(s->ev_pose);
     delete s;
     return ICET_OK;
 }
@@ -1263,7 +1289,19 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
     SlotHot* hot; SlotFit* fit; int16_t* sov; int32_t* ns;
     STORECHK(s, store_alloc(s->V, capacity, hot, fit, sov, ns));
     const size_t old = (size_t)s->capacity, V = (size_t)s->V;
-    hipError_t e = hipMemcpyAsync(hot, s->hotS, sizeof(SlotHot) * old * V, hipMemcpyDeviceToDevice, c->stream);
+    int64_t* pose = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&pose), kPoseBytes * (size_t)capacity);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) (void)hipFree(q);
+        s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+    }
+    // poses and stamps: the new table starts empty (0xFF), then every array's first `old` entries are carried over
+    e = hipMemsetAsync(pose, 0xFF, kPoseBytes * (size_t)capacity, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(pose, s->pose_stamp, sizeof(int64_t) * old, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(pose + capacity, sizeof(float) * (size_t)capacity, s->pose_stamp + old, sizeof(float) * old, sizeof(float) * old, 12, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hot, s->hotS, sizeof(SlotHot) * old * V, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(fit, s->fitS, sizeof(SlotFit) * old * V, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(sov, s->slot_of_voxel, sizeof(int16_t) * old * ((V + 1) & ~(size_t)1), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ns, s->n_slots, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
@@ -1271,11 +1309,12 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) (void)hipFree(q);
+        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose}) (void)hipFree(q);
         s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
     }
-    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots}) (void)hipFree(q);
+    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots, (void*)s->pose_stamp}) (void)hipFree(q);
+    s->pose_stamp = pose;
     s->hotS = hot; s->fitS = fit; s->slot_of_voxel = sov; s->n_slots = ns;
     s->capacity = capacity; s->occupied.resize((size_t)capacity, 0);
     s->gen++;                                                // the tables moved: no graph captured against the old ones is replayed
@@ -1312,6 +1351,8 @@ icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, co
             return ICET_ERR_HIP;
         }
         for (int k = 0; k < cnt; k++) s->occupied[(size_t)dst.slot[k]] = 1;
+        const hipError_t pe = launch_closure_clear_pose(s->pose_table(), dst, cnt, c->stream);      // a new keyframe: whatever pose the slot had is not its pose
+        if (pe != hipSuccess) { s->err = std::string("k_closure_clear_pose: ") + hipGetErrorString(pe); return ICET_ERR_HIP; }
     }
     return ICET_OK;
 }
@@ -1349,8 +1390,19 @@ icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot
     STORECHK(s, hipStreamSynchronize(c->stream));
     int32_t ns = 0;
     STORECHK(s, hipMemcpy(&ns, s->n_slots + slot, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (what == 4) {                                          // the pose: 12 strided floats into a row-major 4 x 4
+        if (count > 16) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
+        float tR[12], T[16];
+        const PoseTable tab = s->pose_table();
+        STORECHK(s, hipMemcpy2D(tR, sizeof(float), tab.f + slot, sizeof(float) * (size_t)tab.cap, sizeof(float), 12, hipMemcpyDeviceToHost));
+        for (int a = 0; a < 3; a++) { for (int b = 0; b < 3; b++) T[4 * a + b] = tR[3 + 3 * a + b]; T[4 * a + 3] = tR[a]; }
+        T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+        std::memcpy(out, T, sizeof(float) * (size_t)count);
+        return ICET_OK;
+    }
     const void* src = nullptr; int64_t cap = 0; size_t elem = 4;
     switch (what) {
+        case 5: src = s->pose_stamp + slot; cap = 1; elem = 8; break;
         case 0: src = s->n_slots + slot; cap = 1; break;
         case 1: src = s->hotS + (size_t)slot * s->V; cap = (int64_t)ns * (int64_t)(sizeof(SlotHot) / 4); break;
         case 2: src = s->fitS + (size_t)slot * s->V; cap = (int64_t)ns * (int64_t)(sizeof(SlotFit) / 4); break;
@@ -1359,6 +1411,154 @@ icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot
     }
     if (count > cap) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
     if (count > 0) STORECHK(s, hipMemcpy(out, src, (size_t)count * elem, hipMemcpyDeviceToHost));
+    return ICET_OK;
+}
+
+// ---- the loop-closure query ------------------------------------------------------------------------------------
+void icet_pose_step_from_x(const float X[6], float T[16]) { if (X && T) icet_closure_rule::pose_step_from_X(X, T); }
+
+icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, const int32_t* slots, const float* poses, const int64_t* stamps) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (n < 0 || (n > 0 && (!slots || !poses || !stamps))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (n == 0) return ICET_OK;
+    std::vector<uint8_t> named((size_t)s->capacity, 0);
+    for (int k = 0; k < n; k++) {
+        const int32_t sl = slots[k];
+        if (sl < 0 || sl >= s->capacity || !s->occupied[(size_t)sl]) { s->err = "slots[" + std::to_string(k) + "] = " + std::to_string(sl) + " is not an occupied slot of the store (capacity " + std::to_string(s->capacity) + ")"; return ICET_ERR_BAD_ARG; }
+        if (named[(size_t)sl]) { s->err = "slot " + std::to_string(sl) + " is named twice in one set_pose"; return ICET_ERR_BAD_ARG; }
+        named[(size_t)sl] = 1;
+    }
+    STORECHK(s, hipSetDevice(c->device));
+    if (s->pose_in_flight) { STORECHK(s, hipEventSynchronize(s->ev_pose)); s->pose_in_flight = false; }      // the previous set_pose's kernel has read the staging
+    if (n > s->cap_h_pose) {
+        if (s->h_pose) { STORECHK(s, hipHostFree(s->h_pose)); s->h_pose = nullptr; s->cap_h_pose = 0; }
+        STORECHK(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_pose), sizeof(PoseUpload) * (size_t)n));
+        s->cap_h_pose = n;
+    }
+    if (!s->ev_pose) STORECHK(s, hipEventCreateWithFlags(&s->ev_pose, hipEventDisableTiming));
+    for (int k = 0; k < n; k++) {
+        PoseUpload& u = s->h_pose[k];
+        const float* T = poses + 16 * (size_t)k;
+        u.slot = slots[k]; u.pad = 0; u.stamp = stamps[k];
+        for (int a = 0; a < 3; a++) { u.tR[a] = T[4 * a + 3]; for (int b = 0; b < 3; b++) u.tR[3 + 3 * a + b] = T[4 * a + b]; }
+    }
+    c->armed_calls = 2;
+    STORECHK(s, launch_closure_set_pose(s->pose_table(), s->h_pose, n, c->stream));
+    STORECHK(s, hipEventRecord(s->ev_pose, c->stream)); s->pose_in_flight = true;
+    return ICET_OK;
+}
+
+// The arguments of a query that both entry points share; K, S as the query names them.
+static icet_status closure_query_ok(icet_keyframe_store* s, int32_t n_queries, const float* poses, const int64_t* stamps, const icet_closure_query* q) {
+    if (n_queries < 1 || n_queries > kClosureMaxQueries) { s->err = "n_queries must be 1 .. " + std::to_string(kClosureMaxQueries); return ICET_ERR_BAD_ARG; }
+    if (!poses || !stamps || !q) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (q->max_candidates < 1 || q->max_candidates > kClosureMaxCandidates) { s->err = "max_candidates must be 1 .. " + std::to_string(kClosureMaxCandidates); return ICET_ERR_BAD_ARG; }
+    if (!(q->radius >= 0.f)) { s->err = "radius must be a number >= 0"; return ICET_ERR_BAD_ARG; }
+    return ICET_OK;
+}
+
+static icet_status closure_ensure(icet_keyframe_store* s, int32_t n_queries, int K, int n_regs) {
+    icet_ctx* c = s->ctx;
+    const size_t need_part = (size_t)n_queries * (size_t)closure_tiles(s->capacity) * (size_t)K;
+    const int32_t qk = n_queries * K;
+    if (need_part <= s->cap_part && qk <= s->cap_qk && n_regs <= s->cap_qr && s->q_offs) return ICET_OK;
+    STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
+    if (!s->q_offs) { STORECHK(s, dev_realloc(s->q_offs, (size_t)kClosureMaxQueries + 1)); STORECHK(s, dev_realloc(s->q_best, (size_t)kClosureMaxQueries)); }
+    if (need_part > s->cap_part) { s->cap_part = 0; STORECHK(s, dev_realloc(s->q_part, need_part)); s->cap_part = need_part; }
+    if (qk > s->cap_qk) { s->cap_qk = 0; STORECHK(s, dev_realloc(s->q_keys, (size_t)qk)); STORECHK(s, dev_realloc(s->q_cand, (size_t)qk)); s->cap_qk = qk; }
+    if (n_regs > s->cap_qr) {
+        s->cap_qr = 0;
+        const size_t r = (size_t)n_regs;
+        STORECHK(s, dev_realloc(s->q_x0, r * 6)); STORECHK(s, dev_realloc(s->q_out, r * 48)); STORECHK(s, dev_realloc(s->q_score, r));
+        STORECHK(s, dev_realloc(s->q_kf_of, r)); STORECHK(s, dev_realloc(s->q_rows, r)); STORECHK(s, dev_realloc(s->q_members, r));
+        s->cap_qr = n_regs;
+    }
+    return ICET_OK;
+}
+
+static void closure_args(int32_t n_queries, const float* poses, const int64_t* stamps, const float* start_offsets, int n_starts, ClosureSearchArgs& qa, ClosurePoseArgs& pa) {
+    std::memset(&qa, 0, sizeof(qa)); std::memset(&pa, 0, sizeof(pa));
+    for (int q = 0; q < n_queries; q++) {
+        const float* T = poses + 16 * (size_t)q;
+        qa.tx[q] = T[3]; qa.ty[q] = T[7]; qa.tz[q] = T[11]; qa.stamp[q] = stamps[q];
+        for (int a = 0; a < 3; a++) { pa.t[q][a] = T[4 * a + 3]; for (int b = 0; b < 3; b++) pa.R[q][3 * a + b] = T[4 * a + b]; }
+    }
+    if (start_offsets) for (int i = 0; i < n_starts; i++) for (int k = 0; k < 6; k++) pa.off[i][k] = start_offsets[6 * i + k];
+}
+
+icet_status icet_keyframe_store_candidates_device(icet_keyframe_store* s, int32_t n_queries, const float* poses, const int64_t* stamps,
+                                                  const icet_closure_query* query, int32_t* d_cand, float* d_x0_base) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    icet_status st = closure_query_ok(s, n_queries, poses, stamps, query);
+    if (st != ICET_OK) return st;
+    if (!d_cand) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    STORECHK(s, hipSetDevice(c->device));
+    const int K = query->max_candidates;
+    st = closure_ensure(s, n_queries, K, 0);
+    if (st != ICET_OK) return st;
+    ClosureSearchArgs qa; ClosurePoseArgs pa;
+    closure_args(n_queries, poses, stamps, nullptr, 0, qa, pa);
+    c->armed_calls = 2;
+    const PoseTable tab = s->pose_table();
+    STORECHK(s, launch_closure_search(tab, qa, n_queries, K, query->radius, query->min_stamp_gap, s->q_part, d_cand, s->q_keys, c->stream));
+    if (d_x0_base) STORECHK(s, launch_closure_resolve(tab, pa, n_queries, K, 0, -1, d_cand, d_x0_base, nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_close_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
+                                             const float* poses, const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
+                                             icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score) {
+    static_assert(sizeof(icet_closure) == 288 && sizeof(icet_closure) % 16 == 0 && sizeof(icet_closure_query) == 32, "the records of the query (include/icet_hip.h; the ctypes mirrors of icet_amd/api.py)");
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    // everything is checked before anything is touched
+    icet_status st = closure_query_ok(s, n_queries, poses, stamps, query);
+    if (st != ICET_OK) return st;
+    if (!params_ok(p) || !scan2 || !d_closure) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (query->n_starts < 1 || query->n_starts > kClosureMaxStarts) { s->err = "n_starts must be 1 .. " + std::to_string(kClosureMaxStarts); return ICET_ERR_BAD_ARG; }
+    const icet_params& sh = s->shape;
+    if (sh.bins_phi != p->bins_phi || sh.bins_theta != p->bins_theta || sh.n != p->n || sh.thresh != p->thresh || sh.buff != p->buff ||
+        ((sh.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
+        s->err = "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG;
+    }
+    for (int q = 0; q < n_queries; q++) {
+        const icet_dev_scan& b = scan2[q];
+        if (b.n < 0 || b.ld < b.n || (b.n > 0 && !b.ptr) || b.ld >= ((int64_t)1 << 30)) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    }
+    if (c->tune.keep != 0) { s->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
+    STORECHK(s, hipSetDevice(c->device));
+    const int K = query->max_candidates, S = query->n_starts, R = n_queries * K * S;
+    st = closure_ensure(s, n_queries, K, R);
+    if (st != ICET_OK) return st;
+    int32_t any = -1;
+    for (int32_t j = 0; j < s->capacity && any < 0; j++) if (s->occupied[(size_t)j]) any = j;
+    ClosureSearchArgs qa; ClosurePoseArgs pa;
+    closure_args(n_queries, poses, stamps, start_offsets, S, qa, pa);
+    int32_t* cand = d_cand ? d_cand : s->q_cand;
+    float* x0 = d_x0 ? d_x0 : s->q_x0;
+    float* out = d_out ? d_out : s->q_out;
+    icet_score* score = d_score ? d_score : s->q_score;
+    c->armed_calls = 2;
+    const PoseTable tab = s->pose_table();
+    // 1 search, 2 resolve, 3 the indexed loop in scored mode, 4 the best of each query, 5 the records
+    STORECHK(s, launch_closure_search(tab, qa, n_queries, K, query->radius, query->min_stamp_gap, s->q_part, cand, s->q_keys, c->stream));
+    STORECHK(s, launch_closure_resolve(tab, pa, n_queries, K, S, any < 0 ? 0 : any, cand, nullptr, x0, s->q_kf_of, s->q_rows, s->q_members, s->q_offs, c->stream));
+    if (any < 0) {                                            // nothing to register against: every query ends without a winner
+        if (d_out) STORECHK(s, hipMemsetAsync(d_out, 0, sizeof(float) * 48 * (size_t)R, c->stream));
+        if (d_score) STORECHK(s, hipMemsetAsync(d_score, 0, sizeof(icet_score) * (size_t)R, c->stream));
+        STORECHK(s, launch_closure_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, nullptr, cand, s->q_keys, x0, out, score, d_closure, c->stream));
+        return ICET_OK;
+    }
+    std::vector<int32_t> idx((size_t)R, any);
+    std::vector<icet_dev_scan> regs((size_t)R);
+    for (int r = 0; r < R; r++) regs[(size_t)r] = scan2[r / (K * S)];
+    const IndexedDev dev{s->q_kf_of, s->q_rows};
+    st = register_indexed(c, p, R, idx.data(), regs.data(), x0, out, score, kIdxScored, s, &dev);
+    if (st != ICET_OK) { s->err = c->err; return st; }
+    STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
+    STORECHK(s, launch_closure_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, s->q_best, cand, s->q_keys, x0, out, score, d_closure, c->stream));
     return ICET_OK;
 }
 

@@ -276,6 +276,31 @@ constexpr int kStoreParkMax = 64;
 struct StoreParkSlots { int32_t slot[kStoreParkMax]; };
 hipError_t launch_keyframe_store_park(const Workspace& w, int V, int first, int count, const StoreParkSlots& dst,
                                       SlotHot* hot_dst, SlotFit* fit_dst, int16_t* sov_dst, int32_t* n_slots_dst, hipStream_t st);
+// icet_closure.hip: the store's pose table and the loop-closure query (icet_keyframe_store_close_device).  The queries' poses, stamps
+// and start offsets travel in the kernels' arguments (no copy command, nothing a later call could rewrite under a launch in flight).
+constexpr int kClosureMaxQueries = 64, kClosureMaxCandidates = 32, kClosureMaxStarts = 16;
+constexpr int kClosureTile = 1024;                  // slots per block of the search's first pass
+struct PoseTable { int64_t* stamp; float* f; int32_t cap; };      // stamp[cap]; f: 12 arrays of cap floats: tx | ty | tz | r0 .. r8 (row-major rotation); no pose: NaN
+struct PoseUpload { int32_t slot, pad; int64_t stamp; float tR[12]; };      // one entry of icet_keyframe_store_set_pose's pinned staging: t[3] | R[9]
+static_assert(sizeof(PoseUpload) == 64, "read as one record per thread");
+struct ClosureSearchArgs { float tx[kClosureMaxQueries], ty[kClosureMaxQueries], tz[kClosureMaxQueries]; int64_t stamp[kClosureMaxQueries]; };
+struct ClosurePoseArgs { float R[kClosureMaxQueries][9]; float t[kClosureMaxQueries][3]; float off[kClosureMaxStarts][6]; };
+static_assert(sizeof(ClosureSearchArgs) + 64 <= 4096 && sizeof(ClosurePoseArgs) + 128 <= 4096, "kernel arguments are at most 4 KB");
+int closure_tiles(int32_t cap);
+// d_part: n_queries x closure_tiles(cap) x K keys; d_cand: n_queries x K slots (-1: none); d_keys: their keys
+hipError_t launch_closure_search(const PoseTable& tab, const ClosureSearchArgs& qa, int n_queries, int K, float radius, int64_t min_gap,
+                                 unsigned long long* d_part, int32_t* d_cand, unsigned long long* d_keys, hipStream_t st);
+hipError_t launch_closure_resolve(const PoseTable& tab, const ClosurePoseArgs& pa, int n_queries, int K, int n_starts, int any_slot, const int32_t* d_cand,
+                                  float* d_x0_base, float* d_x0, int32_t* d_kf_of, int32_t* d_rows, int32_t* d_members, int32_t* d_offs, hipStream_t st);
+hipError_t launch_closure_apply(int32_t* dst, const int32_t* src, int n, hipStream_t st);
+}  // namespace icet
+struct icet_closure;                       // include/icet_hip.h
+namespace icet {
+hipError_t launch_closure_record(const PoseTable& tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels, const int32_t* d_best,
+                                 const int32_t* d_cand, const unsigned long long* d_keys, const float* d_x0, const float* d_out, const ::icet_score* d_score,
+                                 ::icet_closure* d_closure, hipStream_t st);
+hipError_t launch_closure_set_pose(const PoseTable& tab, const PoseUpload* h_up, int n, hipStream_t st);
+hipError_t launch_closure_clear_pose(const PoseTable& tab, const StoreParkSlots& slots, int n, hipStream_t st);
 // icet_sidetables.hip: the per-point members of the reference object, on request (pair 0 of a single-pair solve)
 hipError_t launch_side_scan1(const Workspace& w, const LaunchCfg& c, float* sph, int32_t* index, hipStream_t st);
 hipError_t launch_side_scan2(const Workspace& w, const LaunchCfg& c, const float* xf, float* pts, float* sph, int32_t* voxel, hipStream_t st);

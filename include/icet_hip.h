@@ -301,8 +301,68 @@ icet_status icet_keyframe_store_score_device(icet_keyframe_store* s, const icet_
 /* Test hook, like icet_debug_fetch: one OCCUPIED slot's tables on the host; synchronises the context's stream.  what = 0: n_slots (1 int32);
  * 1: the SlotHot records (12 words each: cluster_bounds row, mu1, voxel, 2 pad), count <= n_slots x 12; 2: the SlotFit records (20 words each:
  * mu1, sigma1 upper triangle / (n1_raw - 1), M = diag(l_diag) x evecs1 row-major, n1, voxel), count <= n_slots x 20; 3: slot_of_voxel (int16,
- * -1 = no slot), count <= V. */
+ * -1 = no slot), count <= V; 4: the slot's pose (16 float32, row-major 4 x 4; NaN entries when the slot has none), count <= 16; 5: its stamp (1 int64,
+ * -1 without a pose), count <= 1. */
 icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot, int32_t what, void* out, int64_t count);
+
+/* --- loop closure against the store: find the candidates by pose, register, score, pick and gate in one call ---------------------------------
+ * POSE.  A pose here is the PHYSICAL sensor pose in a world frame: 4 x 4 row-major float32 T = [R | t; 0 0 0 1], p_world = R p + t; R is taken as
+ *   orthonormal.  It is NOT icet_node_result.pose: that member is the reference's chain X_homo = X_homo * [R(X) | t] (include/icet_nodes.h), while the
+ *   solver's model is q = R(X)^T (p + t), i.e. the physical step of a registration result X is [R(X)^T | R(X)^T X_t].  For the small rotations of
+ *   consecutive frames the two read alike; for a revisit with a real yaw difference the node's chain gives the yaw with the wrong sign.
+ *   icet_pose_step_from_x writes that step; a caller chains T_world,k = T_world,k-1 * step.  A stamp is any int64 that orders the keyframes (a frame
+ *   number, nanoseconds).
+ * SET_POSE.  Gives n occupied, distinct slots a pose and a stamp (HOST arrays: n x 16 floats, n int64; read before the call returns).  In stream order
+ *   with puts and queries.  A put into a slot clears that slot's pose; reserve carries poses and stamps over.  A slot without a pose is never a candidate,
+ *   so a store that sets none behaves as before.
+ * CANDIDATES.  For query q (pose poses[q], stamp stamps[q]; HOST arrays) slot j is eligible when it is occupied and has a pose,
+ *   |stamps[q] - stamp_j| >= min_stamp_gap in 64-bit integers, and d2 <= fl(radius * radius) with d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)),
+ *   dx = fl(t_q.x - t_j.x): float32, one rounding per operation; a NaN anywhere makes the slot ineligible.  The candidates are the first
+ *   K = max_candidates eligible slots in ascending order of (d2, slot); d_cand (device, n_queries x K int32) gets them, -1 behind the last.
+ *   d_x0_base (device, n_queries x K x 6, may be NULL): the start pose of each candidate, zeros for -1.
+ * START POSE.  In double from the float32 poses, sums left to right: R_X = R_q^T R_j, X_t = R_q^T (t_q - t_j), theta = asin(clamp(R_X[2][0], -1, 1)),
+ *   phi = atan2(-R_X[2][1], R_X[2][2]), psi = atan2(-R_X[1][0], R_X[0][0]); X0 = (X_t, phi, theta, psi), each value rounded to float32 once.
+ *   Start s of a candidate is fl(X0 + start_offsets[s]) per component (HOST, n_starts x 6; NULL = zeros; by convention the first row is zero).
+ * CLOSE.  Registration r = (q K + k) S + s: scan2[q] against candidate k of query q from start s, through the indexed kernels in scored mode (the bits
+ *   of icet_keyframe_store_register_scored_device for the same slot, scan and X0); a missing candidate registers a scan of no rows.  The winner of
+ *   query q is icet_select_best_device's over its K x S registrations; d_closure[q] (device) is its record.  accepted = slot >= 0 &&
+ *   score.chi2_per_voxel <= max_chi2_per_voxel && score.voxels >= min_voxels.  d_cand (Q x K), d_x0 (Q K S x 6), d_out (Q K S x 48) and d_score (Q K S)
+ *   may each be NULL (the store then uses buffers of its own).  1 <= n_queries <= 64, 1 <= K <= 32, 1 <= S <= 16.  Asynchronous on the context's stream.
+ *   A store without an occupied slot: ICET_OK, every record has slot = -1 (d_out / d_score, when given, are zeroed).
+ * The calls leave every slot, pose and the context's parked keyframe as they were.  Refusals as above (ICET_ERR_BAD_ARG: NULL store or array, a shape
+ *   mismatch, K, S or n_queries out of range, a negative or NaN radius, an unoccupied or repeated slot in set_pose; ICET_ERR_UNSUPPORTED: option "keep"). */
+typedef struct icet_closure_query {
+    float   radius;               /* metres */
+    int32_t max_candidates;       /* K */
+    int64_t min_stamp_gap;        /* <= 0: none */
+    int32_t n_starts;             /* S */
+    float   max_chi2_per_voxel;   /* gate; +inf: none */
+    int32_t min_voxels;           /* gate; 0: none */
+    int32_t reserved;             /* zero */
+} icet_closure_query;             /* 32 bytes */
+
+typedef struct icet_closure {
+    int32_t slot;                 /* the winner's slot, -1: none */
+    int32_t reg;                  /* the winner's registration (q K + k) S + s, -1: none */
+    int32_t accepted;             /* the gate */
+    int32_t n_candidates;         /* eligible slots found, <= K */
+    int64_t stamp;                /* the slot's stamp */
+    float   d2;                   /* the slot's squared distance, as the candidate rule computed it */
+    int32_t reserved0;            /* zero */
+    float   x0[6];                /* the winner's start pose */
+    int32_t reserved1[2];         /* zero */
+    float   out[48];              /* the winner's row, layout of icet_solve_batch_device */
+    icet_score score;             /* the winner's score */
+} icet_closure;                   /* 288 bytes; without a winner x0, out and score are zero */
+
+icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, const int32_t* slots, const float* poses, const int64_t* stamps);
+icet_status icet_keyframe_store_candidates_device(icet_keyframe_store* s, int32_t n_queries, const float* poses, const int64_t* stamps,
+                                                  const icet_closure_query* query, int32_t* d_cand, float* d_x0_base);
+icet_status icet_keyframe_store_close_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
+                                             const float* poses, const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
+                                             icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score);
+/* One step of a pose chain from a registration result X (host; T: 16 floats).  T = [R(X)^T | R(X)^T X_t] in double, each entry rounded once. */
+void icet_pose_step_from_x(const float X[6], float T[16]);
 
 /* Pre-size the workspace (so the first timed call does not allocate). */
 icet_status icet_reserve(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2);
