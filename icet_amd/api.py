@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_create", "icet_keyframe_store_destroy", "icet_keyframe_store_last_error", "icet_keyframe_store_reserve", "icet_keyframe_store_put_device",
                     "icet_keyframe_store_register_device", "icet_keyframe_store_register_scored_device", "icet_keyframe_store_score_device", "icet_keyframe_store_debug_fetch",
                     "icet_keyframe_store_set_pose", "icet_keyframe_store_candidates_device", "icet_keyframe_store_close_device", "icet_pose_step_from_x",
+                    "icet_keyframe_store_enable_appearance", "icet_keyframe_store_describe_device", "icet_keyframe_store_set_stamp",
+                    "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
@@ -64,6 +66,11 @@ class ClosureQuery(C.Structure):
                 ("max_chi2_per_voxel", C.c_float), ("min_voxels", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AppearanceParams(C.Structure):
+    """icet_appearance_params (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("sectors", C.c_int32), ("rings", C.c_int32), ("rho_max", C.c_float), ("z_lo", C.c_float), ("z_hi", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 class Score(C.Structure):
     """icet_score (include/icet_hip.h), 32 bytes."""
     _fields_ = [("chi2", C.c_float), ("chi2_per_voxel", C.c_float), ("voxels", C.c_int32), ("points_in", C.c_int32), ("points", C.c_int32),
@@ -79,7 +86,12 @@ class Closure(C.Structure):
 # the same record as a NumPy dtype (a device buffer of records comes back as bytes)
 CLOSURE_DTYPE = np.dtype([("slot", "<i4"), ("reg", "<i4"), ("accepted", "<i4"), ("n_candidates", "<i4"), ("stamp", "<i8"), ("d2", "<f4"), ("reserved0", "<i4"),
                           ("x0", "<f4", (6,)), ("reserved1", "<i4", (2,)), ("out", "<f4", (48,)), ("score", SCORE_DTYPE)])
-assert CLOSURE_DTYPE.itemsize == 288 == C.sizeof(Closure) and C.sizeof(ClosureQuery) == 32 and C.sizeof(Score) == 32
+assert CLOSURE_DTYPE.itemsize == 288 == C.sizeof(Closure) and C.sizeof(ClosureQuery) == 32 and C.sizeof(Score) == 32 and C.sizeof(AppearanceParams) == 32
+
+
+# The recommended start offsets of a query by appearance (INTEGRATION "Loop closure without poses"): the search gives the yaw, not the translation, so
+# the starts are a 3 x 3 lattice of {-0.3, 0, 0.3} m in x and y around X0 = (0, 0, 0, 0, 0, yaw).
+LATTICE_STARTS = np.array([[dx, dy, 0, 0, 0, 0] for dx in (-0.3, 0.0, 0.3) for dy in (-0.3, 0.0, 0.3)], np.float32)
 
 
 def pose_step_from_X(X):
@@ -182,6 +194,13 @@ def load_library():
     L.icet_keyframe_store_close_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.POINTER(ClosureQuery), C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_pose_step_from_x.argtypes = [C.c_void_p, C.c_void_p]; L.icet_pose_step_from_x.restype = None
+    L.icet_keyframe_store_enable_appearance.argtypes = [C.c_void_p, C.POINTER(AppearanceParams)]
+    L.icet_keyframe_store_describe_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_set_stamp.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_candidates_appearance_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(ClosureQuery), C.c_void_p, C.c_void_p,
+                                                                   C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_close_appearance_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(ClosureQuery), C.c_void_p,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
     L.icet_multi_destroy.argtypes = [C.c_void_p]
     L.icet_multi_last_error.argtypes = [C.c_void_p]; L.icet_multi_last_error.restype = C.c_char_p
@@ -558,6 +577,7 @@ class KeyframeStore:
             raise IcetError(st, "icet_keyframe_store_create: " + load_library().icet_last_error(ctx._h).decode())
         self._h = h
         self.V = int(num_bins_phi) * int(num_bins_theta)
+        self.appearance = None                                        # AppearanceParams once enable_appearance has run
         import weakref
         if not hasattr(ctx, "_nodes"):
             ctx._nodes = []
@@ -637,9 +657,16 @@ class KeyframeStore:
 
     def debug_fetch(self, slot, what, count=None):
         """Diagnostic: one occupied slot's tables -- 'n_slots' (int), 'hot' ((n_slots, 12) words of SlotHot), 'fit' ((n_slots, 20) words of SlotFit),
-        'slot_of_voxel' (int16, V), 'pose' (4 x 4 float32, NaN entries without a pose), 'stamp' (int; -1 without a pose).  Words are returned as uint32
-        (view them as float32 / int32)."""
+        'slot_of_voxel' (int16, V), 'pose' (4 x 4 float32, NaN entries without a pose), 'stamp' (int; -1 without a pose), 'descriptor' ((rings, sectors)
+        uint8) and 'weights' ((sectors) float32) of a store with appearance enabled.  Words are returned as uint32 (view them as float32 / int32)."""
         L = load_library()
+        if what in ("descriptor", "weights"):
+            if self.appearance is None:
+                raise IcetError(ICET_ERR_BAD_ARG, "appearance is not enabled on this store")
+            a = self.appearance
+            out = np.zeros((a.rings, a.sectors), np.uint8) if what == "descriptor" else np.zeros(a.sectors, np.float32)
+            self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 6 if what == "descriptor" else 7, out.ctypes.data, out.size))
+            return out
         if what == "pose":
             out = np.zeros(16, np.float32)
             self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 4, out.ctypes.data, 16))
@@ -737,6 +764,122 @@ class KeyframeStore:
                 o = np.array(r["out"])
                 d.update(stamp=int(r["stamp"]), d2=float(r["d2"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(), cov=o[12:48].reshape(6, 6).copy(),
                          score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")})
+            res.append(d)
+        return res
+
+    # ---- loop closure by appearance (include/icet_hip.h "loop closure by appearance") ----
+
+    def enable_appearance(self, sectors=120, rings=20, rho_max=80.0, z_lo=-3.0, z_hi=12.0):
+        """Keep a rotation-invariant descriptor (rings x sectors bytes) beside every slot put from now on (icet_keyframe_store_enable_appearance).  Once per
+        store; slots put before have no descriptor and are never appearance candidates."""
+        ap = AppearanceParams(int(sectors), int(rings), float(rho_max), float(z_lo), float(z_hi), (C.c_int32 * 3)(0, 0, 0))
+        self._check(load_library().icet_keyframe_store_enable_appearance(self._h, C.byref(ap)))
+        self.appearance = ap
+
+    def describe_device(self, scan_descs, d_desc_ptr, d_weight_ptr, d_rows_ptr=None):
+        """icet_keyframe_store_describe_device: the descriptors of device scans into device buffers (n x rings x sectors uint8, n x sectors float32).  Asynchronous."""
+        k = len(scan_descs)
+        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan_descs])
+        self._check(load_library().icet_keyframe_store_describe_device(self._h, k, A, C.c_void_p(d_rows_ptr) if d_rows_ptr else None,
+                                                                        C.c_void_p(d_desc_ptr), C.c_void_p(d_weight_ptr)))
+
+    def describe(self, scans):
+        """The descriptors of host scans (N x 3 each): ((n, rings, sectors) uint8, (n, sectors) float32)."""
+        import torch
+        if self.appearance is None:
+            raise IcetError(ICET_ERR_BAD_ARG, "appearance is not enabled on this store")
+        dev = torch.device("cuda", self._ctx.device)
+        a = self.appearance
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        D = torch.zeros((max(len(bufs), 1), a.rings, a.sectors), dtype=torch.uint8, device=dev)
+        w = torch.zeros((max(len(bufs), 1), a.sectors), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.describe_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], D.data_ptr(), w.data_ptr())
+        self._ctx.sync()
+        return D.cpu().numpy()[:len(bufs)], w.cpu().numpy()[:len(bufs)]
+
+    def set_stamp(self, slots, stamps):
+        """Give occupied slots an int64 stamp without a pose (icet_keyframe_store_set_stamp); a later put into a slot clears it."""
+        st = np.ascontiguousarray(np.asarray(stamps, np.int64).reshape(-1))
+        sl = self._index(slots, st.shape[0])
+        self._check(load_library().icet_keyframe_store_set_stamp(self._h, st.shape[0], sl.ctypes.data, st.ctypes.data))
+
+    @staticmethod
+    def _stamps(stamps, q):
+        if stamps is None:
+            return None
+        st = np.ascontiguousarray(np.asarray(stamps, np.int64).reshape(-1))
+        if st.shape[0] != q:
+            raise IcetError(ICET_ERR_BAD_ARG, "scans and stamps differ in length")
+        return st
+
+    def candidates_appearance_device(self, scan2_descs, stamps, query, d_cand_ptr, d_dist_ptr=None, d_shift_ptr=None, d_x0_base_ptr=None):
+        """icet_keyframe_store_candidates_appearance_device: the appearance search alone, into device buffers.  ``query.radius`` is read as max_distance."""
+        q = len(scan2_descs)
+        st = self._stamps(stamps, q)
+        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._check(load_library().icet_keyframe_store_candidates_appearance_device(self._h, q, B, st.ctypes.data if st is not None else None, C.byref(query),
+                                                                                     vp(d_cand_ptr), vp(d_dist_ptr), vp(d_shift_ptr), vp(d_x0_base_ptr)))
+
+    def candidates_by_appearance(self, scans, k, max_distance, stamps=None, min_stamp_gap=0):
+        """Place recognition without poses: for every host scan (N x 3) the first ``k`` eligible slots in ascending (distance, slot) order.  Returns
+        (cand, dist, shift, x0_base): (Q, k) int32 with -1 behind the last, (Q, k) float32 (+inf), (Q, k) int32 (-1), (Q, k, 6) float32 (zeros)."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        q = len(bufs)
+        cand = torch.full((q, int(k)), -2, dtype=torch.int32, device=dev)
+        dist = torch.zeros((q, int(k)), dtype=torch.float32, device=dev)
+        shift = torch.full((q, int(k)), -2, dtype=torch.int32, device=dev)
+        x0 = torch.zeros((q, int(k), 6), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.candidates_appearance_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], stamps,
+                                          ClosureQuery(float(max_distance), int(k), int(min_stamp_gap), 1, float("inf"), 0, 0),
+                                          cand.data_ptr(), dist.data_ptr(), shift.data_ptr(), x0.data_ptr())
+        self._ctx.sync()
+        return cand.cpu().numpy(), dist.cpu().numpy(), shift.cpu().numpy(), x0.cpu().numpy()
+
+    def close_appearance_device(self, scan2_descs, stamps, params, query, d_closure_ptr, start_offsets=None, d_cand_ptr=None, d_x0_ptr=None, d_out_ptr=None, d_score_ptr=None):
+        """icet_keyframe_store_close_appearance_device: close_device without poses -- the candidates come from the appearance search and the yaw of each
+        start pose from the best column shift; ``query.radius`` is read as max_distance.  One record (CLOSURE_DTYPE; d2 = distance, reserved0 = shift) per scan."""
+        q = len(scan2_descs)
+        st = self._stamps(stamps, q)
+        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        off = None
+        if start_offsets is not None:
+            off = np.ascontiguousarray(np.asarray(start_offsets, np.float32).reshape(-1, 6))
+            if off.shape[0] != query.n_starts:
+                raise IcetError(ICET_ERR_BAD_ARG, "start_offsets must hold n_starts rows of 6")
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._check(load_library().icet_keyframe_store_close_appearance_device(self._h, C.byref(params), q, B, st.ctypes.data if st is not None else None, C.byref(query),
+                                                                                off.ctypes.data if off is not None else None, C.c_void_p(d_closure_ptr),
+                                                                                vp(d_cand_ptr), vp(d_x0_ptr), vp(d_out_ptr), vp(d_score_ptr)))
+
+    def find_closures_by_appearance(self, scans, runlen, k, starts=LATTICE_STARTS, max_distance=float("inf"), stamps=None, min_stamp_gap=0,
+                                    max_chi2_per_voxel=float("inf"), min_voxels=0, flags=0):
+        """find_closures without poses, for host scans (N x 3 each): one dict per scan -- slot (None: no winner), accepted, reg, n_candidates, stamp,
+        distance, shift, x0, X, pred_stds, cov, score -- from one icet_keyframe_store_close_appearance_device call.  ``starts``: S x 6 offsets added to
+        (0, 0, 0, 0, 0, yaw of the shift); the default is the 3 x 3 lattice of +-0.3 m, because the search finds the yaw and not the translation."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        off = np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        rec = torch.zeros((len(bufs), CLOSURE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        query = ClosureQuery(float(max_distance), int(k), int(min_stamp_gap), off.shape[0], float(max_chi2_per_voxel), int(min_voxels), 0)
+        self.close_appearance_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], stamps, self._params(runlen, flags), query, rec.data_ptr(), off)
+        self._ctx.sync()
+        recs = np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE)
+        res = []
+        for r in recs:
+            d = dict(slot=None if r["slot"] < 0 else int(r["slot"]), reg=int(r["reg"]), accepted=bool(r["accepted"]), n_candidates=int(r["n_candidates"]))
+            if d["slot"] is None:
+                d.update(stamp=None, distance=None, shift=None, x0=None, X=None, pred_stds=None, cov=None, score=None)
+            else:
+                o = np.array(r["out"])
+                d.update(stamp=int(r["stamp"]), distance=float(r["d2"]), shift=int(r["reserved0"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(),
+                         cov=o[12:48].reshape(6, 6).copy(), score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")})
             res.append(d)
         return res
 

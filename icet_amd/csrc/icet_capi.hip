@@ -9,6 +9,7 @@
 #include "icet_internal.h"
 #include "icet_layout.h"
 #include "icet_closure.h"
+#include "icet_appearance.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -120,6 +121,18 @@ struct icet_keyframe_store {
     unsigned long long* q_keys = nullptr; int32_t* q_cand = nullptr; int32_t cap_qk = 0;
     float* q_x0 = nullptr; float* q_out = nullptr; icet_score* q_score = nullptr; int32_t* q_kf_of = nullptr; int32_t* q_rows = nullptr; int32_t* q_members = nullptr; int32_t cap_qr = 0;
     int32_t* q_offs = nullptr; int32_t* q_best = nullptr;       // kClosureMaxQueries + 1, kClosureMaxQueries
+    // place recognition by appearance: null until icet_keyframe_store_enable_appearance
+    struct Appearance {
+        icet_appearance_rule::Consts k{}; int Rp = 0;             // Rp: words per column, ceil(rings / 4)
+        uint32_t* desc = nullptr; float* w = nullptr; int32_t* has = nullptr;      // the table: capacity rows (AppTable)
+        std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a descriptor
+        uint32_t* scratch = nullptr;                              // kAppBatch x rings x sectors words, zero between calls
+        uint32_t* qdesc = nullptr; float* qw = nullptr; int32_t* qhas = nullptr;   // the descriptors of a call's queries: a table of kAppBatch rows
+        unsigned long long* keys_all = nullptr; uint16_t* shift_all = nullptr; size_t cap_all = 0;      // n_queries x capacity, grown on demand
+        int32_t* shift_of = nullptr;                              // kClosureMaxQueries x kClosureMaxCandidates: the candidates' shifts, for the record
+    };
+    Appearance* app = nullptr;
+    AppTable app_table() const { return AppTable{app->desc, app->w, app->has, capacity, app->k.A, app->Rp}; }
 };
 
 namespace {
@@ -1241,6 +1254,20 @@ static hipError_t store_alloc(int V, int32_t cap, SlotHot*& hot, SlotFit*& fit, 
     return e;
 }
 
+// The descriptor table of `cap` rows (row: `row_words` words of columns, `cols` weights); all or nothing.
+static hipError_t app_alloc_table(size_t row_words, size_t cols, int32_t cap, uint32_t*& desc, float*& w, int32_t*& has) {
+    desc = nullptr; w = nullptr; has = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&desc), sizeof(uint32_t) * row_words * (size_t)cap);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w), sizeof(float) * cols * (size_t)cap);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&has), sizeof(int32_t) * (size_t)cap);
+    if (e != hipSuccess) {
+        for (void* q : {(void*)desc, (void*)w, (void*)has}) if (q) (void)hipFree(q);
+        desc = nullptr; w = nullptr; has = nullptr;
+        (void)hipGetLastError();
+    }
+    return e;
+}
+
 const char* icet_keyframe_store_last_error(const icet_keyframe_store* s) { return s ? s->err.c_str() : "null store"; }
 
 icet_status icet_keyframe_store_create(icet_ctx* c, const icet_params* p, int32_t capacity, icet_keyframe_store** out) {
@@ -1276,6 +1303,11 @@ icet_status icet_keyframe_store_destroy(icet_keyframe_store* s) {
                     (void*)s->q_x0, (void*)s->q_out, (void*)s->q_score, (void*)s->q_kf_of, (void*)s->q_rows, (void*)s->q_members, (void*)s->q_offs, (void*)s->q_best}) if (q) (void)hipFree(q);
     if (s->h_pose) (void)hipHostFree(s->h_pose);
     if (s->ev_pose) (void)hipEventDestroy(s->ev_pose);
+    if (s->app) {
+        for (void* q : {(void*)s->app->desc, (void*)s->app->w, (void*)s->app->has, (void*)s->app->scratch, (void*)s->app->qdesc, (void*)s->app->qw, (void*)s->app->qhas,
+                        (void*)s->app->keys_all, (void*)s->app->shift_all, (void*)s->app->shift_of}) if (q) (void)hipFree(q);
+        delete s->app;
+    }
     delete s;
     return ICET_OK;
 }
@@ -1297,8 +1329,23 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
         s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
     }
+    // descriptors (a store with appearance enabled): a new table, the first `old` rows carried over, no descriptor behind them
+    uint32_t* adesc = nullptr; float* aw = nullptr; int32_t* ahas = nullptr;
+    const size_t arow = s->app ? (size_t)s->app->k.A * (size_t)s->app->Rp : 0, acol = s->app ? (size_t)s->app->k.A : 0;
+    if (s->app) {
+        e = app_alloc_table(arow, acol, capacity, adesc, aw, ahas);
+        if (e != hipSuccess) {
+            for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose}) (void)hipFree(q);
+            s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+        }
+        e = hipMemsetAsync(ahas, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ahas, s->app->has, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(adesc, s->app->desc, sizeof(uint32_t) * arow * old, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(aw, s->app->w, sizeof(float) * acol * old, hipMemcpyDeviceToDevice, c->stream);
+    }
     // poses and stamps: the new table starts empty (0xFF), then every array's first `old` entries are carried over
-    e = hipMemsetAsync(pose, 0xFF, kPoseBytes * (size_t)capacity, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(pose, 0xFF, kPoseBytes * (size_t)capacity, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(pose, s->pose_stamp, sizeof(int64_t) * old, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpy2DAsync(pose + capacity, sizeof(float) * (size_t)capacity, s->pose_stamp + old, sizeof(float) * old, sizeof(float) * old, 12, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(hot, s->hotS, sizeof(SlotHot) * old * V, hipMemcpyDeviceToDevice, c->stream);
@@ -1309,9 +1356,14 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose}) (void)hipFree(q);
+        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas}) if (q) (void)hipFree(q);
         s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+    }
+    if (s->app) {
+        for (void* q : {(void*)s->app->desc, (void*)s->app->w, (void*)s->app->has}) (void)hipFree(q);
+        s->app->desc = adesc; s->app->w = aw; s->app->has = ahas; s->app->has_h.resize((size_t)capacity, 0);
+        s->app->cap_all = 0;                                     // (the per-slot buffers of a search are sized by the capacity)
     }
     for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots, (void*)s->pose_stamp}) (void)hipFree(q);
     s->pose_stamp = pose;
@@ -1320,6 +1372,8 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
     s->gen++;                                                // the tables moved: no graph captured against the old ones is replayed
     return ICET_OK;
 }
+
+static icet_status app_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst);
 
 icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, const int32_t* slots, const icet_dev_scan* scan1, const int32_t* d_rows) {
     if (!s) return ICET_ERR_BAD_ARG;
@@ -1353,6 +1407,10 @@ icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, co
         for (int k = 0; k < cnt; k++) s->occupied[(size_t)dst.slot[k]] = 1;
         const hipError_t pe = launch_closure_clear_pose(s->pose_table(), dst, cnt, c->stream);      // a new keyframe: whatever pose the slot had is not its pose
         if (pe != hipSuccess) { s->err = std::string("k_closure_clear_pose: ") + hipGetErrorString(pe); return ICET_ERR_HIP; }
+        if (s->app) {                                            // the scans' descriptors into the same slots, behind the park
+            const icet_status as = app_put_batch(s, scan1 + first, d_rows ? d_rows + first : nullptr, cnt, dst);
+            if (as != ICET_OK) return as;
+        }
     }
     return ICET_OK;
 }
@@ -1398,6 +1456,17 @@ icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot
         for (int a = 0; a < 3; a++) { for (int b = 0; b < 3; b++) T[4 * a + b] = tR[3 + 3 * a + b]; T[4 * a + 3] = tR[a]; }
         T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
         std::memcpy(out, T, sizeof(float) * (size_t)count);
+        return ICET_OK;
+    }
+    if (what == 6 || what == 7) {                             // the slot's descriptor: D[ring][sector] bytes out of the ring-packed columns; its weights
+        if (!s->app || !s->app->has_h[(size_t)slot]) { s->err = "the slot has no descriptor"; return ICET_ERR_BAD_ARG; }
+        const int A = s->app->k.A, Rn = s->app->k.Rn, Rp = s->app->Rp;
+        if (count > (what == 6 ? (int64_t)A * Rn : (int64_t)A)) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
+        if (what == 7) { if (count > 0) STORECHK(s, hipMemcpy(out, s->app->w + (size_t)slot * A, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost)); return ICET_OK; }
+        std::vector<uint32_t> words((size_t)A * Rp);
+        STORECHK(s, hipMemcpy(words.data(), s->app->desc + (size_t)slot * A * Rp, sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost));
+        uint8_t* o = static_cast<uint8_t*>(out);
+        for (int64_t i = 0; i < count; i++) { const int r = (int)(i / A), j = (int)(i % A); o[i] = (uint8_t)(words[(size_t)j * Rp + (r >> 2)] >> (8 * (r & 3))); }
         return ICET_OK;
     }
     const void* src = nullptr; int64_t cap = 0; size_t elem = 4;
@@ -1559,6 +1628,224 @@ icet_status icet_keyframe_store_close_device(icet_keyframe_store* s, const icet_
     if (st != ICET_OK) { s->err = c->err; return st; }
     STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
     STORECHK(s, launch_closure_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, s->q_best, cand, s->q_keys, x0, out, score, d_closure, c->stream));
+    return ICET_OK;
+}
+
+// ---- loop closure by appearance ----------------------------------------------------------------------------------
+static bool dev_scan_ok(const icet_dev_scan& a) { return !(a.n < 0 || a.ld < a.n || (a.n > 0 && !a.ptr) || a.ld >= ((int64_t)1 << 30)); }
+
+static void app_scans(const icet_dev_scan* scan, int cnt, const int32_t* dst, AppScans& sc) {
+    std::memset(&sc, 0, sizeof(sc));
+    for (int k = 0; k < cnt; k++) { sc.ptr[k] = scan[k].ptr; sc.n[k] = (int32_t)scan[k].n; sc.ld[k] = (int32_t)scan[k].ld; sc.dst[k] = dst ? dst[k] : k; }
+}
+
+// The descriptors of the cnt <= kAppBatch scans a put has just parked, into the rows of their slots.
+static icet_status app_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst) {
+    icet_ctx* c = s->ctx;
+    AppScans sc; app_scans(scan, cnt, dst.slot, sc);
+    const AppTable tab = s->app_table();
+    hipError_t e = launch_app_build(sc, cnt, d_rows, s->app->k, s->app->scratch, c->stream);
+    if (e == hipSuccess) e = launch_app_finish(sc, cnt, s->app->k, s->app->scratch, &tab, nullptr, nullptr, c->stream);
+    if (e != hipSuccess) {
+        for (int k = 0; k < cnt; k++) s->app->has_h[(size_t)dst.slot[k]] = 0;     // (what these rows hold is unknown)
+        s->err = std::string("k_app_build: ") + hipGetErrorString(e);
+        return ICET_ERR_HIP;
+    }
+    for (int k = 0; k < cnt; k++) s->app->has_h[(size_t)dst.slot[k]] = 1;
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_enable_appearance(icet_keyframe_store* s, const icet_appearance_params* ap) {
+    static_assert(sizeof(icet_appearance_params) == 32, "the record of include/icet_hip.h (the ctypes mirror of icet_amd/api.py)");
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (s->app) { s->err = "appearance is already enabled on this store"; return ICET_ERR_BAD_ARG; }
+    icet_appearance_params d{};
+    d.sectors = 120; d.rings = 20; d.rho_max = 80.f; d.z_lo = -3.f; d.z_hi = 12.f;
+    if (ap) d = *ap;
+    if (!icet_appearance_rule::params_ok(d.sectors, d.rings, d.rho_max, d.z_lo, d.z_hi) || d.reserved[0] || d.reserved[1] || d.reserved[2]) {
+        s->err = "appearance parameters out of range (sectors even 8 .. 360, rings 1 .. 64, rho_max > 0, z_hi > z_lo, reserved words zero)"; return ICET_ERR_BAD_ARG;
+    }
+    STORECHK(s, hipSetDevice(c->device));
+    STORECHK(s, hipStreamSynchronize(c->stream));
+    auto* a = new (std::nothrow) icet_keyframe_store::Appearance();
+    if (!a) { s->err = "host allocation failed"; return ICET_ERR_NOMEM; }
+    a->k = icet_appearance_rule::make_consts(d.sectors, d.rings, d.rho_max, d.z_lo, d.z_hi);
+    a->Rp = (d.rings + 3) / 4;
+    const size_t A = (size_t)a->k.A, row = A * (size_t)a->Rp, cells = A * (size_t)a->k.Rn;
+    hipError_t e = app_alloc_table(row, A, s->capacity, a->desc, a->w, a->has);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->scratch), sizeof(uint32_t) * cells * kAppBatch);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qdesc), sizeof(uint32_t) * row * kAppBatch);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qw), sizeof(float) * A * kAppBatch);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qhas), sizeof(int32_t) * kAppBatch);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->shift_of), sizeof(int32_t) * kClosureMaxQueries * kClosureMaxCandidates);
+    if (e == hipSuccess) e = hipMemsetAsync(a->has, 0, sizeof(int32_t) * (size_t)s->capacity, c->stream);          // no slot has a descriptor
+    if (e == hipSuccess) e = hipMemsetAsync(a->scratch, 0, sizeof(uint32_t) * cells * kAppBatch, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* q : {(void*)a->desc, (void*)a->w, (void*)a->has, (void*)a->scratch, (void*)a->qdesc, (void*)a->qw, (void*)a->qhas, (void*)a->shift_of}) if (q) (void)hipFree(q);
+        delete a;
+        s->err = std::string("enable_appearance: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+    }
+    a->has_h.assign((size_t)s->capacity, 0);
+    s->app = a;
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_describe_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows, uint8_t* d_desc, float* d_weight) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (!s->app) { s->err = "appearance is not enabled on this store"; return ICET_ERR_BAD_ARG; }
+    if (n < 0 || (n > 0 && (!scan || !d_desc || !d_weight))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    for (int k = 0; k < n; k++) if (!dev_scan_ok(scan[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    if (n == 0) return ICET_OK;
+    STORECHK(s, hipSetDevice(c->device));
+    c->armed_calls = 2;
+    const size_t A = (size_t)s->app->k.A, cells = A * (size_t)s->app->k.Rn;
+    for (int first = 0; first < n; first += kAppBatch) {
+        const int cnt = std::min(kAppBatch, n - first);
+        AppScans sc; app_scans(scan + first, cnt, nullptr, sc);
+        STORECHK(s, launch_app_build(sc, cnt, d_rows ? d_rows + first : nullptr, s->app->k, s->app->scratch, c->stream));
+        STORECHK(s, launch_app_finish(sc, cnt, s->app->k, s->app->scratch, nullptr, d_desc + cells * (size_t)first, d_weight + A * (size_t)first, c->stream));
+    }
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_set_stamp(icet_keyframe_store* s, int32_t n, const int32_t* slots, const int64_t* stamps) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (n < 0 || (n > 0 && (!slots || !stamps))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (n == 0) return ICET_OK;
+    std::vector<uint8_t> named((size_t)s->capacity, 0);
+    for (int k = 0; k < n; k++) {
+        const int32_t sl = slots[k];
+        if (sl < 0 || sl >= s->capacity || !s->occupied[(size_t)sl]) { s->err = "slots[" + std::to_string(k) + "] = " + std::to_string(sl) + " is not an occupied slot of the store (capacity " + std::to_string(s->capacity) + ")"; return ICET_ERR_BAD_ARG; }
+        if (named[(size_t)sl]) { s->err = "slot " + std::to_string(sl) + " is named twice in one set_stamp"; return ICET_ERR_BAD_ARG; }
+        named[(size_t)sl] = 1;
+    }
+    STORECHK(s, hipSetDevice(c->device));
+    c->armed_calls = 2;
+    for (int first = 0; first < n; first += kAppBatch) {
+        const int cnt = std::min(kAppBatch, n - first);
+        AppStamps st{};
+        for (int k = 0; k < cnt; k++) { st.slot[k] = slots[first + k]; st.stamp[k] = stamps[first + k]; }
+        STORECHK(s, launch_app_set_stamp(s->pose_table(), st, cnt, c->stream));
+    }
+    return ICET_OK;
+}
+
+// The arguments both appearance queries share.
+static icet_status app_query_ok(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps, const icet_closure_query* q) {
+    if (!s->app) { s->err = "appearance is not enabled on this store"; return ICET_ERR_BAD_ARG; }
+    if (n_queries < 1 || n_queries > kClosureMaxQueries) { s->err = "n_queries must be 1 .. " + std::to_string(kClosureMaxQueries); return ICET_ERR_BAD_ARG; }
+    if (!scan2 || !q) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (q->max_candidates < 1 || q->max_candidates > kClosureMaxCandidates) { s->err = "max_candidates must be 1 .. " + std::to_string(kClosureMaxCandidates); return ICET_ERR_BAD_ARG; }
+    if (!(q->radius >= 0.f)) { s->err = "max_distance (the radius member) must be a number >= 0"; return ICET_ERR_BAD_ARG; }
+    if (q->min_stamp_gap > 0 && !stamps) { s->err = "min_stamp_gap > 0 needs the queries' stamps"; return ICET_ERR_BAD_ARG; }
+    for (int k = 0; k < n_queries; k++) if (!dev_scan_ok(scan2[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    return ICET_OK;
+}
+
+static icet_status app_ensure(icet_keyframe_store* s, int32_t n_queries) {
+    icet_ctx* c = s->ctx;
+    const size_t need = (size_t)n_queries * (size_t)s->capacity;
+    if (need <= s->app->cap_all) return ICET_OK;
+    STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
+    s->app->cap_all = 0;
+    STORECHK(s, dev_realloc(s->app->keys_all, need)); STORECHK(s, dev_realloc(s->app->shift_all, need));
+    s->app->cap_all = need;
+    return ICET_OK;
+}
+
+// The queries' descriptors and the search: candidates into cand, their keys into s->q_keys.
+static icet_status app_search(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps, const icet_closure_query* query, int32_t* cand) {
+    icet_ctx* c = s->ctx;
+    AppScans sc; app_scans(scan2, n_queries, nullptr, sc);
+    const AppTable qtab{s->app->qdesc, s->app->qw, s->app->qhas, kAppBatch, s->app->k.A, s->app->Rp};
+    AppQueryStamps qs{};
+    if (stamps) for (int q = 0; q < n_queries; q++) qs.stamp[q] = stamps[q];
+    STORECHK(s, launch_app_build(sc, n_queries, nullptr, s->app->k, s->app->scratch, c->stream));
+    STORECHK(s, launch_app_finish(sc, n_queries, s->app->k, s->app->scratch, &qtab, nullptr, nullptr, c->stream));
+    STORECHK(s, launch_app_search(s->app_table(), s->pose_table(), s->app->qdesc, s->app->qw, qs, n_queries, query->max_candidates, query->radius, query->min_stamp_gap,
+                                  s->app->keys_all, s->app->shift_all, s->q_part, cand, s->q_keys, c->stream));
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_candidates_appearance_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps,
+                                                             const icet_closure_query* query, int32_t* d_cand, float* d_dist, int32_t* d_shift, float* d_x0_base) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    icet_status st = app_query_ok(s, n_queries, scan2, stamps, query);
+    if (st != ICET_OK) return st;
+    if (!d_cand) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    STORECHK(s, hipSetDevice(c->device));
+    const int K = query->max_candidates;
+    st = closure_ensure(s, n_queries, K, 0);
+    if (st == ICET_OK) st = app_ensure(s, n_queries);
+    if (st != ICET_OK) return st;
+    c->armed_calls = 2;
+    st = app_search(s, n_queries, scan2, stamps, query, d_cand);
+    if (st != ICET_OK) return st;
+    if (d_dist || d_shift || d_x0_base) {
+        const AppOffsets off{};
+        STORECHK(s, launch_app_resolve(s->capacity, s->app->k.A, off, n_queries, K, 0, -1, d_cand, s->q_keys, s->app->shift_all, d_dist, d_shift, d_x0_base, nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
+    }
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_close_appearance_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
+                                                        const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
+                                                        icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    // everything is checked before anything is touched
+    icet_status st = app_query_ok(s, n_queries, scan2, stamps, query);
+    if (st != ICET_OK) return st;
+    if (!params_ok(p) || !d_closure) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (query->n_starts < 1 || query->n_starts > kClosureMaxStarts) { s->err = "n_starts must be 1 .. " + std::to_string(kClosureMaxStarts); return ICET_ERR_BAD_ARG; }
+    const icet_params& sh = s->shape;
+    if (sh.bins_phi != p->bins_phi || sh.bins_theta != p->bins_theta || sh.n != p->n || sh.thresh != p->thresh || sh.buff != p->buff ||
+        ((sh.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
+        s->err = "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG;
+    }
+    if (c->tune.keep != 0) { s->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
+    STORECHK(s, hipSetDevice(c->device));
+    const int K = query->max_candidates, S = query->n_starts, R = n_queries * K * S;
+    st = closure_ensure(s, n_queries, K, R);
+    if (st == ICET_OK) st = app_ensure(s, n_queries);
+    if (st != ICET_OK) return st;
+    int32_t any = -1;
+    for (int32_t j = 0; j < s->capacity && any < 0; j++) if (s->occupied[(size_t)j]) any = j;
+    AppOffsets off{};
+    if (start_offsets) for (int i = 0; i < S; i++) for (int k = 0; k < 6; k++) off.off[i][k] = start_offsets[6 * i + k];
+    int32_t* cand = d_cand ? d_cand : s->q_cand;
+    float* x0 = d_x0 ? d_x0 : s->q_x0;
+    float* out = d_out ? d_out : s->q_out;
+    icet_score* score = d_score ? d_score : s->q_score;
+    c->armed_calls = 2;
+    const PoseTable tab = s->pose_table();
+    // 1 the queries' descriptors and the search, 2 resolve, 3 the indexed loop in scored mode, 4 the best of each query, 5 the records
+    st = app_search(s, n_queries, scan2, stamps, query, cand);
+    if (st != ICET_OK) return st;
+    STORECHK(s, launch_app_resolve(s->capacity, s->app->k.A, off, n_queries, K, S, any < 0 ? 0 : any, cand, s->q_keys, s->app->shift_all, nullptr, nullptr, nullptr,
+                                   s->app->shift_of, x0, s->q_kf_of, s->q_rows, s->q_members, s->q_offs, c->stream));
+    if (any < 0) {                                            // nothing to register against: every query ends without a winner
+        if (d_out) STORECHK(s, hipMemsetAsync(d_out, 0, sizeof(float) * 48 * (size_t)R, c->stream));
+        if (d_score) STORECHK(s, hipMemsetAsync(d_score, 0, sizeof(icet_score) * (size_t)R, c->stream));
+        STORECHK(s, launch_app_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, nullptr, cand, s->q_keys, s->app->shift_of, x0, out, score, d_closure, c->stream));
+        return ICET_OK;
+    }
+    std::vector<int32_t> idx((size_t)R, any);
+    std::vector<icet_dev_scan> regs((size_t)R);
+    for (int r = 0; r < R; r++) regs[(size_t)r] = scan2[r / (K * S)];
+    const IndexedDev dev{s->q_kf_of, s->q_rows};
+    st = register_indexed(c, p, R, idx.data(), regs.data(), x0, out, score, kIdxScored, s, &dev);
+    if (st != ICET_OK) { s->err = c->err; return st; }
+    STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
+    STORECHK(s, launch_app_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, s->q_best, cand, s->q_keys, s->app->shift_of, x0, out, score, d_closure, c->stream));
     return ICET_OK;
 }
 

@@ -301,6 +301,35 @@ hipError_t launch_closure_record(const PoseTable& tab, int n_queries, int K, int
                                  ::icet_closure* d_closure, hipStream_t st);
 hipError_t launch_closure_set_pose(const PoseTable& tab, const PoseUpload* h_up, int n, hipStream_t st);
 hipError_t launch_closure_clear_pose(const PoseTable& tab, const StoreParkSlots& slots, int n, hipStream_t st);
+}  // namespace icet
+namespace icet_appearance_rule { struct Consts; }      // icet_appearance.h
+namespace icet {
+// icet_appearance.hip: descriptors and the appearance search of the store (icet_keyframe_store_close_appearance_device).  Scans, stamps and
+// start offsets travel in the kernels' arguments, at most kAppBatch scans per launch.
+constexpr int kAppBatch = 64;
+struct AppScans { const float* ptr[kAppBatch]; int32_t n[kAppBatch]; int32_t ld[kAppBatch]; int32_t dst[kAppBatch]; };      // dst: the table row of scan k (a put)
+struct AppStamps { int64_t stamp[kAppBatch]; int32_t slot[kAppBatch]; };
+struct AppQueryStamps { int64_t stamp[kClosureMaxQueries]; };
+struct AppOffsets { float off[kClosureMaxStarts][6]; };
+static_assert(sizeof(AppScans) + 256 <= 4096 && kAppBatch >= kClosureMaxQueries && kAppBatch >= kStoreParkMax, "kernel arguments are at most 4 KB; a query's scans are one batch");
+// The store's descriptor table: per slot A columns of Rp = ceil(rings / 4) words (byte r & 3 of word r >> 2 is ring r), A weights, and a word "has a descriptor".
+struct AppTable { uint32_t* desc; float* w; int32_t* has; int32_t cap, A, Rp; };
+// d_scratch: kAppBatch x rings x sectors words, all zero between calls (k_app_finish clears what k_app_build wrote).  d_rows (may be null): already offset to scan 0.
+hipError_t launch_app_build(const AppScans& sc, int n_scans, const int32_t* d_rows, const icet_appearance_rule::Consts& c, uint32_t* d_scratch, hipStream_t st);
+// tab != null: into rows sc.dst[k] of the store's table; else D[ring][sector] bytes and weights into rows k of d_desc / d_weight.
+hipError_t launch_app_finish(const AppScans& sc, int n_scans, const icet_appearance_rule::Consts& c, uint32_t* d_scratch, const AppTable* tab,
+                             uint8_t* d_desc, float* d_weight, hipStream_t st);
+hipError_t launch_app_set_stamp(const PoseTable& tab, const AppStamps& s, int n, hipStream_t st);
+// d_qdesc / d_qw: the queries' descriptors in the table's layout.  d_keys_all / d_shift_all: n_queries x cap; d_part, d_cand, d_keys as launch_closure_search's.
+hipError_t launch_app_search(const AppTable& tab, const PoseTable& poses, const uint32_t* d_qdesc, const float* d_qw, const AppQueryStamps& qs, int n_queries, int K,
+                             float max_distance, int64_t min_gap, unsigned long long* d_keys_all, uint16_t* d_shift_all, unsigned long long* d_part,
+                             int32_t* d_cand, unsigned long long* d_keys, hipStream_t st);
+hipError_t launch_app_resolve(int cap, int A, const AppOffsets& off, int n_queries, int K, int n_starts, int any_slot, const int32_t* d_cand,
+                              const unsigned long long* d_keys, const uint16_t* d_shift_all, float* d_dist, int32_t* d_shift, float* d_x0_base, int32_t* d_shift_of,
+                              float* d_x0, int32_t* d_kf_of, int32_t* d_rows, int32_t* d_members, int32_t* d_offs, hipStream_t st);
+hipError_t launch_app_record(const PoseTable& tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels, const int32_t* d_best,
+                             const int32_t* d_cand, const unsigned long long* d_keys, const int32_t* d_shift_of, const float* d_x0, const float* d_out,
+                             const ::icet_score* d_score, ::icet_closure* d_closure, hipStream_t st);
 // icet_sidetables.hip: the per-point members of the reference object, on request (pair 0 of a single-pair solve)
 hipError_t launch_side_scan1(const Workspace& w, const LaunchCfg& c, float* sph, int32_t* index, hipStream_t st);
 hipError_t launch_side_scan2(const Workspace& w, const LaunchCfg& c, const float* xf, float* pts, float* sph, int32_t* voxel, hipStream_t st);

@@ -302,7 +302,7 @@ icet_status icet_keyframe_store_score_device(icet_keyframe_store* s, const icet_
  * 1: the SlotHot records (12 words each: cluster_bounds row, mu1, voxel, 2 pad), count <= n_slots x 12; 2: the SlotFit records (20 words each:
  * mu1, sigma1 upper triangle / (n1_raw - 1), M = diag(l_diag) x evecs1 row-major, n1, voxel), count <= n_slots x 20; 3: slot_of_voxel (int16,
  * -1 = no slot), count <= V; 4: the slot's pose (16 float32, row-major 4 x 4; NaN entries when the slot has none), count <= 16; 5: its stamp (1 int64,
- * -1 without a pose), count <= 1. */
+ * -1 without a pose), count <= 1; 6 / 7: the slot's appearance descriptor and weights ("loop closure by appearance" below). */
 icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot, int32_t what, void* out, int64_t count);
 
 /* --- loop closure against the store: find the candidates by pose, register, score, pick and gate in one call ---------------------------------
@@ -348,7 +348,7 @@ typedef struct icet_closure {
     int32_t n_candidates;         /* eligible slots found, <= K */
     int64_t stamp;                /* the slot's stamp */
     float   d2;                   /* the slot's squared distance, as the candidate rule computed it */
-    int32_t reserved0;            /* zero */
+    int32_t reserved0;            /* zero; the appearance query (below) puts the slot's column shift here, and its distance in d2 */
     float   x0[6];                /* the winner's start pose */
     int32_t reserved1[2];         /* zero */
     float   out[48];              /* the winner's row, layout of icet_solve_batch_device */
@@ -363,6 +363,61 @@ icet_status icet_keyframe_store_close_device(icet_keyframe_store* s, const icet_
                                              icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score);
 /* One step of a pose chain from a registration result X (host; T: 16 floats).  T = [R(X)^T | R(X)^T X_t] in double, each entry rounded once. */
 void icet_pose_step_from_x(const float X[6], float T[16]);
+
+/* --- loop closure by appearance: find the candidates without poses ---------------------------------------------------------------------------
+ * The pose search above needs the true revisit within `radius` of the live pose; after a long loop odometry has drifted further than that.  This
+ * search compares what the scans look like: a rotation-invariant descriptor per keyframe, built on the device when the scan is put and kept beside
+ * the slot, matched against a live scan's descriptor at every column shift.  The best shift is the yaw of the start pose.  No pose is read anywhere.
+ * DESCRIPTOR.  rings x sectors bytes D[ring][sector] in the sensor frame.  A point (x, y, z), float32, one rounding per operation: rho = sqrt(fl(fl(x x) +
+ *   fl(y y))); it counts when x, y, z are finite, rho^2 > 0 (exact-zero rows are skipped) and t = fl(rho kr) < rings; ring = floor(t); az = (float)atan2(
+ *   (double)y, (double)x), sector = floor(fl(fl(az ka) + sectors / 2)), minus sectors when >= sectors, 0 when negative; height code q = 1 + floor(fl(fl(
+ *   min(max(z, z_lo), z_hi) - z_lo) kz)) clamped to 1 .. 255.  kr = rings / rho_max, ka = sectors / 2 pi, kz = 254 / (z_hi - z_lo), each in double and
+ *   rounded to float32 once.  D[ring][sector] is the largest q of the cell, 0 when empty.  Column weight w_j = (float)(1 / sqrt((double)sum_r D[r][j]^2)),
+ *   0 for an empty column.  A maximum does not depend on order: the descriptor is bitwise reproducible whatever the batch.
+ * DISTANCE of a live descriptor (Dq, wq) to a slot's (Dc, wc) at shift s, j' = (j + s) mod sectors: G_j = sum_r Dq[r][j] Dc[r][j'] (an integer),
+ *   c_j = fl(fl((float)G_j wq_j) wc_j'); column j is valid when both weights are positive, m their number; m < ceil(sectors / 4): d_s = +inf; else
+ *   d_s = (float)(1 - (sum of (double)c_j over the valid j, ascending) / m), a negative value becoming +0.  The slot's distance is the smallest d_s, ties to
+ *   the lowest s: the slot's shift.
+ * ENABLE.  enable_appearance allocates the descriptor table -- capacity x (4 ceil(rings / 4) sectors + 4 sectors + 4) bytes, 2.9 KB per slot at the
+ *   defaults -- and fixes the parameters (NULL: sectors 120, rings 20, rho_max 80, z_lo -3, z_hi 12).  Once per store (again: ICET_ERR_BAD_ARG); sectors
+ *   even, 8 .. 360; rings 1 .. 64; rho_max > 0; z_hi > z_lo; reserved words zero; else ICET_ERR_BAD_ARG.  Slots put BEFORE it have no descriptor and are never
+ *   appearance candidates.  From then on put_device also builds the descriptor of every scan it parks, in stream order behind the park, honouring d_rows; a
+ *   put replaces the slot's descriptor and clears its stamp; the slot's keyframe tables are the bytes they would be without.  reserve carries descriptors over.
+ *   A store that never enables appearance issues exactly the launches it did.  Synchronises the context's stream.
+ * DESCRIBE.  describe_device writes the descriptors of n device scans (rules of icet_keyframe_device_n for scan and d_rows): d_desc n x rings x sectors
+ *   bytes, d_weight n x sectors floats (device).  Asynchronous.  debug_fetch what = 6: a slot's descriptor bytes (count <= rings x sectors), 7: its weights
+ *   (count <= sectors); a slot without a descriptor: ICET_ERR_BAD_ARG.
+ * SET_STAMP.  Gives n occupied, distinct slots a stamp (HOST arrays) without a pose, so that min_stamp_gap can keep the frames just behind the vehicle from
+ *   being "revisits".  In stream order; a put clears the stamp (to -1), as it does now.
+ * CANDIDATES.  Slot j is eligible for query q when it is occupied, has a descriptor, |stamps[q] - stamp_j| >= min_stamp_gap (when > 0; stamps may be NULL
+ *   when it is <= 0) and d <= max_distance, which is READ FROM THE `radius` MEMBER of icet_closure_query (a NaN distance fails).  The candidates are the first
+ *   K eligible slots in ascending (d, slot); d_cand (device, Q x K) gets them, -1 behind the last; d_dist (Q x K floats, may be NULL) their distances, +inf
+ *   for -1; d_shift (Q x K int32, may be NULL) their shifts, -1 for -1; d_x0_base (Q x K x 6, may be NULL) their start poses, zeros for -1.
+ * START POSE.  a = (double)s (2 pi / sectors), minus 2 pi when above pi; X0 = (0, 0, 0, 0, 0, (float)a): psi of R(X0) = R_q^T R_j, live sector j being keyframe
+ *   sector j + s.  Start i is fl(X0 + start_offsets[i]).  The translation is NOT found: give a lattice of offsets (INTEGRATION, "Loop closure without poses").
+ * CLOSE.  close_appearance_device is close_device without poses: descriptors of the Q scans, search, resolve, the indexed registrations r = (q K + k) S + s in
+ *   scored mode, icet_select_best_device's winner per query, the gate, one icet_closure record per query, in which d2 carries the appearance distance and
+ *   reserved0 the shift.  Limits, optional buffers and refusals are those of close_device, plus ICET_ERR_BAD_ARG when appearance is not enabled.
+ * Every argument is checked before anything is touched.  Asynchronous on the context's stream (the host arrays are read before the call returns); never
+ *   captured into a graph.  The queries leave every slot, descriptor, pose, stamp and the context's parked keyframe as they were. */
+typedef struct icet_appearance_params {
+    int32_t sectors;              /* A: even, 8 .. 360 */
+    int32_t rings;                /* 1 .. 64 */
+    float   rho_max;              /* metres, > 0 */
+    float   z_lo, z_hi;           /* metres in the sensor frame, z_hi > z_lo */
+    int32_t reserved[3];          /* zero */
+} icet_appearance_params;         /* 32 bytes */
+
+icet_status icet_keyframe_store_enable_appearance(icet_keyframe_store* s, const icet_appearance_params* ap);
+icet_status icet_keyframe_store_describe_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows,
+                                                uint8_t* d_desc, float* d_weight);
+icet_status icet_keyframe_store_set_stamp(icet_keyframe_store* s, int32_t n, const int32_t* slots, const int64_t* stamps);
+icet_status icet_keyframe_store_candidates_appearance_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps,
+                                                             const icet_closure_query* query, int32_t* d_cand, float* d_dist, int32_t* d_shift,
+                                                             float* d_x0_base);
+icet_status icet_keyframe_store_close_appearance_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
+                                                        const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
+                                                        icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score);
 
 /* Pre-size the workspace (so the first timed call does not allocate). */
 icet_status icet_reserve(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2);
