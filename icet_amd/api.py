@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_set_pose", "icet_keyframe_store_candidates_device", "icet_keyframe_store_close_device", "icet_pose_step_from_x",
                     "icet_keyframe_store_enable_appearance", "icet_keyframe_store_describe_device", "icet_keyframe_store_set_stamp",
                     "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
+                    "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
+                    "icet_keyframe_store_close_coarse_device",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
@@ -69,6 +71,27 @@ class ClosureQuery(C.Structure):
 class AppearanceParams(C.Structure):
     """icet_appearance_params (include/icet_hip.h), 32 bytes."""
     _fields_ = [("sectors", C.c_int32), ("rings", C.c_int32), ("rho_max", C.c_float), ("z_lo", C.c_float), ("z_hi", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class CoarseParams(C.Structure):
+    """icet_coarse_params (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("cells", C.c_int32), ("cell", C.c_float), ("z_lo", C.c_float), ("z_hi", C.c_float), ("min_span", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class CoarseSearch(C.Structure):
+    """icet_coarse_search (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("window", C.c_int32), ("n_yaw", C.c_int32), ("yaw_step", C.c_float), ("half_turn", C.c_int32), ("min_score", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class CoarseMatch(C.Structure):
+    """icet_coarse_match (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("score", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("h", C.c_int32), ("live_bits", C.c_int32), ("key_bits", C.c_int32), ("found", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# icet_coarse_match as a NumPy dtype (a device buffer of records comes back as bytes)
+COARSE_MATCH_DTYPE = np.dtype([("score", "<i4"), ("a", "<i4"), ("b", "<i4"), ("h", "<i4"), ("live_bits", "<i4"), ("key_bits", "<i4"), ("found", "<i4"), ("reserved", "<i4")])
+assert COARSE_MATCH_DTYPE.itemsize == 32 == C.sizeof(CoarseMatch) == C.sizeof(CoarseSearch) == C.sizeof(CoarseParams)
 
 
 class Score(C.Structure):
@@ -201,6 +224,12 @@ def load_library():
                                                                    C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_close_appearance_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(ClosureQuery), C.c_void_p,
                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_enable_coarse.argtypes = [C.c_void_p, C.POINTER(CoarseParams)]
+    L.icet_keyframe_store_coarse_grid_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_coarse_align_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(CoarseSearch),
+                                                          C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_close_coarse_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.POINTER(ClosureQuery),
+                                                          C.POINTER(CoarseSearch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
     L.icet_multi_destroy.argtypes = [C.c_void_p]
     L.icet_multi_last_error.argtypes = [C.c_void_p]; L.icet_multi_last_error.restype = C.c_char_p
@@ -578,6 +607,7 @@ class KeyframeStore:
         self._h = h
         self.V = int(num_bins_phi) * int(num_bins_theta)
         self.appearance = None                                        # AppearanceParams once enable_appearance has run
+        self.coarse = None                                            # CoarseParams once enable_coarse has run
         import weakref
         if not hasattr(ctx, "_nodes"):
             ctx._nodes = []
@@ -658,8 +688,15 @@ class KeyframeStore:
     def debug_fetch(self, slot, what, count=None):
         """Diagnostic: one occupied slot's tables -- 'n_slots' (int), 'hot' ((n_slots, 12) words of SlotHot), 'fit' ((n_slots, 20) words of SlotFit),
         'slot_of_voxel' (int16, V), 'pose' (4 x 4 float32, NaN entries without a pose), 'stamp' (int; -1 without a pose), 'descriptor' ((rings, sectors)
-        uint8) and 'weights' ((sectors) float32) of a store with appearance enabled.  Words are returned as uint32 (view them as float32 / int32)."""
+        uint8) and 'weights' ((sectors) float32) of a store with appearance enabled, 'grid' ((cells, cells / 32) uint32) of a store with coarse alignment
+        enabled.  Words are returned as uint32 (view them as float32 / int32)."""
         L = load_library()
+        if what == "grid":
+            if self.coarse is None:
+                raise IcetError(ICET_ERR_BAD_ARG, "coarse alignment is not enabled on this store")
+            out = np.zeros((self.coarse.cells, self.coarse.cells // 32), np.uint32)
+            self._check(L.icet_keyframe_store_debug_fetch(self._h, int(slot), 8, out.ctypes.data, out.size))
+            return out
         if what in ("descriptor", "weights"):
             if self.appearance is None:
                 raise IcetError(ICET_ERR_BAD_ARG, "appearance is not enabled on this store")
@@ -880,6 +917,126 @@ class KeyframeStore:
                 o = np.array(r["out"])
                 d.update(stamp=int(r["stamp"]), distance=float(r["d2"]), shift=int(r["reserved0"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(),
                          cov=o[12:48].reshape(6, 6).copy(), score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")})
+            res.append(d)
+        return res
+
+    # ---- coarse alignment (include/icet_hip.h "coarse alignment") ----
+
+    def enable_coarse(self, cells=256, cell=0.25, z_lo=-3.0, z_hi=12.0, min_span=0.5):
+        """Keep a bird's-eye bit grid (cells x cells bits of vertical structure) beside every slot put from now on (icet_keyframe_store_enable_coarse).  Once per
+        store; slots put before have no grid and the search reports found = 0 for them."""
+        cp = CoarseParams(int(cells), float(cell), float(z_lo), float(z_hi), float(min_span), (C.c_int32 * 3)(0, 0, 0))
+        self._check(load_library().icet_keyframe_store_enable_coarse(self._h, C.byref(cp)))
+        self.coarse = cp
+
+    @staticmethod
+    def coarse_search(window=12, n_yaw=1, yaw_step=np.pi / 120, half_turn=True, min_score=1):
+        """An icet_coarse_search record; the defaults suit candidates by appearance at 120 sectors (yaw_step = pi / sectors)."""
+        return CoarseSearch(int(window), int(n_yaw), float(yaw_step), int(bool(half_turn)), int(min_score), (C.c_int32 * 3)(0, 0, 0))
+
+    def coarse_grid_device(self, scan_descs, d_grid_ptr, d_rows_ptr=None):
+        """icet_keyframe_store_coarse_grid_device: the grids of device scans into a device buffer (n x cells x cells / 32 uint32).  Asynchronous."""
+        k = len(scan_descs)
+        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan_descs])
+        self._check(load_library().icet_keyframe_store_coarse_grid_device(self._h, k, A, C.c_void_p(d_rows_ptr) if d_rows_ptr else None, C.c_void_p(d_grid_ptr)))
+
+    def coarse_grid(self, scans):
+        """The grids of host scans (N x 3 each): (n, cells, cells / 32) uint32."""
+        import torch
+        if self.coarse is None:
+            raise IcetError(ICET_ERR_BAD_ARG, "coarse alignment is not enabled on this store")
+        dev = torch.device("cuda", self._ctx.device)
+        G = self.coarse.cells
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        g = torch.zeros((max(len(bufs), 1), G, G // 32), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.coarse_grid_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], g.data_ptr())
+        self._ctx.sync()
+        return g.cpu().numpy().view(np.uint32)[:len(bufs)]
+
+    def coarse_align_device(self, scan2_descs, k, d_cand_ptr, d_x0_base_ptr, search, d_x0_out_ptr=None, d_match_ptr=None, d_rows_ptr=None):
+        """icet_keyframe_store_coarse_align_device: the search alone for Q x k candidates (device buffers as either candidates call writes them).  Asynchronous."""
+        q = len(scan2_descs)
+        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._check(load_library().icet_keyframe_store_coarse_align_device(self._h, q, B, vp(d_rows_ptr), int(k), vp(d_cand_ptr), vp(d_x0_base_ptr), C.byref(search),
+                                                                            vp(d_x0_out_ptr), vp(d_match_ptr)))
+
+    def coarse_align(self, scans, cand, x0_base, window=12, n_yaw=1, yaw_step=np.pi / 120, half_turn=True, min_score=1):
+        """The coarse search for host scans (N x 3 each): ``cand`` (Q, k) slots (-1: none) and ``x0_base`` (Q, k, 6) base starts, e.g. from candidates() or
+        candidates_by_appearance().  Returns (x0, match): (Q, k, 6) float32 start poses and (Q, k) records of COARSE_MATCH_DTYPE."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        cand = np.ascontiguousarray(np.asarray(cand, np.int32))
+        q, k = cand.shape
+        base = np.ascontiguousarray(np.asarray(x0_base, np.float32).reshape(q, k, 6))
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        if len(bufs) != q:
+            raise IcetError(ICET_ERR_BAD_ARG, "scans and cand differ in length")
+        dc = torch.from_numpy(cand).to(dev); db = torch.from_numpy(base).to(dev)
+        x0 = torch.zeros((q, k, 6), dtype=torch.float32, device=dev)
+        m = torch.zeros((q, k, COARSE_MATCH_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.coarse_align_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], k, dc.data_ptr(), db.data_ptr(),
+                                 self.coarse_search(window, n_yaw, yaw_step, half_turn, min_score), x0.data_ptr(), m.data_ptr())
+        self._ctx.sync()
+        return x0.cpu().numpy(), np.frombuffer(m.cpu().numpy().tobytes(), COARSE_MATCH_DTYPE).reshape(q, k).copy()
+
+    def close_coarse_device(self, scan2_descs, poses, stamps, params, query, search, d_closure_ptr, start_offsets=None, d_cand_ptr=None, d_x0_ptr=None, d_out_ptr=None,
+                            d_score_ptr=None, d_match_ptr=None):
+        """icet_keyframe_store_close_coarse_device: close_device (``poses`` given) or close_appearance_device (``poses`` None) with the coarse alignment of every
+        candidate's base start in between.  One record (CLOSURE_DTYPE; reserved1 = coarse score, h | (a + 32) << 8 | (b + 32) << 16) per scan."""
+        q = len(scan2_descs)
+        T = None
+        if poses is not None:
+            T, st = self._poses(poses, stamps)
+            if T.shape[0] != q:
+                raise IcetError(ICET_ERR_BAD_ARG, "scans and poses differ in length")
+        else:
+            st = self._stamps(stamps, q)
+        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        off = None
+        if start_offsets is not None:
+            off = np.ascontiguousarray(np.asarray(start_offsets, np.float32).reshape(-1, 6))
+            if off.shape[0] != query.n_starts:
+                raise IcetError(ICET_ERR_BAD_ARG, "start_offsets must hold n_starts rows of 6")
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._check(load_library().icet_keyframe_store_close_coarse_device(self._h, C.byref(params), q, B, T.ctypes.data if T is not None else None,
+                                                                            st.ctypes.data if st is not None else None, C.byref(query), C.byref(search),
+                                                                            off.ctypes.data if off is not None else None, C.c_void_p(d_closure_ptr),
+                                                                            vp(d_cand_ptr), vp(d_x0_ptr), vp(d_out_ptr), vp(d_score_ptr), vp(d_match_ptr)))
+
+    def find_closures_coarse(self, scans, runlen, k, poses=None, stamps=None, starts=None, radius=float("inf"), min_stamp_gap=0, window=12, n_yaw=1, yaw_step=None,
+                             half_turn=True, min_score=1, max_chi2_per_voxel=float("inf"), min_voxels=0, flags=0):
+        """find_closures (``poses`` given; ``radius`` in metres) or find_closures_by_appearance (``poses`` None; ``radius`` is max_distance) with the coarse alignment
+        of every candidate's start, for host scans (N x 3 each): their dicts plus ``coarse`` = dict(score, a, b, h) of the winner.  ``starts``: S x 6 offsets
+        added to the coarse start (default: one start, no offset).  ``yaw_step`` defaults to pi / sectors of the appearance search, pi / 120 without one."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        off = np.zeros((1, 6), np.float32) if starts is None else np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
+        if yaw_step is None:
+            yaw_step = np.pi / (self.appearance.sectors if self.appearance is not None else 120)
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        rec = torch.zeros((len(bufs), CLOSURE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        query = ClosureQuery(float(radius), int(k), int(min_stamp_gap), off.shape[0], float(max_chi2_per_voxel), int(min_voxels), 0)
+        self.close_coarse_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], poses, stamps, self._params(runlen, flags), query,
+                                 self.coarse_search(window, n_yaw, yaw_step, half_turn, min_score), rec.data_ptr(), off)
+        self._ctx.sync()
+        recs = np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE)
+        res = []
+        for r in recs:
+            d = dict(slot=None if r["slot"] < 0 else int(r["slot"]), reg=int(r["reg"]), accepted=bool(r["accepted"]), n_candidates=int(r["n_candidates"]))
+            if d["slot"] is None:
+                d.update(stamp=None, d2=None, x0=None, X=None, pred_stds=None, cov=None, score=None, coarse=None)
+            else:
+                o = np.array(r["out"])
+                code = int(r["reserved1"][1])
+                d.update(stamp=int(r["stamp"]), d2=float(r["d2"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(), cov=o[12:48].reshape(6, 6).copy(),
+                         score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")},
+                         coarse=dict(score=int(r["reserved1"][0]), h=code & 255, a=((code >> 8) & 255) - 32, b=((code >> 16) & 255) - 32))
+                if poses is None:
+                    d.update(distance=float(r["d2"]), shift=int(r["reserved0"]))
             res.append(d)
         return res
 

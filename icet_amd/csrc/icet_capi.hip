@@ -10,6 +10,7 @@
 #include "icet_layout.h"
 #include "icet_closure.h"
 #include "icet_appearance.h"
+#include "icet_coarse.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -133,6 +134,20 @@ struct icet_keyframe_store {
     };
     Appearance* app = nullptr;
     AppTable app_table() const { return AppTable{app->desc, app->w, app->has, capacity, app->k.A, app->Rp}; }
+    // coarse alignment: null until icet_keyframe_store_enable_coarse
+    struct Coarse {
+        icet_coarse_rule::Consts k{};
+        uint32_t* grid = nullptr; int32_t* has = nullptr;         // the table: capacity rows of G x G / 32 words (CoarseTable)
+        std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a grid
+        uint32_t* scratch = nullptr;                              // kCoarseBatch x 2 x G x G words, zero between calls
+        uint32_t* qgrid = nullptr;                                // the own grids of a call's queries: kAppBatch rows
+        // per (query, candidate) of the largest call: base starts, coarse starts, matches, keys, slot bit counts; per hypothesis: transforms and live bit counts
+        float* base = nullptr; float* x0c = nullptr; icet_coarse_match* match = nullptr; unsigned long long* keys = nullptr; int32_t* key_bits = nullptr;
+        CoarseHyp* hyp = nullptr; int32_t* live_bits = nullptr;
+        size_t row_words() const { return (size_t)k.G * (size_t)k.W; }
+    };
+    Coarse* coarse = nullptr;
+    CoarseTable coarse_table() const { return CoarseTable{coarse->grid, coarse->has, capacity}; }
 };
 
 namespace {
@@ -1268,6 +1283,19 @@ static hipError_t app_alloc_table(size_t row_words, size_t cols, int32_t cap, ui
     return e;
 }
 
+// The grid table of `cap` rows of `row_words` words; all or nothing.
+static hipError_t coarse_alloc_table(size_t row_words, int32_t cap, uint32_t*& grid, int32_t*& has) {
+    grid = nullptr; has = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&grid), sizeof(uint32_t) * row_words * (size_t)cap);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&has), sizeof(int32_t) * (size_t)cap);
+    if (e != hipSuccess) {
+        for (void* q : {(void*)grid, (void*)has}) if (q) (void)hipFree(q);
+        grid = nullptr; has = nullptr;
+        (void)hipGetLastError();
+    }
+    return e;
+}
+
 const char* icet_keyframe_store_last_error(const icet_keyframe_store* s) { return s ? s->err.c_str() : "null store"; }
 
 icet_status icet_keyframe_store_create(icet_ctx* c, const icet_params* p, int32_t capacity, icet_keyframe_store** out) {
@@ -1308,6 +1336,11 @@ icet_status icet_keyframe_store_destroy(icet_keyframe_store* s) {
                         (void*)s->app->keys_all, (void*)s->app->shift_all, (void*)s->app->shift_of}) if (q) (void)hipFree(q);
         delete s->app;
     }
+    if (s->coarse) {
+        for (void* q : {(void*)s->coarse->grid, (void*)s->coarse->has, (void*)s->coarse->scratch, (void*)s->coarse->qgrid, (void*)s->coarse->base, (void*)s->coarse->x0c,
+                        (void*)s->coarse->match, (void*)s->coarse->keys, (void*)s->coarse->key_bits, (void*)s->coarse->hyp, (void*)s->coarse->live_bits}) if (q) (void)hipFree(q);
+        delete s->coarse;
+    }
     delete s;
     return ICET_OK;
 }
@@ -1344,6 +1377,20 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
         if (e == hipSuccess) e = hipMemcpyAsync(adesc, s->app->desc, sizeof(uint32_t) * arow * old, hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(aw, s->app->w, sizeof(float) * acol * old, hipMemcpyDeviceToDevice, c->stream);
     }
+    // grids (a store with coarse alignment enabled): likewise
+    uint32_t* cgrid = nullptr; int32_t* chas = nullptr;
+    if (s->coarse && e == hipSuccess) {
+        e = coarse_alloc_table(s->coarse->row_words(), capacity, cgrid, chas);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
+            for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas}) if (q) (void)hipFree(q);
+            s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+        }
+        e = hipMemsetAsync(chas, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(chas, s->coarse->has, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cgrid, s->coarse->grid, sizeof(uint32_t) * s->coarse->row_words() * old, hipMemcpyDeviceToDevice, c->stream);
+    }
     // poses and stamps: the new table starts empty (0xFF), then every array's first `old` entries are carried over
     if (e == hipSuccess) e = hipMemsetAsync(pose, 0xFF, kPoseBytes * (size_t)capacity, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(pose, s->pose_stamp, sizeof(int64_t) * old, hipMemcpyDeviceToDevice, c->stream);
@@ -1356,9 +1403,13 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas}) if (q) (void)hipFree(q);
+        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas, (void*)cgrid, (void*)chas}) if (q) (void)hipFree(q);
         s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+    }
+    if (s->coarse) {
+        for (void* q : {(void*)s->coarse->grid, (void*)s->coarse->has}) (void)hipFree(q);
+        s->coarse->grid = cgrid; s->coarse->has = chas; s->coarse->has_h.resize((size_t)capacity, 0);
     }
     if (s->app) {
         for (void* q : {(void*)s->app->desc, (void*)s->app->w, (void*)s->app->has}) (void)hipFree(q);
@@ -1374,6 +1425,7 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
 }
 
 static icet_status app_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst);
+static icet_status coarse_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst);
 
 icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, const int32_t* slots, const icet_dev_scan* scan1, const int32_t* d_rows) {
     if (!s) return ICET_ERR_BAD_ARG;
@@ -1410,6 +1462,10 @@ icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, co
         if (s->app) {                                            // the scans' descriptors into the same slots, behind the park
             const icet_status as = app_put_batch(s, scan1 + first, d_rows ? d_rows + first : nullptr, cnt, dst);
             if (as != ICET_OK) return as;
+        }
+        if (s->coarse) {                                         // and their grids
+            const icet_status cs = coarse_put_batch(s, scan1 + first, d_rows ? d_rows + first : nullptr, cnt, dst);
+            if (cs != ICET_OK) return cs;
         }
     }
     return ICET_OK;
@@ -1467,6 +1523,12 @@ icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot
         STORECHK(s, hipMemcpy(words.data(), s->app->desc + (size_t)slot * A * Rp, sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost));
         uint8_t* o = static_cast<uint8_t*>(out);
         for (int64_t i = 0; i < count; i++) { const int r = (int)(i / A), j = (int)(i % A); o[i] = (uint8_t)(words[(size_t)j * Rp + (r >> 2)] >> (8 * (r & 3))); }
+        return ICET_OK;
+    }
+    if (what == 8) {                                          // the slot's grid: G rows of G / 32 words
+        if (!s->coarse || !s->coarse->has_h[(size_t)slot]) { s->err = "the slot has no grid"; return ICET_ERR_BAD_ARG; }
+        if (count > (int64_t)s->coarse->row_words()) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
+        if (count > 0) STORECHK(s, hipMemcpy(out, s->coarse->grid + (size_t)slot * s->coarse->row_words(), sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost));
         return ICET_OK;
     }
     const void* src = nullptr; int64_t cap = 0; size_t elem = 4;
@@ -1846,6 +1908,213 @@ icet_status icet_keyframe_store_close_appearance_device(icet_keyframe_store* s, 
     if (st != ICET_OK) { s->err = c->err; return st; }
     STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
     STORECHK(s, launch_app_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, s->q_best, cand, s->q_keys, s->app->shift_of, x0, out, score, d_closure, c->stream));
+    return ICET_OK;
+}
+
+// ---- coarse alignment -------------------------------------------------------------------------------------------
+// The grids of the cnt <= kStoreParkMax scans a put has just parked, into the rows of their slots.
+static icet_status coarse_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst) {
+    icet_ctx* c = s->ctx;
+    const CoarseTable tab = s->coarse_table();
+    for (int first = 0; first < cnt; first += kCoarseBatch) {
+        const int m = std::min(kCoarseBatch, cnt - first);
+        AppScans sc; app_scans(scan + first, m, dst.slot + first, sc);
+        const hipError_t e = launch_coarse_structure(sc, m, d_rows ? d_rows + first : nullptr, s->coarse->k, s->coarse->scratch, tab.grid, tab.has, tab.cap, c->stream);
+        if (e != hipSuccess) {
+            for (int k = first; k < cnt; k++) s->coarse->has_h[(size_t)dst.slot[k]] = 0;      // (what these rows hold is unknown)
+            s->err = std::string("k_coarse_extrema: ") + hipGetErrorString(e);
+            return ICET_ERR_HIP;
+        }
+        for (int k = 0; k < m; k++) s->coarse->has_h[(size_t)dst.slot[first + k]] = 1;
+    }
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_enable_coarse(icet_keyframe_store* s, const icet_coarse_params* cp) {
+    static_assert(sizeof(icet_coarse_params) == 32 && sizeof(icet_coarse_search) == 32 && sizeof(icet_coarse_match) == 32, "the records of include/icet_hip.h (the ctypes mirrors of icet_amd/api.py)");
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (s->coarse) { s->err = "coarse alignment is already enabled on this store"; return ICET_ERR_BAD_ARG; }
+    icet_coarse_params d{};
+    d.cells = 256; d.cell = 0.25f; d.z_lo = -3.f; d.z_hi = 12.f; d.min_span = 0.5f;
+    if (cp) d = *cp;
+    if (!icet_coarse_rule::params_ok(d.cells, d.cell, d.z_lo, d.z_hi, d.min_span) || d.reserved[0] || d.reserved[1] || d.reserved[2]) {
+        s->err = "coarse parameters out of range (cells a multiple of 32, 64 .. 512, cell > 0, z_hi > z_lo, min_span > 0, reserved words zero)"; return ICET_ERR_BAD_ARG;
+    }
+    STORECHK(s, hipSetDevice(c->device));
+    STORECHK(s, hipStreamSynchronize(c->stream));
+    auto* a = new (std::nothrow) icet_keyframe_store::Coarse();
+    if (!a) { s->err = "host allocation failed"; return ICET_ERR_NOMEM; }
+    a->k = icet_coarse_rule::make_consts(d.cells, d.cell, d.z_lo, d.z_hi, d.min_span);
+    const size_t row = a->row_words(), cells = (size_t)a->k.G * (size_t)a->k.G;
+    constexpr size_t kQK = (size_t)kClosureMaxQueries * kClosureMaxCandidates, kH = 2 * (2 * icet_coarse_rule::kMaxYaw + 1);
+    hipError_t e = launch_coarse_prepare(a->k);
+    if (e == hipSuccess) e = coarse_alloc_table(row, s->capacity, a->grid, a->has);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->scratch), sizeof(uint32_t) * 2 * cells * kCoarseBatch);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qgrid), sizeof(uint32_t) * row * kAppBatch);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->base), sizeof(float) * 6 * kQK);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->x0c), sizeof(float) * 6 * kQK);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->match), sizeof(icet_coarse_match) * kQK);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->keys), sizeof(unsigned long long) * kQK);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->key_bits), sizeof(int32_t) * kQK);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->hyp), sizeof(CoarseHyp) * kQK * kH);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->live_bits), sizeof(int32_t) * kQK * kH);
+    if (e == hipSuccess) e = hipMemsetAsync(a->has, 0, sizeof(int32_t) * (size_t)s->capacity, c->stream);          // no slot has a grid
+    if (e == hipSuccess) e = hipMemsetAsync(a->scratch, 0, sizeof(uint32_t) * 2 * cells * kCoarseBatch, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* q : {(void*)a->grid, (void*)a->has, (void*)a->scratch, (void*)a->qgrid, (void*)a->base, (void*)a->x0c, (void*)a->match, (void*)a->keys, (void*)a->key_bits,
+                        (void*)a->hyp, (void*)a->live_bits}) if (q) (void)hipFree(q);
+        delete a;
+        s->err = std::string("enable_coarse: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+    }
+    a->has_h.assign((size_t)s->capacity, 0);
+    s->coarse = a;
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_coarse_grid_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows, uint32_t* d_grid) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (!s->coarse) { s->err = "coarse alignment is not enabled on this store"; return ICET_ERR_BAD_ARG; }
+    if (n < 0 || (n > 0 && (!scan || !d_grid))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    for (int k = 0; k < n; k++) if (!dev_scan_ok(scan[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    if (n == 0) return ICET_OK;
+    STORECHK(s, hipSetDevice(c->device));
+    c->armed_calls = 2;
+    for (int first = 0; first < n; first += kCoarseBatch) {
+        const int cnt = std::min(kCoarseBatch, n - first);
+        AppScans sc; app_scans(scan + first, cnt, nullptr, sc);
+        STORECHK(s, launch_coarse_structure(sc, cnt, d_rows ? d_rows + first : nullptr, s->coarse->k, s->coarse->scratch, d_grid + s->coarse->row_words() * (size_t)first,
+                                            nullptr, cnt, c->stream));
+    }
+    return ICET_OK;
+}
+
+static icet_status coarse_search_ok(icet_keyframe_store* s, const icet_coarse_search* se) {
+    if (!s->coarse) { s->err = "coarse alignment is not enabled on this store"; return ICET_ERR_BAD_ARG; }
+    if (!se) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (se->window < 0 || se->window > icet_coarse_rule::kMaxWindow) { s->err = "window must be 0 .. 32"; return ICET_ERR_BAD_ARG; }
+    if (se->n_yaw < 0 || se->n_yaw > icet_coarse_rule::kMaxYaw) { s->err = "n_yaw must be 0 .. 8"; return ICET_ERR_BAD_ARG; }
+    if (!std::isfinite(se->yaw_step)) { s->err = "yaw_step must be finite"; return ICET_ERR_BAD_ARG; }
+    if (se->half_turn != 0 && se->half_turn != 1) { s->err = "half_turn must be 0 or 1"; return ICET_ERR_BAD_ARG; }
+    if (se->min_score < 1) { s->err = "min_score must be >= 1"; return ICET_ERR_BAD_ARG; }
+    if (se->reserved[0] || se->reserved[1] || se->reserved[2]) { s->err = "reserved words must be zero"; return ICET_ERR_BAD_ARG; }
+    return ICET_OK;
+}
+
+// The queries' own grids, then the search of their candidates (d_cand, d_x0_base on the device).
+static icet_status coarse_run(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int32_t* d_rows, int K, const icet_coarse_search* se,
+                              const AppOffsets& off, int n_starts, int any_slot, const int32_t* d_cand, const float* d_x0_base, float* d_x0_out, icet_coarse_match* d_match,
+                              float* d_x0) {
+    icet_ctx* c = s->ctx;
+    icet_keyframe_store::Coarse* a = s->coarse;
+    for (int first = 0; first < n_queries; first += kCoarseBatch) {
+        const int cnt = std::min(kCoarseBatch, n_queries - first);
+        AppScans sc; app_scans(scan2 + first, cnt, nullptr, sc);
+        STORECHK(s, launch_coarse_structure(sc, cnt, d_rows ? d_rows + first : nullptr, a->k, a->scratch, a->qgrid + a->row_words() * (size_t)first, nullptr, cnt, c->stream));
+    }
+    AppScans all; app_scans(scan2, n_queries, nullptr, all);
+    const CoarseSearch cs{se->window, se->n_yaw, se->half_turn, se->min_score, se->yaw_step};
+    STORECHK(s, launch_coarse_align(s->coarse_table(), all, d_rows, a->k, cs, off, n_queries, K, n_starts, any_slot, d_cand, d_x0_base, a->qgrid, a->hyp, a->keys,
+                                    a->live_bits, a->key_bits, d_x0_out, d_match, d_x0, s->q_kf_of, s->q_rows, s->q_members, n_starts > 0 ? s->q_offs : nullptr, c->stream));
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_coarse_align_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int32_t* d_rows, int32_t K,
+                                                    const int32_t* d_cand, const float* d_x0_base, const icet_coarse_search* search, float* d_x0_out,
+                                                    icet_coarse_match* d_match) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    icet_status st = coarse_search_ok(s, search);
+    if (st != ICET_OK) return st;
+    if (n_queries < 1 || n_queries > kClosureMaxQueries) { s->err = "n_queries must be 1 .. " + std::to_string(kClosureMaxQueries); return ICET_ERR_BAD_ARG; }
+    if (K < 1 || K > kClosureMaxCandidates) { s->err = "K must be 1 .. " + std::to_string(kClosureMaxCandidates); return ICET_ERR_BAD_ARG; }
+    if (!scan2 || !d_cand || !d_x0_base) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    for (int k = 0; k < n_queries; k++) if (!dev_scan_ok(scan2[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    STORECHK(s, hipSetDevice(c->device));
+    c->armed_calls = 2;
+    const AppOffsets off{};
+    return coarse_run(s, n_queries, scan2, d_rows, K, search, off, 0, -1, d_cand, d_x0_base, d_x0_out, d_match, nullptr);
+}
+
+icet_status icet_keyframe_store_close_coarse_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
+                                                    const float* poses, const int64_t* stamps, const icet_closure_query* query,
+                                                    const icet_coarse_search* search, const float* start_offsets, icet_closure* d_closure, int32_t* d_cand,
+                                                    float* d_x0, float* d_out, icet_score* d_score, icet_coarse_match* d_match) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    // everything is checked before anything is touched
+    icet_status st = coarse_search_ok(s, search);
+    if (st != ICET_OK) return st;
+    if (poses) {
+        st = closure_query_ok(s, n_queries, poses, stamps, query);
+        if (st != ICET_OK) return st;
+        if (!scan2) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+        for (int q = 0; q < n_queries; q++) if (!dev_scan_ok(scan2[q])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    } else {
+        st = app_query_ok(s, n_queries, scan2, stamps, query);
+        if (st != ICET_OK) return st;
+    }
+    if (!params_ok(p) || !d_closure) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    if (query->n_starts < 1 || query->n_starts > kClosureMaxStarts) { s->err = "n_starts must be 1 .. " + std::to_string(kClosureMaxStarts); return ICET_ERR_BAD_ARG; }
+    const icet_params& sh = s->shape;
+    if (sh.bins_phi != p->bins_phi || sh.bins_theta != p->bins_theta || sh.n != p->n || sh.thresh != p->thresh || sh.buff != p->buff ||
+        ((sh.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
+        s->err = "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG;
+    }
+    if (c->tune.keep != 0) { s->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
+    STORECHK(s, hipSetDevice(c->device));
+    const int K = query->max_candidates, S = query->n_starts, R = n_queries * K * S;
+    st = closure_ensure(s, n_queries, K, R);
+    if (st == ICET_OK && !poses) st = app_ensure(s, n_queries);
+    if (st != ICET_OK) return st;
+    int32_t any = -1;
+    for (int32_t j = 0; j < s->capacity && any < 0; j++) if (s->occupied[(size_t)j]) any = j;
+    AppOffsets off{};
+    if (start_offsets) for (int i = 0; i < S; i++) for (int k = 0; k < 6; k++) off.off[i][k] = start_offsets[6 * i + k];
+    int32_t* cand = d_cand ? d_cand : s->q_cand;
+    float* x0 = d_x0 ? d_x0 : s->q_x0;
+    float* out = d_out ? d_out : s->q_out;
+    icet_score* score = d_score ? d_score : s->q_score;
+    icet_coarse_match* match = d_match ? d_match : s->coarse->match;
+    c->armed_calls = 2;
+    const PoseTable tab = s->pose_table();
+    // 1 the candidates and their base starts, as the existing calls find them, 2 the coarse alignment and the starts, 3 the indexed loop in scored mode,
+    // 4 the best of each query, 5 the records
+    if (poses) {
+        ClosureSearchArgs qa; ClosurePoseArgs pa;
+        closure_args(n_queries, poses, stamps, nullptr, 0, qa, pa);
+        STORECHK(s, launch_closure_search(tab, qa, n_queries, K, query->radius, query->min_stamp_gap, s->q_part, cand, s->q_keys, c->stream));
+        STORECHK(s, launch_closure_resolve(tab, pa, n_queries, K, 0, -1, cand, s->coarse->base, nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
+    } else {
+        st = app_search(s, n_queries, scan2, stamps, query, cand);
+        if (st != ICET_OK) return st;
+        const AppOffsets none{};
+        STORECHK(s, launch_app_resolve(s->capacity, s->app->k.A, none, n_queries, K, 0, -1, cand, s->q_keys, s->app->shift_all, nullptr, nullptr, s->coarse->base,
+                                       s->app->shift_of, nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
+    }
+    st = coarse_run(s, n_queries, scan2, nullptr, K, search, off, S, any < 0 ? 0 : any, cand, s->coarse->base, nullptr, match, x0);
+    if (st != ICET_OK) return st;
+    const int32_t* best = nullptr;
+    if (any < 0) {                                            // nothing to register against: every query ends without a winner
+        if (d_out) STORECHK(s, hipMemsetAsync(d_out, 0, sizeof(float) * 48 * (size_t)R, c->stream));
+        if (d_score) STORECHK(s, hipMemsetAsync(d_score, 0, sizeof(icet_score) * (size_t)R, c->stream));
+    } else {
+        std::vector<int32_t> idx((size_t)R, any);
+        std::vector<icet_dev_scan> regs((size_t)R);
+        for (int r = 0; r < R; r++) regs[(size_t)r] = scan2[r / (K * S)];
+        const IndexedDev dev{s->q_kf_of, s->q_rows};
+        st = register_indexed(c, p, R, idx.data(), regs.data(), x0, out, score, kIdxScored, s, &dev);
+        if (st != ICET_OK) { s->err = c->err; return st; }
+        STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
+        best = s->q_best;
+    }
+    if (poses) STORECHK(s, launch_closure_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, best, cand, s->q_keys, x0, out, score, d_closure, c->stream));
+    else STORECHK(s, launch_app_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, best, cand, s->q_keys, s->app->shift_of, x0, out, score, d_closure, c->stream));
+    STORECHK(s, launch_coarse_record(n_queries, S, match, d_closure, c->stream));
     return ICET_OK;
 }
 

@@ -330,6 +330,30 @@ hipError_t launch_app_resolve(int cap, int A, const AppOffsets& off, int n_queri
 hipError_t launch_app_record(const PoseTable& tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels, const int32_t* d_best,
                              const int32_t* d_cand, const unsigned long long* d_keys, const int32_t* d_shift_of, const float* d_x0, const float* d_out,
                              const ::icet_score* d_score, ::icet_closure* d_closure, hipStream_t st);
+}  // namespace icet
+namespace icet_coarse_rule { struct Consts; }          // icet_coarse.h
+struct icet_coarse_match;                              // include/icet_hip.h
+namespace icet {
+// icet_coarse.hip: the bird's-eye bit grids and the coarse alignment of the store (icet_keyframe_store_coarse_align_device).  Scans travel
+// in the kernels' arguments: at most kCoarseBatch per structure pass (the scratch is two words per cell and scan), a query's scans (<= kAppBatch) per search.
+constexpr int kCoarseBatch = 16;
+// The store's grid table: per slot G rows of W = G / 32 words, and a word "has a grid".
+struct CoarseTable { uint32_t* grid; int32_t* has; int32_t cap; };
+struct CoarseSearch { int32_t window, Y, half_turn, min_score; float yaw_step; };
+struct CoarseHyp { float m[6]; float t[3]; float pad[3]; };      // the float32 transform of one (query, candidate, hypothesis)
+// The dynamic-LDS limit of the correlation for these parameters (enable, with the context's device current).
+hipError_t launch_coarse_prepare(const icet_coarse_rule::Consts& c);
+// The spanning cells of n_scans <= kCoarseBatch scans into rows sc.dst[k] of d_out (rows of G W words; a row outside 0 .. n_rows - 1 is skipped) and, when d_has is
+// given, their "has a grid" words.  d_scratch: kCoarseBatch x 2 x G x G words, all zero between calls.  d_rows (may be null): already offset to scan 0.
+hipError_t launch_coarse_structure(const AppScans& sc, int n_scans, const int32_t* d_rows, const icet_coarse_rule::Consts& c, uint32_t* d_scratch, uint32_t* d_out,
+                                   int32_t* d_has, int n_rows, hipStream_t st);
+// The search of n_queries x K candidates: d_qgrid the queries' own grids (rows q), d_hyp n_queries x K x H, d_keys / d_key_bits n_queries x K, d_live_bits
+// n_queries x K x H.  d_x0_out / d_match may be null; with n_starts > 0 the registrations as launch_closure_resolve writes them.
+hipError_t launch_coarse_align(const CoarseTable& tab, const AppScans& sc, const int32_t* d_rows, const icet_coarse_rule::Consts& c, const CoarseSearch& se,
+                               const AppOffsets& off, int n_queries, int K, int n_starts, int any_slot, const int32_t* d_cand, const float* d_x0_base,
+                               const uint32_t* d_qgrid, CoarseHyp* d_hyp, unsigned long long* d_keys, int32_t* d_live_bits, int32_t* d_key_bits, float* d_x0_out,
+                               ::icet_coarse_match* d_match, float* d_x0, int32_t* d_kf_of, int32_t* d_rows_out, int32_t* d_members, int32_t* d_offs, hipStream_t st);
+hipError_t launch_coarse_record(int n_queries, int n_starts, const ::icet_coarse_match* d_match, ::icet_closure* d_closure, hipStream_t st);
 // icet_sidetables.hip: the per-point members of the reference object, on request (pair 0 of a single-pair solve)
 hipError_t launch_side_scan1(const Workspace& w, const LaunchCfg& c, float* sph, int32_t* index, hipStream_t st);
 hipError_t launch_side_scan2(const Workspace& w, const LaunchCfg& c, const float* xf, float* pts, float* sph, int32_t* voxel, hipStream_t st);

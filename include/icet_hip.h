@@ -350,7 +350,7 @@ typedef struct icet_closure {
     float   d2;                   /* the slot's squared distance, as the candidate rule computed it */
     int32_t reserved0;            /* zero; the appearance query (below) puts the slot's column shift here, and its distance in d2 */
     float   x0[6];                /* the winner's start pose */
-    int32_t reserved1[2];         /* zero */
+    int32_t reserved1[2];         /* zero; close_coarse_device (below) puts the winner's coarse score and shift word here */
     float   out[48];              /* the winner's row, layout of icet_solve_batch_device */
     icet_score score;             /* the winner's score */
 } icet_closure;                   /* 288 bytes; without a winner x0, out and score are zero */
@@ -418,6 +418,84 @@ icet_status icet_keyframe_store_candidates_appearance_device(icet_keyframe_store
 icet_status icet_keyframe_store_close_appearance_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
                                                         const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
                                                         icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score);
+
+/* --- coarse alignment: find a closure's start translation (and settle a half turn) by grid correlation -----------------------------------------
+ * Both searches above hand the registration a start pose that is often outside the solver's basin: the appearance search finds the yaw and not the
+ * translation, the pose search inherits the drift of two poses.  This search is coarse, exhaustive and all integers: a bird's-eye bit grid of the live scan's
+ * vertical structure is correlated against the same grid kept beside each slot, over a window of cell shifts and a few yaw hypotheses.
+ * CELL of (x, y), float32, one rounding per operation: u = fl(fl(x kc) + G / 2); the coordinate is inside when u >= 0 && u < G (a NaN is outside), ix =
+ *   floor(u); likewise iy from y.  kc = 1 / cell, kz = 254 / (z_hi - z_lo): in double, rounded to float32 once; span_codes = ceil(min_span (254 / (z_hi - z_lo)))
+ *   in double from the float32 parameters.
+ * STRUCTURE POINTS of a scan, decided in the sensor frame once per scan: a point counts when x, y, z are finite, fl(fl(x x) + fl(y y)) > 0 (exact-zero rows are
+ *   skipped) and its cell is inside; its height code is q = floor(fl(fl(min(max(z, z_lo), z_hi) - z_lo) kz)).  A cell SPANS when the largest minus the
+ *   smallest q of its counting points is >= span_codes (flat ground does not, whatever the sensor height).  A counting point whose cell spans is a structure
+ *   point.  Minima and maxima do not depend on order.
+ * GRID of a scan under a transform: the cells its structure points hit after the transform; G rows (ix) of G / 32 words, bit iy & 31 of word iy >> 5 (8 KB at
+ *   the defaults).  A keyframe's grid uses the identity: it is exactly its spanning cells.
+ * HYPOTHESIS h of a live scan with base start pose X0 (six float32): delta_h = (double)y yaw_step + f pi, y = -Y .. Y, f = 0 / 1 (1 only with half_turn),
+ *   h = f (2 Y + 1) + (y + Y).  R_h = R(X0) Rz(delta_h) in double, Rz(delta) the solver's R(0, 0, delta), sums left to right; M = R_h^T, each entry rounded to
+ *   float32 once; u = fl(p + X0_t) per component; x' = fl(fl(fl(M00 ux) + fl(M01 uy)) + fl(M02 uz)), y' likewise with row 1.
+ * SCORE S_h(a, b), |a|, |b| <= window: the number of live cells (i, j) whose slot cell (i + a, j + b) is set; cells shifted off the grid are dropped.
+ * WINNER: largest S; then smallest a a + b b; then smallest h; then smallest a; then smallest b -- one 64-bit key (S << 32 | 4095 - (a a + b b) << 20 | 63 - h << 14 |
+ *   32 - a << 7 | 32 - b) whose maximum does not depend on the launch shape.  found = 1 when the slot has a grid and the best S >= min_score; else the start
+ *   stays X0.
+ * START POSE of the winner: d = ((double)a cell, (double)b cell, 0); R(X) = R_h, X_t = X0_t + R_h d, in double, sums left to right; the angles by the inverse
+ *   of the pose search's rule, -pi becoming pi; each of the six values rounded to float32 once.  (q = R_h^T (p + X0_t) + d = R(X)^T (p + X_t).)  Where nothing
+ *   moves the value is X0's own, bit for bit: the translation when a = b = 0, the angles when y = 0 and f = 0.
+ * ENABLE.  enable_coarse allocates the grid table -- capacity x (G G / 8 + 4) bytes -- and fixes the parameters (NULL: cells 256, cell 0.25, z_lo -3, z_hi 12,
+ *   min_span 0.5).  Once per store (again: ICET_ERR_BAD_ARG); cells a multiple of 32, 64 .. 512; cell > 0; z_hi > z_lo; min_span > 0; reserved words zero; else
+ *   ICET_ERR_BAD_ARG.  Independent of enable_appearance.  Slots put BEFORE it have no grid: the search reports found = 0 for them.  From then on put_device also
+ *   builds the grid of every scan it parks, in stream order behind the park, honouring d_rows; a put replaces exactly its own slot's grid; reserve carries the
+ *   grids over.  A store that never enables it issues exactly the launches it did.  Synchronises the context's stream.
+ * GRID.  coarse_grid_device writes the grids of n device scans under the identity (rules of describe_device for scan and d_rows): d_grid n x G x G / 32 words
+ *   (device).  Asynchronous.  debug_fetch what = 8: a slot's grid (count <= G G / 32 words); a slot without one: ICET_ERR_BAD_ARG.
+ * ALIGN.  coarse_align_device searches Q x K candidates: d_cand (device, Q x K slots, -1: none) and d_x0_base (device, Q x K x 6) as either candidates call
+ *   writes them, or the caller's own.  d_x0_out (Q x K x 6, may be NULL) gets the start poses -- X0 where found = 0, zeros for a candidate of -1 --, d_match
+ *   (Q x K records, may be NULL) the winners: score, a, b, h and the bit counts of the winning live grid and of the slot's grid whenever the slot has a grid,
+ *   zeros otherwise.  1 <= Q <= 64, 1 <= K <= 32, window 0 .. 32, n_yaw 0 .. 8, min_score >= 1, reserved words zero.
+ * CLOSE.  close_coarse_device is close_device (poses given) or close_appearance_device (poses NULL: candidates by appearance, which must be enabled) with
+ *   the coarse alignment of each candidate's base start in between: registrations r = (q K + k) S + s in scored mode from fl(X0_coarse + start_offsets[s]),
+ *   icet_select_best_device's winner, the gate, one icet_closure record per query, filled as those calls fill it; in addition reserved1[0] carries the winner's
+ *   coarse score and reserved1[1] h | (a + 32) << 8 | (b + 32) << 16.  d_match (Q x K, may be NULL) as above.  Limits, optional buffers and refusals are those of
+ *   close_device, plus ICET_ERR_BAD_ARG when coarse alignment is not enabled.
+ * Every argument is checked before anything is touched.  Asynchronous on the context's stream (the host arrays are read before the call returns); never
+ *   captured into a graph.  The calls leave every slot, grid, descriptor, pose, stamp and the context's parked keyframe as they were. */
+typedef struct icet_coarse_params {
+    int32_t cells;                /* G: a multiple of 32, 64 .. 512 */
+    float   cell;                 /* metres, > 0 */
+    float   z_lo, z_hi;           /* metres in the sensor frame, z_hi > z_lo */
+    float   min_span;             /* metres, > 0 */
+    int32_t reserved[3];          /* zero */
+} icet_coarse_params;             /* 32 bytes */
+
+typedef struct icet_coarse_search {
+    int32_t window;               /* M_w: shifts -window .. window cells in x and y, 0 .. 32 */
+    int32_t n_yaw;                /* Y: yaw hypotheses -Y .. Y steps, 0 .. 8 */
+    float   yaw_step;             /* radians */
+    int32_t half_turn;            /* 0 / 1: every yaw hypothesis also turned by pi */
+    int32_t min_score;            /* >= 1 */
+    int32_t reserved[3];          /* zero */
+} icet_coarse_search;             /* 32 bytes */
+
+typedef struct icet_coarse_match {
+    int32_t score;                /* S of the winner */
+    int32_t a, b;                 /* its shift in cells */
+    int32_t h;                    /* its hypothesis */
+    int32_t live_bits;            /* bits of the winning live grid */
+    int32_t key_bits;             /* bits of the slot's grid */
+    int32_t found;                /* 1: score >= min_score, the start pose moved */
+    int32_t reserved;             /* zero */
+} icet_coarse_match;              /* 32 bytes */
+
+icet_status icet_keyframe_store_enable_coarse(icet_keyframe_store* s, const icet_coarse_params* cp);
+icet_status icet_keyframe_store_coarse_grid_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows, uint32_t* d_grid);
+icet_status icet_keyframe_store_coarse_align_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int32_t* d_rows, int32_t K,
+                                                    const int32_t* d_cand, const float* d_x0_base, const icet_coarse_search* search, float* d_x0_out,
+                                                    icet_coarse_match* d_match);
+icet_status icet_keyframe_store_close_coarse_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
+                                                    const float* poses, const int64_t* stamps, const icet_closure_query* query,
+                                                    const icet_coarse_search* search, const float* start_offsets, icet_closure* d_closure, int32_t* d_cand,
+                                                    float* d_x0, float* d_out, icet_score* d_score, icet_coarse_match* d_match);
 
 /* Pre-size the workspace (so the first timed call does not allocate). */
 icet_status icet_reserve(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2);
