@@ -26,7 +26,7 @@ FLAG_HALF_GAP_BOUNDS = 8  # non-parity extension (half-gap cluster buffers of th
 
 # every symbol include/icet_hip.h, include/icet_nodes.h and include/icet_io.h declare
 EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_version", "icet_solve", "icet_solve_begin", "icet_solve_keyframe_tables", "icet_solve_end", "icet_solve_batch",
-                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
+                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_debug_point_sums_device", "icet_debug_fix", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
                     "icet_keyframe_store_create", "icet_keyframe_store_destroy", "icet_keyframe_store_last_error", "icet_keyframe_store_reserve", "icet_keyframe_store_put_device",
                     "icet_keyframe_store_register_device", "icet_keyframe_store_register_scored_device", "icet_keyframe_store_score_device", "icet_keyframe_store_debug_fetch",
                     "icet_keyframe_store_set_pose", "icet_keyframe_store_candidates_device", "icet_keyframe_store_close_device", "icet_pose_step_from_x",
@@ -60,6 +60,9 @@ class Params(C.Structure):
 SCORE_DTYPE = np.dtype([("chi2", "<f4"), ("chi2_per_voxel", "<f4"), ("voxels", "<i4"), ("points_in", "<i4"), ("points", "<i4"), ("overlap", "<f4"),
                         ("reserved", "<i4", (2,))])
 assert SCORE_DTYPE.itemsize == 32
+# a voxel's raw accumulator record (icet_debug_point_sums_device): the counts and the nine 2^36 fixed-point sums of d = q - mu1, 80 bytes
+POINT_SUMS_DTYPE = np.dtype([("n2", "<u4"), ("m", "<u4"), ("sums", "<i8", (9,))])
+assert POINT_SUMS_DTYPE.itemsize == 80
 
 
 class ClosureQuery(C.Structure):
@@ -191,6 +194,8 @@ def load_library():
     L.icet_debug_gn_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_debug_pinv3.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_debug_pinv3_double.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.icet_debug_point_sums_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
+    L.icet_debug_fix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_keyframe_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan)]
     L.icet_register_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
     L.icet_keyframe_device_n.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p]
@@ -445,6 +450,24 @@ class Context:
         A = np.ascontiguousarray(packed, np.float32).reshape(-1, 6)
         out = np.zeros_like(A)
         self._check(load_library().icet_debug_pinv3_double(self._h, A.ctypes.data, A.shape[0], out.ctypes.data))
+        return out
+
+    def debug_point_sums(self, kf_index, scan2_descs, params, d_X_ptr, d_sums_ptr):
+        """icet_debug_point_sums_device (test hook): the point pass of score_indexed_device at the poses d_X, then every voxel's raw accumulator record
+        instead of the score.  d_sums_ptr: device pointer to len(scan2_descs) x V records of POINT_SUMS_DTYPE (80 bytes), indexed by voxel id."""
+        k = len(scan2_descs)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
+        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        self._check(load_library().icet_debug_point_sums_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_sums_ptr)))
+
+    def debug_fix(self, values):
+        """icet_debug_fix (test hook): n floats through the point pass's float -> 2^36 fixed-point conversions -> (n, 3) uint64 = to_fix_biased (defined for
+        |v| < 2^15), to_fix_wide_biased, to_fix."""
+        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        out = np.zeros((v.shape[0], 3), np.uint64)
+        self._check(load_library().icet_debug_fix(self._h, v.ctypes.data, v.shape[0], out.ctypes.data))
         return out
 
     def debug_gn_tail(self, htwh, htwdz):

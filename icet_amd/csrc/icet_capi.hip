@@ -682,7 +682,7 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
 // registration r in c->h_kf_of[r].  The registration-side tables (acc, xf, X, overflow counts, tickets) are indexed by r, the keyframe tables by h_kf_of[r]
 // (LaunchCfg::kf_of).  The plain point pass and solve: no fused launch, no keep list.
 // d_score != nullptr: one more point pass at the final transform records and the score (icet_score.hip) behind the loop; `iters` (default runlen): 0 scores the
-// poses d_x0 without iterating.
+// poses d_x0 without iterating.  d_dump != nullptr (test hook): that point pass followed by k_point_sums_dump instead of the score.
 // src: the keyframe tables the registrations read -- nullptr: the context's parked keyframe; a store: its rows (h_kf_of then holds slot indices).
 // dev: the keyframe index and the scan-2 row counts of the registrations are known to the DEVICE only (a loop-closure query, whose candidates a kernel found a
 // moment ago on the same stream): the staging holds an occupied slot and the scans' full row counts -- the launch geometry is sized from those, as in
@@ -690,7 +690,7 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
 // kf_of[r] the index.
 struct IndexedDev { const int32_t* kf_of; const int32_t* rows; };
 icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1,
-                            const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr) {
+                            const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr) {
     if (iters < 0) iters = p->runlen;
     Workspace& w = c->w;
     LaunchCfg cfg = make_cfg(c, p, n_regs, c->h_desc_reg, nullptr);
@@ -727,9 +727,10 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it + 1], c->stream));
         HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, nullptr, c->stream));
     }
-    if (d_score) {                                                          // the last solve (or k_init_state) left the transform record of the pose to score in w.xf
+    if (d_score || d_dump) {                                                // the last solve (or k_init_state) left the transform record of the pose to score in w.xf
         HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
-        HIPCHK(c, launch_gn_score(wl, lcfg, p->runlen, d_score, c->stream));
+        if (d_dump) HIPCHK(c, launch_point_sums_dump(wl, lcfg, d_dump, c->stream));      // (icet_debug_point_sums_device: the raw sums in place of the score)
+        else HIPCHK(c, launch_gn_score(wl, lcfg, p->runlen, d_score, c->stream));
     }
     if (!c->capturing) { HIPCHK(c, hipEventRecord(c->ev_c, c->stream)); c->timing_valid = true; c->last_iters = per_iter ? p->runlen : 0; }
     return ICET_OK;
@@ -1167,12 +1168,12 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
 // The indexed registrations of icet_register_indexed_device (mode kIdxRegister), the same followed by the score (kIdxScored: d_score), or the score of the poses
 // d_x0 alone (kIdxScoreOnly: no iteration, d_out unused).  src: the keyframe tables -- nullptr the context's parked keyframe (kf_index: parked keyframes), or a
 // keyframe store (kf_index: its occupied slots; icet_keyframe_store_register_device and its kin).
-enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2 };
+enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2, kIdxDump = 3 };      // kIdxDump (icet_debug_point_sums_device): kIdxScoreOnly with the raw per-voxel sums (d_dump) in place of the score
 static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
-                                    icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr) {
+                                    icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr) {
     if (!c) return ICET_ERR_BAD_ARG;
-    const bool need_out = mode != kIdxScoreOnly, need_score = mode != kIdxRegister;
-    if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (mode == kIdxScoreOnly && !d_x0)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    const bool need_out = mode == kIdxRegister || mode == kIdxScored, need_score = mode == kIdxScored || mode == kIdxScoreOnly, need_x = mode == kIdxScoreOnly || mode == kIdxDump;
+    if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (need_x && !d_x0) || (mode == kIdxDump && !d_dump)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n_regs == 0) return ICET_OK;
     // everything is checked before anything is touched: a refused call leaves the parked keyframe (and every slot of a store) as it was
     const icet_params& q = src ? src->shape : c->kf_params;
@@ -1218,6 +1219,7 @@ static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n
                                                                   src ? src->id : 0, src ? src->gen : 0), enq);
         return enq();
     }
+    if (mode == kIdxDump) return enqueue_indexed(c, p, n_regs, d_x0, nullptr, nullptr, 0, src, dev, d_dump);      // (never captured)
     // scored calls: runlen == 0 scores X0 (results as the unscored call writes them); score-only calls score d_x0 without iterating
     const bool no_iters = mode == kIdxScoreOnly || p->runlen == 0;
     auto enq = [&]() -> icet_status {
@@ -1245,6 +1247,13 @@ icet_status icet_register_indexed_scored_device(icet_ctx* c, const icet_params* 
 icet_status icet_score_indexed_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
                                       const float* d_X, icet_score* d_score) {
     return register_indexed(c, p, n_regs, kf_index, scan2, d_X, nullptr, d_score, kIdxScoreOnly);
+}
+
+// Test hook: the point pass of icet_score_indexed_device at the poses d_X, then the raw accumulator records instead of the score.
+icet_status icet_debug_point_sums_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
+                                         const float* d_X, void* d_sums) {
+    if (c && (reinterpret_cast<uintptr_t>(d_sums) & 15u)) { c->err = "icet_debug_point_sums_device: d_sums must be 16-byte aligned"; return ICET_ERR_BAD_ARG; }      // (the copy-out kernel stores 16 bytes at a time)
+    return register_indexed(c, p, n_regs, kf_index, scan2, d_X, nullptr, nullptr, kIdxDump, nullptr, nullptr, static_cast<uint32_t*>(d_sums));
 }
 
 // ---- the keyframe store ----------------------------------------------------------------------------------------
@@ -2558,6 +2567,24 @@ icet_status icet_debug_pinv3_double(icet_ctx* c, const float* a, int32_t n, floa
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     if (e != hipSuccess) { c->err = std::string("icet_debug_pinv3_double: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
+    return ICET_OK;
+}
+
+// Test hook: the float -> fixed-point conversions of the point pass (icet_device_common.h) on n host-side floats; out: n x 3 uint64 = to_fix_biased | to_fix_wide_biased | to_fix.
+icet_status icet_debug_fix(icet_ctx* c, const float* v, int32_t n, uint64_t* out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!v || !out || n < 0) { c->err = "icet_debug_fix: bad argument"; return ICET_ERR_BAD_ARG; }
+    if (n == 0) return ICET_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    unsigned long long* d = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(unsigned long long) * (size_t)n * 4));
+    float* d_v = reinterpret_cast<float*>(d + (size_t)n * 3);
+    hipError_t e = hipMemcpyAsync(d_v, v, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_fix_debug(d_v, d, n, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(unsigned long long) * (size_t)n * 3, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { c->err = std::string("icet_debug_fix: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
     return ICET_OK;
 }
 

@@ -2,6 +2,7 @@
 //     k_gn_score        behind one more point pass at the registration's transform record: per slot the moments, R_noise, dz = M (mu2 - mu1) and
 //                       W = pinv(M R_noise M^T) of gn_solve_body, then chi2 = sum dz^T W dz, voxels and points in; one block per registration
 //     k_select_best     one wave per group of registrations: the lowest chi2 per voxel among those with at least half the group's best voxel count
+//     k_point_sums_dump, k_fix_debug   test hooks: the point pass's raw per-voxel accumulator records, and its float -> fixed-point conversions on their own
 // The loop's own kernels are untouched: this file has a body of its own, written after gn_solve_body's per-voxel front statement by statement.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -137,6 +138,44 @@ __global__ __launch_bounds__(kScoreBlock) void k_gn_score(const int32_t* __restr
     }
 }
 
+// Test hook (icet_debug_point_sums_device): what the point pass left for registration `pair` (one block), copied out raw.  The near-overflow list is drained
+// first, exactly as k_gn_score does; then every voxel's 80-byte accumulator record -- n2, m, nine 64-bit fixed-point sums -- goes to dump[pair][voxel] (zeros
+// for a voxel without a slot) and the record and the overflow count are left at zero, as a solve leaves them.
+__global__ __launch_bounds__(kScoreBlock) void k_point_sums_dump(uint32_t* acc, const float* __restrict__ xf_all, int V, NearOverflow over,
+                                                                 const int32_t* __restrict__ kf_of, uint32_t* __restrict__ dump) {
+    const int pair = blockIdx.x;
+    const int kf = kf_of ? __builtin_amdgcn_readfirstlane(kf_of[pair]) : pair;
+    const uint32_t nov = over.count[pair];                              // block-uniform
+    if (nov) {
+        NearOverflow o = over;
+        o.slot_of_voxel += ((ptrdiff_t)kf - pair) * ((V + 1) & ~1); o.hotS += ((ptrdiff_t)kf - pair) * V;
+        drain_near_overflow(o, pair, V, xf_all + pair * kXf, acc + (size_t)pair * V * kAccWords, nov);
+        __threadfence();
+        __syncthreads();
+        if (threadIdx.x == 0) over.count[pair] = 0u;
+    }
+    const int16_t* map = over.slot_of_voxel + (size_t)kf * ((V + 1) & ~1);
+    for (int v = threadIdx.x; v < V; v += kScoreBlock) {
+        const int s = map[v];
+        uint4* out = reinterpret_cast<uint4*>(dump + ((size_t)pair * V + v) * kAccWords);
+        uint4* A = reinterpret_cast<uint4*>(acc + ((size_t)pair * V + (s >= 0 ? s : 0)) * kAccWords);
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            uint4 r = make_uint4(0u, 0u, 0u, 0u);
+            if (s >= 0) { r = A[k]; A[k] = make_uint4(0u, 0u, 0u, 0u); }
+            out[k] = r;
+        }
+    }
+}
+
+// Test hook (icet_debug_fix): n floats through the three float -> fixed-point conversions of the point pass; out[3 i ..] = to_fix_biased, to_fix_wide_biased, to_fix.
+__global__ __launch_bounds__(kScoreBlock) void k_fix_debug(const float* __restrict__ v, unsigned long long* __restrict__ out, int n) {
+    const int i = blockIdx.x * kScoreBlock + threadIdx.x;
+    if (i >= n) return;
+    const float x = v[i];
+    out[3 * (size_t)i + 0] = to_fix_biased(x); out[3 * (size_t)i + 1] = to_fix_wide_biased(x); out[3 * (size_t)i + 2] = to_fix(x);
+}
+
 // (chi2 per voxel, registration) orders the candidates: lower chi2 per voxel first, ties to the lower index; NaN ranks behind every number.
 // r == INT32_MAX: no candidate yet.
 __device__ __forceinline__ bool better(float c, int r, float cb, int rb) {
@@ -179,6 +218,19 @@ hipError_t launch_gn_score(const Workspace& w, const LaunchCfg& c, int iter, ice
     const NearOverflow over{w.desc, w.slot_of_voxel, w.hotS, w.thr, w.near_over, w.near_over_count, c.T, c.P, c.rt2};
     if (c.ref_w) k_gn_score<true><<<c.n_pairs, kScoreBlock, 0, st>>>(w.n_slots, w.fitS, w.acc, w.xf, c.V, c.n, iter, over, c.reject_moving, c.kf_of, d_score);
     else k_gn_score<false><<<c.n_pairs, kScoreBlock, 0, st>>>(w.n_slots, w.fitS, w.acc, w.xf, c.V, c.n, iter, over, c.reject_moving, c.kf_of, d_score);
+    ICET_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_point_sums_dump(const Workspace& w, const LaunchCfg& c, uint32_t* d_dump, hipStream_t st) {
+    const NearOverflow over{w.desc, w.slot_of_voxel, w.hotS, w.thr, w.near_over, w.near_over_count, c.T, c.P, c.rt2};
+    k_point_sums_dump<<<c.n_pairs, kScoreBlock, 0, st>>>(w.acc, w.xf, c.V, over, c.kf_of, d_dump);
+    ICET_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_fix_debug(const float* d_v, unsigned long long* d_out, int n, hipStream_t st) {
+    k_fix_debug<<<(n + kScoreBlock - 1) / kScoreBlock, kScoreBlock, 0, st>>>(d_v, d_out, n);
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -534,6 +534,17 @@ icet_status icet_debug_pinv3(icet_ctx* ctx, const float* a, int32_t n, float* ou
 /* Diagnostic hook for the parity tests: the per-voxel weight W = pinv(.) of ICET_FLAG_DOUBLE_W (the double-precision pseudo-inverse with the 3 eps rank rule) for n
  * host-side symmetric 3 x 3 matrices, packed (xx, xy, xz, yy, yz, zz): n x 6 in, n x 6 out, through the device function the solve kernel runs. */
 icet_status icet_debug_pinv3_double(icet_ctx* ctx, const float* a, int32_t n, float* out);
+/* Diagnostic hook for the point-pass tests: the arguments and the ONE point pass of icet_score_indexed_device (scan 2 r at pose d_X[r] against parked keyframe
+ * kf_index[r]), then, instead of the score, every voxel's raw accumulator record as the point pass and the drain of its overflow list leave it:
+ * d_sums (device, 16-byte aligned -- ICET_ERR_BAD_ARG otherwise --, n_regs * V * 80 bytes) = n_regs x V records of 80 bytes, indexed by voxel id (V = bins_phi * bins_theta, voxel = bins_theta * polar bin + azimuth bin):
+ *     uint32 n2 (points in the voxel's angular bin), uint32 m (those inside the cluster bounds), then nine int64 = round(s * 2^36) summed over flushes for
+ *     s = sum dx, dy, dz, dx dx, dx dy, dx dz, dy dy, dy dz, dz dz of d = q - mu1 over the m points; zeros for a voxel that is not active in the keyframe.
+ * The accumulators and the overflow count are left at zero, as a solve leaves them.  Never captured into a graph. */
+icet_status icet_debug_point_sums_device(icet_ctx* ctx, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
+                                         const float* d_X, void* d_sums);
+/* Diagnostic hook for the point-pass tests: n host-side floats through the float -> 2^36 fixed-point conversions of the point pass; out: n x 3 uint64 =
+ * the two-instruction biased form (defined for |v| < 2^15) | the wide biased form | the unbiased form that selects between them per value. */
+icet_status icet_debug_fix(icet_ctx* ctx, const float* v, int32_t n, uint64_t* out);
 
 /* Launch-shape and diagnostic knobs of ONE context (the library never reads the environment).  Defaults are the measured
  * optima.  Launch-shape knobs yield the same result bits; "force_exact", "guard_scale" and "lut_polar_quantile" preserve every
