@@ -277,6 +277,55 @@ def load_library():
     return L
 
 
+def _dev_scans(descs):
+    """The icet_dev_scan array of (device_ptr, n, ld) triples (one entry even when there is none: ctypes has no empty array to pass)."""
+    return (DevScan * max(len(descs), 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in descs])
+
+
+def _vp(a):
+    """An optional device pointer."""
+    return C.c_void_p(a) if a else None
+
+
+def _start_offsets(start_offsets, query):
+    """The S x 6 float32 start offsets of a closure call (None: none), S as the query names it."""
+    if start_offsets is None:
+        return None
+    off = np.ascontiguousarray(np.asarray(start_offsets, np.float32).reshape(-1, 6))
+    if off.shape[0] != query.n_starts:
+        raise IcetError(ICET_ERR_BAD_ARG, "start_offsets must hold n_starts rows of 6")
+    return off
+
+
+def _data(a):
+    """The address of an optional host array."""
+    return a.ctypes.data if a is not None else None
+
+
+def _closure_dicts(recs, by_appearance, coarse):
+    """One dict per closure record (CLOSURE_DTYPE): slot (None: no winner), reg, accepted, n_candidates, then stamp, d2, x0, X, pred_stds, cov, score, each None
+    without a winner.  A query by appearance alone names its d2 ``distance`` and adds ``shift``; a coarse query adds ``coarse`` = dict(score, a, b, h) and,
+    by appearance and only where there is a winner, ``distance`` and ``shift`` beside d2."""
+    res = []
+    for r in recs:
+        win = r["slot"] >= 0
+        d = dict(slot=int(r["slot"]) if win else None, reg=int(r["reg"]), accepted=bool(r["accepted"]), n_candidates=int(r["n_candidates"]))
+        o = np.array(r["out"])
+        v = {"stamp": int(r["stamp"]), "distance" if by_appearance and not coarse else "d2": float(r["d2"])}
+        if by_appearance and not coarse:
+            v["shift"] = int(r["reserved0"])
+        v.update(x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(), cov=o[12:48].reshape(6, 6).copy(),
+                 score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")})
+        if coarse:
+            code = int(r["reserved1"][1])
+            v["coarse"] = dict(score=int(r["reserved1"][0]), h=code & 255, a=((code >> 8) & 255) - 32, b=((code >> 16) & 255) - 32)
+        d.update(v if win else dict.fromkeys(v))
+        if coarse and by_appearance and win:
+            d.update(distance=float(r["d2"]), shift=int(r["reserved0"]))
+        res.append(d)
+    return res
+
+
 def _colmajor(scan):
     """N x 3 array-like -> float32 (3, N) C-contiguous buffer == column-major N x 3 (Eigen::MatrixXf::data())."""
     a = np.asarray(scan, dtype=np.float32)
@@ -365,12 +414,12 @@ class Context:
     def keyframe_device(self, scan1_descs, params, d_rows_ptr=None):
         """Park the keyframe of the scans (device_ptr, n, ld) in this context (icet_keyframe_device[_n]: with d_rows_ptr -- a device int32
         array -- n is an upper bound and the actual row counts are read on the device)."""
-        A = (DevScan * max(len(scan1_descs), 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan1_descs])
+        A = _dev_scans(scan1_descs)
         self._check(load_library().icet_keyframe_device_n(self._h, C.byref(params), len(scan1_descs), A, C.c_void_p(d_rows_ptr) if d_rows_ptr else None))
 
     def register_device(self, scan2_descs, params, d_out_ptr, d_x0_ptr=None, d_rows_ptr=None):
         """Gauss-Newton loop of the scans against the parked keyframe (icet_register_device[_n])."""
-        B = (DevScan * max(len(scan2_descs), 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_register_device_n(self._h, C.byref(params), len(scan2_descs), B, C.c_void_p(d_rows_ptr) if d_rows_ptr else None,
                                                           C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr)))
 
@@ -381,7 +430,7 @@ class Context:
         idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
         if idx.shape[0] != k:
             raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_register_indexed_device(self._h, C.byref(params), k, idx.ctypes.data, B,
                                                                 C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr)))
 
@@ -392,7 +441,7 @@ class Context:
         idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
         if idx.shape[0] != k:
             raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_register_indexed_scored_device(self._h, C.byref(params), k, idx.ctypes.data, B,
                                                                        C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr), C.c_void_p(d_score_ptr)))
 
@@ -403,7 +452,7 @@ class Context:
         idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
         if idx.shape[0] != k:
             raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_score_indexed_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_score_ptr)))
 
     def select_best_device(self, group, n_groups, d_score_ptr, d_best_ptr, d_out_ptr=None, d_best_out_ptr=None):
@@ -459,7 +508,7 @@ class Context:
         idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
         if idx.shape[0] != k:
             raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_debug_point_sums_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_sums_ptr)))
 
     def debug_fix(self, values):
@@ -609,8 +658,8 @@ class Context:
     def solve_batch_device(self, scan1_descs, scan2_descs, params, d_out_ptr, d_x0_ptr=None):
         """scan*_descs: sequences of (device_ptr, n, ld).  d_out_ptr: device pointer to n_pairs x 48 floats."""
         k = len(scan1_descs)
-        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan1_descs])
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        A = _dev_scans(scan1_descs)
+        B = _dev_scans(scan2_descs)
         st = load_library().icet_solve_batch_device(self._h, C.byref(params), k, A, B,
                                                     C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr))
         self._check(st)
@@ -673,7 +722,7 @@ class KeyframeStore:
         -- a device int32 array -- n is an upper bound and the actual row counts are read on the device).  Asynchronous on the context's stream."""
         k = len(scan1_descs)
         sl = self._index(slots, k)
-        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan1_descs])
+        A = _dev_scans(scan1_descs)
         self._check(load_library().icet_keyframe_store_put_device(self._h, k, sl.ctypes.data, A, C.c_void_p(d_rows_ptr) if d_rows_ptr else None))
 
     def put(self, slots, scans):
@@ -689,7 +738,7 @@ class KeyframeStore:
         """Context.register_indexed_device against the store's slots (icet_keyframe_store_register_device)."""
         k = len(scan2_descs)
         idx = self._index(slot_index, k)
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_keyframe_store_register_device(self._h, C.byref(params), k, idx.ctypes.data, B,
                                                                        C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr)))
 
@@ -697,7 +746,7 @@ class KeyframeStore:
         """Context.register_indexed_scored_device against the store's slots (icet_keyframe_store_register_scored_device)."""
         k = len(scan2_descs)
         idx = self._index(slot_index, k)
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_keyframe_store_register_scored_device(self._h, C.byref(params), k, idx.ctypes.data, B,
                                                                               C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr), C.c_void_p(d_score_ptr)))
 
@@ -705,7 +754,7 @@ class KeyframeStore:
         """Context.score_indexed_device against the store's slots (icet_keyframe_store_score_device)."""
         k = len(scan2_descs)
         idx = self._index(slot_index, k)
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        B = _dev_scans(scan2_descs)
         self._check(load_library().icet_keyframe_store_score_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_score_ptr)))
 
     def debug_fetch(self, slot, what, count=None):
@@ -790,42 +839,30 @@ class KeyframeStore:
         q = len(scan2_descs)
         if T.shape[0] != q:
             raise IcetError(ICET_ERR_BAD_ARG, "scans and poses differ in length")
-        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
-        off = None
-        if start_offsets is not None:
-            off = np.ascontiguousarray(np.asarray(start_offsets, np.float32).reshape(-1, 6))
-            if off.shape[0] != query.n_starts:
-                raise IcetError(ICET_ERR_BAD_ARG, "start_offsets must hold n_starts rows of 6")
-        vp = lambda a: C.c_void_p(a) if a else None
+        B = _dev_scans(scan2_descs)
+        off = _start_offsets(start_offsets, query)
         self._check(load_library().icet_keyframe_store_close_device(self._h, C.byref(params), q, B, T.ctypes.data, st.ctypes.data, C.byref(query),
-                                                                     off.ctypes.data if off is not None else None, C.c_void_p(d_closure_ptr),
-                                                                     vp(d_cand_ptr), vp(d_x0_ptr), vp(d_out_ptr), vp(d_score_ptr)))
+                                                                     _data(off), C.c_void_p(d_closure_ptr),
+                                                                     _vp(d_cand_ptr), _vp(d_x0_ptr), _vp(d_out_ptr), _vp(d_score_ptr)))
 
     def find_closures(self, scans, poses, stamps, runlen, radius, k, starts=None, min_stamp_gap=0, max_chi2_per_voxel=float("inf"), min_voxels=0, flags=0):
         """The loop-closure query for host scans (N x 3 each) with their poses and stamps: one dict per scan -- slot (None: no winner), accepted, reg,
         n_candidates, stamp, d2, x0, X, pred_stds, cov, score -- from one icet_keyframe_store_close_device call.  ``starts``: S x 6 offsets added to each
         candidate's start pose (default: one start, no offset)."""
+        off = np.zeros((1, 6), np.float32) if starts is None else np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
+        query = ClosureQuery(float(radius), int(k), int(min_stamp_gap), off.shape[0], float(max_chi2_per_voxel), int(min_voxels), 0)
+        return self._closures(scans, lambda descs, rec: self.close_device(descs, poses, stamps, self._params(runlen, flags), query, rec, off), False, False)
+
+    def _closures(self, scans, call, by_appearance, coarse):
+        """Host scans (N x 3 each) staged on the device, ``call(scan2_descs, d_closure_ptr)`` -- one of the close_*_device forms -- and its records as dicts."""
         import torch
         dev = torch.device("cuda", self._ctx.device)
-        off = np.zeros((1, 6), np.float32) if starts is None else np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
         bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
         rec = torch.zeros((len(bufs), CLOSURE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
-        query = ClosureQuery(float(radius), int(k), int(min_stamp_gap), off.shape[0], float(max_chi2_per_voxel), int(min_voxels), 0)
-        self.close_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], poses, stamps, self._params(runlen, flags), query, rec.data_ptr(), off)
+        call([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], rec.data_ptr())
         self._ctx.sync()
-        recs = np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE)
-        res = []
-        for r in recs:
-            d = dict(slot=None if r["slot"] < 0 else int(r["slot"]), reg=int(r["reg"]), accepted=bool(r["accepted"]), n_candidates=int(r["n_candidates"]))
-            if d["slot"] is None:
-                d.update(stamp=None, d2=None, x0=None, X=None, pred_stds=None, cov=None, score=None)
-            else:
-                o = np.array(r["out"])
-                d.update(stamp=int(r["stamp"]), d2=float(r["d2"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(), cov=o[12:48].reshape(6, 6).copy(),
-                         score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")})
-            res.append(d)
-        return res
+        return _closure_dicts(np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE), by_appearance, coarse)
 
     # ---- loop closure by appearance (include/icet_hip.h "loop closure by appearance"; DESIGN.md section 17) ----
 
@@ -839,7 +876,7 @@ class KeyframeStore:
     def describe_device(self, scan_descs, d_desc_ptr, d_weight_ptr, d_rows_ptr=None):
         """icet_keyframe_store_describe_device: the descriptors of device scans into device buffers (n x rings x sectors uint8, n x sectors float32).  Asynchronous."""
         k = len(scan_descs)
-        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan_descs])
+        A = _dev_scans(scan_descs)
         self._check(load_library().icet_keyframe_store_describe_device(self._h, k, A, C.c_void_p(d_rows_ptr) if d_rows_ptr else None,
                                                                         C.c_void_p(d_desc_ptr), C.c_void_p(d_weight_ptr)))
 
@@ -877,10 +914,9 @@ class KeyframeStore:
         """icet_keyframe_store_candidates_appearance_device: the appearance search alone, into device buffers.  ``query.radius`` is read as max_distance."""
         q = len(scan2_descs)
         st = self._stamps(stamps, q)
-        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._check(load_library().icet_keyframe_store_candidates_appearance_device(self._h, q, B, st.ctypes.data if st is not None else None, C.byref(query),
-                                                                                     vp(d_cand_ptr), vp(d_dist_ptr), vp(d_shift_ptr), vp(d_x0_base_ptr)))
+        B = _dev_scans(scan2_descs)
+        self._check(load_library().icet_keyframe_store_candidates_appearance_device(self._h, q, B, _data(st), C.byref(query),
+                                                                                     _vp(d_cand_ptr), _vp(d_dist_ptr), _vp(d_shift_ptr), _vp(d_x0_base_ptr)))
 
     def candidates_by_appearance(self, scans, k, max_distance, stamps=None, min_stamp_gap=0):
         """Place recognition without poses: for every host scan (N x 3) the first ``k`` eligible slots in ascending (distance, slot) order.  Returns
@@ -905,43 +941,20 @@ class KeyframeStore:
         start pose from the best column shift; ``query.radius`` is read as max_distance.  One record (CLOSURE_DTYPE; d2 = distance, reserved0 = shift) per scan."""
         q = len(scan2_descs)
         st = self._stamps(stamps, q)
-        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
-        off = None
-        if start_offsets is not None:
-            off = np.ascontiguousarray(np.asarray(start_offsets, np.float32).reshape(-1, 6))
-            if off.shape[0] != query.n_starts:
-                raise IcetError(ICET_ERR_BAD_ARG, "start_offsets must hold n_starts rows of 6")
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._check(load_library().icet_keyframe_store_close_appearance_device(self._h, C.byref(params), q, B, st.ctypes.data if st is not None else None, C.byref(query),
-                                                                                off.ctypes.data if off is not None else None, C.c_void_p(d_closure_ptr),
-                                                                                vp(d_cand_ptr), vp(d_x0_ptr), vp(d_out_ptr), vp(d_score_ptr)))
+        B = _dev_scans(scan2_descs)
+        off = _start_offsets(start_offsets, query)
+        self._check(load_library().icet_keyframe_store_close_appearance_device(self._h, C.byref(params), q, B, _data(st), C.byref(query),
+                                                                                _data(off), C.c_void_p(d_closure_ptr),
+                                                                                _vp(d_cand_ptr), _vp(d_x0_ptr), _vp(d_out_ptr), _vp(d_score_ptr)))
 
     def find_closures_by_appearance(self, scans, runlen, k, starts=LATTICE_STARTS, max_distance=float("inf"), stamps=None, min_stamp_gap=0,
                                     max_chi2_per_voxel=float("inf"), min_voxels=0, flags=0):
         """find_closures without poses, for host scans (N x 3 each): one dict per scan -- slot (None: no winner), accepted, reg, n_candidates, stamp,
         distance, shift, x0, X, pred_stds, cov, score -- from one icet_keyframe_store_close_appearance_device call.  ``starts``: S x 6 offsets added to
         (0, 0, 0, 0, 0, yaw of the shift); the default is the 3 x 3 lattice of +-0.3 m, because the search finds the yaw and not the translation."""
-        import torch
-        dev = torch.device("cuda", self._ctx.device)
         off = np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
-        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
-        rec = torch.zeros((len(bufs), CLOSURE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
         query = ClosureQuery(float(max_distance), int(k), int(min_stamp_gap), off.shape[0], float(max_chi2_per_voxel), int(min_voxels), 0)
-        self.close_appearance_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], stamps, self._params(runlen, flags), query, rec.data_ptr(), off)
-        self._ctx.sync()
-        recs = np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE)
-        res = []
-        for r in recs:
-            d = dict(slot=None if r["slot"] < 0 else int(r["slot"]), reg=int(r["reg"]), accepted=bool(r["accepted"]), n_candidates=int(r["n_candidates"]))
-            if d["slot"] is None:
-                d.update(stamp=None, distance=None, shift=None, x0=None, X=None, pred_stds=None, cov=None, score=None)
-            else:
-                o = np.array(r["out"])
-                d.update(stamp=int(r["stamp"]), distance=float(r["d2"]), shift=int(r["reserved0"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(),
-                         cov=o[12:48].reshape(6, 6).copy(), score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")})
-            res.append(d)
-        return res
+        return self._closures(scans, lambda descs, rec: self.close_appearance_device(descs, stamps, self._params(runlen, flags), query, rec, off), True, False)
 
     # ---- coarse alignment (include/icet_hip.h "coarse alignment"; DESIGN.md section 18) ----
 
@@ -960,7 +973,7 @@ class KeyframeStore:
     def coarse_grid_device(self, scan_descs, d_grid_ptr, d_rows_ptr=None):
         """icet_keyframe_store_coarse_grid_device: the grids of device scans into a device buffer (n x cells x cells / 32 uint32).  Asynchronous."""
         k = len(scan_descs)
-        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan_descs])
+        A = _dev_scans(scan_descs)
         self._check(load_library().icet_keyframe_store_coarse_grid_device(self._h, k, A, C.c_void_p(d_rows_ptr) if d_rows_ptr else None, C.c_void_p(d_grid_ptr)))
 
     def coarse_grid(self, scans):
@@ -980,10 +993,9 @@ class KeyframeStore:
     def coarse_align_device(self, scan2_descs, k, d_cand_ptr, d_x0_base_ptr, search, d_x0_out_ptr=None, d_match_ptr=None, d_rows_ptr=None):
         """icet_keyframe_store_coarse_align_device: the search alone for Q x k candidates (device buffers as either candidates call writes them).  Asynchronous."""
         q = len(scan2_descs)
-        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._check(load_library().icet_keyframe_store_coarse_align_device(self._h, q, B, vp(d_rows_ptr), int(k), vp(d_cand_ptr), vp(d_x0_base_ptr), C.byref(search),
-                                                                            vp(d_x0_out_ptr), vp(d_match_ptr)))
+        B = _dev_scans(scan2_descs)
+        self._check(load_library().icet_keyframe_store_coarse_align_device(self._h, q, B, _vp(d_rows_ptr), int(k), _vp(d_cand_ptr), _vp(d_x0_base_ptr), C.byref(search),
+                                                                            _vp(d_x0_out_ptr), _vp(d_match_ptr)))
 
     def coarse_align(self, scans, cand, x0_base, window=12, n_yaw=1, yaw_step=np.pi / 120, half_turn=True, min_score=1):
         """The coarse search for host scans (N x 3 each): ``cand`` (Q, k) slots (-1: none) and ``x0_base`` (Q, k, 6) base starts, e.g. from candidates() or
@@ -1017,51 +1029,25 @@ class KeyframeStore:
                 raise IcetError(ICET_ERR_BAD_ARG, "scans and poses differ in length")
         else:
             st = self._stamps(stamps, q)
-        B = (DevScan * max(q, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
-        off = None
-        if start_offsets is not None:
-            off = np.ascontiguousarray(np.asarray(start_offsets, np.float32).reshape(-1, 6))
-            if off.shape[0] != query.n_starts:
-                raise IcetError(ICET_ERR_BAD_ARG, "start_offsets must hold n_starts rows of 6")
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._check(load_library().icet_keyframe_store_close_coarse_device(self._h, C.byref(params), q, B, T.ctypes.data if T is not None else None,
-                                                                            st.ctypes.data if st is not None else None, C.byref(query), C.byref(search),
-                                                                            off.ctypes.data if off is not None else None, C.c_void_p(d_closure_ptr),
-                                                                            vp(d_cand_ptr), vp(d_x0_ptr), vp(d_out_ptr), vp(d_score_ptr), vp(d_match_ptr)))
+        B = _dev_scans(scan2_descs)
+        off = _start_offsets(start_offsets, query)
+        self._check(load_library().icet_keyframe_store_close_coarse_device(self._h, C.byref(params), q, B, _data(T),
+                                                                            _data(st), C.byref(query), C.byref(search),
+                                                                            _data(off), C.c_void_p(d_closure_ptr),
+                                                                            _vp(d_cand_ptr), _vp(d_x0_ptr), _vp(d_out_ptr), _vp(d_score_ptr), _vp(d_match_ptr)))
 
     def find_closures_coarse(self, scans, runlen, k, poses=None, stamps=None, starts=None, radius=float("inf"), min_stamp_gap=0, window=12, n_yaw=1, yaw_step=None,
                              half_turn=True, min_score=1, max_chi2_per_voxel=float("inf"), min_voxels=0, flags=0):
         """find_closures (``poses`` given; ``radius`` in metres) or find_closures_by_appearance (``poses`` None; ``radius`` is max_distance) with the coarse alignment
         of every candidate's start, for host scans (N x 3 each): their dicts plus ``coarse`` = dict(score, a, b, h) of the winner.  ``starts``: S x 6 offsets
         added to the coarse start (default: one start, no offset).  ``yaw_step`` defaults to pi / sectors of the appearance search, pi / 120 without one."""
-        import torch
-        dev = torch.device("cuda", self._ctx.device)
         off = np.zeros((1, 6), np.float32) if starts is None else np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 6))
         if yaw_step is None:
             yaw_step = np.pi / (self.appearance.sectors if self.appearance is not None else 120)
-        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
-        rec = torch.zeros((len(bufs), CLOSURE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
         query = ClosureQuery(float(radius), int(k), int(min_stamp_gap), off.shape[0], float(max_chi2_per_voxel), int(min_voxels), 0)
-        self.close_coarse_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], poses, stamps, self._params(runlen, flags), query,
-                                 self.coarse_search(window, n_yaw, yaw_step, half_turn, min_score), rec.data_ptr(), off)
-        self._ctx.sync()
-        recs = np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE)
-        res = []
-        for r in recs:
-            d = dict(slot=None if r["slot"] < 0 else int(r["slot"]), reg=int(r["reg"]), accepted=bool(r["accepted"]), n_candidates=int(r["n_candidates"]))
-            if d["slot"] is None:
-                d.update(stamp=None, d2=None, x0=None, X=None, pred_stds=None, cov=None, score=None, coarse=None)
-            else:
-                o = np.array(r["out"])
-                code = int(r["reserved1"][1])
-                d.update(stamp=int(r["stamp"]), d2=float(r["d2"]), x0=np.array(r["x0"]), X=o[:6].copy(), pred_stds=o[6:12].copy(), cov=o[12:48].reshape(6, 6).copy(),
-                         score={n: r["score"][n].item() for n in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")},
-                         coarse=dict(score=int(r["reserved1"][0]), h=code & 255, a=((code >> 8) & 255) - 32, b=((code >> 16) & 255) - 32))
-                if poses is None:
-                    d.update(distance=float(r["d2"]), shift=int(r["reserved0"]))
-            res.append(d)
-        return res
+        search = self.coarse_search(window, n_yaw, yaw_step, half_turn, min_score)
+        return self._closures(scans, lambda descs, rec: self.close_coarse_device(descs, poses, stamps, self._params(runlen, flags), query, search, rec, off),
+                              poses is None, True)
 
     def best_match(self, scan2, slot_index, x0, runlen, flags=0):
         """The loop-closure check: registration r = host scan2 (N x 3) against slot slot_index[r] from x0[r]; all of them one group, scored and
@@ -1156,8 +1142,8 @@ class MultiContext:
         producer_stream: raw hipStream_t of devices[0] whose queued work (the writes of d_x0 / the scans) the solve must wait for.
         asynchronous=True returns as soon as the shares are handed to the device threads; call :meth:`sync` before reading d_out."""
         k = len(scan1_descs)
-        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan1_descs])
-        B = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in scan2_descs])
+        A = _dev_scans(scan1_descs)
+        B = _dev_scans(scan2_descs)
         fn = load_library().icet_multi_solve_batch_device_async if asynchronous else load_library().icet_multi_solve_batch_device_after
         self._check(fn(self._h, C.byref(params), k, A, B, C.c_void_p(d_x0_ptr) if d_x0_ptr else None, C.c_void_p(d_out_ptr),
                        C.c_void_p(producer_stream) if producer_stream else None))
@@ -1305,7 +1291,7 @@ class Node:
     def push_many_device(self, frames):
         """A burst of frames already in HBM, [(device_ptr, n, ld), ...]: icet_node_push_many_device -- pushed one after the other inside the library (one FFI call for all of them)."""
         k = len(frames)
-        A = (DevScan * max(k, 1))(*[DevScan(int(p), int(n), int(ld)) for (p, n, ld) in frames])
+        A = _dev_scans(frames)
         R = (NodeResult * max(k, 1))()
         st = load_library().icet_node_push_many_device(self._h, A, k, R)
         if st != ICET_OK:

@@ -694,7 +694,6 @@ inline int chunks_for(int n_pairs, int max_n, int per_block_min, int target_bloc
 
 }  // namespace
 
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t init_accumulate_kernels() {
     hipError_t e = hipSuccess;

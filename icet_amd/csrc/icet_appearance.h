@@ -1,6 +1,6 @@
 // icet_amd/csrc/icet_appearance.h -- the RULE of the keyframe store's appearance search (include/icet_hip.h icet_keyframe_store_close_appearance_device;
 // DESIGN.md section 17), in one place: the cell and the height code of a point, the column weight, the distance of two descriptors at a column shift, the
-// eligibility test and the start pose of a shift.  HIP-free C++: the kernels of icet_appearance.hip, the host code of icet_capi.hip and the CPU test
+// eligibility test and the start pose of a shift.  HIP-free C++: the kernels of icet_appearance.hip, the host code of icet_store.hip and the CPU test
 // (tests/cpp/test_appearance.cpp) compile this text.
 //
 // DESCRIPTOR: rings x sectors bytes D[ring][sector], the largest height code of the points of a cell (0: empty), in the sensor frame; a rotation of the

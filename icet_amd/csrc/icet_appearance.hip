@@ -6,14 +6,15 @@
 //                          scratch back to zero for the next batch
 //     k_app_set_stamp      stamps without poses
 //     k_app_match          one block per slot: every shift's distance to each query, one lane per shift walking the columns in ascending order; the slot's key
-//     k_app_select_tiles / k_app_select_merge   the K smallest keys of each query: tiles of 1024 slots, then one block per query (the rounds of icet_closure.hip)
+//     k_app_select_tiles   the K smallest keys of each query, pass 1: tiles of 1024 slots; pass 2 and the record are icet_closure.hip's (launch_closure_merge,
+//                          launch_closure_record with the candidates' shifts)
 //     k_app_resolve        one thread per (query, candidate): distance, shift, start poses, keyframe index and row count of its registrations
-//     k_app_record         one thread per query: the winner's row, score, X0, distance and shift, and the acceptance gate
 // Maxima and minima of integers only: no float atomic, no dependence on the launch shape.  No kernel waits for another block.
 #include <hip/hip_runtime.h>
 #include "../../include/icet_hip.h"
 #include "icet_internal.h"
 #include "icet_appearance.h"
+#include "icet_closure_device.h"
 
 namespace icet {
 namespace {
@@ -22,15 +23,6 @@ using icet_closure_rule::kNoKey;
 namespace rule = icet_appearance_rule;
 
 constexpr int kBuildBlock = 256;
-constexpr int kSelectBlock = 256;
-constexpr int kMergeRegs = 16;                      // keys per thread the merge keeps in registers (icet_closure.hip)
-static_assert(kClosureTile % kSelectBlock == 0 && kSelectBlock == 256, "four waves per block, whole keys per lane");
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const uint64_t u = __shfl_xor((unsigned long long)v, o, 64); v = u < v ? u : v; }
-    return v;
-}
 
 // Grid (chunks, scans).  Block b of scan k takes the points [b * per_block, (b + 1) * per_block) of the scan: x, y and z are three coalesced streams of 4 B per
 // lane (the leading dimension of a scan is any number of floats, so the columns are not 16-byte aligned in general).  kLds: the table of the block fits the LDS
@@ -158,59 +150,10 @@ __global__ __launch_bounds__(384) void k_app_match(AppTable tab, const uint32_t*
 __global__ __launch_bounds__(kSelectBlock) void k_app_select_tiles(const unsigned long long* __restrict__ keys_all, int cap, int n_queries, int K,
                                                                    unsigned long long* __restrict__ part) {
     const int base = blockIdx.x * kClosureTile;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    constexpr int kPerLane = kClosureTile / 64;
-    for (int q = wave; q < n_queries; q += kSelectBlock / 64) {
-        uint64_t key[kPerLane];
-#pragma unroll
-        for (int i = 0; i < kPerLane; i++) {
-            const int slot = base + lane + 64 * i;
-            key[i] = slot < cap ? keys_all[(size_t)q * cap + slot] : kNoKey;
-        }
-        unsigned long long* out = part + ((size_t)q * gridDim.x + blockIdx.x) * K;
-        int k = 0;
-        for (; k < K; k++) {
-            uint64_t m = key[0];
-#pragma unroll
-            for (int i = 1; i < kPerLane; i++) m = key[i] < m ? key[i] : m;
-            const uint64_t b = wave_min_u64(m);
-            if (b == kNoKey) break;                                   // (the same for every lane)
-            if (lane == 0) out[k] = b;
-#pragma unroll
-            for (int i = 0; i < kPerLane; i++) key[i] = key[i] == b ? kNoKey : key[i];
-        }
-        for (int j = k + lane; j < K; j += 64) out[j] = kNoKey;
-    }
-}
-
-// Pass 2: one block per query, K rounds of "the smallest key above the previous one" (keys of distinct slots are distinct).
-__global__ __launch_bounds__(kSelectBlock) void k_app_select_merge(const unsigned long long* __restrict__ part, int n_tiles, int K,
-                                                                   int32_t* __restrict__ cand, unsigned long long* __restrict__ keys) {
-    __shared__ uint64_t wmin[2][4];
-    const int q = blockIdx.x;
-    const unsigned long long* in = part + (size_t)q * n_tiles * K;
-    const int n = n_tiles * K;
-    uint64_t prev = 0; bool have_prev = false;
-    uint64_t reg[kMergeRegs];
-#pragma unroll
-    for (int i = 0; i < kMergeRegs; i++) { const int j = threadIdx.x + kSelectBlock * i; reg[i] = j < n ? in[j] : kNoKey; }
-    int k = 0;
-    for (; k < K; k++) {
-        uint64_t m = kNoKey;
-#pragma unroll
-        for (int i = 0; i < kMergeRegs; i++) { const uint64_t v = reg[i]; if ((!have_prev || v > prev) && v < m) m = v; }
-        for (int i = threadIdx.x + kSelectBlock * kMergeRegs; i < n; i += kSelectBlock) { const uint64_t v = in[i]; if ((!have_prev || v > prev) && v < m) m = v; }
-        m = wave_min_u64(m);
-        if ((threadIdx.x & 63) == 0) wmin[k & 1][threadIdx.x >> 6] = m;
-        __syncthreads();
-        const uint64_t a = wmin[k & 1][0], b2 = wmin[k & 1][1], c2 = wmin[k & 1][2], d2 = wmin[k & 1][3];
-        const uint64_t ab = a < b2 ? a : b2, cd = c2 < d2 ? c2 : d2;
-        const uint64_t b = ab < cd ? ab : cd;
-        if (b == kNoKey) break;
-        if (threadIdx.x == 0) { cand[q * K + k] = icet_closure_rule::key_slot(b); keys[q * K + k] = b; }
-        prev = b; have_prev = true;
-    }
-    for (int j = k + threadIdx.x; j < K; j += kSelectBlock) { cand[q * K + j] = -1; keys[q * K + j] = kNoKey; }
+    select_tile_smallest(n_queries, K, part, [&](int q, int s) -> uint64_t {
+        const int slot = base + s;
+        return slot < cap ? keys_all[(size_t)q * cap + slot] : kNoKey;
+    });
 }
 
 // One thread per (query, candidate).  dist / shift / x0_base (each may be null): the candidate's distance (+inf for a missing one), shift (-1) and start pose
@@ -220,7 +163,7 @@ __global__ __launch_bounds__(64) void k_app_resolve(int cap, int A, AppOffsets o
                                                     int32_t* __restrict__ shift, float* __restrict__ x0_base, int32_t* __restrict__ shift_of, float* __restrict__ x0,
                                                     int32_t* __restrict__ kf_of, int32_t* __restrict__ rows, int32_t* __restrict__ members, int32_t* __restrict__ offs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (offs && i <= n_queries) offs[i] = i * K * n_starts;
+    write_group_offset(i, n_queries, K, n_starts, offs);
     if (i >= n_queries * K) return;
     const int q = i / K;
     const int slot = cand[i];
@@ -231,49 +174,10 @@ __global__ __launch_bounds__(64) void k_app_resolve(int cap, int A, AppOffsets o
     if (shift) shift[i] = sh;
     if (shift_of) shift_of[i] = sh;
     if (x0_base) for (int c = 0; c < 6; c++) x0_base[(size_t)i * 6 + c] = b[c];
-    for (int s = 0; s < n_starts; s++) {
-        const int r = i * n_starts + s;
-        for (int c = 0; c < 6; c++) x0[(size_t)r * 6 + c] = slot >= 0 ? b[c] + off.off[s][c] : 0.f;
-        kf_of[r] = slot >= 0 ? slot : any_slot;
-        rows[r] = slot >= 0 ? INT32_MAX : 0;
-        members[r] = r;
-    }
-}
-
-// One thread per query: k_closure_record with the appearance distance in d2 and the shift in reserved0.  best == nullptr: no registration ran.
-__global__ __launch_bounds__(64) void k_app_record(PoseTable tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels,
-                                                   const int32_t* __restrict__ best, const int32_t* __restrict__ cand, const unsigned long long* __restrict__ keys,
-                                                   const int32_t* __restrict__ shift_of, const float* __restrict__ x0, const float* __restrict__ out,
-                                                   const icet_score* __restrict__ score, icet_closure* __restrict__ rec) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_queries) return;
-    icet_closure c;
-    int nc = 0;
-    for (int k = 0; k < K; k++) nc += cand[q * K + k] >= 0 ? 1 : 0;
-    int r = best ? best[q] : -1;
-    if (r >= 0 && cand[r / n_starts] < 0) r = -1;                     // (a padding registration scores no voxel and is never elected)
-    c.n_candidates = nc; c.reg = r; c.reserved0 = 0; c.reserved1[0] = 0; c.reserved1[1] = 0;
-    if (r >= 0) {
-        const int i = r / n_starts;                                   // q K + k
-        const int slot = cand[i];
-        c.slot = slot; c.stamp = tab.stamp[slot]; c.d2 = icet_closure_rule::key_d2(keys[i]); c.reserved0 = shift_of[i];
-        for (int k = 0; k < 6; k++) c.x0[k] = x0[(size_t)r * 6 + k];
-        for (int k = 0; k < 48; k++) c.out[k] = out[(size_t)r * 48 + k];
-        c.score = score[r];
-        c.accepted = (slot >= 0 && c.score.chi2_per_voxel <= max_chi2_per_voxel && c.score.voxels >= min_voxels) ? 1 : 0;
-    } else {
-        c.slot = -1; c.stamp = 0; c.d2 = 0.f; c.accepted = 0;
-        for (int k = 0; k < 6; k++) c.x0[k] = 0.f;
-        for (int k = 0; k < 48; k++) c.out[k] = 0.f;
-        c.score.chi2 = 0.f; c.score.chi2_per_voxel = 0.f; c.score.voxels = 0; c.score.points_in = 0; c.score.points = 0; c.score.overlap = 0.f;
-        c.score.reserved[0] = 0; c.score.reserved[1] = 0;
-    }
-    rec[q] = c;
+    write_registrations(i, slot, any_slot, b, off.off, n_starts, x0, kf_of, rows, members);
 }
 
 }  // namespace
-
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 constexpr int kAppLdsCells = 12288;                 // 48 KB of words: the largest table k_app_build keeps in LDS
 
@@ -322,9 +226,7 @@ hipError_t launch_app_search(const AppTable& tab, const PoseTable& poses, const 
     const int tiles = closure_tiles(tab.cap);
     k_app_select_tiles<<<tiles, kSelectBlock, 0, st>>>(d_keys_all, tab.cap, n_queries, K, d_part);
     ICET_LAUNCH_CHECK();
-    k_app_select_merge<<<n_queries, kSelectBlock, 0, st>>>(d_part, tiles, K, d_cand, d_keys);
-    ICET_LAUNCH_CHECK();
-    return hipSuccess;
+    return launch_closure_merge(d_part, tiles, n_queries, K, d_cand, d_keys, st);
 }
 
 hipError_t launch_app_resolve(int cap, int A, const AppOffsets& off, int n_queries, int K, int n_starts, int any_slot, const int32_t* d_cand,
@@ -333,15 +235,6 @@ hipError_t launch_app_resolve(int cap, int A, const AppOffsets& off, int n_queri
     const int n = n_queries * K > n_queries + 1 ? n_queries * K : n_queries + 1;
     k_app_resolve<<<(n + 63) / 64, 64, 0, st>>>(cap, A, off, n_queries, K, n_starts, any_slot, d_cand, d_keys, d_shift_all, d_dist, d_shift, d_x0_base, d_shift_of,
                                                d_x0, d_kf_of, d_rows, d_members, d_offs);
-    ICET_LAUNCH_CHECK();
-    return hipSuccess;
-}
-
-hipError_t launch_app_record(const PoseTable& tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels, const int32_t* d_best,
-                             const int32_t* d_cand, const unsigned long long* d_keys, const int32_t* d_shift_of, const float* d_x0, const float* d_out,
-                             const ::icet_score* d_score, ::icet_closure* d_closure, hipStream_t st) {
-    k_app_record<<<(n_queries + 63) / 64, 64, 0, st>>>(tab, n_queries, K, n_starts, max_chi2_per_voxel, min_voxels, d_best, d_cand, d_keys, d_shift_of, d_x0, d_out,
-                                                      d_score, d_closure);
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }

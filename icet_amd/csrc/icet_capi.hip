@@ -4,9 +4,11 @@
 // Gauss-Newton loop on one HIP stream and copies the 48 result floats per pair back.  No CPU
 // implementation of the algorithm lives here: if the device or the kernels are unavailable every
 // entry point returns ICET_ERR_NO_DEVICE / ICET_ERR_HIP.
+// The keyframe store (icet_keyframe_store_*) is icet_store.hip; it registers through register_indexed, below, and shares the context with
+// this file through icet_ctx.h.
 #include "../../include/icet_hip.h"
 #include "../../include/icet_nodes.h"
-#include "icet_internal.h"
+#include "icet_ctx.h"
 #include "icet_layout.h"
 #include "icet_closure.h"
 #include "icet_appearance.h"
@@ -26,148 +28,7 @@
 
 using namespace icet;
 
-struct icet_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    Workspace w;
-    Tuning tune;                    // icet_set_option
-    int32_t kf_pairs = 0; icet_params kf_params{};      // a keyframe parked by icet_keyframe_device (0 pairs = none)
-    int max_lds = 160 * 1024;       // hipDeviceAttributeMaxSharedMemoryPerBlock of the device
-    int lds_rank_ok = 0;            // this device passed lds_rank_selftest (icet_create)
-    std::string err;
-    // host staging (pinned) for descriptors and results
-    PairDesc* h_desc = nullptr; int32_t* h_seg = nullptr; int32_t h_cap_pairs = 0;
-    bool desc_kf_valid = false, desc_reg_valid = false;   // the pinned descriptors hold what the last icet_keyframe_device_n / icet_register_device_n call wrote (any other writer, and a re-allocation, clears both)
-    PairDesc* h_desc_rt = nullptr; int32_t h_cap_rt = 0;       // ICET_FLAG_ROUNDTRIP_SCAN2: descriptors of the round-tripped copy of scan 2
-    PairDesc* h_desc_reg = nullptr; int32_t* h_kf_of = nullptr;  // staging of an indexed call (icet_register_indexed_device), w.cap_regs (+ 1): apart from h_desc, whose scan-1 halves the same_desc shortcut keeps
-    int64_t ws_gen = 0;                                          // counts re-allocations of workspace buffers (part of the indexed call's graph key)
-    // device staging for host-pointer entry points
-    float* d_stage1 = nullptr; float* d_stage2 = nullptr; int64_t cap_stage1 = 0, cap_stage2 = 0;
-    float* d_out = nullptr; float* d_x0 = nullptr; int32_t cap_out_pairs = 0;
-    float* h_out = nullptr;
-    // aux (single pair): every side table of a solve lives in ONE device block (`d_pack`, words of 4 bytes, layout aux_layout()) behind the
-    // 48 result floats, so that results and side tables come back in one DMA into the pinned `h_pack`
-    AuxDev aux_dev{}; int aux_V = 0, aux_runlen = 0;
-    uint32_t* d_pack = nullptr; uint32_t* h_pack = nullptr; size_t cap_pack = 0;
-    float* h_pts2 = nullptr; float* d_pts2 = nullptr; size_t cap_pts2 = 0;   // `points2` (scan 2 under the last iteration's transform): device buffer + pinned host copy
-    float* h_x0 = nullptr;                                       // pinned, 6 x cap_out_pairs
-    icet_score* d_score = nullptr; icet_score* h_score = nullptr; int32_t cap_score = 0;     // scores of the host-pointer entry points (device + pinned)
-    int32_t* d_sel = nullptr; int32_t* h_sel = nullptr; int64_t cap_sel = 0;                // icet_select_best_device: the groups' members | offsets (device + pinned staging)
-    hipEvent_t ev_sel = nullptr; bool sel_in_flight = false;                                 // the copy out of h_sel
-    float* d_sph1 = nullptr; int32_t* d_idx1 = nullptr; size_t cap_side1 = 0;      // points1Spherical / pointIndices1 on request (icet_sidetables.hip)
-    float* d_sph2 = nullptr; int32_t* d_vox2 = nullptr; size_t cap_side2 = 0;      // points2Spherical / the rows' voxels on request
-    // host-pointer entry points: scan 2 is uploaded on a stream of its own, beside the keyframe build of scan 1
-    hipStream_t st_copy = nullptr; hipEvent_t ev_s2 = nullptr;
-    hipEvent_t ev_kf = nullptr, ev_kfd = nullptr, ev_prev = nullptr, ev_pts2 = nullptr;   // keyframe built / its tables on the host / transform of the last iteration known / points2 on the host
-    // icet_solve_begin .. icet_solve_end
-    struct Pending { bool active = false; float* x_out = nullptr; float* ps_out = nullptr; float* cov_out = nullptr; icet_aux aux{}; bool has_aux = false;
-                     int V = 0, rl = 0; int64_t n2 = 0; bool kf_tables = false, kf_done = false, pts2 = false, pts2_dev = false, tail_ints = false, side1 = false, side2 = false; int64_t n1 = 0;
-                     const float* scan2 = nullptr; int64_t ld2 = 0; } pend;
-    // timing
-    hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
-    std::vector<hipEvent_t> ev_acc;
-    float last_ms[4] = {0, 0, 0, 0};
-    bool timing_valid = false;
-    int last_iters = 0;
-    // Large device batches are cut into contiguous parts, each solved by a helper context on its own stream, so that
-    // the keyframe build of one part (latency / LDS bound) overlaps the Gauss-Newton loop of another (VALU bound).
-    std::vector<icet_ctx*> helpers;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_stage = nullptr; int stage_at = 0;            // see LaunchCfg::stage_event
-    hipEvent_t ev_desc = nullptr; bool desc_in_flight = false;   // completion of the last copy out of the pinned descriptor staging
-    // Small device batches whose launch geometry repeats call after call are replayed from a captured hipGraph (option "graph"): the ~33
-    // launches of a single-pair solve then cost one hipGraphLaunch on the host, and the command processor runs them back to back.
-    struct GraphKey { int64_t v[47]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key + the keyframe source (graph_key_of)
-    struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false; };
-    bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
-    GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
-    GraphSlot g_scored, g_score;                               // indexed registrations + score (icet_register_indexed_scored_device), the score of given poses (icet_score_indexed_device)
-    hipEvent_t ev_graph = nullptr; bool graph_in_flight = false;
-    // A caller inside this library (the sequential nodes, icet_nodes.hip) can put work of its own at the head of the NEXT icet_register_device_n call's launch
-    // sequence -- enqueued on the context's stream right before the loop's first kernel, captured into the same graph: the range filter and the loop of a frame
-    // are then ONE hipGraphLaunch (round 6: the loop's graph used to start 30-40 us after the filter's last kernel).  `prologue_key` names what the hook's
-    // launches depend on (buffers, grid): it is part of the graph key.  Cleared by the caller after the call (icet_ctx_set_prologue).
-    // A ragged throughput batch is laid out XCD-balanced (solve_device_part): slot s of the internal tables holds the caller's pair h_seg[n_pairs + 1 + s]
-    bool perm_active = false; int32_t perm_pairs = 0;
-    hipError_t (*prologue)(void*, hipStream_t) = nullptr; void* prologue_user = nullptr; int64_t prologue_key = 0;
-    // ... and have the LAST solve of the next icet_register_device_n call store 1 into a word of (coherent) pinned host memory once the results are written: the caller
-    // watches that word instead of synchronising the stream (icet_ctx_set_done_flag; part of the graph key)
-    int32_t* done_flag = nullptr;
-    // icet_sync after ONE small device-resident solve (icet_solve_batch_device, replayed graph) watches a word of its own the same way: h_sync_word, raised by that solve's
-    // last kernel.  armed_calls counts such solves since the last icet_sync; anything else enqueued on the context (or a second solve, whose reset of the word races with the
-    // first one's store) makes it 2 or more and icet_sync synchronises the stream as before.
-    int32_t* h_sync_word = nullptr; int armed_calls = 2;
-};
-
-// A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
-// keyframe side (row stride V; (V + 1) & ~1 for slot_of_voxel), on the borrowed context's device.  A put builds on the context and parks into rows of its own
-// (k_keyframe_store_park); the indexed calls read a row the way they read a parked keyframe.  id (never reused) and gen (bumped when the tables move) name
-// the tables in the graph key of an indexed call.
-struct icet_keyframe_store {
-    icet_ctx* ctx = nullptr;
-    icet_params shape{};                       // bins_phi, bins_theta, n, thresh, buff, flags & (TRUE_SORT | HALF_GAP_BOUNDS); runlen 0
-    int V = 0; int32_t capacity = 0;
-    SlotHot* hotS = nullptr; SlotFit* fitS = nullptr; int16_t* slot_of_voxel = nullptr; int32_t* n_slots = nullptr;
-    std::vector<uint8_t> occupied;             // capacity: the rows a put has filled
-    int64_t id = 0, gen = 0;
-    std::string err;
-    // the pose table: ONE allocation of capacity x 56 bytes at pose_stamp -- stamp[capacity] | tx | ty | tz | r0 .. r8 --, 0xFF bytes
-    // (NaN, stamp -1) where a slot has no pose; set_pose stages through h_pose (pinned), which its kernel reads when it runs (ev_pose: it has)
-    int64_t* pose_stamp = nullptr;
-    PoseTable pose_table() const { return PoseTable{pose_stamp, reinterpret_cast<float*>(pose_stamp + capacity), capacity}; }
-    PoseUpload* h_pose = nullptr; int32_t cap_h_pose = 0; hipEvent_t ev_pose = nullptr; bool pose_in_flight = false;
-    // buffers of a query (icet_keyframe_store_close_device), grown on demand: the search's per-tile lists; per (query, candidate); per registration; per query
-    unsigned long long* q_part = nullptr; size_t cap_part = 0;
-    unsigned long long* q_keys = nullptr; int32_t* q_cand = nullptr; int32_t cap_qk = 0;
-    float* q_x0 = nullptr; float* q_out = nullptr; icet_score* q_score = nullptr; int32_t* q_kf_of = nullptr; int32_t* q_rows = nullptr; int32_t* q_members = nullptr; int32_t cap_qr = 0;
-    int32_t* q_offs = nullptr; int32_t* q_best = nullptr;       // kClosureMaxQueries + 1, kClosureMaxQueries
-    // place recognition by appearance: null until icet_keyframe_store_enable_appearance
-    struct Appearance {
-        icet_appearance_rule::Consts k{}; int Rp = 0;             // Rp: words per column, ceil(rings / 4)
-        uint32_t* desc = nullptr; float* w = nullptr; int32_t* has = nullptr;      // the table: capacity rows (AppTable)
-        std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a descriptor
-        uint32_t* scratch = nullptr;                              // kAppBatch x rings x sectors words, zero between calls
-        uint32_t* qdesc = nullptr; float* qw = nullptr; int32_t* qhas = nullptr;   // the descriptors of a call's queries: a table of kAppBatch rows
-        unsigned long long* keys_all = nullptr; uint16_t* shift_all = nullptr; size_t cap_all = 0;      // n_queries x capacity, grown on demand
-        int32_t* shift_of = nullptr;                              // kClosureMaxQueries x kClosureMaxCandidates: the candidates' shifts, for the record
-    };
-    Appearance* app = nullptr;
-    AppTable app_table() const { return AppTable{app->desc, app->w, app->has, capacity, app->k.A, app->Rp}; }
-    // coarse alignment: null until icet_keyframe_store_enable_coarse
-    struct Coarse {
-        icet_coarse_rule::Consts k{};
-        uint32_t* grid = nullptr; int32_t* has = nullptr;         // the table: capacity rows of G x G / 32 words (CoarseTable)
-        std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a grid
-        uint32_t* scratch = nullptr;                              // kCoarseBatch x 2 x G x G words, zero between calls
-        uint32_t* qgrid = nullptr;                                // the own grids of a call's queries: kAppBatch rows
-        // per (query, candidate) of the largest call: base starts, coarse starts, matches, keys, slot bit counts; per hypothesis: transforms and live bit counts
-        float* base = nullptr; float* x0c = nullptr; icet_coarse_match* match = nullptr; unsigned long long* keys = nullptr; int32_t* key_bits = nullptr;
-        CoarseHyp* hyp = nullptr; int32_t* live_bits = nullptr;
-        size_t row_words() const { return (size_t)k.G * (size_t)k.W; }
-    };
-    Coarse* coarse = nullptr;
-    CoarseTable coarse_table() const { return CoarseTable{coarse->grid, coarse->has, capacity}; }
-};
-
 namespace {
-
-#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
-
-template <typename T> hipError_t dev_realloc(T*& p, size_t count) {
-    if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-    if (count == 0) return hipSuccess;
-    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-}
-
-bool params_ok(const icet_params* p) {
-    if (!p) return false;
-    if (p->runlen < 0 || p->runlen > 4096) return false;
-    if (p->bins_phi <= 0 || p->bins_theta <= 0 || p->n < 1) return false;
-    return true;
-}
 
 // The REGISTRATION side of the workspace (Workspace, icet_internal.h): n_regs registrations on a grid of V voxels.  Leaves the keyframe side alone.
 icet_status ensure_regs(icet_ctx* c, int32_t n_regs, int V) {
@@ -688,7 +549,6 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
 // moment ago on the same stream): the staging holds an occupied slot and the scans' full row counts -- the launch geometry is sized from those, as in
 // icet_register_device_n --, and behind the descriptor upload rows[r] replaces the count (k_init_state, or k_patch_counts in front of the scan-2 round trip) and
 // kf_of[r] the index.
-struct IndexedDev { const int32_t* kf_of; const int32_t* rows; };
 icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1,
                             const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr) {
     if (iters < 0) iters = p->runlen;
@@ -918,8 +778,7 @@ icet_status icet_solve_batch_device(icet_ctx* c, const icet_params* p, int32_t n
     if (n_pairs == 0) return ICET_OK;
     for (int k = 0; k < n_pairs; k++) {
         const icet_dev_scan &a = scan1[k], &b = scan2[k];
-        if (a.n < 0 || b.n < 0 || a.ld < a.n || b.ld < b.n || (a.n > 0 && !a.ptr) || (b.n > 0 && !b.ptr) ||
-            a.ld >= ((int64_t)1 << 30) || b.ld >= ((int64_t)1 << 30)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+        if (!dev_scan_ok(a) || !dev_scan_ok(b)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
     }
     HIPCHK(c, hipSetDevice(c->device));
     const int parts = (p->runlen == 0) ? 1 : batch_parts(c, p, n_pairs);
@@ -1088,7 +947,7 @@ icet_status icet_keyframe_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     int64_t tot1 = 0;
     for (int k = 0; k < n_pairs; k++) {
         const icet_dev_scan& a = scan1[k];
-        if (a.n < 0 || a.ld < a.n || (a.n > 0 && !a.ptr) || a.ld >= ((int64_t)1 << 30)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+        if (!dev_scan_ok(a)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
         tot1 += a.n;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1136,7 +995,7 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     int64_t tot2 = 0;
     for (int k = 0; k < n_pairs; k++) {
         const icet_dev_scan& b = scan2[k];
-        if (b.n < 0 || b.ld < b.n || (b.n > 0 && !b.ptr) || b.ld >= ((int64_t)1 << 30)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+        if (!dev_scan_ok(b)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
         tot2 += b.n;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1165,12 +1024,9 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     return enq();
 }
 
-// The indexed registrations of icet_register_indexed_device (mode kIdxRegister), the same followed by the score (kIdxScored: d_score), or the score of the poses
-// d_x0 alone (kIdxScoreOnly: no iteration, d_out unused).  src: the keyframe tables -- nullptr the context's parked keyframe (kf_index: parked keyframes), or a
-// keyframe store (kf_index: its occupied slots; icet_keyframe_store_register_device and its kin).
-enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2, kIdxDump = 3 };      // kIdxDump (icet_debug_point_sums_device): kIdxScoreOnly with the raw per-voxel sums (d_dump) in place of the score
-static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
-                                    icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr) {
+}  // extern "C"
+icet_status icet::register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
+                                   icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src, const IndexedDev* dev, uint32_t* d_dump) {
     if (!c) return ICET_ERR_BAD_ARG;
     const bool need_out = mode == kIdxRegister || mode == kIdxScored, need_score = mode == kIdxScored || mode == kIdxScoreOnly, need_x = mode == kIdxScoreOnly || mode == kIdxDump;
     if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (need_x && !d_x0) || (mode == kIdxDump && !d_dump)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
@@ -1178,8 +1034,7 @@ static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n
     // everything is checked before anything is touched: a refused call leaves the parked keyframe (and every slot of a store) as it was
     const icet_params& q = src ? src->shape : c->kf_params;
     const int32_t n_kf = src ? src->capacity : c->kf_pairs;
-    if (n_kf < 1 || q.bins_phi != p->bins_phi || q.bins_theta != p->bins_theta || q.n != p->n || q.thresh != p->thresh || q.buff != p->buff ||
-        ((q.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
+    if (n_kf < 1 || !same_keyframe_shape(q, *p)) {
         c->err = src ? "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape" : "no keyframe with these parameters is parked in this context (icet_keyframe_device)";
         return ICET_ERR_BAD_ARG;
     }
@@ -1190,7 +1045,7 @@ static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n
         }
         if (kf_index[r] < 0 || kf_index[r] >= n_kf) { c->err = "kf_index[" + std::to_string(r) + "] = " + std::to_string(kf_index[r]) + " is not a parked keyframe (0 .. " + std::to_string(c->kf_pairs - 1) + ")"; return ICET_ERR_BAD_ARG; }
         const icet_dev_scan& b = scan2[r];
-        if (b.n < 0 || b.ld < b.n || (b.n > 0 && !b.ptr) || b.ld >= ((int64_t)1 << 30)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+        if (!dev_scan_ok(b)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
         tot2 += b.n;
     }
     if (c->tune.keep != 0) { c->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
@@ -1234,6 +1089,7 @@ static icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n
     }
     return enq();
 }
+extern "C" {
 
 icet_status icet_register_indexed_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out) {
     return register_indexed(c, p, n_regs, kf_index, scan2, d_x0, d_out, nullptr, kIdxRegister);
@@ -1254,877 +1110,6 @@ icet_status icet_debug_point_sums_device(icet_ctx* c, const icet_params* p, int3
                                          const float* d_X, void* d_sums) {
     if (c && (reinterpret_cast<uintptr_t>(d_sums) & 15u)) { c->err = "icet_debug_point_sums_device: d_sums must be 16-byte aligned"; return ICET_ERR_BAD_ARG; }      // (the copy-out kernel stores 16 bytes at a time)
     return register_indexed(c, p, n_regs, kf_index, scan2, d_X, nullptr, nullptr, kIdxDump, nullptr, nullptr, static_cast<uint32_t*>(d_sums));
-}
-
-// ---- the keyframe store ----------------------------------------------------------------------------------------
-#define STORECHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    (s)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
-
-constexpr size_t kPoseBytes = sizeof(int64_t) + 12 * sizeof(float);      // the pose table, per slot (icet_keyframe_store::pose_table)
-
-// The four tables of `cap` rows of V voxels; all or nothing.
-static hipError_t store_alloc(int V, int32_t cap, SlotHot*& hot, SlotFit*& fit, int16_t*& sov, int32_t*& ns) {
-    hot = nullptr; fit = nullptr; sov = nullptr; ns = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&hot), sizeof(SlotHot) * (size_t)cap * V);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fit), sizeof(SlotFit) * (size_t)cap * V);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sov), sizeof(int16_t) * (size_t)cap * ((V + 1) & ~1));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ns), sizeof(int32_t) * (size_t)cap);
-    if (e != hipSuccess) {
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) if (q) (void)hipFree(q);
-        hot = nullptr; fit = nullptr; sov = nullptr; ns = nullptr;
-        (void)hipGetLastError();
-    }
-    return e;
-}
-
-// The descriptor table of `cap` rows (row: `row_words` words of columns, `cols` weights); all or nothing.
-static hipError_t app_alloc_table(size_t row_words, size_t cols, int32_t cap, uint32_t*& desc, float*& w, int32_t*& has) {
-    desc = nullptr; w = nullptr; has = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&desc), sizeof(uint32_t) * row_words * (size_t)cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w), sizeof(float) * cols * (size_t)cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&has), sizeof(int32_t) * (size_t)cap);
-    if (e != hipSuccess) {
-        for (void* q : {(void*)desc, (void*)w, (void*)has}) if (q) (void)hipFree(q);
-        desc = nullptr; w = nullptr; has = nullptr;
-        (void)hipGetLastError();
-    }
-    return e;
-}
-
-// The grid table of `cap` rows of `row_words` words; all or nothing.
-static hipError_t coarse_alloc_table(size_t row_words, int32_t cap, uint32_t*& grid, int32_t*& has) {
-    grid = nullptr; has = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&grid), sizeof(uint32_t) * row_words * (size_t)cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&has), sizeof(int32_t) * (size_t)cap);
-    if (e != hipSuccess) {
-        for (void* q : {(void*)grid, (void*)has}) if (q) (void)hipFree(q);
-        grid = nullptr; has = nullptr;
-        (void)hipGetLastError();
-    }
-    return e;
-}
-
-const char* icet_keyframe_store_last_error(const icet_keyframe_store* s) { return s ? s->err.c_str() : "null store"; }
-
-icet_status icet_keyframe_store_create(icet_ctx* c, const icet_params* p, int32_t capacity, icet_keyframe_store** out) {
-    if (out) *out = nullptr;
-    if (!c) return ICET_ERR_BAD_ARG;
-    if (!out || !p || p->bins_phi <= 0 || p->bins_theta <= 0 || p->n < 1 || capacity < 1) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if ((int64_t)p->bins_phi * p->bins_theta > kMaxVoxels) { c->err = "bins_phi*bins_theta exceeds the voxel limit (10000)"; return ICET_ERR_UNSUPPORTED; }
-    const int V = p->bins_phi * p->bins_theta;
-    if ((size_t)V * 12 + 8 + 4096 > (size_t)c->max_lds) { c->err = "grid too fine for this device's LDS (k_bin_scatter keeps 12 B per voxel in one block)"; return ICET_ERR_UNSUPPORTED; }
-    HIPCHK(c, hipSetDevice(c->device));
-    icet_keyframe_store* s = new (std::nothrow) icet_keyframe_store();
-    if (!s) { c->err = "host allocation failed"; return ICET_ERR_NOMEM; }
-    static std::atomic<int64_t> next_id{1};
-    s->ctx = c; s->V = V; s->capacity = capacity; s->id = next_id++;
-    s->shape = *p; s->shape.runlen = 0; s->shape.flags = p->flags & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS);
-    const hipError_t e = store_alloc(V, capacity, s->hotS, s->fitS, s->slot_of_voxel, s->n_slots);
-    if (e != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(e); delete s; return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
-    s->occupied.assign((size_t)capacity, 0);
-    hipError_t z = hipMalloc(reinterpret_cast<void**>(&s->pose_stamp), kPoseBytes * (size_t)capacity);
-    if (z != hipSuccess) { (void)hipGetLastError(); c->err = std::string("keyframe store: ") + hipGetErrorString(z); s->pose_stamp = nullptr; (void)icet_keyframe_store_destroy(s); return z == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
-    z = hipMemsetAsync(s->pose_stamp, 0xFF, kPoseBytes * (size_t)capacity, c->stream);      // no slot has a pose
-    if (z == hipSuccess) z = hipMemsetAsync(s->n_slots, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
-    if (z != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(z); (void)icet_keyframe_store_destroy(s); return ICET_ERR_HIP; }
-    *out = s;
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_destroy(icet_keyframe_store* s) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);              // (a put or a registration may still read or write the tables)
-    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots, (void*)s->pose_stamp, (void*)s->q_part, (void*)s->q_keys, (void*)s->q_cand,
-                    (void*)s->q_x0, (void*)s->q_out, (void*)s->q_score, (void*)s->q_kf_of, (void*)s->q_rows, (void*)s->q_members, (void*)s->q_offs, (void*)s->q_best}) if (q) (void)hipFree(q);
-    if (s->h_pose) (void)hipHostFree(s->h_pose);
-    if (s->ev_pose) (void)hipEventDestroy(s->ev_pose);
-    if (s->app) {
-        for (void* q : {(void*)s->app->desc, (void*)s->app->w, (void*)s->app->has, (void*)s->app->scratch, (void*)s->app->qdesc, (void*)s->app->qw, (void*)s->app->qhas,
-                        (void*)s->app->keys_all, (void*)s->app->shift_all, (void*)s->app->shift_of}) if (q) (void)hipFree(q);
-        delete s->app;
-    }
-    if (s->coarse) {
-        for (void* q : {(void*)s->coarse->grid, (void*)s->coarse->has, (void*)s->coarse->scratch, (void*)s->coarse->qgrid, (void*)s->coarse->base, (void*)s->coarse->x0c,
-                        (void*)s->coarse->match, (void*)s->coarse->keys, (void*)s->coarse->key_bits, (void*)s->coarse->hyp, (void*)s->coarse->live_bits}) if (q) (void)hipFree(q);
-        delete s->coarse;
-    }
-    delete s;
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    if (capacity <= s->capacity) return ICET_OK;
-    icet_ctx* c = s->ctx;
-    STORECHK(s, hipSetDevice(c->device));
-    STORECHK(s, hipStreamSynchronize(c->stream));            // nothing on the stream reads the old tables any more
-    SlotHot* hot; SlotFit* fit; int16_t* sov; int32_t* ns;
-    STORECHK(s, store_alloc(s->V, capacity, hot, fit, sov, ns));
-    const size_t old = (size_t)s->capacity, V = (size_t)s->V;
-    int64_t* pose = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&pose), kPoseBytes * (size_t)capacity);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) (void)hipFree(q);
-        s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-    }
-    // descriptors (a store with appearance enabled): a new table, the first `old` rows carried over, no descriptor behind them
-    uint32_t* adesc = nullptr; float* aw = nullptr; int32_t* ahas = nullptr;
-    const size_t arow = s->app ? (size_t)s->app->k.A * (size_t)s->app->Rp : 0, acol = s->app ? (size_t)s->app->k.A : 0;
-    if (s->app) {
-        e = app_alloc_table(arow, acol, capacity, adesc, aw, ahas);
-        if (e != hipSuccess) {
-            for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose}) (void)hipFree(q);
-            s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-        }
-        e = hipMemsetAsync(ahas, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ahas, s->app->has, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(adesc, s->app->desc, sizeof(uint32_t) * arow * old, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(aw, s->app->w, sizeof(float) * acol * old, hipMemcpyDeviceToDevice, c->stream);
-    }
-    // grids (a store with coarse alignment enabled): likewise
-    uint32_t* cgrid = nullptr; int32_t* chas = nullptr;
-    if (s->coarse && e == hipSuccess) {
-        e = coarse_alloc_table(s->coarse->row_words(), capacity, cgrid, chas);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);
-            for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas}) if (q) (void)hipFree(q);
-            s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-        }
-        e = hipMemsetAsync(chas, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(chas, s->coarse->has, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(cgrid, s->coarse->grid, sizeof(uint32_t) * s->coarse->row_words() * old, hipMemcpyDeviceToDevice, c->stream);
-    }
-    // poses and stamps: the new table starts empty (0xFF), then every array's first `old` entries are carried over
-    if (e == hipSuccess) e = hipMemsetAsync(pose, 0xFF, kPoseBytes * (size_t)capacity, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(pose, s->pose_stamp, sizeof(int64_t) * old, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(pose + capacity, sizeof(float) * (size_t)capacity, s->pose_stamp + old, sizeof(float) * old, sizeof(float) * old, 12, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hot, s->hotS, sizeof(SlotHot) * old * V, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fit, s->fitS, sizeof(SlotFit) * old * V, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sov, s->slot_of_voxel, sizeof(int16_t) * old * ((V + 1) & ~(size_t)1), hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ns, s->n_slots, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ns + old, 0, sizeof(int32_t) * ((size_t)capacity - old), c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas, (void*)cgrid, (void*)chas}) if (q) (void)hipFree(q);
-        s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-    }
-    if (s->coarse) {
-        for (void* q : {(void*)s->coarse->grid, (void*)s->coarse->has}) (void)hipFree(q);
-        s->coarse->grid = cgrid; s->coarse->has = chas; s->coarse->has_h.resize((size_t)capacity, 0);
-    }
-    if (s->app) {
-        for (void* q : {(void*)s->app->desc, (void*)s->app->w, (void*)s->app->has}) (void)hipFree(q);
-        s->app->desc = adesc; s->app->w = aw; s->app->has = ahas; s->app->has_h.resize((size_t)capacity, 0);
-        s->app->cap_all = 0;                                     // (the per-slot buffers of a search are sized by the capacity)
-    }
-    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots, (void*)s->pose_stamp}) (void)hipFree(q);
-    s->pose_stamp = pose;
-    s->hotS = hot; s->fitS = fit; s->slot_of_voxel = sov; s->n_slots = ns;
-    s->capacity = capacity; s->occupied.resize((size_t)capacity, 0);
-    s->gen++;                                                // the tables moved: no graph captured against the old ones is replayed
-    return ICET_OK;
-}
-
-static icet_status app_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst);
-static icet_status coarse_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst);
-
-icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, const int32_t* slots, const icet_dev_scan* scan1, const int32_t* d_rows) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    if (n < 0 || (n > 0 && (!slots || !scan1))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (n == 0) return ICET_OK;
-    // everything is checked before anything is touched: a refused put leaves every slot and the context's parked keyframe as they were
-    std::vector<uint8_t> named((size_t)s->capacity, 0);
-    for (int k = 0; k < n; k++) {
-        const int32_t sl = slots[k];
-        if (sl < 0 || sl >= s->capacity) { s->err = "slots[" + std::to_string(k) + "] = " + std::to_string(sl) + " is not a slot (0 .. " + std::to_string(s->capacity - 1) + ")"; return ICET_ERR_BAD_ARG; }
-        if (named[(size_t)sl]) { s->err = "slot " + std::to_string(sl) + " is named twice in one put"; return ICET_ERR_BAD_ARG; }
-        named[(size_t)sl] = 1;
-        const icet_dev_scan& a = scan1[k];
-        if (a.n < 0 || a.ld < a.n || (a.n > 0 && !a.ptr) || a.ld >= ((int64_t)1 << 30)) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    }
-    // the build: icet_keyframe_device_n in the store's shape (a replayed graph for <= 8 scans included), then the copy into the slots, never captured
-    icet_status st = icet_keyframe_device_n(c, &s->shape, n, scan1, d_rows);
-    c->kf_pairs = 0;                                         // a put is a keyframe build on the context: its own parked keyframe is gone
-    if (st != ICET_OK) { s->err = c->err; return st; }
-    for (int first = 0; first < n; first += kStoreParkMax) {
-        const int cnt = std::min(kStoreParkMax, n - first);
-        StoreParkSlots dst{};
-        for (int k = 0; k < cnt; k++) dst.slot[k] = slots[first + k];
-        const hipError_t e = launch_keyframe_store_park(c->w, s->V, first, cnt, dst, s->hotS, s->fitS, s->slot_of_voxel, s->n_slots, c->stream);
-        if (e != hipSuccess) {
-            for (int k = first; k < n; k++) s->occupied[(size_t)slots[k]] = 0;    // (what these rows hold is unknown)
-            s->err = std::string("k_keyframe_store_park: ") + hipGetErrorString(e);
-            return ICET_ERR_HIP;
-        }
-        for (int k = 0; k < cnt; k++) s->occupied[(size_t)dst.slot[k]] = 1;
-        const hipError_t pe = launch_closure_clear_pose(s->pose_table(), dst, cnt, c->stream);      // a new keyframe: whatever pose the slot had is not its pose
-        if (pe != hipSuccess) { s->err = std::string("k_closure_clear_pose: ") + hipGetErrorString(pe); return ICET_ERR_HIP; }
-        if (s->app) {                                            // the scans' descriptors into the same slots, behind the park
-            const icet_status as = app_put_batch(s, scan1 + first, d_rows ? d_rows + first : nullptr, cnt, dst);
-            if (as != ICET_OK) return as;
-        }
-        if (s->coarse) {                                         // and their grids
-            const icet_status cs = coarse_put_batch(s, scan1 + first, d_rows ? d_rows + first : nullptr, cnt, dst);
-            if (cs != ICET_OK) return cs;
-        }
-    }
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_register_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
-                                                const icet_dev_scan* scan2, const float* d_x0, float* d_out) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    const icet_status st = register_indexed(s->ctx, p, n_regs, slot_index, scan2, d_x0, d_out, nullptr, kIdxRegister, s);
-    if (st != ICET_OK) s->err = s->ctx->err;
-    return st;
-}
-
-icet_status icet_keyframe_store_register_scored_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
-                                                       const icet_dev_scan* scan2, const float* d_x0, float* d_out, icet_score* d_score) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    const icet_status st = register_indexed(s->ctx, p, n_regs, slot_index, scan2, d_x0, d_out, d_score, kIdxScored, s);
-    if (st != ICET_OK) s->err = s->ctx->err;
-    return st;
-}
-
-icet_status icet_keyframe_store_score_device(icet_keyframe_store* s, const icet_params* p, int32_t n_regs, const int32_t* slot_index,
-                                             const icet_dev_scan* scan2, const float* d_X, icet_score* d_score) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    const icet_status st = register_indexed(s->ctx, p, n_regs, slot_index, scan2, d_X, nullptr, d_score, kIdxScoreOnly, s);
-    if (st != ICET_OK) s->err = s->ctx->err;
-    return st;
-}
-
-// Test hook: one occupied slot's tables on the host (what: 0 n_slots, 1 SlotHot words, 2 SlotFit words, 3 slot_of_voxel int16).  Synchronises the context's stream.
-icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot, int32_t what, void* out, int64_t count) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    if (!out || count < 0 || slot < 0 || slot >= s->capacity || !s->occupied[(size_t)slot]) { s->err = "bad argument or empty slot"; return ICET_ERR_BAD_ARG; }
-    icet_ctx* c = s->ctx;
-    STORECHK(s, hipSetDevice(c->device));
-    STORECHK(s, hipStreamSynchronize(c->stream));
-    int32_t ns = 0;
-    STORECHK(s, hipMemcpy(&ns, s->n_slots + slot, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (what == 4) {                                          // the pose: 12 strided floats into a row-major 4 x 4
-        if (count > 16) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
-        float tR[12], T[16];
-        const PoseTable tab = s->pose_table();
-        STORECHK(s, hipMemcpy2D(tR, sizeof(float), tab.f + slot, sizeof(float) * (size_t)tab.cap, sizeof(float), 12, hipMemcpyDeviceToHost));
-        for (int a = 0; a < 3; a++) { for (int b = 0; b < 3; b++) T[4 * a + b] = tR[3 + 3 * a + b]; T[4 * a + 3] = tR[a]; }
-        T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
-        std::memcpy(out, T, sizeof(float) * (size_t)count);
-        return ICET_OK;
-    }
-    if (what == 6 || what == 7) {                             // the slot's descriptor: D[ring][sector] bytes out of the ring-packed columns; its weights
-        if (!s->app || !s->app->has_h[(size_t)slot]) { s->err = "the slot has no descriptor"; return ICET_ERR_BAD_ARG; }
-        const int A = s->app->k.A, Rn = s->app->k.Rn, Rp = s->app->Rp;
-        if (count > (what == 6 ? (int64_t)A * Rn : (int64_t)A)) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
-        if (what == 7) { if (count > 0) STORECHK(s, hipMemcpy(out, s->app->w + (size_t)slot * A, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost)); return ICET_OK; }
-        std::vector<uint32_t> words((size_t)A * Rp);
-        STORECHK(s, hipMemcpy(words.data(), s->app->desc + (size_t)slot * A * Rp, sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost));
-        uint8_t* o = static_cast<uint8_t*>(out);
-        for (int64_t i = 0; i < count; i++) { const int r = (int)(i / A), j = (int)(i % A); o[i] = (uint8_t)(words[(size_t)j * Rp + (r >> 2)] >> (8 * (r & 3))); }
-        return ICET_OK;
-    }
-    if (what == 8) {                                          // the slot's grid: G rows of G / 32 words
-        if (!s->coarse || !s->coarse->has_h[(size_t)slot]) { s->err = "the slot has no grid"; return ICET_ERR_BAD_ARG; }
-        if (count > (int64_t)s->coarse->row_words()) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
-        if (count > 0) STORECHK(s, hipMemcpy(out, s->coarse->grid + (size_t)slot * s->coarse->row_words(), sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost));
-        return ICET_OK;
-    }
-    const void* src = nullptr; int64_t cap = 0; size_t elem = 4;
-    switch (what) {
-        case 5: src = s->pose_stamp + slot; cap = 1; elem = 8; break;
-        case 0: src = s->n_slots + slot; cap = 1; break;
-        case 1: src = s->hotS + (size_t)slot * s->V; cap = (int64_t)ns * (int64_t)(sizeof(SlotHot) / 4); break;
-        case 2: src = s->fitS + (size_t)slot * s->V; cap = (int64_t)ns * (int64_t)(sizeof(SlotFit) / 4); break;
-        case 3: src = s->slot_of_voxel + (size_t)slot * ((s->V + 1) & ~1); cap = s->V; elem = 2; break;
-        default: s->err = "unknown table id"; return ICET_ERR_BAD_ARG;
-    }
-    if (count > cap) { s->err = "count too large"; return ICET_ERR_BAD_ARG; }
-    if (count > 0) STORECHK(s, hipMemcpy(out, src, (size_t)count * elem, hipMemcpyDeviceToHost));
-    return ICET_OK;
-}
-
-// ---- the loop-closure query ------------------------------------------------------------------------------------
-void icet_pose_step_from_x(const float X[6], float T[16]) { if (X && T) icet_closure_rule::pose_step_from_X(X, T); }
-
-icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, const int32_t* slots, const float* poses, const int64_t* stamps) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    if (n < 0 || (n > 0 && (!slots || !poses || !stamps))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (n == 0) return ICET_OK;
-    std::vector<uint8_t> named((size_t)s->capacity, 0);
-    for (int k = 0; k < n; k++) {
-        const int32_t sl = slots[k];
-        if (sl < 0 || sl >= s->capacity || !s->occupied[(size_t)sl]) { s->err = "slots[" + std::to_string(k) + "] = " + std::to_string(sl) + " is not an occupied slot of the store (capacity " + std::to_string(s->capacity) + ")"; return ICET_ERR_BAD_ARG; }
-        if (named[(size_t)sl]) { s->err = "slot " + std::to_string(sl) + " is named twice in one set_pose"; return ICET_ERR_BAD_ARG; }
-        named[(size_t)sl] = 1;
-    }
-    STORECHK(s, hipSetDevice(c->device));
-    if (s->pose_in_flight) { STORECHK(s, hipEventSynchronize(s->ev_pose)); s->pose_in_flight = false; }      // the previous set_pose's kernel has read the staging
-    if (n > s->cap_h_pose) {
-        if (s->h_pose) { STORECHK(s, hipHostFree(s->h_pose)); s->h_pose = nullptr; s->cap_h_pose = 0; }
-        STORECHK(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_pose), sizeof(PoseUpload) * (size_t)n));
-        s->cap_h_pose = n;
-    }
-    if (!s->ev_pose) STORECHK(s, hipEventCreateWithFlags(&s->ev_pose, hipEventDisableTiming));
-    for (int k = 0; k < n; k++) {
-        PoseUpload& u = s->h_pose[k];
-        const float* T = poses + 16 * (size_t)k;
-        u.slot = slots[k]; u.pad = 0; u.stamp = stamps[k];
-        for (int a = 0; a < 3; a++) { u.tR[a] = T[4 * a + 3]; for (int b = 0; b < 3; b++) u.tR[3 + 3 * a + b] = T[4 * a + b]; }
-    }
-    c->armed_calls = 2;
-    STORECHK(s, launch_closure_set_pose(s->pose_table(), s->h_pose, n, c->stream));
-    STORECHK(s, hipEventRecord(s->ev_pose, c->stream)); s->pose_in_flight = true;
-    return ICET_OK;
-}
-
-// The arguments of a query that both entry points share; K, S as the query names them.
-static icet_status closure_query_ok(icet_keyframe_store* s, int32_t n_queries, const float* poses, const int64_t* stamps, const icet_closure_query* q) {
-    if (n_queries < 1 || n_queries > kClosureMaxQueries) { s->err = "n_queries must be 1 .. " + std::to_string(kClosureMaxQueries); return ICET_ERR_BAD_ARG; }
-    if (!poses || !stamps || !q) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (q->max_candidates < 1 || q->max_candidates > kClosureMaxCandidates) { s->err = "max_candidates must be 1 .. " + std::to_string(kClosureMaxCandidates); return ICET_ERR_BAD_ARG; }
-    if (!(q->radius >= 0.f)) { s->err = "radius must be a number >= 0"; return ICET_ERR_BAD_ARG; }
-    return ICET_OK;
-}
-
-static icet_status closure_ensure(icet_keyframe_store* s, int32_t n_queries, int K, int n_regs) {
-    icet_ctx* c = s->ctx;
-    const size_t need_part = (size_t)n_queries * (size_t)closure_tiles(s->capacity) * (size_t)K;
-    const int32_t qk = n_queries * K;
-    if (need_part <= s->cap_part && qk <= s->cap_qk && n_regs <= s->cap_qr && s->q_offs) return ICET_OK;
-    STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
-    if (!s->q_offs) { STORECHK(s, dev_realloc(s->q_offs, (size_t)kClosureMaxQueries + 1)); STORECHK(s, dev_realloc(s->q_best, (size_t)kClosureMaxQueries)); }
-    if (need_part > s->cap_part) { s->cap_part = 0; STORECHK(s, dev_realloc(s->q_part, need_part)); s->cap_part = need_part; }
-    if (qk > s->cap_qk) { s->cap_qk = 0; STORECHK(s, dev_realloc(s->q_keys, (size_t)qk)); STORECHK(s, dev_realloc(s->q_cand, (size_t)qk)); s->cap_qk = qk; }
-    if (n_regs > s->cap_qr) {
-        s->cap_qr = 0;
-        const size_t r = (size_t)n_regs;
-        STORECHK(s, dev_realloc(s->q_x0, r * 6)); STORECHK(s, dev_realloc(s->q_out, r * 48)); STORECHK(s, dev_realloc(s->q_score, r));
-        STORECHK(s, dev_realloc(s->q_kf_of, r)); STORECHK(s, dev_realloc(s->q_rows, r)); STORECHK(s, dev_realloc(s->q_members, r));
-        s->cap_qr = n_regs;
-    }
-    return ICET_OK;
-}
-
-static void closure_args(int32_t n_queries, const float* poses, const int64_t* stamps, const float* start_offsets, int n_starts, ClosureSearchArgs& qa, ClosurePoseArgs& pa) {
-    std::memset(&qa, 0, sizeof(qa)); std::memset(&pa, 0, sizeof(pa));
-    for (int q = 0; q < n_queries; q++) {
-        const float* T = poses + 16 * (size_t)q;
-        qa.tx[q] = T[3]; qa.ty[q] = T[7]; qa.tz[q] = T[11]; qa.stamp[q] = stamps[q];
-        for (int a = 0; a < 3; a++) { pa.t[q][a] = T[4 * a + 3]; for (int b = 0; b < 3; b++) pa.R[q][3 * a + b] = T[4 * a + b]; }
-    }
-    if (start_offsets) for (int i = 0; i < n_starts; i++) for (int k = 0; k < 6; k++) pa.off[i][k] = start_offsets[6 * i + k];
-}
-
-icet_status icet_keyframe_store_candidates_device(icet_keyframe_store* s, int32_t n_queries, const float* poses, const int64_t* stamps,
-                                                  const icet_closure_query* query, int32_t* d_cand, float* d_x0_base) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    icet_status st = closure_query_ok(s, n_queries, poses, stamps, query);
-    if (st != ICET_OK) return st;
-    if (!d_cand) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    STORECHK(s, hipSetDevice(c->device));
-    const int K = query->max_candidates;
-    st = closure_ensure(s, n_queries, K, 0);
-    if (st != ICET_OK) return st;
-    ClosureSearchArgs qa; ClosurePoseArgs pa;
-    closure_args(n_queries, poses, stamps, nullptr, 0, qa, pa);
-    c->armed_calls = 2;
-    const PoseTable tab = s->pose_table();
-    STORECHK(s, launch_closure_search(tab, qa, n_queries, K, query->radius, query->min_stamp_gap, s->q_part, d_cand, s->q_keys, c->stream));
-    if (d_x0_base) STORECHK(s, launch_closure_resolve(tab, pa, n_queries, K, 0, -1, d_cand, d_x0_base, nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_close_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
-                                             const float* poses, const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
-                                             icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score) {
-    static_assert(sizeof(icet_closure) == 288 && sizeof(icet_closure) % 16 == 0 && sizeof(icet_closure_query) == 32, "the records of the query (include/icet_hip.h; the ctypes mirrors of icet_amd/api.py)");
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    // everything is checked before anything is touched
-    icet_status st = closure_query_ok(s, n_queries, poses, stamps, query);
-    if (st != ICET_OK) return st;
-    if (!params_ok(p) || !scan2 || !d_closure) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (query->n_starts < 1 || query->n_starts > kClosureMaxStarts) { s->err = "n_starts must be 1 .. " + std::to_string(kClosureMaxStarts); return ICET_ERR_BAD_ARG; }
-    const icet_params& sh = s->shape;
-    if (sh.bins_phi != p->bins_phi || sh.bins_theta != p->bins_theta || sh.n != p->n || sh.thresh != p->thresh || sh.buff != p->buff ||
-        ((sh.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
-        s->err = "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG;
-    }
-    for (int q = 0; q < n_queries; q++) {
-        const icet_dev_scan& b = scan2[q];
-        if (b.n < 0 || b.ld < b.n || (b.n > 0 && !b.ptr) || b.ld >= ((int64_t)1 << 30)) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    }
-    if (c->tune.keep != 0) { s->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
-    STORECHK(s, hipSetDevice(c->device));
-    const int K = query->max_candidates, S = query->n_starts, R = n_queries * K * S;
-    st = closure_ensure(s, n_queries, K, R);
-    if (st != ICET_OK) return st;
-    int32_t any = -1;
-    for (int32_t j = 0; j < s->capacity && any < 0; j++) if (s->occupied[(size_t)j]) any = j;
-    ClosureSearchArgs qa; ClosurePoseArgs pa;
-    closure_args(n_queries, poses, stamps, start_offsets, S, qa, pa);
-    int32_t* cand = d_cand ? d_cand : s->q_cand;
-    float* x0 = d_x0 ? d_x0 : s->q_x0;
-    float* out = d_out ? d_out : s->q_out;
-    icet_score* score = d_score ? d_score : s->q_score;
-    c->armed_calls = 2;
-    const PoseTable tab = s->pose_table();
-    // 1 search, 2 resolve, 3 the indexed loop in scored mode, 4 the best of each query, 5 the records
-    STORECHK(s, launch_closure_search(tab, qa, n_queries, K, query->radius, query->min_stamp_gap, s->q_part, cand, s->q_keys, c->stream));
-    STORECHK(s, launch_closure_resolve(tab, pa, n_queries, K, S, any < 0 ? 0 : any, cand, nullptr, x0, s->q_kf_of, s->q_rows, s->q_members, s->q_offs, c->stream));
-    if (any < 0) {                                            // nothing to register against: every query ends without a winner
-        if (d_out) STORECHK(s, hipMemsetAsync(d_out, 0, sizeof(float) * 48 * (size_t)R, c->stream));
-        if (d_score) STORECHK(s, hipMemsetAsync(d_score, 0, sizeof(icet_score) * (size_t)R, c->stream));
-        STORECHK(s, launch_closure_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, nullptr, cand, s->q_keys, x0, out, score, d_closure, c->stream));
-        return ICET_OK;
-    }
-    std::vector<int32_t> idx((size_t)R, any);
-    std::vector<icet_dev_scan> regs((size_t)R);
-    for (int r = 0; r < R; r++) regs[(size_t)r] = scan2[r / (K * S)];
-    const IndexedDev dev{s->q_kf_of, s->q_rows};
-    st = register_indexed(c, p, R, idx.data(), regs.data(), x0, out, score, kIdxScored, s, &dev);
-    if (st != ICET_OK) { s->err = c->err; return st; }
-    STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
-    STORECHK(s, launch_closure_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, s->q_best, cand, s->q_keys, x0, out, score, d_closure, c->stream));
-    return ICET_OK;
-}
-
-// ---- loop closure by appearance ----------------------------------------------------------------------------------
-static bool dev_scan_ok(const icet_dev_scan& a) { return !(a.n < 0 || a.ld < a.n || (a.n > 0 && !a.ptr) || a.ld >= ((int64_t)1 << 30)); }
-
-static void app_scans(const icet_dev_scan* scan, int cnt, const int32_t* dst, AppScans& sc) {
-    std::memset(&sc, 0, sizeof(sc));
-    for (int k = 0; k < cnt; k++) { sc.ptr[k] = scan[k].ptr; sc.n[k] = (int32_t)scan[k].n; sc.ld[k] = (int32_t)scan[k].ld; sc.dst[k] = dst ? dst[k] : k; }
-}
-
-// The descriptors of the cnt <= kAppBatch scans a put has just parked, into the rows of their slots.
-static icet_status app_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst) {
-    icet_ctx* c = s->ctx;
-    AppScans sc; app_scans(scan, cnt, dst.slot, sc);
-    const AppTable tab = s->app_table();
-    hipError_t e = launch_app_build(sc, cnt, d_rows, s->app->k, s->app->scratch, c->stream);
-    if (e == hipSuccess) e = launch_app_finish(sc, cnt, s->app->k, s->app->scratch, &tab, nullptr, nullptr, c->stream);
-    if (e != hipSuccess) {
-        for (int k = 0; k < cnt; k++) s->app->has_h[(size_t)dst.slot[k]] = 0;     // (what these rows hold is unknown)
-        s->err = std::string("k_app_build: ") + hipGetErrorString(e);
-        return ICET_ERR_HIP;
-    }
-    for (int k = 0; k < cnt; k++) s->app->has_h[(size_t)dst.slot[k]] = 1;
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_enable_appearance(icet_keyframe_store* s, const icet_appearance_params* ap) {
-    static_assert(sizeof(icet_appearance_params) == 32, "the record of include/icet_hip.h (the ctypes mirror of icet_amd/api.py)");
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    if (s->app) { s->err = "appearance is already enabled on this store"; return ICET_ERR_BAD_ARG; }
-    icet_appearance_params d{};
-    d.sectors = 120; d.rings = 20; d.rho_max = 80.f; d.z_lo = -3.f; d.z_hi = 12.f;
-    if (ap) d = *ap;
-    if (!icet_appearance_rule::params_ok(d.sectors, d.rings, d.rho_max, d.z_lo, d.z_hi) || d.reserved[0] || d.reserved[1] || d.reserved[2]) {
-        s->err = "appearance parameters out of range (sectors even 8 .. 360, rings 1 .. 64, rho_max > 0, z_hi > z_lo, reserved words zero)"; return ICET_ERR_BAD_ARG;
-    }
-    STORECHK(s, hipSetDevice(c->device));
-    STORECHK(s, hipStreamSynchronize(c->stream));
-    auto* a = new (std::nothrow) icet_keyframe_store::Appearance();
-    if (!a) { s->err = "host allocation failed"; return ICET_ERR_NOMEM; }
-    a->k = icet_appearance_rule::make_consts(d.sectors, d.rings, d.rho_max, d.z_lo, d.z_hi);
-    a->Rp = (d.rings + 3) / 4;
-    const size_t A = (size_t)a->k.A, row = A * (size_t)a->Rp, cells = A * (size_t)a->k.Rn;
-    hipError_t e = app_alloc_table(row, A, s->capacity, a->desc, a->w, a->has);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->scratch), sizeof(uint32_t) * cells * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qdesc), sizeof(uint32_t) * row * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qw), sizeof(float) * A * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qhas), sizeof(int32_t) * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->shift_of), sizeof(int32_t) * kClosureMaxQueries * kClosureMaxCandidates);
-    if (e == hipSuccess) e = hipMemsetAsync(a->has, 0, sizeof(int32_t) * (size_t)s->capacity, c->stream);          // no slot has a descriptor
-    if (e == hipSuccess) e = hipMemsetAsync(a->scratch, 0, sizeof(uint32_t) * cells * kAppBatch, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* q : {(void*)a->desc, (void*)a->w, (void*)a->has, (void*)a->scratch, (void*)a->qdesc, (void*)a->qw, (void*)a->qhas, (void*)a->shift_of}) if (q) (void)hipFree(q);
-        delete a;
-        s->err = std::string("enable_appearance: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-    }
-    a->has_h.assign((size_t)s->capacity, 0);
-    s->app = a;
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_describe_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows, uint8_t* d_desc, float* d_weight) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    if (!s->app) { s->err = "appearance is not enabled on this store"; return ICET_ERR_BAD_ARG; }
-    if (n < 0 || (n > 0 && (!scan || !d_desc || !d_weight))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    for (int k = 0; k < n; k++) if (!dev_scan_ok(scan[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    if (n == 0) return ICET_OK;
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
-    const size_t A = (size_t)s->app->k.A, cells = A * (size_t)s->app->k.Rn;
-    for (int first = 0; first < n; first += kAppBatch) {
-        const int cnt = std::min(kAppBatch, n - first);
-        AppScans sc; app_scans(scan + first, cnt, nullptr, sc);
-        STORECHK(s, launch_app_build(sc, cnt, d_rows ? d_rows + first : nullptr, s->app->k, s->app->scratch, c->stream));
-        STORECHK(s, launch_app_finish(sc, cnt, s->app->k, s->app->scratch, nullptr, d_desc + cells * (size_t)first, d_weight + A * (size_t)first, c->stream));
-    }
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_set_stamp(icet_keyframe_store* s, int32_t n, const int32_t* slots, const int64_t* stamps) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    if (n < 0 || (n > 0 && (!slots || !stamps))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (n == 0) return ICET_OK;
-    std::vector<uint8_t> named((size_t)s->capacity, 0);
-    for (int k = 0; k < n; k++) {
-        const int32_t sl = slots[k];
-        if (sl < 0 || sl >= s->capacity || !s->occupied[(size_t)sl]) { s->err = "slots[" + std::to_string(k) + "] = " + std::to_string(sl) + " is not an occupied slot of the store (capacity " + std::to_string(s->capacity) + ")"; return ICET_ERR_BAD_ARG; }
-        if (named[(size_t)sl]) { s->err = "slot " + std::to_string(sl) + " is named twice in one set_stamp"; return ICET_ERR_BAD_ARG; }
-        named[(size_t)sl] = 1;
-    }
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
-    for (int first = 0; first < n; first += kAppBatch) {
-        const int cnt = std::min(kAppBatch, n - first);
-        AppStamps st{};
-        for (int k = 0; k < cnt; k++) { st.slot[k] = slots[first + k]; st.stamp[k] = stamps[first + k]; }
-        STORECHK(s, launch_app_set_stamp(s->pose_table(), st, cnt, c->stream));
-    }
-    return ICET_OK;
-}
-
-// The arguments both appearance queries share.
-static icet_status app_query_ok(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps, const icet_closure_query* q) {
-    if (!s->app) { s->err = "appearance is not enabled on this store"; return ICET_ERR_BAD_ARG; }
-    if (n_queries < 1 || n_queries > kClosureMaxQueries) { s->err = "n_queries must be 1 .. " + std::to_string(kClosureMaxQueries); return ICET_ERR_BAD_ARG; }
-    if (!scan2 || !q) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (q->max_candidates < 1 || q->max_candidates > kClosureMaxCandidates) { s->err = "max_candidates must be 1 .. " + std::to_string(kClosureMaxCandidates); return ICET_ERR_BAD_ARG; }
-    if (!(q->radius >= 0.f)) { s->err = "max_distance (the radius member) must be a number >= 0"; return ICET_ERR_BAD_ARG; }
-    if (q->min_stamp_gap > 0 && !stamps) { s->err = "min_stamp_gap > 0 needs the queries' stamps"; return ICET_ERR_BAD_ARG; }
-    for (int k = 0; k < n_queries; k++) if (!dev_scan_ok(scan2[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    return ICET_OK;
-}
-
-static icet_status app_ensure(icet_keyframe_store* s, int32_t n_queries) {
-    icet_ctx* c = s->ctx;
-    const size_t need = (size_t)n_queries * (size_t)s->capacity;
-    if (need <= s->app->cap_all) return ICET_OK;
-    STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
-    s->app->cap_all = 0;
-    STORECHK(s, dev_realloc(s->app->keys_all, need)); STORECHK(s, dev_realloc(s->app->shift_all, need));
-    s->app->cap_all = need;
-    return ICET_OK;
-}
-
-// The queries' descriptors and the search: candidates into cand, their keys into s->q_keys.
-static icet_status app_search(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps, const icet_closure_query* query, int32_t* cand) {
-    icet_ctx* c = s->ctx;
-    AppScans sc; app_scans(scan2, n_queries, nullptr, sc);
-    const AppTable qtab{s->app->qdesc, s->app->qw, s->app->qhas, kAppBatch, s->app->k.A, s->app->Rp};
-    AppQueryStamps qs{};
-    if (stamps) for (int q = 0; q < n_queries; q++) qs.stamp[q] = stamps[q];
-    STORECHK(s, launch_app_build(sc, n_queries, nullptr, s->app->k, s->app->scratch, c->stream));
-    STORECHK(s, launch_app_finish(sc, n_queries, s->app->k, s->app->scratch, &qtab, nullptr, nullptr, c->stream));
-    STORECHK(s, launch_app_search(s->app_table(), s->pose_table(), s->app->qdesc, s->app->qw, qs, n_queries, query->max_candidates, query->radius, query->min_stamp_gap,
-                                  s->app->keys_all, s->app->shift_all, s->q_part, cand, s->q_keys, c->stream));
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_candidates_appearance_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps,
-                                                             const icet_closure_query* query, int32_t* d_cand, float* d_dist, int32_t* d_shift, float* d_x0_base) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    icet_status st = app_query_ok(s, n_queries, scan2, stamps, query);
-    if (st != ICET_OK) return st;
-    if (!d_cand) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    STORECHK(s, hipSetDevice(c->device));
-    const int K = query->max_candidates;
-    st = closure_ensure(s, n_queries, K, 0);
-    if (st == ICET_OK) st = app_ensure(s, n_queries);
-    if (st != ICET_OK) return st;
-    c->armed_calls = 2;
-    st = app_search(s, n_queries, scan2, stamps, query, d_cand);
-    if (st != ICET_OK) return st;
-    if (d_dist || d_shift || d_x0_base) {
-        const AppOffsets off{};
-        STORECHK(s, launch_app_resolve(s->capacity, s->app->k.A, off, n_queries, K, 0, -1, d_cand, s->q_keys, s->app->shift_all, d_dist, d_shift, d_x0_base, nullptr,
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
-    }
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_close_appearance_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
-                                                        const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
-                                                        icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    // everything is checked before anything is touched
-    icet_status st = app_query_ok(s, n_queries, scan2, stamps, query);
-    if (st != ICET_OK) return st;
-    if (!params_ok(p) || !d_closure) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (query->n_starts < 1 || query->n_starts > kClosureMaxStarts) { s->err = "n_starts must be 1 .. " + std::to_string(kClosureMaxStarts); return ICET_ERR_BAD_ARG; }
-    const icet_params& sh = s->shape;
-    if (sh.bins_phi != p->bins_phi || sh.bins_theta != p->bins_theta || sh.n != p->n || sh.thresh != p->thresh || sh.buff != p->buff ||
-        ((sh.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
-        s->err = "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG;
-    }
-    if (c->tune.keep != 0) { s->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
-    STORECHK(s, hipSetDevice(c->device));
-    const int K = query->max_candidates, S = query->n_starts, R = n_queries * K * S;
-    st = closure_ensure(s, n_queries, K, R);
-    if (st == ICET_OK) st = app_ensure(s, n_queries);
-    if (st != ICET_OK) return st;
-    int32_t any = -1;
-    for (int32_t j = 0; j < s->capacity && any < 0; j++) if (s->occupied[(size_t)j]) any = j;
-    AppOffsets off{};
-    if (start_offsets) for (int i = 0; i < S; i++) for (int k = 0; k < 6; k++) off.off[i][k] = start_offsets[6 * i + k];
-    int32_t* cand = d_cand ? d_cand : s->q_cand;
-    float* x0 = d_x0 ? d_x0 : s->q_x0;
-    float* out = d_out ? d_out : s->q_out;
-    icet_score* score = d_score ? d_score : s->q_score;
-    c->armed_calls = 2;
-    const PoseTable tab = s->pose_table();
-    // 1 the queries' descriptors and the search, 2 resolve, 3 the indexed loop in scored mode, 4 the best of each query, 5 the records
-    st = app_search(s, n_queries, scan2, stamps, query, cand);
-    if (st != ICET_OK) return st;
-    STORECHK(s, launch_app_resolve(s->capacity, s->app->k.A, off, n_queries, K, S, any < 0 ? 0 : any, cand, s->q_keys, s->app->shift_all, nullptr, nullptr, nullptr,
-                                   s->app->shift_of, x0, s->q_kf_of, s->q_rows, s->q_members, s->q_offs, c->stream));
-    if (any < 0) {                                            // nothing to register against: every query ends without a winner
-        if (d_out) STORECHK(s, hipMemsetAsync(d_out, 0, sizeof(float) * 48 * (size_t)R, c->stream));
-        if (d_score) STORECHK(s, hipMemsetAsync(d_score, 0, sizeof(icet_score) * (size_t)R, c->stream));
-        STORECHK(s, launch_app_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, nullptr, cand, s->q_keys, s->app->shift_of, x0, out, score, d_closure, c->stream));
-        return ICET_OK;
-    }
-    std::vector<int32_t> idx((size_t)R, any);
-    std::vector<icet_dev_scan> regs((size_t)R);
-    for (int r = 0; r < R; r++) regs[(size_t)r] = scan2[r / (K * S)];
-    const IndexedDev dev{s->q_kf_of, s->q_rows};
-    st = register_indexed(c, p, R, idx.data(), regs.data(), x0, out, score, kIdxScored, s, &dev);
-    if (st != ICET_OK) { s->err = c->err; return st; }
-    STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
-    STORECHK(s, launch_app_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, s->q_best, cand, s->q_keys, s->app->shift_of, x0, out, score, d_closure, c->stream));
-    return ICET_OK;
-}
-
-// ---- coarse alignment -------------------------------------------------------------------------------------------
-// The grids of the cnt <= kStoreParkMax scans a put has just parked, into the rows of their slots.
-static icet_status coarse_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst) {
-    icet_ctx* c = s->ctx;
-    const CoarseTable tab = s->coarse_table();
-    for (int first = 0; first < cnt; first += kCoarseBatch) {
-        const int m = std::min(kCoarseBatch, cnt - first);
-        AppScans sc; app_scans(scan + first, m, dst.slot + first, sc);
-        const hipError_t e = launch_coarse_structure(sc, m, d_rows ? d_rows + first : nullptr, s->coarse->k, s->coarse->scratch, tab.grid, tab.has, tab.cap, c->stream);
-        if (e != hipSuccess) {
-            for (int k = first; k < cnt; k++) s->coarse->has_h[(size_t)dst.slot[k]] = 0;      // (what these rows hold is unknown)
-            s->err = std::string("k_coarse_extrema: ") + hipGetErrorString(e);
-            return ICET_ERR_HIP;
-        }
-        for (int k = 0; k < m; k++) s->coarse->has_h[(size_t)dst.slot[first + k]] = 1;
-    }
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_enable_coarse(icet_keyframe_store* s, const icet_coarse_params* cp) {
-    static_assert(sizeof(icet_coarse_params) == 32 && sizeof(icet_coarse_search) == 32 && sizeof(icet_coarse_match) == 32, "the records of include/icet_hip.h (the ctypes mirrors of icet_amd/api.py)");
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    if (s->coarse) { s->err = "coarse alignment is already enabled on this store"; return ICET_ERR_BAD_ARG; }
-    icet_coarse_params d{};
-    d.cells = 256; d.cell = 0.25f; d.z_lo = -3.f; d.z_hi = 12.f; d.min_span = 0.5f;
-    if (cp) d = *cp;
-    if (!icet_coarse_rule::params_ok(d.cells, d.cell, d.z_lo, d.z_hi, d.min_span) || d.reserved[0] || d.reserved[1] || d.reserved[2]) {
-        s->err = "coarse parameters out of range (cells a multiple of 32, 64 .. 512, cell > 0, z_hi > z_lo, min_span > 0, reserved words zero)"; return ICET_ERR_BAD_ARG;
-    }
-    STORECHK(s, hipSetDevice(c->device));
-    STORECHK(s, hipStreamSynchronize(c->stream));
-    auto* a = new (std::nothrow) icet_keyframe_store::Coarse();
-    if (!a) { s->err = "host allocation failed"; return ICET_ERR_NOMEM; }
-    a->k = icet_coarse_rule::make_consts(d.cells, d.cell, d.z_lo, d.z_hi, d.min_span);
-    const size_t row = a->row_words(), cells = (size_t)a->k.G * (size_t)a->k.G;
-    constexpr size_t kQK = (size_t)kClosureMaxQueries * kClosureMaxCandidates, kH = 2 * (2 * icet_coarse_rule::kMaxYaw + 1);
-    hipError_t e = launch_coarse_prepare(a->k);
-    if (e == hipSuccess) e = coarse_alloc_table(row, s->capacity, a->grid, a->has);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->scratch), sizeof(uint32_t) * 2 * cells * kCoarseBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qgrid), sizeof(uint32_t) * row * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->base), sizeof(float) * 6 * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->x0c), sizeof(float) * 6 * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->match), sizeof(icet_coarse_match) * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->keys), sizeof(unsigned long long) * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->key_bits), sizeof(int32_t) * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->hyp), sizeof(CoarseHyp) * kQK * kH);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->live_bits), sizeof(int32_t) * kQK * kH);
-    if (e == hipSuccess) e = hipMemsetAsync(a->has, 0, sizeof(int32_t) * (size_t)s->capacity, c->stream);          // no slot has a grid
-    if (e == hipSuccess) e = hipMemsetAsync(a->scratch, 0, sizeof(uint32_t) * 2 * cells * kCoarseBatch, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* q : {(void*)a->grid, (void*)a->has, (void*)a->scratch, (void*)a->qgrid, (void*)a->base, (void*)a->x0c, (void*)a->match, (void*)a->keys, (void*)a->key_bits,
-                        (void*)a->hyp, (void*)a->live_bits}) if (q) (void)hipFree(q);
-        delete a;
-        s->err = std::string("enable_coarse: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-    }
-    a->has_h.assign((size_t)s->capacity, 0);
-    s->coarse = a;
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_coarse_grid_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows, uint32_t* d_grid) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    if (!s->coarse) { s->err = "coarse alignment is not enabled on this store"; return ICET_ERR_BAD_ARG; }
-    if (n < 0 || (n > 0 && (!scan || !d_grid))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    for (int k = 0; k < n; k++) if (!dev_scan_ok(scan[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    if (n == 0) return ICET_OK;
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
-    for (int first = 0; first < n; first += kCoarseBatch) {
-        const int cnt = std::min(kCoarseBatch, n - first);
-        AppScans sc; app_scans(scan + first, cnt, nullptr, sc);
-        STORECHK(s, launch_coarse_structure(sc, cnt, d_rows ? d_rows + first : nullptr, s->coarse->k, s->coarse->scratch, d_grid + s->coarse->row_words() * (size_t)first,
-                                            nullptr, cnt, c->stream));
-    }
-    return ICET_OK;
-}
-
-static icet_status coarse_search_ok(icet_keyframe_store* s, const icet_coarse_search* se) {
-    if (!s->coarse) { s->err = "coarse alignment is not enabled on this store"; return ICET_ERR_BAD_ARG; }
-    if (!se) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (se->window < 0 || se->window > icet_coarse_rule::kMaxWindow) { s->err = "window must be 0 .. 32"; return ICET_ERR_BAD_ARG; }
-    if (se->n_yaw < 0 || se->n_yaw > icet_coarse_rule::kMaxYaw) { s->err = "n_yaw must be 0 .. 8"; return ICET_ERR_BAD_ARG; }
-    if (!std::isfinite(se->yaw_step)) { s->err = "yaw_step must be finite"; return ICET_ERR_BAD_ARG; }
-    if (se->half_turn != 0 && se->half_turn != 1) { s->err = "half_turn must be 0 or 1"; return ICET_ERR_BAD_ARG; }
-    if (se->min_score < 1) { s->err = "min_score must be >= 1"; return ICET_ERR_BAD_ARG; }
-    if (se->reserved[0] || se->reserved[1] || se->reserved[2]) { s->err = "reserved words must be zero"; return ICET_ERR_BAD_ARG; }
-    return ICET_OK;
-}
-
-// The queries' own grids, then the search of their candidates (d_cand, d_x0_base on the device).
-static icet_status coarse_run(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int32_t* d_rows, int K, const icet_coarse_search* se,
-                              const AppOffsets& off, int n_starts, int any_slot, const int32_t* d_cand, const float* d_x0_base, float* d_x0_out, icet_coarse_match* d_match,
-                              float* d_x0) {
-    icet_ctx* c = s->ctx;
-    icet_keyframe_store::Coarse* a = s->coarse;
-    for (int first = 0; first < n_queries; first += kCoarseBatch) {
-        const int cnt = std::min(kCoarseBatch, n_queries - first);
-        AppScans sc; app_scans(scan2 + first, cnt, nullptr, sc);
-        STORECHK(s, launch_coarse_structure(sc, cnt, d_rows ? d_rows + first : nullptr, a->k, a->scratch, a->qgrid + a->row_words() * (size_t)first, nullptr, cnt, c->stream));
-    }
-    AppScans all; app_scans(scan2, n_queries, nullptr, all);
-    const CoarseSearch cs{se->window, se->n_yaw, se->half_turn, se->min_score, se->yaw_step};
-    STORECHK(s, launch_coarse_align(s->coarse_table(), all, d_rows, a->k, cs, off, n_queries, K, n_starts, any_slot, d_cand, d_x0_base, a->qgrid, a->hyp, a->keys,
-                                    a->live_bits, a->key_bits, d_x0_out, d_match, d_x0, s->q_kf_of, s->q_rows, s->q_members, n_starts > 0 ? s->q_offs : nullptr, c->stream));
-    return ICET_OK;
-}
-
-icet_status icet_keyframe_store_coarse_align_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int32_t* d_rows, int32_t K,
-                                                    const int32_t* d_cand, const float* d_x0_base, const icet_coarse_search* search, float* d_x0_out,
-                                                    icet_coarse_match* d_match) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    icet_status st = coarse_search_ok(s, search);
-    if (st != ICET_OK) return st;
-    if (n_queries < 1 || n_queries > kClosureMaxQueries) { s->err = "n_queries must be 1 .. " + std::to_string(kClosureMaxQueries); return ICET_ERR_BAD_ARG; }
-    if (K < 1 || K > kClosureMaxCandidates) { s->err = "K must be 1 .. " + std::to_string(kClosureMaxCandidates); return ICET_ERR_BAD_ARG; }
-    if (!scan2 || !d_cand || !d_x0_base) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    for (int k = 0; k < n_queries; k++) if (!dev_scan_ok(scan2[k])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
-    const AppOffsets off{};
-    return coarse_run(s, n_queries, scan2, d_rows, K, search, off, 0, -1, d_cand, d_x0_base, d_x0_out, d_match, nullptr);
-}
-
-icet_status icet_keyframe_store_close_coarse_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
-                                                    const float* poses, const int64_t* stamps, const icet_closure_query* query,
-                                                    const icet_coarse_search* search, const float* start_offsets, icet_closure* d_closure, int32_t* d_cand,
-                                                    float* d_x0, float* d_out, icet_score* d_score, icet_coarse_match* d_match) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
-    // everything is checked before anything is touched
-    icet_status st = coarse_search_ok(s, search);
-    if (st != ICET_OK) return st;
-    if (poses) {
-        st = closure_query_ok(s, n_queries, poses, stamps, query);
-        if (st != ICET_OK) return st;
-        if (!scan2) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-        for (int q = 0; q < n_queries; q++) if (!dev_scan_ok(scan2[q])) { s->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    } else {
-        st = app_query_ok(s, n_queries, scan2, stamps, query);
-        if (st != ICET_OK) return st;
-    }
-    if (!params_ok(p) || !d_closure) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    if (query->n_starts < 1 || query->n_starts > kClosureMaxStarts) { s->err = "n_starts must be 1 .. " + std::to_string(kClosureMaxStarts); return ICET_ERR_BAD_ARG; }
-    const icet_params& sh = s->shape;
-    if (sh.bins_phi != p->bins_phi || sh.bins_theta != p->bins_theta || sh.n != p->n || sh.thresh != p->thresh || sh.buff != p->buff ||
-        ((sh.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) {
-        s->err = "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG;
-    }
-    if (c->tune.keep != 0) { s->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
-    STORECHK(s, hipSetDevice(c->device));
-    const int K = query->max_candidates, S = query->n_starts, R = n_queries * K * S;
-    st = closure_ensure(s, n_queries, K, R);
-    if (st == ICET_OK && !poses) st = app_ensure(s, n_queries);
-    if (st != ICET_OK) return st;
-    int32_t any = -1;
-    for (int32_t j = 0; j < s->capacity && any < 0; j++) if (s->occupied[(size_t)j]) any = j;
-    AppOffsets off{};
-    if (start_offsets) for (int i = 0; i < S; i++) for (int k = 0; k < 6; k++) off.off[i][k] = start_offsets[6 * i + k];
-    int32_t* cand = d_cand ? d_cand : s->q_cand;
-    float* x0 = d_x0 ? d_x0 : s->q_x0;
-    float* out = d_out ? d_out : s->q_out;
-    icet_score* score = d_score ? d_score : s->q_score;
-    icet_coarse_match* match = d_match ? d_match : s->coarse->match;
-    c->armed_calls = 2;
-    const PoseTable tab = s->pose_table();
-    // 1 the candidates and their base starts, as the existing calls find them, 2 the coarse alignment and the starts, 3 the indexed loop in scored mode,
-    // 4 the best of each query, 5 the records
-    if (poses) {
-        ClosureSearchArgs qa; ClosurePoseArgs pa;
-        closure_args(n_queries, poses, stamps, nullptr, 0, qa, pa);
-        STORECHK(s, launch_closure_search(tab, qa, n_queries, K, query->radius, query->min_stamp_gap, s->q_part, cand, s->q_keys, c->stream));
-        STORECHK(s, launch_closure_resolve(tab, pa, n_queries, K, 0, -1, cand, s->coarse->base, nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
-    } else {
-        st = app_search(s, n_queries, scan2, stamps, query, cand);
-        if (st != ICET_OK) return st;
-        const AppOffsets none{};
-        STORECHK(s, launch_app_resolve(s->capacity, s->app->k.A, none, n_queries, K, 0, -1, cand, s->q_keys, s->app->shift_all, nullptr, nullptr, s->coarse->base,
-                                       s->app->shift_of, nullptr, nullptr, nullptr, nullptr, nullptr, c->stream));
-    }
-    st = coarse_run(s, n_queries, scan2, nullptr, K, search, off, S, any < 0 ? 0 : any, cand, s->coarse->base, nullptr, match, x0);
-    if (st != ICET_OK) return st;
-    const int32_t* best = nullptr;
-    if (any < 0) {                                            // nothing to register against: every query ends without a winner
-        if (d_out) STORECHK(s, hipMemsetAsync(d_out, 0, sizeof(float) * 48 * (size_t)R, c->stream));
-        if (d_score) STORECHK(s, hipMemsetAsync(d_score, 0, sizeof(icet_score) * (size_t)R, c->stream));
-    } else {
-        std::vector<int32_t> idx((size_t)R, any);
-        std::vector<icet_dev_scan> regs((size_t)R);
-        for (int r = 0; r < R; r++) regs[(size_t)r] = scan2[r / (K * S)];
-        const IndexedDev dev{s->q_kf_of, s->q_rows};
-        st = register_indexed(c, p, R, idx.data(), regs.data(), x0, out, score, kIdxScored, s, &dev);
-        if (st != ICET_OK) { s->err = c->err; return st; }
-        STORECHK(s, launch_select_best(s->q_members, s->q_offs, n_queries, score, out, s->q_best, nullptr, c->stream));
-        best = s->q_best;
-    }
-    if (poses) STORECHK(s, launch_closure_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, best, cand, s->q_keys, x0, out, score, d_closure, c->stream));
-    else STORECHK(s, launch_app_record(tab, n_queries, K, S, query->max_chi2_per_voxel, query->min_voxels, best, cand, s->q_keys, s->app->shift_of, x0, out, score, d_closure, c->stream));
-    STORECHK(s, launch_coarse_record(n_queries, S, match, d_closure, c->stream));
-    return ICET_OK;
 }
 
 // Scores of the host-pointer entry points: device + pinned, n entries.

@@ -2,49 +2,31 @@
 // The rule -- distance, key, eligibility, start pose -- is icet_closure.h; this file is the kernels around it:
 //     k_closure_set_pose / k_closure_clear_pose   the store's pose table (arrays of `cap` entries: stamp | tx | ty | tz | r0 .. r8; a slot without a pose holds NaN)
 //     k_closure_search_tiles                      pass 1: every block reduces its tile of 1024 slots to its K smallest keys for each of the Q queries (a wave per query)
-//     k_closure_search_merge                      pass 2: one block per query merges the tiles' lists into the K candidates
+//     k_closure_search_merge                      pass 2: one block per query merges the tiles' lists into the K candidates (the appearance search's pass 2 as well)
 //     k_closure_resolve                           one thread per (query, candidate): X0 of its S starts, keyframe index and row count of its registrations
 //     k_closure_apply                             the keyframe indices into the indexed loop's table, behind that loop's own descriptor upload
-//     k_closure_record                            one thread per query: the winner's row, score, X0, and the acceptance gate
+//     k_closure_record                            one thread per query: the winner's row, score, X0, the shift of an appearance query, and the acceptance gate
 // Keys are (bits(d2) << 32) | slot, unique per slot, and both passes select minima of u64 keys: no float atomic, no dependence on the launch shape.
 #include <hip/hip_runtime.h>
 #include "../../include/icet_hip.h"
 #include "icet_internal.h"
 #include "icet_closure.h"
+#include "icet_closure_device.h"
 
 namespace icet {
 namespace {
 
 using icet_closure_rule::kNoKey;
-constexpr int kSearchBlock = 256;
-static_assert(kClosureTile % kSearchBlock == 0 && kSearchBlock == 256, "four waves per block, whole keys per lane");
-constexpr int kMergeRegs = 16;                      // keys per thread the merge keeps in registers (4096 per query: 256 tiles x K = 16)
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const uint64_t u = __shfl_xor((unsigned long long)v, o, 64); v = u < v ? u : v; }
-    return v;
-}
-// The block's minimum of v, known to every thread; wmin: 2 x 4 words, `round` alternates the half in use (one barrier per round).
-__device__ __forceinline__ uint64_t block_min_u64(uint64_t v, uint64_t (*wmin)[4], int round) {
-    v = wave_min_u64(v);
-    if ((threadIdx.x & 63) == 0) wmin[round & 1][threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint64_t a = wmin[round & 1][0], b = wmin[round & 1][1], c = wmin[round & 1][2], d = wmin[round & 1][3];
-    const uint64_t ab = a < b ? a : b, cd = c < d ? c : d;
-    return ab < cd ? ab : cd;
-}
 
 // Pass 1.  part[(q * gridDim.x + block) * K + k]: the block's k-th smallest key of query q (kNoKey behind the last).  The block reads its tile of slots once,
-// into LDS, for all queries; wave w then takes the queries w, w + 4, ...: a lane holds the keys of 16 slots in registers and the wave selects its K smallest by
-// K rounds of a wave-wide minimum -- shuffles only, no barrier inside a query (a block-wide round with its barrier cost 0.5 us, and a tile near the queries
-// ran Q x K of them in series).
-__global__ __launch_bounds__(kSearchBlock) void k_closure_search_tiles(PoseTable tab, ClosureSearchArgs qa, int n_queries, int K, float r2, int64_t min_gap,
+// into LDS, for all queries; wave w then takes the queries w, w + 4, ...: a lane holds the keys of 16 slots in registers and the wave selects its K smallest
+// (select_tile_smallest).
+__global__ __launch_bounds__(kSelectBlock) void k_closure_search_tiles(PoseTable tab, ClosureSearchArgs qa, int n_queries, int K, float r2, int64_t min_gap,
                                                                        unsigned long long* __restrict__ part) {
     __shared__ float lx[kClosureTile], ly[kClosureTile], lz[kClosureTile];
     __shared__ int64_t ls[kClosureTile];
     const int base = blockIdx.x * kClosureTile;
-    for (int i = threadIdx.x; i < kClosureTile; i += kSearchBlock) {
+    for (int i = threadIdx.x; i < kClosureTile; i += kSelectBlock) {
         const int slot = base + i;
         const bool in = slot < tab.cap;
         lx[i] = in ? tab.f[slot] : __builtin_nanf("");
@@ -53,33 +35,13 @@ __global__ __launch_bounds__(kSearchBlock) void k_closure_search_tiles(PoseTable
         ls[i] = in ? tab.stamp[slot] : 0;
     }
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    constexpr int kPerLane = kClosureTile / 64;
-    for (int q = wave; q < n_queries; q += kSearchBlock / 64) {
-        uint64_t key[kPerLane];
-#pragma unroll
-        for (int i = 0; i < kPerLane; i++) {
-            const int s = lane + 64 * i;
-            key[i] = icet_closure_rule::candidate_key(qa.tx[q], qa.ty[q], qa.tz[q], qa.stamp[q], lx[s], ly[s], lz[s], ls[s], r2, min_gap, base + s);
-        }
-        unsigned long long* out = part + ((size_t)q * gridDim.x + blockIdx.x) * K;
-        int k = 0;
-        for (; k < K; k++) {
-            uint64_t m = key[0];
-#pragma unroll
-            for (int i = 1; i < kPerLane; i++) m = key[i] < m ? key[i] : m;
-            const uint64_t b = wave_min_u64(m);
-            if (b == kNoKey) break;                                   // (the same for every lane)
-            if (lane == 0) out[k] = b;
-#pragma unroll
-            for (int i = 0; i < kPerLane; i++) key[i] = key[i] == b ? kNoKey : key[i];
-        }
-        for (int j = k + lane; j < K; j += 64) out[j] = kNoKey;
-    }
+    select_tile_smallest(n_queries, K, part, [&](int q, int s) {
+        return icet_closure_rule::candidate_key(qa.tx[q], qa.ty[q], qa.tz[q], qa.stamp[q], lx[s], ly[s], lz[s], ls[s], r2, min_gap, base + s);
+    });
 }
 
 // Pass 2.  One block per query: the K smallest of the n_tiles x K keys pass 1 left, by K rounds of "the smallest key above the previous one" (keys are distinct).
-__global__ __launch_bounds__(kSearchBlock) void k_closure_search_merge(const unsigned long long* __restrict__ part, int n_tiles, int K,
+__global__ __launch_bounds__(kSelectBlock) void k_closure_search_merge(const unsigned long long* __restrict__ part, int n_tiles, int K,
                                                                        int32_t* __restrict__ cand, unsigned long long* __restrict__ keys) {
     __shared__ uint64_t wmin[2][4];
     const int q = blockIdx.x;
@@ -88,30 +50,28 @@ __global__ __launch_bounds__(kSearchBlock) void k_closure_search_merge(const uns
     uint64_t prev = 0; bool have_prev = false;
     uint64_t reg[kMergeRegs];                                          // the first 256 x kMergeRegs keys stay in registers: read once, not once per round
 #pragma unroll
-    for (int i = 0; i < kMergeRegs; i++) { const int j = threadIdx.x + kSearchBlock * i; reg[i] = j < n ? in[j] : kNoKey; }
+    for (int i = 0; i < kMergeRegs; i++) { const int j = threadIdx.x + kSelectBlock * i; reg[i] = j < n ? in[j] : kNoKey; }
     int k = 0;
     for (; k < K; k++) {
         uint64_t m = kNoKey;
 #pragma unroll
         for (int i = 0; i < kMergeRegs; i++) { const uint64_t v = reg[i]; if ((!have_prev || v > prev) && v < m) m = v; }
-        for (int i = threadIdx.x + kSearchBlock * kMergeRegs; i < n; i += kSearchBlock) { const uint64_t v = in[i]; if ((!have_prev || v > prev) && v < m) m = v; }
+        for (int i = threadIdx.x + kSelectBlock * kMergeRegs; i < n; i += kSelectBlock) { const uint64_t v = in[i]; if ((!have_prev || v > prev) && v < m) m = v; }
         const uint64_t b = block_min_u64(m, wmin, k);
         if (b == kNoKey) break;
         if (threadIdx.x == 0) { cand[q * K + k] = icet_closure_rule::key_slot(b); keys[q * K + k] = b; }
         prev = b; have_prev = true;
     }
-    for (int j = k + threadIdx.x; j < K; j += kSearchBlock) { cand[q * K + j] = -1; keys[q * K + j] = kNoKey; }
+    for (int j = k + threadIdx.x; j < K; j += kSelectBlock) { cand[q * K + j] = -1; keys[q * K + j] = kNoKey; }
 }
 
 // One thread per (query, candidate).  x0_base (may be null): Q x K x 6, zeros for a missing candidate.  With n_starts > 0 the registrations
-// r = (q K + k) S + s of the indexed call behind it: x0[r] = fl(base + off[s]), kf_of[r] = the slot -- `any_slot`, an occupied one, for a missing
-// candidate --, rows[r] = "all of the scan" or 0 (a missing candidate registers a scan of no rows: no point pass, a score without voxels), members / offs:
-// the groups of k_select_best (group = query).
+// r = (q K + k) S + s of the indexed call behind it (write_registrations).
 __global__ __launch_bounds__(64) void k_closure_resolve(PoseTable tab, ClosurePoseArgs pa, int n_queries, int K, int n_starts, int any_slot,
                                                         const int32_t* __restrict__ cand, float* __restrict__ x0_base, float* __restrict__ x0,
                                                         int32_t* __restrict__ kf_of, int32_t* __restrict__ rows, int32_t* __restrict__ members, int32_t* __restrict__ offs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (offs && i <= n_queries) offs[i] = i * K * n_starts;
+    write_group_offset(i, n_queries, K, n_starts, offs);
     if (i >= n_queries * K) return;
     const int q = i / K;
     const int slot = cand[i];
@@ -123,13 +83,7 @@ __global__ __launch_bounds__(64) void k_closure_resolve(PoseTable tab, ClosurePo
         icet_closure_rule::start_pose(pa.R[q], pa.t[q], Rj, tj, b);
     }
     if (x0_base) for (int c = 0; c < 6; c++) x0_base[(size_t)i * 6 + c] = b[c];
-    for (int s = 0; s < n_starts; s++) {
-        const int r = i * n_starts + s;
-        for (int c = 0; c < 6; c++) x0[(size_t)r * 6 + c] = slot >= 0 ? b[c] + pa.off[s][c] : 0.f;
-        kf_of[r] = slot >= 0 ? slot : any_slot;
-        rows[r] = slot >= 0 ? INT32_MAX : 0;
-        members[r] = r;
-    }
+    write_registrations(i, slot, any_slot, b, pa.off, n_starts, x0, kf_of, rows, members);
 }
 
 __global__ void k_closure_apply(int32_t* __restrict__ dst, const int32_t* __restrict__ src, int n) {
@@ -137,10 +91,11 @@ __global__ void k_closure_apply(int32_t* __restrict__ dst, const int32_t* __rest
     if (i < n) dst[i] = src[i];
 }
 
-// One thread per query.  best == nullptr: no registration ran (a store without an occupied slot): every record is "none".
+// One thread per query.  best == nullptr: no registration ran (a store without an occupied slot): every record is "none".  shift_of (null by pose): the
+// candidates' shifts of an appearance query, whose record carries the appearance distance in d2 and the winner's shift in reserved0.
 __global__ __launch_bounds__(64) void k_closure_record(PoseTable tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels,
                                                        const int32_t* __restrict__ best, const int32_t* __restrict__ cand, const unsigned long long* __restrict__ keys,
-                                                       const float* __restrict__ x0, const float* __restrict__ out, const icet_score* __restrict__ score,
+                                                       const int32_t* __restrict__ shift_of, const float* __restrict__ x0, const float* __restrict__ out, const icet_score* __restrict__ score,
                                                        icet_closure* __restrict__ rec) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_queries) return;
@@ -154,6 +109,7 @@ __global__ __launch_bounds__(64) void k_closure_record(PoseTable tab, int n_quer
         const int i = r / n_starts;                                   // q K + k
         const int slot = cand[i];
         c.slot = slot; c.stamp = tab.stamp[slot]; c.d2 = icet_closure_rule::key_d2(keys[i]);
+        if (shift_of) c.reserved0 = shift_of[i];
         for (int k = 0; k < 6; k++) c.x0[k] = x0[(size_t)r * 6 + k];
         for (int k = 0; k < 48; k++) c.out[k] = out[(size_t)r * 48 + k];
         c.score = score[r];
@@ -189,16 +145,18 @@ __global__ void k_closure_clear_pose(PoseTable tab, StoreParkSlots slots, int n)
 
 }  // namespace
 
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
-
 int closure_tiles(int32_t cap) { return (int)(((int64_t)cap + kClosureTile - 1) / kClosureTile); }
 
 hipError_t launch_closure_search(const PoseTable& tab, const ClosureSearchArgs& qa, int n_queries, int K, float radius, int64_t min_gap,
                                  unsigned long long* d_part, int32_t* d_cand, unsigned long long* d_keys, hipStream_t st) {
     const int tiles = closure_tiles(tab.cap);
-    k_closure_search_tiles<<<tiles, kSearchBlock, 0, st>>>(tab, qa, n_queries, K, icet_closure_rule::radius2(radius), min_gap, d_part);
+    k_closure_search_tiles<<<tiles, kSelectBlock, 0, st>>>(tab, qa, n_queries, K, icet_closure_rule::radius2(radius), min_gap, d_part);
     ICET_LAUNCH_CHECK();
-    k_closure_search_merge<<<n_queries, kSearchBlock, 0, st>>>(d_part, tiles, K, d_cand, d_keys);
+    return launch_closure_merge(d_part, tiles, n_queries, K, d_cand, d_keys, st);
+}
+
+hipError_t launch_closure_merge(const unsigned long long* d_part, int tiles, int n_queries, int K, int32_t* d_cand, unsigned long long* d_keys, hipStream_t st) {
+    k_closure_search_merge<<<n_queries, kSelectBlock, 0, st>>>(d_part, tiles, K, d_cand, d_keys);
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -219,9 +177,10 @@ hipError_t launch_closure_apply(int32_t* dst, const int32_t* src, int n, hipStre
 }
 
 hipError_t launch_closure_record(const PoseTable& tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels, const int32_t* d_best,
-                                 const int32_t* d_cand, const unsigned long long* d_keys, const float* d_x0, const float* d_out, const ::icet_score* d_score,
-                                 ::icet_closure* d_closure, hipStream_t st) {
-    k_closure_record<<<(n_queries + 63) / 64, 64, 0, st>>>(tab, n_queries, K, n_starts, max_chi2_per_voxel, min_voxels, d_best, d_cand, d_keys, d_x0, d_out, d_score, d_closure);
+                                 const int32_t* d_cand, const unsigned long long* d_keys, const int32_t* d_shift_of, const float* d_x0, const float* d_out,
+                                 const ::icet_score* d_score, ::icet_closure* d_closure, hipStream_t st) {
+    k_closure_record<<<(n_queries + 63) / 64, 64, 0, st>>>(tab, n_queries, K, n_starts, max_chi2_per_voxel, min_voxels, d_best, d_cand, d_keys, d_shift_of, d_x0, d_out, d_score,
+                                                          d_closure);
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -1,6 +1,6 @@
 // icet_amd/csrc/icet_coarse.h -- the RULE of the keyframe store's coarse alignment (include/icet_hip.h icet_keyframe_store_coarse_align_device; DESIGN.md
 // section 18), in one place: the cell and the height code of a point, which cells span, the transform of a yaw hypothesis, the score of a shift, the order
-// of the winners and the start pose of one.  HIP-free C++: the kernels of icet_coarse.hip, the host code of icet_capi.hip and the CPU test
+// of the winners and the start pose of one.  HIP-free C++: the kernels of icet_coarse.hip, the host code of icet_store.hip and the CPU test
 // (tests/cpp/test_coarse.cpp) compile this text.
 //
 // GRID: G rows (ix) of G / 32 words, bit iy & 31 of word iy >> 5; a bird's-eye bit per cell that holds vertical structure.  Everything between the cells and

@@ -15,6 +15,7 @@
 #include "../../include/icet_hip.h"
 #include "icet_internal.h"
 #include "icet_coarse.h"
+#include "icet_closure_device.h"
 
 namespace icet {
 namespace {
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(64) void k_coarse_resolve(rule::Consts c, AppOffset
                                                        float* __restrict__ x0, int32_t* __restrict__ kf_of, int32_t* __restrict__ rows, int32_t* __restrict__ members,
                                                        int32_t* __restrict__ offs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (offs && i <= n_queries) offs[i] = i * K * n_starts;
+    write_group_offset(i, n_queries, K, n_starts, offs);
     if (i >= n_queries * K) return;
     const int slot = cand[i];
     float X[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -215,13 +216,7 @@ __global__ __launch_bounds__(64) void k_coarse_resolve(rule::Consts c, AppOffset
     }
     if (x0_out) for (int k = 0; k < 6; k++) x0_out[(size_t)i * 6 + k] = X[k];
     if (match) match[i] = m;
-    for (int s = 0; s < n_starts; s++) {
-        const int r = i * n_starts + s;
-        for (int k = 0; k < 6; k++) x0[(size_t)r * 6 + k] = slot >= 0 ? X[k] + off.off[s][k] : 0.f;
-        kf_of[r] = slot >= 0 ? slot : any_slot;
-        rows[r] = slot >= 0 ? INT32_MAX : 0;
-        members[r] = r;
-    }
+    write_registrations(i, slot, any_slot, X, off.off, n_starts, x0, kf_of, rows, members);
 }
 
 __global__ __launch_bounds__(64) void k_coarse_record(int n_queries, int n_starts, const icet_coarse_match* __restrict__ match, icet_closure* __restrict__ rec) {
@@ -235,8 +230,6 @@ __global__ __launch_bounds__(64) void k_coarse_record(int n_queries, int n_start
 }
 
 }  // namespace
-
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 static size_t corr_lds(const rule::Consts& c) { return sizeof(uint32_t) * ((size_t)c.G * c.W + (size_t)c.G * (c.W + 3)); }
 

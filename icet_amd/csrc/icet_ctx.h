@@ -1,0 +1,175 @@
+// icet_amd/csrc/icet_ctx.h -- what the two host translation units share: the context (icet_capi.hip owns it), the keyframe store that borrows one (icet_store.hip
+// owns it; the indexed registrations read its tables), the argument checks, and the indexed registrations both run.
+#pragma once
+#include "../../include/icet_hip.h"
+#include "icet_internal.h"
+#include "icet_appearance.h"
+#include "icet_coarse.h"
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+struct icet_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    icet::Workspace w;
+    icet::Tuning tune;                    // icet_set_option
+    int32_t kf_pairs = 0; icet_params kf_params{};      // a keyframe parked by icet_keyframe_device (0 pairs = none)
+    int max_lds = 160 * 1024;       // hipDeviceAttributeMaxSharedMemoryPerBlock of the device
+    int lds_rank_ok = 0;            // this device passed lds_rank_selftest (icet_create)
+    std::string err;
+    // host staging (pinned) for descriptors and results
+    icet::PairDesc* h_desc = nullptr; int32_t* h_seg = nullptr; int32_t h_cap_pairs = 0;
+    bool desc_kf_valid = false, desc_reg_valid = false;   // the pinned descriptors hold what the last icet_keyframe_device_n / icet_register_device_n call wrote (any other writer, and a re-allocation, clears both)
+    icet::PairDesc* h_desc_rt = nullptr; int32_t h_cap_rt = 0;       // ICET_FLAG_ROUNDTRIP_SCAN2: descriptors of the round-tripped copy of scan 2
+    icet::PairDesc* h_desc_reg = nullptr; int32_t* h_kf_of = nullptr;  // staging of an indexed call (icet_register_indexed_device), w.cap_regs (+ 1): apart from h_desc, whose scan-1 halves the same_desc shortcut keeps
+    int64_t ws_gen = 0;                                          // counts re-allocations of workspace buffers (part of the indexed call's graph key)
+    // device staging for host-pointer entry points
+    float* d_stage1 = nullptr; float* d_stage2 = nullptr; int64_t cap_stage1 = 0, cap_stage2 = 0;
+    float* d_out = nullptr; float* d_x0 = nullptr; int32_t cap_out_pairs = 0;
+    float* h_out = nullptr;
+    // aux (single pair): every side table of a solve lives in ONE device block (`d_pack`, words of 4 bytes, layout aux_layout()) behind the
+    // 48 result floats, so that results and side tables come back in one DMA into the pinned `h_pack`
+    icet::AuxDev aux_dev{}; int aux_V = 0, aux_runlen = 0;
+    uint32_t* d_pack = nullptr; uint32_t* h_pack = nullptr; size_t cap_pack = 0;
+    float* h_pts2 = nullptr; float* d_pts2 = nullptr; size_t cap_pts2 = 0;   // `points2` (scan 2 under the last iteration's transform): device buffer + pinned host copy
+    float* h_x0 = nullptr;                                       // pinned, 6 x cap_out_pairs
+    icet_score* d_score = nullptr; icet_score* h_score = nullptr; int32_t cap_score = 0;     // scores of the host-pointer entry points (device + pinned)
+    int32_t* d_sel = nullptr; int32_t* h_sel = nullptr; int64_t cap_sel = 0;                // icet_select_best_device: the groups' members | offsets (device + pinned staging)
+    hipEvent_t ev_sel = nullptr; bool sel_in_flight = false;                                 // the copy out of h_sel
+    float* d_sph1 = nullptr; int32_t* d_idx1 = nullptr; size_t cap_side1 = 0;      // points1Spherical / pointIndices1 on request (icet_sidetables.hip)
+    float* d_sph2 = nullptr; int32_t* d_vox2 = nullptr; size_t cap_side2 = 0;      // points2Spherical / the rows' voxels on request
+    // host-pointer entry points: scan 2 is uploaded on a stream of its own, beside the keyframe build of scan 1
+    hipStream_t st_copy = nullptr; hipEvent_t ev_s2 = nullptr;
+    hipEvent_t ev_kf = nullptr, ev_kfd = nullptr, ev_prev = nullptr, ev_pts2 = nullptr;   // keyframe built / its tables on the host / transform of the last iteration known / points2 on the host
+    // icet_solve_begin .. icet_solve_end
+    struct Pending { bool active = false; float* x_out = nullptr; float* ps_out = nullptr; float* cov_out = nullptr; icet_aux aux{}; bool has_aux = false;
+                     int V = 0, rl = 0; int64_t n2 = 0; bool kf_tables = false, kf_done = false, pts2 = false, pts2_dev = false, tail_ints = false, side1 = false, side2 = false; int64_t n1 = 0;
+                     const float* scan2 = nullptr; int64_t ld2 = 0; } pend;
+    // timing
+    hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
+    std::vector<hipEvent_t> ev_acc;
+    float last_ms[4] = {0, 0, 0, 0};
+    bool timing_valid = false;
+    int last_iters = 0;
+    // Large device batches are cut into contiguous parts, each solved by a helper context on its own stream, so that
+    // the keyframe build of one part (latency / LDS bound) overlaps the Gauss-Newton loop of another (VALU bound).
+    std::vector<icet_ctx*> helpers;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_stage = nullptr; int stage_at = 0;            // see LaunchCfg::stage_event
+    hipEvent_t ev_desc = nullptr; bool desc_in_flight = false;   // completion of the last copy out of the pinned descriptor staging
+    // Small device batches whose launch geometry repeats call after call are replayed from a captured hipGraph (option "graph"): the ~33
+    // launches of a single-pair solve then cost one hipGraphLaunch on the host, and the command processor runs them back to back.
+    struct GraphKey { int64_t v[47]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key + the keyframe source (graph_key_of)
+    struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false; };
+    bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
+    GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
+    GraphSlot g_scored, g_score;                               // indexed registrations + score (icet_register_indexed_scored_device), the score of given poses (icet_score_indexed_device)
+    hipEvent_t ev_graph = nullptr; bool graph_in_flight = false;
+    // A caller inside this library (the sequential nodes, icet_nodes.hip) can put work of its own at the head of the NEXT icet_register_device_n call's launch
+    // sequence -- enqueued on the context's stream right before the loop's first kernel, captured into the same graph: the range filter and the loop of a frame
+    // are then ONE hipGraphLaunch (round 6: the loop's graph used to start 30-40 us after the filter's last kernel).  `prologue_key` names what the hook's
+    // launches depend on (buffers, grid): it is part of the graph key.  Cleared by the caller after the call (icet_ctx_set_prologue).
+    // A ragged throughput batch is laid out XCD-balanced (solve_device_part): slot s of the internal tables holds the caller's pair h_seg[n_pairs + 1 + s]
+    bool perm_active = false; int32_t perm_pairs = 0;
+    hipError_t (*prologue)(void*, hipStream_t) = nullptr; void* prologue_user = nullptr; int64_t prologue_key = 0;
+    // ... and have the LAST solve of the next icet_register_device_n call store 1 into a word of (coherent) pinned host memory once the results are written: the caller
+    // watches that word instead of synchronising the stream (icet_ctx_set_done_flag; part of the graph key)
+    int32_t* done_flag = nullptr;
+    // icet_sync after ONE small device-resident solve (icet_solve_batch_device, replayed graph) watches a word of its own the same way: h_sync_word, raised by that solve's
+    // last kernel.  armed_calls counts such solves since the last icet_sync; anything else enqueued on the context (or a second solve, whose reset of the word races with the
+    // first one's store) makes it 2 or more and icet_sync synchronises the stream as before.
+    int32_t* h_sync_word = nullptr; int armed_calls = 2;
+};
+
+// A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
+// keyframe side (row stride V; (V + 1) & ~1 for slot_of_voxel), on the borrowed context's device.  A put builds on the context and parks into rows of its own
+// (k_keyframe_store_park); the indexed calls read a row the way they read a parked keyframe.  id (never reused) and gen (bumped when the tables move) name
+// the tables in the graph key of an indexed call.
+struct icet_keyframe_store {
+    icet_ctx* ctx = nullptr;
+    icet_params shape{};                       // bins_phi, bins_theta, n, thresh, buff, flags & (TRUE_SORT | HALF_GAP_BOUNDS); runlen 0
+    int V = 0; int32_t capacity = 0;
+    icet::SlotHot* hotS = nullptr; icet::SlotFit* fitS = nullptr; int16_t* slot_of_voxel = nullptr; int32_t* n_slots = nullptr;
+    std::vector<uint8_t> occupied;             // capacity: the rows a put has filled
+    int64_t id = 0, gen = 0;
+    std::string err;
+    // the pose table: ONE allocation of capacity x 56 bytes at pose_stamp -- stamp[capacity] | tx | ty | tz | r0 .. r8 --, 0xFF bytes
+    // (NaN, stamp -1) where a slot has no pose; set_pose stages through h_pose (pinned), which its kernel reads when it runs (ev_pose: it has)
+    int64_t* pose_stamp = nullptr;
+    icet::PoseTable pose_table() const { return icet::PoseTable{pose_stamp, reinterpret_cast<float*>(pose_stamp + capacity), capacity}; }
+    icet::PoseUpload* h_pose = nullptr; int32_t cap_h_pose = 0; hipEvent_t ev_pose = nullptr; bool pose_in_flight = false;
+    // buffers of a query (icet_keyframe_store_close_device), grown on demand: the search's per-tile lists; per (query, candidate); per registration; per query
+    unsigned long long* q_part = nullptr; size_t cap_part = 0;
+    unsigned long long* q_keys = nullptr; int32_t* q_cand = nullptr; int32_t cap_qk = 0;
+    float* q_x0 = nullptr; float* q_out = nullptr; icet_score* q_score = nullptr; int32_t* q_kf_of = nullptr; int32_t* q_rows = nullptr; int32_t* q_members = nullptr; int32_t cap_qr = 0;
+    int32_t* q_offs = nullptr; int32_t* q_best = nullptr;       // kClosureMaxQueries + 1, kClosureMaxQueries
+    // place recognition by appearance: null until icet_keyframe_store_enable_appearance
+    struct Appearance {
+        icet_appearance_rule::Consts k{}; int Rp = 0;             // Rp: words per column, ceil(rings / 4)
+        uint32_t* desc = nullptr; float* w = nullptr; int32_t* has = nullptr;      // the table: capacity rows (AppTable)
+        std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a descriptor
+        uint32_t* scratch = nullptr;                              // kAppBatch x rings x sectors words, zero between calls
+        uint32_t* qdesc = nullptr; float* qw = nullptr; int32_t* qhas = nullptr;   // the descriptors of a call's queries: a table of kAppBatch rows
+        unsigned long long* keys_all = nullptr; uint16_t* shift_all = nullptr; size_t cap_all = 0;      // n_queries x capacity, grown on demand
+        int32_t* shift_of = nullptr;                              // kClosureMaxQueries x kClosureMaxCandidates: the candidates' shifts, for the record
+    };
+    Appearance* app = nullptr;
+    icet::AppTable app_table() const { return icet::AppTable{app->desc, app->w, app->has, capacity, app->k.A, app->Rp}; }
+    // coarse alignment: null until icet_keyframe_store_enable_coarse
+    struct Coarse {
+        icet_coarse_rule::Consts k{};
+        uint32_t* grid = nullptr; int32_t* has = nullptr;         // the table: capacity rows of G x G / 32 words (CoarseTable)
+        std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a grid
+        uint32_t* scratch = nullptr;                              // kCoarseBatch x 2 x G x G words, zero between calls
+        uint32_t* qgrid = nullptr;                                // the own grids of a call's queries: kAppBatch rows
+        // per (query, candidate) of the largest call: base starts, coarse starts, matches, keys, slot bit counts; per hypothesis: transforms and live bit counts
+        float* base = nullptr; icet_coarse_match* match = nullptr; unsigned long long* keys = nullptr; int32_t* key_bits = nullptr;
+        icet::CoarseHyp* hyp = nullptr; int32_t* live_bits = nullptr;
+        size_t row_words() const { return (size_t)k.G * (size_t)k.W; }
+    };
+    Coarse* coarse = nullptr;
+    icet::CoarseTable coarse_table() const { return icet::CoarseTable{coarse->grid, coarse->has, capacity}; }
+};
+
+namespace icet {
+
+#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
+
+template <typename T> static hipError_t dev_realloc(T*& p, size_t count) {
+    if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
+    if (count == 0) return hipSuccess;
+    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
+}
+
+static inline bool params_ok(const icet_params* p) {
+    if (!p) return false;
+    if (p->runlen < 0 || p->runlen > 4096) return false;
+    if (p->bins_phi <= 0 || p->bins_theta <= 0 || p->n < 1) return false;
+    return true;
+}
+
+static inline bool dev_scan_ok(const icet_dev_scan& a) { return !(a.n < 0 || a.ld < a.n || (a.n > 0 && !a.ptr) || a.ld >= ((int64_t)1 << 30)); }
+
+// What makes a keyframe: two calls with the same values here read and write the same tables.
+static inline bool same_keyframe_shape(const icet_params& a, const icet_params& b) {
+    return a.bins_phi == b.bins_phi && a.bins_theta == b.bins_theta && a.n == b.n && a.thresh == b.thresh && a.buff == b.buff &&
+           !((a.flags ^ b.flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS));
+}
+
+// The indexed registrations of icet_register_indexed_device (mode kIdxRegister), the same followed by the score (kIdxScored: d_score), or the score of the poses
+// d_x0 alone (kIdxScoreOnly: no iteration, d_out unused).  src: the keyframe tables -- nullptr the context's parked keyframe (kf_index: parked keyframes), or a
+// keyframe store (kf_index: its occupied slots; icet_keyframe_store_register_device and its kin).  dev: keyframe index and row count of every registration as
+// kernels in front of the call left them on the device (a closure query; never captured into a graph).
+enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2, kIdxDump = 3 };      // kIdxDump (icet_debug_point_sums_device): kIdxScoreOnly with the raw per-voxel sums (d_dump) in place of the score
+struct IndexedDev { const int32_t* kf_of; const int32_t* rows; };
+__attribute__((visibility("hidden")))
+icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
+                             icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr);
+
+}  // namespace icet

@@ -239,6 +239,9 @@ struct LaunchCfg {
 constexpr float kRejectMovingThresh = 0.3f;        // python/ICET_spherical.py:38  RM_thresh
 constexpr int kRejectMovingStartIter = 4;          // python/ICET_spherical.py:36  start_RM_iter
 
+// behind a kernel launch in a function that returns hipError_t
+#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
+
 // icet_keyframe.hip
 hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev* aux, hipStream_t st, const int32_t* d_n1 = nullptr);   // d_n1: scan-1 row counts known to the device only (the descriptors hold upper bounds)
 // icet_solve.hip
@@ -292,15 +295,18 @@ int closure_tiles(int32_t cap);
 // d_part: n_queries x closure_tiles(cap) x K keys; d_cand: n_queries x K slots (-1: none); d_keys: their keys
 hipError_t launch_closure_search(const PoseTable& tab, const ClosureSearchArgs& qa, int n_queries, int K, float radius, int64_t min_gap,
                                  unsigned long long* d_part, int32_t* d_cand, unsigned long long* d_keys, hipStream_t st);
+// the search's second pass alone: the K smallest of each query's tiles x K keys in d_part (the appearance search ends with it as well)
+__attribute__((visibility("hidden"))) hipError_t launch_closure_merge(const unsigned long long* d_part, int tiles, int n_queries, int K, int32_t* d_cand, unsigned long long* d_keys, hipStream_t st);
 hipError_t launch_closure_resolve(const PoseTable& tab, const ClosurePoseArgs& pa, int n_queries, int K, int n_starts, int any_slot, const int32_t* d_cand,
                                   float* d_x0_base, float* d_x0, int32_t* d_kf_of, int32_t* d_rows, int32_t* d_members, int32_t* d_offs, hipStream_t st);
 hipError_t launch_closure_apply(int32_t* dst, const int32_t* src, int n, hipStream_t st);
 }  // namespace icet
 struct icet_closure;                       // include/icet_hip.h
 namespace icet {
+// d_shift_of (null by pose): the candidates' shifts of an appearance query (launch_app_resolve), the winner's into the record's reserved0
 hipError_t launch_closure_record(const PoseTable& tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels, const int32_t* d_best,
-                                 const int32_t* d_cand, const unsigned long long* d_keys, const float* d_x0, const float* d_out, const ::icet_score* d_score,
-                                 ::icet_closure* d_closure, hipStream_t st);
+                                 const int32_t* d_cand, const unsigned long long* d_keys, const int32_t* d_shift_of, const float* d_x0, const float* d_out,
+                                 const ::icet_score* d_score, ::icet_closure* d_closure, hipStream_t st);
 hipError_t launch_closure_set_pose(const PoseTable& tab, const PoseUpload* h_up, int n, hipStream_t st);
 hipError_t launch_closure_clear_pose(const PoseTable& tab, const StoreParkSlots& slots, int n, hipStream_t st);
 }  // namespace icet
@@ -329,9 +335,6 @@ hipError_t launch_app_search(const AppTable& tab, const PoseTable& poses, const 
 hipError_t launch_app_resolve(int cap, int A, const AppOffsets& off, int n_queries, int K, int n_starts, int any_slot, const int32_t* d_cand,
                               const unsigned long long* d_keys, const uint16_t* d_shift_all, float* d_dist, int32_t* d_shift, float* d_x0_base, int32_t* d_shift_of,
                               float* d_x0, int32_t* d_kf_of, int32_t* d_rows, int32_t* d_members, int32_t* d_offs, hipStream_t st);
-hipError_t launch_app_record(const PoseTable& tab, int n_queries, int K, int n_starts, float max_chi2_per_voxel, int min_voxels, const int32_t* d_best,
-                             const int32_t* d_cand, const unsigned long long* d_keys, const int32_t* d_shift_of, const float* d_x0, const float* d_out,
-                             const ::icet_score* d_score, ::icet_closure* d_closure, hipStream_t st);
 }  // namespace icet
 namespace icet_coarse_rule { struct Consts; }          // icet_coarse.h
 struct icet_coarse_match;                              // include/icet_hip.h

@@ -1297,7 +1297,6 @@ __global__ __launch_bounds__(kBlock) void k_lds_order_selftest(int rounds, int32
 
 }  // namespace
 
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t lds_rank_selftest(int32_t* d_scratch, hipStream_t st, int* ok) {
     *ok = 0;

@@ -212,7 +212,6 @@ __global__ __launch_bounds__(64) void k_select_best(const int32_t* __restrict__ 
 
 }  // namespace
 
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t launch_gn_score(const Workspace& w, const LaunchCfg& c, int iter, icet_score* d_score, hipStream_t st) {
     const NearOverflow over{w.desc, w.slot_of_voxel, w.hotS, w.thr, w.near_over, w.near_over_count, c.T, c.P, c.rt2};

@@ -57,7 +57,6 @@ __global__ __launch_bounds__(kBlock) void k_side_scan2(const PairDesc* __restric
 
 }  // namespace
 
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t launch_side_scan1(const Workspace& w, const LaunchCfg& c, float* sph, int32_t* index, hipStream_t st) {
     if (c.max_n1 <= 0) return hipSuccess;

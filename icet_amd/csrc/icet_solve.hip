@@ -115,7 +115,6 @@ hipError_t launch_gn_tail_debug(const float* d_H, const float* d_g, float* d_out
     return hipGetLastError();
 }
 
-#define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 // Row counts that only the device knows (a sequential caller's range filter, include/icet_nodes.h): the descriptors were uploaded with upper
 // bounds -- the launch geometry is sized from those -- and take the actual counts here; every kernel reads n1 / n2 from the descriptor.
