@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
                     "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
                     "icet_keyframe_store_close_coarse_device",
+                    "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
@@ -81,6 +82,12 @@ class CoarseParams(C.Structure):
     _fields_ = [("cells", C.c_int32), ("cell", C.c_float), ("z_lo", C.c_float), ("z_hi", C.c_float), ("min_span", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
+class SnapshotInfo(C.Structure):
+    """icet_snapshot_info (include/icet_hip.h), 120 bytes: what a snapshot file of a keyframe store says about itself."""
+    _fields_ = [("shape", Params), ("V", C.c_int32), ("entries", C.c_int32), ("highest_slot", C.c_int32), ("has_appearance", C.c_int32), ("has_coarse", C.c_int32),
+                ("appearance", AppearanceParams), ("coarse", CoarseParams), ("file_bytes", C.c_int64)]
+
+
 class CoarseSearch(C.Structure):
     """icet_coarse_search (include/icet_hip.h), 32 bytes."""
     _fields_ = [("window", C.c_int32), ("n_yaw", C.c_int32), ("yaw_step", C.c_float), ("half_turn", C.c_int32), ("min_score", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -94,7 +101,7 @@ class CoarseMatch(C.Structure):
 
 # icet_coarse_match as a NumPy dtype (a device buffer of records comes back as bytes)
 COARSE_MATCH_DTYPE = np.dtype([("score", "<i4"), ("a", "<i4"), ("b", "<i4"), ("h", "<i4"), ("live_bits", "<i4"), ("key_bits", "<i4"), ("found", "<i4"), ("reserved", "<i4")])
-assert COARSE_MATCH_DTYPE.itemsize == 32 == C.sizeof(CoarseMatch) == C.sizeof(CoarseSearch) == C.sizeof(CoarseParams)
+assert COARSE_MATCH_DTYPE.itemsize == 32 == C.sizeof(CoarseMatch) == C.sizeof(CoarseSearch) == C.sizeof(CoarseParams) and C.sizeof(SnapshotInfo) == 120
 
 
 class Score(C.Structure):
@@ -235,6 +242,10 @@ def load_library():
                                                           C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_close_coarse_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.POINTER(ClosureQuery),
                                                           C.POINTER(CoarseSearch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_keyframe_store_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p]
+    L.icet_keyframe_store_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.icet_keyframe_store_snapshot_info.argtypes = [C.c_char_p, C.POINTER(SnapshotInfo)]
+    L.icet_keyframe_store_snapshot_slots.argtypes = [C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     L.icet_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
     L.icet_multi_destroy.argtypes = [C.c_void_p]
     L.icet_multi_last_error.argtypes = [C.c_void_p]; L.icet_multi_last_error.restype = C.c_char_p
@@ -863,6 +874,55 @@ class KeyframeStore:
         call([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], rec.data_ptr())
         self._ctx.sync()
         return _closure_dicts(np.frombuffer(rec.cpu().numpy().tobytes(), CLOSURE_DTYPE), by_appearance, coarse)
+
+    # ---- snapshots (include/icet_hip.h "snapshots") ----
+
+    def save(self, path, slots=None):
+        """The occupied slots (or the distinct occupied ``slots``) with their poses, stamps, descriptors and grids into the file ``path``
+        (icet_keyframe_store_save).  In stream order behind what was enqueued; returns once the file is closed.  A failed save leaves nothing at ``path``."""
+        if slots is None:
+            self._check(load_library().icet_keyframe_store_save(self._h, os.fsencode(path), 0, None))
+            return
+        sl = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+        self._check(load_library().icet_keyframe_store_save(self._h, os.fsencode(path), sl.shape[0], sl.ctypes.data))
+
+    def load(self, path, slot_offset=0):
+        """The slots of the file ``path`` into slots ``slot + slot_offset`` of this store, bit for bit (icet_keyframe_store_load): each replaces everything its
+        target held, every other slot keeps its bytes.  The file is validated and held against the store first; a refusal touches nothing."""
+        self._check(load_library().icet_keyframe_store_load(self._h, os.fsencode(path), int(slot_offset)))
+
+    @staticmethod
+    def snapshot_info(path):
+        """What the file ``path`` holds, read and validated on the host: dict(num_bins_phi, num_bins_theta, n, thresh, buff, flags, V, entries, highest_slot,
+        appearance, coarse, file_bytes, slots, stamps) -- appearance / coarse: the keyword arguments of enable_appearance / enable_coarse, or None."""
+        L = load_library()
+        info = SnapshotInfo()
+        st = L.icet_keyframe_store_snapshot_info(os.fsencode(path), C.byref(info))
+        if st != ICET_OK:
+            raise IcetError(st, "%s cannot be read or is not a valid keyframe-store snapshot" % path)
+        slots = np.zeros(max(info.entries, 1), np.int32); stamps = np.zeros(max(info.entries, 1), np.int64); n = C.c_int32(0)
+        st = L.icet_keyframe_store_snapshot_slots(os.fsencode(path), info.entries, slots.ctypes.data, stamps.ctypes.data, C.byref(n))
+        if st != ICET_OK or n.value != info.entries:
+            raise IcetError(ICET_ERR_BAD_ARG, "%s changed while it was read" % path)
+        a, c, p = info.appearance, info.coarse, info.shape
+        return dict(num_bins_phi=p.bins_phi, num_bins_theta=p.bins_theta, n=p.n, thresh=p.thresh, buff=p.buff, flags=p.flags, V=info.V, entries=info.entries,
+                    highest_slot=info.highest_slot, file_bytes=info.file_bytes, slots=slots[:info.entries], stamps=stamps[:info.entries],
+                    appearance=dict(sectors=a.sectors, rings=a.rings, rho_max=a.rho_max, z_lo=a.z_lo, z_hi=a.z_hi) if info.has_appearance else None,
+                    coarse=dict(cells=c.cells, cell=c.cell, z_lo=c.z_lo, z_hi=c.z_hi, min_span=c.min_span) if info.has_coarse else None)
+
+    @classmethod
+    def from_file(cls, ctx, path, capacity=None):
+        """A store of the file's shape on ``ctx`` -- ``capacity`` slots, by default just enough --, appearance and coarse alignment enabled with the saved
+        parameters where the file has them, and the file loaded."""
+        info = cls.snapshot_info(path)
+        need = info["highest_slot"] + 1
+        st = cls(ctx, max(1, need) if capacity is None else int(capacity), info["num_bins_phi"], info["num_bins_theta"], info["n"], info["thresh"], info["buff"], info["flags"])
+        if info["appearance"] is not None:
+            st.enable_appearance(**info["appearance"])
+        if info["coarse"] is not None:
+            st.enable_coarse(**info["coarse"])
+        st.load(path)
+        return st
 
     # ---- loop closure by appearance (include/icet_hip.h "loop closure by appearance"; DESIGN.md section 17) ----
 

@@ -83,6 +83,7 @@ struct icet_ctx {
     // last kernel.  armed_calls counts such solves since the last icet_sync; anything else enqueued on the context (or a second solve, whose reset of the word races with the
     // first one's store) makes it 2 or more and icet_sync synchronises the stream as before.
     int32_t* h_sync_word = nullptr; int armed_calls = 2;
+    int64_t snapshot_chunk_bytes = 0;                            // option "snapshot_chunk_bytes": payload bytes per chunk of a store's save / load (0: 64 MiB)
 };
 
 // A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
@@ -110,6 +111,7 @@ struct icet_keyframe_store {
     // place recognition by appearance: null until icet_keyframe_store_enable_appearance
     struct Appearance {
         icet_appearance_rule::Consts k{}; int Rp = 0;             // Rp: words per column, ceil(rings / 4)
+        icet_appearance_params params{};                          // as enable_appearance took them (a snapshot file names them)
         uint32_t* desc = nullptr; float* w = nullptr; int32_t* has = nullptr;      // the table: capacity rows (AppTable)
         std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a descriptor
         uint32_t* scratch = nullptr;                              // kAppBatch x rings x sectors words, zero between calls
@@ -122,6 +124,7 @@ struct icet_keyframe_store {
     // coarse alignment: null until icet_keyframe_store_enable_coarse
     struct Coarse {
         icet_coarse_rule::Consts k{};
+        icet_coarse_params params{};                              // as enable_coarse took them (a snapshot file names them)
         uint32_t* grid = nullptr; int32_t* has = nullptr;         // the table: capacity rows of G x G / 32 words (CoarseTable)
         std::vector<uint8_t> has_h;                               // capacity: the slots a put has given a grid
         uint32_t* scratch = nullptr;                              // kCoarseBatch x 2 x G x G words, zero between calls

@@ -79,6 +79,12 @@ struct FitMid {
 static_assert(sizeof(FitMid) == 64, "k_fit_scan1 stages this record as 16 words");
 
 static_assert(sizeof(SlotHot) == 48 && sizeof(SlotFit) == 80, "k_compact_slots copies these records as 12 + 20 words");
+// The layout of the two records as a snapshot file of a keyframe store keeps them (icet_snapshot.h): a file names this constant and is
+// refused by a library whose constant differs.
+constexpr uint32_t kSlotLayoutVersion = 1;
+static_assert(__builtin_offsetof(SlotHot, mu) == 24 && __builtin_offsetof(SlotHot, v) == 36 && __builtin_offsetof(SlotFit, s1n) == 12 && __builtin_offsetof(SlotFit, M) == 36 &&
+              __builtin_offsetof(SlotFit, n1) == 72 && __builtin_offsetof(SlotFit, v) == 76,
+              "a field of SlotHot or SlotFit moved: bump kSlotLayoutVersion (saved snapshots hold these records byte for byte) and the offsets icet_snapshot.h validates");
 
 // The KEEP LIST of the point pass (round 6).  H^T W H only ever sees scan-2 points that fall into the angular bin of an ACTIVE voxel
 // (raw count, src/icet.cpp:290,315) or inside its bounds (sums, :299-306); on lidar data 40-60 % of scan 2 lies in bins without a scan-1
@@ -281,6 +287,16 @@ constexpr int kStoreParkMax = 64;
 struct StoreParkSlots { int32_t slot[kStoreParkMax]; };
 hipError_t launch_keyframe_store_park(const Workspace& w, int V, int first, int count, const StoreParkSlots& dst,
                                       SlotHot* hot_dst, SlotFit* fit_dst, int16_t* sov_dst, int32_t* n_slots_dst, hipStream_t st);
+// icet_snapshot.hip: a store's slots to and from the payloads of a snapshot file (icet_keyframe_store_save / _load).  One SnapEntry per slot of
+// a chunk, in a device array the host uploads from pinned memory (a chunk may hold thousands): slot is the store's row, off the payload's place in the staging.
+struct SnapEntry { int32_t slot, n_slots; uint32_t flags, pad; int64_t stamp; uint32_t pose[12]; uint64_t off; uint64_t pad2[2]; };
+static_assert(sizeof(SnapEntry) == 96, "uploaded as an array");
+// The store's tables (null where the store lacks the feature: that part of a payload is skipped) and the sizes the payload layout needs: A, Rp, G are the FILE's.
+struct SnapTables { SlotHot* hot; SlotFit* fit; int16_t* sov; int32_t* n_slots; uint32_t* desc; float* w; int32_t* app_has; uint32_t* grid; int32_t* grid_has;
+                    int64_t* stamp; float* pose; int32_t cap, V, A, Rp, G; };
+// d_stage: 16-byte aligned.  d_sums: one word per entry, zero before the launch; each gets its payload's checksum (icet_snapshot::checksum).
+hipError_t launch_snapshot_pack(const SnapTables& t, const SnapEntry* d_entries, int n_entries, uint8_t* d_stage, unsigned long long* d_sums, hipStream_t st);
+hipError_t launch_snapshot_unpack(const SnapTables& t, const SnapEntry* d_entries, int n_entries, const uint8_t* d_stage, hipStream_t st);
 // icet_closure.hip: the store's pose table and the loop-closure query (icet_keyframe_store_close_device).  The queries' poses, stamps
 // and start offsets travel in the kernels' arguments (no copy command, nothing a later call could rewrite under a launch in flight).
 constexpr int kClosureMaxQueries = 64, kClosureMaxCandidates = 32, kClosureMaxStarts = 16;

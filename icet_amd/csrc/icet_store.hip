@@ -1,11 +1,12 @@
-// icet_amd/csrc/icet_store.hip -- the keyframe store of the C ABI (include/icet_hip.h icet_keyframe_store_*; DESIGN.md sections 15 - 18): slots of keyframes on a
+// icet_amd/csrc/icet_store.hip -- the keyframe store of the C ABI (include/icet_hip.h icet_keyframe_store_*; DESIGN.md sections 15 - 19): slots of keyframes on a
 // borrowed context's device, their poses, descriptors and grids, and the closure queries.  The registrations themselves are the context's indexed call
-// (register_indexed, icet_capi.hip); the kernels are icet_kfstore.hip, icet_closure.hip, icet_appearance.hip and icet_coarse.hip.
+// (register_indexed, icet_capi.hip); the kernels are icet_kfstore.hip, icet_closure.hip, icet_appearance.hip, icet_coarse.hip and icet_snapshot.hip.
 #include "../../include/icet_hip.h"
 #include "icet_ctx.h"
 #include "icet_closure.h"
 #include "icet_appearance.h"
 #include "icet_coarse.h"
+#include "icet_snapshot.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -498,6 +499,7 @@ icet_status icet_keyframe_store_enable_appearance(icet_keyframe_store* s, const 
     auto* a = new (std::nothrow) icet_keyframe_store::Appearance();
     if (!a) { s->err = "host allocation failed"; return ICET_ERR_NOMEM; }
     a->k = icet_appearance_rule::make_consts(d.sectors, d.rings, d.rho_max, d.z_lo, d.z_hi);
+    a->params = d;
     a->Rp = (d.rings + 3) / 4;
     const size_t A = (size_t)a->k.A, row = A * (size_t)a->Rp, cells = A * (size_t)a->k.Rn;
     hipError_t e = app_alloc_table(row, A, s->capacity, a->desc, a->w, a->has);
@@ -636,6 +638,7 @@ icet_status icet_keyframe_store_enable_coarse(icet_keyframe_store* s, const icet
     auto* a = new (std::nothrow) icet_keyframe_store::Coarse();
     if (!a) { s->err = "host allocation failed"; return ICET_ERR_NOMEM; }
     a->k = icet_coarse_rule::make_consts(d.cells, d.cell, d.z_lo, d.z_hi, d.min_span);
+    a->params = d;
     const size_t row = a->row_words(), cells = (size_t)a->k.G * (size_t)a->k.G;
     constexpr size_t kQK = (size_t)kClosureMaxQueries * kClosureMaxCandidates, kH = 2 * (2 * icet_coarse_rule::kMaxYaw + 1);
     hipError_t e = launch_coarse_prepare(a->k);
@@ -815,6 +818,251 @@ icet_status icet_keyframe_store_close_coarse_device(icet_keyframe_store* s, cons
     if (!s) return ICET_ERR_BAD_ARG;
     if (!search) return coarse_search_ok(s, search);          // (refused: the coarse call needs its search)
     return close_pipeline(s, p, n_queries, scan2, poses != nullptr, poses, stamps, query, search, start_offsets, d_closure, d_cand, d_x0, d_out, d_score, d_match);
+}
+
+// ---- snapshots: a store to a file and back (the format and its validation: icet_snapshot.h) ------------------------------------------
+namespace snap = icet_snapshot;
+
+// What a save or a load holds while it runs: the entries (pinned and on the device), the payload checksums, one device staging and two pinned buffers that a
+// chunk's copy and the file I/O of the chunk before it alternate between.
+struct SnapBuffers {
+    SnapEntry* h_ent = nullptr; SnapEntry* d_ent = nullptr; unsigned long long* d_sums = nullptr; unsigned long long* h_sums = nullptr;
+    uint8_t* d_stage = nullptr; uint8_t* h_buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
+};
+static void snap_free(icet_keyframe_store* s, SnapBuffers& b) {
+    (void)hipStreamSynchronize(s->ctx->stream);              // (nothing in flight reads or writes what goes)
+    for (void* q : {(void*)b.d_ent, (void*)b.d_sums, (void*)b.d_stage}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)b.h_ent, (void*)b.h_sums, (void*)b.h_buf[0], (void*)b.h_buf[1]}) if (q) (void)hipHostFree(q);
+    for (hipEvent_t e : b.ev) if (e) (void)hipEventDestroy(e);
+    b = SnapBuffers{};
+}
+static hipError_t snap_alloc(SnapBuffers& b, size_t n_entries, size_t chunk_bytes, bool sums) {
+    const size_t ne = n_entries ? n_entries : 1, cb = chunk_bytes ? chunk_bytes : 16;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&b.h_ent), sizeof(SnapEntry) * ne);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b.d_ent), sizeof(SnapEntry) * ne);
+    if (e == hipSuccess && sums) e = hipMalloc(reinterpret_cast<void**>(&b.d_sums), sizeof(unsigned long long) * ne);
+    if (e == hipSuccess && sums) e = hipHostMalloc(reinterpret_cast<void**>(&b.h_sums), sizeof(unsigned long long) * ne);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b.d_stage), cb);
+    for (int k = 0; k < 2; k++) {
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b.h_buf[k]), cb);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b.ev[k], hipEventDisableTiming);
+    }
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+}
+
+// Entries first .. into chunks of at most `budget` payload bytes, never splitting one: chunk k holds entries cut[k] .. cut[k + 1] - 1.
+static std::vector<size_t> snap_chunks(const std::vector<snap::Entry>& ent, uint64_t budget) {
+    std::vector<size_t> cut{0};
+    uint64_t in = 0;
+    for (size_t k = 0; k < ent.size(); k++) {
+        if (in > 0 && in + ent[k].bytes > budget) { cut.push_back(k); in = 0; }
+        in += ent[k].bytes;
+    }
+    if (!ent.empty()) cut.push_back(ent.size());
+    return cut;
+}
+
+static void snap_header_of(const icet_keyframe_store* s, snap::Header& h) {
+    static_assert(sizeof(icet_appearance_params) == sizeof(h.app) && sizeof(icet_coarse_params) == sizeof(h.coarse), "the feature blocks of a snapshot's header");
+    std::memset(&h, 0, sizeof(h));
+    h.bins_phi = s->shape.bins_phi; h.bins_theta = s->shape.bins_theta; h.n = s->shape.n;
+    std::memcpy(&h.thresh_bits, &s->shape.thresh, 4); std::memcpy(&h.buff_bits, &s->shape.buff, 4);
+    h.shape_flags = (uint32_t)s->shape.flags & snap::kShapeFlags; h.V = s->V;
+    if (s->app) { h.features |= snap::kHasAppearance; std::memcpy(h.app, &s->app->params, sizeof(h.app)); }
+    if (s->coarse) { h.features |= snap::kHasCoarse; std::memcpy(h.coarse, &s->coarse->params, sizeof(h.coarse)); }
+}
+
+// The store's tables as the snapshot kernels take them; A, Rp, G size the payloads (a load: the file's).
+static SnapTables snap_tables(const icet_keyframe_store* s, int A, int Rp, int G) {
+    const PoseTable pt = s->pose_table();
+    SnapTables t{};
+    t.hot = s->hotS; t.fit = s->fitS; t.sov = s->slot_of_voxel; t.n_slots = s->n_slots;
+    if (s->app) { t.desc = s->app->desc; t.w = s->app->w; t.app_has = s->app->has; }
+    if (s->coarse) { t.grid = s->coarse->grid; t.grid_has = s->coarse->has; }
+    t.stamp = pt.stamp; t.pose = pt.f; t.cap = s->capacity; t.V = s->V; t.A = A; t.Rp = Rp; t.G = G;
+    return t;
+}
+
+static uint64_t snap_budget(const icet_ctx* c, const std::vector<snap::Entry>& ent) {
+    uint64_t budget = c->snapshot_chunk_bytes > 0 ? (uint64_t)c->snapshot_chunk_bytes : (uint64_t)64 << 20, total = 0;
+    for (const snap::Entry& e : ent) { budget = std::max(budget, e.bytes); total += e.bytes; }      // entries never split: at least the largest
+    return std::min(budget, std::max<uint64_t>(total, 16));
+}
+
+static void snap_dev_entry(SnapEntry& d, const snap::Entry& e, int32_t slot, uint64_t off) {
+    std::memset(&d, 0, sizeof(d));
+    d.slot = slot; d.n_slots = e.n_slots; d.flags = e.flags; d.stamp = e.stamp; d.off = off;
+    std::memcpy(d.pose, e.pose, sizeof(d.pose));
+}
+
+icet_status icet_keyframe_store_save(icet_keyframe_store* s, const char* path, int32_t n, const int32_t* slots) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (!path || (slots && n < 0)) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    // everything is checked before anything is touched
+    std::vector<int32_t> which;
+    if (slots) {
+        const icet_status ok = slots_ok(s, n, slots, true, "save");
+        if (ok != ICET_OK) return ok;
+        which.assign(slots, slots + n);
+        std::sort(which.begin(), which.end());
+    } else {
+        for (int32_t j = 0; j < s->capacity; j++) if (s->occupied[(size_t)j]) which.push_back(j);
+    }
+    if (c->tune.keep != 0) { s->err = "the store's calls run with option \"keep\" 0"; return ICET_ERR_UNSUPPORTED; }
+    STORECHK(s, hipSetDevice(c->device));
+    STORECHK(s, hipStreamSynchronize(c->stream));              // behind whatever was enqueued: the puts and poses this save is to hold
+    const size_t cap = (size_t)s->capacity, ne = which.size();
+    std::vector<int32_t> ns(cap);
+    std::vector<uint8_t> poses(kPoseBytes * cap);
+    STORECHK(s, hipMemcpy(ns.data(), s->n_slots, sizeof(int32_t) * cap, hipMemcpyDeviceToHost));
+    STORECHK(s, hipMemcpy(poses.data(), s->pose_stamp, kPoseBytes * cap, hipMemcpyDeviceToHost));
+    // the directory, laid out on the host
+    snap::Header h;
+    snap_header_of(s, h);
+    h.n_entries = (uint32_t)ne;
+    std::vector<snap::Entry> ent(ne);
+    uint64_t at = snap::directory_end(h.n_entries);
+    for (size_t k = 0; k < ne; k++) {
+        snap::Entry& e = ent[k];
+        const size_t sl = (size_t)which[k];
+        e.slot = which[k]; e.n_slots = ns[sl];
+        if (e.n_slots < 0 || e.n_slots > s->V) { s->err = "slot " + std::to_string(which[k]) + " holds a row count outside 0 .. V"; return ICET_ERR_HIP; }
+        std::memcpy(&e.stamp, poses.data() + sizeof(int64_t) * sl, sizeof(int64_t));
+        bool ff = true;
+        for (size_t j = 0; j < 12; j++) { std::memcpy(&e.pose[j], poses.data() + sizeof(int64_t) * cap + sizeof(float) * (j * cap + sl), 4); ff = ff && e.pose[j] == 0xFFFFFFFFu; }
+        e.flags = (ff ? 0u : snap::kFlagPose) | (s->app && s->app->has_h[sl] ? snap::kFlagDesc : 0u) | (s->coarse && s->coarse->has_h[sl] ? snap::kFlagGrid : 0u);
+        e.off = at; e.bytes = snap::layout(s->V, e.n_slots, e.flags, h.A(), h.Rp(), h.G()).size; e.sum = 0;
+        at += e.bytes;
+    }
+    h.file_bytes = at;
+    const uint64_t budget = snap_budget(c, ent);
+    const std::vector<size_t> cut = snap_chunks(ent, budget);
+    snap::Writer w;
+    std::vector<uint8_t> front((size_t)snap::directory_end(h.n_entries), 0);
+    if (!snap::writer_open(w, path, s->err)) return ICET_ERR_BAD_ARG;
+    if (!snap::writer_write(w, front.data(), front.size(), s->err)) { snap::writer_abort(w); return ICET_ERR_BAD_ARG; }      // (its place; written again when the checksums are known)
+    SnapBuffers b;
+    hipError_t he = snap_alloc(b, ne, (size_t)budget, true);
+    bool io_ok = true;
+    if (he == hipSuccess && ne > 0) {
+        for (size_t k = 0; k + 1 < cut.size(); k++) for (size_t i = cut[k]; i < cut[k + 1]; i++) snap_dev_entry(b.h_ent[i], ent[i], ent[i].slot, ent[i].off - ent[cut[k]].off);
+        c->armed_calls = 2;
+        he = hipMemcpyAsync(b.d_ent, b.h_ent, sizeof(SnapEntry) * ne, hipMemcpyHostToDevice, c->stream);
+        if (he == hipSuccess) he = hipMemsetAsync(b.d_sums, 0, sizeof(unsigned long long) * ne, c->stream);
+        const SnapTables t = snap_tables(s, h.A(), h.Rp(), h.G());
+        auto chunk_bytes = [&](size_t k) { return (size_t)(ent[cut[k + 1] - 1].off + ent[cut[k + 1] - 1].bytes - ent[cut[k]].off); };
+        // chunk k: pack -> copy into pinned buffer k & 1; chunk k - 1 goes to the file meanwhile
+        for (size_t k = 0; k + 1 < cut.size() && he == hipSuccess && io_ok; k++) {
+            he = launch_snapshot_pack(t, b.d_ent + cut[k], (int)(cut[k + 1] - cut[k]), b.d_stage, b.d_sums + cut[k], c->stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(b.h_buf[k & 1], b.d_stage, chunk_bytes(k), hipMemcpyDeviceToHost, c->stream);
+            if (he == hipSuccess) he = hipEventRecord(b.ev[k & 1], c->stream);
+            if (he == hipSuccess && k > 0) {
+                he = hipEventSynchronize(b.ev[(k - 1) & 1]);
+                if (he == hipSuccess) io_ok = snap::writer_write(w, b.h_buf[(k - 1) & 1], chunk_bytes(k - 1), s->err);
+            }
+        }
+        if (he == hipSuccess && io_ok) {
+            const size_t last = cut.size() - 2;
+            he = hipMemcpyAsync(b.h_sums, b.d_sums, sizeof(unsigned long long) * ne, hipMemcpyDeviceToHost, c->stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+            if (he == hipSuccess) io_ok = snap::writer_write(w, b.h_buf[last & 1], chunk_bytes(last), s->err);
+        }
+    }
+    if (he == hipSuccess && io_ok) {
+        for (size_t k = 0; k < ne; k++) ent[k].sum = b.h_sums[k];
+        snap::put_header(front.data(), h, kSlotLayoutVersion);
+        for (size_t k = 0; k < ne; k++) snap::put_entry(front.data() + snap::kHeaderBytes + (size_t)snap::kEntryBytes * k, ent[k]);
+        snap::seal(front.data(), h.n_entries);
+        io_ok = snap::writer_rewind(w, s->err) && snap::writer_write(w, front.data(), front.size(), s->err) && snap::writer_commit(w, s->err);
+    }
+    if (he != hipSuccess) s->err = std::string("keyframe store save: ") + hipGetErrorString(he);
+    if (he != hipSuccess || !io_ok) snap::writer_abort(w);
+    snap_free(s, b);
+    return he != hipSuccess ? (he == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP) : (io_ok ? ICET_OK : ICET_ERR_BAD_ARG);
+}
+
+icet_status icet_keyframe_store_load(icet_keyframe_store* s, const char* path, int32_t slot_offset) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    icet_ctx* c = s->ctx;
+    if (!path) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    // the file, read and validated on the host, then held against the store: everything is checked before anything is touched
+    std::vector<uint8_t> img; snap::Header h; std::vector<snap::Entry> ent;
+    if (!snap::read_file(path, kSlotLayoutVersion, img, h, ent, s->err, nullptr)) return ICET_ERR_BAD_ARG;
+    snap::Header mine;
+    snap_header_of(s, mine);
+    if (h.bins_phi != mine.bins_phi || h.bins_theta != mine.bins_theta || h.n != mine.n || h.thresh_bits != mine.thresh_bits || h.buff_bits != mine.buff_bits ||
+        h.shape_flags != mine.shape_flags) { s->err = "the grid, n, thresh, buff or keyframe-shaping flags of the file differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG; }
+    for (const snap::Entry& e : ent) {
+        const int64_t target = (int64_t)e.slot + (int64_t)slot_offset;
+        if (target < 0 || target >= s->capacity) {
+            s->err = "slot " + std::to_string(e.slot) + " + slot_offset " + std::to_string(slot_offset) + " is not a slot (0 .. " + std::to_string(s->capacity - 1) + "): reserve first";
+            return ICET_ERR_BAD_ARG;
+        }
+    }
+    if ((h.features & snap::kHasAppearance) && s->app && std::memcmp(h.app, mine.app, sizeof(h.app)) != 0) { s->err = "the file's appearance parameters differ from the store's"; return ICET_ERR_BAD_ARG; }
+    if ((h.features & snap::kHasCoarse) && s->coarse && std::memcmp(h.coarse, mine.coarse, sizeof(h.coarse)) != 0) { s->err = "the file's coarse parameters differ from the store's"; return ICET_ERR_BAD_ARG; }
+    if (c->tune.keep != 0) { s->err = "the store's calls run with option \"keep\" 0"; return ICET_ERR_UNSUPPORTED; }
+    const size_t ne = ent.size();
+    if (ne == 0) return ICET_OK;
+    STORECHK(s, hipSetDevice(c->device));
+    const uint64_t budget = snap_budget(c, ent);
+    const std::vector<size_t> cut = snap_chunks(ent, budget);
+    SnapBuffers b;
+    hipError_t he = snap_alloc(b, ne, (size_t)budget, false);
+    if (he == hipSuccess) {
+        for (size_t k = 0; k + 1 < cut.size(); k++) for (size_t i = cut[k]; i < cut[k + 1]; i++) snap_dev_entry(b.h_ent[i], ent[i], ent[i].slot + slot_offset, ent[i].off - ent[cut[k]].off);
+        c->armed_calls = 2;
+        he = hipMemcpyAsync(b.d_ent, b.h_ent, sizeof(SnapEntry) * ne, hipMemcpyHostToDevice, c->stream);
+        const SnapTables t = snap_tables(s, h.A(), h.Rp(), h.G());
+        // chunk k: the file's bytes into pinned buffer k & 1 (once the copy of chunk k - 2 has left it) -> copy -> unpack
+        for (size_t k = 0; k + 1 < cut.size() && he == hipSuccess; k++) {
+            const size_t bytes = (size_t)(ent[cut[k + 1] - 1].off + ent[cut[k + 1] - 1].bytes - ent[cut[k]].off);
+            if (k >= 2) he = hipEventSynchronize(b.ev[k & 1]);
+            if (he != hipSuccess) break;
+            std::memcpy(b.h_buf[k & 1], img.data() + ent[cut[k]].off, bytes);
+            he = hipMemcpyAsync(b.d_stage, b.h_buf[k & 1], bytes, hipMemcpyHostToDevice, c->stream);
+            if (he == hipSuccess) he = hipEventRecord(b.ev[k & 1], c->stream);
+            if (he == hipSuccess) he = launch_snapshot_unpack(t, b.d_ent + cut[k], (int)(cut[k + 1] - cut[k]), b.d_stage, c->stream);
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    }
+    // the host mirrors follow (after a failure what the target rows hold is unknown: they count as empty)
+    for (const snap::Entry& e : ent) {
+        const size_t sl = (size_t)(e.slot + slot_offset);
+        s->occupied[sl] = he == hipSuccess;
+        if (s->app) s->app->has_h[sl] = he == hipSuccess && (e.flags & snap::kFlagDesc);
+        if (s->coarse) s->coarse->has_h[sl] = he == hipSuccess && (e.flags & snap::kFlagGrid);
+    }
+    if (he != hipSuccess) s->err = std::string("keyframe store load: ") + hipGetErrorString(he);
+    snap_free(s, b);
+    return he == hipSuccess ? ICET_OK : (he == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP);
+}
+
+icet_status icet_keyframe_store_snapshot_info(const char* path, icet_snapshot_info* info) {
+    static_assert(sizeof(icet_snapshot_info) == 120, "the record of include/icet_hip.h (the ctypes mirror of icet_amd/api.py)");
+    if (!path || !info) return ICET_ERR_BAD_ARG;
+    std::vector<uint8_t> img; snap::Header h; std::vector<snap::Entry> ent; std::string err;
+    if (!snap::read_file(path, kSlotLayoutVersion, img, h, ent, err, nullptr)) return ICET_ERR_BAD_ARG;
+    std::memset(info, 0, sizeof(*info));
+    info->shape.bins_phi = h.bins_phi; info->shape.bins_theta = h.bins_theta; info->shape.n = h.n;
+    std::memcpy(&info->shape.thresh, &h.thresh_bits, 4); std::memcpy(&info->shape.buff, &h.buff_bits, 4);
+    info->shape.flags = (int32_t)h.shape_flags;
+    info->V = h.V; info->entries = (int32_t)h.n_entries; info->highest_slot = ent.empty() ? -1 : ent.back().slot;
+    info->has_appearance = (h.features & snap::kHasAppearance) != 0; info->has_coarse = (h.features & snap::kHasCoarse) != 0;
+    std::memcpy(&info->appearance, h.app, sizeof(h.app)); std::memcpy(&info->coarse, h.coarse, sizeof(h.coarse));
+    info->file_bytes = (int64_t)h.file_bytes;
+    return ICET_OK;
+}
+
+icet_status icet_keyframe_store_snapshot_slots(const char* path, int32_t cap, int32_t* slots, int64_t* stamps, int32_t* n_out) {
+    if (!path || cap < 0 || !n_out || (cap > 0 && !slots)) return ICET_ERR_BAD_ARG;
+    std::vector<uint8_t> img; snap::Header h; std::vector<snap::Entry> ent; std::string err;
+    if (!snap::read_file(path, kSlotLayoutVersion, img, h, ent, err, nullptr)) return ICET_ERR_BAD_ARG;
+    for (size_t k = 0; k < ent.size() && k < (size_t)cap; k++) { slots[k] = ent[k].slot; if (stamps) stamps[k] = ent[k].stamp; }
+    *n_out = (int32_t)ent.size();
+    return ICET_OK;
 }
 
 }  // extern "C"

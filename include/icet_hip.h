@@ -497,6 +497,42 @@ icet_status icet_keyframe_store_close_coarse_device(icet_keyframe_store* s, cons
                                                     const icet_coarse_search* search, const float* start_offsets, icet_closure* d_closure, int32_t* d_cand,
                                                     float* d_x0, float* d_out, icet_score* d_score, icet_coarse_match* d_match);
 
+/* --- snapshots: a store to a file and back, bit for bit ------------------------------------------------------------------------------------------
+ * A store keeps no raw scans, so a map made in one process is carried to another as a file: the occupied slots at their used length (n_slots records, not V),
+ * their poses and stamps, and their descriptors and grids where the store has them.  The format -- little-endian, every section 16-byte aligned, every byte
+ * under a checksum, reserved bytes and padding zero -- and its validation are icet_amd/csrc/icet_snapshot.h.
+ * SAVE.  In stream order behind whatever was enqueued.  slots: n distinct occupied slots (HOST array), or NULL for every occupied slot (n is then ignored);
+ *   else ICET_ERR_BAD_ARG.  The payload moves in chunks of option "snapshot_chunk_bytes" (icet_set_option on the store's context; default and 0: 64 MiB; never
+ *   less than the largest single slot; the file does not depend on it): packed on the device, copied into one of two pinned buffers and written while the next
+ *   chunk packs.  Written to path + ".tmp" and renamed on success: a failed save leaves nothing at `path`.  Returns after the file is closed.  A path that
+ *   cannot be written: ICET_ERR_BAD_ARG, the reason in last_error.
+ * LOAD.  Reads and validates the whole file on the host (every checksum, every offset and size, and the contents a kernel would index by), then holds it
+ *   against the store: the keyframe shape (grid, n, bit patterns of thresh and buff, the two keyframe-shaping flags) must be equal and every slot + slot_offset a
+ *   slot of the store (reserve first; snapshot_info gives the highest slot).  A file that carries descriptors loads into a store with appearance enabled only
+ *   when the parameters are bit-equal; into a store without, the descriptors are skipped; a file without them gives slots that have none and are never
+ *   appearance candidates, like slots put before enable_appearance.  Grids likewise.  Any failure of these: ICET_ERR_BAD_ARG, the reason in last_error, and
+ *   nothing is touched.  Only then are the chunks uploaded and unpacked.  A loaded slot replaces everything the target slot held -- tables, pose and stamp,
+ *   descriptor and grid, each cleared where the entry has none --; every other slot keeps its bytes.  Synchronises the stream before it returns.  The tables do
+ *   not move: a replayed graph reads the new bytes as it does after a put.
+ * INFO / SLOTS.  Host only, no store: the validated file's header, and its slots with their stamps in ascending order (at most cap are written, *n_out is the
+ *   file's count; stamps may be NULL).  A file that cannot be read or is refused: ICET_ERR_BAD_ARG.
+ * With option "keep" on, save and load answer ICET_ERR_UNSUPPORTED, as the store's other calls do.  Neither touches the context's parked keyframe. */
+typedef struct icet_snapshot_info {
+    icet_params shape;            /* runlen 0; flags: the keyframe-shaping flags */
+    int32_t V;                    /* bins_phi * bins_theta */
+    int32_t entries;              /* saved slots */
+    int32_t highest_slot;         /* -1 when there is none */
+    int32_t has_appearance, has_coarse;      /* 1: the block below holds the saved store's parameters */
+    icet_appearance_params appearance;
+    icet_coarse_params coarse;
+    int64_t file_bytes;
+} icet_snapshot_info;             /* 120 bytes */
+
+icet_status icet_keyframe_store_save(icet_keyframe_store* s, const char* path, int32_t n, const int32_t* slots);
+icet_status icet_keyframe_store_load(icet_keyframe_store* s, const char* path, int32_t slot_offset);
+icet_status icet_keyframe_store_snapshot_info(const char* path, icet_snapshot_info* info);
+icet_status icet_keyframe_store_snapshot_slots(const char* path, int32_t cap, int32_t* slots, int64_t* stamps, int32_t* n_out);
+
 /* Pre-size the workspace (so the first timed call does not allocate). */
 icet_status icet_reserve(icet_ctx* ctx, const icet_params* p, int32_t n_pairs, int64_t total_n1, int64_t total_n2);
 
@@ -565,7 +601,7 @@ icet_status icet_debug_fix(icet_ctx* ctx, const float* v, int32_t n, uint64_t* o
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
  * bits; default 0: measured no faster on MI355X, where a device-scope fence is an L2 write-back), "batch_parts" (0 = automatic), "batch_stage" (0..4), "force_exact"
  * (every scan-2 point through the literal classification), "library_sort" (rocPRIM radix sort instead of
- * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
+ * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
  * the condition number |A|_F |A^-1|_F exceeds it is inverted by the literal restatement of the reference's statements -- column-pivoted QR
  * pseudo-inverse, eigenvectors, pruning -- instead of a Cholesky factorisation; 0 = always literal.  Not a launch-shape knob: between the two
  * routes cov / dx differ by rounding times the condition number).  Unknown name or value
