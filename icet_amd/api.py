@@ -26,7 +26,7 @@ FLAG_HALF_GAP_BOUNDS = 8  # non-parity extension (half-gap cluster buffers of th
 
 # every symbol include/icet_hip.h, include/icet_nodes.h and include/icet_io.h declare
 EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_version", "icet_solve", "icet_solve_begin", "icet_solve_keyframe_tables", "icet_solve_end", "icet_solve_batch",
-                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_debug_point_sums_device", "icet_debug_fix", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
+                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_debug_point_sums_device", "icet_debug_gn_terms_device", "icet_debug_fix", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
                     "icet_keyframe_store_create", "icet_keyframe_store_destroy", "icet_keyframe_store_last_error", "icet_keyframe_store_reserve", "icet_keyframe_store_put_device",
                     "icet_keyframe_store_register_device", "icet_keyframe_store_register_scored_device", "icet_keyframe_store_score_device", "icet_keyframe_store_debug_fetch",
                     "icet_keyframe_store_set_pose", "icet_keyframe_store_candidates_device", "icet_keyframe_store_close_device", "icet_pose_step_from_x",
@@ -202,6 +202,7 @@ def load_library():
     L.icet_debug_pinv3.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_debug_pinv3_double.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_debug_point_sums_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
+    L.icet_debug_gn_terms_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_debug_fix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.icet_keyframe_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan)]
     L.icet_register_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
@@ -521,6 +522,18 @@ class Context:
             raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
         B = _dev_scans(scan2_descs)
         self._check(load_library().icet_debug_point_sums_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_sums_ptr)))
+
+    def debug_gn_terms(self, kf_index, scan2_descs, params, d_X_ptr, d_sums_ptr, d_xf_ptr, d_htwh_ptr, d_htwdz_ptr, d_out_ptr):
+        """icet_debug_gn_terms_device (test hook): debug_point_sums' point pass with the records left in place, then the production solve of iteration
+        params.runlen - 1 on them.  Device pointers: d_sums (k x V records of POINT_SUMS_DTYPE), d_xf (k x 48 floats, the transform record), d_htwh (k x 36),
+        d_htwdz (k x 6), d_out (k x 48: X | pred_stds | cov).  Returns after the stream has drained."""
+        k = len(scan2_descs)
+        idx = np.ascontiguousarray(np.asarray(kf_index, np.int32).reshape(-1))
+        if idx.shape[0] != k:
+            raise IcetError(ICET_ERR_BAD_ARG, "kf_index and scan2_descs differ in length")
+        B = _dev_scans(scan2_descs)
+        self._check(load_library().icet_debug_gn_terms_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_sums_ptr),
+                                                              C.c_void_p(d_xf_ptr), C.c_void_p(d_htwh_ptr), C.c_void_p(d_htwdz_ptr), C.c_void_p(d_out_ptr)))
 
     def debug_fix(self, values):
         """icet_debug_fix (test hook): n floats through the point pass's float -> 2^36 fixed-point conversions -> (n, 3) uint64 = to_fix_biased (defined for

@@ -550,7 +550,7 @@ icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const fl
 // icet_register_device_n --, and behind the descriptor upload rows[r] replaces the count (k_init_state, or k_patch_counts in front of the scan-2 round trip) and
 // kf_of[r] the index.
 icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1,
-                            const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr) {
+                            const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr, const GnTermsOut* terms = nullptr) {
     if (iters < 0) iters = p->runlen;
     Workspace& w = c->w;
     LaunchCfg cfg = make_cfg(c, p, n_regs, c->h_desc_reg, nullptr);
@@ -587,6 +587,29 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it + 1], c->stream));
         HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, nullptr, c->stream));
     }
+    if (terms) {                                                            // (icet_debug_gn_terms_device; iters == 0: k_init_state left the transform record of d_x0 in w.xf)
+        // the solve writes its sums at [registration][iteration] of arrays sized for the whole run: a scratch of that shape, and the rows of iteration runlen - 1 copied out
+        const int it = p->runlen - 1;
+        const size_t row = (size_t)p->runlen * 42;
+        float* d_tmp = nullptr;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d_tmp), sizeof(float) * row * (size_t)n_regs));
+        auto body = [&]() -> icet_status {
+            HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
+            HIPCHK(c, launch_point_sums_copy(wl, lcfg, d_dump, c->stream));     // drains the overflow list; the records stay
+            HIPCHK(c, hipMemcpyAsync(terms->xf, w.xf, sizeof(float) * 48 * (size_t)n_regs, hipMemcpyDeviceToDevice, c->stream));      // (before the solve replaces it with the next iteration's)
+            AuxDev aux{};
+            aux.htwh = d_tmp; aux.htwdz = d_tmp + (size_t)n_regs * p->runlen * 36;
+            HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, &aux, c->stream));
+            HIPCHK(c, hipMemcpy2DAsync(terms->htwh, 36 * sizeof(float), aux.htwh + (size_t)it * 36, (size_t)p->runlen * 36 * sizeof(float), 36 * sizeof(float), n_regs, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpy2DAsync(terms->htwdz, 6 * sizeof(float), aux.htwdz + (size_t)it * 6, (size_t)p->runlen * 6 * sizeof(float), 6 * sizeof(float), n_regs, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            return ICET_OK;
+        };
+        const icet_status ts = body();
+        if (ts != ICET_OK) (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(d_tmp);
+        if (ts != ICET_OK) return ts;
+    } else
     if (d_score || d_dump) {                                                // the last solve (or k_init_state) left the transform record of the pose to score in w.xf
         HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
         if (d_dump) HIPCHK(c, launch_point_sums_dump(wl, lcfg, d_dump, c->stream));      // (icet_debug_point_sums_device: the raw sums in place of the score)
@@ -1026,10 +1049,10 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
 
 }  // extern "C"
 icet_status icet::register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
-                                   icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src, const IndexedDev* dev, uint32_t* d_dump) {
+                                   icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src, const IndexedDev* dev, uint32_t* d_dump, const GnTermsOut* terms) {
     if (!c) return ICET_ERR_BAD_ARG;
-    const bool need_out = mode == kIdxRegister || mode == kIdxScored, need_score = mode == kIdxScored || mode == kIdxScoreOnly, need_x = mode == kIdxScoreOnly || mode == kIdxDump;
-    if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (need_x && !d_x0) || (mode == kIdxDump && !d_dump)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
+    const bool need_out = mode == kIdxRegister || mode == kIdxScored || mode == kIdxTerms, need_score = mode == kIdxScored || mode == kIdxScoreOnly, need_x = mode == kIdxScoreOnly || mode == kIdxDump || mode == kIdxTerms;
+    if (!params_ok(p) || n_regs < 0 || (n_regs > 0 && (!kf_index || !scan2 || (need_out && !d_out) || (need_score && !d_score) || (need_x && !d_x0) || ((mode == kIdxDump || mode == kIdxTerms) && !d_dump) || (mode == kIdxTerms && (!terms || !terms->xf || !terms->htwh || !terms->htwdz || p->runlen < 1))))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n_regs == 0) return ICET_OK;
     // everything is checked before anything is touched: a refused call leaves the parked keyframe (and every slot of a store) as it was
     const icet_params& q = src ? src->shape : c->kf_params;
@@ -1075,6 +1098,7 @@ icet_status icet::register_indexed(icet_ctx* c, const icet_params* p, int32_t n_
         return enq();
     }
     if (mode == kIdxDump) return enqueue_indexed(c, p, n_regs, d_x0, nullptr, nullptr, 0, src, dev, d_dump);      // (never captured)
+    if (mode == kIdxTerms) return enqueue_indexed(c, p, n_regs, d_x0, d_out, nullptr, 0, src, dev, d_dump, terms);      // (never captured)
     // scored calls: runlen == 0 scores X0 (results as the unscored call writes them); score-only calls score d_x0 without iterating
     const bool no_iters = mode == kIdxScoreOnly || p->runlen == 0;
     auto enq = [&]() -> icet_status {
@@ -1110,6 +1134,14 @@ icet_status icet_debug_point_sums_device(icet_ctx* c, const icet_params* p, int3
                                          const float* d_X, void* d_sums) {
     if (c && (reinterpret_cast<uintptr_t>(d_sums) & 15u)) { c->err = "icet_debug_point_sums_device: d_sums must be 16-byte aligned"; return ICET_ERR_BAD_ARG; }      // (the copy-out kernel stores 16 bytes at a time)
     return register_indexed(c, p, n_regs, kf_index, scan2, d_X, nullptr, nullptr, kIdxDump, nullptr, nullptr, static_cast<uint32_t*>(d_sums));
+}
+
+// Test hook: the point pass at the poses d_X, the raw records (left in place), then the production solve of iteration runlen - 1 on them.
+icet_status icet_debug_gn_terms_device(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
+                                       const float* d_X, void* d_sums, float* d_xf, float* d_htwh, float* d_htwdz, float* d_out) {
+    if (c && (reinterpret_cast<uintptr_t>(d_sums) & 15u)) { c->err = "icet_debug_gn_terms_device: d_sums must be 16-byte aligned"; return ICET_ERR_BAD_ARG; }      // (the copy-out kernel stores 16 bytes at a time)
+    const GnTermsOut t{d_xf, d_htwh, d_htwdz};
+    return register_indexed(c, p, n_regs, kf_index, scan2, d_X, d_out, nullptr, kIdxTerms, nullptr, nullptr, static_cast<uint32_t*>(d_sums), &t);
 }
 
 // Scores of the host-pointer entry points: device + pinned, n entries.

@@ -169,10 +169,13 @@ static inline bool same_keyframe_shape(const icet_params& a, const icet_params& 
 // d_x0 alone (kIdxScoreOnly: no iteration, d_out unused).  src: the keyframe tables -- nullptr the context's parked keyframe (kf_index: parked keyframes), or a
 // keyframe store (kf_index: its occupied slots; icet_keyframe_store_register_device and its kin).  dev: keyframe index and row count of every registration as
 // kernels in front of the call left them on the device (a closure query; never captured into a graph).
-enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2, kIdxDump = 3 };      // kIdxDump (icet_debug_point_sums_device): kIdxScoreOnly with the raw per-voxel sums (d_dump) in place of the score
+enum IndexedMode { kIdxRegister = 0, kIdxScored = 1, kIdxScoreOnly = 2, kIdxDump = 3, kIdxTerms = 4 };      // kIdxDump (icet_debug_point_sums_device): kIdxScoreOnly with the raw per-voxel sums (d_dump) in place of the score
+// kIdxTerms (icet_debug_gn_terms_device): the point pass at d_x0, the raw sums copied out and LEFT IN PLACE (d_dump), the transform record, then the production solve of
+// iteration runlen - 1 on those very records: its H^T W H and H^T W dz, and its results in d_out.  Never captured into a graph.
+struct GnTermsOut { float* xf; float* htwh; float* htwdz; };
 struct IndexedDev { const int32_t* kf_of; const int32_t* rows; };
 __attribute__((visibility("hidden")))
 icet_status register_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2, const float* d_x0, float* d_out,
-                             icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr);
+                             icet_score* d_score, IndexedMode mode, const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr, const GnTermsOut* terms = nullptr);
 
 }  // namespace icet

@@ -2,7 +2,7 @@
 //     k_gn_score        behind one more point pass at the registration's transform record: per slot the moments, R_noise, dz = M (mu2 - mu1) and
 //                       W = pinv(M R_noise M^T) of gn_solve_body, then chi2 = sum dz^T W dz, voxels and points in; one block per registration
 //     k_select_best     one wave per group of registrations: the lowest chi2 per voxel among those with at least half the group's best voxel count
-//     k_point_sums_dump, k_fix_debug   test hooks: the point pass's raw per-voxel accumulator records, and its float -> fixed-point conversions on their own
+//     k_point_sums_dump, k_point_sums_copy, k_fix_debug   test hooks: the point pass's raw per-voxel accumulator records, and its float -> fixed-point conversions on their own
 // The loop's own kernels are untouched: this file has a body of its own, written after gn_solve_body's per-voxel front statement by statement.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -168,6 +168,31 @@ __global__ __launch_bounds__(kScoreBlock) void k_point_sums_dump(uint32_t* acc, 
     }
 }
 
+// Test hook (icet_debug_gn_terms_device): k_point_sums_dump that leaves every record where it is -- the solve launched behind it consumes (and clears) exactly what
+// was copied out.  The overflow list is drained here and its count reset, so that solve finds the list empty and the sums complete.
+__global__ __launch_bounds__(kScoreBlock) void k_point_sums_copy(uint32_t* acc, const float* __restrict__ xf_all, int V, NearOverflow over,
+                                                                 const int32_t* __restrict__ kf_of, uint32_t* __restrict__ dump) {
+    const int pair = blockIdx.x;
+    const int kf = kf_of ? __builtin_amdgcn_readfirstlane(kf_of[pair]) : pair;
+    const uint32_t nov = over.count[pair];                              // block-uniform
+    if (nov) {
+        NearOverflow o = over;
+        o.slot_of_voxel += ((ptrdiff_t)kf - pair) * ((V + 1) & ~1); o.hotS += ((ptrdiff_t)kf - pair) * V;
+        drain_near_overflow(o, pair, V, xf_all + pair * kXf, acc + (size_t)pair * V * kAccWords, nov);
+        __threadfence();
+        __syncthreads();
+        if (threadIdx.x == 0) over.count[pair] = 0u;
+    }
+    const int16_t* map = over.slot_of_voxel + (size_t)kf * ((V + 1) & ~1);
+    for (int v = threadIdx.x; v < V; v += kScoreBlock) {
+        const int s = map[v];
+        uint4* out = reinterpret_cast<uint4*>(dump + ((size_t)pair * V + v) * kAccWords);
+        const uint4* A = reinterpret_cast<const uint4*>(acc + ((size_t)pair * V + (s >= 0 ? s : 0)) * kAccWords);
+#pragma unroll
+        for (int k = 0; k < 5; k++) out[k] = s >= 0 ? A[k] : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
 // Test hook (icet_debug_fix): n floats through the three float -> fixed-point conversions of the point pass; out[3 i ..] = to_fix_biased, to_fix_wide_biased, to_fix.
 __global__ __launch_bounds__(kScoreBlock) void k_fix_debug(const float* __restrict__ v, unsigned long long* __restrict__ out, int n) {
     const int i = blockIdx.x * kScoreBlock + threadIdx.x;
@@ -224,6 +249,13 @@ hipError_t launch_gn_score(const Workspace& w, const LaunchCfg& c, int iter, ice
 hipError_t launch_point_sums_dump(const Workspace& w, const LaunchCfg& c, uint32_t* d_dump, hipStream_t st) {
     const NearOverflow over{w.desc, w.slot_of_voxel, w.hotS, w.thr, w.near_over, w.near_over_count, c.T, c.P, c.rt2};
     k_point_sums_dump<<<c.n_pairs, kScoreBlock, 0, st>>>(w.acc, w.xf, c.V, over, c.kf_of, d_dump);
+    ICET_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_point_sums_copy(const Workspace& w, const LaunchCfg& c, uint32_t* d_dump, hipStream_t st) {
+    const NearOverflow over{w.desc, w.slot_of_voxel, w.hotS, w.thr, w.near_over, w.near_over_count, c.T, c.P, c.rt2};
+    k_point_sums_copy<<<c.n_pairs, kScoreBlock, 0, st>>>(w.acc, w.xf, c.V, over, c.kf_of, d_dump);
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }

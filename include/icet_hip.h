@@ -578,6 +578,13 @@ icet_status icet_debug_pinv3_double(icet_ctx* ctx, const float* a, int32_t n, fl
  * The accumulators and the overflow count are left at zero, as a solve leaves them.  Never captured into a graph. */
 icet_status icet_debug_point_sums_device(icet_ctx* ctx, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
                                          const float* d_X, void* d_sums);
+/* Diagnostic hook for the per-voxel algebra tests: the arguments of icet_debug_point_sums_device and the same ONE point pass at the poses d_X; the records are copied to
+ * d_sums (same layout and alignment rule) but LEFT IN PLACE, and the production solve kernel of Gauss-Newton iteration p->runlen - 1 (>= 0; the index places the
+ * moving-voxel gate of ICET_FLAG_REJECT_MOVING) then consumes exactly those records.  Device outputs: d_xf n_regs x 48 floats, the transform record the kernels read
+ * (t[3] | R[9] row-major | angles[3] | pad | J[27]); d_htwh n_regs x 36 and d_htwdz n_regs x 6, H^T W H and H^T W dz as that kernel formed them; d_out n_regs x 48, the
+ * iteration's X | pred_stds | cov.  The call returns after the stream has drained; the workspace is left as every solve leaves it.  Never captured into a graph. */
+icet_status icet_debug_gn_terms_device(icet_ctx* ctx, const icet_params* p, int32_t n_regs, const int32_t* kf_index, const icet_dev_scan* scan2,
+                                       const float* d_X, void* d_sums, float* d_xf, float* d_htwh, float* d_htwdz, float* d_out);
 /* Diagnostic hook for the point-pass tests: n host-side floats through the float -> 2^36 fixed-point conversions of the point pass; out: n x 3 uint64 =
  * the two-instruction biased form (defined for |v| < 2^15) | the wide biased form | the unbiased form that selects between them per value. */
 icet_status icet_debug_fix(icet_ctx* ctx, const float* v, int32_t n, uint64_t* out);

@@ -292,3 +292,32 @@ def test_multi_gpu_scheduler_with_fake_devices(tmp_path):
     if subprocess.run(["g++", "-std=c++17", "-O1", "-pthread", "-fsanitize=thread", "-I", ROOT, src, "-o", tsan], capture_output=True).returncode == 0:
         r = subprocess.run([tsan], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and r.stdout.strip().endswith("ok") and "ThreadSanitizer" not in r.stderr, (r.returncode, r.stdout, r.stderr[-2000:])
+
+
+# ------------------------------------------------------------------ icet_debug_gn_terms_device: the entry checks of the per-voxel algebra hook
+def _gn_terms_args(ctx_handle, d_sums):
+    from icet_amd import api
+    p = api.Params(1, 24, 75, 25, 0.1, 0.1, 0)
+    idx = (C.c_int32 * 1)(0)
+    scan = (api.DevScan * 1)()
+    return (ctx_handle, C.byref(p), 1, idx, scan, None, d_sums, None, None, None, None)
+
+
+def test_debug_gn_terms_is_exported_and_refuses_a_null_context():
+    import icet_amd
+    from icet_amd import api
+    lib = icet_amd.load_library()
+    assert "icet_debug_gn_terms_device" in api.EXPORTED_SYMBOLS and "icet_debug_gn_terms_device" in _declared_symbols()
+    assert lib.icet_debug_gn_terms_device(*_gn_terms_args(None, None)) == api.ICET_ERR_BAD_ARG
+    assert lib.icet_debug_gn_terms_device(*_gn_terms_args(None, C.c_void_p(8))) == api.ICET_ERR_BAD_ARG
+
+
+@pytest.mark.gpu
+def test_debug_gn_terms_refuses_a_misaligned_d_sums(gpu_ctx):
+    import icet_amd
+    from icet_amd import api
+    lib = icet_amd.load_library()
+    buf = torch.zeros(64, dtype=torch.int32, device="cuda:0")
+    assert lib.icet_debug_gn_terms_device(*_gn_terms_args(gpu_ctx._h, C.c_void_p(buf.data_ptr() + 8))) == api.ICET_ERR_BAD_ARG
+    assert b"16-byte aligned" in lib.icet_last_error(gpu_ctx._h)
+    assert lib.icet_debug_gn_terms_device(*_gn_terms_args(gpu_ctx._h, C.c_void_p(buf.data_ptr()))) == api.ICET_ERR_BAD_ARG      # (aligned, but no poses and no outputs: refused as well)
