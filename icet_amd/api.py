@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
                     "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
                     "icet_keyframe_store_close_coarse_device",
+                    "icet_debug_block_tridiag",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -120,6 +121,27 @@ class Closure(C.Structure):
 CLOSURE_DTYPE = np.dtype([("slot", "<i4"), ("reg", "<i4"), ("accepted", "<i4"), ("n_candidates", "<i4"), ("stamp", "<i8"), ("d2", "<f4"), ("reserved0", "<i4"),
                           ("x0", "<f4", (6,)), ("reserved1", "<i4", (2,)), ("out", "<f4", (48,)), ("score", SCORE_DTYPE)])
 assert CLOSURE_DTYPE.itemsize == 288 == C.sizeof(Closure) and C.sizeof(ClosureQuery) == 32 and C.sizeof(Score) == 32 and C.sizeof(AppearanceParams) == 32
+
+
+def info_from_cov(cov):
+    """The information matrix of a registration for the pose graph: the symmetrised pseudo-inverse of its 6 x 6 ``cov`` in double, rounded to float32."""
+    c = np.asarray(cov, np.float64).reshape(6, 6)
+    p = np.linalg.pinv(0.5 * (c + c.T), hermitian=True)
+    return (0.5 * (p + p.T)).astype(np.float32)
+
+
+def closure_edges(records, live_nodes, node_of_slot):
+    """The closure edges (i, j, X, info) of the ACCEPTED records of find_closures, find_closures_by_appearance or find_closures_coarse: record q is the
+    registration of live scan ``live_nodes[q]`` (node j) against the keyframe in its ``slot`` (node i = ``node_of_slot[slot]``, a dict or a sequence).  A
+    record whose two ends are the same node is left out."""
+    edges = []
+    for q, r in enumerate(records):
+        if r["slot"] is None or not r["accepted"]:
+            continue
+        i, j = int(node_of_slot[r["slot"]]), int(live_nodes[q])
+        if i != j:
+            edges.append((i, j, np.asarray(r["X"], np.float32).copy(), info_from_cov(r["cov"])))
+    return edges
 
 
 # The recommended start offsets of a query by appearance (INTEGRATION "Loop closure without poses"): the search gives the yaw, not the translation, so
@@ -230,6 +252,7 @@ def load_library():
     L.icet_keyframe_store_close_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.POINTER(ClosureQuery), C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_pose_step_from_x.argtypes = [C.c_void_p, C.c_void_p]; L.icet_pose_step_from_x.restype = None
+    L.icet_debug_block_tridiag.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     L.icet_keyframe_store_enable_appearance.argtypes = [C.c_void_p, C.POINTER(AppearanceParams)]
     L.icet_keyframe_store_describe_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_set_stamp.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
@@ -534,6 +557,15 @@ class Context:
         B = _dev_scans(scan2_descs)
         self._check(load_library().icet_debug_gn_terms_device(self._h, C.byref(params), k, idx.ctypes.data, B, C.c_void_p(d_X_ptr), C.c_void_p(d_sums_ptr),
                                                               C.c_void_p(d_xf_ptr), C.c_void_p(d_htwh_ptr), C.c_void_p(d_htwdz_ptr), C.c_void_p(d_out_ptr)))
+
+    def debug_block_tridiag(self, diag, sub, rhs):
+        """icet_debug_block_tridiag: x of the block-tridiagonal system (diag n x 6 x 6, sub n x 6 x 6 with sub[k] at (k, k - 1), rhs n x 6; doubles) through the
+        device's block Cholesky factorisation and sweeps, and the status word (0: solved)."""
+        D = np.ascontiguousarray(np.asarray(diag, np.float64).reshape(-1, 36)); n = D.shape[0]
+        B = np.ascontiguousarray(np.asarray(sub, np.float64).reshape(n, 36)); r = np.ascontiguousarray(np.asarray(rhs, np.float64).reshape(n, 6))
+        x = np.zeros((n, 6), np.float64); st = C.c_int32(-1)
+        self._check(load_library().icet_debug_block_tridiag(self._h, n, D.ctypes.data, B.ctypes.data, r.ctypes.data, x.ctypes.data, C.byref(st)))
+        return x, int(st.value)
 
     def debug_fix(self, values):
         """icet_debug_fix (test hook): n floats through the point pass's float -> 2^36 fixed-point conversions -> (n, 3) uint64 = to_fix_biased (defined for

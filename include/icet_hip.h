@@ -589,6 +589,15 @@ icet_status icet_debug_gn_terms_device(icet_ctx* ctx, const icet_params* p, int3
  * the two-instruction biased form (defined for |v| < 2^15) | the wide biased form | the unbiased form that selects between them per value. */
 icet_status icet_debug_fix(icet_ctx* ctx, const float* v, int32_t n, uint64_t* out);
 
+/* --- towards pose-graph optimisation: the block-tridiagonal solve ---------------------------------------------------------
+ * The odometry chain of a pose graph makes its normal equations block tridiagonal (6 x 6 blocks).  The optimiser itself is not built; this is its solver.
+ * Test hook: ONE symmetric positive definite block-tridiagonal system through the block Cholesky factorisation and the two sweeps, in double, one workgroup.
+ * HOST arrays of doubles: diag n x 36, sub n x 36 (sub[k]: the block at (k, k - 1); sub[0] zero), rhs and x n x 6; *status 0, or ICET_BAND_NOT_POSITIVE_DEFINITE
+ * (a pivot at or below 1e-13 of its diagonal entry) / ICET_BAND_NON_FINITE (a NaN or infinite pivot): x is then rhs.  1 <= n <= 4096.  Synchronises. */
+#define ICET_BAND_NOT_POSITIVE_DEFINITE 2
+#define ICET_BAND_NON_FINITE 3
+icet_status icet_debug_block_tridiag(icet_ctx* ctx, int32_t n, const double* diag, const double* sub, const double* rhs, double* x, int32_t* status);
+
 /* Launch-shape and diagnostic knobs of ONE context (the library never reads the environment).  Defaults are the measured
  * optima.  Launch-shape knobs yield the same result bits; "force_exact", "guard_scale" and "lut_polar_quantile" preserve every
  * DECISION (the per-voxel counts n2_raw / n2_in) but move points between the 4-point runs and the runs of one, i.e. they regroup
