@@ -9,6 +9,8 @@
 //   k_map_add_scan                                    EigenQueue::add_new_scan: the down-sampled rows enter the ring and
 //                                                    the whole ring is re-expressed as (row - t) * R^-1 in ONE pass
 //                                                    (12 B read + 12 B written per ring row)
+// Each row pass is stated once, as a __device__ body; the kernels above and the node group's k_group_* (second half of this file) are its two launch forms.  What a
+// stream keeps between frames (StreamState) and the host rules on it are stated once as well, for icet_node and icet_node_group alike.
 // Host-side scalar work (pose chaining, quaternion, the 3x3 inverse, std::shuffle of the index vector) stays on the
 // host as in the reference: it is O(1) or inherently sequential (Fisher-Yates with one RNG stream).
 // No CPU implementation of the solve lives here; without a device every entry point fails with an error status.
@@ -55,26 +57,26 @@ __device__ __forceinline__ bool keep_row(float x, float y, float z, float min_ra
     return d > min_range;
 }
 
-// pass 1: kept rows per block
-__global__ __launch_bounds__(kFB) void k_range_count(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n,
-                                                    float min_range, int32_t* __restrict__ counts, const FrameDesc* __restrict__ fd = nullptr) {
+// ---- the row passes.  Each has ONE body (__forceinline__); the node's kernel and the group's find their pointers, their row base and their keep_all and call it ----
+
+// pass 1: kept rows of the block that owns rows [base, base + kFB * kFRows), thread 0 stores the count
+__device__ __forceinline__ void count_block(const float* x, const float* y, const float* z, int n, int base, bool keep_all, float min_range, int32_t* count) {
     __shared__ int wsum[kFB / 64];
-    if (fd) { const FrameDesc d = *fd; x = d.x; y = d.x + d.ld; z = d.x + 2 * (size_t)d.ld; n = d.n; }
-    const int base = blockIdx.x * kFB * kFRows;
     int c = 0;
 #pragma unroll
     for (int k = 0; k < kFRows; k++) {
         const int i = base + k * kFB + threadIdx.x;
-        if (i < n) c += keep_row(x[i], y[i], z[i], min_range) ? 1 : 0;
+        if (i < n) c += (keep_all || keep_row(x[i], y[i], z[i], min_range)) ? 1 : 0;
     }
     for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < kFB / 64; w++) t += wsum[w]; counts[blockIdx.x] = t; }
+    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < kFB / 64; w++) t += wsum[w]; *count = t; }
 }
 
-// pass 2: exclusive scan of the block counts (one block; at most a few thousand entries), total -> n_kept
-__global__ __launch_bounds__(kFB) void k_range_scan(const int32_t* __restrict__ counts, int32_t* __restrict__ bases, int n_blocks, int32_t* __restrict__ n_kept, int32_t* __restrict__ n_kept_copy = nullptr) {
+// pass 2: exclusive scan of n_blocks block counts by one block (at most a few thousand entries); the total goes to *total and, where there is one, to its copy in
+// pinned host memory (a host thread may be watching it: the store is followed by a system-scope fence)
+__device__ __forceinline__ void scan_block_counts(const int32_t* counts, int32_t* bases, int n_blocks, int32_t* total, int32_t* total_copy) {
     __shared__ int part[kFB];
     const int per = (n_blocks + kFB - 1) / kFB;
     const int lo = threadIdx.x * per, hi = min(n_blocks, lo + per);
@@ -82,39 +84,97 @@ __global__ __launch_bounds__(kFB) void k_range_scan(const int32_t* __restrict__ 
     for (int i = lo; i < hi; i++) s += counts[i];
     part[threadIdx.x] = s;
     __syncthreads();
-    if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < kFB; t++) { const int v = part[t]; part[t] = run; run += v; } *n_kept = run; if (n_kept_copy) { *n_kept_copy = run; __threadfence_system(); } }      // (the copy lives in pinned host memory: a host thread may be watching it)
+    if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < kFB; t++) { const int v = part[t]; part[t] = run; run += v; } *total = run; if (total_copy) { *total_copy = run; __threadfence_system(); } }
     __syncthreads();
     int run = part[threadIdx.x];
     for (int i = lo; i < hi; i++) { bases[i] = run; run += counts[i]; }
 }
 
-// pass 3: stable scatter.  Row order inside a block is k-major (row = base + k * kFB + thread), so the rank of a kept
-// row is: kept rows in earlier k-slices + kept rows of lower threads in its own slice.
+// pass 3: stable scatter, in two halves.  Row order inside a block is k-major (row = base + k * kFB + thread), so the rank of a kept row is: kept rows in earlier
+// k-slices + kept rows of lower threads in its own slice.
+struct ScatterRows { float vx[kFRows], vy[kFRows], vz[kFRows]; bool keep[kFRows]; int below[kFRows]; };      // a thread's eight rows, in registers
+using ScatterCounts = int[kFRows][kFB / 64];                                                                   // kept rows by k-slice and wave, in LDS
+// ... first half: load, ballot and rank the eight k-slices (a barrier belongs between the halves)
+__device__ __forceinline__ void scatter_rank(const float* x, const float* y, const float* z, int n, int base, bool keep_all, float min_range, ScatterRows& r, ScatterCounts& wcnt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kFRows; k++) {
+        const int i = base + k * kFB + threadIdx.x;
+        r.keep[k] = false; r.vx[k] = r.vy[k] = r.vz[k] = 0.f;
+        if (i < n) { r.vx[k] = x[i]; r.vy[k] = y[i]; r.vz[k] = z[i]; r.keep[k] = keep_all || keep_row(r.vx[k], r.vy[k], r.vz[k], min_range); }
+        const unsigned long long m = __ballot(r.keep[k]);
+        r.below[k] = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wcnt[k][wave] = __popcll(m);
+    }
+}
+// ... second half: run = kept rows in front of this block; store the kept rows
+__device__ __forceinline__ void scatter_store(const ScatterRows& r, const ScatterCounts& wcnt, int run, float* ox, float* oy, float* oz) {
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kFRows; k++) {
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kFB / 64; w++) { const int cw = wcnt[k][w]; before += (w < wave) ? cw : 0; total += cw; }
+        if (r.keep[k]) { const int o = run + before + r.below[k]; ox[o] = r.vx[k]; oy[o] = r.vy[k]; oz[o] = r.vz[k]; }
+        run += total;
+    }
+}
+
+struct RowMove { float tx, ty, tz, i00, i01, i02, i10, i11, i12, i20, i21, i22; };      // a frame's translation and R^-1 (row-major), as the two passes below apply them
+inline RowMove row_move(const float* X, const float* Ri) { return RowMove{X[0], X[1], X[2], Ri[0], Ri[1], Ri[2], Ri[3], Ri[4], Ri[5], Ri[6], Ri[7], Ri[8]}; }
+
+// EigenQueue::add_new_scan (src/simpleMapMaker.cpp:34-41): rows [pos, pos + m) (mod cap) take the down-sampled scan
+// rows, then EVERY ring row becomes (row - trans) * Rinv.  One pass over the ring (a grid-stride loop in the kernels); this is ring row i.
+__device__ __forceinline__ void ring_add_scan_row(int i, float* qx, float* qy, float* qz, int cap, int pos, int m, const float* sx, const float* sy, const float* sz, const int32_t* idx, const RowMove& T) {
+    int j = i - pos; if (j < 0) j += cap;                 // position in this frame's write window
+    float a, b, c;
+    if (j < m) { const int r = idx[j]; a = sx[r]; b = sy[r]; c = sz[r]; }
+    else { a = qx[i]; b = qy[i]; c = qz[i]; }
+    a -= T.tx; b -= T.ty; c -= T.tz;
+    {
+#pragma clang fp contract(off)
+        qx[i] = (a * T.i00 + b * T.i10) + c * T.i20;
+        qy[i] = (a * T.i01 + b * T.i11) + c * T.i21;
+        qz[i] = (a * T.i02 + b * T.i12) + c * T.i22;
+    }
+}
+
+// scan2_in_scan1_frame = (pcl_matrix * rot_mat.inverse()).rowwise() - trans  (src/scanMatcher.cpp:76): rotate first, then subtract; this is row i
+__device__ __forceinline__ void align_row(int i, const float* sx, const float* sy, const float* sz, float* ox, float* oy, float* oz, const RowMove& T) {
+    const float a = sx[i], b = sy[i], c = sz[i];
+    {
+#pragma clang fp contract(off)
+        ox[i] = ((a * T.i00 + b * T.i10) + c * T.i20) - T.tx;
+        oy[i] = ((a * T.i01 + b * T.i11) + c * T.i21) - T.ty;
+        oz[i] = ((a * T.i02 + b * T.i12) + c * T.i22) - T.tz;
+    }
+}
+
+// ---- the node's launch form: pointers in the arguments, or in a pinned FrameDesc where the launch is part of a captured graph; every row goes through keep_row ----
+__global__ __launch_bounds__(kFB) void k_range_count(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n,
+                                                    float min_range, int32_t* __restrict__ counts, const FrameDesc* __restrict__ fd = nullptr) {
+    if (fd) { const FrameDesc d = *fd; x = d.x; y = d.x + d.ld; z = d.x + 2 * (size_t)d.ld; n = d.n; }
+    count_block(x, y, z, n, blockIdx.x * kFB * kFRows, false, min_range, counts + blockIdx.x);
+}
+
+__global__ __launch_bounds__(kFB) void k_range_scan(const int32_t* __restrict__ counts, int32_t* __restrict__ bases, int n_blocks, int32_t* __restrict__ n_kept, int32_t* __restrict__ n_kept_copy = nullptr) {
+    scan_block_counts(counts, bases, n_blocks, n_kept, n_kept_copy);
+}
+
 __global__ __launch_bounds__(kFB) void k_range_scatter(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n,
                                                       float min_range, const int32_t* __restrict__ bases,
                                                       float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz, const FrameDesc* __restrict__ fd = nullptr,
                                                       const int32_t* __restrict__ counts = nullptr, int n_blocks = 0, int32_t* __restrict__ n_kept = nullptr, int32_t* __restrict__ n_kept_copy = nullptr) {
-    __shared__ int wcnt[kFRows][kFB / 64];
+    __shared__ ScatterCounts wcnt;
     __shared__ int s_part[kFB / 64], s_tot[kFB / 64];
     if (fd) { const FrameDesc d = *fd; x = d.x; y = d.x + d.ld; z = d.x + 2 * (size_t)d.ld; n = d.n; }
     // counts: pass 2 folded in (a one-launch frame, at most a few hundred blocks): every block adds up the counts of the blocks in front of it itself, block 0 also the
     // total -- k_range_scan's 4.6 us launch is what the frame saves
     int part = 0, tot = 0;
     if (counts) for (int i = threadIdx.x; i < n_blocks; i += kFB) { const int c = counts[i]; tot += c; part += (i < (int)blockIdx.x) ? c : 0; }
-    const int base = blockIdx.x * kFB * kFRows;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float vx[kFRows], vy[kFRows], vz[kFRows];
-    bool keep[kFRows];
-    int below[kFRows];
-#pragma unroll
-    for (int k = 0; k < kFRows; k++) {
-        const int i = base + k * kFB + threadIdx.x;
-        keep[k] = false; vx[k] = vy[k] = vz[k] = 0.f;
-        if (i < n) { vx[k] = x[i]; vy[k] = y[i]; vz[k] = z[i]; keep[k] = keep_row(vx[k], vy[k], vz[k], min_range); }
-        const unsigned long long m = __ballot(keep[k]);
-        below[k] = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wcnt[k][wave] = __popcll(m);
-    }
+    ScatterRows r;
+    scatter_rank(x, y, z, n, blockIdx.x * kFB * kFRows, false, min_range, r, wcnt);
     if (counts) {
         for (int o = 32; o > 0; o >>= 1) { part += __shfl_down(part, o); tot += __shfl_down(tot, o); }
         if (lane == 0) { s_part[wave] = part; s_tot[wave] = tot; }
@@ -127,50 +187,22 @@ __global__ __launch_bounds__(kFB) void k_range_scatter(const float* __restrict__
         for (int w = 0; w < kFB / 64; w++) { run += s_part[w]; t += s_tot[w]; }
         if (blockIdx.x == 0 && threadIdx.x == 0) { *n_kept = t; if (n_kept_copy) { *n_kept_copy = t; __threadfence_system(); } }
     } else run = bases[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kFRows; k++) {
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kFB / 64; w++) { const int cw = wcnt[k][w]; before += (w < wave) ? cw : 0; total += cw; }
-        if (keep[k]) { const int o = run + before + below[k]; ox[o] = vx[k]; oy[o] = vy[k]; oz[o] = vz[k]; }
-        run += total;
-    }
+    scatter_store(r, wcnt, run, ox, oy, oz);
 }
 
-// EigenQueue::add_new_scan (src/simpleMapMaker.cpp:34-41): rows [pos, pos + m) (mod cap) take the down-sampled scan
-// rows, then EVERY ring row becomes (row - trans) * Rinv.  One pass over the ring.
 __global__ __launch_bounds__(256) void k_map_add_scan(float* __restrict__ qx, float* __restrict__ qy, float* __restrict__ qz, int cap, int pos, int m,
                                                      const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz,
                                                      const int32_t* __restrict__ idx, float tx, float ty, float tz,
                                                      float i00, float i01, float i02, float i10, float i11, float i12, float i20, float i21, float i22) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += gridDim.x * blockDim.x) {
-        int j = i - pos; if (j < 0) j += cap;             // position in this frame's write window
-        float a, b, c;
-        if (j < m) { const int r = idx[j]; a = sx[r]; b = sy[r]; c = sz[r]; }
-        else { a = qx[i]; b = qy[i]; c = qz[i]; }
-        a -= tx; b -= ty; c -= tz;
-        {
-#pragma clang fp contract(off)
-            qx[i] = (a * i00 + b * i10) + c * i20;
-            qy[i] = (a * i01 + b * i11) + c * i21;
-            qz[i] = (a * i02 + b * i12) + c * i22;
-        }
-    }
+    const RowMove T{tx, ty, tz, i00, i01, i02, i10, i11, i12, i20, i21, i22};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += gridDim.x * blockDim.x) ring_add_scan_row(i, qx, qy, qz, cap, pos, m, sx, sy, sz, idx, T);
 }
 
-// scan2_in_scan1_frame = (pcl_matrix * rot_mat.inverse()).rowwise() - trans  (src/scanMatcher.cpp:76): rotate first, then subtract
 __global__ __launch_bounds__(256) void k_align_cloud(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n,
                                                     float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz, float tx, float ty, float tz,
                                                     float i00, float i01, float i02, float i10, float i11, float i12, float i20, float i21, float i22) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float a = sx[i], b = sy[i], c = sz[i];
-        {
-#pragma clang fp contract(off)
-            ox[i] = ((a * i00 + b * i10) + c * i20) - tx;
-            oy[i] = ((a * i01 + b * i11) + c * i21) - ty;
-            oz[i] = ((a * i02 + b * i12) + c * i22) - tz;
-        }
-    }
+    const RowMove T{tx, ty, tz, i00, i01, i02, i10, i11, i12, i20, i21, i22};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) align_row(i, sx, sy, sz, ox, oy, oz, T);
 }
 
 // getQueue (src/simpleMapMaker.cpp:43-50): oldest row first
@@ -239,6 +271,210 @@ void icet_ctx_set_stream(icet_ctx* c, hipStream_t s);      // icet_capi.hip (int
 void icet_ctx_set_prologue(icet_ctx* c, hipError_t (*fn)(void*, hipStream_t), void* user, int64_t key);      // icet_capi.hip (internal)
 void icet_ctx_set_done_flag(icet_ctx* c, int32_t* pinned_word);      // icet_capi.hip (internal)
 
+// ==================================================================================================================================================================
+// What a stream keeps between frames, and the host rules on top of it: ONE statement of each, used by icet_node (which embeds one StreamState) and by icet_node_group
+// (a vector of them).  The helpers that report a HIP failure take the node or the group itself: anything with an `err` (and, for the copies out, a `stream`, a `device`
+// and the parameters `p`).
+// ==================================================================================================================================================================
+namespace {
+
+struct StreamState {
+    bool initialized = false;
+    // previous / current filtered scan (column-major, ld = cap rounded to 64)
+    float* d_scan[2] = {nullptr, nullptr}; int64_t cap_scan[2] = {0, 0}; int64_t n_scan[2] = {0, 0}; int64_t ld_scan[2] = {0, 0};
+    int prev = 0;
+    float X0[6] = {0, 0, 0, 0, 0, 0};
+    float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::mt19937 gen;                                              // default seed: simpleMapMaker.cpp:258 (one generator per stream)
+    icet_shuffle::FastMt fgen;                                     // the same stream written out (icet_shuffle.h); used when it reproduced std::shuffle on this C++ library at creation
+    std::vector<std::size_t> indices;
+    float* d_map = nullptr; int64_t map_pos = 0; bool map_filled = false;
+    int32_t* h_idx = nullptr;                                     // pinned: the frame's down-sample indices (the map kernel can read them in place)
+    float* d_aligned = nullptr; int64_t cap_aligned = 0, n_aligned = 0, ld_aligned = 0;     // scanMatcher.cpp:76
+    std::vector<float> snail;                                                               // scanMatcher.cpp:27-28,79-84: rows x 3 row-major, host
+};
+
+#define NCHK(o, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    (o)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
+
+bool node_params_ok(const icet_ctx* ctx, const icet_node_params* p) {
+    return ctx && p && p->map_capacity >= 0 && p->map_downsample >= 0 && !(p->map_capacity > 0 && p->map_downsample > p->map_capacity) &&
+           p->solve.bins_phi > 0 && p->solve.bins_theta > 0 && p->solve.n >= 1 && p->solve.runlen >= 0;
+}
+
+// (a few milliseconds, once per process: the written-out generator against this C++ library's std::shuffle)
+bool fast_shuffle_ok() { static const bool ok = icet_shuffle::matches_std_shuffle() && icet_shuffle::fast_matches_std_shuffle(); return ok; }
+
+// The map ring (zeroed: Eigen leaves MatrixXf(maxSize, 3) uninitialised; unfilled rows are never returned by getQueue), its pinned index buffer, the snail trail's first row
+icet_status stream_create(const icet_node_params& p, StreamState& st) {
+    if (p.map_capacity > 0) {
+        if (hipMalloc(reinterpret_cast<void**>(&st.d_map), sizeof(float) * 3 * (size_t)p.map_capacity) != hipSuccess) return ICET_ERR_NOMEM;
+        if (hipMemset(st.d_map, 0, sizeof(float) * 3 * (size_t)p.map_capacity) != hipSuccess) return ICET_ERR_HIP;
+        if (hipHostMalloc(reinterpret_cast<void**>(&st.h_idx), sizeof(int32_t) * (size_t)std::max(p.map_downsample, 1)) != hipSuccess) return ICET_ERR_NOMEM;
+    }
+    if (p.flags & ICET_NODE_SNAIL_TRAIL) st.snail.assign(3, 0.f);      // scanMatcher.cpp:27-28: one row at the origin
+    return ICET_OK;
+}
+void stream_destroy(StreamState& st) {
+    void* dp[] = {st.d_scan[0], st.d_scan[1], st.d_map, st.d_aligned};
+    for (void* q : dp) if (q) (void)hipFree(q);
+    if (st.h_idx) (void)hipHostFree(st.h_idx);
+}
+
+// No exception may cross the C ABI (std::async and the draw pool can throw std::system_error, the shuffle's vector bad_alloc): f's status, or the exception as one
+template <class F> icet_status no_throw(std::string& err, F&& f) {
+    try { return f(); }
+    catch (const std::bad_alloc&) { err = "out of host memory"; }
+    catch (const std::exception& e) { err = std::string("host error: ") + e.what(); }
+    catch (...) { err = "host error"; }
+    return ICET_ERR_NOMEM;
+}
+
+// A kernel stores into pinned host memory and this thread watches the word(s): hipStreamSynchronize answers several microseconds after the queue has drained, so the
+// stream is asked only every mask + 1 looks (a frame that failed never stores: then the stream says so), and once more, synchronised, before `what` is given up for lost.
+template <class O, class P> icet_status wait_pinned(O* o, P&& arrived, hipStream_t st, long mask, const char* what) {
+    for (long spins = 1; !arrived(); spins++)
+        if ((spins & mask) == 0 && hipStreamQuery(st) != hipErrorNotReady) break;      // (finished or failed without the store: decided below)
+    (void)hipGetLastError();
+    if (!arrived()) NCHK(o, hipStreamSynchronize(st));
+    if (!arrived()) { o->err = what; return ICET_ERR_HIP; }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return ICET_OK;
+}
+
+// A scan-sized buffer: (n + n / 8) rows rounded to 64.  drain() makes sure that nothing on the device still reads the old one.
+template <class O, class D> icet_status grow_rows(O* o, float*& buf, int64_t& cap, int64_t n, D&& drain) {
+    if (n <= cap) return ICET_OK;
+    NCHK(o, drain());
+    if (buf) { NCHK(o, hipFree(buf)); buf = nullptr; cap = 0; }
+    const int64_t c = (n + n / 8 + 63) / 64 * 64;
+    NCHK(o, hipMalloc(reinterpret_cast<void**>(&buf), sizeof(float) * 3 * (size_t)c));
+    cap = c;
+    return ICET_OK;
+}
+// The range filter's block counts and their bases, n of each
+template <class O, class D> icet_status grow_blocks(O* o, int32_t*& counts, int32_t*& bases, int64_t& cap, int64_t n, D&& drain) {
+    if (n <= cap) return ICET_OK;
+    NCHK(o, drain());
+    if (counts) { NCHK(o, hipFree(counts)); counts = nullptr; }
+    if (bases) { NCHK(o, hipFree(bases)); bases = nullptr; }
+    cap = 0;
+    NCHK(o, hipMalloc(reinterpret_cast<void**>(&counts), sizeof(int32_t) * (size_t)n));
+    NCHK(o, hipMalloc(reinterpret_cast<void**>(&bases), sizeof(int32_t) * (size_t)n));
+    cap = n;
+    return ICET_OK;
+}
+
+// The frame's down-sample indices into pinned h_idx (simpleMapMaker.cpp:147-158: iota, std::shuffle with the stream's generator, the first map_downsample entries): returns
+// how many.  Only the first entries of the shuffled vector are ever used, so only they are tracked while the generator makes its n - 1 draws (icet_shuffle.h).
+int draw_downsample(StreamState& st, bool fast, int32_t map_downsample, int64_t nk) {
+    if (fast) icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)map_downsample, st.fgen, st.indices);
+    else icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)map_downsample, st.gen, st.indices);
+    const int m = (int)st.indices.size();
+    for (int i = 0; i < m; i++) st.h_idx[i] = (int32_t)st.indices[i];
+    return m;
+}
+
+int64_t map_rows(const icet_node_params& p, const StreamState& st) { return st.map_filled ? p.map_capacity : st.map_pos; }
+
+// A stream's first cloud is stored as it is and nothing is solved (odometry.cpp:46-52): its result (res is zeroed)
+void first_result(const icet_node_params& p, const StreamState& st, int64_t n, icet_node_result* res) {
+    res->solved = 0; res->n_kept = n;
+    std::memcpy(res->pose, st.pose, sizeof(st.pose)); quat_of(st.pose, res->quat);
+    res->map_rows = map_rows(p, st);
+}
+
+// The host tail of a solved frame: X and pred_stds from the solve's 48 result floats,
+// X0 seeded for the next frame (odometry.cpp:82 / simpleMapMaker.cpp:124), the divergence guard (simpleMapMaker.cpp:129-137), the map ring's bookkeeping
+// (simpleMapMaker.cpp:147-158, 34-41), the snail trail (scanMatcher.cpp:79-84), the pose chain X_homo = X_homo * X_homo_i (odometry.cpp:91-98) and the result.
+// The device work in between is the caller's: map_dev(X, R^-1, ring position, rows) in front of the ring's bookkeeping, align_dev(X, R^-1) behind it; a failure
+// either returns ends the tail there (nothing behind it has changed).  One compiled body (noinline): the same bits whoever calls it.
+using TailMapDev = std::function<icet_status(const float* X, const float* Ri, int64_t pos, int m)>;
+using TailAlignDev = std::function<icet_status(const float* X, const float* Ri)>;
+__attribute__((noinline)) icet_status frame_tail(const icet_node_params& p, StreamState& st, const float* out48, int64_t nk, int m_map, icet_node_result* res,
+                                                 const TailMapDev& map_dev, const TailAlignDev& align_dev) {
+    float X[6];
+    std::memcpy(X, out48, sizeof(X)); std::memcpy(res->pred_stds, out48 + 6, sizeof(float) * 6);
+    // seed for the next frame (odometry.cpp:82 / simpleMapMaker.cpp:124), then the guard (simpleMapMaker.cpp:129-137)
+    for (int k = 0; k < 6; k++) st.X0[k] = p.seed_x0 ? X[k] : 0.f;
+    {
+        // each group is guarded only when ITS threshold is set (0 = off, include/icet_nodes.h): a caller who sets one of the two
+        // must not have the other group compared against 0
+        const float tt = p.trans_thresh, rt = p.rot_thresh;
+        if ((tt > 0.f && (std::fabs(X[0]) > tt || std::fabs(X[1]) > tt || std::fabs(X[2]) > tt)) ||
+            (rt > 0.f && (std::fabs(X[3]) > rt || std::fabs(X[4]) > rt || std::fabs(X[5]) > rt))) {
+            for (int k = 0; k < 6; k++) X[k] = 0.f;
+            res->diverged = 1;
+        }
+    }
+    float R[9]; euler_R_host(X[3], X[4], X[5], R);
+    float Ri[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (p.map_capacity > 0 || (p.flags & (ICET_NODE_ALIGNED_CLOUD | ICET_NODE_SNAIL_TRAIL))) inverse3_lu(R, Ri);
+    // ---- map queue (simpleMapMaker.cpp:147-158, 34-41) ----
+    if (p.map_capacity > 0) {
+        const int cap = p.map_capacity;
+        const icet_status ds = map_dev(X, Ri, st.map_pos, m_map); if (ds != ICET_OK) return ds;
+        if (st.map_pos + m_map >= cap) st.map_filled = true;
+        st.map_pos = (st.map_pos + m_map) % cap;
+    }
+    if (p.flags & ICET_NODE_ALIGNED_CLOUD) { const icet_status ds = align_dev(X, Ri); if (ds != ICET_OK) return ds; }
+    if (p.flags & ICET_NODE_SNAIL_TRAIL) {                        // snailTrail = (snailTrail * rot_mat.inverse()).rowwise() - trans; append the origin
+        std::vector<float>& sn = st.snail;
+        for (size_t i = 0; i + 2 < sn.size(); i += 3) {
+            const float a = sn[i], b = sn[i + 1], c = sn[i + 2];
+            sn[i] = ((a * Ri[0] + b * Ri[3]) + c * Ri[6]) - X[0];
+            sn[i + 1] = ((a * Ri[1] + b * Ri[4]) + c * Ri[7]) - X[1];
+            sn[i + 2] = ((a * Ri[2] + b * Ri[5]) + c * Ri[8]) - X[2];
+        }
+        sn.insert(sn.end(), {0.f, 0.f, 0.f});
+    }
+    // X_homo = X_homo * X_homo_i (odometry.cpp:91-98)
+    const float Hi[16] = {R[0], R[1], R[2], X[0], R[3], R[4], R[5], X[1], R[6], R[7], R[8], X[2], 0, 0, 0, 1};
+    float P[16];
+    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { float acc = 0.f; for (int k = 0; k < 4; k++) acc += st.pose[r * 4 + k] * Hi[k * 4 + c]; P[r * 4 + c] = acc; }
+    std::memcpy(st.pose, P, sizeof(P));
+    res->solved = 1; res->n_kept = nk;
+    std::memcpy(res->X, X, sizeof(X)); std::memcpy(res->pose, P, sizeof(P)); quat_of(P, res->quat);
+    res->map_rows = map_rows(p, st);
+    return ICET_OK;
+}
+
+// ---- what the accessors return: rows x 3 into out (column-major, ld) ----
+enum StreamRows { kRowsMap, kRowsPrevScan, kRowsAligned, kRowsSnail };
+// The two surfaces differ in one thing: icet_node_* reports the row count and THEN refuses an `ld` below it, icet_node_group_* refuses before it writes anything.
+template <class O> icet_status stream_rows_out(O* o, const StreamState& st, StreamRows what, bool refuse_first, float* out, int64_t ld, int64_t* rows_out) {
+    const int64_t rows = what == kRowsMap ? map_rows(o->p, st) : what == kRowsPrevScan ? (st.initialized ? st.n_scan[st.prev] : 0) :
+                         what == kRowsAligned ? st.n_aligned : (int64_t)(st.snail.size() / 3);
+    if (refuse_first && out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
+    *rows_out = rows;
+    if (!out || rows == 0) return ICET_OK;
+    if (ld < rows) return ICET_ERR_BAD_ARG;
+    if (what == kRowsSnail) {
+        for (int64_t i = 0; i < rows; i++) { out[i] = st.snail[3 * i]; out[ld + i] = st.snail[3 * i + 1]; out[2 * ld + i] = st.snail[3 * i + 2]; }
+        return ICET_OK;
+    }
+    if (hipSetDevice(o->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
+    const float* src = what == kRowsPrevScan ? st.d_scan[st.prev] : st.d_aligned;
+    int64_t lds = what == kRowsPrevScan ? st.ld_scan[st.prev] : st.ld_aligned;
+    float* tmp = nullptr;
+    if (what == kRowsMap) {                                       // getQueue: the ring unrolled, oldest row first, through a temporary
+        NCHK(o, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(float) * 3 * (size_t)rows));
+        const int cap = o->p.map_capacity;
+        k_map_unroll<<<std::min((int)((rows + 255) / 256), 2048), 256, 0, o->stream>>>(st.d_map, st.d_map + cap, st.d_map + 2 * (size_t)cap, cap, (int)st.map_pos,
+                                                                                        st.map_filled ? 1 : 0, (int)rows, tmp, (int)rows);
+        src = tmp; lds = rows;
+    }
+    hipError_t e = tmp ? hipGetLastError() : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy2DAsync(out, ld * sizeof(float), src, lds * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, o->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(o->stream);
+    if (tmp) (void)hipFree(tmp);
+    if (e != hipSuccess) { o->err = hipGetErrorString(e); return ICET_ERR_HIP; }
+    return ICET_OK;
+}
+
+}  // namespace
+
 // The helper thread of a pipelined node: it ENQUEUES the keyframe builds (icet_keyframe_device_n on the context the build goes into, then the event that says it is
 // done) while the calling thread enqueues the frame's loop.  A build is ~20 launches or one graph launch of 20 nodes -- 35 to 140 us of host time that used to sit between
 // the loop's launch and the build's start, so that the build of frame k ran into frame k + 1, whose loop needs it.  One job at a time in order; the calling thread waits
@@ -263,23 +499,13 @@ struct icet_node {
     int device = 0;
     icet_node_params p{};
     std::string err;
-    bool initialized = false;
-    // previous / current filtered scan (column-major, ld = cap rounded to 64)
-    float* d_scan[2] = {nullptr, nullptr}; int64_t cap_scan[2] = {0, 0}; int64_t n_scan[2] = {0, 0}; int64_t ld_scan[2] = {0, 0};
-    int prev = 0;
+    StreamState s;                                                // what the stream keeps between frames
     float* d_stage = nullptr; int64_t cap_stage = 0;              // host scans land here first
-    int32_t* d_counts = nullptr; int32_t* d_bases = nullptr; int cap_blocks = 0;
+    int32_t* d_counts = nullptr; int32_t* d_bases = nullptr; int64_t cap_blocks = 0;
     int32_t* d_nkept = nullptr; int32_t* h_nkept = nullptr;       // d_nkept: TWO counters, one per scan buffer (a frame's count is still read by the keyframe build that runs into the next frame)
     float* d_x0 = nullptr; float* d_out = nullptr; float* h_out = nullptr; float* h_x0 = nullptr;
-    float X0[6] = {0, 0, 0, 0, 0, 0};
-    float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    std::mt19937 gen;                                              // default seed: simpleMapMaker.cpp:258
-    icet_shuffle::FastMt fgen; bool fast_shuffle = false;         // the same stream written out (icet_shuffle.h); used when it reproduced std::shuffle on this C++ library at creation
-    std::vector<std::size_t> indices;
-    float* d_map = nullptr; int64_t map_pos = 0; bool map_filled = false;
-    int32_t* d_idx = nullptr; int32_t* h_idx = nullptr;
-    float* d_aligned = nullptr; int64_t cap_aligned = 0, n_aligned = 0, ld_aligned = 0;     // scanMatcher.cpp:76
-    std::vector<float> snail;                                                               // scanMatcher.cpp:27-28,79-84: rows x 3 row-major, host
+    bool fast_shuffle = false;                                    // fast_shuffle_ok() at creation
+    int32_t* d_idx = nullptr;                                     // the down-sample indices on the device (the frame in phases copies s.h_idx here)
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // [5]: start of the loop on the owner's stream (pipelined)
     bool timing_valid = false, timed_map = false;
     KfWorker* kw = nullptr;                                       // started with the first build that goes through it
@@ -289,7 +515,7 @@ struct icet_node {
     FrameDesc* h_frame = nullptr;                                 // pinned, [2]: by scan buffer
     FilterLaunch fl[2];
     float* d_scan_kf[2] = {nullptr, nullptr}; int64_t cap_scan_kf[2] = {0, 0};
-    int32_t* d_counts_kf = nullptr; int32_t* d_bases_kf = nullptr; int cap_blocks_kf = 0; int32_t* d_nkept_kf = nullptr;
+    int32_t* d_counts_kf = nullptr; int32_t* d_bases_kf = nullptr; int64_t cap_blocks_kf = 0; int32_t* d_nkept_kf = nullptr;
     hipEvent_t ev_f2 = nullptr;                                   // the keyframe side's filter has read the caller's frame
     int32_t* h_done = nullptr;                                    // pinned, coherent: the frame's last solve stores 1 here behind its results (the host watches it instead of synchronising the stream)
 #ifdef ICET_DIAG_ENV
@@ -298,10 +524,6 @@ struct icet_node {
 };
 
 namespace {
-
-#define NCHK(nd, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    (nd)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
 
 bool kf_worker_start(icet_node* nd) {
     if (nd->kw) return true;
@@ -348,84 +570,6 @@ void kf_worker_stop(icet_node* nd) {
     delete nd->kw; nd->kw = nullptr;
 }
 
-icet_status ensure_scan(icet_node* nd, int which, int64_t n) {
-    if (n <= nd->cap_scan[which]) return ICET_OK;
-    NCHK(nd, hipDeviceSynchronize());                             // both streams of a pipelined node may still read the buffer
-    if (nd->d_scan[which]) { NCHK(nd, hipFree(nd->d_scan[which])); nd->d_scan[which] = nullptr; }
-    const int64_t cap = (n + n / 8 + 63) / 64 * 64;
-    NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_scan[which]), sizeof(float) * 3 * (size_t)cap));
-    nd->cap_scan[which] = cap;
-    return ICET_OK;
-}
-
-// The frame's down-sample indices into pinned h_idx (simpleMapMaker.cpp:147-158: iota, std::shuffle with the node's generator, the first map_downsample entries): returns
-// how many.  Only the first entries of the shuffled vector are ever used, so only they are tracked while the generator makes its n - 1 draws (icet_shuffle.h).
-// (a node group's streams draw the same way, each from its own generator)
-int draw_downsample_into(bool fast, icet_shuffle::FastMt& fgen, std::mt19937& gen, std::vector<std::size_t>& indices, int32_t map_downsample, int64_t nk, int32_t* h_idx) {
-    if (fast) icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)map_downsample, fgen, indices);
-    else icet_shuffle::head_of_shuffled_iota((std::size_t)nk, (std::size_t)map_downsample, gen, indices);
-    const int m = (int)indices.size();
-    for (int i = 0; i < m; i++) h_idx[i] = (int32_t)indices[i];
-    return m;
-}
-int draw_downsample(icet_node* nd, int64_t nk) { return draw_downsample_into(nd->fast_shuffle, nd->fgen, nd->gen, nd->indices, nd->p.map_downsample, nk, nd->h_idx); }
-
-// The host tail of a solved frame, shared by icet_node and icet_node_group so that the two cannot drift apart: X and pred_stds from the solve's 48 result floats,
-// X0 seeded for the next frame (odometry.cpp:82 / simpleMapMaker.cpp:124), the divergence guard (simpleMapMaker.cpp:129-137), the map ring's bookkeeping
-// (simpleMapMaker.cpp:147-158, 34-41), the snail trail (scanMatcher.cpp:79-84), the pose chain X_homo = X_homo * X_homo_i (odometry.cpp:91-98) and the result.
-// The device work in between is the caller's: map_dev(X, R^-1, ring position, rows) in front of the ring's bookkeeping, align_dev(X, R^-1) behind it; a failure
-// either returns ends the tail there (nothing behind it has changed).  One compiled body (noinline): the same bits whoever calls it.
-struct NodeTail { float* X0; float* pose; int64_t* map_pos; bool* map_filled; std::vector<float>* snail; };
-using TailMapDev = std::function<icet_status(const float* X, const float* Ri, int64_t pos, int m)>;
-using TailAlignDev = std::function<icet_status(const float* X, const float* Ri)>;
-__attribute__((noinline)) icet_status frame_tail(const icet_node_params& p, const NodeTail& st, const float* out48, int64_t nk, int m_map, icet_node_result* res,
-                                                 const TailMapDev& map_dev, const TailAlignDev& align_dev) {
-    float X[6];
-    std::memcpy(X, out48, sizeof(X)); std::memcpy(res->pred_stds, out48 + 6, sizeof(float) * 6);
-    // seed for the next frame (odometry.cpp:82 / simpleMapMaker.cpp:124), then the guard (simpleMapMaker.cpp:129-137)
-    for (int k = 0; k < 6; k++) st.X0[k] = p.seed_x0 ? X[k] : 0.f;
-    {
-        // each group is guarded only when ITS threshold is set (0 = off, include/icet_nodes.h): a caller who sets one of the two
-        // must not have the other group compared against 0
-        const float tt = p.trans_thresh, rt = p.rot_thresh;
-        if ((tt > 0.f && (std::fabs(X[0]) > tt || std::fabs(X[1]) > tt || std::fabs(X[2]) > tt)) ||
-            (rt > 0.f && (std::fabs(X[3]) > rt || std::fabs(X[4]) > rt || std::fabs(X[5]) > rt))) {
-            for (int k = 0; k < 6; k++) X[k] = 0.f;
-            res->diverged = 1;
-        }
-    }
-    float R[9]; euler_R_host(X[3], X[4], X[5], R);
-    float Ri[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (p.map_capacity > 0 || (p.flags & (ICET_NODE_ALIGNED_CLOUD | ICET_NODE_SNAIL_TRAIL))) inverse3_lu(R, Ri);
-    // ---- map queue (simpleMapMaker.cpp:147-158, 34-41) ----
-    if (p.map_capacity > 0) {
-        const int cap = p.map_capacity;
-        const icet_status ds = map_dev(X, Ri, *st.map_pos, m_map); if (ds != ICET_OK) return ds;
-        if (*st.map_pos + m_map >= cap) *st.map_filled = true;
-        *st.map_pos = (*st.map_pos + m_map) % cap;
-    }
-    if (p.flags & ICET_NODE_ALIGNED_CLOUD) { const icet_status ds = align_dev(X, Ri); if (ds != ICET_OK) return ds; }
-    if (p.flags & ICET_NODE_SNAIL_TRAIL) {                        // snailTrail = (snailTrail * rot_mat.inverse()).rowwise() - trans; append the origin
-        std::vector<float>& sn = *st.snail;
-        for (size_t i = 0; i + 2 < sn.size(); i += 3) {
-            const float a = sn[i], b = sn[i + 1], c = sn[i + 2];
-            sn[i] = ((a * Ri[0] + b * Ri[3]) + c * Ri[6]) - X[0];
-            sn[i + 1] = ((a * Ri[1] + b * Ri[4]) + c * Ri[7]) - X[1];
-            sn[i + 2] = ((a * Ri[2] + b * Ri[5]) + c * Ri[8]) - X[2];
-        }
-        sn.insert(sn.end(), {0.f, 0.f, 0.f});
-    }
-    // X_homo = X_homo * X_homo_i (odometry.cpp:91-98)
-    const float Hi[16] = {R[0], R[1], R[2], X[0], R[3], R[4], R[5], X[1], R[6], R[7], R[8], X[2], 0, 0, 0, 1};
-    float P[16];
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { float acc = 0.f; for (int k = 0; k < 4; k++) acc += st.pose[r * 4 + k] * Hi[k * 4 + c]; P[r * 4 + c] = acc; }
-    std::memcpy(st.pose, P, sizeof(P));
-    res->solved = 1; res->n_kept = nk;
-    std::memcpy(res->X, X, sizeof(X)); std::memcpy(res->pose, P, sizeof(P)); quat_of(P, res->quat);
-    res->map_rows = *st.map_filled ? p.map_capacity : *st.map_pos;
-    return ICET_OK;
-}
-
 // ---- the one-launch frame (round 6) ----
 hipError_t filter_prologue(void* user, hipStream_t st) {          // the hook icet_register_device_n runs in front of its loop (icet_ctx_set_prologue)
     const FilterLaunch& f = *static_cast<const FilterLaunch*>(user);
@@ -451,25 +595,11 @@ icet_status ensure_kf_side(icet_node* nd, int which, int64_t n) {
     if (!nd->d_nkept_kf) NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_nkept_kf), 2 * sizeof(int32_t)));
     if (!nd->ev_f2) NCHK(nd, hipEventCreateWithFlags(&nd->ev_f2, hipEventDisableTiming));
     if (!nd->h_done) { NCHK(nd, hipHostMalloc(reinterpret_cast<void**>(&nd->h_done), sizeof(int32_t), hipHostMallocCoherent)); *nd->h_done = 0; }
-    if (n > nd->cap_scan_kf[which]) {
-        NCHK(nd, hipDeviceSynchronize());
-        if (nd->d_scan_kf[which]) { NCHK(nd, hipFree(nd->d_scan_kf[which])); nd->d_scan_kf[which] = nullptr; }
-        const int64_t cap = (n + n / 8 + 63) / 64 * 64;
-        NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_scan_kf[which]), sizeof(float) * 3 * (size_t)cap));
-        nd->cap_scan_kf[which] = cap;
-    }
-    const int nbl = (int)((nd->cap_scan_kf[which] + kFB * kFRows - 1) / (kFB * kFRows));
-    if (nbl > nd->cap_blocks_kf) {
-        NCHK(nd, hipDeviceSynchronize());
-        if (nd->d_counts_kf) NCHK(nd, hipFree(nd->d_counts_kf));
-        if (nd->d_bases_kf) NCHK(nd, hipFree(nd->d_bases_kf));
-        nd->d_counts_kf = nd->d_bases_kf = nullptr;
-        NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_counts_kf), sizeof(int32_t) * nbl));
-        NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_bases_kf), sizeof(int32_t) * nbl));
-        nd->cap_blocks_kf = nbl;
-    }
-    return ICET_OK;
+    const icet_status s = grow_rows(nd, nd->d_scan_kf[which], nd->cap_scan_kf[which], n, hipDeviceSynchronize); if (s != ICET_OK) return s;
+    return grow_blocks(nd, nd->d_counts_kf, nd->d_bases_kf, nd->cap_blocks_kf, (nd->cap_scan_kf[which] + kFB * kFRows - 1) / (kFB * kFRows), hipDeviceSynchronize);
 }
+// a scan buffer of the node: both streams of a pipelined node may still read the old one
+icet_status ensure_scan(icet_node* nd, int which, int64_t n) { return grow_rows(nd, nd->s.d_scan[which], nd->s.cap_scan[which], n, hipDeviceSynchronize); }
 
 // One frame with the raw scan already in HBM (column-major, ld).
 icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld, icet_node_result* res) {
@@ -484,32 +614,30 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
     std::memset(res, 0, sizeof(*res));
     { const icet_status hs = kf_wait_idle(nd); if (hs != ICET_OK) return hs; }      // the previous frame's keyframe build has been enqueued (or says why not)
     hipStream_t st = nd->stream;
-    const int cur = nd->prev ^ 1;
+    const int cur = nd->s.prev ^ 1;
     nd->timing_valid = false;
-    if (!nd->initialized) {
+    if (!nd->s.initialized) {
         // odometry.cpp:46-52: the first cloud is stored as it is (no range filter) and nothing is solved
-        icet_status s = ensure_scan(nd, nd->prev, n); if (s != ICET_OK) return s;
-        const int64_t l = nd->cap_scan[nd->prev];
-        if (n) NCHK(nd, hipMemcpy2DAsync(nd->d_scan[nd->prev], l * sizeof(float), d_scan, ld * sizeof(float), n * sizeof(float), 3, hipMemcpyDeviceToDevice, st));
+        icet_status s = ensure_scan(nd, nd->s.prev, n); if (s != ICET_OK) return s;
+        const int64_t l = nd->s.cap_scan[nd->s.prev];
+        if (n) NCHK(nd, hipMemcpy2DAsync(nd->s.d_scan[nd->s.prev], l * sizeof(float), d_scan, ld * sizeof(float), n * sizeof(float), 3, hipMemcpyDeviceToDevice, st));
         NCHK(nd, hipStreamSynchronize(st));
-        nd->n_scan[nd->prev] = n; nd->ld_scan[nd->prev] = l;
+        nd->s.n_scan[nd->s.prev] = n; nd->s.ld_scan[nd->s.prev] = l;
         if (nd->pipelined) {
-            icet_dev_scan a{nd->d_scan[nd->prev], n, l};
+            icet_dev_scan a{nd->s.d_scan[nd->s.prev], n, l};
             icet_params sp = nd->p.solve; sp.flags = (nd->p.flags & ICET_NODE_DOUBLE_W) ? ICET_FLAG_DOUBLE_W : ICET_FLAG_NONE;
             nd->owner = 0;
             icet_status ks = icet_keyframe_device(nd->kf[0], &sp, 1, &a);
             if (ks != ICET_OK) { nd->err = icet_last_error(nd->kf[0]); return ks; }
             NCHK(nd, hipEventRecord(nd->ev_kfdone[0], reinterpret_cast<hipStream_t>(icet_stream(nd->kf[0])))); nd->kf_built[0] = true; nd->kf_built[1] = false;
         }
-        nd->initialized = true;
-        res->solved = 0; res->n_kept = n;
-        std::memcpy(res->pose, nd->pose, sizeof(nd->pose)); quat_of(nd->pose, res->quat);
-        res->map_rows = nd->map_filled ? nd->p.map_capacity : nd->map_pos;
+        nd->s.initialized = true;
+        first_result(nd->p, nd->s, n, res);
         return ICET_OK;
     }
     // ---- range filter: stable compaction into the "current" buffer (odometry.cpp:57-70) ----
     icet_status s = ensure_scan(nd, cur, n); if (s != ICET_OK) return s;
-    const int64_t lcur = nd->cap_scan[cur];
+    const int64_t lcur = nd->s.cap_scan[cur];
     // Whoever needs the kept-row count on the HOST before the solve can be enqueued (the map maker's shuffle runs over exactly that many
     // indices; the aligned cloud and the unpipelined solve are sized by it) waits for the filter here.  The pipelined odometry frame does
     // not: the solve's two halves take the unfiltered row count as an upper bound for their launch geometry and read the actual count on
@@ -530,28 +658,20 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
     const bool fused = (fast || map_ok) && loop_on_filter_stream && nd->p.solve.runlen > 0 && !(nd->p.flags & ICET_NODE_TIME_PHASES);
     const bool dev_count = fast || fused;                         // the solve's halves read the row count on the device
     const int n_blocks = fused ? (int)((lcur + kFB * kFRows - 1) / (kFB * kFRows)) : (int)((n + kFB * kFRows - 1) / (kFB * kFRows));      // fused: by CAPACITY (the launch does not change with n)
-    if (n_blocks > nd->cap_blocks) {
-        NCHK(nd, hipDeviceSynchronize());
-        if (nd->d_counts) NCHK(nd, hipFree(nd->d_counts));
-        if (nd->d_bases) NCHK(nd, hipFree(nd->d_bases));
-        nd->d_counts = nd->d_bases = nullptr;
-        NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_counts), sizeof(int32_t) * n_blocks));
-        NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_bases), sizeof(int32_t) * n_blocks));
-        nd->cap_blocks = n_blocks;
-    }
+    s = grow_blocks(nd, nd->d_counts, nd->d_bases, nd->cap_blocks, n_blocks, hipDeviceSynchronize); if (s != ICET_OK) return s;
     if (fused) { s = ensure_kf_side(nd, cur, n); if (s != ICET_OK) return s; }
     int32_t* d_cnt = nd->d_nkept + cur;
     if (!fused) NCHK(nd, hipEventRecord(nd->ev[0], st));         // (the one-launch frame records no timing events: each costs the host 5-10 us IN FRONT of the launch)
     if (nd->p.flags & ICET_NODE_NO_RANGE_FILTER) {               // scanMatcher.cpp:44: the cloud goes to the constructor as it is
-        if (n) NCHK(nd, hipMemcpy2DAsync(nd->d_scan[cur], lcur * sizeof(float), d_scan, ld * sizeof(float), n * sizeof(float), 3, hipMemcpyDeviceToDevice, st));
+        if (n) NCHK(nd, hipMemcpy2DAsync(nd->s.d_scan[cur], lcur * sizeof(float), d_scan, ld * sizeof(float), n * sizeof(float), 3, hipMemcpyDeviceToDevice, st));
         *nd->h_nkept = (int32_t)n;
     } else if (fused) {
         nd->h_frame[cur] = FrameDesc{d_scan, (int32_t)n, (int32_t)ld};                          // what both filters of this frame read
         *static_cast<volatile int32_t*>(nd->h_nkept) = -1;                                      // ("not yet": the map maker's host side watches this word)
-        nd->fl[cur] = FilterLaunch{nd->h_frame + cur, nd->p.min_range, nd->d_counts, nd->d_bases, n_blocks, d_cnt, nd->h_nkept, nd->d_scan[cur], lcur};
+        nd->fl[cur] = FilterLaunch{nd->h_frame + cur, nd->p.min_range, nd->d_counts, nd->d_bases, n_blocks, d_cnt, nd->h_nkept, nd->s.d_scan[cur], lcur};
     } else if (n > 0) {
         const float *x = d_scan, *y = d_scan + ld, *z = d_scan + 2 * ld;
-        float* o = nd->d_scan[cur];
+        float* o = nd->s.d_scan[cur];
         k_range_count<<<n_blocks, kFB, 0, st>>>(x, y, z, (int)n, nd->p.min_range, nd->d_counts);
         // the kept-row count goes to the host by the kernel's own store into pinned memory: a hipMemcpyAsync of four bytes costs the stream ~20 us on this part (round 5's
         // burst timeline), and the frame's other small copy -- the 48 result floats -- went the same way in round 6 (below)
@@ -567,7 +687,7 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
     // fast: an upper bound until the end-of-frame synchronisation -- the buffer's CAPACITY, which does not change from frame to frame, so that the
     // two halves of the solve see the same launch key every frame and replay their captured graphs (one hipGraphLaunch each instead of ~35 launches)
     int64_t nk = dev_count ? lcur : (int64_t)*nd->h_nkept;
-    nd->n_scan[cur] = nk; nd->ld_scan[cur] = lcur;
+    nd->s.n_scan[cur] = nk; nd->s.ld_scan[cur] = lcur;
     // ---- ICET it(prev, cur, runlen, X0, bins_phi, bins_theta, n, thresh, buff)  (odometry.cpp:76) ----
     // The down-sample indices of this frame (simpleMapMaker.cpp:147-158) depend only on the row count and on the node's RNG stream,
     // and Fisher-Yates over ~10^5 indices costs about as much host time as the solve costs device time: a helper thread shuffles
@@ -576,10 +696,10 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
     bool flip_owner = false;
     std::future<int> shuffle;
     if (nd->p.map_capacity > 0 && !fused) {
-        shuffle = std::async(std::launch::async, [nd, nk]() { return draw_downsample(nd, nk); });
+        shuffle = std::async(std::launch::async, [nd, nk]() { return draw_downsample(nd->s, nd->fast_shuffle, nd->p.map_downsample, nk); });
     }
-    std::memcpy(nd->h_x0, nd->X0, sizeof(nd->X0));
-    icet_dev_scan a{nd->d_scan[nd->prev], nd->n_scan[nd->prev], nd->ld_scan[nd->prev]}, b{nd->d_scan[cur], nk, lcur};
+    std::memcpy(nd->h_x0, nd->s.X0, sizeof(nd->s.X0));
+    icet_dev_scan a{nd->s.d_scan[nd->s.prev], nd->s.n_scan[nd->s.prev], nd->s.ld_scan[nd->s.prev]}, b{nd->s.d_scan[cur], nk, lcur};
     icet_params sp = nd->p.solve; sp.flags = (nd->p.flags & ICET_NODE_DOUBLE_W) ? ICET_FLAG_DOUBLE_W : ICET_FLAG_NONE;
     hipStream_t so = st;                                          // the stream the result arrives on
     if (nd->pipelined) {
@@ -641,7 +761,7 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
             if (s != ICET_OK) { nd->err = icet_last_error(oth); return s; }
             NCHK(nd, hipEventRecord(nd->ev_kfdone[nd->owner ^ 1], s_oth)); nd->kf_built[nd->owner ^ 1] = true;
         }
-        flip_owner = true;                                        // committed together with nd->prev once the frame has succeeded
+        flip_owner = true;                                        // committed together with nd->s.prev once the frame has succeeded
     } else {
         float* out_dev = sp.runlen > 0 ? nd->h_out : nd->d_out;
         s = icet_solve_batch_device(nd->ctx, &sp, 1, &a, &b, nd->h_x0, out_dev);
@@ -653,16 +773,13 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
         // the frame is in flight; its filter's count lands in pinned memory ~25 us in (k_range_scan's own store), the loop runs for another ~230: the down-sample
         // shuffle (simpleMapMaker.cpp:147-158: std::shuffle over exactly that many indices with the node's RNG stream) runs here, on this thread, beside it
         volatile int32_t* hc = nd->h_nkept;
-        for (long spins = 1; *hc < 0; spins++)
-            if ((spins & 4095) == 0 && hipStreamQuery(st) != hipErrorNotReady) break;             // (finished or failed without a count: decided below)
-        (void)hipGetLastError();
-        if (*hc < 0) NCHK(nd, hipStreamSynchronize(st));
-        if (*hc < 0) { nd->err = "the range filter's row count did not arrive"; if (nd->kw) (void)kf_wait_idle(nd); return ICET_ERR_HIP; }
-        m_map = draw_downsample(nd, (int64_t)*hc);                                                // into pinned h_idx: the map kernel reads it in place (no copy command)
+        s = wait_pinned(nd, [hc] { return *hc >= 0; }, st, 4095, "the range filter's row count did not arrive");
+        if (s != ICET_OK) { if (nd->kw) (void)kf_wait_idle(nd); return s; }
+        m_map = draw_downsample(nd->s, nd->fast_shuffle, nd->p.map_downsample, (int64_t)*hc);      // into pinned h_idx: the map kernel reads it in place (no copy command)
     }
     if (shuffle.valid()) {
         m_map = shuffle.get();
-        if (m_map) NCHK(nd, hipMemcpyAsync(nd->d_idx, nd->h_idx, sizeof(int32_t) * m_map, hipMemcpyHostToDevice, st));
+        if (m_map) NCHK(nd, hipMemcpyAsync(nd->d_idx, nd->s.h_idx, sizeof(int32_t) * m_map, hipMemcpyHostToDevice, st));
     }
     ICET_TR(3);
     if (so != st) NCHK(nd, hipStreamSynchronize(so));
@@ -670,28 +787,23 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
         // the frame's last kernel stores its 48 result floats and then a 1 into pinned host memory: this thread watches that word -- hipStreamSynchronize answers
         // several microseconds after the queue has drained -- and asks the stream only now and then (a frame that failed never writes the word)
         volatile int32_t* hd = nd->h_done;
-        for (long spins = 1; *hd == 0; spins++)
-            if ((spins & 8191) == 0 && hipStreamQuery(st) != hipErrorNotReady) break;
-        (void)hipGetLastError();
-        if (*hd == 0) NCHK(nd, hipStreamSynchronize(st));
-        if (*hd == 0) { nd->err = "the frame's result did not arrive"; if (nd->kw) (void)kf_wait_idle(nd); return ICET_ERR_HIP; }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        s = wait_pinned(nd, [hd] { return *hd != 0; }, st, 8191, "the frame's result did not arrive");
+        if (s != ICET_OK) { if (nd->kw) (void)kf_wait_idle(nd); return s; }
     } else NCHK(nd, hipStreamSynchronize(st));
     ICET_TR(4);
     if (fused) {                                                  // the caller's frame may be released when this returns: the other stream's filter has read it (long done: it started beside this stream's)
         const icet_status hs = kf_wait_idle(nd); if (hs != ICET_OK) return hs;      // (the helper has recorded the event)
         NCHK(nd, hipEventSynchronize(nd->ev_f2));
     }
-    if (dev_count) { nk = *nd->h_nkept; nd->n_scan[cur] = nk; }   // the filter's count has arrived with everything else
+    if (dev_count) { nk = *nd->h_nkept; nd->s.n_scan[cur] = nk; }   // the filter's count has arrived with everything else
     // ---- the tail (frame_tail): guard, map queue, aligned cloud, snail trail, pose ----
     nd->timed_map = false;
-    const NodeTail tail{nd->X0, nd->pose, &nd->map_pos, &nd->map_filled, &nd->snail};
     auto map_dev = [&](const float* X, const float* Ri, int64_t pos, int m) -> icet_status {
         const int cap = nd->p.map_capacity;
-        float* q = nd->d_map; const float* sc = nd->d_scan[cur];
+        float* q = nd->s.d_map; const float* sc = nd->s.d_scan[cur];
         const int blocks = std::min((cap + 255) / 256, 256 * 8);
         if (!fused) NCHK(nd, hipEventRecord(nd->ev[4], st));
-        k_map_add_scan<<<blocks, 256, 0, st>>>(q, q + cap, q + 2 * (size_t)cap, cap, (int)pos, m, sc, sc + lcur, sc + 2 * lcur, fused ? nd->h_idx : nd->d_idx,
+        k_map_add_scan<<<blocks, 256, 0, st>>>(q, q + cap, q + 2 * (size_t)cap, cap, (int)pos, m, sc, sc + lcur, sc + 2 * lcur, fused ? nd->s.h_idx : nd->d_idx,
                                                X[0], X[1], X[2], Ri[0], Ri[1], Ri[2], Ri[3], Ri[4], Ri[5], Ri[6], Ri[7], Ri[8]);
         NCHK(nd, hipGetLastError());
         if (!fused) NCHK(nd, hipEventRecord(nd->ev[3], st));      // not waited for: the next push (or icet_node_map) synchronises the stream
@@ -699,22 +811,22 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
         return ICET_OK;
     };
     auto align_dev = [&](const float* X, const float* Ri) -> icet_status {
-        if (lcur > nd->cap_aligned) {
+        if (lcur > nd->s.cap_aligned) {
             NCHK(nd, hipStreamSynchronize(st));
-            if (nd->d_aligned) { NCHK(nd, hipFree(nd->d_aligned)); nd->d_aligned = nullptr; }
-            NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_aligned), sizeof(float) * 3 * (size_t)lcur));
-            nd->cap_aligned = lcur;
+            if (nd->s.d_aligned) { NCHK(nd, hipFree(nd->s.d_aligned)); nd->s.d_aligned = nullptr; }
+            NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->s.d_aligned), sizeof(float) * 3 * (size_t)lcur));
+            nd->s.cap_aligned = lcur;
         }
-        const float* sc = nd->d_scan[cur]; float* o = nd->d_aligned; const int64_t la = nd->cap_aligned;
+        const float* sc = nd->s.d_scan[cur]; float* o = nd->s.d_aligned; const int64_t la = nd->s.cap_aligned;
         if (nk) k_align_cloud<<<(int)std::min<int64_t>((nk + 255) / 256, 2048), 256, 0, st>>>(sc, sc + lcur, sc + 2 * lcur, (int)nk, o, o + la, o + 2 * la, X[0], X[1], X[2],
                                                                                            Ri[0], Ri[1], Ri[2], Ri[3], Ri[4], Ri[5], Ri[6], Ri[7], Ri[8]);
         NCHK(nd, hipGetLastError());
-        nd->n_aligned = nk; nd->ld_aligned = la;
+        nd->s.n_aligned = nk; nd->s.ld_aligned = la;
         return ICET_OK;
     };
-    s = frame_tail(nd->p, tail, nd->h_out, nk, m_map, res, map_dev, align_dev);
+    s = frame_tail(nd->p, nd->s, nd->h_out, nk, m_map, res, map_dev, align_dev);
     if (s != ICET_OK) return s;
-    nd->prev = cur;                                               // prev_pcl_matrix = pcl_matrix (odometry.cpp:88)
+    nd->s.prev = cur;                                               // prev_pcl_matrix = pcl_matrix (odometry.cpp:88)
     if (flip_owner) nd->owner ^= 1;                               // ... and the keyframe parked for it becomes the one the next frame registers against
     nd->timing_valid = !fused;
 #ifdef ICET_DIAG_ENV
@@ -725,22 +837,17 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
 #undef ICET_TR
 
 
-// No exception may cross the C ABI (std::async can throw std::system_error, the shuffle's vector bad_alloc -- rethrown by get()), and
+// No exception crosses the C ABI (no_throw), and
 // a frame that fails half way must not leave the node's idea of "previous scan" and the parked keyframe disagreeing: on ANY failure
 // the device is drained and the node drops back to "no previous scan" -- the next cloud is stored like the first one
 // (odometry.cpp:46-52) and the pose chain continues from where it was.
 icet_status push_device(icet_node* nd, const float* d_scan, int64_t n, int64_t ld, icet_node_result* res) {
-    icet_status s;
-    const bool was_initialized = nd->initialized;
-    try {
-        s = push_frame(nd, d_scan, n, ld, res);
-    } catch (const std::bad_alloc&) { nd->err = "out of host memory"; s = ICET_ERR_NOMEM;
-    } catch (const std::exception& e) { nd->err = std::string("host error: ") + e.what(); s = ICET_ERR_NOMEM;
-    } catch (...) { nd->err = "host error"; s = ICET_ERR_NOMEM; }
+    const bool was_initialized = nd->s.initialized;
+    const icet_status s = no_throw(nd->err, [&] { return push_frame(nd, d_scan, n, ld, res); });
     if (s != ICET_OK && was_initialized) {
         (void)kf_wait_idle(nd);
         (void)hipDeviceSynchronize();
-        nd->initialized = false; nd->timing_valid = false;
+        nd->s.initialized = false; nd->timing_valid = false;
     }
     return s;
 }
@@ -752,8 +859,7 @@ extern "C" {
 icet_status icet_node_create(icet_ctx* ctx, const icet_node_params* p, icet_node** out) {
     if (!out) return ICET_ERR_BAD_ARG;
     *out = nullptr;
-    if (!ctx || !p || p->map_capacity < 0 || p->map_downsample < 0 || (p->map_capacity > 0 && p->map_downsample > p->map_capacity) ||
-        p->solve.bins_phi <= 0 || p->solve.bins_theta <= 0 || p->solve.n < 1 || p->solve.runlen < 0) return ICET_ERR_BAD_ARG;
+    if (!node_params_ok(ctx, p)) return ICET_ERR_BAD_ARG;
     icet_node* nd = new (std::nothrow) icet_node();
     if (!nd) return ICET_ERR_NOMEM;
     nd->ctx = ctx; nd->p = *p; nd->stream = reinterpret_cast<hipStream_t>(icet_stream(ctx)); nd->device = icet_device(ctx);
@@ -763,24 +869,15 @@ icet_status icet_node_create(icet_ctx* ctx, const icet_node_params* p, icet_node
         hipMalloc(reinterpret_cast<void**>(&nd->d_x0), sizeof(float) * 6) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&nd->d_out), sizeof(float) * 48) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&nd->h_out), sizeof(float) * 48, hipHostMallocCoherent) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&nd->h_x0), sizeof(float) * 6) != hipSuccess)
         return fail(ICET_ERR_NOMEM);
-    if (p->map_capacity > 0) {                                    // (a few milliseconds, once per process: the written-out generator against this C++ library's std::shuffle)
-        static const bool fast_ok = icet_shuffle::matches_std_shuffle() && icet_shuffle::fast_matches_std_shuffle();
-        nd->fast_shuffle = fast_ok;
-    }
+    if (p->map_capacity > 0) nd->fast_shuffle = fast_shuffle_ok();
     for (hipEvent_t& e : nd->ev) if (hipEventCreate(&e) != hipSuccess) return fail(ICET_ERR_HIP);
     for (hipEvent_t& e : nd->ev_kfdone) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(ICET_ERR_HIP);
     if (!(p->flags & ICET_NODE_NO_PIPELINE)) {
         for (icet_ctx*& k : nd->kf) { icet_status cs = icet_create(&k, nd->device, nullptr); if (cs != ICET_OK) return fail(cs); }
         nd->pipelined = true;
     }
-    if (p->flags & ICET_NODE_SNAIL_TRAIL) nd->snail.assign(3, 0.f);      // scanMatcher.cpp:27-28: one row at the origin
-    if (p->map_capacity > 0) {
-        if (hipMalloc(reinterpret_cast<void**>(&nd->d_map), sizeof(float) * 3 * (size_t)p->map_capacity) != hipSuccess) return fail(ICET_ERR_NOMEM);
-        if (hipMemset(nd->d_map, 0, sizeof(float) * 3 * (size_t)p->map_capacity) != hipSuccess) return fail(ICET_ERR_HIP);      // Eigen leaves MatrixXf(maxSize, 3) uninitialised; unfilled rows are never returned by getQueue
-        const size_t m = p->map_downsample > 0 ? p->map_downsample : 1;
-        if (hipMalloc(reinterpret_cast<void**>(&nd->d_idx), sizeof(int32_t) * m) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&nd->h_idx), sizeof(int32_t) * m) != hipSuccess)
-            return fail(ICET_ERR_NOMEM);
-    }
+    { const icet_status ss = stream_create(*p, nd->s); if (ss != ICET_OK) return fail(ss); }
+    if (p->map_capacity > 0 && hipMalloc(reinterpret_cast<void**>(&nd->d_idx), sizeof(int32_t) * (size_t)std::max(p->map_downsample, 1)) != hipSuccess) return fail(ICET_ERR_NOMEM);
     *out = nd;
     return ICET_OK;
 }
@@ -794,10 +891,11 @@ icet_status icet_node_destroy(icet_node* nd) {
     kf_worker_stop(nd);                      // (drains what it still has to enqueue, then joins)
     (void)hipSetDevice(nd->device);
     (void)hipDeviceSynchronize();            // not the borrowed stream: the context may already be gone
-    void* dp[] = {nd->d_scan[0], nd->d_scan[1], nd->d_stage, nd->d_counts, nd->d_bases, nd->d_nkept, nd->d_x0, nd->d_out, nd->d_map, nd->d_idx, nd->d_aligned,
+    stream_destroy(nd->s);
+    void* dp[] = {nd->d_stage, nd->d_counts, nd->d_bases, nd->d_nkept, nd->d_x0, nd->d_out, nd->d_idx,
                   nd->d_scan_kf[0], nd->d_scan_kf[1], nd->d_counts_kf, nd->d_bases_kf, nd->d_nkept_kf};
     for (void* q : dp) if (q) (void)hipFree(q);
-    void* hp[] = {nd->h_nkept, nd->h_out, nd->h_x0, nd->h_idx, nd->h_frame, nd->h_done};
+    void* hp[] = {nd->h_nkept, nd->h_out, nd->h_x0, nd->h_frame, nd->h_done};
     for (void* q : hp) if (q) (void)hipHostFree(q);
     for (hipEvent_t e : nd->ev) if (e) (void)hipEventDestroy(e);
     if (nd->ev_f2) (void)hipEventDestroy(nd->ev_f2);
@@ -820,7 +918,7 @@ icet_status icet_node_push_many_device(icet_node* nd, const icet_dev_scan* frame
     for (int k = 0; k < n_frames; k++)
         if (frames[k].n < 0 || frames[k].ld < frames[k].n || (frames[k].n > 0 && !frames[k].ptr) || frames[k].n >= ((int64_t)1 << 30)) return ICET_ERR_BAD_ARG;
     if (hipSetDevice(nd->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
-    { const icet_status hs = kf_wait_idle(nd); if (hs != ICET_OK) { (void)hipDeviceSynchronize(); nd->initialized = false; return hs; } }
+    { const icet_status hs = kf_wait_idle(nd); if (hs != ICET_OK) { (void)hipDeviceSynchronize(); nd->s.initialized = false; return hs; } }
     // Rounds 4-5 chained a burst's frames on the device (X0 <- X device to device, results parked in HBM, one copy at the end).  That needs two hand-overs between
     // streams per frame -- the build of frame k waits for the loop of frame k - 1 to let go of the context's tables, the loop of frame k + 1 for that build -- at 30 to
     // 60 us each on this part, and ran at 4.0 - 4.7 k frames/s; since a frame is one graph launch (push_frame, round 6) the host in the loop costs ~25 us and frame by
@@ -843,61 +941,28 @@ icet_status icet_node_push(icet_node* nd, const float* scan, int64_t n, int64_t 
     return push_device(nd, nd->d_stage, n, l, res);
 }
 
+// (stream_rows_out; whatever the helper thread still has to enqueue goes first)
 icet_status icet_node_map(icet_node* nd, float* out, int64_t ld, int64_t* rows_out) {
     if (!nd || !rows_out) return ICET_ERR_BAD_ARG;
     (void)kf_wait_idle(nd);
-    const int64_t rows = nd->map_filled ? nd->p.map_capacity : nd->map_pos;
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    if (ld < rows) return ICET_ERR_BAD_ARG;
-    if (hipSetDevice(nd->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
-    float* tmp = nullptr;
-    NCHK(nd, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(float) * 3 * (size_t)rows));
-    const int cap = nd->p.map_capacity;
-    k_map_unroll<<<std::min((int)((rows + 255) / 256), 2048), 256, 0, nd->stream>>>(nd->d_map, nd->d_map + cap, nd->d_map + 2 * (size_t)cap, cap, (int)nd->map_pos,
-                                                                                     nd->map_filled ? 1 : 0, (int)rows, tmp, (int)rows);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy2DAsync(out, ld * sizeof(float), tmp, rows * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, nd->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(nd->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) { nd->err = hipGetErrorString(e); return ICET_ERR_HIP; }
-    return ICET_OK;
+    return stream_rows_out(nd, nd->s, kRowsMap, false, out, ld, rows_out);
 }
 
 icet_status icet_node_prev_scan(icet_node* nd, float* out, int64_t ld, int64_t* rows_out) {
     if (!nd || !rows_out) return ICET_ERR_BAD_ARG;
     (void)kf_wait_idle(nd);
-    const int64_t rows = nd->initialized ? nd->n_scan[nd->prev] : 0;
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    if (ld < rows) return ICET_ERR_BAD_ARG;
-    if (hipSetDevice(nd->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
-    NCHK(nd, hipMemcpy2DAsync(out, ld * sizeof(float), nd->d_scan[nd->prev], nd->ld_scan[nd->prev] * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, nd->stream));
-    NCHK(nd, hipStreamSynchronize(nd->stream));
-    return ICET_OK;
+    return stream_rows_out(nd, nd->s, kRowsPrevScan, false, out, ld, rows_out);
 }
 
 icet_status icet_node_aligned(icet_node* nd, float* out, int64_t ld, int64_t* rows_out) {
     if (!nd || !rows_out) return ICET_ERR_BAD_ARG;
     (void)kf_wait_idle(nd);
-    const int64_t rows = nd->n_aligned;
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    if (ld < rows) return ICET_ERR_BAD_ARG;
-    if (hipSetDevice(nd->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
-    NCHK(nd, hipMemcpy2DAsync(out, ld * sizeof(float), nd->d_aligned, nd->ld_aligned * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, nd->stream));
-    NCHK(nd, hipStreamSynchronize(nd->stream));
-    return ICET_OK;
+    return stream_rows_out(nd, nd->s, kRowsAligned, false, out, ld, rows_out);
 }
 
 icet_status icet_node_snail_trail(icet_node* nd, float* out, int64_t ld, int64_t* rows_out) {
     if (!nd || !rows_out) return ICET_ERR_BAD_ARG;
-    const int64_t rows = (int64_t)(nd->snail.size() / 3);
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    if (ld < rows) return ICET_ERR_BAD_ARG;
-    for (int64_t i = 0; i < rows; i++) { out[i] = nd->snail[3 * i]; out[ld + i] = nd->snail[3 * i + 1]; out[2 * ld + i] = nd->snail[3 * i + 2]; }
-    return ICET_OK;
+    return stream_rows_out(nd, nd->s, kRowsSnail, false, out, ld, rows_out);
 }
 
 icet_status icet_node_last_timing(icet_node* nd, float out_ms[3]) {
@@ -922,9 +987,12 @@ icet_status icet_node_last_timing(icet_node* nd, float out_ms[3]) {
 //                                                    ICET_NODE_NO_RANGE_FILTER streams keep every row (a copy through the same kernels)
 //   icet_keyframe_device_n + icet_register_device_n   ONE keyframe build over the named streams' stored previous scans and ONE Gauss-Newton loop over their
 //                                                    filtered frames (the raw row counts are the launch bounds, the filter's device-side counts the rows)
-//   k_group_map_add_scan                             EigenQueue::add_new_scan of every map-maker stream of the call, one launch (k_map_add_scan's arithmetic)
-//   k_group_align_cloud                              scan2_in_scan1_frame of every stream of the call (k_align_cloud's arithmetic)
-// A pair's result does not depend on the batch it is solved in, so every stream gets the bits of its own icet_node.
+//   k_group_map_add_scan                             EigenQueue::add_new_scan of every map-maker stream of the call, one launch
+//   k_group_align_cloud                              scan2_in_scan1_frame of every stream of the call
+// These five are the second LAUNCH FORM of the row passes at the top of this file, not a second statement of them: each finds its frame (ring, cloud) in the table and
+// calls the body the node's kernel calls (count_block, scan_block_counts, scatter_rank / scatter_store, ring_add_scan_row, align_row).  The host state per stream is the
+// node's StreamState, its tail the node's frame_tail.  A pair's result does not depend on the batch it is solved in, so every stream gets the
+// bits of its own icet_node.
 // ==================================================================================================================================================================
 namespace {
 
@@ -934,9 +1002,9 @@ constexpr int kGroupMaxThreads = 16;         // the down-sample draws: this thre
 
 struct GFrame { const float* x; float* o; int32_t n, ld, ldo, keep_all; };      // keep_all: a copy (first frame, ICET_NODE_NO_RANGE_FILTER)
 struct GFilterArgs { int32_t n_frames; float min_range; int32_t blk_off[kGroupMaxFrames + 1]; GFrame f[kGroupMaxFrames]; };
-struct GRing { float* q; const float* s; const int32_t* idx; int32_t pos, m, lds; float t[3]; float ri[9]; };
+struct GRing { float* q; const float* s; const int32_t* idx; int32_t pos, m, lds; RowMove T; };
 struct GMapArgs { int32_t n_rings, cap; GRing r[kGroupMaxRings]; };
-struct GAlign { const float* s; float* o; int32_t n, lds, ldo; float t[3]; float ri[9]; };
+struct GAlign { const float* s; float* o; int32_t n, lds, ldo; RowMove T; };
 struct GAlignArgs { int32_t n; GAlign a[kGroupMaxRings]; };
 
 // the frame that owns block b: the last k with blk_off[k] <= b (a frame without rows owns no block)
@@ -946,115 +1014,41 @@ __device__ __forceinline__ int group_frame_of(const GFilterArgs& a, int b) {
     return lo;
 }
 
-// pass 1: kept rows per block, blocks of all frames in one grid (the block layout of k_range_count inside each frame)
+// ---- the group's launch form of the row passes: the frame that owns the block (or blockIdx.y's ring / cloud) gives the pointers, the row base and keep_all ----
 __global__ __launch_bounds__(kFB) void k_group_count(const GFilterArgs a, int32_t* __restrict__ counts) {
-    __shared__ int wsum[kFB / 64];
     const int k = group_frame_of(a, blockIdx.x);
     const GFrame f = a.f[k];
-    const float* x = f.x; const float* y = f.x + f.ld; const float* z = f.x + 2 * (size_t)f.ld;
-    const int base = (blockIdx.x - a.blk_off[k]) * kFB * kFRows;
-    int c = 0;
-#pragma unroll
-    for (int r = 0; r < kFRows; r++) {
-        const int i = base + r * kFB + threadIdx.x;
-        if (i < f.n) c += (f.keep_all || keep_row(x[i], y[i], z[i], a.min_range)) ? 1 : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < kFB / 64; w++) t += wsum[w]; counts[blockIdx.x] = t; }
+    count_block(f.x, f.x + f.ld, f.x + 2 * (size_t)f.ld, f.n, (blockIdx.x - a.blk_off[k]) * kFB * kFRows, f.keep_all, a.min_range, counts + blockIdx.x);
 }
 
-// pass 2: one block per frame: exclusive scan of the frame's block counts; the total is the frame's row count, to the device (the solve's d_rows) and to pinned
-// host memory (a host thread may be watching it: the map maker's down-sample draw)
+// one block per frame; the total is the frame's row count, to the device (the solve's d_rows) and to pinned host memory (the map maker's down-sample draw watches it)
 __global__ __launch_bounds__(kFB) void k_group_scan(const GFilterArgs a, const int32_t* __restrict__ counts, int32_t* __restrict__ bases, int32_t* __restrict__ rows, int32_t* __restrict__ h_rows) {
-    __shared__ int part[kFB];
-    const int k = blockIdx.x;
-    const int b0 = a.blk_off[k], n_blocks = a.blk_off[k + 1] - b0;
-    const int per = (n_blocks + kFB - 1) / kFB;
-    const int lo = threadIdx.x * per, hi = min(n_blocks, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; i++) s += counts[b0 + i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { int run = 0; for (int t = 0; t < kFB; t++) { const int v = part[t]; part[t] = run; run += v; } rows[k] = run; h_rows[k] = run; __threadfence_system(); }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; i++) { bases[b0 + i] = run; run += counts[b0 + i]; }
+    const int k = blockIdx.x, b0 = a.blk_off[k];
+    scan_block_counts(counts + b0, bases + b0, a.blk_off[k + 1] - b0, rows + k, h_rows + k);
 }
 
-// pass 3: stable scatter (k_range_scatter's row order: k-major inside a block, kept rows in earlier slices, then lower threads of the same slice)
 __global__ __launch_bounds__(kFB) void k_group_scatter(const GFilterArgs a, const int32_t* __restrict__ bases) {
-    __shared__ int wcnt[kFRows][kFB / 64];
+    __shared__ ScatterCounts wcnt;
     const int k = group_frame_of(a, blockIdx.x);
     const GFrame f = a.f[k];
-    const float* x = f.x; const float* y = f.x + f.ld; const float* z = f.x + 2 * (size_t)f.ld;
-    float* ox = f.o; float* oy = f.o + f.ldo; float* oz = f.o + 2 * (size_t)f.ldo;
-    const int base = (blockIdx.x - a.blk_off[k]) * kFB * kFRows;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float vx[kFRows], vy[kFRows], vz[kFRows];
-    bool keep[kFRows];
-    int below[kFRows];
-#pragma unroll
-    for (int r = 0; r < kFRows; r++) {
-        const int i = base + r * kFB + threadIdx.x;
-        keep[r] = false; vx[r] = vy[r] = vz[r] = 0.f;
-        if (i < f.n) { vx[r] = x[i]; vy[r] = y[i]; vz[r] = z[i]; keep[r] = f.keep_all || keep_row(vx[r], vy[r], vz[r], a.min_range); }
-        const unsigned long long m = __ballot(keep[r]);
-        below[r] = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wcnt[r][wave] = __popcll(m);
-    }
+    ScatterRows r;
+    scatter_rank(f.x, f.x + f.ld, f.x + 2 * (size_t)f.ld, f.n, (blockIdx.x - a.blk_off[k]) * kFB * kFRows, f.keep_all, a.min_range, r, wcnt);
     __syncthreads();
-    int run = bases[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < kFRows; r++) {
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kFB / 64; w++) { const int cw = wcnt[r][w]; before += (w < wave) ? cw : 0; total += cw; }
-        if (keep[r]) { const int o = run + before + below[r]; ox[o] = vx[r]; oy[o] = vy[r]; oz[o] = vz[r]; }
-        run += total;
-    }
+    scatter_store(r, wcnt, bases[blockIdx.x], f.o, f.o + f.ldo, f.o + 2 * (size_t)f.ldo);
 }
 
-// EigenQueue::add_new_scan of every ring of the call: blockIdx.y picks the ring; per row exactly k_map_add_scan
 __global__ __launch_bounds__(256) void k_group_map_add_scan(const GMapArgs a) {
     const GRing& g = a.r[blockIdx.y];
-    const int cap = a.cap, pos = g.pos, m = g.m;
-    float* qx = g.q; float* qy = g.q + cap; float* qz = g.q + 2 * (size_t)cap;
-    const float* sx = g.s; const float* sy = g.s + g.lds; const float* sz = g.s + 2 * (size_t)g.lds;
-    const float tx = g.t[0], ty = g.t[1], tz = g.t[2];
-    const float i00 = g.ri[0], i01 = g.ri[1], i02 = g.ri[2], i10 = g.ri[3], i11 = g.ri[4], i12 = g.ri[5], i20 = g.ri[6], i21 = g.ri[7], i22 = g.ri[8];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += gridDim.x * blockDim.x) {
-        int j = i - pos; if (j < 0) j += cap;
-        float a0, b0, c0;
-        if (j < m) { const int r = g.idx[j]; a0 = sx[r]; b0 = sy[r]; c0 = sz[r]; }
-        else { a0 = qx[i]; b0 = qy[i]; c0 = qz[i]; }
-        a0 -= tx; b0 -= ty; c0 -= tz;
-        {
-#pragma clang fp contract(off)
-            qx[i] = (a0 * i00 + b0 * i10) + c0 * i20;
-            qy[i] = (a0 * i01 + b0 * i11) + c0 * i21;
-            qz[i] = (a0 * i02 + b0 * i12) + c0 * i22;
-        }
-    }
+    const RowMove T = g.T;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.cap; i += gridDim.x * blockDim.x)
+        ring_add_scan_row(i, g.q, g.q + a.cap, g.q + 2 * (size_t)a.cap, a.cap, g.pos, g.m, g.s, g.s + g.lds, g.s + 2 * (size_t)g.lds, g.idx, T);
 }
 
-// scan2_in_scan1_frame of every cloud of the call: blockIdx.y picks the cloud; per row exactly k_align_cloud
 __global__ __launch_bounds__(256) void k_group_align_cloud(const GAlignArgs a) {
     const GAlign& g = a.a[blockIdx.y];
-    const float* sx = g.s; const float* sy = g.s + g.lds; const float* sz = g.s + 2 * (size_t)g.lds;
-    float* ox = g.o; float* oy = g.o + g.ldo; float* oz = g.o + 2 * (size_t)g.ldo;
-    const float tx = g.t[0], ty = g.t[1], tz = g.t[2];
-    const float i00 = g.ri[0], i01 = g.ri[1], i02 = g.ri[2], i10 = g.ri[3], i11 = g.ri[4], i12 = g.ri[5], i20 = g.ri[6], i21 = g.ri[7], i22 = g.ri[8];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < g.n; i += gridDim.x * blockDim.x) {
-        const float a0 = sx[i], b0 = sy[i], c0 = sz[i];
-        {
-#pragma clang fp contract(off)
-            ox[i] = ((a0 * i00 + b0 * i10) + c0 * i20) - tx;
-            oy[i] = ((a0 * i01 + b0 * i11) + c0 * i21) - ty;
-            oz[i] = ((a0 * i02 + b0 * i12) + c0 * i22) - tz;
-        }
-    }
+    const RowMove T = g.T;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < g.n; i += gridDim.x * blockDim.x)
+        align_row(i, g.s, g.s + g.lds, g.s + 2 * (size_t)g.lds, g.o, g.o + g.ldo, g.o + 2 * (size_t)g.ldo, T);
 }
 
 // f(0) .. f(n - 1) on the calling thread and up to kGroupMaxThreads - 1 persistent helpers; returns when all have run (the first exception is rethrown here)
@@ -1097,21 +1091,6 @@ private:
     const std::function<void(int)>* f_ = nullptr; int n_ = 0, next_ = 0, done_ = 0; long gen_ = 0; bool stop_ = false; std::exception_ptr err_;
 };
 
-// What an icet_node keeps between frames, per stream of a group (the pipelining state and the timing events stay with the node: the group has none)
-struct GroupStream {
-    bool initialized = false;
-    float* d_scan[2] = {nullptr, nullptr}; int64_t cap_scan[2] = {0, 0}; int64_t n_scan[2] = {0, 0}; int64_t ld_scan[2] = {0, 0};
-    int prev = 0;
-    float X0[6] = {0, 0, 0, 0, 0, 0};
-    float pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    std::mt19937 gen; icet_shuffle::FastMt fgen;                  // default-seeded, one per stream (simpleMapMaker.cpp:258)
-    std::vector<std::size_t> indices;
-    float* d_map = nullptr; int64_t map_pos = 0; bool map_filled = false;
-    int32_t* h_idx = nullptr;                                     // pinned: the map kernel reads the down-sample indices in place
-    float* d_aligned = nullptr; int64_t cap_aligned = 0, n_aligned = 0, ld_aligned = 0;
-    std::vector<float> snail;
-};
-
 }  // namespace
 
 struct icet_node_group {
@@ -1120,7 +1099,7 @@ struct icet_node_group {
     std::string err;
     int32_t n_streams = 0;
     bool fast_shuffle = false;
-    std::vector<GroupStream> s;
+    std::vector<StreamState> s;
     // per-call tables, by position in the call (the solved frames first): row counts on the device and pinned, X0 and results pinned, results on the device (runlen 0)
     int32_t* d_rows = nullptr; int32_t* h_rows = nullptr; float* h_x0 = nullptr; float* h_out = nullptr; float* d_out = nullptr;
     int32_t* d_counts = nullptr; int32_t* d_bases = nullptr; int64_t cap_blocks = 0;     // the ragged filter's block counts / bases
@@ -1128,27 +1107,6 @@ struct icet_node_group {
 };
 
 namespace {
-
-#define GCHK(g, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    (g)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
-    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
-
-icet_status group_grow(icet_node_group* g, float*& buf, int64_t& cap, int64_t n) {   // a stream's scan-sized buffer: (n + n / 8) rows rounded to 64, as icet_node
-    if (n <= cap) return ICET_OK;
-    GCHK(g, hipStreamSynchronize(g->stream));                     // everything of this group runs on one stream
-    if (buf) { GCHK(g, hipFree(buf)); buf = nullptr; cap = 0; }
-    const int64_t c = (n + n / 8 + 63) / 64 * 64;
-    GCHK(g, hipMalloc(reinterpret_cast<void**>(&buf), sizeof(float) * 3 * (size_t)c));
-    cap = c;
-    return ICET_OK;
-}
-
-// The first frames of a call are stored and not solved (odometry.cpp:46-52): the result of icet_node's first push
-void group_first_result(const icet_node_group* g, const GroupStream& st, int64_t n, icet_node_result* res) {
-    res->solved = 0; res->n_kept = n;
-    std::memcpy(res->pose, st.pose, sizeof(st.pose)); quat_of(st.pose, res->quat);
-    res->map_rows = st.map_filled ? g->p.map_capacity : st.map_pos;
-}
 
 icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids, const icet_dev_scan* frames, icet_node_result* results) {
     for (int i = 0; i < n; i++) std::memset(&results[i], 0, sizeof(icet_node_result));
@@ -1160,23 +1118,16 @@ icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids,
     const int K = (int)order.size();
     for (int i = 0; i < n; i++) if (!g->s[(size_t)ids[i]].initialized) order.push_back(i);
     // ---- buffers: a solved frame goes to its stream's other buffer, a first frame to the "previous" one ----
+    auto drain = [hs] { return hipStreamSynchronize(hs); };      // everything of this group runs on one stream
     int64_t total_blocks = 0;
     for (int j = 0; j < n; j++) {
-        const int i = order[(size_t)j]; GroupStream& st = g->s[(size_t)ids[i]];
+        const int i = order[(size_t)j]; StreamState& st = g->s[(size_t)ids[i]];
         const int to = j < K ? (st.prev ^ 1) : st.prev;
-        icet_status s = group_grow(g, st.d_scan[to], st.cap_scan[to], frames[i].n); if (s != ICET_OK) return s;
-        if (j < K && (p.flags & ICET_NODE_ALIGNED_CLOUD)) { s = group_grow(g, st.d_aligned, st.cap_aligned, st.cap_scan[to]); if (s != ICET_OK) return s; }
+        icet_status s = grow_rows(g, st.d_scan[to], st.cap_scan[to], frames[i].n, drain); if (s != ICET_OK) return s;
+        if (j < K && (p.flags & ICET_NODE_ALIGNED_CLOUD)) { s = grow_rows(g, st.d_aligned, st.cap_aligned, st.cap_scan[to], drain); if (s != ICET_OK) return s; }
         total_blocks += (frames[i].n + kFB * kFRows - 1) / (kFB * kFRows);
     }
-    if (total_blocks > g->cap_blocks) {
-        GCHK(g, hipStreamSynchronize(hs));
-        if (g->d_counts) { GCHK(g, hipFree(g->d_counts)); g->d_counts = nullptr; }
-        if (g->d_bases) { GCHK(g, hipFree(g->d_bases)); g->d_bases = nullptr; }
-        g->cap_blocks = 0;
-        GCHK(g, hipMalloc(reinterpret_cast<void**>(&g->d_counts), sizeof(int32_t) * (size_t)total_blocks));
-        GCHK(g, hipMalloc(reinterpret_cast<void**>(&g->d_bases), sizeof(int32_t) * (size_t)total_blocks));
-        g->cap_blocks = total_blocks;
-    }
+    { const icet_status s = grow_blocks(g, g->d_counts, g->d_bases, g->cap_blocks, total_blocks, drain); if (s != ICET_OK) return s; }
     // ---- the range filter of every frame (odometry.cpp:57-70), kGroupMaxFrames frames per launch triple ----
     for (int j = 0; j < n; j++) static_cast<volatile int32_t*>(g->h_rows)[j] = -1;                // ("not yet": watched below)
     int64_t blk0 = 0;
@@ -1185,7 +1136,7 @@ icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids,
         a.n_frames = std::min(kGroupMaxFrames, n - j0); a.min_range = p.min_range;
         int32_t nb = 0;
         for (int f = 0; f < a.n_frames; f++) {
-            const int j = j0 + f, i = order[(size_t)j]; const GroupStream& st = g->s[(size_t)ids[i]];
+            const int j = j0 + f, i = order[(size_t)j]; const StreamState& st = g->s[(size_t)ids[i]];
             const int to = j < K ? (st.prev ^ 1) : st.prev;
             a.blk_off[f] = nb;
             a.f[f] = GFrame{frames[i].ptr, st.d_scan[to], (int32_t)frames[i].n, (int32_t)frames[i].ld, (int32_t)st.cap_scan[to],
@@ -1197,7 +1148,7 @@ icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids,
         if (nb) k_group_count<<<nb, kFB, 0, hs>>>(a, counts);
         k_group_scan<<<a.n_frames, kFB, 0, hs>>>(a, counts, bases, g->d_rows + j0, g->h_rows + j0);
         if (nb) k_group_scatter<<<nb, kFB, 0, hs>>>(a, bases);
-        GCHK(g, hipGetLastError());
+        NCHK(g, hipGetLastError());
         blk0 += nb;
     }
     // ---- ONE keyframe build over the stored previous scans, ONE loop over the filtered frames ----
@@ -1206,7 +1157,7 @@ icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids,
     if (K > 0) {
         std::vector<icet_dev_scan> a((size_t)K), b((size_t)K);
         for (int j = 0; j < K; j++) {
-            const int i = order[(size_t)j]; const GroupStream& st = g->s[(size_t)ids[i]];
+            const int i = order[(size_t)j]; const StreamState& st = g->s[(size_t)ids[i]];
             const int cur = st.prev ^ 1;
             a[(size_t)j] = icet_dev_scan{st.d_scan[st.prev], st.n_scan[st.prev], st.ld_scan[st.prev]};
             b[(size_t)j] = icet_dev_scan{st.d_scan[cur], frames[i].n, st.cap_scan[cur]};           // the raw rows: an upper bound; the filter's count is d_rows[j]
@@ -1215,95 +1166,74 @@ icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids,
         icet_status s = icet_keyframe_device_n(g->ctx, &sp, K, a.data(), nullptr);
         if (s == ICET_OK) s = icet_register_device_n(g->ctx, &sp, K, b.data(), g->d_rows, g->h_x0, out_dev);
         if (s != ICET_OK) { g->err = icet_last_error(g->ctx); return s; }
-        if (out_dev != g->h_out) GCHK(g, hipMemcpyAsync(g->h_out, g->d_out, sizeof(float) * 48 * (size_t)K, hipMemcpyDeviceToHost, hs));
+        if (out_dev != g->h_out) NCHK(g, hipMemcpyAsync(g->h_out, g->d_out, sizeof(float) * 48 * (size_t)K, hipMemcpyDeviceToHost, hs));
     }
     // ---- the map maker's down-sample draws (simpleMapMaker.cpp:147-158), each over exactly its frame's kept rows: the counts land in pinned memory early in the
     // call, the draws run on the pool while the loop iterates ----
     std::vector<int> m_map((size_t)K, 0);
     if (p.map_capacity > 0 && K > 0) {
         volatile int32_t* hr = g->h_rows;
-        auto arrived = [&]() { for (int j = 0; j < K; j++) if (hr[j] < 0) return false; return true; };
-        for (long spins = 1; !arrived(); spins++)
-            if ((spins & 4095) == 0 && hipStreamQuery(hs) != hipErrorNotReady) break;      // (finished or failed without a count: decided below)
-        (void)hipGetLastError();
-        if (!arrived()) GCHK(g, hipStreamSynchronize(hs));
-        if (!arrived()) { g->err = "the range filter's row counts did not arrive"; return ICET_ERR_HIP; }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        const icet_status s = wait_pinned(g, [&] { for (int j = 0; j < K; j++) if (hr[j] < 0) return false; return true; }, hs, 4095, "the range filter's row counts did not arrive");
+        if (s != ICET_OK) return s;
         const bool fast = g->fast_shuffle;
         g->pool->run(K, [&](int j) {
-            GroupStream& st = g->s[(size_t)ids[order[(size_t)j]]];
-            m_map[(size_t)j] = draw_downsample_into(fast, st.fgen, st.gen, st.indices, p.map_downsample, (int64_t)hr[j], st.h_idx);
+            StreamState& st = g->s[(size_t)ids[order[(size_t)j]]];
+            m_map[(size_t)j] = draw_downsample(st, fast, p.map_downsample, (int64_t)hr[j]);
         });
     }
-    GCHK(g, hipStreamSynchronize(hs));
+    NCHK(g, hipStreamSynchronize(hs));
     // ---- the tails, stream by stream (frame_tail: the node's own), then the batched map and aligned-cloud launches ----
     std::vector<GRing> rings; std::vector<GAlign> clouds;
     for (int j = 0; j < K; j++) {
-        const int i = order[(size_t)j]; GroupStream& st = g->s[(size_t)ids[i]];
+        const int i = order[(size_t)j]; StreamState& st = g->s[(size_t)ids[i]];
         const int cur = st.prev ^ 1;
         const int64_t nk = g->h_rows[j];
         st.n_scan[cur] = nk; st.ld_scan[cur] = st.cap_scan[cur];
-        const NodeTail tail{st.X0, st.pose, &st.map_pos, &st.map_filled, &st.snail};
         auto map_dev = [&](const float* X, const float* Ri, int64_t pos, int m) -> icet_status {
-            GRing r{st.d_map, st.d_scan[cur], st.h_idx, (int32_t)pos, m, (int32_t)st.cap_scan[cur], {X[0], X[1], X[2]}, {}};
-            std::memcpy(r.ri, Ri, sizeof(r.ri));
-            rings.push_back(r);
+            rings.push_back(GRing{st.d_map, st.d_scan[cur], st.h_idx, (int32_t)pos, m, (int32_t)st.cap_scan[cur], row_move(X, Ri)});
             return ICET_OK;
         };
         auto align_dev = [&](const float* X, const float* Ri) -> icet_status {
-            GAlign c{st.d_scan[cur], st.d_aligned, (int32_t)nk, (int32_t)st.cap_scan[cur], (int32_t)st.cap_aligned, {X[0], X[1], X[2]}, {}};
-            std::memcpy(c.ri, Ri, sizeof(c.ri));
-            if (nk) clouds.push_back(c);
+            if (nk) clouds.push_back(GAlign{st.d_scan[cur], st.d_aligned, (int32_t)nk, (int32_t)st.cap_scan[cur], (int32_t)st.cap_aligned, row_move(X, Ri)});
             st.n_aligned = nk; st.ld_aligned = st.cap_aligned;
             return ICET_OK;
         };
-        const icet_status s = frame_tail(p, tail, g->h_out + 48 * (size_t)j, nk, m_map[(size_t)j], &results[i], map_dev, align_dev);
+        const icet_status s = frame_tail(p, st, g->h_out + 48 * (size_t)j, nk, m_map[(size_t)j], &results[i], map_dev, align_dev);
         if (s != ICET_OK) return s;
         st.prev = cur;                                            // prev_pcl_matrix = pcl_matrix (odometry.cpp:88)
     }
     for (int j = K; j < n; j++) {
-        const int i = order[(size_t)j]; GroupStream& st = g->s[(size_t)ids[i]];
+        const int i = order[(size_t)j]; StreamState& st = g->s[(size_t)ids[i]];
         st.n_scan[st.prev] = frames[i].n; st.ld_scan[st.prev] = st.cap_scan[st.prev];
         st.initialized = true;
-        group_first_result(g, st, frames[i].n, &results[i]);
+        first_result(p, st, frames[i].n, &results[i]);
     }
     for (size_t r0 = 0; r0 < rings.size(); r0 += kGroupMaxRings) {
         GMapArgs a{}; a.n_rings = (int32_t)std::min<size_t>(kGroupMaxRings, rings.size() - r0); a.cap = p.map_capacity;
         for (int r = 0; r < a.n_rings; r++) a.r[r] = rings[r0 + (size_t)r];
         k_group_map_add_scan<<<dim3(std::min((p.map_capacity + 255) / 256, 2048), a.n_rings), 256, 0, hs>>>(a);
-        GCHK(g, hipGetLastError());                               // not waited for: the next call (or an accessor) runs behind it on the same stream
+        NCHK(g, hipGetLastError());                               // not waited for: the next call (or an accessor) runs behind it on the same stream
     }
     for (size_t c0 = 0; c0 < clouds.size(); c0 += kGroupMaxRings) {
         GAlignArgs a{}; a.n = (int32_t)std::min<size_t>(kGroupMaxRings, clouds.size() - c0);
         int64_t most = 0;
         for (int c = 0; c < a.n; c++) { a.a[c] = clouds[c0 + (size_t)c]; most = std::max<int64_t>(most, a.a[c].n); }
         k_group_align_cloud<<<dim3((unsigned)std::min<int64_t>((most + 255) / 256, 2048), a.n), 256, 0, hs>>>(a);
-        GCHK(g, hipGetLastError());
+        NCHK(g, hipGetLastError());
     }
     return ICET_OK;
 }
 
-// As push_device for one node: no exception crosses the C ABI, and a call that fails after it has started drains the stream and drops every stream it named back to
+// As push_device for one node: no exception crosses the C ABI (no_throw), and a call that fails after it has started drains the stream and drops every stream it named back to
 // "no previous scan" (their next frame is stored like a first one; the pose chain continues)
 icet_status group_push(icet_node_group* g, int32_t n, const int32_t* ids, const icet_dev_scan* frames, icet_node_result* results) {
-    icet_status s;
-    try {
-        s = group_push_frames(g, n, ids, frames, results);
-    } catch (const std::bad_alloc&) { g->err = "out of host memory"; s = ICET_ERR_NOMEM;
-    } catch (const std::exception& e) { g->err = std::string("host error: ") + e.what(); s = ICET_ERR_NOMEM;
-    } catch (...) { g->err = "host error"; s = ICET_ERR_NOMEM; }
+    const icet_status s = no_throw(g->err, [&] { return group_push_frames(g, n, ids, frames, results); });
     if (s != ICET_OK) {
         (void)hipStreamSynchronize(g->stream);
         (void)hipGetLastError();
         for (int i = 0; i < n; i++) g->s[(size_t)ids[i]].initialized = false;
     }
     return s;
-}
-
-icet_status group_copy_out(icet_node_group* g, const float* src, int64_t lds, int64_t rows, float* out, int64_t ld) {
-    GCHK(g, hipMemcpy2DAsync(out, ld * sizeof(float), src, lds * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, g->stream));
-    GCHK(g, hipStreamSynchronize(g->stream));
-    return ICET_OK;
 }
 
 }  // namespace
@@ -1313,8 +1243,7 @@ extern "C" {
 icet_status icet_node_group_create(icet_ctx* ctx, const icet_node_params* p, int32_t n_streams, icet_node_group** out) {
     if (!out) return ICET_ERR_BAD_ARG;
     *out = nullptr;
-    if (!ctx || !p || n_streams <= 0 || p->map_capacity < 0 || p->map_downsample < 0 || (p->map_capacity > 0 && p->map_downsample > p->map_capacity) ||
-        p->solve.bins_phi <= 0 || p->solve.bins_theta <= 0 || p->solve.n < 1 || p->solve.runlen < 0) return ICET_ERR_BAD_ARG;
+    if (!node_params_ok(ctx, p) || n_streams <= 0) return ICET_ERR_BAD_ARG;
     icet_node_group* g = new (std::nothrow) icet_node_group();
     if (!g) return ICET_ERR_NOMEM;
     auto fail = [&](icet_status s) { icet_node_group_destroy(g); return s; };
@@ -1329,17 +1258,8 @@ icet_status icet_node_group_create(icet_ctx* ctx, const icet_node_params* p, int
         hipHostMalloc(reinterpret_cast<void**>(&g->h_x0), sizeof(float) * 6 * S) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&g->h_out), sizeof(float) * 48 * S, hipHostMallocCoherent) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&g->d_out), sizeof(float) * 48 * S) != hipSuccess)
         return fail(ICET_ERR_NOMEM);
-    if (p->map_capacity > 0) {
-        static const bool fast_ok = icet_shuffle::matches_std_shuffle() && icet_shuffle::fast_matches_std_shuffle();
-        g->fast_shuffle = fast_ok;
-        const size_t m = p->map_downsample > 0 ? p->map_downsample : 1;
-        for (GroupStream& st : g->s) {
-            if (hipMalloc(reinterpret_cast<void**>(&st.d_map), sizeof(float) * 3 * (size_t)p->map_capacity) != hipSuccess) return fail(ICET_ERR_NOMEM);
-            if (hipMemset(st.d_map, 0, sizeof(float) * 3 * (size_t)p->map_capacity) != hipSuccess) return fail(ICET_ERR_HIP);
-            if (hipHostMalloc(reinterpret_cast<void**>(&st.h_idx), sizeof(int32_t) * m) != hipSuccess) return fail(ICET_ERR_NOMEM);
-        }
-    }
-    if (p->flags & ICET_NODE_SNAIL_TRAIL) for (GroupStream& st : g->s) st.snail.assign(3, 0.f);      // scanMatcher.cpp:27-28: one row at the origin
+    if (p->map_capacity > 0) g->fast_shuffle = fast_shuffle_ok();
+    for (StreamState& st : g->s) { const icet_status ss = stream_create(*p, st); if (ss != ICET_OK) return fail(ss); }
     *out = g;
     return ICET_OK;
 }
@@ -1349,11 +1269,7 @@ icet_status icet_node_group_destroy(icet_node_group* g) {
     delete g->pool; g->pool = nullptr;                            // (joins the helpers: none is drawing between calls)
     (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();                                 // not the borrowed stream: the context may already be gone
-    for (GroupStream& st : g->s) {
-        void* dp[] = {st.d_scan[0], st.d_scan[1], st.d_map, st.d_aligned};
-        for (void* q : dp) if (q) (void)hipFree(q);
-        if (st.h_idx) (void)hipHostFree(st.h_idx);
-    }
+    for (StreamState& st : g->s) stream_destroy(st);
     void* dp[] = {g->d_rows, g->d_out, g->d_counts, g->d_bases};
     for (void* q : dp) if (q) (void)hipFree(q);
     void* hp[] = {g->h_rows, g->h_x0, g->h_out};
@@ -1382,58 +1298,25 @@ icet_status icet_node_group_push_device(icet_node_group* g, int32_t n, const int
     return group_push(g, n, stream_ids, frames, results);
 }
 
+// (stream_rows_out; everything of a group runs on its one stream, so the copy out is behind the last call's map and aligned-cloud launches)
 icet_status icet_node_group_map(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
     if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
-    const GroupStream& st = g->s[(size_t)stream];
-    const int64_t rows = st.map_filled ? g->p.map_capacity : st.map_pos;
-    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    if (hipSetDevice(g->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
-    float* tmp = nullptr;
-    GCHK(g, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(float) * 3 * (size_t)rows));
-    const int cap = g->p.map_capacity;
-    k_map_unroll<<<std::min((int)((rows + 255) / 256), 2048), 256, 0, g->stream>>>(st.d_map, st.d_map + cap, st.d_map + 2 * (size_t)cap, cap, (int)st.map_pos,
-                                                                                    st.map_filled ? 1 : 0, (int)rows, tmp, (int)rows);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy2DAsync(out, ld * sizeof(float), tmp, rows * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) { g->err = hipGetErrorString(e); return ICET_ERR_HIP; }
-    return ICET_OK;
+    return stream_rows_out(g, g->s[(size_t)stream], kRowsMap, true, out, ld, rows_out);
 }
 
 icet_status icet_node_group_prev_scan(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
     if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
-    const GroupStream& st = g->s[(size_t)stream];
-    const int64_t rows = st.initialized ? st.n_scan[st.prev] : 0;
-    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    if (hipSetDevice(g->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
-    return group_copy_out(g, st.d_scan[st.prev], st.ld_scan[st.prev], rows, out, ld);
+    return stream_rows_out(g, g->s[(size_t)stream], kRowsPrevScan, true, out, ld, rows_out);
 }
 
 icet_status icet_node_group_aligned(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
     if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
-    const GroupStream& st = g->s[(size_t)stream];
-    const int64_t rows = st.n_aligned;
-    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    if (hipSetDevice(g->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
-    return group_copy_out(g, st.d_aligned, st.ld_aligned, rows, out, ld);
+    return stream_rows_out(g, g->s[(size_t)stream], kRowsAligned, true, out, ld, rows_out);
 }
 
 icet_status icet_node_group_snail_trail(icet_node_group* g, int32_t stream, float* out, int64_t ld, int64_t* rows_out) {
     if (!g || !rows_out || stream < 0 || stream >= g->n_streams) return ICET_ERR_BAD_ARG;
-    const std::vector<float>& sn = g->s[(size_t)stream].snail;
-    const int64_t rows = (int64_t)(sn.size() / 3);
-    if (out && rows > 0 && ld < rows) return ICET_ERR_BAD_ARG;
-    *rows_out = rows;
-    if (!out || rows == 0) return ICET_OK;
-    for (int64_t i = 0; i < rows; i++) { out[i] = sn[3 * i]; out[ld + i] = sn[3 * i + 1]; out[2 * ld + i] = sn[3 * i + 2]; }
-    return ICET_OK;
+    return stream_rows_out(g, g->s[(size_t)stream], kRowsSnail, true, out, ld, rows_out);
 }
 
 }  // extern "C"

@@ -325,6 +325,79 @@ def test_gpu_range_filter_full_size_and_device_push(gpu_ctx):
     g.close()
 
 
+def _u32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+@pytest.mark.gpu
+def test_gpu_range_filter_every_launch_form_against_numpy(gpu_ctx):
+    """The range filter has one device body and two launch forms (k_range_* with the pointers in the arguments or in a pinned record, k_group_* with a table of
+    frames).  The node-against-group twin tests cannot see an error both forms share, so each form is held to NumPy here: kept rows and their order bit for bit
+    (uint32), and n_kept.  Row counts: the wave, k-slice and block edges of a block of 256 threads x 8 rows, and a third block; one frame that keeps every row,
+    one that keeps none; one frame large enough for the node's separate-scan branch (more than 1024 blocks of buffer capacity)."""
+    from icet_amd import api
+    rs = np.random.RandomState(11)
+    min_range = 2.0
+
+    def random_frame(n):                                              # ranges on both sides of the threshold, exactly on it, and at the origin
+        dirs = rs.normal(size=(n, 3)); dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+        r = rs.uniform(0.0, 4.0, n); r[::7] = 2.0; r[5::11] = 0.0
+        return (dirs * r[:, None]).astype(np.float32)
+
+    def shell(n, radius):
+        dirs = rs.normal(size=(n, 3)); dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+        return (dirs * radius).astype(np.float32)
+
+    frames = [random_frame(n) for n in (1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4097)] + [shell(2049, 3.0), shell(2049, 1.0)]
+    expect = [_range_filter(f, min_range) for f in frames]
+    assert len(expect[-2]) == 2049 and len(expect[-1]) == 0          # all kept, none kept
+    assert any(0 < len(e) < len(f) for e, f in zip(expect, frames))
+
+    def check(got_rows, got_n, want, what):
+        assert got_n == len(want), what
+        assert got_rows.shape == want.shape and np.array_equal(_u32(got_rows), _u32(want)), what
+
+    # ---- the node's forms: the one-launch frame with the folded scan (default), count / k_range_scan / scatter (phases), the unpipelined node
+    for flags in (0, api.NODE_TIME_PHASES, api.NODE_NO_PIPELINE):
+        g = api.Node(gpu_ctx, runlen=1, min_range=min_range, flags=flags)
+        g.push(frames[2])
+        check(g.prev_scan(), len(frames[2]), frames[2], "first frame (stored as it is), flags=%d" % flags)
+        for f, e in zip(frames, expect):
+            res = g.push(f)
+            check(g.prev_scan(), res["n_kept"], e, "node flags=%d, %d rows" % (flags, len(f)))
+        g.close()
+
+    # ---- the group's forms: two streams in one call at different row counts (k_group_*), filtered and with keep_all (ICET_NODE_NO_RANGE_FILTER: the frame itself)
+    dev = torch.device("cuda", 0)
+    pad = 64                                                          # leading dimension != rows
+    tens = []
+    for f in frames:
+        t = torch.zeros((3, len(f) + pad), dtype=torch.float32, device=dev); t[:, :len(f)] = torch.from_numpy(np.ascontiguousarray(f.T)).to(dev)
+        tens.append(t)
+    torch.cuda.synchronize()
+    K = len(frames)
+    for flags, want in ((0, expect), (api.NODE_NO_RANGE_FILTER, frames)):
+        g = api.NodeGroup(gpu_ctx, 2, runlen=1, min_range=min_range, flags=flags)
+        g.push_device([(0, tens[2].data_ptr(), len(frames[2]), len(frames[2]) + pad), (1, tens[9].data_ptr(), len(frames[9]), len(frames[9]) + pad)])
+        check(g.prev_scan(0), len(frames[2]), frames[2], "group first frame, stream 0"); check(g.prev_scan(1), len(frames[9]), frames[9], "group first frame, stream 1")
+        for i in range(K):
+            j = (i + 5) % K
+            assert len(frames[i]) != len(frames[j])
+            res = g.push_device([(0, tens[i].data_ptr(), len(frames[i]), len(frames[i]) + pad), (1, tens[j].data_ptr(), len(frames[j]), len(frames[j]) + pad)])
+            check(g.prev_scan(0), res[0]["n_kept"], want[i], "group flags=%d, stream 0, %d rows" % (flags, len(frames[i])))
+            check(g.prev_scan(1), res[1]["n_kept"], want[j], "group flags=%d, stream 1, %d rows" % (flags, len(frames[j])))
+        g.close()
+
+    # ---- more than 1024 blocks: 1.9 M rows make a buffer of (n + n / 8) rounded to 64 = 2 137 536 rows > 1024 x 2048, so the one-launch frame (whose grid goes by
+    # the buffer's capacity) takes the separate k_range_scan and the scatter from `bases`
+    big = random_frame(1900000)
+    g = api.Node(gpu_ctx, runlen=1, min_range=min_range)
+    g.push(frames[2])
+    res = g.push(big)
+    check(g.prev_scan(), res["n_kept"], _range_filter(big, min_range), "node, 1.9 M rows")
+    g.close()
+
+
 @pytest.mark.gpu
 def test_gpu_cpp_node_demo(tmp_path, gpu_ctx, seq64):
     """include/icet_nodes.hpp compiled with plain g++: frames read from .npy files by icet_load_scan, fed to OdometryNode /
