@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
                     "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
                     "icet_keyframe_store_close_coarse_device",
-                    "icet_debug_block_tridiag",
+                    "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -121,6 +121,22 @@ class Closure(C.Structure):
 CLOSURE_DTYPE = np.dtype([("slot", "<i4"), ("reg", "<i4"), ("accepted", "<i4"), ("n_candidates", "<i4"), ("stamp", "<i8"), ("d2", "<f4"), ("reserved0", "<i4"),
                           ("x0", "<f4", (6,)), ("reserved1", "<i4", (2,)), ("out", "<f4", (48,)), ("score", SCORE_DTYPE)])
 assert CLOSURE_DTYPE.itemsize == 288 == C.sizeof(Closure) and C.sizeof(ClosureQuery) == 32 and C.sizeof(Score) == 32 and C.sizeof(AppearanceParams) == 32
+
+
+class PoseGraphOptions(C.Structure):
+    """icet_pose_graph_options (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("gn_iters", C.c_int32), ("max_pcg", C.c_int32), ("dx_tol", C.c_double), ("damping", C.c_double), ("pcg_tol", C.c_double)]
+
+
+class PoseGraphResult(C.Structure):
+    """icet_pose_graph_result (include/icet_hip.h), 40 bytes."""
+    _fields_ = [("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("max_dx", C.c_double), ("status", C.c_int32), ("gn_iterations", C.c_int32),
+                ("pcg_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40
+# icet_pose_graph_result.status
+POSE_GRAPH_CONVERGED, POSE_GRAPH_ITERATION_CAP, POSE_GRAPH_NOT_POSITIVE_DEFINITE, POSE_GRAPH_NON_FINITE, POSE_GRAPH_STALLED = range(5)
 
 
 def info_from_cov(cov):
@@ -253,6 +269,9 @@ def load_library():
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_pose_step_from_x.argtypes = [C.c_void_p, C.c_void_p]; L.icet_pose_step_from_x.restype = None
     L.icet_debug_block_tridiag.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    L.icet_pose_graph_optimize.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(PoseGraphOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseGraphResult)]
+    L.icet_pose_graph_optimize_device.argtypes = L.icet_pose_graph_optimize.argtypes
     L.icet_keyframe_store_enable_appearance.argtypes = [C.c_void_p, C.POINTER(AppearanceParams)]
     L.icet_keyframe_store_describe_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_set_stamp.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
@@ -566,6 +585,76 @@ class Context:
         x = np.zeros((n, 6), np.float64); st = C.c_int32(-1)
         self._check(load_library().icet_debug_block_tridiag(self._h, n, D.ctypes.data, B.ctypes.data, r.ctypes.data, x.ctypes.data, C.byref(st)))
         return x, int(st.value)
+
+    @staticmethod
+    def _pose_graph_host_args(n, closures, fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol):
+        """The host-side arguments both optimiser calls share: ci, cj, the closures' X and info (float32), fixed (uint8 or None), the options."""
+        closures = list(closures)
+        ci = np.ascontiguousarray([int(c[0]) for c in closures], np.int32); cj = np.ascontiguousarray([int(c[1]) for c in closures], np.int32)
+        cX = np.ascontiguousarray([np.asarray(c[2], np.float32).reshape(6) for c in closures], np.float32).reshape(-1, 6)
+        cI = np.ascontiguousarray([np.asarray(c[3], np.float32).reshape(36) for c in closures], np.float32).reshape(-1, 36)
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, np.uint8)
+            if fx.shape[0] != n:
+                raise IcetError(ICET_ERR_BAD_ARG, "fixed must hold one entry per pose")
+        return ci, cj, cX, cI, fx, PoseGraphOptions(int(gn_iters), int(max_pcg), float(dx_tol), float(damping), float(pcg_tol))
+
+    @staticmethod
+    def _pose_graph_result(res):
+        return dict(chi2_initial=float(res.chi2_initial), chi2_final=float(res.chi2_final), status=int(res.status), gn_iterations=int(res.gn_iterations),
+                    max_dx=float(res.max_dx), pcg_iterations=int(res.pcg_iterations))
+
+    def optimize_pose_graph(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0):
+        """icet_pose_graph_optimize: the poses (n x 4 x 4 float32) of a chain with odometry measurements ``odo_X`` ((n - 1) x 6) and information ``odo_info``
+        ((n - 1) x 6 x 6) and the closure edges ``closures`` = (i, j, X, info) tuples as closure_edges returns them, optimised on the device.  Node 0 and the
+        nodes with ``fixed[k] != 0`` stay.  Returns dict(poses n x 4 x 4 float32, poses64 n x 4 x 4, chi2_initial, chi2_final, status (POSE_GRAPH_*),
+        gn_iterations, max_dx, edge_chi2 2 x E, pcg_iterations).  A status of 2 or 3 is a result, not an error: the poses are then the inputs."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
+        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
+        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol)
+        E = n - 1 + ci.shape[0]
+        out = np.zeros((n, 16), np.float32); p64 = np.zeros((n, 12), np.float64); chi = np.zeros((2, E), np.float64); res = PoseGraphResult()
+        self._check(load_library().icet_pose_graph_optimize(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data,
+                                                            cX.ctypes.data, cI.ctypes.data, _data(fx), C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data,
+                                                            C.byref(res)))
+        T64 = np.zeros((n, 4, 4)); T64[:, 3, 3] = 1.0; T64[:, :3, :3] = p64[:, :9].reshape(n, 3, 3); T64[:, :3, 3] = p64[:, 9:]
+        return dict(self._pose_graph_result(res), poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
+
+    def optimize_pose_graph_device(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0,
+                                   clo_X=None, clo_info=None):
+        """icet_pose_graph_optimize_device for torch tensors on this context's device: ``poses`` n x 4 x 4, ``odo_X`` (n - 1) x 6, ``odo_info`` (n - 1) x 6 x 6,
+        float32 and contiguous.  ``closures`` as in optimize_pose_graph (their X and info are uploaded), or (i, j) pairs with ``clo_X`` C x 6 and ``clo_info``
+        C x 6 x 6 as float32 tensors.  Returns the dict of optimize_pose_graph with poses (float32), poses64 (n x 12 float64: R row-major, then t) and edge_chi2
+        (2 x E float64) as tensors on the device.  The call returns when the result is known."""
+        import torch
+        for t in (poses, odo_X, odo_info):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise IcetError(ICET_ERR_BAD_ARG, "poses, odo_X and odo_info must be contiguous float32 tensors on the device")
+        n = poses.numel() // 16
+        if n < 1 or poses.numel() != n * 16 or odo_X.numel() != (n - 1) * 6 or odo_info.numel() != (n - 1) * 36:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        closures = list(closures)
+        if clo_X is None:
+            ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol)
+            clo_X = torch.from_numpy(cX).to(poses.device); clo_info = torch.from_numpy(cI).to(poses.device)
+        else:
+            ci, cj, _, _, fx, opt = self._pose_graph_host_args(n, [(c[0], c[1], np.zeros(6), np.zeros(36)) for c in closures], fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol)
+            for t in (clo_X, clo_info):
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must be contiguous float32 tensors on the device")
+            if clo_X.numel() != ci.shape[0] * 6 or clo_info.numel() != ci.shape[0] * 36:
+                raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must hold one row per closure")
+        E = n - 1 + ci.shape[0]
+        out = torch.zeros((n, 4, 4), dtype=torch.float32, device=poses.device); p64 = torch.zeros((n, 12), dtype=torch.float64, device=poses.device)
+        chi = torch.zeros((2, E), dtype=torch.float64, device=poses.device); res = PoseGraphResult()
+        torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
+        self._check(load_library().icet_pose_graph_optimize_device(self._h, n, _vp(poses.data_ptr()), _vp(odo_X.data_ptr()), _vp(odo_info.data_ptr()), ci.shape[0],
+                                                                   ci.ctypes.data, cj.ctypes.data, _vp(clo_X.data_ptr()), _vp(clo_info.data_ptr()), _data(fx), C.byref(opt),
+                                                                   _vp(out.data_ptr()), _vp(p64.data_ptr()), _vp(chi.data_ptr()), C.byref(res)))
+        return dict(self._pose_graph_result(res), poses=out, poses64=p64, edge_chi2=chi)
 
     def debug_fix(self, values):
         """icet_debug_fix (test hook): n floats through the point pass's float -> 2^36 fixed-point conversions -> (n, 3) uint64 = to_fix_biased (defined for

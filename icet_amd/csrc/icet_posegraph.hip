@@ -1,12 +1,14 @@
-// icet_amd/csrc/icet_posegraph.hip -- the block-tridiagonal solve a pose-graph optimiser needs, behind a test hook.
+// icet_amd/csrc/icet_posegraph.hip -- the pose-graph optimiser (include/icet_hip.h icet_pose_graph_optimize[_device]): the kernels, the
+// device's backend of the driver, the entry points, and the band solve's test hook.
 //
 // The odometry chain of a pose graph makes its normal equations block tridiagonal with 6 x 6 blocks; every closure adds one block pair off the band.  The solve of
 // the band is the kernel that matters: ONE workgroup of 256 threads factors it by block Cholesky and sweeps it forward and back (a block Thomas recurrence,
-// sequential in the node index: one thread walks it, out of chunks of 32 nodes that all threads stage through LDS).  The optimiser around it is not built.
+// sequential in the node index: one thread walks it, out of chunks of 32 nodes that all threads stage through LDS).  Around it: small kernels that each do one
+// thing on plain global arrays, every body in icet_posegraph_body.h, driven from the host by icet_posegraph_driver.h.  No kernel waits on another block.
 #include "icet_ctx.h"
-#include "icet_posegraph_body.h"
+#include "icet_posegraph_driver.h"
 
-#include <cstring>
+#include <string>
 #include <vector>
 
 namespace icet {
@@ -16,9 +18,173 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_block_tridiag(int N, const do
     pg_block_tridiag(N, Dm, Bm, rhs, x, G, W, u, status, sh);
 }
 
+// grid kernels: one thread per global index below `count`
+constexpr int kPgGridThreads = 256;
+#define ICET_PG_GRID_KERNEL(name, body) \
+    __global__ __launch_bounds__(kPgGridThreads) void name(PgArgs a, int count) { \
+        const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x); \
+        if (gi < count) body(a, gi); \
+    }
+ICET_PG_GRID_KERNEL(k_pg_init, pg_init)
+ICET_PG_GRID_KERNEL(k_pg_chi, pg_chi)
+ICET_PG_GRID_KERNEL(k_pg_linearise, pg_linearise)
+ICET_PG_GRID_KERNEL(k_pg_assemble, pg_assemble)
+ICET_PG_GRID_KERNEL(k_pg_offband, pg_offband)
+ICET_PG_GRID_KERNEL(k_pg_hp, pg_hp)
+ICET_PG_GRID_KERNEL(k_pg_retract, pg_retract)
+ICET_PG_GRID_KERNEL(k_pg_finish, pg_finish)
+#undef ICET_PG_GRID_KERNEL
+
+// one-workgroup kernels
+__global__ __launch_bounds__(kPgThreads) void k_pg_factor(PgArgs a) { __shared__ PgShared sh; pg_group_factor(a, sh); }
+__global__ __launch_bounds__(kPgThreads) void k_pg_precond(PgArgs a) { __shared__ PgShared sh; __shared__ PgRed red; pg_group_precond(a, sh, red); }
+__global__ __launch_bounds__(kPgThreads) void k_pg_step(PgArgs a) { __shared__ PgRed red; pg_group_step(a, red); }
+__global__ __launch_bounds__(kPgThreads) void k_pg_stats(PgArgs a) { __shared__ PgRed red; pg_group_stats(a, red); }
+
+namespace {
+
+// The device's backend of pg_optimise: launches on the context's stream; the scalars come back through pinned memory.
+struct PgDeviceBackend {
+    hipStream_t stream = nullptr;
+    double* h_sc = nullptr;                 // pinned, kPgScalars
+    hipError_t err = hipSuccess;
+    bool ok(hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; return e == hipSuccess; }
+    bool grid(PgGridKernel k, int count, const PgArgs& a) {
+        if (count <= 0) return true;
+        const dim3 g((unsigned)((count + kPgGridThreads - 1) / kPgGridThreads)), b(kPgGridThreads);
+        switch (k) {
+            case kPgInit:      hipLaunchKernelGGL(k_pg_init, g, b, 0, stream, a, count); break;
+            case kPgChi:       hipLaunchKernelGGL(k_pg_chi, g, b, 0, stream, a, count); break;
+            case kPgLinearise: hipLaunchKernelGGL(k_pg_linearise, g, b, 0, stream, a, count); break;
+            case kPgAssemble:  hipLaunchKernelGGL(k_pg_assemble, g, b, 0, stream, a, count); break;
+            case kPgOffband:   hipLaunchKernelGGL(k_pg_offband, g, b, 0, stream, a, count); break;
+            case kPgHp:        hipLaunchKernelGGL(k_pg_hp, g, b, 0, stream, a, count); break;
+            case kPgRetract:   hipLaunchKernelGGL(k_pg_retract, g, b, 0, stream, a, count); break;
+            case kPgFinish:    hipLaunchKernelGGL(k_pg_finish, g, b, 0, stream, a, count); break;
+        }
+        return ok(hipGetLastError());
+    }
+    bool group(PgGroupKernel k, const PgArgs& a) {
+        const dim3 g(1), b(kPgThreads);
+        switch (k) {
+            case kPgFactor:  hipLaunchKernelGGL(k_pg_factor, g, b, 0, stream, a); break;
+            case kPgPrecond: hipLaunchKernelGGL(k_pg_precond, g, b, 0, stream, a); break;
+            case kPgStep:    hipLaunchKernelGGL(k_pg_step, g, b, 0, stream, a); break;
+            case kPgStats:   hipLaunchKernelGGL(k_pg_stats, g, b, 0, stream, a); break;
+        }
+        return ok(hipGetLastError());
+    }
+    bool scalars(const PgArgs& a, double out[kPgScalars]) {
+        if (!ok(hipMemcpyAsync(h_sc, a.sc, sizeof(double) * kPgScalars, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+        for (int i = 0; i < kPgScalars; i++) out[i] = h_sc[i];
+        return true;
+    }
+};
+
+// pg_bind's allocator over ONE device block: a first pass with base = nullptr counts the bytes, the second hands them out.  Doubles come first (pg_bind's order),
+// so every double is 8-byte aligned; float and int32 arrays follow.
+struct PgArena {
+    char* base = nullptr; size_t used = 0;
+    void* take(size_t bytes) { void* p = base ? base + used : nullptr; used += bytes; return p; }
+    double* d(size_t n) { return static_cast<double*>(take(n * sizeof(double))); }
+    int32_t* i(size_t n) { return static_cast<int32_t*>(take(n * sizeof(int32_t))); }
+    float* f(size_t n) { return static_cast<float*>(take(n * sizeof(float))); }
+};
+
+struct PgHostIo {          // the host-pointer form's staging, behind pg_bind's arrays in the same block
+    double *poses64 = nullptr, *edge_chi2 = nullptr;
+    float *poses = nullptr, *odo_X = nullptr, *odo_info = nullptr, *clo_X = nullptr, *clo_info = nullptr, *poses_out = nullptr;
+};
+
+icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci, const int32_t* cj,
+                   const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt, float* poses_out, double* poses64_out,
+                   double* edge_chi2, icet_pose_graph_result* result) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!poses || !poses_out || !result || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_optimize: bad argument"; return ICET_ERR_BAD_ARG; }
+    if ((n > 1 && (!odo_X || !odo_info)) || (n_closures > 0 && (!ci || !cj || !clo_X || !clo_info))) { c->err = "icet_pose_graph_optimize: null array"; return ICET_ERR_BAD_ARG; }
+    if (!pg::closures_ok(n, n_closures, ci, cj)) { c->err = "icet_pose_graph_optimize: a closure's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
+    const icet_pose_graph_options o = opt ? *opt : pg_default_options();
+    if (o.gn_iters < 1) { c->err = "icet_pose_graph_optimize: gn_iters < 1"; return ICET_ERR_BAD_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->armed_calls = 2;
+
+    PgGraph graph;
+    graph.build(n, n_closures, ci, cj, fixed);
+    PgArgs a{};
+    a.N = n; a.C = n_closures; a.E = pg::edge_count(n, n_closures);
+    const size_t N = (size_t)n, E = (size_t)a.E, C = (size_t)n_closures, n_items = graph.items.size();
+    PgArena arena;
+    PgGraphDev gd{};
+    PgHostIo io;
+    auto layout = [&]() {
+        arena.used = 0;
+        gd = pg_bind(a, arena, n_items);
+        if (host_io) {
+            // (int32 lists end on a multiple of 4 bytes; the doubles of the staging need 8)
+            arena.used = (arena.used + 7) & ~(size_t)7;
+            io.poses64 = poses64_out ? arena.d(N * 12) : nullptr; io.edge_chi2 = edge_chi2 ? arena.d(2 * E) : nullptr;
+            io.poses = arena.f(N * 16); io.odo_X = arena.f((N - 1) * 6); io.odo_info = arena.f((N - 1) * 36); io.clo_X = arena.f(C * 6); io.clo_info = arena.f(C * 36);
+            io.poses_out = arena.f(N * 16);
+        }
+    };
+    layout();
+    const size_t bytes = arena.used;
+    char* block = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&block), bytes));
+    arena.base = block;
+    layout();
+
+    PgDeviceBackend be;
+    be.stream = c->stream;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&be.h_sc), sizeof(double) * kPgScalars, hipHostMallocDefault);
+    auto up = [&](void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, c->stream); };
+    auto down = [&](void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && dst && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, c->stream); };
+    up(gd.ei, graph.ei.data(), sizeof(int32_t) * E); up(gd.ej, graph.ej.data(), sizeof(int32_t) * E);
+    up(gd.off, graph.off.data(), sizeof(int32_t) * (N + 1)); up(gd.items, graph.items.data(), sizeof(int32_t) * n_items);
+    if (host_io) {
+        up(io.poses, poses, sizeof(float) * N * 16); up(io.odo_X, odo_X, sizeof(float) * (N - 1) * 6); up(io.odo_info, odo_info, sizeof(float) * (N - 1) * 36);
+        up(io.clo_X, clo_X, sizeof(float) * C * 6); up(io.clo_info, clo_info, sizeof(float) * C * 36);
+        a.poses_in = io.poses; a.odo_X = io.odo_X; a.odo_info = io.odo_info; a.clo_X = io.clo_X; a.clo_info = io.clo_info;
+        a.poses_out = io.poses_out; a.poses64_out = io.poses64; a.edge_chi2_out = io.edge_chi2;
+    } else {
+        a.poses_in = poses; a.odo_X = odo_X; a.odo_info = odo_info; a.clo_X = clo_X; a.clo_info = clo_info;
+        a.poses_out = poses_out; a.poses64_out = poses64_out; a.edge_chi2_out = edge_chi2;
+    }
+    icet_pose_graph_result res{};
+    bool done = false;
+    if (e == hipSuccess) {
+        // (the graph's lists and the caller's arrays outlive the synchronisation below; the stream orders the copies before the kernels)
+        done = pg_optimise(be, a, o, graph.c_offband, &res);
+        if (!done) e = be.err;
+    }
+    if (done && host_io) {
+        down(poses_out, io.poses_out, sizeof(float) * N * 16); down(poses64_out, io.poses64, sizeof(double) * N * 12); down(edge_chi2, io.edge_chi2, sizeof(double) * 2 * E);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(block);
+    if (be.h_sc) (void)hipHostFree(be.h_sc);
+    if (e != hipSuccess) { c->err = std::string("icet_pose_graph_optimize: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    *result = res;
+    return ICET_OK;
+}
+
+}  // namespace
 }  // namespace icet
 
 using namespace icet;
+
+icet_status icet_pose_graph_optimize(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                     const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
+                                     float* poses_out, double* poses64_out, double* edge_chi2, icet_pose_graph_result* result) {
+    return pg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, poses_out, poses64_out, edge_chi2, result);
+}
+
+icet_status icet_pose_graph_optimize_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                            const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
+                                            float* poses_out, double* poses64_out, double* edge_chi2, icet_pose_graph_result* result) {
+    return pg_run(c, false, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, poses_out, poses64_out, edge_chi2, result);
+}
 
 // Test hook: one block-tridiagonal system through the optimiser's factor and sweeps.  diag, sub: n x 36 doubles (sub[k] is the block at (k, k - 1); sub[0] is not
 // read as a coupling and should be zero), rhs and x: n x 6 doubles, all on the host.

@@ -589,9 +589,53 @@ icet_status icet_debug_gn_terms_device(icet_ctx* ctx, const icet_params* p, int3
  * the two-instruction biased form (defined for |v| < 2^15) | the wide biased form | the unbiased form that selects between them per value. */
 icet_status icet_debug_fix(icet_ctx* ctx, const float* v, int32_t n, uint64_t* out);
 
-/* --- towards pose-graph optimisation: the block-tridiagonal solve ---------------------------------------------------------
- * The odometry chain of a pose graph makes its normal equations block tridiagonal (6 x 6 blocks).  The optimiser itself is not built; this is its solver.
- * Test hook: ONE symmetric positive definite block-tridiagonal system through the block Cholesky factorisation and the two sweeps, in double, one workgroup.
+/* --- pose-graph optimisation: corrected poses from closure records --------------------------------------------------------
+ * GRAPH.  n poses (float32 4 x 4 row-major, the store's POSE convention), one odometry edge (k, k + 1) per k < n - 1 and n_closures closure edges
+ *   (ci[c], cj[c]), ci != cj, otherwise free: repeats, adjacent and reversed pairs, ends on fixed nodes.  Edge e < n - 1 is the odometry edge, edge
+ *   n - 1 + c is closure c.  An edge (i, j) carries a measurement X (six float32: what a registration of live scan j against keyframe i returns -- the START
+ *   POSE rule above, in double and unrounded: R_X = R_j^T R_i, X_t = R_j^T (t_j - t_i), the angles of R_X) and a 6 x 6 float32 information matrix, used as
+ *   0.5 (m + m^T) in double.  Node 0 and every node with fixed[k] != 0 do not move.
+ * OPTIMISE.  Gauss-Newton in double on chi2 = sum e^T Omega e, e = predicted - X with the angles wrapped to (-pi, pi]; right updates T <- T Exp(dx); central
+ *   differences of step 1e-6.  Per iteration: the edges are linearised, H = sum J^T Omega J and g = sum J^T Omega e are assembled per node in the order of its
+ *   incidence list (no atomics), and H dx = -g is solved by conjugate gradients preconditioned with the block-tridiagonal part of H (every diagonal block, every
+ *   coupling of neighbouring nodes) through the block Cholesky factorisation below: one factorisation per iteration, one band solve per CG iteration, stop at
+ *   sqrt(r.z / r0.z0) <= pcg_tol or after max_pcg band solves (0: 12 x the closures off the band + 8; a graph with none takes exactly one).  `damping` is added to
+ *   the diagonal of H.  A step that does not lower chi2 is undone and ends the run: ICET_POSE_GRAPH_CONVERGED when max |dx| < dx_tol, else _STALLED; a step
+ *   that does is kept, and max |dx| < dx_tol then ends the run _CONVERGED; gn_iters iterations without either: _ITERATION_CAP.
+ * FAILURE.  A band pivot at or below 1e-13 of its diagonal entry (or p.Hp <= 0 in CG): _NOT_POSITIVE_DEFINITE; a chi2, pivot or r.z that is not finite:
+ *   _NON_FINITE.  The outputs are then the inputs: poses_out the input bits, poses64_out their doubles, chi2_final = chi2_initial, both rows of edge_chi2 the
+ *   initial values.  The status is a RESULT: the call returns ICET_OK.
+ * OUTPUT.  poses_out n x 16 float32: every pose rounded once, row 3 = (0, 0, 0, 1); a fixed node returns its input bits.  poses64_out (may be NULL) n x 12
+ *   doubles, R row-major then t.  edge_chi2 (may be NULL) 2 x E doubles, E = n - 1 + n_closures: chi2 per edge at the start | at the end.  gn_iterations counts
+ *   the linearisations, pcg_iterations the band solves.  Same inputs, same bits, run to run.
+ * The first form takes HOST arrays.  In the _device form poses, odo_X, odo_info, clo_X, clo_info, poses_out, poses64_out and edge_chi2 are DEVICE pointers (8-byte
+ * aligned doubles); ci, cj, fixed, opt and result stay on the host.  Both synchronise: they return when the result is known.  The context's parked keyframe and
+ * workspace are not touched.  ICET_ERR_BAD_ARG: a NULL ctx, poses, poses_out or result; odo_X / odo_info NULL with n > 1; ci, cj, clo_X or clo_info NULL with
+ * n_closures > 0; n < 1 or > 4096; n_closures < 0 or > 512; a closure index out of range or ci[c] == cj[c]; gn_iters < 1. */
+#define ICET_POSE_GRAPH_CONVERGED 0
+#define ICET_POSE_GRAPH_ITERATION_CAP 1
+#define ICET_POSE_GRAPH_NOT_POSITIVE_DEFINITE 2
+#define ICET_POSE_GRAPH_NON_FINITE 3
+#define ICET_POSE_GRAPH_STALLED 4
+typedef struct icet_pose_graph_options {
+    int32_t gn_iters;             /* >= 1 */
+    int32_t max_pcg;              /* band solves per Gauss-Newton iteration; 0 = 12 x closures off the band + 8 */
+    double  dx_tol, damping;
+    double  pcg_tol;              /* <= 0: the default, 1e-10 */
+} icet_pose_graph_options;        /* 32 bytes; NULL = 10, 0, 1e-7, 0, default */
+typedef struct icet_pose_graph_result {
+    double  chi2_initial, chi2_final, max_dx;
+    int32_t status, gn_iterations, pcg_iterations, reserved;
+} icet_pose_graph_result;         /* 40 bytes */
+icet_status icet_pose_graph_optimize(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                     const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                     const icet_pose_graph_options* opt, float* poses_out, double* poses64_out, double* edge_chi2, icet_pose_graph_result* result);
+icet_status icet_pose_graph_optimize_device(icet_ctx* ctx, int32_t n, const float* d_poses, const float* d_odo_X, const float* d_odo_info, int32_t n_closures,
+                                            const int32_t* ci, const int32_t* cj, const float* d_clo_X, const float* d_clo_info, const uint8_t* fixed,
+                                            const icet_pose_graph_options* opt, float* d_poses_out, double* d_poses64_out, double* d_edge_chi2,
+                                            icet_pose_graph_result* result);
+/* The optimiser's solver alone, as a test hook.  The odometry chain of a pose graph makes its normal equations block tridiagonal (6 x 6 blocks).
+ * ONE symmetric positive definite block-tridiagonal system through the block Cholesky factorisation and the two sweeps, in double, one workgroup.
  * HOST arrays of doubles: diag n x 36, sub n x 36 (sub[k]: the block at (k, k - 1); sub[0] zero), rhs and x n x 6; *status 0, or ICET_BAND_NOT_POSITIVE_DEFINITE
  * (a pivot at or below 1e-13 of its diagonal entry) / ICET_BAND_NON_FINITE (a NaN or infinite pivot): x is then rhs.  1 <= n <= 4096.  Synchronises. */
 #define ICET_BAND_NOT_POSITIVE_DEFINITE 2
