@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
                     "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
                     "icet_keyframe_store_close_coarse_device",
-                    "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device",
+                    "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_debug_pose_graph_step",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -134,7 +134,16 @@ class PoseGraphResult(C.Structure):
                 ("pcg_iterations", C.c_int32), ("reserved", C.c_int32)]
 
 
-assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40
+class PoseGraphStep(C.Structure):
+    """icet_pose_graph_step (include/icet_hip.h), 152 bytes."""
+    ARRAYS = ("J", "res", "chi_start", "chi_trial", "D", "B", "A", "g", "x", "Pt", "q", "cg_scalars")
+    _fields_ = [(k, C.c_void_p) for k in ARRAYS] + [(k, C.c_int32) for k in ("cg_capacity", "factor_status", "cg_status", "band_solves", "cg_end", "cap", "c_offband", "trial")] + \
+               [(k, C.c_double) for k in ("chi2_start", "chi2_trial", "max_dx")]
+
+
+assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40 and C.sizeof(PoseGraphStep) == 152
+# icet_pose_graph_step.cg_end
+PG_CG_TOLERANCE, PG_CG_ZERO, PG_CG_CAP, PG_CG_FAILED = range(4)
 # icet_pose_graph_result.status
 POSE_GRAPH_CONVERGED, POSE_GRAPH_ITERATION_CAP, POSE_GRAPH_NOT_POSITIVE_DEFINITE, POSE_GRAPH_NON_FINITE, POSE_GRAPH_STALLED = range(5)
 
@@ -272,6 +281,8 @@ def load_library():
     L.icet_pose_graph_optimize.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(PoseGraphOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseGraphResult)]
     L.icet_pose_graph_optimize_device.argtypes = L.icet_pose_graph_optimize.argtypes
+    L.icet_debug_pose_graph_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(PoseGraphOptions), C.c_int32, C.c_void_p, C.POINTER(PoseGraphStep)]
     L.icet_keyframe_store_enable_appearance.argtypes = [C.c_void_p, C.POINTER(AppearanceParams)]
     L.icet_keyframe_store_describe_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_set_stamp.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
@@ -622,6 +633,31 @@ class Context:
                                                             C.byref(res)))
         T64 = np.zeros((n, 4, 4)); T64[:, 3, 3] = 1.0; T64[:, :3, :3] = p64[:, :9].reshape(n, 3, 3); T64[:, :3, 3] = p64[:, 9:]
         return dict(self._pose_graph_result(res), poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
+
+    def debug_pose_graph_step(self, poses, odo_X, odo_info, closures=(), fixed=None, damping=0.0, max_pcg=0, pcg_tol=0.0, p=None):
+        """icet_debug_pose_graph_step: the optimiser's first iteration on the device with its intermediate arrays, and q = H p for every vector of ``p``
+        (K x n x 6 doubles).  Returns a dict of the arrays of icet_pose_graph_step (J E x 6 x 12, res E x 6, chi_start, chi_trial, D, B n x 6 x 6, A C x 6 x 6,
+        g, x n x 6, Pt n x 12, q K x n x 6, cg_scalars band_solves x 2) and its scalars."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
+        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
+        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, damping, max_pcg, pcg_tol)
+        nc = ci.shape[0]; E = n - 1 + nc
+        pv = np.zeros((0, n, 6)) if p is None else np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, n, 6))
+        cap = int(max_pcg) if max_pcg > 0 else 12 * nc + 8
+        arr = dict(J=np.zeros((E, 6, 12)), res=np.zeros((E, 6)), chi_start=np.zeros(E), chi_trial=np.zeros(E), D=np.zeros((n, 6, 6)), B=np.zeros((n, 6, 6)),
+                   A=np.zeros((nc, 6, 6)), g=np.zeros((n, 6)), x=np.zeros((n, 6)), Pt=np.zeros((n, 12)), q=np.zeros(pv.shape), cg_scalars=np.full((cap, 2), np.nan))
+        st = PoseGraphStep()
+        for k in PoseGraphStep.ARRAYS:
+            setattr(st, k, arr[k].ctypes.data)
+        st.cg_capacity = cap
+        self._check(load_library().icet_debug_pose_graph_step(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, nc, ci.ctypes.data, cj.ctypes.data, cX.ctypes.data,
+                                                              cI.ctypes.data, _data(fx), C.byref(opt), pv.shape[0], pv.ctypes.data, C.byref(st)))
+        out = {k: int(getattr(st, k)) for k in ("factor_status", "cg_status", "band_solves", "cg_end", "cap", "c_offband", "trial")}
+        out.update({k: float(getattr(st, k)) for k in ("chi2_start", "chi2_trial", "max_dx")})
+        arr["cg_scalars"] = arr["cg_scalars"][:min(out["band_solves"], cap)]
+        return dict(out, **arr)
 
     def optimize_pose_graph_device(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0,
                                    clo_X=None, clo_info=None):

@@ -79,6 +79,9 @@ struct PgDeviceBackend {
         for (int i = 0; i < kPgScalars; i++) out[i] = h_sc[i];
         return true;
     }
+    // (the test hook's copies: pageable host memory, complete on return)
+    bool fetch(void* host, const void* dev, size_t bytes) { return ok(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream)) && ok(hipStreamSynchronize(stream)); }
+    bool put(void* dev, const void* host, size_t bytes) { return ok(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream)) && ok(hipStreamSynchronize(stream)); }
 };
 
 // pg_bind's allocator over ONE device block: a first pass with base = nullptr counts the bytes, the second hands them out.  Doubles come first (pg_bind's order),
@@ -98,9 +101,9 @@ struct PgHostIo {          // the host-pointer form's staging, behind pg_bind's 
 
 icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci, const int32_t* cj,
                    const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt, float* poses_out, double* poses64_out,
-                   double* edge_chi2, icet_pose_graph_result* result) {
+                   double* edge_chi2, icet_pose_graph_result* result, int32_t K = 0, const double* dbg_p = nullptr, icet_pose_graph_step* dbg = nullptr) {
     if (!c) return ICET_ERR_BAD_ARG;
-    if (!poses || !poses_out || !result || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_optimize: bad argument"; return ICET_ERR_BAD_ARG; }
+    if (!poses || (!dbg && (!poses_out || !result)) || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_optimize: bad argument"; return ICET_ERR_BAD_ARG; }
     if ((n > 1 && (!odo_X || !odo_info)) || (n_closures > 0 && (!ci || !cj || !clo_X || !clo_info))) { c->err = "icet_pose_graph_optimize: null array"; return ICET_ERR_BAD_ARG; }
     if (!pg::closures_ok(n, n_closures, ci, cj)) { c->err = "icet_pose_graph_optimize: a closure's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
     const icet_pose_graph_options o = opt ? *opt : pg_default_options();
@@ -154,10 +157,10 @@ icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, con
     bool done = false;
     if (e == hipSuccess) {
         // (the graph's lists and the caller's arrays outlive the synchronisation below; the stream orders the copies before the kernels)
-        done = pg_optimise(be, a, o, graph.c_offband, &res);
+        done = dbg ? pg_debug_step(be, a, o, graph.c_offband, K, dbg_p, dbg) : pg_optimise(be, a, o, graph.c_offband, &res);
         if (!done) e = be.err;
     }
-    if (done && host_io) {
+    if (done && host_io && !dbg) {
         down(poses_out, io.poses_out, sizeof(float) * N * 16); down(poses64_out, io.poses64, sizeof(double) * N * 12); down(edge_chi2, io.edge_chi2, sizeof(double) * 2 * E);
     }
     const hipError_t es = hipStreamSynchronize(c->stream);
@@ -165,7 +168,7 @@ icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, con
     (void)hipFree(block);
     if (be.h_sc) (void)hipHostFree(be.h_sc);
     if (e != hipSuccess) { c->err = std::string("icet_pose_graph_optimize: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
-    *result = res;
+    if (result) *result = res;
     return ICET_OK;
 }
 
@@ -184,6 +187,15 @@ icet_status icet_pose_graph_optimize_device(icet_ctx* c, int32_t n, const float*
                                             const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
                                             float* poses_out, double* poses64_out, double* edge_chi2, icet_pose_graph_result* result) {
     return pg_run(c, false, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, poses_out, poses64_out, edge_chi2, result);
+}
+
+// Test hook: the optimiser's first iteration with its intermediate arrays copied out (pg_debug_step).  The host-pointer form's staging; nothing is finished.
+icet_status icet_debug_pose_graph_step(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                       const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
+                                       int32_t K, const double* p, icet_pose_graph_step* out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!out || K < 0 || (K > 0 && (!p || !out->q)) || out->cg_capacity < 0 || (out->cg_capacity > 0 && !out->cg_scalars)) { c->err = "icet_debug_pose_graph_step: bad argument"; return ICET_ERR_BAD_ARG; }
+    return pg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, nullptr, nullptr, nullptr, nullptr, K, p, out);
 }
 
 // Test hook: one block-tridiagonal system through the optimiser's factor and sweeps.  diag, sub: n x 36 doubles (sub[k] is the block at (k, k - 1); sub[0] is not

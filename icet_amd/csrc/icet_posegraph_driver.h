@@ -4,6 +4,7 @@
 //     bool grid(PgGridKernel, int count, const PgArgs&)      the body for every global index below count (count 0: nothing)
 //     bool group(PgGroupKernel, const PgArgs&)               the body as one workgroup
 //     bool scalars(const PgArgs&, double out[kPgScalars])    wait for what was enqueued, then a.sc on the host
+//     bool fetch(void* host, const void* dev, size_t bytes), put(void* dev, const void* host, size_t bytes)      (the test hook only) copies, complete on return
 // each false for a failure of the backend (the driver then returns false at once).  icet_posegraph.hip has the device's backend,
 // tests/cpp/test_posegraph_optimize.cpp the host's.
 #pragma once
@@ -51,6 +52,44 @@ inline PgGraphDev pg_bind(PgArgs& a, Alloc& al, size_t n_items) {
     return gd;
 }
 
+// The band solves one linear solve may take.  H = M + R: with no closure off the band H is the band, and the first preconditioned step is the exact solve.
+inline int pg_cg_cap(int c_offband, const icet_pose_graph_options& o) { return c_offband == 0 ? 1 : (o.max_pcg > 0 ? o.max_pcg : 12 * c_offband + 8); }
+
+// How a linear solve ended (icet_pose_graph_step.cg_end): at pcg_tol, at r.z == 0, at the cap, or in a failure (*bad then has the status).
+enum PgCgEnd { kPgCgTolerance = 0, kPgCgZero = 1, kPgCgCap = 2, kPgCgFailed = 3 };
+
+// ONE linear solve H x = -g by preconditioned conjugate gradients, behind kPgFactor: at most `cap` band solves, *pcg counts them on.  The optimiser and the test
+// hook (pg_debug_step) both run this.  rec (may be null; 2 x cap doubles): per band solve its r.z | the p.Hp of the step behind it (NaN where no step followed);
+// only a recording run reads the scalars once more behind the last step.
+template <class Backend>
+inline bool pg_cg(Backend& be, PgArgs& a, int cap, double pcg_tol, int* pcg, int* bad, int* end = nullptr, double* rec = nullptr) {
+    double h[kPgScalars];
+    int why = kPgCgCap, ci = 0;
+    *bad = 0;
+    for (; ci < cap; ci++) {
+        a.first = ci == 0;
+        if (!be.group(kPgPrecond, a) || !be.scalars(a, h)) return false;
+        if (rec && ci > 0) rec[2 * (ci - 1) + 1] = h[kScPq];
+        if (h[kScFactor] != 0.0) { *bad = (int)h[kScFactor]; break; }
+        if (h[kScCg] != 0.0) { *bad = (int)h[kScCg]; break; }
+        ++*pcg;
+        const double rz = h[kScRz], rz0 = h[kScRz0];
+        if (rec) { rec[2 * ci] = rz; rec[2 * ci + 1] = std::nan(""); }
+        if (!std::isfinite(rz)) { *bad = pg::kNonFinite; break; }
+        if (rz < 0.0) { *bad = pg::kNotPositiveDefinite; break; }
+        if (rz == 0.0) { why = kPgCgZero; break; }
+        if (ci > 0 && std::sqrt(rz / rz0) <= pcg_tol) { why = kPgCgTolerance; break; }
+        if (!be.grid(kPgHp, a.N * 6, a) || !be.group(kPgStep, a)) return false;
+    }
+    if (*bad) why = kPgCgFailed;
+    if (rec && ci == cap && cap > 0) {
+        if (!be.scalars(a, h)) return false;
+        rec[2 * (cap - 1) + 1] = h[kScPq];
+    }
+    if (end) *end = why;
+    return true;
+}
+
 // The run.  `a` is bound (pg_bind), the graph uploaded, the caller's arrays in place.  true: *res is the result (its status says how the run ended).
 template <class Backend>
 inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, icet_pose_graph_result* res) {
@@ -68,22 +107,8 @@ inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o,
     for (int it = 0; it < o.gn_iters && !failed; it++) {
         its++;
         if (!be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) || !be.grid(kPgOffband, C * 36, a) || !be.group(kPgFactor, a)) return false;
-        // H = M + R: with no closure off the band H is the band, and the first preconditioned step is the exact solve
-        const int cap = c_offband == 0 ? 1 : (o.max_pcg > 0 ? o.max_pcg : 12 * c_offband + 8);
         int bad = 0;
-        for (int ci = 0; ci < cap; ci++) {
-            a.first = ci == 0;
-            if (!be.group(kPgPrecond, a) || !be.scalars(a, h)) return false;
-            if (h[kScFactor] != 0.0) { bad = (int)h[kScFactor]; break; }
-            if (h[kScCg] != 0.0) { bad = (int)h[kScCg]; break; }
-            pcg++;
-            const double rz = h[kScRz], rz0 = h[kScRz0];
-            if (!std::isfinite(rz)) { bad = pg::kNonFinite; break; }
-            if (rz < 0.0) { bad = pg::kNotPositiveDefinite; break; }
-            if (rz == 0.0) break;
-            if (ci > 0 && std::sqrt(rz / rz0) <= pcg_tol) break;
-            if (!be.grid(kPgHp, N * 6, a) || !be.group(kPgStep, a)) return false;
-        }
+        if (!pg_cg(be, a, pg_cg_cap(c_offband, o), pcg_tol, &pcg, &bad)) return false;
         if (bad) { status = bad; failed = true; break; }
         a.trial = 1;
         if (!be.grid(kPgRetract, N, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
@@ -105,6 +130,49 @@ inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o,
     if (!be.grid(kPgFinish, n_fin, a) || !be.scalars(a, h)) return false;
     res->chi2_initial = chi2_initial; res->chi2_final = failed ? chi2_initial : chi2; res->max_dx = max_dx;
     res->status = status; res->gn_iterations = its; res->pcg_iterations = pcg; res->reserved = 0;
+    return true;
+}
+
+// The test hook's run (icet_debug_pose_graph_step; the host test runs it too): the optimiser's FIRST iteration, kernel for kernel -- the start's chi2, one
+// linearisation, one linear solve through pg_cg, the trial poses and their chi2 -- with every intermediate array copied out, then q = H p per caller vector.
+// The backend copies with fetch(host, device, bytes) and put(device, host, bytes), each false for a failure.  Where the optimiser would stop (a chi2 that is
+// not finite, a failed solve) the hook stops: out->trial says whether the trial poses were taken.  out's null arrays are skipped.
+template <class Backend>
+inline bool pg_debug_step(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, int K, const double* p, icet_pose_graph_step* out) {
+    double h[kPgScalars];
+    const int N = a.N, E = a.E, C = a.C;
+    const size_t sd = sizeof(double), n6 = (size_t)N * 6;
+    const double pcg_tol = o.pcg_tol > 0.0 ? o.pcg_tol : kPgDefaultPcgTol;
+    const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
+    auto get = [&](double* dst, const double* src, size_t count) { return !dst || count == 0 || be.fetch(dst, src, count * sd); };
+    a.damping = o.damping; a.trial = 0; a.first = 0; a.failed = 0;
+    out->factor_status = 0; out->cg_status = 0; out->band_solves = 0; out->cg_end = kPgCgFailed; out->trial = 0;
+    out->c_offband = c_offband; out->cap = pg_cg_cap(c_offband, o);
+    out->chi2_start = 0.0; out->chi2_trial = 0.0; out->max_dx = 0.0;
+    if (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
+    out->chi2_start = h[kScChi];
+    if (!get(out->res, a.res, (size_t)E * 6) || !get(out->chi_start, a.chi, (size_t)E)) return false;
+    if (!std::isfinite(h[kScChi])) { out->cg_status = pg::kNonFinite; return true; }
+    if (!be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) || !be.grid(kPgOffband, C * 36, a) || !be.group(kPgFactor, a)) return false;
+    if (!get(out->J, a.J, (size_t)E * 72) || !get(out->D, a.D, (size_t)N * 36) || !get(out->B, a.B, (size_t)N * 36) || !get(out->A, a.A, (size_t)C * 36) ||
+        !get(out->g, a.g, n6)) return false;
+    std::vector<double> rec(2 * (size_t)out->cap, std::nan(""));
+    int pcg = 0, bad = 0, end = kPgCgCap;
+    if (!pg_cg(be, a, out->cap, pcg_tol, &pcg, &bad, &end, rec.data())) return false;
+    if (!be.scalars(a, h)) return false;
+    out->factor_status = (int)h[kScFactor]; out->cg_status = bad; out->band_solves = pcg; out->cg_end = end;
+    for (int i = 0; i < pcg && i < out->cg_capacity && out->cg_scalars; i++) { out->cg_scalars[2 * i] = rec[2 * i]; out->cg_scalars[2 * i + 1] = rec[2 * i + 1]; }
+    if (!get(out->x, a.x, n6)) return false;
+    if (!bad) {
+        a.trial = 1;
+        if (!be.grid(kPgRetract, N, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
+        a.trial = 0;
+        out->trial = 1; out->chi2_trial = h[kScChi]; out->max_dx = h[kScMaxDx];
+        if (h[kScCg] != 0.0) { out->cg_status = (int)h[kScCg]; out->cg_end = kPgCgFailed; }      // (the last step under the cap found p.Hp not positive)
+        if (!get(out->Pt, a.Pt, (size_t)N * 12) || !get(out->chi_trial, a.chit, (size_t)E)) return false;
+    }
+    for (int k = 0; k < K && out->q; k++)
+        if (!be.put(a.p, p + (size_t)k * n6, n6 * sd) || !be.grid(kPgHp, N * 6, a) || !be.fetch(out->q + (size_t)k * n6, a.q, n6 * sd)) return false;
     return true;
 }
 

@@ -634,6 +634,29 @@ icet_status icet_pose_graph_optimize_device(icet_ctx* ctx, int32_t n, const floa
                                             const int32_t* ci, const int32_t* cj, const float* d_clo_X, const float* d_clo_info, const uint8_t* fixed,
                                             const icet_pose_graph_options* opt, float* d_poses_out, double* d_poses64_out, double* d_edge_chi2,
                                             icet_pose_graph_result* result);
+/* Test hook: the optimiser's FIRST Gauss-Newton iteration with every intermediate array copied out.  The arguments of icet_pose_graph_optimize (HOST arrays;
+ * opt's gn_iters and dx_tol are not used), then K >= 0 vectors p (K x n x 6 doubles, may be NULL with K = 0).  On the context's stream, the production
+ * kernels in the production order: the start's residuals and chi2, one linearisation, the assembly of the band and the off-band blocks, the band's
+ * factorisation, the conjugate-gradient loop of the optimiser itself, the trial poses T Exp(x) and their chi2; then q = H p per caller vector through the
+ * kernel the loop uses.  Every array of *out is a HOST pointer the caller sizes, or NULL to skip it:
+ *   J E x 72 (6 x 12 per edge: node i's six columns, then node j's) | res E x 6 and chi_start E (at the start) | chi_trial E | D, B n x 36 (B[k]: the block at
+ *   (k, k - 1)) | A n_closures x 36 (the block at (ci, cj); zeros for a closure on the band or with a fixed end) | g, x n x 6 | Pt n x 12 | q K x n x 6 |
+ *   cg_scalars 2 x cg_capacity: per band solve its r.z, then the p.Hp of the step that followed (NaN where none did); band_solves pairs are written.
+ * factor_status / cg_status: 0 or an ICET_POSE_GRAPH_* failure; cg_end: how the loop ended (ICET_PG_CG_*); cap: the band solves it was allowed; trial: 1 when
+ * the trial poses were taken (the optimiser stops before them on a failure, and before the linearisation on a start chi2 that is not finite).  Synchronises. */
+#define ICET_PG_CG_TOLERANCE 0
+#define ICET_PG_CG_ZERO 1
+#define ICET_PG_CG_CAP 2
+#define ICET_PG_CG_FAILED 3
+typedef struct icet_pose_graph_step {
+    double *J, *res, *chi_start, *chi_trial, *D, *B, *A, *g, *x, *Pt, *q, *cg_scalars;
+    int32_t cg_capacity;          /* in: pairs cg_scalars has room for */
+    int32_t factor_status, cg_status, band_solves, cg_end, cap, c_offband, trial;
+    double  chi2_start, chi2_trial, max_dx;
+} icet_pose_graph_step;           /* 152 bytes */
+icet_status icet_debug_pose_graph_step(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                       const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                       const icet_pose_graph_options* opt, int32_t K, const double* p, icet_pose_graph_step* out);
 /* The optimiser's solver alone, as a test hook.  The odometry chain of a pose graph makes its normal equations block tridiagonal (6 x 6 blocks).
  * ONE symmetric positive definite block-tridiagonal system through the block Cholesky factorisation and the two sweeps, in double, one workgroup.
  * HOST arrays of doubles: diag n x 36, sub n x 36 (sub[k]: the block at (k, k - 1); sub[0] zero), rhs and x n x 6; *status 0, or ICET_BAND_NOT_POSITIVE_DEFINITE

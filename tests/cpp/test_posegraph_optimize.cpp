@@ -7,6 +7,10 @@
 //     float clo_X[C x 6], clo_info[C x 36] | uint8 fixed[n]
 // OUT per graph: int32 status, gn_iterations, pcg_iterations, 0 | double chi2_initial, chi2_final, max_dx | float poses[n x 16] | double poses64[n x 12] |
 //     double edge_chi2[2 x E].  Prints OK.
+// Usage: test_posegraph_optimize step IN OUT: pg_debug_step, the test hook's run (include/icet_hip.h icet_debug_pose_graph_step), on the same backend.  IN as
+// above with, behind every graph, int32 K | double p[K x n x 6] (gn_iters and dx_tol are not used).  OUT per graph: int32 factor_status, cg_status, band_solves,
+//     cg_end, cap, c_offband, trial, 0 | double chi2_start, chi2_trial, max_dx | double J[E x 72], res[E x 6], chi_start[E], chi_trial[E], D[n x 36], B[n x 36],
+//     A[C x 36], g[n x 6], x[n x 6], Pt[n x 12], q[K x n x 6], cg_scalars[cap x 2] (NaN behind band_solves rows).
 #if defined(ICET_PG_EMU)
 #include <pthread.h>
 static thread_local int pg_emu_tid = 0;
@@ -76,13 +80,17 @@ struct HostBackend {
         return true;
     }
     bool scalars(const PgArgs& a, double out[kPgScalars]) { for (int i = 0; i < kPgScalars; i++) out[i] = a.sc[i]; return true; }
+    bool fetch(void* host, const void* dev, size_t bytes) { memcpy(host, dev, bytes); return true; }
+    bool put(void* dev, const void* host, size_t bytes) { memcpy(dev, host, bytes); return true; }
 };
 
 template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
 template <class T> static bool wr(FILE* f, const T* p, size_t n) { return n == 0 || fwrite(p, sizeof(T), n, f) == n; }
 
 int main(int argc, char** argv) {
-    if (argc != 3) { printf("usage: %s IN OUT\n", argv[0]); return 2; }
+    const bool step = argc == 4 && strcmp(argv[1], "step") == 0;
+    if (argc != 3 && !step) { printf("usage: %s [step] IN OUT\n", argv[0]); return 2; }
+    if (step) { argv++; argc--; }
 #if defined(ICET_PG_EMU)
     pthread_barrier_init(&pg_emu_barrier, nullptr, ICET_PG_EMU_THREADS);
 #endif
@@ -122,6 +130,27 @@ int main(int argc, char** argv) {
         a.poses_in = h_poses.get(); a.odo_X = h_oX.get(); a.odo_info = h_oI.get(); a.clo_X = h_cX.get(); a.clo_info = h_cI.get();
         a.poses_out = h_out.get(); a.poses64_out = h_p64.get(); a.edge_chi2_out = h_chi.get();
         HostBackend be;
+        if (step) {
+            int32_t K = 0;
+            std::vector<double> p;
+            if (fread(&K, 4, 1, in) != 1 || K < 0 || !rd(in, p, (size_t)K * N * 6)) { printf("short vectors\n"); return 2; }
+            // every output at its exact size, NaN where the run writes nothing
+            const int cap = pg_cg_cap(graph.c_offband, o);
+            const size_t sizes[12] = {E * 72, E * 6, E, E, N * 36, N * 36, Cc * 36, N * 6, N * 6, N * 12, (size_t)K * N * 6, (size_t)cap * 2};
+            std::vector<std::unique_ptr<double[]>> arr;
+            for (size_t sz : sizes) { arr.emplace_back(new double[sz]); for (size_t i = 0; i < sz; i++) arr.back()[i] = std::nan(""); }
+            icet_pose_graph_step so{};
+            so.J = arr[0].get(); so.res = arr[1].get(); so.chi_start = arr[2].get(); so.chi_trial = arr[3].get(); so.D = arr[4].get(); so.B = arr[5].get(); so.A = arr[6].get();
+            so.g = arr[7].get(); so.x = arr[8].get(); so.Pt = arr[9].get(); so.q = arr[10].get(); so.cg_scalars = arr[11].get(); so.cg_capacity = cap;
+            if (!pg_debug_step(be, a, o, graph.c_offband, K, p.data(), &so)) { printf("the hook failed\n"); return 1; }
+            printf("graph %d: n %d C %d (%d off the band): factor %d, cg %d, %d band solves of %d, end %d, chi2 %.6e -> %.6e, max dx %.3e\n", gix, n, C, so.c_offband,
+                   so.factor_status, so.cg_status, so.band_solves, so.cap, so.cg_end, so.chi2_start, so.chi2_trial, so.max_dx);
+            const int32_t oh[8] = {so.factor_status, so.cg_status, so.band_solves, so.cg_end, so.cap, so.c_offband, so.trial, 0};
+            const double od[3] = {so.chi2_start, so.chi2_trial, so.max_dx};
+            if (!wr(out, oh, 8) || !wr(out, od, 3)) { printf("write failed\n"); return 2; }
+            for (int i = 0; i < 12; i++) if (!wr(out, arr[(size_t)i].get(), sizes[i])) { printf("write failed\n"); return 2; }
+            continue;
+        }
         icet_pose_graph_result res{};
         if (!pg_optimise(be, a, o, graph.c_offband, &res)) { printf("the driver failed\n"); return 1; }
         printf("graph %d: n %d C %d (%d off the band) status %d, %d iterations, %d band solves, chi2 %.6e -> %.6e, max dx %.3e, %ld launches\n", gix, n, C, graph.c_offband,

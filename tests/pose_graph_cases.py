@@ -55,6 +55,11 @@ def model(key, g, **kw):
     return _MODEL[key]
 
 
+def model_options(o):
+    """The options of a run that the model knows (it solves exactly: no max_pcg, no pcg_tol)."""
+    return {k: v for k, v in o.items() if k in ("gn_iters", "damping")}
+
+
 def rank5_graph():
     """The 12-node graph of the model's tests with a closure whose information has rank 5."""
     info = pgm.diag_info(*pgm.SIGMA_CLOSURE); info[2, 2] = 0
@@ -75,22 +80,77 @@ def nan_graph():
     return dict(g, poses=p)
 
 
+def _write_graph(f, g, o):
+    n, C = g["poses"].shape[0], len(g["closures"])
+    f.write(struct.pack("<iiii", n, C, o.get("gn_iters", 10), o.get("max_pcg", 0)))
+    f.write(struct.pack("<ddd", o.get("dx_tol", DX_TOL), o.get("damping", 0.0), o.get("pcg_tol", 0.0)))
+    f.write(np.ascontiguousarray(g["poses"], np.float32).tobytes())
+    f.write(np.ascontiguousarray(g["odo_X"], np.float32).tobytes())
+    f.write(np.ascontiguousarray(g["odo_info"], np.float32).tobytes())
+    f.write(np.array([c[0] for c in g["closures"]], np.int32).tobytes())
+    f.write(np.array([c[1] for c in g["closures"]], np.int32).tobytes())
+    f.write(np.array([c[2] for c in g["closures"]], np.float32).tobytes())
+    f.write(np.array([c[3] for c in g["closures"]], np.float32).tobytes())
+    f.write((np.zeros(n, np.uint8) if g["fixed"] is None else np.asarray(g["fixed"], np.uint8)).tobytes())
+
+
 def write_graphs(path, items):
     """The input file of tests/cpp/test_posegraph_optimize.cpp: items = [(graph, dict(gn_iters=, max_pcg=, dx_tol=, damping=, pcg_tol=))]."""
     with open(path, "wb") as f:
         f.write(struct.pack("<i", len(items)))
         for g, o in items:
-            n, C = g["poses"].shape[0], len(g["closures"])
-            f.write(struct.pack("<iiii", n, C, o.get("gn_iters", 10), o.get("max_pcg", 0)))
-            f.write(struct.pack("<ddd", o.get("dx_tol", DX_TOL), o.get("damping", 0.0), o.get("pcg_tol", 0.0)))
-            f.write(np.ascontiguousarray(g["poses"], np.float32).tobytes())
-            f.write(np.ascontiguousarray(g["odo_X"], np.float32).tobytes())
-            f.write(np.ascontiguousarray(g["odo_info"], np.float32).tobytes())
-            f.write(np.array([c[0] for c in g["closures"]], np.int32).tobytes())
-            f.write(np.array([c[1] for c in g["closures"]], np.int32).tobytes())
-            f.write(np.array([c[2] for c in g["closures"]], np.float32).tobytes())
-            f.write(np.array([c[3] for c in g["closures"]], np.float32).tobytes())
-            f.write((np.zeros(n, np.uint8) if g["fixed"] is None else np.asarray(g["fixed"], np.uint8)).tobytes())
+            _write_graph(f, g, o)
+
+
+def stalled_graph():
+    """Six poses thrown far from their chain (0.5 m, 3 rad per pose, seeded): the first Gauss-Newton step is kept, the second raises chi2 with a step that is
+    not small -- the run ends stalled.  Kept because the model and the host build of the optimiser agree on that (status 4 after two iterations)."""
+    g = pgm.make_loop(6, [(0, 5), (1, 4)], seed=11)
+    rng = np.random.default_rng(0)
+    P = g["poses"].astype(np.float64)
+    for k in range(1, 6):
+        P[k] = P[k] @ pgm.exp_se3(np.concatenate([0.5 * rng.standard_normal(3), 3.0 * rng.standard_normal(3)]))
+    return dict(g, poses=P.astype(np.float32), fixed=None)
+
+
+def negative_graph(scale=1.0):
+    """The 12-node graph with a closure whose information is negative definite: H is not positive definite.  At scale 1 the band is not either (a pivot of its
+    factorisation fails); at scale 0.1 the band is and CG meets p.Hp <= 0 (after five band solves on the host build)."""
+    return dict(pgm.make_loop(12, [(0, 11), (2, 9)], seed=11, closure_info=[None, -scale * pgm.diag_info(*pgm.SIGMA_CLOSURE)]), fixed=None)
+
+
+def write_step_graphs(path, items):
+    """The input file of the program's `step` mode: items = [(graph, options, p K x n x 6 doubles)]."""
+    with open(path, "wb") as f:
+        f.write(struct.pack("<i", len(items)))
+        for g, o, p in items:
+            _write_graph(f, g, o)
+            p = np.ascontiguousarray(p, np.float64).reshape(-1, g["poses"].shape[0], 6)
+            f.write(struct.pack("<i", p.shape[0])); f.write(p.tobytes())
+
+
+STEP_ARRAYS = ("J", "res", "chi_start", "chi_trial", "D", "B", "A", "g", "x", "Pt", "q", "cg_scalars")
+
+
+def read_step_results(path, items):
+    """The output file of the `step` mode, one dict per graph with the keys of Context.debug_pose_graph_step."""
+    raw = open(path, "rb").read()
+    pos, out = 0, []
+    for g, _, p in items:
+        n, C = g["poses"].shape[0], len(g["closures"])
+        E, K = n - 1 + C, np.asarray(p).reshape(-1, n, 6).shape[0]
+        hd = struct.unpack_from("<8i", raw, pos); pos += 32
+        r = dict(zip(("factor_status", "cg_status", "band_solves", "cg_end", "cap", "c_offband", "trial"), hd))
+        r.update(zip(("chi2_start", "chi2_trial", "max_dx"), struct.unpack_from("<ddd", raw, pos))); pos += 24
+        shapes = dict(J=(E, 6, 12), res=(E, 6), chi_start=(E,), chi_trial=(E,), D=(n, 6, 6), B=(n, 6, 6), A=(C, 6, 6), g=(n, 6), x=(n, 6), Pt=(n, 12), q=(K, n, 6),
+                      cg_scalars=(r["cap"], 2))
+        for k in STEP_ARRAYS:
+            cnt = int(np.prod(shapes[k]))
+            r[k] = np.frombuffer(raw, np.float64, cnt, pos).reshape(shapes[k]); pos += 8 * cnt
+        r["cg_scalars"] = r["cg_scalars"][:r["band_solves"]]
+        out.append(r)
+    assert pos == len(raw)
+    return out
 
 
 def read_results(path, items):
@@ -141,3 +201,53 @@ def compare(name, r, m, g):
     assert np.array_equal(r["poses"][is_fixed].view(np.uint32), np.asarray(g["poses"], np.float32)[is_fixed].view(np.uint32))
     assert np.array_equal(r["poses"][~is_fixed][:, 3, :], np.tile(np.float32([0, 0, 0, 1]), (int((~is_fixed).sum()), 1)))
     return dict(d64=d64, d32=d32, chi_rel=chi_rel)
+
+
+# ---- the graphs of tests/test_pose_graph_step.py: one Gauss-Newton step taken apart -----------------------------------------------------------------------------
+SEAM_PAIRS = ((0, 32), (5, 37), (40, 8))
+STRONG_RATIO = 4e4        # the strong-closure graph: closure information over the odometry's
+STRONG_PAIRS = ((1, 30), (5, 31), (3, 20), (12, 28))
+
+
+def strong_graph():
+    """33 poses, four closures off the band whose information is STRONG_RATIO times the odometry's with every axis within a decade of that (seeded), as a
+    registration's own covariance gives: M^-1 H then has eigenvalues spread down to about 1 / STRONG_RATIO, and CG needs more band solves than the default
+    cap of 12 x 4 + 8.  (With exactly STRONG_RATIO on every axis the small eigenvalues cluster and CG ends by tolerance after 41 band solves.)"""
+    rng = np.random.default_rng(3)
+    infos = [np.diag(STRONG_RATIO * np.diag(pgm.diag_info(*pgm.SIGMA_ODO)).astype(np.float64) * 10 ** rng.uniform(-1, 1, 6)).astype(np.float32) for _ in STRONG_PAIRS]
+    return dict(pgm.make_loop(33, list(STRONG_PAIRS), seed=11, closure_info=infos), fixed=None)
+
+
+def seam_graph():
+    """A half loop: 64 poses, closures between nodes half a turn apart, so that their relative yaw is within 1e-3 of +-pi.  Where the measured yaw and the yaw
+    the start poses predict are on the same side of the seam, the measurement is moved 1e-4 rad across it."""
+    g = dict(pgm.make_loop(64, list(SEAM_PAIRS), seed=11), fixed=None)
+    T = np.asarray(g["poses"], np.float64)
+    closures = []
+    for (i, j, X, info) in g["closures"]:
+        X = np.array(X, np.float32)
+        pred = pgm.xof(T[i], T[j])[5]
+        if (pred > 0) == (X[5] > 0):
+            X[5] = np.float32(-np.sign(pred) * (np.pi - 1e-4))
+        closures.append((i, j, X, info))
+    return dict(g, closures=closures)
+
+
+@functools.lru_cache(maxsize=None)
+def step_graphs():
+    """name -> (graph, options): the graphs one Gauss-Newton step is taken apart on, noisy, seed 11."""
+    out = {}
+    out["n2"] = (graph(2, CASES[1][1], None, True), {})
+    out["n3"] = (graph(3, CASES[2][1], None, True), {})
+    # CASES[3] (duplicates, a reversed closure, node 4 fixed) and: reversed neighbour closures with a fixed end (4, 3) and between free nodes (3, 2); an
+    # off-band closure whose far end j is the fixed node
+    out["n6"] = (graph(6, CASES[3][1] + ((4, 3), (3, 2), (2, 4)), 4, True), {})
+    for k in (4, 5, 6):
+        out["n%d" % CASES[k][0]] = (graph(CASES[k][0], CASES[k][1], None, True), {})
+    # C x 36 = 288 entries of A: two grid blocks
+    out["c8"] = (graph(40, ((0, 39), (2, 30), (35, 4), (10, 20), (21, 11), (7, 8), (9, 8), (15, 38)), None, True), {})
+    out["seam"] = (seam_graph(), {})
+    out["strong"] = (strong_graph(), {})
+    out["strong100"] = (out["strong"][0], dict(max_pcg=100))
+    out["damped"] = (out["n33"][0], dict(damping=1e-3))
+    return out

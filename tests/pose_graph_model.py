@@ -72,6 +72,30 @@ def jacobians(Ti, Tj):
     return J
 
 
+def linearise(T, edges, X, info, is_fixed, damping=0.0):
+    """One linearisation at the poses T: (J E x 6 x 12, e E x 6, the dense H and g over the free nodes in ascending order).  H = sum J^T Omega J + damping I."""
+    is_fixed = np.asarray(is_fixed, bool)
+    free = np.nonzero(~is_fixed)[0]
+    col = -np.ones(len(is_fixed), int); col[free] = np.arange(free.size)
+    m = 6 * free.size
+    H, g = np.zeros((m, m)), np.zeros(m)
+    Js, es = np.zeros((len(edges), 6, 12)), np.zeros((len(edges), 6))
+    for q, (i, j) in enumerate(edges):
+        J = jacobians(T[i], T[j])
+        e = residual(T[i], T[j], X[q])
+        Js[q], es[q] = J, e
+        for (a, Ja) in ((i, J[:, :6]), (j, J[:, 6:])):
+            if col[a] < 0:
+                continue
+            sa = slice(6 * col[a], 6 * col[a] + 6)
+            g[sa] += Ja.T @ info[q] @ e
+            for (b, Jb) in ((i, J[:, :6]), (j, J[:, 6:])):
+                if col[b] >= 0:
+                    H[sa, 6 * col[b]:6 * col[b] + 6] += Ja.T @ info[q] @ Jb
+    H += damping * np.eye(m)
+    return Js, es, H, g
+
+
 def optimise(poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0):
     """dict(poses float32 N x 4 x 4, poses64, chi2_initial, chi2_final, status, gn_iterations, max_dx, edge_chi2 2 x E)."""
     P32 = np.asarray(poses, np.float32).reshape(-1, 4, 4)
@@ -93,19 +117,7 @@ def optimise(poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_to
     for _ in range(gn_iters if not failed else 0):
         its += 1
         m = 6 * free.size
-        H, g = np.zeros((m, m)), np.zeros(m)
-        for q, (i, j) in enumerate(edges):
-            J = jacobians(T[i], T[j])
-            e = residual(T[i], T[j], X[q])
-            for (a, Ja) in ((i, J[:, :6]), (j, J[:, 6:])):
-                if col[a] < 0:
-                    continue
-                sa = slice(6 * col[a], 6 * col[a] + 6)
-                g[sa] += Ja.T @ info[q] @ e
-                for (b, Jb) in ((i, J[:, :6]), (j, J[:, 6:])):
-                    if col[b] >= 0:
-                        H[sa, 6 * col[b]:6 * col[b] + 6] += Ja.T @ info[q] @ Jb
-        H += damping * np.eye(m)
+        _, _, H, g = linearise(T, edges, X, info, is_fixed, damping)
         if m:
             if not (np.isfinite(H).all() and np.isfinite(g).all()):
                 status, failed = NON_FINITE, True; break
@@ -197,3 +209,133 @@ def pose_error(a, b):
         D = Ra.T @ Rb
         dr = max(dr, float(np.linalg.norm([D[2, 1] - D[1, 2], D[0, 2] - D[2, 0], D[1, 0] - D[0, 1]]) / 2))
     return dt, dr
+
+
+# ---- one Gauss-Newton step taken apart (tests/test_pose_graph_step.py) ----------------------------------------------------------------------------------------
+def fixed_mask(n, fixed=None):
+    m = np.zeros(n, bool); m[0] = True
+    if fixed is not None:
+        m |= np.asarray(fixed).reshape(-1) != 0
+    return m
+
+
+def dense_from_band(D, B, A, edges, is_fixed, dtype=np.float64):
+    """The dense H over the free nodes (ascending) from the device's three arrays: D n x 6 x 6 on the diagonal, B[k] at (k, k - 1) and its transpose at
+    (k - 1, k), A[c] at (i, j) of closure c and its transpose at (j, i) where the closure lies off the band between two free nodes.  A fixed node's identity
+    block is left out."""
+    D, B, A = (np.asarray(v, dtype).reshape(-1, 6, 6) for v in (D, B, A))
+    is_fixed = np.asarray(is_fixed, bool)
+    n = D.shape[0]
+    free = np.nonzero(~is_fixed)[0]
+    col = -np.ones(n, int); col[free] = np.arange(free.size)
+    H = np.zeros((6 * free.size, 6 * free.size), dtype)
+
+    def blk(a, b):
+        return H[6 * col[a]:6 * col[a] + 6, 6 * col[b]:6 * col[b] + 6]
+    for k in free:
+        blk(k, k)[...] = D[k]
+        if k > 0 and col[k - 1] >= 0:
+            blk(k, k - 1)[...] = B[k]; blk(k - 1, k)[...] = B[k].T
+    for c, (i, j) in enumerate(edges[n - 1:]):
+        if abs(i - j) >= 2 and col[i] >= 0 and col[j] >= 0:
+            blk(i, j)[...] += A[c]; blk(j, i)[...] += A[c].T
+    return H
+
+
+def band_of(H, is_fixed):
+    """The block-tridiagonal part of a dense free-node H: the blocks between nodes whose indices differ by at most one."""
+    free = np.nonzero(~np.asarray(is_fixed, bool))[0]
+    node = np.repeat(free, 6)
+    return np.where(np.abs(node[:, None] - node[None, :]) <= 1, H, 0.0)
+
+
+def band_solver(M, cholesky=False):
+    """r -> M^-1 r.  numpy.linalg.solve is LAPACK's gesv, an LU factorisation with partial pivoting and two triangular solves; with SciPy the same factorisation
+    is made once (getrf) and reused (getrs).  `cholesky`: through the Cholesky factor instead -- another float64 solver of the same system."""
+    try:
+        import scipy.linalg as sl
+    except ImportError:
+        if cholesky:
+            L = np.linalg.cholesky(M)
+            return lambda r: np.linalg.solve(L.T, np.linalg.solve(L, r))
+        return lambda r: np.linalg.solve(M, r)
+    f = sl.cho_factor(M, lower=True) if cholesky else sl.lu_factor(M)
+    return (lambda r: sl.cho_solve(f, r)) if cholesky else (lambda r: sl.lu_solve(f, r))
+
+
+def precond_ratio(H, g, M, x):
+    """sqrt(r . M^-1 r / g . M^-1 g) of the TRUE residual r = -g - H x."""
+    r = -g - H @ x
+    return float(np.sqrt((r @ np.linalg.solve(M, r)) / (g @ np.linalg.solve(M, g))))
+
+
+def pcg_reference(H, g, band_of_H, tol, cap):
+    """Textbook preconditioned conjugate gradients on H x = -g in float64, the dense band through numpy.linalg.solve as preconditioner, with the driver's stop
+    rule: per iteration a band solve and r.z, the end at r.z == 0 or (from the second iteration) sqrt(r.z / r0.z0) <= tol, else a step; at most `cap` band
+    solves.  dict(x, iterations (the steps taken: exact arithmetic needs at most rank(H - M) + 1), band_solves (one more where the end was found by a band solve
+    behind the last step), ratio (precond_ratio of x), end ("tolerance" | "zero" | "cap"), rz, pq)."""
+    x, r = np.zeros_like(g), -g.copy()
+    p, rz_prev, rz0, its, end, rzs, pqs = None, None, None, 0, "cap", [], []
+    solve = band_solver(band_of_H)
+    for ci in range(cap):
+        z = solve(r)
+        rz = float(r @ z)
+        its += 1; rzs.append(rz)
+        if ci == 0:
+            rz0, p = rz, z
+        else:
+            p = z + (rz / rz_prev) * p
+        if rz == 0.0:
+            end = "zero"; break
+        if ci > 0 and np.sqrt(rz / rz0) <= tol:
+            end = "tolerance"; break
+        q = H @ p
+        pq = float(p @ q); pqs.append(pq)
+        alpha = rz / pq
+        x, r, rz_prev = x + alpha * p, r - alpha * q, rz
+    return dict(x=x, iterations=len(pqs), band_solves=its, ratio=precond_ratio(H, g, band_of_H, x), end=end, rz=rzs, pq=pqs)
+
+
+# the Jacobians once more in numpy.longdouble: the same central differences of the same step from the same float64 poses.  Only to measure how far the float64
+# evaluation is from itself at higher precision (its rounding noise, about eps |xof| / 2 h).
+_LD = np.longdouble
+_PI_LD = 4 * np.arctan(_LD(1))
+
+
+def _wrap_ld(a):
+    return -((-a + _PI_LD) % (2 * _PI_LD) - _PI_LD)
+
+
+def xof_ld(Ti, Tj):
+    Ti, Tj = np.asarray(Ti, _LD), np.asarray(Tj, _LD)
+    RX = Tj[:3, :3].T @ Ti[:3, :3]
+    xt = Tj[:3, :3].T @ (Tj[:3, 3] - Ti[:3, 3])
+    return np.array([xt[0], xt[1], xt[2], np.arctan2(-RX[2, 1], RX[2, 2]), np.arcsin(np.clip(RX[2, 0], _LD(-1), _LD(1))), np.arctan2(-RX[1, 0], RX[0, 0])], _LD)
+
+
+def exp_se3_ld(d):
+    d = np.asarray(d, _LD)
+    rho, om = d[:3], d[3:]
+    th = np.sqrt(om @ om)
+    K = np.array([[0, -om[2], om[1]], [om[2], 0, -om[0]], [-om[1], om[0], 0]], _LD)
+    if th < 1e-5:
+        A, B, Cc = 1 - th * th / 6, _LD(0.5) - th * th / 24, _LD(1) / 6 - th * th / 120
+    else:
+        A, B, Cc = np.sin(th) / th, (1 - np.cos(th)) / th ** 2, (th - np.sin(th)) / th ** 3
+    T = np.eye(4, dtype=_LD)
+    T[:3, :3] = np.eye(3, dtype=_LD) + A * K + B * (K @ K)
+    T[:3, 3] = (np.eye(3, dtype=_LD) + B * K + Cc * (K @ K)) @ rho
+    return T
+
+
+def jacobians_ld(Ti, Tj):
+    Ti, Tj = np.asarray(Ti, _LD), np.asarray(Tj, _LD)
+    h = _LD(JAC_STEP)
+    J = np.zeros((6, 12), _LD)
+    for c in range(6):
+        d = np.zeros(6, _LD); d[c] = h
+        Ep, Em = exp_se3_ld(d), exp_se3_ld(-d)
+        a = xof_ld(Ti @ Ep, Tj) - xof_ld(Ti @ Em, Tj); a[3:] = _wrap_ld(a[3:])
+        b = xof_ld(Ti, Tj @ Ep) - xof_ld(Ti, Tj @ Em); b[3:] = _wrap_ld(b[3:])
+        J[:, c], J[:, 6 + c] = a / (2 * h), b / (2 * h)
+    return J

@@ -87,6 +87,45 @@ def test_status_paths(ctx):
     pc.compare("one iteration", r, m, g)
 
 
+def test_paths_the_loop_graphs_do_not_take(ctx):
+    """Against the model, with the comparison of the loop graphs: closures across the angle seam (measured and predicted yaw on opposite sides of +-pi), damping,
+    a single pose, and a loose pcg_tol, which reaches the same optimum with no more band solves than the default."""
+    g = pc.seam_graph()
+    T = np.asarray(g["poses"], np.float64)
+    assert sum(1 for c in g["closures"] if (pgm.xof(T[c[0]], T[c[1]])[5] > 0) != (c[2][5] > 0)) >= 2
+    pc.compare("seam", _run(ctx, g), pc.model(("seam",), g), g)
+    g = pc.graph(33, pc.CASES[4][1], None, True)
+    pc.compare("damping 1e-3", _run(ctx, g, damping=1e-3), pc.model(("damped",), g, damping=1e-3), g)
+    default, loose = _run(ctx, g), _run(ctx, g, pcg_tol=1e-4)
+    pc.compare("pcg_tol 1e-4", loose, pc.model(("loop", 33, pc.CASES[4][1], None, True), g), g)
+    print("    band solves: %d at pcg_tol 1e-4, %d at the default" % (loose["pcg_iterations"], default["pcg_iterations"]))
+    assert loose["status"] == pgm.CONVERGED and loose["pcg_iterations"] <= default["pcg_iterations"]
+    g = dict(pgm.make_loop(1, [], seed=11), fixed=None)
+    r = _run(ctx, g)
+    pc.compare("a single pose", r, pc.model(("single",), g), g)
+    assert r["gn_iterations"] == 1 and r["edge_chi2"].shape == (2, 0)
+
+
+def test_stalled_and_negative_definite(ctx):
+    """A start thrown far from its chain ends stalled after the model's two iterations, at the model's poses.  A closure with negative definite information is
+    status 2 on both sides -- through a band pivot at full strength, through p.Hp <= 0 in CG at a tenth of it (plain branches both) -- and the outputs are the
+    inputs bit for bit."""
+    g = pc.stalled_graph()
+    r, m = _run(ctx, g), pc.model(("stalled",), g)
+    pc.compare("stalled", r, m, g)
+    assert r["status"] == m["status"] == pgm.STALLED and r["gn_iterations"] == m["gn_iterations"] == 2
+    for key, scale in (("negative", 1.0), ("negative_cg", 0.1)):
+        g = pc.negative_graph(scale)
+        r, m = _run(ctx, g), pc.model((key,), g)
+        print("    %s: status %d | %d after %d band solves" % (key, r["status"], m["status"], r["pcg_iterations"]))
+        assert r["status"] == m["status"] == pgm.NOT_POSITIVE_DEFINITE and r["gn_iterations"] == m["gn_iterations"] == 1
+        assert (r["pcg_iterations"] > 0) == (key == "negative_cg")          # a band pivot | p.Hp <= 0 in CG
+        assert np.array_equal(r["poses"].view(np.uint32), g["poses"].view(np.uint32))
+        assert np.array_equal(r["poses64"].view(np.uint64), pc.poses64_matrix(np.concatenate([g["poses"][:, :3, :3].reshape(-1, 9), g["poses"][:, :3, 3]], axis=1)).view(np.uint64))
+        assert r["chi2_final"] == r["chi2_initial"] and abs(r["chi2_initial"] - m["chi2_initial"]) <= 1e-12 * np.abs(m["edge_chi2"][0]).sum()
+        assert np.array_equal(r["edge_chi2"][0], r["edge_chi2"][1])
+
+
 def test_refusals(ctx):
     import icet_amd
     from icet_amd import api
