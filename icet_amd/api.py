@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
                     "icet_node_create", "icet_node_destroy", "icet_node_last_error", "icet_node_push", "icet_node_push_device", "icet_node_push_many_device", "icet_node_map",
-                    "icet_node_prev_scan", "icet_node_aligned", "icet_node_snail_trail", "icet_node_last_timing", "icet_stream", "icet_device",
+                    "icet_node_prev_scan", "icet_node_aligned", "icet_node_snail_trail", "icet_node_last_timing", "icet_debug_node_tail", "icet_stream", "icet_device",
                     "icet_node_group_create", "icet_node_group_destroy", "icet_node_group_last_error", "icet_node_group_push_device", "icet_node_group_map",
                     "icet_node_group_prev_scan", "icet_node_group_aligned", "icet_node_group_snail_trail",
                     "icet_load_scan", "icet_free_scan", "icet_save_scan_npy")
@@ -323,6 +323,7 @@ def load_library():
     L.icet_node_prev_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.icet_node_aligned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.icet_node_snail_trail.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.icet_debug_node_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_node_group_create.argtypes = [C.c_void_p, C.POINTER(NodeParams), C.c_int32, C.POINTER(C.c_void_p)]
     L.icet_node_group_destroy.argtypes = [C.c_void_p]
     L.icet_node_group_last_error.argtypes = [C.c_void_p]; L.icet_node_group_last_error.restype = C.c_char_p
@@ -1472,6 +1473,17 @@ def _result_dict(r):
     return dict(solved=bool(r.solved), diverged=bool(r.diverged), n_kept=int(r.n_kept), X=np.array(r.X[:], np.float32),
                 pred_stds=np.array(r.pred_stds[:], np.float32), pose=np.array(r.pose[:], np.float32).reshape(4, 4),
                 quat=np.array(r.quat[:], np.float32), map_rows=int(r.map_rows))
+
+
+def debug_node_tail(X, pose):
+    """icet_debug_node_tail (test hook, host only: no Context, no device): the scalars of a frame's tail as the node's frame_tail evaluates them, for the solution
+    ``X`` (6) and the accumulated pose ``pose`` (4 x 4) before the frame -> dict(R (3, 3), Rinv (3, 3), pose (4, 4), quat (4: x, y, z, w)), float32."""
+    x = np.ascontiguousarray(X, np.float32).reshape(6); p = np.ascontiguousarray(pose, np.float32).reshape(16)
+    R, Ri, P, q = np.zeros(9, np.float32), np.zeros(9, np.float32), np.zeros(16, np.float32), np.zeros(4, np.float32)
+    st = load_library().icet_debug_node_tail(x.ctypes.data, p.ctypes.data, R.ctypes.data, Ri.ctypes.data, P.ctypes.data, q.ctypes.data)
+    if st != ICET_OK:
+        raise IcetError(st, "icet_debug_node_tail")
+    return dict(R=R.reshape(3, 3), Rinv=Ri.reshape(3, 3), pose=P.reshape(4, 4), quat=q)
 
 
 class Node:

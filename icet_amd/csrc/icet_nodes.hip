@@ -16,6 +16,7 @@
 // No CPU implementation of the solve lives here; without a device every entry point fails with an error status.
 #include "../../include/icet_nodes.h"
 #include "icet_shuffle.h"
+#include "icet_node_tail.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -214,55 +215,11 @@ __global__ __launch_bounds__(256) void k_map_unroll(const float* __restrict__ qx
     }
 }
 
-// utils::R (src/utils.cpp:144-152) in host float arithmetic, as the nodes evaluate it (odometry.cpp:85)
-void euler_R_host(float phi, float theta, float psi, float* R) {
-    const float cph = std::cos(phi), sph = std::sin(phi), cth = std::cos(theta), sth = std::sin(theta), cps = std::cos(psi), sps = std::sin(psi);
-    R[0] = cth * cps;  R[1] = sps * cph + sph * sth * cps;  R[2] = sph * sps - sth * cph * cps;
-    R[3] = -sps * cth; R[4] = cph * cps - sph * sth * sps;  R[5] = sph * cps + sth * sps * cph;
-    R[6] = sth;        R[7] = -sph * cth;                   R[8] = cph * cth;
-}
-
-// MatrixXf::inverse() of a dynamic matrix goes through PartialPivLU (Eigen/src/LU/InverseImpl.h): LU with row pivoting,
-// then the two triangular solves against the permuted identity.
-void inverse3_lu(const float* A, float* inv) {
-    float lu[9]; std::memcpy(lu, A, sizeof(lu));
-    int perm[3] = {0, 1, 2};
-    for (int k = 0; k < 3; k++) {
-        int piv = k; float best = std::fabs(lu[k * 3 + k]);
-        for (int r = k + 1; r < 3; r++) if (std::fabs(lu[r * 3 + k]) > best) { best = std::fabs(lu[r * 3 + k]); piv = r; }
-        if (piv != k) { for (int c = 0; c < 3; c++) std::swap(lu[k * 3 + c], lu[piv * 3 + c]); std::swap(perm[k], perm[piv]); }
-        if (lu[k * 3 + k] == 0.f) continue;
-        for (int r = k + 1; r < 3; r++) {
-            lu[r * 3 + k] /= lu[k * 3 + k];
-            for (int c = k + 1; c < 3; c++) lu[r * 3 + c] -= lu[r * 3 + k] * lu[k * 3 + c];
-        }
-    }
-    for (int col = 0; col < 3; col++) {
-        float b[3];
-        for (int r = 0; r < 3; r++) b[r] = (perm[r] == col) ? 1.f : 0.f;
-        for (int r = 1; r < 3; r++) for (int c = 0; c < r; c++) b[r] -= lu[r * 3 + c] * b[c];
-        for (int r = 2; r >= 0; r--) { for (int c = r + 1; c < 3; c++) b[r] -= lu[r * 3 + c] * b[c]; b[r] /= lu[r * 3 + r]; }
-        for (int r = 0; r < 3; r++) inv[r * 3 + col] = b[r];
-    }
-}
-
-// Eigen::Quaternionf(Matrix3f) (Eigen/src/Geometry/Quaternion.h, Shoemake's method); q = x, y, z, w
-void quat_of(const float* P /* 4x4 row-major */, float q[4]) {
-    const float m00 = P[0], m01 = P[1], m02 = P[2], m10 = P[4], m11 = P[5], m12 = P[6], m20 = P[8], m21 = P[9], m22 = P[10];
-    const float m[3][3] = {{m00, m01, m02}, {m10, m11, m12}, {m20, m21, m22}};
-    float t = m00 + m11 + m22;
-    if (t > 0.f) {
-        t = std::sqrt(t + 1.0f); q[3] = 0.5f * t; t = 0.5f / t;
-        q[0] = (m21 - m12) * t; q[1] = (m02 - m20) * t; q[2] = (m10 - m01) * t;
-    } else {
-        int i = 0;
-        if (m11 > m00) i = 1;
-        if (m22 > m[i][i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0f);
-        q[i] = 0.5f * t; t = 0.5f / t;
-        q[3] = (m[k][j] - m[j][k]) * t; q[j] = (m[j][i] + m[i][j]) * t; q[k] = (m[k][i] + m[i][k]) * t;
-    }
+// The scalars of a frame's tail -- R from the frame's Euler angles, R^-1 (always: the caller ignores it when nothing consumes it), the chained pose and its quaternion
+// (icet_node_tail.h) -- compiled ONCE: frame_tail and the test hook icet_debug_node_tail call this body, so what the hook returns is what a frame computes.
+using icet_node_tail::quat_of;
+__attribute__((noinline)) void node_tail_scalars(const float X[6], const float pose_in[16], float R[9], float Rinv[9], float pose_out[16], float quat[4]) {
+    icet_node_tail::tail_scalars(X, pose_in, R, Rinv, pose_out, quat);
 }
 
 }  // namespace
@@ -408,9 +365,8 @@ __attribute__((noinline)) icet_status frame_tail(const icet_node_params& p, Stre
             res->diverged = 1;
         }
     }
-    float R[9]; euler_R_host(X[3], X[4], X[5], R);
-    float Ri[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (p.map_capacity > 0 || (p.flags & (ICET_NODE_ALIGNED_CLOUD | ICET_NODE_SNAIL_TRAIL))) inverse3_lu(R, Ri);
+    float R[9], Ri[9], P[16], quat[4];
+    node_tail_scalars(X, st.pose, R, Ri, P, quat);                // (st.pose is not touched before the chain below commits P)
     // ---- map queue (simpleMapMaker.cpp:147-158, 34-41) ----
     if (p.map_capacity > 0) {
         const int cap = p.map_capacity;
@@ -430,12 +386,9 @@ __attribute__((noinline)) icet_status frame_tail(const icet_node_params& p, Stre
         sn.insert(sn.end(), {0.f, 0.f, 0.f});
     }
     // X_homo = X_homo * X_homo_i (odometry.cpp:91-98)
-    const float Hi[16] = {R[0], R[1], R[2], X[0], R[3], R[4], R[5], X[1], R[6], R[7], R[8], X[2], 0, 0, 0, 1};
-    float P[16];
-    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) { float acc = 0.f; for (int k = 0; k < 4; k++) acc += st.pose[r * 4 + k] * Hi[k * 4 + c]; P[r * 4 + c] = acc; }
     std::memcpy(st.pose, P, sizeof(P));
     res->solved = 1; res->n_kept = nk;
-    std::memcpy(res->X, X, sizeof(X)); std::memcpy(res->pose, P, sizeof(P)); quat_of(P, res->quat);
+    std::memcpy(res->X, X, sizeof(X)); std::memcpy(res->pose, P, sizeof(P)); std::memcpy(res->quat, quat, sizeof(quat));
     res->map_rows = map_rows(p, st);
     return ICET_OK;
 }
@@ -973,6 +926,15 @@ icet_status icet_node_last_timing(icet_node* nd, float out_ms[3]) {
     NCHK(nd, hipEventElapsedTime(&b, nd->pipelined ? nd->ev[5] : nd->ev[1], nd->ev[2]));
     if (nd->timed_map) { NCHK(nd, hipEventSynchronize(nd->ev[3])); NCHK(nd, hipEventElapsedTime(&c, nd->ev[4], nd->ev[3])); }
     out_ms[0] = a; out_ms[1] = b; out_ms[2] = c;
+    return ICET_OK;
+}
+
+// Test hook, host only: the body frame_tail calls (node_tail_scalars), on the caller's X and pose
+icet_status icet_debug_node_tail(const float X[6], const float pose_in[16], float R[9], float Rinv[9], float pose_out[16], float quat[4]) {
+    if (!X || !pose_in || !R || !Rinv || !pose_out || !quat) return ICET_ERR_BAD_ARG;
+    float P[16];                                                  // (pose_out may be pose_in)
+    node_tail_scalars(X, pose_in, R, Rinv, P, quat);
+    std::memcpy(pose_out, P, sizeof(P));
     return ICET_OK;
 }
 

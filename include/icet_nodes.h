@@ -105,6 +105,12 @@ icet_status icet_node_snail_trail(icet_node* node, float* out, int64_t ld, int64
  * one-launch odometry frame (range filter on, no map, no aligned cloud / snail trail, pipelined) unless the node has ICET_NODE_TIME_PHASES. */
 icet_status icet_node_last_timing(icet_node* node, float out_ms[3]);
 
+/* Test hook, host only (no context, no launch): the scalars of a frame's tail exactly as frame_tail evaluates them.  X is the frame's solution (after the guard),
+ * pose_in the accumulated pose before the frame (row-major 4 x 4); R is the frame's rotation (row-major, utils::R of X[3..5]), Rinv the inverse the map ring, the
+ * aligned cloud and the snail trail are multiplied by, pose_out = pose_in * [R X[0..2]; 0 1] and quat its quaternion (x, y, z, w).  The library has ONE compiled
+ * body for these steps; every solved frame and this hook call it.  ICET_ERR_BAD_ARG for a NULL pointer. */
+icet_status icet_debug_node_tail(const float X[6], const float pose_in[16], float R[9], float Rinv[9], float pose_out[16], float quat[4]);
+
 /* --- node groups: many lidar streams advanced in one call -------------------------------------------------------------------------------------------------
  * A frame of one stream needs the previous frame's X, so one stream cannot go faster than the launch chain of its frame; a vehicle with several lidars, a server
  * with several vehicles or an offline run over many drives has many streams.  A group holds n_streams independent nodes that share one icet_node_params, and one
