@@ -8,6 +8,7 @@ the same member names, and calls ``icet_solve`` in ``libicet_hip.so`` (include/i
 
 There is no CPU fallback: if the HIP library is missing or no GPU is usable this module raises.
 """
+import contextlib
 import ctypes as C
 import os
 import numpy as np
@@ -34,7 +35,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
                     "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
                     "icet_keyframe_store_close_coarse_device",
-                    "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_debug_pose_graph_step",
+                    "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_debug_pose_graph_step", "icet_debug_pose_graph_direct",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -131,7 +132,7 @@ class PoseGraphOptions(C.Structure):
 class PoseGraphResult(C.Structure):
     """icet_pose_graph_result (include/icet_hip.h), 40 bytes."""
     _fields_ = [("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("max_dx", C.c_double), ("status", C.c_int32), ("gn_iterations", C.c_int32),
-                ("pcg_iterations", C.c_int32), ("reserved", C.c_int32)]
+                ("pcg_iterations", C.c_int32), ("solver", C.c_int32)]
 
 
 class PoseGraphStep(C.Structure):
@@ -141,7 +142,33 @@ class PoseGraphStep(C.Structure):
                [(k, C.c_double) for k in ("chi2_start", "chi2_trial", "max_dx")]
 
 
-assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40 and C.sizeof(PoseGraphStep) == 152
+class PoseGraphDirectStep(C.Structure):
+    """icet_pose_graph_direct_step (include/icet_hip.h), 176 bytes."""
+    ARRAYS = ("D", "B", "A", "g", "Z", "Wm", "L", "Ks", "Lk", "x0", "x", "Pt", "chi_trial", "q")
+    _fields_ = [(k, C.c_void_p) for k in ARRAYS] + [("ends", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("ends_capacity", "m", "factor_status", "wm_status", "ks_status", "band_solves", "trial", "reserved")] + \
+               [(k, C.c_double) for k in ("chi2_start", "chi2_trial", "max_dx")]
+
+
+assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40 and C.sizeof(PoseGraphStep) == 152 and C.sizeof(PoseGraphDirectStep) == 176
+# option "pg_solver": the pose-graph optimiser's linear solve
+PG_SOLVER_CG, PG_SOLVER_DIRECT, PG_SOLVER_AUTO = range(3)
+PG_SOLVERS = {"cg": PG_SOLVER_CG, "direct": PG_SOLVER_DIRECT, "auto": PG_SOLVER_AUTO}
+PG_DIRECT_MAX_ENDS = 128
+
+
+def pose_graph_ends(n, closures, fixed=None):
+    """The END nodes of the direct solve, ascending: the distinct ends of the closures that lie off the band (|i - j| >= 2) between two free nodes (node 0 and
+    the nodes with fixed[k] != 0 are not free)."""
+    fx = np.zeros(n, bool); fx[0] = True
+    if fixed is not None:
+        fx |= np.asarray(fixed).reshape(-1) != 0
+    ends = set()
+    for c in closures:
+        i, j = int(c[0]), int(c[1])
+        if abs(i - j) >= 2 and not fx[i] and not fx[j]:
+            ends.update((i, j))
+    return sorted(ends)
 # icet_pose_graph_step.cg_end
 PG_CG_TOLERANCE, PG_CG_ZERO, PG_CG_CAP, PG_CG_FAILED = range(4)
 # icet_pose_graph_result.status
@@ -281,6 +308,8 @@ def load_library():
     L.icet_pose_graph_optimize.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(PoseGraphOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseGraphResult)]
     L.icet_pose_graph_optimize_device.argtypes = L.icet_pose_graph_optimize.argtypes
+    L.icet_debug_pose_graph_direct.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(PoseGraphOptions), C.c_int32, C.c_void_p, C.POINTER(PoseGraphDirectStep)]
     L.icet_debug_pose_graph_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(PoseGraphOptions), C.c_int32, C.c_void_p, C.POINTER(PoseGraphStep)]
     L.icet_keyframe_store_enable_appearance.argtypes = [C.c_void_p, C.POINTER(AppearanceParams)]
@@ -534,6 +563,23 @@ class Context:
         """Launch-shape / diagnostic knob of this context (icet_set_option, include/icet_hip.h).  Launch-shape knobs leave the result
         bits alone; force_exact / guard_scale / lut_polar_quantile keep every decision but regroup float partial sums."""
         self._check(load_library().icet_set_option(self._h, name.encode(), float(value)))
+        if name == "pg_solver":
+            self._pg_solver = int(value)
+
+    @contextlib.contextmanager
+    def _pose_graph_solver(self, solver):
+        """Option "pg_solver" for one call: ``solver`` None leaves the context's option alone; "cg", "direct", "auto" set it and put the old value back."""
+        if solver is None:
+            yield
+            return
+        if solver not in PG_SOLVERS:
+            raise IcetError(ICET_ERR_BAD_ARG, 'solver must be None, "cg", "direct" or "auto"')
+        old = getattr(self, "_pg_solver", PG_SOLVER_CG)
+        self.set_option("pg_solver", PG_SOLVERS[solver])
+        try:
+            yield
+        finally:
+            self.set_option("pg_solver", old)
 
     def last_timing(self):
         t = np.zeros(4, np.float32)
@@ -615,13 +661,15 @@ class Context:
     @staticmethod
     def _pose_graph_result(res):
         return dict(chi2_initial=float(res.chi2_initial), chi2_final=float(res.chi2_final), status=int(res.status), gn_iterations=int(res.gn_iterations),
-                    max_dx=float(res.max_dx), pcg_iterations=int(res.pcg_iterations))
+                    max_dx=float(res.max_dx), pcg_iterations=int(res.pcg_iterations), solver=int(res.solver))
 
-    def optimize_pose_graph(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0):
+    def optimize_pose_graph(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0, solver=None):
         """icet_pose_graph_optimize: the poses (n x 4 x 4 float32) of a chain with odometry measurements ``odo_X`` ((n - 1) x 6) and information ``odo_info``
         ((n - 1) x 6 x 6) and the closure edges ``closures`` = (i, j, X, info) tuples as closure_edges returns them, optimised on the device.  Node 0 and the
         nodes with ``fixed[k] != 0`` stay.  Returns dict(poses n x 4 x 4 float32, poses64 n x 4 x 4, chi2_initial, chi2_final, status (POSE_GRAPH_*),
-        gn_iterations, max_dx, edge_chi2 2 x E, pcg_iterations).  A status of 2 or 3 is a result, not an error: the poses are then the inputs."""
+        gn_iterations, max_dx, edge_chi2 2 x E, pcg_iterations, solver).  A status of 2 or 3 is a result, not an error: the poses are then the inputs.
+        ``solver``: None (the context's option "pg_solver"), "cg", "direct" or "auto" for this call; the result's ``solver`` is 1 when the direct solve ran --
+        it ignores max_pcg and pcg_tol, and converges at the defaults where the closures' information is strong (closures from find_closures: use "auto")."""
         P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
         oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
         if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
@@ -629,9 +677,10 @@ class Context:
         ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol)
         E = n - 1 + ci.shape[0]
         out = np.zeros((n, 16), np.float32); p64 = np.zeros((n, 12), np.float64); chi = np.zeros((2, E), np.float64); res = PoseGraphResult()
-        self._check(load_library().icet_pose_graph_optimize(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data,
-                                                            cX.ctypes.data, cI.ctypes.data, _data(fx), C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data,
-                                                            C.byref(res)))
+        with self._pose_graph_solver(solver):
+            self._check(load_library().icet_pose_graph_optimize(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data,
+                                                                cX.ctypes.data, cI.ctypes.data, _data(fx), C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data,
+                                                                C.byref(res)))
         T64 = np.zeros((n, 4, 4)); T64[:, 3, 3] = 1.0; T64[:, :3, :3] = p64[:, :9].reshape(n, 3, 3); T64[:, :3, 3] = p64[:, 9:]
         return dict(self._pose_graph_result(res), poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
 
@@ -660,12 +709,39 @@ class Context:
         arr["cg_scalars"] = arr["cg_scalars"][:min(out["band_solves"], cap)]
         return dict(out, **arr)
 
+    def debug_pose_graph_direct(self, poses, odo_X, odo_info, closures=(), fixed=None, damping=0.0, p=None):
+        """icet_debug_pose_graph_direct: the optimiser's first iteration with the DIRECT solve on the device, its intermediate arrays copied out, and q = H p
+        for every vector of ``p``.  Returns a dict: ends (m int32), D, B n x 6 x 6, A C x 6 x 6, g, x0, x n x 6, Z 6n x q, Wm, L, Ks, Lk q x q (q = 6 m), Pt
+        n x 12, chi_trial, q K x n x 6, and the scalars of icet_pose_graph_direct_step."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
+        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
+        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        closures = list(closures)
+        ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, damping, 0, 0.0)
+        nc = ci.shape[0]; E = n - 1 + nc
+        m = len(pose_graph_ends(n, closures, fixed)); q = 6 * m
+        pv = np.zeros((0, n, 6)) if p is None else np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, n, 6))
+        nan = lambda *shape: np.full(shape, np.nan)      # noqa: E731
+        arr = dict(D=nan(n, 6, 6), B=nan(n, 6, 6), A=nan(nc, 6, 6), g=nan(n, 6), Z=nan(6 * n, q), Wm=nan(q, q), L=nan(q, q), Ks=nan(q, q), Lk=nan(q, q), x0=nan(n, 6),
+                   x=nan(n, 6), Pt=nan(n, 12), chi_trial=nan(E), q=np.zeros(pv.shape))
+        ends = np.full(m, -1, np.int32)
+        st = PoseGraphDirectStep()
+        for k in PoseGraphDirectStep.ARRAYS:
+            setattr(st, k, arr[k].ctypes.data)
+        st.ends = ends.ctypes.data; st.ends_capacity = m
+        self._check(load_library().icet_debug_pose_graph_direct(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, nc, ci.ctypes.data, cj.ctypes.data, cX.ctypes.data,
+                                                                cI.ctypes.data, _data(fx), C.byref(opt), pv.shape[0], pv.ctypes.data, C.byref(st)))
+        out = {k: int(getattr(st, k)) for k in ("m", "factor_status", "wm_status", "ks_status", "band_solves", "trial")}
+        out.update({k: float(getattr(st, k)) for k in ("chi2_start", "chi2_trial", "max_dx")})
+        return dict(out, ends=ends, **arr)
+
     def optimize_pose_graph_device(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0,
-                                   clo_X=None, clo_info=None):
+                                   clo_X=None, clo_info=None, solver=None):
         """icet_pose_graph_optimize_device for torch tensors on this context's device: ``poses`` n x 4 x 4, ``odo_X`` (n - 1) x 6, ``odo_info`` (n - 1) x 6 x 6,
         float32 and contiguous.  ``closures`` as in optimize_pose_graph (their X and info are uploaded), or (i, j) pairs with ``clo_X`` C x 6 and ``clo_info``
         C x 6 x 6 as float32 tensors.  Returns the dict of optimize_pose_graph with poses (float32), poses64 (n x 12 float64: R row-major, then t) and edge_chi2
-        (2 x E float64) as tensors on the device.  The call returns when the result is known."""
+        (2 x E float64) as tensors on the device.  ``solver`` as in optimize_pose_graph.  The call returns when the result is known."""
         import torch
         for t in (poses, odo_X, odo_info):
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
@@ -688,9 +764,10 @@ class Context:
         out = torch.zeros((n, 4, 4), dtype=torch.float32, device=poses.device); p64 = torch.zeros((n, 12), dtype=torch.float64, device=poses.device)
         chi = torch.zeros((2, E), dtype=torch.float64, device=poses.device); res = PoseGraphResult()
         torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
-        self._check(load_library().icet_pose_graph_optimize_device(self._h, n, _vp(poses.data_ptr()), _vp(odo_X.data_ptr()), _vp(odo_info.data_ptr()), ci.shape[0],
-                                                                   ci.ctypes.data, cj.ctypes.data, _vp(clo_X.data_ptr()), _vp(clo_info.data_ptr()), _data(fx), C.byref(opt),
-                                                                   _vp(out.data_ptr()), _vp(p64.data_ptr()), _vp(chi.data_ptr()), C.byref(res)))
+        with self._pose_graph_solver(solver):
+            self._check(load_library().icet_pose_graph_optimize_device(self._h, n, _vp(poses.data_ptr()), _vp(odo_X.data_ptr()), _vp(odo_info.data_ptr()), ci.shape[0],
+                                                                       ci.ctypes.data, cj.ctypes.data, _vp(clo_X.data_ptr()), _vp(clo_info.data_ptr()), _data(fx), C.byref(opt),
+                                                                       _vp(out.data_ptr()), _vp(p64.data_ptr()), _vp(chi.data_ptr()), C.byref(res)))
         return dict(self._pose_graph_result(res), poses=out, poses64=p64, edge_chi2=chi)
 
     def debug_fix(self, values):

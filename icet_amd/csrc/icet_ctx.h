@@ -65,6 +65,7 @@ struct icet_ctx {
     // launches of a single-pair solve then cost one hipGraphLaunch on the host, and the command processor runs them back to back.
     struct GraphKey { int64_t v[47]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key + the keyframe source (graph_key_of)
     struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false; };
+    int pg_solver = 0;                                         // icet_pose_graph_optimize: 0 conjugate gradients, 1 the direct solve, 2 auto (option "pg_solver")
     bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
     GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
     GraphSlot g_scored, g_score;                               // indexed registrations + score (icet_register_indexed_scored_device), the score of given poses (icet_score_indexed_device)

@@ -23,6 +23,7 @@ namespace icet_pg_rule {
 
 constexpr int kMaxNodes = 4096;
 constexpr int kMaxClosures = 512;
+constexpr int kPgDirectMaxEnds = 128;       // the direct solve (icet_posegraph_direct.h): end nodes of closures off the band; 6 x 128 = 768 columns, one workgroup factors them
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kJacStep = 1e-6;            // central differences, fixed step
 constexpr double kPivotRel = 1e-13;          // a Cholesky pivot at or below this fraction of its diagonal entry: not positive definite

@@ -5,6 +5,8 @@
 // the band is the kernel that matters: ONE workgroup of 256 threads factors it by block Cholesky and sweeps it forward and back (a block Thomas recurrence,
 // sequential in the node index: one thread walks it, out of chunks of 32 nodes that all threads stage through LDS).  Around it: small kernels that each do one
 // thing on plain global arrays, every body in icet_posegraph_body.h, driven from the host by icet_posegraph_driver.h.  No kernel waits on another block.
+// Option "pg_solver" replaces the conjugate gradients by a direct solve over the closures' end nodes (icet_posegraph_direct.h): k_pg_z solves the band for
+// all their unit columns in one launch, one thread per column.
 #include "icet_ctx.h"
 #include "icet_posegraph_driver.h"
 
@@ -41,6 +43,23 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_precond(PgArgs a) { __shared_
 __global__ __launch_bounds__(kPgThreads) void k_pg_step(PgArgs a) { __shared__ PgRed red; pg_group_step(a, red); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_stats(PgArgs a) { __shared__ PgRed red; pg_group_stats(a, red); }
 
+// the direct solve (icet_posegraph_direct.h).  k_pg_z is the kernel that matters: one thread per column of Z walks the chain forward and back.
+#define ICET_PG_GRID_KERNEL(name, body) \
+    __global__ __launch_bounds__(kPgGridThreads) void name(PgArgs a, PgDirect d, int count) { \
+        const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x); \
+        if (gi < count) body(a, d, gi); \
+    }
+ICET_PG_GRID_KERNEL(k_pg_z, pg_z)
+ICET_PG_GRID_KERNEL(k_pg_wm, pg_wm)
+ICET_PG_GRID_KERNEL(k_pg_sl, pg_sl)
+ICET_PG_GRID_KERNEL(k_pg_ks, pg_ks)
+ICET_PG_GRID_KERNEL(k_pg_zw, pg_zw)
+ICET_PG_GRID_KERNEL(k_pg_resid, pg_resid)
+#undef ICET_PG_GRID_KERNEL
+__global__ __launch_bounds__(kPgThreads) void k_pg_chol(PgArgs a, PgDirect d, int which) { pg_group_chol(a, d, which); }
+__global__ __launch_bounds__(kPgThreads) void k_pg_band(PgArgs a, PgDirect d) { __shared__ PgShared sh; pg_group_band(a, d, sh); }
+__global__ __launch_bounds__(kPgThreads) void k_pg_cap_solve(PgArgs a, PgDirect d) { pg_group_cap_solve(a, d); }
+
 namespace {
 
 // The device's backend of pg_optimise: launches on the context's stream; the scalars come back through pinned memory.
@@ -74,6 +93,29 @@ struct PgDeviceBackend {
         }
         return ok(hipGetLastError());
     }
+    bool dgrid(PgDirectGridKernel k, int count, const PgArgs& a, const PgDirect& d) {
+        if (count <= 0) return true;
+        const dim3 g((unsigned)((count + kPgGridThreads - 1) / kPgGridThreads)), b(kPgGridThreads);
+        switch (k) {
+            case kPgZ:     hipLaunchKernelGGL(k_pg_z, g, b, 0, stream, a, d, count); break;
+            case kPgWm:    hipLaunchKernelGGL(k_pg_wm, g, b, 0, stream, a, d, count); break;
+            case kPgSl:    hipLaunchKernelGGL(k_pg_sl, g, b, 0, stream, a, d, count); break;
+            case kPgKs:    hipLaunchKernelGGL(k_pg_ks, g, b, 0, stream, a, d, count); break;
+            case kPgZw:    hipLaunchKernelGGL(k_pg_zw, g, b, 0, stream, a, d, count); break;
+            case kPgResid: hipLaunchKernelGGL(k_pg_resid, g, b, 0, stream, a, d, count); break;
+        }
+        return ok(hipGetLastError());
+    }
+    bool dgroup(PgDirectGroupKernel k, const PgArgs& a, const PgDirect& d) {
+        const dim3 g(1), b(kPgThreads);
+        switch (k) {
+            case kPgCholW:    hipLaunchKernelGGL(k_pg_chol, g, b, 0, stream, a, d, 0); break;
+            case kPgCholK:    hipLaunchKernelGGL(k_pg_chol, g, b, 0, stream, a, d, 1); break;
+            case kPgBand:     hipLaunchKernelGGL(k_pg_band, g, b, 0, stream, a, d); break;
+            case kPgCapSolve: hipLaunchKernelGGL(k_pg_cap_solve, g, b, 0, stream, a, d); break;
+        }
+        return ok(hipGetLastError());
+    }
     bool scalars(const PgArgs& a, double out[kPgScalars]) {
         if (!ok(hipMemcpyAsync(h_sc, a.sc, sizeof(double) * kPgScalars, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
         for (int i = 0; i < kPgScalars; i++) out[i] = h_sc[i];
@@ -101,27 +143,44 @@ struct PgHostIo {          // the host-pointer form's staging, behind pg_bind's 
 
 icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci, const int32_t* cj,
                    const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt, float* poses_out, double* poses64_out,
-                   double* edge_chi2, icet_pose_graph_result* result, int32_t K = 0, const double* dbg_p = nullptr, icet_pose_graph_step* dbg = nullptr) {
+                   double* edge_chi2, icet_pose_graph_result* result, int32_t K = 0, const double* dbg_p = nullptr, icet_pose_graph_step* dbg = nullptr,
+                   icet_pose_graph_direct_step* ddbg = nullptr) {
     if (!c) return ICET_ERR_BAD_ARG;
-    if (!poses || (!dbg && (!poses_out || !result)) || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_optimize: bad argument"; return ICET_ERR_BAD_ARG; }
+    const bool hook = dbg || ddbg;
+    if (!poses || (!hook && (!poses_out || !result)) || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_optimize: bad argument"; return ICET_ERR_BAD_ARG; }
     if ((n > 1 && (!odo_X || !odo_info)) || (n_closures > 0 && (!ci || !cj || !clo_X || !clo_info))) { c->err = "icet_pose_graph_optimize: null array"; return ICET_ERR_BAD_ARG; }
     if (!pg::closures_ok(n, n_closures, ci, cj)) { c->err = "icet_pose_graph_optimize: a closure's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
     const icet_pose_graph_options o = opt ? *opt : pg_default_options();
     if (o.gn_iters < 1) { c->err = "icet_pose_graph_optimize: gn_iters < 1"; return ICET_ERR_BAD_ARG; }
+    PgGraph graph;
+    graph.build(n, n_closures, ci, cj, fixed);
+    // the linear solve: the context's option "pg_solver" (the step hook is conjugate gradients, the direct hook direct)
+    const int m_ends = (int)graph.ends.size();
+    if ((ddbg || (!dbg && c->pg_solver == 1)) && m_ends > kPgDirectMaxEnds) {
+        c->err = "icet_pose_graph_optimize: the direct solve takes at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " +
+                 std::to_string(m_ends) + " (option pg_solver 2 falls back to conjugate gradients)";
+        return ICET_ERR_UNSUPPORTED;
+    }
+    if (ddbg && ddbg->ends_capacity != m_ends) { c->err = "icet_debug_pose_graph_direct: ends_capacity is not the graph's count of end nodes (" + std::to_string(m_ends) + ")"; return ICET_ERR_BAD_ARG; }
+    const bool direct = ddbg || (!dbg && (c->pg_solver == 1 || (c->pg_solver == 2 && m_ends >= 1 && m_ends <= kPgDirectMaxEnds)));
     HIPCHK(c, hipSetDevice(c->device));
     c->armed_calls = 2;
 
-    PgGraph graph;
-    graph.build(n, n_closures, ci, cj, fixed);
     PgArgs a{};
+    PgDirect dir{};
     a.N = n; a.C = n_closures; a.E = pg::edge_count(n, n_closures);
     const size_t N = (size_t)n, E = (size_t)a.E, C = (size_t)n_closures, n_items = graph.items.size();
     PgArena arena;
     PgGraphDev gd{};
+    PgDirectDev dd{};
     PgHostIo io;
     auto layout = [&]() {
         arena.used = 0;
         gd = pg_bind(a, arena, n_items);
+        if (direct) {
+            arena.used = (arena.used + 7) & ~(size_t)7;
+            dd = pg_bind_direct(a, dir, arena, (size_t)m_ends);
+        }
         if (host_io) {
             // (int32 lists end on a multiple of 4 bytes; the doubles of the staging need 8)
             arena.used = (arena.used + 7) & ~(size_t)7;
@@ -144,6 +203,7 @@ icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, con
     auto down = [&](void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && dst && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, c->stream); };
     up(gd.ei, graph.ei.data(), sizeof(int32_t) * E); up(gd.ej, graph.ej.data(), sizeof(int32_t) * E);
     up(gd.off, graph.off.data(), sizeof(int32_t) * (N + 1)); up(gd.items, graph.items.data(), sizeof(int32_t) * n_items);
+    if (direct) { up(dd.ends, graph.ends.data(), sizeof(int32_t) * (size_t)m_ends); up(dd.end_of, graph.end_of.data(), sizeof(int32_t) * N); }
     if (host_io) {
         up(io.poses, poses, sizeof(float) * N * 16); up(io.odo_X, odo_X, sizeof(float) * (N - 1) * 6); up(io.odo_info, odo_info, sizeof(float) * (N - 1) * 36);
         up(io.clo_X, clo_X, sizeof(float) * C * 6); up(io.clo_info, clo_info, sizeof(float) * C * 36);
@@ -157,10 +217,12 @@ icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, con
     bool done = false;
     if (e == hipSuccess) {
         // (the graph's lists and the caller's arrays outlive the synchronisation below; the stream orders the copies before the kernels)
-        done = dbg ? pg_debug_step(be, a, o, graph.c_offband, K, dbg_p, dbg) : pg_optimise(be, a, o, graph.c_offband, &res);
+        done = ddbg ? pg_debug_direct_step(be, a, dir, o, K, dbg_p, ddbg)
+             : dbg ? pg_debug_step(be, a, o, graph.c_offband, K, dbg_p, dbg)
+             : direct ? pg_optimise_direct(be, a, dir, o, &res) : pg_optimise(be, a, o, graph.c_offband, &res);
         if (!done) e = be.err;
     }
-    if (done && host_io && !dbg) {
+    if (done && host_io && !hook) {
         down(poses_out, io.poses_out, sizeof(float) * N * 16); down(poses64_out, io.poses64, sizeof(double) * N * 12); down(edge_chi2, io.edge_chi2, sizeof(double) * 2 * E);
     }
     const hipError_t es = hipStreamSynchronize(c->stream);
@@ -196,6 +258,15 @@ icet_status icet_debug_pose_graph_step(icet_ctx* c, int32_t n, const float* pose
     if (!c) return ICET_ERR_BAD_ARG;
     if (!out || K < 0 || (K > 0 && (!p || !out->q)) || out->cg_capacity < 0 || (out->cg_capacity > 0 && !out->cg_scalars)) { c->err = "icet_debug_pose_graph_step: bad argument"; return ICET_ERR_BAD_ARG; }
     return pg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, nullptr, nullptr, nullptr, nullptr, K, p, out);
+}
+
+// Test hook: the first iteration with the direct solve, its intermediate arrays copied out (pg_debug_direct_step).
+icet_status icet_debug_pose_graph_direct(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                         const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
+                                         int32_t K, const double* p, icet_pose_graph_direct_step* out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!out || K < 0 || (K > 0 && (!p || !out->q)) || out->ends_capacity < 0 || out->reserved != 0) { c->err = "icet_debug_pose_graph_direct: bad argument"; return ICET_ERR_BAD_ARG; }
+    return pg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, nullptr, nullptr, nullptr, nullptr, K, p, nullptr, out);
 }
 
 // Test hook: one block-tridiagonal system through the optimiser's factor and sweeps.  diag, sub: n x 36 doubles (sub[k] is the block at (k, k - 1); sub[0] is not

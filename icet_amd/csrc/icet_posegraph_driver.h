@@ -1,14 +1,17 @@
 // icet_amd/csrc/icet_posegraph_driver.h -- the pose-graph optimiser's driver, written ONCE: the Gauss-Newton loop, the preconditioned
-// conjugate gradients, the accept rule and what a failure returns.  HIP-free.  It runs the bodies of icet_posegraph_body.h through a BACKEND that launches a
+// conjugate gradients, the direct solve over the closures (pg_direct_solve), the accept rule and what a failure returns.  HIP-free.  It runs the bodies of icet_posegraph_body.h through a BACKEND that launches a
 // kernel (or loops over its index range on the host) and reads the few scalars back:
 //     bool grid(PgGridKernel, int count, const PgArgs&)      the body for every global index below count (count 0: nothing)
 //     bool group(PgGroupKernel, const PgArgs&)               the body as one workgroup
 //     bool scalars(const PgArgs&, double out[kPgScalars])    wait for what was enqueued, then a.sc on the host
 //     bool fetch(void* host, const void* dev, size_t bytes), put(void* dev, const void* host, size_t bytes)      (the test hook only) copies, complete on return
+//     bool dgrid(PgDirectGridKernel, int count, const PgArgs&, const PgDirect&), dgroup(PgDirectGroupKernel, const PgArgs&, const PgDirect&)
+//                                                            the direct solve's bodies (icet_posegraph_direct.h); only pg_direct_solve calls them
 // each false for a failure of the backend (the driver then returns false at once).  icet_posegraph.hip has the device's backend,
-// tests/cpp/test_posegraph_optimize.cpp the host's.
+// tests/cpp/test_posegraph_optimize.cpp and tests/cpp/test_posegraph_direct.cpp the host's.
 #pragma once
 #include "icet_posegraph_body.h"
+#include "icet_posegraph_direct.h"
 
 #include <cmath>
 #include <vector>
@@ -22,14 +25,18 @@ inline icet_pose_graph_options pg_default_options() { icet_pose_graph_options o;
 // The graph on the host: the edges' ends, the incidence lists, the count of closures that lie off the band between two free nodes.
 struct PgGraph {
     std::vector<int32_t> ei, ej, off, items;
+    std::vector<int32_t> ends, end_of;      // the direct solve: the distinct ends of the closures counted by c_offband, ascending | per node its index in ends or -1
     int c_offband = 0;
     void build(int N, int C, const int32_t* ci, const int32_t* cj, const uint8_t* fixed) {
         pg::build_incidence(N, C, ci, cj, fixed, ei, ej, off, items);
         c_offband = 0;
+        end_of.assign((size_t)N, -1);
         for (int c = 0; c < C; c++) {
             const int i = ci[c], j = cj[c];
-            if ((i - j >= 2 || j - i >= 2) && off[i + 1] != off[i] && off[j + 1] != off[j]) c_offband++;
+            if ((i - j >= 2 || j - i >= 2) && off[i + 1] != off[i] && off[j + 1] != off[j]) { c_offband++; end_of[i] = 0; end_of[j] = 0; }
         }
+        ends.clear();
+        for (int k = 0; k < N; k++) if (end_of[k] == 0) { end_of[k] = (int32_t)ends.size(); ends.push_back(k); }
     }
 };
 
@@ -90,12 +97,12 @@ inline bool pg_cg(Backend& be, PgArgs& a, int cap, double pcg_tol, int* pcg, int
     return true;
 }
 
-// The run.  `a` is bound (pg_bind), the graph uploaded, the caller's arrays in place.  true: *res is the result (its status says how the run ended).
-template <class Backend>
-inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, icet_pose_graph_result* res) {
+// The Gauss-Newton loop, written once over the LINEAR SOLVE: solve(a, &pcg, &bad) runs behind kPgFactor, leaves dx in a.x, counts its band solves on and sets
+// *bad to a failure's status; false for a failure of the backend.
+template <class Backend, class Solve>
+inline bool pg_gauss_newton(Backend& be, PgArgs a, const icet_pose_graph_options& o, Solve&& solve, int solver, icet_pose_graph_result* res) {
     double h[kPgScalars];
     const int N = a.N, E = a.E, C = a.C;
-    const double pcg_tol = o.pcg_tol > 0.0 ? o.pcg_tol : kPgDefaultPcgTol;
     const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
     a.damping = o.damping; a.trial = 0; a.first = 0; a.failed = 0;
     if (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
@@ -108,7 +115,7 @@ inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o,
         its++;
         if (!be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) || !be.grid(kPgOffband, C * 36, a) || !be.group(kPgFactor, a)) return false;
         int bad = 0;
-        if (!pg_cg(be, a, pg_cg_cap(c_offband, o), pcg_tol, &pcg, &bad)) return false;
+        if (!solve(a, &pcg, &bad)) return false;
         if (bad) { status = bad; failed = true; break; }
         a.trial = 1;
         if (!be.grid(kPgRetract, N, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
@@ -129,7 +136,124 @@ inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o,
     const int n_fin = N > E ? N : E;
     if (!be.grid(kPgFinish, n_fin, a) || !be.scalars(a, h)) return false;
     res->chi2_initial = chi2_initial; res->chi2_final = failed ? chi2_initial : chi2; res->max_dx = max_dx;
-    res->status = status; res->gn_iterations = its; res->pcg_iterations = pcg; res->reserved = 0;
+    res->status = status; res->gn_iterations = its; res->pcg_iterations = pcg; res->solver = solver;
+    return true;
+}
+
+// The run.  `a` is bound (pg_bind), the graph uploaded, the caller's arrays in place.  true: *res is the result (its status says how the run ended).
+template <class Backend>
+inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, icet_pose_graph_result* res) {
+    const double pcg_tol = o.pcg_tol > 0.0 ? o.pcg_tol : kPgDefaultPcgTol;
+    const int cap = pg_cg_cap(c_offband, o);
+    return pg_gauss_newton(be, a, o, [&](PgArgs& b, int* pcg, int* bad) { return pg_cg(be, b, cap, pcg_tol, pcg, bad); }, 0, res);
+}
+
+// ---- the direct solve (icet_posegraph_direct.h) --------------------------------------------------------------------------------------------------------------
+// Its work arrays, each at its exact size, beside pg_bind's in the same block: m end nodes, nq = 6 m.  Doubles first, then the two int32 lists.
+struct PgDirectDev { int32_t *ends, *end_of; };
+template <class Alloc>
+inline PgDirectDev pg_bind_direct(const PgArgs& a, PgDirect& d, Alloc& al, size_t m) {
+    const size_t N = (size_t)a.N, q = 6 * m;
+    d.nq = (int)q; d.refine = 0;
+    d.Z = al.d(N * 6 * q);
+    d.Wm = al.d(q * q); d.Lw = al.d(q * q); d.SL = al.d(q * q); d.Ks = al.d(q * q); d.Lk = al.d(q * q);
+    d.rdw = al.d(q); d.rdk = al.d(q); d.cv = al.d(q); d.ct = al.d(q); d.cu = al.d(q); d.cw = al.d(q);
+    d.y = al.d(N * 6);
+    PgDirectDev dd;
+    dd.ends = al.i(m); dd.end_of = al.i(N);
+    d.ends = dd.ends; d.end_of = dd.end_of;
+    return dd;
+}
+
+// What the test hook copies out of one direct solve (null: nothing)
+struct PgDirectTap { double *Z = nullptr, *Wm = nullptr, *L = nullptr, *Ks = nullptr, *Lk = nullptr, *x0 = nullptr; };
+
+// ONE linear solve H x = -g by the direct method, behind kPgFactor (which leaves r = -g): Z, Wm, its factor, Ks, its factor, x = apply(-g), then kPgDirectRefine
+// steps x += apply(-g - H x).  A fixed number of launches whatever the closures are; with no end node the single band solve.  Nothing is read back here: every
+// kernel behind a failed factorisation returns at once, and the caller reads the statuses with the scalars (pg_direct_status).
+template <class Backend>
+inline bool pg_direct_solve(Backend& be, PgArgs& a, PgDirect& d, int* pcg, const PgDirectTap* tap = nullptr) {
+    const int q = d.nq, n6 = a.N * 6;
+    const size_t sd = sizeof(double), qq = (size_t)q * (size_t)q;
+    auto get = [&](double* dst, const double* src, size_t count) { return !tap || !dst || count == 0 || be.fetch(dst, src, count * sd); };
+    d.refine = 0;
+    if (q == 0) {
+        if (!be.dgroup(kPgBand, a, d) || !be.dgrid(kPgZw, n6, a, d)) return false;
+        ++*pcg;
+        return get(tap ? tap->x0 : nullptr, a.x, (size_t)n6);
+    }
+    if (!be.dgrid(kPgZ, q, a, d) || !be.dgrid(kPgWm, q * q, a, d) || !be.dgroup(kPgCholW, a, d) || !be.dgrid(kPgSl, q * q, a, d) || !be.dgrid(kPgKs, q * q, a, d) ||
+        !be.dgroup(kPgCholK, a, d)) return false;
+    if (tap && (!get(tap->Z, d.Z, (size_t)n6 * (size_t)q) || !get(tap->Wm, d.Wm, qq) || !get(tap->L, d.Lw, qq) || !get(tap->Ks, d.Ks, qq) || !get(tap->Lk, d.Lk, qq))) return false;
+    if (!be.dgroup(kPgBand, a, d) || !be.dgroup(kPgCapSolve, a, d) || !be.dgrid(kPgZw, n6, a, d)) return false;
+    ++*pcg;
+    if (!get(tap ? tap->x0 : nullptr, a.x, (size_t)n6)) return false;
+    for (int it = 0; it < kPgDirectRefine; it++) {
+        PgArgs b = a;
+        b.p = a.x;                                  // q = H x through the kernel CG uses
+        if (!be.grid(kPgHp, n6, b) || !be.dgrid(kPgResid, n6, a, d)) return false;
+        d.refine = 1;
+        if (!be.dgroup(kPgBand, a, d) || !be.dgroup(kPgCapSolve, a, d) || !be.dgrid(kPgZw, n6, a, d)) return false;
+        d.refine = 0;
+        ++*pcg;
+    }
+    return true;
+}
+
+// The statuses behind a direct solve from the scalars: the band's factor, Wm's, Ks's; returns the first that failed, or 0.
+inline int pg_direct_status(const double h[kPgScalars], int st[3]) {
+    const int d = (int)h[kScDirect];
+    st[0] = (int)h[kScFactor]; st[1] = d % 4; st[2] = d / 4;
+    return st[0] ? st[0] : (st[1] ? st[1] : st[2]);
+}
+
+// The run with the direct solve in place of conjugate gradients: pg_optimise's loop, accept rule and outputs.  `a` is bound by pg_bind, `d` by pg_bind_direct.
+// o.max_pcg and o.pcg_tol are not used; pcg_iterations counts the single-right-hand-side band solves.
+template <class Backend>
+inline bool pg_optimise_direct(Backend& be, PgArgs a, PgDirect d, const icet_pose_graph_options& o, icet_pose_graph_result* res) {
+    return pg_gauss_newton(be, a, o, [&](PgArgs& b, int* pcg, int* bad) {
+        double h[kPgScalars]; int st[3], solves = 0;
+        if (!pg_direct_solve(be, b, d, &solves) || !be.scalars(b, h)) return false;
+        *bad = pg_direct_status(h, st);
+        if (!*bad) *pcg += solves;          // (behind a failed factorisation the solves were launched but did nothing)
+        return true;
+    }, 1, res);
+}
+
+// The direct solve's test hook (icet_debug_pose_graph_direct; the host test runs it too): the optimiser's FIRST iteration with the direct solve, kernel for
+// kernel, with its intermediate arrays copied out, then q = H p per caller vector.  Stops where the optimiser would: out->trial says whether the trial poses were taken.
+template <class Backend>
+inline bool pg_debug_direct_step(Backend& be, PgArgs a, PgDirect d, const icet_pose_graph_options& o, int K, const double* p, icet_pose_graph_direct_step* out) {
+    double h[kPgScalars];
+    const int N = a.N, E = a.E, C = a.C;
+    const size_t sd = sizeof(double), n6 = (size_t)N * 6;
+    const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
+    auto get = [&](double* dst, const double* src, size_t count) { return !dst || count == 0 || be.fetch(dst, src, count * sd); };
+    a.damping = o.damping; a.trial = 0; a.first = 0; a.failed = 0;
+    out->m = d.nq / 6; out->factor_status = 0; out->wm_status = 0; out->ks_status = 0; out->band_solves = 0; out->trial = 0;
+    out->chi2_start = 0.0; out->chi2_trial = 0.0; out->max_dx = 0.0;
+    if (out->ends && d.nq > 0 && !be.fetch(out->ends, d.ends, sizeof(int32_t) * (size_t)(d.nq / 6))) return false;
+    if (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
+    out->chi2_start = h[kScChi];
+    if (!std::isfinite(h[kScChi])) { out->factor_status = pg::kNonFinite; return true; }
+    if (!be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) || !be.grid(kPgOffband, C * 36, a) || !be.group(kPgFactor, a)) return false;
+    if (!get(out->D, a.D, (size_t)N * 36) || !get(out->B, a.B, (size_t)N * 36) || !get(out->A, a.A, (size_t)C * 36) || !get(out->g, a.g, n6)) return false;
+    PgDirectTap tap;
+    tap.Z = out->Z; tap.Wm = out->Wm; tap.L = out->L; tap.Ks = out->Ks; tap.Lk = out->Lk; tap.x0 = out->x0;
+    int pcg = 0, st[3];
+    if (!pg_direct_solve(be, a, d, &pcg, &tap) || !be.scalars(a, h)) return false;
+    const int bad = pg_direct_status(h, st);
+    out->factor_status = st[0]; out->wm_status = st[1]; out->ks_status = st[2]; out->band_solves = pcg;
+    if (!get(out->x, a.x, n6)) return false;
+    if (!bad) {
+        a.trial = 1;
+        if (!be.grid(kPgRetract, N, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
+        a.trial = 0;
+        out->trial = 1; out->chi2_trial = h[kScChi]; out->max_dx = h[kScMaxDx];
+        if (!get(out->Pt, a.Pt, (size_t)N * 12) || !get(out->chi_trial, a.chit, (size_t)E)) return false;
+    }
+    for (int k = 0; k < K && out->q; k++)
+        if (!be.put(a.p, p + (size_t)k * n6, n6 * sd) || !be.grid(kPgHp, N * 6, a) || !be.fetch(out->q + (size_t)k * n6, a.q, n6 * sd)) return false;
     return true;
 }
 

@@ -625,7 +625,8 @@ typedef struct icet_pose_graph_options {
 } icet_pose_graph_options;        /* 32 bytes; NULL = 10, 0, 1e-7, 0, default */
 typedef struct icet_pose_graph_result {
     double  chi2_initial, chi2_final, max_dx;
-    int32_t status, gn_iterations, pcg_iterations, reserved;
+    int32_t status, gn_iterations, pcg_iterations;
+    int32_t solver;               /* 0: conjugate gradients ran, 1: the direct solve (option "pg_solver", below) */
 } icet_pose_graph_result;         /* 40 bytes */
 icet_status icet_pose_graph_optimize(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
                                      const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
@@ -657,6 +658,31 @@ typedef struct icet_pose_graph_step {
 icet_status icet_debug_pose_graph_step(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
                                        const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
                                        const icet_pose_graph_options* opt, int32_t K, const double* p, icet_pose_graph_step* out);
+/* THE DIRECT SOLVE (option "pg_solver" of icet_set_option: 0 conjugate gradients, the default; 1 direct; 2 auto: direct when the graph has 1 .. 128 end nodes,
+ * else conjugate gradients).  H = M + U S U^T: M the band, U the components of the m distinct END nodes of the closures that lie off the band between two free
+ * nodes, q = 6 m.  Per Gauss-Newton iteration, behind the same factorisation of the band: Z = M^-1 U (q band solves, one thread each, in one launch),
+ * Wm = U^T Z = L L^T, Ks = I + L^T S L = Lk Lk^T, then x = apply(-g) and one step of iterative refinement x += apply(-g - H x), with
+ * apply(b) = y - Z L^-T Ks^-1 L^T S U^T y, y = M^-1 b.  A fixed number of launches whatever the closures are.  A pivot of either Cholesky factorisation at or
+ * below 1e-13 of its diagonal entry: _NOT_POSITIVE_DEFINITE (Ks is positive definite exactly when H is); not finite: _NON_FINITE; the outputs are then the inputs.
+ * With m = 0 the solve is the single band solve.  max_pcg and pcg_tol are not used; pcg_iterations counts the single-right-hand-side band solves (two per
+ * iteration, one with m = 0); result.solver is 1.  With option value 1 a graph of more than 128 end nodes is refused: ICET_ERR_UNSUPPORTED, nothing allocated,
+ * the outputs untouched.
+ * Test hook: icet_debug_pose_graph_step's arguments and conventions, the FIRST iteration with the direct solve whatever the option says.  HOST arrays the caller
+ * sizes, or NULL: D, B n x 36 | A n_closures x 36 | g, x0 (before the refinement), x n x 6 | Z (6 n) x q, row-major | Wm, L, Ks, Lk q x q row-major (L, Lk: zeros
+ * above the diagonal) | Pt n x 12 | chi_trial E | q_out K x n x 6 | ends m int32 (the end nodes, ascending).  ends_capacity (in): the m the caller sized the
+ * arrays for; it must equal the graph's (else ICET_ERR_BAD_ARG; more than 128: ICET_ERR_UNSUPPORTED).  factor_status, wm_status, ks_status: the three
+ * factorisations' statuses; band_solves as pcg_iterations; trial as in icet_pose_graph_step. */
+typedef struct icet_pose_graph_direct_step {
+    double *D, *B, *A, *g, *Z, *Wm, *L, *Ks, *Lk, *x0, *x, *Pt, *chi_trial, *q;
+    int32_t* ends;
+    int32_t ends_capacity;        /* in */
+    int32_t m, factor_status, wm_status, ks_status, band_solves, trial;
+    int32_t reserved;             /* zero */
+    double  chi2_start, chi2_trial, max_dx;
+} icet_pose_graph_direct_step;    /* 176 bytes */
+icet_status icet_debug_pose_graph_direct(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                         const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                         const icet_pose_graph_options* opt, int32_t K, const double* p, icet_pose_graph_direct_step* out);
 /* The optimiser's solver alone, as a test hook.  The odometry chain of a pose graph makes its normal equations block tridiagonal (6 x 6 blocks).
  * ONE symmetric positive definite block-tridiagonal system through the block Cholesky factorisation and the two sweeps, in double, one workgroup.
  * HOST arrays of doubles: diag n x 36, sub n x 36 (sub[k]: the block at (k, k - 1); sub[0] zero), rhs and x n x 6; *status 0, or ICET_BAND_NOT_POSITIVE_DEFINITE
@@ -684,7 +710,7 @@ icet_status icet_debug_block_tridiag(icet_ctx* ctx, int32_t n, const double* dia
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
  * bits; default 0: measured no faster on MI355X, where a device-scope fence is an L2 write-back), "batch_parts" (0 = automatic), "batch_stage" (0..4), "force_exact"
  * (every scan-2 point through the literal classification), "library_sort" (rocPRIM radix sort instead of
- * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
+ * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
  * the condition number |A|_F |A^-1|_F exceeds it is inverted by the literal restatement of the reference's statements -- column-pivoted QR
  * pseudo-inverse, eigenvectors, pruning -- instead of a Cholesky factorisation; 0 = always literal.  Not a launch-shape knob: between the two
  * routes cov / dx differ by rounding times the condition number).  Unknown name or value

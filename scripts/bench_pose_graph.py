@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The pose-graph optimiser (icet_pose_graph_optimize) at a range of sizes, against the NumPy model where that finishes (GPU box):
 
-    python scripts/bench_pose_graph.py [--nodes 64,256,1024,4096] [--closures 4,32,128] [--reps 3] [--model-max 1024] [--out FILE.json]
+    python scripts/bench_pose_graph.py [--nodes 64,256,1024,4096] [--closures 4,32,128] [--reps 3] [--model-max 1024] [--solver cg|direct|auto] [--out FILE.json]
 
 Graph (N, C): tests/pose_graph_model.py make_loop(N, pairs, seed=7) -- a 30 m loop with noisy odometry and C noisy closures between random nodes at least two
 apart, the first of them (0, N - 1) -- optimised from its drifted chain with the defaults (gn_iters 10, dx_tol 1e-7).  Per graph: the wall time of one
@@ -12,6 +12,9 @@ with the largest difference of the two results.  The split of a call into linear
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/bench_pose_graph.py --nodes 1024 --closures 32 --reps 1 --model-max 0
 
 (k_pg_linearise | k_pg_assemble + k_pg_offband | k_pg_factor | k_pg_precond + k_pg_hp + k_pg_step; k_pg_chi, k_pg_retract, k_pg_stats are the accept step).
+--solver: the linear solve (option "pg_solver"): cg (the default), direct (the kernels k_pg_z, k_pg_wm, k_pg_chol, k_pg_sl, k_pg_ks, k_pg_band,
+k_pg_cap_solve, k_pg_zw, k_pg_resid; a graph with more than 128 end nodes is refused and its row says so) or auto.  A row carries the solver that ran and
+q = 6 x the graph's end nodes.
 Prints one JSON line.
 """
 import argparse
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--closures", default="4,32,128")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--model-max", type=int, default=1024, help="largest N the NumPy model is timed at (0: never)")
+    ap.add_argument("--solver", default="cg", choices=["cg", "direct", "auto"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import numpy as np
@@ -50,14 +54,22 @@ def main():
                 if abs(i - j) >= 2:
                     pairs.append((i, j))
             g = pgm.make_loop(n, pairs, seed=7)
-            call = lambda: ctx.optimize_pose_graph(g["poses"], g["odo_X"], g["odo_info"], g["closures"])
-            call()
+            call = lambda: ctx.optimize_pose_graph(g["poses"], g["odo_X"], g["odo_info"], g["closures"], solver=a.solver)
+            q = 6 * len(api.pose_graph_ends(n, g["closures"]))
+            try:
+                call()
+            except api.IcetError as e:
+                if e.status != api.ICET_ERR_UNSUPPORTED:
+                    raise
+                rows.append(dict(n=n, closures=c, q=q, refused=str(e)))
+                print("# " + json.dumps(rows[-1]), file=sys.stderr, flush=True)
+                continue
             t = []
             for _ in range(max(a.reps, 1)):
                 t0 = time.perf_counter(); r = call(); t.append(time.perf_counter() - t0)
                 if t[-1] > 2.0:
                     break
-            row = dict(n=n, closures=c, ms=float(np.median(t)) * 1e3, calls=len(t), status=r["status"], gn_iterations=r["gn_iterations"], band_solves=r["pcg_iterations"],
+            row = dict(n=n, closures=c, q=q, solver=r["solver"], ms=float(np.median(t)) * 1e3, calls=len(t), status=r["status"], gn_iterations=r["gn_iterations"], band_solves=r["pcg_iterations"],
                        chi2_initial=r["chi2_initial"], chi2_final=r["chi2_final"])
             if n <= a.model_max:
                 t0 = time.perf_counter(); m = pgm.optimise(g["poses"], g["odo_X"], g["odo_info"], g["closures"]); row["model_ms"] = (time.perf_counter() - t0) * 1e3
