@@ -28,7 +28,21 @@
 
 using namespace icet;
 
+// The runtime behind every BufferGroup of the library (icet_buffers.h).
+int icet::mem::dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+int icet::mem::dev_free(void* p) { return hipFree(p); }
+int icet::mem::pinned_alloc(void** p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
+int icet::mem::pinned_free(void* p) { return hipHostFree(p); }
+
 namespace {
+
+// THE INVARIANT of every growth below (the ensure_* functions and the blocks of enqueue_keyframe, enqueue_rt2, enqueue_loop, icet_solve_begin and
+// icet_select_best_device): at every return, OK or not, a non-zero capacity means every pointer of its group (icet_ctx::Mem) is non-null and at least that large.
+// A group grows in three steps: ONE statement releases it and zeroes its capacity, the allocations follow, and the capacity is set after the last of them.  A
+// growth the runtime refuses thus leaves capacity 0 and null pointers, and the next call grows again.  The fit group (execbits, fit_items, fit_n_items; capacity
+// cap_fit_items) is sized from OTHER groups' capacities -- cap_pairs, cap_V, cap_n1 --, and no kernel is told its size: its capacity is zeroed as well wherever
+// the pair tables or the scan-1 arrays are released, so that it is rebuilt for their new sizes by the call that grows them or, if that call is refused anywhere
+// between, by the next one.  For it a non-zero capacity means: non-null and sized for the present cap_pairs, cap_V and cap_n1.
 
 // The REGISTRATION side of the workspace (Workspace, icet_internal.h): n_regs registrations on a grid of V voxels.  Leaves the keyframe side alone.
 icet_status ensure_regs(icet_ctx* c, int32_t n_regs, int V) {
@@ -37,19 +51,19 @@ icet_status ensure_regs(icet_ctx* c, int32_t n_regs, int V) {
     const int np = n_regs > w.cap_regs ? n_regs : w.cap_regs;
     const int VV = V > w.cap_reg_V ? V : w.cap_reg_V;
     const size_t pv = (size_t)np * VV;
+    BufferGroup& g = c->mem.regs;
     HIPCHK(c, hipStreamSynchronize(c->stream));                            // (also: no replay or copy still reads the registration staging)
-    HIPCHK(c, dev_realloc(w.acc, pv * kAccWords));
+    w.cap_regs = w.cap_reg_V = 0, g.release();
+    HIPCHK(c, g.device(w.acc, pv * kAccWords));
     HIPCHK(c, hipMemset(w.acc, 0, pv * kAccWords * sizeof(uint32_t)));
-    HIPCHK(c, dev_realloc(w.near_over_count, 2 * (size_t)np + 1));
+    HIPCHK(c, g.device(w.near_over_count, 2 * (size_t)np + 1));
     HIPCHK(c, hipMemset(w.near_over_count, 0, (2 * (size_t)np + 1) * sizeof(uint32_t)));
-    HIPCHK(c, dev_realloc(w.xf, (size_t)np * 48));
-    HIPCHK(c, dev_realloc(w.X, (size_t)np * 6));
-    HIPCHK(c, dev_realloc(w.desc_reg, np));
-    HIPCHK(c, dev_realloc(w.kf_of, (size_t)np + 1));
-    if (c->h_desc_reg) { HIPCHK(c, hipHostFree(c->h_desc_reg)); c->h_desc_reg = nullptr; }
-    if (c->h_kf_of) { HIPCHK(c, hipHostFree(c->h_kf_of)); c->h_kf_of = nullptr; }
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_desc_reg), sizeof(PairDesc) * np));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_kf_of), sizeof(int32_t) * ((size_t)np + 1)));
+    HIPCHK(c, g.device(w.xf, (size_t)np * 48));
+    HIPCHK(c, g.device(w.X, (size_t)np * 6));
+    HIPCHK(c, g.device(w.desc_reg, np));
+    HIPCHK(c, g.device(w.kf_of, (size_t)np + 1));
+    HIPCHK(c, g.pinned(c->h_desc_reg, np));
+    HIPCHK(c, g.pinned(c->h_kf_of, (size_t)np + 1));
     w.cap_regs = np; w.cap_reg_V = VV;
     c->ws_gen++;
     return ICET_OK;
@@ -61,7 +75,8 @@ icet_status ensure_scan2(icet_ctx* c, int64_t total_n2) {
     if (total_n2 >= (int64_t)1 << 31) { c->err = "total scan-2 points per call must be < 2^31"; return ICET_ERR_UNSUPPORTED; }
     if (total_n2 > w.cap_n2) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_realloc(w.near_over, (size_t)total_n2));
+        w.cap_n2 = 0, c->mem.scan2.release();
+        HIPCHK(c, c->mem.scan2.device(w.near_over, (size_t)total_n2));
         w.cap_n2 = total_n2;
         c->ws_gen++;
     }
@@ -80,62 +95,58 @@ icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs,
         const int np = n_pairs > w.cap_pairs ? n_pairs : w.cap_pairs;
         const int VV = V > w.cap_V ? V : w.cap_V;
         const size_t pv = (size_t)np * VV;
+        BufferGroup& g = c->mem.pairs;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_realloc(w.desc, np));
-        HIPCHK(c, dev_realloc(w.seg_off, 2 * (size_t)np + 1));              // segment offsets, then (ragged throughput batches) the caller's pair of every slot
-        HIPCHK(c, dev_realloc(w.bin_count, pv));
-        HIPCHK(c, dev_realloc(w.bin_start, (size_t)np * (VV + 1)));
-        HIPCHK(c, dev_realloc(w.live_bins, pv * 4)); HIPCHK(c, dev_realloc(w.n_live, np));
-        HIPCHK(c, dev_realloc(w.hotD, pv)); HIPCHK(c, dev_realloc(w.fitD, pv)); HIPCHK(c, dev_realloc(w.activeD, pv)); HIPCHK(c, dev_realloc(w.midD, pv));
-        HIPCHK(c, dev_realloc(w.hotS, pv)); HIPCHK(c, dev_realloc(w.fitS, pv));
-        HIPCHK(c, dev_realloc(w.slot_of_voxel, (size_t)np * ((VV + 1) & ~1)));
-        HIPCHK(c, dev_realloc(w.n_slots, np));
-        HIPCHK(c, dev_realloc(w.gn_part, (size_t)kGnPartWords));
-        HIPCHK(c, dev_realloc(w.flags, np));
-        HIPCHK(c, dev_realloc(w.zero_rows, (size_t)np * 4));
-        HIPCHK(c, dev_realloc(w.vrange, (size_t)np * 2));
-        HIPCHK(c, dev_realloc(w.splitters, (size_t)np * kRankSortMaxBuckets)); HIPCHK(c, dev_realloc(w.n_buckets, np)); HIPCHK(c, dev_realloc(w.bucket_start, (size_t)np * (kRankSortMaxBuckets + 1)));
-        if (c->h_desc) { HIPCHK(c, hipHostFree(c->h_desc)); c->h_desc = nullptr; }
-        if (c->h_seg) { HIPCHK(c, hipHostFree(c->h_seg)); c->h_seg = nullptr; }
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_desc), sizeof(PairDesc) * np));
+        w.cap_pairs = w.cap_V = c->h_cap_pairs = 0, w.cap_fit_items = 0, g.release();
+        HIPCHK(c, g.device(w.desc, np));
+        HIPCHK(c, g.device(w.seg_off, 2 * (size_t)np + 1));              // segment offsets, then (ragged throughput batches) the caller's pair of every slot
+        HIPCHK(c, g.device(w.bin_count, pv));
+        HIPCHK(c, g.device(w.bin_start, (size_t)np * (VV + 1)));
+        HIPCHK(c, g.device(w.live_bins, pv * 4)); HIPCHK(c, g.device(w.n_live, np));
+        HIPCHK(c, g.device(w.hotD, pv)); HIPCHK(c, g.device(w.fitD, pv)); HIPCHK(c, g.device(w.activeD, pv)); HIPCHK(c, g.device(w.midD, pv));
+        HIPCHK(c, g.device(w.hotS, pv)); HIPCHK(c, g.device(w.fitS, pv));
+        HIPCHK(c, g.device(w.slot_of_voxel, (size_t)np * ((VV + 1) & ~1)));
+        HIPCHK(c, g.device(w.n_slots, np));
+        HIPCHK(c, g.device(w.gn_part, (size_t)kGnPartWords));
+        HIPCHK(c, g.device(w.flags, np));
+        HIPCHK(c, g.device(w.zero_rows, (size_t)np * 4));
+        HIPCHK(c, g.device(w.vrange, (size_t)np * 2));
+        HIPCHK(c, g.device(w.splitters, (size_t)np * kRankSortMaxBuckets)); HIPCHK(c, g.device(w.n_buckets, np)); HIPCHK(c, g.device(w.bucket_start, (size_t)np * (kRankSortMaxBuckets + 1)));
+        HIPCHK(c, g.pinned(c->h_desc, np));
         std::memset(c->h_desc, 0, sizeof(PairDesc) * np); c->desc_kf_valid = c->desc_reg_valid = false;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_seg), sizeof(int32_t) * (2 * (size_t)np + 1)));
+        HIPCHK(c, g.pinned(c->h_seg, 2 * (size_t)np + 1));
         c->h_cap_pairs = np;
         w.cap_pairs = np; w.cap_V = VV;
         c->ws_gen++;
     }
     { const icet_status rs = ensure_regs(c, n_pairs, V); if (rs != ICET_OK) return rs; }      // (the keyframe build clears the sums and overflow counts of its pairs)
     { const icet_status ss = ensure_scan2(c, total_n2); if (ss != ICET_OK) return ss; }
-    if (total_n1 > w.cap_n1 || grow_pairs) {
+    if (total_n1 > w.cap_n1 || w.cap_fit_items == 0) {      // (cap_fit_items == 0: never built, the pair tables or scan-1 arrays moved, or its last growth was refused)
         c->ws_gen++;
         const int64_t n = total_n1 > w.cap_n1 ? total_n1 : w.cap_n1;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (n > w.cap_n1) {
+            BufferGroup& g = c->mem.scan1;
             c->kf_pairs = 0;
-            HIPCHK(c, dev_realloc(w.r1, n)); HIPCHK(c, dev_realloc(w.cart1, (size_t)3 * n));
-            HIPCHK(c, dev_realloc(w.key64A, n)); HIPCHK(c, dev_realloc(w.key64B, n)); HIPCHK(c, dev_realloc(w.bin16, n)); HIPCHK(c, dev_realloc(w.binpos, n)); HIPCHK(c, dev_realloc(w.bkt, n));
-            HIPCHK(c, dev_realloc(w.keyA, n)); HIPCHK(c, dev_realloc(w.keyB, n)); HIPCHK(c, dev_realloc(w.valA, n)); HIPCHK(c, dev_realloc(w.valB, n));
-            HIPCHK(c, dev_realloc(w.pred, n)); HIPCHK(c, dev_realloc(w.src, n));
+            w.cap_n1 = 0, w.cap_fit_items = 0, g.release();
+            HIPCHK(c, g.device(w.r1, n)); HIPCHK(c, g.device(w.cart1, (size_t)3 * n));
+            HIPCHK(c, g.device(w.key64A, n)); HIPCHK(c, g.device(w.key64B, n)); HIPCHK(c, g.device(w.bin16, n)); HIPCHK(c, g.device(w.binpos, n)); HIPCHK(c, g.device(w.bkt, n));
+            HIPCHK(c, g.device(w.keyA, n)); HIPCHK(c, g.device(w.keyB, n)); HIPCHK(c, g.device(w.valA, n)); HIPCHK(c, g.device(w.valB, n));
+            HIPCHK(c, g.device(w.pred, n)); HIPCHK(c, g.device(w.src, n));
             w.cap_n1 = n;
         }
-        HIPCHK(c, dev_realloc(w.execbits, (size_t)(w.cap_n1 / 64 + w.cap_pairs + 2)));      // exec_word_base: off1 / 64 + pair
-        {
-            const size_t need_items = (size_t)(w.cap_n1 / 64 + (int64_t)w.cap_pairs * (w.cap_V + 1) + 64);
-            if (need_items > w.cap_fit_items) {
-                if (w.fit_items) { HIPCHK(c, hipFree(w.fit_items)); w.fit_items = nullptr; }
-                HIPCHK(c, hipMalloc(&w.fit_items, need_items * 16));
-                w.cap_fit_items = need_items;
-            }
-            HIPCHK(c, dev_realloc(w.fit_n_items, (size_t)w.cap_pairs));
-        }
+        // what depends on both sides; its capacity is cap_fit_items
+        BufferGroup& g = c->mem.fit;
+        const size_t need_items = (size_t)(w.cap_n1 / 64 + (int64_t)w.cap_pairs * (w.cap_V + 1) + 64);
+        w.cap_fit_items = 0, g.release();
+        HIPCHK(c, g.device(w.execbits, (size_t)(w.cap_n1 / 64 + w.cap_pairs + 2)));      // exec_word_base: off1 / 64 + pair
+        HIPCHK(c, g.device_bytes(w.fit_items, need_items * 16));
+        HIPCHK(c, g.device(w.fit_n_items, (size_t)w.cap_pairs));
 #ifdef ICET_DIAG_LIBSORT
-        const size_t need = sort_temp_bytes(w.cap_n1);
-        if (need > w.sort_tmp_bytes) {
-            if (w.sort_tmp) { HIPCHK(c, hipFree(w.sort_tmp)); w.sort_tmp = nullptr; }
-            HIPCHK(c, hipMalloc(&w.sort_tmp, need));
-            w.sort_tmp_bytes = need;
-        }
+        w.sort_tmp_bytes = sort_temp_bytes(w.cap_n1);
+        HIPCHK(c, g.device_bytes(w.sort_tmp, w.sort_tmp_bytes));
 #endif
+        w.cap_fit_items = need_items;
     }
     return ICET_OK;
 }
@@ -186,6 +197,7 @@ int build_lut(const std::vector<double>& edges, double lo, double range, double 
 icet_status ensure_thresholds(icet_ctx* c, int T, int P) {
     Workspace& w = c->w;
     if (w.thr && w.thr_T == T && w.thr_P == P) return ICET_OK;
+    BufferGroup& g = c->mem.lut;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     {
         // azimuth: diamond angle pa(theta) = y/(|x|+|y|) unfolded to [0,4]; polar: w = -cos(phi) in [-1,1]
@@ -215,19 +227,19 @@ icet_status ensure_thresholds(icet_ctx* c, int T, int P) {
         // one spare cell per table: pa == 4 / w == 1 index cell M (it names the last edge, so the point goes to the literal path)
         for (HostCell& c : lp) c.idx *= T;                                 // polar cells carry the map row offset T * edge index
         std::vector<HostCell> all(lt); all.push_back(HostCell{4.0f, T}); all.insert(all.end(), lp.begin(), lp.end()); all.push_back(HostCell{1.0f, P * T});
-        if (w.lut) { HIPCHK(c, hipFree(w.lut)); w.lut = nullptr; }
-        HIPCHK(c, hipMalloc(&w.lut, all.size() * sizeof(HostCell)));
+        w.thr_T = w.thr_P = 0, g.release();                                // (a grid refused above keeps the tables of the last one)
+        HIPCHK(c, g.device_bytes(w.lut, all.size() * sizeof(HostCell)));
         HIPCHK(c, hipMemcpy(w.lut, all.data(), all.size() * sizeof(HostCell), hipMemcpyHostToDevice));
         w.lut_Mt = Mt; w.lut_Mp = Mp;
         // the same edges as floats, for the keep masks of the point pass (margins of 1e-2 rad: the float rounding of an edge is far inside their slack)
         std::vector<float> ef; for (double e : et) ef.push_back((float)e); for (double e : ep) ef.push_back((float)e);
-        HIPCHK(c, dev_realloc(w.edges, ef.size()));
+        HIPCHK(c, g.device(w.edges, ef.size()));
         HIPCHK(c, hipMemcpy(w.edges, ef.data(), ef.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     std::vector<float> h((size_t)T + P + 2);
     build_thresholds(T, 2 * M_PI, h.data());
     build_thresholds(P, M_PI, h.data() + T + 1);
-    HIPCHK(c, dev_realloc(w.thr, h.size()));
+    HIPCHK(c, g.device(w.thr, h.size()));
     HIPCHK(c, hipMemcpy(w.thr, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     // the voxel of an exact-zero row, by the sign bits of (y, x): r = 0, phi = acos(NaN) -> 1000, theta = atan2(+-0, +-0) (src/utils.cpp:103-116) binned as
     // sortSphericalCoordinates bins them (src/icet.cpp:545-546) -- the formulas of theta_cr / phi_cr / voxel_of (icet_device_common.h) in host arithmetic
@@ -245,12 +257,12 @@ icet_status ensure_thresholds(icet_ctx* c, int T, int P) {
 icet_status ensure_out(icet_ctx* c, int32_t n_pairs) {
     if (n_pairs <= c->cap_out_pairs) return ICET_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, dev_realloc(c->d_out, (size_t)n_pairs * 48));
-    HIPCHK(c, dev_realloc(c->d_x0, (size_t)n_pairs * 6));
-    if (c->h_out) { HIPCHK(c, hipHostFree(c->h_out)); c->h_out = nullptr; }
-    if (c->h_x0) { HIPCHK(c, hipHostFree(c->h_x0)); c->h_x0 = nullptr; }
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_out), sizeof(float) * 48 * (size_t)n_pairs));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_x0), sizeof(float) * 6 * (size_t)n_pairs));
+    BufferGroup& g = c->mem.out;
+    c->cap_out_pairs = 0, g.release();
+    HIPCHK(c, g.device(c->d_out, (size_t)n_pairs * 48));
+    HIPCHK(c, g.device(c->d_x0, (size_t)n_pairs * 6));
+    HIPCHK(c, g.pinned(c->h_out, (size_t)n_pairs * 48));
+    HIPCHK(c, g.pinned(c->h_x0, (size_t)n_pairs * 6));
     c->cap_out_pairs = n_pairs;
     return ICET_OK;
 }
@@ -313,22 +325,15 @@ AuxLayout aux_layout(int V, int runlen) {
     return L;
 }
 
-void free_aux(icet_ctx* c) {
-    if (c->d_pack) { (void)hipFree(c->d_pack); c->d_pack = nullptr; }
-    if (c->h_pack) { (void)hipHostFree(c->h_pack); c->h_pack = nullptr; }
-    c->cap_pack = 0;
-    c->aux_dev = AuxDev{};
-    c->aux_V = 0; c->aux_runlen = 0;
-}
-
 // Device and pinned host copies of the result block for (V, runlen); c->aux_dev points into the device block.
 icet_status ensure_pack(icet_ctx* c, int V, int runlen) {
     const AuxLayout L = aux_layout(V, runlen);
     if (L.total > c->cap_pack) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        free_aux(c);
-        HIPCHK(c, dev_realloc(c->d_pack, L.total));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_pack), L.total * sizeof(uint32_t)));
+        c->cap_pack = 0, c->mem.pack.release();
+        c->aux_dev = AuxDev{}; c->aux_V = 0; c->aux_runlen = 0;
+        HIPCHK(c, c->mem.pack.device(c->d_pack, L.total));
+        HIPCHK(c, c->mem.pack.pinned(c->h_pack, L.total));
         c->cap_pack = L.total;
     }
     if (c->aux_V != V || c->aux_runlen != runlen) {
@@ -394,6 +399,13 @@ LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs, PairDesc*
     return cfg;
 }
 
+// Before the host writes the pinned descriptor staging: the last copy out of it has run, and so has the last replayed graph, which re-reads it when it RUNS.
+icet_status wait_staging(icet_ctx* c) {
+    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
+    if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }
+    return ICET_OK;
+}
+
 icet_status upload_desc(icet_ctx* c, int32_t n_pairs, bool by_next_kernel = false) {
     Workspace& w = c->w;
     if (by_next_kernel) {
@@ -417,13 +429,15 @@ icet_status enqueue_keyframe(icet_ctx* c, const icet_params* p, int32_t n_pairs,
         const size_t need = (size_t)n_pairs * cfg.kf_chunks * (cfg.V > kRankSortMaxBuckets ? cfg.V : kRankSortMaxBuckets);
         if (need > w.cap_counts) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, dev_realloc(w.counts, need)); HIPCHK(c, dev_realloc(w.tile_base, need));
+            w.cap_counts = 0, c->mem.counts.release();
+            HIPCHK(c, c->mem.counts.device(w.counts, need)); HIPCHK(c, c->mem.counts.device(w.tile_base, need));
             w.cap_counts = need;
         }
         const size_t need_vr = (size_t)n_pairs * cfg.kf_chunks * 2;        // (its own capacity: tiles per voxel count vary with the grid)
         if (need_vr > w.cap_tile_vr) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, dev_realloc(w.tile_vr, need_vr));
+            w.cap_tile_vr = 0, c->mem.tile_vr.release();
+            HIPCHK(c, c->mem.tile_vr.device(w.tile_vr, need_vr));
             w.cap_tile_vr = need_vr;
         }
     }
@@ -445,12 +459,12 @@ icet_status enqueue_rt2(icet_ctx* c, const LaunchCfg& cfg, int32_t n_pairs, cons
     for (int k = 0; k < n_pairs; k++) tot += (hd[k].n2 + 63) / 64 * 64;
     if (tot > w.cap_rt2 || !w.desc_rt || n_pairs > c->h_cap_rt) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (tot > w.cap_rt2) { HIPCHK(c, dev_realloc(w.rt2, (size_t)3 * tot)); w.cap_rt2 = tot; }
+        if (tot > w.cap_rt2) { w.cap_rt2 = 0, c->mem.rt2.release(); HIPCHK(c, c->mem.rt2.device(w.rt2, (size_t)3 * tot)); w.cap_rt2 = tot; }
         if (n_pairs > c->h_cap_rt || !w.desc_rt) {
             const int np = n_pairs > w.cap_pairs ? n_pairs : w.cap_pairs;
-            HIPCHK(c, dev_realloc(w.desc_rt, np));
-            if (c->h_desc_rt) { HIPCHK(c, hipHostFree(c->h_desc_rt)); c->h_desc_rt = nullptr; }
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_desc_rt), sizeof(PairDesc) * np));
+            c->h_cap_rt = 0, c->mem.rt_desc.release();
+            HIPCHK(c, c->mem.rt_desc.device(w.desc_rt, np));
+            HIPCHK(c, c->mem.rt_desc.pinned(c->h_desc_rt, np));
             c->h_cap_rt = np;
         }
     } else if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
@@ -489,9 +503,14 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
         if (need_mask > w.cap_keep_mask || need_list > w.cap_keep_list || n_pairs > w.cap_keep_pairs) {
             if (c->capturing) { c->err = "keep list: workspace growth during capture"; return ICET_ERR_HIP; }
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (need_mask > w.cap_keep_mask) { HIPCHK(c, dev_realloc(w.keep_mask, need_mask)); w.cap_keep_mask = need_mask; }
-            if (need_list > w.cap_keep_list) { HIPCHK(c, dev_realloc(w.keep_list, need_list)); w.cap_keep_list = need_list; }
-            if (n_pairs > w.cap_keep_pairs) { HIPCHK(c, dev_realloc(w.keep_state, (size_t)n_pairs)); HIPCHK(c, dev_realloc(w.keep_modes, 2 * (size_t)n_pairs)); w.cap_keep_pairs = n_pairs; }
+            if (need_mask > w.cap_keep_mask) { w.cap_keep_mask = 0, c->mem.keep_mask.release(); HIPCHK(c, c->mem.keep_mask.device(w.keep_mask, need_mask)); w.cap_keep_mask = need_mask; }
+            if (need_list > w.cap_keep_list) { w.cap_keep_list = 0, c->mem.keep_list.release(); HIPCHK(c, c->mem.keep_list.device(w.keep_list, need_list)); w.cap_keep_list = need_list; }
+            if (n_pairs > w.cap_keep_pairs) {
+                BufferGroup& g = c->mem.keep_pairs;
+                w.cap_keep_pairs = 0, g.release();
+                HIPCHK(c, g.device(w.keep_state, (size_t)n_pairs)); HIPCHK(c, g.device(w.keep_modes, 2 * (size_t)n_pairs));
+                w.cap_keep_pairs = n_pairs;
+            }
             wl.keep_modes = w.keep_modes; wl.keep_mask = w.keep_mask; wl.keep_list = w.keep_list; wl.keep_state = w.keep_state; wl.cap_keep_mask = w.cap_keep_mask; wl.cap_keep_list = w.cap_keep_list; wl.cap_keep_pairs = w.cap_keep_pairs;
         }
     }
@@ -591,8 +610,8 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
         // the solve writes its sums at [registration][iteration] of arrays sized for the whole run: a scratch of that shape, and the rows of iteration runlen - 1 copied out
         const int it = p->runlen - 1;
         const size_t row = (size_t)p->runlen * 42;
-        float* d_tmp = nullptr;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d_tmp), sizeof(float) * row * (size_t)n_regs));
+        float* d_tmp = nullptr; BufferGroup g;                        // (freed behind the synchronisations below)
+        HIPCHK(c, g.device(d_tmp, row * (size_t)n_regs));
         auto body = [&]() -> icet_status {
             HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
             HIPCHK(c, launch_point_sums_copy(wl, lcfg, d_dump, c->stream));     // drains the overflow list; the records stay
@@ -607,7 +626,6 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
         };
         const icet_status ts = body();
         if (ts != ICET_OK) (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(d_tmp);
         if (ts != ICET_OK) return ts;
     } else
     if (d_score || d_dump) {                                                // the last solve (or k_init_state) left the transform record of the pose to score in w.xf
@@ -624,8 +642,8 @@ icet_status ensure_stage(icet_ctx* c, int64_t tot1, int64_t tot2) {
     if (3 * tot1 > c->cap_stage1 || 3 * tot2 > c->cap_stage2) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
-        if (3 * tot1 > c->cap_stage1) { HIPCHK(c, dev_realloc(c->d_stage1, (size_t)3 * tot1)); c->cap_stage1 = 3 * tot1; }
-        if (3 * tot2 > c->cap_stage2) { HIPCHK(c, dev_realloc(c->d_stage2, (size_t)3 * tot2)); c->cap_stage2 = 3 * tot2; }
+        if (3 * tot1 > c->cap_stage1) { c->cap_stage1 = 0, c->mem.stage1.release(); HIPCHK(c, c->mem.stage1.device(c->d_stage1, (size_t)3 * tot1)); c->cap_stage1 = 3 * tot1; }
+        if (3 * tot2 > c->cap_stage2) { c->cap_stage2 = 0, c->mem.stage2.release(); HIPCHK(c, c->mem.stage2.device(c->d_stage2, (size_t)3 * tot2)); c->cap_stage2 = 3 * tot2; }
     }
     return ICET_OK;
 }
@@ -674,8 +692,8 @@ icet_status icet_create(icet_ctx** out, int device_id, void* hip_stream) {
         if (hipMalloc(reinterpret_cast<void**>(&d_t), sizeof(int32_t)) == hipSuccess) { if (lds_rank_selftest(d_t, c->stream, &ok) != hipSuccess) { ok = 0; (void)hipGetLastError(); } (void)hipFree(d_t); }
         c->lds_rank_ok = ok;
     }
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->h_sync_word), sizeof(int32_t), hipHostMallocCoherent) == hipSuccess) *c->h_sync_word = 0;      // (without it icet_sync synchronises the stream)
-    else { c->h_sync_word = nullptr; (void)hipGetLastError(); }
+    if (c->mem.sync_word.pinned(c->h_sync_word, 1, hipHostMallocCoherent) == hipSuccess) *c->h_sync_word = 0;      // (without it icet_sync synchronises the stream)
+    else (void)hipGetLastError();
     *out = c;
     return ICET_OK;
 }
@@ -684,44 +702,15 @@ icet_status icet_destroy(icet_ctx* c) {
     if (!c) return ICET_ERR_BAD_ARG;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    Workspace& w = c->w;
-    void* ps[] = {w.key64A, w.key64B, w.bin16, w.execbits, w.binpos, w.bkt, w.splitters, w.n_buckets, w.bucket_start, w.counts, w.tile_base, w.desc, w.seg_off, w.r1, w.cart1, w.keyA, w.keyB, w.valA, w.valB, w.pred, w.src,
-                  w.desc_rt, w.rt2, w.gn_part, w.bin_count, w.bin_start, w.hotD, w.fitD, w.activeD, w.midD, w.hotS, w.fitS, w.slot_of_voxel, w.n_slots, w.near_over, w.near_over_count, w.acc, w.xf, w.X, w.flags, w.zero_rows, w.vrange, w.tile_vr,
-                  w.sort_tmp, w.fit_items, w.fit_n_items, w.live_bins, w.n_live, w.thr, w.lut, w.keep_mask, w.keep_list, w.keep_state, w.keep_modes, w.edges, w.desc_reg, w.kf_of, c->d_stage1, c->d_stage2, c->d_out, c->d_x0};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    free_aux(c);
     if (c->st_copy) (void)hipStreamSynchronize(c->st_copy);
-    if (c->h_pts2) (void)hipHostFree(c->h_pts2);
-    if (c->d_pts2) (void)hipFree(c->d_pts2);
-    for (void* q : {(void*)c->d_sph1, (void*)c->d_idx1, (void*)c->d_sph2, (void*)c->d_vox2}) if (q) (void)hipFree(q);
-    if (c->h_x0) (void)hipHostFree(c->h_x0);
-    if (c->d_score) (void)hipFree(c->d_score);
-    if (c->h_score) (void)hipHostFree(c->h_score);
-    if (c->d_sel) (void)hipFree(c->d_sel);
-    if (c->h_sel) (void)hipHostFree(c->h_sel);
-    if (c->ev_sel) (void)hipEventDestroy(c->ev_sel);
-    if (c->h_sync_word) (void)hipHostFree(c->h_sync_word);
-    for (hipEvent_t e : {c->ev_s2, c->ev_kf, c->ev_kfd, c->ev_prev, c->ev_pts2}) if (e) (void)hipEventDestroy(e);
-    if (c->st_copy) (void)hipStreamDestroy(c->st_copy);
-    if (c->h_desc) (void)hipHostFree(c->h_desc);
-    if (c->h_seg) (void)hipHostFree(c->h_seg);
-    if (c->h_desc_rt) (void)hipHostFree(c->h_desc_rt);
-    if (c->h_desc_reg) (void)hipHostFree(c->h_desc_reg);
-    if (c->h_kf_of) (void)hipHostFree(c->h_kf_of);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    for (hipEvent_t e : c->ev_acc) (void)hipEventDestroy(e);
-    if (c->ev_a) (void)hipEventDestroy(c->ev_a);
-    if (c->ev_b) (void)hipEventDestroy(c->ev_b);
-    if (c->ev_c) (void)hipEventDestroy(c->ev_c);
     for (icet_ctx* h : c->helpers) (void)icet_destroy(h);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_desc) (void)hipEventDestroy(c->ev_desc);
     for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop, &c->g_indexed, &c->g_scored, &c->g_score}) if (g->have_graph) { (void)hipGraphExecDestroy(g->exec); (void)hipGraphDestroy(g->graph); }
-    if (c->ev_graph) (void)hipEventDestroy(c->ev_graph);
-    if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    for (hipEvent_t e : c->ev_acc) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev_sel, c->ev_s2, c->ev_kf, c->ev_kfd, c->ev_prev, c->ev_pts2, c->ev_a, c->ev_b, c->ev_c, c->ev_fork, c->ev_desc, c->ev_graph, c->ev_stage, c->ev_join})
+        if (e) (void)hipEventDestroy(e);
+    if (c->st_copy) (void)hipStreamDestroy(c->st_copy);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                 // (the groups of c->mem free what the context owned)
     return ICET_OK;
 }
 
@@ -921,8 +910,8 @@ static icet_status solve_device_part(icet_ctx* c, const icet_params* p, int32_t 
     if (s != ICET_OK) return s;
     // the previous call may still be copying out of the pinned descriptor staging; its kernels may still be running
     // (the device entry point never waits for them: calls queue up behind each other on the stream)
-    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
-    if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }     // a replay re-reads the pinned descriptor staging when it RUNS
+    s = wait_staging(c);
+    if (s != ICET_OK) return s;
     c->desc_kf_valid = c->desc_reg_valid = false;
     // A RAGGED throughput batch is laid out XCD-balanced (round 6; icet_layout.h says why and how).  The caller's order comes back in k_init_state (X0) and
     // k_gn_solve (results): LaunchCfg::pair_user.  Same bits: a pair's result does not depend on its slot (section 6 of DESIGN.md).
@@ -987,8 +976,8 @@ icet_status icet_keyframe_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     }
     if (!same_desc) {
         c->desc_reg_valid = false;                                         // the scan-2 halves are reset below
-        if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
-        if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }
+        s = wait_staging(c);
+        if (s != ICET_OK) return s;
         for (int k = 0; k < n_pairs; k++) {
             PairDesc& d = c->h_desc[k];
             d.s1 = scan1[k].ptr; d.n1 = (int32_t)scan1[k].n; d.ld1 = (int32_t)scan1[k].ld;
@@ -1012,9 +1001,7 @@ icet_status icet_register_device(icet_ctx* c, const icet_params* p, int32_t n_pa
 icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_pairs, const icet_dev_scan* scan2, const int32_t* d_rows, const float* d_x0, float* d_out) {
     if (!c) return ICET_ERR_BAD_ARG;
     if (!params_ok(p) || n_pairs < 1 || !scan2 || !d_out) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    const icet_params& q = c->kf_params;
-    if (c->kf_pairs != n_pairs || q.bins_phi != p->bins_phi || q.bins_theta != p->bins_theta || q.n != p->n || q.thresh != p->thresh || q.buff != p->buff ||
-        ((q.flags ^ p->flags) & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS))) { c->err = "no keyframe with these parameters is parked in this context (icet_keyframe_device)"; return ICET_ERR_BAD_ARG; }
+    if (c->kf_pairs != n_pairs || !same_keyframe_shape(c->kf_params, *p)) { c->err = "no keyframe with these parameters is parked in this context (icet_keyframe_device)"; return ICET_ERR_BAD_ARG; }
     int64_t tot2 = 0;
     for (int k = 0; k < n_pairs; k++) {
         const icet_dev_scan& b = scan2[k];
@@ -1032,8 +1019,8 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
         same_desc = d.s2 == scan2[k].ptr && d.n2 == (int32_t)scan2[k].n && d.ld2 == (int32_t)scan2[k].ld;
     }
     if (!same_desc) {
-        if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
-        if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }
+        s = wait_staging(c);
+        if (s != ICET_OK) return s;
         for (int k = 0; k < n_pairs; k++) { PairDesc& d = c->h_desc[k]; d.s2 = scan2[k].ptr; d.n2 = (int32_t)scan2[k].n; d.ld2 = (int32_t)scan2[k].ld; }
         c->desc_reg_valid = true;
     }
@@ -1078,10 +1065,8 @@ icet_status icet::register_indexed(icet_ctx* c, const icet_params* p, int32_t n_
     icet_status s = ensure_regs(c, n_regs, p->bins_phi * p->bins_theta);   // the registration side only: the keyframe tables stay where they are
     if (s == ICET_OK) s = ensure_scan2(c, tot2);
     if (s == ICET_OK) s = ensure_thresholds(c, p->bins_theta, p->bins_phi);
+    if (s == ICET_OK) s = wait_staging(c);                                // the previous call may still read the registration staging
     if (s != ICET_OK) return s;
-    // the previous call may still read the registration staging (an upload, or a replay, which re-reads it when it runs)
-    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
-    if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }
     for (int r = 0; r < n_regs; r++) {
         PairDesc& d = c->h_desc_reg[r];
         d.s1 = nullptr; d.n1 = 0; d.ld1 = 0; d.off1 = 0; d.off2 = 0;      // (the loop reads no scan-1 field)
@@ -1148,9 +1133,9 @@ icet_status icet_debug_gn_terms_device(icet_ctx* c, const icet_params* p, int32_
 static icet_status ensure_score(icet_ctx* c, int32_t n) {
     if (n <= c->cap_score) return ICET_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, dev_realloc(c->d_score, (size_t)n));
-    if (c->h_score) { HIPCHK(c, hipHostFree(c->h_score)); c->h_score = nullptr; }
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_score), sizeof(icet_score) * (size_t)n));
+    c->cap_score = 0, c->mem.score.release();
+    HIPCHK(c, c->mem.score.device(c->d_score, (size_t)n));
+    HIPCHK(c, c->mem.score.pinned(c->h_score, (size_t)n));
     c->cap_score = n;
     return ICET_OK;
 }
@@ -1245,9 +1230,9 @@ icet_status icet_select_best_device(icet_ctx* c, int32_t n_regs, const int32_t* 
     if (c->sel_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_sel)); c->sel_in_flight = false; }
     if (need > c->cap_sel) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_realloc(c->d_sel, (size_t)need));
-        if (c->h_sel) { HIPCHK(c, hipHostFree(c->h_sel)); c->h_sel = nullptr; }
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_sel), sizeof(int32_t) * (size_t)need));
+        c->cap_sel = 0, c->mem.sel.release();
+        HIPCHK(c, c->mem.sel.device(c->d_sel, (size_t)need));
+        HIPCHK(c, c->mem.sel.pinned(c->h_sel, (size_t)need));
         c->cap_sel = need;
     }
     int32_t* members = c->h_sel; int32_t* offs = c->h_sel + n_regs;
@@ -1348,31 +1333,32 @@ icet_status icet_solve_begin(icet_ctx* c, const icet_params* p, const float* sca
     if (s == ICET_OK) s = ensure_pack(c, V, p->runlen);
     if (s != ICET_OK) return s;
     const bool want_pts2 = aux && aux->points2 && n2 > 0 && p->runlen > 0;
+    auto grow_pts2 = [c](size_t want) -> icet_status {                        // `points2` on the device and its pinned copy
+        c->cap_pts2 = 0, c->mem.pts2.release();
+        HIPCHK(c, c->mem.pts2.device(c->d_pts2, want));
+        HIPCHK(c, c->mem.pts2.pinned(c->h_pts2, want));
+        c->cap_pts2 = want;
+        return ICET_OK;
+    };
     if (want_pts2 && (p->flags & ICET_FLAG_ROUNDTRIP_SCAN2) && (size_t)3 * n2 > c->cap_pts2) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
-        if (c->h_pts2) { HIPCHK(c, hipHostFree(c->h_pts2)); c->h_pts2 = nullptr; c->cap_pts2 = 0; }
-        const size_t want = (size_t)3 * n2 + (size_t)3 * n2 / 8;
-        HIPCHK(c, dev_realloc(c->d_pts2, want));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_pts2), want * sizeof(float)));
-        c->cap_pts2 = want;
+        const icet_status gs = grow_pts2((size_t)3 * n2 + (size_t)3 * n2 / 8);
+        if (gs != ICET_OK) return gs;
     }
     const bool want_side1 = aux && p->runlen > 0 && n1 > 0 && (aux->points1_spherical || aux->point_index1 || aux->bin_start1);
     const bool want_side2 = aux && p->runlen > 0 && n2 > 0 && (aux->points2_spherical || aux->voxel2);
     if (want_side1 && (size_t)n1 > c->cap_side1) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, dev_realloc(c->d_sph1, (size_t)3 * n1)); HIPCHK(c, dev_realloc(c->d_idx1, (size_t)n1)); c->cap_side1 = (size_t)n1;
+        c->cap_side1 = 0, c->mem.side1.release();
+        HIPCHK(c, c->mem.side1.device(c->d_sph1, (size_t)3 * n1)); HIPCHK(c, c->mem.side1.device(c->d_idx1, (size_t)n1)); c->cap_side1 = (size_t)n1;
     }
     if (want_side2 && ((size_t)n2 > c->cap_side2 || (size_t)3 * n2 > c->cap_pts2)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
-        HIPCHK(c, dev_realloc(c->d_sph2, (size_t)3 * n2)); HIPCHK(c, dev_realloc(c->d_vox2, (size_t)n2)); c->cap_side2 = (size_t)n2;
-        if ((size_t)3 * n2 > c->cap_pts2) {
-            if (c->h_pts2) { HIPCHK(c, hipHostFree(c->h_pts2)); c->h_pts2 = nullptr; }
-            HIPCHK(c, dev_realloc(c->d_pts2, (size_t)3 * n2));
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_pts2), (size_t)3 * n2 * sizeof(float)));
-            c->cap_pts2 = (size_t)3 * n2;
-        }
+        c->cap_side2 = 0, c->mem.side2.release();
+        HIPCHK(c, c->mem.side2.device(c->d_sph2, (size_t)3 * n2)); HIPCHK(c, c->mem.side2.device(c->d_vox2, (size_t)n2)); c->cap_side2 = (size_t)n2;
+        if ((size_t)3 * n2 > c->cap_pts2) { const icet_status gs = grow_pts2((size_t)3 * n2); if (gs != ICET_OK) return gs; }
     }
     if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
     // (no stream synchronisation up front: the staging buffers, the result block and the pinned x0 are only ever used by the host-pointer
@@ -1542,15 +1528,14 @@ icet_status icet_debug_gn_tail(icet_ctx* c, const float* htwh, const float* htwd
     if (!c || !htwh || !htwdz || !out || n < 0) return ICET_ERR_BAD_ARG;
     if (n == 0) return ICET_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    float* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(float) * (size_t)n * (36 + 6 + 56)));
+    float* d = nullptr; BufferGroup g;                                       // (freed at every return)
+    HIPCHK(c, g.device(d, (size_t)n * (36 + 6 + 56)));
     float* d_H = d; float* d_g = d + (size_t)n * 36; float* d_o = d_g + (size_t)n * 6;
     hipError_t e = hipMemcpyAsync(d_H, htwh, sizeof(float) * (size_t)n * 36, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_g, htwdz, sizeof(float) * (size_t)n * 6, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = launch_gn_tail_debug(d_H, d_g, d_o, n, (float)(c->tune.gn_cond_bound * c->tune.gn_cond_bound), c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, sizeof(float) * (size_t)n * 56, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { c->err = std::string("icet_debug_gn_tail: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
     return ICET_OK;
 }
@@ -1560,13 +1545,12 @@ icet_status icet_debug_pinv3(icet_ctx* c, const float* a, int32_t n, float* out)
     if (!c || !a || !out || n < 0) return ICET_ERR_BAD_ARG;
     if (n == 0) return ICET_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    float* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(float) * (size_t)n * 18));
+    float* d = nullptr; BufferGroup g;
+    HIPCHK(c, g.device(d, (size_t)n * 18));
     hipError_t e = hipMemcpyAsync(d, a, sizeof(float) * (size_t)n * 9, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = launch_pinv3_debug(d, d + (size_t)n * 9, n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + (size_t)n * 9, sizeof(float) * (size_t)n * 9, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { c->err = std::string("icet_debug_pinv3: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
     return ICET_OK;
 }
@@ -1576,13 +1560,12 @@ icet_status icet_debug_pinv3_double(icet_ctx* c, const float* a, int32_t n, floa
     if (!c || !a || !out || n < 0) return ICET_ERR_BAD_ARG;
     if (n == 0) return ICET_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    float* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(float) * (size_t)n * 12));
+    float* d = nullptr; BufferGroup g;
+    HIPCHK(c, g.device(d, (size_t)n * 12));
     hipError_t e = hipMemcpyAsync(d, a, sizeof(float) * (size_t)n * 6, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = launch_pinv3_double_debug(d, d + (size_t)n * 6, n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + (size_t)n * 6, sizeof(float) * (size_t)n * 6, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { c->err = std::string("icet_debug_pinv3_double: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
     return ICET_OK;
 }
@@ -1593,14 +1576,13 @@ icet_status icet_debug_fix(icet_ctx* c, const float* v, int32_t n, uint64_t* out
     if (!v || !out || n < 0) { c->err = "icet_debug_fix: bad argument"; return ICET_ERR_BAD_ARG; }
     if (n == 0) return ICET_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(unsigned long long) * (size_t)n * 4));
+    unsigned long long* d = nullptr; BufferGroup g;
+    HIPCHK(c, g.device(d, (size_t)n * 4));
     float* d_v = reinterpret_cast<float*>(d + (size_t)n * 3);
     hipError_t e = hipMemcpyAsync(d_v, v, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = launch_fix_debug(d_v, d, n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(unsigned long long) * (size_t)n * 3, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { c->err = std::string("icet_debug_fix: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
     return ICET_OK;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/icet_hip.h"
 #include "icet_internal.h"
+#include "icet_buffers.h"
 #include "icet_appearance.h"
 #include "icet_coarse.h"
 
@@ -85,6 +86,11 @@ struct icet_ctx {
     // first one's store) makes it 2 or more and icet_sync synchronises the stream as before.
     int32_t* h_sync_word = nullptr; int armed_calls = 2;
     int64_t snapshot_chunk_bytes = 0;                            // option "snapshot_chunk_bytes": payload bytes per chunk of a store's save / load (0: 64 MiB)
+    // Who owns what w and the pointers above point at: one group per set of arrays that grows together (the ensure_* functions of icet_capi.hip).  delete frees them (last member: gone first).
+    struct Mem {
+        icet::BufferGroup pairs, regs, scan1, fit, scan2, lut, keep_mask, keep_list, keep_pairs, counts, tile_vr, rt2, rt_desc;      // what w points at (+ the pinned staging sized with it)
+        icet::BufferGroup out, stage1, stage2, pack, pts2, side1, side2, score, sel, sync_word;
+    } mem;
 };
 
 // A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
@@ -119,6 +125,7 @@ struct icet_keyframe_store {
         uint32_t* qdesc = nullptr; float* qw = nullptr; int32_t* qhas = nullptr;   // the descriptors of a call's queries: a table of kAppBatch rows
         unsigned long long* keys_all = nullptr; uint16_t* shift_all = nullptr; size_t cap_all = 0;      // n_queries x capacity, grown on demand
         int32_t* shift_of = nullptr;                              // kClosureMaxQueries x kClosureMaxCandidates: the candidates' shifts, for the record
+        icet::BufferGroup table, work, all;                       // owners: desc / w / has (swapped by a reserve); keys_all / shift_all (cap_all); everything else
     };
     Appearance* app = nullptr;
     icet::AppTable app_table() const { return icet::AppTable{app->desc, app->w, app->has, capacity, app->k.A, app->Rp}; }
@@ -133,23 +140,21 @@ struct icet_keyframe_store {
         // per (query, candidate) of the largest call: base starts, coarse starts, matches, keys, slot bit counts; per hypothesis: transforms and live bit counts
         float* base = nullptr; icet_coarse_match* match = nullptr; unsigned long long* keys = nullptr; int32_t* key_bits = nullptr;
         icet::CoarseHyp* hyp = nullptr; int32_t* live_bits = nullptr;
+        icet::BufferGroup table, work;                            // owners: grid / has (swapped by a reserve); everything else
         size_t row_words() const { return (size_t)k.G * (size_t)k.W; }
     };
     Coarse* coarse = nullptr;
     icet::CoarseTable coarse_table() const { return icet::CoarseTable{coarse->grid, coarse->has, capacity}; }
+    // who owns the arrays of this struct (icet_buffers.h): the four tables + the pose table, which a reserve swaps for larger ones; the pinned pose staging; the
+    // query buffers, one group per capacity (fixed-size, cap_part, cap_qk, cap_qr)
+    icet::BufferGroup tables, pose_stage, q_fixed, q_part_mem, q_qk_mem, q_qr_mem;
 };
 
 namespace icet {
 
-#define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+#define HIPCHK(ctx, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
     (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
     return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
-
-template <typename T> static hipError_t dev_realloc(T*& p, size_t count) {
-    if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-    if (count == 0) return hipSuccess;
-    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-}
 
 static inline bool params_ok(const icet_params* p) {
     if (!p) return false;

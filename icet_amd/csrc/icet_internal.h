@@ -123,7 +123,8 @@ struct AuxDev {
 // Two sides, sized apart ("the workspace split").  KEYFRAME side: what fitScan1 writes -- hotS / fitS / slot_of_voxel / n_slots and the
 // build's temporaries --, cap_pairs x cap_V; growing it moves the tables and un-parks a parked keyframe.  REGISTRATION side: what the Gauss-Newton loop
 // keeps per registration -- acc, xf, X, the overflow list and its counts + block tickets, the indexed call's descriptors and keyframe index --,
-// cap_regs x cap_reg_V; growing it leaves the keyframe side (and a parked keyframe) alone.  cap_regs >= cap_pairs: the keyframe build clears the
+// cap_regs x cap_reg_V; growing it leaves the keyframe side (and a parked keyframe) alone.  cap_regs covers the pairs of every keyframe
+// build (ensure_workspace asks ensure_regs for them; after a refused growth it is 0 beside a live cap_pairs until the next call): the build clears the
 // accumulators and overflow counts of its pairs.
 struct Workspace {
     // capacities

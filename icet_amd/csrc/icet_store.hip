@@ -23,7 +23,7 @@ using namespace icet;
 extern "C" {
 
 // ---- the keyframe store ----------------------------------------------------------------------------------------
-#define STORECHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+#define STORECHK(s, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
     (s)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
     return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
 
@@ -50,60 +50,38 @@ static icet_status scans_ok(icet_keyframe_store* s, int32_t n, const icet_dev_sc
     return ICET_OK;
 }
 
-static void free_appearance(icet_keyframe_store::Appearance* a) {
-    if (!a) return;
-    for (void* q : {(void*)a->desc, (void*)a->w, (void*)a->has, (void*)a->scratch, (void*)a->qdesc, (void*)a->qw, (void*)a->qhas, (void*)a->keys_all, (void*)a->shift_all,
-                    (void*)a->shift_of}) if (q) (void)hipFree(q);
-    delete a;
-}
-
-static void free_coarse(icet_keyframe_store::Coarse* a) {
-    if (!a) return;
-    for (void* q : {(void*)a->grid, (void*)a->has, (void*)a->scratch, (void*)a->qgrid, (void*)a->base, (void*)a->match, (void*)a->keys, (void*)a->key_bits, (void*)a->hyp,
-                    (void*)a->live_bits}) if (q) (void)hipFree(q);
-    delete a;
-}
-
-// The four tables of `cap` rows of V voxels; all or nothing.
-static hipError_t store_alloc(int V, int32_t cap, SlotHot*& hot, SlotFit*& fit, int16_t*& sov, int32_t*& ns) {
-    hot = nullptr; fit = nullptr; sov = nullptr; ns = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&hot), sizeof(SlotHot) * (size_t)cap * V);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fit), sizeof(SlotFit) * (size_t)cap * V);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sov), sizeof(int16_t) * (size_t)cap * ((V + 1) & ~1));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ns), sizeof(int32_t) * (size_t)cap);
-    if (e != hipSuccess) {
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) if (q) (void)hipFree(q);
-        hot = nullptr; fit = nullptr; sov = nullptr; ns = nullptr;
-        (void)hipGetLastError();
-    }
+// The allocators of the store's tables: each allocates INTO a group (the store's own, or the local one a reserve builds beside it), always in the same order, so
+// that two groups filled by the same allocator can be swapped.  All or nothing for the caller: what a failed run got is freed with its group.
+static_assert(kPoseBytes == 7 * sizeof(int64_t), "the pose table is allocated as 7 words of 8 bytes per slot");
+static int store_alloc(BufferGroup& g, int V, int32_t cap, SlotHot*& hot, SlotFit*& fit, int16_t*& sov, int32_t*& ns, int64_t*& pose) {
+    int e = g.device(hot, (size_t)cap * V);
+    if (!e) e = g.device(fit, (size_t)cap * V);
+    if (!e) e = g.device(sov, (size_t)cap * ((V + 1) & ~1));
+    if (!e) e = g.device(ns, (size_t)cap);
+    if (!e) e = g.device(pose, 7 * (size_t)cap);
     return e;
 }
 
-// The descriptor table of `cap` rows (row: `row_words` words of columns, `cols` weights); all or nothing.
-static hipError_t app_alloc_table(size_t row_words, size_t cols, int32_t cap, uint32_t*& desc, float*& w, int32_t*& has) {
-    desc = nullptr; w = nullptr; has = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&desc), sizeof(uint32_t) * row_words * (size_t)cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w), sizeof(float) * cols * (size_t)cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&has), sizeof(int32_t) * (size_t)cap);
-    if (e != hipSuccess) {
-        for (void* q : {(void*)desc, (void*)w, (void*)has}) if (q) (void)hipFree(q);
-        desc = nullptr; w = nullptr; has = nullptr;
-        (void)hipGetLastError();
-    }
+// The descriptor table of `cap` rows (row: `row_words` words of columns, `cols` weights).
+static int app_alloc_table(BufferGroup& g, size_t row_words, size_t cols, int32_t cap, uint32_t*& desc, float*& w, int32_t*& has) {
+    int e = g.device(desc, row_words * (size_t)cap);
+    if (!e) e = g.device(w, cols * (size_t)cap);
+    if (!e) e = g.device(has, (size_t)cap);
     return e;
 }
 
-// The grid table of `cap` rows of `row_words` words; all or nothing.
-static hipError_t coarse_alloc_table(size_t row_words, int32_t cap, uint32_t*& grid, int32_t*& has) {
-    grid = nullptr; has = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&grid), sizeof(uint32_t) * row_words * (size_t)cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&has), sizeof(int32_t) * (size_t)cap);
-    if (e != hipSuccess) {
-        for (void* q : {(void*)grid, (void*)has}) if (q) (void)hipFree(q);
-        grid = nullptr; has = nullptr;
-        (void)hipGetLastError();
-    }
+// The grid table of `cap` rows of `row_words` words.
+static int coarse_alloc_table(BufferGroup& g, size_t row_words, int32_t cap, uint32_t*& grid, int32_t*& has) {
+    int e = g.device(grid, row_words * (size_t)cap);
+    if (!e) e = g.device(has, (size_t)cap);
     return e;
+}
+
+// (e: a hipError_t, as the runtime or a group returned it)
+static icet_status store_fail(icet_keyframe_store* s, const char* what, int e) {
+    (void)hipGetLastError();
+    s->err = std::string(what) + ": " + hipGetErrorString(static_cast<hipError_t>(e));
+    return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
 }
 
 const char* icet_keyframe_store_last_error(const icet_keyframe_store* s) { return s ? s->err.c_str() : "null store"; }
@@ -121,14 +99,11 @@ icet_status icet_keyframe_store_create(icet_ctx* c, const icet_params* p, int32_
     static std::atomic<int64_t> next_id{1};
     s->ctx = c; s->V = V; s->capacity = capacity; s->id = next_id++;
     s->shape = *p; s->shape.runlen = 0; s->shape.flags = p->flags & (ICET_FLAG_TRUE_SORT | ICET_FLAG_HALF_GAP_BOUNDS);
-    const hipError_t e = store_alloc(V, capacity, s->hotS, s->fitS, s->slot_of_voxel, s->n_slots);
-    if (e != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(e); delete s; return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    int z = store_alloc(s->tables, V, capacity, s->hotS, s->fitS, s->slot_of_voxel, s->n_slots, s->pose_stamp);
     s->occupied.assign((size_t)capacity, 0);
-    hipError_t z = hipMalloc(reinterpret_cast<void**>(&s->pose_stamp), kPoseBytes * (size_t)capacity);
-    if (z != hipSuccess) { (void)hipGetLastError(); c->err = std::string("keyframe store: ") + hipGetErrorString(z); s->pose_stamp = nullptr; (void)icet_keyframe_store_destroy(s); return z == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
-    z = hipMemsetAsync(s->pose_stamp, 0xFF, kPoseBytes * (size_t)capacity, c->stream);      // no slot has a pose
+    if (z == hipSuccess) z = hipMemsetAsync(s->pose_stamp, 0xFF, kPoseBytes * (size_t)capacity, c->stream);      // no slot has a pose
     if (z == hipSuccess) z = hipMemsetAsync(s->n_slots, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
-    if (z != hipSuccess) { c->err = std::string("keyframe store: ") + hipGetErrorString(z); (void)icet_keyframe_store_destroy(s); return ICET_ERR_HIP; }
+    if (z != hipSuccess) { const icet_status st = store_fail(s, "keyframe store", z); c->err = s->err; (void)icet_keyframe_store_destroy(s); return st; }
     *out = s;
     return ICET_OK;
 }
@@ -137,12 +112,9 @@ icet_status icet_keyframe_store_destroy(icet_keyframe_store* s) {
     if (!s) return ICET_ERR_BAD_ARG;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);              // (a put or a registration may still read or write the tables)
-    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots, (void*)s->pose_stamp, (void*)s->q_part, (void*)s->q_keys, (void*)s->q_cand,
-                    (void*)s->q_x0, (void*)s->q_out, (void*)s->q_score, (void*)s->q_kf_of, (void*)s->q_rows, (void*)s->q_members, (void*)s->q_offs, (void*)s->q_best}) if (q) (void)hipFree(q);
-    if (s->h_pose) (void)hipHostFree(s->h_pose);
     if (s->ev_pose) (void)hipEventDestroy(s->ev_pose);
-    free_appearance(s->app);
-    free_coarse(s->coarse);
+    delete s->app;                                           // (every array belongs to a group of its struct)
+    delete s->coarse;
     delete s;
     return ICET_OK;
 }
@@ -153,42 +125,25 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
     icet_ctx* c = s->ctx;
     STORECHK(s, hipSetDevice(c->device));
     STORECHK(s, hipStreamSynchronize(c->stream));            // nothing on the stream reads the old tables any more
-    SlotHot* hot; SlotFit* fit; int16_t* sov; int32_t* ns;
-    STORECHK(s, store_alloc(s->V, capacity, hot, fit, sov, ns));
-    const size_t old = (size_t)s->capacity, V = (size_t)s->V;
-    int64_t* pose = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&pose), kPoseBytes * (size_t)capacity);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns}) (void)hipFree(q);
-        s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-    }
-    // descriptors (a store with appearance enabled): a new table, the first `old` rows carried over, no descriptor behind them
+    // Every new table goes into a LOCAL group beside the one it will replace.  A failure returns: the locals free what they got and the store is untouched.
+    SlotHot* hot = nullptr; SlotFit* fit = nullptr; int16_t* sov = nullptr; int32_t* ns = nullptr; int64_t* pose = nullptr;
     uint32_t* adesc = nullptr; float* aw = nullptr; int32_t* ahas = nullptr;
+    uint32_t* cgrid = nullptr; int32_t* chas = nullptr;
+    BufferGroup tables, app_table, coarse_table;             // (behind their slots: a group nulls them when it goes)
+    const size_t old = (size_t)s->capacity, V = (size_t)s->V;
     const size_t arow = s->app ? (size_t)s->app->k.A * (size_t)s->app->Rp : 0, acol = s->app ? (size_t)s->app->k.A : 0;
-    if (s->app) {
-        e = app_alloc_table(arow, acol, capacity, adesc, aw, ahas);
-        if (e != hipSuccess) {
-            for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose}) (void)hipFree(q);
-            s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-        }
+    int e = store_alloc(tables, s->V, capacity, hot, fit, sov, ns, pose);
+    if (e == hipSuccess && s->app) e = app_alloc_table(app_table, arow, acol, capacity, adesc, aw, ahas);
+    if (e == hipSuccess && s->coarse) e = coarse_alloc_table(coarse_table, s->coarse->row_words(), capacity, cgrid, chas);
+    // descriptors (a store with appearance enabled): the first `old` rows carried over, no descriptor behind them
+    if (e == hipSuccess && s->app) {
         e = hipMemsetAsync(ahas, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ahas, s->app->has, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(adesc, s->app->desc, sizeof(uint32_t) * arow * old, hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(aw, s->app->w, sizeof(float) * acol * old, hipMemcpyDeviceToDevice, c->stream);
     }
     // grids (a store with coarse alignment enabled): likewise
-    uint32_t* cgrid = nullptr; int32_t* chas = nullptr;
-    if (s->coarse && e == hipSuccess) {
-        e = coarse_alloc_table(s->coarse->row_words(), capacity, cgrid, chas);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);
-            for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas}) if (q) (void)hipFree(q);
-            s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-        }
+    if (e == hipSuccess && s->coarse) {
         e = hipMemsetAsync(chas, 0, sizeof(int32_t) * (size_t)capacity, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(chas, s->coarse->has, sizeof(int32_t) * old, hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(cgrid, s->coarse->grid, sizeof(uint32_t) * s->coarse->row_words() * old, hipMemcpyDeviceToDevice, c->stream);
@@ -204,23 +159,16 @@ icet_status icet_keyframe_store_reserve(icet_keyframe_store* s, int32_t capacity
     if (e == hipSuccess) e = hipMemsetAsync(ns + old, 0, sizeof(int32_t) * ((size_t)capacity - old), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* q : {(void*)hot, (void*)fit, (void*)sov, (void*)ns, (void*)pose, (void*)adesc, (void*)aw, (void*)ahas, (void*)cgrid, (void*)chas}) if (q) (void)hipFree(q);
-        s->err = std::string("keyframe store reserve: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
+        (void)hipStreamSynchronize(c->stream);                   // (no copy still writes what the local groups are about to free)
+        return store_fail(s, "keyframe store reserve", e);
     }
-    if (s->coarse) {
-        for (void* q : {(void*)s->coarse->grid, (void*)s->coarse->has}) (void)hipFree(q);
-        s->coarse->grid = cgrid; s->coarse->has = chas; s->coarse->has_h.resize((size_t)capacity, 0);
-    }
+    // the swap: every slot of the store now points at its new table, and the local groups free the old ones as they go out of scope
+    if (s->coarse) { s->coarse->table.swap(coarse_table); s->coarse->has_h.resize((size_t)capacity, 0); }
     if (s->app) {
-        for (void* q : {(void*)s->app->desc, (void*)s->app->w, (void*)s->app->has}) (void)hipFree(q);
-        s->app->desc = adesc; s->app->w = aw; s->app->has = ahas; s->app->has_h.resize((size_t)capacity, 0);
+        s->app->table.swap(app_table); s->app->has_h.resize((size_t)capacity, 0);
         s->app->cap_all = 0;                                     // (the per-slot buffers of a search are sized by the capacity)
     }
-    for (void* q : {(void*)s->hotS, (void*)s->fitS, (void*)s->slot_of_voxel, (void*)s->n_slots, (void*)s->pose_stamp}) (void)hipFree(q);
-    s->pose_stamp = pose;
-    s->hotS = hot; s->fitS = fit; s->slot_of_voxel = sov; s->n_slots = ns;
+    s->tables.swap(tables);
     s->capacity = capacity; s->occupied.resize((size_t)capacity, 0);
     s->gen++;                                                // the tables moved: no graph captured against the old ones is replayed
     return ICET_OK;
@@ -354,8 +302,8 @@ icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, cons
     STORECHK(s, hipSetDevice(c->device));
     if (s->pose_in_flight) { STORECHK(s, hipEventSynchronize(s->ev_pose)); s->pose_in_flight = false; }      // the previous set_pose's kernel has read the staging
     if (n > s->cap_h_pose) {
-        if (s->h_pose) { STORECHK(s, hipHostFree(s->h_pose)); s->h_pose = nullptr; s->cap_h_pose = 0; }
-        STORECHK(s, hipHostMalloc(reinterpret_cast<void**>(&s->h_pose), sizeof(PoseUpload) * (size_t)n));
+        s->cap_h_pose = 0, s->pose_stage.release();
+        STORECHK(s, s->pose_stage.pinned(s->h_pose, (size_t)n));
         s->cap_h_pose = n;
     }
     if (!s->ev_pose) STORECHK(s, hipEventCreateWithFlags(&s->ev_pose, hipEventDisableTiming));
@@ -393,16 +341,18 @@ static icet_status closure_ensure(icet_keyframe_store* s, int32_t n_queries, int
     icet_ctx* c = s->ctx;
     const size_t need_part = (size_t)n_queries * (size_t)closure_tiles(s->capacity) * (size_t)K;
     const int32_t qk = n_queries * K;
-    if (need_part <= s->cap_part && qk <= s->cap_qk && n_regs <= s->cap_qr && s->q_offs) return ICET_OK;
+    if (need_part <= s->cap_part && qk <= s->cap_qk && n_regs <= s->cap_qr && s->q_best) return ICET_OK;
     STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
-    if (!s->q_offs) { STORECHK(s, dev_realloc(s->q_offs, (size_t)kClosureMaxQueries + 1)); STORECHK(s, dev_realloc(s->q_best, (size_t)kClosureMaxQueries)); }
-    if (need_part > s->cap_part) { s->cap_part = 0; STORECHK(s, dev_realloc(s->q_part, need_part)); s->cap_part = need_part; }
-    if (qk > s->cap_qk) { s->cap_qk = 0; STORECHK(s, dev_realloc(s->q_keys, (size_t)qk)); STORECHK(s, dev_realloc(s->q_cand, (size_t)qk)); s->cap_qk = qk; }
+    // (as in the context: a group is released with its capacity zeroed, and the capacity -- for the fixed pair, the last pointer -- is set after the last allocation)
+    if (!s->q_best) { s->q_fixed.release(); STORECHK(s, s->q_fixed.device(s->q_offs, (size_t)kClosureMaxQueries + 1)); STORECHK(s, s->q_fixed.device(s->q_best, (size_t)kClosureMaxQueries)); }
+    if (need_part > s->cap_part) { s->cap_part = 0, s->q_part_mem.release(); STORECHK(s, s->q_part_mem.device(s->q_part, need_part)); s->cap_part = need_part; }
+    if (qk > s->cap_qk) { BufferGroup& g = s->q_qk_mem; s->cap_qk = 0, g.release(); STORECHK(s, g.device(s->q_keys, (size_t)qk)); STORECHK(s, g.device(s->q_cand, (size_t)qk)); s->cap_qk = qk; }
     if (n_regs > s->cap_qr) {
-        s->cap_qr = 0;
+        BufferGroup& g = s->q_qr_mem;
+        s->cap_qr = 0, g.release();
         const size_t r = (size_t)n_regs;
-        STORECHK(s, dev_realloc(s->q_x0, r * 6)); STORECHK(s, dev_realloc(s->q_out, r * 48)); STORECHK(s, dev_realloc(s->q_score, r));
-        STORECHK(s, dev_realloc(s->q_kf_of, r)); STORECHK(s, dev_realloc(s->q_rows, r)); STORECHK(s, dev_realloc(s->q_members, r));
+        STORECHK(s, g.device(s->q_x0, r * 6)); STORECHK(s, g.device(s->q_out, r * 48)); STORECHK(s, g.device(s->q_score, r));
+        STORECHK(s, g.device(s->q_kf_of, r)); STORECHK(s, g.device(s->q_rows, r)); STORECHK(s, g.device(s->q_members, r));
         s->cap_qr = n_regs;
     }
     return ICET_OK;
@@ -502,21 +452,17 @@ icet_status icet_keyframe_store_enable_appearance(icet_keyframe_store* s, const 
     a->params = d;
     a->Rp = (d.rings + 3) / 4;
     const size_t A = (size_t)a->k.A, row = A * (size_t)a->Rp, cells = A * (size_t)a->k.Rn;
-    hipError_t e = app_alloc_table(row, A, s->capacity, a->desc, a->w, a->has);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->scratch), sizeof(uint32_t) * cells * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qdesc), sizeof(uint32_t) * row * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qw), sizeof(float) * A * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qhas), sizeof(int32_t) * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->shift_of), sizeof(int32_t) * kClosureMaxQueries * kClosureMaxCandidates);
+    BufferGroup& g = a->work;
+    int e = app_alloc_table(a->table, row, A, s->capacity, a->desc, a->w, a->has);
+    if (e == hipSuccess) e = g.device(a->scratch, cells * kAppBatch);
+    if (e == hipSuccess) e = g.device(a->qdesc, row * kAppBatch);
+    if (e == hipSuccess) e = g.device(a->qw, A * kAppBatch);
+    if (e == hipSuccess) e = g.device(a->qhas, (size_t)kAppBatch);
+    if (e == hipSuccess) e = g.device(a->shift_of, (size_t)kClosureMaxQueries * kClosureMaxCandidates);
     if (e == hipSuccess) e = hipMemsetAsync(a->has, 0, sizeof(int32_t) * (size_t)s->capacity, c->stream);          // no slot has a descriptor
     if (e == hipSuccess) e = hipMemsetAsync(a->scratch, 0, sizeof(uint32_t) * cells * kAppBatch, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        free_appearance(a);
-        s->err = std::string("enable_appearance: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-    }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); delete a; return store_fail(s, "enable_appearance", e); }
     a->has_h.assign((size_t)s->capacity, 0);
     s->app = a;
     return ICET_OK;
@@ -564,8 +510,9 @@ static icet_status app_ensure(icet_keyframe_store* s, int32_t n_queries) {
     const size_t need = (size_t)n_queries * (size_t)s->capacity;
     if (need <= s->app->cap_all) return ICET_OK;
     STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
-    s->app->cap_all = 0;
-    STORECHK(s, dev_realloc(s->app->keys_all, need)); STORECHK(s, dev_realloc(s->app->shift_all, need));
+    BufferGroup& g = s->app->all;
+    s->app->cap_all = 0, g.release();
+    STORECHK(s, g.device(s->app->keys_all, need)); STORECHK(s, g.device(s->app->shift_all, need));
     s->app->cap_all = need;
     return ICET_OK;
 }
@@ -641,25 +588,21 @@ icet_status icet_keyframe_store_enable_coarse(icet_keyframe_store* s, const icet
     a->params = d;
     const size_t row = a->row_words(), cells = (size_t)a->k.G * (size_t)a->k.G;
     constexpr size_t kQK = (size_t)kClosureMaxQueries * kClosureMaxCandidates, kH = 2 * (2 * icet_coarse_rule::kMaxYaw + 1);
-    hipError_t e = launch_coarse_prepare(a->k);
-    if (e == hipSuccess) e = coarse_alloc_table(row, s->capacity, a->grid, a->has);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->scratch), sizeof(uint32_t) * 2 * cells * kCoarseBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->qgrid), sizeof(uint32_t) * row * kAppBatch);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->base), sizeof(float) * 6 * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->match), sizeof(icet_coarse_match) * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->keys), sizeof(unsigned long long) * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->key_bits), sizeof(int32_t) * kQK);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->hyp), sizeof(CoarseHyp) * kQK * kH);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->live_bits), sizeof(int32_t) * kQK * kH);
+    BufferGroup& g = a->work;
+    int e = launch_coarse_prepare(a->k);
+    if (e == hipSuccess) e = coarse_alloc_table(a->table, row, s->capacity, a->grid, a->has);
+    if (e == hipSuccess) e = g.device(a->scratch, 2 * cells * kCoarseBatch);
+    if (e == hipSuccess) e = g.device(a->qgrid, row * kAppBatch);
+    if (e == hipSuccess) e = g.device(a->base, 6 * kQK);
+    if (e == hipSuccess) e = g.device(a->match, kQK);
+    if (e == hipSuccess) e = g.device(a->keys, kQK);
+    if (e == hipSuccess) e = g.device(a->key_bits, kQK);
+    if (e == hipSuccess) e = g.device(a->hyp, kQK * kH);
+    if (e == hipSuccess) e = g.device(a->live_bits, kQK * kH);
     if (e == hipSuccess) e = hipMemsetAsync(a->has, 0, sizeof(int32_t) * (size_t)s->capacity, c->stream);          // no slot has a grid
     if (e == hipSuccess) e = hipMemsetAsync(a->scratch, 0, sizeof(uint32_t) * 2 * cells * kCoarseBatch, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        free_coarse(a);
-        s->err = std::string("enable_coarse: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP;
-    }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); delete a; return store_fail(s, "enable_coarse", e); }
     a->has_h.assign((size_t)s->capacity, 0);
     s->coarse = a;
     return ICET_OK;
@@ -828,27 +771,26 @@ namespace snap = icet_snapshot;
 struct SnapBuffers {
     SnapEntry* h_ent = nullptr; SnapEntry* d_ent = nullptr; unsigned long long* d_sums = nullptr; unsigned long long* h_sums = nullptr;
     uint8_t* d_stage = nullptr; uint8_t* h_buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};
+    BufferGroup mem;                                         // owns the seven buffers
 };
 static void snap_free(icet_keyframe_store* s, SnapBuffers& b) {
     (void)hipStreamSynchronize(s->ctx->stream);              // (nothing in flight reads or writes what goes)
-    for (void* q : {(void*)b.d_ent, (void*)b.d_sums, (void*)b.d_stage}) if (q) (void)hipFree(q);
-    for (void* q : {(void*)b.h_ent, (void*)b.h_sums, (void*)b.h_buf[0], (void*)b.h_buf[1]}) if (q) (void)hipHostFree(q);
-    for (hipEvent_t e : b.ev) if (e) (void)hipEventDestroy(e);
-    b = SnapBuffers{};
+    b.mem.release();
+    for (hipEvent_t& e : b.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
 }
 static hipError_t snap_alloc(SnapBuffers& b, size_t n_entries, size_t chunk_bytes, bool sums) {
     const size_t ne = n_entries ? n_entries : 1, cb = chunk_bytes ? chunk_bytes : 16;
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&b.h_ent), sizeof(SnapEntry) * ne);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b.d_ent), sizeof(SnapEntry) * ne);
-    if (e == hipSuccess && sums) e = hipMalloc(reinterpret_cast<void**>(&b.d_sums), sizeof(unsigned long long) * ne);
-    if (e == hipSuccess && sums) e = hipHostMalloc(reinterpret_cast<void**>(&b.h_sums), sizeof(unsigned long long) * ne);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b.d_stage), cb);
+    int e = b.mem.pinned(b.h_ent, ne);
+    if (e == hipSuccess) e = b.mem.device(b.d_ent, ne);
+    if (e == hipSuccess && sums) e = b.mem.device(b.d_sums, ne);
+    if (e == hipSuccess && sums) e = b.mem.pinned(b.h_sums, ne);
+    if (e == hipSuccess) e = b.mem.device(b.d_stage, cb);
     for (int k = 0; k < 2; k++) {
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b.h_buf[k]), cb);
+        if (e == hipSuccess) e = b.mem.pinned(b.h_buf[k], cb);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b.ev[k], hipEventDisableTiming);
     }
     if (e != hipSuccess) (void)hipGetLastError();
-    return e;
+    return static_cast<hipError_t>(e);
 }
 
 // Entries first .. into chunks of at most `budget` payload bytes, never splitting one: chunk k holds entries cut[k] .. cut[k + 1] - 1.
