@@ -284,6 +284,23 @@ hipError_t upload_scan(float* dst, int64_t l, const float* src, int64_t n, int64
     if (n <= 0) return hipSuccess;
     return hipMemcpy2DAsync(dst, l * sizeof(float), src, ld * sizeof(float), n * sizeof(float), 3, hipMemcpyHostToDevice, st);
 }
+// `count` dense host scans (ld == n) into the places stage_layout gave them, on `st`.
+hipError_t upload_staged(const icet_dev_scan* d, const float* const* scan, int32_t count, hipStream_t st) {
+    for (int k = 0; k < count; k++) {
+        const hipError_t e = upload_scan(const_cast<float*>(d[k].ptr), d[k].ld, scan[k], d[k].n, d[k].n, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// n x 6 start poses through the pinned copy (ensure_out sized both); null stays null.
+icet_status stage_x0(icet_ctx* c, const float* x0, int32_t n, const float** d_x0) {
+    *d_x0 = nullptr;
+    if (!x0) return ICET_OK;
+    std::memcpy(c->h_x0, x0, sizeof(float) * 6 * n);
+    HIPCHK(c, hipMemcpyAsync(c->d_x0, c->h_x0, sizeof(float) * 6 * n, hipMemcpyHostToDevice, c->stream));
+    *d_x0 = c->d_x0;
+    return ICET_OK;
+}
 
 // (p + t) * R over a column-major scan (src/icet.cpp:375-378) with the device's own t and R (the transform record of write_xf): the host
 // half of `points2`.  Plain float arithmetic; the AVX2 + FMA build of the same loop is taken when the CPU has it.
@@ -399,25 +416,21 @@ LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs, PairDesc*
     return cfg;
 }
 
-// Before the host writes the pinned descriptor staging: the last copy out of it has run, and so has the last replayed graph, which re-reads it when it RUNS.
-icet_status wait_staging(icet_ctx* c) {
-    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
-    if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }
-    return ICET_OK;
+// The pair staging (h_desc / h_seg; a permuted batch carries the caller's pair of every slot behind the offsets) to the device.
+icet_status upload_desc(icet_ctx* c, int32_t n_pairs, bool by_next_kernel) {
+    ICET_TRY(staging_upload(c, c->w, c->h_desc, c->h_seg, n_pairs, (size_t)n_pairs + 1 + (c->perm_active ? n_pairs : 0), by_next_kernel));
+    return staging_mark_read(c);
 }
 
-icet_status upload_desc(icet_ctx* c, int32_t n_pairs, bool by_next_kernel = false) {
-    Workspace& w = c->w;
-    if (by_next_kernel) {
-        // (the caller's next launch, k_init_state, copies the pinned words itself)
-    } else if (n_pairs <= kUploadDescMaxPairs) {
-        HIPCHK(c, launch_upload_desc(w, c->h_desc, c->h_seg, n_pairs, c->stream));       // small batch: a kernel reads the pinned words (no copy command, no memcpy node)
-    } else {
-        HIPCHK(c, hipMemcpyAsync(w.desc, c->h_desc, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(w.seg_off, c->h_seg, sizeof(int32_t) * (n_pairs + 1 + (c->perm_active ? n_pairs : 0)), hipMemcpyHostToDevice, c->stream));
-    }
-    if (!c->ev_desc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
-    if (!c->capturing) { HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true; }     // (a captured event cannot be waited for on the host: the replay path orders the staging itself)
+// What the two loop enqueuers share besides the staging: the per-iteration timing events, and the close of a call's timing.
+icet_status grow_ev_acc(icet_ctx* c, int runlen) {
+    while ((int)c->ev_acc.size() < 2 * runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }
+    return ICET_OK;
+}
+icet_status close_timing(icet_ctx* c, const icet_params* p) {
+    if (c->capturing) return ICET_OK;
+    HIPCHK(c, hipEventRecord(c->ev_c, c->stream));
+    c->timing_valid = true; c->last_iters = (p->flags & ICET_FLAG_TIMING) ? p->runlen : 0;
     return ICET_OK;
 }
 
@@ -443,22 +456,22 @@ icet_status enqueue_keyframe(icet_ctx* c, const icet_params* p, int32_t n_pairs,
     }
     // a small batch: k_rs_splitters, the keyframe's first kernel, takes the descriptors from the pinned staging itself
     const bool first_uploads = n_pairs <= kUploadDescMaxPairs && !cfg.use_library_sort;
-    { icet_status us = upload_desc(c, n_pairs, first_uploads); if (us != ICET_OK) return us; }
+    ICET_TRY(upload_desc(c, n_pairs, first_uploads));
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
     LaunchCfg kcfg = cfg; if (first_uploads) { kcfg.h_desc_up = c->h_desc; kcfg.h_seg_up = c->h_seg; }
     HIPCHK(c, launch_keyframe(w, kcfg, aux, c->stream, d_counts1));      // (d_counts1: the descriptors hold upper bounds, the device knows the row counts: patched by the first kernel)
-    if (first_uploads && !c->capturing) { HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true; }      // (the staging has been read once these kernels have run)
+    if (first_uploads) ICET_TRY(staging_mark_read(c));                    // (the staging has been read once these kernels have run)
     return ICET_OK;
 }
 
 // ICET_FLAG_ROUNDTRIP_SCAN2: the round-tripped copy of the scan 2s that the host descriptors `hd` name -- and `wl.desc` on the device, which the
-// pre-pass reads --; on return wl's descriptors are the copy's (wl.desc = w.desc_rt).
-icet_status enqueue_rt2(icet_ctx* c, const LaunchCfg& cfg, int32_t n_pairs, const PairDesc* hd, Workspace& wl, hipEvent_t scan2_ready) {
+// pre-pass reads --; on return wl's descriptors are the copy's (wl.desc = w.desc_rt), and lcfg says that the copy is 64-float aligned whatever the caller's layout was.
+icet_status enqueue_rt2(icet_ctx* c, LaunchCfg& lcfg, int32_t n_pairs, const PairDesc* hd, Workspace& wl, hipEvent_t scan2_ready) {
     Workspace& w = c->w;
     int64_t tot = 0;
-    for (int k = 0; k < n_pairs; k++) tot += (hd[k].n2 + 63) / 64 * 64;
+    for (int k = 0; k < n_pairs; k++) tot += padded_ld(hd[k].n2);
     if (tot > w.cap_rt2 || !w.desc_rt || n_pairs > c->h_cap_rt) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); staging_idle(c);
         if (tot > w.cap_rt2) { w.cap_rt2 = 0, c->mem.rt2.release(); HIPCHK(c, c->mem.rt2.device(w.rt2, (size_t)3 * tot)); w.cap_rt2 = tot; }
         if (n_pairs > c->h_cap_rt || !w.desc_rt) {
             const int np = n_pairs > w.cap_pairs ? n_pairs : w.cap_pairs;
@@ -467,20 +480,21 @@ icet_status enqueue_rt2(icet_ctx* c, const LaunchCfg& cfg, int32_t n_pairs, cons
             HIPCHK(c, c->mem.rt_desc.pinned(c->h_desc_rt, np));
             c->h_cap_rt = np;
         }
-    } else if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
+    }
+    ICET_TRY(staging_wait(c));
     int64_t o = 0;
     for (int k = 0; k < n_pairs; k++) {
-        const int64_t l = (hd[k].n2 + 63) / 64 * 64;
+        const int64_t l = padded_ld(hd[k].n2);
         PairDesc dr = hd[k];
         dr.s2 = w.rt2 + 3 * o; dr.ld2 = (int32_t)l;
         c->h_desc_rt[k] = dr; o += l;
     }
     HIPCHK(c, hipMemcpyAsync(w.desc_rt, c->h_desc_rt, sizeof(PairDesc) * n_pairs, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
+    ICET_TRY(staging_mark_read(c, true));                                 // (never captured: graph_eligible refuses the round trip)
     if (scan2_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, scan2_ready, 0));
     wl.desc_rt = w.desc_rt; wl.rt2 = w.rt2; wl.cap_rt2 = w.cap_rt2;
-    HIPCHK(c, launch_rt2_prepare(wl, cfg, c->stream));
-    wl.desc = w.desc_rt;
+    HIPCHK(c, launch_rt2_prepare(wl, lcfg, c->stream));
+    wl.desc = w.desc_rt; lcfg.vec4_ok = 1;
     return ICET_OK;
 }
 
@@ -490,13 +504,13 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
     const LaunchCfg cfg = make_cfg(c, p, n_pairs);
     // the scan-2 halves arrived after the keyframe call.  A small batch without the scan-2 round trip: k_init_state, the first kernel below that reads a descriptor, uploads them
     const bool init_uploads = reupload && n_pairs <= kUploadDescMaxPairs && !cfg.rt2 && !cfg.keep;
-    if (reupload) { icet_status us = upload_desc(c, n_pairs, init_uploads); if (us != ICET_OK) return us; }
+    if (reupload) ICET_TRY(upload_desc(c, n_pairs, init_uploads));
     if (d_counts2 && cfg.rt2) HIPCHK(c, launch_patch_counts(w, cfg, nullptr, d_counts2, c->stream));      // (otherwise k_init_state, the loop's first kernel, patches them)
-    while ((int)c->ev_acc.size() < 2 * p->runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }
+    ICET_TRY(grow_ev_acc(c, p->runlen));
     Workspace wl = w;                                    // what the loop kernels see: with ICET_FLAG_ROUNDTRIP_SCAN2 their scan 2 is the round-tripped copy
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_b, c->stream));      // keyframe_ms ends here: the scan-2 pre-pass of ICET_FLAG_ROUNDTRIP_SCAN2 belongs to the loop
-    if (cfg.rt2) { const icet_status rs = enqueue_rt2(c, cfg, n_pairs, c->h_desc, wl, scan2_ready); if (rs != ICET_OK) return rs; }
-    LaunchCfg lcfg = cfg; if (cfg.rt2) lcfg.vec4_ok = 1;     // the copy is 64-float aligned whatever the caller's layout was
+    LaunchCfg lcfg = cfg;
+    if (cfg.rt2) ICET_TRY(enqueue_rt2(c, lcfg, n_pairs, c->h_desc, wl, scan2_ready));
     if (cfg.keep) {                                          // masks, list and per-pair state of the keep list (grown here: only throughput batches use them)
         int64_t tot2 = 0; for (int k = 0; k < n_pairs; k++) tot2 += c->h_desc[k].n2;
         const size_t need_mask = (size_t)(tot2 >> 8) + (size_t)n_pairs + 2, need_list = (size_t)(tot2 >> 2) + (size_t)n_pairs + 4;
@@ -515,7 +529,7 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
         }
     }
     HIPCHK(c, launch_init_state(w, cfg, d_x0, c->stream, want_pts2 ? aux->xf_last : nullptr, cfg.rt2 ? nullptr : d_counts2, init_uploads ? c->h_desc : nullptr, init_uploads ? c->h_seg : nullptr));
-    if (init_uploads && !c->capturing) { HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true; }      // (the staging is read by THIS kernel: the event of upload_desc, moved behind it)
+    if (init_uploads) ICET_TRY(staging_mark_read(c));                     // (the staging is read by THIS kernel: the mark of upload_desc, moved behind it)
     // `points2` (include/icet.h:80): scan 2 as the LAST fitScan2 transforms it (src/icet.cpp:375-378).  That transform is known as soon as the
     // solve of iteration runlen - 2 has run: k_gn_solve / k_init_state snapshot its record in aux->xf_last (pinned host memory) and ev_prev
     // marks the moment.  icet_solve_end then transforms scan 2 ON THE HOST while the last iteration still runs on the device (measured: a
@@ -531,7 +545,7 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
         return ICET_OK;
     };
     if (scan2_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, scan2_ready, 0));     // host-pointer entries: scan 2 was uploaded on the copy stream beside the keyframe build
-    if (want_pts2 && p->runlen == 1) { const icet_status ps = enqueue_points2(); if (ps != ICET_OK) return ps; }
+    if (want_pts2 && p->runlen == 1) ICET_TRY(enqueue_points2());
     const bool per_iter = (p->flags & ICET_FLAG_TIMING) != 0;
     for (int it = 0; it < p->runlen; it++) {
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it], c->stream));
@@ -544,17 +558,15 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
         HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream, per_iter ? nullptr : &fa, &fused, keep_pass ? 1 + 2 * (it & 1) : 0));
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it + 1], c->stream));
         if (!fused) HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, aux, c->stream, keep_pass ? (it + 1 < p->runlen ? 1 : 2) : 0));
-        if (want_pts2 && it == p->runlen - 2) { const icet_status ps = enqueue_points2(); if (ps != ICET_OK) return ps; }
+        if (want_pts2 && it == p->runlen - 2) ICET_TRY(enqueue_points2());
     }
-    if (!c->capturing) { HIPCHK(c, hipEventRecord(c->ev_c, c->stream)); c->timing_valid = true; c->last_iters = per_iter ? p->runlen : 0; }
-    return ICET_OK;
+    return close_timing(c, p);
 }
 
 // Enqueue the whole solve for descriptors already sitting in c->h_desc[0..n_pairs).
 icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const float* d_x0, float* d_out, const AuxDev* aux) {
     c->kf_pairs = 0;                                                    // whatever keyframe a sequential caller had parked here is overwritten
-    icet_status s = enqueue_keyframe(c, p, n_pairs, aux);
-    if (s != ICET_OK) return s;
+    ICET_TRY(enqueue_keyframe(c, p, n_pairs, aux));
     return enqueue_loop(c, p, n_pairs, d_x0, d_out, aux, false);
 }
 
@@ -578,27 +590,17 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
     if (src) { wl.hotS = src->hotS; wl.fitS = src->fitS; wl.slot_of_voxel = src->slot_of_voxel; wl.n_slots = src->n_slots; }
     // a small batch without the scan-2 round trip: k_init_state, the loop's first kernel, copies the staging itself (a replayed graph re-reads it then)
     const bool init_uploads = n_regs <= kUploadDescMaxPairs && !cfg.rt2;
-    if (!init_uploads) {
-        if (n_regs <= kUploadDescMaxPairs) HIPCHK(c, launch_upload_desc(wl, c->h_desc_reg, c->h_kf_of, n_regs, c->stream));
-        else {
-            HIPCHK(c, hipMemcpyAsync(w.desc_reg, c->h_desc_reg, sizeof(PairDesc) * n_regs, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(w.kf_of, c->h_kf_of, sizeof(int32_t) * (n_regs + 1), hipMemcpyHostToDevice, c->stream));
-        }
-        if (!c->ev_desc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;      // (never captured: a graph replays small batches without the round trip only)
-    }
-    while ((int)c->ev_acc.size() < 2 * p->runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }
+    ICET_TRY(staging_upload(c, wl, c->h_desc_reg, c->h_kf_of, n_regs, (size_t)n_regs + 1, init_uploads));
+    if (!init_uploads) ICET_TRY(staging_mark_read(c, true));              // (a graph replays small batches without the round trip only: this path records whatever `capturing` says)
+    ICET_TRY(grow_ev_acc(c, p->runlen));
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_b, c->stream));        // (no keyframe build in this call: keyframe_ms = 0)
     if (cfg.rt2 && dev) HIPCHK(c, launch_patch_counts(wl, cfg, nullptr, dev->rows, c->stream));      // (the pre-pass reads the counts of the caller's descriptors)
-    if (cfg.rt2) { const icet_status rs = enqueue_rt2(c, cfg, n_regs, c->h_desc_reg, wl, nullptr); if (rs != ICET_OK) return rs; }
-    LaunchCfg lcfg = cfg; if (cfg.rt2) lcfg.vec4_ok = 1;                     // the copy is 64-float aligned whatever the caller's layout was
+    LaunchCfg lcfg = cfg;
+    if (cfg.rt2) ICET_TRY(enqueue_rt2(c, lcfg, n_regs, c->h_desc_reg, wl, nullptr));
     HIPCHK(c, launch_init_state(wl, lcfg, d_x0, c->stream, nullptr, dev ? dev->rows : nullptr, init_uploads ? c->h_desc_reg : nullptr, init_uploads ? c->h_kf_of : nullptr));
     if (dev) HIPCHK(c, launch_closure_apply(w.kf_of, dev->kf_of, n_regs, c->stream));
-    if (init_uploads && !c->capturing) {
-        if (!c->ev_desc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
-    }
+    if (init_uploads) ICET_TRY(staging_mark_read(c));
     const bool per_iter = (p->flags & ICET_FLAG_TIMING) != 0;
     for (int it = 0; it < iters; it++) {
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it], c->stream));
@@ -633,8 +635,7 @@ icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, c
         if (d_dump) HIPCHK(c, launch_point_sums_dump(wl, lcfg, d_dump, c->stream));      // (icet_debug_point_sums_device: the raw sums in place of the score)
         else HIPCHK(c, launch_gn_score(wl, lcfg, p->runlen, d_score, c->stream));
     }
-    if (!c->capturing) { HIPCHK(c, hipEventRecord(c->ev_c, c->stream)); c->timing_valid = true; c->last_iters = per_iter ? p->runlen : 0; }
-    return ICET_OK;
+    return close_timing(c, p);
 }
 
 // Staging buffers of the host-pointer entry points (3 x l floats per scan, leading dimension l = n rounded up to 64).
@@ -785,17 +786,14 @@ static icet_status solve_device_part(icet_ctx* c, const icet_params* p, int32_t 
 icet_status icet_solve_batch_device(icet_ctx* c, const icet_params* p, int32_t n_pairs,
                                     const icet_dev_scan* scan1, const icet_dev_scan* scan2,
                                     const float* d_x0, float* d_out) {
-    if (!c) return ICET_ERR_BAD_ARG;
+    ICET_TRY(use_device(c));                                              // the arming entry: solve_device_part keeps armed_calls
     if (!params_ok(p) || n_pairs < 0 || (n_pairs > 0 && (!scan1 || !scan2 || !d_out))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n_pairs == 0) return ICET_OK;
-    for (int k = 0; k < n_pairs; k++) {
-        const icet_dev_scan &a = scan1[k], &b = scan2[k];
-        if (!dev_scan_ok(a) || !dev_scan_ok(b)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-    }
-    HIPCHK(c, hipSetDevice(c->device));
+    int64_t tot1 = 0, tot2 = 0;
+    if (!dev_scans_ok(scan1, n_pairs, &tot1) || !dev_scans_ok(scan2, n_pairs, &tot2)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
     const int parts = (p->runlen == 0) ? 1 : batch_parts(c, p, n_pairs);
     auto range_tot = [&](int b, int e) { int64_t t = 0; for (int k = b; k < e; k++) t += scan1[k].n; return t; };
-    if (parts == 1) return solve_device_part(c, p, n_pairs, scan1, scan2, d_x0, d_out, range_tot(0, n_pairs));
+    if (parts == 1) return solve_device_part(c, p, n_pairs, scan1, scan2, d_x0, d_out, tot1);
     c->armed_calls = 2;
     { icet_status s = ensure_helpers(c, parts); if (s != ICET_OK) return s; }
     // fork: helpers start after whatever the caller queued on this context's stream (e.g. the writes of the scans)
@@ -870,7 +868,7 @@ template <typename Enq> static icet_status run_or_replay(icet_ctx* c, icet_ctx::
     auto same = [](const icet_ctx::GraphKey& a, const icet_ctx::GraphKey& b) { return std::memcmp(&a, &b, sizeof(a)) == 0; };
     if (slot.have_graph && same(key, slot.key)) {
         HIPCHK(c, hipGraphLaunch(slot.exec, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_graph, c->stream)); c->graph_in_flight = true;
+        ICET_TRY(staging_mark_replay(c));
         c->timing_valid = false;
         return ICET_OK;
     }
@@ -893,7 +891,7 @@ template <typename Enq> static icet_status run_or_replay(icet_ctx* c, icet_ctx::
         if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); (void)hipGetLastError(); slot.have_seen = false; return enq(); }
         slot.graph = g; slot.exec = ge; slot.key = key; slot.have_graph = true;
         HIPCHK(c, hipGraphLaunch(slot.exec, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev_graph, c->stream)); c->graph_in_flight = true;
+        ICET_TRY(staging_mark_replay(c));
         c->timing_valid = false;
         return ICET_OK;
     }
@@ -906,12 +904,10 @@ static icet_status solve_device_part(icet_ctx* c, const icet_params* p, int32_t 
                                      const float* d_x0, float* d_out, int64_t tot1) {
     int64_t tot2 = 0; for (int k = 0; k < n_pairs; k++) tot2 += scan2[k].n;
     c->kf_pairs = 0;                           // whatever keyframe was parked here is gone (runlen == 0 included: h_desc is overwritten below)
-    icet_status s = ensure_workspace(c, p, n_pairs, tot1, tot2);
-    if (s != ICET_OK) return s;
+    ICET_TRY(ensure_workspace(c, p, n_pairs, tot1, tot2));
     // the previous call may still be copying out of the pinned descriptor staging; its kernels may still be running
     // (the device entry point never waits for them: calls queue up behind each other on the stream)
-    s = wait_staging(c);
-    if (s != ICET_OK) return s;
+    ICET_TRY(staging_wait(c));
     c->desc_kf_valid = c->desc_reg_valid = false;
     // A RAGGED throughput batch is laid out XCD-balanced (round 6; icet_layout.h says why and how).  The caller's order comes back in k_init_state (X0) and
     // k_gn_solve (results): LaunchCfg::pair_user.  Same bits: a pair's result does not depend on its slot (section 6 of DESIGN.md).
@@ -929,15 +925,11 @@ static icet_status solve_device_part(icet_ctx* c, const icet_params* p, int32_t 
     }
     for (int s = 0; s < n_pairs; s++) {
         const int k = order[(size_t)s];
-        PairDesc& d = c->h_desc[s];
-        d.s1 = scan1[k].ptr; d.s2 = scan2[k].ptr;
-        d.n1 = (int32_t)scan1[k].n; d.ld1 = (int32_t)scan1[k].ld; d.n2 = (int32_t)scan2[k].n; d.ld2 = (int32_t)scan2[k].ld;
-        d.off1 = 0; d.off2 = 0;
+        set_scan1(c->h_desc[s], scan1[k]); set_scan2(c->h_desc[s], scan2[k]);
     }
     if (p->runlen == 0) { c->armed_calls = 2; return write_runlen0(c, n_pairs, d_x0, d_out); }
     if (graph_eligible(c, p, n_pairs)) {
-        icet_status ts = ensure_thresholds(c, p->bins_theta, p->bins_phi);
-        if (ts != ICET_OK) return ts;
+        ICET_TRY(ensure_thresholds(c, p->bins_theta, p->bins_phi));
         // (the solve's last kernel raises the context's sync word: icet_sync)
         const bool own_word = !c->done_flag && c->h_sync_word;
         if (own_word) { if (c->armed_calls == 0) *static_cast<volatile int32_t*>(c->h_sync_word) = 0; c->done_flag = c->h_sync_word; }
@@ -954,35 +946,22 @@ icet_status icet_keyframe_device(icet_ctx* c, const icet_params* p, int32_t n_pa
 }
 
 icet_status icet_keyframe_device_n(icet_ctx* c, const icet_params* p, int32_t n_pairs, const icet_dev_scan* scan1, const int32_t* d_rows) {
-    if (!c) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(c));
     if (!params_ok(p) || n_pairs < 1 || !scan1) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     int64_t tot1 = 0;
-    for (int k = 0; k < n_pairs; k++) {
-        const icet_dev_scan& a = scan1[k];
-        if (!dev_scan_ok(a)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-        tot1 += a.n;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    c->kf_pairs = 0; c->perm_active = false; c->armed_calls = 2;
+    if (!dev_scans_ok(scan1, n_pairs, &tot1)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
+    c->kf_pairs = 0; c->perm_active = false;
     icet_status s = ensure_workspace(c, p, n_pairs, tot1, 0);
     if (s != ICET_OK) return s;
     // A sequential caller hands the SAME buffers to this half frame after frame (include/icet_nodes.h): the pinned descriptor staging then already holds
     // this call's scan-1 halves and is left alone -- rewriting it means waiting, on the HOST, for whatever replay or copy of this context still reads it,
     // and a burst of frames (icet_node_push_many_device) would have the host wait for the device twice per frame instead of running ahead
     bool same_desc = c->desc_kf_valid;                                     // (only what the previous call of THIS entry wrote counts: raw staging memory proves nothing)
-    for (int k = 0; k < n_pairs && same_desc; k++) {
-        const PairDesc& d = c->h_desc[k];
-        same_desc = d.s1 == scan1[k].ptr && d.n1 == (int32_t)scan1[k].n && d.ld1 == (int32_t)scan1[k].ld;
-    }
+    for (int k = 0; k < n_pairs && same_desc; k++) same_desc = same_scan1(c->h_desc[k], scan1[k]);
     if (!same_desc) {
         c->desc_reg_valid = false;                                         // the scan-2 halves are reset below
-        s = wait_staging(c);
-        if (s != ICET_OK) return s;
-        for (int k = 0; k < n_pairs; k++) {
-            PairDesc& d = c->h_desc[k];
-            d.s1 = scan1[k].ptr; d.n1 = (int32_t)scan1[k].n; d.ld1 = (int32_t)scan1[k].ld;
-            d.s2 = nullptr; d.n2 = 0; d.ld2 = 0; d.off1 = 0; d.off2 = 0;
-        }
+        ICET_TRY(staging_wait(c));
+        for (int k = 0; k < n_pairs; k++) set_scan1(c->h_desc[k], scan1[k]);
         c->desc_kf_valid = true;
     }
     if (graph_eligible(c, p, n_pairs)) {
@@ -999,29 +978,19 @@ icet_status icet_register_device(icet_ctx* c, const icet_params* p, int32_t n_pa
 }
 
 icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_pairs, const icet_dev_scan* scan2, const int32_t* d_rows, const float* d_x0, float* d_out) {
-    if (!c) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(c));
     if (!params_ok(p) || n_pairs < 1 || !scan2 || !d_out) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (c->kf_pairs != n_pairs || !same_keyframe_shape(c->kf_params, *p)) { c->err = "no keyframe with these parameters is parked in this context (icet_keyframe_device)"; return ICET_ERR_BAD_ARG; }
     int64_t tot2 = 0;
-    for (int k = 0; k < n_pairs; k++) {
-        const icet_dev_scan& b = scan2[k];
-        if (!dev_scan_ok(b)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-        tot2 += b.n;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    c->armed_calls = 2;
+    if (!dev_scans_ok(scan2, n_pairs, &tot2)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
     if (p->runlen == 0) return write_runlen0(c, n_pairs, d_x0, d_out);
     icet_status s = ensure_workspace(c, p, n_pairs, 0, tot2);              // only the scan-2 overflow list can grow here: the keyframe tables stay
     if (s != ICET_OK) return s;
     bool same_desc = c->desc_reg_valid;                                    // (see icet_keyframe_device_n)
-    for (int k = 0; k < n_pairs && same_desc; k++) {
-        const PairDesc& d = c->h_desc[k];
-        same_desc = d.s2 == scan2[k].ptr && d.n2 == (int32_t)scan2[k].n && d.ld2 == (int32_t)scan2[k].ld;
-    }
+    for (int k = 0; k < n_pairs && same_desc; k++) same_desc = same_scan2(c->h_desc[k], scan2[k]);
     if (!same_desc) {
-        s = wait_staging(c);
-        if (s != ICET_OK) return s;
-        for (int k = 0; k < n_pairs; k++) { PairDesc& d = c->h_desc[k]; d.s2 = scan2[k].ptr; d.n2 = (int32_t)scan2[k].n; d.ld2 = (int32_t)scan2[k].ld; }
+        ICET_TRY(staging_wait(c));
+        for (int k = 0; k < n_pairs; k++) set_scan2(c->h_desc[k], scan2[k]);
         c->desc_reg_valid = true;
     }
     s = ensure_thresholds(c, p->bins_theta, p->bins_phi);                 // (a keyframe store's call on another grid may have rebuilt them since the keyframe was parked)
@@ -1054,23 +1023,19 @@ icet_status icet::register_indexed(icet_ctx* c, const icet_params* p, int32_t n_
             c->err = "slot_index[" + std::to_string(r) + "] = " + std::to_string(kf_index[r]) + " is not an occupied slot of the store (capacity " + std::to_string(n_kf) + ")"; return ICET_ERR_BAD_ARG;
         }
         if (kf_index[r] < 0 || kf_index[r] >= n_kf) { c->err = "kf_index[" + std::to_string(r) + "] = " + std::to_string(kf_index[r]) + " is not a parked keyframe (0 .. " + std::to_string(c->kf_pairs - 1) + ")"; return ICET_ERR_BAD_ARG; }
-        const icet_dev_scan& b = scan2[r];
-        if (!dev_scan_ok(b)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
-        tot2 += b.n;
     }
+    if (!dev_scans_ok(scan2, n_regs, &tot2)) { c->err = "bad scan descriptor"; return ICET_ERR_BAD_ARG; }
     if (c->tune.keep != 0) { c->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
-    HIPCHK(c, hipSetDevice(c->device));
-    c->armed_calls = 2;
+    ICET_TRY(enter(c));
     if (mode == kIdxRegister && p->runlen == 0) return write_runlen0(c, n_regs, d_x0, d_out);
     icet_status s = ensure_regs(c, n_regs, p->bins_phi * p->bins_theta);   // the registration side only: the keyframe tables stay where they are
     if (s == ICET_OK) s = ensure_scan2(c, tot2);
     if (s == ICET_OK) s = ensure_thresholds(c, p->bins_theta, p->bins_phi);
-    if (s == ICET_OK) s = wait_staging(c);                                // the previous call may still read the registration staging
+    if (s == ICET_OK) s = staging_wait(c);                                // the previous call may still read the registration staging
     if (s != ICET_OK) return s;
     for (int r = 0; r < n_regs; r++) {
-        PairDesc& d = c->h_desc_reg[r];
-        d.s1 = nullptr; d.n1 = 0; d.ld1 = 0; d.off1 = 0; d.off2 = 0;      // (the loop reads no scan-1 field)
-        d.s2 = scan2[r].ptr; d.n2 = (int32_t)scan2[r].n; d.ld2 = (int32_t)scan2[r].ld;
+        set_scan1(c->h_desc_reg[r], icet_dev_scan{nullptr, 0, 0});        // (the loop reads no scan-1 field)
+        set_scan2(c->h_desc_reg[r], scan2[r]);
         c->h_kf_of[r] = kf_index[r];
     }
     c->h_kf_of[n_regs] = 0;
@@ -1149,52 +1114,33 @@ static icet_status solve_indexed_host(icet_ctx* c, const icet_params* p, int32_t
     if (!params_ok(p) || n_kf < 1 || n_regs < 0 || !scan1 || !n1 || (n_regs > 0 && (!kf_index || !scan2 || !n2 || (need_out && (!x_out || !pred_stds_out)) ||
                                                                                      (mode != kIdxRegister && !score_out) || (mode == kIdxScoreOnly && !x0)))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (c->pend.active) { c->err = "icet_solve_begin without icet_solve_end on this context"; return ICET_ERR_BAD_ARG; }
-    int64_t tot1 = 0, tot2 = 0;
-    for (int k = 0; k < n_kf; k++) {
+    for (int k = 0; k < n_kf; k++)
         if (n1[k] < 0 || (n1[k] > 0 && !scan1[k])) { c->err = "bad scan"; return ICET_ERR_BAD_ARG; }
-        tot1 += (n1[k] + 63) / 64 * 64;
-    }
     for (int r = 0; r < n_regs; r++) {
         if (n2[r] < 0 || (n2[r] > 0 && !scan2[r])) { c->err = "bad scan"; return ICET_ERR_BAD_ARG; }
         if (kf_index[r] < 0 || kf_index[r] >= n_kf) { c->err = "kf_index[" + std::to_string(r) + "] out of range"; return ICET_ERR_BAD_ARG; }
-        tot2 += (n2[r] + 63) / 64 * 64;
     }
     if (n_regs == 0) return ICET_OK;
-    HIPCHK(c, hipSetDevice(c->device));
+    ICET_TRY(enter(c));
     icet_status s = ensure_out(c, n_regs);
-    if (s == ICET_OK) s = ensure_stage(c, tot1, tot2);
+    if (s == ICET_OK) s = ensure_stage(c, stage_layout(n1, n_kf, nullptr, nullptr), stage_layout(n2, n_regs, nullptr, nullptr));
     if (s == ICET_OK && mode != kIdxRegister) s = ensure_score(c, n_regs);
     if (s != ICET_OK) return s;
     // scans into the staging buffers (dense column-major), then the two device halves
     std::vector<icet_dev_scan> d1((size_t)n_kf), d2((size_t)n_regs);
-    int64_t o = 0;
-    for (int k = 0; k < n_kf; k++) {
-        const int64_t l = (n1[k] + 63) / 64 * 64;
-        d1[(size_t)k] = icet_dev_scan{c->d_stage1 + 3 * o, n1[k], l};
-        HIPCHK(c, upload_scan(c->d_stage1 + 3 * o, l, scan1[k], n1[k], n1[k], c->stream));
-        o += l;
-    }
-    o = 0;
-    for (int r = 0; r < n_regs; r++) {
-        const int64_t l = (n2[r] + 63) / 64 * 64;
-        d2[(size_t)r] = icet_dev_scan{c->d_stage2 + 3 * o, n2[r], l};
-        HIPCHK(c, upload_scan(c->d_stage2 + 3 * o, l, scan2[r], n2[r], n2[r], c->stream));
-        o += l;
-    }
+    stage_layout(n1, n_kf, c->d_stage1, d1.data()); stage_layout(n2, n_regs, c->d_stage2, d2.data());
+    HIPCHK(c, upload_staged(d1.data(), scan1, n_kf, c->stream));
+    HIPCHK(c, upload_staged(d2.data(), scan2, n_regs, c->stream));
     const float* dx0 = nullptr;
-    if (x0) { std::memcpy(c->h_x0, x0, sizeof(float) * 6 * n_regs); HIPCHK(c, hipMemcpyAsync(c->d_x0, c->h_x0, sizeof(float) * 6 * n_regs, hipMemcpyHostToDevice, c->stream)); dx0 = c->d_x0; }
+    ICET_TRY(stage_x0(c, x0, n_regs, &dx0));
     s = icet_keyframe_device(c, p, n_kf, d1.data());
     if (s == ICET_OK) s = register_indexed(c, p, n_regs, kf_index, d2.data(), dx0, need_out ? c->d_out : nullptr, mode != kIdxRegister ? c->d_score : nullptr, mode);
     if (s != ICET_OK) { (void)hipStreamSynchronize(c->stream); return s; }
     if (need_out) HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(float) * 48 * n_regs, hipMemcpyDeviceToHost, c->stream));
     if (mode != kIdxRegister) HIPCHK(c, hipMemcpyAsync(c->h_score, c->d_score, sizeof(icet_score) * n_regs, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->armed_calls = 0; c->desc_in_flight = false; c->graph_in_flight = false;
-    for (int r = 0; r < n_regs && need_out; r++) {
-        std::memcpy(x_out + 6 * r, c->h_out + 48 * r, 6 * sizeof(float));
-        std::memcpy(pred_stds_out + 6 * r, c->h_out + 48 * r + 6, 6 * sizeof(float));
-        if (cov_out) std::memcpy(cov_out + 36 * r, c->h_out + 48 * r + 12, 36 * sizeof(float));
-    }
+    c->armed_calls = 0; staging_idle(c);                                  // (a caller that alternates this entry with device calls would otherwise wait for events long past)
+    if (need_out) unpack_results(c->h_out, n_regs, x_out, pred_stds_out, cov_out);
     if (mode != kIdxRegister) std::memcpy(score_out, c->h_score, sizeof(icet_score) * n_regs);
     return ICET_OK;
 }
@@ -1224,7 +1170,7 @@ icet_status icet_select_best_device(icet_ctx* c, int32_t n_regs, const int32_t* 
     for (int r = 0; r < n_regs; r++)
         if (group[r] < 0 || group[r] >= n_groups) { c->err = "group[" + std::to_string(r) + "] = " + std::to_string(group[r]) + " is not a group (0 .. " + std::to_string(n_groups - 1) + ")"; return ICET_ERR_BAD_ARG; }
     if (n_groups == 0) return ICET_OK;
-    HIPCHK(c, hipSetDevice(c->device));
+    ICET_TRY(enter(c));
     // members of every group in ascending order, then the offsets: one upload from pinned staging
     const int64_t need = (int64_t)n_regs + n_groups + 1;
     if (c->sel_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_sel)); c->sel_in_flight = false; }
@@ -1244,7 +1190,6 @@ icet_status icet_select_best_device(icet_ctx* c, int32_t n_regs, const int32_t* 
     HIPCHK(c, hipMemcpyAsync(c->d_sel, c->h_sel, sizeof(int32_t) * (size_t)need, hipMemcpyHostToDevice, c->stream));
     if (!c->ev_sel) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sel, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ev_sel, c->stream)); c->sel_in_flight = true;
-    c->armed_calls = 2;
     HIPCHK(c, launch_select_best(c->d_sel, c->d_sel + n_regs, n_groups, d_score, d_out, d_best, d_best_out, c->stream));
     return ICET_OK;
 }
@@ -1256,46 +1201,32 @@ icet_status icet_solve_batch(icet_ctx* c, const icet_params* p, int32_t n_pairs,
     if (!params_ok(p) || n_pairs < 0 || (n_pairs > 0 && (!scan1 || !n1 || !scan2 || !n2 || !x_out || !pred_stds_out))) { c->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (c->pend.active) { c->err = "icet_solve_begin without icet_solve_end on this context"; return ICET_ERR_BAD_ARG; }
     if (n_pairs == 0) return ICET_OK;
-    int64_t tot1 = 0, tot2 = 0;
-    for (int k = 0; k < n_pairs; k++) {
+    for (int k = 0; k < n_pairs; k++)
         if (n1[k] < 0 || n2[k] < 0 || (n1[k] > 0 && !scan1[k]) || (n2[k] > 0 && !scan2[k])) { c->err = "bad scan"; return ICET_ERR_BAD_ARG; }
-        tot1 += (n1[k] + 63) / 64 * 64; tot2 += (n2[k] + 63) / 64 * 64;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
+    ICET_TRY(enter(c));
+    const int64_t tot1 = stage_layout(n1, n_pairs, nullptr, nullptr), tot2 = stage_layout(n2, n_pairs, nullptr, nullptr);
     icet_status s = ensure_workspace(c, p, n_pairs, tot1, tot2);
     if (s == ICET_OK) s = ensure_out(c, n_pairs);
     if (s == ICET_OK) s = ensure_host_path(c);
     if (s == ICET_OK) s = ensure_stage(c, tot1, tot2);
+    if (s == ICET_OK) s = staging_wait(c);
     if (s != ICET_OK) return s;
-    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
     // Scan 1 of every pair goes up first on the solve stream (the keyframe build needs nothing else); the scan 2s follow on the copy
     // stream while the keyframe kernels run, and the loop waits for them.  Host scans are dense column-major (ld == n) in this entry point.
-    int64_t o1 = 0, o2 = 0;
+    std::vector<icet_dev_scan> d1((size_t)n_pairs), d2((size_t)n_pairs);
+    stage_layout(n1, n_pairs, c->d_stage1, d1.data()); stage_layout(n2, n_pairs, c->d_stage2, d2.data());
     c->desc_kf_valid = c->desc_reg_valid = false;
-    for (int k = 0; k < n_pairs; k++) {
-        const int64_t l1 = (n1[k] + 63) / 64 * 64, l2 = (n2[k] + 63) / 64 * 64;
-        PairDesc& d = c->h_desc[k];
-        d.s1 = c->d_stage1 + 3 * o1; d.s2 = c->d_stage2 + 3 * o2;
-        d.n1 = (int32_t)n1[k]; d.ld1 = (int32_t)l1; d.n2 = (int32_t)n2[k]; d.ld2 = (int32_t)l2; d.off1 = 0; d.off2 = 0;
-        HIPCHK(c, upload_scan(c->d_stage1 + 3 * o1, l1, scan1[k], n1[k], n1[k], c->stream));
-        o1 += l1; o2 += l2;
-    }
+    for (int k = 0; k < n_pairs; k++) { set_scan1(c->h_desc[k], d1[(size_t)k]); set_scan2(c->h_desc[k], d2[(size_t)k]); }
+    HIPCHK(c, upload_staged(d1.data(), scan1, n_pairs, c->stream));
     const float* dx0 = nullptr;
-    if (x0) { std::memcpy(c->h_x0, x0, sizeof(float) * 6 * n_pairs); HIPCHK(c, hipMemcpyAsync(c->d_x0, c->h_x0, sizeof(float) * 6 * n_pairs, hipMemcpyHostToDevice, c->stream)); dx0 = c->d_x0; }
-    auto upload_scan2s = [&]() -> hipError_t {
-        for (int k = 0; k < n_pairs; k++) {
-            const PairDesc& d = c->h_desc[k];
-            hipError_t e = upload_scan(const_cast<float*>(d.s2), d.ld2, scan2[k], n2[k], n2[k], c->st_copy);
-            if (e != hipSuccess) return e;
-        }
-        return hipEventRecord(c->ev_s2, c->st_copy);
-    };
+    ICET_TRY(stage_x0(c, x0, n_pairs, &dx0));
     if (p->runlen == 0) s = write_runlen0(c, n_pairs, dx0, c->d_out);
     else {
-        c->kf_pairs = 0; c->perm_active = false; c->armed_calls = 2;
+        c->kf_pairs = 0; c->perm_active = false;
         s = enqueue_keyframe(c, p, n_pairs, nullptr);
         if (s == ICET_OK) {
-            const hipError_t e = upload_scan2s();
+            hipError_t e = upload_staged(d2.data(), scan2, n_pairs, c->st_copy);
+            if (e == hipSuccess) e = hipEventRecord(c->ev_s2, c->st_copy);
             if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->st_copy); c->err = std::string("scan-2 upload: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
             s = enqueue_loop(c, p, n_pairs, dx0, c->d_out, nullptr, false, nullptr, c->ev_s2);
         }
@@ -1303,11 +1234,8 @@ icet_status icet_solve_batch(icet_ctx* c, const icet_params* p, int32_t n_pairs,
     if (s != ICET_OK) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->st_copy); return s; }
     HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(float) * 48 * n_pairs, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < n_pairs; k++) {
-        std::memcpy(x_out + 6 * k, c->h_out + 48 * k, 6 * sizeof(float));
-        std::memcpy(pred_stds_out + 6 * k, c->h_out + 48 * k + 6, 6 * sizeof(float));
-        if (cov_out) std::memcpy(cov_out + 36 * k, c->h_out + 48 * k + 12, 36 * sizeof(float));
-    }
+    staging_idle(c);
+    unpack_results(c->h_out, n_pairs, x_out, pred_stds_out, cov_out);
     return ICET_OK;
 }
 
@@ -1323,9 +1251,9 @@ icet_status icet_solve_begin(icet_ctx* c, const icet_params* p, const float* sca
         c->err = "bad argument"; return ICET_ERR_BAD_ARG;
     }
     if (c->pend.active) { c->err = "icet_solve_begin without icet_solve_end on this context"; return ICET_ERR_BAD_ARG; }
-    HIPCHK(c, hipSetDevice(c->device));
+    ICET_TRY(enter(c));
     const int V = p->bins_phi * p->bins_theta;
-    const int64_t l1 = (n1 + 63) / 64 * 64, l2 = (n2 + 63) / 64 * 64;
+    const int64_t l1 = padded_ld(n1), l2 = padded_ld(n2);
     icet_status s = ensure_workspace(c, p, 1, l1, l2);
     if (s == ICET_OK) s = ensure_out(c, 1);
     if (s == ICET_OK) s = ensure_host_path(c);
@@ -1360,14 +1288,13 @@ icet_status icet_solve_begin(icet_ctx* c, const icet_params* p, const float* sca
         HIPCHK(c, c->mem.side2.device(c->d_sph2, (size_t)3 * n2)); HIPCHK(c, c->mem.side2.device(c->d_vox2, (size_t)n2)); c->cap_side2 = (size_t)n2;
         if ((size_t)3 * n2 > c->cap_pts2) { const icet_status gs = grow_pts2((size_t)3 * n2); if (gs != ICET_OK) return gs; }
     }
-    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
+    ICET_TRY(staging_wait(c));
     // (no stream synchronisation up front: the staging buffers, the result block and the pinned x0 are only ever used by the host-pointer
-    // entry points, each of which has drained the stream before it returned)
+    // entry points, each of which has drained the stream before it returned; the pinned descriptors are the device entries' too: the wait above)
     std::memcpy(c->h_x0, x0, 6 * sizeof(float));                              // pinned: k_init_state reads X0 straight from it (no H2D command)
     HIPCHK(c, upload_scan(c->d_stage1, l1, scan1, n1, ld1, c->stream));
     c->desc_kf_valid = c->desc_reg_valid = false;
-    PairDesc& d = c->h_desc[0];
-    d.s1 = c->d_stage1; d.s2 = c->d_stage2; d.n1 = (int32_t)n1; d.ld1 = (int32_t)l1; d.n2 = (int32_t)n2; d.ld2 = (int32_t)l2; d.off1 = 0; d.off2 = 0;
+    set_scan1(c->h_desc[0], icet_dev_scan{c->d_stage1, n1, l1}); set_scan2(c->h_desc[0], icet_dev_scan{c->d_stage2, n2, l2});
     const AuxLayout L = aux_layout(V, p->runlen);
     float* h_res = reinterpret_cast<float*>(c->h_pack) + L.out;               // the 48 result floats on the host
     float* d_res = reinterpret_cast<float*>(c->d_pack) + L.out;               // ... and where k_gn_solve writes them
@@ -1394,7 +1321,7 @@ icet_status icet_solve_begin(icet_ctx* c, const icet_params* p, const float* sca
             q.scan2 = scan2; q.ld2 = ld2;
             if (!want_pts2 && !want_side2) ad.xf_last = nullptr;
         }
-        c->kf_pairs = 0; c->perm_active = false; c->armed_calls = 2;
+        c->kf_pairs = 0; c->perm_active = false;
         st = enqueue_keyframe(c, p, 1, aux ? &ad : nullptr);
         if (st == ICET_OK && want_side1) {                                     // points1Spherical / pointIndices1 from the tables the keyframe build has just left
             const LaunchCfg scfg = make_cfg(c, p, 1);
@@ -1473,9 +1400,7 @@ icet_status icet_solve_end(icet_ctx* c) {
     if (ks != ICET_OK) return ks;
     const AuxLayout L = aux_layout(q.V, q.rl);
     const float* out = reinterpret_cast<const float*>(c->h_pack) + L.out;
-    std::memcpy(q.x_out, out, 6 * sizeof(float));
-    std::memcpy(q.ps_out, out + 6, 6 * sizeof(float));
-    if (q.cov_out) std::memcpy(q.cov_out, out + 12, 36 * sizeof(float));
+    unpack_results(out, 1, q.x_out, q.ps_out, q.cov_out);
     if (q.has_aux) {
         const icet_aux& a = q.aux; const size_t rl = q.rl, v = (size_t)q.V;
         auto add = [&](void* dst, size_t at, size_t n) { if (dst && n) std::memcpy(dst, c->h_pack + at, n * sizeof(uint32_t)); };

@@ -1,5 +1,6 @@
 // icet_amd/csrc/icet_ctx.h -- what the two host translation units share: the context (icet_capi.hip owns it), the keyframe store that borrows one (icet_store.hip
-// owns it; the indexed registrations read its tables), the argument checks, and the indexed registrations both run.
+// owns it; the indexed registrations read its tables), the argument checks, the two protocols around the context -- who writes the pinned descriptor staging and
+// when (staging_*), and how an entry that enqueues begins (enter) --, and the indexed registrations both run.
 #pragma once
 #include "../../include/icet_hip.h"
 #include "icet_internal.h"
@@ -61,7 +62,7 @@ struct icet_ctx {
     std::vector<icet_ctx*> helpers;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_stage = nullptr; int stage_at = 0;            // see LaunchCfg::stage_event
-    hipEvent_t ev_desc = nullptr; bool desc_in_flight = false;   // completion of the last copy out of the pinned descriptor staging
+    hipEvent_t ev_desc = nullptr; bool desc_in_flight = false;   // the last copy or kernel that read the pinned descriptor staging (staging_mark_read / staging_wait, below: nobody else touches them)
     // Small device batches whose launch geometry repeats call after call are replayed from a captured hipGraph (option "graph"): the ~33
     // launches of a single-pair solve then cost one hipGraphLaunch on the host, and the command processor runs them back to back.
     struct GraphKey { int64_t v[47]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key + the keyframe source (graph_key_of)
@@ -70,7 +71,7 @@ struct icet_ctx {
     bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
     GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
     GraphSlot g_scored, g_score;                               // indexed registrations + score (icet_register_indexed_scored_device), the score of given poses (icet_score_indexed_device)
-    hipEvent_t ev_graph = nullptr; bool graph_in_flight = false;
+    hipEvent_t ev_graph = nullptr; bool graph_in_flight = false;      // the last replay, which re-reads that staging when it runs (staging_mark_replay / staging_wait)
     // A caller inside this library (the sequential nodes, icet_nodes.hip) can put work of its own at the head of the NEXT icet_register_device_n call's launch
     // sequence -- enqueued on the context's stream right before the loop's first kernel, captured into the same graph: the range filter and the loop of a frame
     // are then ONE hipGraphLaunch (round 6: the loop's graph used to start 30-40 us after the filter's last kernel).  `prologue_key` names what the hook's
@@ -156,6 +157,8 @@ namespace icet {
     (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
     return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
 
+#define ICET_TRY(call) do { const icet_status s_ = (call); if (s_ != ICET_OK) return s_; } while (0)
+
 static inline bool params_ok(const icet_params* p) {
     if (!p) return false;
     if (p->runlen < 0 || p->runlen > 4096) return false;
@@ -163,7 +166,71 @@ static inline bool params_ok(const icet_params* p) {
     return true;
 }
 
-static inline bool dev_scan_ok(const icet_dev_scan& a) { return !(a.n < 0 || a.ld < a.n || (a.n > 0 && !a.ptr) || a.ld >= ((int64_t)1 << 30)); }
+// ---- the pinned descriptor staging: h_desc / h_seg, h_desc_reg / h_kf_of, h_desc_rt ------------------------------------------------
+// The host writes any of them only behind staging_wait; whoever enqueues a reader calls staging_mark_read behind it; nobody else touches the two flags.
+
+// Before the host writes the staging: the last copy out of it has run, and so has the last replayed graph, which re-reads it when it RUNS.
+static inline icet_status staging_wait(icet_ctx* c) {
+    if (c->desc_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_desc)); c->desc_in_flight = false; }
+    if (c->graph_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_graph)); c->graph_in_flight = false; }
+    return ICET_OK;
+}
+// The stream has been synchronised: nothing reads the staging.
+static inline void staging_idle(icet_ctx* c) { c->desc_in_flight = false; c->graph_in_flight = false; }
+// Behind the copy or kernel that reads the staging.  A captured event cannot be waited for on the host -- the replay path orders the staging itself (ev_graph) --,
+// so a capture records nothing; in_capture_too: the caller's path is one no graph replays, and it records whatever the flag says.
+static inline icet_status staging_mark_read(icet_ctx* c, bool in_capture_too = false) {
+    if (c->capturing && !in_capture_too) return ICET_OK;
+    if (!c->ev_desc) HIPCHK(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_desc, c->stream)); c->desc_in_flight = true;
+    return ICET_OK;
+}
+// Behind a replayed graph, which re-reads the staging when it runs (run_or_replay, which created ev_graph before its first capture).
+static inline icet_status staging_mark_replay(icet_ctx* c) { HIPCHK(c, hipEventRecord(c->ev_graph, c->stream)); c->graph_in_flight = true; return ICET_OK; }
+// n descriptors (hd) and seg_words segment words (hs) to wv.desc / wv.seg_off, one of three ways: the caller's next kernel copies the pinned words itself; a small
+// batch: k_upload_desc reads them (no copy command, no memcpy node); else two copies.  The caller marks the staging read behind whichever reads it.
+static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const PairDesc* hd, const int32_t* hs, int32_t n, size_t seg_words, bool by_next_kernel) {
+    if (by_next_kernel) return ICET_OK;
+    if (n <= kUploadDescMaxPairs) { HIPCHK(c, launch_upload_desc(wv, hd, hs, n, c->stream)); return ICET_OK; }
+    HIPCHK(c, hipMemcpyAsync(wv.desc, hd, sizeof(PairDesc) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(wv.seg_off, hs, sizeof(int32_t) * seg_words, hipMemcpyHostToDevice, c->stream));
+    return ICET_OK;
+}
+
+// ---- the entry step -------------------------------------------------------------------------------------------------------------------
+// An entry that enqueues on the context's stream begins with enter(): the context (or store) is there, its device is current, and the sync word is disarmed, so
+// that icet_sync behind it synchronises the stream.  The one arming entry, icet_solve_batch_device, begins with use_device() and counts armed_calls itself
+// (solve_device_part).  Every extern "C" function that takes a context or a store:
+//   disarms (enter)          icet_keyframe_device[_n], icet_register_device[_n], icet_register_indexed[_scored]_device, icet_score_indexed_device, icet_debug_point_sums_device,
+//                            icet_debug_gn_terms_device (register_indexed); icet_solve_indexed[_scored], icet_score_indexed, icet_solve_batch, icet_solve_begin / icet_solve
+//                            (all three also drain, or icet_solve_end does); icet_select_best_device; icet_keyframe_store_create (*), _put_device, _register[_scored]_device,
+//                            _score_device, _set_pose, _set_stamp, _candidates[_appearance]_device, _describe_device, _coarse_grid_device, _coarse_align_device,
+//                            _close[_appearance|_coarse]_device; icet_keyframe_store_save, _load (drain as well); icet_pose_graph_optimize[_device],
+//                            icet_debug_pose_graph_step, _direct (pg_run: drains as well)
+//   arms or disarms itself   icet_solve_batch_device
+//   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_block_tridiag (copy in, one kernel, copy out,
+//                            synchronise); icet_debug_fetch, icet_keyframe_store_debug_fetch, icet_keep_stats (synchronise, then blocking copies);
+//                            icet_last_timing[_iters] (synchronise); icet_solve_end; icet_keyframe_store_reserve, _enable_appearance, _enable_coarse, _destroy;
+//                            icet_destroy; icet_sync (the only one that re-arms: armed_calls = 0; icet_solve_indexed and its kin do the same behind their own drain)
+//   enqueues nothing         icet_reserve (allocations and blocking memsets; a growth synchronises first), icet_solve_keyframe_tables (waits for an event),
+//                            icet_set_option, icet_last_error, icet_stream, icet_device, icet_create (armed_calls starts at 2), icet_keyframe_store_last_error
+// (*) the one entry the audit found enqueuing (two memsets of the new tables) without draining or disarming.
+static inline icet_status use_device(icet_ctx* c) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return ICET_OK;
+}
+static inline icet_status enter(icet_ctx* c) {
+    const icet_status s = use_device(c);
+    if (s == ICET_OK) c->armed_calls = 2;
+    return s;
+}
+static inline icet_status enter(icet_keyframe_store* s) {
+    if (!s) return ICET_ERR_BAD_ARG;
+    const icet_status st = enter(s->ctx);
+    if (st != ICET_OK) s->err = s->ctx->err;
+    return st;
+}
 
 // What makes a keyframe: two calls with the same values here read and write the same tables.
 static inline bool same_keyframe_shape(const icet_params& a, const icet_params& b) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "icet_staging.h"
 
 struct icet_score;                         // include/icet_hip.h
 
@@ -41,13 +42,7 @@ constexpr uint32_t kSortedNearBit = 0x80000000u;   // the same flag in the sorte
 constexpr uint32_t kSortedZeroBit = 0x40000000u;   // kRowZeroBit in the sorted-row table
 constexpr uint32_t kSortedRowMask = ~(kSortedNearBit | kSortedZeroBit);
 
-// One scan pair as the kernels see it (device pointers, column-major N x 3).
-struct PairDesc {
-    const float* s1; const float* s2;
-    int32_t n1, ld1, n2, ld2;
-    int32_t off1;                    // start of this pair's segment in the scan-1 temporaries
-    int32_t off2;                    // start of this pair's segment in the scan-2 overflow list (near_over)
-};
+// One scan pair as the kernels see it (device pointers, column-major N x 3): PairDesc, icet_staging.h.
 
 // What the per-iteration point kernel needs about an active voxel (keyframe voxel with a scan-1
 // Gaussian, outer > 1 and |idx1| > n: the scan-1 side of the gate at src/icet.cpp:290).

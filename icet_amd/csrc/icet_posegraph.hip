@@ -145,7 +145,7 @@ icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, con
                    const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt, float* poses_out, double* poses64_out,
                    double* edge_chi2, icet_pose_graph_result* result, int32_t K = 0, const double* dbg_p = nullptr, icet_pose_graph_step* dbg = nullptr,
                    icet_pose_graph_direct_step* ddbg = nullptr) {
-    if (!c) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(c));
     const bool hook = dbg || ddbg;
     if (!poses || (!hook && (!poses_out || !result)) || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_optimize: bad argument"; return ICET_ERR_BAD_ARG; }
     if ((n > 1 && (!odo_X || !odo_info)) || (n_closures > 0 && (!ci || !cj || !clo_X || !clo_info))) { c->err = "icet_pose_graph_optimize: null array"; return ICET_ERR_BAD_ARG; }
@@ -163,8 +163,6 @@ icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, con
     }
     if (ddbg && ddbg->ends_capacity != m_ends) { c->err = "icet_debug_pose_graph_direct: ends_capacity is not the graph's count of end nodes (" + std::to_string(m_ends) + ")"; return ICET_ERR_BAD_ARG; }
     const bool direct = ddbg || (!dbg && (c->pg_solver == 1 || (c->pg_solver == 2 && m_ends >= 1 && m_ends <= kPgDirectMaxEnds)));
-    HIPCHK(c, hipSetDevice(c->device));
-    c->armed_calls = 2;
 
     PgArgs a{};
     PgDirect dir{};

@@ -93,7 +93,7 @@ icet_status icet_keyframe_store_create(icet_ctx* c, const icet_params* p, int32_
     if ((int64_t)p->bins_phi * p->bins_theta > kMaxVoxels) { c->err = "bins_phi*bins_theta exceeds the voxel limit (10000)"; return ICET_ERR_UNSUPPORTED; }
     const int V = p->bins_phi * p->bins_theta;
     if ((size_t)V * 12 + 8 + 4096 > (size_t)c->max_lds) { c->err = "grid too fine for this device's LDS (k_bin_scatter keeps 12 B per voxel in one block)"; return ICET_ERR_UNSUPPORTED; }
-    HIPCHK(c, hipSetDevice(c->device));
+    ICET_TRY(enter(c));                                      // (the memsets below are enqueued and not waited for)
     icet_keyframe_store* s = new (std::nothrow) icet_keyframe_store();
     if (!s) { c->err = "host allocation failed"; return ICET_ERR_NOMEM; }
     static std::atomic<int64_t> next_id{1};
@@ -178,7 +178,7 @@ static icet_status app_put_batch(icet_keyframe_store* s, const icet_dev_scan* sc
 static icet_status coarse_put_batch(icet_keyframe_store* s, const icet_dev_scan* scan, const int32_t* d_rows, int cnt, const StoreParkSlots& dst);
 
 icet_status icet_keyframe_store_put_device(icet_keyframe_store* s, int32_t n, const int32_t* slots, const icet_dev_scan* scan1, const int32_t* d_rows) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     icet_ctx* c = s->ctx;
     if (n < 0 || (n > 0 && (!slots || !scan1))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n == 0) return ICET_OK;
@@ -293,13 +293,12 @@ icet_status icet_keyframe_store_debug_fetch(icet_keyframe_store* s, int32_t slot
 void icet_pose_step_from_x(const float X[6], float T[16]) { if (X && T) icet_closure_rule::pose_step_from_X(X, T); }
 
 icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, const int32_t* slots, const float* poses, const int64_t* stamps) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     icet_ctx* c = s->ctx;
     if (n < 0 || (n > 0 && (!slots || !poses || !stamps))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n == 0) return ICET_OK;
     const icet_status ok = slots_ok(s, n, slots, true, "set_pose");
     if (ok != ICET_OK) return ok;
-    STORECHK(s, hipSetDevice(c->device));
     if (s->pose_in_flight) { STORECHK(s, hipEventSynchronize(s->ev_pose)); s->pose_in_flight = false; }      // the previous set_pose's kernel has read the staging
     if (n > s->cap_h_pose) {
         s->cap_h_pose = 0, s->pose_stage.release();
@@ -313,7 +312,6 @@ icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, cons
         u.slot = slots[k]; u.pad = 0; u.stamp = stamps[k];
         for (int a = 0; a < 3; a++) { u.tR[a] = T[4 * a + 3]; for (int b = 0; b < 3; b++) u.tR[3 + 3 * a + b] = T[4 * a + b]; }
     }
-    c->armed_calls = 2;
     STORECHK(s, launch_closure_set_pose(s->pose_table(), s->h_pose, n, c->stream));
     STORECHK(s, hipEventRecord(s->ev_pose, c->stream)); s->pose_in_flight = true;
     return ICET_OK;
@@ -396,16 +394,13 @@ static icet_status resolve_candidates(icet_keyframe_store* s, const float* poses
 
 icet_status icet_keyframe_store_candidates_device(icet_keyframe_store* s, int32_t n_queries, const float* poses, const int64_t* stamps,
                                                   const icet_closure_query* query, int32_t* d_cand, float* d_x0_base) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
+    ICET_TRY(enter(s));
     icet_status st = query_ok(s, true, n_queries, poses, stamps, query);
     if (st != ICET_OK) return st;
     if (!d_cand) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    STORECHK(s, hipSetDevice(c->device));
     const int K = query->max_candidates;
     st = closure_ensure(s, n_queries, K, 0);
     if (st != ICET_OK) return st;
-    c->armed_calls = 2;
     st = pose_search(s, n_queries, poses, stamps, query, d_cand);
     if (st == ICET_OK && d_x0_base) st = resolve_candidates(s, poses, n_queries, K, AppOffsets{}, 0, -1, d_cand, nullptr, nullptr, nullptr, d_x0_base, nullptr);
     return st;
@@ -469,14 +464,12 @@ icet_status icet_keyframe_store_enable_appearance(icet_keyframe_store* s, const 
 }
 
 icet_status icet_keyframe_store_describe_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows, uint8_t* d_desc, float* d_weight) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     icet_ctx* c = s->ctx;
     if (!s->app) { s->err = "appearance is not enabled on this store"; return ICET_ERR_BAD_ARG; }
     if (n < 0 || (n > 0 && (!scan || !d_desc || !d_weight))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (scans_ok(s, n, scan) != ICET_OK) return ICET_ERR_BAD_ARG;
     if (n == 0) return ICET_OK;
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
     const size_t A = (size_t)s->app->k.A, cells = A * (size_t)s->app->k.Rn;
     for (int first = 0; first < n; first += kAppBatch) {
         const int cnt = std::min(kAppBatch, n - first);
@@ -488,14 +481,12 @@ icet_status icet_keyframe_store_describe_device(icet_keyframe_store* s, int32_t 
 }
 
 icet_status icet_keyframe_store_set_stamp(icet_keyframe_store* s, int32_t n, const int32_t* slots, const int64_t* stamps) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     icet_ctx* c = s->ctx;
     if (n < 0 || (n > 0 && (!slots || !stamps))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (n == 0) return ICET_OK;
     const icet_status ok = slots_ok(s, n, slots, true, "set_stamp");
     if (ok != ICET_OK) return ok;
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
     for (int first = 0; first < n; first += kAppBatch) {
         const int cnt = std::min(kAppBatch, n - first);
         AppStamps st{};
@@ -533,18 +524,15 @@ static icet_status app_search(icet_keyframe_store* s, int32_t n_queries, const i
 
 icet_status icet_keyframe_store_candidates_appearance_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int64_t* stamps,
                                                              const icet_closure_query* query, int32_t* d_cand, float* d_dist, int32_t* d_shift, float* d_x0_base) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
+    ICET_TRY(enter(s));
     icet_status st = query_ok(s, false, n_queries, nullptr, stamps, query);
     if (st == ICET_OK) st = scans_ok(s, n_queries, scan2);
     if (st != ICET_OK) return st;
     if (!d_cand) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
-    STORECHK(s, hipSetDevice(c->device));
     const int K = query->max_candidates;
     st = closure_ensure(s, n_queries, K, 0);
     if (st == ICET_OK) st = app_ensure(s, n_queries);
     if (st != ICET_OK) return st;
-    c->armed_calls = 2;
     st = app_search(s, n_queries, scan2, stamps, query, d_cand);
     if (st == ICET_OK && (d_dist || d_shift || d_x0_base)) st = resolve_candidates(s, nullptr, n_queries, K, AppOffsets{}, 0, -1, d_cand, d_dist, d_shift, nullptr, d_x0_base, nullptr);
     return st;
@@ -609,14 +597,12 @@ icet_status icet_keyframe_store_enable_coarse(icet_keyframe_store* s, const icet
 }
 
 icet_status icet_keyframe_store_coarse_grid_device(icet_keyframe_store* s, int32_t n, const icet_dev_scan* scan, const int32_t* d_rows, uint32_t* d_grid) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     icet_ctx* c = s->ctx;
     if (!s->coarse) { s->err = "coarse alignment is not enabled on this store"; return ICET_ERR_BAD_ARG; }
     if (n < 0 || (n > 0 && (!scan || !d_grid))) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (scans_ok(s, n, scan) != ICET_OK) return ICET_ERR_BAD_ARG;
     if (n == 0) return ICET_OK;
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
     for (int first = 0; first < n; first += kCoarseBatch) {
         const int cnt = std::min(kCoarseBatch, n - first);
         AppScans sc; app_scans(scan + first, cnt, nullptr, sc);
@@ -659,16 +645,13 @@ static icet_status coarse_run(icet_keyframe_store* s, int32_t n_queries, const i
 icet_status icet_keyframe_store_coarse_align_device(icet_keyframe_store* s, int32_t n_queries, const icet_dev_scan* scan2, const int32_t* d_rows, int32_t K,
                                                     const int32_t* d_cand, const float* d_x0_base, const icet_coarse_search* search, float* d_x0_out,
                                                     icet_coarse_match* d_match) {
-    if (!s) return ICET_ERR_BAD_ARG;
-    icet_ctx* c = s->ctx;
+    ICET_TRY(enter(s));
     icet_status st = coarse_search_ok(s, search);
     if (st == ICET_OK) st = n_queries_ok(s, n_queries);
     if (st != ICET_OK) return st;
     if (K < 1 || K > kClosureMaxCandidates) { s->err = "K must be 1 .. " + std::to_string(kClosureMaxCandidates); return ICET_ERR_BAD_ARG; }
     if (!scan2 || !d_cand || !d_x0_base) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     if (scans_ok(s, n_queries, scan2) != ICET_OK) return ICET_ERR_BAD_ARG;
-    STORECHK(s, hipSetDevice(c->device));
-    c->armed_calls = 2;
     const AppOffsets off{};
     return coarse_run(s, n_queries, scan2, d_rows, K, search, off, 0, -1, d_cand, d_x0_base, d_x0_out, d_match, nullptr);
 }
@@ -690,7 +673,6 @@ static icet_status close_pipeline(icet_keyframe_store* s, const icet_params* p, 
     if (query->n_starts < 1 || query->n_starts > kClosureMaxStarts) { s->err = "n_starts must be 1 .. " + std::to_string(kClosureMaxStarts); return ICET_ERR_BAD_ARG; }
     if (!same_keyframe_shape(s->shape, *p)) { s->err = "the grid, n, thresh, buff or keyframe-shaping flags differ from the keyframe store's shape"; return ICET_ERR_BAD_ARG; }
     if (c->tune.keep != 0) { s->err = "indexed registrations run the plain point pass: option \"keep\" must be 0"; return ICET_ERR_UNSUPPORTED; }
-    STORECHK(s, hipSetDevice(c->device));
     const int K = query->max_candidates, S = query->n_starts, R = n_queries * K * S;
     st = closure_ensure(s, n_queries, K, R);
     if (st == ICET_OK && !by_pose) st = app_ensure(s, n_queries);
@@ -706,7 +688,6 @@ static icet_status close_pipeline(icet_keyframe_store* s, const icet_params* p, 
     icet_score* score = d_score ? d_score : s->q_score;
     icet_coarse_match* match = d_match || !search ? d_match : s->coarse->match;
     int32_t* shift_of = by_pose ? nullptr : s->app->shift_of;      // the candidates' shifts, for the record of a query by appearance
-    c->armed_calls = 2;
     // 1 search
     st = by_pose ? pose_search(s, n_queries, poses, stamps, query, cand) : app_search(s, n_queries, scan2, stamps, query, cand);
     if (st != ICET_OK) return st;
@@ -743,14 +724,14 @@ static icet_status close_pipeline(icet_keyframe_store* s, const icet_params* p, 
 icet_status icet_keyframe_store_close_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
                                              const float* poses, const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
                                              icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     return close_pipeline(s, p, n_queries, scan2, true, poses, stamps, query, nullptr, start_offsets, d_closure, d_cand, d_x0, d_out, d_score, nullptr);
 }
 
 icet_status icet_keyframe_store_close_appearance_device(icet_keyframe_store* s, const icet_params* p, int32_t n_queries, const icet_dev_scan* scan2,
                                                         const int64_t* stamps, const icet_closure_query* query, const float* start_offsets,
                                                         icet_closure* d_closure, int32_t* d_cand, float* d_x0, float* d_out, icet_score* d_score) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     return close_pipeline(s, p, n_queries, scan2, false, nullptr, stamps, query, nullptr, start_offsets, d_closure, d_cand, d_x0, d_out, d_score, nullptr);
 }
 
@@ -758,7 +739,7 @@ icet_status icet_keyframe_store_close_coarse_device(icet_keyframe_store* s, cons
                                                     const float* poses, const int64_t* stamps, const icet_closure_query* query,
                                                     const icet_coarse_search* search, const float* start_offsets, icet_closure* d_closure, int32_t* d_cand,
                                                     float* d_x0, float* d_out, icet_score* d_score, icet_coarse_match* d_match) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     if (!search) return coarse_search_ok(s, search);          // (refused: the coarse call needs its search)
     return close_pipeline(s, p, n_queries, scan2, poses != nullptr, poses, stamps, query, search, start_offsets, d_closure, d_cand, d_x0, d_out, d_score, d_match);
 }
@@ -839,7 +820,7 @@ static void snap_dev_entry(SnapEntry& d, const snap::Entry& e, int32_t slot, uin
 }
 
 icet_status icet_keyframe_store_save(icet_keyframe_store* s, const char* path, int32_t n, const int32_t* slots) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     icet_ctx* c = s->ctx;
     if (!path || (slots && n < 0)) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     // everything is checked before anything is touched
@@ -853,7 +834,6 @@ icet_status icet_keyframe_store_save(icet_keyframe_store* s, const char* path, i
         for (int32_t j = 0; j < s->capacity; j++) if (s->occupied[(size_t)j]) which.push_back(j);
     }
     if (c->tune.keep != 0) { s->err = "the store's calls run with option \"keep\" 0"; return ICET_ERR_UNSUPPORTED; }
-    STORECHK(s, hipSetDevice(c->device));
     STORECHK(s, hipStreamSynchronize(c->stream));              // behind whatever was enqueued: the puts and poses this save is to hold
     const size_t cap = (size_t)s->capacity, ne = which.size();
     std::vector<int32_t> ns(cap);
@@ -890,7 +870,6 @@ icet_status icet_keyframe_store_save(icet_keyframe_store* s, const char* path, i
     bool io_ok = true;
     if (he == hipSuccess && ne > 0) {
         for (size_t k = 0; k + 1 < cut.size(); k++) for (size_t i = cut[k]; i < cut[k + 1]; i++) snap_dev_entry(b.h_ent[i], ent[i], ent[i].slot, ent[i].off - ent[cut[k]].off);
-        c->armed_calls = 2;
         he = hipMemcpyAsync(b.d_ent, b.h_ent, sizeof(SnapEntry) * ne, hipMemcpyHostToDevice, c->stream);
         if (he == hipSuccess) he = hipMemsetAsync(b.d_sums, 0, sizeof(unsigned long long) * ne, c->stream);
         const SnapTables t = snap_tables(s, h.A(), h.Rp(), h.G());
@@ -926,7 +905,7 @@ icet_status icet_keyframe_store_save(icet_keyframe_store* s, const char* path, i
 }
 
 icet_status icet_keyframe_store_load(icet_keyframe_store* s, const char* path, int32_t slot_offset) {
-    if (!s) return ICET_ERR_BAD_ARG;
+    ICET_TRY(enter(s));
     icet_ctx* c = s->ctx;
     if (!path) { s->err = "bad argument"; return ICET_ERR_BAD_ARG; }
     // the file, read and validated on the host, then held against the store: everything is checked before anything is touched
@@ -948,14 +927,12 @@ icet_status icet_keyframe_store_load(icet_keyframe_store* s, const char* path, i
     if (c->tune.keep != 0) { s->err = "the store's calls run with option \"keep\" 0"; return ICET_ERR_UNSUPPORTED; }
     const size_t ne = ent.size();
     if (ne == 0) return ICET_OK;
-    STORECHK(s, hipSetDevice(c->device));
     const uint64_t budget = snap_budget(c, ent);
     const std::vector<size_t> cut = snap_chunks(ent, budget);
     SnapBuffers b;
     hipError_t he = snap_alloc(b, ne, (size_t)budget, false);
     if (he == hipSuccess) {
         for (size_t k = 0; k + 1 < cut.size(); k++) for (size_t i = cut[k]; i < cut[k + 1]; i++) snap_dev_entry(b.h_ent[i], ent[i], ent[i].slot + slot_offset, ent[i].off - ent[cut[k]].off);
-        c->armed_calls = 2;
         he = hipMemcpyAsync(b.d_ent, b.h_ent, sizeof(SnapEntry) * ne, hipMemcpyHostToDevice, c->stream);
         const SnapTables t = snap_tables(s, h.A(), h.Rp(), h.G());
         // chunk k: the file's bytes into pinned buffer k & 1 (once the copy of chunk k - 2 has left it) -> copy -> unpack

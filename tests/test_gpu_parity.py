@@ -994,6 +994,60 @@ def test_graph_replay_of_small_device_batches(gpu_ctx):
     eager.close(); g.close()
 
 
+def test_host_pointer_entries_between_queued_graph_replays(gpu_ctx):
+    """The host-pointer entries write the pinned descriptors that a replayed graph of a small device batch re-reads when it RUNS, and the device entry never
+    drains the stream: each of them waits for a replay in flight before it writes.  One context, graphs on, no sync until the end: three device solves of one
+    key (the third a replay, of another scan 2 of the same size), solve_batch on host scans of another size, a replay, solve (begin / end), solve_indexed
+    (two keyframes, three registrations), a last device solve, sync.  Every result, the outputs of the queued replays included -- each
+    read once a later host-pointer entry has drained the stream --, carries the bits a fresh context with option "graph" 0 gives for the same inputs.  (The test
+    cannot force the overwrite to happen: it pins that the mixed sequence is legal and exact.)"""
+    import icet_amd
+    from icet_amd import lidar_sim as ls, api
+    dev = torch.device("cuda", 0)
+    s1, s2, _ = ls.make_batch_pair(3, device=dev)
+    t2 = s2.clone(); t2[0] += 0.01
+    u1, u2, _ = ls.make_batch_pair(4, rings=32, steps=1024, device=dev)      # a pair of another size
+    d1 = [(s1.data_ptr(), s1.shape[1], s1.shape[1])]; d2 = [(s2.data_ptr(), s2.shape[1], s2.shape[1])]; e2 = [(t2.data_ptr(), t2.shape[1], t2.shape[1])]
+    S1, S2, T2, U1, U2 = (v.cpu().numpy().T for v in (s1, s2, t2, u1, u2))    # N x 3 views of the same floats for the host-pointer entries
+    assert U1.shape[0] != S1.shape[0]
+    rl = 2
+    prm = api.Params(rl, 24, 75, 25, 0.1, 0.1, 0)
+    x0 = torch.zeros((1, 6), dtype=torch.float32, device=dev)
+    o = torch.zeros((1, 48), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+
+    def host_batch(ctx): return ctx.solve_batch([U1], [U2], rl)
+    def host_one(ctx): return ctx.solve(S1, T2, rl, np.zeros(6), 24, 75)
+    def host_indexed(ctx): return ctx.solve_indexed([S1, U1], [S2, U2, T2], [0, 1, 0], rl)
+
+    def same(a, b): return all(np.array_equal(a[k], b[k]) for k in ("X", "pred_stds", "cov"))
+
+    eager = icet_amd.Context(0); eager.set_option("graph", 0)
+    eager.solve_batch_device(d1, d2, prm, o.data_ptr(), x0.data_ptr()); eager.sync(); ref_a = o.cpu().numpy().copy()
+    eager.solve_batch_device(d1, e2, prm, o.data_ptr(), x0.data_ptr()); eager.sync(); ref_b = o.cpu().numpy().copy()
+    ref_batch, ref_one, ref_idx = host_batch(eager), host_one(eager), host_indexed(eager)
+    eager.close()
+    assert not np.array_equal(ref_a, ref_b) and np.isfinite(ref_a).all() and np.isfinite(ref_idx["X"]).all()
+    o.zero_(); torch.cuda.synchronize()
+
+    g = icet_amd.Context(0)                                          # default: graph replay on
+    g.solve_batch_device(d1, d2, prm, o.data_ptr(), x0.data_ptr())   # eager
+    g.solve_batch_device(d1, d2, prm, o.data_ptr(), x0.data_ptr())   # the key repeats: captured, replayed
+    g.solve_batch_device(d1, e2, prm, o.data_ptr(), x0.data_ptr())   # replayed: reads its descriptors when it runs
+    got_batch = host_batch(g)                                        # writes h_desc[0]; drains the stream
+    got_b = o.cpu().numpy().copy()
+    g.solve_batch_device(d1, d2, prm, o.data_ptr(), x0.data_ptr())
+    got_one = host_one(g)
+    got_a = o.cpu().numpy().copy()
+    got_idx = host_indexed(g)
+    g.solve_batch_device(d1, e2, prm, o.data_ptr(), x0.data_ptr())
+    g.sync()
+    got_last = o.cpu().numpy().copy()
+    g.close()
+    assert np.array_equal(got_b, ref_b) and np.array_equal(got_a, ref_a) and np.array_equal(got_last, ref_b)
+    assert same(got_batch, ref_batch) and same(got_one, ref_one) and same(got_idx, ref_idx)
+
+
 def test_keyframe_and_register_halves_equal_the_whole_solve(gpu_ctx):
     """icet_keyframe_device + icet_register_device (the solve in two halves, for the sequential callers) give the bits of
     icet_solve_batch_device; a parked keyframe can be registered against more than once; a mismatched call is refused."""
