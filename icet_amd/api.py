@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
                     "icet_keyframe_store_close_coarse_device",
                     "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_debug_pose_graph_step", "icet_debug_pose_graph_direct",
+                    "icet_pose_graph_marginals", "icet_pose_graph_marginals_device", "icet_debug_pose_graph_marginals",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -150,7 +151,19 @@ class PoseGraphDirectStep(C.Structure):
                [(k, C.c_double) for k in ("chi2_start", "chi2_trial", "max_dx")]
 
 
+class PoseGraphMarginalsResult(C.Structure):
+    """icet_pose_graph_marginals_result (include/icet_hip.h), 24 bytes."""
+    _fields_ = [(k, C.c_int32) for k in ("status", "m", "factor_status", "wm_status", "ks_status", "reserved")]
+
+
+class PoseGraphMarginalsDebug(C.Structure):
+    """icet_pose_graph_marginals_debug (include/icet_hip.h), 80 bytes."""
+    ARRAYS = ("D", "B", "A", "band_cov", "cov")
+    _fields_ = [(k, C.c_void_p) for k in ARRAYS] + [("ends", C.c_void_p), ("ends_capacity", C.c_int32), ("reserved", C.c_int32), ("result", PoseGraphMarginalsResult)]
+
+
 assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40 and C.sizeof(PoseGraphStep) == 152 and C.sizeof(PoseGraphDirectStep) == 176
+assert C.sizeof(PoseGraphMarginalsResult) == 24 and C.sizeof(PoseGraphMarginalsDebug) == 80
 # option "pg_solver": the pose-graph optimiser's linear solve
 PG_SOLVER_CG, PG_SOLVER_DIRECT, PG_SOLVER_AUTO = range(3)
 PG_SOLVERS = {"cg": PG_SOLVER_CG, "direct": PG_SOLVER_DIRECT, "auto": PG_SOLVER_AUTO}
@@ -173,6 +186,21 @@ def pose_graph_ends(n, closures, fixed=None):
 PG_CG_TOLERANCE, PG_CG_ZERO, PG_CG_CAP, PG_CG_FAILED = range(4)
 # icet_pose_graph_result.status
 POSE_GRAPH_CONVERGED, POSE_GRAPH_ITERATION_CAP, POSE_GRAPH_NOT_POSITIVE_DEFINITE, POSE_GRAPH_NON_FINITE, POSE_GRAPH_STALLED = range(5)
+
+
+def pose_stds(cov):
+    """n x 6: the standard deviations of every pose from its marginal covariance ``cov`` (n x 6 x 6, Context.pose_graph_marginals): metres along the node's own
+    axes, then radians of the rotation vector."""
+    c = np.asarray(cov, np.float64).reshape(-1, 6, 6)
+    return np.sqrt(np.einsum("kaa->ka", c))
+
+
+def position_cov_world(poses, cov):
+    """n x 3 x 3: the translation block of every pose's marginal covariance in the MAP frame, R_k Sigma_rho,rho R_k^T (the tangent of the right update moves a
+    pose's position by R_k rho)."""
+    R = np.asarray(poses, np.float64).reshape(-1, 4, 4)[:, :3, :3]
+    c = np.asarray(cov, np.float64).reshape(-1, 6, 6)[:, :3, :3]
+    return R @ c @ R.transpose(0, 2, 1)
 
 
 def info_from_cov(cov):
@@ -310,6 +338,11 @@ def load_library():
     L.icet_pose_graph_optimize_device.argtypes = L.icet_pose_graph_optimize.argtypes
     L.icet_debug_pose_graph_direct.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(PoseGraphOptions), C.c_int32, C.c_void_p, C.POINTER(PoseGraphDirectStep)]
+    L.icet_pose_graph_marginals.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(PoseGraphMarginalsResult)]
+    L.icet_pose_graph_marginals_device.argtypes = L.icet_pose_graph_marginals.argtypes
+    L.icet_debug_pose_graph_marginals.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(PoseGraphMarginalsDebug)]
     L.icet_debug_pose_graph_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(PoseGraphOptions), C.c_int32, C.c_void_p, C.POINTER(PoseGraphStep)]
     L.icet_keyframe_store_enable_appearance.argtypes = [C.c_void_p, C.POINTER(AppearanceParams)]
@@ -663,13 +696,16 @@ class Context:
         return dict(chi2_initial=float(res.chi2_initial), chi2_final=float(res.chi2_final), status=int(res.status), gn_iterations=int(res.gn_iterations),
                     max_dx=float(res.max_dx), pcg_iterations=int(res.pcg_iterations), solver=int(res.solver))
 
-    def optimize_pose_graph(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0, solver=None):
+    def optimize_pose_graph(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0, solver=None,
+                            covariances=False):
         """icet_pose_graph_optimize: the poses (n x 4 x 4 float32) of a chain with odometry measurements ``odo_X`` ((n - 1) x 6) and information ``odo_info``
         ((n - 1) x 6 x 6) and the closure edges ``closures`` = (i, j, X, info) tuples as closure_edges returns them, optimised on the device.  Node 0 and the
         nodes with ``fixed[k] != 0`` stay.  Returns dict(poses n x 4 x 4 float32, poses64 n x 4 x 4, chi2_initial, chi2_final, status (POSE_GRAPH_*),
         gn_iterations, max_dx, edge_chi2 2 x E, pcg_iterations, solver).  A status of 2 or 3 is a result, not an error: the poses are then the inputs.
         ``solver``: None (the context's option "pg_solver"), "cg", "direct" or "auto" for this call; the result's ``solver`` is 1 when the direct solve ran --
-        it ignores max_pcg and pcg_tol, and converges at the defaults where the closures' information is strong (closures from find_closures: use "auto")."""
+        it ignores max_pcg and pcg_tol, and converges at the defaults where the closures' information is strong (closures from find_closures: use "auto").
+        ``covariances``: True adds ``cov`` (n x 6 x 6) and ``cov_status``, pose_graph_marginals at the returned float32 poses."""
+        closures = list(closures)
         P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
         oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
         if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
@@ -682,7 +718,78 @@ class Context:
                                                                 cX.ctypes.data, cI.ctypes.data, _data(fx), C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data,
                                                                 C.byref(res)))
         T64 = np.zeros((n, 4, 4)); T64[:, 3, 3] = 1.0; T64[:, :3, :3] = p64[:, :9].reshape(n, 3, 3); T64[:, :3, 3] = p64[:, 9:]
-        return dict(self._pose_graph_result(res), poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
+        r = dict(self._pose_graph_result(res), poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
+        if covariances:
+            mg = self.pose_graph_marginals(r["poses"], odo_X, odo_info, closures, fixed=fixed)
+            r["cov"] = mg["cov"]; r["cov_status"] = mg["status"]
+        return r
+
+    def _pose_graph_marginals_result(self, res):
+        return {k: int(getattr(res, k)) for k in ("status", "m", "factor_status", "wm_status", "ks_status")}
+
+    def pose_graph_marginals(self, poses, odo_X, odo_info, closures=(), fixed=None):
+        """icet_pose_graph_marginals: how well each pose of the graph is known.  The graph as optimize_pose_graph takes it, ``poses`` the poses to evaluate at
+        (what the optimiser returned).  Returns dict(cov n x 6 x 6 float64, status, m, factor_status, wm_status, ks_status): block (k, k) of the inverse of the
+        Gauss-Newton H at these poses, in the tangent of the right update T Exp(delta), delta = (translation in the node's own frame, rotation vector); a fixed
+        node's block is zero.  pose_stds and position_cov_world read it.  A status of 2 (H is not positive definite) or 3 (not finite) is a result: every free
+        node's block is then NaN.  More than 128 end nodes of closures off the band: IcetError(ICET_ERR_UNSUPPORTED)."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
+        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
+        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        ci, cj, cX, cI, fx, _ = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, 0.0, 0, 0.0)
+        cov = np.zeros((n, 6, 6), np.float64); res = PoseGraphMarginalsResult()
+        self._check(load_library().icet_pose_graph_marginals(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data,
+                                                             cX.ctypes.data, cI.ctypes.data, _data(fx), cov.ctypes.data, C.byref(res)))
+        return dict(self._pose_graph_marginals_result(res), cov=cov)
+
+    def pose_graph_marginals_device(self, poses, odo_X, odo_info, closures=(), fixed=None, clo_X=None, clo_info=None):
+        """icet_pose_graph_marginals_device for torch tensors on this context's device, with the conventions of optimize_pose_graph_device.  Returns the dict of
+        pose_graph_marginals with ``cov`` (n x 6 x 6 float64) as a tensor on the device.  The call returns when the result is known."""
+        import torch
+        for t in (poses, odo_X, odo_info):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise IcetError(ICET_ERR_BAD_ARG, "poses, odo_X and odo_info must be contiguous float32 tensors on the device")
+        n = poses.numel() // 16
+        if n < 1 or poses.numel() != n * 16 or odo_X.numel() != (n - 1) * 6 or odo_info.numel() != (n - 1) * 36:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        closures = list(closures)
+        if clo_X is None:
+            ci, cj, cX, cI, fx, _ = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, 0.0, 0, 0.0)
+            clo_X = torch.from_numpy(cX).to(poses.device); clo_info = torch.from_numpy(cI).to(poses.device)
+        else:
+            ci, cj, _, _, fx, _ = self._pose_graph_host_args(n, [(c[0], c[1], np.zeros(6), np.zeros(36)) for c in closures], fixed, 1, 0.0, 0.0, 0, 0.0)
+            for t in (clo_X, clo_info):
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must be contiguous float32 tensors on the device")
+            if clo_X.numel() != ci.shape[0] * 6 or clo_info.numel() != ci.shape[0] * 36:
+                raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must hold one row per closure")
+        cov = torch.zeros((n, 6, 6), dtype=torch.float64, device=poses.device); res = PoseGraphMarginalsResult()
+        torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
+        self._check(load_library().icet_pose_graph_marginals_device(self._h, n, _vp(poses.data_ptr()), _vp(odo_X.data_ptr()), _vp(odo_info.data_ptr()), ci.shape[0],
+                                                                    ci.ctypes.data, cj.ctypes.data, _vp(clo_X.data_ptr()), _vp(clo_info.data_ptr()), _data(fx),
+                                                                    _vp(cov.data_ptr()), C.byref(res)))
+        return dict(self._pose_graph_marginals_result(res), cov=cov)
+
+    def debug_pose_graph_marginals(self, poses, odo_X, odo_info, closures=(), fixed=None):
+        """icet_debug_pose_graph_marginals: pose_graph_marginals with its intermediate arrays.  Returns its dict with ends (m int32), D, B n x 6 x 6, A C x 6 x 6
+        and band_cov n x 6 x 6 (the diagonal blocks of the band's inverse; NaN where the band did not factor)."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
+        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
+        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        closures = list(closures)
+        ci, cj, cX, cI, fx, _ = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, 0.0, 0, 0.0)
+        nc = ci.shape[0]; m = len(pose_graph_ends(n, closures, fixed))
+        arr = dict(D=np.full((n, 6, 6), np.nan), B=np.full((n, 6, 6), np.nan), A=np.full((nc, 6, 6), np.nan), band_cov=np.full((n, 6, 6), np.nan), cov=np.full((n, 6, 6), np.nan))
+        ends = np.full(m, -1, np.int32)
+        st = PoseGraphMarginalsDebug()
+        for k in PoseGraphMarginalsDebug.ARRAYS:
+            setattr(st, k, arr[k].ctypes.data)
+        st.ends = ends.ctypes.data; st.ends_capacity = m
+        self._check(load_library().icet_debug_pose_graph_marginals(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, nc, ci.ctypes.data, cj.ctypes.data, cX.ctypes.data,
+                                                                   cI.ctypes.data, _data(fx), C.byref(st)))
+        return dict(self._pose_graph_marginals_result(st.result), ends=ends, **arr)
 
     def debug_pose_graph_step(self, poses, odo_X, odo_info, closures=(), fixed=None, damping=0.0, max_pcg=0, pcg_tol=0.0, p=None):
         """icet_debug_pose_graph_step: the optimiser's first iteration on the device with its intermediate arrays, and q = H p for every vector of ``p``

@@ -6,7 +6,8 @@
 // sequential in the node index: one thread walks it, out of chunks of 32 nodes that all threads stage through LDS).  Around it: small kernels that each do one
 // thing on plain global arrays, every body in icet_posegraph_body.h, driven from the host by icet_posegraph_driver.h.  No kernel waits on another block.
 // Option "pg_solver" replaces the conjugate gradients by a direct solve over the closures' end nodes (icet_posegraph_direct.h): k_pg_z solves the band for
-// all their unit columns in one launch, one thread per column.
+// all their unit columns in one launch, one thread per column.  icet_pose_graph_marginals[_device] reads the marginal covariance of every pose off that solve's
+// Z, L and Lk and a selected inverse of the band (icet_posegraph_marginals.h).
 #include "icet_ctx.h"
 #include "icet_posegraph_driver.h"
 
@@ -59,6 +60,18 @@ ICET_PG_GRID_KERNEL(k_pg_resid, pg_resid)
 __global__ __launch_bounds__(kPgThreads) void k_pg_chol(PgArgs a, PgDirect d, int which) { pg_group_chol(a, d, which); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_band(PgArgs a, PgDirect d) { __shared__ PgShared sh; pg_group_band(a, d, sh); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_cap_solve(PgArgs a, PgDirect d) { pg_group_cap_solve(a, d); }
+
+// the marginal covariances (icet_posegraph_marginals.h).  k_pg_selinv is the sequential part; k_pg_marg runs one workgroup per node.
+__global__ __launch_bounds__(kPgGridThreads) void k_pg_selinv_prep(PgArgs a, PgMarg mg, int count) {
+    const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x);
+    if (gi < count) pg_selinv_prep(a, mg, gi);
+}
+__global__ __launch_bounds__(kPgGridThreads) void k_pg_marg_lt(PgArgs a, PgDirect d, PgMarg mg, int count) {
+    const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x);
+    if (gi < count) pg_marg_lt(a, d, mg, gi);
+}
+__global__ __launch_bounds__(kPgThreads) void k_pg_selinv(PgArgs a, PgMarg mg) { __shared__ PgShared sh; pg_group_selinv(a, mg, sh); }
+__global__ __launch_bounds__(kPgThreads) void k_pg_marg(PgArgs a, PgDirect d, PgMarg mg) { __shared__ PgMargShared sh; pg_group_marg(a, d, mg, (int)blockIdx.x, sh); }
 
 namespace {
 
@@ -113,6 +126,24 @@ struct PgDeviceBackend {
             case kPgCholK:    hipLaunchKernelGGL(k_pg_chol, g, b, 0, stream, a, d, 1); break;
             case kPgBand:     hipLaunchKernelGGL(k_pg_band, g, b, 0, stream, a, d); break;
             case kPgCapSolve: hipLaunchKernelGGL(k_pg_cap_solve, g, b, 0, stream, a, d); break;
+        }
+        return ok(hipGetLastError());
+    }
+    bool mgrid(PgMargGridKernel k, int count, const PgArgs& a, const PgDirect& d, const PgMarg& mg) {
+        if (count <= 0) return true;
+        const dim3 g((unsigned)((count + kPgGridThreads - 1) / kPgGridThreads)), b(kPgGridThreads);
+        switch (k) {
+            case kPgSelinvPrep: hipLaunchKernelGGL(k_pg_selinv_prep, g, b, 0, stream, a, mg, count); break;
+            case kPgMargLt:     hipLaunchKernelGGL(k_pg_marg_lt, g, b, 0, stream, a, d, mg, count); break;
+        }
+        return ok(hipGetLastError());
+    }
+    bool mgroups(PgMargGroupKernel k, int groups, const PgArgs& a, const PgDirect& d, const PgMarg& mg) {
+        if (groups <= 0) return true;
+        const dim3 b(kPgThreads);
+        switch (k) {
+            case kPgSelinv:   hipLaunchKernelGGL(k_pg_selinv, dim3(1), b, 0, stream, a, mg); break;
+            case kPgMargNode: hipLaunchKernelGGL(k_pg_marg, dim3((unsigned)groups), b, 0, stream, a, d, mg); break;
         }
         return ok(hipGetLastError());
     }
@@ -232,10 +263,112 @@ icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, con
     return ICET_OK;
 }
 
+// The marginal covariances of a graph (icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals): pg_run's checks, block and staging, pg_marginals in
+// the place of the optimiser.
+icet_status pg_marg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                        const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, double* cov_out, icet_pose_graph_marginals_result* result,
+                        icet_pose_graph_marginals_debug* dbg = nullptr) {
+    ICET_TRY(enter(c));
+    if (!poses || (!dbg && (!cov_out || !result)) || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_marginals: bad argument"; return ICET_ERR_BAD_ARG; }
+    if ((n > 1 && (!odo_X || !odo_info)) || (n_closures > 0 && (!ci || !cj || !clo_X || !clo_info))) { c->err = "icet_pose_graph_marginals: null array"; return ICET_ERR_BAD_ARG; }
+    if (!pg::closures_ok(n, n_closures, ci, cj)) { c->err = "icet_pose_graph_marginals: a closure's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
+    PgGraph graph;
+    graph.build(n, n_closures, ci, cj, fixed);
+    const int m_ends = (int)graph.ends.size();
+    if (m_ends > kPgDirectMaxEnds) {
+        c->err = "icet_pose_graph_marginals: at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " + std::to_string(m_ends);
+        return ICET_ERR_UNSUPPORTED;
+    }
+    if (dbg && dbg->ends_capacity != m_ends) { c->err = "icet_debug_pose_graph_marginals: ends_capacity is not the graph's count of end nodes (" + std::to_string(m_ends) + ")"; return ICET_ERR_BAD_ARG; }
+
+    PgArgs a{};
+    PgDirect dir{};
+    PgMarg mg{};
+    a.N = n; a.C = n_closures; a.E = pg::edge_count(n, n_closures);
+    const size_t N = (size_t)n, E = (size_t)a.E, C = (size_t)n_closures, n_items = graph.items.size();
+    PgArena arena;
+    PgGraphDev gd{};
+    PgDirectDev dd{};
+    PgHostIo io;
+    auto layout = [&]() {
+        arena.used = 0;
+        gd = pg_bind(a, arena, n_items);
+        arena.used = (arena.used + 7) & ~(size_t)7;
+        dd = pg_bind_direct(a, dir, arena, (size_t)m_ends);
+        arena.used = (arena.used + 7) & ~(size_t)7;
+        pg_bind_marg(a, dir, mg, arena, host_io);
+        if (host_io) { io.poses = arena.f(N * 16); io.odo_X = arena.f((N - 1) * 6); io.odo_info = arena.f((N - 1) * 36); io.clo_X = arena.f(C * 6); io.clo_info = arena.f(C * 36); }
+    };
+    layout();
+    const size_t bytes = arena.used;
+    char* block = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&block), bytes));
+    arena.base = block;
+    layout();
+
+    PgDeviceBackend be;
+    be.stream = c->stream;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&be.h_sc), sizeof(double) * kPgScalars, hipHostMallocDefault);
+    auto up = [&](void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, c->stream); };
+    up(gd.ei, graph.ei.data(), sizeof(int32_t) * E); up(gd.ej, graph.ej.data(), sizeof(int32_t) * E);
+    up(gd.off, graph.off.data(), sizeof(int32_t) * (N + 1)); up(gd.items, graph.items.data(), sizeof(int32_t) * n_items);
+    up(dd.ends, graph.ends.data(), sizeof(int32_t) * (size_t)m_ends); up(dd.end_of, graph.end_of.data(), sizeof(int32_t) * N);
+    if (host_io) {
+        up(io.poses, poses, sizeof(float) * N * 16); up(io.odo_X, odo_X, sizeof(float) * (N - 1) * 6); up(io.odo_info, odo_info, sizeof(float) * (N - 1) * 36);
+        up(io.clo_X, clo_X, sizeof(float) * C * 6); up(io.clo_info, clo_info, sizeof(float) * C * 36);
+        a.poses_in = io.poses; a.odo_X = io.odo_X; a.odo_info = io.odo_info; a.clo_X = io.clo_X; a.clo_info = io.clo_info;
+    } else {
+        a.poses_in = poses; a.odo_X = odo_X; a.odo_info = odo_info; a.clo_X = clo_X; a.clo_info = clo_info;
+        mg.cov = cov_out;
+    }
+    a.poses_out = nullptr; a.poses64_out = nullptr; a.edge_chi2_out = nullptr;          // (kPgFinish does not run)
+    icet_pose_graph_marginals_result res{};
+    bool done = false;
+    if (e == hipSuccess) {
+        PgMargTap tap;
+        if (dbg) { tap.D = dbg->D; tap.B = dbg->B; tap.A = dbg->A; tap.band_cov = dbg->band_cov; }
+        done = pg_marginals(be, a, dir, mg, &res, dbg ? &tap : nullptr);
+        if (!done) e = be.err;
+    }
+    double* host_cov = dbg ? dbg->cov : cov_out;
+    if (done && host_io && host_cov && e == hipSuccess) e = hipMemcpyAsync(host_cov, mg.cov, sizeof(double) * N * 36, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(block);
+    if (be.h_sc) (void)hipHostFree(be.h_sc);
+    if (e != hipSuccess) { c->err = std::string("icet_pose_graph_marginals: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    if (dbg) {
+        dbg->result = res;
+        if (dbg->ends) for (int i = 0; i < m_ends; i++) dbg->ends[i] = graph.ends[(size_t)i];
+    }
+    if (result) *result = res;
+    return ICET_OK;
+}
+
 }  // namespace
 }  // namespace icet
 
 using namespace icet;
+
+icet_status icet_pose_graph_marginals(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                      const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, double* cov_out,
+                                      icet_pose_graph_marginals_result* result) {
+    return pg_marg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, cov_out, result);
+}
+
+icet_status icet_pose_graph_marginals_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                             const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, double* cov_out,
+                                             icet_pose_graph_marginals_result* result) {
+    return pg_marg_run(c, false, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, cov_out, result);
+}
+
+// Test hook: the marginals on host arrays with D, B, A, the band's selected inverse and the end nodes copied out.
+icet_status icet_debug_pose_graph_marginals(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                            const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, icet_pose_graph_marginals_debug* out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!out || out->ends_capacity < 0 || out->reserved != 0) { c->err = "icet_debug_pose_graph_marginals: bad argument"; return ICET_ERR_BAD_ARG; }
+    return pg_marg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, nullptr, nullptr, out);
+}
 
 icet_status icet_pose_graph_optimize(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
                                      const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,

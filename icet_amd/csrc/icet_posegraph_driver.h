@@ -6,12 +6,17 @@
 //     bool scalars(const PgArgs&, double out[kPgScalars])    wait for what was enqueued, then a.sc on the host
 //     bool fetch(void* host, const void* dev, size_t bytes), put(void* dev, const void* host, size_t bytes)      (the test hook only) copies, complete on return
 //     bool dgrid(PgDirectGridKernel, int count, const PgArgs&, const PgDirect&), dgroup(PgDirectGroupKernel, const PgArgs&, const PgDirect&)
-//                                                            the direct solve's bodies (icet_posegraph_direct.h); only pg_direct_solve calls them
+//                                                            the direct solve's bodies (icet_posegraph_direct.h); only pg_direct_solve and pg_marginals call them
+//     bool mgrid(PgMargGridKernel, int count, const PgArgs&, const PgDirect&, const PgMarg&)
+//     bool mgroups(PgMargGroupKernel, int groups, const PgArgs&, const PgDirect&, const PgMarg&)
+//                                                            the marginals' bodies (icet_posegraph_marginals.h); mgroups runs a group body once per group index
+//                                                            below `groups` (one workgroup each; the host loops over them); only pg_marginals calls them
 // each false for a failure of the backend (the driver then returns false at once).  icet_posegraph.hip has the device's backend,
 // tests/cpp/test_posegraph_optimize.cpp and tests/cpp/test_posegraph_direct.cpp the host's.
 #pragma once
 #include "icet_posegraph_body.h"
 #include "icet_posegraph_direct.h"
+#include "icet_posegraph_marginals.h"
 
 #include <cmath>
 #include <vector>
@@ -218,6 +223,50 @@ inline bool pg_optimise_direct(Backend& be, PgArgs a, PgDirect d, const icet_pos
         if (!*bad) *pcg += solves;          // (behind a failed factorisation the solves were launched but did nothing)
         return true;
     }, 1, res);
+}
+
+// ---- the marginal covariances (icet_posegraph_marginals.h) ---------------------------------------------------------------------------------------------------
+// Their work arrays beside pg_bind's and pg_bind_direct's in the same block, doubles only.  own_cov: the result is staged in the block (the host-pointer form
+// and the hook); otherwise the caller points mg.cov at its own N x 36 doubles.
+template <class Alloc>
+inline void pg_bind_marg(const PgArgs& a, const PgDirect& d, PgMarg& mg, Alloc& al, bool own_cov) {
+    const size_t N = (size_t)a.N, q = (size_t)d.nq;
+    mg.Y = al.d(N * 36); mg.band_cov = al.d(N * 36);
+    mg.Lt = al.d(q * q); mg.Lkt = al.d(q * q);
+    mg.cov = own_cov ? al.d(N * 36) : nullptr;
+}
+
+// What the test hook copies out of a marginals run (null: nothing)
+struct PgMargTap { double *D = nullptr, *B = nullptr, *A = nullptr, *band_cov = nullptr; };
+
+// The marginal covariances of the poses the caller passed: one linearisation with no damping, the band's factor, with end nodes the direct solve's Z, L and Lk
+// (its bodies, unchanged), then the selected inverse of the band and the closures' correction per node.  A fixed number of launches whatever the graph is,
+// nothing read back but the scalars at the end.  kPgChi runs only so that the gradient kPgAssemble writes beside D is defined; the result does not depend on
+// the measurements.  res->status: 0, or the first failed factorisation's status (kNotPositiveDefinite, kNonFinite) -- every free node's block is then NaN.
+// assembled (the host test only, to run the device's own blocks): D, B, A, a zero g and zero scalars are in place, the run starts at the band's factor.
+template <class Backend>
+inline bool pg_marginals(Backend& be, PgArgs a, PgDirect d, PgMarg mg, icet_pose_graph_marginals_result* res, const PgMargTap* tap = nullptr, bool assembled = false) {
+    double h[kPgScalars];
+    const int N = a.N, E = a.E, C = a.C, q = d.nq;
+    const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
+    a.damping = 0.0; a.trial = 0; a.first = 0; a.failed = 0;
+    if (!assembled && (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) ||
+                       !be.grid(kPgOffband, C * 36, a))) return false;
+    if (!be.group(kPgFactor, a)) return false;
+    if (q > 0 && (!be.dgrid(kPgZ, q, a, d) || !be.dgrid(kPgWm, q * q, a, d) || !be.dgroup(kPgCholW, a, d) || !be.dgrid(kPgSl, q * q, a, d) || !be.dgrid(kPgKs, q * q, a, d) ||
+                  !be.dgroup(kPgCholK, a, d) || !be.mgrid(kPgMargLt, q * q, a, d, mg))) return false;
+    if (!be.mgrid(kPgSelinvPrep, N, a, d, mg) || !be.mgroups(kPgSelinv, 1, a, d, mg) || !be.mgroups(kPgMargNode, N, a, d, mg) || !be.scalars(a, h)) return false;
+    int st[3];
+    res->status = pg_direct_status(h, st);
+    res->m = q / 6; res->factor_status = st[0]; res->wm_status = st[1]; res->ks_status = st[2]; res->reserved = 0;
+    if (tap) {
+        const size_t sd = sizeof(double);
+        auto get = [&](double* dst, const double* src, size_t count) { return !dst || count == 0 || be.fetch(dst, src, count * sd); };
+        // (band_cov is written only behind a band that factored)
+        if (!get(tap->D, a.D, (size_t)N * 36) || !get(tap->B, a.B, (size_t)N * 36) || !get(tap->A, a.A, (size_t)C * 36) ||
+            (st[0] == 0 && !get(tap->band_cov, mg.band_cov, (size_t)N * 36))) return false;
+    }
+    return true;
 }
 
 // The direct solve's test hook (icet_debug_pose_graph_direct; the host test runs it too): the optimiser's FIRST iteration with the direct solve, kernel for

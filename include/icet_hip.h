@@ -683,6 +683,44 @@ typedef struct icet_pose_graph_direct_step {
 icet_status icet_debug_pose_graph_direct(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
                                          const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
                                          const icet_pose_graph_options* opt, int32_t K, const double* p, icet_pose_graph_direct_step* out);
+/* MARGINAL COVARIANCES: how well each pose of a graph is known.  The graph arguments of icet_pose_graph_optimize (n through fixed) and its argument checks;
+ * `poses` are the poses to evaluate at -- what the optimiser returned.  cov_out: n x 36 doubles, block (k, k) of H^-1 per node, H = sum J^T Omega J linearised
+ * at `poses` with no damping, in the optimiser's tangent: delta = (translation, rotation vector) of the right update T Exp(delta), so rows and columns 0 .. 2
+ * are metres in the node's OWN frame and 3 .. 5 radians.  Every block is symmetric bit for bit; a fixed node's block is zero.  The measurements (odo_X, clo_X)
+ * are taken for symmetry of the call and do not enter the result.  H^-1 = M^-1 - P P^T + Q Q^T with the direct solve's Z, L, Lk (P = Z L^-T, Q = P Lk^-T) and
+ * the diagonal blocks of M^-1 by the backward recurrence over the band's factor: a fixed number of launches.  The graph may have at most 128 end nodes (above:
+ * ICET_ERR_UNSUPPORTED whatever option "pg_solver" says, nothing allocated, the outputs untouched).
+ * result->status: 0, or ICET_POSE_GRAPH_NOT_POSITIVE_DEFINITE (a pivot of the band, of Wm or of Ks at or below 1e-13 of its diagonal entry) or _NON_FINITE (a
+ * pivot that is not finite: a pose or an information that is not); factor_status, wm_status, ks_status say which.  Every free node's block is then quiet NaN
+ * and every fixed node's zero.  The status is a RESULT: the call returns ICET_OK.
+ * The first form takes HOST arrays; in the _device form poses, odo_X, odo_info, clo_X, clo_info and cov_out are DEVICE pointers (cov_out 8-byte aligned); ci, cj,
+ * fixed and result stay on the host.  Both synchronise.  The context's parked keyframe and workspace are not touched.  ICET_ERR_BAD_ARG: as
+ * icet_pose_graph_optimize, with cov_out and result in the place of poses_out and result. */
+typedef struct icet_pose_graph_marginals_result {
+    int32_t status;               /* 0, ICET_POSE_GRAPH_NOT_POSITIVE_DEFINITE or ICET_POSE_GRAPH_NON_FINITE */
+    int32_t m;                    /* end nodes */
+    int32_t factor_status, wm_status, ks_status;
+    int32_t reserved;             /* zero */
+} icet_pose_graph_marginals_result;   /* 24 bytes */
+icet_status icet_pose_graph_marginals(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                      const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                      double* cov_out, icet_pose_graph_marginals_result* result);
+icet_status icet_pose_graph_marginals_device(icet_ctx* ctx, int32_t n, const float* d_poses, const float* d_odo_X, const float* d_odo_info, int32_t n_closures,
+                                             const int32_t* ci, const int32_t* cj, const float* d_clo_X, const float* d_clo_info, const uint8_t* fixed,
+                                             double* d_cov_out, icet_pose_graph_marginals_result* result);
+/* Test hook: icet_pose_graph_marginals on HOST arrays with its intermediate arrays copied out.  HOST arrays the caller sizes, or NULL: D, B n x 36 | A
+ * n_closures x 36 | band_cov n x 36 (the diagonal blocks of M^-1, the identity at a fixed node; left alone where the band did not factor) | cov n x 36 | ends m
+ * int32.  ends_capacity (in) as in icet_pose_graph_direct_step; reserved zero. */
+typedef struct icet_pose_graph_marginals_debug {
+    double *D, *B, *A, *band_cov, *cov;
+    int32_t* ends;
+    int32_t ends_capacity;        /* in */
+    int32_t reserved;             /* zero */
+    icet_pose_graph_marginals_result result;
+} icet_pose_graph_marginals_debug;    /* 80 bytes */
+icet_status icet_debug_pose_graph_marginals(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                            const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                            icet_pose_graph_marginals_debug* out);
 /* The optimiser's solver alone, as a test hook.  The odometry chain of a pose graph makes its normal equations block tridiagonal (6 x 6 blocks).
  * ONE symmetric positive definite block-tridiagonal system through the block Cholesky factorisation and the two sweeps, in double, one workgroup.
  * HOST arrays of doubles: diag n x 36, sub n x 36 (sub[k]: the block at (k, k - 1); sub[0] zero), rhs and x n x 6; *status 0, or ICET_BAND_NOT_POSITIVE_DEFINITE

@@ -6,8 +6,9 @@
 Each directory holds the objects of one build (icet_amd/lib/obj, or `make OUT=...`'s obj/).  For every object present in both, the
 gfx950 code object is taken out of the .hip_fatbin section, disassembled with llvm-objdump and cut into functions; addresses and
 encodings are dropped and the pc-relative targets of calls (s_getpc_b64 + s_add_u32 / s_addc_u32) are replaced by the callee's name,
-so that code which merely moved compares equal.  The kernels' resource metadata (registers, LDS, scratch, kernel-argument size) is
-compared too.  Functions found in only one build are listed (new kernels are expected there); exit status 1 when a function present
+so that code which merely moved compares equal; the s_nop padding behind a function's last instruction is dropped too (the last
+function of a section is padded to the section's end, and stops being the last when kernels are added behind it).  The kernels'
+resource metadata (registers, LDS, scratch, kernel-argument size) is compared too.  Functions found in only one build are listed (new kernels are expected there); exit status 1 when a function present
 in both differs.  Runs on any machine with ROCm's LLVM tools: no GPU needed.
 """
 import os
@@ -81,6 +82,9 @@ def functions(co):
         body.append(ins)
     if cur:
         funcs[cur] = body
+    for body in funcs.values():                      # the s_nop padding behind a function's last instruction (the section's last function carries the most)
+        while body and body[-1] == "s_nop 0":
+            body.pop()
     return funcs
 
 
