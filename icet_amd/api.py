@@ -11,6 +11,7 @@ There is no CPU fallback: if the HIP library is missing or no GPU is usable this
 import contextlib
 import ctypes as C
 import os
+import types
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -677,19 +678,58 @@ class Context:
         self._check(load_library().icet_debug_block_tridiag(self._h, n, D.ctypes.data, B.ctypes.data, r.ctypes.data, x.ctypes.data, C.byref(st)))
         return x, int(st.value)
 
+    # ---- the pose graph: every call marshals its graph ONCE, through _pose_graph_host (host arrays) or _pose_graph_device (tensors) -----------------------------
     @staticmethod
-    def _pose_graph_host_args(n, closures, fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol):
-        """The host-side arguments both optimiser calls share: ci, cj, the closures' X and info (float32), fixed (uint8 or None), the options."""
+    def _pose_graph_lists(n, closures, fixed, measurements=True):
+        """ci, cj (int32), the closures' X and info (float32; None without ``measurements``: the caller has them as tensors) and fixed (uint8 or None)."""
         closures = list(closures)
         ci = np.ascontiguousarray([int(c[0]) for c in closures], np.int32); cj = np.ascontiguousarray([int(c[1]) for c in closures], np.int32)
-        cX = np.ascontiguousarray([np.asarray(c[2], np.float32).reshape(6) for c in closures], np.float32).reshape(-1, 6)
-        cI = np.ascontiguousarray([np.asarray(c[3], np.float32).reshape(36) for c in closures], np.float32).reshape(-1, 36)
+        cX = cI = None
+        if measurements:
+            cX = np.ascontiguousarray([np.asarray(c[2], np.float32).reshape(6) for c in closures], np.float32).reshape(-1, 6)
+            cI = np.ascontiguousarray([np.asarray(c[3], np.float32).reshape(36) for c in closures], np.float32).reshape(-1, 36)
         fx = None
         if fixed is not None:
             fx = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, np.uint8)
             if fx.shape[0] != n:
                 raise IcetError(ICET_ERR_BAD_ARG, "fixed must hold one entry per pose")
-        return ci, cj, cX, cI, fx, PoseGraphOptions(int(gn_iters), int(max_pcg), float(dx_tol), float(damping), float(pcg_tol))
+        return ci, cj, cX, cI, fx
+
+    def _pose_graph_args(self, n, poses, odo_X, odo_info, ci, cj, clo_X, clo_info, fx, ptr):
+        """What a call site needs of a marshalled graph: ``n``, ``nc`` (the closure count) and ``args``, the eleven leading arguments of every
+        icet_pose_graph_* entry, to splat.  ``keep`` holds the arrays behind those addresses: the caller keeps the object while the C call runs."""
+        nc = ci.shape[0]
+        return types.SimpleNamespace(n=n, nc=nc, keep=(poses, odo_X, odo_info, ci, cj, clo_X, clo_info, fx),
+                                     args=(self._h, n, ptr(poses), ptr(odo_X), ptr(odo_info), nc, ci.ctypes.data, cj.ctypes.data, ptr(clo_X), ptr(clo_info), _data(fx)))
+
+    def _pose_graph_host(self, poses, odo_X, odo_info, closures, fixed):
+        """The graph of the five host-pointer calls (see _pose_graph_args): float32 rows, one of odo_X and odo_info per pose but the first."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
+        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
+        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        return self._pose_graph_args(n, P, oX, oI, *self._pose_graph_lists(n, closures, fixed), lambda a: a.ctypes.data)
+
+    def _pose_graph_device(self, poses, odo_X, odo_info, closures, fixed, clo_X, clo_info):
+        """The graph of the two _device calls (see _pose_graph_args): contiguous float32 tensors on the device; the closures' X and info are uploaded from
+        ``closures``, or are the tensors ``clo_X`` and ``clo_info``."""
+        import torch
+        for t in (poses, odo_X, odo_info):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise IcetError(ICET_ERR_BAD_ARG, "poses, odo_X and odo_info must be contiguous float32 tensors on the device")
+        n = poses.numel() // 16
+        if n < 1 or poses.numel() != n * 16 or odo_X.numel() != (n - 1) * 6 or odo_info.numel() != (n - 1) * 36:
+            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
+        ci, cj, cX, cI, fx = self._pose_graph_lists(n, closures, fixed, measurements=clo_X is None)
+        if clo_X is None:
+            clo_X = torch.from_numpy(cX).to(poses.device); clo_info = torch.from_numpy(cI).to(poses.device)
+        else:
+            for t in (clo_X, clo_info):
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must be contiguous float32 tensors on the device")
+            if clo_X.numel() != ci.shape[0] * 6 or clo_info.numel() != ci.shape[0] * 36:
+                raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must hold one row per closure")
+        return self._pose_graph_args(n, poses, odo_X, odo_info, ci, cj, clo_X, clo_info, fx, lambda t: _vp(t.data_ptr()))
 
     @staticmethod
     def _pose_graph_result(res):
@@ -706,17 +746,11 @@ class Context:
         it ignores max_pcg and pcg_tol, and converges at the defaults where the closures' information is strong (closures from find_closures: use "auto").
         ``covariances``: True adds ``cov`` (n x 6 x 6) and ``cov_status``, pose_graph_marginals at the returned float32 poses."""
         closures = list(closures)
-        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
-        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
-        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
-            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
-        ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol)
-        E = n - 1 + ci.shape[0]
-        out = np.zeros((n, 16), np.float32); p64 = np.zeros((n, 12), np.float64); chi = np.zeros((2, E), np.float64); res = PoseGraphResult()
+        g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed); n = g.n
+        opt = PoseGraphOptions(int(gn_iters), int(max_pcg), float(dx_tol), float(damping), float(pcg_tol))
+        out = np.zeros((n, 16), np.float32); p64 = np.zeros((n, 12), np.float64); chi = np.zeros((2, n - 1 + g.nc), np.float64); res = PoseGraphResult()
         with self._pose_graph_solver(solver):
-            self._check(load_library().icet_pose_graph_optimize(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data,
-                                                                cX.ctypes.data, cI.ctypes.data, _data(fx), C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data,
-                                                                C.byref(res)))
+            self._check(load_library().icet_pose_graph_optimize(*g.args, C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data, C.byref(res)))
         T64 = np.zeros((n, 4, 4)); T64[:, 3, 3] = 1.0; T64[:, :3, :3] = p64[:, :9].reshape(n, 3, 3); T64[:, :3, 3] = p64[:, 9:]
         r = dict(self._pose_graph_result(res), poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
         if covariances:
@@ -733,74 +767,42 @@ class Context:
         Gauss-Newton H at these poses, in the tangent of the right update T Exp(delta), delta = (translation in the node's own frame, rotation vector); a fixed
         node's block is zero.  pose_stds and position_cov_world read it.  A status of 2 (H is not positive definite) or 3 (not finite) is a result: every free
         node's block is then NaN.  More than 128 end nodes of closures off the band: IcetError(ICET_ERR_UNSUPPORTED)."""
-        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
-        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
-        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
-            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
-        ci, cj, cX, cI, fx, _ = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, 0.0, 0, 0.0)
-        cov = np.zeros((n, 6, 6), np.float64); res = PoseGraphMarginalsResult()
-        self._check(load_library().icet_pose_graph_marginals(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data,
-                                                             cX.ctypes.data, cI.ctypes.data, _data(fx), cov.ctypes.data, C.byref(res)))
+        g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed)
+        cov = np.zeros((g.n, 6, 6), np.float64); res = PoseGraphMarginalsResult()
+        self._check(load_library().icet_pose_graph_marginals(*g.args, cov.ctypes.data, C.byref(res)))
         return dict(self._pose_graph_marginals_result(res), cov=cov)
 
     def pose_graph_marginals_device(self, poses, odo_X, odo_info, closures=(), fixed=None, clo_X=None, clo_info=None):
         """icet_pose_graph_marginals_device for torch tensors on this context's device, with the conventions of optimize_pose_graph_device.  Returns the dict of
         pose_graph_marginals with ``cov`` (n x 6 x 6 float64) as a tensor on the device.  The call returns when the result is known."""
         import torch
-        for t in (poses, odo_X, odo_info):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise IcetError(ICET_ERR_BAD_ARG, "poses, odo_X and odo_info must be contiguous float32 tensors on the device")
-        n = poses.numel() // 16
-        if n < 1 or poses.numel() != n * 16 or odo_X.numel() != (n - 1) * 6 or odo_info.numel() != (n - 1) * 36:
-            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
-        closures = list(closures)
-        if clo_X is None:
-            ci, cj, cX, cI, fx, _ = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, 0.0, 0, 0.0)
-            clo_X = torch.from_numpy(cX).to(poses.device); clo_info = torch.from_numpy(cI).to(poses.device)
-        else:
-            ci, cj, _, _, fx, _ = self._pose_graph_host_args(n, [(c[0], c[1], np.zeros(6), np.zeros(36)) for c in closures], fixed, 1, 0.0, 0.0, 0, 0.0)
-            for t in (clo_X, clo_info):
-                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                    raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must be contiguous float32 tensors on the device")
-            if clo_X.numel() != ci.shape[0] * 6 or clo_info.numel() != ci.shape[0] * 36:
-                raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must hold one row per closure")
-        cov = torch.zeros((n, 6, 6), dtype=torch.float64, device=poses.device); res = PoseGraphMarginalsResult()
+        g = self._pose_graph_device(poses, odo_X, odo_info, closures, fixed, clo_X, clo_info)
+        cov = torch.zeros((g.n, 6, 6), dtype=torch.float64, device=poses.device); res = PoseGraphMarginalsResult()
         torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
-        self._check(load_library().icet_pose_graph_marginals_device(self._h, n, _vp(poses.data_ptr()), _vp(odo_X.data_ptr()), _vp(odo_info.data_ptr()), ci.shape[0],
-                                                                    ci.ctypes.data, cj.ctypes.data, _vp(clo_X.data_ptr()), _vp(clo_info.data_ptr()), _data(fx),
-                                                                    _vp(cov.data_ptr()), C.byref(res)))
+        self._check(load_library().icet_pose_graph_marginals_device(*g.args, _vp(cov.data_ptr()), C.byref(res)))
         return dict(self._pose_graph_marginals_result(res), cov=cov)
 
     def debug_pose_graph_marginals(self, poses, odo_X, odo_info, closures=(), fixed=None):
         """icet_debug_pose_graph_marginals: pose_graph_marginals with its intermediate arrays.  Returns its dict with ends (m int32), D, B n x 6 x 6, A C x 6 x 6
         and band_cov n x 6 x 6 (the diagonal blocks of the band's inverse; NaN where the band did not factor)."""
-        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
-        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
-        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
-            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
         closures = list(closures)
-        ci, cj, cX, cI, fx, _ = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, 0.0, 0, 0.0)
-        nc = ci.shape[0]; m = len(pose_graph_ends(n, closures, fixed))
+        g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed); n, nc = g.n, g.nc
+        m = len(pose_graph_ends(n, closures, fixed))
         arr = dict(D=np.full((n, 6, 6), np.nan), B=np.full((n, 6, 6), np.nan), A=np.full((nc, 6, 6), np.nan), band_cov=np.full((n, 6, 6), np.nan), cov=np.full((n, 6, 6), np.nan))
         ends = np.full(m, -1, np.int32)
         st = PoseGraphMarginalsDebug()
         for k in PoseGraphMarginalsDebug.ARRAYS:
             setattr(st, k, arr[k].ctypes.data)
         st.ends = ends.ctypes.data; st.ends_capacity = m
-        self._check(load_library().icet_debug_pose_graph_marginals(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, nc, ci.ctypes.data, cj.ctypes.data, cX.ctypes.data,
-                                                                   cI.ctypes.data, _data(fx), C.byref(st)))
+        self._check(load_library().icet_debug_pose_graph_marginals(*g.args, C.byref(st)))
         return dict(self._pose_graph_marginals_result(st.result), ends=ends, **arr)
 
     def debug_pose_graph_step(self, poses, odo_X, odo_info, closures=(), fixed=None, damping=0.0, max_pcg=0, pcg_tol=0.0, p=None):
         """icet_debug_pose_graph_step: the optimiser's first iteration on the device with its intermediate arrays, and q = H p for every vector of ``p``
         (K x n x 6 doubles).  Returns a dict of the arrays of icet_pose_graph_step (J E x 6 x 12, res E x 6, chi_start, chi_trial, D, B n x 6 x 6, A C x 6 x 6,
         g, x n x 6, Pt n x 12, q K x n x 6, cg_scalars band_solves x 2) and its scalars."""
-        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
-        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
-        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
-            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
-        ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, damping, max_pcg, pcg_tol)
-        nc = ci.shape[0]; E = n - 1 + nc
+        g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed); n, nc = g.n, g.nc; E = n - 1 + nc
+        opt = PoseGraphOptions(1, int(max_pcg), 0.0, float(damping), float(pcg_tol))
         pv = np.zeros((0, n, 6)) if p is None else np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, n, 6))
         cap = int(max_pcg) if max_pcg > 0 else 12 * nc + 8
         arr = dict(J=np.zeros((E, 6, 12)), res=np.zeros((E, 6)), chi_start=np.zeros(E), chi_trial=np.zeros(E), D=np.zeros((n, 6, 6)), B=np.zeros((n, 6, 6)),
@@ -809,8 +811,7 @@ class Context:
         for k in PoseGraphStep.ARRAYS:
             setattr(st, k, arr[k].ctypes.data)
         st.cg_capacity = cap
-        self._check(load_library().icet_debug_pose_graph_step(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, nc, ci.ctypes.data, cj.ctypes.data, cX.ctypes.data,
-                                                              cI.ctypes.data, _data(fx), C.byref(opt), pv.shape[0], pv.ctypes.data, C.byref(st)))
+        self._check(load_library().icet_debug_pose_graph_step(*g.args, C.byref(opt), pv.shape[0], pv.ctypes.data, C.byref(st)))
         out = {k: int(getattr(st, k)) for k in ("factor_status", "cg_status", "band_solves", "cg_end", "cap", "c_offband", "trial")}
         out.update({k: float(getattr(st, k)) for k in ("chi2_start", "chi2_trial", "max_dx")})
         arr["cg_scalars"] = arr["cg_scalars"][:min(out["band_solves"], cap)]
@@ -820,13 +821,9 @@ class Context:
         """icet_debug_pose_graph_direct: the optimiser's first iteration with the DIRECT solve on the device, its intermediate arrays copied out, and q = H p
         for every vector of ``p``.  Returns a dict: ends (m int32), D, B n x 6 x 6, A C x 6 x 6, g, x0, x n x 6, Z 6n x q, Wm, L, Ks, Lk q x q (q = 6 m), Pt
         n x 12, chi_trial, q K x n x 6, and the scalars of icet_pose_graph_direct_step."""
-        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16)); n = P.shape[0]
-        oX = np.ascontiguousarray(np.asarray(odo_X, np.float32).reshape(-1, 6)); oI = np.ascontiguousarray(np.asarray(odo_info, np.float32).reshape(-1, 36))
-        if n < 1 or oX.shape[0] != n - 1 or oI.shape[0] != n - 1:
-            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
         closures = list(closures)
-        ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, 1, 0.0, damping, 0, 0.0)
-        nc = ci.shape[0]; E = n - 1 + nc
+        g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed); n, nc = g.n, g.nc; E = n - 1 + nc
+        opt = PoseGraphOptions(1, 0, 0.0, float(damping), 0.0)
         m = len(pose_graph_ends(n, closures, fixed)); q = 6 * m
         pv = np.zeros((0, n, 6)) if p is None else np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, n, 6))
         nan = lambda *shape: np.full(shape, np.nan)      # noqa: E731
@@ -837,8 +834,7 @@ class Context:
         for k in PoseGraphDirectStep.ARRAYS:
             setattr(st, k, arr[k].ctypes.data)
         st.ends = ends.ctypes.data; st.ends_capacity = m
-        self._check(load_library().icet_debug_pose_graph_direct(self._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, nc, ci.ctypes.data, cj.ctypes.data, cX.ctypes.data,
-                                                                cI.ctypes.data, _data(fx), C.byref(opt), pv.shape[0], pv.ctypes.data, C.byref(st)))
+        self._check(load_library().icet_debug_pose_graph_direct(*g.args, C.byref(opt), pv.shape[0], pv.ctypes.data, C.byref(st)))
         out = {k: int(getattr(st, k)) for k in ("m", "factor_status", "wm_status", "ks_status", "band_solves", "trial")}
         out.update({k: float(getattr(st, k)) for k in ("chi2_start", "chi2_trial", "max_dx")})
         return dict(out, ends=ends, **arr)
@@ -850,31 +846,13 @@ class Context:
         C x 6 x 6 as float32 tensors.  Returns the dict of optimize_pose_graph with poses (float32), poses64 (n x 12 float64: R row-major, then t) and edge_chi2
         (2 x E float64) as tensors on the device.  ``solver`` as in optimize_pose_graph.  The call returns when the result is known."""
         import torch
-        for t in (poses, odo_X, odo_info):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise IcetError(ICET_ERR_BAD_ARG, "poses, odo_X and odo_info must be contiguous float32 tensors on the device")
-        n = poses.numel() // 16
-        if n < 1 or poses.numel() != n * 16 or odo_X.numel() != (n - 1) * 6 or odo_info.numel() != (n - 1) * 36:
-            raise IcetError(ICET_ERR_BAD_ARG, "odo_X and odo_info must hold one row per pose but the first")
-        closures = list(closures)
-        if clo_X is None:
-            ci, cj, cX, cI, fx, opt = self._pose_graph_host_args(n, closures, fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol)
-            clo_X = torch.from_numpy(cX).to(poses.device); clo_info = torch.from_numpy(cI).to(poses.device)
-        else:
-            ci, cj, _, _, fx, opt = self._pose_graph_host_args(n, [(c[0], c[1], np.zeros(6), np.zeros(36)) for c in closures], fixed, gn_iters, dx_tol, damping, max_pcg, pcg_tol)
-            for t in (clo_X, clo_info):
-                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                    raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must be contiguous float32 tensors on the device")
-            if clo_X.numel() != ci.shape[0] * 6 or clo_info.numel() != ci.shape[0] * 36:
-                raise IcetError(ICET_ERR_BAD_ARG, "clo_X and clo_info must hold one row per closure")
-        E = n - 1 + ci.shape[0]
+        g = self._pose_graph_device(poses, odo_X, odo_info, closures, fixed, clo_X, clo_info); n = g.n
+        opt = PoseGraphOptions(int(gn_iters), int(max_pcg), float(dx_tol), float(damping), float(pcg_tol))
         out = torch.zeros((n, 4, 4), dtype=torch.float32, device=poses.device); p64 = torch.zeros((n, 12), dtype=torch.float64, device=poses.device)
-        chi = torch.zeros((2, E), dtype=torch.float64, device=poses.device); res = PoseGraphResult()
+        chi = torch.zeros((2, n - 1 + g.nc), dtype=torch.float64, device=poses.device); res = PoseGraphResult()
         torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
         with self._pose_graph_solver(solver):
-            self._check(load_library().icet_pose_graph_optimize_device(self._h, n, _vp(poses.data_ptr()), _vp(odo_X.data_ptr()), _vp(odo_info.data_ptr()), ci.shape[0],
-                                                                       ci.ctypes.data, cj.ctypes.data, _vp(clo_X.data_ptr()), _vp(clo_info.data_ptr()), _data(fx), C.byref(opt),
-                                                                       _vp(out.data_ptr()), _vp(p64.data_ptr()), _vp(chi.data_ptr()), C.byref(res)))
+            self._check(load_library().icet_pose_graph_optimize_device(*g.args, C.byref(opt), _vp(out.data_ptr()), _vp(p64.data_ptr()), _vp(chi.data_ptr()), C.byref(res)))
         return dict(self._pose_graph_result(res), poses=out, poses64=p64, edge_chi2=chi)
 
     def debug_fix(self, values):

@@ -206,8 +206,7 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            (all three also drain, or icet_solve_end does); icet_select_best_device; icet_keyframe_store_create (*), _put_device, _register[_scored]_device,
 //                            _score_device, _set_pose, _set_stamp, _candidates[_appearance]_device, _describe_device, _coarse_grid_device, _coarse_align_device,
 //                            _close[_appearance|_coarse]_device; icet_keyframe_store_save, _load (drain as well); icet_pose_graph_optimize[_device],
-//                            icet_debug_pose_graph_step, _direct (pg_run: drains as well);
-//                            icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals (pg_marg_run: drains as well)
+//                            icet_debug_pose_graph_step, _direct, icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals (pg_run: drains as well)
 //   arms or disarms itself   icet_solve_batch_device
 //   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_block_tridiag (copy in, one kernel, copy out,
 //                            synchronise); icet_debug_fetch, icet_keyframe_store_debug_fetch, icet_keep_stats (synchronise, then blocking copies);

@@ -21,21 +21,31 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_block_tridiag(int N, const do
     pg_block_tridiag(N, Dm, Bm, rhs, x, G, W, u, status, sh);
 }
 
-// grid kernels: one thread per global index below `count`
+// grid kernels: one thread per global index below `count`, which follows the body's own arguments
 constexpr int kPgGridThreads = 256;
-#define ICET_PG_GRID_KERNEL(name, body) \
-    __global__ __launch_bounds__(kPgGridThreads) void name(PgArgs a, int count) { \
+#define ICET_PG_GRID_KERNEL(name, call, ...) \
+    __global__ __launch_bounds__(kPgGridThreads) void name(__VA_ARGS__, int count) { \
         const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x); \
-        if (gi < count) body(a, gi); \
+        if (gi < count) call; \
     }
-ICET_PG_GRID_KERNEL(k_pg_init, pg_init)
-ICET_PG_GRID_KERNEL(k_pg_chi, pg_chi)
-ICET_PG_GRID_KERNEL(k_pg_linearise, pg_linearise)
-ICET_PG_GRID_KERNEL(k_pg_assemble, pg_assemble)
-ICET_PG_GRID_KERNEL(k_pg_offband, pg_offband)
-ICET_PG_GRID_KERNEL(k_pg_hp, pg_hp)
-ICET_PG_GRID_KERNEL(k_pg_retract, pg_retract)
-ICET_PG_GRID_KERNEL(k_pg_finish, pg_finish)
+ICET_PG_GRID_KERNEL(k_pg_init, pg_init(a, gi), PgArgs a)
+ICET_PG_GRID_KERNEL(k_pg_chi, pg_chi(a, gi), PgArgs a)
+ICET_PG_GRID_KERNEL(k_pg_linearise, pg_linearise(a, gi), PgArgs a)
+ICET_PG_GRID_KERNEL(k_pg_assemble, pg_assemble(a, gi), PgArgs a)
+ICET_PG_GRID_KERNEL(k_pg_offband, pg_offband(a, gi), PgArgs a)
+ICET_PG_GRID_KERNEL(k_pg_hp, pg_hp(a, gi), PgArgs a)
+ICET_PG_GRID_KERNEL(k_pg_retract, pg_retract(a, gi), PgArgs a)
+ICET_PG_GRID_KERNEL(k_pg_finish, pg_finish(a, gi), PgArgs a)
+// the direct solve (icet_posegraph_direct.h).  k_pg_z is the kernel that matters: one thread per column of Z walks the chain forward and back.
+ICET_PG_GRID_KERNEL(k_pg_z, pg_z(a, d, gi), PgArgs a, PgDirect d)
+ICET_PG_GRID_KERNEL(k_pg_wm, pg_wm(a, d, gi), PgArgs a, PgDirect d)
+ICET_PG_GRID_KERNEL(k_pg_sl, pg_sl(a, d, gi), PgArgs a, PgDirect d)
+ICET_PG_GRID_KERNEL(k_pg_ks, pg_ks(a, d, gi), PgArgs a, PgDirect d)
+ICET_PG_GRID_KERNEL(k_pg_zw, pg_zw(a, d, gi), PgArgs a, PgDirect d)
+ICET_PG_GRID_KERNEL(k_pg_resid, pg_resid(a, d, gi), PgArgs a, PgDirect d)
+// the marginal covariances (icet_posegraph_marginals.h)
+ICET_PG_GRID_KERNEL(k_pg_selinv_prep, pg_selinv_prep(a, mg, gi), PgArgs a, PgMarg mg)
+ICET_PG_GRID_KERNEL(k_pg_marg_lt, pg_marg_lt(a, d, mg, gi), PgArgs a, PgDirect d, PgMarg mg)
 #undef ICET_PG_GRID_KERNEL
 
 // one-workgroup kernels
@@ -43,109 +53,87 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_factor(PgArgs a) { __shared__
 __global__ __launch_bounds__(kPgThreads) void k_pg_precond(PgArgs a) { __shared__ PgShared sh; __shared__ PgRed red; pg_group_precond(a, sh, red); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_step(PgArgs a) { __shared__ PgRed red; pg_group_step(a, red); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_stats(PgArgs a) { __shared__ PgRed red; pg_group_stats(a, red); }
-
-// the direct solve (icet_posegraph_direct.h).  k_pg_z is the kernel that matters: one thread per column of Z walks the chain forward and back.
-#define ICET_PG_GRID_KERNEL(name, body) \
-    __global__ __launch_bounds__(kPgGridThreads) void name(PgArgs a, PgDirect d, int count) { \
-        const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x); \
-        if (gi < count) body(a, d, gi); \
-    }
-ICET_PG_GRID_KERNEL(k_pg_z, pg_z)
-ICET_PG_GRID_KERNEL(k_pg_wm, pg_wm)
-ICET_PG_GRID_KERNEL(k_pg_sl, pg_sl)
-ICET_PG_GRID_KERNEL(k_pg_ks, pg_ks)
-ICET_PG_GRID_KERNEL(k_pg_zw, pg_zw)
-ICET_PG_GRID_KERNEL(k_pg_resid, pg_resid)
-#undef ICET_PG_GRID_KERNEL
 __global__ __launch_bounds__(kPgThreads) void k_pg_chol(PgArgs a, PgDirect d, int which) { pg_group_chol(a, d, which); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_band(PgArgs a, PgDirect d) { __shared__ PgShared sh; pg_group_band(a, d, sh); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_cap_solve(PgArgs a, PgDirect d) { pg_group_cap_solve(a, d); }
-
-// the marginal covariances (icet_posegraph_marginals.h).  k_pg_selinv is the sequential part; k_pg_marg runs one workgroup per node.
-__global__ __launch_bounds__(kPgGridThreads) void k_pg_selinv_prep(PgArgs a, PgMarg mg, int count) {
-    const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x);
-    if (gi < count) pg_selinv_prep(a, mg, gi);
-}
-__global__ __launch_bounds__(kPgGridThreads) void k_pg_marg_lt(PgArgs a, PgDirect d, PgMarg mg, int count) {
-    const int gi = (int)(blockIdx.x * kPgGridThreads + threadIdx.x);
-    if (gi < count) pg_marg_lt(a, d, mg, gi);
-}
+// k_pg_selinv is the marginals' sequential part; k_pg_marg runs one workgroup per node
 __global__ __launch_bounds__(kPgThreads) void k_pg_selinv(PgArgs a, PgMarg mg) { __shared__ PgShared sh; pg_group_selinv(a, mg, sh); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_marg(PgArgs a, PgDirect d, PgMarg mg) { __shared__ PgMargShared sh; pg_group_marg(a, d, mg, (int)blockIdx.x, sh); }
 
 namespace {
 
-// The device's backend of pg_optimise: launches on the context's stream; the scalars come back through pinned memory.
+// The device's backend of the driver: launches on the context's stream; the scalars come back through pinned memory.
 struct PgDeviceBackend {
     hipStream_t stream = nullptr;
     double* h_sc = nullptr;                 // pinned, kPgScalars
     hipError_t err = hipSuccess;
     bool ok(hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; return e == hipSuccess; }
-    bool grid(PgGridKernel k, int count, const PgArgs& a) {
-        if (count <= 0) return true;
-        const dim3 g((unsigned)((count + kPgGridThreads - 1) / kPgGridThreads)), b(kPgGridThreads);
-        switch (k) {
-            case kPgInit:      hipLaunchKernelGGL(k_pg_init, g, b, 0, stream, a, count); break;
-            case kPgChi:       hipLaunchKernelGGL(k_pg_chi, g, b, 0, stream, a, count); break;
-            case kPgLinearise: hipLaunchKernelGGL(k_pg_linearise, g, b, 0, stream, a, count); break;
-            case kPgAssemble:  hipLaunchKernelGGL(k_pg_assemble, g, b, 0, stream, a, count); break;
-            case kPgOffband:   hipLaunchKernelGGL(k_pg_offband, g, b, 0, stream, a, count); break;
-            case kPgHp:        hipLaunchKernelGGL(k_pg_hp, g, b, 0, stream, a, count); break;
-            case kPgRetract:   hipLaunchKernelGGL(k_pg_retract, g, b, 0, stream, a, count); break;
-            case kPgFinish:    hipLaunchKernelGGL(k_pg_finish, g, b, 0, stream, a, count); break;
-        }
+    // THE launch rule: `blocks` workgroups of `threads` on the stream, nothing for blocks <= 0 (a count or a number of groups that is not positive)
+    template <class... Params, class... Args>
+    bool launch(void (*kernel)(Params...), int blocks, int threads, const Args&... args) {
+        if (blocks <= 0) return true;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)threads), 0, stream, args...);
         return ok(hipGetLastError());
+    }
+    static int blocks_for(int count) { return count <= 0 ? 0 : (count + kPgGridThreads - 1) / kPgGridThreads; }
+    bool grid(PgGridKernel k, int count, const PgArgs& a) {
+        void (*f)(PgArgs, int) = nullptr;
+        switch (k) {
+            case kPgInit:      f = k_pg_init; break;
+            case kPgChi:       f = k_pg_chi; break;
+            case kPgLinearise: f = k_pg_linearise; break;
+            case kPgAssemble:  f = k_pg_assemble; break;
+            case kPgOffband:   f = k_pg_offband; break;
+            case kPgHp:        f = k_pg_hp; break;
+            case kPgRetract:   f = k_pg_retract; break;
+            case kPgFinish:    f = k_pg_finish; break;
+        }
+        return launch(f, blocks_for(count), kPgGridThreads, a, count);
     }
     bool group(PgGroupKernel k, const PgArgs& a) {
-        const dim3 g(1), b(kPgThreads);
+        void (*f)(PgArgs) = nullptr;
         switch (k) {
-            case kPgFactor:  hipLaunchKernelGGL(k_pg_factor, g, b, 0, stream, a); break;
-            case kPgPrecond: hipLaunchKernelGGL(k_pg_precond, g, b, 0, stream, a); break;
-            case kPgStep:    hipLaunchKernelGGL(k_pg_step, g, b, 0, stream, a); break;
-            case kPgStats:   hipLaunchKernelGGL(k_pg_stats, g, b, 0, stream, a); break;
+            case kPgFactor:  f = k_pg_factor; break;
+            case kPgPrecond: f = k_pg_precond; break;
+            case kPgStep:    f = k_pg_step; break;
+            case kPgStats:   f = k_pg_stats; break;
         }
-        return ok(hipGetLastError());
+        return launch(f, 1, kPgThreads, a);
     }
     bool dgrid(PgDirectGridKernel k, int count, const PgArgs& a, const PgDirect& d) {
-        if (count <= 0) return true;
-        const dim3 g((unsigned)((count + kPgGridThreads - 1) / kPgGridThreads)), b(kPgGridThreads);
+        void (*f)(PgArgs, PgDirect, int) = nullptr;
         switch (k) {
-            case kPgZ:     hipLaunchKernelGGL(k_pg_z, g, b, 0, stream, a, d, count); break;
-            case kPgWm:    hipLaunchKernelGGL(k_pg_wm, g, b, 0, stream, a, d, count); break;
-            case kPgSl:    hipLaunchKernelGGL(k_pg_sl, g, b, 0, stream, a, d, count); break;
-            case kPgKs:    hipLaunchKernelGGL(k_pg_ks, g, b, 0, stream, a, d, count); break;
-            case kPgZw:    hipLaunchKernelGGL(k_pg_zw, g, b, 0, stream, a, d, count); break;
-            case kPgResid: hipLaunchKernelGGL(k_pg_resid, g, b, 0, stream, a, d, count); break;
+            case kPgZ:     f = k_pg_z; break;
+            case kPgWm:    f = k_pg_wm; break;
+            case kPgSl:    f = k_pg_sl; break;
+            case kPgKs:    f = k_pg_ks; break;
+            case kPgZw:    f = k_pg_zw; break;
+            case kPgResid: f = k_pg_resid; break;
         }
-        return ok(hipGetLastError());
+        return launch(f, blocks_for(count), kPgGridThreads, a, d, count);
     }
     bool dgroup(PgDirectGroupKernel k, const PgArgs& a, const PgDirect& d) {
-        const dim3 g(1), b(kPgThreads);
         switch (k) {
-            case kPgCholW:    hipLaunchKernelGGL(k_pg_chol, g, b, 0, stream, a, d, 0); break;
-            case kPgCholK:    hipLaunchKernelGGL(k_pg_chol, g, b, 0, stream, a, d, 1); break;
-            case kPgBand:     hipLaunchKernelGGL(k_pg_band, g, b, 0, stream, a, d); break;
-            case kPgCapSolve: hipLaunchKernelGGL(k_pg_cap_solve, g, b, 0, stream, a, d); break;
+            case kPgCholW:    return launch(k_pg_chol, 1, kPgThreads, a, d, 0);
+            case kPgCholK:    return launch(k_pg_chol, 1, kPgThreads, a, d, 1);
+            case kPgBand:     return launch(k_pg_band, 1, kPgThreads, a, d);
+            case kPgCapSolve: return launch(k_pg_cap_solve, 1, kPgThreads, a, d);
         }
-        return ok(hipGetLastError());
+        return false;
     }
     bool mgrid(PgMargGridKernel k, int count, const PgArgs& a, const PgDirect& d, const PgMarg& mg) {
-        if (count <= 0) return true;
-        const dim3 g((unsigned)((count + kPgGridThreads - 1) / kPgGridThreads)), b(kPgGridThreads);
         switch (k) {
-            case kPgSelinvPrep: hipLaunchKernelGGL(k_pg_selinv_prep, g, b, 0, stream, a, mg, count); break;
-            case kPgMargLt:     hipLaunchKernelGGL(k_pg_marg_lt, g, b, 0, stream, a, d, mg, count); break;
+            case kPgSelinvPrep: return launch(k_pg_selinv_prep, blocks_for(count), kPgGridThreads, a, mg, count);
+            case kPgMargLt:     return launch(k_pg_marg_lt, blocks_for(count), kPgGridThreads, a, d, mg, count);
         }
-        return ok(hipGetLastError());
+        return false;
     }
     bool mgroups(PgMargGroupKernel k, int groups, const PgArgs& a, const PgDirect& d, const PgMarg& mg) {
-        if (groups <= 0) return true;
-        const dim3 b(kPgThreads);
         switch (k) {
-            case kPgSelinv:   hipLaunchKernelGGL(k_pg_selinv, dim3(1), b, 0, stream, a, mg); break;
-            case kPgMargNode: hipLaunchKernelGGL(k_pg_marg, dim3((unsigned)groups), b, 0, stream, a, d, mg); break;
+            case kPgSelinv:   return launch(k_pg_selinv, groups <= 0 ? 0 : 1, kPgThreads, a, mg);
+            case kPgMargNode: return launch(k_pg_marg, groups, kPgThreads, a, d, mg);
         }
-        return ok(hipGetLastError());
+        return false;
     }
     bool scalars(const PgArgs& a, double out[kPgScalars]) {
         if (!ok(hipMemcpyAsync(h_sc, a.sc, sizeof(double) * kPgScalars, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
@@ -165,181 +153,176 @@ struct PgArena {
     double* d(size_t n) { return static_cast<double*>(take(n * sizeof(double))); }
     int32_t* i(size_t n) { return static_cast<int32_t*>(take(n * sizeof(int32_t))); }
     float* f(size_t n) { return static_cast<float*>(take(n * sizeof(float))); }
+    void align8() { used = (used + 7) & ~(size_t)7; }
 };
 
-struct PgHostIo {          // the host-pointer form's staging, behind pg_bind's arrays in the same block
-    double *poses64 = nullptr, *edge_chi2 = nullptr;
-    float *poses = nullptr, *odo_X = nullptr, *odo_info = nullptr, *clo_X = nullptr, *clo_info = nullptr, *poses_out = nullptr;
+// What the caller describes: the chain, its closures and the nodes that stay.  Every entry point fills one.
+struct PgProblem {
+    int32_t n; const float *poses, *odo_X, *odo_info;
+    int32_t n_closures; const int32_t *ci, *cj; const float *clo_X, *clo_info;
+    const uint8_t* fixed;
 };
 
-icet_status pg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci, const int32_t* cj,
-                   const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt, float* poses_out, double* poses64_out,
-                   double* edge_chi2, icet_pose_graph_result* result, int32_t K = 0, const double* dbg_p = nullptr, icet_pose_graph_step* dbg = nullptr,
-                   icet_pose_graph_direct_step* ddbg = nullptr) {
+// One run on the device (pg_run, below).  The entry point names it and says where the arrays are; its plan sets what is bound and staged; its body finds the
+// graph, the bound arguments and the backend here.
+struct PgFrame {
+    icet_ctx* c; const char* name;          // the entry the error texts name
+    bool host_io;                           // the problem's arrays and the outputs are the host's: staged in the block (false: device pointers, used as they are)
+    PgProblem pb;
+    PgGraph graph; int m_ends = 0;          // (from the checks on)
+    // the plan: the work arrays bound beyond pg_bind's, and with host_io the outputs staged in the block (a.poses_out, a.poses64_out, a.edge_chi2_out; null otherwise)
+    bool direct = false, marg = false, stage_poses_out = false, stage_poses64 = false, stage_chi2 = false;
+    PgArgs a{}; PgDirect dir{}; PgMarg mg{};
+    PgDeviceBackend be;
+    hipError_t e = hipSuccess;              // the first failure of a copy or of the backend
+    PgFrame(icet_ctx* c_, const char* name_, bool host_io_, const PgProblem& pb_) : c(c_), name(name_), host_io(host_io_), pb(pb_) {}
+    // a result from the block to the host, behind the kernels on the stream (a null dst is skipped)
+    void down(void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && dst && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, c->stream); }
+};
+
+// THE frame of every pose-graph entry: the checks of the problem (outputs_ok: the entry's own output pointers are there), the graph, then plan() -- the entry's
+// own checks behind the graph's, and f's plan --, ONE device block for everything bound and staged, the uploads, body() -- the driver's call and f.down() of
+// what goes back; false for a failure of the backend --, the synchronisation and the error mapping.  The block's order: pg_bind | direct | marginals | staging,
+// the doubles first.  A local BufferGroup owns the block and the pinned scalars: every return frees through it.
+template <class Plan, class Body>
+icet_status pg_run(PgFrame& f, bool outputs_ok, Plan&& plan, Body&& body) {
+    icet_ctx* c = f.c;
     ICET_TRY(enter(c));
-    const bool hook = dbg || ddbg;
-    if (!poses || (!hook && (!poses_out || !result)) || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_optimize: bad argument"; return ICET_ERR_BAD_ARG; }
-    if ((n > 1 && (!odo_X || !odo_info)) || (n_closures > 0 && (!ci || !cj || !clo_X || !clo_info))) { c->err = "icet_pose_graph_optimize: null array"; return ICET_ERR_BAD_ARG; }
-    if (!pg::closures_ok(n, n_closures, ci, cj)) { c->err = "icet_pose_graph_optimize: a closure's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
-    const icet_pose_graph_options o = opt ? *opt : pg_default_options();
-    if (o.gn_iters < 1) { c->err = "icet_pose_graph_optimize: gn_iters < 1"; return ICET_ERR_BAD_ARG; }
-    PgGraph graph;
-    graph.build(n, n_closures, ci, cj, fixed);
-    // the linear solve: the context's option "pg_solver" (the step hook is conjugate gradients, the direct hook direct)
-    const int m_ends = (int)graph.ends.size();
-    if ((ddbg || (!dbg && c->pg_solver == 1)) && m_ends > kPgDirectMaxEnds) {
-        c->err = "icet_pose_graph_optimize: the direct solve takes at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " +
-                 std::to_string(m_ends) + " (option pg_solver 2 falls back to conjugate gradients)";
-        return ICET_ERR_UNSUPPORTED;
-    }
-    if (ddbg && ddbg->ends_capacity != m_ends) { c->err = "icet_debug_pose_graph_direct: ends_capacity is not the graph's count of end nodes (" + std::to_string(m_ends) + ")"; return ICET_ERR_BAD_ARG; }
-    const bool direct = ddbg || (!dbg && (c->pg_solver == 1 || (c->pg_solver == 2 && m_ends >= 1 && m_ends <= kPgDirectMaxEnds)));
+    const PgProblem& pb = f.pb;
+    const std::string name = f.name;
+    const int32_t n = pb.n, n_closures = pb.n_closures;
+    if (!pb.poses || !outputs_ok || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = name + ": bad argument"; return ICET_ERR_BAD_ARG; }
+    if ((n > 1 && (!pb.odo_X || !pb.odo_info)) || (n_closures > 0 && (!pb.ci || !pb.cj || !pb.clo_X || !pb.clo_info))) { c->err = name + ": null array"; return ICET_ERR_BAD_ARG; }
+    if (!pg::closures_ok(n, n_closures, pb.ci, pb.cj)) { c->err = name + ": a closure's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
+    PgGraph& graph = f.graph;
+    graph.build(n, n_closures, pb.ci, pb.cj, pb.fixed);
+    f.m_ends = (int)graph.ends.size();
+    ICET_TRY(plan());
 
-    PgArgs a{};
-    PgDirect dir{};
+    PgArgs& a = f.a;
     a.N = n; a.C = n_closures; a.E = pg::edge_count(n, n_closures);
-    const size_t N = (size_t)n, E = (size_t)a.E, C = (size_t)n_closures, n_items = graph.items.size();
+    const size_t N = (size_t)n, E = (size_t)a.E, C = (size_t)n_closures, n_items = graph.items.size(), m = (size_t)f.m_ends;
     PgArena arena;
     PgGraphDev gd{};
     PgDirectDev dd{};
-    PgHostIo io;
+    float *s_poses = nullptr, *s_odo_X = nullptr, *s_odo_info = nullptr, *s_clo_X = nullptr, *s_clo_info = nullptr;      // the staging of the problem's arrays
     auto layout = [&]() {
         arena.used = 0;
         gd = pg_bind(a, arena, n_items);
-        if (direct) {
-            arena.used = (arena.used + 7) & ~(size_t)7;
-            dd = pg_bind_direct(a, dir, arena, (size_t)m_ends);
-        }
-        if (host_io) {
-            // (int32 lists end on a multiple of 4 bytes; the doubles of the staging need 8)
-            arena.used = (arena.used + 7) & ~(size_t)7;
-            io.poses64 = poses64_out ? arena.d(N * 12) : nullptr; io.edge_chi2 = edge_chi2 ? arena.d(2 * E) : nullptr;
-            io.poses = arena.f(N * 16); io.odo_X = arena.f((N - 1) * 6); io.odo_info = arena.f((N - 1) * 36); io.clo_X = arena.f(C * 6); io.clo_info = arena.f(C * 36);
-            io.poses_out = arena.f(N * 16);
+        if (f.direct) { arena.align8(); dd = pg_bind_direct(a, f.dir, arena, m); }
+        if (f.marg) { arena.align8(); pg_bind_marg(a, f.dir, f.mg, arena, f.host_io); }
+        a.poses_out = nullptr; a.poses64_out = nullptr; a.edge_chi2_out = nullptr;
+        if (f.host_io) {
+            arena.align8();          // (int32 lists end on a multiple of 4 bytes; the doubles of the staging need 8)
+            if (f.stage_poses64) a.poses64_out = arena.d(N * 12);
+            if (f.stage_chi2) a.edge_chi2_out = arena.d(2 * E);
+            s_poses = arena.f(N * 16); s_odo_X = arena.f((N - 1) * 6); s_odo_info = arena.f((N - 1) * 36); s_clo_X = arena.f(C * 6); s_clo_info = arena.f(C * 36);
+            if (f.stage_poses_out) a.poses_out = arena.f(N * 16);
         }
     };
     layout();
     const size_t bytes = arena.used;
+    BufferGroup bufs;
     char* block = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&block), bytes));
+    HIPCHK(c, bufs.device(block, bytes));
     arena.base = block;
     layout();
 
-    PgDeviceBackend be;
-    be.stream = c->stream;
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&be.h_sc), sizeof(double) * kPgScalars, hipHostMallocDefault);
-    auto up = [&](void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, c->stream); };
-    auto down = [&](void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && dst && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToHost, c->stream); };
+    f.be.stream = c->stream;
+    f.e = static_cast<hipError_t>(bufs.pinned(f.be.h_sc, (size_t)kPgScalars, hipHostMallocDefault));
+    auto up = [&](void* dst, const void* src, size_t nbytes) { if (f.e == hipSuccess && nbytes) f.e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, c->stream); };
     up(gd.ei, graph.ei.data(), sizeof(int32_t) * E); up(gd.ej, graph.ej.data(), sizeof(int32_t) * E);
     up(gd.off, graph.off.data(), sizeof(int32_t) * (N + 1)); up(gd.items, graph.items.data(), sizeof(int32_t) * n_items);
-    if (direct) { up(dd.ends, graph.ends.data(), sizeof(int32_t) * (size_t)m_ends); up(dd.end_of, graph.end_of.data(), sizeof(int32_t) * N); }
-    if (host_io) {
-        up(io.poses, poses, sizeof(float) * N * 16); up(io.odo_X, odo_X, sizeof(float) * (N - 1) * 6); up(io.odo_info, odo_info, sizeof(float) * (N - 1) * 36);
-        up(io.clo_X, clo_X, sizeof(float) * C * 6); up(io.clo_info, clo_info, sizeof(float) * C * 36);
-        a.poses_in = io.poses; a.odo_X = io.odo_X; a.odo_info = io.odo_info; a.clo_X = io.clo_X; a.clo_info = io.clo_info;
-        a.poses_out = io.poses_out; a.poses64_out = io.poses64; a.edge_chi2_out = io.edge_chi2;
+    if (f.direct) { up(dd.ends, graph.ends.data(), sizeof(int32_t) * m); up(dd.end_of, graph.end_of.data(), sizeof(int32_t) * N); }
+    if (f.host_io) {
+        up(s_poses, pb.poses, sizeof(float) * N * 16); up(s_odo_X, pb.odo_X, sizeof(float) * (N - 1) * 6); up(s_odo_info, pb.odo_info, sizeof(float) * (N - 1) * 36);
+        up(s_clo_X, pb.clo_X, sizeof(float) * C * 6); up(s_clo_info, pb.clo_info, sizeof(float) * C * 36);
+        a.poses_in = s_poses; a.odo_X = s_odo_X; a.odo_info = s_odo_info; a.clo_X = s_clo_X; a.clo_info = s_clo_info;
     } else {
-        a.poses_in = poses; a.odo_X = odo_X; a.odo_info = odo_info; a.clo_X = clo_X; a.clo_info = clo_info;
-        a.poses_out = poses_out; a.poses64_out = poses64_out; a.edge_chi2_out = edge_chi2;
+        a.poses_in = pb.poses; a.odo_X = pb.odo_X; a.odo_info = pb.odo_info; a.clo_X = pb.clo_X; a.clo_info = pb.clo_info;
     }
-    icet_pose_graph_result res{};
-    bool done = false;
-    if (e == hipSuccess) {
-        // (the graph's lists and the caller's arrays outlive the synchronisation below; the stream orders the copies before the kernels)
-        done = ddbg ? pg_debug_direct_step(be, a, dir, o, K, dbg_p, ddbg)
-             : dbg ? pg_debug_step(be, a, o, graph.c_offband, K, dbg_p, dbg)
-             : direct ? pg_optimise_direct(be, a, dir, o, &res) : pg_optimise(be, a, o, graph.c_offband, &res);
-        if (!done) e = be.err;
-    }
-    if (done && host_io && !hook) {
-        down(poses_out, io.poses_out, sizeof(float) * N * 16); down(poses64_out, io.poses64, sizeof(double) * N * 12); down(edge_chi2, io.edge_chi2, sizeof(double) * 2 * E);
-    }
+    // (the graph's lists and the caller's arrays outlive the synchronisation below; the stream orders the copies before the kernels)
+    if (f.e == hipSuccess && !body()) f.e = f.be.err;
     const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(block);
-    if (be.h_sc) (void)hipHostFree(be.h_sc);
-    if (e != hipSuccess) { c->err = std::string("icet_pose_graph_optimize: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
-    if (result) *result = res;
+    if (f.e == hipSuccess) f.e = es;
+    if (f.e != hipSuccess) { c->err = name + ": " + hipGetErrorString(f.e); return f.e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
     return ICET_OK;
 }
 
-// The marginal covariances of a graph (icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals): pg_run's checks, block and staging, pg_marginals in
-// the place of the optimiser.
-icet_status pg_marg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
-                        const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, double* cov_out, icet_pose_graph_marginals_result* result,
-                        icet_pose_graph_marginals_debug* dbg = nullptr) {
-    ICET_TRY(enter(c));
-    if (!poses || (!dbg && (!cov_out || !result)) || n < 1 || n > pg::kMaxNodes || n_closures < 0 || n_closures > pg::kMaxClosures) { c->err = "icet_pose_graph_marginals: bad argument"; return ICET_ERR_BAD_ARG; }
-    if ((n > 1 && (!odo_X || !odo_info)) || (n_closures > 0 && (!ci || !cj || !clo_X || !clo_info))) { c->err = "icet_pose_graph_marginals: null array"; return ICET_ERR_BAD_ARG; }
-    if (!pg::closures_ok(n, n_closures, ci, cj)) { c->err = "icet_pose_graph_marginals: a closure's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
-    PgGraph graph;
-    graph.build(n, n_closures, ci, cj, fixed);
-    const int m_ends = (int)graph.ends.size();
-    if (m_ends > kPgDirectMaxEnds) {
-        c->err = "icet_pose_graph_marginals: at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " + std::to_string(m_ends);
-        return ICET_ERR_UNSUPPORTED;
-    }
-    if (dbg && dbg->ends_capacity != m_ends) { c->err = "icet_debug_pose_graph_marginals: ends_capacity is not the graph's count of end nodes (" + std::to_string(m_ends) + ")"; return ICET_ERR_BAD_ARG; }
+// ---- the optimiser: icet_pose_graph_optimize[_device] and its two hooks, which report under its name ----------------------------------------------------------
+constexpr const char* kPgOptimiseName = "icet_pose_graph_optimize";
 
-    PgArgs a{};
-    PgDirect dir{};
-    PgMarg mg{};
-    a.N = n; a.C = n_closures; a.E = pg::edge_count(n, n_closures);
-    const size_t N = (size_t)n, E = (size_t)a.E, C = (size_t)n_closures, n_items = graph.items.size();
-    PgArena arena;
-    PgGraphDev gd{};
-    PgDirectDev dd{};
-    PgHostIo io;
-    auto layout = [&]() {
-        arena.used = 0;
-        gd = pg_bind(a, arena, n_items);
-        arena.used = (arena.used + 7) & ~(size_t)7;
-        dd = pg_bind_direct(a, dir, arena, (size_t)m_ends);
-        arena.used = (arena.used + 7) & ~(size_t)7;
-        pg_bind_marg(a, dir, mg, arena, host_io);
-        if (host_io) { io.poses = arena.f(N * 16); io.odo_X = arena.f((N - 1) * 6); io.odo_info = arena.f((N - 1) * 36); io.clo_X = arena.f(C * 6); io.clo_info = arena.f(C * 36); }
-    };
-    layout();
-    const size_t bytes = arena.used;
-    char* block = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&block), bytes));
-    arena.base = block;
-    layout();
+// The options (null: the defaults), the first check of every optimiser plan
+icet_status pg_options(icet_ctx* c, const icet_pose_graph_options* opt, icet_pose_graph_options* o) {
+    *o = opt ? *opt : pg_default_options();
+    if (o->gn_iters < 1) { c->err = "icet_pose_graph_optimize: gn_iters < 1"; return ICET_ERR_BAD_ARG; }
+    return ICET_OK;
+}
+// The direct solve's limit on the end nodes
+icet_status pg_direct_limit(icet_ctx* c, int m_ends) {
+    if (m_ends <= kPgDirectMaxEnds) return ICET_OK;
+    c->err = "icet_pose_graph_optimize: the direct solve takes at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " +
+             std::to_string(m_ends) + " (option pg_solver 2 falls back to conjugate gradients)";
+    return ICET_ERR_UNSUPPORTED;
+}
+// A hook's ends_capacity against the graph's count
+icet_status pg_ends_capacity(icet_ctx* c, const char* hook, int32_t capacity, int m_ends) {
+    if (capacity == m_ends) return ICET_OK;
+    c->err = std::string(hook) + ": ends_capacity is not the graph's count of end nodes (" + std::to_string(m_ends) + ")";
+    return ICET_ERR_BAD_ARG;
+}
 
-    PgDeviceBackend be;
-    be.stream = c->stream;
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&be.h_sc), sizeof(double) * kPgScalars, hipHostMallocDefault);
-    auto up = [&](void* dst, const void* src, size_t nbytes) { if (e == hipSuccess && nbytes) e = hipMemcpyAsync(dst, src, nbytes, hipMemcpyHostToDevice, c->stream); };
-    up(gd.ei, graph.ei.data(), sizeof(int32_t) * E); up(gd.ej, graph.ej.data(), sizeof(int32_t) * E);
-    up(gd.off, graph.off.data(), sizeof(int32_t) * (N + 1)); up(gd.items, graph.items.data(), sizeof(int32_t) * n_items);
-    up(dd.ends, graph.ends.data(), sizeof(int32_t) * (size_t)m_ends); up(dd.end_of, graph.end_of.data(), sizeof(int32_t) * N);
-    if (host_io) {
-        up(io.poses, poses, sizeof(float) * N * 16); up(io.odo_X, odo_X, sizeof(float) * (N - 1) * 6); up(io.odo_info, odo_info, sizeof(float) * (N - 1) * 36);
-        up(io.clo_X, clo_X, sizeof(float) * C * 6); up(io.clo_info, clo_info, sizeof(float) * C * 36);
-        a.poses_in = io.poses; a.odo_X = io.odo_X; a.odo_info = io.odo_info; a.clo_X = io.clo_X; a.clo_info = io.clo_info;
-    } else {
-        a.poses_in = poses; a.odo_X = odo_X; a.odo_info = odo_info; a.clo_X = clo_X; a.clo_info = clo_info;
-        mg.cov = cov_out;
-    }
-    a.poses_out = nullptr; a.poses64_out = nullptr; a.edge_chi2_out = nullptr;          // (kPgFinish does not run)
+// The linear solve is the context's option "pg_solver": 0 conjugate gradients, 1 the direct solve, 2 the direct solve where the graph has end nodes within its limit.
+icet_status pg_optimise_entry(icet_ctx* c, bool host_io, const PgProblem& pb, const icet_pose_graph_options* opt, float* poses_out, double* poses64_out,
+                              double* edge_chi2, icet_pose_graph_result* result) {
+    PgFrame f(c, kPgOptimiseName, host_io, pb);
+    icet_pose_graph_options o;
+    icet_pose_graph_result res{};
+    ICET_TRY(pg_run(f, poses_out && result,
+        [&]() {
+            ICET_TRY(pg_options(c, opt, &o));
+            if (c->pg_solver == 1) ICET_TRY(pg_direct_limit(c, f.m_ends));
+            f.direct = c->pg_solver == 1 || (c->pg_solver == 2 && f.m_ends >= 1 && f.m_ends <= kPgDirectMaxEnds);
+            f.stage_poses_out = true; f.stage_poses64 = poses64_out != nullptr; f.stage_chi2 = edge_chi2 != nullptr;
+            return ICET_OK;
+        },
+        [&]() {
+            const size_t N = (size_t)f.a.N, E = (size_t)f.a.E;
+            if (!host_io) { f.a.poses_out = poses_out; f.a.poses64_out = poses64_out; f.a.edge_chi2_out = edge_chi2; }
+            if (!(f.direct ? pg_optimise_direct(f.be, f.a, f.dir, o, &res) : pg_optimise(f.be, f.a, o, f.graph.c_offband, &res))) return false;
+            if (host_io) { f.down(poses_out, f.a.poses_out, sizeof(float) * N * 16); f.down(poses64_out, f.a.poses64_out, sizeof(double) * N * 12); f.down(edge_chi2, f.a.edge_chi2_out, sizeof(double) * 2 * E); }
+            return true;
+        }));
+    *result = res;
+    return ICET_OK;
+}
+
+// ---- the marginal covariances: icet_pose_graph_marginals[_device] and, with dbg, its hook (D, B, A, the band's selected inverse and the end nodes copied out) ------
+icet_status pg_marginals_entry(icet_ctx* c, bool host_io, const PgProblem& pb, double* cov_out, icet_pose_graph_marginals_result* result,
+                               icet_pose_graph_marginals_debug* dbg = nullptr) {
+    PgFrame f(c, "icet_pose_graph_marginals", host_io, pb);
     icet_pose_graph_marginals_result res{};
-    bool done = false;
-    if (e == hipSuccess) {
-        PgMargTap tap;
-        if (dbg) { tap.D = dbg->D; tap.B = dbg->B; tap.A = dbg->A; tap.band_cov = dbg->band_cov; }
-        done = pg_marginals(be, a, dir, mg, &res, dbg ? &tap : nullptr);
-        if (!done) e = be.err;
-    }
-    double* host_cov = dbg ? dbg->cov : cov_out;
-    if (done && host_io && host_cov && e == hipSuccess) e = hipMemcpyAsync(host_cov, mg.cov, sizeof(double) * N * 36, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(block);
-    if (be.h_sc) (void)hipHostFree(be.h_sc);
-    if (e != hipSuccess) { c->err = std::string("icet_pose_graph_marginals: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    ICET_TRY(pg_run(f, dbg || (cov_out && result),
+        [&]() {
+            if (f.m_ends > kPgDirectMaxEnds) {
+                c->err = "icet_pose_graph_marginals: at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " + std::to_string(f.m_ends);
+                return ICET_ERR_UNSUPPORTED;
+            }
+            if (dbg) ICET_TRY(pg_ends_capacity(c, "icet_debug_pose_graph_marginals", dbg->ends_capacity, f.m_ends));
+            f.direct = true; f.marg = true;          // (the block stages cov with host_io: pg_bind_marg; kPgFinish does not run, so none of its outputs)
+            return ICET_OK;
+        },
+        [&]() {
+            if (!host_io) f.mg.cov = cov_out;
+            PgMargTap tap;
+            if (dbg) { tap.D = dbg->D; tap.B = dbg->B; tap.A = dbg->A; tap.band_cov = dbg->band_cov; }
+            if (!pg_marginals(f.be, f.a, f.dir, f.mg, &res, dbg ? &tap : nullptr)) return false;
+            if (host_io) f.down(dbg ? dbg->cov : cov_out, f.mg.cov, sizeof(double) * (size_t)f.a.N * 36);
+            return true;
+        }));
     if (dbg) {
         dbg->result = res;
-        if (dbg->ends) for (int i = 0; i < m_ends; i++) dbg->ends[i] = graph.ends[(size_t)i];
+        if (dbg->ends) for (int i = 0; i < f.m_ends; i++) dbg->ends[i] = f.graph.ends[(size_t)i];
     }
     if (result) *result = res;
     return ICET_OK;
@@ -350,45 +333,53 @@ icet_status pg_marg_run(icet_ctx* c, bool host_io, int32_t n, const float* poses
 
 using namespace icet;
 
+// Every entry point hands the eleven arguments that describe the graph on as one PgProblem.
 icet_status icet_pose_graph_marginals(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
                                       const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, double* cov_out,
                                       icet_pose_graph_marginals_result* result) {
-    return pg_marg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, cov_out, result);
+    return pg_marginals_entry(c, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, cov_out, result);
 }
 
-icet_status icet_pose_graph_marginals_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
-                                             const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, double* cov_out,
+icet_status icet_pose_graph_marginals_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                             const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, double* cov_out,
                                              icet_pose_graph_marginals_result* result) {
-    return pg_marg_run(c, false, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, cov_out, result);
+    return pg_marginals_entry(c, false, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, cov_out, result);
 }
 
 // Test hook: the marginals on host arrays with D, B, A, the band's selected inverse and the end nodes copied out.
-icet_status icet_debug_pose_graph_marginals(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
-                                            const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, icet_pose_graph_marginals_debug* out) {
+icet_status icet_debug_pose_graph_marginals(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                            const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                            icet_pose_graph_marginals_debug* out) {
     if (!c) return ICET_ERR_BAD_ARG;
     if (!out || out->ends_capacity < 0 || out->reserved != 0) { c->err = "icet_debug_pose_graph_marginals: bad argument"; return ICET_ERR_BAD_ARG; }
-    return pg_marg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, nullptr, nullptr, out);
+    return pg_marginals_entry(c, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, nullptr, nullptr, out);
 }
 
 icet_status icet_pose_graph_optimize(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
                                      const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
                                      float* poses_out, double* poses64_out, double* edge_chi2, icet_pose_graph_result* result) {
-    return pg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, poses_out, poses64_out, edge_chi2, result);
+    return pg_optimise_entry(c, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, opt, poses_out, poses64_out, edge_chi2, result);
 }
 
-icet_status icet_pose_graph_optimize_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
-                                            const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
-                                            float* poses_out, double* poses64_out, double* edge_chi2, icet_pose_graph_result* result) {
-    return pg_run(c, false, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, poses_out, poses64_out, edge_chi2, result);
+icet_status icet_pose_graph_optimize_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                            const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                            const icet_pose_graph_options* opt, float* poses_out, double* poses64_out, double* edge_chi2,
+                                            icet_pose_graph_result* result) {
+    return pg_optimise_entry(c, false, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, opt, poses_out, poses64_out, edge_chi2, result);
 }
 
-// Test hook: the optimiser's first iteration with its intermediate arrays copied out (pg_debug_step).  The host-pointer form's staging; nothing is finished.
+// Test hook: the optimiser's first iteration with its intermediate arrays copied out (pg_debug_step): conjugate gradients whatever "pg_solver" says.  The
+// host-pointer form's staging; nothing is finished.
 icet_status icet_debug_pose_graph_step(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
                                        const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
                                        int32_t K, const double* p, icet_pose_graph_step* out) {
     if (!c) return ICET_ERR_BAD_ARG;
     if (!out || K < 0 || (K > 0 && (!p || !out->q)) || out->cg_capacity < 0 || (out->cg_capacity > 0 && !out->cg_scalars)) { c->err = "icet_debug_pose_graph_step: bad argument"; return ICET_ERR_BAD_ARG; }
-    return pg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, nullptr, nullptr, nullptr, nullptr, K, p, out);
+    PgFrame f(c, kPgOptimiseName, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed});
+    icet_pose_graph_options o;
+    return pg_run(f, true,
+        [&]() { ICET_TRY(pg_options(c, opt, &o)); f.stage_poses_out = true; return ICET_OK; },
+        [&]() { return pg_debug_step(f.be, f.a, o, f.graph.c_offband, K, p, out); });
 }
 
 // Test hook: the first iteration with the direct solve, its intermediate arrays copied out (pg_debug_direct_step).
@@ -397,7 +388,17 @@ icet_status icet_debug_pose_graph_direct(icet_ctx* c, int32_t n, const float* po
                                          int32_t K, const double* p, icet_pose_graph_direct_step* out) {
     if (!c) return ICET_ERR_BAD_ARG;
     if (!out || K < 0 || (K > 0 && (!p || !out->q)) || out->ends_capacity < 0 || out->reserved != 0) { c->err = "icet_debug_pose_graph_direct: bad argument"; return ICET_ERR_BAD_ARG; }
-    return pg_run(c, true, n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed, opt, nullptr, nullptr, nullptr, nullptr, K, p, nullptr, out);
+    PgFrame f(c, kPgOptimiseName, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed});
+    icet_pose_graph_options o;
+    return pg_run(f, true,
+        [&]() {
+            ICET_TRY(pg_options(c, opt, &o));
+            ICET_TRY(pg_direct_limit(c, f.m_ends));
+            ICET_TRY(pg_ends_capacity(c, "icet_debug_pose_graph_direct", out->ends_capacity, f.m_ends));
+            f.direct = true; f.stage_poses_out = true;
+            return ICET_OK;
+        },
+        [&]() { return pg_debug_direct_step(f.be, f.a, f.dir, o, K, p, out); });
 }
 
 // Test hook: one block-tridiagonal system through the optimiser's factor and sweeps.  diag, sub: n x 36 doubles (sub[k] is the block at (k, k - 1); sub[0] is not

@@ -11,8 +11,10 @@
 //     bool mgroups(PgMargGroupKernel, int groups, const PgArgs&, const PgDirect&, const PgMarg&)
 //                                                            the marginals' bodies (icet_posegraph_marginals.h); mgroups runs a group body once per group index
 //                                                            below `groups` (one workgroup each; the host loops over them); only pg_marginals calls them
-// each false for a failure of the backend (the driver then returns false at once).  icet_posegraph.hip has the device's backend,
-// tests/cpp/test_posegraph_optimize.cpp and tests/cpp/test_posegraph_direct.cpp the host's.
+// each false for a failure of the backend (the driver then returns false at once).  icet_posegraph.hip has the device's backend (PgDeviceBackend),
+// tests/cpp/posegraph_host.h the host's (HostBackend), which the three host programs beside it share.
+// The sequences of launches that every run repeats are named once (pg_phase_*, below); the four drivers -- pg_gauss_newton, pg_marginals and the two hooks --
+// are made of them.
 #pragma once
 #include "icet_posegraph_body.h"
 #include "icet_posegraph_direct.h"
@@ -64,6 +66,52 @@ inline PgGraphDev pg_bind(PgArgs& a, Alloc& al, size_t n_items) {
     return gd;
 }
 
+// ---- the phases: the sequences of launches the drivers share, each false for a failure of the backend ----------------------------------------------------
+// (the test hooks) count doubles from the device to dst; a null dst is skipped
+template <class Backend>
+inline bool pg_get(Backend& be, double* dst, const double* src, size_t count) { return !dst || count == 0 || be.fetch(dst, src, count * sizeof(double)); }
+
+// The poses and the information matrices in place, every edge's chi2 at them
+template <class Backend>
+inline bool pg_phase_init(Backend& be, const PgArgs& a) {
+    const int n_init = a.N * 12 > a.E * 36 ? a.N * 12 : a.E * 36;
+    return be.grid(kPgInit, n_init, a) && be.grid(kPgChi, a.E, a);
+}
+// The start of a run: pg_phase_init, then the sum of the chi2 in the scalars, read into h
+template <class Backend>
+inline bool pg_phase_start(Backend& be, const PgArgs& a, double h[kPgScalars]) { return pg_phase_init(be, a) && be.group(kPgStats, a) && be.scalars(a, h); }
+// The normal equations at the current poses: D, B, A and g
+template <class Backend>
+inline bool pg_phase_linearise(Backend& be, const PgArgs& a) {
+    return be.grid(kPgLinearise, a.E * 12, a) && be.grid(kPgAssemble, a.N * 36, a) && be.grid(kPgOffband, a.C * 36, a);
+}
+// ... and the band's factor behind them: what a linear solve starts from
+template <class Backend>
+inline bool pg_phase_factor(Backend& be, const PgArgs& a) { return pg_phase_linearise(be, a) && be.group(kPgFactor, a); }
+// The trial poses P (+) x, their chi2 and the step's length in the scalars, read into h.  a.trial is set for these launches alone.
+template <class Backend>
+inline bool pg_phase_trial(Backend& be, PgArgs& a, double h[kPgScalars]) {
+    a.trial = 1;
+    const bool ok = be.grid(kPgRetract, a.N, a) && be.grid(kPgChi, a.E, a) && be.group(kPgStats, a) && be.scalars(a, h);
+    a.trial = 0;
+    return ok;
+}
+// The direct solve's factorisation behind the band's factor (q = d.nq > 0): Z, Wm and its factor, Ks and its factor
+template <class Backend>
+inline bool pg_phase_direct_factor(Backend& be, const PgArgs& a, const PgDirect& d) {
+    const int q = d.nq;
+    return be.dgrid(kPgZ, q, a, d) && be.dgrid(kPgWm, q * q, a, d) && be.dgroup(kPgCholW, a, d) && be.dgrid(kPgSl, q * q, a, d) && be.dgrid(kPgKs, q * q, a, d) &&
+           be.dgroup(kPgCholK, a, d);
+}
+// (the test hooks) q = H p for each of the caller's K vectors, through the kernel CG uses; a null q: nothing
+template <class Backend>
+inline bool pg_phase_hp(Backend& be, const PgArgs& a, int K, const double* p, double* q) {
+    const size_t n6 = (size_t)a.N * 6, sd = sizeof(double);
+    for (int k = 0; k < K && q; k++)
+        if (!be.put(a.p, p + (size_t)k * n6, n6 * sd) || !be.grid(kPgHp, a.N * 6, a) || !be.fetch(q + (size_t)k * n6, a.q, n6 * sd)) return false;
+    return true;
+}
+
 // The band solves one linear solve may take.  H = M + R: with no closure off the band H is the band, and the first preconditioned step is the exact solve.
 inline int pg_cg_cap(int c_offband, const icet_pose_graph_options& o) { return c_offband == 0 ? 1 : (o.max_pcg > 0 ? o.max_pcg : 12 * c_offband + 8); }
 
@@ -107,10 +155,9 @@ inline bool pg_cg(Backend& be, PgArgs& a, int cap, double pcg_tol, int* pcg, int
 template <class Backend, class Solve>
 inline bool pg_gauss_newton(Backend& be, PgArgs a, const icet_pose_graph_options& o, Solve&& solve, int solver, icet_pose_graph_result* res) {
     double h[kPgScalars];
-    const int N = a.N, E = a.E, C = a.C;
-    const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
+    const int N = a.N, E = a.E;
     a.damping = o.damping; a.trial = 0; a.first = 0; a.failed = 0;
-    if (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
+    if (!pg_phase_start(be, a, h)) return false;
     const double chi2_initial = h[kScChi];
     double chi2 = chi2_initial, max_dx = 0.0;
     int status = pg::kIterationCap, its = 0, pcg = 0;
@@ -118,13 +165,11 @@ inline bool pg_gauss_newton(Backend& be, PgArgs a, const icet_pose_graph_options
     if (!std::isfinite(chi2)) { status = pg::kNonFinite; failed = true; }
     for (int it = 0; it < o.gn_iters && !failed; it++) {
         its++;
-        if (!be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) || !be.grid(kPgOffband, C * 36, a) || !be.group(kPgFactor, a)) return false;
+        if (!pg_phase_factor(be, a)) return false;
         int bad = 0;
         if (!solve(a, &pcg, &bad)) return false;
         if (bad) { status = bad; failed = true; break; }
-        a.trial = 1;
-        if (!be.grid(kPgRetract, N, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
-        a.trial = 0;
+        if (!pg_phase_trial(be, a, h)) return false;
         if (h[kScCg] != 0.0) { status = (int)h[kScCg]; failed = true; break; }
         max_dx = h[kScMaxDx];
         const double chit = h[kScChi];
@@ -179,20 +224,18 @@ struct PgDirectTap { double *Z = nullptr, *Wm = nullptr, *L = nullptr, *Ks = nul
 template <class Backend>
 inline bool pg_direct_solve(Backend& be, PgArgs& a, PgDirect& d, int* pcg, const PgDirectTap* tap = nullptr) {
     const int q = d.nq, n6 = a.N * 6;
-    const size_t sd = sizeof(double), qq = (size_t)q * (size_t)q;
-    auto get = [&](double* dst, const double* src, size_t count) { return !tap || !dst || count == 0 || be.fetch(dst, src, count * sd); };
+    const size_t qq = (size_t)q * (size_t)q;
     d.refine = 0;
     if (q == 0) {
         if (!be.dgroup(kPgBand, a, d) || !be.dgrid(kPgZw, n6, a, d)) return false;
         ++*pcg;
-        return get(tap ? tap->x0 : nullptr, a.x, (size_t)n6);
+        return pg_get(be, tap ? tap->x0 : nullptr, a.x, (size_t)n6);
     }
-    if (!be.dgrid(kPgZ, q, a, d) || !be.dgrid(kPgWm, q * q, a, d) || !be.dgroup(kPgCholW, a, d) || !be.dgrid(kPgSl, q * q, a, d) || !be.dgrid(kPgKs, q * q, a, d) ||
-        !be.dgroup(kPgCholK, a, d)) return false;
-    if (tap && (!get(tap->Z, d.Z, (size_t)n6 * (size_t)q) || !get(tap->Wm, d.Wm, qq) || !get(tap->L, d.Lw, qq) || !get(tap->Ks, d.Ks, qq) || !get(tap->Lk, d.Lk, qq))) return false;
+    if (!pg_phase_direct_factor(be, a, d)) return false;
+    if (tap && (!pg_get(be, tap->Z, d.Z, (size_t)n6 * (size_t)q) || !pg_get(be, tap->Wm, d.Wm, qq) || !pg_get(be, tap->L, d.Lw, qq) || !pg_get(be, tap->Ks, d.Ks, qq) || !pg_get(be, tap->Lk, d.Lk, qq))) return false;
     if (!be.dgroup(kPgBand, a, d) || !be.dgroup(kPgCapSolve, a, d) || !be.dgrid(kPgZw, n6, a, d)) return false;
     ++*pcg;
-    if (!get(tap ? tap->x0 : nullptr, a.x, (size_t)n6)) return false;
+    if (!pg_get(be, tap ? tap->x0 : nullptr, a.x, (size_t)n6)) return false;
     for (int it = 0; it < kPgDirectRefine; it++) {
         PgArgs b = a;
         b.p = a.x;                                  // q = H x through the kernel CG uses
@@ -247,24 +290,20 @@ struct PgMargTap { double *D = nullptr, *B = nullptr, *A = nullptr, *band_cov = 
 template <class Backend>
 inline bool pg_marginals(Backend& be, PgArgs a, PgDirect d, PgMarg mg, icet_pose_graph_marginals_result* res, const PgMargTap* tap = nullptr, bool assembled = false) {
     double h[kPgScalars];
-    const int N = a.N, E = a.E, C = a.C, q = d.nq;
-    const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
+    const int N = a.N, C = a.C, q = d.nq;
     a.damping = 0.0; a.trial = 0; a.first = 0; a.failed = 0;
-    if (!assembled && (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) ||
-                       !be.grid(kPgOffband, C * 36, a))) return false;
+    // (no sum of the chi2 and no scalars read at the start: nothing here depends on them)
+    if (!assembled && (!pg_phase_init(be, a) || !pg_phase_linearise(be, a))) return false;
     if (!be.group(kPgFactor, a)) return false;
-    if (q > 0 && (!be.dgrid(kPgZ, q, a, d) || !be.dgrid(kPgWm, q * q, a, d) || !be.dgroup(kPgCholW, a, d) || !be.dgrid(kPgSl, q * q, a, d) || !be.dgrid(kPgKs, q * q, a, d) ||
-                  !be.dgroup(kPgCholK, a, d) || !be.mgrid(kPgMargLt, q * q, a, d, mg))) return false;
+    if (q > 0 && (!pg_phase_direct_factor(be, a, d) || !be.mgrid(kPgMargLt, q * q, a, d, mg))) return false;
     if (!be.mgrid(kPgSelinvPrep, N, a, d, mg) || !be.mgroups(kPgSelinv, 1, a, d, mg) || !be.mgroups(kPgMargNode, N, a, d, mg) || !be.scalars(a, h)) return false;
     int st[3];
     res->status = pg_direct_status(h, st);
     res->m = q / 6; res->factor_status = st[0]; res->wm_status = st[1]; res->ks_status = st[2]; res->reserved = 0;
     if (tap) {
-        const size_t sd = sizeof(double);
-        auto get = [&](double* dst, const double* src, size_t count) { return !dst || count == 0 || be.fetch(dst, src, count * sd); };
         // (band_cov is written only behind a band that factored)
-        if (!get(tap->D, a.D, (size_t)N * 36) || !get(tap->B, a.B, (size_t)N * 36) || !get(tap->A, a.A, (size_t)C * 36) ||
-            (st[0] == 0 && !get(tap->band_cov, mg.band_cov, (size_t)N * 36))) return false;
+        if (!pg_get(be, tap->D, a.D, (size_t)N * 36) || !pg_get(be, tap->B, a.B, (size_t)N * 36) || !pg_get(be, tap->A, a.A, (size_t)C * 36) ||
+            (st[0] == 0 && !pg_get(be, tap->band_cov, mg.band_cov, (size_t)N * 36))) return false;
     }
     return true;
 }
@@ -275,35 +314,29 @@ template <class Backend>
 inline bool pg_debug_direct_step(Backend& be, PgArgs a, PgDirect d, const icet_pose_graph_options& o, int K, const double* p, icet_pose_graph_direct_step* out) {
     double h[kPgScalars];
     const int N = a.N, E = a.E, C = a.C;
-    const size_t sd = sizeof(double), n6 = (size_t)N * 6;
-    const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
-    auto get = [&](double* dst, const double* src, size_t count) { return !dst || count == 0 || be.fetch(dst, src, count * sd); };
+    const size_t n6 = (size_t)N * 6;
     a.damping = o.damping; a.trial = 0; a.first = 0; a.failed = 0;
     out->m = d.nq / 6; out->factor_status = 0; out->wm_status = 0; out->ks_status = 0; out->band_solves = 0; out->trial = 0;
     out->chi2_start = 0.0; out->chi2_trial = 0.0; out->max_dx = 0.0;
     if (out->ends && d.nq > 0 && !be.fetch(out->ends, d.ends, sizeof(int32_t) * (size_t)(d.nq / 6))) return false;
-    if (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
+    if (!pg_phase_start(be, a, h)) return false;
     out->chi2_start = h[kScChi];
     if (!std::isfinite(h[kScChi])) { out->factor_status = pg::kNonFinite; return true; }
-    if (!be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) || !be.grid(kPgOffband, C * 36, a) || !be.group(kPgFactor, a)) return false;
-    if (!get(out->D, a.D, (size_t)N * 36) || !get(out->B, a.B, (size_t)N * 36) || !get(out->A, a.A, (size_t)C * 36) || !get(out->g, a.g, n6)) return false;
+    if (!pg_phase_factor(be, a)) return false;
+    if (!pg_get(be, out->D, a.D, (size_t)N * 36) || !pg_get(be, out->B, a.B, (size_t)N * 36) || !pg_get(be, out->A, a.A, (size_t)C * 36) || !pg_get(be, out->g, a.g, n6)) return false;
     PgDirectTap tap;
     tap.Z = out->Z; tap.Wm = out->Wm; tap.L = out->L; tap.Ks = out->Ks; tap.Lk = out->Lk; tap.x0 = out->x0;
     int pcg = 0, st[3];
     if (!pg_direct_solve(be, a, d, &pcg, &tap) || !be.scalars(a, h)) return false;
     const int bad = pg_direct_status(h, st);
     out->factor_status = st[0]; out->wm_status = st[1]; out->ks_status = st[2]; out->band_solves = pcg;
-    if (!get(out->x, a.x, n6)) return false;
+    if (!pg_get(be, out->x, a.x, n6)) return false;
     if (!bad) {
-        a.trial = 1;
-        if (!be.grid(kPgRetract, N, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
-        a.trial = 0;
+        if (!pg_phase_trial(be, a, h)) return false;
         out->trial = 1; out->chi2_trial = h[kScChi]; out->max_dx = h[kScMaxDx];
-        if (!get(out->Pt, a.Pt, (size_t)N * 12) || !get(out->chi_trial, a.chit, (size_t)E)) return false;
+        if (!pg_get(be, out->Pt, a.Pt, (size_t)N * 12) || !pg_get(be, out->chi_trial, a.chit, (size_t)E)) return false;
     }
-    for (int k = 0; k < K && out->q; k++)
-        if (!be.put(a.p, p + (size_t)k * n6, n6 * sd) || !be.grid(kPgHp, N * 6, a) || !be.fetch(out->q + (size_t)k * n6, a.q, n6 * sd)) return false;
-    return true;
+    return pg_phase_hp(be, a, K, p, out->q);
 }
 
 // The test hook's run (icet_debug_pose_graph_step; the host test runs it too): the optimiser's FIRST iteration, kernel for kernel -- the start's chi2, one
@@ -314,39 +347,33 @@ template <class Backend>
 inline bool pg_debug_step(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, int K, const double* p, icet_pose_graph_step* out) {
     double h[kPgScalars];
     const int N = a.N, E = a.E, C = a.C;
-    const size_t sd = sizeof(double), n6 = (size_t)N * 6;
+    const size_t n6 = (size_t)N * 6;
     const double pcg_tol = o.pcg_tol > 0.0 ? o.pcg_tol : kPgDefaultPcgTol;
-    const int n_init = N * 12 > E * 36 ? N * 12 : E * 36;
-    auto get = [&](double* dst, const double* src, size_t count) { return !dst || count == 0 || be.fetch(dst, src, count * sd); };
     a.damping = o.damping; a.trial = 0; a.first = 0; a.failed = 0;
     out->factor_status = 0; out->cg_status = 0; out->band_solves = 0; out->cg_end = kPgCgFailed; out->trial = 0;
     out->c_offband = c_offband; out->cap = pg_cg_cap(c_offband, o);
     out->chi2_start = 0.0; out->chi2_trial = 0.0; out->max_dx = 0.0;
-    if (!be.grid(kPgInit, n_init, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
+    if (!pg_phase_start(be, a, h)) return false;
     out->chi2_start = h[kScChi];
-    if (!get(out->res, a.res, (size_t)E * 6) || !get(out->chi_start, a.chi, (size_t)E)) return false;
+    if (!pg_get(be, out->res, a.res, (size_t)E * 6) || !pg_get(be, out->chi_start, a.chi, (size_t)E)) return false;
     if (!std::isfinite(h[kScChi])) { out->cg_status = pg::kNonFinite; return true; }
-    if (!be.grid(kPgLinearise, E * 12, a) || !be.grid(kPgAssemble, N * 36, a) || !be.grid(kPgOffband, C * 36, a) || !be.group(kPgFactor, a)) return false;
-    if (!get(out->J, a.J, (size_t)E * 72) || !get(out->D, a.D, (size_t)N * 36) || !get(out->B, a.B, (size_t)N * 36) || !get(out->A, a.A, (size_t)C * 36) ||
-        !get(out->g, a.g, n6)) return false;
+    if (!pg_phase_factor(be, a)) return false;
+    if (!pg_get(be, out->J, a.J, (size_t)E * 72) || !pg_get(be, out->D, a.D, (size_t)N * 36) || !pg_get(be, out->B, a.B, (size_t)N * 36) || !pg_get(be, out->A, a.A, (size_t)C * 36) ||
+        !pg_get(be, out->g, a.g, n6)) return false;
     std::vector<double> rec(2 * (size_t)out->cap, std::nan(""));
     int pcg = 0, bad = 0, end = kPgCgCap;
     if (!pg_cg(be, a, out->cap, pcg_tol, &pcg, &bad, &end, rec.data())) return false;
     if (!be.scalars(a, h)) return false;
     out->factor_status = (int)h[kScFactor]; out->cg_status = bad; out->band_solves = pcg; out->cg_end = end;
     for (int i = 0; i < pcg && i < out->cg_capacity && out->cg_scalars; i++) { out->cg_scalars[2 * i] = rec[2 * i]; out->cg_scalars[2 * i + 1] = rec[2 * i + 1]; }
-    if (!get(out->x, a.x, n6)) return false;
+    if (!pg_get(be, out->x, a.x, n6)) return false;
     if (!bad) {
-        a.trial = 1;
-        if (!be.grid(kPgRetract, N, a) || !be.grid(kPgChi, E, a) || !be.group(kPgStats, a) || !be.scalars(a, h)) return false;
-        a.trial = 0;
+        if (!pg_phase_trial(be, a, h)) return false;
         out->trial = 1; out->chi2_trial = h[kScChi]; out->max_dx = h[kScMaxDx];
         if (h[kScCg] != 0.0) { out->cg_status = (int)h[kScCg]; out->cg_end = kPgCgFailed; }      // (the last step under the cap found p.Hp not positive)
-        if (!get(out->Pt, a.Pt, (size_t)N * 12) || !get(out->chi_trial, a.chit, (size_t)E)) return false;
+        if (!pg_get(be, out->Pt, a.Pt, (size_t)N * 12) || !pg_get(be, out->chi_trial, a.chit, (size_t)E)) return false;
     }
-    for (int k = 0; k < K && out->q; k++)
-        if (!be.put(a.p, p + (size_t)k * n6, n6 * sd) || !be.grid(kPgHp, N * 6, a) || !be.fetch(out->q + (size_t)k * n6, a.q, n6 * sd)) return false;
-    return true;
+    return pg_phase_hp(be, a, K, p, out->q);
 }
 
 }  // namespace icet

@@ -9,158 +9,24 @@
 // Usage: test_posegraph_direct step IN OUT: pg_debug_direct_step.  IN with, behind every graph, int32 K | double p[K x n x 6].  OUT per graph: int32 m,
 //     factor_status, wm_status, ks_status, band_solves, trial, 0, 0 | double chi2_start, chi2_trial, max_dx | int32 ends[m] | double D[n x 36], B[n x 36], A[C x 36],
 //     g[n x 6], Z[6n x q], Wm, L, Ks, Lk [q x q], x0[n x 6], x[n x 6], Pt[n x 12], chi_trial[E], q[K x n x 6] (NaN where the run wrote nothing).
-#if defined(ICET_PG_EMU)
-#include <pthread.h>
-static thread_local int pg_emu_tid = 0;
-static pthread_barrier_t pg_emu_barrier;
-#define ICET_PG_EMU_THREADS 4
-#define ICET_PG_DEV static inline
-#define ICET_PG_TID pg_emu_tid
-#define ICET_PG_SYNC() pthread_barrier_wait(&pg_emu_barrier)
-#define ICET_PG_UNROLL
-#endif
-#include "icet_amd/csrc/icet_posegraph_driver.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <vector>
-#if defined(ICET_PG_EMU)
-#include <thread>
-#endif
-
-using namespace icet;
-
-struct HostAlloc {
-    std::vector<std::unique_ptr<double[]>> dd;
-    std::vector<std::unique_ptr<int32_t[]>> ii;
-    double* d(size_t n) { dd.emplace_back(new double[n]); return dd.back().get(); }
-    int32_t* i(size_t n) { ii.emplace_back(new int32_t[n]); return ii.back().get(); }
-};
-
-struct HostBackend {
-    long launches = 0;
-    bool grid(PgGridKernel k, int count, const PgArgs& a) {
-        launches++;
-        for (int gi = 0; gi < count; gi++)
-            switch (k) {
-                case kPgInit: pg_init(a, gi); break;
-                case kPgChi: pg_chi(a, gi); break;
-                case kPgLinearise: pg_linearise(a, gi); break;
-                case kPgAssemble: pg_assemble(a, gi); break;
-                case kPgOffband: pg_offband(a, gi); break;
-                case kPgHp: pg_hp(a, gi); break;
-                case kPgRetract: pg_retract(a, gi); break;
-                case kPgFinish: pg_finish(a, gi); break;
-            }
-        return true;
-    }
-    bool dgrid(PgDirectGridKernel k, int count, const PgArgs& a, const PgDirect& d) {
-        launches++;
-        for (int gi = 0; gi < count; gi++)
-            switch (k) {
-                case kPgZ: pg_z(a, d, gi); break;
-                case kPgWm: pg_wm(a, d, gi); break;
-                case kPgSl: pg_sl(a, d, gi); break;
-                case kPgKs: pg_ks(a, d, gi); break;
-                case kPgZw: pg_zw(a, d, gi); break;
-                case kPgResid: pg_resid(a, d, gi); break;
-            }
-        return true;
-    }
-    template <class Body> static void workgroup(Body body) {
-#if defined(ICET_PG_EMU)
-        std::vector<std::thread> th;
-        for (int t = 0; t < kPgThreads; t++) th.emplace_back([&body, t]() { pg_emu_tid = t; body(); });
-        for (auto& t : th) t.join();
-#else
-        body();
-#endif
-    }
-    bool group(PgGroupKernel k, const PgArgs& a) {
-        launches++;
-        static PgShared sh;
-        static PgRed red;
-        workgroup([&]() {
-            switch (k) {
-                case kPgFactor: pg_group_factor(a, sh); break;
-                case kPgPrecond: pg_group_precond(a, sh, red); break;
-                case kPgStep: pg_group_step(a, red); break;
-                case kPgStats: pg_group_stats(a, red); break;
-            }
-        });
-        return true;
-    }
-    bool dgroup(PgDirectGroupKernel k, const PgArgs& a, const PgDirect& d) {
-        launches++;
-        static PgShared sh;
-        workgroup([&]() {
-            switch (k) {
-                case kPgCholW: pg_group_chol(a, d, 0); break;
-                case kPgCholK: pg_group_chol(a, d, 1); break;
-                case kPgBand: pg_group_band(a, d, sh); break;
-                case kPgCapSolve: pg_group_cap_solve(a, d); break;
-            }
-        });
-        return true;
-    }
-    bool scalars(const PgArgs& a, double out[kPgScalars]) { for (int i = 0; i < kPgScalars; i++) out[i] = a.sc[i]; return true; }
-    bool fetch(void* host, const void* dev, size_t bytes) { memcpy(host, dev, bytes); return true; }
-    bool put(void* dev, const void* host, size_t bytes) { memcpy(dev, host, bytes); return true; }
-};
-
-template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return n == 0 || fread(v.data(), sizeof(T), n, f) == n; }
-template <class T> static bool wr(FILE* f, const T* p, size_t n) { return n == 0 || fwrite(p, sizeof(T), n, f) == n; }
+#include "posegraph_host.h"
 
 int main(int argc, char** argv) {
     const bool step = argc == 4 && strcmp(argv[1], "step") == 0;
     if (argc != 3 && !step) { printf("usage: %s [step] IN OUT\n", argv[0]); return 2; }
     if (step) { argv++; argc--; }
-#if defined(ICET_PG_EMU)
-    pthread_barrier_init(&pg_emu_barrier, nullptr, ICET_PG_EMU_THREADS);
-#endif
+    pg_host_start();
     FILE* in = fopen(argv[1], "rb"); FILE* out = fopen(argv[2], "wb");
     if (!in || !out) { printf("cannot open the files\n"); return 2; }
     int32_t count = 0;
     if (fread(&count, 4, 1, in) != 1) return 2;
     for (int gix = 0; gix < count; gix++) {
-        int32_t hd[4]; double tol[3];
-        if (fread(hd, 4, 4, in) != 4 || fread(tol, 8, 3, in) != 3) { printf("short header\n"); return 2; }
-        const int n = hd[0], C = hd[1];
-        const size_t N = (size_t)n, Cc = (size_t)C, E = (size_t)pg::edge_count(n, C);
-        std::vector<float> poses, odo_X, odo_info, clo_X, clo_info;
-        std::vector<int32_t> ci, cj;
-        std::vector<uint8_t> fixed;
-        if (!rd(in, poses, N * 16) || !rd(in, odo_X, (N - 1) * 6) || !rd(in, odo_info, (N - 1) * 36) || !rd(in, ci, Cc) || !rd(in, cj, Cc) || !rd(in, clo_X, Cc * 6) ||
-            !rd(in, clo_info, Cc * 36) || !rd(in, fixed, N)) { printf("short graph\n"); return 2; }
-        if (!pg::closures_ok(n, C, ci.data(), cj.data())) { printf("bad closures\n"); return 2; }
-        icet_pose_graph_options o = pg_default_options();
-        o.gn_iters = hd[2]; o.max_pcg = hd[3]; o.dx_tol = tol[0]; o.damping = tol[1]; o.pcg_tol = tol[2];
-        PgGraph graph;
-        graph.build(n, C, ci.data(), cj.data(), fixed.data());
-        const size_t m = graph.ends.size(), q = 6 * m;
+        HostGraph g;
+        if (!g.read(in)) return 2;
+        const int n = g.n, C = g.C;
+        const size_t N = g.N, Cc = g.Cc, E = g.E, m = g.graph.ends.size(), q = 6 * m;
         if (m > (size_t)kPgDirectMaxEnds) { printf("graph %d has %zu end nodes: above the limit\n", gix, m); return 2; }
-        PgArgs a{};
-        PgDirect dir{};
-        a.N = n; a.C = C; a.E = (int)E;
-        HostAlloc al;
-        const PgGraphDev gd = pg_bind(a, al, graph.items.size());
-        const PgDirectDev dd = pg_bind_direct(a, dir, al, m);
-        if (E) { memcpy(gd.ei, graph.ei.data(), 4 * E); memcpy(gd.ej, graph.ej.data(), 4 * E); }
-        memcpy(gd.off, graph.off.data(), 4 * (N + 1));
-        if (!graph.items.empty()) memcpy(gd.items, graph.items.data(), 4 * graph.items.size());
-        if (m) memcpy(dd.ends, graph.ends.data(), 4 * m);
-        memcpy(dd.end_of, graph.end_of.data(), 4 * N);
-        // the caller's arrays and the outputs at their exact sizes too
-        std::unique_ptr<float[]> h_poses(new float[N * 16]), h_oX(new float[(N - 1) * 6]), h_oI(new float[(N - 1) * 36]), h_cX(new float[Cc * 6]), h_cI(new float[Cc * 36]),
-            h_out(new float[N * 16]);
-        std::unique_ptr<double[]> h_p64(new double[N * 12]), h_chi(new double[2 * E]);
-        memcpy(h_poses.get(), poses.data(), 4 * N * 16);
-        if (N > 1) { memcpy(h_oX.get(), odo_X.data(), 4 * (N - 1) * 6); memcpy(h_oI.get(), odo_info.data(), 4 * (N - 1) * 36); }
-        if (Cc) { memcpy(h_cX.get(), clo_X.data(), 4 * Cc * 6); memcpy(h_cI.get(), clo_info.data(), 4 * Cc * 36); }
-        a.poses_in = h_poses.get(); a.odo_X = h_oX.get(); a.odo_info = h_oI.get(); a.clo_X = h_cX.get(); a.clo_info = h_cI.get();
-        a.poses_out = h_out.get(); a.poses64_out = h_p64.get(); a.edge_chi2_out = h_chi.get();
+        HostBound b(g, true, true);
         HostBackend be;
         if (step) {
             int32_t K = 0;
@@ -169,13 +35,13 @@ int main(int argc, char** argv) {
             // every output at its exact size, NaN where the run writes nothing
             const size_t sizes[14] = {N * 36, N * 36, Cc * 36, N * 6, N * 6 * q, q * q, q * q, q * q, q * q, N * 6, N * 6, N * 12, E, (size_t)K * N * 6};
             std::vector<std::unique_ptr<double[]>> arr;
-            for (size_t sz : sizes) { arr.emplace_back(new double[sz]); for (size_t i = 0; i < sz; i++) arr.back()[i] = std::nan(""); }
+            for (size_t sz : sizes) arr.push_back(nan_block(sz));
             std::unique_ptr<int32_t[]> ends(new int32_t[m]);
             icet_pose_graph_direct_step so{};
             so.D = arr[0].get(); so.B = arr[1].get(); so.A = arr[2].get(); so.g = arr[3].get(); so.Z = arr[4].get(); so.Wm = arr[5].get(); so.L = arr[6].get(); so.Ks = arr[7].get();
             so.Lk = arr[8].get(); so.x0 = arr[9].get(); so.x = arr[10].get(); so.Pt = arr[11].get(); so.chi_trial = arr[12].get(); so.q = arr[13].get();
             so.ends = ends.get(); so.ends_capacity = (int32_t)m;
-            if (!pg_debug_direct_step(be, a, dir, o, K, p.data(), &so)) { printf("the hook failed\n"); return 1; }
+            if (!pg_debug_direct_step(be, b.a, b.dir, g.o, K, p.data(), &so)) { printf("the hook failed\n"); return 1; }
             printf("graph %d: n %d C %d, %d end nodes: factor %d, Wm %d, Ks %d, %d band solves, chi2 %.6e -> %.6e, max dx %.3e, %ld launches\n", gix, n, C, so.m, so.factor_status,
                    so.wm_status, so.ks_status, so.band_solves, so.chi2_start, so.chi2_trial, so.max_dx, be.launches);
             const int32_t oh[8] = {so.m, so.factor_status, so.wm_status, so.ks_status, so.band_solves, so.trial, 0, 0};
@@ -185,12 +51,12 @@ int main(int argc, char** argv) {
             continue;
         }
         icet_pose_graph_result res{};
-        if (!pg_optimise_direct(be, a, dir, o, &res)) { printf("the driver failed\n"); return 1; }
+        if (!pg_optimise_direct(be, b.a, b.dir, g.o, &res)) { printf("the driver failed\n"); return 1; }
         printf("graph %d: n %d C %d, %zu end nodes: status %d, %d iterations, %d band solves, chi2 %.6e -> %.6e, max dx %.3e, %ld launches\n", gix, n, C, m,
                res.status, res.gn_iterations, res.pcg_iterations, res.chi2_initial, res.chi2_final, res.max_dx, be.launches);
         const int32_t oh[4] = {res.status, res.gn_iterations, res.pcg_iterations, res.solver};
         const double od[3] = {res.chi2_initial, res.chi2_final, res.max_dx};
-        if (!wr(out, oh, 4) || !wr(out, od, 3) || !wr(out, h_out.get(), N * 16) || !wr(out, h_p64.get(), N * 12) || !wr(out, h_chi.get(), 2 * E)) { printf("write failed\n"); return 2; }
+        if (!wr(out, oh, 4) || !wr(out, od, 3) || !wr(out, b.poses_out.get(), N * 16) || !wr(out, b.poses64.get(), N * 12) || !wr(out, b.edge_chi2.get(), 2 * E)) { printf("write failed\n"); return 2; }
     }
     fclose(in);
     if (fclose(out) != 0) return 2;

@@ -147,15 +147,13 @@ def test_limits(ctx):
         _run(ctx, g, solver="direct")
     assert e.value.status == api.ICET_ERR_UNSUPPORTED and "138" in str(e.value) and "128" in str(e.value)
     # the outputs untouched: the raw call with sentinel buffers
-    n = g["poses"].shape[0]
-    P = np.ascontiguousarray(g["poses"], np.float32).reshape(n, 16); oX = np.ascontiguousarray(g["odo_X"], np.float32); oI = np.ascontiguousarray(g["odo_info"], np.float32)
-    ci, cj, cX, cI, _, opt = ctx._pose_graph_host_args(n, g["closures"], None, 10, pc.DX_TOL, 0.0, 0, 0.0)
-    out = np.full((n, 16), 7.0, np.float32); p64 = np.full((n, 12), 7.0); chi = np.full((2, n - 1 + ci.shape[0]), 7.0); res = api.PoseGraphResult()
+    pg = ctx._pose_graph_host(g["poses"], g["odo_X"], g["odo_info"], g["closures"], None); n = pg.n
+    opt = api.PoseGraphOptions(10, 0, pc.DX_TOL, 0.0, 0.0)
+    out = np.full((n, 16), 7.0, np.float32); p64 = np.full((n, 12), 7.0); chi = np.full((2, n - 1 + pg.nc), 7.0); res = api.PoseGraphResult()
     res.status = -5
     ctx.set_option("pg_solver", 1)
     try:
-        s = icet_amd.load_library().icet_pose_graph_optimize(ctx._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data,
-                                                             cX.ctypes.data, cI.ctypes.data, None, C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data, C.byref(res))
+        s = icet_amd.load_library().icet_pose_graph_optimize(*pg.args, C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data, C.byref(res))
     finally:
         ctx.set_option("pg_solver", 0)
     assert s == api.ICET_ERR_UNSUPPORTED and (out == 7.0).all() and (p64 == 7.0).all() and (chi == 7.0).all() and res.status == -5

@@ -101,14 +101,11 @@ def test_over_the_limit(ctx):
     import ctypes as C
     import icet_amd
     lib = icet_amd.load_library()
-    P = np.ascontiguousarray(g["poses"], np.float32).reshape(n, 16)
-    oX = np.ascontiguousarray(g["odo_X"], np.float32); oI = np.ascontiguousarray(g["odo_info"], np.float32)
-    ci, cj, cX, cI, _, _ = ctx._pose_graph_host_args(n, g["closures"], None, 1, 0.0, 0.0, 0, 0.0)
+    pg = ctx._pose_graph_host(g["poses"], g["odo_X"], g["odo_info"], g["closures"], None)
     for solver in ("cg", "direct", "auto"):
         with ctx._pose_graph_solver(solver):
             cov = np.full((n, 36), 7.0); res = api.PoseGraphMarginalsResult(5, 5, 5, 5, 5, 5)
-            st = lib.icet_pose_graph_marginals(ctx._h, n, P.ctypes.data, oX.ctypes.data, oI.ctypes.data, ci.shape[0], ci.ctypes.data, cj.ctypes.data, cX.ctypes.data,
-                                               cI.ctypes.data, None, cov.ctypes.data, C.byref(res))
+            st = lib.icet_pose_graph_marginals(*pg.args, cov.ctypes.data, C.byref(res))
             assert st == api.ICET_ERR_UNSUPPORTED and (cov == 7.0).all() and res.status == 5 and res.reserved == 5
 
 

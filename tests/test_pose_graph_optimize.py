@@ -137,6 +137,32 @@ def test_refusals(ctx):
         assert e.value.status == api.ICET_ERR_BAD_ARG
 
 
+PG_METHODS = ["optimize_pose_graph", "optimize_pose_graph_device", "pose_graph_marginals", "pose_graph_marginals_device", "debug_pose_graph_marginals",
+              "debug_pose_graph_step", "debug_pose_graph_direct"]
+
+
+@pytest.mark.parametrize("method", PG_METHODS)
+def test_every_pose_graph_method_checks_the_graph_alike(ctx, method):
+    """The seven Context methods on a chain of three nodes with the closure (0, 2): odo_X one row short and a ``fixed`` of two entries are ICET_ERR_BAD_ARG from
+    each, the well-formed call ends with status 0 -- the result's status, and every factor's status a hook reports."""
+    import icet_amd
+    from icet_amd import api
+    g = pgm.make_loop(3, [(0, 2)], seed=11)
+    dev = torch.device("cuda", 0)
+    arg = (lambda v: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(dev)) if method.endswith("_device") else (lambda v: v)
+
+    def call(odo_X, fixed):
+        return getattr(ctx, method)(arg(g["poses"]), arg(odo_X), arg(g["odo_info"]), g["closures"], fixed=fixed)
+    for odo_X, fixed in ((g["odo_X"][:-1], None), (g["odo_X"], [0, 0])):
+        with pytest.raises(icet_amd.IcetError) as e:
+            call(odo_X, fixed)
+        assert e.value.status == api.ICET_ERR_BAD_ARG
+    r = call(g["odo_X"], None)
+    statuses = {k: r[k] for k in ("status", "factor_status", "cg_status", "wm_status", "ks_status") if k in r}
+    print(method, statuses)
+    assert statuses and not any(statuses.values())
+
+
 def test_the_optimiser_disturbs_nothing(ctx):
     """A small icet_solve on the same context before and after an optimisation: the same bits."""
     d = np.load(os.path.join(ROOT, "tests", "golden", "scans_frame_804_805.npz"))
