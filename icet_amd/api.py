@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_candidates_appearance_device", "icet_keyframe_store_close_appearance_device",
                     "icet_keyframe_store_enable_coarse", "icet_keyframe_store_coarse_grid_device", "icet_keyframe_store_coarse_align_device",
                     "icet_keyframe_store_close_coarse_device",
-                    "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_debug_pose_graph_step", "icet_debug_pose_graph_direct",
+                    "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_pose_graph_optimize_robust", "icet_pose_graph_optimize_robust_device", "icet_debug_pose_graph_step", "icet_debug_pose_graph_direct",
                     "icet_pose_graph_marginals", "icet_pose_graph_marginals_device", "icet_debug_pose_graph_marginals",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
@@ -137,6 +137,16 @@ class PoseGraphResult(C.Structure):
                 ("pcg_iterations", C.c_int32), ("solver", C.c_int32)]
 
 
+class PoseGraphRobust(C.Structure):
+    """icet_pose_graph_robust (include/icet_hip.h), 16 bytes."""
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("scale", C.c_double)]
+
+
+class PoseGraphRobustResult(C.Structure):
+    """icet_pose_graph_robust_result (include/icet_hip.h), 64 bytes."""
+    _fields_ = [("base", PoseGraphResult), ("cost_initial", C.c_double), ("cost_final", C.c_double), ("downweighted", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PoseGraphStep(C.Structure):
     """icet_pose_graph_step (include/icet_hip.h), 152 bytes."""
     ARRAYS = ("J", "res", "chi_start", "chi_trial", "D", "B", "A", "g", "x", "Pt", "q", "cg_scalars")
@@ -165,6 +175,11 @@ class PoseGraphMarginalsDebug(C.Structure):
 
 assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40 and C.sizeof(PoseGraphStep) == 152 and C.sizeof(PoseGraphDirectStep) == 176
 assert C.sizeof(PoseGraphMarginalsResult) == 24 and C.sizeof(PoseGraphMarginalsDebug) == 80
+assert C.sizeof(PoseGraphRobust) == 16 and C.sizeof(PoseGraphRobustResult) == 64
+# icet_pose_graph_robust: the kinds by name, flag bit 0, the default threshold (the 99 % quantile of chi2 with six degrees of freedom)
+PG_ROBUST_KINDS = {"huber": 1, "cauchy": 2, "geman_mcclure": 3}
+PG_ROBUST_ODOMETRY = 1
+PG_ROBUST_DEFAULT_SCALE = 16.8119
 # option "pg_solver": the pose-graph optimiser's linear solve
 PG_SOLVER_CG, PG_SOLVER_DIRECT, PG_SOLVER_AUTO = range(3)
 PG_SOLVERS = {"cg": PG_SOLVER_CG, "direct": PG_SOLVER_DIRECT, "auto": PG_SOLVER_AUTO}
@@ -187,6 +202,30 @@ def pose_graph_ends(n, closures, fixed=None):
 PG_CG_TOLERANCE, PG_CG_ZERO, PG_CG_CAP, PG_CG_FAILED = range(4)
 # icet_pose_graph_result.status
 POSE_GRAPH_CONVERGED, POSE_GRAPH_ITERATION_CAP, POSE_GRAPH_NOT_POSITIVE_DEFINITE, POSE_GRAPH_NON_FINITE, POSE_GRAPH_STALLED = range(5)
+
+
+def _closure_weights(closures, weights, n):
+    closures = list(closures)
+    w = np.asarray(weights, np.float64).reshape(-1)
+    if n is None and w.shape[0] == len(closures):
+        return closures, w
+    if n is not None and w.shape[0] == int(n) - 1 + len(closures):
+        return closures, w[int(n) - 1:]
+    raise IcetError(ICET_ERR_BAD_ARG, "weights must hold one entry per closure, or with n the n - 1 + C entries of a result's edge_weight")
+
+
+def reweighted_closures(closures, weights, n=None):
+    """``closures`` ((i, j, X, info) tuples) with every information matrix scaled by its closure's final weight.  ``weights`` is one entry per closure; or,
+    with ``n`` the number of poses, the ``edge_weight`` of a robust optimize_pose_graph (n - 1 + C entries: the closures' are the last).  Any other length is
+    refused.  Context.pose_graph_marginals on the result gives the covariances at the robust optimum: H there is sum w_e J^T Omega J."""
+    closures, w = _closure_weights(closures, weights, n)
+    return [(c[0], c[1], c[2], (np.asarray(c[3], np.float64) * wi).astype(np.float32)) for c, wi in zip(closures, w)]
+
+
+def inlier_closures(closures, weights, min_weight=0.5, n=None):
+    """The closures whose final weight is at least ``min_weight`` (``weights`` and ``n`` as in reweighted_closures): what a robust run kept."""
+    closures, w = _closure_weights(closures, weights, n)
+    return [c for c, wi in zip(closures, w) if wi >= min_weight]
 
 
 def pose_stds(cov):
@@ -337,6 +376,10 @@ def load_library():
     L.icet_pose_graph_optimize.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(PoseGraphOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseGraphResult)]
     L.icet_pose_graph_optimize_device.argtypes = L.icet_pose_graph_optimize.argtypes
+    L.icet_pose_graph_optimize_robust.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(PoseGraphOptions), C.POINTER(PoseGraphRobust), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(PoseGraphRobustResult)]
+    L.icet_pose_graph_optimize_robust_device.argtypes = L.icet_pose_graph_optimize_robust.argtypes
     L.icet_debug_pose_graph_direct.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(PoseGraphOptions), C.c_int32, C.c_void_p, C.POINTER(PoseGraphDirectStep)]
     L.icet_pose_graph_marginals.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -736,24 +779,55 @@ class Context:
         return dict(chi2_initial=float(res.chi2_initial), chi2_final=float(res.chi2_final), status=int(res.status), gn_iterations=int(res.gn_iterations),
                     max_dx=float(res.max_dx), pcg_iterations=int(res.pcg_iterations), solver=int(res.solver))
 
+    @staticmethod
+    def _pose_graph_robust(robust, robust_scale=None, robust_odometry=False):
+        """icet_pose_graph_robust of the three keyword arguments of the optimiser calls (``robust`` a name of PG_ROBUST_KINDS)."""
+        if robust not in PG_ROBUST_KINDS:
+            raise IcetError(ICET_ERR_BAD_ARG, 'robust must be None, "huber", "cauchy" or "geman_mcclure"')
+        scale = PG_ROBUST_DEFAULT_SCALE if robust_scale is None else float(robust_scale)
+        if not (scale > 0.0 and np.isfinite(scale)):
+            raise IcetError(ICET_ERR_BAD_ARG, "robust_scale must be finite and positive")
+        return PoseGraphRobust(PG_ROBUST_KINDS[robust], PG_ROBUST_ODOMETRY if robust_odometry else 0, scale)
+
+    @classmethod
+    def _pose_graph_robust_result(cls, res):
+        return dict(cls._pose_graph_result(res.base), cost_initial=float(res.cost_initial), cost_final=float(res.cost_final), downweighted=int(res.downweighted))
+
     def optimize_pose_graph(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0, solver=None,
-                            covariances=False):
+                            covariances=False, robust=None, robust_scale=None, robust_odometry=False):
         """icet_pose_graph_optimize: the poses (n x 4 x 4 float32) of a chain with odometry measurements ``odo_X`` ((n - 1) x 6) and information ``odo_info``
         ((n - 1) x 6 x 6) and the closure edges ``closures`` = (i, j, X, info) tuples as closure_edges returns them, optimised on the device.  Node 0 and the
         nodes with ``fixed[k] != 0`` stay.  Returns dict(poses n x 4 x 4 float32, poses64 n x 4 x 4, chi2_initial, chi2_final, status (POSE_GRAPH_*),
         gn_iterations, max_dx, edge_chi2 2 x E, pcg_iterations, solver).  A status of 2 or 3 is a result, not an error: the poses are then the inputs.
         ``solver``: None (the context's option "pg_solver"), "cg", "direct" or "auto" for this call; the result's ``solver`` is 1 when the direct solve ran --
         it ignores max_pcg and pcg_tol, and converges at the defaults where the closures' information is strong (closures from find_closures: use "auto").
-        ``covariances``: True adds ``cov`` (n x 6 x 6) and ``cov_status``, pose_graph_marginals at the returned float32 poses."""
+        ``covariances``: True adds ``cov`` (n x 6 x 6) and ``cov_status``, pose_graph_marginals at the returned float32 poses.
+        ``robust``: None, or "huber", "cauchy", "geman_mcclure": icet_pose_graph_optimize_robust, iteratively reweighted least squares with the threshold
+        ``robust_scale`` in chi2 units (None: PG_ROBUST_DEFAULT_SCALE) on the closures, with ``robust_odometry`` on the odometry edges too.  The result then
+        also has ``edge_weight`` (E: every edge's final weight), ``cost_initial``, ``cost_final`` (the robust objective; chi2_* stay the raw sums) and
+        ``downweighted`` (the edges whose weight is below 0.5); its covariances are taken with the closures' information scaled by their weights
+        (reweighted_closures; robust odometry weights are not applied there)."""
         closures = list(closures)
         g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed); n = g.n
         opt = PoseGraphOptions(int(gn_iters), int(max_pcg), float(dx_tol), float(damping), float(pcg_tol))
-        out = np.zeros((n, 16), np.float32); p64 = np.zeros((n, 12), np.float64); chi = np.zeros((2, n - 1 + g.nc), np.float64); res = PoseGraphResult()
-        with self._pose_graph_solver(solver):
-            self._check(load_library().icet_pose_graph_optimize(*g.args, C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data, C.byref(res)))
+        out = np.zeros((n, 16), np.float32); p64 = np.zeros((n, 12), np.float64); chi = np.zeros((2, n - 1 + g.nc), np.float64)
+        if robust is None:
+            res = PoseGraphResult()
+            with self._pose_graph_solver(solver):
+                self._check(load_library().icet_pose_graph_optimize(*g.args, C.byref(opt), out.ctypes.data, p64.ctypes.data, chi.ctypes.data, C.byref(res)))
+            r = self._pose_graph_result(res)
+        else:
+            rob = self._pose_graph_robust(robust, robust_scale, robust_odometry)
+            wt = np.zeros(n - 1 + g.nc, np.float64); res = PoseGraphRobustResult()
+            with self._pose_graph_solver(solver):
+                self._check(load_library().icet_pose_graph_optimize_robust(*g.args, C.byref(opt), C.byref(rob), out.ctypes.data, p64.ctypes.data, chi.ctypes.data,
+                                                                           wt.ctypes.data, C.byref(res)))
+            r = dict(self._pose_graph_robust_result(res), edge_weight=wt)
         T64 = np.zeros((n, 4, 4)); T64[:, 3, 3] = 1.0; T64[:, :3, :3] = p64[:, :9].reshape(n, 3, 3); T64[:, :3, 3] = p64[:, 9:]
-        r = dict(self._pose_graph_result(res), poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
+        r = dict(r, poses=out.reshape(n, 4, 4), poses64=T64, edge_chi2=chi)
         if covariances:
+            if robust is not None:
+                closures = reweighted_closures(closures, r["edge_weight"], n=n)
             mg = self.pose_graph_marginals(r["poses"], odo_X, odo_info, closures, fixed=fixed)
             r["cov"] = mg["cov"]; r["cov_status"] = mg["status"]
         return r
@@ -840,20 +914,32 @@ class Context:
         return dict(out, ends=ends, **arr)
 
     def optimize_pose_graph_device(self, poses, odo_X, odo_info, closures=(), fixed=None, gn_iters=10, dx_tol=1e-7, damping=0.0, max_pcg=0, pcg_tol=0.0,
-                                   clo_X=None, clo_info=None, solver=None):
+                                   clo_X=None, clo_info=None, solver=None, robust=None, robust_scale=None, robust_odometry=False):
         """icet_pose_graph_optimize_device for torch tensors on this context's device: ``poses`` n x 4 x 4, ``odo_X`` (n - 1) x 6, ``odo_info`` (n - 1) x 6 x 6,
         float32 and contiguous.  ``closures`` as in optimize_pose_graph (their X and info are uploaded), or (i, j) pairs with ``clo_X`` C x 6 and ``clo_info``
         C x 6 x 6 as float32 tensors.  Returns the dict of optimize_pose_graph with poses (float32), poses64 (n x 12 float64: R row-major, then t) and edge_chi2
-        (2 x E float64) as tensors on the device.  ``solver`` as in optimize_pose_graph.  The call returns when the result is known."""
+        (2 x E float64) as tensors on the device.  ``solver`` as in optimize_pose_graph.  The call returns when the result is known.
+        ``robust``, ``robust_scale``, ``robust_odometry`` as in optimize_pose_graph: icet_pose_graph_optimize_robust_device; ``edge_weight`` (E float64) is then
+        a tensor on the device."""
         import torch
         g = self._pose_graph_device(poses, odo_X, odo_info, closures, fixed, clo_X, clo_info); n = g.n
         opt = PoseGraphOptions(int(gn_iters), int(max_pcg), float(dx_tol), float(damping), float(pcg_tol))
         out = torch.zeros((n, 4, 4), dtype=torch.float32, device=poses.device); p64 = torch.zeros((n, 12), dtype=torch.float64, device=poses.device)
-        chi = torch.zeros((2, n - 1 + g.nc), dtype=torch.float64, device=poses.device); res = PoseGraphResult()
+        chi = torch.zeros((2, n - 1 + g.nc), dtype=torch.float64, device=poses.device)
+        rob = None if robust is None else self._pose_graph_robust(robust, robust_scale, robust_odometry)
+        wt = None if robust is None else torch.zeros(n - 1 + g.nc, dtype=torch.float64, device=poses.device)
         torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
+        outs = (_vp(out.data_ptr()), _vp(p64.data_ptr()), _vp(chi.data_ptr()))
         with self._pose_graph_solver(solver):
-            self._check(load_library().icet_pose_graph_optimize_device(*g.args, C.byref(opt), _vp(out.data_ptr()), _vp(p64.data_ptr()), _vp(chi.data_ptr()), C.byref(res)))
-        return dict(self._pose_graph_result(res), poses=out, poses64=p64, edge_chi2=chi)
+            if robust is None:
+                res = PoseGraphResult()
+                self._check(load_library().icet_pose_graph_optimize_device(*g.args, C.byref(opt), *outs, C.byref(res)))
+                r = self._pose_graph_result(res)
+            else:
+                res = PoseGraphRobustResult()
+                self._check(load_library().icet_pose_graph_optimize_robust_device(*g.args, C.byref(opt), C.byref(rob), *outs, _vp(wt.data_ptr()), C.byref(res)))
+                r = dict(self._pose_graph_robust_result(res), edge_weight=wt)
+        return dict(r, poses=out, poses64=p64, edge_chi2=chi)
 
     def debug_fix(self, values):
         """icet_debug_fix (test hook): n floats through the point pass's float -> 2^36 fixed-point conversions -> (n, 3) uint64 = to_fix_biased (defined for

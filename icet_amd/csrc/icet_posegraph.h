@@ -95,6 +95,35 @@ ICET_PG_HD inline void jacobian_column(const double Pi[12], const double Pj[12],
     for (int a = 3; a < 6; a++) out[a] = wrap_pi(xp[a] - xm[a]) / (2.0 * kJacStep);
 }
 
+// ---- robust kernels (DESIGN.md section 20 "Robust kernels") --------------------------------------------------------------------------------------------------
+// Per edge s = e^T Omega e, c > 0 the threshold in chi2 units: the objective is F = sum rho(s), an edge's weight in H and g is w(s) = rho'(s).  Where !(s > 0)
+// every kind has rho = s and w = 1 (a NaN s stays a NaN cost).  tests/pose_graph_robust_model.py restates each expression in this order of operations.
+enum RobustKind { kRobustNone = 0, kRobustHuber = 1, kRobustCauchy = 2, kRobustGemanMcClure = 3 };
+constexpr int kRobustOdometry = 1;                    // flag bit 0 (ICET_PG_ROBUST_ODOMETRY): the odometry edges take the kind too
+constexpr double kRobustDefaultScale = 16.8119;       // the 99 % quantile of chi2 with six degrees of freedom
+
+ICET_PG_HD inline double robust_rho(int kind, double c, double s) {
+    if (!(s > 0.0)) return s;
+    if (kind == kRobustHuber) return s <= c ? s : 2.0 * sqrt(c * s) - c;
+    if (kind == kRobustCauchy) return c * log1p(s / c);
+    if (kind == kRobustGemanMcClure) return c * s / (c + s);
+    return s;
+}
+ICET_PG_HD inline double robust_weight(int kind, double c, double s) {
+    if (!(s > 0.0)) return 1.0;
+    if (kind == kRobustHuber) return s <= c ? 1.0 : sqrt(c / s);
+    if (kind == kRobustCauchy) return 1.0 / (1.0 + s / c);
+    if (kind == kRobustGemanMcClure) { const double t = c / (c + s); return t * t; }
+    return 1.0;
+}
+// The kind edge e of a chain of N nodes takes: the closures always, the odometry edges (e < N - 1) only under kRobustOdometry
+ICET_PG_HD inline int robust_kind_of_edge(int kind, int flags, int N, int e) { return (e >= N - 1 || (flags & kRobustOdometry)) ? kind : (int)kRobustNone; }
+// (host) true for a (kind, flags, scale) the optimiser takes: kind 0 .. 3, no flag bit but bit 0, and with a kind a scale that is finite and positive
+inline bool robust_ok(int kind, int flags, double scale) {
+    if (kind < kRobustNone || kind > kRobustGemanMcClure || (flags & ~kRobustOdometry) != 0) return false;
+    return kind == kRobustNone || (scale > 0.0 && scale <= 1.7976931348623157e308);
+}
+
 ICET_PG_HD inline int edge_count(int N, int C) { return N - 1 + C; }
 
 // (host) true when the closure list is one the optimiser takes: indices in range, i != j

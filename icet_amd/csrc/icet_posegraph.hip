@@ -7,7 +7,8 @@
 // thing on plain global arrays, every body in icet_posegraph_body.h, driven from the host by icet_posegraph_driver.h.  No kernel waits on another block.
 // Option "pg_solver" replaces the conjugate gradients by a direct solve over the closures' end nodes (icet_posegraph_direct.h): k_pg_z solves the band for
 // all their unit columns in one launch, one thread per column.  icet_pose_graph_marginals[_device] reads the marginal covariance of every pose off that solve's
-// Z, L and Lk and a selected inverse of the band (icet_posegraph_marginals.h).
+// Z, L and Lk and a selected inverse of the band (icet_posegraph_marginals.h).  icet_pose_graph_optimize_robust[_device] runs the same optimiser under a
+// robust kernel (icet_posegraph_robust.h): three small kernels around the unchanged ones.
 #include "icet_ctx.h"
 #include "icet_posegraph_driver.h"
 
@@ -46,6 +47,9 @@ ICET_PG_GRID_KERNEL(k_pg_resid, pg_resid(a, d, gi), PgArgs a, PgDirect d)
 // the marginal covariances (icet_posegraph_marginals.h)
 ICET_PG_GRID_KERNEL(k_pg_selinv_prep, pg_selinv_prep(a, mg, gi), PgArgs a, PgMarg mg)
 ICET_PG_GRID_KERNEL(k_pg_marg_lt, pg_marg_lt(a, d, mg, gi), PgArgs a, PgDirect d, PgMarg mg)
+// the robust kernels (icet_posegraph_robust.h)
+ICET_PG_GRID_KERNEL(k_pg_robust_scale, pg_robust_scale(a, r, gi), PgArgs a, PgRobust r)
+ICET_PG_GRID_KERNEL(k_pg_robust_finish, pg_robust_finish(a, r, gi), PgArgs a, PgRobust r)
 #undef ICET_PG_GRID_KERNEL
 
 // one-workgroup kernels
@@ -56,6 +60,7 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_stats(PgArgs a) { __shared__ 
 __global__ __launch_bounds__(kPgThreads) void k_pg_chol(PgArgs a, PgDirect d, int which) { pg_group_chol(a, d, which); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_band(PgArgs a, PgDirect d) { __shared__ PgShared sh; pg_group_band(a, d, sh); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_cap_solve(PgArgs a, PgDirect d) { pg_group_cap_solve(a, d); }
+__global__ __launch_bounds__(kPgThreads) void k_pg_robust_stats(PgArgs a, PgRobust r) { __shared__ PgRed red; pg_group_robust_stats(a, r, red); }
 // k_pg_selinv is the marginals' sequential part; k_pg_marg runs one workgroup per node
 __global__ __launch_bounds__(kPgThreads) void k_pg_selinv(PgArgs a, PgMarg mg) { __shared__ PgShared sh; pg_group_selinv(a, mg, sh); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_marg(PgArgs a, PgDirect d, PgMarg mg) { __shared__ PgMargShared sh; pg_group_marg(a, d, mg, (int)blockIdx.x, sh); }
@@ -135,12 +140,25 @@ struct PgDeviceBackend {
         }
         return false;
     }
+    bool rgrid(PgRobustGridKernel k, int count, const PgArgs& a, const PgRobust& r) {
+        switch (k) {
+            case kPgRobustScale:  return launch(k_pg_robust_scale, blocks_for(count), kPgGridThreads, a, r, count);
+            case kPgRobustFinish: return launch(k_pg_robust_finish, blocks_for(count), kPgGridThreads, a, r, count);
+        }
+        return false;
+    }
+    bool rgroup(PgRobustGroupKernel k, const PgArgs& a, const PgRobust& r) {
+        switch (k) {
+            case kPgRobustStats: return launch(k_pg_robust_stats, 1, kPgThreads, a, r);
+        }
+        return false;
+    }
     bool scalars(const PgArgs& a, double out[kPgScalars]) {
         if (!ok(hipMemcpyAsync(h_sc, a.sc, sizeof(double) * kPgScalars, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
         for (int i = 0; i < kPgScalars; i++) out[i] = h_sc[i];
         return true;
     }
-    // (the test hook's copies: pageable host memory, complete on return)
+    // (the test hooks' copies, and the robust run's weights at its end: pageable host memory, complete on return)
     bool fetch(void* host, const void* dev, size_t bytes) { return ok(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream)) && ok(hipStreamSynchronize(stream)); }
     bool put(void* dev, const void* host, size_t bytes) { return ok(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream)) && ok(hipStreamSynchronize(stream)); }
 };
@@ -171,8 +189,9 @@ struct PgFrame {
     PgProblem pb;
     PgGraph graph; int m_ends = 0;          // (from the checks on)
     // the plan: the work arrays bound beyond pg_bind's, and with host_io the outputs staged in the block (a.poses_out, a.poses64_out, a.edge_chi2_out; null otherwise)
-    bool direct = false, marg = false, stage_poses_out = false, stage_poses64 = false, stage_chi2 = false;
-    PgArgs a{}; PgDirect dir{}; PgMarg mg{};
+    // robust: the robust run's own arrays (a run with a kind); stage_weight: with host_io its edge weights staged in the block (rb.weight_out)
+    bool direct = false, marg = false, stage_poses_out = false, stage_poses64 = false, stage_chi2 = false, robust = false, stage_weight = false;
+    PgArgs a{}; PgDirect dir{}; PgMarg mg{}; PgRobust rb{};
     PgDeviceBackend be;
     hipError_t e = hipSuccess;              // the first failure of a copy or of the backend
     PgFrame(icet_ctx* c_, const char* name_, bool host_io_, const PgProblem& pb_) : c(c_), name(name_), host_io(host_io_), pb(pb_) {}
@@ -182,7 +201,7 @@ struct PgFrame {
 
 // THE frame of every pose-graph entry: the checks of the problem (outputs_ok: the entry's own output pointers are there), the graph, then plan() -- the entry's
 // own checks behind the graph's, and f's plan --, ONE device block for everything bound and staged, the uploads, body() -- the driver's call and f.down() of
-// what goes back; false for a failure of the backend --, the synchronisation and the error mapping.  The block's order: pg_bind | direct | marginals | staging,
+// what goes back; false for a failure of the backend --, the synchronisation and the error mapping.  The block's order: pg_bind | direct | marginals | robust | staging,
 // the doubles first.  A local BufferGroup owns the block and the pinned scalars: every return frees through it.
 template <class Plan, class Body>
 icet_status pg_run(PgFrame& f, bool outputs_ok, Plan&& plan, Body&& body) {
@@ -211,11 +230,13 @@ icet_status pg_run(PgFrame& f, bool outputs_ok, Plan&& plan, Body&& body) {
         gd = pg_bind(a, arena, n_items);
         if (f.direct) { arena.align8(); dd = pg_bind_direct(a, f.dir, arena, m); }
         if (f.marg) { arena.align8(); pg_bind_marg(a, f.dir, f.mg, arena, f.host_io); }
+        if (f.robust) { arena.align8(); pg_bind_robust(a, f.rb, arena); }
         a.poses_out = nullptr; a.poses64_out = nullptr; a.edge_chi2_out = nullptr;
         if (f.host_io) {
             arena.align8();          // (int32 lists end on a multiple of 4 bytes; the doubles of the staging need 8)
             if (f.stage_poses64) a.poses64_out = arena.d(N * 12);
             if (f.stage_chi2) a.edge_chi2_out = arena.d(2 * E);
+            if (f.stage_weight) f.rb.weight_out = arena.d(E);
             s_poses = arena.f(N * 16); s_odo_X = arena.f((N - 1) * 6); s_odo_info = arena.f((N - 1) * 36); s_clo_X = arena.f(C * 6); s_clo_info = arena.f(C * 36);
             if (f.stage_poses_out) a.poses_out = arena.f(N * 16);
         }
@@ -253,15 +274,15 @@ icet_status pg_run(PgFrame& f, bool outputs_ok, Plan&& plan, Body&& body) {
 constexpr const char* kPgOptimiseName = "icet_pose_graph_optimize";
 
 // The options (null: the defaults), the first check of every optimiser plan
-icet_status pg_options(icet_ctx* c, const icet_pose_graph_options* opt, icet_pose_graph_options* o) {
+icet_status pg_options(icet_ctx* c, const icet_pose_graph_options* opt, icet_pose_graph_options* o, const char* name = kPgOptimiseName) {
     *o = opt ? *opt : pg_default_options();
-    if (o->gn_iters < 1) { c->err = "icet_pose_graph_optimize: gn_iters < 1"; return ICET_ERR_BAD_ARG; }
+    if (o->gn_iters < 1) { c->err = std::string(name) + ": gn_iters < 1"; return ICET_ERR_BAD_ARG; }
     return ICET_OK;
 }
 // The direct solve's limit on the end nodes
-icet_status pg_direct_limit(icet_ctx* c, int m_ends) {
+icet_status pg_direct_limit(icet_ctx* c, int m_ends, const char* name = kPgOptimiseName) {
     if (m_ends <= kPgDirectMaxEnds) return ICET_OK;
-    c->err = "icet_pose_graph_optimize: the direct solve takes at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " +
+    c->err = std::string(name) + ": the direct solve takes at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " +
              std::to_string(m_ends) + " (option pg_solver 2 falls back to conjugate gradients)";
     return ICET_ERR_UNSUPPORTED;
 }
@@ -272,25 +293,58 @@ icet_status pg_ends_capacity(icet_ctx* c, const char* hook, int32_t capacity, in
     return ICET_ERR_BAD_ARG;
 }
 
-// The linear solve is the context's option "pg_solver": 0 conjugate gradients, 1 the direct solve, 2 the direct solve where the graph has end nodes within its limit.
+// The plan of an optimiser run, plain or robust: the options, then the linear solve by the context's option "pg_solver" (0 conjugate gradients, 1 the direct
+// solve, 2 the direct solve where the graph has end nodes within its limit), then the three outputs staged.
+icet_status pg_optimise_plan(PgFrame& f, const icet_pose_graph_options* opt, icet_pose_graph_options* o, const double* poses64_out, const double* edge_chi2) {
+    icet_ctx* c = f.c;
+    ICET_TRY(pg_options(c, opt, o, f.name));
+    if (c->pg_solver == 1) ICET_TRY(pg_direct_limit(c, f.m_ends, f.name));
+    f.direct = c->pg_solver == 1 || (c->pg_solver == 2 && f.m_ends >= 1 && f.m_ends <= kPgDirectMaxEnds);
+    f.stage_poses_out = true; f.stage_poses64 = poses64_out != nullptr; f.stage_chi2 = edge_chi2 != nullptr;
+    return ICET_OK;
+}
+
 icet_status pg_optimise_entry(icet_ctx* c, bool host_io, const PgProblem& pb, const icet_pose_graph_options* opt, float* poses_out, double* poses64_out,
                               double* edge_chi2, icet_pose_graph_result* result) {
     PgFrame f(c, kPgOptimiseName, host_io, pb);
     icet_pose_graph_options o;
     icet_pose_graph_result res{};
     ICET_TRY(pg_run(f, poses_out && result,
-        [&]() {
-            ICET_TRY(pg_options(c, opt, &o));
-            if (c->pg_solver == 1) ICET_TRY(pg_direct_limit(c, f.m_ends));
-            f.direct = c->pg_solver == 1 || (c->pg_solver == 2 && f.m_ends >= 1 && f.m_ends <= kPgDirectMaxEnds);
-            f.stage_poses_out = true; f.stage_poses64 = poses64_out != nullptr; f.stage_chi2 = edge_chi2 != nullptr;
-            return ICET_OK;
-        },
+        [&]() { return pg_optimise_plan(f, opt, &o, poses64_out, edge_chi2); },
         [&]() {
             const size_t N = (size_t)f.a.N, E = (size_t)f.a.E;
             if (!host_io) { f.a.poses_out = poses_out; f.a.poses64_out = poses64_out; f.a.edge_chi2_out = edge_chi2; }
             if (!(f.direct ? pg_optimise_direct(f.be, f.a, f.dir, o, &res) : pg_optimise(f.be, f.a, o, f.graph.c_offband, &res))) return false;
             if (host_io) { f.down(poses_out, f.a.poses_out, sizeof(float) * N * 16); f.down(poses64_out, f.a.poses64_out, sizeof(double) * N * 12); f.down(edge_chi2, f.a.edge_chi2_out, sizeof(double) * 2 * E); }
+            return true;
+        }));
+    *result = res;
+    return ICET_OK;
+}
+
+// ---- the robust run: icet_pose_graph_optimize_robust[_device].  The plan of pg_optimise_entry, the robust arrays bound with a kind, the weights staged. -----------
+icet_status pg_robust_entry(icet_ctx* c, bool host_io, const PgProblem& pb, const icet_pose_graph_options* opt, const icet_pose_graph_robust* robust, float* poses_out,
+                            double* poses64_out, double* edge_chi2, double* edge_weight, icet_pose_graph_robust_result* result) {
+    constexpr const char* kName = "icet_pose_graph_optimize_robust";
+    PgFrame f(c, kName, host_io, pb);
+    icet_pose_graph_options o;
+    icet_pose_graph_robust_result res{};
+    ICET_TRY(pg_run(f, poses_out && result,
+        [&]() {
+            ICET_TRY(pg_optimise_plan(f, opt, &o, poses64_out, edge_chi2));
+            if (!pg_robust_args(robust, &f.rb)) { c->err = std::string(kName) + ": the kind, the flags or the scale of `robust` is not one the optimiser takes"; return ICET_ERR_BAD_ARG; }
+            f.robust = f.rb.kind != pg::kRobustNone;
+            f.stage_weight = edge_weight != nullptr;
+            return ICET_OK;
+        },
+        [&]() {
+            const size_t N = (size_t)f.a.N, E = (size_t)f.a.E;
+            if (!host_io) { f.a.poses_out = poses_out; f.a.poses64_out = poses64_out; f.a.edge_chi2_out = edge_chi2; f.rb.weight_out = edge_weight; }
+            if (!pg_optimise_robust(f.be, f.a, f.dir, f.direct, o, f.graph.c_offband, f.rb, &res)) return false;
+            if (host_io) {
+                f.down(poses_out, f.a.poses_out, sizeof(float) * N * 16); f.down(poses64_out, f.a.poses64_out, sizeof(double) * N * 12);
+                f.down(edge_chi2, f.a.edge_chi2_out, sizeof(double) * 2 * E); f.down(edge_weight, f.rb.weight_out, sizeof(double) * E);
+            }
             return true;
         }));
     *result = res;
@@ -366,6 +420,22 @@ icet_status icet_pose_graph_optimize_device(icet_ctx* c, int32_t n, const float*
                                             const icet_pose_graph_options* opt, float* poses_out, double* poses64_out, double* edge_chi2,
                                             icet_pose_graph_result* result) {
     return pg_optimise_entry(c, false, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, opt, poses_out, poses64_out, edge_chi2, result);
+}
+
+icet_status icet_pose_graph_optimize_robust(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                            const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, const icet_pose_graph_options* opt,
+                                            const icet_pose_graph_robust* robust, float* poses_out, double* poses64_out, double* edge_chi2, double* edge_weight,
+                                            icet_pose_graph_robust_result* result) {
+    return pg_robust_entry(c, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, opt, robust, poses_out, poses64_out, edge_chi2,
+                           edge_weight, result);
+}
+
+icet_status icet_pose_graph_optimize_robust_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                                   const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                                   const icet_pose_graph_options* opt, const icet_pose_graph_robust* robust, float* poses_out, double* poses64_out,
+                                                   double* edge_chi2, double* edge_weight, icet_pose_graph_robust_result* result) {
+    return pg_robust_entry(c, false, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, opt, robust, poses_out, poses64_out, edge_chi2,
+                           edge_weight, result);
 }
 
 // Test hook: the optimiser's first iteration with its intermediate arrays copied out (pg_debug_step): conjugate gradients whatever "pg_solver" says.  The

@@ -11,6 +11,9 @@
 //     bool mgroups(PgMargGroupKernel, int groups, const PgArgs&, const PgDirect&, const PgMarg&)
 //                                                            the marginals' bodies (icet_posegraph_marginals.h); mgroups runs a group body once per group index
 //                                                            below `groups` (one workgroup each; the host loops over them); only pg_marginals calls them
+//     bool rgrid(PgRobustGridKernel, int count, const PgArgs&, const PgRobust&), rgroup(PgRobustGroupKernel, const PgArgs&, const PgRobust&)
+//                                                            the robust kernels' bodies (icet_posegraph_robust.h); only PgRobustPolicy and pg_optimise_robust call
+//                                                            them, so a backend without them still runs every other driver
 // each false for a failure of the backend (the driver then returns false at once).  icet_posegraph.hip has the device's backend (PgDeviceBackend),
 // tests/cpp/posegraph_host.h the host's (HostBackend), which the three host programs beside it share.
 // The sequences of launches that every run repeats are named once (pg_phase_*, below); the four drivers -- pg_gauss_newton, pg_marginals and the two hooks --
@@ -19,6 +22,7 @@
 #include "icet_posegraph_body.h"
 #include "icet_posegraph_direct.h"
 #include "icet_posegraph_marginals.h"
+#include "icet_posegraph_robust.h"
 
 #include <cmath>
 #include <vector>
@@ -66,6 +70,31 @@ inline PgGraphDev pg_bind(PgArgs& a, Alloc& al, size_t n_items) {
     return gd;
 }
 
+// ---- the policy of a Gauss-Newton run: what differs between the plain run and a robust one, so that the loop, the accept rule and the failure semantics stay
+// written once.  reweight runs between kPgLinearise and kPgAssemble; stats closes pg_phase_start and pg_phase_trial (it leaves the objective in sc[kScChi] and
+// max |dx| in sc[kScMaxDx]); finish runs behind kPgFinish with the run's final arguments.  A policy has no state that changes during a run.
+struct PgPlainPolicy {
+    template <class Backend> bool reweight(Backend&, const PgArgs&) const { return true; }
+    template <class Backend> bool stats(Backend& be, const PgArgs& a) const { return be.group(kPgStats, a); }
+    template <class Backend> bool finish(Backend&, const PgArgs&) const { return true; }
+};
+// The robust run (icet_posegraph_robust.h): the weights at the current chi2 scale Omega J, the objective is F = sum rho(chi2).  The raw sum of chi2 goes to
+// r.raw: kPgRawStart at the start, kPgRawTrial for every trial (a trial that is refused ends the run, so this slot says nothing at the end), and kPgRawFinal by
+// one more launch of the stats kernel over the row of the RETURNED poses behind the weights -- nothing on the host follows which trial was kept.
+struct PgRobustPolicy {
+    PgRobust r;
+    explicit PgRobustPolicy(const PgRobust& r_) : r(r_) {}
+    template <class Backend> bool stats_into(Backend& be, const PgArgs& a, int slot) const { PgRobust q = r; q.raw_slot = slot; return be.rgroup(kPgRobustStats, a, q); }
+    template <class Backend> bool reweight(Backend& be, const PgArgs& a) const { return be.rgrid(kPgRobustScale, a.E * 72, a, r); }
+    template <class Backend> bool stats(Backend& be, const PgArgs& a) const { return stats_into(be, a, a.trial ? kPgRawTrial : kPgRawStart); }
+    template <class Backend> bool finish(Backend& be, const PgArgs& a) const {
+        PgArgs b = a;
+        b.trial = 0;
+        if (a.failed) b.chi = a.chi0;          // (the outputs are the inputs: their row is the start's)
+        return be.rgrid(kPgRobustFinish, a.E, a, r) && stats_into(be, b, kPgRawFinal);
+    }
+};
+
 // ---- the phases: the sequences of launches the drivers share, each false for a failure of the backend ----------------------------------------------------
 // (the test hooks) count doubles from the device to dst; a null dst is skipped
 template <class Backend>
@@ -78,24 +107,32 @@ inline bool pg_phase_init(Backend& be, const PgArgs& a) {
     return be.grid(kPgInit, n_init, a) && be.grid(kPgChi, a.E, a);
 }
 // The start of a run: pg_phase_init, then the sum of the chi2 in the scalars, read into h
+template <class Backend, class Policy>
+inline bool pg_phase_start(Backend& be, const PgArgs& a, double h[kPgScalars], Policy& pol) { return pg_phase_init(be, a) && pol.stats(be, a) && be.scalars(a, h); }
 template <class Backend>
-inline bool pg_phase_start(Backend& be, const PgArgs& a, double h[kPgScalars]) { return pg_phase_init(be, a) && be.group(kPgStats, a) && be.scalars(a, h); }
+inline bool pg_phase_start(Backend& be, const PgArgs& a, double h[kPgScalars]) { PgPlainPolicy pol; return pg_phase_start(be, a, h, pol); }
 // The normal equations at the current poses: D, B, A and g
-template <class Backend>
-inline bool pg_phase_linearise(Backend& be, const PgArgs& a) {
-    return be.grid(kPgLinearise, a.E * 12, a) && be.grid(kPgAssemble, a.N * 36, a) && be.grid(kPgOffband, a.C * 36, a);
+template <class Backend, class Policy>
+inline bool pg_phase_linearise(Backend& be, const PgArgs& a, Policy& pol) {
+    return be.grid(kPgLinearise, a.E * 12, a) && pol.reweight(be, a) && be.grid(kPgAssemble, a.N * 36, a) && be.grid(kPgOffband, a.C * 36, a);
 }
+template <class Backend>
+inline bool pg_phase_linearise(Backend& be, const PgArgs& a) { PgPlainPolicy pol; return pg_phase_linearise(be, a, pol); }
 // ... and the band's factor behind them: what a linear solve starts from
+template <class Backend, class Policy>
+inline bool pg_phase_factor(Backend& be, const PgArgs& a, Policy& pol) { return pg_phase_linearise(be, a, pol) && be.group(kPgFactor, a); }
 template <class Backend>
-inline bool pg_phase_factor(Backend& be, const PgArgs& a) { return pg_phase_linearise(be, a) && be.group(kPgFactor, a); }
+inline bool pg_phase_factor(Backend& be, const PgArgs& a) { PgPlainPolicy pol; return pg_phase_factor(be, a, pol); }
 // The trial poses P (+) x, their chi2 and the step's length in the scalars, read into h.  a.trial is set for these launches alone.
-template <class Backend>
-inline bool pg_phase_trial(Backend& be, PgArgs& a, double h[kPgScalars]) {
+template <class Backend, class Policy>
+inline bool pg_phase_trial(Backend& be, PgArgs& a, double h[kPgScalars], Policy& pol) {
     a.trial = 1;
-    const bool ok = be.grid(kPgRetract, a.N, a) && be.grid(kPgChi, a.E, a) && be.group(kPgStats, a) && be.scalars(a, h);
+    const bool ok = be.grid(kPgRetract, a.N, a) && be.grid(kPgChi, a.E, a) && pol.stats(be, a) && be.scalars(a, h);
     a.trial = 0;
     return ok;
 }
+template <class Backend>
+inline bool pg_phase_trial(Backend& be, PgArgs& a, double h[kPgScalars]) { PgPlainPolicy pol; return pg_phase_trial(be, a, h, pol); }
 // The direct solve's factorisation behind the band's factor (q = d.nq > 0): Z, Wm and its factor, Ks and its factor
 template <class Backend>
 inline bool pg_phase_direct_factor(Backend& be, const PgArgs& a, const PgDirect& d) {
@@ -151,13 +188,14 @@ inline bool pg_cg(Backend& be, PgArgs& a, int cap, double pcg_tol, int* pcg, int
 }
 
 // The Gauss-Newton loop, written once over the LINEAR SOLVE: solve(a, &pcg, &bad) runs behind kPgFactor, leaves dx in a.x, counts its band solves on and sets
-// *bad to a failure's status; false for a failure of the backend.
-template <class Backend, class Solve>
-inline bool pg_gauss_newton(Backend& be, PgArgs a, const icet_pose_graph_options& o, Solve&& solve, int solver, icet_pose_graph_result* res) {
+// *bad to a failure's status; false for a failure of the backend.  `pol` (PgPlainPolicy, PgRobustPolicy) names the objective: chi2_initial and chi2_final
+// of *res are the objective's values, the sum of chi2 in a plain run.
+template <class Backend, class Solve, class Policy>
+inline bool pg_gauss_newton(Backend& be, PgArgs a, const icet_pose_graph_options& o, Solve&& solve, int solver, icet_pose_graph_result* res, Policy& pol) {
     double h[kPgScalars];
     const int N = a.N, E = a.E;
     a.damping = o.damping; a.trial = 0; a.first = 0; a.failed = 0;
-    if (!pg_phase_start(be, a, h)) return false;
+    if (!pg_phase_start(be, a, h, pol)) return false;
     const double chi2_initial = h[kScChi];
     double chi2 = chi2_initial, max_dx = 0.0;
     int status = pg::kIterationCap, its = 0, pcg = 0;
@@ -165,11 +203,11 @@ inline bool pg_gauss_newton(Backend& be, PgArgs a, const icet_pose_graph_options
     if (!std::isfinite(chi2)) { status = pg::kNonFinite; failed = true; }
     for (int it = 0; it < o.gn_iters && !failed; it++) {
         its++;
-        if (!pg_phase_factor(be, a)) return false;
+        if (!pg_phase_factor(be, a, pol)) return false;
         int bad = 0;
         if (!solve(a, &pcg, &bad)) return false;
         if (bad) { status = bad; failed = true; break; }
-        if (!pg_phase_trial(be, a, h)) return false;
+        if (!pg_phase_trial(be, a, h, pol)) return false;
         if (h[kScCg] != 0.0) { status = (int)h[kScCg]; failed = true; break; }
         max_dx = h[kScMaxDx];
         const double chit = h[kScChi];
@@ -184,18 +222,23 @@ inline bool pg_gauss_newton(Backend& be, PgArgs a, const icet_pose_graph_options
     }
     a.failed = failed ? 1 : 0;
     const int n_fin = N > E ? N : E;
-    if (!be.grid(kPgFinish, n_fin, a) || !be.scalars(a, h)) return false;
+    if (!be.grid(kPgFinish, n_fin, a) || !pol.finish(be, a) || !be.scalars(a, h)) return false;
     res->chi2_initial = chi2_initial; res->chi2_final = failed ? chi2_initial : chi2; res->max_dx = max_dx;
     res->status = status; res->gn_iterations = its; res->pcg_iterations = pcg; res->solver = solver;
     return true;
 }
 
 // The run.  `a` is bound (pg_bind), the graph uploaded, the caller's arrays in place.  true: *res is the result (its status says how the run ended).
-template <class Backend>
-inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, icet_pose_graph_result* res) {
+template <class Backend, class Policy>
+inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, icet_pose_graph_result* res, Policy& pol) {
     const double pcg_tol = o.pcg_tol > 0.0 ? o.pcg_tol : kPgDefaultPcgTol;
     const int cap = pg_cg_cap(c_offband, o);
-    return pg_gauss_newton(be, a, o, [&](PgArgs& b, int* pcg, int* bad) { return pg_cg(be, b, cap, pcg_tol, pcg, bad); }, 0, res);
+    return pg_gauss_newton(be, a, o, [&](PgArgs& b, int* pcg, int* bad) { return pg_cg(be, b, cap, pcg_tol, pcg, bad); }, 0, res, pol);
+}
+template <class Backend>
+inline bool pg_optimise(Backend& be, PgArgs a, const icet_pose_graph_options& o, int c_offband, icet_pose_graph_result* res) {
+    PgPlainPolicy pol;
+    return pg_optimise(be, a, o, c_offband, res, pol);
 }
 
 // ---- the direct solve (icet_posegraph_direct.h) --------------------------------------------------------------------------------------------------------------
@@ -257,15 +300,60 @@ inline int pg_direct_status(const double h[kPgScalars], int st[3]) {
 
 // The run with the direct solve in place of conjugate gradients: pg_optimise's loop, accept rule and outputs.  `a` is bound by pg_bind, `d` by pg_bind_direct.
 // o.max_pcg and o.pcg_tol are not used; pcg_iterations counts the single-right-hand-side band solves.
-template <class Backend>
-inline bool pg_optimise_direct(Backend& be, PgArgs a, PgDirect d, const icet_pose_graph_options& o, icet_pose_graph_result* res) {
+template <class Backend, class Policy>
+inline bool pg_optimise_direct(Backend& be, PgArgs a, PgDirect d, const icet_pose_graph_options& o, icet_pose_graph_result* res, Policy& pol) {
     return pg_gauss_newton(be, a, o, [&](PgArgs& b, int* pcg, int* bad) {
         double h[kPgScalars]; int st[3], solves = 0;
         if (!pg_direct_solve(be, b, d, &solves) || !be.scalars(b, h)) return false;
         *bad = pg_direct_status(h, st);
         if (!*bad) *pcg += solves;          // (behind a failed factorisation the solves were launched but did nothing)
         return true;
-    }, 1, res);
+    }, 1, res, pol);
+}
+template <class Backend>
+inline bool pg_optimise_direct(Backend& be, PgArgs a, PgDirect d, const icet_pose_graph_options& o, icet_pose_graph_result* res) {
+    PgPlainPolicy pol;
+    return pg_optimise_direct(be, a, d, o, res, pol);
+}
+
+// ---- the robust run (icet_posegraph_robust.h) ----------------------------------------------------------------------------------------------------------------
+// Its arrays beside the others in the same block: the weights and the raw sums of chi2, doubles only.  Bound only for a run with a kind.
+template <class Alloc>
+inline void pg_bind_robust(const PgArgs& a, PgRobust& r, Alloc& al) { r.wt = al.d((size_t)a.E); r.raw = al.d((size_t)kPgRobustRaw); }
+
+// The arguments of a robust run from the caller's struct (null: kind 0); false for one the optimiser does not take (pg::robust_ok)
+inline bool pg_robust_args(const icet_pose_graph_robust* rb, PgRobust* r) {
+    *r = PgRobust{};
+    if (!rb) return true;
+    r->kind = rb->kind; r->flags = rb->flags; r->scale = rb->scale;
+    return pg::robust_ok(rb->kind, rb->flags, rb->scale);
+}
+
+// The run under a robust kernel, through conjugate gradients or (direct; `d` bound by pg_bind_direct) the direct solve.  `r` has the kind, the caller's
+// weight_out and, with a kind, pg_bind_robust's arrays.  With kind 0 the launches are pg_optimise's or pg_optimise_direct's, and kPgRobustFinish behind them
+// where weights were asked for.  out->base has the RAW sums of chi2, cost_* the objective F.
+template <class Backend>
+inline bool pg_optimise_robust(Backend& be, const PgArgs& a, const PgDirect& d, bool direct, const icet_pose_graph_options& o, int c_offband, const PgRobust& r,
+                               icet_pose_graph_robust_result* out) {
+    icet_pose_graph_result res{};
+    out->downweighted = 0; out->reserved = 0;
+    if (r.kind == pg::kRobustNone) {
+        if (!(direct ? pg_optimise_direct(be, a, d, o, &res) : pg_optimise(be, a, o, c_offband, &res))) return false;
+        if (r.weight_out && !be.rgrid(kPgRobustFinish, a.E, a, r)) return false;
+        out->base = res; out->cost_initial = res.chi2_initial; out->cost_final = res.chi2_final;
+        return true;
+    }
+    PgRobustPolicy pol(r);
+    if (!(direct ? pg_optimise_direct(be, a, d, o, &res, pol) : pg_optimise(be, a, o, c_offband, &res, pol))) return false;
+    const bool failed = res.status == pg::kNotPositiveDefinite || res.status == pg::kNonFinite;
+    double raw[kPgRobustRaw];
+    std::vector<double> w((size_t)a.E);
+    if (!be.fetch(raw, r.raw, sizeof(raw)) || (a.E > 0 && !be.fetch(w.data(), r.wt, sizeof(double) * (size_t)a.E))) return false;
+    for (double v : w) if (v < 0.5) out->downweighted++;
+    out->cost_initial = res.chi2_initial; out->cost_final = res.chi2_final;
+    res.chi2_initial = raw[kPgRawStart]; res.chi2_final = failed ? raw[kPgRawStart] : raw[kPgRawFinal];
+    out->base = res;
+    return true;
 }
 
 // ---- the marginal covariances (icet_posegraph_marginals.h) ---------------------------------------------------------------------------------------------------

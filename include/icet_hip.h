@@ -635,6 +635,46 @@ icet_status icet_pose_graph_optimize_device(icet_ctx* ctx, int32_t n, const floa
                                             const int32_t* ci, const int32_t* cj, const float* d_clo_X, const float* d_clo_info, const uint8_t* fixed,
                                             const icet_pose_graph_options* opt, float* d_poses_out, double* d_poses64_out, double* d_edge_chi2,
                                             icet_pose_graph_result* result);
+/* ROBUST KERNELS: the same optimiser by iteratively reweighted least squares, so that a wrong closure cannot bend the map.  Per edge s = e^T Omega e and a
+ * threshold c > 0 in chi2 units (`scale`; ICET_PG_ROBUST_DEFAULT_SCALE is the 99 % quantile of chi2 with six degrees of freedom):
+ *   kind 0 none            rho = s                                   w = 1
+ *   kind 1 Huber           rho = s (s <= c), 2 sqrt(c s) - c         w = 1 (s <= c), sqrt(c / s)
+ *   kind 2 Cauchy          rho = c log1p(s / c)                      w = 1 / (1 + s / c)
+ *   kind 3 Geman-McClure   rho = c s / (c + s)                       w = (c / (c + s))^2
+ * (where s is not above zero: rho = s, w = 1).  The objective is F = sum rho(s_e).  The closures take the kind; the odometry edges only with flag
+ * ICET_PG_ROBUST_ODOMETRY.  Per iteration the weights w_e at the current poses scale the edges: H = sum w_e J^T Omega J (+ damping), g = sum w_e J^T Omega e;
+ * the step is kept only if F falls.  Statuses, failures, fixed nodes, the float32 rounding and the linear solves (option "pg_solver") are
+ * icet_pose_graph_optimize's.  The arguments are its arguments with `robust` (NULL: kind 0) behind opt and edge_weight (E doubles, may be NULL; a DEVICE
+ * pointer in the _device form) behind edge_chi2: every edge's w at the chi2 of the returned poses, 1 for an edge the flags leave alone.
+ * result: base.chi2_initial and base.chi2_final are the RAW sums of chi2, cost_initial and cost_final are F, downweighted counts the edges whose final w is
+ * below 0.5.  After a failure (status 2 or 3) the outputs are the inputs, edge_weight is w at the start's chi2 and cost_final = cost_initial.  With kind 0 the
+ * run is icet_pose_graph_optimize's, bit for bit, every weight 1 and cost = chi2.  ICET_ERR_BAD_ARG as icet_pose_graph_optimize, and: a kind outside 0 .. 3,
+ * a flag bit other than bit 0, with a kind a scale that is not finite and positive. */
+#define ICET_PG_ROBUST_NONE 0
+#define ICET_PG_ROBUST_HUBER 1
+#define ICET_PG_ROBUST_CAUCHY 2
+#define ICET_PG_ROBUST_GEMAN_MCCLURE 3
+#define ICET_PG_ROBUST_ODOMETRY 1
+#define ICET_PG_ROBUST_DEFAULT_SCALE 16.8119
+typedef struct icet_pose_graph_robust {
+    int32_t kind, flags;
+    double  scale;
+} icet_pose_graph_robust;         /* 16 bytes; NULL = kind 0 */
+typedef struct icet_pose_graph_robust_result {
+    icet_pose_graph_result base;
+    double  cost_initial, cost_final;
+    int32_t downweighted;
+    int32_t reserved;             /* zero */
+} icet_pose_graph_robust_result;  /* 64 bytes */
+icet_status icet_pose_graph_optimize_robust(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                            const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                            const icet_pose_graph_options* opt, const icet_pose_graph_robust* robust, float* poses_out, double* poses64_out,
+                                            double* edge_chi2, double* edge_weight, icet_pose_graph_robust_result* result);
+icet_status icet_pose_graph_optimize_robust_device(icet_ctx* ctx, int32_t n, const float* d_poses, const float* d_odo_X, const float* d_odo_info,
+                                                   int32_t n_closures, const int32_t* ci, const int32_t* cj, const float* d_clo_X, const float* d_clo_info,
+                                                   const uint8_t* fixed, const icet_pose_graph_options* opt, const icet_pose_graph_robust* robust,
+                                                   float* d_poses_out, double* d_poses64_out, double* d_edge_chi2, double* d_edge_weight,
+                                                   icet_pose_graph_robust_result* result);
 /* Test hook: the optimiser's FIRST Gauss-Newton iteration with every intermediate array copied out.  The arguments of icet_pose_graph_optimize (HOST arrays;
  * opt's gn_iters and dx_tol are not used), then K >= 0 vectors p (K x n x 6 doubles, may be NULL with K = 0).  On the context's stream, the production
  * kernels in the production order: the start's residuals and chi2, one linearisation, the assembly of the band and the off-band blocks, the band's
