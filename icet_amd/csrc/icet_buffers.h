@@ -64,4 +64,15 @@ private:
     }
 };
 
+// THE GROW STEP of a group that one capacity guards (the caller has seen need > cap and drained whatever may still read the old buffers): the capacity goes to 0 and
+// the group is released, `allocate` makes the new allocations (0, or the first error code), and only when all of them succeeded is the capacity set.  A refusal
+// returns the runtime's code and leaves capacity 0 and every slot null (what the refused growth did get is freed), so the next call grows again: at every return
+// a non-zero capacity means live buffers, and a null pointer means capacity 0.
+template <class C, class N, class F> int grow(BufferGroup& g, C& cap, N need, F&& allocate) {
+    cap = 0; g.release();
+    const int e = static_cast<int>(allocate());
+    if (e == 0) cap = static_cast<C>(need); else g.release();
+    return e;
+}
+
 }  // namespace icet

@@ -36,13 +36,13 @@ int icet::mem::pinned_free(void* p) { return hipHostFree(p); }
 
 namespace {
 
-// THE INVARIANT of every growth below (the ensure_* functions and the blocks of enqueue_keyframe, enqueue_rt2, enqueue_loop, icet_solve_begin and
-// icet_select_best_device): at every return, OK or not, a non-zero capacity means every pointer of its group (icet_ctx::Mem) is non-null and at least that large.
-// A group grows in three steps: ONE statement releases it and zeroes its capacity, the allocations follow, and the capacity is set after the last of them.  A
-// growth the runtime refuses thus leaves capacity 0 and null pointers, and the next call grows again.  The fit group (execbits, fit_items, fit_n_items; capacity
-// cap_fit_items) is sized from OTHER groups' capacities -- cap_pairs, cap_V, cap_n1 --, and no kernel is told its size: its capacity is zeroed as well wherever
-// the pair tables or the scan-1 arrays are released, so that it is rebuilt for their new sizes by the call that grows them or, if that call is refused anywhere
-// between, by the next one.  For it a non-zero capacity means: non-null and sized for the present cap_pairs, cap_V and cap_n1.
+// THE INVARIANT of every growth below: at every return, OK or not, a non-zero capacity means every pointer of its group (icet_ctx::Mem) is non-null and at least
+// that large.  Where ONE capacity guards a group, grow() (icet_buffers.h) keeps it.  Four groups spell the same three steps out -- one statement releases the group
+// and zeroes its capacity, the allocations follow, the capacity is set after the last -- because their capacity is more than one variable: the pair tables
+// (cap_pairs, cap_V, h_cap_pairs), the registration side (cap_regs, cap_reg_V), the threshold tables (thr_T, thr_P), and scan 1 with the fit group (execbits,
+// fit_items, fit_n_items; capacity cap_fit_items).  The fit group is sized from OTHER groups' capacities -- cap_pairs, cap_V, cap_n1 --, and no kernel is told its
+// size: its capacity is zeroed as well wherever the pair tables or the scan-1 arrays are released, so that it is rebuilt for their new sizes by the call that grows
+// them or, if that call is refused anywhere between, by the next one.  For it a non-zero capacity means: non-null and sized for the present cap_pairs, cap_V, cap_n1.
 
 // The REGISTRATION side of the workspace (Workspace, icet_internal.h): n_regs registrations on a grid of V voxels.  Leaves the keyframe side alone.
 icet_status ensure_regs(icet_ctx* c, int32_t n_regs, int V) {
@@ -75,9 +75,7 @@ icet_status ensure_scan2(icet_ctx* c, int64_t total_n2) {
     if (total_n2 >= (int64_t)1 << 31) { c->err = "total scan-2 points per call must be < 2^31"; return ICET_ERR_UNSUPPORTED; }
     if (total_n2 > w.cap_n2) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        w.cap_n2 = 0, c->mem.scan2.release();
-        HIPCHK(c, c->mem.scan2.device(w.near_over, (size_t)total_n2));
-        w.cap_n2 = total_n2;
+        HIPCHK(c, grow(c->mem.scan2, w.cap_n2, total_n2, [&] { return c->mem.scan2.device(w.near_over, (size_t)total_n2); }));
         c->ws_gen++;
     }
     return ICET_OK;
@@ -258,12 +256,13 @@ icet_status ensure_out(icet_ctx* c, int32_t n_pairs) {
     if (n_pairs <= c->cap_out_pairs) return ICET_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     BufferGroup& g = c->mem.out;
-    c->cap_out_pairs = 0, g.release();
-    HIPCHK(c, g.device(c->d_out, (size_t)n_pairs * 48));
-    HIPCHK(c, g.device(c->d_x0, (size_t)n_pairs * 6));
-    HIPCHK(c, g.pinned(c->h_out, (size_t)n_pairs * 48));
-    HIPCHK(c, g.pinned(c->h_x0, (size_t)n_pairs * 6));
-    c->cap_out_pairs = n_pairs;
+    HIPCHK(c, grow(g, c->cap_out_pairs, n_pairs, [&] {
+        int e = g.device(c->d_out, (size_t)n_pairs * 48);
+        if (!e) e = g.device(c->d_x0, (size_t)n_pairs * 6);
+        if (!e) e = g.pinned(c->h_out, (size_t)n_pairs * 48);
+        if (!e) e = g.pinned(c->h_x0, (size_t)n_pairs * 6);
+        return e;
+    }));
     return ICET_OK;
 }
 
@@ -347,11 +346,9 @@ icet_status ensure_pack(icet_ctx* c, int V, int runlen) {
     const AuxLayout L = aux_layout(V, runlen);
     if (L.total > c->cap_pack) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->cap_pack = 0, c->mem.pack.release();
         c->aux_dev = AuxDev{}; c->aux_V = 0; c->aux_runlen = 0;
-        HIPCHK(c, c->mem.pack.device(c->d_pack, L.total));
-        HIPCHK(c, c->mem.pack.pinned(c->h_pack, L.total));
-        c->cap_pack = L.total;
+        BufferGroup& g = c->mem.pack;
+        HIPCHK(c, grow(g, c->cap_pack, L.total, [&] { const int e = g.device(c->d_pack, L.total); return e ? e : g.pinned(c->h_pack, L.total); }));
     }
     if (c->aux_V != V || c->aux_runlen != runlen) {
         AuxDev& a = c->aux_dev; uint32_t* d = c->d_pack;
@@ -442,16 +439,13 @@ icet_status enqueue_keyframe(icet_ctx* c, const icet_params* p, int32_t n_pairs,
         const size_t need = (size_t)n_pairs * cfg.kf_chunks * (cfg.V > kRankSortMaxBuckets ? cfg.V : kRankSortMaxBuckets);
         if (need > w.cap_counts) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            w.cap_counts = 0, c->mem.counts.release();
-            HIPCHK(c, c->mem.counts.device(w.counts, need)); HIPCHK(c, c->mem.counts.device(w.tile_base, need));
-            w.cap_counts = need;
+            BufferGroup& g = c->mem.counts;
+            HIPCHK(c, grow(g, w.cap_counts, need, [&] { const int e = g.device(w.counts, need); return e ? e : g.device(w.tile_base, need); }));
         }
         const size_t need_vr = (size_t)n_pairs * cfg.kf_chunks * 2;        // (its own capacity: tiles per voxel count vary with the grid)
         if (need_vr > w.cap_tile_vr) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            w.cap_tile_vr = 0, c->mem.tile_vr.release();
-            HIPCHK(c, c->mem.tile_vr.device(w.tile_vr, need_vr));
-            w.cap_tile_vr = need_vr;
+            HIPCHK(c, grow(c->mem.tile_vr, w.cap_tile_vr, need_vr, [&] { return c->mem.tile_vr.device(w.tile_vr, need_vr); }));
         }
     }
     // a small batch: k_rs_splitters, the keyframe's first kernel, takes the descriptors from the pinned staging itself
@@ -472,13 +466,11 @@ icet_status enqueue_rt2(icet_ctx* c, LaunchCfg& lcfg, int32_t n_pairs, const Pai
     for (int k = 0; k < n_pairs; k++) tot += padded_ld(hd[k].n2);
     if (tot > w.cap_rt2 || !w.desc_rt || n_pairs > c->h_cap_rt) {
         HIPCHK(c, hipStreamSynchronize(c->stream)); staging_idle(c);
-        if (tot > w.cap_rt2) { w.cap_rt2 = 0, c->mem.rt2.release(); HIPCHK(c, c->mem.rt2.device(w.rt2, (size_t)3 * tot)); w.cap_rt2 = tot; }
+        if (tot > w.cap_rt2) HIPCHK(c, grow(c->mem.rt2, w.cap_rt2, tot, [&] { return c->mem.rt2.device(w.rt2, (size_t)3 * tot); }));
         if (n_pairs > c->h_cap_rt || !w.desc_rt) {
             const int np = n_pairs > w.cap_pairs ? n_pairs : w.cap_pairs;
-            c->h_cap_rt = 0, c->mem.rt_desc.release();
-            HIPCHK(c, c->mem.rt_desc.device(w.desc_rt, np));
-            HIPCHK(c, c->mem.rt_desc.pinned(c->h_desc_rt, np));
-            c->h_cap_rt = np;
+            BufferGroup& g = c->mem.rt_desc;
+            HIPCHK(c, grow(g, c->h_cap_rt, np, [&] { const int e = g.device(w.desc_rt, np); return e ? e : g.pinned(c->h_desc_rt, np); }));
         }
     }
     ICET_TRY(staging_wait(c));
@@ -517,13 +509,11 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
         if (need_mask > w.cap_keep_mask || need_list > w.cap_keep_list || n_pairs > w.cap_keep_pairs) {
             if (c->capturing) { c->err = "keep list: workspace growth during capture"; return ICET_ERR_HIP; }
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (need_mask > w.cap_keep_mask) { w.cap_keep_mask = 0, c->mem.keep_mask.release(); HIPCHK(c, c->mem.keep_mask.device(w.keep_mask, need_mask)); w.cap_keep_mask = need_mask; }
-            if (need_list > w.cap_keep_list) { w.cap_keep_list = 0, c->mem.keep_list.release(); HIPCHK(c, c->mem.keep_list.device(w.keep_list, need_list)); w.cap_keep_list = need_list; }
+            if (need_mask > w.cap_keep_mask) HIPCHK(c, grow(c->mem.keep_mask, w.cap_keep_mask, need_mask, [&] { return c->mem.keep_mask.device(w.keep_mask, need_mask); }));
+            if (need_list > w.cap_keep_list) HIPCHK(c, grow(c->mem.keep_list, w.cap_keep_list, need_list, [&] { return c->mem.keep_list.device(w.keep_list, need_list); }));
             if (n_pairs > w.cap_keep_pairs) {
                 BufferGroup& g = c->mem.keep_pairs;
-                w.cap_keep_pairs = 0, g.release();
-                HIPCHK(c, g.device(w.keep_state, (size_t)n_pairs)); HIPCHK(c, g.device(w.keep_modes, 2 * (size_t)n_pairs));
-                w.cap_keep_pairs = n_pairs;
+                HIPCHK(c, grow(g, w.cap_keep_pairs, n_pairs, [&] { const int e = g.device(w.keep_state, (size_t)n_pairs); return e ? e : g.device(w.keep_modes, 2 * (size_t)n_pairs); }));
             }
             wl.keep_modes = w.keep_modes; wl.keep_mask = w.keep_mask; wl.keep_list = w.keep_list; wl.keep_state = w.keep_state; wl.cap_keep_mask = w.cap_keep_mask; wl.cap_keep_list = w.cap_keep_list; wl.cap_keep_pairs = w.cap_keep_pairs;
         }
@@ -643,8 +633,8 @@ icet_status ensure_stage(icet_ctx* c, int64_t tot1, int64_t tot2) {
     if (3 * tot1 > c->cap_stage1 || 3 * tot2 > c->cap_stage2) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
-        if (3 * tot1 > c->cap_stage1) { c->cap_stage1 = 0, c->mem.stage1.release(); HIPCHK(c, c->mem.stage1.device(c->d_stage1, (size_t)3 * tot1)); c->cap_stage1 = 3 * tot1; }
-        if (3 * tot2 > c->cap_stage2) { c->cap_stage2 = 0, c->mem.stage2.release(); HIPCHK(c, c->mem.stage2.device(c->d_stage2, (size_t)3 * tot2)); c->cap_stage2 = 3 * tot2; }
+        if (3 * tot1 > c->cap_stage1) HIPCHK(c, grow(c->mem.stage1, c->cap_stage1, 3 * tot1, [&] { return c->mem.stage1.device(c->d_stage1, (size_t)3 * tot1); }));
+        if (3 * tot2 > c->cap_stage2) HIPCHK(c, grow(c->mem.stage2, c->cap_stage2, 3 * tot2, [&] { return c->mem.stage2.device(c->d_stage2, (size_t)3 * tot2); }));
     }
     return ICET_OK;
 }
@@ -689,8 +679,8 @@ icet_status icet_create(icet_ctx** out, int device_id, void* hip_stream) {
         delete c; return ICET_ERR_HIP;       // no usable kernel image for this device: fail loudly, there is no fallback
     }
     {   // which form of the stable multi-splits this device gets (Tuning::lds_rank): ~0.1 ms once per context
-        int32_t* d_t = nullptr; int ok = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&d_t), sizeof(int32_t)) == hipSuccess) { if (lds_rank_selftest(d_t, c->stream, &ok) != hipSuccess) { ok = 0; (void)hipGetLastError(); } (void)hipFree(d_t); }
+        int32_t* d_t = nullptr; BufferGroup g; int ok = 0;                // (the word is freed at the end of this block)
+        if (g.device(d_t, 1) == hipSuccess) { if (lds_rank_selftest(d_t, c->stream, &ok) != hipSuccess) { ok = 0; (void)hipGetLastError(); } }
         c->lds_rank_ok = ok;
     }
     if (c->mem.sync_word.pinned(c->h_sync_word, 1, hipHostMallocCoherent) == hipSuccess) *c->h_sync_word = 0;      // (without it icet_sync synchronises the stream)
@@ -1098,10 +1088,8 @@ icet_status icet_debug_gn_terms_device(icet_ctx* c, const icet_params* p, int32_
 static icet_status ensure_score(icet_ctx* c, int32_t n) {
     if (n <= c->cap_score) return ICET_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->cap_score = 0, c->mem.score.release();
-    HIPCHK(c, c->mem.score.device(c->d_score, (size_t)n));
-    HIPCHK(c, c->mem.score.pinned(c->h_score, (size_t)n));
-    c->cap_score = n;
+    BufferGroup& g = c->mem.score;
+    HIPCHK(c, grow(g, c->cap_score, n, [&] { const int e = g.device(c->d_score, (size_t)n); return e ? e : g.pinned(c->h_score, (size_t)n); }));
     return ICET_OK;
 }
 
@@ -1176,10 +1164,8 @@ icet_status icet_select_best_device(icet_ctx* c, int32_t n_regs, const int32_t* 
     if (c->sel_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_sel)); c->sel_in_flight = false; }
     if (need > c->cap_sel) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->cap_sel = 0, c->mem.sel.release();
-        HIPCHK(c, c->mem.sel.device(c->d_sel, (size_t)need));
-        HIPCHK(c, c->mem.sel.pinned(c->h_sel, (size_t)need));
-        c->cap_sel = need;
+        BufferGroup& sm = c->mem.sel;
+        HIPCHK(c, grow(sm, c->cap_sel, need, [&] { const int e = sm.device(c->d_sel, (size_t)need); return e ? e : sm.pinned(c->h_sel, (size_t)need); }));
     }
     int32_t* members = c->h_sel; int32_t* offs = c->h_sel + n_regs;
     for (int g = 0; g <= n_groups; g++) offs[g] = 0;
@@ -1262,10 +1248,8 @@ icet_status icet_solve_begin(icet_ctx* c, const icet_params* p, const float* sca
     if (s != ICET_OK) return s;
     const bool want_pts2 = aux && aux->points2 && n2 > 0 && p->runlen > 0;
     auto grow_pts2 = [c](size_t want) -> icet_status {                        // `points2` on the device and its pinned copy
-        c->cap_pts2 = 0, c->mem.pts2.release();
-        HIPCHK(c, c->mem.pts2.device(c->d_pts2, want));
-        HIPCHK(c, c->mem.pts2.pinned(c->h_pts2, want));
-        c->cap_pts2 = want;
+        BufferGroup& g = c->mem.pts2;
+        HIPCHK(c, grow(g, c->cap_pts2, want, [&] { const int e = g.device(c->d_pts2, want); return e ? e : g.pinned(c->h_pts2, want); }));
         return ICET_OK;
     };
     if (want_pts2 && (p->flags & ICET_FLAG_ROUNDTRIP_SCAN2) && (size_t)3 * n2 > c->cap_pts2) {
@@ -1278,14 +1262,14 @@ icet_status icet_solve_begin(icet_ctx* c, const icet_params* p, const float* sca
     const bool want_side2 = aux && p->runlen > 0 && n2 > 0 && (aux->points2_spherical || aux->voxel2);
     if (want_side1 && (size_t)n1 > c->cap_side1) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->cap_side1 = 0, c->mem.side1.release();
-        HIPCHK(c, c->mem.side1.device(c->d_sph1, (size_t)3 * n1)); HIPCHK(c, c->mem.side1.device(c->d_idx1, (size_t)n1)); c->cap_side1 = (size_t)n1;
+        BufferGroup& g = c->mem.side1;
+        HIPCHK(c, grow(g, c->cap_side1, n1, [&] { const int e = g.device(c->d_sph1, (size_t)3 * n1); return e ? e : g.device(c->d_idx1, (size_t)n1); }));
     }
     if (want_side2 && ((size_t)n2 > c->cap_side2 || (size_t)3 * n2 > c->cap_pts2)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
-        c->cap_side2 = 0, c->mem.side2.release();
-        HIPCHK(c, c->mem.side2.device(c->d_sph2, (size_t)3 * n2)); HIPCHK(c, c->mem.side2.device(c->d_vox2, (size_t)n2)); c->cap_side2 = (size_t)n2;
+        BufferGroup& g = c->mem.side2;
+        HIPCHK(c, grow(g, c->cap_side2, n2, [&] { const int e = g.device(c->d_sph2, (size_t)3 * n2); return e ? e : g.device(c->d_vox2, (size_t)n2); }));
         if ((size_t)3 * n2 > c->cap_pts2) { const icet_status gs = grow_pts2((size_t)3 * n2); if (gs != ICET_OK) return gs; }
     }
     ICET_TRY(staging_wait(c));

@@ -22,12 +22,14 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
 #include <vector>
 #include "icet_multi_sched.h"
+#include "icet_buffers.h"
 
 namespace {
 
@@ -56,18 +58,22 @@ struct Rccl {
 
 }  // namespace
 
+// A device entry's two result buffers, each with its capacity and its owner (grown on the device's own thread: icet::grow, icet_buffers.h)
+struct DevBufs {
+    float* d_part = nullptr; int32_t cap_part = 0;      // results of its pairs (device-resident entry), cap x 48, then cap x 6 of X0
+    float* d_full = nullptr; int32_t cap_full = 0;      // receive buffer of the all-gather (n_devices x m x 48)
+    icet::BufferGroup part_mem, full_mem;
+};
+
 struct icet_multi {
     std::vector<int> dev;
     std::vector<icet_ctx*> ctx;
-    std::vector<float*> d_part;          // per device: results of its pairs (device-resident entry), cap x 48, then cap x 6 of X0
-    std::vector<int32_t> cap_part;
+    std::unique_ptr<DevBufs[]> buf;      // per device entry, made once (a buffer group holds the address of its pointer)
     icet_sched::Sched sched;             // the device threads and the record of their failures (icet_multi_sched.h)
     hipEvent_t ev_producer = nullptr;    // recorded on the caller's stream (device_ids[0]); every device's stream waits for it
     int gather_mode = 0;                 // 0 peer copies, 1 RCCL all-gather
     Rccl rccl;
     std::vector<ncclComm_t> comms;       // one per device entry once gather_mode 1 has been used
-    std::vector<float*> d_full;          // per device: receive buffer of the all-gather (n_devices x m x 48)
-    std::vector<int32_t> cap_full;
     // asynchronous calls: the first failure of every device since the last icet_multi_sync, and one event per device recorded behind
     // the last gather it enqueued
     std::vector<hipEvent_t> ev_done;
@@ -122,8 +128,7 @@ icet_status icet_multi_create(icet_multi** out, const int32_t* device_ids, int32
     if (!m) return ICET_ERR_NOMEM;
     try {
         m->dev.assign(device_ids, device_ids + n_devices);
-        m->ctx.assign(n_devices, nullptr); m->d_part.assign(n_devices, nullptr); m->cap_part.assign(n_devices, 0);
-        m->d_full.assign(n_devices, nullptr); m->cap_full.assign(n_devices, 0);
+        m->ctx.assign(n_devices, nullptr); m->buf.reset(new DevBufs[(size_t)n_devices]);
         m->ev_done.assign(n_devices, nullptr);
     } catch (...) { icet_multi_destroy(m); return ICET_ERR_NOMEM; }
     if (!m->sched.start(n_devices)) { icet_multi_destroy(m); return ICET_ERR_NOMEM; }      // (std::system_error / bad_alloc: the threads that started have been joined)
@@ -155,8 +160,7 @@ icet_status icet_multi_destroy(icet_multi* m) {
     for (size_t i = 0; i < m->comms.size(); i++) if (m->comms[i]) (void)m->rccl.CommDestroy(m->comms[i]);
     for (size_t i = 0; i < m->ctx.size(); i++) {
         (void)hipSetDevice(m->dev[i]);
-        if (m->d_part[i]) (void)hipFree(m->d_part[i]);
-        if (i < m->d_full.size() && m->d_full[i]) (void)hipFree(m->d_full[i]);
+        if (m->buf) { m->buf[i].part_mem.release(); m->buf[i].full_mem.release(); }
         if (i < m->ev_done.size() && m->ev_done[i]) (void)hipEventDestroy(m->ev_done[i]);
         if (m->ctx[i]) (void)icet_destroy(m->ctx[i]);
     }
@@ -261,7 +265,7 @@ static icet_status multi_enqueue(icet_multi* m, const icet_params* p, int32_t n_
     bool grow = false;
     for (int d = 0; d < D; d++) {
         const int np = (n_pairs - d + D - 1) / D;
-        if ((mode == 1 ? mrows : np) > m->cap_part[d] || (mode == 1 && D * mrows > m->cap_full[d])) grow = true;
+        if ((mode == 1 ? mrows : np) > m->buf[d].cap_part || (mode == 1 && D * mrows > m->buf[d].cap_full)) grow = true;
     }
     if (grow) {
         int fail_status = 0;
@@ -271,18 +275,14 @@ static icet_status multi_enqueue(icet_multi* m, const icet_params* p, int32_t n_
             if (hipSetDevice(m->dev[d]) != hipSuccess) return (int)ICET_ERR_NO_DEVICE;
             hipStream_t s = reinterpret_cast<hipStream_t>(icet_stream(m->ctx[d]));
             if (hipStreamSynchronize(s) != hipSuccess) return (int)ICET_ERR_HIP;
-            if (need > m->cap_part[d]) {
-                if (m->d_part[d]) { (void)hipFree(m->d_part[d]); m->d_part[d] = nullptr; m->cap_part[d] = 0; }
+            DevBufs& b = m->buf[d];
+            if (need > b.cap_part) {
                 // results (48 floats) and the share's X0 (6 floats) per pair
-                if (hipMalloc(reinterpret_cast<void**>(&m->d_part[d]), sizeof(float) * 54 * (size_t)need) != hipSuccess) return (int)ICET_ERR_NOMEM;
-                (void)hipMemsetAsync(m->d_part[d], 0, sizeof(float) * 54 * (size_t)need, s);
-                m->cap_part[d] = need;
+                if (icet::grow(b.part_mem, b.cap_part, need, [&] { return b.part_mem.device(b.d_part, 54 * (size_t)need); }) != 0) return (int)ICET_ERR_NOMEM;
+                (void)hipMemsetAsync(b.d_part, 0, sizeof(float) * 54 * (size_t)need, s);
             }
-            if (mode == 1 && D * mrows > m->cap_full[d]) {
-                if (m->d_full[d]) { (void)hipFree(m->d_full[d]); m->d_full[d] = nullptr; m->cap_full[d] = 0; }
-                if (hipMalloc(reinterpret_cast<void**>(&m->d_full[d]), sizeof(float) * 48 * (size_t)D * mrows) != hipSuccess) return (int)ICET_ERR_NOMEM;
-                m->cap_full[d] = D * mrows;
-            }
+            if (mode == 1 && D * mrows > b.cap_full &&
+                icet::grow(b.full_mem, b.cap_full, D * mrows, [&] { return b.full_mem.device(b.d_full, 48 * (size_t)D * mrows); }) != 0) return (int)ICET_ERR_NOMEM;
             return 0;
         }, &fail_status);
         if (bad == -2) { m->err = "cannot hand the work to the device threads"; return ICET_ERR_NOMEM; }
@@ -300,7 +300,7 @@ static icet_status multi_enqueue(icet_multi* m, const icet_params* p, int32_t n_
                 const int np = (int)a.size();
                 hipError_t e = hipSetDevice(m->dev[d]);
                 hipStream_t s = reinterpret_cast<hipStream_t>(icet_stream(m->ctx[d]));
-                float* part = m->d_part[d]; float* px0 = part + 48 * (size_t)m->cap_part[d];
+                float* part = m->buf[d].d_part; float* px0 = part + 48 * (size_t)m->buf[d].cap_part;
                 if (e == hipSuccess && wait_producer) e = hipStreamWaitEvent(s, m->ev_producer, 0);
                 if (e == hipSuccess && d_x0 && np) e = hipMemcpy2DAsync(px0, 6 * sizeof(float), d_x0 + 6 * (size_t)d, 6 * sizeof(float) * D, 6 * sizeof(float), np, hipMemcpyDefault, s);
                 if (e != hipSuccess) { why = hipGetErrorString(e); return (int)ICET_ERR_HIP; }
@@ -311,16 +311,16 @@ static icet_status multi_enqueue(icet_multi* m, const icet_params* p, int32_t n_
             [m, D, mode, mrows, n_pairs, d_out, as](int d, int solve_status, std::string& why) -> int {
                 const int np = (int)(*as)[d].size();
                 hipStream_t s = reinterpret_cast<hipStream_t>(icet_stream(m->ctx[d]));
-                float* part = m->d_part[d];
+                float* part = m->buf[d].d_part;
                 hipError_t e = hipSuccess;
                 if (mode == 1) {
-                    ncclResult_t r = m->rccl.AllGather(part, m->d_full[d], (size_t)mrows * 48, ncclFloat, m->comms[d], s);
+                    ncclResult_t r = m->rccl.AllGather(part, m->buf[d].d_full, (size_t)mrows * 48, ncclFloat, m->comms[d], s);
                     if (r != ncclSuccess) { why = std::string("ncclAllGather: ") + m->rccl.GetErrorString(r); return (int)ICET_ERR_HIP; }
                     if (d == 0) {
                         // undo the round-robin interleave on the gathering device: block r of the receive buffer holds pairs r, r + D, ...
                         for (int r2 = 0; r2 < D && e == hipSuccess; r2++) {
                             const int rows = (n_pairs - r2 + D - 1) / D;
-                            if (rows > 0) e = hipMemcpy2DAsync(d_out + 48 * (size_t)r2, 48 * sizeof(float) * D, m->d_full[0] + 48 * (size_t)r2 * mrows, 48 * sizeof(float),
+                            if (rows > 0) e = hipMemcpy2DAsync(d_out + 48 * (size_t)r2, 48 * sizeof(float) * D, m->buf[0].d_full + 48 * (size_t)r2 * mrows, 48 * sizeof(float),
                                                                48 * sizeof(float), rows, hipMemcpyDeviceToDevice, s);
                         }
                     }

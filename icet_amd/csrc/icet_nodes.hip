@@ -17,6 +17,7 @@
 #include "../../include/icet_nodes.h"
 #include "icet_shuffle.h"
 #include "icet_node_tail.h"
+#include "icet_buffers.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include <numeric>
 #include <random>
 #include <future>
+#include <memory>
 #include <thread>
 #include <chrono>
 #include <cstdio>
@@ -249,9 +251,10 @@ struct StreamState {
     int32_t* h_idx = nullptr;                                     // pinned: the frame's down-sample indices (the map kernel can read them in place)
     float* d_aligned = nullptr; int64_t cap_aligned = 0, n_aligned = 0, ld_aligned = 0;     // scanMatcher.cpp:76
     std::vector<float> snail;                                                               // scanMatcher.cpp:27-28,79-84: rows x 3 row-major, host
+    icet::BufferGroup fixed, scan_mem[2], aligned_mem;                                      // owners: d_map + h_idx (creation); d_scan[i]; d_aligned.  They free when the stream goes
 };
 
-#define NCHK(o, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+#define NCHK(o, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
     (o)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
     return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
 
@@ -266,17 +269,12 @@ bool fast_shuffle_ok() { static const bool ok = icet_shuffle::matches_std_shuffl
 // The map ring (zeroed: Eigen leaves MatrixXf(maxSize, 3) uninitialised; unfilled rows are never returned by getQueue), its pinned index buffer, the snail trail's first row
 icet_status stream_create(const icet_node_params& p, StreamState& st) {
     if (p.map_capacity > 0) {
-        if (hipMalloc(reinterpret_cast<void**>(&st.d_map), sizeof(float) * 3 * (size_t)p.map_capacity) != hipSuccess) return ICET_ERR_NOMEM;
+        if (st.fixed.device(st.d_map, 3 * (size_t)p.map_capacity) != 0) return ICET_ERR_NOMEM;
         if (hipMemset(st.d_map, 0, sizeof(float) * 3 * (size_t)p.map_capacity) != hipSuccess) return ICET_ERR_HIP;
-        if (hipHostMalloc(reinterpret_cast<void**>(&st.h_idx), sizeof(int32_t) * (size_t)std::max(p.map_downsample, 1)) != hipSuccess) return ICET_ERR_NOMEM;
+        if (st.fixed.pinned(st.h_idx, (size_t)std::max(p.map_downsample, 1)) != 0) return ICET_ERR_NOMEM;
     }
     if (p.flags & ICET_NODE_SNAIL_TRAIL) st.snail.assign(3, 0.f);      // scanMatcher.cpp:27-28: one row at the origin
     return ICET_OK;
-}
-void stream_destroy(StreamState& st) {
-    void* dp[] = {st.d_scan[0], st.d_scan[1], st.d_map, st.d_aligned};
-    for (void* q : dp) if (q) (void)hipFree(q);
-    if (st.h_idx) (void)hipHostFree(st.h_idx);
 }
 
 // No exception may cross the C ABI (std::async and the draw pool can throw std::system_error, the shuffle's vector bad_alloc): f's status, or the exception as one
@@ -300,26 +298,20 @@ template <class O, class P> icet_status wait_pinned(O* o, P&& arrived, hipStream
     return ICET_OK;
 }
 
+// Every growth below is icet::grow (icet_buffers.h) behind the caller's drain: a refused one leaves capacity 0 and null pointers, and the next call grows again.
 // A scan-sized buffer: (n + n / 8) rows rounded to 64.  drain() makes sure that nothing on the device still reads the old one.
-template <class O, class D> icet_status grow_rows(O* o, float*& buf, int64_t& cap, int64_t n, D&& drain) {
+template <class O, class D> icet_status grow_rows(O* o, icet::BufferGroup& g, float*& buf, int64_t& cap, int64_t n, D&& drain) {
     if (n <= cap) return ICET_OK;
     NCHK(o, drain());
-    if (buf) { NCHK(o, hipFree(buf)); buf = nullptr; cap = 0; }
     const int64_t c = (n + n / 8 + 63) / 64 * 64;
-    NCHK(o, hipMalloc(reinterpret_cast<void**>(&buf), sizeof(float) * 3 * (size_t)c));
-    cap = c;
+    NCHK(o, icet::grow(g, cap, c, [&] { return g.device(buf, 3 * (size_t)c); }));
     return ICET_OK;
 }
 // The range filter's block counts and their bases, n of each
-template <class O, class D> icet_status grow_blocks(O* o, int32_t*& counts, int32_t*& bases, int64_t& cap, int64_t n, D&& drain) {
+template <class O, class D> icet_status grow_blocks(O* o, icet::BufferGroup& g, int32_t*& counts, int32_t*& bases, int64_t& cap, int64_t n, D&& drain) {
     if (n <= cap) return ICET_OK;
     NCHK(o, drain());
-    if (counts) { NCHK(o, hipFree(counts)); counts = nullptr; }
-    if (bases) { NCHK(o, hipFree(bases)); bases = nullptr; }
-    cap = 0;
-    NCHK(o, hipMalloc(reinterpret_cast<void**>(&counts), sizeof(int32_t) * (size_t)n));
-    NCHK(o, hipMalloc(reinterpret_cast<void**>(&bases), sizeof(int32_t) * (size_t)n));
-    cap = n;
+    NCHK(o, icet::grow(g, cap, n, [&] { const int e = g.device(counts, (size_t)n); return e ? e : g.device(bases, (size_t)n); }));
     return ICET_OK;
 }
 
@@ -410,9 +402,9 @@ template <class O> icet_status stream_rows_out(O* o, const StreamState& st, Stre
     if (hipSetDevice(o->device) != hipSuccess) return ICET_ERR_NO_DEVICE;
     const float* src = what == kRowsPrevScan ? st.d_scan[st.prev] : st.d_aligned;
     int64_t lds = what == kRowsPrevScan ? st.ld_scan[st.prev] : st.ld_aligned;
-    float* tmp = nullptr;
+    float* tmp = nullptr; icet::BufferGroup g;                   // (freed at every return: behind the synchronisation below)
     if (what == kRowsMap) {                                       // getQueue: the ring unrolled, oldest row first, through a temporary
-        NCHK(o, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(float) * 3 * (size_t)rows));
+        NCHK(o, g.device(tmp, 3 * (size_t)rows));
         const int cap = o->p.map_capacity;
         k_map_unroll<<<std::min((int)((rows + 255) / 256), 2048), 256, 0, o->stream>>>(st.d_map, st.d_map + cap, st.d_map + 2 * (size_t)cap, cap, (int)st.map_pos,
                                                                                         st.map_filled ? 1 : 0, (int)rows, tmp, (int)rows);
@@ -421,7 +413,6 @@ template <class O> icet_status stream_rows_out(O* o, const StreamState& st, Stre
     hipError_t e = tmp ? hipGetLastError() : hipSuccess;
     if (e == hipSuccess) e = hipMemcpy2DAsync(out, ld * sizeof(float), src, lds * sizeof(float), rows * sizeof(float), 3, hipMemcpyDeviceToHost, o->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(o->stream);
-    if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) { o->err = hipGetErrorString(e); return ICET_ERR_HIP; }
     return ICET_OK;
 }
@@ -471,6 +462,8 @@ struct icet_node {
     int32_t* d_counts_kf = nullptr; int32_t* d_bases_kf = nullptr; int64_t cap_blocks_kf = 0; int32_t* d_nkept_kf = nullptr;
     hipEvent_t ev_f2 = nullptr;                                   // the keyframe side's filter has read the caller's frame
     int32_t* h_done = nullptr;                                    // pinned, coherent: the frame's last solve stores 1 here behind its results (the host watches it instead of synchronising the stream)
+    // owners, one per lifetime: what icet_node_create allocates; h_frame + d_nkept_kf + h_done (ensure_kf_side, once); then one per buffer (pair) that grows on its own
+    icet::BufferGroup fixed, kf_fixed, stage_mem, blocks_mem, scan_kf_mem[2], blocks_kf_mem;
 #ifdef ICET_DIAG_ENV
     double tr[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long tr_n = 0, tr_seen = 0;       // ICET_NODE_TRACE: host microseconds of push_frame by section, summed (printed by icet_node_destroy)
 #endif
@@ -544,15 +537,19 @@ int64_t filter_key(const FilterLaunch& f) {            // everything the hook's 
 }
 // the keyframe side's own filtered copy of scan `which`, its block counters and its row counters
 icet_status ensure_kf_side(icet_node* nd, int which, int64_t n) {
-    if (!nd->h_frame) { NCHK(nd, hipHostMalloc(reinterpret_cast<void**>(&nd->h_frame), 2 * sizeof(FrameDesc))); std::memset(nd->h_frame, 0, 2 * sizeof(FrameDesc)); }
-    if (!nd->d_nkept_kf) NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_nkept_kf), 2 * sizeof(int32_t)));
+    if (!nd->h_done) {                                            // (the last of the fixed set: one that was refused half way is made anew, and nothing has used it)
+        icet::BufferGroup& g = nd->kf_fixed;
+        g.release();
+        NCHK(nd, g.pinned(nd->h_frame, 2)); std::memset(nd->h_frame, 0, 2 * sizeof(FrameDesc));
+        NCHK(nd, g.device(nd->d_nkept_kf, 2));
+        NCHK(nd, g.pinned(nd->h_done, 1, hipHostMallocCoherent)); *nd->h_done = 0;
+    }
     if (!nd->ev_f2) NCHK(nd, hipEventCreateWithFlags(&nd->ev_f2, hipEventDisableTiming));
-    if (!nd->h_done) { NCHK(nd, hipHostMalloc(reinterpret_cast<void**>(&nd->h_done), sizeof(int32_t), hipHostMallocCoherent)); *nd->h_done = 0; }
-    const icet_status s = grow_rows(nd, nd->d_scan_kf[which], nd->cap_scan_kf[which], n, hipDeviceSynchronize); if (s != ICET_OK) return s;
-    return grow_blocks(nd, nd->d_counts_kf, nd->d_bases_kf, nd->cap_blocks_kf, (nd->cap_scan_kf[which] + kFB * kFRows - 1) / (kFB * kFRows), hipDeviceSynchronize);
+    const icet_status s = grow_rows(nd, nd->scan_kf_mem[which], nd->d_scan_kf[which], nd->cap_scan_kf[which], n, hipDeviceSynchronize); if (s != ICET_OK) return s;
+    return grow_blocks(nd, nd->blocks_kf_mem, nd->d_counts_kf, nd->d_bases_kf, nd->cap_blocks_kf, (nd->cap_scan_kf[which] + kFB * kFRows - 1) / (kFB * kFRows), hipDeviceSynchronize);
 }
 // a scan buffer of the node: both streams of a pipelined node may still read the old one
-icet_status ensure_scan(icet_node* nd, int which, int64_t n) { return grow_rows(nd, nd->s.d_scan[which], nd->s.cap_scan[which], n, hipDeviceSynchronize); }
+icet_status ensure_scan(icet_node* nd, int which, int64_t n) { return grow_rows(nd, nd->s.scan_mem[which], nd->s.d_scan[which], nd->s.cap_scan[which], n, hipDeviceSynchronize); }
 
 // One frame with the raw scan already in HBM (column-major, ld).
 icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld, icet_node_result* res) {
@@ -611,7 +608,7 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
     const bool fused = (fast || map_ok) && loop_on_filter_stream && nd->p.solve.runlen > 0 && !(nd->p.flags & ICET_NODE_TIME_PHASES);
     const bool dev_count = fast || fused;                         // the solve's halves read the row count on the device
     const int n_blocks = fused ? (int)((lcur + kFB * kFRows - 1) / (kFB * kFRows)) : (int)((n + kFB * kFRows - 1) / (kFB * kFRows));      // fused: by CAPACITY (the launch does not change with n)
-    s = grow_blocks(nd, nd->d_counts, nd->d_bases, nd->cap_blocks, n_blocks, hipDeviceSynchronize); if (s != ICET_OK) return s;
+    s = grow_blocks(nd, nd->blocks_mem, nd->d_counts, nd->d_bases, nd->cap_blocks, n_blocks, hipDeviceSynchronize); if (s != ICET_OK) return s;
     if (fused) { s = ensure_kf_side(nd, cur, n); if (s != ICET_OK) return s; }
     int32_t* d_cnt = nd->d_nkept + cur;
     if (!fused) NCHK(nd, hipEventRecord(nd->ev[0], st));         // (the one-launch frame records no timing events: each costs the host 5-10 us IN FRONT of the launch)
@@ -766,9 +763,7 @@ icet_status push_frame(icet_node* nd, const float* d_scan, int64_t n, int64_t ld
     auto align_dev = [&](const float* X, const float* Ri) -> icet_status {
         if (lcur > nd->s.cap_aligned) {
             NCHK(nd, hipStreamSynchronize(st));
-            if (nd->s.d_aligned) { NCHK(nd, hipFree(nd->s.d_aligned)); nd->s.d_aligned = nullptr; }
-            NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->s.d_aligned), sizeof(float) * 3 * (size_t)lcur));
-            nd->s.cap_aligned = lcur;
+            NCHK(nd, icet::grow(nd->s.aligned_mem, nd->s.cap_aligned, lcur, [&] { return nd->s.aligned_mem.device(nd->s.d_aligned, 3 * (size_t)lcur); }));
         }
         const float* sc = nd->s.d_scan[cur]; float* o = nd->s.d_aligned; const int64_t la = nd->s.cap_aligned;
         if (nk) k_align_cloud<<<(int)std::min<int64_t>((nk + 255) / 256, 2048), 256, 0, st>>>(sc, sc + lcur, sc + 2 * lcur, (int)nk, o, o + la, o + 2 * la, X[0], X[1], X[2],
@@ -818,9 +813,9 @@ icet_status icet_node_create(icet_ctx* ctx, const icet_node_params* p, icet_node
     nd->ctx = ctx; nd->p = *p; nd->stream = reinterpret_cast<hipStream_t>(icet_stream(ctx)); nd->device = icet_device(ctx);
     auto fail = [&](icet_status s) { icet_node_destroy(nd); return s; };
     if (hipSetDevice(nd->device) != hipSuccess) return fail(ICET_ERR_NO_DEVICE);
-    if (hipMalloc(reinterpret_cast<void**>(&nd->d_nkept), 2 * sizeof(int32_t)) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&nd->h_nkept), sizeof(int32_t), hipHostMallocCoherent) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&nd->d_x0), sizeof(float) * 6) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&nd->d_out), sizeof(float) * 48) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&nd->h_out), sizeof(float) * 48, hipHostMallocCoherent) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&nd->h_x0), sizeof(float) * 6) != hipSuccess)
+    icet::BufferGroup& m = nd->fixed;
+    if (m.device(nd->d_nkept, 2) || m.pinned(nd->h_nkept, 1, hipHostMallocCoherent) || m.device(nd->d_x0, 6) || m.device(nd->d_out, 48) ||
+        m.pinned(nd->h_out, 48, hipHostMallocCoherent) || m.pinned(nd->h_x0, 6))
         return fail(ICET_ERR_NOMEM);
     if (p->map_capacity > 0) nd->fast_shuffle = fast_shuffle_ok();
     for (hipEvent_t& e : nd->ev) if (hipEventCreate(&e) != hipSuccess) return fail(ICET_ERR_HIP);
@@ -830,7 +825,7 @@ icet_status icet_node_create(icet_ctx* ctx, const icet_node_params* p, icet_node
         nd->pipelined = true;
     }
     { const icet_status ss = stream_create(*p, nd->s); if (ss != ICET_OK) return fail(ss); }
-    if (p->map_capacity > 0 && hipMalloc(reinterpret_cast<void**>(&nd->d_idx), sizeof(int32_t) * (size_t)std::max(p->map_downsample, 1)) != hipSuccess) return fail(ICET_ERR_NOMEM);
+    if (p->map_capacity > 0 && m.device(nd->d_idx, (size_t)std::max(p->map_downsample, 1)) != 0) return fail(ICET_ERR_NOMEM);
     *out = nd;
     return ICET_OK;
 }
@@ -844,17 +839,11 @@ icet_status icet_node_destroy(icet_node* nd) {
     kf_worker_stop(nd);                      // (drains what it still has to enqueue, then joins)
     (void)hipSetDevice(nd->device);
     (void)hipDeviceSynchronize();            // not the borrowed stream: the context may already be gone
-    stream_destroy(nd->s);
-    void* dp[] = {nd->d_stage, nd->d_counts, nd->d_bases, nd->d_nkept, nd->d_x0, nd->d_out, nd->d_idx,
-                  nd->d_scan_kf[0], nd->d_scan_kf[1], nd->d_counts_kf, nd->d_bases_kf, nd->d_nkept_kf};
-    for (void* q : dp) if (q) (void)hipFree(q);
-    void* hp[] = {nd->h_nkept, nd->h_out, nd->h_x0, nd->h_frame, nd->h_done};
-    for (void* q : hp) if (q) (void)hipHostFree(q);
     for (hipEvent_t e : nd->ev) if (e) (void)hipEventDestroy(e);
     if (nd->ev_f2) (void)hipEventDestroy(nd->ev_f2);
     for (hipEvent_t e : nd->ev_kfdone) if (e) (void)hipEventDestroy(e);
     for (icet_ctx* k : nd->kf) if (k) (void)icet_destroy(k);
-    delete nd;
+    delete nd;                               // (its buffer groups and the stream's free here: behind the synchronisation, with the node's device current)
     return ICET_OK;
 }
 
@@ -886,9 +875,7 @@ icet_status icet_node_push(icet_node* nd, const float* scan, int64_t n, int64_t 
     const int64_t l = (n + 63) / 64 * 64;
     if (3 * l > nd->cap_stage) {
         NCHK(nd, hipStreamSynchronize(nd->stream));
-        if (nd->d_stage) { NCHK(nd, hipFree(nd->d_stage)); nd->d_stage = nullptr; }
-        NCHK(nd, hipMalloc(reinterpret_cast<void**>(&nd->d_stage), sizeof(float) * 3 * (size_t)(l + l / 8)));
-        nd->cap_stage = 3 * (l + l / 8);
+        NCHK(nd, icet::grow(nd->stage_mem, nd->cap_stage, 3 * (l + l / 8), [&] { return nd->stage_mem.device(nd->d_stage, 3 * (size_t)(l + l / 8)); }));
     }
     if (n) NCHK(nd, hipMemcpy2DAsync(nd->d_stage, l * sizeof(float), scan, ld * sizeof(float), n * sizeof(float), 3, hipMemcpyHostToDevice, nd->stream));
     return push_device(nd, nd->d_stage, n, l, res);
@@ -1061,10 +1048,11 @@ struct icet_node_group {
     std::string err;
     int32_t n_streams = 0;
     bool fast_shuffle = false;
-    std::vector<StreamState> s;
+    std::unique_ptr<StreamState[]> s;                            // n_streams of them, made once: a stream's buffer groups hold the addresses of its pointers
     // per-call tables, by position in the call (the solved frames first): row counts on the device and pinned, X0 and results pinned, results on the device (runlen 0)
     int32_t* d_rows = nullptr; int32_t* h_rows = nullptr; float* h_x0 = nullptr; float* h_out = nullptr; float* d_out = nullptr;
     int32_t* d_counts = nullptr; int32_t* d_bases = nullptr; int64_t cap_blocks = 0;     // the ragged filter's block counts / bases
+    icet::BufferGroup fixed, blocks_mem;                         // owners: the per-call tables (creation); d_counts + d_bases
     DrawPool* pool = nullptr;
 };
 
@@ -1085,11 +1073,11 @@ icet_status group_push_frames(icet_node_group* g, int32_t n, const int32_t* ids,
     for (int j = 0; j < n; j++) {
         const int i = order[(size_t)j]; StreamState& st = g->s[(size_t)ids[i]];
         const int to = j < K ? (st.prev ^ 1) : st.prev;
-        icet_status s = grow_rows(g, st.d_scan[to], st.cap_scan[to], frames[i].n, drain); if (s != ICET_OK) return s;
-        if (j < K && (p.flags & ICET_NODE_ALIGNED_CLOUD)) { s = grow_rows(g, st.d_aligned, st.cap_aligned, st.cap_scan[to], drain); if (s != ICET_OK) return s; }
+        icet_status s = grow_rows(g, st.scan_mem[to], st.d_scan[to], st.cap_scan[to], frames[i].n, drain); if (s != ICET_OK) return s;
+        if (j < K && (p.flags & ICET_NODE_ALIGNED_CLOUD)) { s = grow_rows(g, st.aligned_mem, st.d_aligned, st.cap_aligned, st.cap_scan[to], drain); if (s != ICET_OK) return s; }
         total_blocks += (frames[i].n + kFB * kFRows - 1) / (kFB * kFRows);
     }
-    { const icet_status s = grow_blocks(g, g->d_counts, g->d_bases, g->cap_blocks, total_blocks, drain); if (s != ICET_OK) return s; }
+    { const icet_status s = grow_blocks(g, g->blocks_mem, g->d_counts, g->d_bases, g->cap_blocks, total_blocks, drain); if (s != ICET_OK) return s; }
     // ---- the range filter of every frame (odometry.cpp:57-70), kGroupMaxFrames frames per launch triple ----
     for (int j = 0; j < n; j++) static_cast<volatile int32_t*>(g->h_rows)[j] = -1;                // ("not yet": watched below)
     int64_t blk0 = 0;
@@ -1211,17 +1199,16 @@ icet_status icet_node_group_create(icet_ctx* ctx, const icet_node_params* p, int
     auto fail = [&](icet_status s) { icet_node_group_destroy(g); return s; };
     try {
         g->ctx = ctx; g->p = *p; g->n_streams = n_streams; g->stream = reinterpret_cast<hipStream_t>(icet_stream(ctx)); g->device = icet_device(ctx);
-        g->s.resize((size_t)n_streams);
+        g->s.reset(new StreamState[(size_t)n_streams]);
         g->pool = new DrawPool();
     } catch (...) { return fail(ICET_ERR_NOMEM); }
     if (hipSetDevice(g->device) != hipSuccess) return fail(ICET_ERR_NO_DEVICE);
     const size_t S = (size_t)n_streams;
-    if (hipMalloc(reinterpret_cast<void**>(&g->d_rows), sizeof(int32_t) * S) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&g->h_rows), sizeof(int32_t) * S, hipHostMallocCoherent) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&g->h_x0), sizeof(float) * 6 * S) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&g->h_out), sizeof(float) * 48 * S, hipHostMallocCoherent) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&g->d_out), sizeof(float) * 48 * S) != hipSuccess)
+    icet::BufferGroup& m = g->fixed;
+    if (m.device(g->d_rows, S) || m.pinned(g->h_rows, S, hipHostMallocCoherent) || m.pinned(g->h_x0, 6 * S) || m.pinned(g->h_out, 48 * S, hipHostMallocCoherent) || m.device(g->d_out, 48 * S))
         return fail(ICET_ERR_NOMEM);
     if (p->map_capacity > 0) g->fast_shuffle = fast_shuffle_ok();
-    for (StreamState& st : g->s) { const icet_status ss = stream_create(*p, st); if (ss != ICET_OK) return fail(ss); }
+    for (size_t i = 0; i < S; i++) { const icet_status ss = stream_create(*p, g->s[i]); if (ss != ICET_OK) return fail(ss); }
     *out = g;
     return ICET_OK;
 }
@@ -1231,12 +1218,7 @@ icet_status icet_node_group_destroy(icet_node_group* g) {
     delete g->pool; g->pool = nullptr;                            // (joins the helpers: none is drawing between calls)
     (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();                                 // not the borrowed stream: the context may already be gone
-    for (StreamState& st : g->s) stream_destroy(st);
-    void* dp[] = {g->d_rows, g->d_out, g->d_counts, g->d_bases};
-    for (void* q : dp) if (q) (void)hipFree(q);
-    void* hp[] = {g->h_rows, g->h_x0, g->h_out};
-    for (void* q : hp) if (q) (void)hipHostFree(q);
-    delete g;
+    delete g;                                                     // (its buffer groups and its streams' free here: behind the synchronisation, with the group's device current)
     return ICET_OK;
 }
 

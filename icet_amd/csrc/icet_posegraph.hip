@@ -477,8 +477,8 @@ icet_status icet_debug_block_tridiag(icet_ctx* c, int32_t n, const double* diag,
     if (!c || !diag || !sub || !rhs || !x || !status || n < 1 || n > pg::kMaxNodes) return ICET_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n36 = (size_t)n * 36, n6 = (size_t)n * 6;
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * (4 * n36 + 3 * n6 + 1)));
+    double* d = nullptr; BufferGroup g;                                      // (freed at every return: behind the synchronisation below)
+    HIPCHK(c, g.device(d, 4 * n36 + 3 * n6 + 1));
     double *dD = d, *dB = d + n36, *dG = dB + n36, *dW = dG + n36, *dr = dW + n36, *dx = dr + n6, *du = dx + n6;
     int32_t* ds = reinterpret_cast<int32_t*>(du + n6);
     hipError_t e = hipMemcpyAsync(dD, diag, sizeof(double) * n36, hipMemcpyHostToDevice, c->stream);
@@ -489,7 +489,6 @@ icet_status icet_debug_block_tridiag(icet_ctx* c, int32_t n, const double* diag,
     if (e == hipSuccess) e = hipMemcpyAsync(status, ds, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;
-    (void)hipFree(d);
     if (e != hipSuccess) { c->err = std::string("icet_debug_block_tridiag: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
     return ICET_OK;
 }

@@ -300,11 +300,7 @@ icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, cons
     const icet_status ok = slots_ok(s, n, slots, true, "set_pose");
     if (ok != ICET_OK) return ok;
     if (s->pose_in_flight) { STORECHK(s, hipEventSynchronize(s->ev_pose)); s->pose_in_flight = false; }      // the previous set_pose's kernel has read the staging
-    if (n > s->cap_h_pose) {
-        s->cap_h_pose = 0, s->pose_stage.release();
-        STORECHK(s, s->pose_stage.pinned(s->h_pose, (size_t)n));
-        s->cap_h_pose = n;
-    }
+    if (n > s->cap_h_pose) STORECHK(s, grow(s->pose_stage, s->cap_h_pose, n, [&] { return s->pose_stage.pinned(s->h_pose, (size_t)n); }));
     if (!s->ev_pose) STORECHK(s, hipEventCreateWithFlags(&s->ev_pose, hipEventDisableTiming));
     for (int k = 0; k < n; k++) {
         PoseUpload& u = s->h_pose[k];
@@ -341,17 +337,22 @@ static icet_status closure_ensure(icet_keyframe_store* s, int32_t n_queries, int
     const int32_t qk = n_queries * K;
     if (need_part <= s->cap_part && qk <= s->cap_qk && n_regs <= s->cap_qr && s->q_best) return ICET_OK;
     STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
-    // (as in the context: a group is released with its capacity zeroed, and the capacity -- for the fixed pair, the last pointer -- is set after the last allocation)
+    // (the fixed pair's capacity is its last pointer, set after the last allocation; the other three grow by grow(), icet_buffers.h)
     if (!s->q_best) { s->q_fixed.release(); STORECHK(s, s->q_fixed.device(s->q_offs, (size_t)kClosureMaxQueries + 1)); STORECHK(s, s->q_fixed.device(s->q_best, (size_t)kClosureMaxQueries)); }
-    if (need_part > s->cap_part) { s->cap_part = 0, s->q_part_mem.release(); STORECHK(s, s->q_part_mem.device(s->q_part, need_part)); s->cap_part = need_part; }
-    if (qk > s->cap_qk) { BufferGroup& g = s->q_qk_mem; s->cap_qk = 0, g.release(); STORECHK(s, g.device(s->q_keys, (size_t)qk)); STORECHK(s, g.device(s->q_cand, (size_t)qk)); s->cap_qk = qk; }
+    if (need_part > s->cap_part) STORECHK(s, grow(s->q_part_mem, s->cap_part, need_part, [&] { return s->q_part_mem.device(s->q_part, need_part); }));
+    if (qk > s->cap_qk) { BufferGroup& g = s->q_qk_mem; STORECHK(s, grow(g, s->cap_qk, qk, [&] { const int e = g.device(s->q_keys, (size_t)qk); return e ? e : g.device(s->q_cand, (size_t)qk); })); }
     if (n_regs > s->cap_qr) {
         BufferGroup& g = s->q_qr_mem;
-        s->cap_qr = 0, g.release();
         const size_t r = (size_t)n_regs;
-        STORECHK(s, g.device(s->q_x0, r * 6)); STORECHK(s, g.device(s->q_out, r * 48)); STORECHK(s, g.device(s->q_score, r));
-        STORECHK(s, g.device(s->q_kf_of, r)); STORECHK(s, g.device(s->q_rows, r)); STORECHK(s, g.device(s->q_members, r));
-        s->cap_qr = n_regs;
+        STORECHK(s, grow(g, s->cap_qr, n_regs, [&] {
+            int e = g.device(s->q_x0, r * 6);
+            if (!e) e = g.device(s->q_out, r * 48);
+            if (!e) e = g.device(s->q_score, r);
+            if (!e) e = g.device(s->q_kf_of, r);
+            if (!e) e = g.device(s->q_rows, r);
+            if (!e) e = g.device(s->q_members, r);
+            return e;
+        }));
     }
     return ICET_OK;
 }
@@ -502,9 +503,7 @@ static icet_status app_ensure(icet_keyframe_store* s, int32_t n_queries) {
     if (need <= s->app->cap_all) return ICET_OK;
     STORECHK(s, hipStreamSynchronize(c->stream));              // no query in flight reads the buffers that move
     BufferGroup& g = s->app->all;
-    s->app->cap_all = 0, g.release();
-    STORECHK(s, g.device(s->app->keys_all, need)); STORECHK(s, g.device(s->app->shift_all, need));
-    s->app->cap_all = need;
+    STORECHK(s, grow(g, s->app->cap_all, need, [&] { const int e = g.device(s->app->keys_all, need); return e ? e : g.device(s->app->shift_all, need); }));
     return ICET_OK;
 }
 

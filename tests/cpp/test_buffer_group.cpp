@@ -1,7 +1,8 @@
 // tests/cpp/test_buffer_group.cpp -- icet::BufferGroup (icet_amd/csrc/icet_buffers.h) on the host: the four icet::mem functions over malloc, with counters, a
 // table of live blocks (a free of anything else, or a second free, ends the program) and a "fail the k-th allocation" switch.  Every block has its exact size, so
-// the address sanitizer sees a write past one and a use after release.  What it checks: a refused allocation at every position of a group of six, and the
-// grow-then-swap of the keyframe store's reserve with a refusal at every position.
+// the address sanitizer sees a write past one and a use after release.  What it checks: a refused allocation at every position of a group of six, the
+// grow-then-swap of the keyframe store's reserve with a refusal at every position, and the grow step (icet::grow) of a one-buffer group and of a pair with a
+// refusal at every position, a retry, a growth that is not needed, and a second call at the old size after a refused growth.
 // Build: g++ -std=c++17 -I <repo root> (also with -fsanitize=address,undefined).  Prints one line per case and OK.
 #include "icet_amd/csrc/icet_buffers.h"
 
@@ -140,11 +141,63 @@ void reserve_cases() {
     CHECK(live.empty() && frees - f0 == allocs - a0);
     std::printf("reserve: rows carried over, old tables freed once, balance %ld\n", (allocs - a0) - (frees - f0));
 }
+
+// The grow step as its callers use it: a capacity check, (the drain), icet::grow.  One buffer sized like a scan (3 floats per row), and a pair like the range
+// filter's block counts and bases.
+struct Grown {
+    float* rows = nullptr; int64_t cap_rows = 0;
+    int32_t* counts = nullptr; int32_t* bases = nullptr; int64_t cap_blocks = 0;
+    icet::BufferGroup rows_mem, blocks_mem;
+};
+int ensure_rows(Grown& s, int64_t n) {
+    if (n <= s.cap_rows) return 0;
+    return icet::grow(s.rows_mem, s.cap_rows, n, [&] { return s.rows_mem.device(s.rows, 3 * (size_t)n); });
+}
+int ensure_blocks(Grown& s, int64_t n) {
+    if (n <= s.cap_blocks) return 0;
+    return icet::grow(s.blocks_mem, s.cap_blocks, n, [&] { const int e = s.blocks_mem.device(s.counts, (size_t)n); return e ? e : s.blocks_mem.device(s.bases, (size_t)n); });
+}
+
+// `pair`: the counts-and-bases pair (two allocations), else the one buffer.  Grown to 5, then to 40 with allocation k refused, then the retry.
+void grow_refused_at(bool pair, int k) {
+    const long a0 = allocs, f0 = frees;
+    const int per = pair ? 2 : 1;
+    auto s = std::make_unique<Grown>();
+    auto ensure = [&](int64_t n) { return pair ? ensure_blocks(*s, n) : ensure_rows(*s, n); };
+    auto cap = [&] { return pair ? s->cap_blocks : s->cap_rows; };
+    auto all_null = [&] { return pair ? (!s->counts && !s->bases) : !s->rows; };
+    auto bytes_ok = [&](int64_t n) {
+        if (pair) return live.at(s->counts).bytes == 4 * (size_t)n && live.at(s->bases).bytes == 4 * (size_t)n;
+        return live.at(s->rows).bytes == 12 * (size_t)n;
+    };
+    auto fill = [&](int64_t n, int v) { if (pair) { std::memset(s->counts, v, 4 * (size_t)n); std::memset(s->bases, v, 4 * (size_t)n); } else std::memset(s->rows, v, 12 * (size_t)n); };
+    CHECK(ensure(5) == 0 && cap() == 5 && bytes_ok(5));
+    fill(5, 0x11);
+    CHECK(allocs - a0 == per && frees == f0);
+    CHECK(ensure(5) == 0 && ensure(3) == 0 && allocs - a0 == per && frees == f0);                   // not needed: nothing allocated, nothing freed
+    arm(k);
+    CHECK(ensure(40) == 2);                                                                         // the runtime's code
+    arm(0);
+    CHECK(cap() == 0 && all_null() && s->rows_mem.empty() && s->blocks_mem.empty());
+    CHECK(allocs - a0 == per + (k - 1) && frees - f0 == allocs - a0 && live.empty());               // the old blocks and what the refused growth got: each freed once
+    // the shape of the two holes: a second call at the OLD size after the refusal must allocate, not "fit"
+    CHECK(ensure(5) == 0 && cap() == 5 && !all_null() && bytes_ok(5) && allocs - a0 == 2 * per + (k - 1));
+    fill(5, 0x22);
+    CHECK(ensure(40) == 0 && cap() == 40 && bytes_ok(40));                                          // the retry: the wanted capacity, exact sizes
+    fill(40, 0x33);
+    CHECK((int)live.size() == per && allocs - a0 == 3 * per + (k - 1) && frees - f0 == 2 * per + (k - 1));
+    s.reset();
+    CHECK(live.empty() && frees - f0 == allocs - a0);
+    std::printf("grow %s, allocation %d refused: capacity 0 and null slots, old blocks freed once, old size allocates, retry ok, balance %ld\n", pair ? "pair" : "one", k,
+                (allocs - a0) - (frees - f0));
+}
 }  // namespace
 
 int main() {
     for (int k = 1; k <= 6; k++) six_refused_at(k);
     reserve_cases();
+    grow_refused_at(false, 1);
+    for (int k = 1; k <= 2; k++) grow_refused_at(true, k);
     CHECK(live.empty() && allocs == frees);
     std::printf("allocations %ld, frees %ld\nOK\n", allocs, frees);
     return 0;

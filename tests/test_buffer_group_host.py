@@ -1,6 +1,6 @@
 """The owner of the context's and the keyframe store's memory, icet::BufferGroup (icet_amd/csrc/icet_buffers.h), on the host: tests/cpp/test_buffer_group.cpp defines
-the four icet::mem functions over malloc and refuses the k-th allocation, for every k, of a group of six and of the store's grow-then-swap.  No GPU, nothing loaded
-into Python."""
+the four icet::mem functions over malloc and refuses the k-th allocation, for every k, of a group of six, of the store's grow-then-swap and of the grow step
+(icet::grow) on a one-buffer group and on a pair.  No GPU, nothing loaded into Python."""
 import os
 import subprocess
 
@@ -22,3 +22,4 @@ def test_buffer_group_standalone_under_sanitizers(tmp_path):
     assert outs["plain"] == outs["san"] and outs["plain"].endswith(b"OK\n")
     lines = outs["plain"].decode().splitlines()
     assert sum(l.startswith("six, allocation") for l in lines) == 6 and sum(l.startswith("reserve, allocation") for l in lines) == 3
+    assert sum(l.startswith("grow one, allocation") for l in lines) == 1 and sum(l.startswith("grow pair, allocation") for l in lines) == 2

@@ -299,6 +299,43 @@ def test_gpu_map_maker_node_matches_oracle(gpu_ctx, seq64):
 
 
 @pytest.mark.gpu
+def test_gpu_node_staging_and_aligned_cloud_grow_once_and_are_reused(gpu_ctx):
+    """The two buffers of a node that no other test grows and then reuses: the staging of the host-pointer push and the aligned cloud.  One node with
+    ICET_NODE_ALIGNED_CLOUD and a map takes host frames of ~315, ~315, ~5400 and ~315 rows (4 x 96 and 16 x 384 rays).  The first frame is only stored, so the
+    second one makes the aligned cloud at the small size; the third outgrows the staging, a scan buffer and the aligned cloud; the fourth fits all of them and
+    leaves the aligned cloud with a leading dimension far above its rows.  Frame by frame against the oracle's node, as test_gpu_map_maker_node_matches_oracle
+    compares: decisions equal, X within 3e-4, map within 2e-3 (the aligned cloud is the same kind of row, rows * R^-1 - t: the same 2e-3), the filtered scan
+    bit for bit.  Twice, each with a node of its own that is destroyed at the end:
+      * the map maker's grid (24 x 75, 25 rows make a voxel): at most 16 rings x 6 rays of a frame fall into one voxel's azimuth, so no voxel is ever fitted, X
+        stays 0 and R = I on both sides;
+      * a coarse grid that does fit voxels, with the guard tripped on every frame (thresholds 1e-6): the solve runs on the grown buffers, X is zeroed, and the ring
+        and the aligned cloud only move data -- bit for bit, wrap-around included (700 ring rows, 250 a frame)."""
+    from oracle import pyoracle as po
+    from icet_amd import api
+    small, large = _sequence(4, rings=4, steps=96), _sequence(4, rings=16, steps=384)
+    frames = [small[0], small[1], large[2], small[3]]
+    assert [250 < len(f) < 384 for f in frames] == [True, True, False, True] and 5000 < len(frames[2]) < 6144
+    base = dict(api.MAP_MAKER_NODE); base.update(map_capacity=700, map_downsample=250, runlen=7, min_range=3.0, flags=api.NODE_ALIGNED_CLOUD)
+    for name, extra in (("nothing fitted", dict()), ("guard tripped", dict(bins_phi=8, bins_theta=24, n=3, trans_thresh=1e-6, rot_thresh=1e-6))):
+        kw = dict(base); kw.update(extra)
+        g, o = api.Node(gpu_ctx, **kw), po.Node(**kw)
+        for k, s in enumerate(frames):
+            rg, ro = g.push(s), o.push(s)
+            assert rg["solved"] == ro["solved"] == (k > 0) and rg["n_kept"] == ro["n_kept"] and rg["map_rows"] == ro["map_rows"] and rg["diverged"] == ro["diverged"], (name, k, rg, ro)
+            expect = s if k == 0 else _range_filter(s, 3.0)
+            assert 0 < len(expect) and (k == 0 or len(expect) < len(s))
+            assert np.array_equal(g.prev_scan(), expect), (name, k)
+            assert np.abs(rg["X"] - ro["X"]).max() <= 3e-4 and np.abs(rg["pose"] - ro["pose"]).max() <= 1e-3, (name, k, rg["X"], ro["X"])
+            mg, mo, ag, ao = g.map(), o.map(), g.aligned(), o.aligned()
+            assert mg.shape == mo.shape == (min(250 * k, 700), 3) and ag.shape == ao.shape == ((len(expect), 3) if k else (0, 3)), (name, k, mg.shape, ag.shape)
+            if k:
+                assert np.abs(mg - mo).max() <= 2e-3 and np.abs(ag - ao).max() <= 2e-3, (name, k)
+                if extra:
+                    assert rg["diverged"] == 1 and np.array_equal(mg, mo) and np.array_equal(ag, ao) and np.array_equal(ag, expect), (name, k)
+        g.close(); o.close()
+
+
+@pytest.mark.gpu
 def test_gpu_range_filter_full_size_and_device_push(gpu_ctx):
     """config-5 size (524288 rows), rows on both sides of the threshold and exactly on it, pushed from HBM."""
     from icet_amd import api
