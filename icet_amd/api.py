@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_keyframe_store_close_coarse_device",
                     "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_pose_graph_optimize_robust", "icet_pose_graph_optimize_robust_device", "icet_debug_pose_graph_step", "icet_debug_pose_graph_direct",
                     "icet_pose_graph_marginals", "icet_pose_graph_marginals_device", "icet_debug_pose_graph_marginals",
+                    "icet_pose_graph_covariance_columns", "icet_pose_graph_covariance_columns_device", "icet_pose_graph_gate", "icet_pose_graph_gate_device",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -173,6 +174,12 @@ class PoseGraphMarginalsDebug(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ARRAYS] + [("ends", C.c_void_p), ("ends_capacity", C.c_int32), ("reserved", C.c_int32), ("result", PoseGraphMarginalsResult)]
 
 
+class PoseGraphGateResult(C.Structure):
+    """icet_pose_graph_gate_result (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("marg", PoseGraphMarginalsResult), ("n_targets", C.c_int32), ("rejected", C.c_int32)]
+
+
+assert C.sizeof(PoseGraphGateResult) == 32
 assert C.sizeof(PoseGraphOptions) == 32 and C.sizeof(PoseGraphResult) == 40 and C.sizeof(PoseGraphStep) == 152 and C.sizeof(PoseGraphDirectStep) == 176
 assert C.sizeof(PoseGraphMarginalsResult) == 24 and C.sizeof(PoseGraphMarginalsDebug) == 80
 assert C.sizeof(PoseGraphRobust) == 16 and C.sizeof(PoseGraphRobustResult) == 64
@@ -184,6 +191,8 @@ PG_ROBUST_DEFAULT_SCALE = 16.8119
 PG_SOLVER_CG, PG_SOLVER_DIRECT, PG_SOLVER_AUTO = range(3)
 PG_SOLVERS = {"cg": PG_SOLVER_CG, "direct": PG_SOLVER_DIRECT, "auto": PG_SOLVER_AUTO}
 PG_DIRECT_MAX_ENDS = 128
+PG_MAX_TARGETS = 32          # icet_pose_graph_covariance_columns: targets per call; icet_pose_graph_gate: distinct live nodes per call
+PG_GATE_MAX_CANDIDATES = 512
 
 
 def pose_graph_ends(n, closures, fixed=None):
@@ -243,6 +252,17 @@ def position_cov_world(poses, cov):
     return R @ c @ R.transpose(0, 2, 1)
 
 
+def relative_cov(J, cov_i, cov_j, cov_ij):
+    """6 x 6: J [[cov_i, cov_ij], [cov_ij^T, cov_j]] J^T for a 6 x 12 Jacobian J = [J_i | J_j] of a function of two poses -- the covariance of that function
+    under the graph.  cov_i, cov_j are the poses' marginals (Context.pose_graph_marginals), cov_ij is block (i, j) of H^-1: ``cols[t][i]`` of
+    Context.pose_graph_covariance_columns with targets[t] = j.  For callers with their own Jacobians; Context.pose_graph_gate has the optimiser's.  The result
+    is symmetric bit for bit."""
+    J = np.asarray(J, np.float64).reshape(6, 12)
+    ci, cj, cij = (np.asarray(x, np.float64).reshape(6, 6) for x in (cov_i, cov_j, cov_ij))
+    S = J @ np.block([[ci, cij], [cij.T, cj]]) @ J.T
+    return 0.5 * (S + S.T)
+
+
 def info_from_cov(cov):
     """The information matrix of a registration for the pose graph: the symmetrised pseudo-inverse of its 6 x 6 ``cov`` in double, rounded to float32."""
     c = np.asarray(cov, np.float64).reshape(6, 6)
@@ -262,6 +282,22 @@ def closure_edges(records, live_nodes, node_of_slot):
         if i != j:
             edges.append((i, j, np.asarray(r["X"], np.float32).copy(), info_from_cov(r["cov"])))
     return edges
+
+
+def closure_candidates(records, live_nodes, node_of_slot):
+    """closure_edges with the record's covariance in the place of the information: the candidates (i, j, X, cov) of the ACCEPTED records, as
+    Context.pose_graph_gate takes them.  find -> gate -> edges:
+        cands = closure_candidates(records, live_nodes, node_of_slot)
+        keep = ctx.pose_graph_gate(poses, odo_X, odo_info, closures, cands)["accepted"]
+        closures += [(i, j, X, info_from_cov(cov)) for (i, j, X, cov), ok in zip(cands, keep) if ok]"""
+    cands = []
+    for q, r in enumerate(records):
+        if r["slot"] is None or not r["accepted"]:
+            continue
+        i, j = int(node_of_slot[r["slot"]]), int(live_nodes[q])
+        if i != j:
+            cands.append((i, j, np.asarray(r["X"], np.float32).copy(), np.asarray(r["cov"], np.float32).reshape(6, 6).copy()))
+    return cands
 
 
 # The recommended start offsets of a query by appearance (INTEGRATION "Loop closure without poses"): the search gives the yaw, not the translation, so
@@ -385,6 +421,13 @@ def load_library():
     L.icet_pose_graph_marginals.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.POINTER(PoseGraphMarginalsResult)]
     L.icet_pose_graph_marginals_device.argtypes = L.icet_pose_graph_marginals.argtypes
+    L.icet_pose_graph_covariance_columns.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseGraphMarginalsResult)]
+    L.icet_pose_graph_covariance_columns_device.argtypes = L.icet_pose_graph_covariance_columns.argtypes
+    L.icet_pose_graph_gate.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(PoseGraphGateResult)]
+    L.icet_pose_graph_gate_device.argtypes = L.icet_pose_graph_gate.argtypes
     L.icet_debug_pose_graph_marginals.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(PoseGraphMarginalsDebug)]
     L.icet_debug_pose_graph_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -855,6 +898,82 @@ class Context:
         torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
         self._check(load_library().icet_pose_graph_marginals_device(*g.args, _vp(cov.data_ptr()), C.byref(res)))
         return dict(self._pose_graph_marginals_result(res), cov=cov)
+
+    @staticmethod
+    def _pose_graph_targets(targets):
+        t = np.ascontiguousarray(np.asarray(targets).reshape(-1), np.int32)
+        if t.shape[0] < 1:
+            raise IcetError(ICET_ERR_BAD_ARG, "targets must name at least one node")
+        return t
+
+    def pose_graph_covariance_columns(self, poses, odo_X, odo_info, closures=(), targets=(), fixed=None):
+        """icet_pose_graph_covariance_columns: how well the poses are known relative to the ``targets`` (1 .. PG_MAX_TARGETS distinct nodes).  The graph as
+        pose_graph_marginals takes it.  Returns dict(cols T x n x 6 x 6 float64, cov n x 6 x 6, status, m, factor_status, wm_status, ks_status): ``cols[t][k]`` is
+        block (k, targets[t]) of the inverse of the Gauss-Newton H, rows node k's tangent and columns the target's; ``cov`` carries the bits of
+        pose_graph_marginals, and so does ``cols[t][targets[t]]``.  A block that touches a fixed node is zero.  A status of 2 or 3 is a result: every block
+        between two free nodes is then NaN.  relative_cov turns the blocks into the covariance of a function of two poses."""
+        g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed)
+        t = self._pose_graph_targets(targets)
+        cols = np.zeros((t.shape[0], g.n, 6, 6), np.float64); cov = np.zeros((g.n, 6, 6), np.float64); res = PoseGraphMarginalsResult()
+        self._check(load_library().icet_pose_graph_covariance_columns(*g.args, t.shape[0], t.ctypes.data, cols.ctypes.data, cov.ctypes.data, C.byref(res)))
+        return dict(self._pose_graph_marginals_result(res), cols=cols, cov=cov)
+
+    def pose_graph_covariance_columns_device(self, poses, odo_X, odo_info, closures=(), targets=(), fixed=None, clo_X=None, clo_info=None):
+        """icet_pose_graph_covariance_columns_device for torch tensors on this context's device, with the conventions of pose_graph_marginals_device.  Returns
+        the dict of pose_graph_covariance_columns with ``cols`` and ``cov`` as float64 tensors on the device.  The call returns when the result is known."""
+        import torch
+        g = self._pose_graph_device(poses, odo_X, odo_info, closures, fixed, clo_X, clo_info)
+        t = self._pose_graph_targets(targets)
+        cols = torch.zeros((t.shape[0], g.n, 6, 6), dtype=torch.float64, device=poses.device)
+        cov = torch.zeros((g.n, 6, 6), dtype=torch.float64, device=poses.device); res = PoseGraphMarginalsResult()
+        torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
+        self._check(load_library().icet_pose_graph_covariance_columns_device(*g.args, t.shape[0], t.ctypes.data, _vp(cols.data_ptr()), _vp(cov.data_ptr()), C.byref(res)))
+        return dict(self._pose_graph_marginals_result(res), cols=cols, cov=cov)
+
+    @staticmethod
+    def _pose_graph_gate_result(res, threshold, d2, status):
+        return dict(status=int(res.marg.status), m=int(res.marg.m), n_targets=int(res.n_targets), rejected=int(res.rejected), threshold=threshold,
+                    accepted=(d2 < threshold) & (status == 0))
+
+    def pose_graph_gate(self, poses, odo_X, odo_info, closures, candidates, fixed=None, threshold=None):
+        """icet_pose_graph_gate: is each candidate closure plausible under what the graph knows?  The graph as pose_graph_marginals takes it; ``candidates`` is a
+        list of (i, j, X, cov) -- keyframe node i seen from live node j with the measurement X and its 6 x 6 covariance, as closure_candidates returns them -- that
+        are NOT edges of the graph yet (their noise would be counted twice).  Returns dict(d2 (the squared Mahalanobis distance of the residual under the
+        covariance of the relative pose plus cov), res_cov n_cand x 6 x 6 (that covariance S), cand_status (0; 2: S is not positive definite; 3: not finite),
+        accepted (d2 < threshold and cand_status 0), rejected, n_targets, threshold, status, m).  ``threshold``: None for PG_ROBUST_DEFAULT_SCALE, the 99 %
+        quantile of chi2 with six degrees of freedom.  At most PG_GATE_MAX_CANDIDATES candidates with at most PG_MAX_TARGETS distinct live nodes per call."""
+        candidates = list(candidates)
+        g = self._pose_graph_host(poses, odo_X, odo_info, closures, fixed)
+        gi, gj, cX, cC, _ = self._pose_graph_lists(g.n, candidates, None)
+        nc = gi.shape[0]
+        thr = PG_ROBUST_DEFAULT_SCALE if threshold is None else float(threshold)
+        d2 = np.zeros(nc, np.float64); S = np.zeros((nc, 6, 6), np.float64); st = np.zeros(nc, np.int32); res = PoseGraphGateResult()
+        self._check(load_library().icet_pose_graph_gate(*g.args, nc, gi.ctypes.data, gj.ctypes.data, cX.ctypes.data, cC.ctypes.data, thr, d2.ctypes.data, S.ctypes.data,
+                                                        st.ctypes.data, C.byref(res)))
+        thr = thr if thr > 0.0 else PG_ROBUST_DEFAULT_SCALE
+        return dict(self._pose_graph_gate_result(res, thr, d2, st), d2=d2, res_cov=S, cand_status=st)
+
+    def pose_graph_gate_device(self, poses, odo_X, odo_info, closures, gi, gj, cand_X, cand_cov, fixed=None, threshold=None, clo_X=None, clo_info=None):
+        """icet_pose_graph_gate_device for torch tensors on this context's device, with the conventions of pose_graph_marginals_device: ``gi``, ``gj`` the
+        candidates' nodes (host), ``cand_X`` (n_cand x 6) and ``cand_cov`` (n_cand x 6 x 6) contiguous float32 tensors on the device.  Returns the dict of
+        pose_graph_gate with d2, res_cov, cand_status and accepted as tensors on the device.  The call returns when the result is known."""
+        import torch
+        g = self._pose_graph_device(poses, odo_X, odo_info, closures, fixed, clo_X, clo_info)
+        gi = np.ascontiguousarray(np.asarray(gi).reshape(-1), np.int32); gj = np.ascontiguousarray(np.asarray(gj).reshape(-1), np.int32)
+        nc = gi.shape[0]
+        for t in (cand_X, cand_cov):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise IcetError(ICET_ERR_BAD_ARG, "cand_X and cand_cov must be contiguous float32 tensors on the device")
+        if gj.shape[0] != nc or cand_X.numel() != nc * 6 or cand_cov.numel() != nc * 36:
+            raise IcetError(ICET_ERR_BAD_ARG, "gi, gj, cand_X and cand_cov must hold one row per candidate")
+        thr = PG_ROBUST_DEFAULT_SCALE if threshold is None else float(threshold)
+        d2 = torch.zeros(nc, dtype=torch.float64, device=poses.device); S = torch.zeros((nc, 6, 6), dtype=torch.float64, device=poses.device)
+        st = torch.zeros(nc, dtype=torch.int32, device=poses.device); res = PoseGraphGateResult()
+        torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensors must be complete
+        self._check(load_library().icet_pose_graph_gate_device(*g.args, nc, gi.ctypes.data, gj.ctypes.data, _vp(cand_X.data_ptr()), _vp(cand_cov.data_ptr()), thr,
+                                                               _vp(d2.data_ptr()), _vp(S.data_ptr()), _vp(st.data_ptr()), C.byref(res)))
+        thr = thr if thr > 0.0 else PG_ROBUST_DEFAULT_SCALE
+        return dict(self._pose_graph_gate_result(res, thr, d2, st), d2=d2, res_cov=S, cand_status=st)
 
     def debug_pose_graph_marginals(self, poses, odo_X, odo_info, closures=(), fixed=None):
         """icet_debug_pose_graph_marginals: pose_graph_marginals with its intermediate arrays.  Returns its dict with ends (m int32), D, B n x 6 x 6, A C x 6 x 6

@@ -8,7 +8,9 @@
 // Option "pg_solver" replaces the conjugate gradients by a direct solve over the closures' end nodes (icet_posegraph_direct.h): k_pg_z solves the band for
 // all their unit columns in one launch, one thread per column.  icet_pose_graph_marginals[_device] reads the marginal covariance of every pose off that solve's
 // Z, L and Lk and a selected inverse of the band (icet_posegraph_marginals.h).  icet_pose_graph_optimize_robust[_device] runs the same optimiser under a
-// robust kernel (icet_posegraph_robust.h): three small kernels around the unchanged ones.
+// robust kernel (icet_posegraph_robust.h): three small kernels around the unchanged ones.  icet_pose_graph_covariance_columns[_device] and
+// icet_pose_graph_gate[_device] run behind the marginals: the blocks (k, t) of H^-1 for a few target nodes, and the Mahalanobis test of candidate closures
+// under them (icet_posegraph_cross.h the bodies, icet_posegraph_cross.hip their kernels).
 #include "icet_ctx.h"
 #include "icet_posegraph_driver.h"
 
@@ -64,6 +66,8 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_robust_stats(PgArgs a, PgRobu
 // k_pg_selinv is the marginals' sequential part; k_pg_marg runs one workgroup per node
 __global__ __launch_bounds__(kPgThreads) void k_pg_selinv(PgArgs a, PgMarg mg) { __shared__ PgShared sh; pg_group_selinv(a, mg, sh); }
 __global__ __launch_bounds__(kPgThreads) void k_pg_marg(PgArgs a, PgDirect d, PgMarg mg) { __shared__ PgMargShared sh; pg_group_marg(a, d, mg, (int)blockIdx.x, sh); }
+// the covariance columns' and the gate's kernels and their launch: icet_posegraph_cross.hip
+hipError_t pg_launch_cross(PgCrossGroupKernel k, int groups, hipStream_t stream, const PgArgs& a, const PgDirect& d, const PgMarg& mg, const PgCross& x, const PgGate& g);
 
 namespace {
 
@@ -140,6 +144,9 @@ struct PgDeviceBackend {
         }
         return false;
     }
+    bool xgroups(PgCrossGroupKernel k, int groups, const PgArgs& a, const PgDirect& d, const PgMarg& mg, const PgCross& x, const PgGate& g) {
+        return ok(pg_launch_cross(k, groups, stream, a, d, mg, x, g));
+    }
     bool rgrid(PgRobustGridKernel k, int count, const PgArgs& a, const PgRobust& r) {
         switch (k) {
             case kPgRobustScale:  return launch(k_pg_robust_scale, blocks_for(count), kPgGridThreads, a, r, count);
@@ -191,7 +198,12 @@ struct PgFrame {
     // the plan: the work arrays bound beyond pg_bind's, and with host_io the outputs staged in the block (a.poses_out, a.poses64_out, a.edge_chi2_out; null otherwise)
     // robust: the robust run's own arrays (a run with a kind); stage_weight: with host_io its edge weights staged in the block (rb.weight_out)
     bool direct = false, marg = false, stage_poses_out = false, stage_poses64 = false, stage_chi2 = false, robust = false, stage_weight = false;
-    PgArgs a{}; PgDirect dir{}; PgMarg mg{}; PgRobust rb{};
+    // cross: the covariance columns' arrays for `targets`; marg_own_cov / own_cols: cov and cols staged in the block whatever host_io says; gate: the gate's
+    // lists for g_i, g_j, g_tcol, with host_io its measurements (cand_X, cand_cov: the caller's) and outputs staged; gate_S: the residual covariances asked for
+    bool cross = false, marg_own_cov = false, own_cols = false, gate = false, gate_S = false;
+    std::vector<int32_t> targets, g_i, g_j, g_tcol;
+    const float *cand_X = nullptr, *cand_cov = nullptr;
+    PgArgs a{}; PgDirect dir{}; PgMarg mg{}; PgRobust rb{}; PgCross x{}; PgGate gt{};
     PgDeviceBackend be;
     hipError_t e = hipSuccess;              // the first failure of a copy or of the backend
     PgFrame(icet_ctx* c_, const char* name_, bool host_io_, const PgProblem& pb_) : c(c_), name(name_), host_io(host_io_), pb(pb_) {}
@@ -201,7 +213,8 @@ struct PgFrame {
 
 // THE frame of every pose-graph entry: the checks of the problem (outputs_ok: the entry's own output pointers are there), the graph, then plan() -- the entry's
 // own checks behind the graph's, and f's plan --, ONE device block for everything bound and staged, the uploads, body() -- the driver's call and f.down() of
-// what goes back; false for a failure of the backend --, the synchronisation and the error mapping.  The block's order: pg_bind | direct | marginals | robust | staging,
+// what goes back; false for a failure of the backend --, the synchronisation and the error mapping.  The block's order: pg_bind | direct | marginals | robust |
+// columns | gate | staging,
 // the doubles first.  A local BufferGroup owns the block and the pinned scalars: every return frees through it.
 template <class Plan, class Body>
 icet_status pg_run(PgFrame& f, bool outputs_ok, Plan&& plan, Body&& body) {
@@ -224,13 +237,21 @@ icet_status pg_run(PgFrame& f, bool outputs_ok, Plan&& plan, Body&& body) {
     PgArena arena;
     PgGraphDev gd{};
     PgDirectDev dd{};
+    PgCrossDev xd{};
+    PgGateDev gtd{};
+    float *s_cand_X = nullptr, *s_cand_cov = nullptr;
     float *s_poses = nullptr, *s_odo_X = nullptr, *s_odo_info = nullptr, *s_clo_X = nullptr, *s_clo_info = nullptr;      // the staging of the problem's arrays
     auto layout = [&]() {
         arena.used = 0;
         gd = pg_bind(a, arena, n_items);
         if (f.direct) { arena.align8(); dd = pg_bind_direct(a, f.dir, arena, m); }
-        if (f.marg) { arena.align8(); pg_bind_marg(a, f.dir, f.mg, arena, f.host_io); }
+        if (f.marg) { arena.align8(); pg_bind_marg(a, f.dir, f.mg, arena, f.host_io || f.marg_own_cov); }
         if (f.robust) { arena.align8(); pg_bind_robust(a, f.rb, arena); }
+        if (f.cross) { arena.align8(); xd = pg_bind_cross(a, f.dir, f.x, arena, (int)f.targets.size(), f.host_io || f.own_cols); }
+        if (f.gate) {
+            arena.align8(); gtd = pg_bind_gate(f.gt, arena, (int)f.g_i.size(), f.host_io, f.gate_S);
+            if (f.host_io) { s_cand_X = arena.f(f.g_i.size() * 6); s_cand_cov = arena.f(f.g_i.size() * 36); }
+        }
         a.poses_out = nullptr; a.poses64_out = nullptr; a.edge_chi2_out = nullptr;
         if (f.host_io) {
             arena.align8();          // (int32 lists end on a multiple of 4 bytes; the doubles of the staging need 8)
@@ -255,6 +276,13 @@ icet_status pg_run(PgFrame& f, bool outputs_ok, Plan&& plan, Body&& body) {
     up(gd.ei, graph.ei.data(), sizeof(int32_t) * E); up(gd.ej, graph.ej.data(), sizeof(int32_t) * E);
     up(gd.off, graph.off.data(), sizeof(int32_t) * (N + 1)); up(gd.items, graph.items.data(), sizeof(int32_t) * n_items);
     if (f.direct) { up(dd.ends, graph.ends.data(), sizeof(int32_t) * m); up(dd.end_of, graph.end_of.data(), sizeof(int32_t) * N); }
+    if (f.cross) up(xd.targets, f.targets.data(), sizeof(int32_t) * f.targets.size());
+    if (f.gate) {
+        const size_t nc = f.g_i.size();
+        up(gtd.gi, f.g_i.data(), sizeof(int32_t) * nc); up(gtd.gj, f.g_j.data(), sizeof(int32_t) * nc); up(gtd.tcol, f.g_tcol.data(), sizeof(int32_t) * nc);
+        if (f.host_io) { up(s_cand_X, f.cand_X, sizeof(float) * nc * 6); up(s_cand_cov, f.cand_cov, sizeof(float) * nc * 36); f.gt.X = s_cand_X; f.gt.cov = s_cand_cov; }
+        else { f.gt.X = f.cand_X; f.gt.cov = f.cand_cov; }
+    }
     if (f.host_io) {
         up(s_poses, pb.poses, sizeof(float) * N * 16); up(s_odo_X, pb.odo_X, sizeof(float) * (N - 1) * 6); up(s_odo_info, pb.odo_info, sizeof(float) * (N - 1) * 36);
         up(s_clo_X, pb.clo_X, sizeof(float) * C * 6); up(s_clo_info, pb.clo_info, sizeof(float) * C * 36);
@@ -382,10 +410,106 @@ icet_status pg_marginals_entry(icet_ctx* c, bool host_io, const PgProblem& pb, d
     return ICET_OK;
 }
 
+// ---- the covariance columns and the gate: icet_pose_graph_covariance_columns[_device], icet_pose_graph_gate[_device] --------------------------------------------
+// The plan both share: the marginals' limit, then the targets -- 1 .. 32 distinct nodes in range.
+icet_status pg_columns_plan(PgFrame& f, const char* name) {
+    icet_ctx* c = f.c;
+    if (f.m_ends > kPgDirectMaxEnds) {
+        c->err = std::string(name) + ": at most " + std::to_string(kPgDirectMaxEnds) + " end nodes of closures off the band, this graph has " + std::to_string(f.m_ends);
+        return ICET_ERR_UNSUPPORTED;
+    }
+    const size_t T = f.targets.size();
+    if (T < 1 || T > (size_t)kPgCrossMaxTargets) { c->err = std::string(name) + ": 1 .. " + std::to_string(kPgCrossMaxTargets) + " distinct target nodes"; return ICET_ERR_BAD_ARG; }
+    std::vector<uint8_t> seen((size_t)f.pb.n, 0);
+    for (int32_t t : f.targets) {
+        if (t < 0 || t >= f.pb.n || seen[(size_t)t]) { c->err = std::string(name) + ": a target is out of range or named twice"; return ICET_ERR_BAD_ARG; }
+        seen[(size_t)t] = 1;
+    }
+    f.direct = true; f.marg = true; f.cross = true;
+    return ICET_OK;
+}
+
+icet_status pg_columns_entry(icet_ctx* c, bool host_io, const PgProblem& pb, int32_t n_targets, const int32_t* targets, double* cols_out, double* cov_out,
+                             icet_pose_graph_marginals_result* result) {
+    constexpr const char* kName = "icet_pose_graph_covariance_columns";
+    PgFrame f(c, kName, host_io, pb);
+    icet_pose_graph_marginals_result res{};
+    const bool have = targets && cols_out && result && n_targets >= 1 && n_targets <= kPgCrossMaxTargets;
+    if (have) f.targets.assign(targets, targets + n_targets);
+    ICET_TRY(pg_run(f, have,
+        [&]() { f.marg_own_cov = cov_out == nullptr; return pg_columns_plan(f, kName); },
+        [&]() {
+            const size_t N = (size_t)f.a.N;
+            if (!host_io) { f.x.cols = cols_out; if (cov_out) f.mg.cov = cov_out; }
+            if (!pg_columns(f.be, f.a, f.dir, f.mg, f.x, &res)) return false;
+            if (host_io) { f.down(cols_out, f.x.cols, sizeof(double) * (size_t)n_targets * N * 36); f.down(cov_out, f.mg.cov, sizeof(double) * N * 36); }
+            return true;
+        }));
+    *result = res;
+    return ICET_OK;
+}
+
+icet_status pg_gate_entry(icet_ctx* c, bool host_io, const PgProblem& pb, int32_t n_cand, const int32_t* gi, const int32_t* gj, const float* cand_X,
+                          const float* cand_cov, double threshold, double* d2_out, double* res_cov_out, int32_t* cand_status, icet_pose_graph_gate_result* result) {
+    constexpr const char* kName = "icet_pose_graph_gate";
+    PgFrame f(c, kName, host_io, pb);
+    icet_pose_graph_gate_result res{};
+    const bool have = gi && gj && cand_X && cand_cov && d2_out && cand_status && result && n_cand >= 1 && n_cand <= kPgGateMaxCand;
+    ICET_TRY(pg_run(f, have,
+        [&]() {
+            // the targets: the distinct live nodes, ascending
+            if (!pg_gate_targets(pb.n, n_cand, gi, gj, f.targets, f.g_tcol)) { c->err = std::string(kName) + ": a candidate's ends are out of range or equal"; return ICET_ERR_BAD_ARG; }
+            if (f.targets.size() > (size_t)kPgCrossMaxTargets) { c->err = std::string(kName) + ": the candidates have more than " + std::to_string(kPgCrossMaxTargets) + " distinct live nodes"; return ICET_ERR_BAD_ARG; }
+            f.g_i.assign(gi, gi + n_cand); f.g_j.assign(gj, gj + n_cand);
+            f.cand_X = cand_X; f.cand_cov = cand_cov;
+            f.gate = true; f.gate_S = res_cov_out != nullptr; f.marg_own_cov = true; f.own_cols = true;
+            return pg_columns_plan(f, kName);
+        },
+        [&]() {
+            const size_t nc = (size_t)n_cand;
+            if (!host_io) { f.gt.d2 = d2_out; f.gt.S = res_cov_out; f.gt.status = cand_status; }
+            if (!pg_gate(f.be, f.a, f.dir, f.mg, f.x, f.gt, threshold > 0.0 ? threshold : pg::kRobustDefaultScale, &res)) return false;
+            if (host_io) { f.down(d2_out, f.gt.d2, sizeof(double) * nc); f.down(res_cov_out, f.gt.S, sizeof(double) * nc * 36); f.down(cand_status, f.gt.status, sizeof(int32_t) * nc); }
+            return true;
+        }));
+    *result = res;
+    return ICET_OK;
+}
+
 }  // namespace
 }  // namespace icet
 
 using namespace icet;
+
+icet_status icet_pose_graph_covariance_columns(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                               const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                               int32_t n_targets, const int32_t* targets, double* cols_out, double* cov_out,
+                                               icet_pose_graph_marginals_result* result) {
+    return pg_columns_entry(c, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, n_targets, targets, cols_out, cov_out, result);
+}
+
+icet_status icet_pose_graph_covariance_columns_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                                      const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                                      int32_t n_targets, const int32_t* targets, double* cols_out, double* cov_out,
+                                                      icet_pose_graph_marginals_result* result) {
+    return pg_columns_entry(c, false, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, n_targets, targets, cols_out, cov_out, result);
+}
+
+icet_status icet_pose_graph_gate(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                 const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, int32_t n_cand, const int32_t* gi,
+                                 const int32_t* gj, const float* cand_X, const float* cand_cov, double threshold, double* d2_out, double* res_cov_out,
+                                 int32_t* cand_status, icet_pose_graph_gate_result* result) {
+    return pg_gate_entry(c, true, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, n_cand, gi, gj, cand_X, cand_cov, threshold, d2_out,
+                         res_cov_out, cand_status, result);
+}
+
+icet_status icet_pose_graph_gate_device(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                        const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, int32_t n_cand, const int32_t* gi,
+                                        const int32_t* gj, const float* cand_X, const float* cand_cov, double threshold, double* d2_out, double* res_cov_out,
+                                        int32_t* cand_status, icet_pose_graph_gate_result* result) {
+    return pg_gate_entry(c, false, PgProblem{n, poses, odo_X, odo_info, n_closures, ci, cj, clo_X, clo_info, fixed}, n_cand, gi, gj, cand_X, cand_cov, threshold, d2_out,
+                         res_cov_out, cand_status, result);
+}
 
 // Every entry point hands the eleven arguments that describe the graph on as one PgProblem.
 icet_status icet_pose_graph_marginals(icet_ctx* c, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,

@@ -14,6 +14,9 @@
 //     bool rgrid(PgRobustGridKernel, int count, const PgArgs&, const PgRobust&), rgroup(PgRobustGroupKernel, const PgArgs&, const PgRobust&)
 //                                                            the robust kernels' bodies (icet_posegraph_robust.h); only PgRobustPolicy and pg_optimise_robust call
 //                                                            them, so a backend without them still runs every other driver
+//     bool xgroups(PgCrossGroupKernel, int groups, const PgArgs&, const PgDirect&, const PgMarg&, const PgCross&, const PgGate&)
+//                                                            the columns' and the gate's bodies (icet_posegraph_cross.h), once per group index below `groups`;
+//                                                            only pg_columns and pg_gate call them
 // each false for a failure of the backend (the driver then returns false at once).  icet_posegraph.hip has the device's backend (PgDeviceBackend),
 // tests/cpp/posegraph_host.h the host's (HostBackend), which the three host programs beside it share.
 // The sequences of launches that every run repeats are named once (pg_phase_*, below); the four drivers -- pg_gauss_newton, pg_marginals and the two hooks --
@@ -22,6 +25,7 @@
 #include "icet_posegraph_body.h"
 #include "icet_posegraph_direct.h"
 #include "icet_posegraph_marginals.h"
+#include "icet_posegraph_cross.h"
 #include "icet_posegraph_robust.h"
 
 #include <cmath>
@@ -393,6 +397,76 @@ inline bool pg_marginals(Backend& be, PgArgs a, PgDirect d, PgMarg mg, icet_pose
         if (!pg_get(be, tap->D, a.D, (size_t)N * 36) || !pg_get(be, tap->B, a.B, (size_t)N * 36) || !pg_get(be, tap->A, a.A, (size_t)C * 36) ||
             (st[0] == 0 && !pg_get(be, tap->band_cov, mg.band_cov, (size_t)N * 36))) return false;
     }
+    return true;
+}
+
+// ---- the covariance columns and the gate (icet_posegraph_cross.h) -----------------------------------------------------------------------------------------
+// Their work arrays beside the marginals' in the same block: the doubles, then the int32 list of the targets.  own_cols: the result is staged in the block (the
+// host-pointer form); otherwise the caller points x.cols at its own T x N x 36 doubles.
+struct PgCrossDev { int32_t* targets; };
+template <class Alloc>
+inline PgCrossDev pg_bind_cross(const PgArgs& a, const PgDirect& d, PgCross& x, Alloc& al, int T, bool own_cols) {
+    const size_t N = (size_t)a.N, q = (size_t)d.nq, t = (size_t)T;
+    x.T = T;
+    x.Zt = al.d(N * 6 * 6 * t);
+    x.Pt = al.d(t * 6 * q); x.Qt = al.d(t * 6 * q);
+    x.cols = own_cols ? al.d(t * N * 36) : nullptr;
+    PgCrossDev xd;
+    xd.targets = al.i(t);
+    x.targets = xd.targets;
+    return xd;
+}
+// The gate's arrays: d2, S and the statuses where they are staged (own_out), the candidates' ends and target indices; the measurements are the caller's.
+struct PgGateDev { int32_t *gi, *gj, *tcol; };
+template <class Alloc>
+inline PgGateDev pg_bind_gate(PgGate& g, Alloc& al, int n_cand, bool own_out, bool want_S) {
+    const size_t n = (size_t)n_cand;
+    g.n = n_cand;
+    if (own_out) { g.d2 = al.d(n); g.S = want_S ? al.d(n * 36) : nullptr; }
+    PgGateDev gd;
+    gd.gi = al.i(n); gd.gj = al.i(n); gd.tcol = al.i(n);
+    g.gi = gd.gi; g.gj = gd.gj; g.tcol = gd.tcol;
+    if (own_out) g.status = al.i(n);
+    return gd;
+}
+
+// The covariance columns of the poses the caller passed: pg_marginals as it is, then the band solves for the targets' 6 T unit columns (pg_z, the targets in
+// the place of the end nodes), P_t and Q_t of the targets, and one workgroup per node for its T blocks.  A fixed number of launches whatever the graph is.
+template <class Backend>
+inline bool pg_columns(Backend& be, const PgArgs& a, const PgDirect& d, const PgMarg& mg, const PgCross& x, icet_pose_graph_marginals_result* res,
+                       const PgMargTap* tap = nullptr, bool assembled = false) {
+    if (!pg_marginals(be, a, d, mg, res, tap, assembled)) return false;
+    PgDirect dz = d;          // Zt = M^-1 E_T: pg_z's columns are the targets'
+    dz.nq = 6 * x.T; dz.ends = x.targets; dz.Z = x.Zt;
+    const PgGate none{};
+    return be.dgrid(kPgZ, 6 * x.T, a, dz) && be.xgroups(kPgCrossTarget, x.T, a, d, mg, x, none) && be.xgroups(kPgCrossNode, a.N, a, d, mg, x, none);
+}
+
+// (host) The gate's targets: the distinct live nodes gj of the candidates, ascending, and per candidate the index of its live node among them.  false: an end
+// is out of range or a candidate's two ends are equal.
+inline bool pg_gate_targets(int N, int n_cand, const int32_t* gi, const int32_t* gj, std::vector<int32_t>& targets, std::vector<int32_t>& tcol) {
+    std::vector<int32_t> col((size_t)N, -1);
+    for (int c = 0; c < n_cand; c++) {
+        if (gi[c] < 0 || gi[c] >= N || gj[c] < 0 || gj[c] >= N || gi[c] == gj[c]) return false;
+        col[(size_t)gj[c]] = 0;
+    }
+    targets.clear();
+    for (int k = 0; k < N; k++) if (col[(size_t)k] == 0) { col[(size_t)k] = (int32_t)targets.size(); targets.push_back(k); }
+    tcol.resize((size_t)n_cand);
+    for (int c = 0; c < n_cand; c++) tcol[(size_t)c] = col[(size_t)gj[c]];
+    return true;
+}
+
+// The covariance gate: pg_columns for the distinct live nodes of the candidates, then one workgroup per candidate.  rejected: the candidates whose d2 is not
+// below the threshold (a NaN counts).
+template <class Backend>
+inline bool pg_gate(Backend& be, const PgArgs& a, const PgDirect& d, const PgMarg& mg, const PgCross& x, const PgGate& g, double threshold,
+                    icet_pose_graph_gate_result* res) {
+    if (!pg_columns(be, a, d, mg, x, &res->marg) || !be.xgroups(kPgGateCand, g.n, a, d, mg, x, g)) return false;
+    std::vector<double> d2((size_t)g.n);
+    if (!be.fetch(d2.data(), g.d2, sizeof(double) * (size_t)g.n)) return false;
+    res->n_targets = x.T; res->rejected = 0;
+    for (double v : d2) if (!(v < threshold)) res->rejected++;
     return true;
 }
 

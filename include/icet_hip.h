@@ -761,6 +761,52 @@ typedef struct icet_pose_graph_marginals_debug {
 icet_status icet_debug_pose_graph_marginals(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
                                             const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
                                             icet_pose_graph_marginals_debug* out);
+/* COVARIANCE COLUMNS: how well two poses are known relative to each other.  The graph arguments, H, the tangent and the argument checks of
+ * icet_pose_graph_marginals; `targets` (HOST) names 1 .. 32 distinct nodes.  cols_out: n_targets x n x 36 doubles, cols_out[t][k] is block (k, targets[t]) of
+ * H^-1, row-major 6 x 6: rows are node k's tangent, columns the target's.  No damping; the measurements do not enter.  cov_out (n x 36, may be NULL) carries
+ * the bits of icet_pose_graph_marginals on the same inputs, and so does cols_out[t][targets[t]]: it is copied from that result.  A block whose row node or
+ * target is fixed (node 0 included) is +0.0 in every entry.  block (k, t) = [M^-1](k, t) - P_k P_t^T + Q_k Q_t^T with the marginals' P and Q: the marginals'
+ * launches, one band solve for the targets' 6 x n_targets unit columns, one launch for the targets' P_t and Q_t and one with a workgroup per node.
+ * result: as icet_pose_graph_marginals.  After a failed factorisation (status 2 or 3) every block between two free nodes is quiet NaN and every block that
+ * touches a fixed node zero; the call returns ICET_OK.  Refused with nothing allocated and the outputs untouched: more than 128 end nodes
+ * (ICET_ERR_UNSUPPORTED, whatever "pg_solver" says); n_targets outside 1 .. 32, a target out of range, a duplicate target, or a NULL targets, cols_out or
+ * result (ICET_ERR_BAD_ARG).  In the _device form cols_out and cov_out are DEVICE pointers too (8-byte aligned).  Both forms synchronise and give the same bits,
+ * run to run and form to form.  The context's parked keyframe and workspace are not touched. */
+#define ICET_PG_MAX_TARGETS 32
+icet_status icet_pose_graph_covariance_columns(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures,
+                                               const int32_t* ci, const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed,
+                                               int32_t n_targets, const int32_t* targets, double* cols_out, double* cov_out,
+                                               icet_pose_graph_marginals_result* result);
+icet_status icet_pose_graph_covariance_columns_device(icet_ctx* ctx, int32_t n, const float* d_poses, const float* d_odo_X, const float* d_odo_info,
+                                                      int32_t n_closures, const int32_t* ci, const int32_t* cj, const float* d_clo_X, const float* d_clo_info,
+                                                      const uint8_t* fixed, int32_t n_targets, const int32_t* targets, double* d_cols_out, double* d_cov_out,
+                                                      icet_pose_graph_marginals_result* result);
+/* THE COVARIANCE GATE: is a candidate closure plausible under what the graph knows?  Candidate c (gi[c], gj[c] on the HOST; 1 <= n_cand <= 512) is a closure
+ * that is NOT in the graph yet: keyframe node gi[c] seen from live node gj[c], with the measurement cand_X[c] (as clo_X) and its 6 x 6 covariance cand_cov[c]
+ * (the record's own, used as 0.5 (c + c^T) in double).  Per candidate, in double: e is the optimiser's residual of edge (gi, gj) with that measurement at
+ * `poses`, J_i, J_j its central-difference Jacobians, and
+ *     S = J_i Sigma_ii J_i^T + J_i Sigma_ij J_j^T + J_j Sigma_ji J_i^T + J_j Sigma_jj J_j^T + cov,      d2 = e^T S^-1 e
+ * with Sigma_ii, Sigma_jj the marginals and Sigma_ij the covariance column of target gj: ONE columns run whose targets are the distinct nodes among gj,
+ * ascending (more than 32 of them: ICET_ERR_BAD_ARG), then one workgroup per candidate.  d2 goes through a 6 x 6 Cholesky factorisation of S: a pivot at or
+ * below 1e-13 of its diagonal entry gives cand_status[c] 2, one that is not finite 3, otherwise 0.  d2_out[c] is d2, or quiet NaN behind status 2 or 3 or
+ * behind a failed factorisation of the graph (result->marg.status); res_cov_out[c] (may be NULL) is S, symmetric bit for bit.  result->rejected counts the
+ * candidates whose d2 is not below `threshold`; a threshold <= 0 means ICET_PG_ROBUST_DEFAULT_SCALE.  gi[c] == gj[c], an index out of range or n_cand
+ * outside 1 .. 512: ICET_ERR_BAD_ARG; the refusals of icet_pose_graph_covariance_columns hold, nothing allocated, the outputs untouched.
+ * CAVEAT: a candidate must not already be an edge of the graph -- its noise would be counted twice, in Sigma and in cov.
+ * The first form takes HOST arrays; in the _device form cand_X, cand_cov, d2_out, res_cov_out and cand_status are DEVICE pointers too.  Both synchronise. */
+typedef struct icet_pose_graph_gate_result {
+    icet_pose_graph_marginals_result marg;
+    int32_t n_targets;            /* the distinct nodes among gj */
+    int32_t rejected;             /* candidates whose d2 is not below the threshold */
+} icet_pose_graph_gate_result;    /* 32 bytes */
+icet_status icet_pose_graph_gate(icet_ctx* ctx, int32_t n, const float* poses, const float* odo_X, const float* odo_info, int32_t n_closures, const int32_t* ci,
+                                 const int32_t* cj, const float* clo_X, const float* clo_info, const uint8_t* fixed, int32_t n_cand, const int32_t* gi,
+                                 const int32_t* gj, const float* cand_X, const float* cand_cov, double threshold, double* d2_out, double* res_cov_out,
+                                 int32_t* cand_status, icet_pose_graph_gate_result* result);
+icet_status icet_pose_graph_gate_device(icet_ctx* ctx, int32_t n, const float* d_poses, const float* d_odo_X, const float* d_odo_info, int32_t n_closures,
+                                        const int32_t* ci, const int32_t* cj, const float* d_clo_X, const float* d_clo_info, const uint8_t* fixed, int32_t n_cand,
+                                        const int32_t* gi, const int32_t* gj, const float* d_cand_X, const float* d_cand_cov, double threshold, double* d_d2_out,
+                                        double* d_res_cov_out, int32_t* d_cand_status, icet_pose_graph_gate_result* result);
 /* The optimiser's solver alone, as a test hook.  The odometry chain of a pose graph makes its normal equations block tridiagonal (6 x 6 blocks).
  * ONE symmetric positive definite block-tridiagonal system through the block Cholesky factorisation and the two sweeps, in double, one workgroup.
  * HOST arrays of doubles: diag n x 36, sub n x 36 (sub[k]: the block at (k, k - 1); sub[0] zero), rhs and x n x 6; *status 0, or ICET_BAND_NOT_POSITIVE_DEFINITE
