@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_debug_block_tridiag", "icet_pose_graph_optimize", "icet_pose_graph_optimize_device", "icet_pose_graph_optimize_robust", "icet_pose_graph_optimize_robust_device", "icet_debug_pose_graph_step", "icet_debug_pose_graph_direct",
                     "icet_pose_graph_marginals", "icet_pose_graph_marginals_device", "icet_debug_pose_graph_marginals",
                     "icet_pose_graph_covariance_columns", "icet_pose_graph_covariance_columns_device", "icet_pose_graph_gate", "icet_pose_graph_gate_device",
+                    "icet_voxel_map_create", "icet_voxel_map_destroy", "icet_voxel_map_last_error", "icet_voxel_map_clear", "icet_voxel_map_add_device",
+                    "icet_voxel_map_add_posed_device", "icet_voxel_map_stats", "icet_voxel_map_extract_device", "icet_voxel_map_extract",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -48,7 +50,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_node_group_prev_scan", "icet_node_group_aligned", "icet_node_group_snail_trail",
                     "icet_load_scan", "icet_free_scan", "icet_save_scan_npy")
 _NON_STATUS = ("icet_version", "icet_last_error", "icet_node_last_error", "icet_node_group_last_error", "icet_stream", "icet_device", "icet_free_scan", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
-               "icet_keyframe_store_last_error", "icet_pose_step_from_x")
+               "icet_keyframe_store_last_error", "icet_pose_step_from_x", "icet_voxel_map_last_error")
 
 
 class IcetError(RuntimeError):
@@ -85,6 +87,30 @@ class AppearanceParams(C.Structure):
 class CoarseParams(C.Structure):
     """icet_coarse_params (include/icet_hip.h), 32 bytes."""
     _fields_ = [("cells", C.c_int32), ("cell", C.c_float), ("z_lo", C.c_float), ("z_hi", C.c_float), ("min_span", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class MapParams(C.Structure):
+    """icet_voxel_map_params (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("cell", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("table_log2", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MapStats(C.Structure):
+    """struct icet_voxel_map_stats (include/icet_hip.h), 64 bytes."""
+    _fields_ = [("points_in", C.c_int64), ("points_kept", C.c_int64), ("points_nonfinite", C.c_int64), ("points_outside", C.c_int64), ("points_dropped", C.c_int64),
+                ("cells_occupied", C.c_int32), ("cells_out", C.c_int32), ("cells_negative", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:9]}
+
+
+VOXEL_MAP_OK, VOXEL_MAP_TABLE_FULL, VOXEL_MAP_NEGATIVE, VOXEL_MAP_TRUNCATED = 0, 1, 2, 4
+
+
+def voxel_key_cells(key):
+    """The integer cell indices (c_x, c_y, c_z) of voxel-map keys (include/icet_hip.h, the rule's step 5): an (..., 3) int64 array."""
+    k = np.asarray(key, np.uint64)
+    m = np.uint64(0x1FFFFF)
+    return np.stack([((k >> np.uint64(42)) & m).astype(np.int64), ((k >> np.uint64(21)) & m).astype(np.int64), (k & m).astype(np.int64)], axis=-1) - (1 << 20)
 
 
 class SnapshotInfo(C.Structure):
@@ -445,6 +471,15 @@ def load_library():
                                                           C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_close_coarse_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.POINTER(ClosureQuery),
                                                           C.POINTER(CoarseSearch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_voxel_map_create.argtypes = [C.c_void_p, C.POINTER(MapParams), C.POINTER(C.c_void_p)]
+    L.icet_voxel_map_destroy.argtypes = [C.c_void_p]
+    L.icet_voxel_map_last_error.argtypes = [C.c_void_p]; L.icet_voxel_map_last_error.restype = C.c_char_p
+    L.icet_voxel_map_clear.argtypes = [C.c_void_p]
+    L.icet_voxel_map_add_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_int32]
+    L.icet_voxel_map_add_posed_device.argtypes = L.icet_voxel_map_add_device.argtypes
+    L.icet_voxel_map_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(MapStats)]
+    L.icet_voxel_map_extract_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(MapStats)]
+    L.icet_voxel_map_extract.argtypes = L.icet_voxel_map_extract_device.argtypes
     L.icet_keyframe_store_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p]
     L.icet_keyframe_store_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.icet_keyframe_store_snapshot_info.argtypes = [C.c_char_p, C.POINTER(SnapshotInfo)]
@@ -1674,6 +1709,105 @@ class KeyframeStore:
         else:
             res.update(slot=int(idx[b]), X=o[b, :6].copy(), pred_stds=o[b, 6:12].copy(), cov=o[b, 12:48].reshape(6, 6).copy())
         return res
+
+
+class VoxelMap:
+    """``icet_voxel_map`` (include/icet_hip.h): scans at 4 x 4 poses fused into one centroid and one count per occupied cell on ``ctx``'s
+    device.  ``remove`` undoes an ``add`` at the same pose exactly, so a scan can be moved to a corrected pose; ``extract`` gives the cells sorted by key as a
+    scan.  The map borrows ``ctx`` (closed before it)."""
+
+    def __init__(self, ctx, cell=0.1, min_range=0.0, max_range=0.0, table_log2=22):
+        self._ctx = ctx
+        self.params = MapParams(float(cell), float(min_range), float(max_range), int(table_log2), 0)
+        h = C.c_void_p()
+        st = load_library().icet_voxel_map_create(ctx._h, C.byref(self.params), C.byref(h))
+        if st != ICET_OK:
+            raise IcetError(st, "icet_voxel_map_create: " + load_library().icet_last_error(ctx._h).decode())
+        self._h = h
+        import weakref
+        if not hasattr(ctx, "_nodes"):
+            ctx._nodes = []
+        ctx._nodes.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._ctx, "_h", None):               # (a context finalised first took the device with it: see KeyframeStore.close)
+                load_library().icet_voxel_map_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        if st != ICET_OK:
+            raise IcetError(st, load_library().icet_voxel_map_last_error(self._h).decode())
+
+    def _add_device(self, descs, poses, sign):
+        A = _dev_scans(descs)
+        if isinstance(poses, np.ndarray) or not hasattr(poses, "data_ptr"):
+            T = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
+            if T.shape[0] != len(descs):
+                raise IcetError(ICET_ERR_BAD_ARG, "one 4 x 4 pose per scan")
+            self._check(load_library().icet_voxel_map_add_device(self._h, len(descs), A, T.ctypes.data, int(sign)))
+            return
+        import torch
+        if not (poses.is_cuda and poses.dtype == torch.float32 and poses.is_contiguous()) or poses.numel() != 16 * len(descs):
+            raise IcetError(ICET_ERR_BAD_ARG, "device poses must be a contiguous float32 CUDA tensor of one 4 x 4 pose per scan")
+        torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensor must be complete
+        self._check(load_library().icet_voxel_map_add_posed_device(self._h, len(descs), A, _vp(poses.data_ptr()), int(sign)))
+
+    def add_device(self, descs, poses):
+        """Add the scans (device_ptr, n, ld) at ``poses``: an n x 4 x 4 NumPy array (icet_voxel_map_add_device) or a float32 CUDA tensor
+        (icet_voxel_map_add_posed_device).  Asynchronous on the context's stream."""
+        self._add_device(descs, poses, 1)
+
+    def remove_device(self, descs, poses):
+        """Remove the scans at the poses they were added at (sign -1)."""
+        self._add_device(descs, poses, -1)
+
+    def _add_host(self, scans, poses, sign):
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        torch.cuda.synchronize(dev)
+        self._add_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], poses, sign)
+        self._ctx.sync()
+
+    def add(self, scans, poses):
+        """add_device for host N x 3 arrays: staged on the device; returns once the add has run."""
+        self._add_host(scans, poses, 1)
+
+    def remove(self, scans, poses):
+        self._add_host(scans, poses, -1)
+
+    def clear(self):
+        self._check(load_library().icet_voxel_map_clear(self._h))
+
+    def stats(self, min_points=1):
+        """The running totals since the last clear and the cells as they are now (MapStats.as_dict()).  Synchronises."""
+        s = MapStats()
+        self._check(load_library().icet_voxel_map_stats(self._h, int(min_points), C.byref(s)))
+        return s.as_dict()
+
+    def extract_device(self, d_xyz_ptr, ld, cap_rows, min_points=1, d_count_ptr=None, d_key_ptr=None):
+        """The cells with count >= max(1, min_points), sorted by key, into device buffers: d_xyz N x 3 column-major float32 (leading dimension ld), optional
+        int64 counts and uint64 keys.  Returns the stats; cells_out rows exist, min(cells_out, cap_rows) were written.  Synchronises."""
+        s = MapStats()
+        self._check(load_library().icet_voxel_map_extract_device(self._h, int(min_points), _vp(d_xyz_ptr), int(ld), int(cap_rows), _vp(d_count_ptr), _vp(d_key_ptr),
+                                                                 C.byref(s)))
+        return s.as_dict()
+
+    def extract(self, min_points=1, cap_rows=None):
+        """The map on the host: dict(xyz (n, 3) float32, count (n,) int64, key (n,) uint64, stats).  cap_rows: at most so many rows (the lowest keys)."""
+        cap = self.stats(min_points)["cells_out"] if cap_rows is None else int(cap_rows)
+        xyz = np.zeros((3, max(cap, 1)), np.float32); cnt = np.zeros(max(cap, 1), np.int64); key = np.zeros(max(cap, 1), np.uint64)
+        s = MapStats()
+        self._check(load_library().icet_voxel_map_extract(self._h, int(min_points), xyz.ctypes.data, max(cap, 1), cap, cnt.ctypes.data, key.ctypes.data, C.byref(s)))
+        n = min(cap, s.cells_out)
+        return dict(xyz=np.ascontiguousarray(xyz[:, :n].T), count=cnt[:n].copy(), key=key[:n].copy(), stats=s.as_dict())
 
 
 class MultiContext:

@@ -86,7 +86,8 @@ struct icet_ctx {
     // last kernel.  armed_calls counts such solves since the last icet_sync; anything else enqueued on the context (or a second solve, whose reset of the word races with the
     // first one's store) makes it 2 or more and icet_sync synchronises the stream as before.
     int32_t* h_sync_word = nullptr; int armed_calls = 2;
-    int64_t snapshot_chunk_bytes = 0;                            // option "snapshot_chunk_bytes": payload bytes per chunk of a store's save / load (0: 64 MiB)
+    int map_lds = 1;                                             // option "map_lds": a voxel map's add reduces a block's rows in LDS first (icet_map.hip)
+    int64_t snapshot_chunk_bytes = 0;                          // option "snapshot_chunk_bytes": payload bytes per chunk of a store's save / load (0: 64 MiB)
     // Who owns what w and the pointers above point at: one group per set of arrays that grows together (the ensure_* functions of icet_capi.hip).  delete frees them (last member: gone first).
     struct Mem {
         icet::BufferGroup pairs, regs, scan1, fit, scan2, lut, keep_mask, keep_list, keep_pairs, counts, tile_vr, rt2, rt_desc;      // what w points at (+ the pinned staging sized with it)
@@ -206,7 +207,8 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            (all three also drain, or icet_solve_end does); icet_select_best_device; icet_keyframe_store_create (*), _put_device, _register[_scored]_device,
 //                            _score_device, _set_pose, _set_stamp, _candidates[_appearance]_device, _describe_device, _coarse_grid_device, _coarse_align_device,
 //                            _close[_appearance|_coarse]_device; icet_keyframe_store_save, _load (drain as well); icet_pose_graph_optimize[_device],
-//                            icet_debug_pose_graph_step, _direct, icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals (pg_run: drains as well)
+//                            icet_debug_pose_graph_step, _direct, icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals (pg_run: drains as well);
+//                            icet_voxel_map_create, _clear, _add_device, _add_posed_device; _stats, _extract_device, _extract (drain as well; icet_map.hip)
 //   arms or disarms itself   icet_solve_batch_device
 //   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_block_tridiag (copy in, one kernel, copy out,
 //                            synchronise); icet_debug_fetch, icet_keyframe_store_debug_fetch, icet_keep_stats (synchronise, then blocking copies);

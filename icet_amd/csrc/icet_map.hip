@@ -1,0 +1,458 @@
+// icet_amd/csrc/icet_map.hip -- the voxel map of the C ABI (include/icet_hip.h icet_voxel_map_*): scans at poses fused into one centroid and
+// one count per occupied cell, in an open-addressing hash table in HBM.  The rule -- which rows count, a row's key and offsets, a cell's centroid -- is
+// icet_map.h; this file is the kernels around it and the entry points:
+//     k_map_add       one launch for all scans of a call, blockIdx -> (scan, chunk of kRowsPerBlock rows), 16-byte loads of 4 consecutive rows per lane.  A lane
+//                     first merges the equal keys among its own 4 rows; with kLds the block then reduces its rows in an LDS table of kLdsSlots cells (64-bit ds
+//                     compare-and-swap on the key, ds adds on count and sums) and flushes every distinct cell ONCE with global 64-bit atomics; a cell that finds
+//                     no LDS slot within kLdsProbes goes to the global table directly.  Without kLds (option "map_lds" 0): one global update per merged run.
+//     k_map_cells     a pass over the entries, 16 per thread: <false> counts the cells with count > 0, count >= min_points, count < 0 (tallied in LDS, one
+//                     atomic per block and counter); <true> compacts (key, entry) of the cells with count >= min_points (a block claims its places with one atomic)
+//     k_map_centroid  one thread per output row, behind rocPRIM's device radix sort of the pairs by key
+// Sums of integers only: no float atomic, no block waits for another block, no fence inside a kernel, and the contents do not depend on the launch shape.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include "../../include/icet_hip.h"
+#include "icet_ctx.h"
+#include "icet_staging.h"
+#include "icet_map.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+
+namespace icet {
+namespace {
+
+namespace rule = icet_map_rule;
+typedef unsigned long long u64;
+
+constexpr int kAddBlock = 256;
+constexpr int kRowsPerBlock = 2048;      // a block's chunk of one scan: two trips of 256 lanes x 4 rows
+constexpr int kLdsSlots = 1024;          // 36 KB of LDS: key 8 | sums 24 | count 4 bytes per slot
+constexpr int kLdsProbes = 8;
+constexpr int kCellBlock = 256;
+constexpr int kCellPer = 16;            // entries per thread of a pass over the table
+constexpr int kCellSpan = kCellBlock * kCellPer;
+
+struct MapScan { const float* ptr; int32_t n, ld, block0, pad; };      // block0: the first block of the scan in the launch
+static_assert(sizeof(MapScan) == 24, "ptr | n | ld | block0 | pad");
+// key[size] | count[size] (two's complement) | sum[3][size]
+struct MapTable { u64* key; u64* count; u64* sum; uint32_t log2; };
+// the device record: kTotCopies copies of the running totals, one 64-byte line each (a block adds to copy blockIdx % kTotCopies, so that the blocks of a launch
+// do not all queue on one address; the host sums the copies), then what the last count pass saw and the select pass's cursor
+enum { kCtrIn = 0, kCtrKept, kCtrNonfinite, kCtrOutside, kCtrDropped, kTotWords = 8 };
+constexpr int kTotCopies = 64;
+enum { kCtrOccupied = kTotCopies * kTotWords, kCtrOut, kCtrNegative, kCtrSelected, kCtrWords = kTotCopies * kTotWords + 8 };
+
+#define MAP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+#define MAP_RLX_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
+
+// count += dn, sum_a += d_a in the cell of `key`, claimed on the way if it is new.  False: the probe run met neither the key nor a free entry (the table is full).
+// An entry's key changes once, from empty to its key, so a stale read of "empty" only costs the compare-and-swap that then returns the truth.
+__device__ __forceinline__ bool table_update(const MapTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2) {
+    const u64 mask = ((u64)1 << t.log2) - 1;
+    u64 h = rule::mix(key) & mask;                                    // h <= mask: inside every array
+    for (u64 p = 0; p <= mask; p++) {
+        u64 k = __hip_atomic_load(&t.key[h], MAP_RLX_AGENT);
+        if (k == rule::kEmpty) {
+            u64 expected = rule::kEmpty;
+            k = __hip_atomic_compare_exchange_strong(&t.key[h], &expected, key, __ATOMIC_RELAXED, MAP_RLX_AGENT) ? key : expected;
+        }
+        if (k == key) {
+            const u64 size = mask + 1;
+            __hip_atomic_fetch_add(&t.count[h], dn, MAP_RLX_AGENT);
+            __hip_atomic_fetch_add(&t.sum[h], d0, MAP_RLX_AGENT);
+            __hip_atomic_fetch_add(&t.sum[size + h], d1, MAP_RLX_AGENT);
+            __hip_atomic_fetch_add(&t.sum[2 * size + h], d2, MAP_RLX_AGENT);
+            return true;
+        }
+        h = (h + 1) & mask;
+    }
+    return false;
+}
+
+// m <= 4 rows of one column from row i (a multiple of 4): one 16-byte load where the column's address allows it and all four rows exist.
+__device__ __forceinline__ void load_rows(const float* __restrict__ col, int i, int m, float v[4]) {
+    const float* p = col + i;
+    if (m == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+        for (int r = 0; r < 4; r++) v[r] = r < m ? p[r] : 0.f;
+    }
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(kAddBlock) void k_map_add(const MapScan* __restrict__ scans, int n_scans, const float* __restrict__ poses, rule::Consts kc, MapTable t,
+                                                       u64 sign, u64* __restrict__ ctr) {
+    __shared__ u64 lkey[kLds ? kLdsSlots : 1];
+    __shared__ u64 lsum[3][kLds ? kLdsSlots : 1];
+    __shared__ uint32_t lcnt[kLds ? kLdsSlots : 1];
+    __shared__ uint32_t lctr[5];
+    __shared__ float sT[12];
+    // the scan of this block: the last one whose first block is not behind it (a scan without rows has no block)
+    int lo = 0, hi = n_scans - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (scans[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const MapScan sc = scans[lo];
+    const int row0 = ((int)blockIdx.x - sc.block0) * kRowsPerBlock;
+    if (row0 < 0 || row0 >= sc.n) return;                             // (the same for every thread of the block)
+    const int end = min(sc.n, row0 + kRowsPerBlock);
+    if (kLds) for (int s = threadIdx.x; s < kLdsSlots; s += kAddBlock) { lkey[s] = rule::kEmpty; lsum[0][s] = 0; lsum[1][s] = 0; lsum[2][s] = 0; lcnt[s] = 0u; }
+    if (threadIdx.x < 5) lctr[threadIdx.x] = 0u;
+    if (threadIdx.x < 12) sT[threadIdx.x] = poses[16 * (size_t)lo + threadIdx.x];
+    __syncthreads();
+    const float* cx = sc.ptr; const float* cy = cx + sc.ld; const float* cz = cx + 2 * (size_t)sc.ld;
+    uint32_t n_in = 0, n_kept = 0, n_nonfinite = 0, n_outside = 0, n_dropped = 0;
+
+    // a run of rows of one cell: into the block's LDS table, or the global table
+    auto push = [&](u64 key, uint32_t c, u64 s0, u64 s1, u64 s2) {
+        if (kLds) {
+            uint32_t s = (uint32_t)(rule::mix(key) >> 40) & (kLdsSlots - 1);
+            for (int p = 0; p < kLdsProbes; p++) {
+                u64 expected = rule::kEmpty;
+                if (__hip_atomic_compare_exchange_strong(&lkey[s], &expected, key, __ATOMIC_RELAXED, MAP_RLX_WG) || expected == key) {
+                    __hip_atomic_fetch_add(&lcnt[s], c, MAP_RLX_WG);
+                    __hip_atomic_fetch_add(&lsum[0][s], s0, MAP_RLX_WG);
+                    __hip_atomic_fetch_add(&lsum[1][s], s1, MAP_RLX_WG);
+                    __hip_atomic_fetch_add(&lsum[2][s], s2, MAP_RLX_WG);
+                    return;
+                }
+                s = (s + 1) & (kLdsSlots - 1);
+            }
+        }
+        if (table_update(t, key, sign * c, sign * s0, sign * s1, sign * s2)) n_kept += c; else n_dropped += c;
+    };
+
+    for (int i = row0 + 4 * (int)threadIdx.x; i < end; i += 4 * kAddBlock) {
+        const int m = min(4, end - i);
+        float x[4], y[4], z[4];
+        load_rows(cx, i, m, x); load_rows(cy, i, m, y); load_rows(cz, i, m, z);
+        n_in += (uint32_t)m;
+        u64 run_key = rule::kEmpty, r0 = 0, r1 = 0, r2 = 0; uint32_t run = 0;
+        for (int r = 0; r < m; r++) {
+            rule::Point pt;
+            const int cls = rule::classify(kc, sT, x[r], y[r], z[r], pt);
+            if (cls == rule::kRowNonfinite) n_nonfinite++;
+            if (cls == rule::kRowOutside) n_outside++;
+            if (cls != rule::kRowKept) continue;
+            if (run && pt.key != run_key) { push(run_key, run, r0, r1, r2); run = 0; r0 = 0; r1 = 0; r2 = 0; }
+            run_key = pt.key; run++; r0 += pt.q[0]; r1 += pt.q[1]; r2 += pt.q[2];
+        }
+        if (run) push(run_key, run, r0, r1, r2);
+    }
+    if (kLds) {
+        __syncthreads();
+        for (int s = threadIdx.x; s < kLdsSlots; s += kAddBlock) {
+            const u64 key = lkey[s];
+            if (key == rule::kEmpty) continue;
+            const uint32_t c = lcnt[s];
+            if (table_update(t, key, sign * c, sign * lsum[0][s], sign * lsum[1][s], sign * lsum[2][s])) n_kept += c; else n_dropped += c;
+        }
+    }
+    if (n_in) atomicAdd(&lctr[0], n_in);
+    if (n_kept) atomicAdd(&lctr[1], n_kept);
+    if (n_nonfinite) atomicAdd(&lctr[2], n_nonfinite);
+    if (n_outside) atomicAdd(&lctr[3], n_outside);
+    if (n_dropped) atomicAdd(&lctr[4], n_dropped);
+    __syncthreads();
+    if (threadIdx.x < 5 && lctr[threadIdx.x]) {
+        const u64 v = lctr[threadIdx.x];
+        __hip_atomic_fetch_add(&ctr[(blockIdx.x % kTotCopies) * kTotWords + threadIdx.x], threadIdx.x == kCtrKept ? sign * v : v, MAP_RLX_AGENT);
+    }
+}
+
+// A block walks kCellSpan entries, kCellPer per thread.  Threads tally in LDS and the block touches the device record once per counter: every block of the
+// grid adds to the same few words, and adders on one address are what memory-side atomics do worst.  select: the cells of count >= minp are written as
+// (key, entry) at places the block claims with one atomic (the order of the places is free: the pairs are sorted next); else they are only counted.
+template <bool kSelect>
+__global__ __launch_bounds__(kCellBlock) void k_map_cells(MapTable t, long long minp, u64* __restrict__ ctr, u64* __restrict__ sel_key, uint32_t* __restrict__ sel_idx, u64 cap) {
+    __shared__ uint32_t tally[3];
+    __shared__ u64 base;
+    const u64 size = (u64)1 << t.log2, first = (u64)blockIdx.x * kCellSpan + threadIdx.x;      // the grid covers the entries; a table below kCellSpan is one block
+    if (threadIdx.x < 3) tally[threadIdx.x] = 0u;
+    __syncthreads();
+    uint32_t n_out = 0, n_occ = 0, n_neg = 0, mask = 0;
+#pragma unroll
+    for (int j = 0; j < kCellPer; j++) {
+        const u64 i = first + (u64)j * kCellBlock;
+        if (i >= size) break;
+        const long long c = (long long)t.count[i];
+        if (c >= minp) { n_out++; mask |= 1u << j; }
+        n_occ += c > 0; n_neg += c < 0;
+    }
+    if (kSelect) {
+        uint32_t at = 0;
+        if (n_out) at = atomicAdd(&tally[0], n_out);
+        __syncthreads();
+        if (threadIdx.x == 0 && tally[0]) base = __hip_atomic_fetch_add(&ctr[kCtrSelected], (u64)tally[0], MAP_RLX_AGENT);
+        __syncthreads();
+        if (!n_out) return;
+        u64 pos = base + at;
+        for (int j = 0; j < kCellPer; j++) {
+            if (!((mask >> j) & 1u)) continue;
+            const u64 i = first + (u64)j * kCellBlock;
+            if (pos < cap) { sel_key[pos] = t.key[i]; sel_idx[pos] = (uint32_t)i; }      // (cap: the count pass's cells_out, on the same stream)
+            pos++;
+        }
+    } else {
+        if (n_occ) atomicAdd(&tally[0], n_occ);
+        if (n_out) atomicAdd(&tally[1], n_out);
+        if (n_neg) atomicAdd(&tally[2], n_neg);
+        __syncthreads();
+        if (threadIdx.x < 3 && tally[threadIdx.x]) __hip_atomic_fetch_add(&ctr[kCtrOccupied + threadIdx.x], (u64)tally[threadIdx.x], MAP_RLX_AGENT);
+    }
+}
+
+// Row i of the output: the centroid, count and key of the cell with the i-th lowest key.
+__global__ __launch_bounds__(kCellBlock) void k_map_centroid(MapTable t, rule::Consts kc, const u64* __restrict__ keys, const uint32_t* __restrict__ idx, long long rows,
+                                                             float* __restrict__ xyz, long long ld, long long* __restrict__ d_count, u64* __restrict__ d_key) {
+    const long long i = (long long)blockIdx.x * kCellBlock + threadIdx.x;
+    if (i >= rows) return;
+    const u64 key = keys[i];
+    const u64 e = idx[i], size = (u64)1 << t.log2;                    // e < size: k_map_select wrote an entry's index
+    const long long n = (long long)t.count[e];
+    int32_t c[3];
+    rule::key_cells(key, c);
+    for (int a = 0; a < 3; a++) xyz[a * ld + i] = rule::centroid(kc, c[a], t.sum[a * size + e], n);
+    if (d_count) d_count[i] = n;
+    if (d_key) d_key[i] = key;
+}
+
+}  // namespace
+}  // namespace icet
+
+using namespace icet;
+
+// A voxel map: the table, the device record of its totals and the pinned copy a stats call reads, the staging of a call's descriptors and poses, the buffers of
+// an extract.  Every array belongs to a group; the struct is a heap object that never moves.
+struct icet_voxel_map {
+    icet_ctx* ctx = nullptr;
+    icet_voxel_map_params params{};
+    rule::Consts k{};
+    std::string err;
+    MapTable t{};
+    u64* ctr = nullptr; u64* h_rec = nullptr;                         // kCtrWords each: device, pinned
+    // a call's descriptors and host poses: pinned, then copied to the device; the host writes the pinned side only behind ev_stage
+    MapScan* h_scan = nullptr; MapScan* d_scan = nullptr; float* h_pose = nullptr; float* d_pose = nullptr; int32_t cap_scans = 0;
+    hipEvent_t ev_stage = nullptr; bool stage_in_flight = false;
+    // an extract: the selected (key, entry) pairs, their sorted copy, rocPRIM's scratch; the rows of the host form
+    u64* sel_key = nullptr; u64* sorted_key = nullptr; uint32_t* sel_idx = nullptr; uint32_t* sorted_idx = nullptr; void* sort_tmp = nullptr; int64_t cap_sel = 0;
+    float* x_xyz = nullptr; long long* x_count = nullptr; u64* x_key = nullptr; int64_t cap_x = 0;
+    BufferGroup table, record, stage, sel, xout;
+};
+
+#define MAPCHK(m, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
+    (void)hipGetLastError(); (m)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
+    return e_ == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; } } while (0)
+
+static icet_status enter(icet_voxel_map* m) {
+    if (!m) return ICET_ERR_BAD_ARG;
+    const icet_status st = enter(m->ctx);
+    if (st != ICET_OK) m->err = m->ctx->err;
+    return st;
+}
+static icet_status map_refuse(icet_voxel_map* m, const std::string& why) { m->err = why; return ICET_ERR_BAD_ARG; }
+
+static icet_status map_clear(icet_voxel_map* m) {
+    const size_t size = (size_t)1 << m->t.log2;
+    hipStream_t st = m->ctx->stream;
+    MAPCHK(m, hipMemsetAsync(m->t.key, 0xFF, sizeof(u64) * size, st));
+    MAPCHK(m, hipMemsetAsync(m->t.count, 0, sizeof(u64) * size, st));
+    MAPCHK(m, hipMemsetAsync(m->t.sum, 0, sizeof(u64) * 3 * size, st));
+    MAPCHK(m, hipMemsetAsync(m->ctr, 0, sizeof(u64) * kCtrWords, st));
+    return ICET_OK;
+}
+
+// The cells as they are now, and the totals, into *out: one pass over the table, the record copied to its pinned twin, the stream drained.
+static icet_status map_count(icet_voxel_map* m, int32_t min_points, struct icet_voxel_map_stats* out) {
+    hipStream_t st = m->ctx->stream;
+    const long long minp = std::max(1, min_points);
+    MAPCHK(m, hipMemsetAsync(m->ctr + kCtrOccupied, 0, sizeof(u64) * 4, st));      // occupied, out, negative, selected
+    k_map_cells<false><<<(unsigned)((((size_t)1 << m->t.log2) + kCellSpan - 1) / kCellSpan), kCellBlock, 0, st>>>(m->t, minp, m->ctr, nullptr, nullptr, 0);
+    MAPCHK(m, hipGetLastError());
+    MAPCHK(m, hipMemcpyAsync(m->h_rec, m->ctr, sizeof(u64) * kCtrWords, hipMemcpyDeviceToHost, st));
+    MAPCHK(m, hipStreamSynchronize(st));
+    u64 r[kCtrWords] = {0};                                           // the copies of the totals summed (two's complement: the signed one too)
+    for (int k = 0; k < kTotCopies; k++) for (int w = 0; w < kTotWords; w++) r[w] += m->h_rec[k * kTotWords + w];
+    for (int w = kCtrOccupied; w < kCtrWords; w++) r[w] = m->h_rec[w];
+    std::memset(out, 0, sizeof(*out));
+    out->points_in = (int64_t)r[kCtrIn]; out->points_kept = (int64_t)r[kCtrKept]; out->points_nonfinite = (int64_t)r[kCtrNonfinite];
+    out->points_outside = (int64_t)r[kCtrOutside]; out->points_dropped = (int64_t)r[kCtrDropped];
+    out->cells_occupied = (int32_t)r[kCtrOccupied]; out->cells_out = (int32_t)r[kCtrOut]; out->cells_negative = (int32_t)r[kCtrNegative];
+    out->status = (r[kCtrDropped] ? ICET_VOXEL_MAP_TABLE_FULL : 0) | (r[kCtrNegative] ? ICET_VOXEL_MAP_NEGATIVE : 0);
+    return ICET_OK;
+}
+
+static icet_status map_add(icet_voxel_map* m, int32_t n, const icet_dev_scan* scans, const float* poses, bool poses_on_device, int32_t sign, const char* call) {
+    ICET_TRY(enter(m));
+    // everything is checked before anything is touched
+    if (n < 0 || (n > 0 && (!scans || !poses))) return map_refuse(m, std::string(call) + ": bad argument");
+    if (!rule::sign_ok(sign)) return map_refuse(m, std::string(call) + ": sign must be +1 (add) or -1 (remove)");
+    if (poses_on_device && (reinterpret_cast<uintptr_t>(poses) & 3)) return map_refuse(m, std::string(call) + ": d_poses is not aligned to 4 bytes");
+    int64_t blocks = 0;
+    for (int k = 0; k < n; k++) {
+        if (!dev_scan_ok(scans[k]) || (reinterpret_cast<uintptr_t>(scans[k].ptr) & 3)) return map_refuse(m, std::string(call) + ": bad scan descriptor (scans[" + std::to_string(k) + "])");
+        blocks += (scans[k].n + kRowsPerBlock - 1) / kRowsPerBlock;
+    }
+    if (blocks > 0x7FFFFFFF) return map_refuse(m, std::string(call) + ": too many rows in one call");
+    if (blocks == 0) return ICET_OK;                                  // nothing to read
+    icet_ctx* c = m->ctx;
+    if (m->stage_in_flight) { MAPCHK(m, hipEventSynchronize(m->ev_stage)); m->stage_in_flight = false; }      // the previous call has read the staging
+    if (n > m->cap_scans) {
+        MAPCHK(m, hipStreamSynchronize(c->stream));              // (its kernel may still read the device side)
+        BufferGroup& g = m->stage;
+        MAPCHK(m, grow(g, m->cap_scans, n, [&] {
+            int e = g.pinned(m->h_scan, (size_t)n);
+            if (!e) e = g.device(m->d_scan, (size_t)n);
+            if (!e) e = g.pinned(m->h_pose, 16 * (size_t)n);
+            if (!e) e = g.device(m->d_pose, 16 * (size_t)n);
+            return e;
+        }));
+    }
+    if (!m->ev_stage) MAPCHK(m, hipEventCreateWithFlags(&m->ev_stage, hipEventDisableTiming));
+    int32_t b0 = 0;
+    for (int k = 0; k < n; k++) {
+        m->h_scan[k] = MapScan{scans[k].ptr, (int32_t)scans[k].n, (int32_t)scans[k].ld, b0, 0};
+        b0 += (int32_t)((scans[k].n + kRowsPerBlock - 1) / kRowsPerBlock);
+    }
+    MAPCHK(m, hipMemcpyAsync(m->d_scan, m->h_scan, sizeof(MapScan) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (!poses_on_device) {
+        std::memcpy(m->h_pose, poses, sizeof(float) * 16 * (size_t)n);
+        MAPCHK(m, hipMemcpyAsync(m->d_pose, m->h_pose, sizeof(float) * 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    const float* dp = poses_on_device ? poses : m->d_pose;
+    const u64 sg = sign > 0 ? (u64)1 : ~(u64)0;                       // -1 in two's complement
+    if (c->map_lds) k_map_add<true><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(m->d_scan, n, dp, m->k, m->t, sg, m->ctr);
+    else k_map_add<false><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(m->d_scan, n, dp, m->k, m->t, sg, m->ctr);
+    MAPCHK(m, hipGetLastError());
+    MAPCHK(m, hipEventRecord(m->ev_stage, c->stream)); m->stage_in_flight = true;
+    return ICET_OK;
+}
+
+static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_host, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
+                               struct icet_voxel_map_stats* out, const char* call) {
+    ICET_TRY(enter(m));
+    if (cap_rows < 0 || ld < cap_rows || (cap_rows > 0 && !xyz)) return map_refuse(m, std::string(call) + ": bad argument (cap_rows >= 0, ld >= cap_rows, a buffer of rows)");
+    if (!to_host && ((reinterpret_cast<uintptr_t>(xyz) & 3) || (reinterpret_cast<uintptr_t>(count) & 7) || (reinterpret_cast<uintptr_t>(key) & 7)))
+        return map_refuse(m, std::string(call) + ": a device pointer is not aligned to its element");
+    hipStream_t st = m->ctx->stream;
+    struct icet_voxel_map_stats s;
+    ICET_TRY(map_count(m, min_points, &s));
+    const int64_t n_out = s.cells_out, rows = std::min(n_out, cap_rows);
+    if (n_out > cap_rows) s.status |= ICET_VOXEL_MAP_TRUNCATED;
+    if (rows > 0) {
+        size_t tmp_bytes = 0;
+        MAPCHK(m, rocprim::radix_sort_pairs(nullptr, tmp_bytes, m->sel_key, m->sorted_key, m->sel_idx, m->sorted_idx, (size_t)n_out, 0, 63, st));
+        if (n_out > m->cap_sel) {                                     // (the count above drained the stream: nothing reads the old buffers)
+            BufferGroup& g = m->sel;
+            // rocPRIM's scratch grows with the size: what this size asks for, and the group grows as one
+            MAPCHK(m, grow(g, m->cap_sel, n_out, [&] {
+                int e = g.device(m->sel_key, (size_t)n_out);
+                if (!e) e = g.device(m->sorted_key, (size_t)n_out);
+                if (!e) e = g.device(m->sel_idx, (size_t)n_out);
+                if (!e) e = g.device(m->sorted_idx, (size_t)n_out);
+                if (!e) e = g.device_bytes(m->sort_tmp, std::max(tmp_bytes, (size_t)16));
+                return e;
+            }));
+        }
+        if (to_host && rows > m->cap_x) {
+            BufferGroup& g = m->xout;
+            MAPCHK(m, grow(g, m->cap_x, rows, [&] {
+                int e = g.device(m->x_xyz, 3 * (size_t)rows);
+                if (!e) e = g.device(m->x_count, (size_t)rows);
+                if (!e) e = g.device(m->x_key, (size_t)rows);
+                return e;
+            }));
+        }
+        const long long minp = std::max(1, min_points);
+        k_map_cells<true><<<(unsigned)((((size_t)1 << m->t.log2) + kCellSpan - 1) / kCellSpan), kCellBlock, 0, st>>>(m->t, minp, m->ctr, m->sel_key, m->sel_idx, (u64)n_out);
+        MAPCHK(m, hipGetLastError());
+        MAPCHK(m, rocprim::radix_sort_pairs(m->sort_tmp, tmp_bytes, m->sel_key, m->sorted_key, m->sel_idx, m->sorted_idx, (size_t)n_out, 0, 63, st));
+        float* dx = to_host ? m->x_xyz : xyz;
+        long long* dc = to_host ? (count ? m->x_count : nullptr) : reinterpret_cast<long long*>(count);
+        u64* dk = to_host ? (key ? m->x_key : nullptr) : reinterpret_cast<u64*>(key);
+        const long long dld = to_host ? rows : ld;
+        k_map_centroid<<<(unsigned)((rows + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->t, m->k, m->sorted_key, m->sorted_idx, rows, dx, dld, dc, dk);
+        MAPCHK(m, hipGetLastError());
+        if (to_host) {
+            MAPCHK(m, hipMemcpy2DAsync(xyz, sizeof(float) * (size_t)ld, dx, sizeof(float) * (size_t)rows, sizeof(float) * (size_t)rows, 3, hipMemcpyDeviceToHost, st));
+            if (count) MAPCHK(m, hipMemcpyAsync(count, dc, sizeof(int64_t) * (size_t)rows, hipMemcpyDeviceToHost, st));
+            if (key) MAPCHK(m, hipMemcpyAsync(key, dk, sizeof(uint64_t) * (size_t)rows, hipMemcpyDeviceToHost, st));
+        }
+        MAPCHK(m, hipStreamSynchronize(st));
+    }
+    if (out) *out = s;
+    return ICET_OK;
+}
+
+extern "C" {
+
+const char* icet_voxel_map_last_error(const icet_voxel_map* m) { return m ? m->err.c_str() : "null voxel map"; }
+
+icet_status icet_voxel_map_create(icet_ctx* c, const icet_voxel_map_params* p, icet_voxel_map** out) {
+    if (out) *out = nullptr;
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!out || !p) { c->err = "icet_voxel_map_create: bad argument"; return ICET_ERR_BAD_ARG; }
+    if (!rule::params_ok(p->cell, p->min_range, p->max_range, p->table_log2, p->flags) || p->reserved[0] || p->reserved[1] || p->reserved[2]) {
+        c->err = "icet_voxel_map_create: cell must be finite and > 0, the ranges finite, table_log2 10 .. 30, flags and the reserved words 0";
+        return ICET_ERR_BAD_ARG;
+    }
+    ICET_TRY(enter(c));
+    icet_voxel_map* m = new (std::nothrow) icet_voxel_map();
+    if (!m) { c->err = "host allocation failed"; return ICET_ERR_NOMEM; }
+    m->ctx = c; m->params = *p; m->k = rule::make_consts(p->cell, p->min_range, p->max_range); m->t.log2 = (uint32_t)p->table_log2;
+    const size_t size = (size_t)1 << p->table_log2;
+    int e = m->table.device(m->t.key, size);
+    if (!e) e = m->table.device(m->t.count, size);
+    if (!e) e = m->table.device(m->t.sum, 3 * size);
+    if (!e) e = m->record.device(m->ctr, (size_t)kCtrWords);
+    if (!e) e = m->record.pinned(m->h_rec, (size_t)kCtrWords);
+    icet_status st = ICET_OK;
+    if (e) { (void)hipGetLastError(); m->err = std::string("icet_voxel_map_create: ") + hipGetErrorString(static_cast<hipError_t>(e)); st = e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    if (st == ICET_OK) st = map_clear(m);
+    if (st != ICET_OK) { c->err = m->err; (void)icet_voxel_map_destroy(m); return st; }
+    *out = m;
+    return ICET_OK;
+}
+
+icet_status icet_voxel_map_destroy(icet_voxel_map* m) {
+    if (!m) return ICET_ERR_BAD_ARG;
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->stream);              // (an add or an extract may still read or write the table)
+    if (m->ev_stage) (void)hipEventDestroy(m->ev_stage);
+    delete m;                                                // (every array belongs to a group)
+    return ICET_OK;
+}
+
+icet_status icet_voxel_map_clear(icet_voxel_map* m) {
+    ICET_TRY(enter(m));
+    return map_clear(m);
+}
+
+icet_status icet_voxel_map_add_device(icet_voxel_map* m, int32_t n, const icet_dev_scan* scans, const float* poses, int32_t sign) {
+    return map_add(m, n, scans, poses, false, sign, "icet_voxel_map_add_device");
+}
+
+icet_status icet_voxel_map_add_posed_device(icet_voxel_map* m, int32_t n, const icet_dev_scan* scans, const float* d_poses, int32_t sign) {
+    return map_add(m, n, scans, d_poses, true, sign, "icet_voxel_map_add_posed_device");
+}
+
+icet_status icet_voxel_map_stats(icet_voxel_map* m, int32_t min_points, struct icet_voxel_map_stats* out) {
+    ICET_TRY(enter(m));
+    if (!out) return map_refuse(m, "icet_voxel_map_stats: bad argument");
+    return map_count(m, min_points, out);
+}
+
+icet_status icet_voxel_map_extract_device(icet_voxel_map* m, int32_t min_points, float* d_xyz, int64_t ld, int64_t cap_rows, int64_t* d_count, uint64_t* d_key,
+                                          struct icet_voxel_map_stats* out) {
+    return map_extract(m, min_points, false, d_xyz, ld, cap_rows, d_count, d_key, out, "icet_voxel_map_extract_device");
+}
+
+icet_status icet_voxel_map_extract(icet_voxel_map* m, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
+                                   struct icet_voxel_map_stats* out) {
+    return map_extract(m, min_points, true, xyz, ld, cap_rows, count, key, out, "icet_voxel_map_extract");
+}
+
+}  // extern "C"

@@ -815,6 +815,68 @@ icet_status icet_pose_graph_gate_device(icet_ctx* ctx, int32_t n, const float* d
 #define ICET_BAND_NON_FINITE 3
 icet_status icet_debug_block_tridiag(icet_ctx* ctx, int32_t n, const double* diag, const double* sub, const double* rhs, double* x, int32_t* status);
 
+/* --- the voxel map: many scans, each at a pose, fused into one centroid and one count per occupied cell, in HBM ---------------------
+ * A map borrows a context like a keyframe store (destroy it before the context) and owns its memory: an open-addressing hash table of 2^table_log2 entries
+ * of 40 bytes (key, count, three offset sums, all 64-bit integers).  THE RULE, for a row (x, y, z) of a scan at the pose T = [R | t] (4 x 4 row-major
+ * float32, p_world = R p + t), every operation IEEE double, rounded once, nothing contracted:
+ *   1. a row with a non-finite coordinate is counted in points_nonfinite and skipped;
+ *   2. d2 = (x x + y y) + z z; the row is kept iff d2 > min_range^2 and (max_range <= 0 or d2 <= max_range^2) -- at min_range = 0 exactly the all-zero rows go;
+ *   3. w_a = ((R[a][0] x + R[a][1] y) + R[a][2] z) + t[a], s_a = w_a (1 / (double)cell), c_a = floor(s_a); unless |c_a| < 2^20 on all three axes the row is
+ *      counted in points_outside and skipped (a NaN or infinity in the pose ends here);
+ *   4. u_a = s_a - c_a, q_a = min(floor(u_a 2^32), 2^32 - 1);
+ *   5. key = (c_x + 2^20) << 42 | (c_y + 2^20) << 21 | (c_z + 2^20); the cell of the key gets count += sign and sum_a += sign q_a, in 64-bit integers.
+ * The centroid of a cell of count n >= 1 is (float)(((double)c_a + (double)sum_a / ((double)n 2^32)) (double)cell).  Every sum is an integer, so a map holds
+ * the same bits whatever the order, the call boundaries or the launch shape, and REMOVING a scan (sign -1) at the pose it was added at undoes it exactly:
+ * remove at the old poses + add at the corrected ones is bit for bit a fresh build.
+ * CREATE: cell finite and > 0, min_range and max_range finite, table_log2 10 .. 30, flags and the reserved words 0, else ICET_ERR_BAD_ARG; a failed allocation
+ *   ICET_ERR_NOMEM (*out stays NULL).  The map starts empty.
+ * ADD: n scans (HOST descriptors of DEVICE rows, N x 3 column-major float32, ld >= n, padding never read, n = 0 allowed) at n poses -- HOST n x 16 floats
+ *   (add_device) or DEVICE n x 16 floats, 4-byte aligned (add_posed_device: what icet_pose_graph_optimize_device leaves in d_poses_out) --, sign +1 (add) or
+ *   -1 (remove); one launch for the whole call, asynchronous on the context's stream.  A row that finds no free entry is counted in points_dropped and raises
+ *   ICET_VOXEL_MAP_TABLE_FULL: it is never lost silently (a full table is not rehashed).  Option "map_lds" (icet_set_option; default 1): a block first
+ *   reduces its rows in an LDS table and flushes each distinct cell once; 0: one global update per row.  Same contents either way.
+ * STATS: the running totals since the last clear, and the cells as they are now, counted for min_points (cells_out: count >= max(1, min_points)).  Synchronises.
+ * EXTRACT: the cells with count >= max(1, min_points), sorted by key ascending (x-major, reproducible), as a scan: d_xyz N x 3 column-major float32 with
+ *   leading dimension ld >= cap_rows; d_count and d_key (either may be NULL) the cells' counts and keys.  With cap_rows < cells_out the cap_rows lowest keys
+ *   are written and ICET_VOXEL_MAP_TRUNCATED is set.  extract_device writes DEVICE pointers, extract HOST pointers; both synchronise and fill *out (may be NULL).
+ * CLEAR empties the table and zeroes the totals (asynchronous).
+ * Refusals (ICET_ERR_BAD_ARG, the reason in icet_voxel_map_last_error, nothing touched): a NULL map or array, n < 0, a bad descriptor, sign not +1 / -1,
+ *   cap_rows < 0, ld < cap_rows.  There is no CPU fallback.  The context's parked keyframe, workspace and every store are not touched. */
+typedef struct icet_voxel_map icet_voxel_map;
+typedef struct icet_voxel_map_params {
+    float cell;                   /* edge of a cell, metres */
+    float min_range, max_range;   /* rows with d2 <= min_range^2 or (max_range > 0) d2 > max_range^2 are skipped */
+    int32_t table_log2;           /* 10 .. 30 */
+    int32_t flags;                /* 0 */
+    int32_t reserved[3];
+} icet_voxel_map_params;          /* 32 bytes */
+#define ICET_VOXEL_MAP_OK 0
+#define ICET_VOXEL_MAP_TABLE_FULL 1       /* status bits */
+#define ICET_VOXEL_MAP_NEGATIVE 2         /* a cell's count is below zero: a remove without its add */
+#define ICET_VOXEL_MAP_TRUNCATED 4        /* (extract) fewer rows than cells_out were written */
+/* (a struct tag without a typedef: the call below has the same name) */
+struct icet_voxel_map_stats {
+    int64_t points_in;            /* rows read, adds and removes */
+    int64_t points_kept;          /* rows that reached a cell: adds minus removes */
+    int64_t points_nonfinite, points_outside, points_dropped;
+    int32_t cells_occupied;       /* count > 0 */
+    int32_t cells_out;            /* count >= max(1, min_points) */
+    int32_t cells_negative;       /* count < 0 */
+    int32_t status;               /* ICET_VOXEL_MAP_* bits */
+    int32_t reserved[2];
+};                                /* 64 bytes */
+icet_status icet_voxel_map_create(icet_ctx* ctx, const icet_voxel_map_params* p, icet_voxel_map** out);
+icet_status icet_voxel_map_destroy(icet_voxel_map* map);
+const char* icet_voxel_map_last_error(const icet_voxel_map* map);
+icet_status icet_voxel_map_clear(icet_voxel_map* map);
+icet_status icet_voxel_map_add_device(icet_voxel_map* map, int32_t n, const icet_dev_scan* scans, const float* poses, int32_t sign);
+icet_status icet_voxel_map_add_posed_device(icet_voxel_map* map, int32_t n, const icet_dev_scan* scans, const float* d_poses, int32_t sign);
+icet_status icet_voxel_map_stats(icet_voxel_map* map, int32_t min_points, struct icet_voxel_map_stats* out);
+icet_status icet_voxel_map_extract_device(icet_voxel_map* map, int32_t min_points, float* d_xyz, int64_t ld, int64_t cap_rows, int64_t* d_count, uint64_t* d_key,
+                                          struct icet_voxel_map_stats* out);
+icet_status icet_voxel_map_extract(icet_voxel_map* map, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
+                                   struct icet_voxel_map_stats* out);
+
 /* Launch-shape and diagnostic knobs of ONE context (the library never reads the environment).  Defaults are the measured
  * optima.  Launch-shape knobs yield the same result bits; "force_exact", "guard_scale" and "lut_polar_quantile" preserve every
  * DECISION (the per-voxel counts n2_raw / n2_in) but move points between the 4-point runs and the runs of one, i.e. they regroup
@@ -834,7 +896,7 @@ icet_status icet_debug_block_tridiag(icet_ctx* ctx, int32_t n, const double* dia
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
  * bits; default 0: measured no faster on MI355X, where a device-scope fence is an L2 write-back), "batch_parts" (0 = automatic), "batch_stage" (0..4), "force_exact"
  * (every scan-2 point through the literal classification), "library_sort" (rocPRIM radix sort instead of
- * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
+ * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents),"gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
  * the condition number |A|_F |A^-1|_F exceeds it is inverted by the literal restatement of the reference's statements -- column-pivoted QR
  * pseudo-inverse, eigenvectors, pruning -- instead of a Cholesky factorisation; 0 = always literal.  Not a launch-shape knob: between the two
  * routes cov / dx differ by rounding times the condition number).  Unknown name or value
