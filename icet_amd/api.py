@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_pose_graph_covariance_columns", "icet_pose_graph_covariance_columns_device", "icet_pose_graph_gate", "icet_pose_graph_gate_device",
                     "icet_voxel_map_create", "icet_voxel_map_destroy", "icet_voxel_map_last_error", "icet_voxel_map_clear", "icet_voxel_map_add_device",
                     "icet_voxel_map_add_posed_device", "icet_voxel_map_stats", "icet_voxel_map_extract_device", "icet_voxel_map_extract",
+                    "icet_voxel_map_index", "icet_voxel_map_query_device", "icet_voxel_map_query_posed_device",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -104,6 +105,20 @@ class MapStats(C.Structure):
 
 
 VOXEL_MAP_OK, VOXEL_MAP_TABLE_FULL, VOXEL_MAP_NEGATIVE, VOXEL_MAP_TRUNCATED = 0, 1, 2, 4
+VOXEL_MAP_QUERY_BAD_POSE = 8      # status bit of a query
+VOXEL_MAP_QUERY_WORLD = 1         # flag of a query
+VOXEL_MAP_MAX_QUERIES = 256
+MAP_QUERY_CHUNK = 2048            # ICET_VOXEL_MAP_QUERY_CHUNK: index entries per block of a query (the sizes at which its kernels take another path)
+
+
+class MapQuery(C.Structure):
+    """icet_voxel_map_query (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("min_points", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class MapSubmap(C.Structure):
+    """icet_voxel_map_submap (include/icet_hip.h), 40 bytes: a host descriptor of device memory."""
+    _fields_ = [("xyz", C.c_void_p), ("ld", C.c_int64), ("cap_rows", C.c_int64), ("count", C.c_void_p), ("key", C.c_void_p)]
 
 
 def voxel_key_cells(key):
@@ -480,6 +495,9 @@ def load_library():
     L.icet_voxel_map_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(MapStats)]
     L.icet_voxel_map_extract_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(MapStats)]
     L.icet_voxel_map_extract.argtypes = L.icet_voxel_map_extract_device.argtypes
+    L.icet_voxel_map_index.argtypes = [C.c_void_p, C.POINTER(MapStats)]
+    L.icet_voxel_map_query_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(MapQuery), C.POINTER(MapSubmap), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icet_voxel_map_query_posed_device.argtypes = L.icet_voxel_map_query_device.argtypes
     L.icet_keyframe_store_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p]
     L.icet_keyframe_store_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.icet_keyframe_store_snapshot_info.argtypes = [C.c_char_p, C.POINTER(SnapshotInfo)]
@@ -1318,6 +1336,28 @@ class KeyframeStore:
         self.put_device(slots, [(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs])
         self._ctx.sync()
 
+    def put_from_map(self, slots, vmap, poses, max_range, min_range=0.0, min_points=1, cap_rows=None, stamps=None):
+        """Fill slots[k] with the sub-map of ``vmap`` (a VoxelMap on the same context) around poses[k], in that pose's frame: VoxelMap.query_device into buffers
+        the store object keeps alive, then put_device with the query's d_rows -- the row counts never visit the host, and nothing synchronises between the two.
+        cap_rows: the rows reserved per sub-map (None: the cells the map's index holds, which no sub-map exceeds; a smaller value truncates to the lowest
+        keys).  With ``stamps`` the slots also get ``poses`` and the stamps (set_pose).  Returns the device int32 tensors (rows, total, status)."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        T = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
+        k = T.shape[0]
+        sl = self._index(slots, k)
+        cap = max(int(vmap.index()["cells_out"]) if cap_rows is None else int(cap_rows), 1)
+        xyz = torch.zeros((k, 3, cap), dtype=torch.float32, device=dev)
+        words = torch.zeros((3, k), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)                                   # (the buffers are complete before the context's stream writes them)
+        self._map_bufs = (xyz, words)                                 # alive until the next call: the put reads them in stream order
+        vmap.query_device(T, [(xyz[j].data_ptr(), cap, cap) for j in range(k)], words[0].data_ptr(), min_range=min_range, max_range=max_range,
+                          min_points=min_points, d_total_ptr=words[1].data_ptr(), d_status_ptr=words[2].data_ptr())
+        self.put_device(sl, [(xyz[j].data_ptr(), cap, cap) for j in range(k)], words[0].data_ptr())
+        if stamps is not None:
+            self.set_pose(sl, T, stamps)
+        return words[0], words[1], words[2]
+
     def register_device(self, slot_index, scan2_descs, params, d_out_ptr, d_x0_ptr=None):
         """Context.register_indexed_device against the store's slots (icet_keyframe_store_register_device)."""
         k = len(scan2_descs)
@@ -1808,6 +1848,60 @@ class VoxelMap:
         self._check(load_library().icet_voxel_map_extract(self._h, int(min_points), xyz.ctypes.data, max(cap, 1), cap, cnt.ctypes.data, key.ctypes.data, C.byref(s)))
         n = min(cap, s.cells_out)
         return dict(xyz=np.ascontiguousarray(xyz[:, :n].T), count=cnt[:n].copy(), key=key[:n].copy(), stats=s.as_dict())
+
+    def index(self):
+        """Rebuild the sorted index the queries read, if the map changed since the last one (icet_voxel_map_index).  Returns the stats at min_points 1 as the
+        build saw them.  Synchronises when it builds; does nothing otherwise."""
+        s = MapStats()
+        self._check(load_library().icet_voxel_map_index(self._h, C.byref(s)))
+        return s.as_dict()
+
+    def query_device(self, poses, outs, d_rows_ptr, min_range=0.0, max_range=0.0, min_points=1, world=False, d_total_ptr=None, d_status_ptr=None):
+        """For each pose the cells of the map within (min_range, max_range] of it, in the pose's own frame (``world``: in the map's), in key order, into device
+        buffers.  ``poses``: a Q x 4 x 4 NumPy array (icet_voxel_map_query_device) or a float32 CUDA tensor (icet_voxel_map_query_posed_device); ``outs``: one
+        (d_xyz_ptr, ld, cap_rows, d_count_ptr, d_key_ptr) per pose (a MapSubmap each; None for a pointer left out); d_rows / d_total / d_status: device int32
+        arrays of Q entries.  Asynchronous on the context's stream unless the index is stale."""
+        q = MapQuery(float(min_range), float(max_range), int(min_points), VOXEL_MAP_QUERY_WORLD if world else 0)
+        O = (MapSubmap * max(len(outs), 1))(*[MapSubmap(int(o[0]) if o[0] else None, int(o[1]), int(o[2]), int(o[3]) if len(o) > 3 and o[3] else None,
+                                                         int(o[4]) if len(o) > 4 and o[4] else None) for o in outs])
+        L = load_library()
+        if isinstance(poses, np.ndarray) or not hasattr(poses, "data_ptr"):
+            T = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
+            if T.shape[0] != len(outs):
+                raise IcetError(ICET_ERR_BAD_ARG, "one sub-map per 4 x 4 pose")
+            self._check(L.icet_voxel_map_query_device(self._h, len(outs), T.ctypes.data, C.byref(q), O, _vp(d_rows_ptr), _vp(d_total_ptr), _vp(d_status_ptr)))
+            return
+        import torch
+        if not (poses.is_cuda and poses.dtype == torch.float32 and poses.is_contiguous()) or poses.numel() != 16 * len(outs):
+            raise IcetError(ICET_ERR_BAD_ARG, "device poses must be a contiguous float32 CUDA tensor of one 4 x 4 pose per sub-map")
+        torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensor must be complete
+        self._check(L.icet_voxel_map_query_posed_device(self._h, len(outs), _vp(poses.data_ptr()), C.byref(q), O, _vp(d_rows_ptr), _vp(d_total_ptr), _vp(d_status_ptr)))
+
+    def query(self, poses, min_range=0.0, max_range=0.0, min_points=1, world=False, cap_rows=None):
+        """The host form: a count-only call, buffers of each query's total (or ``cap_rows``), the real call.  One dict per pose: xyz (n, 3) float32, count (n,)
+        int64, key (n,) uint64, total, status."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        nq = int(poses.shape[0]) if hasattr(poses, "data_ptr") else np.asarray(poses, np.float32).reshape(-1, 16).shape[0]
+        words = torch.zeros((3, max(nq, 1)), dtype=torch.int32, device=dev)      # rows | total | status
+        torch.cuda.synchronize(dev)
+        kw = dict(min_range=min_range, max_range=max_range, min_points=min_points, world=world)
+        self.query_device(poses, [(None, 0, 0)] * nq, words[0].data_ptr(), d_total_ptr=words[1].data_ptr(), **kw)
+        self._ctx.sync()
+        caps = [int(t) if cap_rows is None else int(cap_rows) for t in words[1, :nq].cpu().numpy()]
+        bufs = [(torch.zeros((3, max(c, 1)), dtype=torch.float32, device=dev), torch.zeros(max(c, 1), dtype=torch.int64, device=dev),
+                 torch.zeros(max(c, 1), dtype=torch.int64, device=dev)) for c in caps]
+        torch.cuda.synchronize(dev)
+        outs = [(x.data_ptr() if c else None, max(c, 1), c, n.data_ptr(), k.data_ptr()) for c, (x, n, k) in zip(caps, bufs)]
+        self.query_device(poses, outs, words[0].data_ptr(), d_total_ptr=words[1].data_ptr(), d_status_ptr=words[2].data_ptr(), **kw)
+        self._ctx.sync()
+        w = words.cpu().numpy()
+        res = []
+        for j, (x, n, k) in enumerate(bufs):
+            r = int(w[0, j])
+            res.append(dict(xyz=np.ascontiguousarray(x[:, :r].cpu().numpy().T), count=n[:r].cpu().numpy(), key=k[:r].cpu().numpy().view(np.uint64),
+                            total=int(w[1, j]), status=int(w[2, j])))
+        return res
 
 
 class MultiContext:

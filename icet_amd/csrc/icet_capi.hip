@@ -1533,6 +1533,7 @@ icet_status icet_set_option(icet_ctx* c, const char* name, double value) {
     else if (k == "snapshot_chunk_bytes") { if (!(value >= 0.0 && value <= 1e12)) { c->err = "snapshot_chunk_bytes must lie in [0, 1e12] (0: the default, 64 MiB)"; return ICET_ERR_BAD_ARG; } c->snapshot_chunk_bytes = (int64_t)value; }
     else if (k == "pg_solver") { if (!(value == 0.0 || value == 1.0 || value == 2.0)) { c->err = "pg_solver must be 0 (conjugate gradients), 1 (direct) or 2 (auto)"; return ICET_ERR_BAD_ARG; } c->pg_solver = iv; }
     else if (k == "map_lds") c->map_lds = iv != 0;
+    else if (k == "map_query_prune") c->map_query_prune = iv != 0;
     else { c->err = "unknown option: " + k; return ICET_ERR_BAD_ARG; }
     return ICET_OK;
 }

@@ -87,6 +87,7 @@ struct icet_ctx {
     // first one's store) makes it 2 or more and icet_sync synchronises the stream as before.
     int32_t* h_sync_word = nullptr; int armed_calls = 2;
     int map_lds = 1;                                             // option "map_lds": a voxel map's add reduces a block's rows in LDS first (icet_map.hip)
+    int map_query_prune = 1;                                     // option "map_query_prune": a voxel map's query skips the chunks outside a pose's run of x cells
     int64_t snapshot_chunk_bytes = 0;                          // option "snapshot_chunk_bytes": payload bytes per chunk of a store's save / load (0: 64 MiB)
     // Who owns what w and the pointers above point at: one group per set of arrays that grows together (the ensure_* functions of icet_capi.hip).  delete frees them (last member: gone first).
     struct Mem {

@@ -8,6 +8,11 @@
 //     k_map_cells     a pass over the entries, 16 per thread: <false> counts the cells with count > 0, count >= min_points, count < 0 (tallied in LDS, one
 //                     atomic per block and counter); <true> compacts (key, entry) of the cells with count >= min_points (a block claims its places with one atomic)
 //     k_map_centroid  one thread per output row, behind rocPRIM's device radix sort of the pairs by key
+// and the query (icet_voxel_map_query_*; the rule: icet_map_query.h) over the INDEX, the extract's sequence kept as sorted arrays:
+//     k_map_query_count   a block reads a chunk of kQueryChunk consecutive cells once and tests them against every pose of the call (poses in LDS, wave64 ballots
+//                         and popcounts): one int32 per (query, chunk).  A query whose run of x cells misses the chunk's is not tested (option "map_query_prune")
+//     k_map_query_scan    one block per query: exclusive offsets of its chunks, and d_rows / d_total / d_status
+//     k_map_query_write   the test again; a kept cell's rank is chunk offset + wave prefix + lane prefix, so the rows keep the index order, which is key order
 // Sums of integers only: no float atomic, no block waits for another block, no fence inside a kernel, and the contents do not depend on the launch shape.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -15,6 +20,7 @@
 #include "icet_ctx.h"
 #include "icet_staging.h"
 #include "icet_map.h"
+#include "icet_map_query.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -26,6 +32,7 @@ namespace icet {
 namespace {
 
 namespace rule = icet_map_rule;
+namespace qrule = icet_map_query_rule;
 typedef unsigned long long u64;
 
 constexpr int kAddBlock = 256;
@@ -35,6 +42,13 @@ constexpr int kLdsProbes = 8;
 constexpr int kCellBlock = 256;
 constexpr int kCellPer = 16;            // entries per thread of a pass over the table
 constexpr int kCellSpan = kCellBlock * kCellPer;
+constexpr int kQueryBlock = 256;         // a query block: 4 waves, each with kQueryTrips trips of 64 consecutive cells of the index
+constexpr int kQueryWaves = kQueryBlock / 64;
+constexpr int kQueryTrips = 8;
+constexpr int kQueryPerWave = 64 * kQueryTrips;
+constexpr int kQueryChunk = kQueryWaves * kQueryPerWave;
+static_assert(kQueryChunk == ICET_VOXEL_MAP_QUERY_CHUNK, "the chunk the header names");
+static_assert(qrule::kMaxQueries <= kQueryBlock && qrule::kMaxQueries == ICET_VOXEL_MAP_MAX_QUERIES, "a block stages the call's poses in one step per thread");
 
 struct MapScan { const float* ptr; int32_t n, ld, block0, pad; };      // block0: the first block of the scan in the launch
 static_assert(sizeof(MapScan) == 24, "ptr | n | ld | block0 | pad");
@@ -220,6 +234,144 @@ __global__ __launch_bounds__(kCellBlock) void k_map_centroid(MapTable t, rule::C
     if (d_key) d_key[i] = key;
 }
 
+// ---- the query: sub-maps around poses, out of the sorted index ---------------------------------------------------------------------------
+// The index: the cells of count >= 1 by ascending key, as contiguous arrays.  xyz: three columns of `ld` floats.
+struct MapIndex { const u64* key; const long long* count; const float* xyz; long long ld, n; };
+// A query's outputs as the device reads them (icet_voxel_map_submap, word for word).
+struct MapSubmap { float* xyz; long long ld, cap_rows; long long* count; u64* key; };
+static_assert(sizeof(MapSubmap) == sizeof(icet_voxel_map_submap) && sizeof(MapSubmap) == 40, "xyz | ld | cap_rows | count | key");
+
+// What a block knows of the call's queries: the poses, and the run of x cells each can reach (empty for an unusable pose).
+struct QueryLds {
+    float T[qrule::kMaxQueries][12];
+    int32_t lo[qrule::kMaxQueries], hi[qrule::kMaxQueries];
+    int32_t wcnt[qrule::kMaxQueries][kQueryWaves];                    // kept cells per (query, wave) of this block's chunk
+};
+// The cells of one lane: wave w of the block owns cells [w kQueryPerWave, (w + 1) kQueryPerWave) of the chunk, lane l the cells j * 64 + l of those, so that a
+// (trip j, lane) order within a wave and the wave order within the block are the index order.
+struct QueryCells { float m[kQueryTrips][3]; long long n[kQueryTrips]; };
+
+__device__ __forceinline__ void query_setup(QueryLds& s, const float* __restrict__ poses, int n_q, const qrule::Consts& kc, bool prune) {
+    for (int q = threadIdx.x; q < n_q; q += kQueryBlock) {
+        for (int j = 0; j < 12; j++) s.T[q][j] = poses[16 * (size_t)q + j];
+        qrule::x_interval(kc, s.T[q], prune, s.lo[q], s.hi[q]);
+    }
+}
+__device__ __forceinline__ void query_load(const MapIndex& ix, long long first, QueryCells& c) {
+#pragma unroll
+    for (int j = 0; j < kQueryTrips; j++) {
+        const long long i = first + j * 64;
+        const bool in = i < ix.n;                                      // a cell behind the index: count 0 takes part in nothing
+        c.n[j] = in ? ix.count[i] : 0;
+        for (int a = 0; a < 3; a++) c.m[j][a] = in ? ix.xyz[a * ix.ld + i] : 0.f;
+    }
+}
+// Kept cells of this wave per query of the call, into s.wcnt.  A query whose run of x cells misses the chunk's keeps none of its cells and is not tested.
+__device__ __forceinline__ void query_count(QueryLds& s, const QueryCells& c, int n_q, const qrule::Consts& kc, int32_t x_first, int32_t x_last) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int q = 0; q < n_q; q++) {
+        int32_t kept = 0;
+        if (s.lo[q] <= x_last && s.hi[q] >= x_first) {                // (the same for every thread of the block)
+#pragma unroll
+            for (int j = 0; j < kQueryTrips; j++) {
+                double d[3];
+                kept += __popcll(__ballot(qrule::keep(kc, s.T[q], c.m[j][0], c.m[j][1], c.m[j][2], c.n[j], d)));
+            }
+        }
+        if (lane == 0) s.wcnt[q][wave] = kept;
+    }
+}
+
+// One int32 per (query, chunk): counts[q * n_chunks + chunk].
+__global__ __launch_bounds__(kQueryBlock) void k_map_query_count(MapIndex ix, const float* __restrict__ poses, int n_q, qrule::Consts kc, int prune,
+                                                                 int32_t* __restrict__ counts, long long n_chunks) {
+    __shared__ QueryLds s;
+    const long long chunk0 = (long long)blockIdx.x * kQueryChunk;     // < ix.n: the grid is the chunks of the index
+    const int32_t x_first = qrule::key_x(ix.key[chunk0]), x_last = qrule::key_x(ix.key[min(chunk0 + kQueryChunk, ix.n) - 1]);
+    query_setup(s, poses, n_q, kc, prune != 0);
+    QueryCells c;
+    query_load(ix, chunk0 + (threadIdx.x >> 6) * kQueryPerWave + (threadIdx.x & 63), c);
+    __syncthreads();
+    query_count(s, c, n_q, kc, x_first, x_last);
+    __syncthreads();
+    for (int q = threadIdx.x; q < n_q; q += kQueryBlock) {
+        int32_t t = 0;
+        for (int w = 0; w < kQueryWaves; w++) t += s.wcnt[q][w];
+        counts[(long long)q * n_chunks + blockIdx.x] = t;
+    }
+}
+
+// One block per query: counts[q][*] -> offs[q][*] (exclusive), and the query's three words.  A thread owns a run of consecutive chunks.
+__global__ __launch_bounds__(kQueryBlock) void k_map_query_scan(const int32_t* __restrict__ counts, int32_t* __restrict__ offs, long long n_chunks, const float* __restrict__ poses,
+                                                                const MapSubmap* __restrict__ outs, int32_t* __restrict__ d_rows, int32_t* __restrict__ d_total,
+                                                                int32_t* __restrict__ d_status) {
+    __shared__ int32_t part[kQueryBlock];
+    const int q = blockIdx.x;
+    const long long per = (n_chunks + kQueryBlock - 1) / kQueryBlock, b = min(n_chunks, (long long)threadIdx.x * per), e = min(n_chunks, b + per);
+    const int32_t* cq = counts + (long long)q * n_chunks;
+    int32_t* oq = offs + (long long)q * n_chunks;
+    int32_t mine = 0;
+    for (long long i = b; i < e; i++) mine += cq[i];
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (int step = 1; step < kQueryBlock; step <<= 1) {              // inclusive scan of the 256 partial sums
+        const int32_t v = (int)threadIdx.x >= step ? part[threadIdx.x - step] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int32_t run = part[threadIdx.x] - mine;
+    for (long long i = b; i < e; i++) { oq[i] = run; run += cq[i]; }
+    if (threadIdx.x == 0) {
+        const long long total = part[kQueryBlock - 1], cap = outs[q].cap_rows;
+        float T[12];
+        for (int j = 0; j < 12; j++) T[j] = poses[16 * (size_t)q + j];
+        d_rows[q] = (int32_t)min(total, cap);
+        if (d_total) d_total[q] = (int32_t)total;
+        if (d_status) d_status[q] = (qrule::pose_ok(T) ? 0 : ICET_VOXEL_MAP_QUERY_BAD_POSE) | (total > cap ? ICET_VOXEL_MAP_TRUNCATED : 0);
+    }
+}
+
+// The test again, and the rows: a kept cell's rank is its chunk's offset + the kept cells of the waves before its own + those of its wave's earlier trips +
+// those of the lanes below it in its trip's ballot -- the index order.  Ranks from cap_rows on are not written.
+__global__ __launch_bounds__(kQueryBlock) void k_map_query_write(MapIndex ix, const float* __restrict__ poses, int n_q, qrule::Consts kc, int prune,
+                                                                 const int32_t* __restrict__ counts, const int32_t* __restrict__ offs, long long n_chunks,
+                                                                 const MapSubmap* __restrict__ outs) {
+    __shared__ QueryLds s;
+    const long long chunk0 = (long long)blockIdx.x * kQueryChunk;
+    const int32_t x_first = qrule::key_x(ix.key[chunk0]), x_last = qrule::key_x(ix.key[min(chunk0 + kQueryChunk, ix.n) - 1]);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long first = chunk0 + wave * kQueryPerWave + lane;
+    query_setup(s, poses, n_q, kc, prune != 0);
+    for (int q = threadIdx.x; q < n_q; q += kQueryBlock) {            // (the thread that staged query q) no row of q comes from this chunk: as if pruned
+        const long long at = (long long)q * n_chunks + blockIdx.x;
+        if (counts[at] == 0 || offs[at] >= outs[q].cap_rows) { s.lo[q] = rule::kCellLimit; s.hi[q] = -rule::kCellLimit; }
+    }
+    QueryCells c;
+    query_load(ix, first, c);
+    __syncthreads();
+    query_count(s, c, n_q, kc, x_first, x_last);
+    __syncthreads();
+    for (int q = 0; q < n_q; q++) {
+        if (!(s.lo[q] <= x_last && s.hi[q] >= x_first)) continue;     // (the same for every thread of the block)
+        const MapSubmap o = outs[q];
+        long long rank0 = offs[(long long)q * n_chunks + blockIdx.x];
+        for (int w = 0; w < wave; w++) rank0 += s.wcnt[q][w];
+#pragma unroll
+        for (int j = 0; j < kQueryTrips; j++) {
+            double d[3];
+            const bool kept = qrule::keep(kc, s.T[q], c.m[j][0], c.m[j][1], c.m[j][2], c.n[j], d);
+            const u64 mask = __ballot(kept);
+            const long long rank = rank0 + __popcll(mask & (((u64)1 << lane) - 1));
+            rank0 += __popcll(mask);
+            if (!kept || rank >= o.cap_rows) continue;                // rank < cap_rows <= ld: inside the caller's columns
+            for (int a = 0; a < 3; a++) o.xyz[a * o.ld + rank] = kc.world ? c.m[j][a] : qrule::row(s.T[q], d, a);
+            if (o.count) o.count[rank] = c.n[j];
+            if (o.key) o.key[rank] = ix.key[first + j * 64];           // (kept: the cell exists)
+        }
+    }
+}
+
 }  // namespace
 }  // namespace icet
 
@@ -240,7 +392,16 @@ struct icet_voxel_map {
     // an extract: the selected (key, entry) pairs, their sorted copy, rocPRIM's scratch; the rows of the host form
     u64* sel_key = nullptr; u64* sorted_key = nullptr; uint32_t* sel_idx = nullptr; uint32_t* sorted_idx = nullptr; void* sort_tmp = nullptr; int64_t cap_sel = 0;
     float* x_xyz = nullptr; long long* x_count = nullptr; u64* x_key = nullptr; int64_t cap_x = 0;
-    BufferGroup table, record, stage, sel, xout;
+    // the index of the queries: the cells of count >= 1 by key (key, count, three columns of cap_ix centroid floats), its own select and sort buffers; what the
+    // build saw; stale after every add, remove and clear
+    u64* ix_key = nullptr; long long* ix_count = nullptr; float* ix_xyz = nullptr; u64* ix_sel_key = nullptr; uint32_t* ix_sel_idx = nullptr;
+    uint32_t* ix_sorted_idx = nullptr; void* ix_tmp = nullptr; size_t ix_tmp_bytes = 0; int64_t cap_ix = 0, ix_n = 0;
+    struct icet_voxel_map_stats ix_stats{}; bool ix_stale = true;
+    // a query call: its host poses and output descriptors (staged like an add's), and its per-(query, chunk) counts and offsets
+    float* h_qpose = nullptr; float* d_qpose = nullptr; MapSubmap* h_qout = nullptr; MapSubmap* d_qout = nullptr; int32_t cap_q = 0;
+    hipEvent_t ev_qstage = nullptr; bool qstage_in_flight = false;
+    int32_t* q_counts = nullptr; int32_t* q_offs = nullptr; int64_t cap_qc = 0;
+    BufferGroup table, record, stage, sel, xout, index, qstage, qcounts;
 };
 
 #define MAPCHK(m, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
@@ -258,6 +419,7 @@ static icet_status map_refuse(icet_voxel_map* m, const std::string& why) { m->er
 static icet_status map_clear(icet_voxel_map* m) {
     const size_t size = (size_t)1 << m->t.log2;
     hipStream_t st = m->ctx->stream;
+    m->ix_stale = true;
     MAPCHK(m, hipMemsetAsync(m->t.key, 0xFF, sizeof(u64) * size, st));
     MAPCHK(m, hipMemsetAsync(m->t.count, 0, sizeof(u64) * size, st));
     MAPCHK(m, hipMemsetAsync(m->t.sum, 0, sizeof(u64) * 3 * size, st));
@@ -299,6 +461,7 @@ static icet_status map_add(icet_voxel_map* m, int32_t n, const icet_dev_scan* sc
     if (blocks > 0x7FFFFFFF) return map_refuse(m, std::string(call) + ": too many rows in one call");
     if (blocks == 0) return ICET_OK;                                  // nothing to read
     icet_ctx* c = m->ctx;
+    m->ix_stale = true;                                               // (from here on the table may change)
     if (m->stage_in_flight) { MAPCHK(m, hipEventSynchronize(m->ev_stage)); m->stage_in_flight = false; }      // the previous call has read the staging
     if (n > m->cap_scans) {
         MAPCHK(m, hipStreamSynchronize(c->stream));              // (its kernel may still read the device side)
@@ -387,6 +550,115 @@ static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_ho
     return ICET_OK;
 }
 
+// The index of the queries, if the table changed since it was built: extract's sequence -- count, select, sort by key, centroids -- for min_points 1, into the
+// index's own buffers.  The count drains the stream (the sort's size is a host value), so nothing reads the old index when it grows.
+static icet_status map_index(icet_voxel_map* m) {
+    if (!m->ix_stale) return ICET_OK;
+    hipStream_t st = m->ctx->stream;
+    struct icet_voxel_map_stats s;
+    ICET_TRY(map_count(m, 1, &s));
+    const int64_t n = s.cells_out;
+    m->ix_n = 0;
+    if (n > 0) {
+        size_t tmp_bytes = 0;
+        MAPCHK(m, rocprim::radix_sort_pairs(nullptr, tmp_bytes, m->ix_sel_key, m->ix_key, m->ix_sel_idx, m->ix_sorted_idx, (size_t)n, 0, 63, st));
+        if (n > m->cap_ix || tmp_bytes > m->ix_tmp_bytes) {           // (the scratch is what rocPRIM asked for at the capacity: a smaller sort is not promised to ask less)
+            BufferGroup& g = m->index;
+            const int64_t need = std::max(n + n / 4, m->cap_ix);      // (a map that grows scan by scan does not allocate at every query)
+            size_t need_tmp = 0;
+            MAPCHK(m, rocprim::radix_sort_pairs(nullptr, need_tmp, m->ix_sel_key, m->ix_key, m->ix_sel_idx, m->ix_sorted_idx, (size_t)need, 0, 63, st));
+            need_tmp = std::max(std::max(need_tmp, tmp_bytes), (size_t)16);
+            MAPCHK(m, grow(g, m->cap_ix, need, [&] {
+                int e = g.device(m->ix_key, (size_t)need);
+                if (!e) e = g.device(m->ix_count, (size_t)need);
+                if (!e) e = g.device(m->ix_xyz, 3 * (size_t)need);
+                if (!e) e = g.device(m->ix_sel_key, (size_t)need);
+                if (!e) e = g.device(m->ix_sel_idx, (size_t)need);
+                if (!e) e = g.device(m->ix_sorted_idx, (size_t)need);
+                if (!e) e = g.device_bytes(m->ix_tmp, need_tmp);
+                return e;
+            }));
+            m->ix_tmp_bytes = need_tmp;
+        }
+        k_map_cells<true><<<(unsigned)((((size_t)1 << m->t.log2) + kCellSpan - 1) / kCellSpan), kCellBlock, 0, st>>>(m->t, 1, m->ctr, m->ix_sel_key, m->ix_sel_idx, (u64)n);
+        MAPCHK(m, hipGetLastError());
+        MAPCHK(m, rocprim::radix_sort_pairs(m->ix_tmp, tmp_bytes, m->ix_sel_key, m->ix_key, m->ix_sel_idx, m->ix_sorted_idx, (size_t)n, 0, 63, st));
+        k_map_centroid<<<(unsigned)((n + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->t, m->k, m->ix_key, m->ix_sorted_idx, n, m->ix_xyz, m->cap_ix, m->ix_count, nullptr);
+        MAPCHK(m, hipGetLastError());
+    }
+    m->ix_n = n; m->ix_stats = s; m->ix_stale = false;
+    return ICET_OK;
+}
+
+static icet_status map_query(icet_voxel_map* m, int32_t n_q, const float* poses, bool poses_on_device, const icet_voxel_map_query* q, const icet_voxel_map_submap* outs,
+                             int32_t* d_rows, int32_t* d_total, int32_t* d_status, const char* call) {
+    ICET_TRY(enter(m));
+    // everything is checked before anything is touched
+    const std::string who(call);
+    if (n_q < 1 || n_q > qrule::kMaxQueries) return map_refuse(m, who + ": n_q must lie in 1 .. 256");
+    if (!poses || !q || !outs || !d_rows) return map_refuse(m, who + ": bad argument (a NULL array)");
+    if (!qrule::params_ok(q->min_range, q->max_range, q->flags, q->reserved)) return map_refuse(m, who + ": the ranges must be finite, the flags known and the reserved words 0");
+    if ((poses_on_device && (reinterpret_cast<uintptr_t>(poses) & 3)) || ((reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_total) | reinterpret_cast<uintptr_t>(d_status)) & 3))
+        return map_refuse(m, who + ": a device pointer is not aligned to its element");
+    bool any_rows = false;
+    for (int k = 0; k < n_q; k++) {
+        const icet_voxel_map_submap& o = outs[k];
+        if (!qrule::submap_ok(o.xyz, o.ld, o.cap_rows)) return map_refuse(m, who + ": bad sub-map (outs[" + std::to_string(k) + "]: cap_rows >= 0, ld >= cap_rows, a buffer of rows)");
+        if ((reinterpret_cast<uintptr_t>(o.xyz) & 3) || (reinterpret_cast<uintptr_t>(o.count) & 7) || (reinterpret_cast<uintptr_t>(o.key) & 7))
+            return map_refuse(m, who + ": a device pointer is not aligned to its element (outs[" + std::to_string(k) + "])");
+        any_rows = any_rows || o.cap_rows > 0;
+    }
+    icet_ctx* c = m->ctx;
+    hipStream_t st = c->stream;
+    ICET_TRY(map_index(m));
+    const long long n_chunks = (m->ix_n + kQueryChunk - 1) / kQueryChunk;
+    if (m->qstage_in_flight) { MAPCHK(m, hipEventSynchronize(m->ev_qstage)); m->qstage_in_flight = false; }      // the previous call has read the staging
+    if (n_q > m->cap_q) {
+        MAPCHK(m, hipStreamSynchronize(st));                         // (its kernels may still read the device side)
+        BufferGroup& g = m->qstage;
+        MAPCHK(m, grow(g, m->cap_q, n_q, [&] {
+            int e = g.pinned(m->h_qpose, 16 * (size_t)n_q);
+            if (!e) e = g.device(m->d_qpose, 16 * (size_t)n_q);
+            if (!e) e = g.pinned(m->h_qout, (size_t)n_q);
+            if (!e) e = g.device(m->d_qout, (size_t)n_q);
+            return e;
+        }));
+    }
+    const int64_t words = (int64_t)n_q * n_chunks;
+    if (words > m->cap_qc) {
+        MAPCHK(m, hipStreamSynchronize(st));
+        BufferGroup& g = m->qcounts;
+        MAPCHK(m, grow(g, m->cap_qc, words, [&] {
+            int e = g.device(m->q_counts, (size_t)words);
+            if (!e) e = g.device(m->q_offs, (size_t)words);
+            return e;
+        }));
+    }
+    if (!m->ev_qstage) MAPCHK(m, hipEventCreateWithFlags(&m->ev_qstage, hipEventDisableTiming));
+    for (int k = 0; k < n_q; k++) m->h_qout[k] = MapSubmap{outs[k].xyz, outs[k].ld, outs[k].cap_rows, reinterpret_cast<long long*>(outs[k].count), reinterpret_cast<u64*>(outs[k].key)};
+    MAPCHK(m, hipMemcpyAsync(m->d_qout, m->h_qout, sizeof(MapSubmap) * (size_t)n_q, hipMemcpyHostToDevice, st));
+    if (!poses_on_device) {
+        std::memcpy(m->h_qpose, poses, sizeof(float) * 16 * (size_t)n_q);
+        MAPCHK(m, hipMemcpyAsync(m->d_qpose, m->h_qpose, sizeof(float) * 16 * (size_t)n_q, hipMemcpyHostToDevice, st));
+    }
+    const float* dp = poses_on_device ? poses : m->d_qpose;
+    const qrule::Consts kc = qrule::make_consts(m->params.cell, q->min_range, q->max_range, q->min_points, q->flags);
+    const MapIndex ix{m->ix_key, m->ix_count, m->ix_xyz, (long long)m->cap_ix, (long long)m->ix_n};
+    const int prune = c->map_query_prune;
+    if (n_chunks > 0) {
+        k_map_query_count<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, n_chunks);
+        MAPCHK(m, hipGetLastError());
+    }
+    k_map_query_scan<<<(unsigned)n_q, kQueryBlock, 0, st>>>(m->q_counts, m->q_offs, n_chunks, dp, m->d_qout, d_rows, d_total, d_status);
+    MAPCHK(m, hipGetLastError());
+    if (n_chunks > 0 && any_rows) {                                   // (a count-only call writes no row)
+        k_map_query_write<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, m->q_offs, n_chunks, m->d_qout);
+        MAPCHK(m, hipGetLastError());
+    }
+    MAPCHK(m, hipEventRecord(m->ev_qstage, st)); m->qstage_in_flight = true;
+    return ICET_OK;
+}
+
 extern "C" {
 
 const char* icet_voxel_map_last_error(const icet_voxel_map* m) { return m ? m->err.c_str() : "null voxel map"; }
@@ -422,6 +694,7 @@ icet_status icet_voxel_map_destroy(icet_voxel_map* m) {
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);              // (an add or an extract may still read or write the table)
     if (m->ev_stage) (void)hipEventDestroy(m->ev_stage);
+    if (m->ev_qstage) (void)hipEventDestroy(m->ev_qstage);
     delete m;                                                // (every array belongs to a group)
     return ICET_OK;
 }
@@ -453,6 +726,23 @@ icet_status icet_voxel_map_extract_device(icet_voxel_map* m, int32_t min_points,
 icet_status icet_voxel_map_extract(icet_voxel_map* m, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
                                    struct icet_voxel_map_stats* out) {
     return map_extract(m, min_points, true, xyz, ld, cap_rows, count, key, out, "icet_voxel_map_extract");
+}
+
+icet_status icet_voxel_map_index(icet_voxel_map* m, struct icet_voxel_map_stats* out) {
+    ICET_TRY(enter(m));
+    ICET_TRY(map_index(m));
+    if (out) *out = m->ix_stats;
+    return ICET_OK;
+}
+
+icet_status icet_voxel_map_query_device(icet_voxel_map* m, int32_t n_q, const float* poses, const icet_voxel_map_query* q, const icet_voxel_map_submap* outs,
+                                        int32_t* d_rows, int32_t* d_total, int32_t* d_status) {
+    return map_query(m, n_q, poses, false, q, outs, d_rows, d_total, d_status, "icet_voxel_map_query_device");
+}
+
+icet_status icet_voxel_map_query_posed_device(icet_voxel_map* m, int32_t n_q, const float* d_poses, const icet_voxel_map_query* q, const icet_voxel_map_submap* outs,
+                                              int32_t* d_rows, int32_t* d_total, int32_t* d_status) {
+    return map_query(m, n_q, d_poses, true, q, outs, d_rows, d_total, d_status, "icet_voxel_map_query_posed_device");
 }
 
 }  // extern "C"

@@ -877,6 +877,56 @@ icet_status icet_voxel_map_extract_device(icet_voxel_map* map, int32_t min_point
 icet_status icet_voxel_map_extract(icet_voxel_map* map, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
                                    struct icet_voxel_map_stats* out);
 
+/* --- the voxel map's query: sub-maps around poses, each in its pose's own frame, in one call -------------------------------------------
+ * For each of n_q poses T = [R | t] (the map's POSE convention) the cells of the map within a range of t, laid out as a scan, so that a sub-map goes into
+ * icet_keyframe_store_put_device / icet_keyframe_device_n with its row count read on the device.  THE RULE, for a cell of count n and centroid
+ * m = (m_0, m_1, m_2) -- the three float32 values extract writes --, every operation IEEE double, rounded once, nothing contracted:
+ *   1. if any of the 12 entries T[0 .. 11] is not finite the query yields 0 rows and status bit ICET_VOXEL_MAP_QUERY_BAD_POSE (host and device poses alike:
+ *      a pose is never refused on the host);
+ *   2. the cell takes part iff n >= max(1, min_points);
+ *   3. d_a = (double)m_a - (double)t_a, d2 = (d_0 d_0 + d_1 d_1) + d_2 d_2; the cell is kept iff d2 > min_range^2 and (max_range <= 0 or d2 <= max_range^2),
+ *      the squares taken in double from the float32 parameters -- the map's own range rule: a centroid exactly at t is dropped at min_range = 0;
+ *   4. the row is (float)((R[0][a] d_0 + R[1][a] d_1) + R[2][a] d_2) for a = 0, 1, 2: R^T d, the inverse of the pose taken as the transpose (R is the
+ *      caller's and is not checked); with flag ICET_VOXEL_MAP_QUERY_WORLD the row is m itself, bit for bit the row extract writes;
+ *   5. a query's rows are in ascending key order, extract's; count (int64) and key (uint64) per row are optional outputs;
+ *   6. total = the kept cells, rows = min(total, cap_rows); with total > cap_rows the cap_rows lowest keys are written and ICET_VOXEL_MAP_TRUNCATED is set for
+ *      that query.  cap_rows = 0 with a NULL xyz is a count-only query: how a caller sizes its buffers.  Padding beyond rows is never written.
+ * INDEX: the queries read a sorted index of the map -- the cells with count >= 1 by ascending key, as contiguous arrays of key, count and centroid, in buffers
+ *   of its own (extract's results do not change).  add, remove and clear make it stale; icet_voxel_map_index rebuilds a stale index with extract's
+ *   sequence (count, select, sort, centroids), which synchronises, fills *out (may be NULL) with the stats at min_points 1, and does nothing but that when the
+ *   index is current.
+ * QUERY: poses are HOST n_q x 16 floats (query_device) or DEVICE n_q x 16 floats, 4-byte aligned (query_posed_device: what icet_pose_graph_optimize_device
+ *   leaves in d_poses_out); outs HOST descriptors of DEVICE memory; d_rows (required), d_total and d_status (either may be NULL) DEVICE int32 arrays of n_q
+ *   entries.  Both calls rebuild a stale index first (and synchronise then, or when their own buffers grow); otherwise they are asynchronous on the context's
+ *   stream and write nothing on the host.  1 <= n_q <= ICET_VOXEL_MAP_MAX_QUERIES.  Three launches: the cells are read in chunks of
+ *   ICET_VOXEL_MAP_QUERY_CHUNK consecutive index entries and counted per (query, chunk); one block per query scans its counts and writes the three words; the
+ *   test is repeated and the rows are written at chunk offset + wave prefix + lane prefix.  No atomics on global memory.  Option "map_query_prune"
+ *   (icet_set_option; default 1): keys sort x-major, so a chunk whose x cells lie outside [floor((t_0 - max_range) / cell) - 1, floor((t_0 + max_range) / cell) + 1]
+ *   is not tested for that query; 0 tests everything.  Same bits either way.
+ * Refusals (ICET_ERR_BAD_ARG, the reason in icet_voxel_map_last_error, nothing touched): a NULL map or array, n_q out of range, cap_rows < 0, ld < cap_rows,
+ *   cap_rows > 0 with a NULL xyz, a device pointer not aligned to its element, a non-finite min_range or max_range, unknown flag bits, nonzero reserved words. */
+#define ICET_VOXEL_MAP_QUERY_BAD_POSE 8   /* status bit of a query: a non-finite entry in its pose */
+#define ICET_VOXEL_MAP_QUERY_WORLD 1      /* flag: rows in the world frame */
+#define ICET_VOXEL_MAP_MAX_QUERIES 256
+#define ICET_VOXEL_MAP_QUERY_CHUNK 2048   /* index entries per block of a query */
+typedef struct icet_voxel_map_query {
+    float min_range, max_range;   /* cells with d2 <= min_range^2 or (max_range > 0) d2 > max_range^2 are dropped */
+    int32_t min_points;           /* cells with count >= max(1, min_points) take part */
+    int32_t flags;                /* ICET_VOXEL_MAP_QUERY_* */
+    int32_t reserved[4];
+} icet_voxel_map_query;           /* 32 bytes */
+typedef struct icet_voxel_map_submap {
+    float* xyz;                   /* DEVICE rows, N x 3 column-major float32; may be NULL with cap_rows 0 */
+    int64_t ld, cap_rows;         /* ld >= cap_rows >= 0 */
+    int64_t* count;               /* DEVICE, cap_rows entries, or NULL */
+    uint64_t* key;                /* DEVICE, cap_rows entries, or NULL */
+} icet_voxel_map_submap;          /* 40 bytes: a HOST descriptor of DEVICE memory */
+icet_status icet_voxel_map_index(icet_voxel_map* map, struct icet_voxel_map_stats* out);
+icet_status icet_voxel_map_query_device(icet_voxel_map* map, int32_t n_q, const float* poses, const icet_voxel_map_query* q, const icet_voxel_map_submap* outs,
+                                        int32_t* d_rows, int32_t* d_total, int32_t* d_status);
+icet_status icet_voxel_map_query_posed_device(icet_voxel_map* map, int32_t n_q, const float* d_poses, const icet_voxel_map_query* q, const icet_voxel_map_submap* outs,
+                                              int32_t* d_rows, int32_t* d_total, int32_t* d_status);
+
 /* Launch-shape and diagnostic knobs of ONE context (the library never reads the environment).  Defaults are the measured
  * optima.  Launch-shape knobs yield the same result bits; "force_exact", "guard_scale" and "lut_polar_quantile" preserve every
  * DECISION (the per-voxel counts n2_raw / n2_in) but move points between the 4-point runs and the runs of one, i.e. they regroup
@@ -896,7 +946,7 @@ icet_status icet_voxel_map_extract(icet_voxel_map* map, int32_t min_points, floa
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
  * bits; default 0: measured no faster on MI355X, where a device-scope fence is an L2 write-back), "batch_parts" (0 = automatic), "batch_stage" (0..4), "force_exact"
  * (every scan-2 point through the literal classification), "library_sort" (rocPRIM radix sort instead of
- * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents),"gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
+ * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents), "map_query_prune" (icet_voxel_map_query_*: 1, the default, a block skips the queries whose run of x cells misses its chunk; 0 every cell is tested for every query; same bits), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
  * the condition number |A|_F |A^-1|_F exceeds it is inverted by the literal restatement of the reference's statements -- column-pivoted QR
  * pseudo-inverse, eigenvectors, pruning -- instead of a Cholesky factorisation; 0 = always literal.  Not a launch-shape knob: between the two
  * routes cov / dx differ by rounding times the condition number).  Unknown name or value
