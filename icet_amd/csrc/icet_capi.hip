@@ -697,7 +697,8 @@ icet_status icet_destroy(icet_ctx* c) {
     for (icet_ctx* h : c->helpers) (void)icet_destroy(h);
     for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop, &c->g_indexed, &c->g_scored, &c->g_score}) if (g->have_graph) { (void)hipGraphExecDestroy(g->exec); (void)hipGraphDestroy(g->graph); }
     for (hipEvent_t e : c->ev_acc) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {c->ev_sel, c->ev_s2, c->ev_kf, c->ev_kfd, c->ev_prev, c->ev_pts2, c->ev_a, c->ev_b, c->ev_c, c->ev_fork, c->ev_desc, c->ev_graph, c->ev_stage, c->ev_join})
+    c->sel_read.destroy();
+    for (hipEvent_t e : {c->ev_s2, c->ev_kf, c->ev_kfd, c->ev_prev, c->ev_pts2, c->ev_a, c->ev_b, c->ev_c, c->ev_fork, c->ev_desc, c->ev_graph, c->ev_stage, c->ev_join})
         if (e) (void)hipEventDestroy(e);
     if (c->st_copy) (void)hipStreamDestroy(c->st_copy);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -1161,7 +1162,7 @@ icet_status icet_select_best_device(icet_ctx* c, int32_t n_regs, const int32_t* 
     ICET_TRY(enter(c));
     // members of every group in ascending order, then the offsets: one upload from pinned staging
     const int64_t need = (int64_t)n_regs + n_groups + 1;
-    if (c->sel_in_flight) { HIPCHK(c, hipEventSynchronize(c->ev_sel)); c->sel_in_flight = false; }
+    HIPCHK(c, c->sel_read.wait());                                    // the previous call's copy has read h_sel
     if (need > c->cap_sel) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         BufferGroup& sm = c->mem.sel;
@@ -1174,8 +1175,7 @@ icet_status icet_select_best_device(icet_ctx* c, int32_t n_regs, const int32_t* 
     std::vector<int32_t> fill(offs, offs + n_groups);
     for (int r = 0; r < n_regs; r++) members[fill[(size_t)group[r]]++] = r;
     HIPCHK(c, hipMemcpyAsync(c->d_sel, c->h_sel, sizeof(int32_t) * (size_t)need, hipMemcpyHostToDevice, c->stream));
-    if (!c->ev_sel) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sel, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_sel, c->stream)); c->sel_in_flight = true;
+    HIPCHK(c, c->sel_read.mark(c->stream));
     HIPCHK(c, launch_select_best(c->d_sel, c->d_sel + n_regs, n_groups, d_score, d_out, d_best, d_best_out, c->stream));
     return ICET_OK;
 }

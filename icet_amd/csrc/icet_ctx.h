@@ -13,6 +13,28 @@
 #include <string>
 #include <vector>
 
+namespace icet {
+// A READ FENCE: a pinned staging that the host writes and a copy or kernel on the stream reads when it RUNS.  The owner calls wait() before the host writes the
+// staging again and mark(stream) behind whatever it enqueued to read it; destroy() goes with the owner.  The codes are the runtime's: an owner wraps them in its
+// own check macro.  (The descriptor staging, staging_* below, is not one of these: it has a second reader, the replayed graph, and rules under capture.)
+struct ReadFence {
+    hipEvent_t ev = nullptr; bool pending = false;                // pending: a reader was marked and not waited for since
+    hipError_t wait() {
+        if (!pending) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(ev);
+        if (e == hipSuccess) pending = false;
+        return e;
+    }
+    hipError_t mark(hipStream_t stream) {
+        hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ev, stream);
+        if (e == hipSuccess) pending = true;
+        return e;
+    }
+    void destroy() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; pending = false; }
+};
+}  // namespace icet
+
 struct icet_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -41,7 +63,7 @@ struct icet_ctx {
     float* h_x0 = nullptr;                                       // pinned, 6 x cap_out_pairs
     icet_score* d_score = nullptr; icet_score* h_score = nullptr; int32_t cap_score = 0;     // scores of the host-pointer entry points (device + pinned)
     int32_t* d_sel = nullptr; int32_t* h_sel = nullptr; int64_t cap_sel = 0;                // icet_select_best_device: the groups' members | offsets (device + pinned staging)
-    hipEvent_t ev_sel = nullptr; bool sel_in_flight = false;                                 // the copy out of h_sel
+    icet::ReadFence sel_read;                                                                // the copy out of h_sel
     float* d_sph1 = nullptr; int32_t* d_idx1 = nullptr; size_t cap_side1 = 0;      // points1Spherical / pointIndices1 on request (icet_sidetables.hip)
     float* d_sph2 = nullptr; int32_t* d_vox2 = nullptr; size_t cap_side2 = 0;      // points2Spherical / the rows' voxels on request
     // host-pointer entry points: scan 2 is uploaded on a stream of its own, beside the keyframe build of scan 1
@@ -109,10 +131,10 @@ struct icet_keyframe_store {
     int64_t id = 0, gen = 0;
     std::string err;
     // the pose table: ONE allocation of capacity x 56 bytes at pose_stamp -- stamp[capacity] | tx | ty | tz | r0 .. r8 --, 0xFF bytes
-    // (NaN, stamp -1) where a slot has no pose; set_pose stages through h_pose (pinned), which its kernel reads when it runs (ev_pose: it has)
+    // (NaN, stamp -1) where a slot has no pose; set_pose stages through h_pose (pinned), which its kernel reads when it runs (pose_read: it has)
     int64_t* pose_stamp = nullptr;
     icet::PoseTable pose_table() const { return icet::PoseTable{pose_stamp, reinterpret_cast<float*>(pose_stamp + capacity), capacity}; }
-    icet::PoseUpload* h_pose = nullptr; int32_t cap_h_pose = 0; hipEvent_t ev_pose = nullptr; bool pose_in_flight = false;
+    icet::PoseUpload* h_pose = nullptr; int32_t cap_h_pose = 0; icet::ReadFence pose_read;
     // buffers of a query (icet_keyframe_store_close_device), grown on demand: the search's per-tile lists; per (query, candidate); per registration; per query
     unsigned long long* q_part = nullptr; size_t cap_part = 0;
     unsigned long long* q_keys = nullptr; int32_t* q_cand = nullptr; int32_t cap_qk = 0;
@@ -209,14 +231,15 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            _score_device, _set_pose, _set_stamp, _candidates[_appearance]_device, _describe_device, _coarse_grid_device, _coarse_align_device,
 //                            _close[_appearance|_coarse]_device; icet_keyframe_store_save, _load (drain as well); icet_pose_graph_optimize[_device],
 //                            icet_debug_pose_graph_step, _direct, icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals (pg_run: drains as well);
-//                            icet_voxel_map_create, _clear, _add_device, _add_posed_device; _stats, _extract_device, _extract (drain as well; icet_map.hip)
+//                            icet_voxel_map_create, _clear, _add_device, _add_posed_device; _stats, _extract_device, _extract (drain as well; icet_map.hip);
+//                            icet_voxel_map_index, _query_device, _query_posed_device (drain only when the index is stale and they rebuild it)
 //   arms or disarms itself   icet_solve_batch_device
 //   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_block_tridiag (copy in, one kernel, copy out,
 //                            synchronise); icet_debug_fetch, icet_keyframe_store_debug_fetch, icet_keep_stats (synchronise, then blocking copies);
 //                            icet_last_timing[_iters] (synchronise); icet_solve_end; icet_keyframe_store_reserve, _enable_appearance, _enable_coarse, _destroy;
-//                            icet_destroy; icet_sync (the only one that re-arms: armed_calls = 0; icet_solve_indexed and its kin do the same behind their own drain)
+//                            icet_voxel_map_destroy; icet_destroy; icet_sync (the only one that re-arms: armed_calls = 0; icet_solve_indexed and its kin do the same behind their own drain)
 //   enqueues nothing         icet_reserve (allocations and blocking memsets; a growth synchronises first), icet_solve_keyframe_tables (waits for an event),
-//                            icet_set_option, icet_last_error, icet_stream, icet_device, icet_create (armed_calls starts at 2), icet_keyframe_store_last_error
+//                            icet_set_option, icet_last_error, icet_stream, icet_device, icet_create (armed_calls starts at 2), icet_keyframe_store_last_error, icet_voxel_map_last_error
 // (*) the one entry the audit found enqueuing (two memsets of the new tables) without draining or disarming.
 static inline icet_status use_device(icet_ctx* c) {
     if (!c) return ICET_ERR_BAD_ARG;

@@ -13,6 +13,8 @@
 //                         and popcounts): one int32 per (query, chunk).  A query whose run of x cells misses the chunk's is not tested (option "map_query_prune")
 //     k_map_query_scan    one block per query: exclusive offsets of its chunks, and d_rows / d_total / d_status
 //     k_map_query_write   the test again; a kept cell's rank is chunk offset + wave prefix + lane prefix, so the rows keep the index order, which is key order
+// The host side shares two pieces: CallStage, a call's records and poses (pinned, then on the device, behind a read fence), for an add's scan descriptors and a query's
+// sub-map descriptors; and map_sorted_cells (size query, growth, select, sort), which the extract and the index each run over a SortedCells of their own.
 // Sums of integers only: no float atomic, no block waits for another block, no fence inside a kernel, and the contents do not depend on the launch shape.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -266,6 +268,15 @@ __device__ __forceinline__ void query_load(const MapIndex& ix, long long first, 
         for (int a = 0; a < 3; a++) c.m[j][a] = in ? ix.xyz[a * ix.ld + i] : 0.f;
     }
 }
+// What the count and the write begin with: the run of x cells the block's chunk spans, the call's queries into LDS, the lane's cells into registers.  Returns the
+// lane's first cell.  The grid is the chunks of the index, so the chunk's first cell is < ix.n.
+__device__ __forceinline__ long long query_begin(QueryLds& s, QueryCells& c, const MapIndex& ix, const float* __restrict__ poses, int n_q, const qrule::Consts& kc, int prune, int32_t& x_first, int32_t& x_last) {
+    const long long chunk0 = (long long)blockIdx.x * kQueryChunk, first = chunk0 + (threadIdx.x >> 6) * kQueryPerWave + (threadIdx.x & 63);
+    x_first = qrule::key_x(ix.key[chunk0]); x_last = qrule::key_x(ix.key[min(chunk0 + kQueryChunk, ix.n) - 1]);
+    query_setup(s, poses, n_q, kc, prune != 0);
+    query_load(ix, first, c);
+    return first;
+}
 // Kept cells of this wave per query of the call, into s.wcnt.  A query whose run of x cells misses the chunk's keeps none of its cells and is not tested.
 __device__ __forceinline__ void query_count(QueryLds& s, const QueryCells& c, int n_q, const qrule::Consts& kc, int32_t x_first, int32_t x_last) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -286,11 +297,8 @@ __device__ __forceinline__ void query_count(QueryLds& s, const QueryCells& c, in
 __global__ __launch_bounds__(kQueryBlock) void k_map_query_count(MapIndex ix, const float* __restrict__ poses, int n_q, qrule::Consts kc, int prune,
                                                                  int32_t* __restrict__ counts, long long n_chunks) {
     __shared__ QueryLds s;
-    const long long chunk0 = (long long)blockIdx.x * kQueryChunk;     // < ix.n: the grid is the chunks of the index
-    const int32_t x_first = qrule::key_x(ix.key[chunk0]), x_last = qrule::key_x(ix.key[min(chunk0 + kQueryChunk, ix.n) - 1]);
-    query_setup(s, poses, n_q, kc, prune != 0);
-    QueryCells c;
-    query_load(ix, chunk0 + (threadIdx.x >> 6) * kQueryPerWave + (threadIdx.x & 63), c);
+    QueryCells c; int32_t x_first, x_last;
+    query_begin(s, c, ix, poses, n_q, kc, prune, x_first, x_last);
     __syncthreads();
     query_count(s, c, n_q, kc, x_first, x_last);
     __syncthreads();
@@ -338,17 +346,13 @@ __global__ __launch_bounds__(kQueryBlock) void k_map_query_write(MapIndex ix, co
                                                                  const int32_t* __restrict__ counts, const int32_t* __restrict__ offs, long long n_chunks,
                                                                  const MapSubmap* __restrict__ outs) {
     __shared__ QueryLds s;
-    const long long chunk0 = (long long)blockIdx.x * kQueryChunk;
-    const int32_t x_first = qrule::key_x(ix.key[chunk0]), x_last = qrule::key_x(ix.key[min(chunk0 + kQueryChunk, ix.n) - 1]);
+    QueryCells c; int32_t x_first, x_last;
+    const long long first = query_begin(s, c, ix, poses, n_q, kc, prune, x_first, x_last);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long first = chunk0 + wave * kQueryPerWave + lane;
-    query_setup(s, poses, n_q, kc, prune != 0);
     for (int q = threadIdx.x; q < n_q; q += kQueryBlock) {            // (the thread that staged query q) no row of q comes from this chunk: as if pruned
         const long long at = (long long)q * n_chunks + blockIdx.x;
         if (counts[at] == 0 || offs[at] >= outs[q].cap_rows) { s.lo[q] = rule::kCellLimit; s.hi[q] = -rule::kCellLimit; }
     }
-    QueryCells c;
-    query_load(ix, first, c);
     __syncthreads();
     query_count(s, c, n_q, kc, x_first, x_last);
     __syncthreads();
@@ -377,8 +381,44 @@ __global__ __launch_bounds__(kQueryBlock) void k_map_query_write(MapIndex ix, co
 
 using namespace icet;
 
-// A voxel map: the table, the device record of its totals and the pinned copy a stats call reads, the staging of a call's descriptors and poses, the buffers of
-// an extract.  Every array belongs to a group; the struct is a heap object that never moves.
+// THE STAGE OF A CALL: n records of Rec and n poses of 16 floats, each pinned and then copied to the device.  The host writes the pinned side only behind the
+// fence, which the call marks behind its last kernel; a call that reads poses the caller left on the device stages the records alone.
+template <class Rec> struct CallStage {
+    Rec* h_rec = nullptr; Rec* d_rec = nullptr; float* h_pose = nullptr; float* d_pose = nullptr; int32_t cap = 0;
+    ReadFence fence; BufferGroup mem;
+    ~CallStage() { fence.destroy(); }
+    // A call of n begins: the previous call has read the staging; n above the capacity drains the stream (its kernels may still read the device side) and grows.
+    hipError_t begin(int32_t n, hipStream_t st) {
+        hipError_t e = fence.wait();
+        if (e == hipSuccess && n > cap) e = hipStreamSynchronize(st);
+        if (e != hipSuccess || n <= cap) return e;
+        return static_cast<hipError_t>(grow(mem, cap, n, [&] {
+            int a = mem.pinned(h_rec, (size_t)n);
+            if (!a) a = mem.device(d_rec, (size_t)n);
+            if (!a) a = mem.pinned(h_pose, 16 * (size_t)n);
+            if (!a) a = mem.device(d_pose, 16 * (size_t)n);
+            return a;
+        }));
+    }
+    // h_rec[0 .. n) is written: the records to the device, and host poses with them.  *dp: the poses as the kernels read them.
+    hipError_t upload(int32_t n, const float* poses, bool poses_on_device, hipStream_t st, const float** dp) {
+        *dp = poses_on_device ? poses : d_pose;
+        const hipError_t e = hipMemcpyAsync(d_rec, h_rec, sizeof(Rec) * (size_t)n, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess || poses_on_device) return e;
+        std::memcpy(h_pose, poses, sizeof(float) * 16 * (size_t)n);
+        return hipMemcpyAsync(d_pose, h_pose, sizeof(float) * 16 * (size_t)n, hipMemcpyHostToDevice, st);
+    }
+    hipError_t mark_read(hipStream_t st) { return fence.mark(st); }      // behind the call's last kernel
+};
+
+// THE CELLS SORTED BY KEY (map_sorted_cells): the selected (key, entry) pairs, their sorted copy, rocPRIM's scratch and what it holds.  cap: pairs.
+struct SortedCells {
+    u64* sel_key = nullptr; u64* key = nullptr; uint32_t* sel_idx = nullptr; uint32_t* idx = nullptr; void* tmp = nullptr; size_t tmp_bytes = 0; int64_t cap = 0;
+    BufferGroup mem;
+};
+
+// A voxel map: the table, the device record of its totals and the pinned copy a stats call reads, the stages of an add and of a query, the sorted cells of an
+// extract and of the index.  Every array belongs to a group; the struct is a heap object that never moves.
 struct icet_voxel_map {
     icet_ctx* ctx = nullptr;
     icet_voxel_map_params params{};
@@ -386,22 +426,16 @@ struct icet_voxel_map {
     std::string err;
     MapTable t{};
     u64* ctr = nullptr; u64* h_rec = nullptr;                         // kCtrWords each: device, pinned
-    // a call's descriptors and host poses: pinned, then copied to the device; the host writes the pinned side only behind ev_stage
-    MapScan* h_scan = nullptr; MapScan* d_scan = nullptr; float* h_pose = nullptr; float* d_pose = nullptr; int32_t cap_scans = 0;
-    hipEvent_t ev_stage = nullptr; bool stage_in_flight = false;
-    // an extract: the selected (key, entry) pairs, their sorted copy, rocPRIM's scratch; the rows of the host form
-    u64* sel_key = nullptr; u64* sorted_key = nullptr; uint32_t* sel_idx = nullptr; uint32_t* sorted_idx = nullptr; void* sort_tmp = nullptr; int64_t cap_sel = 0;
+    CallStage<MapScan> add;                                           // an add or remove: the scans' descriptors and poses
+    CallStage<MapSubmap> query;                                       // a query: the output descriptors and poses
+    SortedCells x_cells;                                              // an extract: its sorted cells; the rows of the host form
     float* x_xyz = nullptr; long long* x_count = nullptr; u64* x_key = nullptr; int64_t cap_x = 0;
-    // the index of the queries: the cells of count >= 1 by key (key, count, three columns of cap_ix centroid floats), its own select and sort buffers; what the
-    // build saw; stale after every add, remove and clear
-    u64* ix_key = nullptr; long long* ix_count = nullptr; float* ix_xyz = nullptr; u64* ix_sel_key = nullptr; uint32_t* ix_sel_idx = nullptr;
-    uint32_t* ix_sorted_idx = nullptr; void* ix_tmp = nullptr; size_t ix_tmp_bytes = 0; int64_t cap_ix = 0, ix_n = 0;
+    // the index of the queries: the cells of count >= 1 by key -- the key is ix_cells.key, beside it count and three columns of cap_ix centroid floats --; what
+    // the build saw; stale after every add, remove and clear
+    SortedCells ix_cells; long long* ix_count = nullptr; float* ix_xyz = nullptr; int64_t cap_ix = 0, ix_n = 0;
     struct icet_voxel_map_stats ix_stats{}; bool ix_stale = true;
-    // a query call: its host poses and output descriptors (staged like an add's), and its per-(query, chunk) counts and offsets
-    float* h_qpose = nullptr; float* d_qpose = nullptr; MapSubmap* h_qout = nullptr; MapSubmap* d_qout = nullptr; int32_t cap_q = 0;
-    hipEvent_t ev_qstage = nullptr; bool qstage_in_flight = false;
-    int32_t* q_counts = nullptr; int32_t* q_offs = nullptr; int64_t cap_qc = 0;
-    BufferGroup table, record, stage, sel, xout, index, qstage, qcounts;
+    int32_t* q_counts = nullptr; int32_t* q_offs = nullptr; int64_t cap_qc = 0;      // a query call's per-(query, chunk) counts and offsets
+    BufferGroup table, record, xout, index, qcounts;
 };
 
 #define MAPCHK(m, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
@@ -415,6 +449,8 @@ static icet_status enter(icet_voxel_map* m) {
     return st;
 }
 static icet_status map_refuse(icet_voxel_map* m, const std::string& why) { m->err = why; return ICET_ERR_BAD_ARG; }
+template <class T> static bool elem_aligned(const T* p) { return reinterpret_cast<uintptr_t>(p) % sizeof(T) == 0; }      // (a null pointer is)
+static unsigned table_grid(const MapTable& t) { return (unsigned)((((size_t)1 << t.log2) + kCellSpan - 1) / kCellSpan); }  // a pass over the table: k_map_cells
 
 static icet_status map_clear(icet_voxel_map* m) {
     const size_t size = (size_t)1 << m->t.log2;
@@ -432,7 +468,7 @@ static icet_status map_count(icet_voxel_map* m, int32_t min_points, struct icet_
     hipStream_t st = m->ctx->stream;
     const long long minp = std::max(1, min_points);
     MAPCHK(m, hipMemsetAsync(m->ctr + kCtrOccupied, 0, sizeof(u64) * 4, st));      // occupied, out, negative, selected
-    k_map_cells<false><<<(unsigned)((((size_t)1 << m->t.log2) + kCellSpan - 1) / kCellSpan), kCellBlock, 0, st>>>(m->t, minp, m->ctr, nullptr, nullptr, 0);
+    k_map_cells<false><<<table_grid(m->t), kCellBlock, 0, st>>>(m->t, minp, m->ctr, nullptr, nullptr, 0);
     MAPCHK(m, hipGetLastError());
     MAPCHK(m, hipMemcpyAsync(m->h_rec, m->ctr, sizeof(u64) * kCtrWords, hipMemcpyDeviceToHost, st));
     MAPCHK(m, hipStreamSynchronize(st));
@@ -452,45 +488,58 @@ static icet_status map_add(icet_voxel_map* m, int32_t n, const icet_dev_scan* sc
     // everything is checked before anything is touched
     if (n < 0 || (n > 0 && (!scans || !poses))) return map_refuse(m, std::string(call) + ": bad argument");
     if (!rule::sign_ok(sign)) return map_refuse(m, std::string(call) + ": sign must be +1 (add) or -1 (remove)");
-    if (poses_on_device && (reinterpret_cast<uintptr_t>(poses) & 3)) return map_refuse(m, std::string(call) + ": d_poses is not aligned to 4 bytes");
+    if (poses_on_device && !elem_aligned(poses)) return map_refuse(m, std::string(call) + ": d_poses is not aligned to 4 bytes");
     int64_t blocks = 0;
     for (int k = 0; k < n; k++) {
-        if (!dev_scan_ok(scans[k]) || (reinterpret_cast<uintptr_t>(scans[k].ptr) & 3)) return map_refuse(m, std::string(call) + ": bad scan descriptor (scans[" + std::to_string(k) + "])");
+        if (!dev_scan_ok(scans[k]) || !elem_aligned(scans[k].ptr)) return map_refuse(m, std::string(call) + ": bad scan descriptor (scans[" + std::to_string(k) + "])");
         blocks += (scans[k].n + kRowsPerBlock - 1) / kRowsPerBlock;
     }
     if (blocks > 0x7FFFFFFF) return map_refuse(m, std::string(call) + ": too many rows in one call");
     if (blocks == 0) return ICET_OK;                                  // nothing to read
     icet_ctx* c = m->ctx;
     m->ix_stale = true;                                               // (from here on the table may change)
-    if (m->stage_in_flight) { MAPCHK(m, hipEventSynchronize(m->ev_stage)); m->stage_in_flight = false; }      // the previous call has read the staging
-    if (n > m->cap_scans) {
-        MAPCHK(m, hipStreamSynchronize(c->stream));              // (its kernel may still read the device side)
-        BufferGroup& g = m->stage;
-        MAPCHK(m, grow(g, m->cap_scans, n, [&] {
-            int e = g.pinned(m->h_scan, (size_t)n);
-            if (!e) e = g.device(m->d_scan, (size_t)n);
-            if (!e) e = g.pinned(m->h_pose, 16 * (size_t)n);
-            if (!e) e = g.device(m->d_pose, 16 * (size_t)n);
-            return e;
-        }));
-    }
-    if (!m->ev_stage) MAPCHK(m, hipEventCreateWithFlags(&m->ev_stage, hipEventDisableTiming));
+    CallStage<MapScan>& s = m->add;
+    MAPCHK(m, s.begin(n, c->stream));
     int32_t b0 = 0;
     for (int k = 0; k < n; k++) {
-        m->h_scan[k] = MapScan{scans[k].ptr, (int32_t)scans[k].n, (int32_t)scans[k].ld, b0, 0};
+        s.h_rec[k] = MapScan{scans[k].ptr, (int32_t)scans[k].n, (int32_t)scans[k].ld, b0, 0};
         b0 += (int32_t)((scans[k].n + kRowsPerBlock - 1) / kRowsPerBlock);
     }
-    MAPCHK(m, hipMemcpyAsync(m->d_scan, m->h_scan, sizeof(MapScan) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (!poses_on_device) {
-        std::memcpy(m->h_pose, poses, sizeof(float) * 16 * (size_t)n);
-        MAPCHK(m, hipMemcpyAsync(m->d_pose, m->h_pose, sizeof(float) * 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    }
-    const float* dp = poses_on_device ? poses : m->d_pose;
+    const float* dp = nullptr;
+    MAPCHK(m, s.upload(n, poses, poses_on_device, c->stream, &dp));
     const u64 sg = sign > 0 ? (u64)1 : ~(u64)0;                       // -1 in two's complement
-    if (c->map_lds) k_map_add<true><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(m->d_scan, n, dp, m->k, m->t, sg, m->ctr);
-    else k_map_add<false><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(m->d_scan, n, dp, m->k, m->t, sg, m->ctr);
+    if (c->map_lds) k_map_add<true><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, m->t, sg, m->ctr);
+    else k_map_add<false><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, m->t, sg, m->ctr);
     MAPCHK(m, hipGetLastError());
-    MAPCHK(m, hipEventRecord(m->ev_stage, c->stream)); m->stage_in_flight = true;
+    MAPCHK(m, s.mark_read(c->stream));
+    return ICET_OK;
+}
+
+// The cells of count >= minp, sorted by key, into sc.key / sc.idx.  n > 0 is the cells_out that map_count just returned for minp: it drained the stream, so nothing
+// reads the old buffers when they grow.  They grow to n + headroom pairs (a map that grows scan by scan does not allocate at every call), and also when this
+// sort asks for more scratch than they hold: the scratch is what rocPRIM asks for at the capacity, and a smaller sort is not promised to ask less.
+static icet_status map_sorted_cells(icet_voxel_map* m, SortedCells& sc, int64_t n, long long minp, int64_t headroom) {
+    hipStream_t st = m->ctx->stream;
+    size_t tmp_bytes = 0;
+    MAPCHK(m, rocprim::radix_sort_pairs(nullptr, tmp_bytes, sc.sel_key, sc.key, sc.sel_idx, sc.idx, (size_t)n, 0, 63, st));
+    if (n > sc.cap || tmp_bytes > sc.tmp_bytes) {
+        const int64_t need = std::max(n + headroom, sc.cap);
+        size_t need_tmp = 0;
+        MAPCHK(m, rocprim::radix_sort_pairs(nullptr, need_tmp, sc.sel_key, sc.key, sc.sel_idx, sc.idx, (size_t)need, 0, 63, st));
+        need_tmp = std::max(std::max(need_tmp, tmp_bytes), (size_t)16);
+        MAPCHK(m, grow(sc.mem, sc.cap, need, [&] {
+            int e = sc.mem.device(sc.sel_key, (size_t)need);
+            if (!e) e = sc.mem.device(sc.key, (size_t)need);
+            if (!e) e = sc.mem.device(sc.sel_idx, (size_t)need);
+            if (!e) e = sc.mem.device(sc.idx, (size_t)need);
+            if (!e) e = sc.mem.device_bytes(sc.tmp, need_tmp);
+            return e;
+        }));
+        sc.tmp_bytes = need_tmp;
+    }
+    k_map_cells<true><<<table_grid(m->t), kCellBlock, 0, st>>>(m->t, minp, m->ctr, sc.sel_key, sc.sel_idx, (u64)n);
+    MAPCHK(m, hipGetLastError());
+    MAPCHK(m, rocprim::radix_sort_pairs(sc.tmp, tmp_bytes, sc.sel_key, sc.key, sc.sel_idx, sc.idx, (size_t)n, 0, 63, st));
     return ICET_OK;
 }
 
@@ -498,7 +547,7 @@ static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_ho
                                struct icet_voxel_map_stats* out, const char* call) {
     ICET_TRY(enter(m));
     if (cap_rows < 0 || ld < cap_rows || (cap_rows > 0 && !xyz)) return map_refuse(m, std::string(call) + ": bad argument (cap_rows >= 0, ld >= cap_rows, a buffer of rows)");
-    if (!to_host && ((reinterpret_cast<uintptr_t>(xyz) & 3) || (reinterpret_cast<uintptr_t>(count) & 7) || (reinterpret_cast<uintptr_t>(key) & 7)))
+    if (!to_host && !(elem_aligned(xyz) && elem_aligned(count) && elem_aligned(key)))
         return map_refuse(m, std::string(call) + ": a device pointer is not aligned to its element");
     hipStream_t st = m->ctx->stream;
     struct icet_voxel_map_stats s;
@@ -506,21 +555,7 @@ static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_ho
     const int64_t n_out = s.cells_out, rows = std::min(n_out, cap_rows);
     if (n_out > cap_rows) s.status |= ICET_VOXEL_MAP_TRUNCATED;
     if (rows > 0) {
-        size_t tmp_bytes = 0;
-        MAPCHK(m, rocprim::radix_sort_pairs(nullptr, tmp_bytes, m->sel_key, m->sorted_key, m->sel_idx, m->sorted_idx, (size_t)n_out, 0, 63, st));
-        if (n_out > m->cap_sel) {                                     // (the count above drained the stream: nothing reads the old buffers)
-            BufferGroup& g = m->sel;
-            // rocPRIM's scratch grows with the size: what this size asks for, and the group grows as one
-            MAPCHK(m, grow(g, m->cap_sel, n_out, [&] {
-                int e = g.device(m->sel_key, (size_t)n_out);
-                if (!e) e = g.device(m->sorted_key, (size_t)n_out);
-                if (!e) e = g.device(m->sel_idx, (size_t)n_out);
-                if (!e) e = g.device(m->sorted_idx, (size_t)n_out);
-                if (!e) e = g.device_bytes(m->sort_tmp, std::max(tmp_bytes, (size_t)16));
-                return e;
-            }));
-        }
-        if (to_host && rows > m->cap_x) {
+        if (to_host && rows > m->cap_x) {                             // (the count above drained the stream: nothing reads the old buffers)
             BufferGroup& g = m->xout;
             MAPCHK(m, grow(g, m->cap_x, rows, [&] {
                 int e = g.device(m->x_xyz, 3 * (size_t)rows);
@@ -529,15 +564,12 @@ static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_ho
                 return e;
             }));
         }
-        const long long minp = std::max(1, min_points);
-        k_map_cells<true><<<(unsigned)((((size_t)1 << m->t.log2) + kCellSpan - 1) / kCellSpan), kCellBlock, 0, st>>>(m->t, minp, m->ctr, m->sel_key, m->sel_idx, (u64)n_out);
-        MAPCHK(m, hipGetLastError());
-        MAPCHK(m, rocprim::radix_sort_pairs(m->sort_tmp, tmp_bytes, m->sel_key, m->sorted_key, m->sel_idx, m->sorted_idx, (size_t)n_out, 0, 63, st));
+        ICET_TRY(map_sorted_cells(m, m->x_cells, n_out, std::max(1, min_points), 0));
         float* dx = to_host ? m->x_xyz : xyz;
         long long* dc = to_host ? (count ? m->x_count : nullptr) : reinterpret_cast<long long*>(count);
         u64* dk = to_host ? (key ? m->x_key : nullptr) : reinterpret_cast<u64*>(key);
         const long long dld = to_host ? rows : ld;
-        k_map_centroid<<<(unsigned)((rows + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->t, m->k, m->sorted_key, m->sorted_idx, rows, dx, dld, dc, dk);
+        k_map_centroid<<<(unsigned)((rows + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->t, m->k, m->x_cells.key, m->x_cells.idx, rows, dx, dld, dc, dk);
         MAPCHK(m, hipGetLastError());
         if (to_host) {
             MAPCHK(m, hipMemcpy2DAsync(xyz, sizeof(float) * (size_t)ld, dx, sizeof(float) * (size_t)rows, sizeof(float) * (size_t)rows, 3, hipMemcpyDeviceToHost, st));
@@ -560,30 +592,13 @@ static icet_status map_index(icet_voxel_map* m) {
     const int64_t n = s.cells_out;
     m->ix_n = 0;
     if (n > 0) {
-        size_t tmp_bytes = 0;
-        MAPCHK(m, rocprim::radix_sort_pairs(nullptr, tmp_bytes, m->ix_sel_key, m->ix_key, m->ix_sel_idx, m->ix_sorted_idx, (size_t)n, 0, 63, st));
-        if (n > m->cap_ix || tmp_bytes > m->ix_tmp_bytes) {           // (the scratch is what rocPRIM asked for at the capacity: a smaller sort is not promised to ask less)
+        if (n > m->cap_ix) {                                          // (the headroom of the sorted cells below; each capacity guards its own arrays)
             BufferGroup& g = m->index;
-            const int64_t need = std::max(n + n / 4, m->cap_ix);      // (a map that grows scan by scan does not allocate at every query)
-            size_t need_tmp = 0;
-            MAPCHK(m, rocprim::radix_sort_pairs(nullptr, need_tmp, m->ix_sel_key, m->ix_key, m->ix_sel_idx, m->ix_sorted_idx, (size_t)need, 0, 63, st));
-            need_tmp = std::max(std::max(need_tmp, tmp_bytes), (size_t)16);
-            MAPCHK(m, grow(g, m->cap_ix, need, [&] {
-                int e = g.device(m->ix_key, (size_t)need);
-                if (!e) e = g.device(m->ix_count, (size_t)need);
-                if (!e) e = g.device(m->ix_xyz, 3 * (size_t)need);
-                if (!e) e = g.device(m->ix_sel_key, (size_t)need);
-                if (!e) e = g.device(m->ix_sel_idx, (size_t)need);
-                if (!e) e = g.device(m->ix_sorted_idx, (size_t)need);
-                if (!e) e = g.device_bytes(m->ix_tmp, need_tmp);
-                return e;
-            }));
-            m->ix_tmp_bytes = need_tmp;
+            const int64_t need = n + n / 4;
+            MAPCHK(m, grow(g, m->cap_ix, need, [&] { const int e = g.device(m->ix_count, (size_t)need); return e ? e : g.device(m->ix_xyz, 3 * (size_t)need); }));
         }
-        k_map_cells<true><<<(unsigned)((((size_t)1 << m->t.log2) + kCellSpan - 1) / kCellSpan), kCellBlock, 0, st>>>(m->t, 1, m->ctr, m->ix_sel_key, m->ix_sel_idx, (u64)n);
-        MAPCHK(m, hipGetLastError());
-        MAPCHK(m, rocprim::radix_sort_pairs(m->ix_tmp, tmp_bytes, m->ix_sel_key, m->ix_key, m->ix_sel_idx, m->ix_sorted_idx, (size_t)n, 0, 63, st));
-        k_map_centroid<<<(unsigned)((n + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->t, m->k, m->ix_key, m->ix_sorted_idx, n, m->ix_xyz, m->cap_ix, m->ix_count, nullptr);
+        ICET_TRY(map_sorted_cells(m, m->ix_cells, n, 1, n / 4));
+        k_map_centroid<<<(unsigned)((n + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->t, m->k, m->ix_cells.key, m->ix_cells.idx, n, m->ix_xyz, m->cap_ix, m->ix_count, nullptr);
         MAPCHK(m, hipGetLastError());
     }
     m->ix_n = n; m->ix_stats = s; m->ix_stale = false;
@@ -598,13 +613,13 @@ static icet_status map_query(icet_voxel_map* m, int32_t n_q, const float* poses,
     if (n_q < 1 || n_q > qrule::kMaxQueries) return map_refuse(m, who + ": n_q must lie in 1 .. 256");
     if (!poses || !q || !outs || !d_rows) return map_refuse(m, who + ": bad argument (a NULL array)");
     if (!qrule::params_ok(q->min_range, q->max_range, q->flags, q->reserved)) return map_refuse(m, who + ": the ranges must be finite, the flags known and the reserved words 0");
-    if ((poses_on_device && (reinterpret_cast<uintptr_t>(poses) & 3)) || ((reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_total) | reinterpret_cast<uintptr_t>(d_status)) & 3))
+    if ((poses_on_device && !elem_aligned(poses)) || !(elem_aligned(d_rows) && elem_aligned(d_total) && elem_aligned(d_status)))
         return map_refuse(m, who + ": a device pointer is not aligned to its element");
     bool any_rows = false;
     for (int k = 0; k < n_q; k++) {
         const icet_voxel_map_submap& o = outs[k];
         if (!qrule::submap_ok(o.xyz, o.ld, o.cap_rows)) return map_refuse(m, who + ": bad sub-map (outs[" + std::to_string(k) + "]: cap_rows >= 0, ld >= cap_rows, a buffer of rows)");
-        if ((reinterpret_cast<uintptr_t>(o.xyz) & 3) || (reinterpret_cast<uintptr_t>(o.count) & 7) || (reinterpret_cast<uintptr_t>(o.key) & 7))
+        if (!(elem_aligned(o.xyz) && elem_aligned(o.count) && elem_aligned(o.key)))
             return map_refuse(m, who + ": a device pointer is not aligned to its element (outs[" + std::to_string(k) + "])");
         any_rows = any_rows || o.cap_rows > 0;
     }
@@ -612,18 +627,8 @@ static icet_status map_query(icet_voxel_map* m, int32_t n_q, const float* poses,
     hipStream_t st = c->stream;
     ICET_TRY(map_index(m));
     const long long n_chunks = (m->ix_n + kQueryChunk - 1) / kQueryChunk;
-    if (m->qstage_in_flight) { MAPCHK(m, hipEventSynchronize(m->ev_qstage)); m->qstage_in_flight = false; }      // the previous call has read the staging
-    if (n_q > m->cap_q) {
-        MAPCHK(m, hipStreamSynchronize(st));                         // (its kernels may still read the device side)
-        BufferGroup& g = m->qstage;
-        MAPCHK(m, grow(g, m->cap_q, n_q, [&] {
-            int e = g.pinned(m->h_qpose, 16 * (size_t)n_q);
-            if (!e) e = g.device(m->d_qpose, 16 * (size_t)n_q);
-            if (!e) e = g.pinned(m->h_qout, (size_t)n_q);
-            if (!e) e = g.device(m->d_qout, (size_t)n_q);
-            return e;
-        }));
-    }
+    CallStage<MapSubmap>& s = m->query;
+    MAPCHK(m, s.begin(n_q, st));
     const int64_t words = (int64_t)n_q * n_chunks;
     if (words > m->cap_qc) {
         MAPCHK(m, hipStreamSynchronize(st));
@@ -634,28 +639,23 @@ static icet_status map_query(icet_voxel_map* m, int32_t n_q, const float* poses,
             return e;
         }));
     }
-    if (!m->ev_qstage) MAPCHK(m, hipEventCreateWithFlags(&m->ev_qstage, hipEventDisableTiming));
-    for (int k = 0; k < n_q; k++) m->h_qout[k] = MapSubmap{outs[k].xyz, outs[k].ld, outs[k].cap_rows, reinterpret_cast<long long*>(outs[k].count), reinterpret_cast<u64*>(outs[k].key)};
-    MAPCHK(m, hipMemcpyAsync(m->d_qout, m->h_qout, sizeof(MapSubmap) * (size_t)n_q, hipMemcpyHostToDevice, st));
-    if (!poses_on_device) {
-        std::memcpy(m->h_qpose, poses, sizeof(float) * 16 * (size_t)n_q);
-        MAPCHK(m, hipMemcpyAsync(m->d_qpose, m->h_qpose, sizeof(float) * 16 * (size_t)n_q, hipMemcpyHostToDevice, st));
-    }
-    const float* dp = poses_on_device ? poses : m->d_qpose;
+    for (int k = 0; k < n_q; k++) s.h_rec[k] = MapSubmap{outs[k].xyz, outs[k].ld, outs[k].cap_rows, reinterpret_cast<long long*>(outs[k].count), reinterpret_cast<u64*>(outs[k].key)};
+    const float* dp = nullptr;
+    MAPCHK(m, s.upload(n_q, poses, poses_on_device, st, &dp));
     const qrule::Consts kc = qrule::make_consts(m->params.cell, q->min_range, q->max_range, q->min_points, q->flags);
-    const MapIndex ix{m->ix_key, m->ix_count, m->ix_xyz, (long long)m->cap_ix, (long long)m->ix_n};
+    const MapIndex ix{m->ix_cells.key, m->ix_count, m->ix_xyz, (long long)m->cap_ix, (long long)m->ix_n};
     const int prune = c->map_query_prune;
     if (n_chunks > 0) {
         k_map_query_count<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, n_chunks);
         MAPCHK(m, hipGetLastError());
     }
-    k_map_query_scan<<<(unsigned)n_q, kQueryBlock, 0, st>>>(m->q_counts, m->q_offs, n_chunks, dp, m->d_qout, d_rows, d_total, d_status);
+    k_map_query_scan<<<(unsigned)n_q, kQueryBlock, 0, st>>>(m->q_counts, m->q_offs, n_chunks, dp, s.d_rec, d_rows, d_total, d_status);
     MAPCHK(m, hipGetLastError());
     if (n_chunks > 0 && any_rows) {                                   // (a count-only call writes no row)
-        k_map_query_write<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, m->q_offs, n_chunks, m->d_qout);
+        k_map_query_write<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, m->q_offs, n_chunks, s.d_rec);
         MAPCHK(m, hipGetLastError());
     }
-    MAPCHK(m, hipEventRecord(m->ev_qstage, st)); m->qstage_in_flight = true;
+    MAPCHK(m, s.mark_read(st));
     return ICET_OK;
 }
 
@@ -693,9 +693,7 @@ icet_status icet_voxel_map_destroy(icet_voxel_map* m) {
     if (!m) return ICET_ERR_BAD_ARG;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);              // (an add or an extract may still read or write the table)
-    if (m->ev_stage) (void)hipEventDestroy(m->ev_stage);
-    if (m->ev_qstage) (void)hipEventDestroy(m->ev_qstage);
-    delete m;                                                // (every array belongs to a group)
+    delete m;                                                // (every array belongs to a group, every event to a stage)
     return ICET_OK;
 }
 

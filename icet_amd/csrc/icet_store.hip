@@ -112,7 +112,7 @@ icet_status icet_keyframe_store_destroy(icet_keyframe_store* s) {
     if (!s) return ICET_ERR_BAD_ARG;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);              // (a put or a registration may still read or write the tables)
-    if (s->ev_pose) (void)hipEventDestroy(s->ev_pose);
+    s->pose_read.destroy();
     delete s->app;                                           // (every array belongs to a group of its struct)
     delete s->coarse;
     delete s;
@@ -299,9 +299,8 @@ icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, cons
     if (n == 0) return ICET_OK;
     const icet_status ok = slots_ok(s, n, slots, true, "set_pose");
     if (ok != ICET_OK) return ok;
-    if (s->pose_in_flight) { STORECHK(s, hipEventSynchronize(s->ev_pose)); s->pose_in_flight = false; }      // the previous set_pose's kernel has read the staging
+    STORECHK(s, s->pose_read.wait());                            // the previous set_pose's kernel has read the staging
     if (n > s->cap_h_pose) STORECHK(s, grow(s->pose_stage, s->cap_h_pose, n, [&] { return s->pose_stage.pinned(s->h_pose, (size_t)n); }));
-    if (!s->ev_pose) STORECHK(s, hipEventCreateWithFlags(&s->ev_pose, hipEventDisableTiming));
     for (int k = 0; k < n; k++) {
         PoseUpload& u = s->h_pose[k];
         const float* T = poses + 16 * (size_t)k;
@@ -309,7 +308,7 @@ icet_status icet_keyframe_store_set_pose(icet_keyframe_store* s, int32_t n, cons
         for (int a = 0; a < 3; a++) { u.tR[a] = T[4 * a + 3]; for (int b = 0; b < 3; b++) u.tR[3 + 3 * a + b] = T[4 * a + b]; }
     }
     STORECHK(s, launch_closure_set_pose(s->pose_table(), s->h_pose, n, c->stream));
-    STORECHK(s, hipEventRecord(s->ev_pose, c->stream)); s->pose_in_flight = true;
+    STORECHK(s, s->pose_read.mark(c->stream));
     return ICET_OK;
 }
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import map_model as mm
+import map_query_model as qm
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -180,6 +181,58 @@ def test_table_near_full_and_full(gpu_ctx):
             m.close()
     finally:
         gpu_ctx.set_option("map_lds", 1)
+
+
+# ---- 4b. the sorted cells of one map shrink and grow from extract to extract --------------------------------------------------------------------------------------
+def _extract_device(m, cap, min_points):
+    """extract_device into pre-filled buffers of `cap` rows (leading dimension cap + 5), as the dict of extract(); nothing beyond the rows is written."""
+    dx = torch.full((3, cap + 5), -1.0, dtype=torch.float32, device=DEV)
+    dc = torch.full((max(cap, 1),), -1, dtype=torch.int64, device=DEV); dk = torch.full((max(cap, 1),), -1, dtype=torch.int64, device=DEV)
+    torch.cuda.synchronize(DEV)
+    st = m.extract_device(dx.data_ptr(), cap + 5, cap, min_points, dc.data_ptr(), dk.data_ptr())
+    n = min(cap, st["cells_out"])
+    assert (dx[:, n:] == -1.0).all() and (dc[n:] == -1).all() and (dk[n:] == -1).all()
+    return dict(xyz=np.ascontiguousarray(dx[:, :n].cpu().numpy().T), count=dc[:n].cpu().numpy(), key=dk[:n].cpu().numpy().view(np.uint64), stats=st)
+
+
+def test_sorted_cells_of_changing_size_one_map(gpu_ctx):
+    """cells_out 3000, 17, 3000, 3500, 1, 0 on ONE map, extract and extract_device in turn: the select-and-sort buffers serve a smaller sort after a larger one and
+    grow again, and between the steps a world-frame query that takes every cell (the index's buffers) equals the extract."""
+    from icet_amd import api
+    first = _line(3000)
+    twice = first[np.arange(17) * 173 + 5] + np.float32(0.03)         # a second point in 17 of the cells ...
+    second = np.concatenate([twice, twice[3:4]])                      # ... and a third in one of them
+    more = _line(3500)[3000:]
+    T = mm.pose()[None]
+    far = mm.pose(t=(-1000.0, 0.0, 0.0))                              # every cell lies beyond min_range 0 of it
+    model = mm.Map(0.125)
+    m = api.VoxelMap(gpu_ctx, cell=0.125, table_log2=12)
+    keep, descs = _descs([first, second, more])
+
+    def step(what, min_points, cells, device):
+        want = model.extract(min_points)
+        assert want["key"].shape[0] == cells, what
+        got = _extract_device(m, cells, min_points) if device else m.extract(min_points)
+        _same(got, want, what)
+        assert m.stats(min_points) == want["stats"], what
+        q = m.query(far, min_points=min_points, world=True)[0]
+        w = qm.query_extract(model.extract(1), far, min_points=min_points, world=True)
+        assert (q["total"], q["status"]) == (w["total"], w["status"]) == (cells, 0), what
+        for g in (w, want):                                           # the model's query, and the extract itself
+            assert np.array_equal(q["key"], g["key"]) and np.array_equal(q["count"], g["count"]), what
+            assert np.array_equal(q["xyz"].view(np.uint32), g["xyz"].view(np.uint32)), what
+
+    m.add_device(descs[:1], T); model.add([first], T)
+    step("3000 cells", 1, 3000, False)
+    m.add_device(descs[1:2], T); model.add([second], T)
+    step("17 cells of two points", 2, 17, True)
+    step("3000 cells again", 1, 3000, False)
+    m.add_device(descs[2:], T); model.add([more], T)
+    step("3500 cells", 1, 3500, True)
+    step("1 cell of three points", 3, 1, False)
+    m.clear(); model.clear()
+    step("cleared", 1, 0, True)
+    m.close()
 
 
 # ---- 5, 6, 9. several lidar scans ------------------------------------------------------------------------------------------------------------------------------

@@ -248,6 +248,56 @@ def test_no_query_and_too_many_are_refused(gpu_ctx):
     m.close()
 
 
+# ---- 3b. the stages of an add and of a query grow while the previous call is still in flight -----------------------------------------------------------------------
+def test_add_stage_grows_while_the_previous_call_is_in_flight(gpu_ctx):
+    """Add calls of 1, 5, 2, 33 and 1 scans back to back, host poses and a pose tensor on the device in turn, one synchronisation at the end: the model of all 42."""
+    d = _cloud()
+    m = _cloud_map(gpu_ctx)
+    rs = np.random.RandomState(77)
+    scans = [(rs.randn(40 + 7 * k, 3) * [7, 7, 1.0]).astype(np.float32) for k in range(42)]
+    poses = _mixed_poses(42, seed=78, spread=2.0)
+    want = mm.Map(0.1).add(d["scans"], d["poses"]).add(scans, poses).extract()
+    keep, descs = _descs(scans)
+    calls, at = [], 0
+    for j, n in enumerate((1, 5, 2, 33, 1)):
+        T = poses[at:at + n]
+        calls.append((descs[at:at + n], torch.from_numpy(T.copy()).to(DEV) if j % 2 else T))
+        at += n
+    torch.cuda.synchronize(DEV)
+    for ds, T in calls:
+        m.add_device(ds, T)
+    gpu_ctx.sync()
+    got = m.extract()
+    assert got["stats"] == want["stats"] and got["stats"]["points_in"] == sum(s.shape[0] for s in scans + d["scans"])
+    assert np.array_equal(got["key"], want["key"]) and np.array_equal(got["count"], want["count"])
+    assert np.array_equal(got["xyz"].view(np.uint32), want["xyz"].view(np.uint32))
+    m.close()
+
+
+def test_query_stage_grows_while_the_previous_call_is_in_flight(gpu_ctx):
+    """Query calls of 1, 3, 2, 256 and 1 poses back to back, each into its own buffers, host poses and a pose tensor on the device in turn: every call is the model's."""
+    d = _cloud()
+    m = _cloud_map(gpu_ctx)
+    m.index()                                                         # current from here on: the calls below do not synchronise
+    n = d["ext"]["key"].shape[0]
+    kw = dict(min_range=0.3, max_range=6.0)
+    calls = []
+    for j, q in enumerate((1, 3, 2, 256, 1)):
+        T = _mixed_poses(q, seed=90 + j)
+        calls.append((T, torch.from_numpy(T.copy()).to(DEV) if j % 2 else T, Outs([n] * q)))
+    torch.cuda.synchronize(DEV)
+    for T, given, o in calls:
+        m.query_device(given, o.descs, **o.ptrs(), **kw)
+    gpu_ctx.sync()
+    rows = 0
+    for T, given, o in calls:
+        want = _want(d["ext"], T, [n] * T.shape[0], **kw)
+        rows += sum(w["total"] for w in want)
+        _same(o.fetch(), want, "%d poses" % T.shape[0])
+    assert rows > 100 * 263
+    m.close()
+
+
 # ---- 4. the drive ------------------------------------------------------------------------------------------------------------------------------------------------
 _DRIVE = {}
 
