@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_voxel_map_create", "icet_voxel_map_destroy", "icet_voxel_map_last_error", "icet_voxel_map_clear", "icet_voxel_map_add_device",
                     "icet_voxel_map_add_posed_device", "icet_voxel_map_stats", "icet_voxel_map_extract_device", "icet_voxel_map_extract",
                     "icet_voxel_map_index", "icet_voxel_map_query_device", "icet_voxel_map_query_posed_device",
+                    "icet_voxel_map_evidence_device", "icet_voxel_map_evidence_posed_device", "icet_voxel_map_evidence_fetch_device",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -107,6 +108,7 @@ class MapStats(C.Structure):
 VOXEL_MAP_OK, VOXEL_MAP_TABLE_FULL, VOXEL_MAP_NEGATIVE, VOXEL_MAP_TRUNCATED = 0, 1, 2, 4
 VOXEL_MAP_QUERY_BAD_POSE = 8      # status bit of a query
 VOXEL_MAP_QUERY_WORLD = 1         # flag of a query
+VOXEL_MAP_QUERY_STATIC = 2        # flag of a query: the cells the current evidence calls transient take no part
 VOXEL_MAP_MAX_QUERIES = 256
 MAP_QUERY_CHUNK = 2048            # ICET_VOXEL_MAP_QUERY_CHUNK: index entries per block of a query (the sizes at which its kernels take another path)
 
@@ -114,6 +116,21 @@ MAP_QUERY_CHUNK = 2048            # ICET_VOXEL_MAP_QUERY_CHUNK: index entries pe
 class MapQuery(C.Structure):
     """icet_voxel_map_query (include/icet_hip.h), 32 bytes."""
     _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("min_points", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class MapEvidence(C.Structure):
+    """icet_voxel_map_evidence (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("margin", C.c_float), ("image_log2", C.c_int32), ("window", C.c_int32), ("min_miss", C.c_int32),
+                ("agree_factor", C.c_int32), ("flags", C.c_int32)]
+
+
+class MapEvidenceStats(C.Structure):
+    """struct icet_voxel_map_evidence_stats (include/icet_hip.h), 32 bytes."""
+    _fields_ = [("rows_imaged", C.c_int64), ("cells", C.c_int32), ("cells_transient", C.c_int32), ("scans_used", C.c_int32), ("scans_bad_pose", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:5]}
 
 
 class MapSubmap(C.Structure):
@@ -498,6 +515,9 @@ def load_library():
     L.icet_voxel_map_index.argtypes = [C.c_void_p, C.POINTER(MapStats)]
     L.icet_voxel_map_query_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(MapQuery), C.POINTER(MapSubmap), C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_voxel_map_query_posed_device.argtypes = L.icet_voxel_map_query_device.argtypes
+    L.icet_voxel_map_evidence_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(MapEvidence), C.POINTER(MapEvidenceStats)]
+    L.icet_voxel_map_evidence_posed_device.argtypes = L.icet_voxel_map_evidence_device.argtypes
+    L.icet_voxel_map_evidence_fetch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.icet_keyframe_store_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p]
     L.icet_keyframe_store_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.icet_keyframe_store_snapshot_info.argtypes = [C.c_char_p, C.POINTER(SnapshotInfo)]
@@ -1336,11 +1356,12 @@ class KeyframeStore:
         self.put_device(slots, [(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs])
         self._ctx.sync()
 
-    def put_from_map(self, slots, vmap, poses, max_range, min_range=0.0, min_points=1, cap_rows=None, stamps=None):
+    def put_from_map(self, slots, vmap, poses, max_range, min_range=0.0, min_points=1, cap_rows=None, stamps=None, static=False):
         """Fill slots[k] with the sub-map of ``vmap`` (a VoxelMap on the same context) around poses[k], in that pose's frame: VoxelMap.query_device into buffers
         the store object keeps alive, then put_device with the query's d_rows -- the row counts never visit the host, and nothing synchronises between the two.
         cap_rows: the rows reserved per sub-map (None: the cells the map's index holds, which no sub-map exceeds; a smaller value truncates to the lowest
-        keys).  With ``stamps`` the slots also get ``poses`` and the stamps (set_pose).  Returns the device int32 tensors (rows, total, status)."""
+        keys).  With ``stamps`` the slots also get ``poses`` and the stamps (set_pose).  ``static``: without the cells the map's current evidence calls transient
+        (VoxelMap.evidence).  Returns the device int32 tensors (rows, total, status)."""
         import torch
         dev = torch.device("cuda", self._ctx.device)
         T = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
@@ -1352,7 +1373,7 @@ class KeyframeStore:
         torch.cuda.synchronize(dev)                                   # (the buffers are complete before the context's stream writes them)
         self._map_bufs = (xyz, words)                                 # alive until the next call: the put reads them in stream order
         vmap.query_device(T, [(xyz[j].data_ptr(), cap, cap) for j in range(k)], words[0].data_ptr(), min_range=min_range, max_range=max_range,
-                          min_points=min_points, d_total_ptr=words[1].data_ptr(), d_status_ptr=words[2].data_ptr())
+                          min_points=min_points, d_total_ptr=words[1].data_ptr(), d_status_ptr=words[2].data_ptr(), static=static)
         self.put_device(sl, [(xyz[j].data_ptr(), cap, cap) for j in range(k)], words[0].data_ptr())
         if stamps is not None:
             self.set_pose(sl, T, stamps)
@@ -1856,12 +1877,68 @@ class VoxelMap:
         self._check(load_library().icet_voxel_map_index(self._h, C.byref(s)))
         return s.as_dict()
 
-    def query_device(self, poses, outs, d_rows_ptr, min_range=0.0, max_range=0.0, min_points=1, world=False, d_total_ptr=None, d_status_ptr=None):
+    def evidence_device(self, descs, poses, max_range, margin=None, min_range=0.0, image_log2=8, window=1, min_miss=2, agree_factor=1, stats=True):
+        """The visibility evidence of the map's cells from the scans (device_ptr, n, ld) at ``poses`` (an n x 4 x 4 NumPy array: icet_voxel_map_evidence_device; a
+        float32 CUDA tensor: icet_voxel_map_evidence_posed_device): per cell of the index how many scans measured something further away through it (miss) and
+        how many measured it (agree), and the decision transient = miss >= max(1, min_miss) and miss > agree_factor * agree.  margin None: three cells.  The map
+        keeps the evidence (evidence_fetch, ``static=True`` of the queries) until the next add, remove or clear.  Returns the stats as a dict and synchronises;
+        ``stats=False``: returns None, asynchronous on the context's stream unless the index is stale."""
+        A = _dev_scans(descs)
+        mg = 3.0 * float(self.params.cell) if margin is None else float(margin)
+        e = MapEvidence(float(min_range), float(max_range), mg, int(image_log2), int(window), int(min_miss), int(agree_factor), 0)
+        s = MapEvidenceStats() if stats else None
+        L = load_library()
+        if isinstance(poses, np.ndarray) or not hasattr(poses, "data_ptr"):
+            T = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
+            if T.shape[0] != len(descs):
+                raise IcetError(ICET_ERR_BAD_ARG, "one 4 x 4 pose per scan")
+            self._check(L.icet_voxel_map_evidence_device(self._h, len(descs), A, T.ctypes.data if len(descs) else None, C.byref(e), C.byref(s) if stats else None))
+        else:
+            import torch
+            if not (poses.is_cuda and poses.dtype == torch.float32 and poses.is_contiguous()) or poses.numel() != 16 * len(descs):
+                raise IcetError(ICET_ERR_BAD_ARG, "device poses must be a contiguous float32 CUDA tensor of one 4 x 4 pose per scan")
+            torch.cuda.current_stream(poses.device).synchronize()      # the context's stream is its own: the tensor must be complete
+            self._check(L.icet_voxel_map_evidence_posed_device(self._h, len(descs), A, _vp(poses.data_ptr()), C.byref(e), C.byref(s) if stats else None))
+        return s.as_dict() if stats else None
+
+    def evidence_fetch_device(self, cap, d_miss_ptr=None, d_agree_ptr=None, d_transient_ptr=None):
+        """Copy the evidence the map holds into device arrays of ``cap`` entries (int32, int32, uint8; any may be left out), in index order, on the context's
+        stream (icet_voxel_map_evidence_fetch_device).  Refused when there is no current evidence or cap is below the cells of the index.  Returns the rows."""
+        rows = C.c_int64(0)
+        self._check(load_library().icet_voxel_map_evidence_fetch_device(self._h, _vp(d_miss_ptr), _vp(d_agree_ptr), _vp(d_transient_ptr), int(cap), C.byref(rows)))
+        return int(rows.value)
+
+    def evidence_fetch(self):
+        """The evidence the map holds, on the host: dict(miss (n,) int32, agree (n,) int32, transient (n,) uint8, key (n,) uint64), in index order."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        n = int(self.index()["cells_out"])
+        miss = torch.zeros(max(n, 1), dtype=torch.int32, device=dev); agree = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        tr = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        rows = self.evidence_fetch_device(n, miss.data_ptr(), agree.data_ptr(), tr.data_ptr())
+        self._ctx.sync()
+        key = self.extract(1)["key"]                                  # the index order is extract's at min_points 1
+        return dict(miss=miss[:rows].cpu().numpy(), agree=agree[:rows].cpu().numpy(), transient=tr[:rows].cpu().numpy(), key=key)
+
+    def evidence(self, scans, poses, max_range, margin=None, min_range=0.0, image_log2=8, window=1, min_miss=2, agree_factor=1):
+        """evidence_device for host N x 3 arrays, and the fetch: dict(miss, agree, transient, key, stats)."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        torch.cuda.synchronize(dev)
+        st = self.evidence_device([(b.data_ptr(), b.shape[1], b.shape[1]) for b in bufs], poses, max_range, margin, min_range, image_log2, window, min_miss, agree_factor)
+        res = self.evidence_fetch()
+        res["stats"] = st
+        return res
+
+    def query_device(self, poses, outs, d_rows_ptr, min_range=0.0, max_range=0.0, min_points=1, world=False, d_total_ptr=None, d_status_ptr=None, static=False):
         """For each pose the cells of the map within (min_range, max_range] of it, in the pose's own frame (``world``: in the map's), in key order, into device
         buffers.  ``poses``: a Q x 4 x 4 NumPy array (icet_voxel_map_query_device) or a float32 CUDA tensor (icet_voxel_map_query_posed_device); ``outs``: one
         (d_xyz_ptr, ld, cap_rows, d_count_ptr, d_key_ptr) per pose (a MapSubmap each; None for a pointer left out); d_rows / d_total / d_status: device int32
-        arrays of Q entries.  Asynchronous on the context's stream unless the index is stale."""
-        q = MapQuery(float(min_range), float(max_range), int(min_points), VOXEL_MAP_QUERY_WORLD if world else 0)
+        arrays of Q entries.  ``static``: the cells the current evidence calls transient take no part (refused without current evidence).  Asynchronous on the
+        context's stream unless the index is stale."""
+        q = MapQuery(float(min_range), float(max_range), int(min_points), (VOXEL_MAP_QUERY_WORLD if world else 0) | (VOXEL_MAP_QUERY_STATIC if static else 0))
         O = (MapSubmap * max(len(outs), 1))(*[MapSubmap(int(o[0]) if o[0] else None, int(o[1]), int(o[2]), int(o[3]) if len(o) > 3 and o[3] else None,
                                                          int(o[4]) if len(o) > 4 and o[4] else None) for o in outs])
         L = load_library()
@@ -1877,7 +1954,7 @@ class VoxelMap:
         torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensor must be complete
         self._check(L.icet_voxel_map_query_posed_device(self._h, len(outs), _vp(poses.data_ptr()), C.byref(q), O, _vp(d_rows_ptr), _vp(d_total_ptr), _vp(d_status_ptr)))
 
-    def query(self, poses, min_range=0.0, max_range=0.0, min_points=1, world=False, cap_rows=None):
+    def query(self, poses, min_range=0.0, max_range=0.0, min_points=1, world=False, cap_rows=None, static=False):
         """The host form: a count-only call, buffers of each query's total (or ``cap_rows``), the real call.  One dict per pose: xyz (n, 3) float32, count (n,)
         int64, key (n,) uint64, total, status."""
         import torch
@@ -1885,7 +1962,7 @@ class VoxelMap:
         nq = int(poses.shape[0]) if hasattr(poses, "data_ptr") else np.asarray(poses, np.float32).reshape(-1, 16).shape[0]
         words = torch.zeros((3, max(nq, 1)), dtype=torch.int32, device=dev)      # rows | total | status
         torch.cuda.synchronize(dev)
-        kw = dict(min_range=min_range, max_range=max_range, min_points=min_points, world=world)
+        kw = dict(min_range=min_range, max_range=max_range, min_points=min_points, world=world, static=static)
         self.query_device(poses, [(None, 0, 0)] * nq, words[0].data_ptr(), d_total_ptr=words[1].data_ptr(), **kw)
         self._ctx.sync()
         caps = [int(t) if cap_rows is None else int(cap_rows) for t in words[1, :nq].cpu().numpy()]

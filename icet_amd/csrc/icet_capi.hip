@@ -1534,6 +1534,8 @@ icet_status icet_set_option(icet_ctx* c, const char* name, double value) {
     else if (k == "pg_solver") { if (!(value == 0.0 || value == 1.0 || value == 2.0)) { c->err = "pg_solver must be 0 (conjugate gradients), 1 (direct) or 2 (auto)"; return ICET_ERR_BAD_ARG; } c->pg_solver = iv; }
     else if (k == "map_lds") c->map_lds = iv != 0;
     else if (k == "map_query_prune") c->map_query_prune = iv != 0;
+    else if (k == "map_evidence_prune") c->map_evidence_prune = iv != 0;
+    else if (k == "map_evidence_batch") { if (!(value >= 0.0 && value <= 256.0)) { c->err = "map_evidence_batch must lie in 0 .. 256 (0: automatic)"; return ICET_ERR_BAD_ARG; } c->map_evidence_batch = iv; }
     else { c->err = "unknown option: " + k; return ICET_ERR_BAD_ARG; }
     return ICET_OK;
 }

@@ -110,6 +110,8 @@ struct icet_ctx {
     int32_t* h_sync_word = nullptr; int armed_calls = 2;
     int map_lds = 1;                                             // option "map_lds": a voxel map's add reduces a block's rows in LDS first (icet_map.hip)
     int map_query_prune = 1;                                     // option "map_query_prune": a voxel map's query skips the chunks outside a pose's run of x cells
+    int map_evidence_prune = 1;                                  // option "map_evidence_prune": the same for the scans of a voxel map's evidence (icet_map.hip)
+    int map_evidence_batch = 0;                                  // option "map_evidence_batch": scans per batch of range images; 0: as many as fit 64 MiB, 1 .. 256
     int64_t snapshot_chunk_bytes = 0;                          // option "snapshot_chunk_bytes": payload bytes per chunk of a store's save / load (0: 64 MiB)
     // Who owns what w and the pointers above point at: one group per set of arrays that grows together (the ensure_* functions of icet_capi.hip).  delete frees them (last member: gone first).
     struct Mem {
@@ -232,7 +234,8 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            _close[_appearance|_coarse]_device; icet_keyframe_store_save, _load (drain as well); icet_pose_graph_optimize[_device],
 //                            icet_debug_pose_graph_step, _direct, icet_pose_graph_marginals[_device], icet_debug_pose_graph_marginals (pg_run: drains as well);
 //                            icet_voxel_map_create, _clear, _add_device, _add_posed_device; _stats, _extract_device, _extract (drain as well; icet_map.hip);
-//                            icet_voxel_map_index, _query_device, _query_posed_device (drain only when the index is stale and they rebuild it)
+//                            icet_voxel_map_index, _query_device, _query_posed_device (drain only when the index is stale and they rebuild it);
+//                            icet_voxel_map_evidence_device, _evidence_posed_device (the same, and when their buffers grow or *out is asked for), _evidence_fetch_device
 //   arms or disarms itself   icet_solve_batch_device
 //   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_block_tridiag (copy in, one kernel, copy out,
 //                            synchronise); icet_debug_fetch, icet_keyframe_store_debug_fetch, icet_keep_stats (synchronise, then blocking copies);

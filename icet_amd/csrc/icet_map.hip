@@ -13,6 +13,12 @@
 //                         and popcounts): one int32 per (query, chunk).  A query whose run of x cells misses the chunk's is not tested (option "map_query_prune")
 //     k_map_query_scan    one block per query: exclusive offsets of its chunks, and d_rows / d_total / d_status
 //     k_map_query_write   the test again; a kept cell's rank is chunk offset + wave prefix + lane prefix, so the rows keep the index order, which is key order
+// and the visibility evidence (icet_voxel_map_evidence_*; the rule: icet_map_evidence.h), per cell of the index, from scans in batches:
+//     k_map_image         the add's table and loads; a row's octahedral pixel and range word, one 32-bit atomicMin per run of equal pixels among a lane's 4 rows
+//     k_map_image_near    one thread per pixel: the minimum over the pixel's window
+//     k_map_evidence      the query's chunks and load shape; the batch's poses in LDS, a block-uniform loop over its scans (pruned by their run of x cells), one
+//                         gather from the near image per (cell, scan), two counters per cell added to miss[] / agree[] with plain stores
+//     k_map_evidence_decide   the transient byte per cell, which the <true> instantiations of the two query kernels read (ICET_VOXEL_MAP_QUERY_STATIC)
 // The host side shares two pieces: CallStage, a call's records and poses (pinned, then on the device, behind a read fence), for an add's scan descriptors and a query's
 // sub-map descriptors; and map_sorted_cells (size query, growth, select, sort), which the extract and the index each run over a SortedCells of their own.
 // Sums of integers only: no float atomic, no block waits for another block, no fence inside a kernel, and the contents do not depend on the launch shape.
@@ -23,6 +29,7 @@
 #include "icet_staging.h"
 #include "icet_map.h"
 #include "icet_map_query.h"
+#include "icet_map_evidence.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -35,6 +42,7 @@ namespace {
 
 namespace rule = icet_map_rule;
 namespace qrule = icet_map_query_rule;
+namespace erule = icet_map_evidence_rule;
 typedef unsigned long long u64;
 
 constexpr int kAddBlock = 256;
@@ -238,7 +246,8 @@ __global__ __launch_bounds__(kCellBlock) void k_map_centroid(MapTable t, rule::C
 
 // ---- the query: sub-maps around poses, out of the sorted index ---------------------------------------------------------------------------
 // The index: the cells of count >= 1 by ascending key, as contiguous arrays.  xyz: three columns of `ld` floats.
-struct MapIndex { const u64* key; const long long* count; const float* xyz; long long ld, n; };
+// trans: the evidence's decision per cell (section 23), read by the STATIC instantiations of the query kernels only.
+struct MapIndex { const u64* key; const long long* count; const float* xyz; long long ld, n; const uint8_t* trans; };
 // A query's outputs as the device reads them (icet_voxel_map_submap, word for word).
 struct MapSubmap { float* xyz; long long ld, cap_rows; long long* count; u64* key; };
 static_assert(sizeof(MapSubmap) == sizeof(icet_voxel_map_submap) && sizeof(MapSubmap) == 40, "xyz | ld | cap_rows | count | key");
@@ -259,22 +268,23 @@ __device__ __forceinline__ void query_setup(QueryLds& s, const float* __restrict
         qrule::x_interval(kc, s.T[q], prune, s.lo[q], s.hi[q]);
     }
 }
-__device__ __forceinline__ void query_load(const MapIndex& ix, long long first, QueryCells& c) {
+template <bool kStatic> __device__ __forceinline__ void query_load(const MapIndex& ix, long long first, QueryCells& c) {
 #pragma unroll
     for (int j = 0; j < kQueryTrips; j++) {
         const long long i = first + j * 64;
-        const bool in = i < ix.n;                                      // a cell behind the index: count 0 takes part in nothing
+        bool in = i < ix.n;                                            // a cell behind the index: count 0 takes part in nothing
+        if (kStatic) in = in && ix.trans[i] == 0;                      // (ICET_VOXEL_MAP_QUERY_STATIC) nor does a transient cell
         c.n[j] = in ? ix.count[i] : 0;
         for (int a = 0; a < 3; a++) c.m[j][a] = in ? ix.xyz[a * ix.ld + i] : 0.f;
     }
 }
 // What the count and the write begin with: the run of x cells the block's chunk spans, the call's queries into LDS, the lane's cells into registers.  Returns the
 // lane's first cell.  The grid is the chunks of the index, so the chunk's first cell is < ix.n.
-__device__ __forceinline__ long long query_begin(QueryLds& s, QueryCells& c, const MapIndex& ix, const float* __restrict__ poses, int n_q, const qrule::Consts& kc, int prune, int32_t& x_first, int32_t& x_last) {
+template <bool kStatic> __device__ __forceinline__ long long query_begin(QueryLds& s, QueryCells& c, const MapIndex& ix, const float* __restrict__ poses, int n_q, const qrule::Consts& kc, int prune, int32_t& x_first, int32_t& x_last) {
     const long long chunk0 = (long long)blockIdx.x * kQueryChunk, first = chunk0 + (threadIdx.x >> 6) * kQueryPerWave + (threadIdx.x & 63);
     x_first = qrule::key_x(ix.key[chunk0]); x_last = qrule::key_x(ix.key[min(chunk0 + kQueryChunk, ix.n) - 1]);
     query_setup(s, poses, n_q, kc, prune != 0);
-    query_load(ix, first, c);
+    query_load<kStatic>(ix, first, c);
     return first;
 }
 // Kept cells of this wave per query of the call, into s.wcnt.  A query whose run of x cells misses the chunk's keeps none of its cells and is not tested.
@@ -294,11 +304,11 @@ __device__ __forceinline__ void query_count(QueryLds& s, const QueryCells& c, in
 }
 
 // One int32 per (query, chunk): counts[q * n_chunks + chunk].
-__global__ __launch_bounds__(kQueryBlock) void k_map_query_count(MapIndex ix, const float* __restrict__ poses, int n_q, qrule::Consts kc, int prune,
+template <bool kStatic> __global__ __launch_bounds__(kQueryBlock) void k_map_query_count(MapIndex ix, const float* __restrict__ poses, int n_q, qrule::Consts kc, int prune,
                                                                  int32_t* __restrict__ counts, long long n_chunks) {
     __shared__ QueryLds s;
     QueryCells c; int32_t x_first, x_last;
-    query_begin(s, c, ix, poses, n_q, kc, prune, x_first, x_last);
+    query_begin<kStatic>(s, c, ix, poses, n_q, kc, prune, x_first, x_last);
     __syncthreads();
     query_count(s, c, n_q, kc, x_first, x_last);
     __syncthreads();
@@ -342,12 +352,12 @@ __global__ __launch_bounds__(kQueryBlock) void k_map_query_scan(const int32_t* _
 
 // The test again, and the rows: a kept cell's rank is its chunk's offset + the kept cells of the waves before its own + those of its wave's earlier trips +
 // those of the lanes below it in its trip's ballot -- the index order.  Ranks from cap_rows on are not written.
-__global__ __launch_bounds__(kQueryBlock) void k_map_query_write(MapIndex ix, const float* __restrict__ poses, int n_q, qrule::Consts kc, int prune,
+template <bool kStatic> __global__ __launch_bounds__(kQueryBlock) void k_map_query_write(MapIndex ix, const float* __restrict__ poses, int n_q, qrule::Consts kc, int prune,
                                                                  const int32_t* __restrict__ counts, const int32_t* __restrict__ offs, long long n_chunks,
                                                                  const MapSubmap* __restrict__ outs) {
     __shared__ QueryLds s;
     QueryCells c; int32_t x_first, x_last;
-    const long long first = query_begin(s, c, ix, poses, n_q, kc, prune, x_first, x_last);
+    const long long first = query_begin<kStatic>(s, c, ix, poses, n_q, kc, prune, x_first, x_last);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int q = threadIdx.x; q < n_q; q += kQueryBlock) {            // (the thread that staged query q) no row of q comes from this chunk: as if pruned
         const long long at = (long long)q * n_chunks + blockIdx.x;
@@ -373,6 +383,121 @@ __global__ __launch_bounds__(kQueryBlock) void k_map_query_write(MapIndex ix, co
             if (o.count) o.count[rank] = c.n[j];
             if (o.key) o.key[rank] = ix.key[first + j * 64];           // (kept: the cell exists)
         }
+    }
+}
+
+// ---- the visibility evidence: per cell of the index, how many scans saw through it and how many saw it ----------------------------------
+// A batch of scans has two images per scan, img and near, of W x W range words each; scan k of the batch owns words [k W^2, (k + 1) W^2) of both.
+
+// One launch for the scans of a batch, with the add's table and its loads: each row makes one 32-bit atomicMin on its pixel, after a lane has merged the equal
+// pixels among its four consecutive rows (the rows of a ring often share one).  ctr[0] += the rows that entered an image, once per block.
+__global__ __launch_bounds__(kAddBlock) void k_map_image(const MapScan* __restrict__ scans, int n_scans, erule::Consts kc, uint32_t* __restrict__ img, u64* __restrict__ ctr) {
+    __shared__ uint32_t tally;
+    int lo = 0, hi = n_scans - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (scans[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const MapScan sc = scans[lo];
+    const int row0 = ((int)blockIdx.x - sc.block0) * kRowsPerBlock;
+    if (row0 < 0 || row0 >= sc.n) return;                             // (the same for every thread of the block)
+    const int end = min(sc.n, row0 + kRowsPerBlock);
+    if (threadIdx.x == 0) tally = 0u;
+    __syncthreads();
+    uint32_t* im = img + ((size_t)lo << (2 * kc.w_log2));
+    const float* cx = sc.ptr; const float* cy = cx + sc.ld; const float* cz = cx + 2 * (size_t)sc.ld;
+    uint32_t rows = 0;
+    for (int i = row0 + 4 * (int)threadIdx.x; i < end; i += 4 * kAddBlock) {
+        const int m = min(4, end - i);
+        float x[4], y[4], z[4];
+        load_rows(cx, i, m, x); load_rows(cy, i, m, y); load_rows(cz, i, m, z);
+        int32_t run_pix = -1; uint32_t run_word = erule::kEmptyPixel;
+        for (int r = 0; r < m; r++) {
+            int32_t pix; uint32_t word;
+            if (!erule::row_pixel(kc, x[r], y[r], z[r], pix, word)) continue;      // 0 <= pix < W^2: the rule clamps u and v
+            rows++;
+            if (pix != run_pix) {
+                if (run_pix >= 0) atomicMin(&im[run_pix], run_word);
+                run_pix = pix; run_word = word;
+            } else {
+                run_word = min(run_word, word);
+            }
+        }
+        if (run_pix >= 0) atomicMin(&im[run_pix], run_word);
+    }
+    if (rows) atomicAdd(&tally, rows);
+    __syncthreads();
+    if (threadIdx.x == 0 && tally) __hip_atomic_fetch_add(&ctr[0], (u64)tally, MAP_RLX_AGENT);
+}
+
+// One thread per pixel of every image of the batch: the minimum over the pixel's window.
+__global__ __launch_bounds__(kCellBlock) void k_map_image_near(const uint32_t* __restrict__ img, uint32_t* __restrict__ near, erule::Consts kc, long long total) {
+    const long long i = (long long)blockIdx.x * kCellBlock + threadIdx.x;
+    if (i >= total) return;
+    const int32_t pix = (int32_t)(i & (((long long)1 << (2 * kc.w_log2)) - 1));
+    near[i] = erule::near_word(kc, img + (i - pix), pix & (kc.width - 1), pix >> kc.w_log2);
+}
+
+struct EvidenceLds { float T[erule::kMaxBatch][12]; int32_t lo[erule::kMaxBatch], hi[erule::kMaxBatch]; };
+
+// The grid is the chunks of the index, with the query's load shape: a lane holds its kQueryTrips cells in registers and reads them once.  The batch's poses are
+// staged in LDS; the loop over the scans is block-uniform, and a scan whose run of x cells misses the chunk's is skipped (an unusable pose reaches no cell).  Per
+// (cell, scan): one gather from the scan's near image and two counters.  A cell has one owner and the batches follow each other on the stream, so the sums are
+// plain loads and stores: no atomics on global memory, no block waits for another.
+__global__ __launch_bounds__(kQueryBlock) void k_map_evidence(MapIndex ix, const float* __restrict__ poses, int n_s, erule::Consts kc, int prune,
+                                                              const uint32_t* __restrict__ near, int32_t* __restrict__ miss, int32_t* __restrict__ agree) {
+    __shared__ EvidenceLds s;
+    QueryCells c;
+    const long long chunk0 = (long long)blockIdx.x * kQueryChunk, first = chunk0 + (threadIdx.x >> 6) * kQueryPerWave + (threadIdx.x & 63);
+    const int32_t x_first = qrule::key_x(ix.key[chunk0]), x_last = qrule::key_x(ix.key[min(chunk0 + kQueryChunk, ix.n) - 1]);
+    for (int q = threadIdx.x; q < n_s; q += kQueryBlock) {
+        for (int j = 0; j < 12; j++) s.T[q][j] = poses[16 * (size_t)q + j];
+        erule::x_interval(kc, s.T[q], prune != 0, s.lo[q], s.hi[q]);
+    }
+    query_load<false>(ix, first, c);
+    __syncthreads();
+    int32_t n_miss[kQueryTrips], n_agree[kQueryTrips];
+#pragma unroll
+    for (int j = 0; j < kQueryTrips; j++) { n_miss[j] = 0; n_agree[j] = 0; }
+    for (int q = 0; q < n_s; q++) {
+        if (!(s.lo[q] <= x_last && s.hi[q] >= x_first)) continue;     // (the same for every thread of the block)
+        const uint32_t* nq = near + ((size_t)q << (2 * kc.w_log2));
+#pragma unroll
+        for (int j = 0; j < kQueryTrips; j++) {
+            int32_t pix; double d2;
+            if (c.n[j] <= 0 || !erule::cell_pixel(kc, s.T[q], c.m[j][0], c.m[j][1], c.m[j][2], pix, d2)) continue;
+            const int cls = erule::cell_class(kc, d2, nq[pix]);       // 0 <= pix < W^2
+            n_miss[j] += cls == erule::kMiss; n_agree[j] += cls == erule::kAgree;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kQueryTrips; j++) {
+        const long long i = first + j * 64;
+        if (i >= ix.n || !(n_miss[j] | n_agree[j])) continue;
+        miss[i] += n_miss[j]; agree[i] += n_agree[j];
+    }
+}
+
+// Behind the last batch: the decision per cell, ctr[1] += the transient cells (tallied per block, one atomic per block), and block 0 counts the call's
+// unusable poses into ctr[2].
+__global__ __launch_bounds__(kCellBlock) void k_map_evidence_decide(const int32_t* __restrict__ miss, const int32_t* __restrict__ agree, uint8_t* __restrict__ trans, long long n,
+                                                                    erule::Consts kc, const float* __restrict__ poses, int n_s, u64* __restrict__ ctr) {
+    __shared__ uint32_t tally[2];
+    if (threadIdx.x < 2) tally[threadIdx.x] = 0u;
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * kCellBlock + threadIdx.x;
+    bool t = false;
+    if (i < n) { t = erule::transient(kc, miss[i], agree[i]); trans[i] = t ? 1 : 0; }
+    const int in_wave = __popcll(__ballot(t));
+    if ((threadIdx.x & 63) == 0 && in_wave) atomicAdd(&tally[0], (uint32_t)in_wave);
+    if (blockIdx.x == 0) {
+        for (int k = threadIdx.x; k < n_s; k += kCellBlock) {
+            float T[12];
+            for (int j = 0; j < 12; j++) T[j] = poses[16 * (size_t)k + j];
+            if (!qrule::pose_ok(T)) atomicAdd(&tally[1], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (tally[0]) __hip_atomic_fetch_add(&ctr[1], (u64)tally[0], MAP_RLX_AGENT);
+        if (blockIdx.x == 0) ctr[2] = tally[1];
     }
 }
 
@@ -435,7 +560,14 @@ struct icet_voxel_map {
     SortedCells ix_cells; long long* ix_count = nullptr; float* ix_xyz = nullptr; int64_t cap_ix = 0, ix_n = 0;
     struct icet_voxel_map_stats ix_stats{}; bool ix_stale = true;
     int32_t* q_counts = nullptr; int32_t* q_offs = nullptr; int64_t cap_qc = 0;      // a query call's per-(query, chunk) counts and offsets
-    BufferGroup table, record, xout, index, qcounts;
+    // the evidence of section 23, one entry per cell of the index it was computed on: current iff ev_valid and the index is not stale.  ev_img / ev_near: the
+    // range images of one batch of scans (cap_img words each); ev_ctr: rows imaged | transient cells | unusable poses | unused, on the device and pinned
+    CallStage<MapScan> ev;
+    int32_t* ev_miss = nullptr; int32_t* ev_agree = nullptr; uint8_t* ev_trans = nullptr; int64_t cap_ev = 0;
+    uint32_t* ev_img = nullptr; uint32_t* ev_near = nullptr; int64_t cap_img = 0;
+    u64* ev_ctr = nullptr; u64* ev_h_ctr = nullptr; int32_t cap_evrec = 0;
+    bool ev_valid = false;
+    BufferGroup table, record, xout, index, qcounts, evidence, evimages, evrecord;
 };
 
 #define MAPCHK(m, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
@@ -586,6 +718,7 @@ static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_ho
 // index's own buffers.  The count drains the stream (the sort's size is a host value), so nothing reads the old index when it grows.
 static icet_status map_index(icet_voxel_map* m) {
     if (!m->ix_stale) return ICET_OK;
+    m->ev_valid = false;                                              // (the evidence belongs to the index it was computed on)
     hipStream_t st = m->ctx->stream;
     struct icet_voxel_map_stats s;
     ICET_TRY(map_count(m, 1, &s));
@@ -612,7 +745,11 @@ static icet_status map_query(icet_voxel_map* m, int32_t n_q, const float* poses,
     const std::string who(call);
     if (n_q < 1 || n_q > qrule::kMaxQueries) return map_refuse(m, who + ": n_q must lie in 1 .. 256");
     if (!poses || !q || !outs || !d_rows) return map_refuse(m, who + ": bad argument (a NULL array)");
-    if (!qrule::params_ok(q->min_range, q->max_range, q->flags, q->reserved)) return map_refuse(m, who + ": the ranges must be finite, the flags known and the reserved words 0");
+    const bool is_static = (q->flags & ICET_VOXEL_MAP_QUERY_STATIC) != 0;
+    const int32_t rule_flags = q->flags & ~ICET_VOXEL_MAP_QUERY_STATIC;
+    if (!qrule::params_ok(q->min_range, q->max_range, rule_flags, q->reserved)) return map_refuse(m, who + ": the ranges must be finite, the flags known and the reserved words 0");
+    if (is_static && !(m->ev_valid && !m->ix_stale))
+        return map_refuse(m, who + ": ICET_VOXEL_MAP_QUERY_STATIC needs current evidence (icet_voxel_map_evidence_device after the last add, remove or clear)");
     if ((poses_on_device && !elem_aligned(poses)) || !(elem_aligned(d_rows) && elem_aligned(d_total) && elem_aligned(d_status)))
         return map_refuse(m, who + ": a device pointer is not aligned to its element");
     bool any_rows = false;
@@ -642,24 +779,152 @@ static icet_status map_query(icet_voxel_map* m, int32_t n_q, const float* poses,
     for (int k = 0; k < n_q; k++) s.h_rec[k] = MapSubmap{outs[k].xyz, outs[k].ld, outs[k].cap_rows, reinterpret_cast<long long*>(outs[k].count), reinterpret_cast<u64*>(outs[k].key)};
     const float* dp = nullptr;
     MAPCHK(m, s.upload(n_q, poses, poses_on_device, st, &dp));
-    const qrule::Consts kc = qrule::make_consts(m->params.cell, q->min_range, q->max_range, q->min_points, q->flags);
-    const MapIndex ix{m->ix_cells.key, m->ix_count, m->ix_xyz, (long long)m->cap_ix, (long long)m->ix_n};
+    const qrule::Consts kc = qrule::make_consts(m->params.cell, q->min_range, q->max_range, q->min_points, rule_flags);
+    const MapIndex ix{m->ix_cells.key, m->ix_count, m->ix_xyz, (long long)m->cap_ix, (long long)m->ix_n, is_static ? m->ev_trans : nullptr};
     const int prune = c->map_query_prune;
     if (n_chunks > 0) {
-        k_map_query_count<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, n_chunks);
+        if (is_static) k_map_query_count<true><<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, n_chunks);
+        else k_map_query_count<false><<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, n_chunks);
         MAPCHK(m, hipGetLastError());
     }
     k_map_query_scan<<<(unsigned)n_q, kQueryBlock, 0, st>>>(m->q_counts, m->q_offs, n_chunks, dp, s.d_rec, d_rows, d_total, d_status);
     MAPCHK(m, hipGetLastError());
     if (n_chunks > 0 && any_rows) {                                   // (a count-only call writes no row)
-        k_map_query_write<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, m->q_offs, n_chunks, s.d_rec);
+        if (is_static) k_map_query_write<true><<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, m->q_offs, n_chunks, s.d_rec);
+        else k_map_query_write<false><<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp, n_q, kc, prune, m->q_counts, m->q_offs, n_chunks, s.d_rec);
         MAPCHK(m, hipGetLastError());
     }
     MAPCHK(m, s.mark_read(st));
     return ICET_OK;
 }
 
+// The scans of one evidence batch: option "map_evidence_batch", or as many as fit 64 MiB of images (two of W^2 words per scan); 1 .. 256.
+static int32_t evidence_batch(const icet_ctx* c, int32_t image_log2) {
+    const int64_t per_scan = (int64_t)2 * 4 << (2 * image_log2);
+    const int64_t b = c->map_evidence_batch > 0 ? c->map_evidence_batch : ((int64_t)64 << 20) / per_scan;
+    return (int32_t)std::min<int64_t>(std::max<int64_t>(b, 1), erule::kMaxBatch);
+}
+
+static icet_status map_evidence(icet_voxel_map* m, int32_t n, const icet_dev_scan* scans, const float* poses, bool poses_on_device, const icet_voxel_map_evidence* e,
+                                struct icet_voxel_map_evidence_stats* out, const char* call) {
+    ICET_TRY(enter(m));
+    // everything is checked before anything is touched
+    const std::string who(call);
+    if (n < 0 || !e || (n > 0 && (!scans || !poses))) return map_refuse(m, who + ": bad argument");
+    if (!erule::params_ok(e->min_range, e->max_range, e->margin, e->image_log2, e->window, e->min_miss, e->agree_factor, e->flags))
+        return map_refuse(m, who + ": the ranges and the margin must be finite, max_range > 0, margin >= 0, image_log2 4 .. 10, window 0 .. 2, min_miss and agree_factor >= 0, flags 0");
+    if (poses_on_device && !elem_aligned(poses)) return map_refuse(m, who + ": d_poses is not aligned to 4 bytes");
+    int64_t blocks = 0;
+    for (int k = 0; k < n; k++) {
+        if (!dev_scan_ok(scans[k]) || !elem_aligned(scans[k].ptr)) return map_refuse(m, who + ": bad scan descriptor (scans[" + std::to_string(k) + "])");
+        blocks += (scans[k].n + kRowsPerBlock - 1) / kRowsPerBlock;
+    }
+    if (blocks > 0x7FFFFFFF) return map_refuse(m, who + ": too many rows in one call");
+    icet_ctx* c = m->ctx;
+    hipStream_t st = c->stream;
+    ICET_TRY(map_index(m));
+    m->ev_valid = false;                                              // (from here on the evidence changes)
+    const erule::Consts kc = erule::make_consts(m->params.cell, e->min_range, e->max_range, e->margin, e->image_log2, e->window, e->min_miss, e->agree_factor);
+    const int64_t w2 = (int64_t)1 << (2 * e->image_log2), cells = m->ix_n;
+    const int32_t batch = std::min(evidence_batch(c, e->image_log2), std::max(n, 1));
+    // the buffers: each group grows behind a drained stream (an earlier call's kernels may still read the old ones)
+    if (!m->cap_evrec) {
+        BufferGroup& g = m->evrecord;
+        MAPCHK(m, grow(g, m->cap_evrec, 4, [&] { const int a = g.device(m->ev_ctr, 4); return a ? a : g.pinned(m->ev_h_ctr, 4); }));
+    }
+    if (cells > m->cap_ev) {
+        MAPCHK(m, hipStreamSynchronize(st));
+        BufferGroup& g = m->evidence;
+        const int64_t need = cells + cells / 4;
+        MAPCHK(m, grow(g, m->cap_ev, need, [&] {
+            int a = g.device(m->ev_miss, (size_t)need);
+            if (!a) a = g.device(m->ev_agree, (size_t)need);
+            if (!a) a = g.device(m->ev_trans, (size_t)need);
+            return a;
+        }));
+    }
+    if (batch * w2 > m->cap_img) {
+        MAPCHK(m, hipStreamSynchronize(st));
+        BufferGroup& g = m->evimages;
+        const int64_t need = batch * w2;
+        MAPCHK(m, grow(g, m->cap_img, need, [&] { const int a = g.device(m->ev_img, (size_t)need); return a ? a : g.device(m->ev_near, (size_t)need); }));
+    }
+    CallStage<MapScan>& s = m->ev;
+    const float* dp = nullptr;
+    MAPCHK(m, s.begin(n, st));
+    if (n > 0) {
+        int32_t b0 = 0;
+        for (int k = 0; k < n; k++) {                                 // block0: the scan's first block in the launch of its batch
+            if (k % batch == 0) b0 = 0;
+            s.h_rec[k] = MapScan{scans[k].ptr, (int32_t)scans[k].n, (int32_t)scans[k].ld, b0, 0};
+            b0 += (int32_t)((scans[k].n + kRowsPerBlock - 1) / kRowsPerBlock);
+        }
+        MAPCHK(m, s.upload(n, poses, poses_on_device, st, &dp));
+    }
+    MAPCHK(m, hipMemsetAsync(m->ev_ctr, 0, sizeof(u64) * 4, st));
+    if (cells > 0) {
+        MAPCHK(m, hipMemsetAsync(m->ev_miss, 0, sizeof(int32_t) * (size_t)cells, st));
+        MAPCHK(m, hipMemsetAsync(m->ev_agree, 0, sizeof(int32_t) * (size_t)cells, st));
+    }
+    const MapIndex ix{m->ix_cells.key, m->ix_count, m->ix_xyz, (long long)m->cap_ix, (long long)cells, nullptr};
+    const long long n_chunks = (cells + kQueryChunk - 1) / kQueryChunk;
+    for (int32_t k0 = 0; k0 < n; k0 += batch) {
+        const int32_t nb = std::min(batch, n - k0);
+        int64_t bb = 0;
+        for (int k = k0; k < k0 + nb; k++) bb += (scans[k].n + kRowsPerBlock - 1) / kRowsPerBlock;
+        if (bb == 0) continue;                                        // no row: every pixel is empty, and an empty pixel is no evidence
+        const long long words = (long long)nb * w2;
+        MAPCHK(m, hipMemsetAsync(m->ev_img, 0xFF, sizeof(uint32_t) * (size_t)words, st));
+        k_map_image<<<(unsigned)bb, kAddBlock, 0, st>>>(s.d_rec + k0, nb, kc, m->ev_img, m->ev_ctr);
+        MAPCHK(m, hipGetLastError());
+        k_map_image_near<<<(unsigned)((words + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->ev_img, m->ev_near, kc, words);
+        MAPCHK(m, hipGetLastError());
+        if (n_chunks == 0) continue;                                  // (an empty map: the images alone, which is how scripts/bench_map_evidence.py times them)
+        k_map_evidence<<<(unsigned)n_chunks, kQueryBlock, 0, st>>>(ix, dp + 16 * (size_t)k0, nb, kc, c->map_evidence_prune, m->ev_near, m->ev_miss, m->ev_agree);
+        MAPCHK(m, hipGetLastError());
+    }
+    k_map_evidence_decide<<<(unsigned)std::max<int64_t>(1, (cells + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->ev_miss, m->ev_agree, m->ev_trans, cells, kc, dp, n, m->ev_ctr);
+    MAPCHK(m, hipGetLastError());
+    MAPCHK(m, s.mark_read(st));
+    m->ev_valid = true;
+    if (out) {
+        MAPCHK(m, hipMemcpyAsync(m->ev_h_ctr, m->ev_ctr, sizeof(u64) * 4, hipMemcpyDeviceToHost, st));
+        MAPCHK(m, hipStreamSynchronize(st));
+        std::memset(out, 0, sizeof(*out));
+        out->rows_imaged = (int64_t)m->ev_h_ctr[0]; out->cells = (int32_t)cells; out->cells_transient = (int32_t)m->ev_h_ctr[1];
+        out->scans_bad_pose = (int32_t)m->ev_h_ctr[2]; out->scans_used = n - out->scans_bad_pose;
+    }
+    return ICET_OK;
+}
+
 extern "C" {
+
+icet_status icet_voxel_map_evidence_device(icet_voxel_map* m, int32_t n, const icet_dev_scan* scans, const float* poses, const icet_voxel_map_evidence* e,
+                                           struct icet_voxel_map_evidence_stats* out) {
+    return map_evidence(m, n, scans, poses, false, e, out, "icet_voxel_map_evidence_device");
+}
+
+icet_status icet_voxel_map_evidence_posed_device(icet_voxel_map* m, int32_t n, const icet_dev_scan* scans, const float* d_poses, const icet_voxel_map_evidence* e,
+                                                 struct icet_voxel_map_evidence_stats* out) {
+    return map_evidence(m, n, scans, d_poses, true, e, out, "icet_voxel_map_evidence_posed_device");
+}
+
+icet_status icet_voxel_map_evidence_fetch_device(icet_voxel_map* m, int32_t* d_miss, int32_t* d_agree, uint8_t* d_transient, int64_t cap, int64_t* rows_out) {
+    ICET_TRY(enter(m));
+    const std::string who("icet_voxel_map_evidence_fetch_device");
+    if (!(m->ev_valid && !m->ix_stale)) return map_refuse(m, who + ": no current evidence (icet_voxel_map_evidence_device after the last add, remove or clear)");
+    if (cap < m->ix_n) return map_refuse(m, who + ": cap is below the cells of the index");
+    if (!(elem_aligned(d_miss) && elem_aligned(d_agree))) return map_refuse(m, who + ": a device pointer is not aligned to its element");
+    hipStream_t st = m->ctx->stream;
+    const size_t n = (size_t)m->ix_n;
+    if (n > 0) {
+        if (d_miss) MAPCHK(m, hipMemcpyAsync(d_miss, m->ev_miss, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, st));
+        if (d_agree) MAPCHK(m, hipMemcpyAsync(d_agree, m->ev_agree, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, st));
+        if (d_transient) MAPCHK(m, hipMemcpyAsync(d_transient, m->ev_trans, n, hipMemcpyDeviceToDevice, st));
+    }
+    if (rows_out) *rows_out = m->ix_n;
+    return ICET_OK;
+}
 
 const char* icet_voxel_map_last_error(const icet_voxel_map* m) { return m ? m->err.c_str() : "null voxel map"; }
 

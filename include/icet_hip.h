@@ -927,6 +927,53 @@ icet_status icet_voxel_map_query_device(icet_voxel_map* map, int32_t n_q, const 
 icet_status icet_voxel_map_query_posed_device(icet_voxel_map* map, int32_t n_q, const float* d_poses, const icet_voxel_map_query* q, const icet_voxel_map_submap* outs,
                                               int32_t* d_rows, int32_t* d_total, int32_t* d_status);
 
+/* --- the voxel map's visibility evidence: which cells later scans saw THROUGH, so that movers leave the map ----------------------------
+ * A cell that any scan ever hit stays in the map; a car that drove past stays as ghost cells.  A cell is suspect when scans measured something further away
+ * through it.  The evidence is a pure function of the map's index, the scans and the poses given: integers and minima only, independent of order, call
+ * boundaries and launch shape.  THE RULE (icet_amd/csrc/icet_map_evidence.h), every operation IEEE double, rounded once, nothing contracted, division and
+ * square root correctly rounded; W = 2^image_log2:
+ *   A. the RANGE IMAGE of one scan, in the sensor's frame (no pose involved), for a row (x, y, z): a non-finite coordinate takes no part;
+ *      d2 = (x x + y y) + z z, the row takes part iff d2 > min_range^2 (the map's max_range is not applied: a far return is evidence about everything in front
+ *      of it); a = (|x| + |y|) + |z|, px = x / a, py = y / a; if z < 0: (px, py) <- ((1 - |py|) sgn(px), (1 - |px|) sgn(py)) with the old px, py on the right
+ *      and sgn(v) = v < 0 ? -1 : +1 (the octahedral map); u = clamp(floor((px + 1) (W / 2)), 0, W - 1), v likewise from py, the double clamped before the
+ *      conversion; the pixel v W + u keeps the MINIMUM of r = (float)sqrt(d2) over its rows, taken on the float's bits as uint32; all ones is an empty pixel;
+ *   B. the NEAR IMAGE: near[v][u] = the minimum of the image over [v - window, v + window] x [u - window, u + window] clipped to the image (no wrap);
+ *   C. one cell (centroid m, the three float32 values extract writes) against one scan at the pose T = [R | t]: a non-finite entry among T[0 .. 11] -- the scan
+ *      gives no evidence and counts in scans_bad_pose; d_a = (double)m_a - (double)t_a, p_a = (R[0][a] d_0 + R[1][a] d_1) + R[2][a] d_2,
+ *      d2 = (p_0 p_0 + p_1 p_1) + p_2 p_2; the scan takes part for the cell iff d2 > min_range^2 and d2 <= max_range^2; the pixel of p by A; an empty near
+ *      pixel is no evidence; rc = sqrt(d2), rn = (double)near, mg = (double)margin: MISS iff rn > rc + mg, else AGREE iff rn >= rc - mg, else the cell is
+ *      occluded, which is no evidence;
+ *   D. per cell: miss and agree are int32 sums over the call's scans; transient = miss >= max(1, min_miss) && (int64)miss > (int64)agree_factor * agree.
+ * The evidence covers the cells of the index (count >= 1) in index order: the order of extract at min_points 1 and of a world query of everything.
+ * evidence_device (HOST poses) and evidence_posed_device (DEVICE poses, 4-byte aligned) rebuild a stale index first, zero the evidence, accumulate it over the
+ *   n >= 0 scans (n = 0: all zero), take the decision, and with out != NULL fill *out and synchronise (out == NULL: asynchronous unless the index was stale or
+ *   a buffer grew).  The scans are imaged in batches (option "map_evidence_batch": 0, the default, as many as fit 64 MiB of images, 1 .. 256; same bits for every
+ *   value); a scan whose run of x cells misses a chunk of the index is not tested against it (option "map_evidence_prune", default 1; same bits).
+ * The evidence belongs to the index it was computed on: add, remove and clear make it stale together with the index.  evidence_fetch_device copies what the map
+ *   holds into DEVICE arrays of cap >= the index's cells (any of the three may be NULL; *rows_out, HOST, may be NULL), on the context's stream.
+ * ICET_VOXEL_MAP_QUERY_STATIC in icet_voxel_map_query.flags: transient cells take no part in the query.  Without current evidence such a query is refused.
+ * Refusals (ICET_ERR_BAD_ARG, the reason in icet_voxel_map_last_error, nothing touched): a NULL map or record, a NULL array with n > 0, n < 0, a bad descriptor,
+ *   a non-finite parameter or one out of its range, unknown flags, a misaligned device pointer; a fetch without current evidence or with cap below the index.
+ * No CPU fall-back.  Stores, the context's workspace and extract's buffers are not touched. */
+#define ICET_VOXEL_MAP_QUERY_STATIC 2     /* flag of a query: the cells the current evidence calls transient take no part */
+typedef struct icet_voxel_map_evidence {
+    float min_range, max_range, margin;   /* finite; max_range > 0; margin >= 0 */
+    int32_t image_log2;                   /* 4 .. 10 */
+    int32_t window;                       /* 0 .. 2 */
+    int32_t min_miss, agree_factor;       /* >= 0 */
+    int32_t flags;                        /* 0 */
+} icet_voxel_map_evidence;        /* 32 bytes */
+struct icet_voxel_map_evidence_stats {
+    int64_t rows_imaged;          /* rows that entered a range image (a scan with an unusable pose is imaged too) */
+    int32_t cells, cells_transient, scans_used, scans_bad_pose;
+    int32_t reserved[2];
+};                                /* 32 bytes */
+icet_status icet_voxel_map_evidence_device(icet_voxel_map* map, int32_t n, const icet_dev_scan* scans, const float* poses, const icet_voxel_map_evidence* e,
+                                           struct icet_voxel_map_evidence_stats* out);
+icet_status icet_voxel_map_evidence_posed_device(icet_voxel_map* map, int32_t n, const icet_dev_scan* scans, const float* d_poses, const icet_voxel_map_evidence* e,
+                                                 struct icet_voxel_map_evidence_stats* out);
+icet_status icet_voxel_map_evidence_fetch_device(icet_voxel_map* map, int32_t* d_miss, int32_t* d_agree, uint8_t* d_transient, int64_t cap, int64_t* rows_out);
+
 /* Launch-shape and diagnostic knobs of ONE context (the library never reads the environment).  Defaults are the measured
  * optima.  Launch-shape knobs yield the same result bits; "force_exact", "guard_scale" and "lut_polar_quantile" preserve every
  * DECISION (the per-voxel counts n2_raw / n2_in) but move points between the 4-point runs and the runs of one, i.e. they regroup
@@ -946,7 +993,7 @@ icet_status icet_voxel_map_query_posed_device(icet_voxel_map* map, int32_t n_q, 
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
  * bits; default 0: measured no faster on MI355X, where a device-scope fence is an L2 write-back), "batch_parts" (0 = automatic), "batch_stage" (0..4), "force_exact"
  * (every scan-2 point through the literal classification), "library_sort" (rocPRIM radix sort instead of
- * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents), "map_query_prune" (icet_voxel_map_query_*: 1, the default, a block skips the queries whose run of x cells misses its chunk; 0 every cell is tested for every query; same bits), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
+ * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents), "map_query_prune" (icet_voxel_map_query_*: 1, the default, a block skips the queries whose run of x cells misses its chunk; 0 every cell is tested for every query; same bits), "map_evidence_prune" (icet_voxel_map_evidence_*: 1, the default, a block skips the scans whose run of x cells misses its chunk; same bits), "map_evidence_batch" (scans per batch of range images: 0, the default, as many as fit 64 MiB, else 1 .. 256; same bits), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
  * the condition number |A|_F |A^-1|_F exceeds it is inverted by the literal restatement of the reference's statements -- column-pivoted QR
  * pseudo-inverse, eigenvectors, pruning -- instead of a Cholesky factorisation; 0 = always literal.  Not a launch-shape knob: between the two
  * routes cov / dx differ by rounding times the condition number).  Unknown name or value
