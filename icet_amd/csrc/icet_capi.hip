@@ -363,14 +363,13 @@ icet_status ensure_pack(icet_ctx* c, int V, int runlen) {
     return ICET_OK;
 }
 
-// Enqueue the whole solve for descriptors already sitting in c->h_desc[0..n_pairs).
 // The solve in two halves, so that a sequential caller can build the keyframe of a scan while the previous pair is still iterating
 // (icet_keyframe_device / icet_register_device): enqueue_keyframe = ICET::fitScan1 (src/icet.cpp:68-107) for the scan-1 halves of the
 // descriptors in c->h_desc[0..n_pairs), enqueue_loop = prepScan2 + runlen x fitScan2 (:254-277, :372-436) for their scan-2 halves
 // against the tables the keyframe left in the workspace.
-// hd / hs: the staging the call's descriptors sit in (default: h_desc / h_seg; an indexed call passes its own staging and no segment table).
-LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs, PairDesc* hd = nullptr, int32_t* hs = nullptr) {
-    if (!hd) { hd = c->h_desc; hs = c->h_seg; }
+// THE PLAN of a call: its launch configuration, from the parameters, the options and the totals of the staging the call has laid out (lay_out_staging,
+// icet_staging.h).  Pure: computed once per call -- behind ensure_thresholds, whose table sizes the keep list's LDS test reads -- and handed to the graph key and the enqueuers.
+LaunchCfg make_cfg(const icet_ctx* c, const icet_params* p, int32_t n_pairs, const StagingTotals& t) {
     LaunchCfg cfg{};
     cfg.T = p->bins_theta; cfg.P = p->bins_phi; cfg.V = cfg.T * cfg.P; cfg.n = p->n; cfg.runlen = p->runlen;
     cfg.thresh = p->thresh; cfg.buff = p->buff; cfg.n_pairs = n_pairs;
@@ -392,18 +391,8 @@ LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs, PairDesc*
     if (cfg.kf_pts_per_thread > kKfMaxPtsPerThread) cfg.kf_pts_per_thread = kKfMaxPtsPerThread;      // k_bin_scatter: a tile is at most 4 waves x that many rounds x 64 positions
     if (cfg.kf_pts_per_thread < 1) cfg.kf_pts_per_thread = 1;
     cfg.stage_event = c->stage_at ? c->ev_stage : nullptr; cfg.stage_at = c->stage_at;
-    cfg.vec4_ok = 1;
-    int64_t tot = 0, tot2 = 0; int mx1 = 0, mx2 = 0;
-    for (int k = 0; k < n_pairs; k++) {
-        if ((reinterpret_cast<uintptr_t>(hd[k].s2) & 15u) || (hd[k].ld2 & 3)) cfg.vec4_ok = 0;
-        if (hs) hs[k] = (int32_t)tot;
-        hd[k].off1 = (int32_t)tot; tot += hd[k].n1;
-        hd[k].off2 = (int32_t)tot2; tot2 += hd[k].n2;
-        if (hd[k].n1 > mx1) mx1 = hd[k].n1;
-        if (hd[k].n2 > mx2) mx2 = hd[k].n2;
-    }
-    if (hs) hs[n_pairs] = (int32_t)tot;
-    cfg.total_n1 = tot; cfg.max_n1 = mx1; cfg.max_n2 = mx2;
+    cfg.vec4_ok = t.vec4_ok; cfg.total_n1 = t.total_n1; cfg.max_n1 = t.max_n1; cfg.max_n2 = t.max_n2;
+    const int mx1 = t.max_n1;
     // A small batch of ordinary scans leaves most CUs without a keyframe tile at the full tile size (one 120 k-row scan: 59 tiles on 256 CUs): half-size tiles
     // then (measured, single pair: keyframe 0.170 -> 0.160 ms; a 485 k-row scan keeps the full size: 0.29 vs 0.31).  Same bits either way.
     if (cfg.kf_pts_per_thread == kKfMaxPtsPerThread && kKfMaxPtsPerThread >= 8 && (int64_t)n_pairs * ((mx1 + 256 * kKfMaxPtsPerThread - 1) / (256 * kKfMaxPtsPerThread)) < 128)
@@ -412,29 +401,27 @@ LaunchCfg make_cfg(icet_ctx* c, const icet_params* p, int32_t n_pairs, PairDesc*
     if (cfg.kf_chunks < 1) cfg.kf_chunks = 1;
     return cfg;
 }
-
-// The pair staging (h_desc / h_seg; a permuted batch carries the caller's pair of every slot behind the offsets) to the device.
-icet_status upload_desc(icet_ctx* c, int32_t n_pairs, bool by_next_kernel) {
-    ICET_TRY(staging_upload(c, c->w, c->h_desc, c->h_seg, n_pairs, (size_t)n_pairs + 1 + (c->perm_active ? n_pairs : 0), by_next_kernel));
-    return staging_mark_read(c);
+// The plan's part of a graph key (icet_ctx::GraphKey::launch): what grids, LDS sizes, template choices and by-value arguments are made from.  Not in it: what an
+// option's setter un-sees the keys for (fuse_solve, gn_cond_bound) and what no captured call uses (the keep list, batch stages).
+void launch_key_of(const LaunchCfg& k, int64_t (&out)[29]) {
+    auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return (int64_t)i; };
+    const int64_t v[] = {k.T, k.P, k.V, k.n, k.runlen, bits(k.thresh), bits(k.buff), k.n_pairs, k.max_n1, k.max_n2, k.total_n1, k.lds_slots, k.acc_min_pts_per_thread,
+                         k.acc_target_blocks, k.kf_chunks, k.kf_pts_per_thread, k.use_library_sort, k.vec4_ok, k.true_sort, k.force_exact, k.rs_cap, k.rs_max_cell,
+                         k.exec_bits_lds, k.exec_pairwise, k.lds_rank, k.reject_moving, k.half_gap, k.rt2, k.ref_w};
+    static_assert(sizeof(v) == sizeof(out), "GraphKey::launch");
+    std::memcpy(out, v, sizeof(v));
 }
 
-// What the two loop enqueuers share besides the staging: the per-iteration timing events, and the close of a call's timing.
-icet_status grow_ev_acc(icet_ctx* c, int runlen) {
-    while ((int)c->ev_acc.size() < 2 * runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }
+// The plan of a call over the pair staging (h_desc / h_seg), which the caller has finished writing: thresholds, layout, launch configuration -- in that order.
+icet_status plan_pairs(icet_ctx* c, const icet_params* p, int32_t n_pairs, LaunchCfg* cfg) {
+    ICET_TRY(ensure_thresholds(c, p->bins_theta, p->bins_phi));
+    *cfg = make_cfg(c, p, n_pairs, lay_out_staging(c->h_desc, c->h_seg, n_pairs));
     return ICET_OK;
 }
-icet_status close_timing(icet_ctx* c, const icet_params* p) {
-    if (c->capturing) return ICET_OK;
-    HIPCHK(c, hipEventRecord(c->ev_c, c->stream));
-    c->timing_valid = true; c->last_iters = (p->flags & ICET_FLAG_TIMING) ? p->runlen : 0;
-    return ICET_OK;
-}
 
-icet_status enqueue_keyframe(icet_ctx* c, const icet_params* p, int32_t n_pairs, const AuxDev* aux, const int32_t* d_counts1 = nullptr) {
+icet_status enqueue_keyframe(icet_ctx* c, const LaunchCfg& cfg, const AuxDev* aux, const int32_t* d_counts1 = nullptr) {
     Workspace& w = c->w;
-    { icet_status ts = ensure_thresholds(c, p->bins_theta, p->bins_phi); if (ts != ICET_OK) return ts; }
-    const LaunchCfg cfg = make_cfg(c, p, n_pairs);
+    const int32_t n_pairs = cfg.n_pairs;
     {
         const size_t need = (size_t)n_pairs * cfg.kf_chunks * (cfg.V > kRankSortMaxBuckets ? cfg.V : kRankSortMaxBuckets);
         if (need > w.cap_counts) {
@@ -450,7 +437,8 @@ icet_status enqueue_keyframe(icet_ctx* c, const icet_params* p, int32_t n_pairs,
     }
     // a small batch: k_rs_splitters, the keyframe's first kernel, takes the descriptors from the pinned staging itself
     const bool first_uploads = n_pairs <= kUploadDescMaxPairs && !cfg.use_library_sort;
-    ICET_TRY(upload_desc(c, n_pairs, first_uploads));
+    ICET_TRY(staging_upload(c, w, c->h_desc, c->h_seg, n_pairs, (size_t)n_pairs + 1 + (c->perm_active ? n_pairs : 0), first_uploads));      // (a permuted batch carries the caller's pair of every slot behind the offsets)
+    if (!first_uploads) ICET_TRY(staging_mark_read(c));
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
     LaunchCfg kcfg = cfg; if (first_uploads) { kcfg.h_desc_up = c->h_desc; kcfg.h_seg_up = c->h_seg; }
     HIPCHK(c, launch_keyframe(w, kcfg, aux, c->stream, d_counts1));      // (d_counts1: the descriptors hold upper bounds, the device knows the row counts: patched by the first kernel)
@@ -490,36 +478,106 @@ icet_status enqueue_rt2(icet_ctx* c, LaunchCfg& lcfg, int32_t n_pairs, const Pai
     return ICET_OK;
 }
 
-icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, const float* d_x0, float* d_out, const AuxDev* aux, bool reupload, float* pts2_out = nullptr, hipEvent_t scan2_ready = nullptr, const int32_t* d_counts2 = nullptr) {
-    const bool want_pts2 = aux && aux->xf_last && p->runlen > 0;      // pts2_out: the device computes `points2` (else only the transform snapshot + its event: the host does)
+// One call of the Gauss-Newton loop: what enqueue_loop, the ONE function that enqueues it, is told.  Two kinds of caller fill it: the pair entries (pair_loop,
+// below: the whole solve, icet_register_device_n, the host-pointer entries) and the indexed registrations (register_indexed: registration r against the keyframe
+// tables of kf_of[r]; the registration-side tables -- acc, xf, X, overflow counts, tickets -- are indexed by r).
+enum LoopTail { kTailNone, kTailScore, kTailDump, kTailTerms };
+struct LoopCall {
+    // the staging the loop reads -- h_desc / h_seg, or h_desc_reg / h_kf_of (k_init_state / k_upload_desc copy the keyframe index as their "segment" table) --, the
+    // words of its segment table, and whether it goes up HERE (false: it went up with the keyframe, earlier in this call)
+    PairDesc* hd = nullptr; int32_t* hs = nullptr; size_t seg_words = 0; bool upload = false;
+    // what the loop's kernels see of the workspace: the keyframe tables of the context or of a store, desc or desc_reg; kf_of: set for an indexed call (LaunchCfg::kf_of)
+    Workspace view; const int32_t* kf_of = nullptr;
+    const float* d_x0 = nullptr; float* d_out = nullptr; const AuxDev* aux = nullptr; int iters = 0;
+    // known to the DEVICE only: the scan-2 row counts (the descriptors hold upper bounds, which size the launches; k_init_state clamps them, or k_patch_counts in
+    // front of the scan-2 round trip) and, for a loop-closure query, the keyframe index (copied over the staged one behind k_init_state)
+    const int32_t* d_rows = nullptr; const int32_t* d_kf_of = nullptr;
+    hipEvent_t scan2_ready = nullptr;      // host-pointer entries: scan 2 was uploaded on the copy stream beside the keyframe build
+    float* pts2_out = nullptr;             // the device computes `points2` into this (else only the transform snapshot + its event: the host does)
+    // plain: the plain point pass and solve -- no fused launch, no keep list, no pair_user, no done_flag (an indexed call: launch_gn_accumulate refuses the rest with kf_of)
+    // own_timing: no keyframe build in this call, keyframe_ms = 0: ev_a is recorded here too.  An indexed call.  (icet_register_device_n leaves ev_a where its keyframe
+    // call recorded it: its keyframe_ms runs from there.)
+    // init_on_copy: under the scan-2 round trip k_init_state sees the descriptors of the round-tripped copy and clamps THEIR counts to d_rows.  An indexed call.  The pair
+    // entries hand it the caller's descriptors and no rows (k_patch_counts has clamped those): the copy's descriptors keep the bounds of the host staging, and the loop
+    // reads the copy up to them (tests/test_halves_device_rows.py pins that as it is).
+    bool plain = false, own_timing = false, init_on_copy = false;
+    // behind the loop: one more point pass at the final transform records (the last solve, or k_init_state, left them in w.xf), then the score, the raw sums in
+    // place of it (d_dump), or the terms (d_dump and terms: enqueue_terms_tail)
+    LoopTail tail = kTailNone; icet_score* d_score = nullptr; uint32_t* d_dump = nullptr; const GnTermsOut* terms = nullptr;
+};
+// The loop of a pair entry over h_desc / h_seg and the context's own tables, with every launch feature the plan allows.
+LoopCall pair_loop(icet_ctx* c, const LaunchCfg& cfg, const float* d_x0, float* d_out, const AuxDev* aux, bool upload, hipEvent_t scan2_ready = nullptr) {
+    LoopCall L;
+    L.hd = c->h_desc; L.hs = c->h_seg; L.seg_words = (size_t)cfg.n_pairs + 1 + (c->perm_active ? cfg.n_pairs : 0); L.upload = upload;      // (a permuted batch carries the caller's pair of every slot behind the offsets)
+    L.view = c->w; L.d_x0 = d_x0; L.d_out = d_out; L.aux = aux; L.iters = cfg.runlen; L.scan2_ready = scan2_ready;
+    return L;
+}
+
+// The tail of icet_debug_gn_terms_device: the point pass, the raw records copied out and left in place, the transform record, then the production solve of
+// iteration runlen - 1 on those records.  Synchronises (its scratch is freed at return).
+icet_status enqueue_terms_tail(icet_ctx* c, const icet_params* p, const Workspace& wl, const LaunchCfg& lcfg, const LoopCall& L) {
+    // the solve writes its sums at [registration][iteration] of arrays sized for the whole run: a scratch of that shape, and the rows of iteration runlen - 1 copied out
+    const int it = p->runlen - 1, n_regs = lcfg.n_pairs;
+    const size_t row = (size_t)p->runlen * 42;
+    float* d_tmp = nullptr; BufferGroup g;
+    HIPCHK(c, g.device(d_tmp, row * (size_t)n_regs));
+    auto body = [&]() -> icet_status {
+        HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
+        HIPCHK(c, launch_point_sums_copy(wl, lcfg, L.d_dump, c->stream));     // drains the overflow list; the records stay
+        HIPCHK(c, hipMemcpyAsync(L.terms->xf, c->w.xf, sizeof(float) * 48 * (size_t)n_regs, hipMemcpyDeviceToDevice, c->stream));      // (before the solve replaces it with the next iteration's)
+        AuxDev aux{};
+        aux.htwh = d_tmp; aux.htwdz = d_tmp + (size_t)n_regs * p->runlen * 36;
+        HIPCHK(c, launch_gn_solve(wl, lcfg, it, L.d_out, &aux, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(L.terms->htwh, 36 * sizeof(float), aux.htwh + (size_t)it * 36, (size_t)p->runlen * 36 * sizeof(float), 36 * sizeof(float), n_regs, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(L.terms->htwdz, 6 * sizeof(float), aux.htwdz + (size_t)it * 6, (size_t)p->runlen * 6 * sizeof(float), 6 * sizeof(float), n_regs, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return ICET_OK;
+    };
+    const icet_status ts = body();
+    if (ts != ICET_OK) (void)hipStreamSynchronize(c->stream);
+    return ts;
+}
+
+// prepScan2 + iters x fitScan2 (src/icet.cpp:254-277, :372-436) + the tail, for the call L under the plan `plan`, whose staging is laid out.
+icet_status enqueue_loop(icet_ctx* c, const icet_params* p, const LaunchCfg& plan, const LoopCall& L) {
+    const int32_t n = plan.n_pairs;
+    const bool want_pts2 = L.aux && L.aux->xf_last && p->runlen > 0;
+    LaunchCfg cfg = plan; cfg.kf_of = L.kf_of;
+    if (L.plain) { cfg.pair_user = nullptr; cfg.done_flag = nullptr; cfg.keep = 0; cfg.fuse_solve = 0; }
     Workspace& w = c->w;
-    const LaunchCfg cfg = make_cfg(c, p, n_pairs);
-    // the scan-2 halves arrived after the keyframe call.  A small batch without the scan-2 round trip: k_init_state, the first kernel below that reads a descriptor, uploads them
-    const bool init_uploads = reupload && n_pairs <= kUploadDescMaxPairs && !cfg.rt2 && !cfg.keep;
-    if (reupload) ICET_TRY(upload_desc(c, n_pairs, init_uploads));
-    if (d_counts2 && cfg.rt2) HIPCHK(c, launch_patch_counts(w, cfg, nullptr, d_counts2, c->stream));      // (otherwise k_init_state, the loop's first kernel, patches them)
-    ICET_TRY(grow_ev_acc(c, p->runlen));
-    Workspace wl = w;                                    // what the loop kernels see: with ICET_FLAG_ROUNDTRIP_SCAN2 their scan 2 is the round-tripped copy
+    Workspace wl = L.view;                               // what the loop kernels see: with ICET_FLAG_ROUNDTRIP_SCAN2 their scan 2 is the round-tripped copy
+    // A small batch without the scan-2 round trip or the keep list: k_init_state, the first kernel below that reads a descriptor, copies the staging itself (a replayed
+    // graph re-reads it then).  Otherwise it goes up in front, and the mark behind it is never skipped for a capture: a graph holds small batches without the round trip only.
+    const bool init_uploads = L.upload && n <= kUploadDescMaxPairs && !cfg.rt2 && !cfg.keep;
+    if (L.upload) ICET_TRY(staging_upload(c, wl, L.hd, L.hs, n, L.seg_words, init_uploads));
+    if (L.upload && !init_uploads) ICET_TRY(staging_mark_read(c));
+    while ((int)c->ev_acc.size() < 2 * p->runlen) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->ev_acc.push_back(e); }      // the per-iteration timing events
+    if (L.own_timing && !c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_b, c->stream));      // keyframe_ms ends here: the scan-2 pre-pass of ICET_FLAG_ROUNDTRIP_SCAN2 belongs to the loop
     LaunchCfg lcfg = cfg;
-    if (cfg.rt2) ICET_TRY(enqueue_rt2(c, lcfg, n_pairs, c->h_desc, wl, scan2_ready));
+    if (cfg.rt2 && L.d_rows) HIPCHK(c, launch_patch_counts(wl, cfg, nullptr, L.d_rows, c->stream));      // (the pre-pass reads the counts of the caller's descriptors; otherwise k_init_state patches them)
+    if (cfg.rt2) ICET_TRY(enqueue_rt2(c, lcfg, n, L.hd, wl, L.scan2_ready));
     if (cfg.keep) {                                          // masks, list and per-pair state of the keep list (grown here: only throughput batches use them)
-        int64_t tot2 = 0; for (int k = 0; k < n_pairs; k++) tot2 += c->h_desc[k].n2;
-        const size_t need_mask = (size_t)(tot2 >> 8) + (size_t)n_pairs + 2, need_list = (size_t)(tot2 >> 2) + (size_t)n_pairs + 4;
-        if (need_mask > w.cap_keep_mask || need_list > w.cap_keep_list || n_pairs > w.cap_keep_pairs) {
+        int64_t tot2 = 0; for (int k = 0; k < n; k++) tot2 += L.hd[k].n2;
+        const size_t need_mask = (size_t)(tot2 >> 8) + (size_t)n + 2, need_list = (size_t)(tot2 >> 2) + (size_t)n + 4;
+        if (need_mask > w.cap_keep_mask || need_list > w.cap_keep_list || n > w.cap_keep_pairs) {
             if (c->capturing) { c->err = "keep list: workspace growth during capture"; return ICET_ERR_HIP; }
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (need_mask > w.cap_keep_mask) HIPCHK(c, grow(c->mem.keep_mask, w.cap_keep_mask, need_mask, [&] { return c->mem.keep_mask.device(w.keep_mask, need_mask); }));
             if (need_list > w.cap_keep_list) HIPCHK(c, grow(c->mem.keep_list, w.cap_keep_list, need_list, [&] { return c->mem.keep_list.device(w.keep_list, need_list); }));
-            if (n_pairs > w.cap_keep_pairs) {
+            if (n > w.cap_keep_pairs) {
                 BufferGroup& g = c->mem.keep_pairs;
-                HIPCHK(c, grow(g, w.cap_keep_pairs, n_pairs, [&] { const int e = g.device(w.keep_state, (size_t)n_pairs); return e ? e : g.device(w.keep_modes, 2 * (size_t)n_pairs); }));
+                HIPCHK(c, grow(g, w.cap_keep_pairs, n, [&] { const int e = g.device(w.keep_state, (size_t)n); return e ? e : g.device(w.keep_modes, 2 * (size_t)n); }));
             }
             wl.keep_modes = w.keep_modes; wl.keep_mask = w.keep_mask; wl.keep_list = w.keep_list; wl.keep_state = w.keep_state; wl.cap_keep_mask = w.cap_keep_mask; wl.cap_keep_list = w.cap_keep_list; wl.cap_keep_pairs = w.cap_keep_pairs;
         }
     }
-    HIPCHK(c, launch_init_state(w, cfg, d_x0, c->stream, want_pts2 ? aux->xf_last : nullptr, cfg.rt2 ? nullptr : d_counts2, init_uploads ? c->h_desc : nullptr, init_uploads ? c->h_seg : nullptr));
-    if (init_uploads) ICET_TRY(staging_mark_read(c));                     // (the staging is read by THIS kernel: the mark of upload_desc, moved behind it)
+    // k_init_state: of the workspace it reads the descriptors, X, xf, the tickets and the keep state; of the plan n_pairs, keep and pair_user, which the round trip leaves alone
+    Workspace wi = wl; const int32_t* rows = L.d_rows;
+    if (cfg.rt2 && !L.init_on_copy) { wi.desc = L.view.desc; rows = nullptr; }
+    HIPCHK(c, launch_init_state(wi, lcfg, L.d_x0, c->stream, want_pts2 ? L.aux->xf_last : nullptr, rows, init_uploads ? L.hd : nullptr, init_uploads ? L.hs : nullptr));
+    if (L.d_kf_of) HIPCHK(c, launch_closure_apply(w.kf_of, L.d_kf_of, n, c->stream));
+    if (init_uploads) ICET_TRY(staging_mark_read(c));                     // (the staging is read by THIS kernel)
     // `points2` (include/icet.h:80): scan 2 as the LAST fitScan2 transforms it (src/icet.cpp:375-378).  That transform is known as soon as the
     // solve of iteration runlen - 2 has run: k_gn_solve / k_init_state snapshot its record in aux->xf_last (pinned host memory) and ev_prev
     // marks the moment.  icet_solve_end then transforms scan 2 ON THE HOST while the last iteration still runs on the device (measured: a
@@ -527,105 +585,38 @@ icet_status enqueue_loop(icet_ctx* c, const icet_params* p, int32_t n_pairs, con
     // Only with ICET_FLAG_ROUNDTRIP_SCAN2, whose points2_OG exists on the device alone, the device computes it (copy stream).
     auto enqueue_points2 = [&]() -> icet_status {
         HIPCHK(c, hipEventRecord(c->ev_prev, c->stream));
-        if (!pts2_out) return ICET_OK;
+        if (!L.pts2_out) return ICET_OK;
         HIPCHK(c, hipStreamWaitEvent(c->st_copy, c->ev_prev, 0));
-        HIPCHK(c, launch_points2(wl, lcfg, aux->xf_last, c->d_pts2, c->st_copy));
-        HIPCHK(c, hipMemcpyAsync(pts2_out, c->d_pts2, sizeof(float) * 3 * (size_t)c->h_desc[0].n2, hipMemcpyDeviceToHost, c->st_copy));
+        HIPCHK(c, launch_points2(wl, lcfg, L.aux->xf_last, c->d_pts2, c->st_copy));
+        HIPCHK(c, hipMemcpyAsync(L.pts2_out, c->d_pts2, sizeof(float) * 3 * (size_t)L.hd[0].n2, hipMemcpyDeviceToHost, c->st_copy));
         HIPCHK(c, hipEventRecord(c->ev_pts2, c->st_copy));
         return ICET_OK;
     };
-    if (scan2_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, scan2_ready, 0));     // host-pointer entries: scan 2 was uploaded on the copy stream beside the keyframe build
+    if (L.scan2_ready && !cfg.rt2) HIPCHK(c, hipStreamWaitEvent(c->stream, L.scan2_ready, 0));      // (with the round trip its pre-pass has waited: enqueue_rt2)
     if (want_pts2 && p->runlen == 1) ICET_TRY(enqueue_points2());
     const bool per_iter = (p->flags & ICET_FLAG_TIMING) != 0;
-    for (int it = 0; it < p->runlen; it++) {
+    for (int it = 0; it < L.iters; it++) {
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it], c->stream));
         // (per-iteration timing wants the two halves apart; otherwise a small batch runs the solve inside the point pass' launch)
-        const FuseArgs fa{it, d_out, aux};
-        bool fused = false;
+        const FuseArgs fa{it, L.d_out, L.aux}; bool fused = false;
         // keep list: from iteration keep_from on the point pass is the kernel that walks a pair's list or, for a pair without a valid one, its whole scan + keep masks;
         // the solve behind it builds / checks the lists (not behind the last pass: nothing follows)
         const int keep_pass = (lcfg.keep && it >= lcfg.keep_from) ? 1 : 0;
-        HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream, per_iter ? nullptr : &fa, &fused, keep_pass ? 1 + 2 * (it & 1) : 0));
+        HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream, (per_iter || L.plain) ? nullptr : &fa, &fused, keep_pass ? 1 + 2 * (it & 1) : 0));
         if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it + 1], c->stream));
-        if (!fused) HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, aux, c->stream, keep_pass ? (it + 1 < p->runlen ? 1 : 2) : 0));
+        if (!fused) HIPCHK(c, launch_gn_solve(wl, lcfg, it, L.d_out, L.aux, c->stream, keep_pass ? (it + 1 < L.iters ? 1 : 2) : 0));
         if (want_pts2 && it == p->runlen - 2) ICET_TRY(enqueue_points2());
     }
-    return close_timing(c, p);
-}
-
-// Enqueue the whole solve for descriptors already sitting in c->h_desc[0..n_pairs).
-icet_status enqueue(icet_ctx* c, const icet_params* p, int32_t n_pairs, const float* d_x0, float* d_out, const AuxDev* aux) {
-    c->kf_pairs = 0;                                                    // whatever keyframe a sequential caller had parked here is overwritten
-    ICET_TRY(enqueue_keyframe(c, p, n_pairs, aux));
-    return enqueue_loop(c, p, n_pairs, d_x0, d_out, aux, false);
-}
-
-// The Gauss-Newton loop of n_regs INDEXED registrations (icet_register_indexed_device) against the parked keyframe: descriptors in c->h_desc_reg, keyframe of
-// registration r in c->h_kf_of[r].  The registration-side tables (acc, xf, X, overflow counts, tickets) are indexed by r, the keyframe tables by h_kf_of[r]
-// (LaunchCfg::kf_of).  The plain point pass and solve: no fused launch, no keep list.
-// d_score != nullptr: one more point pass at the final transform records and the score (icet_score.hip) behind the loop; `iters` (default runlen): 0 scores the
-// poses d_x0 without iterating.  d_dump != nullptr (test hook): that point pass followed by k_point_sums_dump instead of the score.
-// src: the keyframe tables the registrations read -- nullptr: the context's parked keyframe; a store: its rows (h_kf_of then holds slot indices).
-// dev: the keyframe index and the scan-2 row counts of the registrations are known to the DEVICE only (a loop-closure query, whose candidates a kernel found a
-// moment ago on the same stream): the staging holds an occupied slot and the scans' full row counts -- the launch geometry is sized from those, as in
-// icet_register_device_n --, and behind the descriptor upload rows[r] replaces the count (k_init_state, or k_patch_counts in front of the scan-2 round trip) and
-// kf_of[r] the index.
-icet_status enqueue_indexed(icet_ctx* c, const icet_params* p, int32_t n_regs, const float* d_x0, float* d_out, icet_score* d_score = nullptr, int iters = -1,
-                            const icet_keyframe_store* src = nullptr, const IndexedDev* dev = nullptr, uint32_t* d_dump = nullptr, const GnTermsOut* terms = nullptr) {
-    if (iters < 0) iters = p->runlen;
-    Workspace& w = c->w;
-    LaunchCfg cfg = make_cfg(c, p, n_regs, c->h_desc_reg, nullptr);
-    cfg.pair_user = nullptr; cfg.done_flag = nullptr; cfg.keep = 0; cfg.fuse_solve = 0; cfg.kf_of = w.kf_of;
-    Workspace wl = w; wl.desc = w.desc_reg; wl.seg_off = w.kf_of;           // (k_init_state / k_upload_desc copy the keyframe index as their "segment" table: n_regs + 1 words)
-    if (src) { wl.hotS = src->hotS; wl.fitS = src->fitS; wl.slot_of_voxel = src->slot_of_voxel; wl.n_slots = src->n_slots; }
-    // a small batch without the scan-2 round trip: k_init_state, the loop's first kernel, copies the staging itself (a replayed graph re-reads it then)
-    const bool init_uploads = n_regs <= kUploadDescMaxPairs && !cfg.rt2;
-    ICET_TRY(staging_upload(c, wl, c->h_desc_reg, c->h_kf_of, n_regs, (size_t)n_regs + 1, init_uploads));
-    if (!init_uploads) ICET_TRY(staging_mark_read(c, true));              // (a graph replays small batches without the round trip only: this path records whatever `capturing` says)
-    ICET_TRY(grow_ev_acc(c, p->runlen));
-    if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
-    if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_b, c->stream));        // (no keyframe build in this call: keyframe_ms = 0)
-    if (cfg.rt2 && dev) HIPCHK(c, launch_patch_counts(wl, cfg, nullptr, dev->rows, c->stream));      // (the pre-pass reads the counts of the caller's descriptors)
-    LaunchCfg lcfg = cfg;
-    if (cfg.rt2) ICET_TRY(enqueue_rt2(c, lcfg, n_regs, c->h_desc_reg, wl, nullptr));
-    HIPCHK(c, launch_init_state(wl, lcfg, d_x0, c->stream, nullptr, dev ? dev->rows : nullptr, init_uploads ? c->h_desc_reg : nullptr, init_uploads ? c->h_kf_of : nullptr));
-    if (dev) HIPCHK(c, launch_closure_apply(w.kf_of, dev->kf_of, n_regs, c->stream));
-    if (init_uploads) ICET_TRY(staging_mark_read(c));
-    const bool per_iter = (p->flags & ICET_FLAG_TIMING) != 0;
-    for (int it = 0; it < iters; it++) {
-        if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it], c->stream));
+    if (L.tail == kTailTerms) ICET_TRY(enqueue_terms_tail(c, p, wl, lcfg, L));
+    else if (L.tail != kTailNone) {
         HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
-        if (per_iter) HIPCHK(c, hipEventRecord(c->ev_acc[2 * it + 1], c->stream));
-        HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, nullptr, c->stream));
+        if (L.tail == kTailDump) HIPCHK(c, launch_point_sums_dump(wl, lcfg, L.d_dump, c->stream));      // (icet_debug_point_sums_device: the raw sums in place of the score)
+        else HIPCHK(c, launch_gn_score(wl, lcfg, p->runlen, L.d_score, c->stream));
     }
-    if (terms) {                                                            // (icet_debug_gn_terms_device; iters == 0: k_init_state left the transform record of d_x0 in w.xf)
-        // the solve writes its sums at [registration][iteration] of arrays sized for the whole run: a scratch of that shape, and the rows of iteration runlen - 1 copied out
-        const int it = p->runlen - 1;
-        const size_t row = (size_t)p->runlen * 42;
-        float* d_tmp = nullptr; BufferGroup g;                        // (freed behind the synchronisations below)
-        HIPCHK(c, g.device(d_tmp, row * (size_t)n_regs));
-        auto body = [&]() -> icet_status {
-            HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
-            HIPCHK(c, launch_point_sums_copy(wl, lcfg, d_dump, c->stream));     // drains the overflow list; the records stay
-            HIPCHK(c, hipMemcpyAsync(terms->xf, w.xf, sizeof(float) * 48 * (size_t)n_regs, hipMemcpyDeviceToDevice, c->stream));      // (before the solve replaces it with the next iteration's)
-            AuxDev aux{};
-            aux.htwh = d_tmp; aux.htwdz = d_tmp + (size_t)n_regs * p->runlen * 36;
-            HIPCHK(c, launch_gn_solve(wl, lcfg, it, d_out, &aux, c->stream));
-            HIPCHK(c, hipMemcpy2DAsync(terms->htwh, 36 * sizeof(float), aux.htwh + (size_t)it * 36, (size_t)p->runlen * 36 * sizeof(float), 36 * sizeof(float), n_regs, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpy2DAsync(terms->htwdz, 6 * sizeof(float), aux.htwdz + (size_t)it * 6, (size_t)p->runlen * 6 * sizeof(float), 6 * sizeof(float), n_regs, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            return ICET_OK;
-        };
-        const icet_status ts = body();
-        if (ts != ICET_OK) (void)hipStreamSynchronize(c->stream);
-        if (ts != ICET_OK) return ts;
-    } else
-    if (d_score || d_dump) {                                                // the last solve (or k_init_state) left the transform record of the pose to score in w.xf
-        HIPCHK(c, launch_gn_accumulate(wl, lcfg, c->stream));
-        if (d_dump) HIPCHK(c, launch_point_sums_dump(wl, lcfg, d_dump, c->stream));      // (icet_debug_point_sums_device: the raw sums in place of the score)
-        else HIPCHK(c, launch_gn_score(wl, lcfg, p->runlen, d_score, c->stream));
-    }
-    return close_timing(c, p);
+    if (c->capturing) return ICET_OK;
+    HIPCHK(c, hipEventRecord(c->ev_c, c->stream));
+    c->timing_valid = true; c->last_iters = (p->flags & ICET_FLAG_TIMING) ? p->runlen : 0;
+    return ICET_OK;
 }
 
 // Staging buffers of the host-pointer entry points (3 x l floats per scan, leading dimension l = n rounded up to 64).
@@ -637,6 +628,17 @@ icet_status ensure_stage(icet_ctx* c, int64_t tot1, int64_t tot2) {
         if (3 * tot2 > c->cap_stage2) HIPCHK(c, grow(c->mem.stage2, c->cap_stage2, 3 * tot2, [&] { return c->mem.stage2.device(c->d_stage2, (size_t)3 * tot2); }));
     }
     return ICET_OK;
+}
+
+// The host-pointer entries: scan 2 goes up on the copy stream (`up`) while the keyframe kernels enqueued in front of this run; ev_s2 marks it, and the loop waits for
+// that; `then` puts what else the entry has for the copy stream behind the mark.  A failure drains both streams.
+template <typename Up, typename Then> icet_status upload_scan2_beside(icet_ctx* c, const char* what, Up up, Then then) {
+    hipError_t e = up();
+    if (e == hipSuccess) e = hipEventRecord(c->ev_s2, c->st_copy);
+    if (e == hipSuccess) e = then();
+    if (e == hipSuccess) return ICET_OK;
+    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->st_copy); c->err = std::string(what) + ": " + hipGetErrorString(e);
+    return ICET_ERR_HIP;
 }
 
 icet_status write_runlen0(icet_ctx* c, int32_t n_pairs, const float* d_x0, float* d_out) {
@@ -695,7 +697,7 @@ icet_status icet_destroy(icet_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->st_copy) (void)hipStreamSynchronize(c->st_copy);
     for (icet_ctx* h : c->helpers) (void)icet_destroy(h);
-    for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop, &c->g_indexed, &c->g_scored, &c->g_score}) if (g->have_graph) { (void)hipGraphExecDestroy(g->exec); (void)hipGraphDestroy(g->graph); }
+    for (icet_ctx::GraphSlot* g : {&c->g_solve, &c->g_keyframe, &c->g_loop, &c->g_indexed, &c->g_scored, &c->g_score}) g->reset();
     for (hipEvent_t e : c->ev_acc) (void)hipEventDestroy(e);
     c->sel_read.destroy();
     for (hipEvent_t e : {c->ev_s2, c->ev_kf, c->ev_kfd, c->ev_prev, c->ev_pts2, c->ev_a, c->ev_b, c->ev_c, c->ev_fork, c->ev_desc, c->ev_graph, c->ev_stage, c->ev_join})
@@ -829,20 +831,20 @@ extern "C++" {
 // every replay, and patched with device-side row counts where the caller has them); what the launches themselves depend on is the LaunchCfg
 // (grids, LDS sizes, point counts passed by value) and the workspace pointers.  A call whose key equals the previous call's is captured;
 // later calls with that key replay: one hipGraphLaunch instead of 15 - 35 launches on the host.
-// src_id / src_gen: the keyframe tables of an indexed call -- 0 / 0 the context's own, else a store's identity and generation (icet_keyframe_store)
-static icet_ctx::GraphKey graph_key_of(icet_ctx* c, const icet_params* p, int32_t n_pairs, const void* a0, const void* a1, const void* a2, const void* a3, PairDesc* hd = nullptr,
-                                       int64_t src_id = 0, int64_t src_gen = 0) {
+// The identity of an entry's call -- which entry, and the caller's argument pointers -- as the start of its key; an indexed call adds mode, ws_gen and its keyframe source.
+static icet_ctx::GraphKey entry_key(icet_ctx::GraphEntry entry, const void* x0, const void* out, const void* extra) {
     icet_ctx::GraphKey key{};
-    const LaunchCfg k = make_cfg(c, p, n_pairs, hd, hd ? nullptr : c->h_seg);
-    auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return (int64_t)i; };
-    const int64_t vals[] = {k.T, k.P, k.V, k.n, k.runlen, bits(k.thresh), bits(k.buff), k.n_pairs, k.max_n1, k.max_n2, k.total_n1, k.lds_slots, k.acc_min_pts_per_thread,
-                            k.acc_target_blocks, k.kf_chunks, k.kf_pts_per_thread, k.use_library_sort, k.vec4_ok, k.true_sort, k.force_exact, k.rs_cap, k.rs_max_cell,
-                            k.exec_bits_lds, k.exec_pairwise, k.lds_rank, k.reject_moving, k.half_gap, k.rt2 + 2 * k.ref_w, p->flags, (int64_t)(intptr_t)a0, (int64_t)(intptr_t)a1, (int64_t)(intptr_t)a2, (int64_t)(intptr_t)a3,
-                            (int64_t)(intptr_t)c->w.desc, (int64_t)(intptr_t)c->w.thr, (int64_t)(intptr_t)c->w.lut, (int64_t)(intptr_t)c->w.r1, (int64_t)(intptr_t)c->w.counts,
-                            (int64_t)(intptr_t)c->w.near_over, (int64_t)(intptr_t)c->w.acc, (int64_t)(intptr_t)c->w.fit_items, (int64_t)(intptr_t)c->w.sort_tmp, (int64_t)(intptr_t)c->w.tile_vr,
-                            c->prologue ? c->prologue_key : 0, (int64_t)(intptr_t)c->done_flag, src_id, src_gen};
-    static_assert(sizeof(vals) == sizeof(key.v), "GraphKey size");
-    std::memcpy(key.v, vals, sizeof(vals));
+    key.entry = entry; key.x0 = x0; key.out = out; key.extra = extra;
+    return key;
+}
+// ... completed with what the launches of ANY entry depend on: the plan, the workspace pointers, the prologue and the done flag.
+static icet_ctx::GraphKey graph_key_of(const icet_ctx* c, const icet_params* p, const LaunchCfg& cfg, icet_ctx::GraphKey key) {
+    const Workspace& w = c->w;
+    const void* ws[] = {w.desc, w.thr, w.lut, w.r1, w.counts, w.near_over, w.acc, w.fit_items, w.sort_tmp, w.tile_vr};
+    static_assert(sizeof(ws) == sizeof(key.ws), "GraphKey::ws");
+    std::memcpy(key.ws, ws, sizeof(ws));
+    key.prologue_key = c->prologue ? c->prologue_key : 0; key.done_flag = c->done_flag; key.flags = p->flags;
+    launch_key_of(cfg, key.launch);
     return key;
 }
 static bool graph_eligible(const icet_ctx* c, const icet_params* p, int32_t n_pairs) {
@@ -857,37 +859,51 @@ static bool graph_eligible(const icet_ctx* c, const icet_params* p, int32_t n_pa
 // descriptors; the caller has waited for a replay in flight before it wrote them.
 template <typename Enq> static icet_status run_or_replay(icet_ctx* c, icet_ctx::GraphSlot& slot, const icet_ctx::GraphKey& key, Enq enq) {
     auto same = [](const icet_ctx::GraphKey& a, const icet_ctx::GraphKey& b) { return std::memcmp(&a, &b, sizeof(a)) == 0; };
-    if (slot.have_graph && same(key, slot.key)) {
-        HIPCHK(c, hipGraphLaunch(slot.exec, c->stream));
-        ICET_TRY(staging_mark_replay(c));
-        c->timing_valid = false;
-        return ICET_OK;
-    }
-    if (slot.have_seen && same(key, slot.seen)) {
-        if (slot.have_graph) { (void)hipGraphExecDestroy(slot.exec); (void)hipGraphDestroy(slot.graph); slot.have_graph = false; }
+    if (!(slot.have_graph && same(key, slot.key))) {
+        if (!(slot.have_seen && same(key, slot.seen))) { slot.seen = key; slot.have_seen = true; return enq(); }      // a key's first call runs eagerly, its second is captured
+        slot.reset();
         if (!c->ev_graph) HIPCHK(c, hipEventCreateWithFlags(&c->ev_graph, hipEventDisableTiming));
         HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         c->capturing = true;
         const icet_status es = enq();
         c->capturing = false;
-        hipGraph_t g = nullptr;
+        hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
         const hipError_t ee = hipStreamEndCapture(c->stream, &g);
-        if (es != ICET_OK || ee != hipSuccess || !g) {           // could not capture (a capacity grew, an unsupported call): run this call eagerly and stop trying for this key
+        // could not capture (a capacity grew, an unsupported call) or instantiate: run this call eagerly and stop trying for this key
+        if (es != ICET_OK || ee != hipSuccess || !g || hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) {
             if (g) (void)hipGraphDestroy(g);
             (void)hipGetLastError();
             slot.have_seen = false;
             return enq();
         }
-        hipGraphExec_t ge = nullptr;
-        if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); (void)hipGetLastError(); slot.have_seen = false; return enq(); }
         slot.graph = g; slot.exec = ge; slot.key = key; slot.have_graph = true;
-        HIPCHK(c, hipGraphLaunch(slot.exec, c->stream));
-        ICET_TRY(staging_mark_replay(c));
-        c->timing_valid = false;
-        return ICET_OK;
     }
-    slot.seen = key; slot.have_seen = true;
-    return enq();
+    HIPCHK(c, hipGraphLaunch(slot.exec, c->stream));
+    ICET_TRY(staging_mark_replay(c));
+    c->timing_valid = false;
+    return ICET_OK;
+}
+// THE CAPTURE STEP of every entry that can replay: `enq` run eagerly, or through `slot` under the key that `ident` (entry_key) begins.  The call's staging is laid
+// out and `cfg` is its plan: a replay runs no enqueuer and reads the staging as the layout left it, and the thresholds, which no capture may build, exist since the
+// plan was made.  allowed: the entry's own condition (a query, whose search kernels take the call's poses as arguments, is never captured; nor are dump and terms).
+template <typename Enq> static icet_status run_captured(icet_ctx* c, icet_ctx::GraphSlot& slot, const icet_params* p, const LaunchCfg& cfg, const icet_ctx::GraphKey& ident, bool allowed, Enq enq) {
+    if (!allowed || !graph_eligible(c, p, cfg.n_pairs)) return enq();
+    return run_or_replay(c, slot, graph_key_of(c, p, cfg, ident), enq);
+}
+// One half (1: scan 1, icet_keyframe_device_n; 2: scan 2, icet_register_device_n) of the call's descriptors into h_desc.  A sequential caller hands the SAME buffers
+// to a half frame after frame (include/icet_nodes.h): the pinned staging then already holds this call's halves and is left alone -- rewriting it means waiting, on
+// the HOST, for whatever replay or copy of this context still reads it, and a burst of frames (icet_node_push_many_device) would have the host wait for the device
+// twice per frame instead of running ahead.  Only what the previous call of THIS entry wrote counts (desc_kf_valid / desc_reg_valid): raw staging memory proves nothing.
+static icet_status stage_half(icet_ctx* c, int half, int32_t n_pairs, const icet_dev_scan* scan) {
+    bool& valid = half == 1 ? c->desc_kf_valid : c->desc_reg_valid;
+    bool same_desc = valid;
+    for (int k = 0; k < n_pairs && same_desc; k++) same_desc = half == 1 ? same_scan1(c->h_desc[k], scan[k]) : same_scan2(c->h_desc[k], scan[k]);
+    if (same_desc) return ICET_OK;
+    if (half == 1) c->desc_reg_valid = false;                              // (set_scan1 resets the scan-2 halves)
+    ICET_TRY(staging_wait(c));
+    for (int k = 0; k < n_pairs; k++) { if (half == 1) set_scan1(c->h_desc[k], scan[k]); else set_scan2(c->h_desc[k], scan[k]); }
+    valid = true;
+    return ICET_OK;
 }
 }  // extern "C++"
 
@@ -919,17 +935,19 @@ static icet_status solve_device_part(icet_ctx* c, const icet_params* p, int32_t 
         set_scan1(c->h_desc[s], scan1[k]); set_scan2(c->h_desc[s], scan2[k]);
     }
     if (p->runlen == 0) { c->armed_calls = 2; return write_runlen0(c, n_pairs, d_x0, d_out); }
-    if (graph_eligible(c, p, n_pairs)) {
-        ICET_TRY(ensure_thresholds(c, p->bins_theta, p->bins_phi));
-        // (the solve's last kernel raises the context's sync word: icet_sync)
-        const bool own_word = !c->done_flag && c->h_sync_word;
-        if (own_word) { if (c->armed_calls == 0) *static_cast<volatile int32_t*>(c->h_sync_word) = 0; c->done_flag = c->h_sync_word; }
-        const icet_status rs = run_or_replay(c, c->g_solve, graph_key_of(c, p, n_pairs, d_x0, d_out, nullptr, nullptr), [&]() { return enqueue(c, p, n_pairs, d_x0, d_out, nullptr); });
-        if (own_word) { c->done_flag = nullptr; c->armed_calls = (rs == ICET_OK && c->g_solve.have_graph) ? c->armed_calls + 1 : 2; }
-        return rs;
-    }
-    c->armed_calls = 2;
-    return enqueue(c, p, n_pairs, d_x0, d_out, nullptr);
+    const bool eligible = graph_eligible(c, p, n_pairs);
+    if (!eligible) c->armed_calls = 2;
+    ICET_TRY(ensure_thresholds(c, p->bins_theta, p->bins_phi));
+    // (a captured solve's last kernel raises the context's sync word: icet_sync.  The word is the plan's done_flag, and a part of the key: set before either is made)
+    const bool own_word = eligible && !c->done_flag && c->h_sync_word;
+    if (own_word) { if (c->armed_calls == 0) *static_cast<volatile int32_t*>(c->h_sync_word) = 0; c->done_flag = c->h_sync_word; }
+    const LaunchCfg cfg = make_cfg(c, p, n_pairs, lay_out_staging(c->h_desc, c->h_seg, n_pairs));
+    const icet_status rs = run_captured(c, c->g_solve, p, cfg, entry_key(icet_ctx::kEntrySolve, d_x0, d_out, nullptr), true, [&]() -> icet_status {
+        ICET_TRY(enqueue_keyframe(c, cfg, nullptr));
+        return enqueue_loop(c, p, cfg, pair_loop(c, cfg, d_x0, d_out, nullptr, false));      // (the staging went up with the keyframe)
+    });
+    if (own_word) { c->done_flag = nullptr; c->armed_calls = (rs == ICET_OK && c->g_solve.have_graph) ? c->armed_calls + 1 : 2; }
+    return rs;
 }
 
 icet_status icet_keyframe_device(icet_ctx* c, const icet_params* p, int32_t n_pairs, const icet_dev_scan* scan1) {
@@ -944,22 +962,9 @@ icet_status icet_keyframe_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     c->kf_pairs = 0; c->perm_active = false;
     icet_status s = ensure_workspace(c, p, n_pairs, tot1, 0);
     if (s != ICET_OK) return s;
-    // A sequential caller hands the SAME buffers to this half frame after frame (include/icet_nodes.h): the pinned descriptor staging then already holds
-    // this call's scan-1 halves and is left alone -- rewriting it means waiting, on the HOST, for whatever replay or copy of this context still reads it,
-    // and a burst of frames (icet_node_push_many_device) would have the host wait for the device twice per frame instead of running ahead
-    bool same_desc = c->desc_kf_valid;                                     // (only what the previous call of THIS entry wrote counts: raw staging memory proves nothing)
-    for (int k = 0; k < n_pairs && same_desc; k++) same_desc = same_scan1(c->h_desc[k], scan1[k]);
-    if (!same_desc) {
-        c->desc_reg_valid = false;                                         // the scan-2 halves are reset below
-        ICET_TRY(staging_wait(c));
-        for (int k = 0; k < n_pairs; k++) set_scan1(c->h_desc[k], scan1[k]);
-        c->desc_kf_valid = true;
-    }
-    if (graph_eligible(c, p, n_pairs)) {
-        s = ensure_thresholds(c, p->bins_theta, p->bins_phi);
-        if (s == ICET_OK) s = run_or_replay(c, c->g_keyframe, graph_key_of(c, p, n_pairs, d_rows, nullptr, nullptr, (const void*)1), [&]() { return enqueue_keyframe(c, p, n_pairs, nullptr, d_rows); });
-    } else s = enqueue_keyframe(c, p, n_pairs, nullptr, d_rows);
-    if (s != ICET_OK) return s;
+    ICET_TRY(stage_half(c, 1, n_pairs, scan1));
+    LaunchCfg cfg; ICET_TRY(plan_pairs(c, p, n_pairs, &cfg));
+    ICET_TRY(run_captured(c, c->g_keyframe, p, cfg, entry_key(icet_ctx::kEntryKeyframe, nullptr, nullptr, d_rows), true, [&]() { return enqueue_keyframe(c, cfg, nullptr, d_rows); }));
     c->kf_pairs = n_pairs; c->kf_params = *p;
     return ICET_OK;
 }
@@ -977,21 +982,14 @@ icet_status icet_register_device_n(icet_ctx* c, const icet_params* p, int32_t n_
     if (p->runlen == 0) return write_runlen0(c, n_pairs, d_x0, d_out);
     icet_status s = ensure_workspace(c, p, n_pairs, 0, tot2);              // only the scan-2 overflow list can grow here: the keyframe tables stay
     if (s != ICET_OK) return s;
-    bool same_desc = c->desc_reg_valid;                                    // (see icet_keyframe_device_n)
-    for (int k = 0; k < n_pairs && same_desc; k++) same_desc = same_scan2(c->h_desc[k], scan2[k]);
-    if (!same_desc) {
-        ICET_TRY(staging_wait(c));
-        for (int k = 0; k < n_pairs; k++) set_scan2(c->h_desc[k], scan2[k]);
-        c->desc_reg_valid = true;
-    }
-    s = ensure_thresholds(c, p->bins_theta, p->bins_phi);                 // (a keyframe store's call on another grid may have rebuilt them since the keyframe was parked)
-    if (s != ICET_OK) return s;
-    auto enq = [&]() -> icet_status {
+    ICET_TRY(stage_half(c, 2, n_pairs, scan2));
+    LaunchCfg cfg; ICET_TRY(plan_pairs(c, p, n_pairs, &cfg));                            // (the thresholds: a keyframe store's call on another grid may have rebuilt them since the keyframe was parked)
+    return run_captured(c, c->g_loop, p, cfg, entry_key(icet_ctx::kEntryLoop, d_x0, d_out, d_rows), true, [&]() -> icet_status {
         if (c->prologue) HIPCHK(c, c->prologue(c->prologue_user, c->stream));
-        return enqueue_loop(c, p, n_pairs, d_x0, d_out, nullptr, true, nullptr, nullptr, d_rows);
-    };
-    if (graph_eligible(c, p, n_pairs)) return run_or_replay(c, c->g_loop, graph_key_of(c, p, n_pairs, d_x0, d_out, d_rows, (const void*)2), enq);
-    return enq();
+        LoopCall L = pair_loop(c, cfg, d_x0, d_out, nullptr, true);       // (the scan-2 halves arrived after the keyframe call: the staging goes up again)
+        L.d_rows = d_rows;
+        return enqueue_loop(c, p, cfg, L);
+    });
 }
 
 }  // extern "C"
@@ -1030,29 +1028,29 @@ icet_status icet::register_indexed(icet_ctx* c, const icet_params* p, int32_t n_
         c->h_kf_of[r] = kf_index[r];
     }
     c->h_kf_of[n_regs] = 0;
-    if (mode == kIdxRegister) {
-        auto enq = [&]() { return enqueue_indexed(c, p, n_regs, d_x0, d_out, nullptr, -1, src, dev); };
-        // a replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved;
-        // the keyframe source: the context's tables, or a store's identity and generation)
-        if (!dev && graph_eligible(c, p, n_regs)) return run_or_replay(c, c->g_indexed, graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>((intptr_t)c->ws_gen), (const void*)3, c->h_desc_reg,
-                                                                  src ? src->id : 0, src ? src->gen : 0), enq);
-        return enq();
-    }
-    if (mode == kIdxDump) return enqueue_indexed(c, p, n_regs, d_x0, nullptr, nullptr, 0, src, dev, d_dump);      // (never captured)
-    if (mode == kIdxTerms) return enqueue_indexed(c, p, n_regs, d_x0, d_out, nullptr, 0, src, dev, d_dump, terms);      // (never captured)
-    // scored calls: runlen == 0 scores X0 (results as the unscored call writes them); score-only calls score d_x0 without iterating
-    const bool no_iters = mode == kIdxScoreOnly || p->runlen == 0;
-    auto enq = [&]() -> icet_status {
-        if (mode == kIdxScored && p->runlen == 0) { const icet_status ws = write_runlen0(c, n_regs, d_x0, d_out); if (ws != ICET_OK) return ws; }
-        return enqueue_indexed(c, p, n_regs, d_x0, d_out, d_score, no_iters ? 0 : p->runlen, src, dev);
-    };
-    if (!dev && graph_eligible(c, p, n_regs)) {                           // (a query is never captured: its search kernels take this call's poses as arguments)
-        // slots and keys of their own: a scored call never replays an unscored call's graph, nor the reverse (the mode is a bit of the key as well)
-        const intptr_t tag = (intptr_t)c->ws_gen | ((intptr_t)mode << 56);
-        return run_or_replay(c, mode == kIdxScored ? c->g_scored : c->g_score,
-                             graph_key_of(c, p, n_regs, d_x0, d_out, reinterpret_cast<const void*>(tag), d_score, c->h_desc_reg, src ? src->id : 0, src ? src->gen : 0), enq);
-    }
-    return enq();
+    // (no segment table in the layout: the keyframe index travels in its place.  A query's staging holds an occupied slot and the scans' full row counts: the launch
+    // geometry is sized from those, as in icet_register_device_n)
+    const LaunchCfg cfg = make_cfg(c, p, n_regs, lay_out_staging(c->h_desc_reg, nullptr, n_regs));
+    const Workspace& w = c->w; LoopCall L;
+    L.hd = c->h_desc_reg; L.hs = c->h_kf_of; L.seg_words = (size_t)n_regs + 1; L.upload = true;
+    L.view = w; L.view.desc = w.desc_reg; L.view.seg_off = w.kf_of; L.kf_of = w.kf_of;
+    if (src) { L.view.hotS = src->hotS; L.view.fitS = src->fitS; L.view.slot_of_voxel = src->slot_of_voxel; L.view.n_slots = src->n_slots; }      // (a store's rows: h_kf_of then holds slot indices)
+    L.d_x0 = d_x0; L.d_out = d_out; L.plain = L.own_timing = L.init_on_copy = true;
+    if (dev) { L.d_rows = dev->rows; L.d_kf_of = dev->kf_of; }
+    // scored calls: runlen == 0 scores X0 (results as the unscored call writes them); score-only, dump and terms take d_x0 without iterating
+    L.iters = (mode == kIdxRegister || mode == kIdxScored) ? p->runlen : 0;
+    L.tail = mode == kIdxRegister ? kTailNone : mode == kIdxDump ? kTailDump : mode == kIdxTerms ? kTailTerms : kTailScore;
+    L.d_score = d_score; L.d_dump = d_dump; L.terms = terms;
+    // A replay re-reads the staging -- descriptors AND keyframe index -- when it runs; the key names what the launches themselves take (ws_gen: any buffer moved; the
+    // keyframe source: the context's tables, or a store's identity and generation).  Scored and score-only calls have slots of their own, and the mode is a part of
+    // the key: a scored call never replays an unscored call's graph, nor the reverse.  A query (dev), dump and terms are never captured.
+    icet_ctx::GraphKey ident = entry_key(icet_ctx::kEntryIndexed, d_x0, d_out, d_score);
+    ident.mode = mode; ident.ws_gen = c->ws_gen; ident.src_id = src ? src->id : 0; ident.src_gen = src ? src->gen : 0;
+    icet_ctx::GraphSlot& slot = mode == kIdxScored ? c->g_scored : mode == kIdxScoreOnly ? c->g_score : c->g_indexed;
+    return run_captured(c, slot, p, cfg, ident, !dev && mode != kIdxDump && mode != kIdxTerms, [&]() -> icet_status {
+        if (mode == kIdxScored && p->runlen == 0) ICET_TRY(write_runlen0(c, n_regs, d_x0, d_out));
+        return enqueue_loop(c, p, cfg, L);
+    });
 }
 extern "C" {
 
@@ -1209,13 +1207,10 @@ icet_status icet_solve_batch(icet_ctx* c, const icet_params* p, int32_t n_pairs,
     if (p->runlen == 0) s = write_runlen0(c, n_pairs, dx0, c->d_out);
     else {
         c->kf_pairs = 0; c->perm_active = false;
-        s = enqueue_keyframe(c, p, n_pairs, nullptr);
-        if (s == ICET_OK) {
-            hipError_t e = upload_staged(d2.data(), scan2, n_pairs, c->st_copy);
-            if (e == hipSuccess) e = hipEventRecord(c->ev_s2, c->st_copy);
-            if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->st_copy); c->err = std::string("scan-2 upload: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
-            s = enqueue_loop(c, p, n_pairs, dx0, c->d_out, nullptr, false, nullptr, c->ev_s2);
-        }
+        LaunchCfg cfg; s = plan_pairs(c, p, n_pairs, &cfg);
+        if (s == ICET_OK) s = enqueue_keyframe(c, cfg, nullptr);
+        if (s == ICET_OK) s = upload_scan2_beside(c, "scan-2 upload", [&] { return upload_staged(d2.data(), scan2, n_pairs, c->st_copy); }, [] { return hipSuccess; });
+        if (s == ICET_OK) s = enqueue_loop(c, p, cfg, pair_loop(c, cfg, dx0, c->d_out, nullptr, false, c->ev_s2));
     }
     if (s != ICET_OK) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->st_copy); return s; }
     HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(float) * 48 * n_pairs, hipMemcpyDeviceToHost, c->stream));
@@ -1306,32 +1301,30 @@ icet_status icet_solve_begin(icet_ctx* c, const icet_params* p, const float* sca
             if (!want_pts2 && !want_side2) ad.xf_last = nullptr;
         }
         c->kf_pairs = 0; c->perm_active = false;
-        st = enqueue_keyframe(c, p, 1, aux ? &ad : nullptr);
-        if (st == ICET_OK && want_side1) {                                     // points1Spherical / pointIndices1 from the tables the keyframe build has just left
-            const LaunchCfg scfg = make_cfg(c, p, 1);
-            HIPCHK(c, launch_side_scan1(c->w, scfg, c->d_sph1, c->d_idx1, c->stream));
-        }
+        LaunchCfg cfg; st = plan_pairs(c, p, 1, &cfg);
+        if (st == ICET_OK) st = enqueue_keyframe(c, cfg, aux ? &ad : nullptr);
+        if (st == ICET_OK && want_side1)                                       // points1Spherical / pointIndices1 from the tables the keyframe build has just left
+            HIPCHK(c, launch_side_scan1(c->w, cfg, c->d_sph1, c->d_idx1, c->stream));
+        if (st == ICET_OK) st = upload_scan2_beside(c, "scan-2 upload / table download", [&] { return upload_scan(c->d_stage2, l2, scan2, n2, ld2, c->st_copy); }, [&] {
+            if (!q.kf_tables) return hipSuccess;
+            // the keyframe tables are final now: they travel to the host on the copy stream while the loop iterates
+            hipError_t e = hipEventRecord(c->ev_kf, c->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(c->st_copy, c->ev_kf, 0);
+            if (e == hipSuccess) e = hipMemcpyAsync(c->h_pack + L.bounds, c->d_pack + L.bounds, (L.kf_end - L.bounds) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st_copy);
+            if (e == hipSuccess) e = hipEventRecord(c->ev_kfd, c->st_copy);
+            return e;
+        });
         if (st == ICET_OK) {
-            // scan 2 goes up on the copy stream while the keyframe kernels enqueued above run; the loop waits for ev_s2
-            hipError_t e = upload_scan(c->d_stage2, l2, scan2, n2, ld2, c->st_copy);
-            if (e == hipSuccess) e = hipEventRecord(c->ev_s2, c->st_copy);
-            if (e == hipSuccess && q.kf_tables) {
-                // the keyframe tables are final now: they travel to the host on the copy stream while the loop iterates
-                e = hipEventRecord(c->ev_kf, c->stream);
-                if (e == hipSuccess) e = hipStreamWaitEvent(c->st_copy, c->ev_kf, 0);
-                if (e == hipSuccess) e = hipMemcpyAsync(c->h_pack + L.bounds, c->d_pack + L.bounds, (L.kf_end - L.bounds) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st_copy);
-                if (e == hipSuccess) e = hipEventRecord(c->ev_kfd, c->st_copy);
-            }
-            if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->st_copy); c->err = std::string("scan-2 upload / table download: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
-            st = enqueue_loop(c, p, 1, c->h_x0, d_res, aux ? &ad : nullptr, false, q.pts2_dev ? c->h_pts2 : nullptr, c->ev_s2);
+            LoopCall lc = pair_loop(c, cfg, c->h_x0, d_res, aux ? &ad : nullptr, false, c->ev_s2);
+            lc.pts2_out = q.pts2_dev ? c->h_pts2 : nullptr;
+            st = enqueue_loop(c, p, cfg, lc);
             if (st == ICET_OK) HIPCHK(c, hipMemcpyAsync(c->h_pack + L.out, c->d_pack + L.out, (aux ? L.small_end : 48) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         }
         if (st == ICET_OK && want_side2) {
             // points2 / points2Spherical / the rows' voxels of the LAST fitScan2: one kernel behind the loop, with the transform record that
             // iteration used (it reads the scan the loop read: the round-tripped copy under ICET_FLAG_ROUNDTRIP_SCAN2)
-            LaunchCfg scfg = make_cfg(c, p, 1);
-            Workspace wl = c->w; if (scfg.rt2) wl.desc = c->w.desc_rt;
-            HIPCHK(c, launch_side_scan2(wl, scfg, ad.xf_last, c->d_pts2, c->d_sph2, c->d_vox2, c->stream));
+            Workspace wl = c->w; if (cfg.rt2) wl.desc = c->w.desc_rt;
+            HIPCHK(c, launch_side_scan2(wl, cfg, ad.xf_last, c->d_pts2, c->d_sph2, c->d_vox2, c->stream));
         }
         if (st == ICET_OK && q.tail_ints)
             HIPCHK(c, hipMemcpyAsync(c->h_pack + L.n1_raw, c->d_pack + L.n1_raw, (L.ints_end - L.n1_raw) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));

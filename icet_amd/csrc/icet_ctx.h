@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace icet {
@@ -87,8 +88,21 @@ struct icet_ctx {
     hipEvent_t ev_desc = nullptr; bool desc_in_flight = false;   // the last copy or kernel that read the pinned descriptor staging (staging_mark_read / staging_wait, below: nobody else touches them)
     // Small device batches whose launch geometry repeats call after call are replayed from a captured hipGraph (option "graph"): the ~33
     // launches of a single-pair solve then cost one hipGraphLaunch on the host, and the command processor runs them back to back.
-    struct GraphKey { int64_t v[47]; };                        // every LaunchCfg field + the pointers the launches take + the prologue's key + the keyframe source (graph_key_of)
-    struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false; };
+    // What a captured graph depends on apart from the staging it re-reads (graph_key_of, icet_capi.hip): two calls with equal keys enqueue the same launches with
+    // the same arguments.  Compared with memcmp: value-initialised, every member 8 bytes wide, no padding (the static_assert below the struct).
+    enum GraphEntry : int64_t { kEntrySolve, kEntryKeyframe, kEntryLoop, kEntryIndexed };      // icet_solve_batch_device, icet_keyframe_device_n, icet_register_device_n, register_indexed
+    struct GraphKey {
+        int64_t entry, mode;                                   // GraphEntry; the IndexedMode of an indexed call (0 elsewhere)
+        const void* x0; const void* out; const void* extra;    // the caller's argument pointers; extra: d_rows of the two halves, d_score of a scored call
+        int64_t ws_gen, src_id, src_gen;                       // indexed calls: any workspace buffer moved; the keyframe tables -- 0 / 0 the context's own, else a store's id and generation
+        int64_t prologue_key; const void* done_flag; int64_t flags;      // the prologue's key (0: none), the word the last solve raises, icet_params::flags
+        const void* ws[10];                                    // desc, thr, lut, r1, counts, near_over, acc, fit_items, sort_tmp, tile_vr
+        int64_t launch[29];                                    // what the launches take of the plan (launch_key_of, icet_capi.hip)
+    };
+    struct GraphSlot {
+        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false;
+        void reset() { if (have_graph) { (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph); } graph = nullptr; exec = nullptr; have_graph = false; }      // (have_seen stays: the key may be captured again)
+    };
     int pg_solver = 0;                                         // icet_pose_graph_optimize: 0 conjugate gradients, 1 the direct solve, 2 auto (option "pg_solver")
     bool capturing = false; int graph_mode = -1;               // -1: replay batches of <= 8 pairs whose launch key repeats; 0 never; 1 same as -1
     GraphSlot g_solve, g_keyframe, g_loop, g_indexed;          // the whole solve (icet_solve_batch_device), its two halves (icet_keyframe_device_n / icet_register_device_n), indexed registrations
@@ -119,6 +133,7 @@ struct icet_ctx {
         icet::BufferGroup out, stage1, stage2, pack, pts2, side1, side2, score, sel, sync_word;
     } mem;
 };
+static_assert(std::has_unique_object_representations_v<icet_ctx::GraphKey> && sizeof(icet_ctx::GraphKey) == 8 * (21 + 29), "GraphKey is compared with memcmp: 8-byte integers and pointers, no padding");
 
 // A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
 // keyframe side (row stride V; (V + 1) & ~1 for slot_of_voxel), on the borrowed context's device.  A put builds on the context and parks into rows of its own

@@ -1,5 +1,5 @@
 // tests/cpp/test_staging.cpp -- the HIP-free rules of icet_amd/csrc/icet_staging.h on the host: the layout of host scans in a staging buffer, the two halves
-// of a pair descriptor, the unpacking of n x 48 result floats and the check of a call's device scans.
+// of a pair descriptor, the layout of a call's descriptors (offsets, segment table, totals), the unpacking of n x 48 result floats and the check of a call's device scans.
 // Build: g++ -std=c++17 -I <repo root> (also with -fsanitize=address,undefined).  Prints one line per case and OK.
 #include "icet_amd/csrc/icet_staging.h"
 
@@ -51,7 +51,7 @@ void halves() {
     CHECK(same_scan1(d, s1) && !same_scan2(d, s2));
     set_scan2(d, s2);
     CHECK(d.s2 == b && d.n2 == 90 && d.ld2 == 96 && same_scan1(d, s1) && same_scan2(d, s2));
-    d.off1 = 7; d.off2 = 9;                                // (make_cfg's; a new scan 2 leaves them)
+    d.off1 = 7; d.off2 = 9;                                // (lay_out_staging's; a new scan 2 leaves them)
     set_scan2(d, s2);
     CHECK(d.off1 == 7 && d.off2 == 9);
     // one field apart
@@ -64,6 +64,70 @@ void halves() {
     set_scan1(d, icet_dev_scan{nullptr, 0, 0}); set_scan2(d, s2);
     CHECK(d.s1 == nullptr && d.n1 == 0 && d.ld1 == 0 && same_scan2(d, s2));
     std::printf("halves: set, same, one field apart, reset\n");
+}
+
+// lay_out_staging: the offsets, the n + 1 segment words and the totals, against values worked out by hand.
+bool totals_are(const StagingTotals& t, int64_t tot1, int64_t tot2, int32_t mx1, int32_t mx2, int32_t v4) {
+    return t.total_n1 == tot1 && t.total_n2 == tot2 && t.max_n1 == mx1 && t.max_n2 == mx2 && t.vec4_ok == v4;
+}
+void staging_layout() {
+    alignas(16) static float a[16], b[16];                 // b + 1 .. b + 3 are not 16-byte aligned
+    {   // no pair: one segment word, nothing else touched (exact sizes: a write past either ends the sanitised run)
+        std::vector<int32_t> hs(1, -1);
+        CHECK(totals_are(lay_out_staging(nullptr, hs.data(), 0), 0, 0, 0, 0, 1) && hs[0] == 0);
+        CHECK(totals_are(lay_out_staging(nullptr, nullptr, 0), 0, 0, 0, 0, 1));
+        std::printf("staging layout: no pair\n");
+    }
+    {   // one pair
+        std::vector<PairDesc> d(1); std::vector<int32_t> hs(2, -1);
+        set_scan1(d[0], icet_dev_scan{a, 100, 128}); set_scan2(d[0], icet_dev_scan{b, 90, 96});
+        d[0].off1 = 7; d[0].off2 = 9;
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 1), 100, 90, 100, 90, 1));
+        CHECK(d[0].off1 == 0 && d[0].off2 == 0 && hs[0] == 0 && hs[1] == 100);
+        CHECK(d[0].s1 == a && d[0].n1 == 100 && d[0].ld1 == 128 && d[0].s2 == b && d[0].n2 == 90 && d[0].ld2 == 96);      // nothing else written
+        std::printf("staging layout: one pair\n");
+    }
+    // three pairs, the middle one with both scans empty (null pointers, which count as aligned)
+    auto three = [&](std::vector<PairDesc>& d) {
+        d.assign(3, PairDesc{});
+        set_scan1(d[0], icet_dev_scan{a, 10, 64});  set_scan2(d[0], icet_dev_scan{b, 7, 8});
+        set_scan1(d[1], icet_dev_scan{nullptr, 0, 0}); set_scan2(d[1], icet_dev_scan{nullptr, 0, 0});
+        set_scan1(d[2], icet_dev_scan{a, 5, 64});   set_scan2(d[2], icet_dev_scan{b + 4, 11, 12});
+    };
+    {
+        std::vector<PairDesc> d; three(d); std::vector<int32_t> hs(4, -1);
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 3), 15, 18, 10, 11, 1));
+        CHECK(d[0].off1 == 0 && d[1].off1 == 10 && d[2].off1 == 10 && d[0].off2 == 0 && d[1].off2 == 7 && d[2].off2 == 7);
+        CHECK(hs[0] == 0 && hs[1] == 10 && hs[2] == 10 && hs[3] == 15);
+        // laying out twice gives the same words
+        const std::vector<PairDesc> d_once = d; const std::vector<int32_t> hs_once = hs;
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 3), 15, 18, 10, 11, 1));
+        CHECK(std::memcmp(d.data(), d_once.data(), sizeof(PairDesc) * 3) == 0 && hs == hs_once);
+        // no segment table (an indexed call keeps its keyframe index there): the same offsets and totals
+        std::vector<PairDesc> e; three(e);
+        CHECK(totals_are(lay_out_staging(e.data(), nullptr, 3), 15, 18, 10, 11, 1));
+        CHECK(std::memcmp(e.data(), d.data(), sizeof(PairDesc) * 3) == 0);
+        std::printf("staging layout: three pairs, an empty one in the middle; twice; without a segment table\n");
+        // a scan-2 pointer, then a leading dimension, that is not 16-byte aligned, in the LAST pair only: everything as before, vec4_ok 0
+        set_scan2(d[2], icet_dev_scan{b + 1, 11, 12});
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 3), 15, 18, 10, 11, 0) && hs == hs_once && d[2].off1 == 10 && d[2].off2 == 7);
+        set_scan2(d[2], icet_dev_scan{b + 4, 11, 13});
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 3), 15, 18, 10, 11, 0) && hs == hs_once);
+        set_scan2(d[2], icet_dev_scan{b + 4, 11, 12});
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 3), 15, 18, 10, 11, 1));
+        std::printf("staging layout: unaligned scan 2 in the last pair\n");
+        // a new scan 1 in the first pair resets its offsets and its scan-2 half: the next layout moves everything behind it
+        set_scan1(d[0], icet_dev_scan{a, 12, 64});
+        CHECK(d[0].off1 == 0 && d[0].off2 == 0 && d[0].n2 == 0);
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 3), 17, 11, 12, 11, 1));
+        CHECK(d[0].off1 == 0 && d[1].off1 == 12 && d[2].off1 == 12 && d[0].off2 == 0 && d[1].off2 == 0 && d[2].off2 == 0);
+        CHECK(hs[0] == 0 && hs[1] == 12 && hs[2] == 12 && hs[3] == 17);
+        // ... and in the LAST pair, whose own offsets the reset zeroed: the layout puts them back
+        set_scan1(d[2], icet_dev_scan{a, 5, 64});
+        CHECK(d[2].off1 == 0 && d[2].off2 == 0);
+        CHECK(totals_are(lay_out_staging(d.data(), hs.data(), 3), 17, 0, 12, 0, 1) && d[2].off1 == 12 && d[2].off2 == 0 && hs[3] == 17);
+        std::printf("staging layout: after a set_scan1 reset\n");
+    }
 }
 
 void unpack() {
@@ -105,6 +169,7 @@ void scans() {
 int main() {
     layout();
     halves();
+    staging_layout();
     unpack();
     scans();
     std::printf("OK\n");

@@ -1,5 +1,5 @@
 """The HIP-free rules around the context's staging (icet_amd/csrc/icet_staging.h) on the host: tests/cpp/test_staging.cpp lays host scans out in a staging buffer,
-sets and compares the halves of a pair descriptor, unpacks n x 48 result floats and checks device scans.  No GPU, nothing loaded into Python."""
+sets and compares the halves of a pair descriptor, lays a call's descriptors out (offsets, segment table, totals), unpacks n x 48 result floats and checks device scans.  No GPU, nothing loaded into Python."""
 import os
 import subprocess
 
@@ -22,3 +22,4 @@ def test_staging_standalone_under_sanitizers(tmp_path):
     lines = outs["plain"].decode().splitlines()
     assert sum(l.startswith("layout ") for l in lines) == 7 and sum(l.startswith("scan check: ") for l in lines) == 4
     assert sum(l.startswith("unpack ") for l in lines) == 2 and sum(l.startswith("halves: ") for l in lines) == 1
+    assert sum(l.startswith("staging layout: ") for l in lines) == 5
