@@ -128,7 +128,7 @@ icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs,
             c->kf_pairs = 0;
             w.cap_n1 = 0, w.cap_fit_items = 0, g.release();
             HIPCHK(c, g.device(w.r1, n)); HIPCHK(c, g.device(w.cart1, (size_t)3 * n));
-            HIPCHK(c, g.device(w.key64A, n)); HIPCHK(c, g.device(w.key64B, n)); HIPCHK(c, g.device(w.bin16, n)); HIPCHK(c, g.device(w.binpos, n)); HIPCHK(c, g.device(w.bkt, n));
+            HIPCHK(c, g.device(w.key64A, n)); HIPCHK(c, g.device(w.key64B, n)); HIPCHK(c, g.device(w.bin16, n + 8));      /* (+ 8: k_rs_bucket_sort reads aligned groups of eight words) */ HIPCHK(c, g.device(w.binpos, n)); HIPCHK(c, g.device(w.bkt, n));
             HIPCHK(c, g.device(w.keyA, n)); HIPCHK(c, g.device(w.keyB, n)); HIPCHK(c, g.device(w.valA, n)); HIPCHK(c, g.device(w.valB, n));
             HIPCHK(c, g.device(w.pred, n)); HIPCHK(c, g.device(w.src, n));
             w.cap_n1 = n;
@@ -399,15 +399,19 @@ LaunchCfg make_cfg(const icet_ctx* c, const icet_params* p, int32_t n_pairs, con
         cfg.kf_pts_per_thread = kKfMaxPtsPerThread / 2;
     cfg.kf_chunks = (mx1 + 256 * cfg.kf_pts_per_thread - 1) / (256 * cfg.kf_pts_per_thread);
     if (cfg.kf_chunks < 1) cfg.kf_chunks = 1;
+    // packed rows (LaunchCfg::packed_rows): the layout of pred[] / src[] for this call -- whenever the largest rank and a voxel word fit 32 bits together
+    // (17 + 13 on 75 x 24 with scans up to 131 072 rows), unless the option says no; the library sort's inverse-permutation pass writes plain ranks
+    cfg.row_shift = packed_row_shift(mx1); cfg.id_bits = bits_of((int64_t)cfg.V - 1);
+    cfg.packed_rows = (c->tune.packed_rows != 0 && !cfg.use_library_sort && packed_row_bits(mx1, cfg.V) <= 32) ? 1 : 0;
     return cfg;
 }
 // The plan's part of a graph key (icet_ctx::GraphKey::launch): what grids, LDS sizes, template choices and by-value arguments are made from.  Not in it: what an
 // option's setter un-sees the keys for (fuse_solve, gn_cond_bound) and what no captured call uses (the keep list, batch stages).
-void launch_key_of(const LaunchCfg& k, int64_t (&out)[29]) {
+void launch_key_of(const LaunchCfg& k, int64_t (&out)[30]) {
     auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return (int64_t)i; };
     const int64_t v[] = {k.T, k.P, k.V, k.n, k.runlen, bits(k.thresh), bits(k.buff), k.n_pairs, k.max_n1, k.max_n2, k.total_n1, k.lds_slots, k.acc_min_pts_per_thread,
                          k.acc_target_blocks, k.kf_chunks, k.kf_pts_per_thread, k.use_library_sort, k.vec4_ok, k.true_sort, k.force_exact, k.rs_cap, k.rs_max_cell,
-                         k.exec_bits_lds, k.exec_pairwise, k.lds_rank, k.reject_moving, k.half_gap, k.rt2, k.ref_w};
+                         k.exec_bits_lds, k.exec_pairwise, k.lds_rank, k.reject_moving, k.half_gap, k.rt2, k.ref_w, k.packed_rows};
     static_assert(sizeof(v) == sizeof(out), "GraphKey::launch");
     std::memcpy(out, v, sizeof(v));
 }
@@ -422,6 +426,11 @@ icet_status plan_pairs(icet_ctx* c, const icet_params* p, int32_t n_pairs, Launc
 icet_status enqueue_keyframe(icet_ctx* c, const LaunchCfg& cfg, const AuxDev* aux, const int32_t* d_counts1 = nullptr) {
     Workspace& w = c->w;
     const int32_t n_pairs = cfg.n_pairs;
+    if (c->tune.packed_rows > 0 && !cfg.packed_rows) {
+        c->err = "option \"packed_rows\" is 1, but a rank and a voxel word of this call do not fit 32 bits together (" + std::to_string(packed_row_bits(cfg.max_n1, cfg.V)) + " bits), or the library sort is on";
+        return ICET_ERR_UNSUPPORTED;
+    }
+    c->kf_row_mask = packed_row_mask(cfg);
     {
         const size_t need = (size_t)n_pairs * cfg.kf_chunks * (cfg.V > kRankSortMaxBuckets ? cfg.V : kRankSortMaxBuckets);
         if (need > w.cap_counts) {
@@ -1422,6 +1431,7 @@ icet_status icet_debug_fetch(icet_ctx* c, int32_t what, void* out, int64_t count
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, src, (size_t)count * elem, hipMemcpyDeviceToHost));
+    if (what == 3) { uint32_t* o = static_cast<uint32_t*>(out); for (int64_t i = 0; i < count; i++) o[i] &= c->kf_row_mask; }      // packed rows: the rows without their voxel words
     return ICET_OK;
 }
 
@@ -1512,6 +1522,7 @@ icet_status icet_set_option(icet_ctx* c, const char* name, double value) {
     else if (k == "rs_max_cell") t.rs_max_cell = iv < 0 ? 0 : iv;
     else if (k == "exec_bits_lds") t.exec_bits_lds = iv != 0;
     else if (k == "lds_rank") t.lds_rank = iv < 0 ? -1 : (iv != 0);
+    else if (k == "packed_rows") t.packed_rows = iv < 0 ? -1 : (iv != 0);      // (1: a keyframe call whose shapes do not fit is refused, enqueue_keyframe)
     else if (k == "exec_pairwise") t.exec_pairwise = iv < 0 ? -1 : (iv != 0);
     else if (k == "fuse_solve") { t.fuse_solve = iv < 0 ? -1 : (iv != 0); c->g_solve.have_seen = c->g_keyframe.have_seen = c->g_loop.have_seen = false; }
     else if (k == "keep") t.keep = iv != 0;

@@ -45,6 +45,7 @@ struct icet_ctx {
     int32_t kf_pairs = 0; icet_params kf_params{};      // a keyframe parked by icet_keyframe_device (0 pairs = none)
     int max_lds = 160 * 1024;       // hipDeviceAttributeMaxSharedMemoryPerBlock of the device
     int lds_rank_ok = 0;            // this device passed lds_rank_selftest (icet_create)
+    uint32_t kf_row_mask = 0xFFFFFFFFu;   // the row's bits of a word of w.src as the last keyframe build left it (packed rows, LaunchCfg::packed_rows): icet_debug_fetch hands out plain rows
     std::string err;
     // host staging (pinned) for descriptors and results
     icet::PairDesc* h_desc = nullptr; int32_t* h_seg = nullptr; int32_t h_cap_pairs = 0;
@@ -97,7 +98,7 @@ struct icet_ctx {
         int64_t ws_gen, src_id, src_gen;                       // indexed calls: any workspace buffer moved; the keyframe tables -- 0 / 0 the context's own, else a store's id and generation
         int64_t prologue_key; const void* done_flag; int64_t flags;      // the prologue's key (0: none), the word the last solve raises, icet_params::flags
         const void* ws[10];                                    // desc, thr, lut, r1, counts, near_over, acc, fit_items, sort_tmp, tile_vr
-        int64_t launch[29];                                    // what the launches take of the plan (launch_key_of, icet_capi.hip)
+        int64_t launch[30];                                    // what the launches take of the plan (launch_key_of, icet_capi.hip)
     };
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false;
@@ -133,7 +134,7 @@ struct icet_ctx {
         icet::BufferGroup out, stage1, stage2, pack, pts2, side1, side2, score, sel, sync_word;
     } mem;
 };
-static_assert(std::has_unique_object_representations_v<icet_ctx::GraphKey> && sizeof(icet_ctx::GraphKey) == 8 * (21 + 29), "GraphKey is compared with memcmp: 8-byte integers and pointers, no padding");
+static_assert(std::has_unique_object_representations_v<icet_ctx::GraphKey> && sizeof(icet_ctx::GraphKey) == 8 * (21 + 30), "GraphKey is compared with memcmp: 8-byte integers and pointers, no padding");
 
 // A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
 // keyframe side (row stride V; (V + 1) & ~1 for slot_of_voxel), on the borrowed context's device.  A put builds on the context and parks into rows of its own

@@ -24,6 +24,11 @@ constexpr double kTwoPi = 6.283185307179586476925286766559;      // == 2.0 * M_P
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kTwoPiTail = 2.4492935982947064e-16;             // (exact 2 pi) - kTwoPi
 
+// A row's voxel word as bin16[] holds it (id in 14 bits, kRowNearBit, kRowZeroBit) <-> as packed rows carry it (LaunchCfg::packed_rows): the id in
+// id_bits, the near flag and the zero flag right above it -- id_bits + 2 bits in all.
+__device__ __forceinline__ uint32_t pack_voxel_word(uint32_t wd, int id_bits) { return (wd & kRowBinMask) | ((wd >> 14) << id_bits); }
+__device__ __forceinline__ uint32_t unpack_voxel_word(uint32_t pw, int id_bits) { return (pw & ((1u << id_bits) - 1u)) | ((pw >> id_bits) << 14); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -192,6 +192,7 @@ struct Tuning {
     int rs_cap = 0;               // LDS rows of the per-bucket sort (0 = from the largest scan)
     int rs_max_cell = 24;         // per-bucket counting sort: a cell above this many rows sends the bucket to the radix sort (0: always)
     int exec_bits_lds = 1;        // k_scramble_src keeps the pair's swap-loop bit table in LDS (0: reads it from memory, the path of scans above ~0.75 M rows)
+    int packed_rows = -1;         // pred[] / src[] carry each row's voxel word in their spare bits (LaunchCfg::packed_rows): -1 when rank and word fit 32 bits, 0 never, 1 required (a call whose shapes do not fit is refused)
     int lds_rank = -1;            // the stable multi-splits take a row's rank from the value its LDS atomic hands back (1 / -1: if this device passed lds_rank_selftest; 0: ballots per id bit)
     int fuse_solve = ICET_FUSE_DEFAULT;   // small batches: the pair's last point-pass block runs the solve in the same launch (1 / -1), or one k_gn_solve launch per iteration (0)
     int exec_pairwise = -1;       // "did step v execute": one block per pair in index order with the bit table in LDS (k_exec_flags_pair) 1, chain walks (k_exec_flags) 0, by batch size -1
@@ -230,6 +231,9 @@ struct LaunchCfg {
     int rt2 = 0;                      // ICET_FLAG_ROUNDTRIP_SCAN2 (parity-study option)
     int ref_w = 1;                    // per-voxel W by the reference's float COD (default); 0: ICET_FLAG_DOUBLE_W, in double with an eigenvalue rank rule
     int lds_rank = 0;                 // Tuning::lds_rank, resolved against the context's self-test
+    // Packed rows (Tuning::packed_rows resolved for this launch; icet_keyframe.hip, rank_of): 1 = a word of pred[] / src[] is a rank / row in its low row_shift bits with the
+    // voxel word (the id, then the near flag, then the zero flag) of a row above them; binpos[] is then unused.  Possible when packed_row_bits(max_n1, V) <= 32.
+    int packed_rows = 0, row_shift = 0, id_bits = 0;     // id_bits: bits of a voxel id, bits_of(V - 1) (pack_voxel_word, icet_device_common.h)
     int keep = 0, keep_from = 1;      // Tuning::keep resolved for this launch (batch size, flags), Tuning::keep_from
     float keep_bt = 0.f, keep_br = 0.f, keep_check_scale = 1.f;   // Tuning::keep_budget_t / _r / keep_check_scale
     float gn_cond_bound2 = 6.25e10f;     // Tuning::gn_cond_bound squared: k_gn_solve's Cholesky route needs |A|_F |A^-1|_F <= the bound (icet_solve.hip gn_tail)
@@ -238,6 +242,10 @@ struct LaunchCfg {
     const int32_t* kf_of = nullptr;        // set (indexed registrations, icet_register_indexed_device): the loop's block of registration r reads the keyframe tables of kf_of[r]
     const PairDesc* h_desc_up = nullptr; const int32_t* h_seg_up = nullptr;      // set: the keyframe's first kernel (k_rs_splitters) copies the descriptors / segment offsets from this pinned staging itself (small batches: launch_upload_desc's job)
 };
+inline int bits_of(int64_t x) { int b = 0; while (x > 0) { b++; x >>= 1; } return b; }              // bits needed for 0 .. x
+inline int packed_row_shift(int max_n1) { return max_n1 > 1 ? bits_of((int64_t)max_n1 - 1) : 1; }   // bits of a rank / row of the largest scan (at least one)
+inline int packed_row_bits(int max_n1, int V) { return packed_row_shift(max_n1) + bits_of((int64_t)V - 1) + 2; }   // + the voxel id + the two flags, which sit right above the id
+inline uint32_t packed_row_mask(const LaunchCfg& c) { return c.packed_rows ? (1u << c.row_shift) - 1u : 0xFFFFFFFFu; }
 constexpr float kRejectMovingThresh = 0.3f;        // python/ICET_spherical.py:38  RM_thresh
 constexpr int kRejectMovingStartIter = 4;          // python/ICET_spherical.py:36  start_RM_iter
 

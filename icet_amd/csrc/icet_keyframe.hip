@@ -160,8 +160,17 @@ constexpr int kWalk = ICET_WALK;
 constexpr uint16_t kBinMask = kRowBinMask;
 __device__ __host__ __forceinline__ size_t exec_word_base(int32_t off1, int pair) { return (size_t)(off1 >> 6) + (size_t)pair; }
 
+// PACKED ROWS (LaunchCfg::packed_rows, kPacked below): when a rank and a voxel word fit one 32-bit word together, pred[] and src[] carry both --
+// the rank / row in the low row_shift bits, the voxel word (pack_voxel_word: the id, the near flag, the zero flag) above them.  pred[row] holds the word of
+// the row whose INDEX is the rank (the rank sort reads it coalesced where it stores the rank): that is the row the swap loop puts on every position
+// that is not the head of a run, so k_scramble_src gathers bin16[] for the heads alone; src[v] holds the word of the row that lands on v, so there
+// is no binpos[].  Same permutation, same counts, same bits.
+static_assert(kSortedNearBit == 1u << 31 && kSortedZeroBit == 1u << 30, "k_bin_scatter moves the two packed flags to the top of a sorted row by shifts");
+template <bool kPacked> __device__ __forceinline__ int rank_of(int32_t w, int row_shift) { return kPacked ? (int)((uint32_t)w & ((1u << row_shift) - 1u)) : (int)w; }
+
+template <bool kPacked>
 __global__ __launch_bounds__(kBlock) void k_exec_flags(const PairDesc* __restrict__ desc, const int32_t* __restrict__ pred,
-                                                       unsigned long long* __restrict__ execbits, int32_t* __restrict__ flags, int max_walk, int n_pairs, int chunks) {
+                                                       unsigned long long* __restrict__ execbits, int32_t* __restrict__ flags, int max_walk, int n_pairs, int chunks, int row_shift) {
     int pair, chunk;
     if (!decode_block(n_pairs, chunks, pair, chunk)) return;
     const PairDesc d = desc[pair];
@@ -183,6 +192,8 @@ __global__ __launch_bounds__(kBlock) void k_exec_flags(const PairDesc* __restric
             int p[kWalk];
 #pragma unroll
             for (int k = 0; k < kWalk; k++) p[k] = act[k] ? pred[o + u[k]] : 0;
+#pragma unroll
+            for (int k = 0; k < kWalk; k++) p[k] = rank_of<kPacked>(p[k], row_shift);      // (behind the loads, not inside their conditions: `act ? f(load) : 0` becomes a branch with its own wait per load)
             any = false;
 #pragma unroll
             for (int k = 0; k < kWalk; k++) {
@@ -220,9 +231,9 @@ __global__ __launch_bounds__(kBlock) void k_exec_flags(const PairDesc* __restric
 #define ICET_EXEC_PAIR_THREADS 1024
 #endif
 constexpr int kExecPairThreads = ICET_EXEC_PAIR_THREADS;
-template <int kR>
+template <int kR, bool kPacked>
 __global__ __launch_bounds__(kExecPairThreads) void k_exec_flags_pair(const PairDesc* __restrict__ desc, const int32_t* __restrict__ pred,
-                                                                      unsigned long long* __restrict__ execbits) {
+                                                                      unsigned long long* __restrict__ execbits, int row_shift) {
     extern __shared__ __attribute__((aligned(8))) unsigned char sm_exec[];
     constexpr int kT = kExecPairThreads, kC = kT * kR;
     unsigned char* st = sm_exec;                                          // per row of the chunk: 0 pending, 2 | bit resolved
@@ -233,7 +244,7 @@ __global__ __launch_bounds__(kExecPairThreads) void k_exec_flags_pair(const Pair
     const int32_t* pp = pred + (size_t)d.off1;
     int pn[kR];
 #pragma unroll
-    for (int r = 0; r < kR; r++) { const int v = r * kT + tid; pn[r] = (v < n) ? pp[v] : 0; }
+    for (int r = 0; r < kR; r++) { const int v = r * kT + tid; pn[r] = (v < n) ? pp[v] : 0; }      // (packed rows: the raw words; the rank is taken where the word is used)
     // "does any row of the block still wait": one flag per wave, ONE barrier, two sets of flags used in turn (a wave can only write set A again
     // after a barrier that every wave reaches after its reads of set A).  __syncthreads_or (ockl's work-group reduction) cost 0.9 us per
     // round -- the rounds were half of this kernel.
@@ -252,7 +263,7 @@ __global__ __launch_bounds__(kExecPairThreads) void k_exec_flags_pair(const Pair
     for (int c0 = 0; c0 < n; c0 += kC) {
         int p[kR];
 #pragma unroll
-        for (int r = 0; r < kR; r++) { p[r] = pn[r]; const int v = c0 + kC + r * kT + tid; pn[r] = (v < n) ? pp[v] : 0; }      // the next chunk is in flight
+        for (int r = 0; r < kR; r++) { p[r] = rank_of<kPacked>(pn[r], row_shift); const int v = c0 + kC + r * kT + tid; pn[r] = (v < n) ? pp[v] : 0; }      // the next chunk is in flight
         // straight-line (selects, no branch per row): the eight table reads leave together; behind `if (earlier chunk)` each one waited inside
         // its row's branch.  pv is a row of the pair (0 past the end), so the read is always inside the table; its word is only USED for an earlier chunk.
         unsigned long long w[kR];
@@ -317,11 +328,13 @@ __global__ __launch_bounds__(kExecPairThreads) void k_exec_flags_pair(const Pair
 #endif
 // kBitsInLds: the pair's exec table sits in LDS behind the voxel histogram (any scan below ~0.75 M rows); otherwise its words are
 // read from memory.
-template <bool kBitsInLds>
+// kPacked: pred[] carries the voxel word of row pred(v) (see rank_of above) -- only a head gathers bin16[], at the end of its chain -- and src[v] is written
+// as ONE word, the row with its voxel word above it; binpos[] is not written.
+template <bool kBitsInLds, bool kPacked>
 __global__ __launch_bounds__(kBlock, ICET_SCR_WAVES) void k_scramble_src(const PairDesc* __restrict__ desc, const uint32_t* __restrict__ s, const int32_t* __restrict__ pred,
                                                          const unsigned long long* __restrict__ execbits, int32_t* __restrict__ src, int32_t* __restrict__ flags, int max_walk,
                                                          const uint16_t* __restrict__ bin16, uint16_t* __restrict__ binpos, uint32_t* __restrict__ counts, int V,
-                                                         int n_pairs, int chunks, const int32_t* __restrict__ vrange) {
+                                                         int n_pairs, int chunks, const int32_t* __restrict__ vrange, int row_shift, int id_bits) {
     extern __shared__ __attribute__((aligned(8))) uint32_t lh[];
     int pair, chunk;
     if (!decode_block(n_pairs, chunks, pair, chunk)) return;
@@ -355,10 +368,12 @@ __global__ __launch_bounds__(kBlock, ICET_SCR_WAVES) void k_scramble_src(const P
     for (int base = lo_ + threadIdx.x; base < hi_; base += kWalk * kBlock) {
         int f[kWalk]; uint32_t act[kWalk];                      // act: 0 / ~0 -- masks, not bools: a bool that lives across the rounds costs a v_cndmask 0/1 and a v_cmp per use
         int pv[kWalk];
+        uint32_t pw[kWalk];                                     // (packed) the word of pred[v]: rank pred(v) and, above it, the voxel word of ROW pred(v)
 #pragma unroll
         for (int k = 0; k < kWalk; k++) {
             const int v = base + k * kBlock;
-            pv[k] = pred[o + (v < hi_ ? v : lo_)];
+            const int32_t wv = pred[o + (v < hi_ ? v : lo_)];
+            pv[k] = rank_of<kPacked>(wv, row_shift); pw[k] = kPacked ? (uint32_t)wv : 0u;
         }
         uint32_t any = 0u;
 #pragma unroll
@@ -402,14 +417,36 @@ __global__ __launch_bounds__(kBlock, ICET_SCR_WAVES) void k_scramble_src(const P
         if (over) atomicOr(&flags[pair], 1);
         uint16_t fb[kWalk];                                      // packed word of the row that lands here (its voxel id is what the histogram needs)
 #pragma unroll
-        for (int k = 0; k < kWalk; k++) { const int v = base + k * kBlock; fb[k] = (v < hi_) ? bin16[o + f[k]] : (uint16_t)0; }
+        for (int k = 0; k < kWalk; k++) {
+            const int v = base + k * kBlock;
+            if (!kPacked) fb[k] = (v < hi_) ? bin16[o + f[k]] : (uint16_t)0;
+        }
+        if (kPacked) {
+            // The word that came with pred[v] is the voxel word of row pred(v): right wherever that row lands here -- every position that is not a head
+            // (a fixed point has pred(v) = v), and a head whose chain ends at pred(v).  Any other head gathers bin16[] at the end of its chain.  A load
+            // under `if (gather)` -- or one whose result is only used under it -- is compiled to a branch with its own wait: eight memory round trips in
+            // a row.  So the load is unconditional, every lane that need not gather reads ONE word, the tile's first (the lanes of a wave that share an
+            // address are one access: the gathering heads alone are divergent), and the empty asm makes every result a value the thread uses, after
+            // all eight loads have left.
+            const uint32_t rmask = (1u << row_shift) - 1u;
+            uint32_t t[kWalk];
+#pragma unroll
+            for (int k = 0; k < kWalk; k++) t[k] = bin16[o + ((base + k * kBlock < hi_ && (uint32_t)f[k] != (pw[k] & rmask)) ? f[k] : lo_)];      // (past the tile's end f is no row)
+#pragma unroll
+            for (int k = 0; k < kWalk; k++) asm volatile("" : "+v"(t[k]));
+#pragma unroll
+            for (int k = 0; k < kWalk; k++) fb[k] = ((uint32_t)f[k] != (pw[k] & rmask)) ? (uint16_t)pack_voxel_word(t[k], id_bits) : (uint16_t)(pw[k] >> row_shift);
+        }
 #pragma unroll
         for (int k = 0; k < kWalk; k++) {
             const int v = base + k * kBlock;
             if (v < hi_) {
-                src[o + v] = f[k];
-                const uint16_t b = fb[k] & kBinMask;
-                binpos[o + v] = fb[k];                              // voxel id + the row's near-edge flag
+                const uint16_t b = kPacked ? (uint16_t)(fb[k] & ((1u << id_bits) - 1u)) : (uint16_t)(fb[k] & kBinMask);
+                if (kPacked) src[o + v] = (int32_t)((uint32_t)f[k] | ((uint32_t)fb[k] << row_shift));
+                else {
+                    src[o + v] = f[k];
+                    binpos[o + v] = fb[k];                          // voxel id + the row's near-edge flag
+                }
                 atomicAdd(&lh[b >> 1], 1u << (16u * (b & 1u)));
             }
         }
@@ -431,9 +468,10 @@ __global__ __launch_bounds__(kBlock, ICET_SCR_WAVES) void k_scramble_src(const P
 //   k_bin_scatter  one wave per tile walks its positions 64 at a time; lanes holding the same voxel find each other
 //                  with a ballot per id bit (match-any), so rank = popcount of lower peers -- stable by construction --
 //                  and the row's spherical coordinates are written straight to their final place.
-__global__ __launch_bounds__(kBlock) void k_bin_hist(const PairDesc* __restrict__ desc, const int32_t* __restrict__ src, const uint16_t* __restrict__ bin16,
+// (row_shift > 0, packed rows: src[] holds plain rows on entry and leaves with each row's voxel word above it; binpos[] is not written)
+__global__ __launch_bounds__(kBlock) void k_bin_hist(const PairDesc* __restrict__ desc, int32_t* __restrict__ src, const uint16_t* __restrict__ bin16,
                                                      uint16_t* __restrict__ binpos, uint32_t* __restrict__ counts, const int32_t* __restrict__ flags,
-                                                     int V, int n_pairs, int chunks, int force) {
+                                                     int V, int n_pairs, int chunks, int force, int row_shift, int id_bits) {
     extern __shared__ uint32_t lh[];
     int pair, chunk;
     if (!decode_block(n_pairs, chunks, pair, chunk)) return;
@@ -445,8 +483,9 @@ __global__ __launch_bounds__(kBlock) void k_bin_hist(const PairDesc* __restrict_
     __syncthreads();
     const size_t o = d.off1;
     for (int v = lo_ + threadIdx.x; v < hi_; v += kBlock) {
-        const uint16_t wd = bin16[o + src[o + v]];
-        binpos[o + v] = wd;
+        const int row = src[o + v];
+        const uint16_t wd = bin16[o + row];
+        if (row_shift > 0) src[o + v] = (int32_t)((uint32_t)row | (pack_voxel_word(wd, id_bits) << row_shift)); else binpos[o + v] = wd;
         atomicAdd(&lh[wd & kBinMask], 1u);
     }
     __syncthreads();
@@ -460,7 +499,7 @@ __global__ __launch_bounds__(kBlock) void k_bin_hist(const PairDesc* __restrict_
 // and nothing else (two separate always-launched kernels cost a single pair ~5 us each for nothing).
 __global__ __launch_bounds__(kBlock) void k_scramble_replay(const PairDesc* __restrict__ desc, const uint32_t* __restrict__ s, int32_t* __restrict__ idx_tmp,
                                                             int32_t* __restrict__ src, const int32_t* __restrict__ flags, const uint16_t* __restrict__ bin16,
-                                                            uint16_t* __restrict__ binpos, uint32_t* __restrict__ counts, int V, int chunks) {
+                                                            uint16_t* __restrict__ binpos, uint32_t* __restrict__ counts, int V, int chunks, int row_shift, int id_bits) {      // row_shift > 0: packed rows (k_bin_hist)
     extern __shared__ uint32_t lh[];
     const int pair = blockIdx.x;
     if (!(flags[pair] & 1)) return;
@@ -484,8 +523,9 @@ __global__ __launch_bounds__(kBlock) void k_scramble_replay(const PairDesc* __re
         for (int b = threadIdx.x; b < V; b += kBlock) lh[b] = 0u;
         __syncthreads();
         for (int v = lo_ + threadIdx.x; v < hi_; v += kBlock) {
-            const uint16_t wd = bin16[o + src[o + v]];
-            binpos[o + v] = wd;
+            const int row = src[o + v];
+            const uint16_t wd = bin16[o + row];
+            if (row_shift > 0) src[o + v] = (int32_t)((uint32_t)row | (pack_voxel_word(wd, id_bits) << row_shift)); else binpos[o + v] = wd;
             atomicAdd(&lh[wd & kBinMask], 1u);
         }
         __syncthreads();
@@ -594,10 +634,11 @@ __global__ __launch_bounds__(kScanBlock) void k_bin_scan(int32_t* __restrict__ c
 // lds_rank_selftest; the ballot form below stays as the fallback and as the tests' cross-check).  The ballot form costs ~10 VALU
 // instructions per id bit and round -- 11 bits x 8 rounds -- and this kernel is bound by VALU issue (4 cycles per wave64 instruction).
 constexpr int kScatterRounds = kKfMaxPtsPerThread;   // a tile is at most 4 waves x this many rounds x 64 positions
-template <bool kLdsRank>
+// kPacked: ONE word per position, the row with its voxel word above it (k_scramble_src); binpos[] is not read.
+template <bool kLdsRank, bool kPacked>
 __global__ __launch_bounds__(kBlock) void k_bin_scatter(const PairDesc* __restrict__ desc, const int32_t* __restrict__ src, const uint16_t* __restrict__ binpos,
                                                         const uint32_t* __restrict__ tile_base, const int32_t* __restrict__ bin_start,
-                                                        uint32_t* __restrict__ sorted_row, int V, int vbits, int n_pairs, int chunks, const int32_t* __restrict__ vrange) {
+                                                        uint32_t* __restrict__ sorted_row, int V, int vbits, int n_pairs, int chunks, const int32_t* __restrict__ vrange, int row_shift, int id_bits) {
     // LDS: gb[V] (u32: where the tile's rows of a voxel start in the pair's table) | lc[4][V] (u16: per-wave counts, then the running
     // offset of each wave inside the tile's rows of the voxel).  12 bytes per voxel -- 21.6 KB for 75 x 24, seven blocks per CU; with
     // four u32 arrays (28.8 KB, five blocks) the kernel took 260 us per 256 pairs: it wants occupancy (capped at 4 / 3 blocks: 281 / 334).
@@ -626,13 +667,20 @@ __global__ __launch_bounds__(kBlock) void k_bin_scatter(const PairDesc* __restri
         const int v = wlo + 64 * k + lane;
         ok[k] = (k < rounds) & (v < whi);
         const size_t vv = o + (size_t)(ok[k] ? v : lo_);
-        bb[k] = binpos[vv]; row[k] = (uint32_t)src[vv];
+        if (kPacked) { const uint32_t wv = (uint32_t)src[vv]; bb[k] = wv >> row_shift; row[k] = wv & ((1u << row_shift) - 1u); }
+        else { bb[k] = binpos[vv]; row[k] = (uint32_t)src[vv]; }
     }
 #pragma unroll
     for (int k = 0; k < kScatterRounds; k++) {
         const uint32_t wd = ok[k] ? bb[k] : 0u;
-        bb[k] = wd & kRowBinMask;
-        row[k] = (ok[k] ? row[k] : 0u) | ((wd & kRowNearBit) ? kSortedNearBit : 0u) | ((wd & kRowZeroBit) ? kSortedZeroBit : 0u);   // the flags travel with the row
+        if (kPacked) {                                                 // the packed voxel word: the near flag sits right above the id, the zero flag above that
+            const uint32_t fl = wd >> id_bits;
+            bb[k] = wd & ((1u << id_bits) - 1u);
+            row[k] = (ok[k] ? row[k] : 0u) | (fl << 31) | ((fl >> 1) << 30);
+        } else {
+            bb[k] = wd & kRowBinMask;
+            row[k] = (ok[k] ? row[k] : 0u) | ((wd & kRowNearBit) ? kSortedNearBit : 0u) | ((wd & kRowZeroBit) ? kSortedZeroBit : 0u);   // the flags travel with the row
+        }
         if (ok[k]) {                                                   // 16-bit counters, 32-bit atomics: a quarter tile holds <= 512 rows, no carry into the neighbour
             const uint32_t e = (uint32_t)(wave * V) + bb[k];
             const uint32_t old = atomicAdd(&lb[V + (e >> 1)], 1u << (16u * (e & 1u)));
@@ -1318,13 +1366,16 @@ static size_t scan1_lds_bytes(const Workspace& w) { return (size_t)(w.lut_Mt + w
 
 hipError_t init_keyframe_kernels() {
     const int cap = 160 * 1024 - 4096;        // static __shared__ of the kernels comes on top (k_scan1_spherical: 8 B per rank-sort bucket + 32)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin_scatter<false>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_scramble_src<true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_scramble_src<false>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+    hipError_t e = hipSuccess;
+    const void* const grow[] = {reinterpret_cast<const void*>(k_bin_scatter<false, false>), reinterpret_cast<const void*>(k_bin_scatter<true, false>),
+                                reinterpret_cast<const void*>(k_bin_scatter<false, true>), reinterpret_cast<const void*>(k_bin_scatter<true, true>),
+                                reinterpret_cast<const void*>(k_scramble_src<true, false>), reinterpret_cast<const void*>(k_scramble_src<false, false>),
+                                reinterpret_cast<const void*>(k_scramble_src<true, true>), reinterpret_cast<const void*>(k_scramble_src<false, true>),
+                                reinterpret_cast<const void*>(k_exec_flags_pair<ICET_EXEC_PAIR_ROWS, true>)};
+    for (const void* f : grow) if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin_hist), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_scan1_spherical), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_exec_flags_pair<ICET_EXEC_PAIR_ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_exec_flags_pair<ICET_EXEC_PAIR_ROWS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
     return e;
 }
 
@@ -1339,6 +1390,8 @@ hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev*
     int pbits = 0; while ((1 << pbits) < c.n_pairs) pbits++;
     int vbits = 1; while ((1 << vbits) < c.V) vbits++;
     const bool batch = c.n_pairs > 1;
+    const bool packed = c.packed_rows != 0;           // (make_cfg: never with the library sort, whose k_inverse_perm writes plain ranks)
+    const int rsh = packed ? c.row_shift : 0;
     if (!c.use_library_sort) { e = launch_rank_sort_splitters(w, c, st, d_n1); if (e != hipSuccess) return e; }
     else {   // diagnostic path: no rank sort, hence nobody reduces the tiles' voxel ranges: the full range (vmin = 0, vmax = "large", clipped to V - 1 by the readers)
         if (d_n1) { e = launch_patch_counts(w, c, d_n1, nullptr, st); if (e != hipSuccess) return e; }
@@ -1370,7 +1423,7 @@ hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev*
     if (c.true_sort) {
         // non-parity extension: the rows stay in sorted order (what the reference's comment says the loop is meant to do)
         e = hipMemcpyAsync(w.src, w.valB, sizeof(int32_t) * (size_t)c.total_n1, hipMemcpyDeviceToDevice, st); if (e != hipSuccess) return e;
-        k_bin_hist<<<grid, blk, (size_t)c.V * 4, st>>>(w.desc, w.src, w.bin16, w.binpos, w.counts, w.flags, c.V, np, chunks, 1);
+        k_bin_hist<<<grid, blk, (size_t)c.V * 4, st>>>(w.desc, w.src, w.bin16, w.binpos, w.counts, w.flags, c.V, np, chunks, 1, rsh, c.id_bits);
         ICET_LAUNCH_CHECK();
     } else {
         const int max_walk = 4096;
@@ -1379,24 +1432,29 @@ hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev*
             const size_t pair_lds = (size_t)kExecPairThreads * kR + (size_t)((c.max_n1 + 63) / 64) * 8;    // state bytes + the bit table
             const bool fits = pair_lds <= (size_t)150 * 1024;
             const bool pairwise = fits && (c.exec_pairwise > 0 || (c.exec_pairwise < 0 && c.n_pairs >= 64));
-            if (pairwise) k_exec_flags_pair<kR><<<c.n_pairs, kExecPairThreads, pair_lds, st>>>(w.desc, w.pred, w.execbits);
-            else k_exec_flags<<<grid, blk, 0, st>>>(w.desc, w.pred, w.execbits, w.flags, max_walk, np, chunks);
+            if (pairwise) {
+                if (packed) k_exec_flags_pair<kR, true><<<c.n_pairs, kExecPairThreads, pair_lds, st>>>(w.desc, w.pred, w.execbits, rsh);
+                else k_exec_flags_pair<kR, false><<<c.n_pairs, kExecPairThreads, pair_lds, st>>>(w.desc, w.pred, w.execbits, rsh);
+            } else if (packed) k_exec_flags<true><<<grid, blk, 0, st>>>(w.desc, w.pred, w.execbits, w.flags, max_walk, np, chunks, rsh);
+            else k_exec_flags<false><<<grid, blk, 0, st>>>(w.desc, w.pred, w.execbits, w.flags, max_walk, np, chunks, rsh);
         }
         ICET_LAUNCH_CHECK();
         const size_t hist_bytes = (size_t)((((c.V + 1) / 2 + 1) & ~1)) * 4, bit_bytes = (size_t)((c.max_n1 + 63) / 64) * 8;
-        if (c.exec_bits_lds && hist_bytes + bit_bytes <= kScrambleLdsMax)
-            k_scramble_src<true><<<grid, blk, hist_bytes + bit_bytes, st>>>(w.desc, w.valB, w.pred, w.execbits, w.src, w.flags, max_walk, w.bin16, w.binpos, w.counts, c.V, np, chunks, w.vrange);
-        else
-            k_scramble_src<false><<<grid, blk, hist_bytes, st>>>(w.desc, w.valB, w.pred, w.execbits, w.src, w.flags, max_walk, w.bin16, w.binpos, w.counts, c.V, np, chunks, w.vrange);
+#define ICET_SCRAMBLE(LDS, PACKED, BYTES) k_scramble_src<LDS, PACKED><<<grid, blk, BYTES, st>>>(w.desc, w.valB, w.pred, w.execbits, w.src, w.flags, max_walk, w.bin16, w.binpos, w.counts, c.V, np, chunks, w.vrange, rsh, c.id_bits)
+        if (c.exec_bits_lds && hist_bytes + bit_bytes <= kScrambleLdsMax) { if (packed) ICET_SCRAMBLE(true, true, hist_bytes + bit_bytes); else ICET_SCRAMBLE(true, false, hist_bytes + bit_bytes); }
+        else { if (packed) ICET_SCRAMBLE(false, true, hist_bytes); else ICET_SCRAMBLE(false, false, hist_bytes); }
+#undef ICET_SCRAMBLE
         ICET_LAUNCH_CHECK();
-        k_scramble_replay<<<c.n_pairs, blk, (size_t)c.V * 4, st>>>(w.desc, w.valB, w.pred /* reused as scratch */, w.src, w.flags, w.bin16, w.binpos, w.counts, c.V, chunks);
+        k_scramble_replay<<<c.n_pairs, blk, (size_t)c.V * 4, st>>>(w.desc, w.valB, w.pred /* reused as scratch */, w.src, w.flags, w.bin16, w.binpos, w.counts, c.V, chunks, rsh, c.id_bits);
         ICET_LAUNCH_CHECK();
         if (c.stage_event && c.stage_at == 2) { e = hipEventRecord(c.stage_event, st); if (e != hipSuccess) return e; }
     }
     e = launch_class_scan(w.counts, w.tile_base, w.bin_start, c.V, chunks, c.n_pairs, st, w.live_bins, w.n_live, c.n, w.fit_n_items, w.vrange);
     if (e != hipSuccess) return e;
-    if (c.lds_rank) k_bin_scatter<true><<<grid, blk, (size_t)c.V * 12 + 8, st>>>(w.desc, w.src, w.binpos, w.tile_base, w.bin_start, w.valA, c.V, vbits, np, chunks, w.vrange);
-    else k_bin_scatter<false><<<grid, blk, (size_t)c.V * 12 + 8, st>>>(w.desc, w.src, w.binpos, w.tile_base, w.bin_start, w.valA, c.V, vbits, np, chunks, w.vrange);
+#define ICET_BIN_SCATTER(RANK, PACKED) k_bin_scatter<RANK, PACKED><<<grid, blk, (size_t)c.V * 12 + 8, st>>>(w.desc, w.src, w.binpos, w.tile_base, w.bin_start, w.valA, c.V, vbits, np, chunks, w.vrange, rsh, c.id_bits)
+    if (c.lds_rank) { if (packed) ICET_BIN_SCATTER(true, true); else ICET_BIN_SCATTER(true, false); }
+    else { if (packed) ICET_BIN_SCATTER(false, true); else ICET_BIN_SCATTER(false, false); }
+#undef ICET_BIN_SCATTER
     ICET_LAUNCH_CHECK();
     if (c.stage_event && c.stage_at == 3) { e = hipEventRecord(c.stage_event, st); if (e != hipSuccess) return e; }
     // keyA / keyB (bucket-grouped keys and the overflow scratch of the rank sort) are dead by now: candidate rows and their r

@@ -59,6 +59,11 @@ constexpr int kRsPerBlockBatch = ICET_RS_PER_BLOCK;   // buckets per block of k_
 constexpr int kRsPrefetch = 5;                   // (key, row) pairs per thread fetched ahead: 5 x 256 = 1280 rows, more than 97 % of the buckets of a 64-channel scan
 constexpr int kCapMin = 1664, kCapMax = 8960;  // 8960 rows + 4096 cells = 156 KB: one block per CU, still far better than global scratch
 
+// What is stored in pred[row] for the row with rank `rank`: the rank alone, or (packed rows) the rank with the voxel word of the ROW whose index is
+// that rank above it -- bin16[rank], the word of the row that the swap loop puts on a non-head position (icet_keyframe.hip, k_scramble_src).
+template <bool kPacked>
+__device__ __forceinline__ int32_t pred_word(int rank, uint32_t wd, int row_shift, int id_bits) { return kPacked ? (int32_t)((uint32_t)rank | (pack_voxel_word(wd, id_bits) << row_shift)) : (int32_t)rank; }
+
 // ---- splitters -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float radius_of(float x, float y, float z) {     // the r that k_scan1_spherical stores, bit for bit
     const float r = radius_raw(x, y, z);
@@ -227,10 +232,14 @@ static_assert(kMaxBuckets <= kBlock && kMaxBuckets % 64 == 0 && kMaxBuckets <= 2
 __device__ __forceinline__ bool zero_bucket_done(const uint32_t* __restrict__ splitters, int pair, const int32_t* __restrict__ n_buckets) {
     return n_buckets[pair] >= 2 && splitters[(size_t)pair * kMaxBuckets + 1] == 0u;
 }
+// kPacked (LaunchCfg::packed_rows): pred[row] = rank | voxel word of ROW `rank` << row_shift -- the word the swap loop needs at every position that is
+// not the head of a run (k_scramble_src); here rank = dest is consecutive across lanes, so the read of bin16[] is coalesced.
+template <bool kPacked>
 __global__ __launch_bounds__(kBlock) void k_rs_scatter_staged(const PairDesc* __restrict__ desc, const float* __restrict__ r1, const uint8_t* __restrict__ bkt,
                                                               const uint32_t* __restrict__ tile_base, const int32_t* __restrict__ bucket_start,
                                                               uint2* __restrict__ bkv, int n_pairs, int chunks,
-                                                              const uint32_t* __restrict__ splitters, const int32_t* __restrict__ n_buckets, uint32_t* __restrict__ s_out, int32_t* __restrict__ pred_out) {
+                                                              const uint32_t* __restrict__ splitters, const int32_t* __restrict__ n_buckets, uint32_t* __restrict__ s_out, int32_t* __restrict__ pred_out,
+                                                              const uint16_t* __restrict__ bin16, int row_shift, int id_bits) {
     __shared__ uint32_t lb[4 * kMaxBuckets];                         // per wave and bucket: rows counted, then the wave's first slot in the stage
     __shared__ int32_t gdelta[kMaxBuckets];                          // bucket: (global position - stage position) of its rows of this tile
     __shared__ uint32_t wtot[kMaxBuckets / 64];
@@ -299,7 +308,7 @@ __global__ __launch_bounds__(kBlock) void k_rs_scatter_staged(const PairDesc* __
             const int b = stage_b[j];
             const int dest = gdelta[b] + j;
             bkv[(int64_t)o + dest] = stage[j];
-            if (zero_done && b == 0) { s_out[o + dest] = stage[j].y; pred_out[o + stage[j].y] = dest; }      // (bucket 0 starts at rank 0)
+            if (zero_done && b == 0) { s_out[o + dest] = stage[j].y; pred_out[o + stage[j].y] = pred_word<kPacked>(dest, kPacked ? bin16[o + dest] : 0u, row_shift, id_bits); }      // (bucket 0 starts at rank 0)
         }
     }
 }
@@ -312,8 +321,9 @@ __host__ __device__ constexpr int cell_region(int C) { return C > kRadixWords ? 
 
 // Counting sort of the n (key, row) pairs in buf0 on the bucket's own key range; true = done (s / pred written), false = some cell
 // is too crowded (block-uniform; nothing written): the caller falls back to the radix sort.
+template <bool kPacked>
 __device__ __forceinline__ bool counting_sort_lds(uint32_t* smem, int Clayout, int logCmax, int kCap, int n, uint32_t kmin, uint32_t kmax,
-                                                  int lo, size_t off1, uint32_t* s_out, int32_t* pred_out, int max_cell) {
+                                                  int lo, size_t off1, uint32_t* s_out, int32_t* pred_out, int max_cell, const uint16_t* __restrict__ bin16, int row_shift, int id_bits) {
     uint32_t* cells = smem; uint32_t* red = smem + cell_region(Clayout);
     const int offBuf = cell_region(Clayout) + kRedWords;
     // cells for THIS bucket: a launch whose LDS is sized for large buckets (small batches: every bucket up to 8960 rows stays in LDS) still
@@ -361,7 +371,8 @@ __device__ __forceinline__ bool counting_sort_lds(uint32_t* smem, int Clayout, i
         uint32_t r = b;
         for (uint32_t j = b; j < e; j++) { const uint32_t kj = K1[j], ij = I1[j]; r += ((kj < k) | ((kj == k) & (ij < id))) ? 1u : 0u; }
         s_out[off1 + lo + r] = id;
-        pred_out[off1 + id] = lo + (int)r;
+        // (packed rows: a gather inside the bucket's own few KB of bin16[]; this path takes the ~3 % of the buckets that do not fit the registers)
+        pred_out[off1 + id] = pred_word<kPacked>(lo + (int)r, kPacked ? bin16[off1 + lo + r] : 0u, row_shift, id_bits);
     }
     return true;
 }
@@ -370,8 +381,11 @@ __device__ __forceinline__ bool counting_sort_lds(uint32_t* smem, int Clayout, i
 // 64-channel scan): the keys never go through the first LDS buffer, and every phase is straight-line code over the thread's <= 5 rows -- five
 // independent LDS atomics, then five placements, then five rank walks -- instead of a loop whose every trip waits for its own LDS reads.
 // The cells must have been zeroed before the barriers of block_key_stats.  Same cells, same ranks, same bits as counting_sort_lds.
+// kPacked: wds[r] = the voxel word of row lo + r, in LDS (bucket_sort_body put the words there from the prefetched registers, in front of this
+// function's first barrier), so the word of row lo + r costs the rank loop an LDS read, not a global gather.
+template <bool kPacked>
 __device__ __forceinline__ bool counting_sort_regs(uint32_t* smem, int Clayout, int logC, int kCap, int n, const uint2 (&pf)[kRsPrefetch], uint32_t kmin, uint32_t kmax,
-                                                   int lo, size_t off1, uint32_t* s_out, int32_t* pred_out, int max_cell) {
+                                                   int lo, size_t off1, uint32_t* s_out, int32_t* pred_out, int max_cell, const uint16_t* wds, int row_shift, int id_bits) {
     uint32_t* cells = smem; uint32_t* red = smem + cell_region(Clayout);
     const int offBuf = cell_region(Clayout) + kRedWords;
     const int C = 1 << logC;
@@ -430,22 +444,32 @@ __device__ __forceinline__ bool counting_sort_regs(uint32_t* smem, int Clayout, 
         for (uint32_t t = 0; t < kCellAhead; t++) r += (m[t] < me) ? 1u : 0u;
         for (uint32_t j = b[k] + kCellAhead; j < e[k]; j++) r += (KI[j] < me) ? 1u : 0u;
         s_out[off1 + lo + r] = id;
-        pred_out[off1 + id] = lo + (int)r;
+        pred_out[off1 + id] = pred_word<kPacked>(lo + (int)r, kPacked ? (uint32_t)wds[r] : 0u, row_shift, id_bits);
     }
     return true;
 }
 
 // pf: the bucket's first kRsPrefetch x 256 (key, row) pairs, already in registers (fetched while the block sorted its previous bucket)
-template <bool kLds>
+// pw (packed rows): eight of the voxel words of rows lo .. lo + n - 1 -- the rows whose INDEX is one of the bucket's ranks --, fetched with pf: the
+// aligned group of eight bin16[] words number tid, counted from the last multiple of eight at or below off1 + lo (ONE 16-byte load per thread)
+template <bool kLds, bool kPacked>
 __device__ __forceinline__ void bucket_sort_body(uint32_t* smem, int C, int logC, int kCap, const uint2* bkv, uint2* gA, uint2* gB,
                                                  int n, int lo, size_t off1, uint32_t* s_out, int32_t* pred_out, int max_cell, const uint2 (&pf)[kRsPrefetch],
-                                                 uint32_t key_lo, uint32_t key_hi) {      // key_lo <= key_hi: bounds of the bucket's keys known from the splitters
+                                                 uint32_t key_lo, uint32_t key_hi,        // key_lo <= key_hi: bounds of the bucket's keys known from the splitters
+                                                 const uint16_t* __restrict__ bin16, int row_shift, int id_bits, const uint4& pw) {
     const size_t o = off1 + lo;
     const int offBuf = cell_region(C) + kRedWords;
     uint32_t vor = 0u, vand = 0xFFFFFFFFu, vmin = 0xFFFFFFFFu, vmax = 0u;
     if (kLds && n <= kRsPrefetch * kSortBlock) {                              // block-uniform: the whole bucket is in registers
         const int logCr = min(logC, 10);
         for (int j = threadIdx.x; j < (1 << logCr); j += kSortBlock) smem[j] = 0u;     // the cells
+        // the last quarter of the buffers is free on this path (the 64-bit (key, row) words of counting_sort_regs end at 2 n + 8 <= 3 kCap words): the
+        // voxel words of the bucket's ranks as the threads fetched them, one 16-byte store each, published by the barriers below; the word of row
+        // lo + i is wds[i] (the stage starts at the multiple of eight at or below off1 + lo; 16-byte aligned: (n + 15) / 2 <= kCap - 3 words, kCap >= 64)
+        const int wd0 = (int)((off1 + (size_t)lo) & 7);
+        uint16_t* stage_w = reinterpret_cast<uint16_t*>(smem + ((offBuf + 3 * kCap + 3) & ~3));
+        const uint16_t* wds = stage_w + wd0;
+        if constexpr (kPacked) { if (8 * (int)threadIdx.x < n + wd0) *reinterpret_cast<uint4*>(stage_w + 8 * threadIdx.x) = pw; }
         if (key_lo <= key_hi) {
             // an inner bucket: its keys lie in (splitter, next splitter] -- the counting sort only needs A range that holds them, so the
             // block-wide min / max (four wave reductions, two barriers) is left to the first and the last bucket of the pair
@@ -459,10 +483,10 @@ __device__ __forceinline__ void bucket_sort_body(uint32_t* smem, int C, int logC
         }
         if ((vor & ~vand) == 0u) {                                             // identical keys: already in order (the multi-split is stable)
 #pragma unroll
-            for (int k = 0; k < kRsPrefetch; k++) { const int i = (int)threadIdx.x + k * kSortBlock; if (i < n) { s_out[o + i] = pf[k].y; pred_out[off1 + pf[k].y] = lo + i; } }
+            for (int k = 0; k < kRsPrefetch; k++) { const int i = (int)threadIdx.x + k * kSortBlock; if (i < n) { s_out[o + i] = pf[k].y; pred_out[off1 + pf[k].y] = pred_word<kPacked>(lo + i, kPacked ? (uint32_t)wds[i] : 0u, row_shift, id_bits); } }
             return;
         }
-        if (counting_sort_regs(smem, C, logCr, kCap, n, pf, vmin, vmax, lo, off1, s_out, pred_out, max_cell)) return;
+        if (counting_sort_regs<kPacked>(smem, C, logCr, kCap, n, pf, vmin, vmax, lo, off1, s_out, pred_out, max_cell, wds, row_shift, id_bits)) return;
         vor = 0u; vand = 0xFFFFFFFFu; vmin = 0xFFFFFFFFu; vmax = 0u;            // a crowded cell: the general path below, from the start
     }
 #pragma unroll
@@ -485,7 +509,7 @@ __device__ __forceinline__ void bucket_sort_body(uint32_t* smem, int C, int logC
     const uint32_t differ = vor & ~vand;
     int sel = 0;
     if (differ != 0u) {
-        if constexpr (kLds) { if (counting_sort_lds(smem, C, logC, kCap, n, vmin, vmax, lo, off1, s_out, pred_out, max_cell)) return; }
+        if constexpr (kLds) { if (counting_sort_lds<kPacked>(smem, C, logC, kCap, n, vmin, vmax, lo, off1, s_out, pred_out, max_cell, bin16, row_shift, id_bits)) return; }
         for (int pass = 0; pass < 4; pass++) {
             if (((differ >> (8 * pass)) & 255u) == 0u) continue;    // block-uniform
             radix_pass<kLds>(smem, offBuf, kCap, sel, sel ? gB : gA, sel ? gA : gB, n, 8 * pass, (differ >> (8 * pass)) & 255u);
@@ -496,15 +520,15 @@ __device__ __forceinline__ void bucket_sort_body(uint32_t* smem, int C, int logC
         uint32_t row;
         if constexpr (kLds) row = smem[offBuf + sel * 2 * kCap + kCap + i]; else row = (sel ? gB : gA)[i].y;
         s_out[o + i] = row;
-        pred_out[off1 + row] = lo + i;
+        pred_out[off1 + row] = pred_word<kPacked>(lo + i, kPacked ? bin16[o + i] : 0u, row_shift, id_bits);      // (rank lo + i: consecutive across lanes)
     }
 }
 
-template <int kRsPerBlock>
+template <int kRsPerBlock, bool kPacked>
 __global__ __launch_bounds__(kSortBlock) void k_rs_bucket_sort(const PairDesc* __restrict__ desc, const int32_t* __restrict__ bucket_start,
                                                                const int32_t* __restrict__ n_buckets, uint2* __restrict__ bkv, uint2* __restrict__ alt,
                                                                uint32_t* __restrict__ s_out, int32_t* __restrict__ pred_out, int kCap, int logC, int max_cell, int n_pairs,
-                                                               const uint32_t* __restrict__ splitters, int zero_in_scatter) {
+                                                               const uint32_t* __restrict__ splitters, int zero_in_scatter, const uint16_t* __restrict__ bin16, int row_shift, int id_bits) {
     extern __shared__ uint32_t smem[];
     // all buckets of a pair on one XCD (decode_block): their scattered 4-byte writes of pred[] then complete whole cache lines in
     // ONE L2 instead of leaving partial lines in eight
@@ -532,25 +556,31 @@ __global__ __launch_bounds__(kSortBlock) void k_rs_bucket_sort(const PairDesc* _
         const uint32_t a = inner ? splitters[(size_t)pair * kMaxBuckets + bkt] : 0xFFFFFFFFu, b2 = inner ? splitters[(size_t)pair * kMaxBuckets + bkt + 1] : 0u;
         klo[q] = (inner && a < b2) ? a + 1u : 1u; khi[q] = (inner && a < b2) ? b2 : 0u;           // (1, 0): not known
     }
-    auto fetch = [&](int lo, int n, uint2 (&pf)[kRsPrefetch]) {
+    // (packed rows: with the (key, row) pairs the voxel words of the rows whose INDEX is one of the bucket's ranks lo .. lo + n - 1, eight per thread in one
+    // aligned 16-byte read that leaves with the others -- 256 x 8 words cover every bucket that sorts from registers; bin16[] is allocated with eight words to spare)
+    static_assert(8 * kSortBlock >= kRsPrefetch * kSortBlock + 7, "one aligned group of eight voxel words per thread covers a bucket that sorts from registers");
+    auto fetch = [&](int lo, int n, uint2 (&pf)[kRsPrefetch], uint4& pw) {
 #pragma unroll
         for (int k = 0; k < kRsPrefetch; k++) { const int i = threadIdx.x + k * kSortBlock; pf[k] = (i < n) ? bkv[off1 + lo + i] : make_uint2(0u, 0u); }
+        const size_t e0 = off1 + (size_t)lo, el = (e0 & ~(size_t)7) + 8 * (size_t)threadIdx.x;
+        pw = (kPacked && el < e0 + (size_t)n) ? *reinterpret_cast<const uint4*>(bin16 + el) : make_uint4(0u, 0u, 0u, 0u);
     };
-    uint2 pf[kRsPrefetch];
-    fetch(los[0], ns[0], pf);
+    uint2 pf[kRsPrefetch]; uint4 pw;
+    fetch(los[0], ns[0], pf, pw);
 #pragma unroll
     for (int q = 0; q < kRsPerBlock; q++) {
-        uint2 nf[kRsPrefetch];
-        if (q + 1 < kRsPerBlock) fetch(los[q + 1], ns[q + 1], nf);
+        uint2 nf[kRsPrefetch]; uint4 nw;
+        if (q + 1 < kRsPerBlock) fetch(los[q + 1], ns[q + 1], nf, nw);
         const int lo = los[q], n = ns[q];
         if (n > 0) {                                                   // block-uniform
-            if (n <= kCap) bucket_sort_body<true>(smem, C, logC, kCap, bkv, nullptr, nullptr, n, lo, off1, s_out, pred_out, max_cell, pf, klo[q], khi[q]);
-            else bucket_sort_body<false>(smem, C, logC, kCap, bkv, bkv + off1 + lo, alt + off1 + lo, n, lo, off1, s_out, pred_out, max_cell, pf, 1u, 0u);
+            if (n <= kCap) bucket_sort_body<true, kPacked>(smem, C, logC, kCap, bkv, nullptr, nullptr, n, lo, off1, s_out, pred_out, max_cell, pf, klo[q], khi[q], bin16, row_shift, id_bits, pw);
+            else bucket_sort_body<false, kPacked>(smem, C, logC, kCap, bkv, bkv + off1 + lo, alt + off1 + lo, n, lo, off1, s_out, pred_out, max_cell, pf, 1u, 0u, bin16, row_shift, id_bits, pw);
             __syncthreads();                                           // the LDS buffers are reused by the next bucket
         }
         if (q + 1 < kRsPerBlock) {
 #pragma unroll
             for (int k = 0; k < kRsPrefetch; k++) pf[k] = nf[k];
+            pw = nw;
         }
     }
 }
@@ -586,8 +616,11 @@ static size_t rank_sort_lds_bytes(int cap) { return (size_t)(cell_region(1 << ra
 // Outputs: w.valB = s (row with rank i), w.pred = rank of every row.  Scratch: w.key64A (bucket-grouped (key, row) pairs),
 // w.key64B (second buffer of an overflow bucket), w.bkt, w.counts / w.tile_base, w.splitters, w.n_buckets, w.bucket_start.
 hipError_t init_rank_sort_kernels() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_bucket_sort<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_sort_lds_bytes(kCapMax));
-    if (e == hipSuccess && kRsPerBlockBatch != 1) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_bucket_sort<kRsPerBlockBatch>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rank_sort_lds_bytes(kCapMax));
+    const int lds = (int)rank_sort_lds_bytes(kCapMax);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_bucket_sort<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_bucket_sort<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess && kRsPerBlockBatch != 1) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_bucket_sort<kRsPerBlockBatch, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess && kRsPerBlockBatch != 1) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_bucket_sort<kRsPerBlockBatch, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     return e;
 }
 
@@ -605,19 +638,24 @@ hipError_t launch_rank_sort(const Workspace& w, const LaunchCfg& c, hipStream_t 
     // (its per-pair scan block also reduces the tiles' voxel ranges, written by k_scan1_spherical, to the pair's)
     hipError_t e = launch_class_scan(w.counts, w.tile_base, w.bucket_start, kMaxBuckets, chunks, np, st, nullptr, nullptr, 0, nullptr, nullptr, w.tile_vr, w.vrange);
     if (e != hipSuccess) return e;
-    if (c.lds_rank) k_rs_scatter_staged<<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, reinterpret_cast<uint2*>(w.key64A), np, chunks, w.splitters, w.n_buckets, w.valB, w.pred);
-    else k_rs_scatter<<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, reinterpret_cast<uint2*>(w.key64A), np, chunks);
+    const bool packed = c.packed_rows != 0;
+    uint2* bkv = reinterpret_cast<uint2*>(w.key64A); uint2* alt = reinterpret_cast<uint2*>(w.key64B);
+    if (c.lds_rank) {
+        if (packed) k_rs_scatter_staged<true><<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, bkv, np, chunks, w.splitters, w.n_buckets, w.valB, w.pred, w.bin16, c.row_shift, c.id_bits);
+        else k_rs_scatter_staged<false><<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, bkv, np, chunks, w.splitters, w.n_buckets, w.valB, w.pred, w.bin16, c.row_shift, c.id_bits);
+    } else k_rs_scatter<<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, bkv, np, chunks);
     ICET_LAUNCH_CHECK();
     const int cap = rank_sort_cap(c.max_n1, c.rs_cap, c.n_pairs);
     const int zero_in_scatter = c.lds_rank ? 1 : 0;                       // (the ballot form of the multi-split does not write the zero bucket's ranks)
     // two buckets per block (the second one's pairs in flight during the first one's sort) once the launch fills the chip several times over;
     // a small batch -- one pair is at most 256 blocks on 256 CUs -- keeps a block per bucket
-    if (groups * kMaxBuckets >= 16 * 256 && kRsPerBlockBatch != 1)
-        k_rs_bucket_sort<kRsPerBlockBatch><<<dim3(groups * (kMaxBuckets / kRsPerBlockBatch)), kSortBlock, rank_sort_lds_bytes(cap), st>>>(w.desc, w.bucket_start, w.n_buckets, reinterpret_cast<uint2*>(w.key64A),
-                                                                                             reinterpret_cast<uint2*>(w.key64B), w.valB, w.pred, cap, rank_sort_log_cells(cap), c.rs_max_cell, np, w.splitters, zero_in_scatter);
-    else
-        k_rs_bucket_sort<1><<<dim3(groups * kMaxBuckets), kSortBlock, rank_sort_lds_bytes(cap), st>>>(w.desc, w.bucket_start, w.n_buckets, reinterpret_cast<uint2*>(w.key64A),
-                                                                                             reinterpret_cast<uint2*>(w.key64B), w.valB, w.pred, cap, rank_sort_log_cells(cap), c.rs_max_cell, np, w.splitters, zero_in_scatter);
+    const bool two = groups * kMaxBuckets >= 16 * 256 && kRsPerBlockBatch != 1;
+    const dim3 sgrid(two ? groups * (kMaxBuckets / kRsPerBlockBatch) : groups * kMaxBuckets);
+    const size_t lds = rank_sort_lds_bytes(cap); const int logC = rank_sort_log_cells(cap);
+#define ICET_RS_SORT(PER, PACKED) k_rs_bucket_sort<PER, PACKED><<<sgrid, kSortBlock, lds, st>>>(w.desc, w.bucket_start, w.n_buckets, bkv, alt, w.valB, w.pred, cap, logC, c.rs_max_cell, np, w.splitters, zero_in_scatter, w.bin16, c.row_shift, c.id_bits)
+    if (two) { if (packed) ICET_RS_SORT(kRsPerBlockBatch, true); else ICET_RS_SORT(kRsPerBlockBatch, false); }
+    else { if (packed) ICET_RS_SORT(1, true); else ICET_RS_SORT(1, false); }
+#undef ICET_RS_SORT
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -18,12 +18,13 @@
 namespace icet {
 namespace {
 
+// row_mask: the row's bits of a src[] word (packed rows, LaunchCfg::packed_rows, keep the voxel word above them; all ones otherwise)
 __global__ __launch_bounds__(kBlock) void k_side_scan1(const PairDesc* __restrict__ desc, const int32_t* __restrict__ src, uint32_t* __restrict__ inv,
-                                                       float* __restrict__ sph) {
+                                                       float* __restrict__ sph, uint32_t row_mask) {
     const PairDesc d = desc[0];
     const float* px = d.s1; const float* py = px + d.ld1; const float* pz = px + 2 * (size_t)d.ld1;
     for (int p = blockIdx.x * kBlock + threadIdx.x; p < d.n1; p += gridDim.x * kBlock) {
-        const int row = src[(size_t)d.off1 + p];
+        const int row = (int)((uint32_t)src[(size_t)d.off1 + p] & row_mask);
         inv[(size_t)d.off1 + row] = (uint32_t)p;
         float r, th, ph;
         c2s_cr(px[row], py[row], pz[row], r, th, ph);
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(kBlock) void k_side_scan2(const PairDesc* __restric
 hipError_t launch_side_scan1(const Workspace& w, const LaunchCfg& c, float* sph, int32_t* index, hipStream_t st) {
     if (c.max_n1 <= 0) return hipSuccess;
     const int blocks = std::min(2048, (c.max_n1 + kBlock - 1) / kBlock);
-    k_side_scan1<<<blocks, kBlock, 0, st>>>(w.desc, w.src, w.keyB, sph);          // keyB: keyframe scratch, dead once the keyframe is built
+    k_side_scan1<<<blocks, kBlock, 0, st>>>(w.desc, w.src, w.keyB, sph, packed_row_mask(c));          // keyB: keyframe scratch, dead once the keyframe is built
     ICET_LAUNCH_CHECK();
     k_side_index1<<<blocks, kBlock, 0, st>>>(w.desc, w.valA, w.keyB, index);
     ICET_LAUNCH_CHECK();

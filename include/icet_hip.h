@@ -988,6 +988,9 @@ icet_status icet_voxel_map_evidence_fetch_device(icet_voxel_map* map, int32_t* d
  * solve is captured into a hipGraph and replayed from then on -- one hipGraphLaunch instead of ~33 launches on the host; 0 = never, default -1 = on),
  * "lds_rank" (the keyframe's stable multi-splits take a row's rank among equal classes from the value its LDS atomic hands back: -1 / 1 if
  * the device passed the order self-test run at icet_create, 0 = one ballot per class-id bit; same bits either way),
+ * "packed_rows" (the keyframe's rank and row tables carry each row's voxel word in their spare bits, so the swap loop gathers it for run heads only and the voxel
+ * split reads one word per position: -1, the default, whenever bits(largest scan 1 - 1) + bits(voxels - 1) + 2 <= 32 -- 75 x 24 with scans up to 2^19 rows,
+ * 150 x 48 up to 2^17 --, 0 never, 1 required: a call whose shapes do not fit answers ICET_ERR_UNSUPPORTED; same bits either way),
  * "exec_bits_lds" (0: swap-loop bit table read from memory), "exec_pairwise" (which kernel computes the swap loop's executed-step bits:
  * 1 one block per pair from the recurrence, 0 chain walks over independent tiles, -1 by batch size), "fuse_solve" (batches below 32 pairs on grids up to 4096 voxels:
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
