@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_voxel_map_add_posed_device", "icet_voxel_map_stats", "icet_voxel_map_extract_device", "icet_voxel_map_extract",
                     "icet_voxel_map_index", "icet_voxel_map_query_device", "icet_voxel_map_query_posed_device",
                     "icet_voxel_map_evidence_device", "icet_voxel_map_evidence_posed_device", "icet_voxel_map_evidence_fetch_device",
+                    "icet_deskewer_create", "icet_deskewer_destroy", "icet_deskewer_last_error", "icet_deskew_device", "icet_deskew",
+                    "icet_deskew_twists_from_poses_device", "icet_twist_from_pose", "icet_pose_from_twist", "icet_debug_deskew_rows",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
                     "icet_multi_create", "icet_multi_destroy", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
                     "icet_multi_solve_batch", "icet_multi_solve_batch_device", "icet_multi_solve_batch_device_after", "icet_multi_solve_batch_device_async", "icet_multi_sync", "icet_multi_set_option",
@@ -52,7 +54,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_node_group_prev_scan", "icet_node_group_aligned", "icet_node_group_snail_trail",
                     "icet_load_scan", "icet_free_scan", "icet_save_scan_npy")
 _NON_STATUS = ("icet_version", "icet_last_error", "icet_node_last_error", "icet_node_group_last_error", "icet_stream", "icet_device", "icet_free_scan", "icet_multi_last_error", "icet_multi_devices", "icet_multi_context",
-               "icet_keyframe_store_last_error", "icet_pose_step_from_x", "icet_voxel_map_last_error")
+               "icet_keyframe_store_last_error", "icet_pose_step_from_x", "icet_voxel_map_last_error", "icet_deskewer_last_error")
 
 
 class IcetError(RuntimeError):
@@ -136,6 +138,32 @@ class MapEvidenceStats(C.Structure):
 class MapSubmap(C.Structure):
     """icet_voxel_map_submap (include/icet_hip.h), 40 bytes: a host descriptor of device memory."""
     _fields_ = [("xyz", C.c_void_p), ("ld", C.c_int64), ("cap_rows", C.c_int64), ("count", C.c_void_p), ("key", C.c_void_p)]
+
+
+DESKEW_TIME_ARRAY, DESKEW_TIME_COLUMN_FAST, DESKEW_TIME_COLUMN_SLOW = 0, 1, 2      # ICET_DESKEW_TIME_*
+
+
+class DeskewScan(C.Structure):
+    """icet_deskew_scan (include/icet_hip.h), 128 bytes: one scan of a deskew call, its times and the motion of its sweep."""
+    _fields_ = [("src", C.c_void_p), ("n", C.c_int64), ("ld", C.c_int64), ("dst", C.c_void_p), ("ld_out", C.c_int64), ("time", C.c_void_p),
+                ("time_mode", C.c_int32), ("period", C.c_int32), ("t0", C.c_double), ("inv_span", C.c_double), ("s_ref", C.c_double), ("twist", C.c_double * 6)]
+
+
+class DeskewCounts(C.Structure):
+    """icet_deskew_counts (include/icet_hip.h), 64 bytes: the rows of one scan by class."""
+    _fields_ = [("moved", C.c_int64), ("zero", C.c_int64), ("nonfinite", C.c_int64), ("bad_time", C.c_int64), ("out_of_range", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:5]}
+
+
+def deskew_scan(src, n, ld, dst=None, ld_out=None, time=None, time_mode=DESKEW_TIME_ARRAY, period=0, t0=0.0, span=1.0, ref=1.0, twist=(0, 0, 0, 0, 0, 0)):
+    """A DeskewScan from addresses (device or host, as the call takes them): dst None is in place; span is the time of a whole sweep (the record carries its
+    reciprocal, taken here once); ref the sweep fraction whose frame the rows are carried into (0 sweep start, 1 sweep end)."""
+    tw = np.asarray(twist, np.float64).reshape(6)
+    return DeskewScan(int(src) if src else None, int(n), int(ld), int(dst if dst is not None else src) if (dst if dst is not None else src) else None,
+                      int(ld if ld_out is None else ld_out), int(time) if time else None, int(time_mode), int(period), float(t0), 1.0 / float(span), float(ref),
+                      (C.c_double * 6)(*[float(v) for v in tw]))
 
 
 def voxel_key_cells(key):
@@ -372,6 +400,45 @@ def pose_step_from_X(X):
     return T.reshape(4, 4)
 
 
+def twist_from_pose(T):
+    """log of a 4 x 4 pose (icet_twist_from_pose): the twist (rho, phi) as six float64, exp of which is T.  Rotation angles below 3 rad."""
+    t = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+    xi = np.zeros(6, np.float64)
+    st = load_library().icet_twist_from_pose(t.ctypes.data, xi.ctypes.data)
+    if st != ICET_OK:
+        raise IcetError(st, "icet_twist_from_pose")
+    return xi
+
+
+def pose_from_twist(xi, s=1.0):
+    """exp(s xi) (icet_pose_from_twist): the 4 x 4 float64 pose of the sensor at sweep fraction s, in the sensor frame at s = 0."""
+    x = np.ascontiguousarray(np.asarray(xi, np.float64).reshape(6))
+    T = np.zeros(16, np.float64)
+    st = load_library().icet_pose_from_twist(x.ctypes.data, float(s), T.ctypes.data)
+    if st != ICET_OK:
+        raise IcetError(st, "icet_pose_from_twist")
+    return T.reshape(4, 4)
+
+
+def twist_from_X(X):
+    """The twist of one frame period under constant velocity, from a registration result X: twist_from_pose(pose_step_from_X(X))."""
+    return twist_from_pose(pose_step_from_X(X))
+
+
+def debug_deskew_rows(rows, twist, time=None, time_mode=DESKEW_TIME_ARRAY, period=0, t0=0.0, inv_span=1.0, ref=1.0):
+    """The library's compiled body of the deskew rule on host rows (icet_debug_deskew_rows; no GPU): (N x 3 float32 rows out, int32 classes)."""
+    p = np.ascontiguousarray(np.asarray(rows, np.float32).reshape(-1, 3).T)
+    n = p.shape[1]
+    out = np.zeros_like(p); cls = np.zeros(max(n, 1), np.int32)
+    tm = None if time is None else np.ascontiguousarray(np.asarray(time, np.float32).reshape(-1))
+    m = DeskewScan(None, n, n, None, n, None, int(time_mode), int(period), float(t0), float(inv_span), float(ref), (C.c_double * 6)(*[float(v) for v in np.asarray(twist, np.float64).reshape(6)]))
+    st = load_library().icet_debug_deskew_rows(C.byref(m), n, p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, _data(tm), out[0].ctypes.data, out[1].ctypes.data,
+                                               out[2].ctypes.data, cls.ctypes.data)
+    if st != ICET_OK:
+        raise IcetError(st, "icet_debug_deskew_rows")
+    return np.ascontiguousarray(out.T), cls[:n].copy()
+
+
 def scores_as_dict(rec):
     """An icet_score array (SCORE_DTYPE) as named arrays: chi2, chi2_per_voxel, voxels, points_in, points, overlap."""
     return {k: np.array(rec[k]) for k in ("chi2", "chi2_per_voxel", "voxels", "points_in", "points", "overlap")}
@@ -518,6 +585,15 @@ def load_library():
     L.icet_voxel_map_evidence_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(MapEvidence), C.POINTER(MapEvidenceStats)]
     L.icet_voxel_map_evidence_posed_device.argtypes = L.icet_voxel_map_evidence_device.argtypes
     L.icet_voxel_map_evidence_fetch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.icet_deskewer_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.icet_deskewer_destroy.argtypes = [C.c_void_p]
+    L.icet_deskewer_last_error.argtypes = [C.c_void_p]; L.icet_deskewer_last_error.restype = C.c_char_p
+    L.icet_deskew_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DeskewScan), C.c_void_p, C.c_void_p]
+    L.icet_deskew.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DeskewScan), C.c_void_p]
+    L.icet_deskew_twists_from_poses_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p]
+    L.icet_twist_from_pose.argtypes = [C.c_void_p, C.c_void_p]
+    L.icet_pose_from_twist.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+    L.icet_debug_deskew_rows.argtypes = [C.POINTER(DeskewScan), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_keyframe_store_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p]
     L.icet_keyframe_store_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.icet_keyframe_store_snapshot_info.argtypes = [C.c_char_p, C.POINTER(SnapshotInfo)]
@@ -1979,6 +2055,73 @@ class VoxelMap:
             res.append(dict(xyz=np.ascontiguousarray(x[:, :r].cpu().numpy().T), count=n[:r].cpu().numpy(), key=k[:r].cpu().numpy().view(np.uint64),
                             total=int(w[1, j]), status=int(w[2, j])))
         return res
+
+
+class Deskewer:
+    """``icet_deskewer`` (include/icet_hip.h): the rows of many scans, each with the motion of its own sweep as a twist, carried into the
+    sensor frame at one instant of that sweep, in one launch on ``ctx``'s device.  The deskewer borrows ``ctx`` (closed before it)."""
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+        h = C.c_void_p()
+        st = load_library().icet_deskewer_create(ctx._h, C.byref(h))
+        if st != ICET_OK:
+            raise IcetError(st, "icet_deskewer_create: " + load_library().icet_last_error(ctx._h).decode())
+        self._h = h
+        import weakref
+        if not hasattr(ctx, "_nodes"):
+            ctx._nodes = []
+        ctx._nodes.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._ctx, "_h", None):               # (a context finalised first took the device with it: see KeyframeStore.close)
+                load_library().icet_deskewer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        if st != ICET_OK:
+            raise IcetError(st, load_library().icet_deskewer_last_error(self._h).decode())
+
+    def deskew_device(self, scans, twists=None, d_counts_ptr=None):
+        """One launch over ``scans`` (DeskewScan records of device memory: deskew_scan(); a list, or a ctypes array of them).  twists: None (the records' own), or a float64 CUDA tensor of
+        n x 6 that replaces them.  d_counts_ptr: n DeskewCounts records in HBM, zeroed and filled in stream order.  Asynchronous on the context's stream."""
+        A = scans if isinstance(scans, C.Array) else (DeskewScan * max(len(scans), 1))(*scans)      # (a caller that repeats a call keeps the array)
+        tw = None
+        if twists is not None:
+            import torch
+            if not (twists.is_cuda and twists.dtype == torch.float64 and twists.is_contiguous()) or twists.numel() != 6 * len(scans):
+                raise IcetError(ICET_ERR_BAD_ARG, "device twists must be a contiguous float64 CUDA tensor of six values per scan")
+            torch.cuda.current_stream(twists.device).synchronize()          # the context's stream is its own: the tensor must be complete
+            tw = _vp(twists.data_ptr())
+        self._check(load_library().icet_deskew_device(self._h, len(scans), A, tw, _vp(d_counts_ptr)))
+
+    def deskew(self, scans, times, twists, ref=1.0, t0=0.0, span=1.0):
+        """Host arrays: scans N_k x 3, times N_k (sweep time of every row; s = (time - t0) / span), twists n x 6.  Staged, synchronous.  Returns
+        (the deskewed N_k x 3 float32 arrays, the counts as dicts)."""
+        src = [_colmajor(s) for s in scans]
+        tms = [np.ascontiguousarray(np.asarray(t, np.float32).reshape(-1)) for t in times]
+        tw = np.asarray(twists, np.float64).reshape(-1, 6)
+        if not (len(src) == len(tms) == tw.shape[0]) or any(a.shape[1] != t.shape[0] for a, t in zip(src, tms)):
+            raise IcetError(ICET_ERR_BAD_ARG, "one time per row and one twist per scan")
+        dst = [np.zeros_like(a) for a in src]
+        recs = [deskew_scan(a.ctypes.data if a.size else 0, a.shape[1], a.shape[1], d.ctypes.data if d.size else 0, a.shape[1], t.ctypes.data if t.size else 0,
+                            DESKEW_TIME_ARRAY, 0, t0, span, ref, x) for a, d, t, x in zip(src, dst, tms, tw)]
+        A = (DeskewScan * max(len(recs), 1))(*recs)
+        cnt = (DeskewCounts * max(len(recs), 1))()
+        self._check(load_library().icet_deskew(self._h, len(recs), A, C.byref(cnt)))
+        return [np.ascontiguousarray(d.T) for d in dst], [cnt[k].as_dict() for k in range(len(recs))]
+
+    def twists_from_poses_device(self, d_poses_ptr, n, d_twists_ptr, scale=1.0):
+        """d_twists[k] = scale log(T_k^-1 T_(k+1)), k < n, from n + 1 consecutive float32 4 x 4 poses in HBM (what optimize_pose_graph_device leaves there)
+        into n x 6 float64 in HBM.  Asynchronous on the context's stream."""
+        self._check(load_library().icet_deskew_twists_from_poses_device(self._h, int(n), _vp(d_poses_ptr), float(scale), _vp(d_twists_ptr)))
 
 
 class MultiContext:

@@ -252,13 +252,15 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            icet_voxel_map_create, _clear, _add_device, _add_posed_device; _stats, _extract_device, _extract (drain as well; icet_map.hip);
 //                            icet_voxel_map_index, _query_device, _query_posed_device (drain only when the index is stale and they rebuild it);
 //                            icet_voxel_map_evidence_device, _evidence_posed_device (the same, and when their buffers grow or *out is asked for), _evidence_fetch_device
+//                            icet_deskewer_create, icet_deskew_device, icet_deskew_twists_from_poses_device (drain only when the records' stage grows); icet_deskew (drains as well; icet_deskew.hip)
 //   arms or disarms itself   icet_solve_batch_device
 //   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_block_tridiag (copy in, one kernel, copy out,
 //                            synchronise); icet_debug_fetch, icet_keyframe_store_debug_fetch, icet_keep_stats (synchronise, then blocking copies);
 //                            icet_last_timing[_iters] (synchronise); icet_solve_end; icet_keyframe_store_reserve, _enable_appearance, _enable_coarse, _destroy;
-//                            icet_voxel_map_destroy; icet_destroy; icet_sync (the only one that re-arms: armed_calls = 0; icet_solve_indexed and its kin do the same behind their own drain)
+//                            icet_voxel_map_destroy; icet_deskewer_destroy; icet_destroy; icet_sync (the only one that re-arms: armed_calls = 0; icet_solve_indexed and its kin do the same behind their own drain)
 //   enqueues nothing         icet_reserve (allocations and blocking memsets; a growth synchronises first), icet_solve_keyframe_tables (waits for an event),
-//                            icet_set_option, icet_last_error, icet_stream, icet_device, icet_create (armed_calls starts at 2), icet_keyframe_store_last_error, icet_voxel_map_last_error
+//                            icet_set_option, icet_last_error, icet_stream, icet_device, icet_create (armed_calls starts at 2), icet_keyframe_store_last_error, icet_voxel_map_last_error,
+//                            icet_deskewer_last_error, icet_twist_from_pose, icet_pose_from_twist, icet_debug_deskew_rows (no context)
 // (*) the one entry the audit found enqueuing (two memsets of the new tables) without draining or disarming.
 static inline icet_status use_device(icet_ctx* c) {
     if (!c) return ICET_ERR_BAD_ARG;

@@ -242,3 +242,68 @@ def real_batch_rotation(k):
     fall into other voxels and sort differently while the registration stays the pair's and the invalid returns stay exact-zero rows.  float32 3 x 3."""
     ang = np.random.RandomState(7000 + k).uniform(-1, 1, 3) * np.array([0.01, 0.01, 0.05])
     return euler_R(*ang).astype(np.float32)
+
+
+# ---- scans taken while the sensor moves (DESIGN.md section 24) ------------------------------------------------------------------------------------------------------
+
+def exp_twist(twist, s=1.0):
+    """exp(s xi) of a twist xi = (rho, phi): (R 3 x 3, t 3) float64, the sensor's pose at sweep fraction s in the sensor frame at s = 0
+    (p_0 = R p_s + t; Rodrigues' formula and its integral V(phi))."""
+    xi = np.asarray(twist, np.float64).reshape(6)
+    sg, th = s * xi[:3], s * xi[3:]
+    a = float(np.linalg.norm(th))
+    K = np.array([[0.0, -th[2], th[1]], [th[2], 0.0, -th[0]], [-th[1], th[0], 0.0]])
+    if a < 1e-7:
+        A, B, C = 1.0 - a * a / 6.0, 0.5 - a * a / 24.0, 1.0 / 6.0 - a * a / 120.0
+    else:
+        A, B, C = math.sin(a) / a, (1.0 - math.cos(a)) / (a * a), (a - math.sin(a)) / (a ** 3)
+    return np.eye(3) + A * K + B * (K @ K), (np.eye(3) + B * K + C * (K @ K)) @ sg
+
+
+def make_sweep(scene, pose_start, twist, noise_seed, rings=64, steps=2048, sigma=0.02, max_range=120.0, device="cpu", order="ring", drop=True, return_world=False):
+    """One sweep of a MOVING sensor.  pose_start = (t_s[3], R_s[3x3]) as in make_scan, the sensor's pose in the scene frame when the sweep starts; `twist` = (rho, phi)
+    is its motion over the whole sweep, in its own frame at the start: azimuth column c is fired at sweep fraction s = (c + 0.5) / steps from the pose
+    pose_start . exp(s twist), and every row is in the sensor frame of ITS instant, as a driver delivers it.
+    Returns (scan, s): a float32 (3, N) tensor (column-major N x 3) and the float32 sweep fraction of every row; with return_world also the float64 N x 3
+    points where the rays hit, in the scene frame.  drop=False keeps the rays without a hit as exact-zero rows (NaN in the world points), so the scan stays
+    organised: row i is column i % steps for order "ring" and column i // rings for order "azimuth"."""
+    t_s, R_s = pose_start
+    t_s = np.asarray(t_s, np.float64).reshape(3); R_s = np.asarray(R_s, np.float64).reshape(3, 3)
+    d = sensor_dirs(rings, steps, device, order)
+    idx = torch.arange(rings * steps, device=device)
+    col = idx % steps if order == "ring" else idx // rings
+    Rc = np.zeros((steps, 3, 3)); tc = np.zeros((steps, 3))
+    for c in range(steps):
+        R, t = exp_twist(twist, (c + 0.5) / steps)
+        Rc[c] = R_s @ R; tc[c] = R_s @ t + t_s
+    Rr = torch.as_tensor(Rc, device=device)[col]; O = torch.as_tensor(tc, device=device)[col]
+    dw = torch.einsum("nab,nb->na", Rr, d)                   # world directions, per row
+    rng = _raycast(scene, (O[:, 0], O[:, 1], O[:, 2]), dw, max_range)
+    gen = torch.Generator(device=device); gen.manual_seed(int(noise_seed))
+    noise = torch.randn(rng.shape[0], generator=gen, device=device, dtype=torch.float64) * sigma
+    hit = torch.isfinite(rng)
+    r = torch.where(hit, rng + noise, torch.zeros_like(rng))
+    pts = torch.where(hit[:, None], d * r[:, None], torch.zeros_like(d))      # a miss: an exact-zero row, +0.0 as a driver writes it
+    world = torch.where(hit[:, None], O + dw * r[:, None], torch.full_like(dw, float("nan")))
+    s = ((col.to(torch.float64) + 0.5) / steps).to(torch.float32)
+    if drop:
+        pts, s, world = pts[hit], s[hit], world[hit]
+    scan = pts.to(torch.float32).T.contiguous()
+    return (scan, s, world) if return_world else (scan, s)
+
+
+def make_sweep_sequence(n_frames, twist, scene_seed=2000, noise_seed=2001, rings=64, steps=2048, sigma=0.02, max_range=120.0, device="cpu", order="ring", drop=True,
+                        return_world=False):
+    """A drive through one scene at a CONSTANT twist per sweep, the sweeps back to back: sweep k starts at exp(twist)^k (the first at the identity).
+    Returns (sweeps, poses): the make_sweep tuples and the float64 n x 4 x 4 start poses (p_scene = R p + t)."""
+    scene = make_scene(scene_seed)
+    R_step, t_step = exp_twist(twist, 1.0)
+    t, Rw = np.zeros(3), np.eye(3)
+    sweeps, poses = [], []
+    for k in range(n_frames):
+        sweeps.append(make_sweep(scene, (t.copy(), Rw.copy()), twist, noise_seed * 2 + 1 + k, rings, steps, sigma, max_range, device, order, drop, return_world))
+        T = np.eye(4); T[:3, :3] = Rw; T[:3, 3] = t
+        poses.append(T)
+        t = t + Rw @ t_step
+        Rw = Rw @ R_step
+    return sweeps, np.stack(poses)

@@ -974,6 +974,64 @@ icet_status icet_voxel_map_evidence_posed_device(icet_voxel_map* map, int32_t n,
                                                  struct icet_voxel_map_evidence_stats* out);
 icet_status icet_voxel_map_evidence_fetch_device(icet_voxel_map* map, int32_t* d_miss, int32_t* d_agree, uint8_t* d_transient, int64_t cap, int64_t* rows_out);
 
+/* --- deskew: undo a sweep's motion in many scans, in one call ---------------------------------------------------------------------------
+ * A spinning lidar takes 50 - 100 ms per sweep; the rows of one scan are taken from a moving sensor.  A deskewer carries every row into the sensor frame at ONE
+ * instant of the sweep, given the sweep's motion as a twist and a time (or a column index) per row.  It borrows a context like a store or a map (destroy it
+ * before the context), owns its memory and borrows only the stream.
+ * MOTION: a twist xi = (rho, phi), six doubles; T(s) = exp(s xi) = [exp(s phi^) | V(s phi) s rho] is the sensor's pose at sweep fraction s in the sensor frame
+ * at s = 0 (the store's POSE convention: p_0 = R p_s + t).  Under constant velocity over a frame period xi = log(icet_pose_step_from_x(X)).  A row taken at s
+ * is carried into the frame at s_ref (0: sweep start, 1: sweep end) by p' = exp((s - s_ref) xi) p.
+ * THE RULE (icet_amd/csrc/icet_deskew.h), per row i with float32 coordinates x, y, z; every operation IEEE double, rounded once, nothing contracted:
+ *   1. a non-finite coordinate: the row's bits are copied, class nonfinite;
+ *   2. x, y and z all 0 (either sign): the bits are copied (the invalid returns of a real scan stay exact zeros), class zero;
+ *   3. the row's time tau: ICET_DESKEW_TIME_ARRAY (double)time[i], a non-finite one copies the bits, class bad_time; ICET_DESKEW_TIME_COLUMN_FAST
+ *      (i mod period) + 0.5, period the columns of an organised scan whose ring index is the slow one; ICET_DESKEW_TIME_COLUMN_SLOW (i div period) + 0.5, period the
+ *      rows per column.  s = (tau - t0) inv_span: the caller takes the reciprocal of the span once;
+ *   4. d = s - s_ref, theta_a = d phi_a, u = (theta_x^2 + theta_y^2) + theta_z^2; unless u <= 1 the bits are copied, class out_of_range (more than one radian
+ *      between the row and the reference instant; a NaN twist or parameter ends here, on the host and in HBM alike: it is never refused);
+ *   5. A, B, C = the polynomials of degree 9 in u with the coefficients nearest to (-1)^k / (2k+1)!, / (2k+2)!, / (2k+3)!, by Horner from k = 9;
+ *   6. sigma_a = d rho_a; c1 = theta x p, c2 = theta x c1, r1 = theta x sigma, r2 = theta x r1, each component two products and one difference,
+ *      (a_y b_z - a_z b_y) and cyclic;
+ *   7. out_a = (float)(((p_a + A c1_a) + B c2_a) + ((sigma_a + B r1_a) + C r2_a)), class moved.  s outside [0, 1] is extrapolated as it stands.
+ * icet_deskew_device: n scans (HOST descriptors of DEVICE memory: src and dst N x 3 column-major float32 with leading dimensions ld and ld_out, 4-byte aligned,
+ *   padding never read or written; dst == src with ld_out == ld is the in-place form) in ONE launch, asynchronous on the context's stream.  d_twists: NULL, or
+ *   n x 6 DEVICE doubles that replace scans[k].twist; d_counts: NULL, or n DEVICE records, zeroed in stream order ahead of the launch.
+ * icet_deskew: the same for HOST pointers inside the descriptors and HOST counts (may be NULL); staged, synchronous.
+ * icet_deskew_twists_from_poses_device: d_twists[k] = scale log(T_k^-1 T_(k+1)), k = 0 .. n - 1, from n + 1 consecutive DEVICE float32 4 x 4 poses (what
+ *   icet_pose_graph_optimize_device leaves in d_poses_out; the inverse of a pose is the transpose of its rotation), so that optimiser -> twists -> deskew ->
+ *   icet_voxel_map_add_posed_device never leaves the device.  Valid for steps below 3 rad.  Asynchronous.
+ * icet_twist_from_pose / icet_pose_from_twist (T = exp(s xi)): HOST only, no context, row-major 4 x 4 doubles.  icet_debug_deskew_rows: HOST only, the
+ *   library's one compiled body of the rule over host arrays (x, y, z and out_x, out_y, out_z columns of n; time may be NULL outside array mode; cls n int32
+ *   or NULL).
+ * Refusals (ICET_ERR_BAD_ARG, the reason in icet_deskewer_last_error, nothing touched): a NULL handle or array, n < 0; a scan with n < 0, ld < n, ld_out < n
+ *   or either >= 2^30; a NULL src or dst with n > 0, a NULL time in array mode with n > 0; a misaligned device pointer; an unknown mode, period <= 0 in a column
+ *   mode; a dst that overlaps its src without being identical to it.  There is no CPU fall-back. */
+#define ICET_DESKEW_TIME_ARRAY 0
+#define ICET_DESKEW_TIME_COLUMN_FAST 1
+#define ICET_DESKEW_TIME_COLUMN_SLOW 2
+typedef struct icet_deskewer icet_deskewer;
+typedef struct icet_deskew_scan {
+    const float* src; int64_t n, ld;
+    float* dst; int64_t ld_out;
+    const float* time;            /* n floats, ICET_DESKEW_TIME_ARRAY only */
+    int32_t time_mode, period;
+    double t0, inv_span, s_ref;
+    double twist[6];              /* rho | phi */
+} icet_deskew_scan;               /* 128 bytes */
+typedef struct icet_deskew_counts {
+    int64_t moved, zero, nonfinite, bad_time, out_of_range, reserved[3];
+} icet_deskew_counts;             /* 64 bytes */
+icet_status icet_deskewer_create(icet_ctx* ctx, icet_deskewer** out);
+icet_status icet_deskewer_destroy(icet_deskewer* h);
+const char* icet_deskewer_last_error(const icet_deskewer* h);
+icet_status icet_deskew_device(icet_deskewer* h, int32_t n, const icet_deskew_scan* scans, const double* d_twists, icet_deskew_counts* d_counts);
+icet_status icet_deskew(icet_deskewer* h, int32_t n, const icet_deskew_scan* scans, icet_deskew_counts* counts);
+icet_status icet_deskew_twists_from_poses_device(icet_deskewer* h, int32_t n, const float* d_poses, double scale, double* d_twists);
+icet_status icet_twist_from_pose(const double T[16], double xi[6]);
+icet_status icet_pose_from_twist(const double xi[6], double s, double T[16]);
+icet_status icet_debug_deskew_rows(const icet_deskew_scan* motion, int64_t n, const float* x, const float* y, const float* z, const float* time,
+                                   float* out_x, float* out_y, float* out_z, int32_t* cls);
+
 /* Launch-shape and diagnostic knobs of ONE context (the library never reads the environment).  Defaults are the measured
  * optima.  Launch-shape knobs yield the same result bits; "force_exact", "guard_scale" and "lut_polar_quantile" preserve every
  * DECISION (the per-voxel counts n2_raw / n2_in) but move points between the 4-point runs and the runs of one, i.e. they regroup
