@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_voxel_map_add_posed_device", "icet_voxel_map_stats", "icet_voxel_map_extract_device", "icet_voxel_map_extract",
                     "icet_voxel_map_index", "icet_voxel_map_query_device", "icet_voxel_map_query_posed_device",
                     "icet_voxel_map_evidence_device", "icet_voxel_map_evidence_posed_device", "icet_voxel_map_evidence_fetch_device",
+                    "icet_voxel_map_enable_shape", "icet_voxel_map_extract_shape_device", "icet_voxel_map_extract_shape",
                     "icet_deskewer_create", "icet_deskewer_destroy", "icet_deskewer_last_error", "icet_deskew_device", "icet_deskew",
                     "icet_deskew_twists_from_poses_device", "icet_twist_from_pose", "icet_pose_from_twist", "icet_debug_deskew_rows",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
@@ -138,6 +139,28 @@ class MapEvidenceStats(C.Structure):
 class MapSubmap(C.Structure):
     """icet_voxel_map_submap (include/icet_hip.h), 40 bytes: a host descriptor of device memory."""
     _fields_ = [("xyz", C.c_void_p), ("ld", C.c_int64), ("cap_rows", C.c_int64), ("count", C.c_void_p), ("key", C.c_void_p)]
+
+
+class MapShape(C.Structure):
+    """icet_voxel_map_shape (include/icet_hip.h), 48 bytes: the shape columns of an extract_shape call, each column-major over ld; a pointer left out is None."""
+    _fields_ = [("cov", C.c_void_p), ("normal", C.c_void_p), ("evals", C.c_void_p), ("moments", C.c_void_p), ("ld", C.c_int64), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def cov_matrix(cov6):
+    """The symmetric 3 x 3 matrices of (..., 6) covariance rows in extract_shape's order xx, xy, xz, yy, yz, zz: an (..., 3, 3) array of the same dtype."""
+    c = np.asarray(cov6)
+    return c[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(c.shape[:-1] + (3, 3))
+
+
+def shape_features(evals):
+    """Linearity (l2 - l1) / l2, planarity (l1 - l0) / l2 and sphericity l0 / l2 from (..., 3) ASCENDING eigenvalues l0 <= l1 <= l2, as extract_shape writes
+    them: a dict of float64 arrays.  A cell whose largest eigenvalue is not positive (one row, or coincident rows) gives zeros."""
+    e = np.asarray(evals, np.float64)
+    l0, l1, l2 = e[..., 0], e[..., 1], e[..., 2]
+    ok = l2 > 0
+    den = np.where(ok, l2, 1.0)
+    return dict(linearity=np.where(ok, (l2 - l1) / den, 0.0), planarity=np.where(ok, (l1 - l0) / den, 0.0), sphericity=np.where(ok, l0 / den, 0.0))
 
 
 DESKEW_TIME_ARRAY, DESKEW_TIME_COLUMN_FAST, DESKEW_TIME_COLUMN_SLOW = 0, 1, 2      # ICET_DESKEW_TIME_*
@@ -585,6 +608,9 @@ def load_library():
     L.icet_voxel_map_evidence_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(MapEvidence), C.POINTER(MapEvidenceStats)]
     L.icet_voxel_map_evidence_posed_device.argtypes = L.icet_voxel_map_evidence_device.argtypes
     L.icet_voxel_map_evidence_fetch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.icet_voxel_map_enable_shape.argtypes = [C.c_void_p]
+    L.icet_voxel_map_extract_shape_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(MapShape), C.POINTER(MapStats)]
+    L.icet_voxel_map_extract_shape.argtypes = L.icet_voxel_map_extract_shape_device.argtypes
     L.icet_deskewer_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.icet_deskewer_destroy.argtypes = [C.c_void_p]
     L.icet_deskewer_last_error.argtypes = [C.c_void_p]; L.icet_deskewer_last_error.restype = C.c_char_p
@@ -1853,8 +1879,9 @@ class VoxelMap:
     device.  ``remove`` undoes an ``add`` at the same pose exactly, so a scan can be moved to a corrected pose; ``extract`` gives the cells sorted by key as a
     scan.  The map borrows ``ctx`` (closed before it)."""
 
-    def __init__(self, ctx, cell=0.1, min_range=0.0, max_range=0.0, table_log2=22):
+    def __init__(self, ctx, cell=0.1, min_range=0.0, max_range=0.0, table_log2=22, shape=False):
         self._ctx = ctx
+        self.shape = False
         self.params = MapParams(float(cell), float(min_range), float(max_range), int(table_log2), 0)
         h = C.c_void_p()
         st = load_library().icet_voxel_map_create(ctx._h, C.byref(self.params), C.byref(h))
@@ -1865,6 +1892,12 @@ class VoxelMap:
         if not hasattr(ctx, "_nodes"):
             ctx._nodes = []
         ctx._nodes.append(weakref.ref(self))
+        if shape:
+            try:
+                self.enable_shape()
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1945,6 +1978,39 @@ class VoxelMap:
         self._check(load_library().icet_voxel_map_extract(self._h, int(min_points), xyz.ctypes.data, max(cap, 1), cap, cnt.ctypes.data, key.ctypes.data, C.byref(s)))
         n = min(cap, s.cells_out)
         return dict(xyz=np.ascontiguousarray(xyz[:, :n].T), count=cnt[:n].copy(), key=key[:n].copy(), stats=s.as_dict())
+
+    def enable_shape(self):
+        """Carry nine integer moment words per cell from now on (icet_voxel_map_enable_shape), so that extract_shape gives a covariance,
+        eigenvalues and a normal per cell.  Only on a map that has read no row since it was created or last cleared; does nothing on a shaped map."""
+        self._check(load_library().icet_voxel_map_enable_shape(self._h))
+        self.shape = True
+
+    def extract_shape_device(self, d_xyz_ptr, ld, cap_rows, min_points=1, d_count_ptr=None, d_key_ptr=None, d_cov_ptr=None, d_normal_ptr=None, d_evals_ptr=None,
+                             d_moments_ptr=None, shape_ld=None):
+        """extract_device's rows, and per row the shape columns into device buffers, each column-major over ``shape_ld`` (default ld): d_cov 6 float32 columns (xx,
+        xy, xz, yy, yz, zz), d_normal 3, d_evals 3 (ascending), d_moments 9 uint64 columns (the raw words); any may be left out.  Returns the stats.  Synchronises."""
+        s = MapStats()
+        sh = MapShape(*[int(p) if p else None for p in (d_cov_ptr, d_normal_ptr, d_evals_ptr, d_moments_ptr)], int(ld if shape_ld is None else shape_ld), 0, 0)
+        self._check(load_library().icet_voxel_map_extract_shape_device(self._h, int(min_points), _vp(d_xyz_ptr), int(ld), int(cap_rows), _vp(d_count_ptr), _vp(d_key_ptr),
+                                                                       C.byref(sh), C.byref(s)))
+        return s.as_dict()
+
+    def extract_shape(self, min_points=1, cap_rows=None, moments=False):
+        """extract's dict, and cov (n, 6) float32, normal (n, 3) float32, evals (n, 3) float32 ascending; ``moments``: also the nine raw words, (n, 9) uint64."""
+        cap = self.stats(min_points)["cells_out"] if cap_rows is None else int(cap_rows)
+        ld = max(cap, 1)
+        xyz = np.zeros((3, ld), np.float32); cnt = np.zeros(ld, np.int64); key = np.zeros(ld, np.uint64)
+        cov = np.zeros((6, ld), np.float32); nrm = np.zeros((3, ld), np.float32); ev = np.zeros((3, ld), np.float32)
+        mom = np.zeros((9, ld), np.uint64) if moments else None
+        sh = MapShape(cov.ctypes.data, nrm.ctypes.data, ev.ctypes.data, mom.ctypes.data if moments else None, ld, 0, 0)
+        s = MapStats()
+        self._check(load_library().icet_voxel_map_extract_shape(self._h, int(min_points), xyz.ctypes.data, ld, cap, cnt.ctypes.data, key.ctypes.data, C.byref(sh), C.byref(s)))
+        n = min(cap, s.cells_out)
+        res = dict(xyz=np.ascontiguousarray(xyz[:, :n].T), count=cnt[:n].copy(), key=key[:n].copy(), cov=np.ascontiguousarray(cov[:, :n].T),
+                   normal=np.ascontiguousarray(nrm[:, :n].T), evals=np.ascontiguousarray(ev[:, :n].T), stats=s.as_dict())
+        if moments:
+            res["moments"] = np.ascontiguousarray(mom[:, :n].T)
+        return res
 
     def index(self):
         """Rebuild the sorted index the queries read, if the map changed since the last one (icet_voxel_map_index).  Returns the stats at min_points 1 as the

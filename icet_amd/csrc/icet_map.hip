@@ -8,6 +8,9 @@
 //     k_map_cells     a pass over the entries, 16 per thread: <false> counts the cells with count > 0, count >= min_points, count < 0 (tallied in LDS, one
 //                     atomic per block and counter); <true> compacts (key, entry) of the cells with count >= min_points (a block claims its places with one atomic)
 //     k_map_centroid  one thread per output row, behind rocPRIM's device radix sort of the pairs by key
+//     k_map_shape     (a shaped map: icet_voxel_map_enable_shape; the rule: icet_map_shape.h) one thread per output row behind k_map_centroid:
+//                     the cell's nine integer moment words, its covariance in double, six Jacobi sweeps for the eigenvalues and the normal.  k_map_add<., true>
+//                     carries the nine words beside the three sums through the run merge, the LDS table (kLdsSlotsShape cells), the flush and the direct path
 // and the query (icet_voxel_map_query_*; the rule: icet_map_query.h) over the INDEX, the extract's sequence kept as sorted arrays:
 //     k_map_query_count   a block reads a chunk of kQueryChunk consecutive cells once and tests them against every pose of the call (poses in LDS, wave64 ballots
 //                         and popcounts): one int32 per (query, chunk).  A query whose run of x cells misses the chunk's is not tested (option "map_query_prune")
@@ -30,12 +33,14 @@
 #include "icet_map.h"
 #include "icet_map_query.h"
 #include "icet_map_evidence.h"
+#include "icet_map_shape.h"
 
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 
 namespace icet {
 namespace {
@@ -43,11 +48,13 @@ namespace {
 namespace rule = icet_map_rule;
 namespace qrule = icet_map_query_rule;
 namespace erule = icet_map_evidence_rule;
+namespace srule = icet_map_shape_rule;
 typedef unsigned long long u64;
 
 constexpr int kAddBlock = 256;
 constexpr int kRowsPerBlock = 2048;      // a block's chunk of one scan: two trips of 256 lanes x 4 rows
 constexpr int kLdsSlots = 1024;          // 36 KB of LDS: key 8 | sums 24 | count 4 bytes per slot
+constexpr int kLdsSlotsShape = 512;      // a shaped block: 48 KB, key 8 | sums 24 | count 4 | S 12 (32-bit: 2048 rows x 65535 < 2^27) | M 48 bytes per slot
 constexpr int kLdsProbes = 8;
 constexpr int kCellBlock = 256;
 constexpr int kCellPer = 16;            // entries per thread of a pass over the table
@@ -64,6 +71,9 @@ struct MapScan { const float* ptr; int32_t n, ld, block0, pad; };      // block0
 static_assert(sizeof(MapScan) == 24, "ptr | n | ld | block0 | pad");
 // key[size] | count[size] (two's complement) | sum[3][size]
 struct MapTable { u64* key; u64* count; u64* sum; uint32_t log2; };
+// a shaped map's table (section 25): beside it mom[9][size], the words S_x S_y S_z M_xx M_xy M_xz M_yy M_yz M_zz.  The plain kernels take the plain struct.
+struct MapShapeTable : MapTable { u64* mom; };
+template <bool kShape> using TableOf = std::conditional_t<kShape, MapShapeTable, MapTable>;
 // the device record: kTotCopies copies of the running totals, one 64-byte line each (a block adds to copy blockIdx % kTotCopies, so that the blocks of a launch
 // do not all queue on one address; the host sums the copies), then what the last count pass saw and the select pass's cursor
 enum { kCtrIn = 0, kCtrKept, kCtrNonfinite, kCtrOutside, kCtrDropped, kTotWords = 8 };
@@ -75,7 +85,9 @@ enum { kCtrOccupied = kTotCopies * kTotWords, kCtrOut, kCtrNegative, kCtrSelecte
 
 // count += dn, sum_a += d_a in the cell of `key`, claimed on the way if it is new.  False: the probe run met neither the key nor a free entry (the table is full).
 // An entry's key changes once, from empty to its key, so a stale read of "empty" only costs the compare-and-swap that then returns the truth.
-__device__ __forceinline__ bool table_update(const MapTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2) {
+// more(h, size): what a shaped map adds behind the same claimed entry (table_update_shape); table_update adds nothing.
+template <class More>
+__device__ __forceinline__ bool table_update_and(const MapTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2, More&& more) {
     const u64 mask = ((u64)1 << t.log2) - 1;
     u64 h = rule::mix(key) & mask;                                    // h <= mask: inside every array
     for (u64 p = 0; p <= mask; p++) {
@@ -90,11 +102,23 @@ __device__ __forceinline__ bool table_update(const MapTable& t, u64 key, u64 dn,
             __hip_atomic_fetch_add(&t.sum[h], d0, MAP_RLX_AGENT);
             __hip_atomic_fetch_add(&t.sum[size + h], d1, MAP_RLX_AGENT);
             __hip_atomic_fetch_add(&t.sum[2 * size + h], d2, MAP_RLX_AGENT);
+            more(h, size);
             return true;
         }
         h = (h + 1) & mask;
     }
     return false;
+}
+
+__device__ __forceinline__ bool table_update(const MapTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2) {
+    return table_update_and(t, key, dn, d0, d1, d2, [](u64, u64) {});
+}
+// The shaped form: nine more relaxed agent-scope adds, mom[w] += dm[w], behind the same claimed entry.
+__device__ __forceinline__ bool table_update_shape(const MapShapeTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2, const u64* dm) {
+    return table_update_and(t, key, dn, d0, d1, d2, [&](u64 h, u64 size) {
+#pragma unroll
+        for (int w = 0; w < srule::kWords; w++) __hip_atomic_fetch_add(&t.mom[w * size + h], dm[w], MAP_RLX_AGENT);
+    });
 }
 
 // m <= 4 rows of one column from row i (a multiple of 4): one 16-byte load where the column's address allows it and all four rows exist.
@@ -108,12 +132,17 @@ __device__ __forceinline__ void load_rows(const float* __restrict__ col, int i, 
     }
 }
 
-template <bool kLds>
-__global__ __launch_bounds__(kAddBlock) void k_map_add(const MapScan* __restrict__ scans, int n_scans, const float* __restrict__ poses, rule::Consts kc, MapTable t,
+// kShape: the nine moment words travel with the three sums through every stage -- the lane's run, the LDS table (32-bit S, 64-bit M), the flush and the direct
+// path.  Every shaped statement is behind `if constexpr` and the plain kernels take the plain table: the <., false> instantiations are the kernel without shape.
+template <bool kLds, bool kShape>
+__global__ __launch_bounds__(kAddBlock) void k_map_add(const MapScan* __restrict__ scans, int n_scans, const float* __restrict__ poses, rule::Consts kc, TableOf<kShape> t,
                                                        u64 sign, u64* __restrict__ ctr) {
-    __shared__ u64 lkey[kLds ? kLdsSlots : 1];
-    __shared__ u64 lsum[3][kLds ? kLdsSlots : 1];
-    __shared__ uint32_t lcnt[kLds ? kLdsSlots : 1];
+    constexpr int kSlots = kLds ? (kShape ? kLdsSlotsShape : kLdsSlots) : 1;
+    __shared__ u64 lkey[kSlots];
+    __shared__ u64 lsum[3][kSlots];
+    __shared__ uint32_t lcnt[kSlots];
+    __shared__ uint32_t lS[3][kShape ? kSlots : 1];
+    __shared__ u64 lM[6][kShape ? kSlots : 1];
     __shared__ uint32_t lctr[5];
     __shared__ float sT[12];
     // the scan of this block: the last one whose first block is not behind it (a scan without rows has no block)
@@ -123,17 +152,20 @@ __global__ __launch_bounds__(kAddBlock) void k_map_add(const MapScan* __restrict
     const int row0 = ((int)blockIdx.x - sc.block0) * kRowsPerBlock;
     if (row0 < 0 || row0 >= sc.n) return;                             // (the same for every thread of the block)
     const int end = min(sc.n, row0 + kRowsPerBlock);
-    if (kLds) for (int s = threadIdx.x; s < kLdsSlots; s += kAddBlock) { lkey[s] = rule::kEmpty; lsum[0][s] = 0; lsum[1][s] = 0; lsum[2][s] = 0; lcnt[s] = 0u; }
+    if (kLds) for (int s = threadIdx.x; s < kSlots; s += kAddBlock) {
+        lkey[s] = rule::kEmpty; lsum[0][s] = 0; lsum[1][s] = 0; lsum[2][s] = 0; lcnt[s] = 0u;
+        if constexpr (kShape) { for (int a = 0; a < 3; a++) lS[a][s] = 0u; for (int j = 0; j < 6; j++) lM[j][s] = 0; }
+    }
     if (threadIdx.x < 5) lctr[threadIdx.x] = 0u;
     if (threadIdx.x < 12) sT[threadIdx.x] = poses[16 * (size_t)lo + threadIdx.x];
     __syncthreads();
     const float* cx = sc.ptr; const float* cy = cx + sc.ld; const float* cz = cx + 2 * (size_t)sc.ld;
     uint32_t n_in = 0, n_kept = 0, n_nonfinite = 0, n_outside = 0, n_dropped = 0;
 
-    // a run of rows of one cell: into the block's LDS table, or the global table
-    auto push = [&](u64 key, uint32_t c, u64 s0, u64 s1, u64 s2) {
+    // a run of rows of one cell: into the block's LDS table, or the global table.  rS / rM: the run's moment words (kShape; a run is at most 4 rows)
+    auto push = [&](u64 key, uint32_t c, u64 s0, u64 s1, u64 s2, const uint32_t* rS, const u64* rM) {
         if (kLds) {
-            uint32_t s = (uint32_t)(rule::mix(key) >> 40) & (kLdsSlots - 1);
+            uint32_t s = (uint32_t)(rule::mix(key) >> 40) & (kSlots - 1);
             for (int p = 0; p < kLdsProbes; p++) {
                 u64 expected = rule::kEmpty;
                 if (__hip_atomic_compare_exchange_strong(&lkey[s], &expected, key, __ATOMIC_RELAXED, MAP_RLX_WG) || expected == key) {
@@ -141,12 +173,27 @@ __global__ __launch_bounds__(kAddBlock) void k_map_add(const MapScan* __restrict
                     __hip_atomic_fetch_add(&lsum[0][s], s0, MAP_RLX_WG);
                     __hip_atomic_fetch_add(&lsum[1][s], s1, MAP_RLX_WG);
                     __hip_atomic_fetch_add(&lsum[2][s], s2, MAP_RLX_WG);
+                    if constexpr (kShape) {
+#pragma unroll
+                        for (int a = 0; a < 3; a++) __hip_atomic_fetch_add(&lS[a][s], rS[a], MAP_RLX_WG);
+#pragma unroll
+                        for (int j = 0; j < 6; j++) __hip_atomic_fetch_add(&lM[j][s], rM[j], MAP_RLX_WG);
+                    }
                     return;
                 }
-                s = (s + 1) & (kLdsSlots - 1);
+                s = (s + 1) & (kSlots - 1);
             }
         }
-        if (table_update(t, key, sign * c, sign * s0, sign * s1, sign * s2)) n_kept += c; else n_dropped += c;
+        if constexpr (kShape) {
+            u64 dm[srule::kWords];
+#pragma unroll
+            for (int a = 0; a < 3; a++) dm[a] = sign * (u64)rS[a];
+#pragma unroll
+            for (int j = 0; j < 6; j++) dm[3 + j] = sign * rM[j];
+            if (table_update_shape(t, key, sign * c, sign * s0, sign * s1, sign * s2, dm)) n_kept += c; else n_dropped += c;
+        } else {
+            if (table_update(t, key, sign * c, sign * s0, sign * s1, sign * s2)) n_kept += c; else n_dropped += c;
+        }
     };
 
     for (int i = row0 + 4 * (int)threadIdx.x; i < end; i += 4 * kAddBlock) {
@@ -155,24 +202,45 @@ __global__ __launch_bounds__(kAddBlock) void k_map_add(const MapScan* __restrict
         load_rows(cx, i, m, x); load_rows(cy, i, m, y); load_rows(cz, i, m, z);
         n_in += (uint32_t)m;
         u64 run_key = rule::kEmpty, r0 = 0, r1 = 0, r2 = 0; uint32_t run = 0;
+        uint32_t rS[3] = {0u, 0u, 0u}; u64 rM[6] = {0, 0, 0, 0, 0, 0};
         for (int r = 0; r < m; r++) {
             rule::Point pt;
             const int cls = rule::classify(kc, sT, x[r], y[r], z[r], pt);
             if (cls == rule::kRowNonfinite) n_nonfinite++;
             if (cls == rule::kRowOutside) n_outside++;
             if (cls != rule::kRowKept) continue;
-            if (run && pt.key != run_key) { push(run_key, run, r0, r1, r2); run = 0; r0 = 0; r1 = 0; r2 = 0; }
+            if (run && pt.key != run_key) {
+                push(run_key, run, r0, r1, r2, rS, rM); run = 0; r0 = 0; r1 = 0; r2 = 0;
+                if constexpr (kShape) { for (int a = 0; a < 3; a++) rS[a] = 0u; for (int j = 0; j < 6; j++) rM[j] = 0; }
+            }
             run_key = pt.key; run++; r0 += pt.q[0]; r1 += pt.q[1]; r2 += pt.q[2];
+            if constexpr (kShape) {
+                uint32_t hS[3], hM[6];
+                srule::row_moments(pt.q, hS, hM);
+#pragma unroll
+                for (int a = 0; a < 3; a++) rS[a] += hS[a];
+#pragma unroll
+                for (int j = 0; j < 6; j++) rM[j] += hM[j];
+            }
         }
-        if (run) push(run_key, run, r0, r1, r2);
+        if (run) push(run_key, run, r0, r1, r2, rS, rM);
     }
     if (kLds) {
         __syncthreads();
-        for (int s = threadIdx.x; s < kLdsSlots; s += kAddBlock) {
+        for (int s = threadIdx.x; s < kSlots; s += kAddBlock) {
             const u64 key = lkey[s];
             if (key == rule::kEmpty) continue;
             const uint32_t c = lcnt[s];
-            if (table_update(t, key, sign * c, sign * lsum[0][s], sign * lsum[1][s], sign * lsum[2][s])) n_kept += c; else n_dropped += c;
+            if constexpr (kShape) {
+                u64 dm[srule::kWords];
+#pragma unroll
+                for (int a = 0; a < 3; a++) dm[a] = sign * (u64)lS[a][s];
+#pragma unroll
+                for (int j = 0; j < 6; j++) dm[3 + j] = sign * lM[j][s];
+                if (table_update_shape(t, key, sign * c, sign * lsum[0][s], sign * lsum[1][s], sign * lsum[2][s], dm)) n_kept += c; else n_dropped += c;
+            } else {
+                if (table_update(t, key, sign * c, sign * lsum[0][s], sign * lsum[1][s], sign * lsum[2][s])) n_kept += c; else n_dropped += c;
+            }
         }
     }
     if (n_in) atomicAdd(&lctr[0], n_in);
@@ -242,6 +310,38 @@ __global__ __launch_bounds__(kCellBlock) void k_map_centroid(MapTable t, rule::C
     for (int a = 0; a < 3; a++) xyz[a * ld + i] = rule::centroid(kc, c[a], t.sum[a * size + e], n);
     if (d_count) d_count[i] = n;
     if (d_key) d_key[i] = key;
+}
+
+// The shape of row i, behind k_map_centroid over the same sorted cells: the nine words of the cell, its covariance, its eigenvalues and
+// its normal.  Any of the four outputs may be null; all are column-major over ld.
+struct MapShapeOut { float* cov; float* normal; float* evals; u64* moments; long long ld; };
+__global__ __launch_bounds__(kCellBlock) void k_map_shape(MapShapeTable t, srule::Consts kc, const uint32_t* __restrict__ idx, long long rows, MapShapeOut o) {
+    const long long i = (long long)blockIdx.x * kCellBlock + threadIdx.x;
+    if (i >= rows) return;
+    const u64 e = idx[i], size = (u64)1 << t.log2;                    // e < size: an entry's index, as in k_map_centroid
+    const long long n = (long long)t.count[e];
+    uint64_t w[srule::kWords];
+#pragma unroll
+    for (int j = 0; j < srule::kWords; j++) w[j] = t.mom[j * size + e];
+    if (o.moments) {
+#pragma unroll
+        for (int j = 0; j < srule::kWords; j++) o.moments[j * o.ld + i] = w[j];      // i < rows <= cap_rows <= ld: inside the caller's columns
+    }
+    if (!o.cov && !o.normal && !o.evals) return;
+    double C[6];
+    srule::cov(kc, n, w, C);
+    if (o.cov) {
+#pragma unroll
+        for (int j = 0; j < 6; j++) o.cov[j * o.ld + i] = (float)C[j];
+    }
+    if (!o.normal && !o.evals) return;
+    float ev[3], nm[3];
+    srule::eigen(C, ev, nm);
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        if (o.evals) o.evals[a * o.ld + i] = ev[a];
+        if (o.normal) o.normal[a * o.ld + i] = nm[a];
+    }
 }
 
 // ---- the query: sub-maps around poses, out of the sorted index ---------------------------------------------------------------------------
@@ -555,6 +655,10 @@ struct icet_voxel_map {
     CallStage<MapSubmap> query;                                       // a query: the output descriptors and poses
     SortedCells x_cells;                                              // an extract: its sorted cells; the rows of the host form
     float* x_xyz = nullptr; long long* x_count = nullptr; u64* x_key = nullptr; int64_t cap_x = 0;
+    // the shape of section 25: mom[9][size] beside the table once icet_voxel_map_enable_shape has run (null: a plain map); dirty: an add or remove has read rows
+    // since the map was created or last cleared; the rows of the host form of extract_shape: 12 float and 9 word columns of cap_xs rows
+    u64* mom = nullptr; bool dirty = false;
+    float* xs_f = nullptr; u64* xs_w = nullptr; int64_t cap_xs = 0;
     // the index of the queries: the cells of count >= 1 by key -- the key is ix_cells.key, beside it count and three columns of cap_ix centroid floats --; what
     // the build saw; stale after every add, remove and clear
     SortedCells ix_cells; long long* ix_count = nullptr; float* ix_xyz = nullptr; int64_t cap_ix = 0, ix_n = 0;
@@ -567,7 +671,8 @@ struct icet_voxel_map {
     uint32_t* ev_img = nullptr; uint32_t* ev_near = nullptr; int64_t cap_img = 0;
     u64* ev_ctr = nullptr; u64* ev_h_ctr = nullptr; int32_t cap_evrec = 0;
     bool ev_valid = false;
-    BufferGroup table, record, xout, index, qcounts, evidence, evimages, evrecord;
+    BufferGroup table, record, xout, index, qcounts, evidence, evimages, evrecord, moments, xshape;
+    MapShapeTable shape_table() const { MapShapeTable s; static_cast<MapTable&>(s) = t; s.mom = mom; return s; }
 };
 
 #define MAPCHK(m, call) do { const hipError_t e_ = static_cast<hipError_t>(call); if (e_ != hipSuccess) { \
@@ -591,7 +696,9 @@ static icet_status map_clear(icet_voxel_map* m) {
     MAPCHK(m, hipMemsetAsync(m->t.key, 0xFF, sizeof(u64) * size, st));
     MAPCHK(m, hipMemsetAsync(m->t.count, 0, sizeof(u64) * size, st));
     MAPCHK(m, hipMemsetAsync(m->t.sum, 0, sizeof(u64) * 3 * size, st));
+    if (m->mom) MAPCHK(m, hipMemsetAsync(m->mom, 0, sizeof(u64) * srule::kWords * size, st));
     MAPCHK(m, hipMemsetAsync(m->ctr, 0, sizeof(u64) * kCtrWords, st));
+    m->dirty = false;
     return ICET_OK;
 }
 
@@ -629,7 +736,7 @@ static icet_status map_add(icet_voxel_map* m, int32_t n, const icet_dev_scan* sc
     if (blocks > 0x7FFFFFFF) return map_refuse(m, std::string(call) + ": too many rows in one call");
     if (blocks == 0) return ICET_OK;                                  // nothing to read
     icet_ctx* c = m->ctx;
-    m->ix_stale = true;                                               // (from here on the table may change)
+    m->ix_stale = true; m->dirty = true;                              // (from here on the table may change)
     CallStage<MapScan>& s = m->add;
     MAPCHK(m, s.begin(n, c->stream));
     int32_t b0 = 0;
@@ -640,8 +747,12 @@ static icet_status map_add(icet_voxel_map* m, int32_t n, const icet_dev_scan* sc
     const float* dp = nullptr;
     MAPCHK(m, s.upload(n, poses, poses_on_device, c->stream, &dp));
     const u64 sg = sign > 0 ? (u64)1 : ~(u64)0;                       // -1 in two's complement
-    if (c->map_lds) k_map_add<true><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, m->t, sg, m->ctr);
-    else k_map_add<false><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, m->t, sg, m->ctr);
+    if (m->mom) {
+        const MapShapeTable ts = m->shape_table();
+        if (c->map_lds) k_map_add<true, true><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, ts, sg, m->ctr);
+        else k_map_add<false, true><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, ts, sg, m->ctr);
+    } else if (c->map_lds) k_map_add<true, false><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, m->t, sg, m->ctr);
+    else k_map_add<false, false><<<(unsigned)blocks, kAddBlock, 0, c->stream>>>(s.d_rec, n, dp, m->k, m->t, sg, m->ctr);
     MAPCHK(m, hipGetLastError());
     MAPCHK(m, s.mark_read(c->stream));
     return ICET_OK;
@@ -675,12 +786,20 @@ static icet_status map_sorted_cells(icet_voxel_map* m, SortedCells& sc, int64_t 
     return ICET_OK;
 }
 
+// shaped (extract_shape, section 25): the same rows, and behind k_map_centroid the columns of *shape from k_map_shape.
 static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_host, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
-                               struct icet_voxel_map_stats* out, const char* call) {
+                               bool shaped, const icet_voxel_map_shape* shape, struct icet_voxel_map_stats* out, const char* call) {
     ICET_TRY(enter(m));
     if (cap_rows < 0 || ld < cap_rows || (cap_rows > 0 && !xyz)) return map_refuse(m, std::string(call) + ": bad argument (cap_rows >= 0, ld >= cap_rows, a buffer of rows)");
     if (!to_host && !(elem_aligned(xyz) && elem_aligned(count) && elem_aligned(key)))
         return map_refuse(m, std::string(call) + ": a device pointer is not aligned to its element");
+    if (shaped) {
+        if (!m->mom) return map_refuse(m, std::string(call) + ": the map has no shape (icet_voxel_map_enable_shape on an empty map)");
+        if (!shape) return map_refuse(m, std::string(call) + ": bad argument (a NULL shape descriptor)");
+        if (shape->ld < cap_rows || shape->flags != 0 || shape->reserved != 0) return map_refuse(m, std::string(call) + ": bad shape descriptor (ld >= cap_rows, flags and reserved 0)");
+        if (!to_host && !(elem_aligned(shape->cov) && elem_aligned(shape->normal) && elem_aligned(shape->evals) && elem_aligned(shape->moments)))
+            return map_refuse(m, std::string(call) + ": a device pointer is not aligned to its element");
+    }
     hipStream_t st = m->ctx->stream;
     struct icet_voxel_map_stats s;
     ICET_TRY(map_count(m, min_points, &s));
@@ -696,6 +815,10 @@ static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_ho
                 return e;
             }));
         }
+        if (shaped && to_host && rows > m->cap_xs) {
+            BufferGroup& g = m->xshape;
+            MAPCHK(m, grow(g, m->cap_xs, rows, [&] { const int e = g.device(m->xs_f, 12 * (size_t)rows); return e ? e : g.device(m->xs_w, srule::kWords * (size_t)rows); }));
+        }
         ICET_TRY(map_sorted_cells(m, m->x_cells, n_out, std::max(1, min_points), 0));
         float* dx = to_host ? m->x_xyz : xyz;
         long long* dc = to_host ? (count ? m->x_count : nullptr) : reinterpret_cast<long long*>(count);
@@ -703,6 +826,21 @@ static icet_status map_extract(icet_voxel_map* m, int32_t min_points, bool to_ho
         const long long dld = to_host ? rows : ld;
         k_map_centroid<<<(unsigned)((rows + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->t, m->k, m->x_cells.key, m->x_cells.idx, rows, dx, dld, dc, dk);
         MAPCHK(m, hipGetLastError());
+        if (shaped) {
+            // the host form: cov | normal | evals in 6 + 3 + 3 columns of `rows` floats, the words in 9 columns; a column the caller left out is not computed
+            MapShapeOut o{shape->cov, shape->normal, shape->evals, reinterpret_cast<u64*>(shape->moments), (long long)shape->ld};
+            if (to_host) o = MapShapeOut{shape->cov ? m->xs_f : nullptr, shape->normal ? m->xs_f + 6 * rows : nullptr, shape->evals ? m->xs_f + 9 * rows : nullptr,
+                                         shape->moments ? m->xs_w : nullptr, (long long)rows};
+            k_map_shape<<<(unsigned)((rows + kCellBlock - 1) / kCellBlock), kCellBlock, 0, st>>>(m->shape_table(), srule::make_consts(m->params.cell), m->x_cells.idx, rows, o);
+            MAPCHK(m, hipGetLastError());
+            if (to_host) {
+                const size_t wf = sizeof(float) * (size_t)rows, ww = sizeof(u64) * (size_t)rows, sld = (size_t)shape->ld;
+                if (shape->cov) MAPCHK(m, hipMemcpy2DAsync(shape->cov, sizeof(float) * sld, o.cov, wf, wf, 6, hipMemcpyDeviceToHost, st));
+                if (shape->normal) MAPCHK(m, hipMemcpy2DAsync(shape->normal, sizeof(float) * sld, o.normal, wf, wf, 3, hipMemcpyDeviceToHost, st));
+                if (shape->evals) MAPCHK(m, hipMemcpy2DAsync(shape->evals, sizeof(float) * sld, o.evals, wf, wf, 3, hipMemcpyDeviceToHost, st));
+                if (shape->moments) MAPCHK(m, hipMemcpy2DAsync(shape->moments, sizeof(u64) * sld, o.moments, ww, ww, srule::kWords, hipMemcpyDeviceToHost, st));
+            }
+        }
         if (to_host) {
             MAPCHK(m, hipMemcpy2DAsync(xyz, sizeof(float) * (size_t)ld, dx, sizeof(float) * (size_t)rows, sizeof(float) * (size_t)rows, 3, hipMemcpyDeviceToHost, st));
             if (count) MAPCHK(m, hipMemcpyAsync(count, dc, sizeof(int64_t) * (size_t)rows, hipMemcpyDeviceToHost, st));
@@ -983,12 +1121,35 @@ icet_status icet_voxel_map_stats(icet_voxel_map* m, int32_t min_points, struct i
 
 icet_status icet_voxel_map_extract_device(icet_voxel_map* m, int32_t min_points, float* d_xyz, int64_t ld, int64_t cap_rows, int64_t* d_count, uint64_t* d_key,
                                           struct icet_voxel_map_stats* out) {
-    return map_extract(m, min_points, false, d_xyz, ld, cap_rows, d_count, d_key, out, "icet_voxel_map_extract_device");
+    return map_extract(m, min_points, false, d_xyz, ld, cap_rows, d_count, d_key, false, nullptr, out, "icet_voxel_map_extract_device");
 }
 
 icet_status icet_voxel_map_extract(icet_voxel_map* m, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
                                    struct icet_voxel_map_stats* out) {
-    return map_extract(m, min_points, true, xyz, ld, cap_rows, count, key, out, "icet_voxel_map_extract");
+    return map_extract(m, min_points, true, xyz, ld, cap_rows, count, key, false, nullptr, out, "icet_voxel_map_extract");
+}
+
+icet_status icet_voxel_map_enable_shape(icet_voxel_map* m) {
+    ICET_TRY(enter(m));
+    if (m->mom) return ICET_OK;
+    if (m->dirty) return map_refuse(m, "icet_voxel_map_enable_shape: the map has read rows since it was created or last cleared (enable shape on an empty map)");
+    const size_t size = (size_t)1 << m->t.log2;
+    const int e = m->moments.device(m->mom, srule::kWords * size);      // (a refused allocation leaves the slot null: the map stays plain)
+    if (e) { (void)hipGetLastError(); m->err = std::string("icet_voxel_map_enable_shape: ") + hipGetErrorString(static_cast<hipError_t>(e)); return e == hipErrorOutOfMemory ? ICET_ERR_NOMEM : ICET_ERR_HIP; }
+    const hipError_t z = hipMemsetAsync(m->mom, 0, sizeof(u64) * srule::kWords * size, m->ctx->stream);
+    if (z != hipSuccess) m->moments.release();
+    MAPCHK(m, z);
+    return ICET_OK;
+}
+
+icet_status icet_voxel_map_extract_shape_device(icet_voxel_map* m, int32_t min_points, float* d_xyz, int64_t ld, int64_t cap_rows, int64_t* d_count, uint64_t* d_key,
+                                                const icet_voxel_map_shape* shape, struct icet_voxel_map_stats* out) {
+    return map_extract(m, min_points, false, d_xyz, ld, cap_rows, d_count, d_key, true, shape, out, "icet_voxel_map_extract_shape_device");
+}
+
+icet_status icet_voxel_map_extract_shape(icet_voxel_map* m, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
+                                         const icet_voxel_map_shape* shape, struct icet_voxel_map_stats* out) {
+    return map_extract(m, min_points, true, xyz, ld, cap_rows, count, key, true, shape, out, "icet_voxel_map_extract_shape");
 }
 
 icet_status icet_voxel_map_index(icet_voxel_map* m, struct icet_voxel_map_stats* out) {

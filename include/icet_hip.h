@@ -817,7 +817,7 @@ icet_status icet_debug_block_tridiag(icet_ctx* ctx, int32_t n, const double* dia
 
 /* --- the voxel map: many scans, each at a pose, fused into one centroid and one count per occupied cell, in HBM ---------------------
  * A map borrows a context like a keyframe store (destroy it before the context) and owns its memory: an open-addressing hash table of 2^table_log2 entries
- * of 40 bytes (key, count, three offset sums, all 64-bit integers).  THE RULE, for a row (x, y, z) of a scan at the pose T = [R | t] (4 x 4 row-major
+ * of 40 bytes (key, count, three offset sums, all 64-bit integers; 72 bytes more once icet_voxel_map_enable_shape has run: "the voxel map's shape" below).  THE RULE, for a row (x, y, z) of a scan at the pose T = [R | t] (4 x 4 row-major
  * float32, p_world = R p + t), every operation IEEE double, rounded once, nothing contracted:
  *   1. a row with a non-finite coordinate is counted in points_nonfinite and skipped;
  *   2. d2 = (x x + y y) + z z; the row is kept iff d2 > min_range^2 and (max_range <= 0 or d2 <= max_range^2) -- at min_range = 0 exactly the all-zero rows go;
@@ -973,6 +973,41 @@ icet_status icet_voxel_map_evidence_device(icet_voxel_map* map, int32_t n, const
 icet_status icet_voxel_map_evidence_posed_device(icet_voxel_map* map, int32_t n, const icet_dev_scan* scans, const float* d_poses, const icet_voxel_map_evidence* e,
                                                  struct icet_voxel_map_evidence_stats* out);
 icet_status icet_voxel_map_evidence_fetch_device(icet_voxel_map* map, int32_t* d_miss, int32_t* d_agree, uint8_t* d_transient, int64_t cap, int64_t* rows_out);
+
+/* --- the voxel map's shape: a covariance, its eigenvalues and a normal per cell, from integer second moments ---------------------------
+ * A plain map knows where a surface is; a SHAPED map also knows how its points lie in each cell.  THE RULE (icet_amd/csrc/icet_map_shape.h), for a kept row with
+ * the offsets q_a of step 4 of the map's rule: h_a = q_a >> 16 (0 .. 65535); beside count and sum the cell of the key gets nine more 64-bit two's-complement words,
+ *   S_x S_y S_z M_xx M_xy M_xz M_yy M_yz M_zz:   S_a += sign h_a,   M_ab += sign h_a h_b.
+ * h_a h_b < 2^32, so a cell still holds 2^32 rows; the resolution is cell / 65536.  The words are sums of integers: they depend on the multiset of (row, pose,
+ * sign) only, and remove at the old pose + add at the corrected one is a rebuild, bit for bit, moments included.
+ * COVARIANCE of a cell of count n >= 1, in the world frame, every operation IEEE double, rounded once, nothing contracted, u64 -> double to nearest even:
+ *   m_a = (double)S_a / (double)n, E_ab = (double)M_ab / (double)n, k = (double)cell 2^-16, k2 = k k, C_ab = (E_ab - m_a m_b) k2; cov = (float)C in the order
+ *   xx, xy, xz, yy, yz, zz.  No quantisation correction.  A cell of one row gives exactly zero.
+ * EIGENVALUES AND NORMAL: a cyclic Jacobi on the double C with V = I at the start, 6 sweeps over the pairs (0,1), (0,2), (1,2); a pair with C_pq == 0 is
+ *   skipped; theta = (C_qq - C_pp) / (2 C_pq), t = sgn(theta) / (|theta| + sqrt(theta theta + 1)) with sgn(0) = +1, c = 1 / sqrt(t t + 1), s = t c.  evals: the
+ *   diagonal ascending, as computed (a tiny negative value stays negative), float32.  normal: the column of V of the smallest eigenvalue, ties to the lowest
+ *   column, rounded to float32, then signed so that its component of largest magnitude is positive, the lowest axis winning a tie.  One row: zeros and (1, 0, 0).
+ * ENABLE: icet_voxel_map_enable_shape allocates and zeroes the words (72 bytes per entry more) on a map that has read no row since it was created or last
+ *   cleared -- else ICET_ERR_BAD_ARG --, and does nothing on a shaped map.  ICET_ERR_NOMEM when the allocation fails: the map stays plain.  From then on add and
+ *   remove carry the words (both forms of option "map_lds"), clear zeroes them, and extract, stats, index, the queries and the evidence read the map as before.
+ * EXTRACT_SHAPE: extract's rows -- the same cells, order, bits of xyz / count / key, and TRUNCATED rule -- and per row the columns of *shape, each column-major
+ *   over shape->ld >= cap_rows; any of the four pointers may be NULL.  extract_shape_device takes DEVICE pointers, extract_shape HOST pointers; both synchronise.
+ * Refusals (ICET_ERR_BAD_ARG, nothing touched): extract's, a map without shape, a NULL descriptor, shape->ld < cap_rows, nonzero flags or reserved, a misaligned
+ *   device pointer.  No CPU fall-back. */
+typedef struct icet_voxel_map_shape {
+    float* cov;                   /* 6 columns: xx xy xz yy yz zz, square metres */
+    float* normal;                /* 3 columns */
+    float* evals;                 /* 3 columns, ascending */
+    uint64_t* moments;            /* 9 columns: the raw words */
+    int64_t ld;                   /* >= cap_rows */
+    int32_t flags;                /* 0 */
+    int32_t reserved;             /* 0 */
+} icet_voxel_map_shape;           /* 48 bytes */
+icet_status icet_voxel_map_enable_shape(icet_voxel_map* map);
+icet_status icet_voxel_map_extract_shape_device(icet_voxel_map* map, int32_t min_points, float* d_xyz, int64_t ld, int64_t cap_rows, int64_t* d_count, uint64_t* d_key,
+                                                const icet_voxel_map_shape* shape, struct icet_voxel_map_stats* out);
+icet_status icet_voxel_map_extract_shape(icet_voxel_map* map, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
+                                         const icet_voxel_map_shape* shape, struct icet_voxel_map_stats* out);
 
 /* --- deskew: undo a sweep's motion in many scans, in one call ---------------------------------------------------------------------------
  * A spinning lidar takes 50 - 100 ms per sweep; the rows of one scan are taken from a moving sensor.  A deskewer carries every row into the sensor frame at ONE
