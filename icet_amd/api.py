@@ -28,7 +28,7 @@ FLAG_HALF_GAP_BOUNDS = 8  # non-parity extension (half-gap cluster buffers of th
 
 # every symbol include/icet_hip.h, include/icet_nodes.h and include/icet_io.h declare
 EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_version", "icet_solve", "icet_solve_begin", "icet_solve_keyframe_tables", "icet_solve_end", "icet_solve_batch",
-                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_debug_point_sums_device", "icet_debug_gn_terms_device", "icet_debug_fix", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
+                    "icet_solve_batch_device", "icet_sync", "icet_reserve", "icet_last_timing", "icet_last_timing_iters", "icet_keep_stats", "icet_debug_fetch", "icet_debug_gn_tail", "icet_debug_pinv3", "icet_debug_pinv3_double", "icet_debug_point_sums_device", "icet_debug_gn_terms_device", "icet_debug_fix", "icet_debug_spherical", "icet_set_option", "icet_keyframe_device", "icet_register_device", "icet_keyframe_device_n", "icet_register_device_n", "icet_register_indexed_device", "icet_solve_indexed", "icet_score_indexed_device", "icet_register_indexed_scored_device", "icet_solve_indexed_scored", "icet_score_indexed", "icet_select_best_device",
                     "icet_keyframe_store_create", "icet_keyframe_store_destroy", "icet_keyframe_store_last_error", "icet_keyframe_store_reserve", "icet_keyframe_store_put_device",
                     "icet_keyframe_store_register_device", "icet_keyframe_store_register_scored_device", "icet_keyframe_store_score_device", "icet_keyframe_store_debug_fetch",
                     "icet_keyframe_store_set_pose", "icet_keyframe_store_candidates_device", "icet_keyframe_store_close_device", "icet_pose_step_from_x",
@@ -530,6 +530,7 @@ def load_library():
     L.icet_debug_point_sums_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
     L.icet_debug_gn_terms_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icet_debug_fix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.icet_debug_spherical.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.icet_keyframe_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan)]
     L.icet_register_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p, C.c_void_p]
     L.icet_keyframe_device_n.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.POINTER(DevScan), C.c_void_p]
@@ -1242,6 +1243,15 @@ class Context:
         out = np.zeros((v.shape[0], 3), np.uint64)
         self._check(load_library().icet_debug_fix(self._h, v.ctypes.data, v.shape[0], out.ctypes.data))
         return out
+
+    def debug_spherical(self, xyz, num_bins_theta=75, num_bins_phi=24):
+        """icet_debug_spherical (test hook): N x 3 rows through the device functions of the shared arithmetic rule.  Returns dict of float32 (N, k) arrays (voxel: int32
+        (N,)): sph = r | theta | phi of c2s_cr, voxel = voxel_of(theta, phi), rt_any = x | y | z of roundtrip_any, cr_ang = theta | phi and cr = x | y | z of
+        roundtrip_cr called directly (NaN for rows whose r is 0 or not finite)."""
+        s = _colmajor(xyz); n = s.shape[1]
+        out = np.zeros((12, n), np.float32)
+        self._check(load_library().icet_debug_spherical(self._h, s.ctypes.data, n, n, int(num_bins_theta), int(num_bins_phi), out.ctypes.data))
+        return dict(sph=out[0:3].T.copy(), voxel=out[3].view(np.int32).copy(), rt_any=out[4:7].T.copy(), cr_ang=out[7:9].T.copy(), cr=out[9:12].T.copy())
 
     def debug_gn_tail(self, htwh, htwdz):
         """icet_debug_gn_tail (test hook): the 6x6 tail of an iteration on the device for n (HTWH, HTWdz).  Returns dict of arrays with leading dimension n:

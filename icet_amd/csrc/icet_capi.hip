@@ -1499,6 +1499,25 @@ icet_status icet_debug_fix(icet_ctx* c, const float* v, int32_t n, uint64_t* out
     return ICET_OK;
 }
 
+// Test hook: the device functions of the shared arithmetic rule (icet_device_common.h: c2s_cr, voxel_of, roundtrip_any, roundtrip_cr) on n host-side rows x[n] | y[n] | z[n]
+// with leading dimension ld; out: 12 columns of n 32-bit words (k_spherical_debug, icet_keyframe.hip).
+icet_status icet_debug_spherical(icet_ctx* c, const float* xyz, int32_t n, int32_t ld, int32_t T, int32_t P, float* out) {
+    if (!c) return ICET_ERR_BAD_ARG;
+    if (!xyz || !out || n < 0 || ld < n || T < 1 || P < 1) { c->err = "icet_debug_spherical: bad argument"; return ICET_ERR_BAD_ARG; }
+    if (n == 0) return ICET_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    float* d = nullptr; BufferGroup g;
+    HIPCHK(c, g.device(d, (size_t)n * 15));
+    float* d_o = d + (size_t)n * 3;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 3 && e == hipSuccess; k++) e = hipMemcpyAsync(d + (size_t)n * k, xyz + (size_t)ld * k, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_spherical_debug(d, n, n, T, P, d_o, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, sizeof(float) * (size_t)n * 12, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("icet_debug_spherical: ") + hipGetErrorString(e); return ICET_ERR_HIP; }
+    return ICET_OK;
+}
+
 icet_status icet_set_option(icet_ctx* c, const char* name, double value) {
     if (!c || !name) return ICET_ERR_BAD_ARG;
     Tuning& t = c->tune;

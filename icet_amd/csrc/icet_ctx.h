@@ -254,7 +254,7 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            icet_voxel_map_evidence_device, _evidence_posed_device (the same, and when their buffers grow or *out is asked for), _evidence_fetch_device
 //                            icet_deskewer_create, icet_deskew_device, icet_deskew_twists_from_poses_device (drain only when the records' stage grows); icet_deskew (drains as well; icet_deskew.hip)
 //   arms or disarms itself   icet_solve_batch_device
-//   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_block_tridiag (copy in, one kernel, copy out,
+//   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_spherical, icet_debug_block_tridiag (copy in, one kernel, copy out,
 //                            synchronise); icet_debug_fetch, icet_keyframe_store_debug_fetch, icet_keep_stats (synchronise, then blocking copies);
 //                            icet_last_timing[_iters] (synchronise); icet_solve_end; icet_keyframe_store_reserve, _enable_appearance, _enable_coarse, _destroy;
 //                            icet_voxel_map_destroy; icet_deskewer_destroy; icet_destroy; icet_sync (the only one that re-arms: armed_calls = 0; icet_solve_indexed and its kin do the same behind their own drain)

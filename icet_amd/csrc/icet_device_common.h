@@ -114,9 +114,31 @@ __device__ __forceinline__ void voxel_limits(int theta, int phi, int T, int P, f
 
 // cartesianToSpherical followed by sphericalToCartesian (src/utils.cpp:93-142) for one finite point with r > 0, under the
 // shared rule: th = fl(atan2), ph = fl(acos(z / r)), out = (r sin ph cos th, r sin ph sin th, r cos ph) with the four
-// sines / cosines correctly rounded -- WITHOUT a double sin / cos.  With a_d the double angle and a_f its float rounding
+// sines / cosines correctly rounded -- on the common path WITHOUT a double sin / cos.  With a_d the double angle and a_f its float rounding
 // (plus the wrap of theta), sin a_f = sin(a_d + d) = sin a_d (1 - d^2/2) + cos a_d d, and sin a_d, cos a_d are algebraic in
 // the Cartesian inputs (y / rho, x / rho; sqrt(1 - q^2), q).  |d| < 5e-7, so the dropped d^3 term is below 1e-20.
+// The error of that form is ABSOLUTE: d is taken against the library's angle, whose own error (assumed <= 2 ulp of a double in [4, 8), 1.8e-15) enters through
+// cos a_d d, plus three roundings of values <= 1 -- 2.1e-15 in all, whatever the size of the result.  Against a float's ulp that is harmless while the result is large
+// and decides the float when it is tiny: sin(float(pi)) = -8.742278e-08 lies 1.2e-16 from a rounding boundary, and a row whose azimuth rounds to float(pi) got the wrong
+// float in 17 % (-x) to 45 % (+y) of all cases (measured on the device).  So a sine or cosine below kTrigSmall = 2^-10 in magnitude is taken again in double from
+// the FLOAT angle a itself (trig_small): a lies within 2^-9 of a multiple k of pi / 2, the tiny value is +-sin(a - k pi/2), the reduction against pi/2 = head + tail
+// (a 33-bit head: k head and a - k head are exact) leaves a relative error of 2^-53, and four terms of the sine series another.  That error is RELATIVE -- millions of
+// double ulps clear of those boundaries -- and the product form returns the literal formula's sign of zero (sin(-0) = -0, where the algebraic form gives +0).
+// At and above 2^-10 a float's ulp is at least 2^-33 = 1.2e-10, so at most 2 x 2.1e-15 / 1.2e-10 = 3.6e-5 of the values there lie within the algebraic form's error
+// of a boundary, falling as 1 / |value|.  (The same recomputation as an out-of-line call of the library's sin / cos cost k_fit_roundtrip 8 spilled VGPRs at its
+// 128-register budget; inline it costs none, and only lanes with a tiny value execute it.)
+constexpr float kTrigSmall = 0x1p-10f;
+constexpr double kPio2Head = 0x1.921fb544p+0;                    // pi / 2 to 33 bits
+constexpr double kPio2Tail = 0x1.0b4611a626331p-34;              // pi / 2 - kPio2Head (what is left is below 4e-27)
+// The tiny one of sin a / cos a (want_cos) for a float angle a in [-0, 2 pi] within 2^-9 of k pi / 2 (k even for the sine, odd for the cosine).
+__device__ __forceinline__ float trig_small(float a, bool want_cos) {
+    const int k = __float2int_rn(a * 0.63661977f);
+    const double kd = (double)k;
+    const double r = ((double)a - kd * kPio2Head) - kd * kPio2Tail;
+    const double r2 = r * r;
+    const double s = r * (1.0 + r2 * (-1.0 / 6.0 + r2 * (1.0 / 120.0 - r2 * (1.0 / 5040.0))));      // sin r, |r| < 2^-9: the next term is below 2^-60 relative
+    return (float)((((k & 2) != 0) != want_cos) ? -s : s);          // sin(r + k pi/2) = +s, -s for k = 0 (4), 2; cos(r + k pi/2) = -s, +s for k = 1, 3
+}
 __device__ __forceinline__ void roundtrip_cr(float x, float y, float z, float r_raw, float& th, float& ph, float& ox, float& oy, float& oz) {
     const double xd = (double)x, yd = (double)y;
     const double td = atan2(yd, xd);
@@ -139,7 +161,11 @@ __device__ __forceinline__ void roundtrip_cr(float x, float y, float z, float r_
     const double hph = 0.5 * dph * dph;
     const double sp = sp0 + (qd * dph - sp0 * hph);
     const double cp = qd - (sp0 * dph + qd * hph);
-    const float stf = (float)st, ctf = (float)ct, spf = (float)sp, cpf = (float)cp;
+    float stf = (float)st, ctf = (float)ct, spf = (float)sp, cpf = (float)cp;
+    if (fabsf(stf) < kTrigSmall) stf = trig_small(th, false);    // rare: a row near an axis, the horizontal plane or a pole
+    if (fabsf(ctf) < kTrigSmall) ctf = trig_small(th, true);
+    if (fabsf(spf) < kTrigSmall) spf = trig_small(ph, false);
+    if (fabsf(cpf) < kTrigSmall) cpf = trig_small(ph, true);
     {
 #pragma clang fp contract(off)
         ox = r_raw * spf * ctf;                                  // src/utils.cpp:134-136, left to right in float

@@ -266,6 +266,7 @@ hipError_t launch_select_best(const int32_t* d_members, const int32_t* d_offs, i
 hipError_t launch_point_sums_dump(const Workspace& w, const LaunchCfg& c, uint32_t* d_dump, hipStream_t st);                  // test hook: in place of launch_gn_score, the raw accumulator records by voxel
 hipError_t launch_point_sums_copy(const Workspace& w, const LaunchCfg& c, uint32_t* d_dump, hipStream_t st);                  // test hook: the same records, left in place for the solve that follows
 hipError_t launch_fix_debug(const float* d_v, unsigned long long* d_out, int n, hipStream_t st);                             // test hook: to_fix_biased / to_fix_wide_biased / to_fix of n floats
+hipError_t launch_spherical_debug(const float* d_xyz, int n, int ld, int T, int P, float* d_out, hipStream_t st);                    // test hook: the shared rule's device functions on n rows (icet_keyframe.hip)
 hipError_t launch_gn_tail_debug(const float* d_H, const float* d_g, float* d_out, int n, float bound2, hipStream_t st);     // test hook: the 6x6 tail on its own
 hipError_t launch_pinv3_debug(const float* d_A, float* d_out, int n, hipStream_t st);                                        // test hook: the 3x3 float COD pseudo-inverse of ICET_FLAG_REFERENCE_W
 hipError_t launch_pinv3_double_debug(const float* d_A, float* d_out, int n, hipStream_t st);                                 // test hook: the 3x3 double pseudo-inverse of ICET_FLAG_DOUBLE_W

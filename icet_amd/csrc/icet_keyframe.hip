@@ -1343,7 +1343,34 @@ __global__ __launch_bounds__(kBlock) void k_lds_order_selftest(int rounds, int32
     if (nbad) atomicAdd(bad, nbad);
 }
 
+// Test hook (icet_debug_spherical): the device functions of the shared arithmetic rule on n rows, one thread per row.  out: 12 columns of n words --
+// r | th | ph of c2s_cr, voxel_of(th, ph) (an int), ox | oy | oz of roundtrip_any, th | ph | ox | oy | oz of roundtrip_cr called as k_fit_roundtrip calls
+// it (rows with a finite r_raw > 0; NaN otherwise).
+__global__ __launch_bounds__(kBlock) void k_spherical_debug(const float* __restrict__ xyz, int n, int ld, int T, int P, float* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[i], y = xyz[(size_t)ld + i], z = xyz[2 * (size_t)ld + i];
+    const size_t N = (size_t)n;
+    float r, th, ph;
+    c2s_cr(x, y, z, r, th, ph);
+    out[i] = r; out[N + i] = th; out[2 * N + i] = ph;
+    out[3 * N + i] = __int_as_float(voxel_of(th, ph, T, P));
+    float ox, oy, oz;
+    roundtrip_any(x, y, z, ox, oy, oz);
+    out[4 * N + i] = ox; out[5 * N + i] = oy; out[6 * N + i] = oz;
+    const float rr = radius_raw(x, y, z), nan = __builtin_nanf("");
+    float cth = nan, cph = nan, cx = nan, cy = nan, cz = nan;
+    if (rr > 0.f && rr < INFINITY) roundtrip_cr(x, y, z, rr, cth, cph, cx, cy, cz);
+    out[7 * N + i] = cth; out[8 * N + i] = cph; out[9 * N + i] = cx; out[10 * N + i] = cy; out[11 * N + i] = cz;
+}
+
 }  // namespace
+
+hipError_t launch_spherical_debug(const float* d_xyz, int n, int ld, int T, int P, float* d_out, hipStream_t st) {
+    k_spherical_debug<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(d_xyz, n, ld, T, P, d_out);
+    ICET_LAUNCH_CHECK();
+    return hipSuccess;
+}
 
 
 hipError_t lds_rank_selftest(int32_t* d_scratch, hipStream_t st, int* ok) {

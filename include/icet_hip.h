@@ -588,6 +588,11 @@ icet_status icet_debug_gn_terms_device(icet_ctx* ctx, const icet_params* p, int3
 /* Diagnostic hook for the point-pass tests: n host-side floats through the float -> 2^36 fixed-point conversions of the point pass; out: n x 3 uint64 =
  * the two-instruction biased form (defined for |v| < 2^15) | the wide biased form | the unbiased form that selects between them per value. */
 icet_status icet_debug_fix(icet_ctx* ctx, const float* v, int32_t n, uint64_t* out);
+/* Diagnostic hook for the shared arithmetic rule: n host-side rows x[n] | y[n] | z[n] (leading dimension ld >= n) through the device functions
+ * every kernel takes its angles and round trips from.  out: 12 columns of n 32-bit words -- r | theta | phi of cartesianToSpherical, the voxel of (theta, phi) on a
+ * T x P grid (int32), x | y | z of the round trip of ANY row (what ICET_FLAG_ROUNDTRIP_SCAN2 stores), and theta | phi | x | y | z of the ordinary-row round trip that
+ * the scan-1 fit runs (NaN for rows whose r is 0, infinite or NaN).  Drains the stream before it returns. */
+icet_status icet_debug_spherical(icet_ctx* ctx, const float* xyz, int32_t n, int32_t ld, int32_t T, int32_t P, float* out);
 
 /* --- pose-graph optimisation: corrected poses from closure records --------------------------------------------------------
  * GRAPH.  n poses (float32 4 x 4 row-major, the store's POSE convention), one odometry edge (k, k + 1) per k < n - 1 and n_closures closure edges

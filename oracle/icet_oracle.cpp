@@ -40,8 +40,14 @@
 //     both follow one rule, stated mathematically rather than by shared code:
 //       - every transcendental is the correctly rounded float of the exact value: evaluated in double, rounded once
 //         (here glibc's double functions; on the device ocml's double atan2/acos and an algebraic double evaluation of
-//         sin/cos -- independent implementations that agree unless a double result lies within ~1e-16 of a float
-//         rounding boundary, probability ~1e-8 per call);
+//         sin/cos -- independent implementations).  What is pinned (tests/test_arith_rule.py, against an mpmath model of this sentence):
+//         both sides give the correctly rounded float, sign of zero included, whenever the exact angle lies 4 or more double-ulps
+//         from a float rounding boundary (twice an assumed 2-ulp error of ocml's atan2 / acos) and the exact sine / cosine 2^-47 or
+//         more (three times the 2.1e-15 ABSOLUTE error of the device's algebraic form: 2 ulp of a double angle in [4, 8) + three
+//         roundings).  A sine or cosine below 2^-10 -- a row near an axis, the horizontal plane or a pole, where that absolute error
+//         decided the float: sin(float(pi)) lies 1.2e-16 from a boundary -- is taken by the device from the float angle itself with a
+//         relative error of 2^-52 instead (icet_device_common.h trig_small).  Closer than the excluded distances two honest evaluations
+//         may round apart; measured: glibc, and the device before and after that change, each 0 of 2 M random rows over 80 octaves;
 //       - the per-voxel sums (mean, centred products) are exact: accumulated in double from float addends, rounded to
 //         float once, then divided in float -- the value every summation order approximates;
 //       - hypot in the QR step is Eigen 3.3's own formula p * sqrt(1 + (q/p)^2) (numext::hypot), not libm's.
@@ -738,6 +744,13 @@ int icet_oracle_pinv(const float* A, int rows, int cols, float* out) {
 }
 void icet_oracle_c2s(const float* xyz, int64_t n, int64_t ld, float* out /* n x 3 col-major r|th|ph */) {
     for (int64_t i = 0; i < n; i++) ico::c2s_one(xyz[i], xyz[ld + i], xyz[2 * ld + i], out[i], out[n + i], out[2 * n + i]);
+}
+// sphericalToCartesian(cartesianToSpherical(.)) of every row, as prepScan1 / prepScan2 chain them (src/utils.cpp:93-142): out n x 3 col-major x|y|z.
+void icet_oracle_roundtrip(const float* xyz, int64_t n, int64_t ld, float* out) {
+    for (int64_t i = 0; i < n; i++) {
+        float r, th, ph; ico::c2s_one(xyz[i], xyz[ld + i], xyz[2 * ld + i], r, th, ph);
+        ico::s2c_one(r, th, ph, out[i], out[n + i], out[2 * n + i]);
+    }
 }
 // The scramble on its own: given r[n], returns src[v] = original row that ends at position v.
 void icet_oracle_scramble(const float* r, int64_t n, int32_t* src) {

@@ -63,6 +63,7 @@ def lib():
         L.icet_oracle_gn_tail.restype = C.c_int
         L.icet_oracle_gn_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
         L.icet_oracle_c2s.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.icet_oracle_roundtrip.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.icet_oracle_scramble.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.icet_oracle_get_H.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.icet_oracle_R.argtypes = [C.c_void_p, C.c_void_p]
@@ -184,6 +185,14 @@ def c2s(scan):
     s = colmajor(scan); n = s.shape[1]
     out = np.zeros((3, n), np.float32)
     lib().icet_oracle_c2s(s.ctypes.data, n, n, out.ctypes.data)
+    return out.T.copy()
+
+
+def roundtrip(scan):
+    """sphericalToCartesian(cartesianToSpherical(row)) of every row (s2c_one(c2s_one(.)), the oracle's own functions): N x 3 float32."""
+    s = colmajor(scan); n = s.shape[1]
+    out = np.zeros((3, n), np.float32)
+    lib().icet_oracle_roundtrip(s.ctypes.data, n, n, out.ctypes.data)
     return out.T.copy()
 
 
