@@ -128,9 +128,9 @@ icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs,
             c->kf_pairs = 0;
             w.cap_n1 = 0, w.cap_fit_items = 0, g.release();
             HIPCHK(c, g.device(w.r1, n)); HIPCHK(c, g.device(w.cart1, (size_t)3 * n));
-            HIPCHK(c, g.device(w.key64A, n)); HIPCHK(c, g.device(w.key64B, n)); HIPCHK(c, g.device(w.bin16, n + 8));      /* (+ 8: k_rs_bucket_sort reads aligned groups of eight words) */ HIPCHK(c, g.device(w.binpos, n)); HIPCHK(c, g.device(w.bkt, n));
-            HIPCHK(c, g.device(w.keyA, n)); HIPCHK(c, g.device(w.keyB, n)); HIPCHK(c, g.device(w.valA, n)); HIPCHK(c, g.device(w.valB, n));
-            HIPCHK(c, g.device(w.pred, n)); HIPCHK(c, g.device(w.src, n));
+            HIPCHK(c, g.device(w.rs_pairs, n)); HIPCHK(c, g.device(w.rs_pairs_alt, n)); HIPCHK(c, g.device(w.bin16, n + 8));      /* (+ 8: k_rs_bucket_sort reads aligned groups of eight words) */ HIPCHK(c, g.device(w.binpos, n)); HIPCHK(c, g.device(w.bkt, n));
+            HIPCHK(c, g.device(w.cand_row, n)); HIPCHK(c, g.device(w.cand_r, n)); HIPCHK(c, g.device(w.sorted_row, n)); HIPCHK(c, g.device(w.row_of_rank, n));
+            HIPCHK(c, g.device(w.rank_of_row, n)); HIPCHK(c, g.device(w.src, n));
             w.cap_n1 = n;
         }
         // what depends on both sides; its capacity is cap_fit_items
@@ -140,10 +140,6 @@ icet_status ensure_workspace(icet_ctx* c, const icet_params* p, int32_t n_pairs,
         HIPCHK(c, g.device(w.execbits, (size_t)(w.cap_n1 / 64 + w.cap_pairs + 2)));      // exec_word_base: off1 / 64 + pair
         HIPCHK(c, g.device_bytes(w.fit_items, need_items * 16));
         HIPCHK(c, g.device(w.fit_n_items, (size_t)w.cap_pairs));
-#ifdef ICET_DIAG_LIBSORT
-        w.sort_tmp_bytes = sort_temp_bytes(w.cap_n1);
-        HIPCHK(c, g.device_bytes(w.sort_tmp, w.sort_tmp_bytes));
-#endif
         w.cap_fit_items = need_items;
     }
     return ICET_OK;
@@ -379,7 +375,7 @@ LaunchCfg make_cfg(const icet_ctx* c, const icet_params* p, int32_t n_pairs, con
     cfg.rt2 = (p->flags & ICET_FLAG_ROUNDTRIP_SCAN2) ? 1 : 0;
     cfg.ref_w = (p->flags & ICET_FLAG_DOUBLE_W) ? 0 : 1;
     cfg.lds_slots = c->tune.lds_slots; cfg.acc_min_pts_per_thread = c->tune.acc_pts; cfg.acc_target_blocks = c->tune.acc_blocks;
-    cfg.force_exact = c->tune.force_exact; cfg.use_library_sort = c->tune.library_sort; cfg.kf_pts_per_thread = c->tune.kf_pts; cfg.rs_cap = c->tune.rs_cap; cfg.rs_max_cell = c->tune.rs_max_cell; cfg.exec_bits_lds = c->tune.exec_bits_lds; cfg.exec_pairwise = c->tune.exec_pairwise; cfg.fuse_solve = c->tune.fuse_solve != 0 ? 1 : 0; cfg.lds_rank = (c->tune.lds_rank != 0 && c->lds_rank_ok) ? 1 : 0;
+    cfg.force_exact = c->tune.force_exact; cfg.kf_pts_per_thread = c->tune.kf_pts; cfg.rs_cap = c->tune.rs_cap; cfg.rs_max_cell = c->tune.rs_max_cell; cfg.exec_bits_lds = c->tune.exec_bits_lds; cfg.exec_pairwise = c->tune.exec_pairwise; cfg.fuse_solve = c->tune.fuse_solve != 0 ? 1 : 0; cfg.lds_rank = (c->tune.lds_rank != 0 && c->lds_rank_ok) ? 1 : 0;
     cfg.gn_cond_bound2 = (float)(c->tune.gn_cond_bound * c->tune.gn_cond_bound);
     cfg.pair_user = (c->perm_active && c->perm_pairs == n_pairs) ? c->w.seg_off + n_pairs + 1 : nullptr;
     cfg.done_flag = c->done_flag;
@@ -400,17 +396,17 @@ LaunchCfg make_cfg(const icet_ctx* c, const icet_params* p, int32_t n_pairs, con
     cfg.kf_chunks = (mx1 + 256 * cfg.kf_pts_per_thread - 1) / (256 * cfg.kf_pts_per_thread);
     if (cfg.kf_chunks < 1) cfg.kf_chunks = 1;
     // packed rows (LaunchCfg::packed_rows): the layout of pred[] / src[] for this call -- whenever the largest rank and a voxel word fit 32 bits together
-    // (17 + 13 on 75 x 24 with scans up to 131 072 rows), unless the option says no; the library sort's inverse-permutation pass writes plain ranks
+    // (17 + 13 on 75 x 24 with scans up to 131 072 rows), unless the option says no
     cfg.row_shift = packed_row_shift(mx1); cfg.id_bits = bits_of((int64_t)cfg.V - 1);
-    cfg.packed_rows = (c->tune.packed_rows != 0 && !cfg.use_library_sort && packed_row_bits(mx1, cfg.V) <= 32) ? 1 : 0;
+    cfg.packed_rows = (c->tune.packed_rows != 0 && packed_row_bits(mx1, cfg.V) <= 32) ? 1 : 0;
     return cfg;
 }
 // The plan's part of a graph key (icet_ctx::GraphKey::launch): what grids, LDS sizes, template choices and by-value arguments are made from.  Not in it: what an
 // option's setter un-sees the keys for (fuse_solve, gn_cond_bound) and what no captured call uses (the keep list, batch stages).
-void launch_key_of(const LaunchCfg& k, int64_t (&out)[30]) {
+void launch_key_of(const LaunchCfg& k, int64_t (&out)[29]) {
     auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return (int64_t)i; };
     const int64_t v[] = {k.T, k.P, k.V, k.n, k.runlen, bits(k.thresh), bits(k.buff), k.n_pairs, k.max_n1, k.max_n2, k.total_n1, k.lds_slots, k.acc_min_pts_per_thread,
-                         k.acc_target_blocks, k.kf_chunks, k.kf_pts_per_thread, k.use_library_sort, k.vec4_ok, k.true_sort, k.force_exact, k.rs_cap, k.rs_max_cell,
+                         k.acc_target_blocks, k.kf_chunks, k.kf_pts_per_thread, k.vec4_ok, k.true_sort, k.force_exact, k.rs_cap, k.rs_max_cell,
                          k.exec_bits_lds, k.exec_pairwise, k.lds_rank, k.reject_moving, k.half_gap, k.rt2, k.ref_w, k.packed_rows};
     static_assert(sizeof(v) == sizeof(out), "GraphKey::launch");
     std::memcpy(out, v, sizeof(v));
@@ -427,7 +423,7 @@ icet_status enqueue_keyframe(icet_ctx* c, const LaunchCfg& cfg, const AuxDev* au
     Workspace& w = c->w;
     const int32_t n_pairs = cfg.n_pairs;
     if (c->tune.packed_rows > 0 && !cfg.packed_rows) {
-        c->err = "option \"packed_rows\" is 1, but a rank and a voxel word of this call do not fit 32 bits together (" + std::to_string(packed_row_bits(cfg.max_n1, cfg.V)) + " bits), or the library sort is on";
+        c->err = "option \"packed_rows\" is 1, but a rank and a voxel word of this call do not fit 32 bits together (" + std::to_string(packed_row_bits(cfg.max_n1, cfg.V)) + " bits)";
         return ICET_ERR_UNSUPPORTED;
     }
     c->kf_row_mask = packed_row_mask(cfg);
@@ -445,7 +441,7 @@ icet_status enqueue_keyframe(icet_ctx* c, const LaunchCfg& cfg, const AuxDev* au
         }
     }
     // a small batch: k_rs_splitters, the keyframe's first kernel, takes the descriptors from the pinned staging itself
-    const bool first_uploads = n_pairs <= kUploadDescMaxPairs && !cfg.use_library_sort;
+    const bool first_uploads = n_pairs <= kUploadDescMaxPairs;
     ICET_TRY(staging_upload(c, w, c->h_desc, c->h_seg, n_pairs, (size_t)n_pairs + 1 + (c->perm_active ? n_pairs : 0), first_uploads));      // (a permuted batch carries the caller's pair of every slot behind the offsets)
     if (!first_uploads) ICET_TRY(staging_mark_read(c));
     if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
@@ -849,7 +845,7 @@ static icet_ctx::GraphKey entry_key(icet_ctx::GraphEntry entry, const void* x0, 
 // ... completed with what the launches of ANY entry depend on: the plan, the workspace pointers, the prologue and the done flag.
 static icet_ctx::GraphKey graph_key_of(const icet_ctx* c, const icet_params* p, const LaunchCfg& cfg, icet_ctx::GraphKey key) {
     const Workspace& w = c->w;
-    const void* ws[] = {w.desc, w.thr, w.lut, w.r1, w.counts, w.near_over, w.acc, w.fit_items, w.sort_tmp, w.tile_vr};
+    const void* ws[] = {w.desc, w.thr, w.lut, w.r1, w.counts, w.near_over, w.acc, w.fit_items, w.tile_vr};
     static_assert(sizeof(ws) == sizeof(key.ws), "GraphKey::ws");
     std::memcpy(key.ws, ws, sizeof(ws));
     key.prologue_key = c->prologue ? c->prologue_key : 0; key.done_flag = c->done_flag; key.flags = p->flags;
@@ -1527,12 +1523,8 @@ icet_status icet_set_option(icet_ctx* c, const char* name, double value) {
     else if (k == "acc_pts") t.acc_pts = iv < 1 ? 1 : iv;
     else if (k == "acc_blocks") t.acc_blocks = iv < 1 ? 1 : iv;
     else if (k == "force_exact") t.force_exact = iv != 0;
-    else if (k == "library_sort") {
-#ifdef ICET_DIAG_LIBSORT
-        t.library_sort = iv != 0;
-#else
-        if (iv != 0) { c->err = "library_sort: this build has ONE sort, the hand-written rank sort (the rocPRIM A/B backend is compiled in with `make EXTRA=-DICET_DIAG_LIBSORT`)"; return ICET_ERR_UNSUPPORTED; }
-#endif
+    else if (k == "library_sort") {      // the name stays known: 0 is what the library does
+        if (iv != 0) { c->err = "library_sort: the library has ONE sort, the hand-written rank sort, and no build flag brings another"; return ICET_ERR_UNSUPPORTED; }
     }
     else if (k == "kf_pts") t.kf_pts = iv < 1 ? 1 : (iv > kKfMaxPtsPerThread ? kKfMaxPtsPerThread : iv);
     else if (k == "batch_parts") t.batch_parts = iv < 0 ? 0 : (iv > 8 ? 8 : iv);

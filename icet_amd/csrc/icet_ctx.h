@@ -97,8 +97,8 @@ struct icet_ctx {
         const void* x0; const void* out; const void* extra;    // the caller's argument pointers; extra: d_rows of the two halves, d_score of a scored call
         int64_t ws_gen, src_id, src_gen;                       // indexed calls: any workspace buffer moved; the keyframe tables -- 0 / 0 the context's own, else a store's id and generation
         int64_t prologue_key; const void* done_flag; int64_t flags;      // the prologue's key (0: none), the word the last solve raises, icet_params::flags
-        const void* ws[10];                                    // desc, thr, lut, r1, counts, near_over, acc, fit_items, sort_tmp, tile_vr
-        int64_t launch[30];                                    // what the launches take of the plan (launch_key_of, icet_capi.hip)
+        const void* ws[9];                                     // desc, thr, lut, r1, counts, near_over, acc, fit_items, tile_vr
+        int64_t launch[29];                                   // what the launches take of the plan (launch_key_of, icet_capi.hip)
     };
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}, seen{}; bool have_seen = false, have_graph = false;
@@ -134,7 +134,7 @@ struct icet_ctx {
         icet::BufferGroup out, stage1, stage2, pack, pts2, side1, side2, score, sel, sync_word;
     } mem;
 };
-static_assert(std::has_unique_object_representations_v<icet_ctx::GraphKey> && sizeof(icet_ctx::GraphKey) == 8 * (21 + 30), "GraphKey is compared with memcmp: 8-byte integers and pointers, no padding");
+static_assert(std::has_unique_object_representations_v<icet_ctx::GraphKey> && sizeof(icet_ctx::GraphKey) == 8 * (20 + 29), "GraphKey is compared with memcmp: 8-byte integers and pointers, no padding");
 
 // A keyframe store (include/icet_hip.h icet_keyframe_store_*): `capacity` rows of the four keyframe tables in the layout of the workspace's
 // keyframe side (row stride V; (V + 1) & ~1 for slot_of_voxel), on the borrowed context's device.  A put builds on the context and parks into rows of its own

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "icet_staging.h"
 
 struct icet_score;                         // include/icet_hip.h
@@ -130,17 +131,38 @@ struct Workspace {
     PairDesc* desc = nullptr;
     PairDesc* desc_rt = nullptr; float* rt2 = nullptr; int64_t cap_rt2 = 0;   // ICET_FLAG_ROUNDTRIP_SCAN2: descriptors whose scan 2 is the round-tripped copy, and that copy (3 x cap_rt2 floats)
     int32_t* seg_off = nullptr;               // pairs+1, scan-1 segment offsets
-    float *r1 = nullptr;                                             // radial distance of every scan-1 row, input order (bit-exact c2s r)
-    float *cart1 = nullptr;                                          // 3 x cap_n1: round-tripped Cartesian rows of large bins (k_fit_scan1's second pass)
-    unsigned long long *key64A = nullptr, *key64B = nullptr;         // (pair << 32 | r bits)
-    uint32_t *keyA = nullptr, *keyB = nullptr, *valA = nullptr, *valB = nullptr;
+    // The keyframe build's per-row arrays, cap_n1 elements each (61 bytes per scan-1 row, + 1 bit).  In build order; "next build": live until the next keyframe
+    // build overwrites it.  An array is free for reuse behind its last reader; nothing is aliased today except the two reuses named in the last column.
+    //   array         B/row  written by                               last read by                               afterwards
+    //   r1             4     k_scan1_spherical                        k_fit_cluster; icet_debug_fetch            next build
+    //   bin16          2     k_scan1_spherical                        k_scramble_replay; icet_debug_fetch        next build
+    //   bkt            1     k_scan1_spherical                        k_rs_scatter / k_rs_scatter_staged         free
+    //   rs_pairs       8     k_rs_scatter / k_rs_scatter_staged       k_rs_bucket_sort                           free
+    //   rs_pairs_alt   8     k_rs_bucket_sort (overflow buckets)      k_rs_bucket_sort                           free
+    //   row_of_rank    4     k_rs_bucket_sort (+ the staged scatter)  k_scramble_replay (true_sort: the copy)    free
+    //   rank_of_row    4     k_rs_bucket_sort (+ the staged scatter)  k_scramble_src                             k_scramble_replay's scratch, then free
+    //   execbits      1/8    k_exec_flags / k_exec_flags_pair         k_scramble_src                             free
+    //   src            4     k_scramble_src (+ k_scramble_replay)     k_bin_scatter; k_side_scan1, debug_fetch   next build
+    //   binpos         2     k_scramble_src (plain rows only)         k_bin_scatter                              free
+    //                        (src, binpos under true_sort: the copy of row_of_rank and k_bin_hist)
+    //   sorted_row     4     k_bin_scatter                            k_fit_cluster; k_side_index1               next build
+    //   cand_row       4     k_fit_cluster                            k_fit_roundtrip                            free
+    //   cand_r         4     k_fit_cluster                            k_fit_roundtrip                            scratch of k_side_scan1 / k_side_index1 (row -> position), then free
+    //   cart1         12     k_fit_roundtrip                          k_fit_moments                              free
+    float* r1 = nullptr;                                             // radial distance of every scan-1 row, input order (bit-exact c2s r)
+    float* cart1 = nullptr;                                          // 3 x cap_n1: round-tripped Cartesian rows of large bins (k_fit_roundtrip)
+    uint2 *rs_pairs = nullptr, *rs_pairs_alt = nullptr;              // rank sort: (key, row) records grouped by bucket; second buffer of a bucket that does not fit LDS
+    uint32_t* row_of_rank = nullptr;                                 // s[]: the row that has rank i
+    int32_t* rank_of_row = nullptr;                                  // pred[]: rank of every row (packed rows: with a voxel word above it, rank_of, icet_keyframe.hip)
+    uint32_t* sorted_row = nullptr;                                  // rows in (voxel, position) order (top bits: the row's near / zero flags)
+    uint32_t* cand_row = nullptr; float* cand_r = nullptr;           // the fit's compacted candidate rows and their radii
     uint32_t* splitters = nullptr; int32_t* n_buckets = nullptr; int32_t* bucket_start = nullptr;   // rank sort: pairs x kRankSortMaxBuckets, pairs, pairs x (kRankSortMaxBuckets + 1)
     uint8_t* bkt = nullptr;                                          // rank sort: bucket id of every scan-1 row
     uint16_t* binpos = nullptr;                                      // angular bin of the row at every position after the scramble
     uint32_t* counts = nullptr; uint32_t* tile_base = nullptr; size_t cap_counts = 0;               // pairs x tiles x V histogram / tile base offsets
     uint16_t* bin16 = nullptr;                                       // angular bin of every scan-1 row (input order)
     unsigned long long* execbits = nullptr;                          // swap loop: "step v executed", 64 rows per word (exec_word_base, icet_keyframe.hip)
-    int32_t *pred = nullptr, *src = nullptr;
+    int32_t* src = nullptr;                                          // the row that lands on every position after the swap loop (packed rows: with its voxel word)
     int32_t *bin_count = nullptr, *bin_start = nullptr;             // pairs x V, pairs x (V+1)
     SlotHot* hotD = nullptr; SlotFit* fitD = nullptr; int32_t* activeD = nullptr;   // dense, pairs x V
     FitMid* midD = nullptr;                                                          // dense, pairs x V
@@ -171,7 +193,6 @@ struct Workspace {
     unsigned long long* keep_mask = nullptr; size_t cap_keep_mask = 0; uint32_t* keep_list = nullptr; size_t cap_keep_list = 0; KeepState* keep_state = nullptr; int32_t cap_keep_pairs = 0;
     int32_t* keep_modes = nullptr;            // 2 x cap_keep_pairs: per pair what the point pass of an even / odd iteration does with it (KeepArgs::modes_next)
     float* edges = nullptr;
-    void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
 };
 
 // Launch-shape and diagnostic knobs.  Defaults are the measured optima; every value gives the same bits
@@ -185,7 +206,6 @@ struct Tuning {
     int acc_pts = 4;              // k_gn_accumulate: minimum points per thread per block
     int acc_blocks = 1536;        // k_gn_accumulate: target blocks per launch
     int force_exact = 0;          // route every scan-2 point through the literal classification
-    int library_sort = 0;         // rocPRIM radix sort instead of the hand-written rank sort
     int kf_pts = kKfMaxPtsPerThread;   // keyframe tile = 256 threads x this many rows
     int batch_parts = 0;          // parts a device batch is cut into (0 = automatic)
     int batch_stage = 4;          // keyframe stage after which the next part may start (0 = lock step)
@@ -219,7 +239,6 @@ struct LaunchCfg {
     int kf_pts_per_thread = kKfMaxPtsPerThread;        // keyframe kernels: points per thread (sets chunks per pair)
     hipEvent_t stage_event = nullptr; /* recorded inside launch_keyframe after stage `stage_at` (4 spherical, 1 sort, 2 scramble, 3 gather): lets the next batch part start there */
     int stage_at = 0;
-    int use_library_sort = 0;         // diagnostic: rocPRIM device radix sort instead of the hand-written rank sort
     int vec4_ok = 0;                  // every scan-2 pointer and leading dimension is 16-byte aligned
     int true_sort = 0;                // ICET_FLAG_TRUE_SORT (non-parity extension): src[] = the sorted order itself
     int force_exact = 0;              // diagnostic: route every point through the literal evaluation
@@ -251,6 +270,9 @@ constexpr int kRejectMovingStartIter = 4;          // python/ICET_spherical.py:3
 
 // behind a kernel launch in a function that returns hipError_t
 #define ICET_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
+// A run-time flag as a template argument: f gets std::true_type or std::false_type, so a launch site is written once --
+//     with_flag(packed, [&](auto kPacked) { k<kPacked()><<<grid, blk, 0, st>>>(...); });      one call nested in another per further flag
+template <class F> inline void with_flag(bool on, F&& f) { if (on) f(std::true_type{}); else f(std::false_type{}); }
 
 // icet_keyframe.hip
 hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev* aux, hipStream_t st, const int32_t* d_n1 = nullptr);   // d_n1: scan-1 row counts known to the device only (the descriptors hold upper bounds)
@@ -406,13 +428,6 @@ __device__ __forceinline__ int rank_sort_bucket_of(uint32_t key, const uint32_t*
 hipError_t launch_class_scan(const uint32_t* counts, uint32_t* tile_base, int32_t* class_start, int n_classes, int chunks, int n_pairs, hipStream_t st,
                              int32_t* live = nullptr, int32_t* n_live = nullptr, int live_min = 0, uint32_t* n_items = nullptr, const int32_t* class_range = nullptr,
                              const int32_t* tile_vr = nullptr, int32_t* vrange_out = nullptr);
-
-// sort.hip
-size_t sort_temp_bytes(int64_t total_n);
-hipError_t sort_pairs_u64(void* tmp, size_t tmp_bytes, const unsigned long long* key_in, unsigned long long* key_out,
-                          const uint32_t* val_in, uint32_t* val_out, int64_t total_n, int end_bit, hipStream_t st);
-hipError_t sort_pairs_u32(void* tmp, size_t tmp_bytes, const uint32_t* key_in, uint32_t* key_out,
-                          const uint32_t* val_in, uint32_t* val_out, int64_t total_n, int end_bit, hipStream_t st);
 
 }  // namespace icet
 

@@ -47,13 +47,12 @@ __device__ __noinline__ int voxel_literal(float px, float py, float pz, float r_
 __device__ __forceinline__ int zero_voxel_of(int patt, const int4& zv) { return patt == 0 ? zv.x : (patt == 1 ? zv.y : (patt == 2 ? zv.z : zv.w)); }
 
 __global__ __launch_bounds__(kBlock) void k_scan1_spherical(const PairDesc* __restrict__ desc, float* __restrict__ r1,
-                                                            unsigned long long* __restrict__ key64, uint32_t* __restrict__ key32,
-                                                            uint32_t* __restrict__ val, uint16_t* __restrict__ bin16, int T, int P, int n_pairs, int chunks,
+                                                            uint16_t* __restrict__ bin16, int T, int P, int n_pairs, int chunks,
                                                             const uint32_t* __restrict__ splitters, uint8_t* __restrict__ bkt, uint32_t* __restrict__ counts,
                                                             const LutCell* __restrict__ lut, int Mt, int Mp, float guard_t, float guard_p, int32_t* __restrict__ tile_vr, int4 zv, int32_t* __restrict__ zero_rows) {
     // First step of the rank sort fused in (icet_ranksort.hip): the pair's splitters are already known (k_rs_splitters
     // samples the radii straight from the Cartesian rows), so each row's bucket and this tile's bucket histogram cost no
-    // extra pass over r1[].  splitters == nullptr: library-sort diagnostic path, nothing of this is needed.
+    // extra pass over r1[].
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s1[];
     LutCell* lut_t = reinterpret_cast<LutCell*>(smem_s1);               // Mt + 1 cells (the spare one catches pa == 4)
     LutCell* lut_p = lut_t + (Mt + 1);                                  // Mp + 1 cells (w == 1)
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void k_scan1_spherical(const PairDesc* __re
         uint2* ll = reinterpret_cast<uint2*>(lut_t);
         for (int i = threadIdx.x; i < Mt + Mp + 2; i += kBlock) ll[i] = gl[i];
         int pair_, chunk_;
-        if (splitters && decode_block(n_pairs, chunks, pair_, chunk_))
+        if (decode_block(n_pairs, chunks, pair_, chunk_))
             for (int j = threadIdx.x; j < kRankSortMaxBuckets; j += kBlock) { sp[j] = splitters[(size_t)pair_ * kRankSortMaxBuckets + j]; lh[j] = 0u; }
         __syncthreads();
     }
@@ -93,21 +92,14 @@ __global__ __launch_bounds__(kBlock) void k_scan1_spherical(const PairDesc* __re
             const bool zrow = (rr == 0.f) & (px == 0.f) & (py == 0.f);
             const int patt = (__builtin_signbit(py) ? 2 : 0) | (__builtin_signbit(px) ? 1 : 0);
             v = zrow ? zero_voxel_of(patt, zv) : voxel_literal(px, py, pz, rr, T, P);
-            if (zrow) atomicAdd(&s_zc[patt], 1u);                      // (an LDS counter, not a register carried through the loop: the kernel sits at 64 VGPRs = 8 waves per SIMD)
+            if (zrow) atomicAdd(&s_zc[patt], 1u);                      // (an LDS counter, not a register carried through the loop: the kernel has to stay within 64 VGPRs = 8 waves per SIMD)
         }
         const float r = (rr != rr) ? 1000.0f : rr;                      // src/utils.cpp:116
         size_t o = (size_t)d.off1 + i;
         r1[o] = r;
-        if (splitters) {
-            const int b = rank_sort_bucket_of(__float_as_uint(r), sp);
-            bkt[o] = (uint8_t)b;
-            atomicAdd(&lh[b], 1u);
-        }
-        // r >= +0 (or 1000 for NaN): the bit pattern orders like the float; the pair id in the high word keeps
-        // every pair's points contiguous, so one device-wide sort handles the whole batch
-        if (key64) key64[o] = ((unsigned long long)pair << 32) | (unsigned long long)__float_as_uint(r);
-        else if (key32) key32[o] = __float_as_uint(r);
-        if (key64 || key32) val[o] = (uint32_t)i;               // library-sort path only
+        const int b = rank_sort_bucket_of(__float_as_uint(r), sp);      // r >= +0 (or 1000 for NaN): the bit pattern orders like the float
+        bkt[o] = (uint8_t)b;
+        atomicAdd(&lh[b], 1u);
         bin16[o] = (uint16_t)v | (near ? kRowNearBit : (uint16_t)0) | (r == 0.f ? kRowZeroBit : (uint16_t)0);
         vlo = min(vlo, v); vhi = max(vhi, v);
     }
@@ -118,26 +110,16 @@ __global__ __launch_bounds__(kBlock) void k_scan1_spherical(const PairDesc* __re
         if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = vlo; s_hi[threadIdx.x >> 6] = vhi; }
 
         __syncthreads();
-        if (zero_rows && threadIdx.x >= 64 && threadIdx.x < 68 && s_zc[threadIdx.x - 64] != 0u) atomicAdd(&zero_rows[4 * pair + (threadIdx.x - 64)], (int)s_zc[threadIdx.x - 64]);
+        if (threadIdx.x >= 64 && threadIdx.x < 68 && s_zc[threadIdx.x - 64] != 0u) atomicAdd(&zero_rows[4 * pair + (threadIdx.x - 64)], (int)s_zc[threadIdx.x - 64]);
         if (threadIdx.x == 0) {
             int lo = s_lo[0], hi = s_hi[0];
             for (int k = 1; k < kBlock / 64; k++) { lo = min(lo, s_lo[k]); hi = max(hi, s_hi[k]); }
             tile_vr[((size_t)pair * chunks + chunk) * 2] = lo; tile_vr[((size_t)pair * chunks + chunk) * 2 + 1] = hi;
         }
     }
-    if (splitters) {
-        __syncthreads();
-        for (int j = threadIdx.x; j < kRankSortMaxBuckets; j += kBlock) counts[((size_t)pair * chunks + chunk) * kRankSortMaxBuckets + j] = lh[j];
-    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < kRankSortMaxBuckets; j += kBlock) counts[((size_t)pair * chunks + chunk) * kRankSortMaxBuckets + j] = lh[j];
 }
-
-#ifdef ICET_DIAG_LIBSORT
-// pred[s[i]] = i : rank of every original row (the library sort's inverse-permutation pass; the rank sort writes pred[] itself).
-__global__ __launch_bounds__(kBlock) void k_inverse_perm(const PairDesc* __restrict__ desc, const uint32_t* __restrict__ s, int32_t* __restrict__ pred,
-                                                         int n_pairs, int chunks) {
-    ICET_FOR_CHUNK_OF_SCAN1(i) pred[(size_t)d.off1 + s[(size_t)d.off1 + i]] = i;
-}
-#endif
 
 // The reference "sorts" rows in place with
 //     for i: if (index[i] != i) { swap(row i, row index[i]); swap(index[i], index[index[i]]); }
@@ -1414,42 +1396,20 @@ hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev*
     dim3 grid(groups * chunks), blk(kBlock);
     const int np = c.n_pairs;
     hipError_t e;
-    int pbits = 0; while ((1 << pbits) < c.n_pairs) pbits++;
     int vbits = 1; while ((1 << vbits) < c.V) vbits++;
-    const bool batch = c.n_pairs > 1;
-    const bool packed = c.packed_rows != 0;           // (make_cfg: never with the library sort, whose k_inverse_perm writes plain ranks)
+    const bool packed = c.packed_rows != 0;
     const int rsh = packed ? c.row_shift : 0;
-    if (!c.use_library_sort) { e = launch_rank_sort_splitters(w, c, st, d_n1); if (e != hipSuccess) return e; }
-    else {   // diagnostic path: no rank sort, hence nobody reduces the tiles' voxel ranges: the full range (vmin = 0, vmax = "large", clipped to V - 1 by the readers)
-        if (d_n1) { e = launch_patch_counts(w, c, d_n1, nullptr, st); if (e != hipSuccess) return e; }
-        e = hipMemset2DAsync(w.vrange, 8, 0x00, 4, c.n_pairs, st); if (e != hipSuccess) return e;
-        e = hipMemset2DAsync(w.vrange + 1, 8, 0x7F, 4, c.n_pairs, st); if (e != hipSuccess) return e;
-    }
-    k_scan1_spherical<<<grid, blk, scan1_lds_bytes(w), st>>>(w.desc, w.r1, (batch && c.use_library_sort) ? w.key64A : nullptr, c.use_library_sort ? w.keyA : nullptr, w.valA, w.bin16,
-                                                              c.T, c.P, np, chunks, c.use_library_sort ? nullptr : w.splitters, w.bkt, w.counts,
-                                                              reinterpret_cast<const LutCell*>(w.lut), w.lut_Mt, w.lut_Mp, w.guard_t, w.guard_p, w.tile_vr, make_int4(w.zero_voxel[0], w.zero_voxel[1], w.zero_voxel[2], w.zero_voxel[3]), c.use_library_sort ? nullptr : w.zero_rows);
+    e = launch_rank_sort_splitters(w, c, st, d_n1); if (e != hipSuccess) return e;      // (k_rs_splitters also clears the pairs' flags and zero_rows)
+    k_scan1_spherical<<<grid, blk, scan1_lds_bytes(w), st>>>(w.desc, w.r1, w.bin16, c.T, c.P, np, chunks, w.splitters, w.bkt, w.counts,
+                                                              reinterpret_cast<const LutCell*>(w.lut), w.lut_Mt, w.lut_Mp, w.guard_t, w.guard_p, w.tile_vr, make_int4(w.zero_voxel[0], w.zero_voxel[1], w.zero_voxel[2], w.zero_voxel[3]), w.zero_rows);
     ICET_LAUNCH_CHECK();
     if (c.stage_event && c.stage_at == 4) { e = hipEventRecord(c.stage_event, st); if (e != hipSuccess) return e; }
-    if (c.use_library_sort) {
-#ifdef ICET_DIAG_LIBSORT
-        if (batch) e = sort_pairs_u64(w.sort_tmp, w.sort_tmp_bytes, w.key64A, w.key64B, w.valA, w.valB, c.total_n1, 32 + pbits, st);
-        else e = sort_pairs_u32(w.sort_tmp, w.sort_tmp_bytes, w.keyA, w.keyB, w.valA, w.valB, c.total_n1, 32, st);
-        if (e != hipSuccess) return e;
-        // valB = s : original index of the row with rank i
-        k_inverse_perm<<<grid, blk, 0, st>>>(w.desc, w.valB, w.pred, np, chunks);
-        ICET_LAUNCH_CHECK();
-#else
-        (void)pbits; return hipErrorNotSupported;        // (icet_set_option refuses "library_sort" in a build without the diagnostic backend)
-#endif
-    } else {
-        e = launch_rank_sort(w, c, st);        // valB = s, pred = s^-1  (icet_ranksort.hip)
-        if (e != hipSuccess) return e;
-    }
+    e = launch_rank_sort(w, c, st);        // row_of_rank = s, rank_of_row = s^-1  (icet_ranksort.hip)
+    if (e != hipSuccess) return e;
     if (c.stage_event && c.stage_at == 1) { e = hipEventRecord(c.stage_event, st); if (e != hipSuccess) return e; }
-    if (c.use_library_sort) { e = hipMemsetAsync(w.flags, 0, sizeof(int32_t) * c.n_pairs, st); if (e != hipSuccess) return e; }      // (otherwise k_rs_splitters cleared the flags)
     if (c.true_sort) {
         // non-parity extension: the rows stay in sorted order (what the reference's comment says the loop is meant to do)
-        e = hipMemcpyAsync(w.src, w.valB, sizeof(int32_t) * (size_t)c.total_n1, hipMemcpyDeviceToDevice, st); if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(w.src, w.row_of_rank, sizeof(int32_t) * (size_t)c.total_n1, hipMemcpyDeviceToDevice, st); if (e != hipSuccess) return e;
         k_bin_hist<<<grid, blk, (size_t)c.V * 4, st>>>(w.desc, w.src, w.bin16, w.binpos, w.counts, w.flags, c.V, np, chunks, 1, rsh, c.id_bits);
         ICET_LAUNCH_CHECK();
     } else {
@@ -1459,47 +1419,44 @@ hipError_t launch_keyframe(const Workspace& w, const LaunchCfg& c, const AuxDev*
             const size_t pair_lds = (size_t)kExecPairThreads * kR + (size_t)((c.max_n1 + 63) / 64) * 8;    // state bytes + the bit table
             const bool fits = pair_lds <= (size_t)150 * 1024;
             const bool pairwise = fits && (c.exec_pairwise > 0 || (c.exec_pairwise < 0 && c.n_pairs >= 64));
-            if (pairwise) {
-                if (packed) k_exec_flags_pair<kR, true><<<c.n_pairs, kExecPairThreads, pair_lds, st>>>(w.desc, w.pred, w.execbits, rsh);
-                else k_exec_flags_pair<kR, false><<<c.n_pairs, kExecPairThreads, pair_lds, st>>>(w.desc, w.pred, w.execbits, rsh);
-            } else if (packed) k_exec_flags<true><<<grid, blk, 0, st>>>(w.desc, w.pred, w.execbits, w.flags, max_walk, np, chunks, rsh);
-            else k_exec_flags<false><<<grid, blk, 0, st>>>(w.desc, w.pred, w.execbits, w.flags, max_walk, np, chunks, rsh);
+            with_flag(packed, [&](auto kPacked) {      // (k_exec_flags_pair's dynamic LDS: init_keyframe_kernels names every instantiation)
+                if (pairwise) k_exec_flags_pair<kR, kPacked()><<<c.n_pairs, kExecPairThreads, pair_lds, st>>>(w.desc, w.rank_of_row, w.execbits, rsh);
+                else k_exec_flags<kPacked()><<<grid, blk, 0, st>>>(w.desc, w.rank_of_row, w.execbits, w.flags, max_walk, np, chunks, rsh);
+            });
         }
         ICET_LAUNCH_CHECK();
         const size_t hist_bytes = (size_t)((((c.V + 1) / 2 + 1) & ~1)) * 4, bit_bytes = (size_t)((c.max_n1 + 63) / 64) * 8;
-#define ICET_SCRAMBLE(LDS, PACKED, BYTES) k_scramble_src<LDS, PACKED><<<grid, blk, BYTES, st>>>(w.desc, w.valB, w.pred, w.execbits, w.src, w.flags, max_walk, w.bin16, w.binpos, w.counts, c.V, np, chunks, w.vrange, rsh, c.id_bits)
-        if (c.exec_bits_lds && hist_bytes + bit_bytes <= kScrambleLdsMax) { if (packed) ICET_SCRAMBLE(true, true, hist_bytes + bit_bytes); else ICET_SCRAMBLE(true, false, hist_bytes + bit_bytes); }
-        else { if (packed) ICET_SCRAMBLE(false, true, hist_bytes); else ICET_SCRAMBLE(false, false, hist_bytes); }
-#undef ICET_SCRAMBLE
+        const bool bits_in_lds = c.exec_bits_lds && hist_bytes + bit_bytes <= kScrambleLdsMax;
+        with_flag(bits_in_lds, [&](auto kBitsInLds) { with_flag(packed, [&](auto kPacked) {      // (dynamic LDS: init_keyframe_kernels names every instantiation)
+            k_scramble_src<kBitsInLds(), kPacked()><<<grid, blk, kBitsInLds() ? hist_bytes + bit_bytes : hist_bytes, st>>>(w.desc, w.row_of_rank, w.rank_of_row, w.execbits, w.src, w.flags, max_walk, w.bin16, w.binpos, w.counts, c.V, np, chunks, w.vrange, rsh, c.id_bits);
+        }); });
         ICET_LAUNCH_CHECK();
-        k_scramble_replay<<<c.n_pairs, blk, (size_t)c.V * 4, st>>>(w.desc, w.valB, w.pred /* reused as scratch */, w.src, w.flags, w.bin16, w.binpos, w.counts, c.V, chunks, rsh, c.id_bits);
+        k_scramble_replay<<<c.n_pairs, blk, (size_t)c.V * 4, st>>>(w.desc, w.row_of_rank, w.rank_of_row, w.src, w.flags, w.bin16, w.binpos, w.counts, c.V, chunks, rsh, c.id_bits);
         ICET_LAUNCH_CHECK();
         if (c.stage_event && c.stage_at == 2) { e = hipEventRecord(c.stage_event, st); if (e != hipSuccess) return e; }
     }
     e = launch_class_scan(w.counts, w.tile_base, w.bin_start, c.V, chunks, c.n_pairs, st, w.live_bins, w.n_live, c.n, w.fit_n_items, w.vrange);
     if (e != hipSuccess) return e;
-#define ICET_BIN_SCATTER(RANK, PACKED) k_bin_scatter<RANK, PACKED><<<grid, blk, (size_t)c.V * 12 + 8, st>>>(w.desc, w.src, w.binpos, w.tile_base, w.bin_start, w.valA, c.V, vbits, np, chunks, w.vrange, rsh, c.id_bits)
-    if (c.lds_rank) { if (packed) ICET_BIN_SCATTER(true, true); else ICET_BIN_SCATTER(true, false); }
-    else { if (packed) ICET_BIN_SCATTER(false, true); else ICET_BIN_SCATTER(false, false); }
-#undef ICET_BIN_SCATTER
+    with_flag(c.lds_rank != 0, [&](auto kLdsRank) { with_flag(packed, [&](auto kPacked) {      // (dynamic LDS: init_keyframe_kernels names every instantiation)
+        k_bin_scatter<kLdsRank(), kPacked()><<<grid, blk, (size_t)c.V * 12 + 8, st>>>(w.desc, w.src, w.binpos, w.tile_base, w.bin_start, w.sorted_row, c.V, vbits, np, chunks, w.vrange, rsh, c.id_bits);
+    }); });
     ICET_LAUNCH_CHECK();
     if (c.stage_event && c.stage_at == 3) { e = hipEventRecord(c.stage_event, st); if (e != hipSuccess) return e; }
-    // keyA / keyB (bucket-grouped keys and the overflow scratch of the rank sort) are dead by now: candidate rows and their r
     // (k_bin_scan zeroed the pairs' item counters; k_fit_finish takes a bin below n rows for empty without reading its record)
     FitItem* items = reinterpret_cast<FitItem*>(w.fit_items);
     // a fixed number of blocks per pair walks the pair's live bins / work items (their numbers are only known on the device):
     // enough blocks to fill the chip whatever the batch size
     const int fit_chunks = std::max(1, std::min((c.V + kBlock / 64 - 1) / (kBlock / 64), (ICET_FIT_BLOCKS + c.n_pairs - 1) / c.n_pairs));
     if (c.n_pairs <= 16)
-        k_fit_cluster<16><<<dim3(groups * fit_chunks), blk, 0, st>>>(w.desc, w.bin_start, w.valA, w.r1, w.keyA, reinterpret_cast<float*>(w.keyB), items, w.fit_n_items,
-                                                                    w.live_bins, w.n_live, w.midD, c.T, c.P, c.n, c.thresh, c.buff, np, fit_chunks, c.half_gap, c.use_library_sort ? nullptr : w.zero_rows, make_int4(w.zero_voxel[0], w.zero_voxel[1], w.zero_voxel[2], w.zero_voxel[3]));
+        k_fit_cluster<16><<<dim3(groups * fit_chunks), blk, 0, st>>>(w.desc, w.bin_start, w.sorted_row, w.r1, w.cand_row, w.cand_r, items, w.fit_n_items,
+                                                                    w.live_bins, w.n_live, w.midD, c.T, c.P, c.n, c.thresh, c.buff, np, fit_chunks, c.half_gap, w.zero_rows, make_int4(w.zero_voxel[0], w.zero_voxel[1], w.zero_voxel[2], w.zero_voxel[3]));
     else
-        k_fit_cluster<2><<<dim3(groups * fit_chunks), blk, 0, st>>>(w.desc, w.bin_start, w.valA, w.r1, w.keyA, reinterpret_cast<float*>(w.keyB), items, w.fit_n_items,
-                                                                    w.live_bins, w.n_live, w.midD, c.T, c.P, c.n, c.thresh, c.buff, np, fit_chunks, c.half_gap, c.use_library_sort ? nullptr : w.zero_rows, make_int4(w.zero_voxel[0], w.zero_voxel[1], w.zero_voxel[2], w.zero_voxel[3]));
+        k_fit_cluster<2><<<dim3(groups * fit_chunks), blk, 0, st>>>(w.desc, w.bin_start, w.sorted_row, w.r1, w.cand_row, w.cand_r, items, w.fit_n_items,
+                                                                    w.live_bins, w.n_live, w.midD, c.T, c.P, c.n, c.thresh, c.buff, np, fit_chunks, c.half_gap, w.zero_rows, make_int4(w.zero_voxel[0], w.zero_voxel[1], w.zero_voxel[2], w.zero_voxel[3]));
     ICET_LAUNCH_CHECK();
     {
         const int rt_chunks = std::max(1, std::min(64, (ICET_RT_BLOCKS + c.n_pairs - 1) / c.n_pairs));
-        k_fit_roundtrip<<<dim3(groups * rt_chunks), blk, 0, st>>>(w.desc, w.bin_start, w.keyA, reinterpret_cast<const float*>(w.keyB), items, w.fit_n_items, w.cart1, (size_t)w.cap_n1,
+        k_fit_roundtrip<<<dim3(groups * rt_chunks), blk, 0, st>>>(w.desc, w.bin_start, w.cand_row, w.cand_r, items, w.fit_n_items, w.cart1, (size_t)w.cap_n1,
                                                                   c.T, c.P, np, rt_chunks);
         ICET_LAUNCH_CHECK();
     }

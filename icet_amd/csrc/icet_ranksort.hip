@@ -613,8 +613,6 @@ static int rank_sort_cap(int max_n, int forced, int n_pairs) {
 static int rank_sort_log_cells(int cap) { return cap <= ICET_RS_SMALL_CAP ? ICET_RS_LOGC_SMALL : 12; }
 static size_t rank_sort_lds_bytes(int cap) { return (size_t)(cell_region(1 << rank_sort_log_cells(cap)) + kRedWords + 4 * cap) * 4; }
 
-// Outputs: w.valB = s (row with rank i), w.pred = rank of every row.  Scratch: w.key64A (bucket-grouped (key, row) pairs),
-// w.key64B (second buffer of an overflow bucket), w.bkt, w.counts / w.tile_base, w.splitters, w.n_buckets, w.bucket_start.
 hipError_t init_rank_sort_kernels() {
     const int lds = (int)rank_sort_lds_bytes(kCapMax);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_bucket_sort<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -639,11 +637,10 @@ hipError_t launch_rank_sort(const Workspace& w, const LaunchCfg& c, hipStream_t 
     hipError_t e = launch_class_scan(w.counts, w.tile_base, w.bucket_start, kMaxBuckets, chunks, np, st, nullptr, nullptr, 0, nullptr, nullptr, w.tile_vr, w.vrange);
     if (e != hipSuccess) return e;
     const bool packed = c.packed_rows != 0;
-    uint2* bkv = reinterpret_cast<uint2*>(w.key64A); uint2* alt = reinterpret_cast<uint2*>(w.key64B);
-    if (c.lds_rank) {
-        if (packed) k_rs_scatter_staged<true><<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, bkv, np, chunks, w.splitters, w.n_buckets, w.valB, w.pred, w.bin16, c.row_shift, c.id_bits);
-        else k_rs_scatter_staged<false><<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, bkv, np, chunks, w.splitters, w.n_buckets, w.valB, w.pred, w.bin16, c.row_shift, c.id_bits);
-    } else k_rs_scatter<<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, bkv, np, chunks);
+    if (c.lds_rank) with_flag(packed, [&](auto kPacked) {
+        k_rs_scatter_staged<kPacked()><<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, w.rs_pairs, np, chunks, w.splitters, w.n_buckets, w.row_of_rank, w.rank_of_row, w.bin16, c.row_shift, c.id_bits);
+    });
+    else k_rs_scatter<<<grid, blk, 0, st>>>(w.desc, w.r1, w.bkt, w.tile_base, w.bucket_start, w.rs_pairs, np, chunks);
     ICET_LAUNCH_CHECK();
     const int cap = rank_sort_cap(c.max_n1, c.rs_cap, c.n_pairs);
     const int zero_in_scatter = c.lds_rank ? 1 : 0;                       // (the ballot form of the multi-split does not write the zero bucket's ranks)
@@ -652,10 +649,9 @@ hipError_t launch_rank_sort(const Workspace& w, const LaunchCfg& c, hipStream_t 
     const bool two = groups * kMaxBuckets >= 16 * 256 && kRsPerBlockBatch != 1;
     const dim3 sgrid(two ? groups * (kMaxBuckets / kRsPerBlockBatch) : groups * kMaxBuckets);
     const size_t lds = rank_sort_lds_bytes(cap); const int logC = rank_sort_log_cells(cap);
-#define ICET_RS_SORT(PER, PACKED) k_rs_bucket_sort<PER, PACKED><<<sgrid, kSortBlock, lds, st>>>(w.desc, w.bucket_start, w.n_buckets, bkv, alt, w.valB, w.pred, cap, logC, c.rs_max_cell, np, w.splitters, zero_in_scatter, w.bin16, c.row_shift, c.id_bits)
-    if (two) { if (packed) ICET_RS_SORT(kRsPerBlockBatch, true); else ICET_RS_SORT(kRsPerBlockBatch, false); }
-    else { if (packed) ICET_RS_SORT(1, true); else ICET_RS_SORT(1, false); }
-#undef ICET_RS_SORT
+    with_flag(two, [&](auto kTwo) { with_flag(packed, [&](auto kPacked) {      // (dynamic LDS: init_rank_sort_kernels names every instantiation)
+        k_rs_bucket_sort<kTwo() ? kRsPerBlockBatch : 1, kPacked()><<<sgrid, kSortBlock, lds, st>>>(w.desc, w.bucket_start, w.n_buckets, w.rs_pairs, w.rs_pairs_alt, w.row_of_rank, w.rank_of_row, cap, logC, c.rs_max_cell, np, w.splitters, zero_in_scatter, w.bin16, c.row_shift, c.id_bits);
+    }); });
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }

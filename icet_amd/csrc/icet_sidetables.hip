@@ -62,9 +62,10 @@ __global__ __launch_bounds__(kBlock) void k_side_scan2(const PairDesc* __restric
 hipError_t launch_side_scan1(const Workspace& w, const LaunchCfg& c, float* sph, int32_t* index, hipStream_t st) {
     if (c.max_n1 <= 0) return hipSuccess;
     const int blocks = std::min(2048, (c.max_n1 + kBlock - 1) / kBlock);
-    k_side_scan1<<<blocks, kBlock, 0, st>>>(w.desc, w.src, w.keyB, sph, packed_row_mask(c));          // keyB: keyframe scratch, dead once the keyframe is built
+    uint32_t* inv = reinterpret_cast<uint32_t*>(w.cand_r);      // the position of every row, in scratch of the finished build (Workspace's lifetime table)
+    k_side_scan1<<<blocks, kBlock, 0, st>>>(w.desc, w.src, inv, sph, packed_row_mask(c));
     ICET_LAUNCH_CHECK();
-    k_side_index1<<<blocks, kBlock, 0, st>>>(w.desc, w.valA, w.keyB, index);
+    k_side_index1<<<blocks, kBlock, 0, st>>>(w.desc, w.sorted_row, inv, index);
     ICET_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -1093,8 +1093,8 @@ icet_status icet_debug_deskew_rows(const icet_deskew_scan* motion, int64_t n, co
  * 1 one block per pair from the recurrence, 0 chain walks over independent tiles, -1 by batch size), "fuse_solve" (batches below 32 pairs on grids up to 4096 voxels:
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
  * bits; default 0: measured no faster on MI355X, where a device-scope fence is an L2 write-back), "batch_parts" (0 = automatic), "batch_stage" (0..4), "force_exact"
- * (every scan-2 point through the literal classification), "library_sort" (rocPRIM radix sort instead of
- * the hand-written rank sort: only in a diagnostic build, `make EXTRA=-DICET_DIAG_LIBSORT`; the shipped library answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents), "map_query_prune" (icet_voxel_map_query_*: 1, the default, a block skips the queries whose run of x cells misses its chunk; 0 every cell is tested for every query; same bits), "map_evidence_prune" (icet_voxel_map_evidence_*: 1, the default, a block skips the scans whose run of x cells misses its chunk; same bits), "map_evidence_batch" (scans per batch of range images: 0, the default, as many as fit 64 MiB, else 1 .. 256; same bits), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
+ * (every scan-2 point through the literal classification), "library_sort" (0 only: the library has ONE sort, the
+ * hand-written rank sort, and no build flag brings another; any other value answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents), "map_query_prune" (icet_voxel_map_query_*: 1, the default, a block skips the queries whose run of x cells misses its chunk; 0 every cell is tested for every query; same bits), "map_evidence_prune" (icet_voxel_map_evidence_*: 1, the default, a block skips the scans whose run of x cells misses its chunk; same bits), "map_evidence_batch" (scans per batch of range images: 0, the default, as many as fit 64 MiB, else 1 .. 256; same bits), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
  * the condition number |A|_F |A^-1|_F exceeds it is inverted by the literal restatement of the reference's statements -- column-pivoted QR
  * pseudo-inverse, eigenvectors, pruning -- instead of a Cholesky factorisation; 0 = always literal.  Not a launch-shape knob: between the two
  * routes cov / dx differ by rounding times the condition number).  Unknown name or value

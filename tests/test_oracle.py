@@ -184,7 +184,7 @@ def _scramble_brute(s):
 
 
 def _scramble_closed_form(s):
-    """The parallel formulation the HIP kernels use (k_inverse_perm / k_exec_flags / k_scramble_src)."""
+    """The parallel formulation the HIP kernels use (the rank sort's pred[] / k_exec_flags / k_scramble_src)."""
     n = len(s); pred = np.empty(n, int); pred[s] = np.arange(n)
     ex = np.zeros(n, bool)
     for v in range(n):
