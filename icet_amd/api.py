@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_voxel_map_index", "icet_voxel_map_query_device", "icet_voxel_map_query_posed_device",
                     "icet_voxel_map_evidence_device", "icet_voxel_map_evidence_posed_device", "icet_voxel_map_evidence_fetch_device",
                     "icet_voxel_map_enable_shape", "icet_voxel_map_extract_shape_device", "icet_voxel_map_extract_shape",
+                    "icet_voxel_map_register_device", "icet_voxel_map_register_posed_device", "icet_debug_voxel_map_register_terms",
                     "icet_deskewer_create", "icet_deskewer_destroy", "icet_deskewer_last_error", "icet_deskew_device", "icet_deskew",
                     "icet_deskew_twists_from_poses_device", "icet_twist_from_pose", "icet_pose_from_twist", "icet_debug_deskew_rows",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
@@ -145,6 +146,78 @@ class MapShape(C.Structure):
     """icet_voxel_map_shape (include/icet_hip.h), 48 bytes: the shape columns of an extract_shape call, each column-major over ld; a pointer left out is None."""
     _fields_ = [("cov", C.c_void_p), ("normal", C.c_void_p), ("evals", C.c_void_p), ("moments", C.c_void_p), ("ld", C.c_int64), ("flags", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+VOXEL_MAP_REG_CONVERGED, VOXEL_MAP_REG_ITERATION_CAP, VOXEL_MAP_REG_STALLED, VOXEL_MAP_REG_NO_OVERLAP, VOXEL_MAP_REG_BAD_POSE = 0, 1, 2, 3, 4
+VOXEL_MAP_REG_MAX_ITERS = 64
+VOXEL_MAP_REG_CHUNK = 2048        # rows per block of the row pass (the sizes at which it takes another path)
+
+
+class MapRegisterParams(C.Structure):
+    """icet_voxel_map_register_params (include/icet_hip.h), 72 bytes."""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("sigma_min", C.c_double), ("scale", C.c_double), ("tol_t", C.c_double), ("tol_r", C.c_double),
+                ("lambda0", C.c_double), ("min_points", C.c_int32), ("min_matched", C.c_int32), ("max_iters", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class MapRegistration(C.Structure):
+    """icet_voxel_map_registration (include/icet_hip.h), 328 bytes: the record of one query."""
+    _fields_ = [("pose", C.c_float * 16), ("info", C.c_double * 21), ("g", C.c_double * 6), ("cost", C.c_double), ("cost_start", C.c_double), ("lambda_", C.c_double),
+                ("rows_scored", C.c_int32), ("rows_matched", C.c_int32), ("iterations", C.c_int32), ("accepted", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+MAP_REGISTRATION_DTYPE = np.dtype([("pose", "<f4", (16,)), ("info", "<f8", (21,)), ("g", "<f8", (6,)), ("cost", "<f8"), ("cost_start", "<f8"), ("lambda", "<f8"),
+                                   ("rows_scored", "<i4"), ("rows_matched", "<i4"), ("iterations", "<i4"), ("accepted", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+assert MAP_REGISTRATION_DTYPE.itemsize == 328 == C.sizeof(MapRegistration)
+# one row of icet_debug_voxel_map_register_terms, 256 bytes
+MAP_REGISTER_TERM_DTYPE = np.dtype([("key", "<u8"), ("cls", "<i4"), ("matched", "<i4"), ("s", "<f8"), ("omega", "<f8"), ("rho", "<f8"), ("g", "<f8", (6,)),
+                                    ("H", "<f8", (21,))])
+assert MAP_REGISTER_TERM_DTYPE.itemsize == 256
+MAP_REGISTER_DEFAULTS = dict(min_range=0.0, max_range=0.0, sigma_min=0.02, scale=11.3449, tol_t=1e-4, tol_r=1e-5, lambda0=1e-3, min_points=5, min_matched=50,
+                             max_iters=20)
+
+
+def map_register_params(**kw):
+    """A MapRegisterParams from keywords over MAP_REGISTER_DEFAULTS (the values a NULL params gives)."""
+    d = dict(MAP_REGISTER_DEFAULTS)
+    extra = set(kw) - set(d) - {"flags"}
+    if extra:
+        raise TypeError("unknown registration parameter(s): " + ", ".join(sorted(extra)))
+    d.update(kw)
+    return MapRegisterParams(float(d["min_range"]), float(d["max_range"]), float(d["sigma_min"]), float(d["scale"]), float(d["tol_t"]), float(d["tol_r"]),
+                             float(d["lambda0"]), int(d["min_points"]), int(d["min_matched"]), int(d["max_iters"]), int(d.get("flags", 0)))
+
+
+def info_matrix(info21):
+    """The symmetric 6 x 6 matrix of a record's 21 upper-triangle words (by rows)."""
+    H = np.zeros((6, 6), np.float64)
+    H[np.triu_indices(6)] = np.asarray(info21, np.float64).reshape(21)
+    return H + np.triu(H, 1).T
+
+
+def registration_cov(rec):
+    """H^-1 of a registration record (a dict of VoxelMap.register, or anything with an ``info`` of 21 words): the 6 x 6 covariance of the pose in the record's
+    tangent (translation, then rotation, world-aligned at the sensor origin).  NaN everywhere where H is not positive definite."""
+    H = info_matrix(rec["info"])
+    try:
+        if not np.isfinite(H).all():
+            raise np.linalg.LinAlgError("not finite")
+        L = np.linalg.cholesky(H)
+    except np.linalg.LinAlgError:
+        return np.full((6, 6), np.nan)
+    Li = np.linalg.inv(L)
+    return Li.T @ Li
+
+
+def info_body_from_world(info, R):
+    """A record's information in the pose graph's right-hand (body) tangent: both 3-blocks rotated by the pose's rotation R, A = diag(R, R), A^T H A.  ``info``:
+    21 words or a 6 x 6 matrix; returns 6 x 6."""
+    H = np.asarray(info, np.float64)
+    H = info_matrix(H) if H.size == 21 else H.reshape(6, 6)
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    A = np.zeros((6, 6)); A[:3, :3] = R; A[3:, 3:] = R
+    return A.T @ H @ A
 
 
 def cov_matrix(cov6):
@@ -612,6 +685,9 @@ def load_library():
     L.icet_voxel_map_enable_shape.argtypes = [C.c_void_p]
     L.icet_voxel_map_extract_shape_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(MapShape), C.POINTER(MapStats)]
     L.icet_voxel_map_extract_shape.argtypes = L.icet_voxel_map_extract_shape_device.argtypes
+    L.icet_voxel_map_register_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(MapRegisterParams), C.c_void_p]
+    L.icet_voxel_map_register_posed_device.argtypes = L.icet_voxel_map_register_device.argtypes
+    L.icet_debug_voxel_map_register_terms.argtypes = [C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.POINTER(MapRegisterParams), C.c_void_p]
     L.icet_deskewer_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.icet_deskewer_destroy.argtypes = [C.c_void_p]
     L.icet_deskewer_last_error.argtypes = [C.c_void_p]; L.icet_deskewer_last_error.restype = C.c_char_p
@@ -2083,6 +2159,86 @@ class VoxelMap:
         res = self.evidence_fetch()
         res["stats"] = st
         return res
+
+    def register_device(self, descs, poses, d_records_ptr, params=None, **kw):
+        """Register the scans (device_ptr, n, ld) against the map's Gaussians from the start ``poses``: a Q x 4 x 4 NumPy array
+        (icet_voxel_map_register_device) or a float32 CUDA tensor (icet_voxel_map_register_posed_device; ``register_posed_device`` is this call with a tensor).
+        ``d_records_ptr``: Q records of MAP_REGISTRATION_DTYPE on the device.  ``params``: a MapRegisterParams, or keywords over MAP_REGISTER_DEFAULTS; neither:
+        NULL, the library's defaults.  Several queries may name one scan.  Asynchronous on the context's stream."""
+        A = _dev_scans(descs)
+        P = params if params is not None else (map_register_params(**kw) if kw else None)
+        pp = C.byref(P) if P is not None else None
+        L = load_library()
+        if isinstance(poses, np.ndarray) or not hasattr(poses, "data_ptr"):
+            T = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 16))
+            if T.shape[0] != len(descs):
+                raise IcetError(ICET_ERR_BAD_ARG, "one 4 x 4 pose per scan")
+            self._check(L.icet_voxel_map_register_device(self._h, len(descs), A, T.ctypes.data if len(descs) else None, pp, _vp(d_records_ptr)))
+            return
+        import torch
+        if not (poses.is_cuda and poses.dtype == torch.float32 and poses.is_contiguous()) or poses.numel() != 16 * len(descs):
+            raise IcetError(ICET_ERR_BAD_ARG, "device poses must be a contiguous float32 CUDA tensor of one 4 x 4 pose per scan")
+        torch.cuda.current_stream(poses.device).synchronize()          # the context's stream is its own: the tensor must be complete
+        self._check(L.icet_voxel_map_register_posed_device(self._h, len(descs), A, _vp(poses.data_ptr()), pp, _vp(d_records_ptr)))
+
+    def register_posed_device(self, descs, d_poses, d_records_ptr, params=None, **kw):
+        """register_device with the start poses in a float32 CUDA tensor (icet_voxel_map_register_posed_device)."""
+        if not hasattr(d_poses, "data_ptr"):
+            raise IcetError(ICET_ERR_BAD_ARG, "register_posed_device takes a CUDA tensor of poses")
+        self.register_device(descs, d_poses, d_records_ptr, params, **kw)
+
+    def register_records(self, descs, poses, params=None, **kw):
+        """register_device into a buffer of its own; synchronises; the records as a NumPy array of MAP_REGISTRATION_DTYPE."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        out = torch.zeros(max(len(descs), 1) * MAP_REGISTRATION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.register_device(descs, poses, out.data_ptr(), params, **kw)
+        self._ctx.sync()
+        return out.cpu().numpy().view(MAP_REGISTRATION_DTYPE)[:len(descs)].copy()
+
+    def register(self, scans, poses, scan_of=None, **params):
+        """register_device for host N x 3 arrays: staged on the device, synchronises, one dict per pose -- pose (4, 4) float32, info (21,), g (6,), cost,
+        cost_start, lambda, rows_scored, rows_matched, iterations, accepted, status.  ``scan_of``: per pose the index of its scan (default: pose k takes scan k),
+        so that several start poses share one staged scan."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        bufs = [torch.from_numpy(_colmajor(s)).to(dev) for s in scans]
+        torch.cuda.synchronize(dev)
+        T = np.asarray(poses, np.float32).reshape(-1, 16)
+        of = list(range(T.shape[0])) if scan_of is None else [int(k) for k in scan_of]
+        descs = [(bufs[k].data_ptr(), bufs[k].shape[1], bufs[k].shape[1]) for k in of]
+        recs = self.register_records(descs, T, **params)
+        res = []
+        for r in recs:
+            d = {n: (r[n].copy() if r[n].shape else r[n].item()) for n in MAP_REGISTRATION_DTYPE.names if n != "reserved"}
+            d["pose"] = d["pose"].reshape(4, 4)
+            res.append(d)
+        return res
+
+    def score(self, scans, poses, scan_of=None, **params):
+        """The cost, gradient and information of the given poses against the map, without a step: ``register`` with max_iters = 0."""
+        params["max_iters"] = 0
+        return self.register(scans, poses, scan_of, **params)
+
+    def register_terms(self, scan, pose, **params):
+        """icet_debug_voxel_map_register_terms for a host N x 3 array: one record of MAP_REGISTER_TERM_DTYPE per row at ``pose``."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        buf = torch.from_numpy(_colmajor(scan)).to(dev)
+        n = buf.shape[1]
+        out = torch.zeros(max(n, 1) * MAP_REGISTER_TERM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.register_terms_device((buf.data_ptr(), n, n), pose, out.data_ptr(), **params)
+        self._ctx.sync()
+        return out.cpu().numpy().view(MAP_REGISTER_TERM_DTYPE)[:n].copy()
+
+    def register_terms_device(self, desc, pose, d_terms_ptr, params=None, **kw):
+        """One record per row of the scan (device_ptr, n, ld) at the HOST pose into d_terms (device, n records of MAP_REGISTER_TERM_DTYPE).  Asynchronous."""
+        A = _dev_scans([desc])
+        P = params if params is not None else (map_register_params(**kw) if kw else None)
+        T = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        self._check(load_library().icet_debug_voxel_map_register_terms(self._h, A, T.ctypes.data, C.byref(P) if P is not None else None, _vp(d_terms_ptr)))
 
     def query_device(self, poses, outs, d_rows_ptr, min_range=0.0, max_range=0.0, min_points=1, world=False, d_total_ptr=None, d_status_ptr=None, static=False):
         """For each pose the cells of the map within (min_range, max_range] of it, in the pose's own frame (``world``: in the map's), in key order, into device

@@ -252,6 +252,7 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            icet_voxel_map_create, _clear, _add_device, _add_posed_device; _stats, _extract_device, _extract (drain as well; icet_map.hip);
 //                            icet_voxel_map_index, _query_device, _query_posed_device (drain only when the index is stale and they rebuild it);
 //                            icet_voxel_map_evidence_device, _evidence_posed_device (the same, and when their buffers grow or *out is asked for), _evidence_fetch_device
+//                            icet_voxel_map_register_device, _register_posed_device, icet_debug_voxel_map_register_terms (drain only when their buffers grow; icet_map_register.hip)
 //                            icet_deskewer_create, icet_deskew_device, icet_deskew_twists_from_poses_device (drain only when the records' stage grows); icet_deskew (drains as well; icet_deskew.hip)
 //   arms or disarms itself   icet_solve_batch_device
 //   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_spherical, icet_debug_block_tridiag (copy in, one kernel, copy out,

@@ -429,6 +429,18 @@ hipError_t launch_class_scan(const uint32_t* counts, uint32_t* tile_base, int32_
                              int32_t* live = nullptr, int32_t* n_live = nullptr, int live_min = 0, uint32_t* n_items = nullptr, const int32_t* class_range = nullptr,
                              const int32_t* tile_vr = nullptr, int32_t* vrange_out = nullptr);
 
+// icet_map.hip: what icet_map_register.hip reads of a voxel map -- the table as it lies on the device (key | count | sum[3] | mom[9], each
+// of 2^log2 entries; mom null on a plain map), a generation that every add, remove, clear and enable_shape raises, and the slot of the registration's own state,
+// which the map frees with `reg_free` when it is destroyed.  Null map: false.
+struct MapRegisterView {
+    icet_ctx* ctx; float cell; uint32_t log2;
+    const unsigned long long* key; const unsigned long long* count; const unsigned long long* sum; const unsigned long long* mom;
+    uint64_t generation;
+    void** reg; void (**reg_free)(void*);
+};
+__attribute__((visibility("hidden"))) bool map_register_view(icet_voxel_map* m, MapRegisterView* v);
+__attribute__((visibility("hidden"))) void map_set_error(icet_voxel_map* m, const char* why);
+
 }  // namespace icet
 
 // nodes: point a context at another stream for the calls that follow (the caller restores it; a captured graph replays into whatever stream is set)

@@ -671,6 +671,9 @@ struct icet_voxel_map {
     uint32_t* ev_img = nullptr; uint32_t* ev_near = nullptr; int64_t cap_img = 0;
     u64* ev_ctr = nullptr; u64* ev_h_ctr = nullptr; int32_t cap_evrec = 0;
     bool ev_valid = false;
+    // the registration against the Gaussians (section 26; icet_map_register.hip, through map_register_view): generation counts what changes the table -- add, remove,
+    // clear, enable_shape --, reg is that file's own state, freed with reg_free when the map goes
+    uint64_t generation = 0; void* reg = nullptr; void (*reg_free)(void*) = nullptr;
     BufferGroup table, record, xout, index, qcounts, evidence, evimages, evrecord, moments, xshape;
     MapShapeTable shape_table() const { MapShapeTable s; static_cast<MapTable&>(s) = t; s.mom = mom; return s; }
 };
@@ -692,7 +695,7 @@ static unsigned table_grid(const MapTable& t) { return (unsigned)((((size_t)1 <<
 static icet_status map_clear(icet_voxel_map* m) {
     const size_t size = (size_t)1 << m->t.log2;
     hipStream_t st = m->ctx->stream;
-    m->ix_stale = true;
+    m->ix_stale = true; m->generation++;
     MAPCHK(m, hipMemsetAsync(m->t.key, 0xFF, sizeof(u64) * size, st));
     MAPCHK(m, hipMemsetAsync(m->t.count, 0, sizeof(u64) * size, st));
     MAPCHK(m, hipMemsetAsync(m->t.sum, 0, sizeof(u64) * 3 * size, st));
@@ -736,7 +739,7 @@ static icet_status map_add(icet_voxel_map* m, int32_t n, const icet_dev_scan* sc
     if (blocks > 0x7FFFFFFF) return map_refuse(m, std::string(call) + ": too many rows in one call");
     if (blocks == 0) return ICET_OK;                                  // nothing to read
     icet_ctx* c = m->ctx;
-    m->ix_stale = true; m->dirty = true;                              // (from here on the table may change)
+    m->ix_stale = true; m->dirty = true; m->generation++;             // (from here on the table may change)
     CallStage<MapScan>& s = m->add;
     MAPCHK(m, s.begin(n, c->stream));
     int32_t b0 = 0;
@@ -1035,6 +1038,15 @@ static icet_status map_evidence(icet_voxel_map* m, int32_t n, const icet_dev_sca
     return ICET_OK;
 }
 
+namespace icet {
+bool map_register_view(icet_voxel_map* m, MapRegisterView* v) {
+    if (!m) return false;
+    *v = MapRegisterView{m->ctx, m->params.cell, m->t.log2, m->t.key, m->t.count, m->t.sum, m->mom, m->generation, &m->reg, &m->reg_free};
+    return true;
+}
+void map_set_error(icet_voxel_map* m, const char* why) { if (m) m->err = why; }
+}  // namespace icet
+
 extern "C" {
 
 icet_status icet_voxel_map_evidence_device(icet_voxel_map* m, int32_t n, const icet_dev_scan* scans, const float* poses, const icet_voxel_map_evidence* e,
@@ -1096,6 +1108,7 @@ icet_status icet_voxel_map_destroy(icet_voxel_map* m) {
     if (!m) return ICET_ERR_BAD_ARG;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);              // (an add or an extract may still read or write the table)
+    if (m->reg && m->reg_free) m->reg_free(m->reg);
     delete m;                                                // (every array belongs to a group, every event to a stage)
     return ICET_OK;
 }
@@ -1139,6 +1152,7 @@ icet_status icet_voxel_map_enable_shape(icet_voxel_map* m) {
     const hipError_t z = hipMemsetAsync(m->mom, 0, sizeof(u64) * srule::kWords * size, m->ctx->stream);
     if (z != hipSuccess) m->moments.release();
     MAPCHK(m, z);
+    m->generation++;
     return ICET_OK;
 }
 

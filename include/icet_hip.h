@@ -1014,6 +1014,71 @@ icet_status icet_voxel_map_extract_shape_device(icet_voxel_map* map, int32_t min
 icet_status icet_voxel_map_extract_shape(icet_voxel_map* map, int32_t min_points, float* xyz, int64_t ld, int64_t cap_rows, int64_t* count, uint64_t* key,
                                          const icet_voxel_map_shape* shape, struct icet_voxel_map_stats* out);
 
+/* --- registration against the map's Gaussians (a SHAPED map) -------------------------------------------------------------------------------
+ * Scans at start poses in, refined poses out: NDT-style point-to-distribution Gauss-Newton against the cells of the map as they lie in the table, for many scans
+ * or many start hypotheses of one scan in one call, nothing leaving the device.  THE RULE (icet_amd/csrc/icet_map_register.h is the authority on the order of
+ * the operations; IEEE double, one rounding per operation, nothing contracted, no transcendental):
+ *   a cell of count n >= max(1, min_points) has the mean mu_a = ((double)c_a + (double)sum_a / ((double)n 2^32)) (double)cell, the covariance C of "the voxel
+ *   map's shape", C' = C + sigma_min^2 I and the weight W = C'^-1 (adjugate over determinant); a determinant that is not finite and > 0 leaves the cell out.
+ *   A row p of a scan at the pose P = (R, t): non-finite rows and rows outside (min_range, max_range] of THIS call take no part; every other row is SCORED:
+ *   r = R p, w = r + t; a row outside the grid, in no cell or in an unusable one is a MISS and costs exactly `scale`; else d = w - mu, a = W d, s = d . a,
+ *   the row costs rho = scale s / (scale + s) (Geman-McClure) and weighs omega = (scale / (scale + s))^2.  cost = sum rho.
+ *   TANGENT: delta = (rho_t, om), world-aligned at the sensor origin: w' = w + rho_t + om x r, J = [I | -[r]x]; g = sum omega J^T a, info = sum omega J^T W J
+ *   (the upper triangle by rows, 21 doubles).  RETRACTION: R <- E(om) R, t <- t + rho_t, E the rotation of icet_pose_from_twist((0, om), 1), |om| <= 1.
+ *   LOOP: Levenberg-Marquardt, (info + lambda diag(info)) delta = -g by a 6 x 6 Cholesky; a trial is accepted iff its cost is finite and below the current one
+ *   (lambda / 10, not below 1e-9), else lambda x 10 (above 1e9: STALLED); CONVERGED when an accepted step has |rho_t| <= tol_t and |om| <= tol_r.
+ * max_iters = 0 scores the given poses.  Asynchronous on the context's stream: a fixed number of launches (the Gaussians if they are stale, then 1 + max_iters
+ * passes of two kernels), no host round trip.  The Gaussians are rebuilt after add, remove, clear and enable_shape and when sigma_min or min_points change.
+ * Queries may share a scan descriptor (several start poses of one scan).  Sums in a fixed order: the same call gives the same bits, and a query's bits depend on
+ * neither its place in the call nor its neighbours.
+ * Refusals (ICET_ERR_BAD_ARG, the reason in icet_voxel_map_last_error, nothing touched): a map without shape, a NULL map or array, n_q outside 1 ..
+ *   ICET_VOXEL_MAP_MAX_QUERIES, a bad descriptor, sigma_min, scale or lambda0 not finite and > 0, max_iters outside 0 .. 64, negative tolerances, non-finite
+ *   ranges, nonzero flags or reserved words, d_records or d_poses misaligned.  No CPU fall-back. */
+#define ICET_VOXEL_MAP_REG_CONVERGED 0
+#define ICET_VOXEL_MAP_REG_ITERATION_CAP 1         /* still running after pass max_iters (every scored pose of max_iters = 0) */
+#define ICET_VOXEL_MAP_REG_STALLED 2
+#define ICET_VOXEL_MAP_REG_NO_OVERLAP 3            /* fewer than min_matched rows matched at the start pose: pose = the start pose's bits */
+#define ICET_VOXEL_MAP_REG_BAD_POSE 4              /* a non-finite entry in the start pose */
+#define ICET_VOXEL_MAP_REG_MAX_ITERS 64
+typedef struct icet_voxel_map_register_params {
+    float min_range, max_range;   /* of this call, as icet_voxel_map_params' (max_range <= 0: no limit) */
+    double sigma_min;             /* the live point's own noise, metres (0.02) */
+    double scale;                 /* the robust scale in chi2 units, and the cost of a miss (11.3449: the 99 % quantile of chi2 with three degrees of freedom) */
+    double tol_t, tol_r;          /* metres (1e-4), radians (1e-5) */
+    double lambda0;               /* 1e-3 */
+    int32_t min_points;           /* 5 */
+    int32_t min_matched;          /* 50 */
+    int32_t max_iters;            /* 20; 0 .. 64 */
+    int32_t flags;                /* 0 */
+    int32_t reserved[2];          /* 0 */
+} icet_voxel_map_register_params; /* 72 bytes; NULL: the defaults */
+typedef struct icet_voxel_map_registration {
+    float pose[16];               /* the pose returned, 4 x 4 row-major */
+    double info[21];              /* sum omega J^T W J at that pose, upper triangle by rows, in the tangent (rho_t, om) above */
+    double g[6];                  /* sum omega J^T a at that pose */
+    double cost, cost_start;      /* sum rho at the pose returned and at the start pose */
+    double lambda;
+    int32_t rows_scored, rows_matched;
+    int32_t iterations, accepted; /* passes after the first, and the trials among them that were accepted */
+    int32_t status;               /* ICET_VOXEL_MAP_REG_* */
+    int32_t reserved;
+} icet_voxel_map_registration;    /* 328 bytes, 8-byte aligned */
+/* one row of icet_debug_voxel_map_register_terms */
+typedef struct icet_voxel_map_register_term {
+    uint64_t key;                 /* the row's cell (all ones: outside the grid or not scored) */
+    int32_t cls;                  /* the map rule's class: 0 scored, 1 non-finite, 2 range, 3 outside the grid */
+    int32_t matched;
+    double s, omega, rho;         /* zero for a row that is not scored; a miss: s 0, omega 0, rho scale */
+    double g[6], H[21];
+} icet_voxel_map_register_term;   /* 256 bytes */
+icet_status icet_voxel_map_register_device(icet_voxel_map* map, int32_t n_q, const icet_dev_scan* scans, const float* poses,
+                                           const icet_voxel_map_register_params* params, icet_voxel_map_registration* d_records);
+icet_status icet_voxel_map_register_posed_device(icet_voxel_map* map, int32_t n_q, const icet_dev_scan* scans, const float* d_poses,
+                                                 const icet_voxel_map_register_params* params, icet_voxel_map_registration* d_records);
+/* For ONE query (a scan and a HOST pose): the row pass of the start pose, and per row of the scan one record into d_terms (DEVICE, scan->n records). */
+icet_status icet_debug_voxel_map_register_terms(icet_voxel_map* map, const icet_dev_scan* scan, const float* pose, const icet_voxel_map_register_params* params,
+                                                icet_voxel_map_register_term* d_terms);
+
 /* --- deskew: undo a sweep's motion in many scans, in one call ---------------------------------------------------------------------------
  * A spinning lidar takes 50 - 100 ms per sweep; the rows of one scan are taken from a moving sensor.  A deskewer carries every row into the sensor frame at ONE
  * instant of the sweep, given the sweep's motion as a twist and a time (or a column index) per row.  It borrows a context like a store or a map (destroy it
