@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = ("icet_create", "icet_destroy", "icet_last_error", "icet_vers
                     "icet_voxel_map_evidence_device", "icet_voxel_map_evidence_posed_device", "icet_voxel_map_evidence_fetch_device",
                     "icet_voxel_map_enable_shape", "icet_voxel_map_extract_shape_device", "icet_voxel_map_extract_shape",
                     "icet_voxel_map_register_device", "icet_voxel_map_register_posed_device", "icet_debug_voxel_map_register_terms",
+                    "icet_voxel_map_save", "icet_voxel_map_load", "icet_voxel_map_snapshot_info", "icet_voxel_map_merge_device",
                     "icet_deskewer_create", "icet_deskewer_destroy", "icet_deskewer_last_error", "icet_deskew_device", "icet_deskew",
                     "icet_deskew_twists_from_poses_device", "icet_twist_from_pose", "icet_pose_from_twist", "icet_debug_deskew_rows",
                     "icet_keyframe_store_save", "icet_keyframe_store_load", "icet_keyframe_store_snapshot_info", "icet_keyframe_store_snapshot_slots",
@@ -273,6 +274,13 @@ class SnapshotInfo(C.Structure):
     """icet_snapshot_info (include/icet_hip.h), 120 bytes: what a snapshot file of a keyframe store says about itself."""
     _fields_ = [("shape", Params), ("V", C.c_int32), ("entries", C.c_int32), ("highest_slot", C.c_int32), ("has_appearance", C.c_int32), ("has_coarse", C.c_int32),
                 ("appearance", AppearanceParams), ("coarse", CoarseParams), ("file_bytes", C.c_int64)]
+
+
+class MapSnapshotInfo(C.Structure):
+    """struct icet_voxel_map_snapshot_info (include/icet_hip.h), 96 bytes: what a snapshot file of a voxel map says about itself."""
+    _fields_ = [("cell", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("shaped", C.c_int32), ("words_per_entry", C.c_int32), ("reserved0", C.c_int32),
+                ("entries", C.c_int64), ("points_in", C.c_int64), ("points_kept", C.c_int64), ("points_nonfinite", C.c_int64), ("points_outside", C.c_int64),
+                ("points_dropped", C.c_int64), ("file_bytes", C.c_int64), ("payload_checksum", C.c_uint64), ("reserved", C.c_int32 * 2)]
 
 
 class CoarseSearch(C.Structure):
@@ -688,6 +696,10 @@ def load_library():
     L.icet_voxel_map_register_device.argtypes = [C.c_void_p, C.c_int32, C.POINTER(DevScan), C.c_void_p, C.POINTER(MapRegisterParams), C.c_void_p]
     L.icet_voxel_map_register_posed_device.argtypes = L.icet_voxel_map_register_device.argtypes
     L.icet_debug_voxel_map_register_terms.argtypes = [C.c_void_p, C.POINTER(DevScan), C.c_void_p, C.POINTER(MapRegisterParams), C.c_void_p]
+    L.icet_voxel_map_save.argtypes = [C.c_void_p, C.c_char_p]
+    L.icet_voxel_map_load.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.icet_voxel_map_snapshot_info.argtypes = [C.c_char_p, C.POINTER(MapSnapshotInfo)]
+    L.icet_voxel_map_merge_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     L.icet_deskewer_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.icet_deskewer_destroy.argtypes = [C.c_void_p]
     L.icet_deskewer_last_error.argtypes = [C.c_void_p]; L.icet_deskewer_last_error.restype = C.c_char_p
@@ -2070,6 +2082,62 @@ class VoxelMap:
         eigenvalues and a normal per cell.  Only on a map that has read no row since it was created or last cleared; does nothing on a shaped map."""
         self._check(load_library().icet_voxel_map_enable_shape(self._h))
         self.shape = True
+
+    def save(self, path):
+        """The map's cells and running totals into the file ``path`` (icet_voxel_map_save): every claimed entry with a non-zero word, by
+        ascending key, so the bytes are a function of the map's contents alone.  In stream order behind what was enqueued; returns once the file is closed.  A
+        failed save leaves nothing at ``path``.  The map is not changed."""
+        self._check(load_library().icet_voxel_map_save(self._h, os.fsencode(path)))
+
+    def load(self, path, sign=1):
+        """Add (``sign`` 1) or subtract (-1) the cells and totals of the file ``path`` (icet_voxel_map_load).  The file is validated and held against the map
+        first -- the same cell, no plain file into a shaped map, room for its new keys --; a refusal touches nothing.  Synchronises."""
+        self._check(load_library().icet_voxel_map_load(self._h, os.fsencode(path), int(sign)))
+
+    @staticmethod
+    def snapshot_info(path):
+        """What the file ``path`` holds, read and validated on the host: dict(cell, min_range, max_range, shaped, words_per_entry, entries, the five totals,
+        file_bytes, payload_checksum)."""
+        info = MapSnapshotInfo()
+        st = load_library().icet_voxel_map_snapshot_info(os.fsencode(path), C.byref(info))
+        if st != ICET_OK:
+            raise IcetError(st, "%s cannot be read or is not a valid voxel-map snapshot" % path)
+        d = {n: getattr(info, n) for n, _ in info._fields_ if not n.startswith("reserved")}
+        d["shaped"] = bool(d["shaped"])
+        return d
+
+    @classmethod
+    def from_file(cls, ctx, path, table_log2=None):
+        """A new map on ``ctx`` with the file's cell, ranges and shape, holding its contents.  ``table_log2``: by default the smallest table that the file's
+        entries fill at most half, never below 10."""
+        info = cls.snapshot_info(path)
+        if table_log2 is None:
+            table_log2 = max(10, (2 * max(int(info["entries"]), 1) - 1).bit_length())
+        m = cls(ctx, cell=info["cell"], min_range=info["min_range"], max_range=info["max_range"], table_log2=table_log2, shape=info["shaped"])
+        try:
+            m.load(path)
+        except Exception:
+            m.close()
+            raise
+        return m
+
+    def merge(self, other, sign=1):
+        """Add (``sign`` 1) or subtract (-1) the cells and totals of ``other``, a map of the same cell on the same context (icet_voxel_map_merge_device): load's
+        rules with the source in device memory.  ``other`` is only read."""
+        if not isinstance(other, VoxelMap) or not getattr(other, "_h", None):
+            raise IcetError(ICET_ERR_BAD_ARG, "merge takes an open VoxelMap")
+        self._check(load_library().icet_voxel_map_merge_device(self._h, other._h, int(sign)))
+
+    def grown(self, table_log2):
+        """A new map with a table of 2^table_log2 entries and this map's parameters, shape, contents and totals (through ``merge``): the answer to
+        VOXEL_MAP_TABLE_FULL.  Entries that a remove emptied are not carried over.  This map is only read."""
+        m = VoxelMap(self._ctx, cell=self.params.cell, min_range=self.params.min_range, max_range=self.params.max_range, table_log2=table_log2, shape=self.shape)
+        try:
+            m.merge(self)
+        except Exception:
+            m.close()
+            raise
+        return m
 
     def extract_shape_device(self, d_xyz_ptr, ld, cap_rows, min_points=1, d_count_ptr=None, d_key_ptr=None, d_cov_ptr=None, d_normal_ptr=None, d_evals_ptr=None,
                              d_moments_ptr=None, shape_ld=None):

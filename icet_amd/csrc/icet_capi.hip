@@ -1551,6 +1551,7 @@ icet_status icet_set_option(icet_ctx* c, const char* name, double value) {
     else if (k == "map_query_prune") c->map_query_prune = iv != 0;
     else if (k == "map_evidence_prune") c->map_evidence_prune = iv != 0;
     else if (k == "map_evidence_batch") { if (!(value >= 0.0 && value <= 256.0)) { c->err = "map_evidence_batch must lie in 0 .. 256 (0: automatic)"; return ICET_ERR_BAD_ARG; } c->map_evidence_batch = iv; }
+    else if (k == "map_snapshot_chunk_entries") { if (!(value >= 0.0 && value <= 1073741824.0)) { c->err = "map_snapshot_chunk_entries must lie in 0 .. 2^30 (0: the default, 2^20)"; return ICET_ERR_BAD_ARG; } c->map_snapshot_chunk_entries = (int64_t)value; }
     else { c->err = "unknown option: " + k; return ICET_ERR_BAD_ARG; }
     return ICET_OK;
 }

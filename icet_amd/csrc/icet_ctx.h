@@ -127,6 +127,7 @@ struct icet_ctx {
     int map_query_prune = 1;                                     // option "map_query_prune": a voxel map's query skips the chunks outside a pose's run of x cells
     int map_evidence_prune = 1;                                  // option "map_evidence_prune": the same for the scans of a voxel map's evidence (icet_map.hip)
     int map_evidence_batch = 0;                                  // option "map_evidence_batch": scans per batch of range images; 0: as many as fit 64 MiB, 1 .. 256
+    int64_t map_snapshot_chunk_entries = 0;                    // option "map_snapshot_chunk_entries": entries per chunk of a voxel map's save / load (0: 2^20; icet_map_snapshot.hip)
     int64_t snapshot_chunk_bytes = 0;                          // option "snapshot_chunk_bytes": payload bytes per chunk of a store's save / load (0: 64 MiB)
     // Who owns what w and the pointers above point at: one group per set of arrays that grows together (the ensure_* functions of icet_capi.hip).  delete frees them (last member: gone first).
     struct Mem {
@@ -253,6 +254,7 @@ static inline icet_status staging_upload(icet_ctx* c, const Workspace& wv, const
 //                            icet_voxel_map_index, _query_device, _query_posed_device (drain only when the index is stale and they rebuild it);
 //                            icet_voxel_map_evidence_device, _evidence_posed_device (the same, and when their buffers grow or *out is asked for), _evidence_fetch_device
 //                            icet_voxel_map_register_device, _register_posed_device, icet_debug_voxel_map_register_terms (drain only when their buffers grow; icet_map_register.hip)
+//                            icet_voxel_map_save, _load (drain as well), _merge_device (drains once, for its capacity check; icet_map_snapshot.hip)
 //                            icet_deskewer_create, icet_deskew_device, icet_deskew_twists_from_poses_device (drain only when the records' stage grows); icet_deskew (drains as well; icet_deskew.hip)
 //   arms or disarms itself   icet_solve_batch_device
 //   drains before it returns icet_debug_gn_tail, icet_debug_pinv3, icet_debug_pinv3_double, icet_debug_fix, icet_debug_spherical, icet_debug_block_tridiag (copy in, one kernel, copy out,

@@ -440,6 +440,21 @@ struct MapRegisterView {
 };
 __attribute__((visibility("hidden"))) bool map_register_view(icet_voxel_map* m, MapRegisterView* v);
 __attribute__((visibility("hidden"))) void map_set_error(icet_voxel_map* m, const char* why);
+// icet_map.hip: what icet_map_snapshot.hip reads and writes of a voxel map -- the parameters a file names, the table and the device record
+// of the totals (kCtr*, icet_map_table.h), the three words a load or a merge changes as an add does (generation raised, ix_stale and dirty set), and the slot of
+// the snapshot code's own state, which the map frees with `snap_free` when it is destroyed.  Null map: false.
+struct MapSnapshotView {
+    icet_ctx* ctx; float cell, min_range, max_range; uint32_t log2;
+    unsigned long long* key; unsigned long long* count; unsigned long long* sum; unsigned long long* mom; unsigned long long* ctr;
+    uint64_t* generation; bool* ix_stale; bool* dirty;
+    void** snap; void (**snap_free)(void*);
+};
+__attribute__((visibility("hidden"))) bool map_snapshot_view(icet_voxel_map* m, MapSnapshotView* v);
+// The sort by key of map_sorted_cells over a SortedCells (icet_map_table.h) of the caller's, with the caller's selection step: `select` enqueues what writes the n
+// pairs into sc.sel_key / sc.sel_idx; n is a host value read behind a drained stream (the buffers may grow).  A failure names itself in the map's last error.
+struct SortedCells;
+typedef hipError_t (*MapSelectFn)(void* arg, SortedCells& sc, int64_t n, hipStream_t st);
+__attribute__((visibility("hidden"))) int map_sort_cells(icet_voxel_map* m, SortedCells& sc, int64_t n, MapSelectFn select, void* arg);      // an icet_status
 
 }  // namespace icet
 

@@ -34,6 +34,7 @@
 #include "icet_map_query.h"
 #include "icet_map_evidence.h"
 #include "icet_map_shape.h"
+#include "icet_map_table.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -49,8 +50,6 @@ namespace rule = icet_map_rule;
 namespace qrule = icet_map_query_rule;
 namespace erule = icet_map_evidence_rule;
 namespace srule = icet_map_shape_rule;
-typedef unsigned long long u64;
-
 constexpr int kAddBlock = 256;
 constexpr int kRowsPerBlock = 2048;      // a block's chunk of one scan: two trips of 256 lanes x 4 rows
 constexpr int kLdsSlots = 1024;          // 36 KB of LDS: key 8 | sums 24 | count 4 bytes per slot
@@ -69,57 +68,7 @@ static_assert(qrule::kMaxQueries <= kQueryBlock && qrule::kMaxQueries == ICET_VO
 
 struct MapScan { const float* ptr; int32_t n, ld, block0, pad; };      // block0: the first block of the scan in the launch
 static_assert(sizeof(MapScan) == 24, "ptr | n | ld | block0 | pad");
-// key[size] | count[size] (two's complement) | sum[3][size]
-struct MapTable { u64* key; u64* count; u64* sum; uint32_t log2; };
-// a shaped map's table (section 25): beside it mom[9][size], the words S_x S_y S_z M_xx M_xy M_xz M_yy M_yz M_zz.  The plain kernels take the plain struct.
-struct MapShapeTable : MapTable { u64* mom; };
-template <bool kShape> using TableOf = std::conditional_t<kShape, MapShapeTable, MapTable>;
-// the device record: kTotCopies copies of the running totals, one 64-byte line each (a block adds to copy blockIdx % kTotCopies, so that the blocks of a launch
-// do not all queue on one address; the host sums the copies), then what the last count pass saw and the select pass's cursor
-enum { kCtrIn = 0, kCtrKept, kCtrNonfinite, kCtrOutside, kCtrDropped, kTotWords = 8 };
-constexpr int kTotCopies = 64;
-enum { kCtrOccupied = kTotCopies * kTotWords, kCtrOut, kCtrNegative, kCtrSelected, kCtrWords = kTotCopies * kTotWords + 8 };
-
-#define MAP_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#define MAP_RLX_WG __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP
-
-// count += dn, sum_a += d_a in the cell of `key`, claimed on the way if it is new.  False: the probe run met neither the key nor a free entry (the table is full).
-// An entry's key changes once, from empty to its key, so a stale read of "empty" only costs the compare-and-swap that then returns the truth.
-// more(h, size): what a shaped map adds behind the same claimed entry (table_update_shape); table_update adds nothing.
-template <class More>
-__device__ __forceinline__ bool table_update_and(const MapTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2, More&& more) {
-    const u64 mask = ((u64)1 << t.log2) - 1;
-    u64 h = rule::mix(key) & mask;                                    // h <= mask: inside every array
-    for (u64 p = 0; p <= mask; p++) {
-        u64 k = __hip_atomic_load(&t.key[h], MAP_RLX_AGENT);
-        if (k == rule::kEmpty) {
-            u64 expected = rule::kEmpty;
-            k = __hip_atomic_compare_exchange_strong(&t.key[h], &expected, key, __ATOMIC_RELAXED, MAP_RLX_AGENT) ? key : expected;
-        }
-        if (k == key) {
-            const u64 size = mask + 1;
-            __hip_atomic_fetch_add(&t.count[h], dn, MAP_RLX_AGENT);
-            __hip_atomic_fetch_add(&t.sum[h], d0, MAP_RLX_AGENT);
-            __hip_atomic_fetch_add(&t.sum[size + h], d1, MAP_RLX_AGENT);
-            __hip_atomic_fetch_add(&t.sum[2 * size + h], d2, MAP_RLX_AGENT);
-            more(h, size);
-            return true;
-        }
-        h = (h + 1) & mask;
-    }
-    return false;
-}
-
-__device__ __forceinline__ bool table_update(const MapTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2) {
-    return table_update_and(t, key, dn, d0, d1, d2, [](u64, u64) {});
-}
-// The shaped form: nine more relaxed agent-scope adds, mom[w] += dm[w], behind the same claimed entry.
-__device__ __forceinline__ bool table_update_shape(const MapShapeTable& t, u64 key, u64 dn, u64 d0, u64 d1, u64 d2, const u64* dm) {
-    return table_update_and(t, key, dn, d0, d1, d2, [&](u64 h, u64 size) {
-#pragma unroll
-        for (int w = 0; w < srule::kWords; w++) __hip_atomic_fetch_add(&t.mom[w * size + h], dm[w], MAP_RLX_AGENT);
-    });
-}
+// MapTable / MapShapeTable, the device record's words (kCtr*) and table_update / table_update_shape: icet_map_table.h, shared with icet_map_snapshot.hip
 
 // m <= 4 rows of one column from row i (a multiple of 4): one 16-byte load where the column's address allows it and all four rows exist.
 __device__ __forceinline__ void load_rows(const float* __restrict__ col, int i, int m, float v[4]) {
@@ -636,11 +585,7 @@ template <class Rec> struct CallStage {
     hipError_t mark_read(hipStream_t st) { return fence.mark(st); }      // behind the call's last kernel
 };
 
-// THE CELLS SORTED BY KEY (map_sorted_cells): the selected (key, entry) pairs, their sorted copy, rocPRIM's scratch and what it holds.  cap: pairs.
-struct SortedCells {
-    u64* sel_key = nullptr; u64* key = nullptr; uint32_t* sel_idx = nullptr; uint32_t* idx = nullptr; void* tmp = nullptr; size_t tmp_bytes = 0; int64_t cap = 0;
-    BufferGroup mem;
-};
+// THE CELLS SORTED BY KEY (map_sorted_cells): SortedCells, icet_map_table.h.
 
 // A voxel map: the table, the device record of its totals and the pinned copy a stats call reads, the stages of an add and of a query, the sorted cells of an
 // extract and of the index.  Every array belongs to a group; the struct is a heap object that never moves.
@@ -674,6 +619,9 @@ struct icet_voxel_map {
     // the registration against the Gaussians (section 26; icet_map_register.hip, through map_register_view): generation counts what changes the table -- add, remove,
     // clear, enable_shape --, reg is that file's own state, freed with reg_free when the map goes
     uint64_t generation = 0; void* reg = nullptr; void (*reg_free)(void*) = nullptr;
+    // save, load and merge (section 27; icet_map_snapshot.hip, through map_snapshot_view): that file's own state, freed with snap_free when the map goes.  A load or
+    // a merge raises generation and sets ix_stale and dirty as an add does
+    void* snap = nullptr; void (*snap_free)(void*) = nullptr;
     BufferGroup table, record, xout, index, qcounts, evidence, evimages, evrecord, moments, xshape;
     MapShapeTable shape_table() const { MapShapeTable s; static_cast<MapTable&>(s) = t; s.mom = mom; return s; }
 };
@@ -764,7 +712,8 @@ static icet_status map_add(icet_voxel_map* m, int32_t n, const icet_dev_scan* sc
 // The cells of count >= minp, sorted by key, into sc.key / sc.idx.  n > 0 is the cells_out that map_count just returned for minp: it drained the stream, so nothing
 // reads the old buffers when they grow.  They grow to n + headroom pairs (a map that grows scan by scan does not allocate at every call), and also when this
 // sort asks for more scratch than they hold: the scratch is what rocPRIM asks for at the capacity, and a smaller sort is not promised to ask less.
-static icet_status map_sorted_cells(icet_voxel_map* m, SortedCells& sc, int64_t n, long long minp, int64_t headroom) {
+// `select` writes the n pairs into sc.sel_key / sc.sel_idx: k_map_cells<true> for the extract and the index (map_sorted_cells below), the snapshot's own pass for a save.
+static icet_status map_sort_selected(icet_voxel_map* m, SortedCells& sc, int64_t n, int64_t headroom, MapSelectFn select, void* arg) {
     hipStream_t st = m->ctx->stream;
     size_t tmp_bytes = 0;
     MAPCHK(m, rocprim::radix_sort_pairs(nullptr, tmp_bytes, sc.sel_key, sc.key, sc.sel_idx, sc.idx, (size_t)n, 0, 63, st));
@@ -783,10 +732,17 @@ static icet_status map_sorted_cells(icet_voxel_map* m, SortedCells& sc, int64_t 
         }));
         sc.tmp_bytes = need_tmp;
     }
-    k_map_cells<true><<<table_grid(m->t), kCellBlock, 0, st>>>(m->t, minp, m->ctr, sc.sel_key, sc.sel_idx, (u64)n);
-    MAPCHK(m, hipGetLastError());
+    MAPCHK(m, select(arg, sc, n, st));
     MAPCHK(m, rocprim::radix_sort_pairs(sc.tmp, tmp_bytes, sc.sel_key, sc.key, sc.sel_idx, sc.idx, (size_t)n, 0, 63, st));
     return ICET_OK;
+}
+static icet_status map_sorted_cells(icet_voxel_map* m, SortedCells& sc, int64_t n, long long minp, int64_t headroom) {
+    struct Arg { icet_voxel_map* m; long long minp; } a{m, minp};
+    return map_sort_selected(m, sc, n, headroom, [](void* arg, SortedCells& s, int64_t rows, hipStream_t st) {
+        const Arg& g = *static_cast<const Arg*>(arg);
+        k_map_cells<true><<<table_grid(g.m->t), kCellBlock, 0, st>>>(g.m->t, g.minp, g.m->ctr, s.sel_key, s.sel_idx, (u64)rows);
+        return hipGetLastError();
+    }, &a);
 }
 
 // shaped (extract_shape, section 25): the same rows, and behind k_map_centroid the columns of *shape from k_map_shape.
@@ -1045,6 +1001,13 @@ bool map_register_view(icet_voxel_map* m, MapRegisterView* v) {
     return true;
 }
 void map_set_error(icet_voxel_map* m, const char* why) { if (m) m->err = why; }
+bool map_snapshot_view(icet_voxel_map* m, MapSnapshotView* v) {
+    if (!m) return false;
+    *v = MapSnapshotView{m->ctx, m->params.cell, m->params.min_range, m->params.max_range, m->t.log2, m->t.key, m->t.count, m->t.sum, m->mom, m->ctr,
+                         &m->generation, &m->ix_stale, &m->dirty, &m->snap, &m->snap_free};
+    return true;
+}
+int map_sort_cells(icet_voxel_map* m, SortedCells& sc, int64_t n, MapSelectFn select, void* arg) { return map_sort_selected(m, sc, n, 0, select, arg); }
 }  // namespace icet
 
 extern "C" {
@@ -1109,6 +1072,7 @@ icet_status icet_voxel_map_destroy(icet_voxel_map* m) {
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);              // (an add or an extract may still read or write the table)
     if (m->reg && m->reg_free) m->reg_free(m->reg);
+    if (m->snap && m->snap_free) m->snap_free(m->snap);
     delete m;                                                // (every array belongs to a group, every event to a stage)
     return ICET_OK;
 }

@@ -50,6 +50,11 @@ bool writer_rewind(Writer& w, std::string& err) {
     return true;
 }
 
+bool writer_seek(Writer& w, uint64_t offset, std::string& err) {
+    if (fseeko(w.f, (off_t)offset, SEEK_SET) != 0) { err = "cannot seek in " + w.tmp + ": " + std::strerror(errno); return false; }
+    return true;
+}
+
 bool writer_commit(Writer& w, std::string& err) {
     const bool closed = std::fclose(w.f) == 0;
     w.f = nullptr;

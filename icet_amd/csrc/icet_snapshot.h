@@ -203,6 +203,7 @@ struct Writer { FILE* f = nullptr; std::string path, tmp; };
 bool writer_open(Writer& w, const char* path, std::string& err);
 bool writer_write(Writer& w, const void* p, uint64_t bytes, std::string& err);
 bool writer_rewind(Writer& w, std::string& err);
+bool writer_seek(Writer& w, uint64_t offset, std::string& err);      // the next write goes to `offset` from the file's start (a voxel map's columns, icet_map_snapshot.h)
 bool writer_commit(Writer& w, std::string& err);          // close and rename
 void writer_abort(Writer& w);                             // close and remove the temporary file
 

@@ -1079,6 +1079,51 @@ icet_status icet_voxel_map_register_posed_device(icet_voxel_map* map, int32_t n_
 icet_status icet_debug_voxel_map_register_terms(icet_voxel_map* map, const icet_dev_scan* scan, const float* pose, const icet_voxel_map_register_params* params,
                                                 icet_voxel_map_register_term* d_terms);
 
+/* --- the voxel map kept: save, load, merge (the file format and its validation: icet_amd/csrc/icet_map_snapshot.h) --------------------------
+ * Every per-cell word of a map is a 64-bit integer sum, so maps in ONE frame are additive cell by cell: adding the words of map B's cells to map A's gives, bit
+ * for bit, the map built from the scans of both, and subtracting them gives A back.  Save, load, merge and growing a table are that one operation -- the words
+ * of a set of cells into a table with sign +1 or -1 -- with the source in a file or in another table.
+ * THE FILE (little-endian, every part on a 16-byte boundary, reserved bytes and padding zero, every byte under a checksum): a 128-byte header -- magic
+ *   "ICETVXM1", version, the bit patterns of cell / min_range / max_range, the shaped flag, words per entry W (5: key, count, three sums; a shaped map 14: and
+ *   the nine moment words), the entry count n, the five running totals, the file's size, the payload's and the header's checksum -- and W columns of n u64
+ *   words.  Written: every claimed entry with a non-zero value word, by ascending key; a cell emptied by a remove is not written, a negative count or a zero
+ *   count beside non-zero sums is.  The file is a function of the map's contents alone: not of the table's size, the order of the adds, option "map_lds", the
+ *   call boundaries or the chunk size.
+ * SAVE runs behind what was enqueued, synchronises, and writes `path`.tmp, renamed when complete: a failed save leaves nothing at `path`.  The map is not changed
+ *   (its index, evidence and Gaussians stay current).  The payload moves in chunks of option "map_snapshot_chunk_entries" entries (icet_set_option on the
+ *   map's context; default and 0: 2^20; same bytes for every value).
+ * LOAD reads and validates the whole file on the host, holds it against the map, counts on the device how many of its keys the table does not hold yet, and
+ *   only then adds the words times `sign`.  The file's cell must equal the map's bit for bit; a shaped file into a plain map leaves the moment columns out; a
+ *   plain file into a shaped map is refused (the moments would no longer belong to the counts); the ranges are recorded and reported, not compared.  When
+ *   claimed entries + new keys exceed the table's size the load is refused with nothing touched (below that bound no insert can fail: a loaded cell is never
+ *   dropped).  The file's five totals are added to the map's, or with sign -1 ALL FIVE are subtracted, points_in included -- unlike a remove, which keeps
+ *   counting the rows it reads: a load or merge at -1 undoes the same load or merge at +1 exactly, totals too.  Afterwards the map is as after an add: index,
+ *   evidence and Gaussians are stale, and icet_voxel_map_enable_shape is refused until the next clear.  Synchronises.
+ * MERGE is load with the source in device memory: dst and src on the same context, dst != src, the same cell, shape and capacity rules, the same effects on
+ *   dst; src is only read.  Growing a full table (ICET_VOXEL_MAP_TABLE_FULL) is a merge into a new, larger map.  Asynchronous behind its capacity check.
+ * Refusals (ICET_ERR_BAD_ARG, the reason in icet_voxel_map_last_error, nothing touched): a NULL argument, a path that cannot be opened, a file the validation
+ *   refuses, a cell mismatch, the shape rule, the capacity bound, sign not +1 / -1, two contexts in a merge.  A save whose file cannot be written to the
+ *   end -- a full disk, a failed seek, write, close or rename -- answers ICET_ERR_BAD_ARG as well (the status set has nothing nearer): the message names
+ *   the failed step and the system's reason, which is how a caller tells it from a bad path; the temporary file is removed.  No CPU fall-back.
+ * The sorted cells of a save and the staging of a save or a load (one device and two pinned buffers of min(chunk, entries) x W words) stay with the map and
+ *   grow on demand; icet_voxel_map_destroy frees them. */
+/* (a struct tag without a typedef: the call below has the same name) */
+struct icet_voxel_map_snapshot_info {
+    float cell, min_range, max_range;         /* of the map that was saved */
+    int32_t shaped;                           /* 1: the file carries the nine moment words */
+    int32_t words_per_entry;                  /* 5 or 14 */
+    int32_t reserved0;
+    int64_t entries;
+    int64_t points_in, points_kept, points_nonfinite, points_outside, points_dropped;
+    int64_t file_bytes;
+    uint64_t payload_checksum;
+    int32_t reserved[2];
+};                                /* 96 bytes */
+icet_status icet_voxel_map_save(icet_voxel_map* map, const char* path);
+icet_status icet_voxel_map_load(icet_voxel_map* map, const char* path, int32_t sign);
+icet_status icet_voxel_map_snapshot_info(const char* path, struct icet_voxel_map_snapshot_info* out);
+icet_status icet_voxel_map_merge_device(icet_voxel_map* dst, icet_voxel_map* src, int32_t sign);
+
 /* --- deskew: undo a sweep's motion in many scans, in one call ---------------------------------------------------------------------------
  * A spinning lidar takes 50 - 100 ms per sweep; the rows of one scan are taken from a moving sensor.  A deskewer carries every row into the sensor frame at ONE
  * instant of the sweep, given the sweep's motion as a twist and a time (or a column index) per row.  It borrows a context like a store or a map (destroy it
@@ -1159,7 +1204,7 @@ icet_status icet_debug_deskew_rows(const icet_deskew_scan* motion, int64_t n, co
  * 1 the block of a pair that finishes its share of an iteration's point pass last runs the pair's solve in the same launch -- 7 launches less per solve, same
  * bits; default 0: measured no faster on MI355X, where a device-scope fence is an L2 write-back), "batch_parts" (0 = automatic), "batch_stage" (0..4), "force_exact"
  * (every scan-2 point through the literal classification), "library_sort" (0 only: the library has ONE sort, the
- * hand-written rank sort, and no build flag brings another; any other value answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents), "map_query_prune" (icet_voxel_map_query_*: 1, the default, a block skips the queries whose run of x cells misses its chunk; 0 every cell is tested for every query; same bits), "map_evidence_prune" (icet_voxel_map_evidence_*: 1, the default, a block skips the scans whose run of x cells misses its chunk; same bits), "map_evidence_batch" (scans per batch of range images: 0, the default, as many as fit 64 MiB, else 1 .. 256; same bits), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
+ * hand-written rank sort, and no build flag brings another; any other value answers ICET_ERR_UNSUPPORTED), "guard_scale" (>= 1), "lut_polar_quantile" (0..1), "snapshot_chunk_bytes" (payload bytes per chunk of icet_keyframe_store_save / _load; 0 = the default, 64 MiB), "pg_solver" (the pose-graph optimiser's linear solve: 0 conjugate gradients, the default; 1 the direct solve; 2 auto; any other value ICET_ERR_BAD_ARG), "map_lds" (icet_voxel_map_add_*: 1, the default, a block reduces its rows in LDS before it touches the table; 0 one global update per row; same contents), "map_query_prune" (icet_voxel_map_query_*: 1, the default, a block skips the queries whose run of x cells misses its chunk; 0 every cell is tested for every query; same bits), "map_evidence_prune" (icet_voxel_map_evidence_*: 1, the default, a block skips the scans whose run of x cells misses its chunk; same bits), "map_evidence_batch" (scans per batch of range images: 0, the default, as many as fit 64 MiB, else 1 .. 256; same bits), "map_snapshot_chunk_entries" (icet_voxel_map_save / _load: entries per chunk of the payload, 0 .. 2^30; 0, the default: 2^20; same bytes), "gn_cond_bound" (0 .. 1e6, default 2.5e5 -- a factor 4 below checkCondition's cutoff, because a float Cholesky inverse knows its own norm to a few per cent only at such condition numbers: an H^T W H whose Frobenius bound on
  * the condition number |A|_F |A^-1|_F exceeds it is inverted by the literal restatement of the reference's statements -- column-pivoted QR
  * pseudo-inverse, eigenvectors, pruning -- instead of a Cholesky factorisation; 0 = always literal.  Not a launch-shape knob: between the two
  * routes cov / dx differ by rounding times the condition number).  Unknown name or value
