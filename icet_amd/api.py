@@ -151,6 +151,7 @@ class MapShape(C.Structure):
 
 VOXEL_MAP_REG_CONVERGED, VOXEL_MAP_REG_ITERATION_CAP, VOXEL_MAP_REG_STALLED, VOXEL_MAP_REG_NO_OVERLAP, VOXEL_MAP_REG_BAD_POSE = 0, 1, 2, 3, 4
 VOXEL_MAP_REG_MAX_ITERS = 64
+VOXEL_MAP_REG_NEIGHBOURS_7, VOXEL_MAP_REG_NEIGHBOURS_27 = 2, 4      # MapRegisterParams.flags: score a row against the best of 7 or 27 cells (0: its own cell)
 VOXEL_MAP_REG_CHUNK = 2048        # rows per block of the row pass (the sizes at which it takes another path)
 
 
@@ -180,12 +181,17 @@ MAP_REGISTER_DEFAULTS = dict(min_range=0.0, max_range=0.0, sigma_min=0.02, scale
 
 
 def map_register_params(**kw):
-    """A MapRegisterParams from keywords over MAP_REGISTER_DEFAULTS (the values a NULL params gives)."""
+    """A MapRegisterParams from keywords over MAP_REGISTER_DEFAULTS (the values a NULL params gives).  ``neighbours`` = 1 (default), 7 or 27: the cells a row is
+    scored against the best of, as the bit of ``flags`` that names them (``flags=`` itself still passes through; both: the bits are joined)."""
     d = dict(MAP_REGISTER_DEFAULTS)
-    extra = set(kw) - set(d) - {"flags"}
+    extra = set(kw) - set(d) - {"flags", "neighbours"}
     if extra:
         raise TypeError("unknown registration parameter(s): " + ", ".join(sorted(extra)))
     d.update(kw)
+    nb = d.pop("neighbours", 1)
+    if nb not in (1, 7, 27) or isinstance(nb, bool):
+        raise ValueError("neighbours must be 1, 7 or 27")
+    d["flags"] = int(d.get("flags", 0)) | {1: 0, 7: VOXEL_MAP_REG_NEIGHBOURS_7, 27: VOXEL_MAP_REG_NEIGHBOURS_27}[nb]
     return MapRegisterParams(float(d["min_range"]), float(d["max_range"]), float(d["sigma_min"]), float(d["scale"]), float(d["tol_t"]), float(d["tol_r"]),
                              float(d["lambda0"]), int(d["min_points"]), int(d["min_matched"]), int(d["max_iters"]), int(d.get("flags", 0)))
 

@@ -204,6 +204,73 @@ ICET_CLOSURE_HD inline void match_terms(const Consts& k, const Gauss& G, const d
     H[20] = om * RR[2][2];
 }
 
+// ---- the neighbourhood of a row ---------------------------------------------------------------------------------------------------------------------------------
+// A row is scored against ONE cell of its neighbourhood: the usable cell with the smallest s = d . W d, the earlier in the order on a tie.  N1: the row's own cell
+// (the code above and nothing else).  N7: own, -x, +x, -y, +y, -z, +z.  N27: own, then the other 26 offsets (dx, dy, dz), dx slowest, each over -1, 0, 1.  A
+// neighbour whose cell index leaves the grid is skipped; a row outside the grid has no neighbourhood.  rho is at most c and a miss exactly c whatever the
+// neighbourhood, row by row rho(N27) <= rho(N7) <= rho(N1), and the cost is continuous across a face whenever the winner is among the cells on both sides.
+constexpr int32_t kFlagNeighbours7 = 2, kFlagNeighbours27 = 4;      // params.flags (include/icet_hip.h ICET_VOXEL_MAP_REG_NEIGHBOURS_*)
+constexpr double kInf = __builtin_huge_val();                       // +infinity
+
+// The cells of the neighbourhood that `flags` names: 1, 7 or 27; 0 for flags that are refused (both bits, or any other bit).
+inline int neighbours_of(int32_t flags) {
+    return flags == 0 ? 1 : flags == kFlagNeighbours7 ? 7 : flags == kFlagNeighbours27 ? 27 : 0;
+}
+// Place j (0 .. K - 1) of the neighbourhood of K = 7 or 27 cells: the offset in cells.  Place 0 is the row's own cell.
+ICET_CLOSURE_HD inline void neighbour_offset(int K, int j, int32_t d[3]) {
+    d[0] = 0; d[1] = 0; d[2] = 0;
+    if (j == 0) return;
+    if (K == 7) { d[(j - 1) >> 1] = ((j - 1) & 1) ? 1 : -1; return; }
+    const int i = j <= 13 ? j - 1 : j;                                // the place among all 27 offsets, the centre (13) taken out
+    d[0] = i / 9 - 1; d[1] = (i / 3) % 3 - 1; d[2] = i % 3 - 1;
+}
+// The key of the cell at place j around the cell of `own` (a key, not kEmpty).  False: the cell is outside the grid (a key field outside 1 .. 2^21 - 1).
+ICET_CLOSURE_HD inline bool neighbour_key(int K, int j, uint64_t own, uint64_t& key) {
+    int32_t c[3], d[3];
+    mrule::key_cells(own, c);
+    neighbour_offset(K, j, d);
+    bool in = true;
+    for (int a = 0; a < 3; a++) { c[a] += d[a]; in = in && c[a] > -mrule::kCellLimit && c[a] < mrule::kCellLimit; }
+    key = in ? mrule::make_key(c[0], c[1], c[2]) : mrule::kEmpty;
+    return in;
+}
+// s = d . W d of the world point w against G, in match_terms' order of operations: what the selection compares.
+ICET_CLOSURE_HD inline double match_s(const Gauss& G, const double w[3]) {
+    ICET_CLOSURE_NO_CONTRACT
+    const double* W = G.W;
+    double d[3];
+    for (int a = 0; a < 3; a++) d[a] = w[a] - G.mu[a];
+    const double m00 = W[0] * d[0], m01 = W[1] * d[1], m02 = W[2] * d[2];
+    const double m10 = W[1] * d[0], m11 = W[3] * d[1], m12 = W[4] * d[2];
+    const double m20 = W[2] * d[0], m21 = W[4] * d[1], m22 = W[5] * d[2];
+    const double s0 = m00 + m01, s1 = m10 + m11, s2 = m20 + m21;
+    const double a[3] = {s0 + m02, s1 + m12, s2 + m22};
+    const double q0 = d[0] * a[0], q1 = d[1] * a[1], q2 = d[2] * a[2];
+    const double q01 = q0 + q1;
+    return q01 + q2;
+}
+// The running selection of one row: start() before the first cell, offer() per usable cell in the order of the places.  A cell wins iff its s is below the best so
+// far: a tie stays with the earlier place, and a NaN or infinite s never wins.  place < 0: no winner, the row is a miss.
+struct Best { double s; int32_t place; };
+ICET_CLOSURE_HD inline void best_start(Best& b) { b.s = kInf; b.place = -1; }
+ICET_CLOSURE_HD inline bool best_offer(Best& b, int place, double s) {
+    if (!(s < b.s)) return false;
+    b.s = s; b.place = place;
+    return true;
+}
+// The same selection with the cells offered in ANY order: the winner is the least (s, place), which is what offering them in the order of the places gives (an
+// infinite s equals the start's and no place is below -1, a NaN compares false: neither wins here either).  The 27-cell row pass walks x slices with it.
+ICET_CLOSURE_HD inline bool best_offer_any(Best& b, int place, double s) {
+    if (!(s < b.s || (s == b.s && place < b.place))) return false;
+    b.s = s; b.place = place;
+    return true;
+}
+// The place in N27's order of the offset (dx, dy, dz), each -1, 0 or 1.
+ICET_CLOSURE_HD inline int place27(int dx, int dy, int dz) {
+    const int i = (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1);
+    return i == 13 ? 0 : i < 13 ? i + 1 : i;
+}
+
 // A running sum of rows: the 28 doubles and the two counts.
 struct Acc { double v[kSums]; int32_t scored, matched; };
 ICET_CLOSURE_HD inline void acc_zero(Acc& a) { for (int j = 0; j < kSums; j++) a.v[j] = 0.0; a.scored = 0; a.matched = 0; }

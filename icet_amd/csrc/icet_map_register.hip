@@ -6,6 +6,9 @@
 //     k_mapreg_rows    one block per chunk of kChunkRows rows of one query (blockIdx -> (query, chunk), k_map_add's scheme); a block of a terminal query exits at
 //                      once.  16-byte loads of 4 consecutive rows per lane; a read-only probe bounded by the table size; 28 double accumulators and two counts per
 //                      thread over its rows in row order, then a fixed wave64 butterfly, then the block's waves in order through LDS: one partial per (query, chunk)
+//     k_mapreg_rows_nb the same pass under a neighbourhood of K = 7 or 27 cells (params.flags), K a compile-time constant: per row the K keys, their first probes
+//                      issued together, each candidate's s from a record that is dropped at once, the winner's slot and s alone kept through the selection and
+//                      its record read again for the terms.  The same loads, pose staging, sums and partials as k_mapreg_rows, which flags = 0 still launches
 //     k_mapreg_step    one block per query: lane j sums component j of the query's partials in ascending chunk order, thread 0 runs the rule's state machine and
 //                      writes the query's state and record
 // A call enqueues the Gaussians if stale and 1 + max_iters x (rows, step): no atomics, no fence, no block waits for another, no host round trip.
@@ -43,6 +46,7 @@ static_assert(sizeof(rr::Record) == sizeof(icet_voxel_map_registration) && sizeo
               offsetof(rr::Record, g) == offsetof(icet_voxel_map_registration, g) && offsetof(rr::Record, cost) == offsetof(icet_voxel_map_registration, cost) &&
               offsetof(rr::Record, rows_scored) == offsetof(icet_voxel_map_registration, rows_scored) && offsetof(rr::Record, status) == offsetof(icet_voxel_map_registration, status),
               "the rule's record is the header's, word for word");
+static_assert(rr::kFlagNeighbours7 == ICET_VOXEL_MAP_REG_NEIGHBOURS_7 && rr::kFlagNeighbours27 == ICET_VOXEL_MAP_REG_NEIGHBOURS_27, "the flags the header names");
 static_assert(sizeof(rr::Gauss) == 80, "mu[3] | W[6] | n");
 static_assert(sizeof(icet_voxel_map_register_term) == 256 && sizeof(icet_voxel_map_register_params) == 72, "the sizes the header names");
 
@@ -182,6 +186,206 @@ __global__ __launch_bounds__(kRegBlock) void k_mapreg_rows(const RegScan* __rest
     }
 }
 
+// ---- the row pass under a neighbourhood ------------------------------------------------------------------------------------------------------------------------
+// k_mapreg_rows' own steps as functions, for k_mapreg_rows_nb: k_mapreg_rows keeps its text, and with it its machine code (scripts/isa_compare.py), word for word.
+// The query of this block: the last one whose first block is not behind it (a query without rows has no block).
+__device__ __forceinline__ int query_of_block(const RegScan* __restrict__ scans, int n_q) {
+    int lo = 0, hi = n_q - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (scans[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// The pose of query q in this pass, through sP (12 doubles of LDS) into every thread: pass 0 reads the start pose, a later pass the trial pose of the state.
+__device__ __forceinline__ void stage_pose(double* sP, const float* __restrict__ poses, int pass, const rr::State* __restrict__ state, int q, rr::Pose& P) {
+    if (threadIdx.x < 12) {
+        const int j = threadIdx.x;
+        if (pass == 0) sP[j] = (double)(j < 9 ? poses[16 * (size_t)q + 4 * (j / 3) + j % 3] : poses[16 * (size_t)q + 4 * (j - 9) + 3]);
+        else sP[j] = j < 9 ? state[q].trial.R[j] : state[q].trial.t[j - 9];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 9; j++) P.R[j] = sP[j];
+#pragma unroll
+    for (int a = 0; a < 3; a++) P.t[a] = sP[9 + a];
+}
+
+// A block's partial from its threads' sums: the thread, then a fixed butterfly over the wave (every lane ends with the same bits), then the waves in order.
+__device__ __forceinline__ void reduce_block(const rr::Acc& acc, double (*sv)[rr::kSums], int32_t (*sn)[2], Partial* out) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int j = 0; j < rr::kSums; j++) {
+        double v = acc.v[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
+        if (lane == 0) sv[wave][j] = v;
+    }
+    int32_t ns = acc.scored, nm = acc.matched;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { ns += __shfl_xor(ns, off, 64); nm += __shfl_xor(nm, off, 64); }
+    if (lane == 0) { sn[wave][0] = ns; sn[wave][1] = nm; }
+    __syncthreads();
+    if (threadIdx.x < rr::kSums) {
+        double s = sv[0][threadIdx.x];
+        for (int w = 1; w < kRegWaves; w++) s = s + sv[w][threadIdx.x];
+        out->v[threadIdx.x] = s;
+    } else if (threadIdx.x < rr::kSums + 2) {
+        const int c = threadIdx.x - rr::kSums;
+        int32_t s = 0;
+        for (int w = 0; w < kRegWaves; w++) s += sn[w][c];
+        if (c == 0) out->scored = s; else out->matched = s;
+    }
+}
+
+// probe() with the first key already loaded, entries as 32-bit words (the table has at most 2^31 of them: map_register): k = t.key[h], h = mix(key) & mask.
+// The same answer as probe(t, key), at most `size` keys compared.
+__device__ __forceinline__ int32_t probe_from(const RegTable& t, u64 key, uint32_t h, u64 k) {
+    const uint32_t mask = (uint32_t)(((u64)1 << t.log2) - 1);
+    for (uint32_t p = 0; p <= mask; p++) {
+        if (k == key) return (int32_t)h;
+        if (k == mrule::kEmpty) return -1;
+        h = (h + 1) & mask;                                           // h <= mask: inside every array
+        k = t.key[h];
+        if (p == mask) break;                                         // (mask may be all ones: no p + 1 past it)
+    }
+    return -1;
+}
+
+// The cell of the neighbourhood of K cells around `own` that the world point w is scored against (icet_map_register.h: the smallest s, the earlier place on a
+// tie): its entry, or -1, and its place.  A batch of cells at a time: their first probes together (independent 8-byte reads that overlap), then the entries,
+// then the records kGroup at a time -- each read whole from an entry inside the table (entry 0 for a cell that has none, its s not offered: measured faster than
+// a load under the lane's own condition) and dropped once its s is known.  Between batches a thread keeps the winner's entry, place and s and nothing else.
+constexpr int kGroup = 3;
+
+// One batch: cell j of the kBatch has the key key_of(j) (kEmpty: outside the grid, read but never probed) and the place place_of(j).  kOrdered: the cells come in
+// the order of the places and the plain comparison selects (measured: the (s, place) comparison where it is not needed costs the 7-cell pass 15 %).
+template <int kBatch, bool kOrdered, class KeyOf, class PlaceOf>
+__device__ __forceinline__ void select_batch(const RegTable& t, const rr::Gauss* __restrict__ gauss, const double w[3], KeyOf key_of, PlaceOf place_of,
+                                             rr::Best& best, int32_t& slot) {
+    const uint32_t mask = (uint32_t)(((u64)1 << t.log2) - 1);
+    uint32_t h[kBatch];
+    u64 k0[kBatch];
+    int32_t e[kBatch];
+#pragma unroll
+    for (int j = 0; j < kBatch; j++) {
+        h[j] = (uint32_t)mrule::mix(key_of(j)) & mask;                // h <= mask: inside every array
+        k0[j] = t.key[h[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < kBatch; j++) {
+        const u64 key = key_of(j);
+        e[j] = key != mrule::kEmpty ? probe_from(t, key, h[j], k0[j]) : -1;
+    }
+#pragma unroll
+    for (int g0 = 0; g0 < kBatch; g0 += kGroup) {
+        double s[kGroup]; bool ok[kGroup];
+#pragma unroll
+        for (int j = 0; j < kGroup; j++) {
+            if (g0 + j >= kBatch) { ok[j] = false; s[j] = 0.0; continue; }
+            const rr::Gauss G = gauss[e[g0 + j] >= 0 ? e[g0 + j] : 0];          // an entry's index, or entry 0: inside the records
+            ok[j] = e[g0 + j] >= 0 && G.n > 0;
+            s[j] = rr::match_s(G, w);
+        }
+#pragma unroll
+        for (int j = 0; j < kGroup; j++)
+            if (g0 + j < kBatch && ok[j] && (kOrdered ? rr::best_offer(best, place_of(g0 + j), s[j]) : rr::best_offer_any(best, place_of(g0 + j), s[j]))) slot = e[g0 + j];
+        __builtin_amdgcn_sched_barrier(0);                            // the next group's records are not loaded before these are dropped
+    }
+}
+
+template <int K>
+__device__ __forceinline__ int32_t select_cell(const RegTable& t, const rr::Gauss* __restrict__ gauss, uint64_t own, const double w[3], int& place);
+
+// 7 cells: one batch, in the order of the places, every offset a compile-time constant.
+template <>
+__device__ __forceinline__ int32_t select_cell<7>(const RegTable& t, const rr::Gauss* __restrict__ gauss, uint64_t own, const double w[3], int& place) {
+    rr::Best best;
+    rr::best_start(best);
+    int32_t slot = -1;
+    select_batch<7, true>(t, gauss, w, [&](int j) { uint64_t key; rr::neighbour_key(7, j, own, key); return (u64)key; }, [](int j) { return j; }, best, slot);
+    place = best.place;
+    return slot;
+}
+
+// 27 cells: one batch per x slice (a rolled loop: unrolled, the three batches' loads are hoisted together and the pass spills), the nine (dy, dz) offsets of a
+// slice compile-time constants.  The cells are offered out of the order of the places -- the own cell in the middle of the second slice -- which the (s, place)
+// comparison of best_offer_any makes the same selection.
+template <>
+__device__ __forceinline__ int32_t select_cell<27>(const RegTable& t, const rr::Gauss* __restrict__ gauss, uint64_t own, const double w[3], int& place) {
+    rr::Best best;
+    rr::best_start(best);
+    int32_t slot = -1;
+    int32_t c[3];
+    mrule::key_cells(own, c);
+#pragma nounroll
+    for (int dx = -1; dx <= 1; dx++) {
+        const int32_t cx = c[0] + dx;
+        const bool inx = cx > -mrule::kCellLimit && cx < mrule::kCellLimit;
+        auto key_of = [&](int j) {
+            const int32_t cy = c[1] + (j / 3 - 1), cz = c[2] + (j % 3 - 1);
+            const bool in = inx && cy > -mrule::kCellLimit && cy < mrule::kCellLimit && cz > -mrule::kCellLimit && cz < mrule::kCellLimit;
+            return in ? (u64)mrule::make_key(cx, cy, cz) : (u64)mrule::kEmpty;
+        };
+        select_batch<9, false>(t, gauss, w, key_of, [&](int j) { return rr::place27(dx, j / 3 - 1, j % 3 - 1); }, best, slot);
+    }
+    place = best.place;
+    return slot;
+}
+
+// k_mapreg_rows under a neighbourhood of K cells: the same launch shape, loads, pose, sums and partial; a record's `matched` is 1 + the winner's place.
+template <int K, bool kTerms>
+__global__ __launch_bounds__(kRegBlock, 2) void k_mapreg_rows_nb(const RegScan* __restrict__ scans, int n_q, const float* __restrict__ poses, int pass,
+                                                                 const rr::State* __restrict__ state, rr::Consts kc, RegTable t, const rr::Gauss* __restrict__ gauss,
+                                                                 Partial* __restrict__ part, icet_voxel_map_register_term* __restrict__ terms) {
+    __shared__ double sv[kRegWaves][rr::kSums];
+    __shared__ int32_t sn[kRegWaves][2];
+    __shared__ double sP[12];
+    const int lo = query_of_block(scans, n_q);
+    const RegScan sc = scans[lo];
+    const int row0 = ((int)blockIdx.x - sc.block0) * kRowsPerBlock;
+    if (row0 < 0 || row0 >= sc.n) return;                             // (the same for every thread of the block)
+    if (pass > 0 && state[lo].status != rr::kIterationCap) return;    // (the same too) a terminal query is frozen
+    const int end = min(sc.n, row0 + kRowsPerBlock);
+    rr::Pose P;
+    stage_pose(sP, poses, pass, state, lo, P);
+    const float* cx = sc.ptr; const float* cy = cx + sc.ld; const float* cz = cx + 2 * (size_t)sc.ld;
+    rr::Acc acc;
+    rr::acc_zero(acc);
+    for (int i = row0 + 4 * (int)threadIdx.x; i < end; i += 4 * kRegBlock) {
+        const int m = min(4, end - i);
+        float x[4], y[4], z[4];
+        load_rows(cx, i, m, x); load_rows(cy, i, m, y); load_rows(cz, i, m, z);
+        for (int r = 0; r < m; r++) {
+            int cls = rr::row_class(kc, x[r], y[r], z[r]);
+            uint64_t key = mrule::kEmpty;
+            int place = -1;
+            rr::Terms tm;
+            if (cls == mrule::kRowKept) {
+                double rv[3], w[3];
+                const bool in = rr::row_world(kc, P, x[r], y[r], z[r], rv, w, key);
+                if (!in) cls = mrule::kRowOutside;
+                const int32_t e = in ? select_cell<K>(t, gauss, key, w, place) : -1;
+                if (e >= 0) {
+                    const rr::Gauss G = gauss[e];                     // the winner's record again (e < size: an entry's index)
+                    rr::match_terms(kc, G, rv, w, tm);
+                } else {
+                    rr::miss_terms(kc, tm);
+                }
+                rr::acc_row(acc, tm, e >= 0);
+            }
+            if (kTerms) {
+                icet_voxel_map_register_term o;                       // i + r < end <= sc.n: inside the caller's records
+                const bool scored = cls == mrule::kRowKept || cls == mrule::kRowOutside;
+                o.key = key; o.cls = cls; o.matched = place + 1;
+                o.s = scored ? tm.s : 0.0; o.omega = scored ? tm.omega : 0.0; o.rho = scored ? tm.rho : 0.0;
+                for (int j = 0; j < 6; j++) o.g[j] = scored ? tm.v[1 + j] : 0.0;
+                for (int j = 0; j < 21; j++) o.H[j] = scored ? tm.v[7 + j] : 0.0;
+                terms[i + r] = o;
+            }
+        }
+    }
+    reduce_block(acc, sv, sn, part + blockIdx.x);
+}
+
 __global__ __launch_bounds__(kStepBlock) void k_mapreg_step(const RegScan* __restrict__ scans, const float* __restrict__ poses, int pass, rr::Consts kc,
                                                             const Partial* __restrict__ part, rr::State* __restrict__ state, rr::Record* __restrict__ recs) {
     __shared__ rr::Acc tot;
@@ -232,6 +436,15 @@ icet_status reg_refuse(icet_voxel_map* m, const std::string& why) { map_set_erro
 
 template <class T> bool aligned_to(const T* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
+// The row pass of the call's neighbourhood: nb = 1 is k_mapreg_rows, the centre-only pass, unchanged.
+void launch_rows(int nb, bool terms, unsigned blocks, hipStream_t st, const RegScan* scans, int n_q, const float* poses, int pass, const rr::State* state, const rr::Consts& kc,
+                 const RegTable& t, const rr::Gauss* gauss, Partial* part, icet_voxel_map_register_term* d_terms) {
+    auto k = nb == 27 ? (terms ? k_mapreg_rows_nb<27, true> : k_mapreg_rows_nb<27, false>)
+           : nb == 7 ? (terms ? k_mapreg_rows_nb<7, true> : k_mapreg_rows_nb<7, false>)
+                     : (terms ? k_mapreg_rows<true> : k_mapreg_rows<false>);
+    k<<<blocks, kRegBlock, 0, st>>>(scans, n_q, poses, pass, state, kc, t, gauss, part, d_terms);
+}
+
 // terms: the debug form -- one query, the row pass of the start pose with a record per row, no step.
 icet_status map_register(icet_voxel_map* m, int32_t n_q, const icet_dev_scan* scans, const float* poses, bool poses_on_device, const icet_voxel_map_register_params* params,
                          icet_voxel_map_registration* d_records, icet_voxel_map_register_term* d_terms, bool terms, const char* call) {
@@ -245,10 +458,13 @@ icet_status map_register(icet_voxel_map* m, int32_t n_q, const icet_dev_scan* sc
     if (params) p = *params;
     else { std::memset(&p, 0, sizeof(p)); p.sigma_min = 0.02; p.scale = 11.3449; p.tol_t = 1e-4; p.tol_r = 1e-5; p.lambda0 = 1e-3; p.min_points = 5; p.min_matched = 50; p.max_iters = 20; }
     if (!v.mom) return reg_refuse(m, who + ": the map has no shape (icet_voxel_map_enable_shape on an empty map)");
+    if (v.log2 > 31) return reg_refuse(m, who + ": the table is too large (the row pass keeps an entry in 32 bits)");
     if (n_q < 1 || n_q > rr::kMaxQueries) return reg_refuse(m, who + ": n_q must lie in 1 .. 256");
     if (!scans || !poses || (terms ? !d_terms : !d_records)) return reg_refuse(m, who + ": bad argument (a NULL array)");
-    if (!rr::params_ok(p.min_range, p.max_range, p.sigma_min, p.scale, p.tol_t, p.tol_r, p.lambda0, p.max_iters, p.flags) || p.reserved[0] || p.reserved[1])
-        return reg_refuse(m, who + ": sigma_min, scale and lambda0 must be finite and > 0, the tolerances finite and >= 0, the ranges finite, max_iters 0 .. 64, flags and the reserved words 0");
+    const int nb = rr::neighbours_of(p.flags);                        // 1, 7 or 27 cells per row; 0: flags that name no neighbourhood
+    if (!rr::params_ok(p.min_range, p.max_range, p.sigma_min, p.scale, p.tol_t, p.tol_r, p.lambda0, p.max_iters, 0) || nb == 0 || p.reserved[0] || p.reserved[1])
+        return reg_refuse(m, who + ": sigma_min, scale and lambda0 must be finite and > 0, the tolerances finite and >= 0, the ranges finite, max_iters 0 .. 64, flags 0 or ONE of "
+                                   "ICET_VOXEL_MAP_REG_NEIGHBOURS_7 / _27, the reserved words 0");
     if ((poses_on_device && !aligned_to(poses, 4)) || !aligned_to(d_records, 8) || !aligned_to(d_terms, 8))
         return reg_refuse(m, who + ": a device pointer is not aligned to its element");
     int64_t blocks = 0;
@@ -309,14 +525,14 @@ icet_status map_register(icet_voxel_map* m, int32_t n_q, const icet_dev_scan* sc
     }
     if (terms) {
         if (blocks > 0) {
-            k_mapreg_rows<true><<<(unsigned)blocks, kRegBlock, 0, st>>>(s->d_rec, n_q, dp, 0, s->state, kc, t, s->gauss, s->part, d_terms);
+            launch_rows(nb, true, (unsigned)blocks, st, s->d_rec, n_q, dp, 0, s->state, kc, t, s->gauss, s->part, d_terms);
             REGCHK(m, hipGetLastError());
         }
     } else {
         rr::Record* recs = reinterpret_cast<rr::Record*>(d_records);
         for (int pass = 0; pass <= p.max_iters; pass++) {
             if (blocks > 0) {
-                k_mapreg_rows<false><<<(unsigned)blocks, kRegBlock, 0, st>>>(s->d_rec, n_q, dp, pass, s->state, kc, t, s->gauss, s->part, nullptr);
+                launch_rows(nb, false, (unsigned)blocks, st, s->d_rec, n_q, dp, pass, s->state, kc, t, s->gauss, s->part, nullptr);
                 REGCHK(m, hipGetLastError());
             }
             k_mapreg_step<<<(unsigned)n_q, kStepBlock, 0, st>>>(s->d_rec, dp, pass, kc, s->part, s->state, recs);

@@ -1027,19 +1027,29 @@ icet_status icet_voxel_map_extract_shape(icet_voxel_map* map, int32_t min_points
  *   (the upper triangle by rows, 21 doubles).  RETRACTION: R <- E(om) R, t <- t + rho_t, E the rotation of icet_pose_from_twist((0, om), 1), |om| <= 1.
  *   LOOP: Levenberg-Marquardt, (info + lambda diag(info)) delta = -g by a 6 x 6 Cholesky; a trial is accepted iff its cost is finite and below the current one
  *   (lambda / 10, not below 1e-9), else lambda x 10 (above 1e9: STALLED); CONVERGED when an accepted step has |rho_t| <= tol_t and |om| <= tol_r.
+ *   NEIGHBOURHOODS (flags): 0 scores a row against its own cell, as above.  ICET_VOXEL_MAP_REG_NEIGHBOURS_7 looks at own, -x, +x, -y, +y, -z, +z in this order,
+ *   ICET_VOXEL_MAP_REG_NEIGHBOURS_27 at own, then the other 26 offsets (dx, dy, dz), dx slowest, each over -1, 0, 1; a neighbour outside the grid is skipped and a
+ *   row outside the grid stays a miss.  Every usable cell among them gives s = d . W d as above; the row is scored against the cell with the SMALLEST s (a cell
+ *   wins iff its s is below the best so far, which starts at +infinity: a tie stays with the earlier cell, a NaN or infinite s never wins) and takes that cell's
+ *   rho, omega, g and info terms; without a winner it is a miss.  A row still costs at most `scale`, row by row rho(27) <= rho(7) <= rho(own), and the cost is
+ *   continuous where a row crosses a face between two usable cells.  Everything else -- the sums, the loop, the statuses, the Gaussians and when they are stale --
+ *   is the same; flags = 0 runs the same code and gives the same bits as before the neighbourhoods existed.
  * max_iters = 0 scores the given poses.  Asynchronous on the context's stream: a fixed number of launches (the Gaussians if they are stale, then 1 + max_iters
  * passes of two kernels), no host round trip.  The Gaussians are rebuilt after add, remove, clear and enable_shape and when sigma_min or min_points change.
  * Queries may share a scan descriptor (several start poses of one scan).  Sums in a fixed order: the same call gives the same bits, and a query's bits depend on
  * neither its place in the call nor its neighbours.
  * Refusals (ICET_ERR_BAD_ARG, the reason in icet_voxel_map_last_error, nothing touched): a map without shape, a NULL map or array, n_q outside 1 ..
  *   ICET_VOXEL_MAP_MAX_QUERIES, a bad descriptor, sigma_min, scale or lambda0 not finite and > 0, max_iters outside 0 .. 64, negative tolerances, non-finite
- *   ranges, nonzero flags or reserved words, d_records or d_poses misaligned.  No CPU fall-back. */
+ *   ranges, flags other than 0 or ONE of ICET_VOXEL_MAP_REG_NEIGHBOURS_7 / _27 (both bits, or any other bit), nonzero reserved words, d_records or d_poses
+ *   misaligned.  No CPU fall-back. */
 #define ICET_VOXEL_MAP_REG_CONVERGED 0
 #define ICET_VOXEL_MAP_REG_ITERATION_CAP 1         /* still running after pass max_iters (every scored pose of max_iters = 0) */
 #define ICET_VOXEL_MAP_REG_STALLED 2
 #define ICET_VOXEL_MAP_REG_NO_OVERLAP 3            /* fewer than min_matched rows matched at the start pose: pose = the start pose's bits */
 #define ICET_VOXEL_MAP_REG_BAD_POSE 4              /* a non-finite entry in the start pose */
 #define ICET_VOXEL_MAP_REG_MAX_ITERS 64
+#define ICET_VOXEL_MAP_REG_NEIGHBOURS_7 2          /* icet_voxel_map_register_params.flags: a row is scored against the best of its own cell and the six across its faces */
+#define ICET_VOXEL_MAP_REG_NEIGHBOURS_27 4         /* the best of the 27 cells around it */
 typedef struct icet_voxel_map_register_params {
     float min_range, max_range;   /* of this call, as icet_voxel_map_params' (max_range <= 0: no limit) */
     double sigma_min;             /* the live point's own noise, metres (0.02) */
@@ -1049,7 +1059,7 @@ typedef struct icet_voxel_map_register_params {
     int32_t min_points;           /* 5 */
     int32_t min_matched;          /* 50 */
     int32_t max_iters;            /* 20; 0 .. 64 */
-    int32_t flags;                /* 0 */
+    int32_t flags;                /* 0: a row is scored against its own cell; or ONE of ICET_VOXEL_MAP_REG_NEIGHBOURS_* */
     int32_t reserved[2];          /* 0 */
 } icet_voxel_map_register_params; /* 72 bytes; NULL: the defaults */
 typedef struct icet_voxel_map_registration {
@@ -1067,8 +1077,8 @@ typedef struct icet_voxel_map_registration {
 typedef struct icet_voxel_map_register_term {
     uint64_t key;                 /* the row's cell (all ones: outside the grid or not scored) */
     int32_t cls;                  /* the map rule's class: 0 scored, 1 non-finite, 2 range, 3 outside the grid */
-    int32_t matched;
-    double s, omega, rho;         /* zero for a row that is not scored; a miss: s 0, omega 0, rho scale */
+    int32_t matched;              /* 0: a miss; else 1 + the place of the cell the row is scored against in the order of its neighbourhood (1: its own cell) */
+    double s, omega, rho;         /* zero for a row that is not scored; a miss: s 0, omega 0, rho scale; under a neighbourhood: the winning cell's */
     double g[6], H[21];
 } icet_voxel_map_register_term;   /* 256 bytes */
 icet_status icet_voxel_map_register_device(icet_voxel_map* map, int32_t n_q, const icet_dev_scan* scans, const float* poses,

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """The registration against a shaped voxel map on one GPU, variants alternating in one process (GPU box):
 
-    python scripts/bench_map_register.py [--scans 64] [--table-log2 22] [--cell 0.5] [--reps 7] [--max-iters 20] [--out FILE.json]
+    python scripts/bench_map_register.py [--scans 64] [--table-log2 22] [--cell 0.5] [--reps 7] [--max-iters 20] [--neighbours 1,7,27] [--out FILE.json]
 
 The workload is bench_map.py's: --scans synthetic 64-channel scans (lidar_sim, scene 2000, about 116 k rows each) along a drive, fused at their poses into a shaped
 map.  Live scans are taken at poses between the fused ones and started 0.15 m and 0.02 rad off.
   (1) register   one icet_voxel_map_register_device call of 1 / 16 / 64 live scans, max_iters as given: ms per call, ms per pass (the call enqueues 1 + max_iters
                  passes whatever the queries do), rows / s over the passes the queries actually ran, and how they ended.
   (2) score      the same scans with max_iters = 0: one row pass and one step -- the row pass's own rate.
+                 --neighbours 1,7,27 runs (1) and (2) under each neighbourhood (the cells a row is scored against the best of), all of them alternating in the
+                 same windows; the keys of a neighbourhood other than 1 end in _n7 / _n27.  (3) and (4) are centre-only.
   (3) gauss      the score of one scan with sigma_min changing from call to call, so that every call rebuilds the Gaussians, then the same call with them current
                  (two runs of windows, one after the other: alternating the two would make every call stale).
   (4) detour     the same localisations the way they were done before: VoxelMap.query + KeyframeStore.put_from_map (a keyframe per start pose) and
@@ -34,8 +36,10 @@ def main():
     ap.add_argument("--rings", type=int, default=64)
     ap.add_argument("--steps", type=int, default=2048)
     ap.add_argument("--runlen", type=int, default=7)
+    ap.add_argument("--neighbours", default="1", help="comma-separated: 1, 7, 27")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    nbs = [int(v) for v in a.neighbours.split(",")]
     import numpy as np
     import torch
     from icet_amd import api, lidar_sim
@@ -95,28 +99,34 @@ def main():
     par = api.map_register_params(max_iters=a.max_iters)
     par0 = api.map_register_params(max_iters=0)
     sizes = (1, 16, 64)
+    result["neighbours"] = nbs
 
-    # (1) and (2): the loop and the score, 1 / 16 / 64 scans, alternating
+    # (1) and (2): the loop and the score, 1 / 16 / 64 scans, under every neighbourhood asked for, alternating
+    pars = {nb: (api.map_register_params(max_iters=a.max_iters, neighbours=nb), api.map_register_params(max_iters=0, neighbours=nb)) for nb in nbs}
+    tag = lambda nb: "" if nb == 1 else "_n%d" % nb
     fns = {}
     for q in sizes:
-        fns["register_%d" % q] = (lambda q=q: m.register_device(ldesc[:q], starts[:q], recs.data_ptr(), par))
-        fns["score_%d" % q] = (lambda q=q: m.register_device(ldesc[:q], starts[:q], recs.data_ptr(), par0))
+        for nb in nbs:
+            fns["register_%d%s" % (q, tag(nb))] = (lambda q=q, nb=nb: m.register_device(ldesc[:q], starts[:q], recs.data_ptr(), pars[nb][0]))
+            fns["score_%d%s" % (q, tag(nb))] = (lambda q=q, nb=nb: m.register_device(ldesc[:q], starts[:q], recs.data_ptr(), pars[nb][1]))
     med, spread = measure(fns)
     for q in sizes:
         rows = int(sum(s.shape[1] for s in live[:q]))
-        m.register_device(ldesc[:q], starts[:q], recs.data_ptr(), par)
-        r = records(q)
-        passes = int((r["iterations"] + 1).sum())
-        ran = float(sum(live[k].shape[1] * (int(r["iterations"][k]) + 1) for k in range(q)))
-        err = [float(np.linalg.norm(r["pose"][k].reshape(4, 4)[:3, 3] - true[k][:3, 3])) for k in range(q)]
-        result["register_%d" % q] = dict(ms=med["register_%d" % q], range_ms=spread["register_%d" % q], ms_per_pass=med["register_%d" % q] / (a.max_iters + 1), rows=rows,
-                                         query_passes=passes, rows_per_s=ran / med["register_%d" % q] * 1e3, status_counts=np.bincount(r["status"], minlength=5).tolist(),
-                                         median_error_m=float(np.median(err)), max_error_m=float(max(err)))
-        result["score_%d" % q] = dict(ms=med["score_%d" % q], range_ms=spread["score_%d" % q], rows=rows, rows_per_s=rows / med["score_%d" % q] * 1e3)
-        print("(1) register %2d scans, %8d rows: %.3f ms [%.3f, %.3f]  %.3f ms / pass  %.2f G rows/s over %d query passes  status %s  error median %.4f m max %.4f m"
-              % (q, rows, med["register_%d" % q], *spread["register_%d" % q], med["register_%d" % q] / (a.max_iters + 1), ran / med["register_%d" % q] * 1e-6, passes,
-                 result["register_%d" % q]["status_counts"], np.median(err), max(err)), flush=True)
-        print("(2) score    %2d scans: %.3f ms [%.3f, %.3f]  %.2f G rows/s" % (q, med["score_%d" % q], *spread["score_%d" % q], rows / med["score_%d" % q] * 1e-6), flush=True)
+        for nb in nbs:
+            kr, ks = "register_%d%s" % (q, tag(nb)), "score_%d%s" % (q, tag(nb))
+            m.register_device(ldesc[:q], starts[:q], recs.data_ptr(), pars[nb][0])
+            r = records(q)
+            passes = int((r["iterations"] + 1).sum())
+            ran = float(sum(live[k].shape[1] * (int(r["iterations"][k]) + 1) for k in range(q)))
+            err = [float(np.linalg.norm(r["pose"][k].reshape(4, 4)[:3, 3] - true[k][:3, 3])) for k in range(q)]
+            result[kr] = dict(ms=med[kr], range_ms=spread[kr], ms_per_pass=med[kr] / (a.max_iters + 1), rows=rows, query_passes=passes, accepted=int(r["accepted"].sum()),
+                              max_query_passes=int(r["iterations"].max()) + 1, rows_per_s=ran / med[kr] * 1e3, status_counts=np.bincount(r["status"], minlength=5).tolist(),
+                              rows_matched=int(r["rows_matched"].sum()), median_error_m=float(np.median(err)), max_error_m=float(max(err)))
+            result[ks] = dict(ms=med[ks], range_ms=spread[ks], rows=rows, rows_per_s=rows / med[ks] * 1e3)
+            print("(1) register %2d scans, %2d cells, %8d rows: %.3f ms [%.3f, %.3f]  %.3f ms / pass  %.2f G rows/s over %d query passes (%d accepted, longest %d)  status %s  "
+                  "error median %.4f m max %.4f m" % (q, nb, rows, med[kr], *spread[kr], med[kr] / (a.max_iters + 1), ran / med[kr] * 1e-6, passes, result[kr]["accepted"],
+                                                      result[kr]["max_query_passes"], result[kr]["status_counts"], np.median(err), max(err)), flush=True)
+            print("(2) score    %2d scans, %2d cells: %.3f ms [%.3f, %.3f]  %.2f G rows/s" % (q, nb, med[ks], *spread[ks], rows / med[ks] * 1e-6), flush=True)
 
     # (3) the Gaussians: every call stale against every call current
     flip = dict(k=0)
